@@ -18,10 +18,17 @@ synthetic (ref, test) pairs.
                       records are gathered with one RCCL all_gather.
 
 Prints ONE JSON line (rank 0): `value` = stereo 2048-sample frame-pairs per
-second over all GPUs; `roofline` prices the dominant kernel (the FFT ear-model
-front end) against HBM with the ALGORITHMIC 16 384 B per stereo frame-pair of
-SURVEY.md 8(d), from HIP events recorded around that kernel's launches on its
-stream; `cpu_baseline` times the reference element itself (oracle/_ref, built
+second over all GPUs, `ms_per_step` = milliseconds per timed step; `roofline`
+prices the dominant kernel (the FFT ear-model front end) against HBM with the
+ALGORITHMIC 16 384 B per stereo frame-pair of SURVEY.md 8(d), from HIP events
+recorded around that kernel's launches on its stream in the timed steps.
+A plain run sets up, warms up, times --steps steps and prints that line, nothing
+else.  `--dump-outputs DIR` writes the result records of the last timed step
+(what gstpeaq_amd.batch_run hands its caller) to DIR/results.npy.
+
+`--full` adds what takes runs or processes of its own: `device_clock` gets the
+calibration kernel before and after the timed region and what the board reported;
+`cpu_baseline` times the reference element itself (oracle/_ref, built
 from the reference's sources; the C oracle if that binary is absent) on one core
 and on all host cores; `odg_max_abs_delta` etc. compare the GPU results with the
 reference's on the pairs the single-core leg ran (the second half of
@@ -32,6 +39,7 @@ reduced-precision FIR as the labelled sub-object `reduced_precision_f16x3`;
 `scaling_reference` is this GPU in the regime every rank of an N > 1 run is in.
 """
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -51,6 +59,22 @@ FP32_MATRIX_PEAK_TFLOPS = 157.3        # v_mfma_f32_16x16x4_f32 (MI355X_MICROARC
 FP16_MATRIX_PEAK_TFLOPS = 2516.0       # v_mfma_f32_16x16x32_f16, dense (MI355X_MICROARCH.md: 2.5 PFLOP/s)
 CONFIG4_PAIRS_PER_GPU = 32768         # BASELINE.json configs[3]: 262 144 pairs over 8 GPUs
 WAVE_PAIRS = 4096
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the result records of the last timed step -- what gstpeaq_amd.batch_run hands its caller,
+    [pairs, 16] float64 in pair order (MOVs, DI, ODG, TotalSNR, frames, filter-bank blocks) -- as out_dir/results.npy.
+    Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the rows, their indices in out_dir/results_rows.npy."""
+    import numpy as np
+    rows = records.cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (DUMP_LIMIT_BYTES - 4096) // (rows.shape[1] * 8 + 8)
+    if rows.shape[0] > cap:
+        keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], cap, replace=False))
+        np.save(os.path.join(out_dir, "results_rows.npy"), keep.astype(np.float64))
+        rows = rows[keep]
+    np.save(os.path.join(out_dir, "results.npy"), rows)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -405,6 +429,12 @@ def main():
                     help="pairs whose results are compared with the reference's (both versions; all host cores)")
     ap.add_argument("--no-scaling-reference", action="store_true",
                     help="skip the waves-mode pass that makes an N = 1 line comparable with N > 1 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also the device calibration and board readings, the `advanced` sub-object, "
+                         "the scaling reference, the CPU baselines and the comparison with the reference's results "
+                         "(the --no-* switches above leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result records of the last timed step to DIR/results.npy")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` by itself (no launcher, N > 1): become the launcher -- one process per GPU under
@@ -487,13 +517,15 @@ def main():
             for _ in range(warmup):
                 gstpeaq_amd.batch_run(ctx, advanced, ref, test, results=results, sync=False)
             barrier()
-            with DeviceSampler(local_rank) as smp:
+            smp = DeviceSampler(local_rank) if args.full else None
+            with smp or contextlib.nullcontext():
                 t0 = time.perf_counter()
                 for _ in range(steps):
                     gstpeaq_amd.batch_run(ctx, advanced, ref, test, results=results, sync=False)
                 barrier()
                 el = time.perf_counter() - t0
-            sampled[bool(advanced)] = smp.summary()
+            if smp:
+                sampled[bool(advanced)] = smp.summary()
             return el, el, ctx.last_timing()
         # waves: the resident buffers hold wave 0 on entry; a warm-up step runs that wave only
         for _ in range(warmup):
@@ -650,10 +682,12 @@ def main():
 
     main_adv = bool(args.advanced)
     # the device's clock under a fixed FP64 load before and after the timed region, and (below) while the step itself ran
-    cal0 = ctx.calibrate() if rank == 0 else None
+    cal0 = ctx.calibrate() if rank == 0 and args.full else None
     m = measure(main_adv, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["gathered"])
     step_clock_mhz = ctx.last_clock_mhz()
-    cal1 = ctx.calibrate() if rank == 0 else None
+    cal1 = ctx.calibrate() if rank == 0 and args.full else None
     odg = m["gathered"][:, 12]
     line = None
     if rank == 0:
@@ -693,16 +727,18 @@ def main():
         }
         line["per_gpu_value"] = value / world
         nominal = (cal0 or {}).get("max_clock_mhz") or 2400.0
-        line["device_clock"] = {
-            "step_shader_clock_mhz": step_clock_mhz,
-            "calibration_before": cal0, "calibration_after": cal1, "nominal_mhz": nominal,
-            "power": device_power_info(local_rank), "board_during_steps": sampled.get(main_adv),
-            "how": "step clock: workgroup 0 of every back-end launch of the last timed pass reads the shader-clock and the "
-                   "constant-rate counter around its lifetime, beside the front end of the next chunk (peaq_batch_last_clock); "
-                   "calibration: peaq_calibrate, a fixed v_fma_f64 kernel (one wave per SIMD, sixteen chains, ~70 ms, alone on the device) "
-                   "before and after the timed region -- its second half is the steady state (shader_clock_mhz, fp64_tflops, "
-                   "cycles_per_fma: 4 = the FP64 pipe), its first half the ramp from the idle clock "
-                   "(ramp_*); rank 0's device"}
+        how = ("step clock: workgroup 0 of every back-end launch of the last timed pass reads the shader-clock and the "
+               "constant-rate counter around its lifetime, beside the front end of the next chunk (peaq_batch_last_clock); ")
+        line["device_clock"] = {"step_shader_clock_mhz": step_clock_mhz, "nominal_mhz": nominal,
+                                "how": how + "nominal: 2400 MHz unless --full calibrates; rank 0's device"}
+        if args.full:
+            line["device_clock"].update(
+                calibration_before=cal0, calibration_after=cal1,
+                power=device_power_info(local_rank), board_during_steps=sampled.get(main_adv),
+                how=how + "calibration: peaq_calibrate, a fixed v_fma_f64 kernel (one wave per SIMD, sixteen chains, ~70 ms, "
+                          "alone on the device) before and after the timed region -- its second half is the steady state "
+                          "(shader_clock_mhz, fp64_tflops, cycles_per_fma: 4 = the FP64 pipe), its first half the ramp from "
+                          "the idle clock (ramp_*), its max_clock_mhz the nominal clock; rank 0's device")
         # the same line at the device's nominal clock: the path is issue-bound, its time scales with 1 / clock
         line["value_at_nominal_clock"] = value * nominal / step_clock_mhz if step_clock_mhz else None
         line["result_gather_ms"] = m["gather_ms"]           # after the timed region; 128 B per pair
@@ -719,7 +755,7 @@ def main():
     # roofline and its deviation from the default on these pairs.
     adv = None
     rows_adv = None
-    if not main_adv and not args.no_advanced:
+    if args.full and not main_adv and not args.no_advanced:
         adv_steps = max(1, min(args.steps, 3))
         default_mode = ctx.fir_mode()
         wl = line["config"]["workload"].replace("Basic PEAQ", "Advanced PEAQ").replace("configs[1]", "configs[2]") if rank == 0 else ""
@@ -771,8 +807,8 @@ def main():
     # ---- the scaling regime on this GPU (N = 1 only): what every rank of an N > 1 run does -- 32 768 pairs
     # consumed in synchronised waves of 4096 -- so that an efficiency computed from the driver's N = 1, 2, 4, 8
     # lines can compare like with like (`scaling_reference.value`, not `value`, is the per-GPU rate of that regime)
-    if world == 1 and not waves_mode and not main_adv and not args.no_scaling_reference and args.pairs is None \
-            and rank == 0:
+    if args.full and world == 1 and not waves_mode and not main_adv and not args.no_scaling_reference \
+            and args.pairs is None and rank == 0:
         try:
             wr = torch.empty((CONFIG4_PAIRS_PER_GPU, 16), dtype=torch.float64, device=dev)
             barrier()
@@ -794,7 +830,7 @@ def main():
     # The comparison with the reference's results (`odg_max_abs_delta` ...) runs on the FIRST `--delta-pairs` pairs of
     # the job (256: SURVEY.md 8(d)) in both versions, through one reference process per usable host core; the one-core
     # leg only times.
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             base, cpu = cpu_single(n_samples, args.channels, seed_base + lo, main_adv, 8.0)
             line["cpu_baseline"] = base

@@ -33,12 +33,14 @@ def test_two_ranks_on_one_gpu_equal_one_process(tmp_path):
                 HSA_ENABLE_IPC_MODE_LEGACY="0")
     line2 = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                  "--master-addr", "127.0.0.1", "--master-port", "29531", str(ROOT / "bench.py"), "--gpus", "2",
-                 "--pairs", "96"] + COMMON, env2)
+                 "--pairs", "96", "--full"] + COMMON, env2)
     env1 = dict(os.environ, PEAQ_BENCH_DUMP_RESULTS=str(one))
     line1 = run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--waves", "--pairs", "192",
-                 "--no-cpu-baseline", "--no-scaling-reference"] + COMMON, env1)
+                 "--no-cpu-baseline", "--no-scaling-reference", "--dump-outputs", str(tmp_path / "out1")] + COMMON, env1)
     a, b = np.load(two), np.load(one)
     assert a.shape == b.shape == (192, 16)
+    # --dump-outputs writes the same records: the last timed step's, in pair order
+    assert np.array_equal(np.load(tmp_path / "out1" / "results.npy").view(np.uint64), b.view(np.uint64))
     assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), "gathered records differ from the one-process run"
     # pair i carries seed 1 + i: its ODG differs from pair to pair, so equal arrays also mean equal ORDER; and the
     # second rank's block really came from the other process

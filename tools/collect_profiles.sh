@@ -9,7 +9,7 @@ python $R/tools/rocprof_summary.py pmc /tmp/p_fetch/r_results.db /tmp/p_write/r_
 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/p_adv -o r -- python $R/bench.py --advanced --reduced-precision --steps 1 --warmup 1 --no-cpu-baseline > $O/prof_adv.log 2>&1
 python $R/tools/rocprof_summary.py stats /tmp/p_adv/r_results.db > $O/stats_adv.json
 cd $R
-python bench.py > $O/bench_basic.json 2> $O/bench_basic.err
-python bench.py --advanced --steps 2 > $O/bench_adv.json 2> /dev/null
-python bench.py --advanced --reduced-precision --steps 2 > $O/bench_adv_default.json 2> /dev/null
+python bench.py --full > $O/bench_basic.json 2> $O/bench_basic.err
+python bench.py --full --advanced --steps 2 > $O/bench_adv.json 2> /dev/null
+python bench.py --full --advanced --reduced-precision --steps 2 > $O/bench_adv_default.json 2> /dev/null
 ls -la $O

@@ -25,7 +25,7 @@ if [ -f gstpeaq_amd/libpeaq_amd_serial.so ]; then
   python $R/tools/rocprof_summary.py stats /tmp/p_ser/r_results.db > $O/r04_stats_adv_serial.json
   cd $R
 fi
-python bench.py > $O/bench_basic.json 2> $O/bench_basic.err
-python bench.py --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
-python bench.py --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
+python bench.py --full > $O/bench_basic.json 2> $O/bench_basic.err
+python bench.py --full --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
+python bench.py --full --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
 ls -la $O | tail -30

@@ -30,7 +30,7 @@ if [ -f gstpeaq_amd/libpeaq_amd_prof.so ]; then
   PEAQ_AMD_LIB=$R/gstpeaq_amd/libpeaq_amd_prof.so python tools/fe_profile.py 1024 > $O/r05_frontend_phases.json 2>/dev/null
 fi
 python tools/make_pmc_frontend.py > /dev/null 2> $O/make_pmc.err; cp profiles/pmc_frontend.json $O/pmc_frontend.json
-python bench.py > $O/bench_basic.json 2> $O/bench_basic.err
-python bench.py --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
-python bench.py --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
+python bench.py --full > $O/bench_basic.json 2> $O/bench_basic.err
+python bench.py --full --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
+python bench.py --full --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
 ls -la $O | tail -30

@@ -35,7 +35,7 @@ cd /tmp
 timeout 200 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_WAVES SQ_WAVE_CYCLES -d /tmp/p_ic -o r -- python $R/bench.py --pairs 1024 --steps 1 --warmup 0 --no-cpu-baseline --no-advanced --no-scaling-reference > $O/prof_ic.log 2>&1
 python $R/tools/rocprof_summary.py pmc /tmp/p_ic/r_results.db > $O/r06_pmc_icache.json
 cd $R
-python bench.py > $O/bench_basic.json 2> $O/bench_basic.err
-python bench.py --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
-python bench.py --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
+python bench.py --full > $O/bench_basic.json 2> $O/bench_basic.err
+python bench.py --full --advanced --steps 3 > $O/bench_adv.json 2> /dev/null
+python bench.py --full --advanced --reduced-precision --steps 3 > $O/bench_adv_f16x3.json 2> /dev/null
 ls -la $O | tail -30

@@ -15,6 +15,8 @@ not exist on the GPU box, the committed fixtures travel instead.
   tests/golden/ref_e2e_resampled.json pairs at 44.1 / 32 / 96 kHz through the chain of the reference's CLI,
                                       rawaudioparse ! audioconvert ! audioresample ! peaq (peaq.c:154-209), and the
                                       measured prototype filter of that audioresample  (python tools/make_golden.py resampled)
+  tests/golden/ref_bench_parity.npz   the reference element on the first 256 pairs of bench.py's workload, both
+                                      versions                                 (python tools/make_golden.py bench_parity)
 """
 import json
 import os
@@ -251,7 +253,25 @@ def tables():
     (GOLD / "ref_tables.json").write_text(json.dumps(out))
 
 
+def bench_parity():
+    """MOVs / DI / ODG of the reference element on the first 256 pairs of bench.py's workload (10 s stereo,
+    seeds 1 .. 256), both versions: the parity subset of tests/test_gpu_fullsize.py"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    out = {}
+    for advanced, name in ((0, "basic"), (1, "advanced")):
+        d = bench.cpu_records(480000, 2, 1, bool(advanced), 256)
+        assert d["kind"] == "reference", d["kind"]
+        out[f"{name}_odg"] = np.asarray(d["odg"], dtype=np.float64)
+        out[f"{name}_di"] = np.asarray(d["di"], dtype=np.float64)
+        out[f"{name}_movs"] = np.asarray(d["movs"], dtype=np.float64).reshape(256, 11)
+    np.savez_compressed(GOLD / "ref_bench_parity.npz", **out)
+
+
 def main():
+    if sys.argv[1:] == ["bench_parity"]:             # only the parity subset of bench.py's workload
+        bench_parity()
+        return
     if sys.argv[1:] == ["settings"]:                 # only the settings.h variants
         GOLD.mkdir(parents=True, exist_ok=True)
         e2e_settings()
