@@ -117,6 +117,13 @@ def load_library():
     L.peaq_run_pair.argtypes = [vp, C.c_int, C.c_int, C.c_double, fp, C.c_size_t, fp, C.c_size_t, dp]
     L.peaq_batch_workspace_bytes.restype = C.c_size_t
     L.peaq_batch_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32]
+    if hasattr(L, "peaq_batch_run_trajectory"):      # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_batch_run_trajectory.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t,
+                                                u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp]
+        L.peaq_batch_trajectory_workspace_bytes.restype = C.c_size_t
+        L.peaq_batch_trajectory_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.peaq_run_pair_trajectory.argtypes = [vp, C.c_int, C.c_int, C.c_double, fp, C.c_size_t, fp, C.c_size_t,
+                                               C.c_uint32, C.c_int, dp, dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -387,6 +394,55 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     torch.cuda.synchronize(ref.device)
     rows = results.cpu().numpy()
     return [_result_dict(r, advanced) for r in rows]
+
+
+def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n_test=None, playback_level=92.0,
+                     stream=None, sync=True):
+    """Readings every `interval` samples per channel through each pair (peaq_batch_run_trajectory): point k of pair p
+    is what a session pushed the first min((k + 1) interval, n) samples of each signal reads, unflushed.
+    ref/test as for batch_run.  Returns (points, results): lists of result dicts, points[p][k], (sync=True) or the
+    device tensors [n_pairs, n_points, 16] and [n_pairs, 16]."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    n_points = int(n_points)
+    points = torch.empty((n_pairs, max(n_points, 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_run_trajectory(ctx.h, int(bool(advanced)), channels, float(playback_level), n_pairs,
+                                           C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                           a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                           a_test.ctypes.data_as(u32p) if a_test is not None else None,
+                                           stride, int(interval), n_points, C.c_void_p(points.data_ptr()),
+                                           C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    if not sync:
+        return points, results
+    torch.cuda.synchronize(ref.device)
+    pts = points.cpu().numpy()
+    return ([[_result_dict(r, advanced) for r in row] for row in pts],
+            [_result_dict(r, advanced) for r in results.cpu().numpy()])
+
+
+def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_level=92.0):
+    """peaq_run_pair_trajectory: one whole pair from host memory (numpy float32 [n, channels]);
+    returns (points, result) as result dicts"""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    ch = ref.shape[1]
+    assert test.shape[1] == ch
+    pts = np.zeros((max(int(n_points), 1), RESULT_DOUBLES))
+    out = np.zeros(RESULT_DOUBLES)
+    dp = C.POINTER(C.c_double)
+    _check(ctx.L.peaq_run_pair_trajectory(ctx.h, int(bool(advanced)), ch, float(playback_level),
+                                          ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                          test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                          int(interval), int(n_points), pts.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return [_result_dict(r, bool(advanced)) for r in pts], _result_dict(out, bool(advanced))
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0):

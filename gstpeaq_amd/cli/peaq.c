@@ -21,6 +21,9 @@
  * in FP64 like the reference (the engine's default); PEAQ_AMD_FIR=f16x3 selects
  * the reduced-precision bank (held to 1e-6 in ODG/DI, include/peaq_amd.h).
  * --no-resample refuses files at other rates instead.
+ * --interval=SECONDS also prints, before those two lines, one line per reading taken every SECONDS of the (resampled)
+ * signals, "Time %.3f s: ODG %.3f, DI %.3f" -- what the element's odg / di properties read at that point of the stream
+ * (gstpeaq.c:484-497; peaq_run_pair_trajectory).
  */
 #include <math.h>
 #include <stdint.h>
@@ -254,14 +257,15 @@ usage (const char *prog)
       "  --advanced    use advanced version\n"
       "  --basic       use basic version (default)\n"
       "  --level=DB    playback level in dB SPL of a full-scale sine (default 92)\n"
-      "  --no-resample refuse files that are not sampled at 48 kHz instead of converting them\n", prog);
+      "  --no-resample refuse files that are not sampled at 48 kHz instead of converting them\n"
+      "  --interval=S  also print ODG and DI read every S seconds through the files\n", prog);
 }
 
 int
 main (int argc, char **argv)
 {
   int advanced = 0, i, nfiles = 0, rc, allow_resample = 1;
-  double level = 92.;
+  double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -278,6 +282,14 @@ main (int argc, char **argv)
       level = atof (argv[i] + 8);
     else if (!strcmp (argv[i], "--no-resample"))
       allow_resample = 0;
+    else if (!strncmp (argv[i], "--interval=", 11)) {
+      char *end;
+      interval_s = strtod (argv[i] + 11, &end);
+      if (*end || !(interval_s * 48000. >= 0.5 && interval_s * 48000. < 4294967295.)) {
+        fprintf (stderr, "Failed to initialize: invalid interval %s\n", argv[i] + 11);
+        return 1;
+      }
+    }
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -343,7 +355,29 @@ main (int argc, char **argv)
   }
   /* The advanced version's filter bank runs in the engine's default arithmetic, the reference's own (all FP64);
    * the faster reduced-precision bank only on request (PEAQ_AMD_FIR=f16x3, read by peaq_ctx_create). */
-  if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
+  if (interval_s > 0.) {
+    /* readings every `interval` samples at 48 kHz (after the rate conversion) up to the end of the longer file; the
+     * end result is the one of peaq_run_pair */
+    const size_t n_max = ref.frames > test.frames ? ref.frames : test.frames;
+    const uint32_t interval = (uint32_t) llround (interval_s * 48000.);
+    const size_t n_points = n_max ? (n_max + interval - 1) / interval : 1;
+    peaq_result *pts;
+    size_t k;
+    if (n_points > 0x7fffffff || !(pts = malloc (n_points * sizeof *pts))) {
+      printf ("Error: too many readings\n");
+      return 2;
+    }
+    if (peaq_run_pair_trajectory (ctx, advanced, ref.channels, level, ref.samples, ref.frames, test.samples,
+            test.frames, interval, (int) n_points, pts, &r) != PEAQ_OK) {
+      printf ("Error: %s\n", peaq_last_error ());
+      return 2;
+    }
+    for (k = 0; k < n_points; k++) {
+      const size_t end = (k + 1) * (size_t) interval < n_max ? (k + 1) * (size_t) interval : n_max;
+      printf ("Time %.3f s: ODG %.3f, DI %.3f\n", end / 48000., pts[k].odg, pts[k].di);
+    }
+    free (pts);
+  } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
     if (peaq_run_pair (ctx, advanced, ref.channels, level, ref.samples, ref.frames, test.samples, test.frames, &r) !=

@@ -397,6 +397,57 @@ __device__ __forceinline__ void mod_difference(const BandLane<NB, SLOTS>& bl, co
 }
 
 // ---------------------------------------------------------------------------
+// Reading points of a trajectory (PointArgs, peaq_batch_run_trajectory): point k of a pair falls on the frame (FB:
+// block) after which the pair has processed F(a_k) frames (B(a_k) blocks), a_k = min((k + 1) interval, n_ref, n_test),
+// F(a) = a >= 2048 ? (a - 2048) / 1024 + 1 : 0 (do_processing, gstpeaq.c:596-611), B(a) = a / 192.  Every quantity is
+// wave-uniform: the first pending point is found once per workgroup, then one comparison per frame (block) tells
+// whether the next one is due.  The walk's state is in LDS, one copy per wave that all its lanes write alike, and is
+// read back as scalars where it is used: kept in registers across the frame loop it cost the basic back end registers
+// it does not have.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+template <bool FB>
+struct PointWalk {
+  PointSnap* row;                   // this pair's snapshots
+  uint32_t n_min, interval;
+  int n_points, k;                  // k: the next point to take
+  uint32_t due;                     // F(a_k) / B(a_k): the count after which point k is taken (UINT_MAX: none left)
+  __device__ __forceinline__ static uint32_t count(uint32_t a) {
+    return FB ? a / kFbFrame : a >= (uint32_t)kFrame ? (a - kFrame) / kHop + 1 : 0u;
+  }
+  __device__ __forceinline__ void set_due(int k1) {
+    k = k1;
+    if (k1 >= n_points) {
+      due = UINT_MAX;
+      return;
+    }
+    const uint64_t t = (uint64_t)(k1 + 1) * interval;
+    due = count(t < n_min ? (uint32_t)t : n_min);
+  }
+  // c0: frames (blocks) the pair has processed before this launch -- the first pending point has a count above it
+  __device__ __forceinline__ void init(const PointArgs& p, unsigned pair, uint32_t c0) {
+    row = p.snap + (size_t)pair * p.n_points;
+    const uint32_t nr = p.n_ref ? p.n_ref[pair] : p.n_uniform, nt = p.n_test ? p.n_test[pair] : p.n_uniform;
+    n_min = nr < nt ? nr : nt;
+    interval = p.interval;
+    n_points = p.n_points;
+    const uint64_t thr = FB ? (uint64_t)kFbFrame * (c0 + 1ull) : (uint64_t)kFrame + (uint64_t)kHop * c0;   // a_k >= thr
+    const uint64_t k0 = n_min < thr ? (uint64_t)n_points : (thr + interval - 1) / interval - 1;
+    set_due(k0 < (uint64_t)n_points ? (int)k0 : n_points);
+  }
+  // the snapshot to write after count c, or nullptr; advances to the next point
+  __device__ __forceinline__ PointSnap* take(uint32_t c) {
+    if (wave_uniform(due) != c) return nullptr;
+    const int k1 = (int)wave_uniform((uint32_t)k);
+    const uint64_t r = reinterpret_cast<uint64_t>(row);
+    PointSnap* sp = reinterpret_cast<PointSnap*>(((uint64_t)wave_uniform((uint32_t)(r >> 32)) << 32) |
+                                                 wave_uniform((uint32_t)r)) + k1;
+    set_due(k1 + 1);
+    return sp;
+  }
+};
+
+// ---------------------------------------------------------------------------
 // FFT-model back end.  ADV = false: basic version (109 bands, 11 MOVs).
 // ADV = true: the FFT part of the advanced version (55 bands; SegmentalNMR, EHS).
 // ---------------------------------------------------------------------------
@@ -417,370 +468,31 @@ struct BackendShared {
 // holds 3 x 168 VGPRs per SIMD); with the default budget (256) it could never be co-scheduled
 // DBG = true (basic version only, peaq_debug_backend): the per-frame patterns are also written to
 // a.debug for the stage-level parity tests; the arithmetic is the same instantiation otherwise.
+// PTS = true (backend_points_kernel, trajectory launches only): after each frame the reading points that fall on it
+// get a snapshot (PointWalk); the arithmetic is the same as the plain instantiation's.
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  __shared__ BackendShared sh;
-  __shared__ double sh_tab[T_COUNT * kBandStride];
-  __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
-  constexpr int SLOTS = 2;
-  const int lane = threadIdx.x & 63;
-  const int chan = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: keep it scalar
-  const int channels = a.channels;                  // == blockDim.x / 64
-  const unsigned pair = blockIdx.x;
-  const BandLane<NB, SLOTS> bl{lane};
-  {
-    const BandTables* __restrict__ g = a.bands;
-    const double* const src[T_COUNT] = {g->adapt_tc, g->ear_tc, g->threshold, g->loud_factor, g->exc_threshold,
-                                        g->internal_noise, g->noise_pow03, g->mask_diff, g->inv_spread_norm,
-                                        g->inv_spread_norm_pow03, g->ln_internal_noise, g->inv_window_count};
-#pragma unroll
-    for (int t = 0; t < T_COUNT; ++t)
-      for (int i = threadIdx.x; i < kBandStride; i += blockDim.x) sh_tab[t * kBandStride + i] = src[t][i];
-    for (int i = threadIdx.x; i < 2 * kLogTabEntries; i += blockDim.x) sh_ltab[i] = a.common->log_tab[i >> 1][i & 1];
-  }
-  LdsTabs bt{sh_tab, 0, a.bands->deriv_factor, sh_ltab};
-  PairState* __restrict__ ps = a.state + (a.pair_slot ? a.pair_slot[pair] : pair);
-  ChannelState* __restrict__ cs = &ps->ch[chan];
-
-  unsigned f_begin, f_end;
-  if (a.pair_frame0) {                               // broker launch: this pair's own window
-    f_begin = a.pair_frame0[pair];
-    f_end = f_begin + a.pair_nframes[pair];
-  } else {
-    const unsigned n_frames = a.n_frames ? a.n_frames[pair] : a.n_frames_uniform;
-    f_begin = a.frame0;
-    f_end = a.frame0 + a.frames_per_launch;
-    if (f_end > n_frames) f_end = n_frames;
-  }
-  if (f_begin >= f_end) return;
-  const bool clk_wave = a.clk && blockIdx.x == 0 && chan == 0;   // wave-uniform
-  unsigned long long clk_s0 = 0, clk_w0 = 0;
-  if (clk_wave) {
-    clk_w0 = wall_clock64();
-    clk_s0 = __builtin_readcyclecounter();
-  }
-  if (lane < kPaPad) sh.pa[chan][0][lane] = sh.pa[chan][1][lane] = 0.;
-  __syncthreads();                                   // the table copy is complete
-
-  // ---- recurrent state -> registers -----------------------------------------------
-  double sm[2][SLOTS];                               // smeared excitation filters (ref, test)
-  double la[6][SLOTS];
-  double mdr[3][SLOTS], mdt[3][SLOTS];
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int b = bl.band(s);
-    sm[0][s] = cs->vec[kSmearRef][b < kBandStride ? b : 0];
-    sm[1][s] = cs->vec[kSmearTest][b < kBandStride ? b : 0];
-#pragma unroll
-    for (int v = 0; v < 6; ++v) la[v][s] = cs->vec[kLaFiltRef + v][b < kBandStride ? b : 0];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      mdr[v][s] = cs->vec[kModPrevRef + v][b < kBandStride ? b : 0];
-      mdt[v][s] = cs->vec[kModPrevTest + v][b < kBandStride ? b : 0];
-    }
-  }
-  LaneAcc acc;
-  {
-    const int i = lane < kMaxAcc ? lane : 0;
-    acc.load(&sh.acc[chan][0][lane < kAccLdsStride ? lane : kAccLdsStride - 1], cs->acc[i], acc_mode(ADV, i),
-             ps->status[i]);   // lanes beyond the 11 accumulators work on dummy slots
-  }
-  unsigned loud_reached = ps->loudness_reached;
-  if (chan == 0 && lane == 0) {
-    sh.energy[0] = ps->sig_energy;
-    sh.energy[1] = ps->noise_energy;
-  }
-
-  for (unsigned frame = f_begin; frame < f_end; ++frame) {
-    asm volatile("" : "+v"(bt.off));                 // the tables are re-read from LDS where they are used
-    const double* __restrict__ rec0 =
-        a.records + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels) * kRecDoubles;
-    const double* __restrict__ rec = rec0 + (size_t)chan * kRecDoubles;
-
-    // ---- frame flags over all channels (gstpeaq.c:858-862, movs.c:1374-1381) -----
-    int fl_ref = (int)rec0[kRecFlagsRef], fl_test = (int)rec0[kRecFlagsTest];
-    if (channels == 2) {
-      fl_ref |= (int)rec0[kRecDoubles + kRecFlagsRef];
-      fl_test |= (int)rec0[kRecDoubles + kRecFlagsTest];
-    }
-    const bool above = fl_ref & 1;
-    const bool ehs_valid = ((fl_ref | fl_test) & 2) != 0;
-    if (!ADV || lane == MA_SEGNMR || lane == MA_EHS) acc.set_tentative(!above);
-
-    // ---- this frame's patterns -------------------------------------------------------
-    double ur[SLOTS], ut[SLOTS], lr[SLOTS], lt[SLOTS], nz[SLOTS];
-    {
-      const int b0 = bl.band(0);
-      const int bb = b0 < kBandStride ? b0 : 0;
-      const double2 v0 = *reinterpret_cast<const double2*>(rec + kRecRootRef + bb);
-      const double2 v1 = *reinterpret_cast<const double2*>(rec + kRecRootTest + bb);
-      const double2 v4 = *reinterpret_cast<const double2*>(rec + kRecNoise + bb);
-      // unsmeared excitation (fftearmodel.c:593-597) and its 0.3rd power (modpatt.c:235) from the roots
-      const double n0 = bt.at(T_ISN, bb), n1 = bt.at(T_ISN, bb + 1);
-      const double m0 = bt.at(T_ISN03, bb), m1 = bt.at(T_ISN03, bb + 1);
-      excitation_from_root(v0.x, n0, m0, ur[0], lr[0]);
-      excitation_from_root(v0.y, n1, m1, ur[1], lr[1]);
-      excitation_from_root(v1.x, n0, m0, ut[0], lt[0]);
-      excitation_from_root(v1.y, n1, m1, ut[1], lt[1]);
-      nz[0] = v4.x; nz[1] = v4.y;
-    }
-    double nl_part = 0.;                               // basic version: the lane's part of the noise loudness, summed with the NMR's
-    bool nl_open = false;
-    // time smearing, fftearmodel.c:496-504
-    double er[SLOTS], et[SLOTS];
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      const int b = bl.band(s) < kBandStride ? bl.band(s) : 0;
-      const double ac = bt.ear_tc(b);
-      sm[0][s] = ac * sm[0][s] + (1. - ac) * ur[s];
-      er[s] = sm[0][s] > ur[s] ? sm[0][s] : ur[s];
-      if (!ADV) {
-        sm[1][s] = ac * sm[1][s] + (1. - ac) * ut[s];
-        et[s] = sm[1][s] > ut[s] ? sm[1][s] : ut[s];
-      } else {
-        et[s] = 0.;
-      }
-    }
-
-    // lane i owns accumulator i: every MOV value of the frame is routed to its owner as soon as
-    // it exists (two selects) instead of being kept in a per-lane table
-    double my_v = 0., my_w = 1.;
-    bool my_hit = false;
-    auto route = [&](int idx, double v, double w) {
-      if (lane == idx) {
-        my_v = v;
-        my_w = w;
-        my_hit = true;
-      }
-    };
-
-    if (!ADV) {
-      // ---- pattern processing (gstpeaq.c:834-845) ------------------------------------
-      double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
-      level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
-      modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
-      modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
-      if (DBG) {
-        double* __restrict__ d =
-            a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles;
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-          if (bl.valid(s)) {
-            const int b = bl.band(s);
-            d[kDbgExcRef + b] = er[s];
-            d[kDbgExcTest + b] = et[s];
-            d[kDbgAdaptRef + b] = ad_ref[s];
-            d[kDbgAdaptTest + b] = ad_test[s];
-            d[kDbgModRef + b] = mr[s];
-            d[kDbgModTest + b] = mt[s];
-            d[kDbgAvgLoudRef + b] = mdr[1][s];
-            d[kDbgAvgLoudTest + b] = mdt[1][s];
-          }
-        }
-      }
-      if (loud_reached == UINT_MAX) {                // wave-uniform
-        double n_ref, n_test;
-        wave_sum2(total_loudness_part<NB, SLOTS>(bl, bt, er), total_loudness_part<NB, SLOTS>(bl, bt, et), n_ref, n_test);
-        n_ref *= 24. / NB;
-        n_test *= 24. / NB;
-        if (lane == 0) sh.gate[chan] = (n_ref > 0.1 && n_test > 0.1);
-        if (DBG && lane == 0) {
-          double* __restrict__ d =
-              a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles;
-          d[kDbgLoudnessRef] = n_ref;
-          d[kDbgLoudnessTest] = n_test;
-        }
-      }
-      // ---- detection probability, per channel part (movs.c:1239-1262) -----------------
-#pragma unroll
-      for (int s = 0; s < SLOTS; ++s) {
-        double pc = 0., qc = 0.;
-        if (bl.valid(s)) {
-          const double er_db = (10. * kInvLn10) * bt.log(er[s]);      // 10 log10: excitations are > 0
-          const double et_db = (10. * kInvLn10) * bt.log(et[s]);
-          const double l = 0.3 * fmax(er_db, et_db) + 0.7 * et_db;
-          const double l2 = l * l;
-          // (6.39468 / l)^1.71332 = exp(1.71332 (ln 6.39468 - ln l)); one reciprocal of s for both quotients
-          const double sd = l > 0. ? 5.95072 * bt.exp(1.71332 * (1.8554663946857675 - bt.log(l))) + 9.01033e-11 * l2 * l2 +
-                                         5.05622e-6 * l2 * l - 0.00102438 * l * l + 0.0550197 * l - 0.198719
-                                   : 1e30;
-          const double inv_sd = div_fast(1., sd);
-          const double e = er_db - et_db;
-          const double x = e * inv_sd, x2 = x * x;
-          const double xb = er_db > et_db ? x2 * x2 : x2 * x2 * x2;   // (e/s)^b, b = 4 or 6
-          // The channel's detection probability is pc = 1 - 0.5^xb (movs.c:1253); what the frame needs of it is
-          // prod_b (1 - max_c pc) = 0.5^(sum_b max_c xb) (pc grows with xb, so the maxima agree): the EXPONENTS are
-          // exchanged and summed, and the one exponential of the frame is taken after the reduction -- an exponential
-          // per band, channel and frame less, and the product's own reduction rides in the free slot of the sums'.
-          pc = xb;
-          qc = fabs(a.cfg.floor_steps ? floor(e) : trunc(e)) * inv_sd;        // movs.c:1256-1260
-        }
-        sh.pc[chan][bl.band(s)] = pc;
-        sh.qc[chan][bl.band(s)] = qc;
-      }
-      __syncthreads();
-      if (loud_reached == UINT_MAX) {
-        const int g = sh.gate[0] | (channels == 2 ? sh.gate[1] : 0);
-        if (g) loud_reached = frame;
-      }
-      double* __restrict__ dmov =                    // debug instantiation: this (frame, channel)'s MOV values
-          DBG ? a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov
-              : nullptr;
-      // ---- modulation difference (gstpeaq.c:871-877) --------------------------------
-      if (DBG || frame >= 24) {
-        double d1, d2, wt;
-        mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
-        d1 *= 100. / NB;
-        d2 *= 100. / NB;
-        if (frame >= 24) {
-          route(MB_AVGMOD1, d1, wt);
-          route(MB_AVGMOD2, d2, wt);
-          route(MB_WINMOD, d1, 1.);
-        }
-        if (DBG && lane == 0) {
-          dmov[0] = d1;
-          dmov[1] = d2;
-          dmov[2] = wt;
-        }
-      }
-      // ---- noise loudness (gstpeaq.c:880-886; unsigned compare with UINT_MAX sentinel)
-      // (its sum over the bands goes through the reduction of the noise-to-mask ratio below)
-      nl_open = DBG || (frame >= 24 && frame - 3 >= loud_reached);
-      if (nl_open) nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
-      // ---- bandwidth (movs.c:797-807) ------------------------------------------------------
-      {
-        const double bw_ref = rec[kRecBwRef];
-        if (bw_ref > 346.) {
-          route(MB_BW_REF, bw_ref, 1.);
-          route(MB_BW_TEST, rec[kRecBwTest], 1.);
-        }
-      }
-    }
-    // ---- noise-to-mask ratio (movs.c:1002-1022), detection probability's binaural part (movs.c:1263-1275): the
-    // lanes' parts first, then ONE reduction for the three sums of this place (with the noise loudness's from above) ----
-    {
-      double nsum = 0., nmax = 0.;
-#pragma unroll
-      for (int s = 0; s < SLOTS; ++s) {
-        if (bl.valid(s)) {
-          const double r = div_fast(nz[s] * bt.mask_diff(bl.band(s)), er[s]);   // noise / (excitation / mask)
-          nsum += r;
-          if (r > nmax) nmax = r;
-        }
-      }
-      double xsum = 0., qsum = 0.;                    // sum of the bands' exponents (pc above), of the steps
-      if (!ADV && chan == 0) {
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-          if (bl.valid(s)) {
-            const int b = bl.band(s);
-            double x = fmax(sh.pc[0][b], 0.), q = sh.qc[0][b];      // (fmax: a NaN exponent counts as 0, like `pc > p`)
-            if (channels == 2) {
-              if (sh.pc[1][b] > x) x = sh.pc[1][b];
-              if (sh.qc[1][b] > q) q = sh.qc[1][b];
-            }
-            xsum += x;
-            qsum += q;
-          }
-        }
-      }
-      double nl_sum;
-      if (!ADV)
-        wave_sum4(nsum, nl_part, qsum, xsum, nsum, nl_sum, qsum, xsum);
-      else
-        nsum = wave_sum(nsum);
-      nsum /= NB;
-      // RelDistFrames asks whether ANY band's ratio is above 1.5 dB: a vote, not a maximum (the debug build reports the value)
-      const bool disturbed = __any(nmax > 1.41253754462275);
-      if (DBG) nmax = wave_max(nmax);
-      if (!ADV && nl_open) {
-        const double nl = noise_loudness_total<NB>(nl_sum, 0.);
-        if (frame >= 24 && frame - 3 >= loud_reached) route(MB_NOISELOUD, nl, 1.);
-        if (DBG && lane == 0)
-          a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = nl;
-      }
-      if (DBG && lane == 0) {
-        double* __restrict__ d =
-            a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov;
-        d[4] = nsum;
-        d[5] = nmax;
-      }
-      if (!ADV) {
-        route(MB_NMR, nsum, 1.);                                    // MODE_AVG_LOG
-        route(MB_RELDIST, disturbed ? 1. : 0., 1.);
-      } else {
-        const double seg = (10. * kInvLn10) * log_pos(nsum);        // 10 log10, MODE_AVG; nsum > 0 (floored bands)
-        route(MA_SEGNMR, seg, 1.);
-        if (DBG && lane == 0)
-          a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = seg;
-      }
-      if (!ADV && chan == 0) {
-        const double p_bin = 1. - bt.exp(-kLn2 * xsum);             // 1 - prod_b 0.5^xb (movs.c:1263-1270)
-        if (DBG && lane == 0) {
-          double* __restrict__ d =
-              a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels) * kDbgDoubles + kDbgMov;
-          d[6] = p_bin;
-          d[7] = qsum;
-        }
-        if (p_bin > 0.5) route(MB_ADB, qsum, 1.);
-        route(MB_MFPD, p_bin, 1.);
-      }
-    }
-    // ---- error harmonic structure (movs.c:1374-1381,1442) ------------------------------
-    if (ehs_valid) {
-      route(ADV ? MA_EHS : MB_EHS, 1000. * rec[kRecEhs], 1.);
-    }
-    // ---- totalsnr (gstpeaq.c:913-918) --------------------------------------------------------
-    if (chan == 0 && lane == 0) {
-      sh.energy[0] += rec0[kRecSigE] + (channels == 2 ? rec0[kRecDoubles + kRecSigE] : 0.);
-      sh.energy[1] += rec0[kRecNoiseE] + (channels == 2 ? rec0[kRecDoubles + kRecNoiseE] : 0.);
-    }
-    // ---- accumulate: lane i owns accumulator i --------------------------------------------------
-    if (my_hit) acc.add(my_v, my_w);
-    if (!ADV) __syncthreads();                       // sh.pc/qc/gate are rewritten next frame
-  }
-
-  // ---- registers -> recurrent state -------------------------------------------------------
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int b = bl.band(s);
-    if (b < kBandStride) {
-      cs->vec[kSmearRef][b] = sm[0][s];
-      cs->vec[kSmearTest][b] = sm[1][s];
-      if (!ADV) {                                    // advanced: these belong to the filter-bank back end
-#pragma unroll
-        for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][b] = la[v][s];
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          cs->vec[kModPrevRef + v][b] = mdr[v][s];
-          cs->vec[kModPrevTest + v][b] = mdt[v][s];
-        }
-      }
-    }
-  }
-  if (lane < kMaxAcc) {
-    if (!ADV || lane == MA_SEGNMR || lane == MA_EHS) {
-      acc.store(cs->acc[lane]);
-      if (chan == 0) ps->status[lane] = acc.status;
-    }
-  }
-  if (chan == 0 && lane == 0) {
-    ps->frame_counter = f_end;
-    if (!ADV) ps->loudness_reached = loud_reached;
-    ps->sig_energy = sh.energy[0];
-    ps->noise_energy = sh.energy[1];
-  }
-  if (clk_wave && lane == 0) {                       // launches of one batch follow each other on one stream: one writer
-    a.clk[0] += __builtin_readcyclecounter() - clk_s0;
-    a.clk[1] += wall_clock64() - clk_w0;
-  }
+  constexpr bool PTS = false;
+  constexpr PointArgs pts{};
+#include "peaq_backend_fft.inc"
+}
+// The points instantiation is a kernel of its own name with the same body (not a fourth template parameter of
+// backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
+  constexpr bool DBG = false, PTS = true;
+#include "peaq_backend_fft.inc"
 }
 
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream) {
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
-  if (!a.advanced && a.debug)
+  if (pts && !a.advanced)
+    hipLaunchKernelGGL((backend_points_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pts);
+  else if (pts)
+    hipLaunchKernelGGL((backend_points_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *pts);
+  else if (!a.advanced && a.debug)
     hipLaunchKernelGGL((backend_kernel<109, false, true>), dim3(n_pairs), block, 0, stream, a);
   else if (a.debug)
     hipLaunchKernelGGL((backend_kernel<55, true, true>), dim3(n_pairs), block, 0, stream, a);
@@ -806,186 +518,25 @@ struct FbBackendShared {
 // (held to 128 registers -- 44 B of them spilled around the block loop, none inside: beside the FP64 bank this kernel
 // runs in the place of ONE of a CU's two bank workgroups, 272 registers per SIMD lane, and two of its waves fit there
 // instead of one: + 0.5 % on the advanced pass)
+// PTS = true (fb_backend_points_kernel, trajectory launches only): after each block the reading points that fall on it
+// get the snapshot of the accumulators this path owns (0, 1, 4).
 template <bool DBG>
 __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
-  __shared__ FbBackendShared sh;
-  __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
-  __shared__ double sh_etab[kExpTabEntries];
-  constexpr int NB = kFbBands, SLOTS = 1;
-  const int lane = threadIdx.x & 63;
-  const int chan = threadIdx.x >> 6;
-  const int channels = a.channels;
-  const unsigned pair = blockIdx.x;
-  for (int i = threadIdx.x; i < 2 * kLogTabEntries; i += blockDim.x) sh_ltab[i] = a.common->log_tab[i >> 1][i & 1];
-  if (threadIdx.x < kExpTabEntries) sh_etab[threadIdx.x] = a.common->exp_tab[threadIdx.x];
-  __syncthreads();
-  const GlobalTabs bt{a.bands, sh_ltab, sh_etab};
-  const BandLane<NB, SLOTS> bl{lane};
-  unsigned b_begin, b_end, slot = pair;
-  if (a.windows) {                                   // broker launch: this session's own window and state
-    const FbPairWindow w = a.windows[pair];
-    b_begin = w.block0;
-    b_end = w.block0 + w.n_blocks;
-    slot = w.slot;
-  } else {
-    const unsigned n_blocks = a.n_blocks ? a.n_blocks[pair] : a.n_blocks_uniform;
-    b_begin = a.block0;
-    b_end = a.block0 + a.blocks_per_launch;
-    if (b_end > n_blocks) b_end = n_blocks;
-  }
-  if (b_begin >= b_end) return;
-  PairState* __restrict__ ps = a.state + slot;
-  ChannelState* __restrict__ cs = &ps->ch[chan];
-
-  const int bb = lane < kBandStride ? lane : 0;
-  double la[6][SLOTS], mdr[3][SLOTS], mdt[3][SLOTS];
-#pragma unroll
-  for (int v = 0; v < 6; ++v) la[v][0] = cs->vec[kLaFiltRef + v][bb];
-#pragma unroll
-  for (int v = 0; v < 3; ++v) {
-    mdr[v][0] = cs->vec[kModPrevRef + v][bb];
-    mdt[v][0] = cs->vec[kModPrevTest + v][bb];
-  }
-  LaneAcc acc;
-  {
-    const int i = lane < kMaxAcc ? lane : 0;
-    acc.load(&sh.acc[chan][0][lane < kAccLdsStride ? lane : kAccLdsStride - 1], cs->acc[i], acc_mode(true, i),
-             ps->status[i]);
-  }
-  if (lane < kPaPad) sh.pa[chan][0][lane] = sh.pa[chan][1][lane] = 0.;
-  wave_lds_fence();
-  const bool owns = lane == MA_RMSMOD || lane == MA_NLASYM || lane == MA_LINDIST;
-  unsigned loud_reached = ps->loudness_reached;
-
-  // the block's values are requested one block ahead: the walk is a chain of dependent transcendental
-  // arithmetic, a record load per block would add its full memory latency 320 times per launch
-  const int lb = lane < NB ? lane : 0;
-  struct BlockIn {
-    double ur, ut, er, et, f0, f1;
-  };
-  auto fetch = [&](unsigned blk) {
-    const double* __restrict__ rec0 =
-        a.records + ((size_t)(pair * a.blocks_per_launch + (blk - b_begin)) * channels) * kFbRecDoubles;
-    const double* __restrict__ rec = rec0 + (size_t)chan * kFbRecDoubles;
-    BlockIn in;
-    in.ur = rec[kFbRecUnsmRef + lb];
-    in.ut = rec[kFbRecUnsmTest + lb];
-    in.er = rec[kFbRecExcRef + lb];
-    in.et = rec[kFbRecExcTest + lb];
-    in.f0 = rec0[kFbRecFlags];
-    in.f1 = channels == 2 ? rec0[kFbRecDoubles + kFbRecFlags] : 0.;
-    return in;
-  };
-  BlockIn nxt = fetch(b_begin);
-  for (unsigned blk = b_begin; blk < b_end; ++blk) {
-    const BlockIn cur = nxt;
-    if (blk + 1 < b_end) nxt = fetch(blk + 1);
-    // boundary detector on the 192-sample block, any reference channel (gstpeaq.c:971-979)
-    const bool above = cur.f0 != 0. || cur.f1 != 0.;
-    if (owns) acc.set_tentative(!above);
-
-    double ur[SLOTS], ut[SLOTS], er[SLOTS], et[SLOTS], lr[SLOTS], lt[SLOTS];
-    ur[0] = cur.ur;
-    ut[0] = cur.ut;
-    er[0] = cur.er;
-    et[0] = cur.et;
-    lr[0] = bt.pow(ur[0], 0.3);                      // modpatt.c:235
-    lt[0] = bt.pow(ut[0], 0.3);
-    double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
-    level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
-    modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
-    modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
-    double* __restrict__ dbg =
-        DBG ? a.debug + ((size_t)(pair * a.blocks_per_launch + (blk - b_begin)) * channels + chan) * kDbgFbDoubles : nullptr;
-    if (loud_reached == UINT_MAX) {                  // workgroup-uniform
-      double n_ref, n_test;
-      wave_sum2(total_loudness_part<NB, SLOTS>(bl, bt, er), total_loudness_part<NB, SLOTS>(bl, bt, et), n_ref, n_test);
-      n_ref *= 24. / NB;
-      n_test *= 24. / NB;
-      if (lane == 0) sh.gate[chan] = (n_ref > 0.1 && n_test > 0.1);
-      if (DBG && lane == 0) {
-        dbg[5] = n_ref;
-        dbg[6] = n_test;
-      }
-      __syncthreads();
-      const int g = sh.gate[0] | (channels == 2 ? sh.gate[1] : 0);
-      __syncthreads();
-      if (g) loud_reached = blk;
-    }
-    double v0 = 0., w0 = 1.;
-    bool hit = false;
-    if (DBG || blk >= 125) {                         // gstpeaq.c:988-993
-      double d1, d2, wt;
-      mod_difference<NB, SLOTS>(bl, bt, 1., mr, mt, mdr[1], d1, d2, wt);
-      d1 *= 100. / sqrt((double)NB);                 // MODE_RMS variant, movs.c:243-244
-      if (blk >= 125 && lane == MA_RMSMOD) {
-        v0 = d1;
-        w0 = wt;
-        hit = true;
-      }
-      if (DBG && lane == 0) {
-        dbg[0] = d1;
-        dbg[1] = wt;
-      }
-    }
-    if (DBG || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
-      // movs.c:551-577; SWAP_MOD_PATTS_FOR_NOISE_LOUDNESS_MOVS (shipped: 1) exchanges the modulation
-      // patterns of the missing-components term ...
-      const bool swap = a.cfg.swap_mod_patts != 0;   // workgroup-uniform
-      const double nl_p = noise_loudness_part<NB, SLOTS>(bl, bt, 2.5, 0.3, 1., mr, mt, ad_ref, ad_test);
-      double lead[SLOTS] = {};                       // (ethres / stest)^0.23: the same stest in both calls below
-      const double mc_p = noise_loudness_part<NB, SLOTS, GlobalTabs, LEAD_KEEP>(bl, bt, 1.5, 0.15, 1., swap ? mt : mr,
-                                                                                swap ? mr : mt, ad_test, ad_ref, lead);
-      // ... and (movs.c:679-706) takes the reference modulation twice; unadapted FB excitation
-      const double ld_p = noise_loudness_part<NB, SLOTS, GlobalTabs, LEAD_USE>(bl, bt, 1.5, 0.15, 1., mr, swap ? mr : mt,
-                                                                               ad_ref, er, lead);
-      double nl, mc, ld, none;                       // the three sums over the bands in one reduction
-      wave_sum4(nl_p, mc_p, ld_p, 0., nl, mc, ld, none);
-      nl = noise_loudness_total<NB>(nl, 0.1);
-      mc = noise_loudness_total<NB>(mc, 0.);
-      ld = noise_loudness_total<NB>(ld, 0.);
-      const bool open = blk >= 125 && blk - 13 >= loud_reached;
-      if (open && lane == MA_NLASYM) {
-        v0 = nl;
-        w0 = mc;
-        hit = true;
-      }
-      if (open && lane == MA_LINDIST) {
-        v0 = ld;
-        w0 = 1.;
-        hit = true;
-      }
-      if (DBG && lane == 0) {
-        dbg[2] = nl;
-        dbg[3] = mc;
-        dbg[4] = ld;
-      }
-    }
-    if (hit) acc.add(v0, w0);
-  }
-
-  if (lane < kBandStride) {
-#pragma unroll
-    for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][lane] = la[v][0];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      cs->vec[kModPrevRef + v][lane] = mdr[v][0];
-      cs->vec[kModPrevTest + v][lane] = mdt[v][0];
-    }
-  }
-  if (owns) {
-    acc.store(cs->acc[lane]);
-    if (chan == 0) ps->status[lane] = acc.status;
-  }
-  if (chan == 0 && lane == 0) {
-    ps->fb_counter = b_end;
-    ps->loudness_reached = loud_reached;
-  }
+  constexpr bool PTS = false;
+  constexpr PointArgs pts{};
+#include "peaq_backend_fb.inc"
+}
+// the points instantiation (see backend_points_kernel)
+__global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs a, PointArgs pts) {
+  constexpr bool DBG = false, PTS = true;
+#include "peaq_backend_fb.inc"
 }
 
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream) {
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts) {
   if (n_pairs == 0) return hipSuccess;
-  if (a.debug)
+  if (pts)
+    hipLaunchKernelGGL(fb_backend_points_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *pts);
+  else if (a.debug)
     hipLaunchKernelGGL(fb_backend_kernel<true>, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a);
   else
     hipLaunchKernelGGL(fb_backend_kernel<false>, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a);
@@ -1019,6 +570,29 @@ hipError_t launch_state_init(PairState* state, int /*advanced*/, unsigned n_pair
   return hipGetLastError();
 }
 
+// trajectories: a snapshot holds what state_init_kernel leaves in the fields it copies -- zeros (status kInit,
+// energies, counts, accumulators) but the AVG_WINDOW history's NaN sentinels; one thread per double
+static_assert(kInit == 0, "points_init_kernel writes status as zero");
+__global__ void points_init_kernel(double* __restrict__ raw, size_t n_doubles) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_doubles) return;
+  const unsigned j = (unsigned)(i % kSnapDoubles);
+  double v = 0.;
+  if (j >= (unsigned)kSnapAccHead) {
+    const unsigned f = (j - kSnapAccHead) % kAccFields;
+    if (f >= 3 && f <= 5) v = __builtin_nan("");     // movaccum.c:293
+  }
+  raw[i] = v;
+}
+
+hipError_t launch_points_init(PointSnap* snap, size_t n_snaps, hipStream_t stream) {
+  if (n_snaps == 0) return hipSuccess;
+  const size_t n = n_snaps * kSnapDoubles;
+  hipLaunchKernelGGL(points_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     reinterpret_cast<double*>(snap), n);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // read-out: one thread per pair (movaccum.c:438-481, gstpeaq.c:1013-1078, nn.c)
 // ---------------------------------------------------------------------------
@@ -1044,11 +618,13 @@ __constant__ double na_wx[5][5] = {{21.211773, -39.013052, -1.382553, -14.545348
 __constant__ double na_wxb[5] = {1.330890, 2.686103, 2.096598, -1.327851, 3.087055};
 __constant__ double na_wy[5] = {-4.696996, -3.289959, 7.004782, 6.651897, 4.009144};
 
-__global__ void finalize_kernel(const PairState* __restrict__ st, int advanced, int channels, unsigned n_pairs,
-                                ResultRecord* __restrict__ out, int clamp_movs) {
-  const unsigned pair = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pair >= n_pairs) return;
-  const PairState* ps = st + pair;
+// One pair's read-out from its readable state -- a PairState (finalize_kernel) or a reading point's snapshot
+// (finalize_points_kernel): both go through this one function, so a point and the end result are the same arithmetic.
+// acc0 / acc1: the accumulators [kMaxAcc][kAccFields] of channel 0 / 1.
+__device__ __forceinline__ ResultRecord finalize_state(const int32_t* status, const double (*acc0)[kAccFields],
+                                                       const double (*acc1)[kAccFields], double sig_energy,
+                                                       double noise_energy, double frames, double fb_blocks,
+                                                       int advanced, int channels, int clamp_movs) {
   ResultRecord r;
   const int n_movs = advanced ? 5 : 11;
   for (int i = 0; i < 11; ++i) r.movs[i] = 0.;
@@ -1056,9 +632,9 @@ __global__ void finalize_kernel(const PairState* __restrict__ st, int advanced, 
     const int mode = acc_mode(advanced, i);
     // basic: ADB and MFPD have ONE channel (gstpeaq.c:580-584)
     const int nch = (!advanced && (i == MB_ADB || i == MB_MFPD)) ? 1 : channels;
-    const bool tent = ps->status[i] == kTentative;
+    const bool tent = status[i] == kTentative;
     double v = 0.;
-    for (int c = 0; c < nch; ++c) v += acc_channel_value(mode, tent, ps->ch[c].acc[i]);
+    for (int c = 0; c < nch; ++c) v += acc_channel_value(mode, tent, (c ? acc1 : acc0)[i]);
     r.movs[i] = v / nch;
   }
   double di;
@@ -1084,10 +660,29 @@ __global__ void finalize_kernel(const PairState* __restrict__ st, int advanced, 
   }
   r.di = di;
   r.odg = -3.98 + (0.22 - -3.98) / (1 + exp(-di));          // nn.c:92-93,372-375
-  r.totalsnr = 10 * log10(ps->sig_energy / ps->noise_energy);
-  r.frames = (double)ps->frame_counter;
-  r.fb_blocks = (double)ps->fb_counter;
-  out[pair] = r;
+  r.totalsnr = 10 * log10(sig_energy / noise_energy);
+  r.frames = frames;
+  r.fb_blocks = fb_blocks;
+  return r;
+}
+
+__global__ void finalize_kernel(const PairState* __restrict__ st, int advanced, int channels, unsigned n_pairs,
+                                ResultRecord* __restrict__ out, int clamp_movs) {
+  const unsigned pair = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pair >= n_pairs) return;
+  const PairState* ps = st + pair;
+  out[pair] = finalize_state(ps->status, ps->ch[0].acc, ps->ch[1].acc, ps->sig_energy, ps->noise_energy,
+                             (double)ps->frame_counter, (double)ps->fb_counter, advanced, channels, clamp_movs);
+}
+
+// one thread per (pair, point): out[pair][point]
+__global__ void finalize_points_kernel(const PointSnap* __restrict__ snap, int advanced, int channels, size_t n_snaps,
+                                       ResultRecord* __restrict__ out, int clamp_movs) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_snaps) return;
+  const PointSnap* sp = snap + i;
+  out[i] = finalize_state(sp->status, sp->acc[0], sp->acc[1], sp->sig_energy, sp->noise_energy, (double)sp->frames,
+                          (double)sp->fb_blocks, advanced, channels, clamp_movs);
 }
 
 hipError_t launch_finalize(const PairState* state, int advanced, int channels, unsigned n_pairs, ResultRecord* out,
@@ -1095,6 +690,15 @@ hipError_t launch_finalize(const PairState* state, int advanced, int channels, u
   if (n_pairs == 0) return hipSuccess;
   hipLaunchKernelGGL(finalize_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, stream, state, advanced, channels,
                      n_pairs, out, cfg.clamp_movs);
+  return hipGetLastError();
+}
+
+hipError_t launch_finalize_points(const PointSnap* snap, int advanced, int channels, unsigned n_pairs, int n_points,
+                                  ResultRecord* out, hipStream_t stream, const Settings& cfg) {
+  const size_t n = (size_t)n_pairs * (size_t)(n_points > 0 ? n_points : 0);
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(finalize_points_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, snap, advanced,
+                     channels, n, out, cfg.clamp_movs);
   return hipGetLastError();
 }
 

@@ -1,0 +1,188 @@
+// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = false) and
+// fb_backend_points_kernel (PTS = true) in peaq_backend.hip: one text, two kernels of their own names.
+  __shared__ FbBackendShared sh;
+  __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
+  __shared__ double sh_etab[kExpTabEntries];
+  constexpr int NB = kFbBands, SLOTS = 1;
+  const int lane = threadIdx.x & 63;
+  const int chan = threadIdx.x >> 6;
+  const int channels = a.channels;
+  const unsigned pair = blockIdx.x;
+  for (int i = threadIdx.x; i < 2 * kLogTabEntries; i += blockDim.x) sh_ltab[i] = a.common->log_tab[i >> 1][i & 1];
+  if (threadIdx.x < kExpTabEntries) sh_etab[threadIdx.x] = a.common->exp_tab[threadIdx.x];
+  __syncthreads();
+  const GlobalTabs bt{a.bands, sh_ltab, sh_etab};
+  const BandLane<NB, SLOTS> bl{lane};
+  unsigned b_begin, b_end, slot = pair;
+  if (a.windows) {                                   // broker launch: this session's own window and state
+    const FbPairWindow w = a.windows[pair];
+    b_begin = w.block0;
+    b_end = w.block0 + w.n_blocks;
+    slot = w.slot;
+  } else {
+    const unsigned n_blocks = a.n_blocks ? a.n_blocks[pair] : a.n_blocks_uniform;
+    b_begin = a.block0;
+    b_end = a.block0 + a.blocks_per_launch;
+    if (b_end > n_blocks) b_end = n_blocks;
+  }
+  if (b_begin >= b_end) return;
+  PairState* __restrict__ ps = a.state + slot;
+  ChannelState* __restrict__ cs = &ps->ch[chan];
+
+  const int bb = lane < kBandStride ? lane : 0;
+  double la[6][SLOTS], mdr[3][SLOTS], mdt[3][SLOTS];
+#pragma unroll
+  for (int v = 0; v < 6; ++v) la[v][0] = cs->vec[kLaFiltRef + v][bb];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    mdr[v][0] = cs->vec[kModPrevRef + v][bb];
+    mdt[v][0] = cs->vec[kModPrevTest + v][bb];
+  }
+  LaneAcc acc;
+  {
+    const int i = lane < kMaxAcc ? lane : 0;
+    acc.load(&sh.acc[chan][0][lane < kAccLdsStride ? lane : kAccLdsStride - 1], cs->acc[i], acc_mode(true, i),
+             ps->status[i]);
+  }
+  if (lane < kPaPad) sh.pa[chan][0][lane] = sh.pa[chan][1][lane] = 0.;
+  wave_lds_fence();
+  const bool owns = lane == MA_RMSMOD || lane == MA_NLASYM || lane == MA_LINDIST;
+  unsigned loud_reached = ps->loudness_reached;
+  __shared__ PointWalk<true> sh_pw[2];                  // (points instantiation only)
+  PointWalk<true>& pw = sh_pw[wave_uniform(chan)];
+  if (PTS) pw.init(pts, pair, b_begin);
+
+  // the block's values are requested one block ahead: the walk is a chain of dependent transcendental
+  // arithmetic, a record load per block would add its full memory latency 320 times per launch
+  const int lb = lane < NB ? lane : 0;
+  struct BlockIn {
+    double ur, ut, er, et, f0, f1;
+  };
+  auto fetch = [&](unsigned blk) {
+    const double* __restrict__ rec0 =
+        a.records + ((size_t)(pair * a.blocks_per_launch + (blk - b_begin)) * channels) * kFbRecDoubles;
+    const double* __restrict__ rec = rec0 + (size_t)chan * kFbRecDoubles;
+    BlockIn in;
+    in.ur = rec[kFbRecUnsmRef + lb];
+    in.ut = rec[kFbRecUnsmTest + lb];
+    in.er = rec[kFbRecExcRef + lb];
+    in.et = rec[kFbRecExcTest + lb];
+    in.f0 = rec0[kFbRecFlags];
+    in.f1 = channels == 2 ? rec0[kFbRecDoubles + kFbRecFlags] : 0.;
+    return in;
+  };
+  BlockIn nxt = fetch(b_begin);
+  for (unsigned blk = b_begin; blk < b_end; ++blk) {
+    const BlockIn cur = nxt;
+    if (blk + 1 < b_end) nxt = fetch(blk + 1);
+    // boundary detector on the 192-sample block, any reference channel (gstpeaq.c:971-979)
+    const bool above = cur.f0 != 0. || cur.f1 != 0.;
+    if (owns) acc.set_tentative(!above);
+
+    double ur[SLOTS], ut[SLOTS], er[SLOTS], et[SLOTS], lr[SLOTS], lt[SLOTS];
+    ur[0] = cur.ur;
+    ut[0] = cur.ut;
+    er[0] = cur.er;
+    et[0] = cur.et;
+    lr[0] = bt.pow(ur[0], 0.3);                      // modpatt.c:235
+    lt[0] = bt.pow(ut[0], 0.3);
+    double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
+    level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
+    modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
+    modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+    double* __restrict__ dbg =
+        DBG ? a.debug + ((size_t)(pair * a.blocks_per_launch + (blk - b_begin)) * channels + chan) * kDbgFbDoubles : nullptr;
+    if (loud_reached == UINT_MAX) {                  // workgroup-uniform
+      double n_ref, n_test;
+      wave_sum2(total_loudness_part<NB, SLOTS>(bl, bt, er), total_loudness_part<NB, SLOTS>(bl, bt, et), n_ref, n_test);
+      n_ref *= 24. / NB;
+      n_test *= 24. / NB;
+      if (lane == 0) sh.gate[chan] = (n_ref > 0.1 && n_test > 0.1);
+      if (DBG && lane == 0) {
+        dbg[5] = n_ref;
+        dbg[6] = n_test;
+      }
+      __syncthreads();
+      const int g = sh.gate[0] | (channels == 2 ? sh.gate[1] : 0);
+      __syncthreads();
+      if (g) loud_reached = blk;
+    }
+    double v0 = 0., w0 = 1.;
+    bool hit = false;
+    if (DBG || blk >= 125) {                         // gstpeaq.c:988-993
+      double d1, d2, wt;
+      mod_difference<NB, SLOTS>(bl, bt, 1., mr, mt, mdr[1], d1, d2, wt);
+      d1 *= 100. / sqrt((double)NB);                 // MODE_RMS variant, movs.c:243-244
+      if (blk >= 125 && lane == MA_RMSMOD) {
+        v0 = d1;
+        w0 = wt;
+        hit = true;
+      }
+      if (DBG && lane == 0) {
+        dbg[0] = d1;
+        dbg[1] = wt;
+      }
+    }
+    if (DBG || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
+      // movs.c:551-577; SWAP_MOD_PATTS_FOR_NOISE_LOUDNESS_MOVS (shipped: 1) exchanges the modulation
+      // patterns of the missing-components term ...
+      const bool swap = a.cfg.swap_mod_patts != 0;   // workgroup-uniform
+      const double nl_p = noise_loudness_part<NB, SLOTS>(bl, bt, 2.5, 0.3, 1., mr, mt, ad_ref, ad_test);
+      double lead[SLOTS] = {};                       // (ethres / stest)^0.23: the same stest in both calls below
+      const double mc_p = noise_loudness_part<NB, SLOTS, GlobalTabs, LEAD_KEEP>(bl, bt, 1.5, 0.15, 1., swap ? mt : mr,
+                                                                                swap ? mr : mt, ad_test, ad_ref, lead);
+      // ... and (movs.c:679-706) takes the reference modulation twice; unadapted FB excitation
+      const double ld_p = noise_loudness_part<NB, SLOTS, GlobalTabs, LEAD_USE>(bl, bt, 1.5, 0.15, 1., mr, swap ? mr : mt,
+                                                                               ad_ref, er, lead);
+      double nl, mc, ld, none;                       // the three sums over the bands in one reduction
+      wave_sum4(nl_p, mc_p, ld_p, 0., nl, mc, ld, none);
+      nl = noise_loudness_total<NB>(nl, 0.1);
+      mc = noise_loudness_total<NB>(mc, 0.);
+      ld = noise_loudness_total<NB>(ld, 0.);
+      const bool open = blk >= 125 && blk - 13 >= loud_reached;
+      if (open && lane == MA_NLASYM) {
+        v0 = nl;
+        w0 = mc;
+        hit = true;
+      }
+      if (open && lane == MA_LINDIST) {
+        v0 = ld;
+        w0 = 1.;
+        hit = true;
+      }
+      if (DBG && lane == 0) {
+        dbg[2] = nl;
+        dbg[3] = mc;
+        dbg[4] = ld;
+      }
+    }
+    if (hit) acc.add(v0, w0);
+    if (PTS) {                                       // reading points after this block (see backend_kernel)
+      while (PointSnap* __restrict__ sp = pw.take(blk + 1)) {
+        if (owns) {
+#pragma unroll 1
+          for (int k = 0; k < kAccFields; ++k) sp->acc[chan][lane][k] = acc.at(k);
+          if (chan == 0) sp->status[lane] = acc.status;
+        }
+        if (chan == 0 && lane == 0) sp->fb_blocks = blk + 1;
+      }
+    }
+  }
+
+  if (lane < kBandStride) {
+#pragma unroll
+    for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][lane] = la[v][0];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      cs->vec[kModPrevRef + v][lane] = mdr[v][0];
+      cs->vec[kModPrevTest + v][lane] = mdt[v][0];
+    }
+  }
+  if (owns) {
+    acc.store(cs->acc[lane]);
+    if (chan == 0) ps->status[lane] = acc.status;
+  }
+  if (chan == 0 && lane == 0) {
+    ps->fb_counter = b_end;
+    ps->loudness_reached = loud_reached;
+  }

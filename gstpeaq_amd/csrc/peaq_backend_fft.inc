@@ -1,0 +1,376 @@
+// peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = false) and
+// backend_points_kernel<NB, ADV> (PTS = true) in peaq_backend.hip: one text, two kernels of their own names.
+  __shared__ BackendShared sh;
+  __shared__ double sh_tab[T_COUNT * kBandStride];
+  __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
+  constexpr int SLOTS = 2;
+  const int lane = threadIdx.x & 63;
+  const int chan = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: keep it scalar
+  const int channels = a.channels;                  // == blockDim.x / 64
+  const unsigned pair = blockIdx.x;
+  const BandLane<NB, SLOTS> bl{lane};
+  {
+    const BandTables* __restrict__ g = a.bands;
+    const double* const src[T_COUNT] = {g->adapt_tc, g->ear_tc, g->threshold, g->loud_factor, g->exc_threshold,
+                                        g->internal_noise, g->noise_pow03, g->mask_diff, g->inv_spread_norm,
+                                        g->inv_spread_norm_pow03, g->ln_internal_noise, g->inv_window_count};
+#pragma unroll
+    for (int t = 0; t < T_COUNT; ++t)
+      for (int i = threadIdx.x; i < kBandStride; i += blockDim.x) sh_tab[t * kBandStride + i] = src[t][i];
+    for (int i = threadIdx.x; i < 2 * kLogTabEntries; i += blockDim.x) sh_ltab[i] = a.common->log_tab[i >> 1][i & 1];
+  }
+  LdsTabs bt{sh_tab, 0, a.bands->deriv_factor, sh_ltab};
+  PairState* __restrict__ ps = a.state + (a.pair_slot ? a.pair_slot[pair] : pair);
+  ChannelState* __restrict__ cs = &ps->ch[chan];
+
+  unsigned f_begin, f_end;
+  if (a.pair_frame0) {                               // broker launch: this pair's own window
+    f_begin = a.pair_frame0[pair];
+    f_end = f_begin + a.pair_nframes[pair];
+  } else {
+    const unsigned n_frames = a.n_frames ? a.n_frames[pair] : a.n_frames_uniform;
+    f_begin = a.frame0;
+    f_end = a.frame0 + a.frames_per_launch;
+    if (f_end > n_frames) f_end = n_frames;
+  }
+  if (f_begin >= f_end) return;
+  const bool clk_wave = a.clk && blockIdx.x == 0 && chan == 0;   // wave-uniform
+  unsigned long long clk_s0 = 0, clk_w0 = 0;
+  if (clk_wave) {
+    clk_w0 = wall_clock64();
+    clk_s0 = __builtin_readcyclecounter();
+  }
+  if (lane < kPaPad) sh.pa[chan][0][lane] = sh.pa[chan][1][lane] = 0.;
+  __syncthreads();                                   // the table copy is complete
+
+  // ---- recurrent state -> registers -----------------------------------------------
+  double sm[2][SLOTS];                               // smeared excitation filters (ref, test)
+  double la[6][SLOTS];
+  double mdr[3][SLOTS], mdt[3][SLOTS];
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const int b = bl.band(s);
+    sm[0][s] = cs->vec[kSmearRef][b < kBandStride ? b : 0];
+    sm[1][s] = cs->vec[kSmearTest][b < kBandStride ? b : 0];
+#pragma unroll
+    for (int v = 0; v < 6; ++v) la[v][s] = cs->vec[kLaFiltRef + v][b < kBandStride ? b : 0];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      mdr[v][s] = cs->vec[kModPrevRef + v][b < kBandStride ? b : 0];
+      mdt[v][s] = cs->vec[kModPrevTest + v][b < kBandStride ? b : 0];
+    }
+  }
+  LaneAcc acc;
+  {
+    const int i = lane < kMaxAcc ? lane : 0;
+    acc.load(&sh.acc[chan][0][lane < kAccLdsStride ? lane : kAccLdsStride - 1], cs->acc[i], acc_mode(ADV, i),
+             ps->status[i]);   // lanes beyond the 11 accumulators work on dummy slots
+  }
+  unsigned loud_reached = ps->loudness_reached;
+  __shared__ PointWalk<false> sh_pw[2];                  // (points instantiation only)
+  PointWalk<false>& pw = sh_pw[chan];
+  if (PTS) pw.init(pts, pair, f_begin);
+  if (chan == 0 && lane == 0) {
+    sh.energy[0] = ps->sig_energy;
+    sh.energy[1] = ps->noise_energy;
+  }
+
+  for (unsigned frame = f_begin; frame < f_end; ++frame) {
+    asm volatile("" : "+v"(bt.off));                 // the tables are re-read from LDS where they are used
+    const double* __restrict__ rec0 =
+        a.records + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels) * kRecDoubles;
+    const double* __restrict__ rec = rec0 + (size_t)chan * kRecDoubles;
+
+    // ---- frame flags over all channels (gstpeaq.c:858-862, movs.c:1374-1381) -----
+    int fl_ref = (int)rec0[kRecFlagsRef], fl_test = (int)rec0[kRecFlagsTest];
+    if (channels == 2) {
+      fl_ref |= (int)rec0[kRecDoubles + kRecFlagsRef];
+      fl_test |= (int)rec0[kRecDoubles + kRecFlagsTest];
+    }
+    const bool above = fl_ref & 1;
+    const bool ehs_valid = ((fl_ref | fl_test) & 2) != 0;
+    if (!ADV || lane == MA_SEGNMR || lane == MA_EHS) acc.set_tentative(!above);
+
+    // ---- this frame's patterns -------------------------------------------------------
+    double ur[SLOTS], ut[SLOTS], lr[SLOTS], lt[SLOTS], nz[SLOTS];
+    {
+      const int b0 = bl.band(0);
+      const int bb = b0 < kBandStride ? b0 : 0;
+      const double2 v0 = *reinterpret_cast<const double2*>(rec + kRecRootRef + bb);
+      const double2 v1 = *reinterpret_cast<const double2*>(rec + kRecRootTest + bb);
+      const double2 v4 = *reinterpret_cast<const double2*>(rec + kRecNoise + bb);
+      // unsmeared excitation (fftearmodel.c:593-597) and its 0.3rd power (modpatt.c:235) from the roots
+      const double n0 = bt.at(T_ISN, bb), n1 = bt.at(T_ISN, bb + 1);
+      const double m0 = bt.at(T_ISN03, bb), m1 = bt.at(T_ISN03, bb + 1);
+      excitation_from_root(v0.x, n0, m0, ur[0], lr[0]);
+      excitation_from_root(v0.y, n1, m1, ur[1], lr[1]);
+      excitation_from_root(v1.x, n0, m0, ut[0], lt[0]);
+      excitation_from_root(v1.y, n1, m1, ut[1], lt[1]);
+      nz[0] = v4.x; nz[1] = v4.y;
+    }
+    double nl_part = 0.;                               // basic version: the lane's part of the noise loudness, summed with the NMR's
+    bool nl_open = false;
+    // time smearing, fftearmodel.c:496-504
+    double er[SLOTS], et[SLOTS];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+      const int b = bl.band(s) < kBandStride ? bl.band(s) : 0;
+      const double ac = bt.ear_tc(b);
+      sm[0][s] = ac * sm[0][s] + (1. - ac) * ur[s];
+      er[s] = sm[0][s] > ur[s] ? sm[0][s] : ur[s];
+      if (!ADV) {
+        sm[1][s] = ac * sm[1][s] + (1. - ac) * ut[s];
+        et[s] = sm[1][s] > ut[s] ? sm[1][s] : ut[s];
+      } else {
+        et[s] = 0.;
+      }
+    }
+
+    // lane i owns accumulator i: every MOV value of the frame is routed to its owner as soon as
+    // it exists (two selects) instead of being kept in a per-lane table
+    double my_v = 0., my_w = 1.;
+    bool my_hit = false;
+    auto route = [&](int idx, double v, double w) {
+      if (lane == idx) {
+        my_v = v;
+        my_w = w;
+        my_hit = true;
+      }
+    };
+
+    if (!ADV) {
+      // ---- pattern processing (gstpeaq.c:834-845) ------------------------------------
+      double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
+      level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
+      modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
+      modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+      if (DBG) {
+        double* __restrict__ d =
+            a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+          if (bl.valid(s)) {
+            const int b = bl.band(s);
+            d[kDbgExcRef + b] = er[s];
+            d[kDbgExcTest + b] = et[s];
+            d[kDbgAdaptRef + b] = ad_ref[s];
+            d[kDbgAdaptTest + b] = ad_test[s];
+            d[kDbgModRef + b] = mr[s];
+            d[kDbgModTest + b] = mt[s];
+            d[kDbgAvgLoudRef + b] = mdr[1][s];
+            d[kDbgAvgLoudTest + b] = mdt[1][s];
+          }
+        }
+      }
+      if (loud_reached == UINT_MAX) {                // wave-uniform
+        double n_ref, n_test;
+        wave_sum2(total_loudness_part<NB, SLOTS>(bl, bt, er), total_loudness_part<NB, SLOTS>(bl, bt, et), n_ref, n_test);
+        n_ref *= 24. / NB;
+        n_test *= 24. / NB;
+        if (lane == 0) sh.gate[chan] = (n_ref > 0.1 && n_test > 0.1);
+        if (DBG && lane == 0) {
+          double* __restrict__ d =
+              a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles;
+          d[kDbgLoudnessRef] = n_ref;
+          d[kDbgLoudnessTest] = n_test;
+        }
+      }
+      // ---- detection probability, per channel part (movs.c:1239-1262) -----------------
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        double pc = 0., qc = 0.;
+        if (bl.valid(s)) {
+          const double er_db = (10. * kInvLn10) * bt.log(er[s]);      // 10 log10: excitations are > 0
+          const double et_db = (10. * kInvLn10) * bt.log(et[s]);
+          const double l = 0.3 * fmax(er_db, et_db) + 0.7 * et_db;
+          const double l2 = l * l;
+          // (6.39468 / l)^1.71332 = exp(1.71332 (ln 6.39468 - ln l)); one reciprocal of s for both quotients
+          const double sd = l > 0. ? 5.95072 * bt.exp(1.71332 * (1.8554663946857675 - bt.log(l))) + 9.01033e-11 * l2 * l2 +
+                                         5.05622e-6 * l2 * l - 0.00102438 * l * l + 0.0550197 * l - 0.198719
+                                   : 1e30;
+          const double inv_sd = div_fast(1., sd);
+          const double e = er_db - et_db;
+          const double x = e * inv_sd, x2 = x * x;
+          const double xb = er_db > et_db ? x2 * x2 : x2 * x2 * x2;   // (e/s)^b, b = 4 or 6
+          // The channel's detection probability is pc = 1 - 0.5^xb (movs.c:1253); what the frame needs of it is
+          // prod_b (1 - max_c pc) = 0.5^(sum_b max_c xb) (pc grows with xb, so the maxima agree): the EXPONENTS are
+          // exchanged and summed, and the one exponential of the frame is taken after the reduction -- an exponential
+          // per band, channel and frame less, and the product's own reduction rides in the free slot of the sums'.
+          pc = xb;
+          qc = fabs(a.cfg.floor_steps ? floor(e) : trunc(e)) * inv_sd;        // movs.c:1256-1260
+        }
+        sh.pc[chan][bl.band(s)] = pc;
+        sh.qc[chan][bl.band(s)] = qc;
+      }
+      __syncthreads();
+      if (loud_reached == UINT_MAX) {
+        const int g = sh.gate[0] | (channels == 2 ? sh.gate[1] : 0);
+        if (g) loud_reached = frame;
+      }
+      double* __restrict__ dmov =                    // debug instantiation: this (frame, channel)'s MOV values
+          DBG ? a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov
+              : nullptr;
+      // ---- modulation difference (gstpeaq.c:871-877) --------------------------------
+      if (DBG || frame >= 24) {
+        double d1, d2, wt;
+        mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
+        d1 *= 100. / NB;
+        d2 *= 100. / NB;
+        if (frame >= 24) {
+          route(MB_AVGMOD1, d1, wt);
+          route(MB_AVGMOD2, d2, wt);
+          route(MB_WINMOD, d1, 1.);
+        }
+        if (DBG && lane == 0) {
+          dmov[0] = d1;
+          dmov[1] = d2;
+          dmov[2] = wt;
+        }
+      }
+      // ---- noise loudness (gstpeaq.c:880-886; unsigned compare with UINT_MAX sentinel)
+      // (its sum over the bands goes through the reduction of the noise-to-mask ratio below)
+      nl_open = DBG || (frame >= 24 && frame - 3 >= loud_reached);
+      if (nl_open) nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
+      // ---- bandwidth (movs.c:797-807) ------------------------------------------------------
+      {
+        const double bw_ref = rec[kRecBwRef];
+        if (bw_ref > 346.) {
+          route(MB_BW_REF, bw_ref, 1.);
+          route(MB_BW_TEST, rec[kRecBwTest], 1.);
+        }
+      }
+    }
+    // ---- noise-to-mask ratio (movs.c:1002-1022), detection probability's binaural part (movs.c:1263-1275): the
+    // lanes' parts first, then ONE reduction for the three sums of this place (with the noise loudness's from above) ----
+    {
+      double nsum = 0., nmax = 0.;
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        if (bl.valid(s)) {
+          const double r = div_fast(nz[s] * bt.mask_diff(bl.band(s)), er[s]);   // noise / (excitation / mask)
+          nsum += r;
+          if (r > nmax) nmax = r;
+        }
+      }
+      double xsum = 0., qsum = 0.;                    // sum of the bands' exponents (pc above), of the steps
+      if (!ADV && chan == 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+          if (bl.valid(s)) {
+            const int b = bl.band(s);
+            double x = fmax(sh.pc[0][b], 0.), q = sh.qc[0][b];      // (fmax: a NaN exponent counts as 0, like `pc > p`)
+            if (channels == 2) {
+              if (sh.pc[1][b] > x) x = sh.pc[1][b];
+              if (sh.qc[1][b] > q) q = sh.qc[1][b];
+            }
+            xsum += x;
+            qsum += q;
+          }
+        }
+      }
+      double nl_sum;
+      if (!ADV)
+        wave_sum4(nsum, nl_part, qsum, xsum, nsum, nl_sum, qsum, xsum);
+      else
+        nsum = wave_sum(nsum);
+      nsum /= NB;
+      // RelDistFrames asks whether ANY band's ratio is above 1.5 dB: a vote, not a maximum (the debug build reports the value)
+      const bool disturbed = __any(nmax > 1.41253754462275);
+      if (DBG) nmax = wave_max(nmax);
+      if (!ADV && nl_open) {
+        const double nl = noise_loudness_total<NB>(nl_sum, 0.);
+        if (frame >= 24 && frame - 3 >= loud_reached) route(MB_NOISELOUD, nl, 1.);
+        if (DBG && lane == 0)
+          a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = nl;
+      }
+      if (DBG && lane == 0) {
+        double* __restrict__ d =
+            a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov;
+        d[4] = nsum;
+        d[5] = nmax;
+      }
+      if (!ADV) {
+        route(MB_NMR, nsum, 1.);                                    // MODE_AVG_LOG
+        route(MB_RELDIST, disturbed ? 1. : 0., 1.);
+      } else {
+        const double seg = (10. * kInvLn10) * log_pos(nsum);        // 10 log10, MODE_AVG; nsum > 0 (floored bands)
+        route(MA_SEGNMR, seg, 1.);
+        if (DBG && lane == 0)
+          a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = seg;
+      }
+      if (!ADV && chan == 0) {
+        const double p_bin = 1. - bt.exp(-kLn2 * xsum);             // 1 - prod_b 0.5^xb (movs.c:1263-1270)
+        if (DBG && lane == 0) {
+          double* __restrict__ d =
+              a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels) * kDbgDoubles + kDbgMov;
+          d[6] = p_bin;
+          d[7] = qsum;
+        }
+        if (p_bin > 0.5) route(MB_ADB, qsum, 1.);
+        route(MB_MFPD, p_bin, 1.);
+      }
+    }
+    // ---- error harmonic structure (movs.c:1374-1381,1442) ------------------------------
+    if (ehs_valid) {
+      route(ADV ? MA_EHS : MB_EHS, 1000. * rec[kRecEhs], 1.);
+    }
+    // ---- totalsnr (gstpeaq.c:913-918) --------------------------------------------------------
+    if (chan == 0 && lane == 0) {
+      sh.energy[0] += rec0[kRecSigE] + (channels == 2 ? rec0[kRecDoubles + kRecSigE] : 0.);
+      sh.energy[1] += rec0[kRecNoiseE] + (channels == 2 ? rec0[kRecDoubles + kRecNoiseE] : 0.);
+    }
+    // ---- accumulate: lane i owns accumulator i --------------------------------------------------
+    if (my_hit) acc.add(my_v, my_w);
+    // ---- reading points after this frame: every lane stores what it wrote itself (its accumulator's LDS slot,
+    // lane 0 of channel 0 the energies), so no barrier -----------------------------------------------------------
+    if (PTS) {
+      while (PointSnap* __restrict__ sp = pw.take(frame + 1)) {
+        if (lane < kMaxAcc && (!ADV || lane == MA_SEGNMR || lane == MA_EHS)) {
+#pragma unroll
+          for (int k = 0; k < kAccFields; ++k) sp->acc[chan][lane][k] = acc.at(k);
+          if (chan == 0) sp->status[lane] = acc.status;
+        }
+        if (chan == 0 && lane == 0) {
+          sp->frames = frame + 1;
+          sp->sig_energy = sh.energy[0];
+          sp->noise_energy = sh.energy[1];
+        }
+      }
+    }
+    if (!ADV) __syncthreads();                       // sh.pc/qc/gate are rewritten next frame
+  }
+
+  // ---- registers -> recurrent state -------------------------------------------------------
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const int b = bl.band(s);
+    if (b < kBandStride) {
+      cs->vec[kSmearRef][b] = sm[0][s];
+      cs->vec[kSmearTest][b] = sm[1][s];
+      if (!ADV) {                                    // advanced: these belong to the filter-bank back end
+#pragma unroll
+        for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][b] = la[v][s];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+          cs->vec[kModPrevRef + v][b] = mdr[v][s];
+          cs->vec[kModPrevTest + v][b] = mdt[v][s];
+        }
+      }
+    }
+  }
+  if (lane < kMaxAcc) {
+    if (!ADV || lane == MA_SEGNMR || lane == MA_EHS) {
+      acc.store(cs->acc[lane]);
+      if (chan == 0) ps->status[lane] = acc.status;
+    }
+  }
+  if (chan == 0 && lane == 0) {
+    ps->frame_counter = f_end;
+    if (!ADV) ps->loudness_reached = loud_reached;
+    ps->sig_energy = sh.energy[0];
+    ps->noise_energy = sh.energy[1];
+  }
+  if (clk_wave && lane == 0) {                       // launches of one batch follow each other on one stream: one writer
+    a.clk[0] += __builtin_readcyclecounter() - clk_s0;
+    a.clk[1] += wall_clock64() - clk_w0;
+  }

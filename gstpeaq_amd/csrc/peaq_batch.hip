@@ -72,7 +72,7 @@ extern "C" size_t peaq_batch_workspace_bytes(int advanced, int channels, int n_p
 static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
                                const float* d_test, size_t pair_stride, const uint32_t* d_nref,
                                const uint32_t* d_ntest, uint32_t n_uniform, const uint32_t* d_nblocks,
-                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate) {
+                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const PointArgs* pts) {
     // ---- filter-bank path: blocks of 192 samples (gstpeaq.c:648-652) ------------------
     const unsigned n_signals = (unsigned)n_pairs * channels * 2;
     const unsigned bc = fb_blocks_per_chunk(n_pairs, channels, max_blocks);
@@ -159,7 +159,7 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
       HIP_TRY(hipEventRecord(e1, s_bank));
       bank_done[b] = e1;
       if (piped) HIP_TRY(hipStreamWaitEvent(s_be, e1, 0));
-      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be));
+      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts));
       if (piped) {
         HIP_TRY(hipEventRecord(e_be, s_be));
         be_done[b] = e_be;
@@ -175,20 +175,30 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
   return PEAQ_OK;
 }
 
+// Reading points of a trajectory (peaq_batch_run_trajectory): nullptr for a plain batch.
+struct TrajectoryOut {
+  uint32_t interval;
+  int n_points;
+  peaq_result* d_points;        // [n_pairs][n_points]
+};
+
 static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs, const float* d_ref,
                             const float* d_test, size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
-                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream);
+                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream, const TrajectoryOut* tr);
 
-extern "C" int peaq_batch_run(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
-                              const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
-                              const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_) {
-  if (!c) return fail(PEAQ_ERR_ARG, "peaq_batch_run: ctx is NULL");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_batch_run: channels must be 1 or 2");
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, "peaq_batch_run: n_pairs < 0");
+// peaq_batch_run and peaq_batch_run_trajectory: one driver, the points optional (`who` names the entry in messages)
+static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                           const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                           const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
+                           const TrajectoryOut* tr) {
+  const std::string w(who);
+  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
+  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2");
+  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || !d_results) return fail(PEAQ_ERR_ARG, "peaq_batch_run: NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
-    return fail(PEAQ_ERR_ARG, "peaq_batch_run: give both n_ref and n_test or neither");
+    return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::lock_guard<std::mutex> lock(c->mu);
   HIP_TRY(hipSetDevice(c->device));
@@ -199,7 +209,7 @@ extern "C" int peaq_batch_run(peaq_ctx* c, int advanced, int channels, double le
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref, n_test,
-                                  n_uniform, d_results, stream);
+                                  n_uniform, d_results, stream, tr);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -211,39 +221,98 @@ extern "C" int peaq_batch_run(peaq_ctx* c, int advanced, int channels, double le
   return PEAQ_OK;
 }
 
+extern "C" int peaq_batch_run(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                              const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                              const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_) {
+  return batch_run_entry("peaq_batch_run", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
+                         n_test, n_uniform, d_results, stream_, nullptr);
+}
+
+// snapshot scratch of a trajectory; 0 when it does not fit size_t
+static size_t trajectory_snap_bytes(int n_pairs, int n_points) {
+  const size_t n = (size_t)std::max(n_pairs, 0) * (size_t)std::max(n_points, 0);
+  return n > SIZE_MAX / sizeof(PointSnap) ? 0 : n * sizeof(PointSnap);
+}
+
+extern "C" int peaq_batch_run_trajectory(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                                         const float* d_ref, const float* d_test, size_t pair_stride,
+                                         const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform,
+                                         uint32_t interval, int n_points, peaq_result* d_points,
+                                         peaq_result* d_results, void* stream_) {
+  // (the points' own arguments first: they need no context)
+  if (interval == 0) return fail(PEAQ_ERR_ARG, "peaq_batch_run_trajectory: interval is 0");
+  if (n_points < 1) return fail(PEAQ_ERR_ARG, "peaq_batch_run_trajectory: n_points < 1");
+  if (!d_points) return fail(PEAQ_ERR_ARG, "peaq_batch_run_trajectory: d_points is NULL");
+  if (n_pairs > 0 && trajectory_snap_bytes(n_pairs, n_points) == 0)
+    return fail(PEAQ_ERR_NOMEM, "peaq_batch_run_trajectory: n_pairs x n_points snapshots exceed the address space");
+  const TrajectoryOut tr{interval, n_points, d_points};
+  return batch_run_entry("peaq_batch_run_trajectory", c, advanced, channels, level_db, n_pairs, d_ref, d_test,
+                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, &tr);
+}
+
+extern "C" size_t peaq_batch_trajectory_workspace_bytes(int advanced, int channels, int n_pairs, uint32_t n_max,
+                                                        int n_points) {
+  return peaq_batch_workspace_bytes(advanced, channels, n_pairs, n_max) + trajectory_snap_bytes(n_pairs, n_points);
+}
+
 // One whole (ref, test) pair from host memory: the batch path with n_pairs = 1 -- for a caller that holds both
 // files (the CLI).  The same frames and blocks as a session fed with the same samples (count_frames), but every
 // kernel sees the whole stream: one front-end launch, the filter-bank path pipelined over its three streams.
-extern "C" int peaq_run_pair(peaq_ctx* c, int advanced, int channels, double level_db, const float* ref, size_t n_ref,
-                             const float* test, size_t n_test, peaq_result* out) {
-  if (!c || !out) return fail(PEAQ_ERR_ARG, "peaq_run_pair: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_run_pair: channels must be 1 or 2");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, "peaq_run_pair: NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, "peaq_run_pair: more than 2^32 samples");
+// points != nullptr: peaq_run_pair_trajectory, n_points readings into host memory as well.
+static int run_pair_host(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, const float* ref,
+                         size_t n_ref, const float* test, size_t n_test, uint32_t interval, int n_points,
+                         peaq_result* points, peaq_result* out) {
+  const std::string w(who);
+  if (!c || (!out && !points)) return fail(PEAQ_ERR_ARG, w + ": NULL argument");
+  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, w + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, w + ": more than 2^32 samples");
   HIP_TRY(hipSetDevice(c->device));
   size_t stride = std::max<size_t>(std::max(n_ref, n_test), 2);
   stride += stride & 1;                              // 8-byte rows: the frame loads are dword pairs
-  TmpBuf d_ref, d_test, d_res;
+  TmpBuf d_ref, d_test, d_res, d_pts;
   const size_t bytes = stride * channels * sizeof(float);
   HIP_TRY(d_ref.reserve(bytes));
   HIP_TRY(d_test.reserve(bytes));
   HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  if (points) HIP_TRY(d_pts.reserve((size_t)n_points * sizeof(peaq_result)));
   HIP_TRY(hipMemset(d_ref.p, 0, bytes));
   HIP_TRY(hipMemset(d_test.p, 0, bytes));
   if (n_ref) HIP_TRY(hipMemcpy(d_ref.p, ref, n_ref * channels * sizeof(float), hipMemcpyHostToDevice));
   if (n_test) HIP_TRY(hipMemcpy(d_test.p, test, n_test * channels * sizeof(float), hipMemcpyHostToDevice));
   const uint32_t h_n[2] = {(uint32_t)n_ref, (uint32_t)n_test};    // peaq_batch_run takes the lengths as HOST arrays
-  const int rc = peaq_batch_run(c, advanced, channels, level_db, 1, d_ref.as<float>(), d_test.as<float>(), stride,
-                                h_n, h_n + 1, 0, d_res.as<peaq_result>(), nullptr);
+  const int rc =
+      points ? peaq_batch_run_trajectory(c, advanced, channels, level_db, 1, d_ref.as<float>(), d_test.as<float>(),
+                                         stride, h_n, h_n + 1, 0, interval, n_points, d_pts.as<peaq_result>(),
+                                         d_res.as<peaq_result>(), nullptr)
+             : peaq_batch_run(c, advanced, channels, level_db, 1, d_ref.as<float>(), d_test.as<float>(), stride, h_n,
+                              h_n + 1, 0, d_res.as<peaq_result>(), nullptr);
   if (rc != PEAQ_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  if (points) HIP_TRY(hipMemcpy(points, d_pts.p, (size_t)n_points * sizeof(peaq_result), hipMemcpyDeviceToHost));
   return PEAQ_OK;
+}
+
+extern "C" int peaq_run_pair(peaq_ctx* c, int advanced, int channels, double level_db, const float* ref, size_t n_ref,
+                             const float* test, size_t n_test, peaq_result* out) {
+  if (!out) return fail(PEAQ_ERR_ARG, "peaq_run_pair: NULL argument");
+  return run_pair_host("peaq_run_pair", c, advanced, channels, level_db, ref, n_ref, test, n_test, 0, 0, nullptr, out);
+}
+
+extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels, double level_db, const float* ref,
+                                        size_t n_ref, const float* test, size_t n_test, uint32_t interval,
+                                        int n_points, peaq_result* points, peaq_result* out) {
+  if (interval == 0) return fail(PEAQ_ERR_ARG, "peaq_run_pair_trajectory: interval is 0");
+  if (n_points < 1) return fail(PEAQ_ERR_ARG, "peaq_run_pair_trajectory: n_points < 1");
+  if (!points) return fail(PEAQ_ERR_ARG, "peaq_run_pair_trajectory: points is NULL");
+  return run_pair_host("peaq_run_pair_trajectory", c, advanced, channels, level_db, ref, n_ref, test, n_test, interval,
+                       n_points, points, out);
 }
 
 static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs, const float* d_ref,
                             const float* d_test, size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
-                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream) {
+                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream, const TrajectoryOut* tr) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -255,7 +324,8 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     std::vector<uint32_t> h(4 * (size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
       if (n_ref[p] > pair_stride || n_test[p] > pair_stride)
-        return fail(PEAQ_ERR_ARG, "peaq_batch_run: a pair is longer than pair_stride");
+        return fail(PEAQ_ERR_ARG, std::string(tr ? "peaq_batch_run_trajectory" : "peaq_batch_run") +
+                                      ": a pair is longer than pair_stride");
       h[p] = n_ref[p];
       h[n_pairs + p] = n_test[p];
       h[2 * (size_t)n_pairs + p] = count_frames(n_ref[p], n_test[p], kFrame, kHop);
@@ -271,7 +341,9 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     d_nframes = d_nref + 2 * (size_t)n_pairs;
     d_nblocks = d_nref + 3 * (size_t)n_pairs;
   } else {
-    if (n_uniform > pair_stride) return fail(PEAQ_ERR_ARG, "peaq_batch_run: n_uniform > pair_stride");
+    if (n_uniform > pair_stride)
+      return fail(PEAQ_ERR_ARG, std::string(tr ? "peaq_batch_run_trajectory" : "peaq_batch_run") +
+                                    ": n_uniform > pair_stride");
     max_frames = count_frames(n_uniform, n_uniform, kFrame, kHop);
     max_blocks = count_frames(n_uniform, n_uniform, kFbFrame, kFbFrame);
   }
@@ -281,9 +353,23 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
   HIP_TRY(c->records.reserve(rec_bytes));
   HIP_TRY(c->records2.reserve(rec_bytes));
   HIP_TRY(c->state.reserve((size_t)n_pairs * sizeof(PairState)));
+  // trajectory: the snapshots of the reading points, [pair][point] (the back ends write them, finalize_points reads them)
+  PointArgs pa{};
+  const size_t n_snaps = tr ? (size_t)n_pairs * tr->n_points : 0;
+  if (tr) {
+    HIP_TRY(c->snaps.reserve(n_snaps * sizeof(PointSnap)));
+    pa.snap = c->snaps.as<PointSnap>();
+    pa.n_ref = d_nref;
+    pa.n_test = d_ntest;
+    pa.n_uniform = n_uniform;
+    pa.interval = tr->interval;
+    pa.n_points = tr->n_points;
+  }
+  const PointArgs* pts = tr ? &pa : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
+  if (tr) HIP_TRY(launch_points_init(pa.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
   const bool with_fb = advanced && max_blocks > 0;
@@ -299,7 +385,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
   auto issue_filterbank_path = [&](hipEvent_t bank_gate) -> int {
     hipStream_t s_fb = PEAQ_DEV_SERIAL_KERNELS ? stream : c->aux2;
     const int rc = run_filterbank_path(c, channels, level_db, n_pairs, d_ref, d_test, pair_stride, d_nref, d_ntest,
-                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate);
+                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts);
     if (rc != PEAQ_OK) return rc;
     fb_done = c->next_event();
     if (!fb_done) return fail(PEAQ_ERR_DEVICE, "hipEventCreate failed");
@@ -384,7 +470,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;
@@ -408,8 +494,12 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
   for (int i = 0; i < 2; ++i)
     if (back_done[i]) HIP_TRY(hipStreamWaitEvent(stream, back_done[i], 0));
   if (fb_done) HIP_TRY(hipStreamWaitEvent(stream, fb_done, 0));
-  HIP_TRY(launch_finalize(c->state.as<PairState>(), advanced, channels, n_pairs,
-                          reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));
+  if (d_results)
+    HIP_TRY(launch_finalize(c->state.as<PairState>(), advanced, channels, n_pairs,
+                            reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));
+  if (tr)
+    HIP_TRY(launch_finalize_points(pa.snap, advanced, channels, n_pairs, tr->n_points,
+                                   reinterpret_cast<ResultRecord*>(tr->d_points), stream, c->settings));
   HIP_TRY(hipEventRecord(c->batch_end, stream));
   c->batch_pending = true;
   return PEAQ_OK;

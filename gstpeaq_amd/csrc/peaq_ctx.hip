@@ -167,6 +167,7 @@ extern "C" void peaq_ctx_destroy(peaq_ctx* c) {
   c->hp_scratch.release();
   c->counts.release();
   c->clk.release();
+  c->snaps.release();
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->batch_begin) (void)hipEventDestroy(c->batch_begin);
   if (c->batch_end) (void)hipEventDestroy(c->batch_end);

@@ -309,6 +309,23 @@ struct PairState {
   ChannelState ch[2];
 };
 
+// The readable part of a pair's state at one reading point of a trajectory (peaq_batch_run_trajectory): what the
+// read-out takes from a PairState.  Written by the back ends after the frame / block at which the point falls, each
+// lane only what it wrote itself (the FFT path: accumulators it owns, status of those, energies, frames; the
+// filter-bank path: its accumulators, their status, fb_blocks).  2184 bytes.
+struct PointSnap {
+  uint32_t frames;              // F(a): FFT frames processed
+  uint32_t fb_blocks;           // B(a): filter-bank blocks processed (advanced)
+  int32_t  status[kMaxAcc];
+  int32_t  pad;
+  double   sig_energy;
+  double   noise_energy;
+  double   acc[2][kMaxAcc][kAccFields];   // [channel][accumulator][field]
+};
+constexpr int kSnapDoubles = sizeof(PointSnap) / sizeof(double);
+constexpr int kSnapAccHead = (int)(sizeof(PointSnap) - sizeof(double) * 2 * kMaxAcc * kAccFields) / (int)sizeof(double);
+static_assert(sizeof(PointSnap) % sizeof(double) == 0, "PointSnap is filled as doubles");
+
 // filter-bank ear-model state of one (pair, channel, signal)  (fbearmodel.c:93-107)
 struct FbSignalState {
   double hp[6];                 // hpfilter1_x1,x2,y1,y2, hpfilter2_y1,y2

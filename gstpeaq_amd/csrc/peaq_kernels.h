@@ -49,6 +49,19 @@ inline unsigned max_frames_per_launch(unsigned n_pairs) {
   return (unsigned)d;
 }
 
+// ---- reading points of a trajectory (peaq_batch_run_trajectory) ----------------
+// Point k of pair p reads the state after F(a_k) FFT frames and B(a_k) filter-bank blocks,
+// a_k = min((k + 1) interval, n_ref[p], n_test[p]).  A kernel argument of the points instantiations only: the
+// argument blocks of the other launches keep their size and layout.
+struct PointArgs {
+  PointSnap* snap;              // [pair][n_points]
+  const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform
+  const uint32_t* n_test;
+  uint32_t n_uniform;
+  uint32_t interval;
+  int n_points;
+};
+
 // ---- pattern back end (time smearing .. MOV accumulation) -------------------
 struct BackendArgs {
   const double* records;        // as written by the front end
@@ -70,7 +83,8 @@ struct BackendArgs {
   // its own lifetime to clk[0], clk[1] -- the clock the device held while the step ran (peaq_batch_last_clock)
   unsigned long long* clk;
 };
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream);
+// pts != nullptr (trajectory launches only): the points instantiation, snapshots after frames (PointArgs)
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr);
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h
@@ -80,6 +94,10 @@ struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h
 hipError_t launch_finalize(const PairState* state, int advanced, int channels, unsigned n_pairs,
                            ResultRecord* out, hipStream_t stream, const Settings& cfg = Settings());   // clamp_movs
 hipError_t launch_state_init(PairState* state, int advanced, unsigned n_pairs, hipStream_t stream);
+// trajectories: every snapshot as state_init_kernel leaves a pair, and the read-out of n_pairs x n_points snapshots
+hipError_t launch_points_init(PointSnap* snap, size_t n_snaps, hipStream_t stream);
+hipError_t launch_finalize_points(const PointSnap* snap, int advanced, int channels, unsigned n_pairs, int n_points,
+                                  ResultRecord* out, hipStream_t stream, const Settings& cfg);
 
 // ---- advanced mode: filter-bank ear model ------------------------------------------
 // Broker launches: "pair" p of the launch is a live session at its own position in its stream.
@@ -140,7 +158,8 @@ struct FbBackendArgs {
   // values before accumulation, computed for EVERY block in the debug instantiation -- or nullptr
   double* debug;
 };
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream);
+// pts != nullptr (trajectory launches only): the points instantiation, snapshots after blocks (PointArgs)
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr);
 
 // ---- synthetic workload --------------------------------------------------------------
 hipError_t launch_synth(uint32_t seed0, unsigned n_pairs, int channels, uint32_t n_samples, size_t pair_stride,

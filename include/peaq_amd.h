@@ -239,6 +239,41 @@ int peaq_batch_run (peaq_ctx *ctx, int advanced, int channels, double playback_l
  * lazily inside the context and reused across calls). */
 size_t peaq_batch_workspace_bytes (int advanced, int channels, int n_pairs, uint32_t n_max);
 
+/* ---- trajectories: readings at fixed intervals through each pair -----------
+ * The element's di / odg / totalsnr properties can be read at any time during a
+ * stream (gstpeaq.c:484-497).  peaq_batch_run_trajectory takes such readings
+ * every `interval` samples per channel (48 kHz) of every pair, in ONE batch run:
+ *
+ *   Point k (0 <= k < n_points) of pair p is exactly what peaq_session_results
+ *   returns for a session that has been pushed the first
+ *   min((k+1) interval, n_ref[p]) reference samples and the first
+ *   min((k+1) interval, n_test[p]) test samples, and has NOT been flushed.
+ *   With a = min((k+1) interval, n_ref[p], n_test[p]) that session has
+ *   processed F(a) = a >= 2048 ? (a - 2048) / 1024 + 1 : 0 FFT frames
+ *   (do_processing, gstpeaq.c:596-611) and, in the advanced version,
+ *   B(a) = a / 192 filter-bank blocks.  The point's record carries
+ *   frames = F(a), fb_blocks = B(a) (0 in basic) and the MOVs, DI, ODG and
+ *   totalsnr of that state: tentative accumulators read their saved values,
+ *   accumulators that are still empty read NaN, as in the reference.  Points
+ *   past the end of both signals all hold the final UNFLUSHED reading.
+ *
+ * d_points: device array [n_pairs][n_points] of peaq_result.  d_results (may be
+ * NULL): the flushed end result of every pair, bit for bit what peaq_batch_run
+ * writes for the same inputs.  Arguments otherwise as for peaq_batch_run, and
+ * the context's settings and FIR mode apply as they do there.  Returns
+ * PEAQ_ERR_ARG for interval == 0, n_points < 1 or d_points == NULL, and
+ * PEAQ_ERR_NOMEM when the snapshot scratch (n_pairs x n_points x about 2.2 KB)
+ * cannot be reserved. */
+int peaq_batch_run_trajectory (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
+                               int n_pairs, const float *d_ref, const float *d_test, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                               uint32_t interval, int n_points,
+                               peaq_result *d_points,   /* device, [n_pairs][n_points] */
+                               peaq_result *d_results,  /* device, [n_pairs], may be NULL */
+                               void *stream);
+/* peaq_batch_workspace_bytes plus the snapshot scratch of n_points readings per pair. */
+size_t peaq_batch_trajectory_workspace_bytes (int advanced, int channels, int n_pairs, uint32_t n_max, int n_points);
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -264,6 +299,11 @@ int peaq_batch_last_clock (peaq_ctx *ctx, double *shader_clock_mhz);
  * framing, flush and results as a session fed with the same samples (gstpeaq.c:596-611, 716-745). */
 int peaq_run_pair (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
                    const float *ref, size_t n_ref, const float *test, size_t n_test, peaq_result *out);
+/* The same with the n_points readings of peaq_batch_run_trajectory into `points` (host, n_points records);
+ * `out` (may be NULL) receives the flushed end result. */
+int peaq_run_pair_trajectory (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
+                              const float *ref, size_t n_ref, const float *test, size_t n_test,
+                              uint32_t interval, int n_points, peaq_result *points /* host */, peaq_result *out);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
