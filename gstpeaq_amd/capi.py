@@ -29,6 +29,13 @@ class PeaqError(RuntimeError):
     pass
 
 
+class ResamplePlan(C.Structure):
+    """mirrors peaq_resample_plan (include/peaq_amd.h)"""
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("taps", C.c_uint32), ("tiled", C.c_int),
+                ("period_out", C.c_uint32), ("period_in", C.c_uint32), ("zero_taps", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("table_bytes", C.c_uint64), ("max_sum_abs_taps", C.c_double)]
+
+
 class _Calibration(C.Structure):
     _fields_ = [("elapsed_ms", C.c_double), ("shader_clock_mhz", C.c_double), ("fp64_tflops", C.c_double),
                 ("cycles_per_fma", C.c_double), ("max_clock_mhz", C.c_double), ("compute_units", C.c_int),
@@ -124,6 +131,14 @@ def load_library():
         L.peaq_batch_trajectory_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.peaq_run_pair_trajectory.argtypes = [vp, C.c_int, C.c_int, C.c_double, fp, C.c_size_t, fp, C.c_size_t,
                                                C.c_uint32, C.c_int, dp, dp]
+    if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_resample_supported.argtypes = [C.c_uint32]
+        L.peaq_resampled_length.restype = C.c_uint32
+        L.peaq_resampled_length.argtypes = [C.c_uint64, C.c_uint32]
+        L.peaq_batch_resample.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, vp, C.c_size_t, u32p, C.c_uint32,
+                                          vp, C.c_size_t, u32p, vp]
+        L.peaq_run_pair_rate.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, fp, C.c_size_t, fp, C.c_size_t, dp]
+        L.peaq_resample_plan_info.argtypes = [C.c_uint32, C.POINTER(ResamplePlan)]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -361,6 +376,18 @@ class Broker:
             pass
 
 
+def _torch_stream(stream):
+    """context manager that makes `stream` (None, a torch.cuda.Stream or a raw hipStream_t) torch's current stream:
+    tensors made inside are filled, and later recycled by the caching allocator, in that stream's order"""
+    import contextlib
+    import torch
+    if stream is None:
+        return contextlib.nullcontext()
+    if not hasattr(stream, "cuda_stream"):
+        stream = torch.cuda.ExternalStream(int(stream))
+    return torch.cuda.stream(stream)
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch
@@ -368,12 +395,77 @@ def _stream_ptr(stream):
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))   # torch.cuda.Stream or a raw hipStream_t
 
 
+def resample_supported(rate):
+    """True if the device converter takes this sampling rate (peaq_resample_supported)"""
+    return bool(load_library().peaq_resample_supported(int(rate)))
+
+
+def resample_plan(rate):
+    """peaq_resample_plan_info as a dict: what the device converter does for `rate` (host arithmetic, no GPU)"""
+    pl = ResamplePlan()
+    _check(load_library().peaq_resample_plan_info(int(rate), C.byref(pl)))
+    return {k: getattr(pl, k) for k, _ in ResamplePlan._fields_}
+
+
+def resampled_length(n, rate):
+    """samples per channel at 48 kHz of n samples per channel at `rate` (peaq_resampled_length)"""
+    L = load_library()
+    v = L.peaq_resampled_length(int(n), int(rate))
+    if v == 0 and n and L.peaq_last_error():
+        raise PeaqError(L.peaq_last_error().decode())
+    return int(v)
+
+
+def resample(ctx, x, rate, n=None, out=None, stream=None):
+    """Converts x, a CUDA float32 tensor [n_pairs, n_samples, channels] sampled at `rate`, to 48 kHz on the device
+    (peaq_batch_resample).  n: optional per-pair lengths.  out: optional tensor [n_pairs, stride, channels] to write into
+    (samples past a pair's converted length keep what they held); without it a zero-filled one with an even stride is
+    made.  Returns (y, n_out): the 48 kHz tensor and the converted lengths (numpy uint32 [n_pairs])."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_n = None if n is None else np.ascontiguousarray(n, dtype=np.uint32)
+    if out is None:
+        longest = resampled_length(int(a_n.max()) if a_n is not None and len(a_n) else (stride if a_n is None else 0), rate)
+        o_stride = max(longest, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the converter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    n_out = np.zeros(n_pairs, dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_resample(ctx.h, channels, int(rate), n_pairs, C.c_void_p(x.data_ptr()), stride,
+                                     a_n.ctypes.data_as(u32p) if a_n is not None else None, stride,
+                                     C.c_void_p(out.data_ptr()), out.shape[1], n_out.ctypes.data_as(u32p),
+                                     _stream_ptr(stream)))
+    return out, n_out
+
+
+def _to_48k(ctx, ref, test, n_ref, n_test, rate, stream):
+    """both buffers of a batch at `rate` -> (ref, test, n_ref, n_test) at 48 kHz with one common stride"""
+    import torch
+    assert ref.shape == test.shape
+    n_pairs, stride, channels = ref.shape
+    if n_ref is None:
+        n_ref = n_test = np.full(n_pairs, stride, dtype=np.uint32)
+    longest = max([resampled_length(int(v), rate) for v in set(np.asarray(n_ref).tolist()) | set(np.asarray(n_test).tolist())] + [2])
+    with _torch_stream(stream):                        # filled, and given back to the allocator, in `stream`'s order
+        bufs = [torch.zeros((n_pairs, longest + (longest & 1), channels), dtype=torch.float32, device=ref.device)
+                for _ in (0, 1)]
+    _, o_ref = resample(ctx, ref, rate, n_ref, out=bufs[0], stream=stream)
+    _, o_test = resample(ctx, test, rate, n_test, out=bufs[1], stream=stream)
+    return bufs[0], bufs[1], o_ref, o_test
+
+
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
-              stream=None, sync=True):
+              stream=None, sync=True, rate=48000):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
     n_ref/n_test: optional per-pair lengths (samples per channel).
+    rate: sampling rate of ref/test; anything but 48000 is converted on the device first (resample).
     Returns a list of result dicts (sync=True) or the device result tensor."""
     import torch
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
     n_pairs, stride, channels = ref.shape
@@ -397,12 +489,15 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
 
 
 def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n_test=None, playback_level=92.0,
-                     stream=None, sync=True):
+                     stream=None, sync=True, rate=48000):
     """Readings every `interval` samples per channel through each pair (peaq_batch_run_trajectory): point k of pair p
     is what a session pushed the first min((k + 1) interval, n) samples of each signal reads, unflushed.
-    ref/test as for batch_run.  Returns (points, results): lists of result dicts, points[p][k], (sync=True) or the
-    device tensors [n_pairs, n_points, 16] and [n_pairs, 16]."""
+    ref/test and rate as for batch_run; `interval` counts samples at 48 kHz whatever the rate.  Returns
+    (points, results): lists of result dicts, points[p][k], (sync=True) or the device tensors [n_pairs, n_points, 16]
+    and [n_pairs, 16]."""
     import torch
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
     n_pairs, stride, channels = ref.shape
@@ -428,13 +523,23 @@ def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n
             [_result_dict(r, advanced) for r in results.cpu().numpy()])
 
 
-def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_level=92.0):
+def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_level=92.0, rate=48000):
     """peaq_run_pair_trajectory: one whole pair from host memory (numpy float32 [n, channels]);
-    returns (points, result) as result dicts"""
+    returns (points, result) as result dicts.  rate other than 48000: the pair is converted on the device first and
+    read through batch_trajectory (interval in 48 kHz samples)."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
+    if int(rate) != 48000:
+        import torch
+        n = max(len(ref), len(test), 1)
+        both = np.zeros((2, n, ch), dtype=np.float32)
+        both[0, :len(ref)], both[1, :len(test)] = ref, test
+        d = torch.from_numpy(both).cuda(ctx.device)
+        pts, res = batch_trajectory(ctx, advanced, d[0:1], d[1:2], interval, n_points, [len(ref)], [len(test)],
+                                    playback_level, rate=rate)
+        return pts[0], res[0]
     pts = np.zeros((max(int(n_points), 1), RESULT_DOUBLES))
     out = np.zeros(RESULT_DOUBLES)
     dp = C.POINTER(C.c_double)
@@ -445,13 +550,20 @@ def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_l
     return [_result_dict(r, bool(advanced)) for r in pts], _result_dict(out, bool(advanced))
 
 
-def run_pair(ctx, advanced, ref, test, playback_level=92.0):
-    """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]"""
+def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000):
+    """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
+    other than 48000 they are converted on the device first (peaq_run_pair_rate)"""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
+    if int(rate) != 48000:
+        _check(ctx.L.peaq_run_pair_rate(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),
+                                        ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                        test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+        return _result_dict(out, bool(advanced))
     _check(ctx.L.peaq_run_pair(ctx.h, int(bool(advanced)), ch, float(playback_level),
                                ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
                                test.ctypes.data_as(C.POINTER(C.c_float)), len(test),

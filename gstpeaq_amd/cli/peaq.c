@@ -21,6 +21,10 @@
  * in FP64 like the reference (the engine's default); PEAQ_AMD_FIR=f16x3 selects
  * the reduced-precision bank (held to 1e-6 in ODG/DI, include/peaq_amd.h).
  * --no-resample refuses files at other rates instead.
+ * --device-resample hands files at another rate to the engine as they are (peaq_run_pair_rate): the same converter
+ * as a kernel, for both files at once; rates the device does not take, two files at different rates, and the modes
+ * that work on 48 kHz samples in host memory (--interval, PEAQ_AMD_CLI_STREAM, PEAQ_AMD_CLI_DUMP) still go through
+ * resample_to_48k, with a note on stderr.
  * --interval=SECONDS also prints, before those two lines, one line per reading taken every SECONDS of the (resampled)
  * signals, "Time %.3f s: ODG %.3f, DI %.3f" -- what the element's odg / di properties read at that point of the stream
  * (gstpeaq.c:484-497; peaq_run_pair_trajectory).
@@ -258,13 +262,16 @@ usage (const char *prog)
       "  --basic       use basic version (default)\n"
       "  --level=DB    playback level in dB SPL of a full-scale sine (default 92)\n"
       "  --no-resample refuse files that are not sampled at 48 kHz instead of converting them\n"
+      "  --device-resample convert files at other rates on the GPU instead of on the host\n"
+      "                (the plain one-call mode only: not with --interval; both files at one rate)\n"
       "  --interval=S  also print ODG and DI read every S seconds through the files\n", prog);
 }
 
 int
 main (int argc, char **argv)
 {
-  int advanced = 0, i, nfiles = 0, rc, allow_resample = 1;
+  int advanced = 0, i, nfiles = 0, rc, allow_resample = 1, device_resample = 0;
+  uint32_t device_rate = 0;     /* != 0: both files stay at this rate, peaq_run_pair_rate converts them */
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   wav_t ref, test;
@@ -282,6 +289,8 @@ main (int argc, char **argv)
       level = atof (argv[i] + 8);
     else if (!strcmp (argv[i], "--no-resample"))
       allow_resample = 0;
+    else if (!strcmp (argv[i], "--device-resample"))
+      device_resample = 1;
     else if (!strncmp (argv[i], "--interval=", 11)) {
       char *end;
       interval_s = strtod (argv[i] + 11, &end);
@@ -315,7 +324,18 @@ main (int argc, char **argv)
       fprintf (stderr, "Error: both files must be sampled at 48 kHz (got %d and %d Hz)\n", ref.rate, test.rate);
       return 2;
     }
-    if ((ref.rate != 48000 && resample_to_48k (&ref)) || (test.rate != 48000 && resample_to_48k (&test))) {
+    /* the device converter takes one rate for both signals; readings at intervals, the streaming path and the dump
+     * hook work on 48 kHz samples in host memory */
+    if (device_resample && !(interval_s > 0.) && !getenv ("PEAQ_AMD_CLI_STREAM") && !getenv ("PEAQ_AMD_CLI_DUMP")) {
+      if (ref.rate != test.rate)
+        fprintf (stderr, "Note: files at different rates (%d and %d Hz): converting on the host\n", ref.rate, test.rate);
+      else if (!peaq_resample_supported ((uint32_t) ref.rate))
+        fprintf (stderr, "Note: the device converter does not take %d Hz: converting on the host\n", ref.rate);
+      else
+        device_rate = (uint32_t) ref.rate;
+    } else if (device_resample)
+      fprintf (stderr, "Note: --device-resample does not apply to this mode: converting on the host\n");
+    if (!device_rate && ((ref.rate != 48000 && resample_to_48k (&ref)) || (test.rate != 48000 && resample_to_48k (&test)))) {
       fprintf (stderr, "Error: out of memory while resampling\n");
       return 2;
     }
@@ -380,8 +400,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (peaq_run_pair (ctx, advanced, ref.channels, level, ref.samples, ref.frames, test.samples, test.frames, &r) !=
-        PEAQ_OK) {
+    if ((device_rate ? peaq_run_pair_rate (ctx, advanced, ref.channels, level, device_rate, ref.samples, ref.frames,
+                test.samples, test.frames, &r)
+            : peaq_run_pair (ctx, advanced, ref.channels, level, ref.samples, ref.frames, test.samples, test.frames,
+                &r)) != PEAQ_OK) {
       printf ("Error: %s\n", peaq_last_error ());
       return 2;
     }

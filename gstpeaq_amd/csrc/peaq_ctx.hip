@@ -168,6 +168,7 @@ extern "C" void peaq_ctx_destroy(peaq_ctx* c) {
   c->counts.release();
   c->clk.release();
   c->snaps.release();
+  resample_release(c);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->batch_begin) (void)hipEventDestroy(c->batch_begin);
   if (c->batch_end) (void)hipEventDestroy(c->batch_end);

@@ -4,6 +4,7 @@
 // peaq_frontend.hip / peaq_backend.hip / peaq_fb.hip / peaq_synth.hip.
 //   peaq_ctx.hip      errors, version, framing, context, settings, calibration
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
+//   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element)
 //   peaq_broker.hip   live-pipeline broker (many sessions, one launch per tick), one or several devices
@@ -144,6 +145,7 @@ struct peaq_ctx {
   unsigned long long* d_prof = nullptr;   // -DPEAQ_FE_PROFILE builds only
   int fir_fp64 = 1;                       // advanced version: arithmetic of the FIR bank (PEAQ_FIR_*; default the reference's FP64)
   peaq::Settings settings;                      // the reference's settings.h switches (peaq_ctx_set_settings)
+  struct RsState* rs = nullptr;           // rate converter: tap tables per rate, length scratch (peaq_resample.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -154,6 +156,9 @@ struct peaq_ctx {
     return event_pool[events_used++];
   }
 };
+
+// frees what peaq_batch_resample has cached in the context (peaq_resample.hip); the device is idle
+void resample_release(peaq_ctx* c);
 
 // ---- batch driver pieces used elsewhere (peaq_batch.hip) --------------------------------------------------
 unsigned fb_blocks_per_chunk(int n_pairs, int channels, uint32_t max_blocks);

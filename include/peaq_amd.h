@@ -305,6 +305,66 @@ int peaq_run_pair_trajectory (peaq_ctx *ctx, int advanced, int channels, double 
                               const float *ref, size_t n_ref, const float *test, size_t n_test,
                               uint32_t interval, int n_points, peaq_result *points /* host */, peaq_result *out);
 
+/* ---- sample-rate conversion to 48 kHz on the device -----------------------------
+ * The ear models are defined for 48 kHz only (earmodel.c:43) and every entry point above takes 48 kHz.  The
+ * reference's CLI puts `audioresample` in front of the element (peaq.c:154-209); gstpeaq_amd/cli/peaq.c stands in for
+ * it with a Kaiser-windowed sinc interpolator (resample_to_48k) whose parameters are the measured ones of that
+ * `audioresample`.  peaq_batch_resample is the same converter for whole batches resident in device memory: same
+ * filter, same tap table (built on the host in double, once per rate and context), same output length, samples in
+ * FP32, taps and accumulation in FP64 in the tap order j = 0 .. 2K-1, one rounding to FP32 at the end -- the CLI's
+ * samples up to the rounding of the FP64 sum (the device contracts multiply and add; |difference| <= one FP32 ulp).
+ *
+ *   g = gcd (48000, rate), L = 48000 / g, M = rate / g.  Output sample m sits at input position
+ *   t_m = m M / L - 1/8: a delay of one eighth of an INPUT sample, audioresample's.
+ *   y[m] = sum_j h_p[j] x[n_first + j], j = 0 .. 2K-1, p = (m M) mod L,
+ *   n_first = (m M) div L + floor (p / L - 1/8) - K + 1; taps outside [0, n) contribute nothing.
+ *   rate < 48000: cutoff 0.94 x 0.5, half width 32.15, Kaiser beta 8.49; rate > 48000: cutoff
+ *   0.921 x 0.5 x 48000 / rate, half width 4 ceil (64 rate / 48000 / 8), beta 8.41; K = ceil (half width) + 1.
+ *   Length: n samples per channel become n ? floor ((n - 1) x 48000 / rate) + 1 : 0, evaluated in double as
+ *   the CLI does (the last output sample is the last one whose position does not pass the last input sample).
+ *
+ * Supported rates: 8000 <= rate <= 384000 with L <= 4096, 48000 itself excluded (nothing to convert: hand the
+ * buffers straight on) -- 8, 11.025, 16, 22.05, 24, 32, 44.1, 88.2, 96, 176.4 and 192 kHz among them.  Every other
+ * rate is PEAQ_ERR_ARG with a message that names it.  Non-finite input samples: the device evaluates a few
+ * zero-valued taps beside each filter's 2K (fewer than 4 ceil (rate / 48000) + 4), so an Inf or NaN reaches that many more
+ * output samples than in the CLI. */
+int      peaq_resample_supported (uint32_t rate);              /* 1 if peaq_batch_resample takes this rate, else 0 */
+/* Samples per channel at 48 kHz of n samples per channel at `rate` (any rate > 0, supported or not).  A length that
+ * does not fit uint32_t, or rate 0, returns 0 with peaq_last_error() set (the message is cleared on success). */
+uint32_t peaq_resampled_length   (uint64_t n, uint32_t rate);
+/* Converts one buffer of the batch layout -- interleaved F32 [pair][sample][channel], `in_stride` samples per channel
+ * between pairs, lengths n_in (host array of n_pairs entries; NULL = n_uniform each) -- into d_out of the same layout
+ * with `out_stride` samples between pairs.  n_out (host, may be NULL) receives each pair's converted length, valid
+ * on return.  Samples of d_out between a pair's converted length and out_stride are left untouched.  out_stride
+ * smaller than the longest converted signal, a pair longer than in_stride, a length that does not fit uint32_t,
+ * channels other than 1 or 2, more than 65535 pairs, NULL buffers and unsupported rates are PEAQ_ERR_ARG.  Enqueues
+ * on `stream` and returns, like peaq_batch_run, and synchronises nothing: per-pair lengths travel through one of four
+ * pinned staging slots and are copied on `stream` itself; only the fifth call in a row with lengths waits, for the
+ * FIRST one's kernel.  (The first call for a rate on a context builds and uploads that rate's table, synchronously.)
+ * Call it for the reference and for the test buffer and hand the results and n_out to peaq_batch_run /
+ * peaq_batch_run_trajectory (whose `interval` stays in 48 kHz samples). */
+int peaq_batch_resample (peaq_ctx *ctx, int channels, uint32_t rate, int n_pairs,
+                         const float *d_in, size_t in_stride, const uint32_t *n_in, uint32_t n_uniform,
+                         float *d_out, size_t out_stride, uint32_t *n_out /* host, may be NULL */, void *stream);
+/* What the device converter does for `rate`, computed on the host (no device needed): the reduced ratio, the filter
+ * length, which kernel takes the rate and what its workgroups need -- what tests/test_resample_budgets.py holds to
+ * the ceilings of DESIGN.md 10, and what tools/resample_cost.py counts work with. */
+typedef struct peaq_resample_plan {
+  uint32_t L, M;              /* 48000 / g, rate / g */
+  uint32_t taps;              /* 2K */
+  int      tiled;             /* 1: resample_tile_kernel (both tiles fit a CU's LDS), 0: resample_any_kernel */
+  uint32_t period_out, period_in;  /* tiled: L' = c L outputs and M' = c M inputs per lane */
+  uint32_t zero_taps;         /* tiled: taps evaluated beside the 2K per output, all zero (union of four phases' windows) */
+  uint32_t lds_bytes;         /* tiled: dynamic LDS of one workgroup (512 threads) */
+  uint64_t table_bytes;       /* the tap table in device memory */
+  double   max_sum_abs_taps;  /* max over the phases of sum_j |h_p[j]|: the factor in the bound of the sum's rounding error */
+} peaq_resample_plan;
+int peaq_resample_plan_info (uint32_t rate, peaq_resample_plan *out);
+/* peaq_run_pair for host signals sampled at `rate`: upload, convert both on the device, the one-pair path.
+ * rate == 48000 is peaq_run_pair itself. */
+int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                        const float *ref, size_t n_ref, const float *test, size_t n_test, peaq_result *out);
+
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
  * multiply-adds per wave, <= 0: about 70 ms) on the context's device -- alone: it waits for everything this PROCESS has
