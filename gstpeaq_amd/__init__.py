@@ -7,10 +7,10 @@ is only the thin ctypes binding used by the tests and by bench.py; PyTorch is
 used for device memory and streams, nothing else.  There is no CPU fallback:
 every entry point raises if the HIP library or the GPU is missing.
 """
-from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_trajectory, build_library, debug_backend, debug_frontend, debug_filterbank, run_pair,  # noqa: F401
+from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_trajectory, build_library, debug_backend, debug_frontend, debug_filterbank, debug_wave, debug_common_tables, run_pair,  # noqa: F401
                    run_pair_trajectory, library_path, load_library, synth_fill, resample, resample_plan, resampled_length, resample_supported,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
-__all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "run_pair",
+__all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
            "run_pair_trajectory", "library_path", "load_library", "synth_fill", "resample", "resample_plan", "resampled_length",
            "resample_supported", "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

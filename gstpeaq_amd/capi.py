@@ -147,6 +147,9 @@ def load_library():
     L.peaq_debug_frontend.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_uint32, C.c_uint32,
                                       C.c_int, dp]
     L.peaq_debug_filterbank.argtypes = [vp, C.c_int, C.c_double, vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, dp]
+    if hasattr(L, "peaq_debug_wave"):                # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_debug_wave.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, dp, C.c_int, dp, C.c_int, dp]
+        L.peaq_debug_common_tables.argtypes = [dp, dp]
     ip = C.POINTER(C.c_int)
     L.peaq_broker_create.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(vp)]
     L.peaq_broker_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.c_int,
@@ -666,3 +669,37 @@ def debug_backend_advanced(ctx, fb_records, fft_records):
                                              ob.ctypes.data_as(dp), of.ctypes.data_as(dp), res.ctypes.data_as(dp)))
     return (dict(zip(ADVANCED_DEBUG_BLOCK, np.moveaxis(ob[:, :, :7], 2, 0))),
             dict(zip(ADVANCED_DEBUG_FRAME, np.moveaxis(of, 2, 0))), _result_dict(res, True))
+
+
+# planes in / out of the ops of peaq_debug_wave (include/peaq_amd.h); every other op is 1 -> 1
+WAVE_OP_PLANES = {"div_fast": (2, 1), "pow_pos": (2, 1), "pow_tab": (2, 1), "pow_logtab": (2, 1),
+                  "log_nonneg_n5": (5, 5), "exp_fast_n5": (5, 5), "wave_sum2": (2, 2), "wave_sum4": (4, 4),
+                  "rows_transpose4": (4, 4), "wave_prefix_geometric_z": (3, 3), "dft4": (8, 8), "dft8": (16, 16),
+                  "dft16": (32, 32)}
+
+
+def debug_wave(ctx, op, inputs, params=()):
+    """The primitives of csrc/peaq_wave.h on their own (peaq_debug_wave, include/peaq_amd.h).
+    inputs: float64 [n] or [planes, n]; params: the op's scalar parameters (m of the geometric scans).
+    -> np float64 [planes_out, n] ([n] for an op with one output plane); for the
+    cross-lane ops every 64 consecutive elements are one wave and the output is what each lane holds."""
+    x = np.ascontiguousarray(inputs, dtype=np.float64)
+    flat = x.ndim == 1
+    if flat:
+        x = x[None, :]
+    assert x.ndim == 2
+    planes_out = WAVE_OP_PLANES.get(op, (1, 1))[1]
+    out = np.zeros((planes_out, x.shape[1]))
+    par = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    dp = C.POINTER(C.c_double)
+    _check(ctx.L.peaq_debug_wave(ctx.h, op.encode(), x.shape[1], x.shape[0], x.ctypes.data_as(dp), len(par),
+                                 par.ctypes.data_as(dp) if len(par) else None, planes_out, out.ctypes.data_as(dp)))
+    return out[0] if planes_out == 1 else out
+
+
+def debug_common_tables():
+    """-> (log_tab [130, 2], exp_tab [64]): the tables of log_tab / exp_tab as every context uploads them (host only)"""
+    lt, et = np.zeros((130, 2)), np.zeros(64)
+    dp = C.POINTER(C.c_double)
+    _check(load_library().peaq_debug_common_tables(lt.ctypes.data_as(dp), et.ctypes.data_as(dp)))
+    return lt, et

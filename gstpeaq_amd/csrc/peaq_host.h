@@ -6,6 +6,7 @@
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
 //   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests
+//   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element)
 //   peaq_broker.hip   live-pipeline broker (many sessions, one launch per tick), one or several devices
 #pragma once

@@ -426,15 +426,17 @@ void build_common_tables(CommonTables& c) {
 
 void fill_log_tab(double (*tab)[2]) {                 // log_tab (peaq_device.h), 130 entries
   for (int i = 0; i < 130; ++i) {
-    const long double centre = 1.0L + i / 128.0L, ln2 = 0.693147180559945309417232121458176568L;
+    const long double centre = 1.0L + i / 128.0L;
     tab[i][0] = (double)(2.0L / centre);
-    // the centre that the ROUNDED reciprocal stands for: r = fma(m, [i][0], -1) is then exact with respect to it,
-    // and the only rounding left in ln m = log1p(r) + ln C - ln 2 is that of the entry itself
-    const long double c_eff = 2.0L / (long double)tab[i][0];
-    // the lower bins count one binade less in e instead of carrying - ln 2
-    tab[i][1] = (double)(i < kLogTabFold ? std::log(c_eff) : std::log(c_eff) - ln2);
+    // the centre that the ROUNDED reciprocal stands for, C = 2 / [i][0]: r = fma(m, [i][0], -1) is then exact with
+    // respect to it, and the only rounding left in ln m = log1p(r) + ln C - ln 2 is that of the entry itself.
+    // ln C - ln 2 = - ln [i][0], the logarithm of a number that is exact here; the lower bins count one binade less
+    // in e instead of carrying - ln 2: ln C = - ln([i][0] / 2).  (Formed as ln(2 / [i][0]) - ln 2 in long double, the
+    // quotient's rounding and the cancellation against ln 2 put the entries of the uppermost bins up to 0.51 ulp off.)
+    const long double t0 = tab[i][0];
+    tab[i][1] = (double)-std::log(i < kLogTabFold ? 0.5L * t0 : t0);
   }
-  tab[128][1] = 0.;                                   // ln 2 - ln 2 (the long-double difference is 0 anyway)
+  tab[0][1] = tab[128][1] = 0.;                       // the bins whose centre is 1: + 0, not the - 0 of - ln 1
 }
 
 // Self-check of the FP64 engine's filter-bank tables on the host (no device involved; tests/test_capi_host.py):

@@ -276,18 +276,6 @@ __device__ __forceinline__ double wave_reduce_d(double v, OP op) {
   swap_halves_d<false>(v, a, b);
   return op(a, b);
 }
-template <typename OP>
-__device__ __forceinline__ int wave_reduce_i(int v, OP op) {
-  v = op(v, dpp_i<kDppXor1>(v));
-  v = op(v, dpp_i<kDppXor2>(v));
-  v = op(v, dpp_i<kDppHalfMirror>(v));
-  v = op(v, dpp_i<kDppMirror>(v));
-  int a, b;
-  swap_halves_i<true>(v, a, b);
-  v = op(a, b);
-  swap_halves_i<false>(v, a, b);
-  return op(a, b);
-}
 __device__ __forceinline__ double wave_sum(double v) {
   return wave_reduce_d(v, [](double x, double y) { return x + y; });
 }
@@ -334,15 +322,6 @@ __device__ __forceinline__ void wave_sum4(double a, double b, double c, double d
   sc = lane_value_d(v, 16);
   sb = lane_value_d(v, 32);
   sd = lane_value_d(v, 48);
-}
-__device__ __forceinline__ double wave_prod(double v) {
-  return wave_reduce_d(v, [](double x, double y) { return x * y; });
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-  return wave_reduce_i(v, [](int x, int y) { return max(x, y); });
-}
-__device__ __forceinline__ int wave_or_i(int v) {
-  return wave_reduce_i(v, [](int x, int y) { return x | y; });
 }
 
 // ---- logarithm and exponential for this model ------------------------------------------
@@ -420,7 +399,11 @@ template <bool SK = PEAQ_SK_DEFAULT> __device__ __forceinline__ double log_pos(d
 // fraction of 2 m, r = 2 m / C - 1 with |r| <= 2^-8, log1p(r) = r - r^2/2 + ... - r^6/6 (truncation 2^-56 / 7), and
 // the power of two joins the entry in one multiply-add (relative error of that product: ln 2's, 1e-17).
 // 17 vector instructions and one 16-byte LDS read against 31 of log_pos; <= 2 ulp like log_pos, <= 5 ulp for
-// arguments around 1 (their bins have the centre 1: r = x - 1 exactly, ln 1 = 0 exactly); tools/check_math.hip.
+// arguments in [1, 1 + 3/256), bins 0 and 1: in bin 0 r = x - 1 exactly and ln 1 = 0 exactly, but the result is
+// log1p(r) alone, with the polynomial's own few ulp; in the lower half of bin 1 it is smaller than the entry ln C
+// it is formed from, whose rounding then weighs double (tools/check_math.hip, against OCML; against the exact value
+// tests/test_gpu_wave_primitives.py measures 1.97 ulp outside these two bins -- the bins below 1 included -- and
+// 5.04 inside).
 // Measured (same box, 4096 pairs): +2.3 % frame-pairs/s for the basic version with the front end's and the back
 // end's logarithms from the table -- the vector ALU is what the step is bound by, the LDS reads cost less.
 __device__ __forceinline__ double log_tab(double x, const double* __restrict__ tab) {
@@ -588,6 +571,9 @@ __device__ __forceinline__ double div_fast(double a, double b) {
 
 // sqrt(x) for finite x >= 0 (0 -> 0), <= 1 ulp: reciprocal square root, ONE coupled Newton step
 // on (sqrt, 1/(2 sqrt)), one residual correction (tools/check_math.hip).  11 instructions instead of 23.
+// (No scaling: below x = 2^-1000 the residual x - g^2 drops under the subnormal spacing and its rounding, up to
+// 2^-1075, comes back as 2^-1023 / x ulp of the result -- <= 1 + 2^-1023 / x ulp there, 9 ulp measured on subnormal
+// arguments.  What the kernels take roots of -- power spectra, excitations and their products -- is 0 or far above.)
 __device__ __forceinline__ double sqrt_pos(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;

@@ -465,6 +465,37 @@ int peaq_debug_backend_advanced (peaq_ctx *ctx, int channels, int n_blocks, cons
                                  int n_frames, const double *fft_records, double *out_blocks,
                                  double *out_frames, peaq_result *result);
 
+/* The primitives of csrc/peaq_wave.h on their own (tests/test_gpu_wave_primitives.py): the inline functions every
+ * kernel is made of -- logarithm, exponential, quotient and roots, the wave reductions and scans, the lane moves,
+ * the register DFTs -- called by one small kernel on host arrays.
+ *   in  [planes_in][n]   host memory, plane p at in + p n
+ *   out [planes_out][n]  likewise
+ * The arrays are padded with 0. to whole workgroups of four waves, so every wave runs with all 64 lanes active.
+ * Element-wise ops: out[i] = f(in[0][i] (, in[1][i])).  Cross-lane ops: every 64 consecutive elements are one wave
+ * (lane = i & 63) and out[i] is what lane i holds afterwards -- 64 values per wave also where all lanes agree.
+ * op (planes in -> out):
+ *   "log_pos" "log_pos_sk" "log_nonneg" "log_nonneg_sk" "log_tab" "log_tab_nonneg" "exp_fast" "exp_fast_sk" "exp_tab"
+ *   "sqrt_pos" "rsqrt_pos" (1 -> 1; _sk: the instantiation with its constants in scalar registers),
+ *   "div_fast" (a, b), "pow_pos" (x, y), "pow_tab" = exp_tab(y log_tab(x)) and "pow_logtab" = exp_fast(y log_tab(x)),
+ *   the two forms the back ends raise to a power with (2 -> 1),
+ *   "log_nonneg_n5" "exp_fast_n5" (5 -> 5: plane k is element k of each lane's array of five),
+ *   "wave_sum" "wave_max" "wave_prefix_sum" "lane_below" "lane_above" "read_lane_0" "read_lane_63" (1 -> 1),
+ *   "wave_sum2" (2 -> 2), "wave_sum4" "rows_transpose4" (4 -> 4),
+ *   "wave_suffix_geometric" "wave_prefix_geometric" "wave_prefix_geometric_f32" (1 -> 1, params[0] = m),
+ *   "wave_prefix_geometric_z" (3 -> 3, params[0] = m: three scans in a row through the same pair of zero registers).
+ *   The prefix forms get m, m^2 .. m^16 by repeated squaring and the row weight m^((lane & 15) + 1) by squaring and
+ *   multiplying, as the filter bank's slope filter forms them (csrc/peaq_fb.hip); the FP32 form does the same in
+ *   FP32 from (float)m and rounds its data to FP32.
+ *   "dft4" "dft8" "dft16" (8, 16, 32 planes in and out: planes 2 k, 2 k + 1 are the real and imaginary part of x[k]).
+ * PEAQ_ERR_ARG (before any device is touched) for an unknown op, a plane or parameter count other than the op's, and
+ * NULL arguments. */
+int peaq_debug_wave (peaq_ctx *ctx, const char *op, size_t n, int planes_in, const double *in,
+                     int n_params, const double *params, int planes_out, double *out);
+
+/* Host only, no device: the tables log_tab ([130][2]: 2 / C, ln C [- ln 2] per bin) and exp_tab ([64]: 2^(j/64)) that
+ * every context uploads (csrc/peaq_device.h, CommonTables). */
+int peaq_debug_common_tables (double *log_tab /* [260] */, double *exp_tab /* [64] */);
+
 #ifdef __cplusplus
 }
 #endif

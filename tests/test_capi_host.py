@@ -132,3 +132,59 @@ def test_multi_device_broker_argument_checks(lib):
     lib.peaq_broker_stats_size.restype = C.c_size_t
     from gstpeaq_amd.capi import _BrokerStats
     assert lib.peaq_broker_stats_size() == C.sizeof(_BrokerStats)
+
+
+def test_log_and_exp_tables_against_mpmath(lib):
+    """What log_tab / exp_tab read (peaq_debug_common_tables = build_common_tables, no device): [i][0] is 2 / C rounded
+    to nearest, [i][1] within half an ulp of ln of the centre that ROUNDED reciprocal stands for (- ln 2 from
+    kLogTabFold = 54 on, where the power of two is counted in full), the entries of the bins whose centre is 1 exact,
+    exp_tab[j] within half an ulp of 2^(j/64)."""
+    import mpmath
+    import numpy as np
+    import gstpeaq_amd
+    mpmath.mp.prec = 200
+    lt, et = gstpeaq_amd.debug_common_tables()
+    mpf = mpmath.mpf
+
+    def ulps(got, exact):
+        return float(abs(mpf(float(got)) - exact) / mpf(float(np.spacing(abs(float(exact))))))
+
+    worst = 0.
+    for i in range(130):
+        assert lt[i, 0] == float(2 / (1 + mpf(i) / 128)), i
+        exact = mpmath.log(2 / mpf(float(lt[i, 0]))) - (mpmath.log(2) if i >= 54 else 0)
+        if i in (0, 128):
+            assert lt[i, 1] == 0. and exact == 0, i
+            continue
+        worst = max(worst, ulps(lt[i, 1], exact))
+        assert ulps(lt[i, 1], exact) <= 0.5, (i, lt[i, 1], ulps(lt[i, 1], exact))
+    assert lt[0, 0] == 2. and lt[128, 0] == 1.
+    for j in range(64):
+        exact = mpf(2) ** (mpf(j) / 64)
+        worst = max(worst, ulps(et[j], exact))
+        assert ulps(et[j], exact) <= 0.5, (j, et[j])
+    print("worst table entry:", worst, "ulp")
+
+
+def test_debug_wave_checks_its_arguments_before_any_device(lib):
+    """peaq_debug_wave: unknown op, NULL, wrong plane or parameter count are PEAQ_ERR_ARG with a message, context or not"""
+    import numpy as np
+    lib.peaq_last_error.restype = C.c_char_p
+    dp = C.POINTER(C.c_double)
+    x = np.zeros(4 * 64)
+    px = x.ctypes.data_as(dp)
+    m = (C.c_double * 1)(0.5)
+    f = lib.peaq_debug_wave
+    assert f(None, None, 64, 1, px, 0, None, 1, px) == -1 and b"NULL op" in lib.peaq_last_error()
+    assert f(None, b"wave_prod", 64, 1, px, 0, None, 1, px) == -1 and b"unknown op 'wave_prod'" in lib.peaq_last_error()
+    assert f(None, b"wave_sum2", 64, 1, px, 0, None, 2, px) == -1 and b"takes 2 planes" in lib.peaq_last_error()
+    assert f(None, b"wave_sum4", 64, 4, px, 0, None, 1, px) == -1 and b"returns 4" in lib.peaq_last_error()
+    assert f(None, b"dft16", 64, 16, px, 0, None, 16, px) == -1 and b"takes 32 planes" in lib.peaq_last_error()
+    assert f(None, b"wave_suffix_geometric", 64, 1, px, 0, None, 1, px) == -1 and b"1 parameters" in lib.peaq_last_error()
+    assert f(None, b"wave_suffix_geometric", 64, 1, px, 1, None, 1, px) == -1 and b"1 parameters" in lib.peaq_last_error()
+    assert f(None, b"log_tab", 64, 1, px, 1, m, 1, px) == -1 and b"0 parameters" in lib.peaq_last_error()
+    assert f(None, b"log_tab", 64, 1, px, 0, None, 1, px) == -1 and b"NULL argument" in lib.peaq_last_error()
+    assert lib.peaq_debug_common_tables(None, None) == -1 and b"NULL" in lib.peaq_last_error()
+    import gstpeaq_amd
+    from gstpeaq_amd.capi import WAVE_OP_PLANES
+    assert callable(gstpeaq_amd.debug_wave) and WAVE_OP_PLANES["dft16"] == (32, 32)

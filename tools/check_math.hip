@@ -5,6 +5,8 @@
 // (log_tab reads the engine's own table, built by peaq_tables.cpp)
 // prints the worst error in ulp over 2^24 arguments per function (log-uniform over the ranges the
 // model produces and beyond) and checks the special values.
+// The gate is tests/test_gpu_wave_primitives.py: every primitive of peaq_wave.h against exact references (not OCML),
+// on sweeps and on the structured edges, under pytest.  This tool stays as the larger on-device sweep.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
