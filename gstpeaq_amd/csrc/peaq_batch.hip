@@ -86,9 +86,8 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
     }
     HIP_TRY(c->fbstate.reserve((size_t)n_signals * sizeof(FbSignalState)));
     HIP_TRY(hipMemsetAsync(c->fbstate.p, 0, (size_t)n_signals * sizeof(FbSignalState), stream));
-    FbFrontArgs ff{};
-    ff.cfg = c->settings;
-    ff.fir_fp64 = c->fir_fp64;
+    const ModelSetup m{c, c->settings, 1, channels, level_db};
+    FbFrontArgs ff = m.fb_frontend();
     ff.ref = d_ref;
     ff.test = d_test;
     ff.pair_stride = pair_stride;
@@ -98,20 +97,11 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
     ff.n_blocks = d_nblocks;
     ff.n_blocks_uniform = max_blocks;
     ff.block_origin = 0;
-    ff.channels = channels;
-    ff.level_factor = fb_level_factor(level_db);
-    set_fir_scale(ff);
-    ff.bands = c->d_bands40;
-    ff.fb = c->d_fb;
     ff.fbstate = c->fbstate.as<FbSignalState>();
     ff.hp_row_stride = row_stride;
-    FbBackendArgs fbk{};
-    fbk.cfg = c->settings;
+    FbBackendArgs fbk = m.fb_backend(ff);
     fbk.n_blocks = d_nblocks;
     fbk.n_blocks_uniform = max_blocks;
-    fbk.channels = channels;
-    fbk.bands = c->d_bands40;
-  fbk.common = c->d_common;
     fbk.state = c->state.as<PairState>();
     // Three stages per chunk of blocks, each on its own stream: the high-pass filter (a few hundred
     // waves, latency bound), the filter bank (the bulk), the back end (one workgroup per pair).
@@ -193,7 +183,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
                            const TrajectoryOut* tr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2");
+  if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
   if (!d_ref || !d_test || (!d_results && !tr)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
@@ -264,13 +254,13 @@ static int run_pair_host(const char* who, peaq_ctx* c, int advanced, int channel
                          peaq_result* points, peaq_result* out) {
   const std::string w(who);
   if (!c || (!out && !points)) return fail(PEAQ_ERR_ARG, w + ": NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2");
+  if (int rc = check_channels(w, channels)) return rc;
   if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, w + ": NULL samples");
   if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, w + ": more than 2^32 samples");
   HIP_TRY(hipSetDevice(c->device));
   size_t stride = std::max<size_t>(std::max(n_ref, n_test), 2);
   stride += stride & 1;                              // 8-byte rows: the frame loads are dword pairs
-  TmpBuf d_ref, d_test, d_res, d_pts;
+  DevBuf d_ref, d_test, d_res, d_pts;
   const size_t bytes = stride * channels * sizeof(float);
   HIP_TRY(d_ref.reserve(bytes));
   HIP_TRY(d_test.reserve(bytes));
@@ -393,8 +383,8 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     return PEAQ_OK;
   };
 
-  FrontendArgs fa{};
-  fa.cfg = c->settings;
+  const ModelSetup m{c, c->settings, advanced ? 1 : 0, channels, level_db};
+  FrontendArgs fa = m.frontend();
   fa.ref = d_ref;
   fa.test = d_test;
   fa.pair_stride = pair_stride;
@@ -407,19 +397,9 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
   fa.frame_origin = 0;
   fa.off_ref = 0;
   fa.off_test = 0;
-  fa.channels = channels;
-  fa.level_factor = fft_level_factor(level_db);
-  fa.common = c->d_common;
-  fa.bands = advanced ? c->d_bands55 : c->d_bands109;    // gstpeaq.c:521-526
-  fa.prof = c->d_prof;
-  BackendArgs ba{};
-  ba.cfg = c->settings;
+  BackendArgs ba = m.backend(fa);
   ba.n_frames = d_nframes;
   ba.n_frames_uniform = max_frames;
-  ba.channels = channels;
-  ba.advanced = advanced ? 1 : 0;
-  ba.bands = fa.bands;
-  ba.common = c->d_common;
   ba.state = c->state.as<PairState>();
   HIP_TRY(c->clk.reserve(2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(c->clk.p, 0, 2 * sizeof(unsigned long long), stream));   // (the first back-end launch waits for this stream)
@@ -466,7 +446,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     if (!e0 || !e1 || !e2 || !e3) return fail(PEAQ_ERR_DEVICE, "hipEventCreate failed");
     if (back_done[chunk & 1]) HIP_TRY(hipStreamWaitEvent(stream, back_done[chunk & 1], 0));   // buffer free again
     HIP_TRY(hipEventRecord(e0, stream));
-    HIP_TRY(launch_frontend(advanced ? 55 : 109, fa, n_pairs, stream));
+    HIP_TRY(launch_frontend(m.fft_bands(), fa, n_pairs, stream));
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
@@ -551,7 +531,7 @@ extern "C" int peaq_batch_last_clock(peaq_ctx* c, double* shader_clock_mhz) {
 extern "C" int peaq_synth_fill(peaq_ctx* c, uint32_t seed0, int n_pairs, int channels, uint32_t n_samples,
                                size_t pair_stride, float* d_ref, float* d_test, void* stream) {
   if (!c || !d_ref || !d_test) return fail(PEAQ_ERR_ARG, "peaq_synth_fill: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_synth_fill: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_synth_fill", channels)) return rc;
   if (n_samples > pair_stride) return fail(PEAQ_ERR_ARG, "peaq_synth_fill: n_samples > pair_stride");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(launch_synth(seed0, n_pairs, channels, n_samples, pair_stride, d_ref, d_test,

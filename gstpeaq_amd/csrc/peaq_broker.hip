@@ -34,10 +34,7 @@ struct BrokerSlot {
   std::mutex mu;
   bool open = false;
   bool flush_requested = false, fft_flushed = false, fb_flushed = false;
-  PadFifo pad[2];
-  uint64_t fft_pos[2] = {0, 0};
-  uint64_t fb_pos[2] = {0, 0};
-  uint32_t frames_done = 0, blocks_done = 0, fb_prev_blocks = 0;
+  StreamFramer framer;              // the two pads' FIFOs and where the next frame / block starts
   double t_ready_us = -1.;          // when the oldest not yet launched frame / block became whole (-1: none waiting)
 };
 
@@ -82,12 +79,9 @@ struct BrokerStage {
     }
     return PEAQ_OK;
   }
-  void release() {
-    for (int p = 0; p < 2; ++p) {
+  ~BrokerStage() {
+    for (int p = 0; p < 2; ++p)
       if (h[p]) (void)hipHostFree(h[p]);
-      h[p] = nullptr;
-      d[p].release();
-    }
   }
 };
 
@@ -95,10 +89,8 @@ struct BrokerStage {
 // copied into the staging buffers afterwards (by the staging threads, several sessions at a time)
 struct BrokerJob {
   int sid = 0;
-  bool fft = false, fb = false;
-  unsigned fft_idx = 0, fb_idx = 0;
-  uint64_t fft_from[2] = {0, 0}, fft_n[2] = {0, 0};
-  uint64_t fb_from[2] = {0, 0}, fb_n[2] = {0, 0};
+  unsigned fft_idx = 0, fb_idx = 0;   // staging entries (launch pairs) of the two windows
+  StreamWindow fft, fb;               // count 0: none of that kind
 };
 
 // A few helper threads for the tick's one heavy host-side step, the copy of every session's new samples
@@ -213,6 +205,8 @@ struct peaq_broker {
   std::vector<peaq_broker*> shards;
   std::vector<peaq_ctx*> shard_ctx;
   std::vector<int> shard_open;      // open sessions per shard (guarded by tick_mu)
+
+  ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
 };
 
 static inline bool broker_is_multi(const peaq_broker* b) { return b && !b->shards.empty(); }
@@ -224,15 +218,12 @@ static inline peaq_broker* broker_shard_of(peaq_broker* b, int sid, int* local) 
   return b->shards[sid % n];
 }
 
-// copies nv[p] samples per pad from the slot's FIFOs at pos[] into staging entry `idx`
+// window w of the slot's stream into staging entry `idx`
 static void broker_stage_copy(const peaq_broker* b, const BrokerSlot& sl, const BrokerStage& st, unsigned idx,
-                              const uint64_t pos[2], const uint64_t nv[2]) {
-  const size_t stride = st.samples * b->channels;
-  for (int p = 0; p < 2; ++p) {
-    const PadFifo& f = sl.pad[p];
-    if (nv[p])
-      std::memcpy(st.h[p] + idx * stride, f.at(pos[p], b->channels), (size_t)nv[p] * b->channels * sizeof(float));
-  }
+                              const StreamWindow& w) {
+  const size_t off = idx * st.samples * b->channels;
+  float* const dst[2] = {st.h[0] + off, st.h[1] + off};
+  stage_window(sl.framer, w, dst);
 }
 
 // the previous tick's device work is complete: its device time is known now, and with it the latency of the
@@ -274,88 +265,43 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     if (!sl.open) continue;
     BrokerJob job;
     job.sid = sid;
-    // ---- FFT frames: do_processing, else the one zero-padded frame of do_flush -------------------
-    {
-      const uint64_t left[2] = {sl.pad[0].total - sl.fft_pos[0], sl.pad[1].total - sl.fft_pos[1]};
-      const uint64_t av = std::min(left[0], left[1]);
-      unsigned nf = 0;
-      uint64_t nv[2] = {0, 0}, adv[2] = {0, 0};
-      if (av >= (uint64_t)kFrame) {
-        nf = static_cast<unsigned>(std::min<uint64_t>((av - kFrame) / kHop + 1, kBrokerMaxFrames));
-        nv[0] = nv[1] = (uint64_t)(nf - 1) * kHop + kFrame;
-        adv[0] = adv[1] = (uint64_t)nf * kHop;
-      } else if (sl.flush_requested && !sl.fft_flushed) {
-        sl.fft_flushed = true;
-        if (left[0] || left[1]) {
-          nf = 1;
-          nv[0] = adv[0] = std::min<uint64_t>(left[0], kFrame);
-          nv[1] = adv[1] = std::min<uint64_t>(left[1], kFrame);
-        }
-      }
-      if (nf) {
-        job.fft = true;
-        job.fft_idx = active;
-        for (int p = 0; p < 2; ++p) {
-          job.fft_from[p] = sl.fft_pos[p];
-          job.fft_n[p] = nv[p];
-        }
-        m_nref[active] = static_cast<uint32_t>(nv[0]);
-        m_ntest[active] = static_cast<uint32_t>(nv[1]);
-        m_f0[active] = sl.frames_done;
-        m_nf[active] = nf;
-        m_slot[active] = static_cast<uint32_t>(sid);
-        sl.fft_pos[0] += adv[0];
-        sl.fft_pos[1] += adv[1];
-        sl.frames_done += nf;
-        frames += nf;
-        max_nf = std::max(max_nf, nf);
-        ++active;
-      }
+    // ---- at most one window per kind: whole units (do_processing), else, once, the zero-padded unit of
+    // do_flush.  The samples are copied further down: only the positions are taken here. ----------------
+    const bool flush_fft = sl.flush_requested && !sl.fft_flushed;
+    job.fft = sl.framer.take(kUnitFrame, kBrokerMaxFrames, flush_fft);
+    if (flush_fft && (job.fft.flush || !job.fft.count)) sl.fft_flushed = true;   // (no whole frame was left)
+    if (job.fft.count) {
+      job.fft_idx = active;
+      m_nref[active] = static_cast<uint32_t>(job.fft.valid[0]);
+      m_ntest[active] = static_cast<uint32_t>(job.fft.valid[1]);
+      m_f0[active] = job.fft.first;
+      m_nf[active] = job.fft.count;
+      m_slot[active] = static_cast<uint32_t>(sid);
+      frames += job.fft.count;
+      max_nf = std::max(max_nf, job.fft.count);
+      ++active;
     }
-    // ---- filter-bank blocks (advanced): whole blocks, else the zero-padded block of the flush ----
     if (b->advanced) {
-      const uint64_t left[2] = {sl.pad[0].total - sl.fb_pos[0], sl.pad[1].total - sl.fb_pos[1]};
-      const uint64_t av = std::min(left[0], left[1]);
-      unsigned nb = 0;
-      uint64_t nv[2] = {0, 0};
-      if (av >= (uint64_t)kFbFrame) {
-        nb = static_cast<unsigned>(std::min<uint64_t>(av / kFbFrame, kBrokerMaxBlocks));
-        nv[0] = nv[1] = (uint64_t)nb * kFbFrame;
-      } else if (sl.flush_requested && !sl.fb_flushed) {
-        sl.fb_flushed = true;
-        if (left[0] || left[1]) {
-          nb = 1;
-          nv[0] = std::min<uint64_t>(left[0], kFbFrame);
-          nv[1] = std::min<uint64_t>(left[1], kFbFrame);
-        }
-      }
-      if (nb) {
-        job.fb = true;
+      const bool flush_fb = sl.flush_requested && !sl.fb_flushed;
+      job.fb = sl.framer.take(kUnitBlock, kBrokerMaxBlocks, flush_fb);
+      if (flush_fb && (job.fb.flush || !job.fb.count)) sl.fb_flushed = true;
+      if (job.fb.count) {
         job.fb_idx = fb_active;
-        for (int p = 0; p < 2; ++p) {
-          job.fb_from[p] = sl.fb_pos[p];
-          job.fb_n[p] = nv[p];
-        }
-        m_fb_nref[fb_active] = static_cast<uint32_t>(nv[0]);
-        m_fb_ntest[fb_active] = static_cast<uint32_t>(nv[1]);
-        b->h_win[fb_active] = FbPairWindow{sl.blocks_done, nb, sl.fb_prev_blocks, static_cast<uint32_t>(sid)};
-        sl.fb_pos[0] += nv[0];
-        sl.fb_pos[1] += nv[1];
-        sl.blocks_done += nb;
-        sl.fb_prev_blocks = nb;
-        max_nb = std::max(max_nb, nb);
+        m_fb_nref[fb_active] = static_cast<uint32_t>(job.fb.valid[0]);
+        m_fb_ntest[fb_active] = static_cast<uint32_t>(job.fb.valid[1]);
+        b->h_win[fb_active] =
+            FbPairWindow{job.fb.first, job.fb.count, job.fb.prev_blocks, static_cast<uint32_t>(sid)};
+        max_nb = std::max(max_nb, job.fb.count);
         ++fb_active;
       }
     }
     if (sl.flush_requested && sl.fft_flushed && (!b->advanced || sl.fb_flushed))
       sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
-    if (job.fft || job.fb) {
+    if (job.fft.count || job.fb.count) {
       b->jobs.push_back(job);
       if (sl.t_ready_us >= 0.) b->parked_wait_us.push_back((float)(t_tick - sl.t_ready_us));
       // more whole units left behind (the per-tick cap)?  They have been waiting since now at the latest.
-      const uint64_t av = std::min(sl.pad[0].total - sl.fft_pos[0], sl.pad[1].total - sl.fft_pos[1]);
-      const uint64_t avb = b->advanced ? std::min(sl.pad[0].total - sl.fb_pos[0], sl.pad[1].total - sl.fb_pos[1]) : 0;
-      sl.t_ready_us = (av >= (uint64_t)kFrame || avb >= (uint64_t)kFbFrame || sl.flush_requested) ? t_tick : -1.;
+      sl.t_ready_us = (sl.framer.ready() || sl.flush_requested) ? t_tick : -1.;
     }
   }
   ++b->n_ticks;
@@ -367,23 +313,20 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     const BrokerJob& j = b->jobs[i];
     BrokerSlot& sl = *b->slots[j.sid];
     std::lock_guard<std::mutex> lock(sl.mu);
-    if (j.fft) broker_stage_copy(b, sl, b->fft, j.fft_idx, j.fft_from, j.fft_n);
-    if (j.fb) broker_stage_copy(b, sl, b->fbs, j.fb_idx, j.fb_from, j.fb_n);
-    for (int p = 0; p < 2; ++p) {
-      const uint64_t keep_from = b->advanced ? std::min(sl.fft_pos[p], sl.fb_pos[p]) : sl.fft_pos[p];
-      sl.pad[p].drop_until(keep_from, b->channels);
-    }
+    if (j.fft.count) broker_stage_copy(b, sl, b->fft, j.fft_idx, j.fft);
+    if (j.fb.count) broker_stage_copy(b, sl, b->fbs, j.fb_idx, j.fb);
+    sl.framer.trim();
   });
   HIP_TRY(hipEventRecord(b->t_begin, b->stream));
   HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, 7 * S * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
   const uint32_t* d_meta = b->d_meta.as<uint32_t>();
+  const ModelSetup m = b->model();
   if (active) {
     const size_t stride = b->fft.samples * b->channels;
     for (int p = 0; p < 2; ++p)
       HIP_TRY(hipMemcpyAsync(b->fft.d[p].p, b->fft.h[p], active * stride * sizeof(float), hipMemcpyHostToDevice,
                              b->stream));
-    FrontendArgs fa{};
-    fa.cfg = b->cfg;
+    FrontendArgs fa = m.frontend();
     fa.ref = b->fft.d[0].as<float>();
     fa.test = b->fft.d[1].as<float>();
     fa.pair_stride = b->fft.samples;
@@ -391,24 +334,12 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     fa.n_test = d_meta + S;
     fa.pair_frame0 = d_meta + 2 * S;
     fa.pair_nframes = d_meta + 3 * S;
-    fa.channels = b->channels;
     fa.frames_per_launch = max_nf;
-    fa.level_factor = fft_level_factor(b->level_db);
-    fa.common = c->d_common;
-    fa.bands = b->advanced ? c->d_bands55 : c->d_bands109;
     fa.records = b->records.as<double>();
-    HIP_TRY(launch_frontend(b->advanced ? 55 : 109, fa, active, b->stream));
-    BackendArgs ba{};
-    ba.cfg = b->cfg;
-    ba.records = fa.records;
+    HIP_TRY(launch_frontend(m.fft_bands(), fa, active, b->stream));
+    BackendArgs ba = m.backend(fa);
     ba.frames_per_launch = max_nf;
-    ba.channels = b->channels;
-    ba.advanced = b->advanced;
-    ba.bands = fa.bands;
-    ba.common = c->d_common;
     ba.state = b->state.as<PairState>();
-    ba.pair_frame0 = fa.pair_frame0;
-    ba.pair_nframes = fa.pair_nframes;
     ba.pair_slot = d_meta + 4 * S;
     HIP_TRY(launch_backend(ba, active, b->stream));
   }
@@ -418,35 +349,22 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
       HIP_TRY(hipMemcpyAsync(b->fbs.d[p].p, b->fbs.h[p], fb_active * stride * sizeof(float), hipMemcpyHostToDevice,
                              b->stream));
     HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, fb_active * sizeof(FbPairWindow), hipMemcpyHostToDevice, b->stream));
-    FbFrontArgs ff{};
-    ff.cfg = b->cfg;
-    ff.fir_fp64 = c->fir_fp64;
+    FbFrontArgs ff = m.fb_frontend();
     ff.ref = b->fbs.d[0].as<float>();
     ff.test = b->fbs.d[1].as<float>();
     ff.pair_stride = b->fbs.samples;
     ff.n_ref = d_meta + 5 * S;
     ff.n_test = d_meta + 6 * S;
-    ff.channels = b->channels;
     ff.blocks_per_launch = max_nb;
-    ff.level_factor = fb_level_factor(b->level_db);
-    set_fir_scale(ff);
-    ff.bands = c->d_bands40;
-    ff.fb = c->d_fb;
     ff.fbstate = b->fbstate.as<FbSignalState>();
     ff.hp_scratch = b->hp_rows.as<double>();
     ff.hp_row_stride = kBrokerRowStride;
     ff.records = b->fb_records.as<double>();
     ff.windows = b->d_win.as<FbPairWindow>();
     HIP_TRY(launch_fb_frontend(ff, fb_active, b->stream));
-    FbBackendArgs fbk{};
-    fbk.cfg = b->cfg;
-    fbk.records = ff.records;
+    FbBackendArgs fbk = m.fb_backend(ff);
     fbk.blocks_per_launch = max_nb;
-    fbk.channels = b->channels;
-    fbk.bands = c->d_bands40;
-  fbk.common = c->d_common;
     fbk.state = b->state.as<PairState>();
-    fbk.windows = ff.windows;
     HIP_TRY(launch_fb_backend(fbk, fb_active, b->stream));
   }
   HIP_TRY(hipEventRecord(b->t_end, b->stream));
@@ -484,9 +402,8 @@ extern "C" int peaq_broker_create(peaq_ctx* c, int advanced, int channels, doubl
                                   peaq_broker** out) {
   if (!c || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_create: NULL argument");
   *out = nullptr;
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_broker_create: channels must be 1 or 2");
-  if (!(level_db >= 0. && level_db <= 130.))
-    return fail(PEAQ_ERR_ARG, "peaq_broker_create: playback level outside 0..130 dB (gstpeaq.c:275-281)");
+  if (int rc = check_channels("peaq_broker_create", channels)) return rc;
+  if (int rc = check_level("peaq_broker_create", level_db)) return rc;
   if (max_sessions < 1 || max_sessions > 65536) return fail(PEAQ_ERR_ARG, "peaq_broker_create: max_sessions 1..65536");
   HIP_TRY(hipSetDevice(c->device));
   peaq_broker* b = new (std::nothrow) peaq_broker;
@@ -623,24 +540,14 @@ extern "C" void peaq_broker_destroy(peaq_broker* b) {
   (void)peaq_broker_stop(b);
   (void)hipSetDevice(b->ctx->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  b->fft.release();
-  b->fbs.release();
   if (b->h_meta) (void)hipHostFree(b->h_meta);
   if (b->h_win) (void)hipHostFree(b->h_win);
-  b->d_meta.release();
-  b->d_win.release();
-  b->records.release();
-  b->fb_records.release();
-  b->state.release();
-  b->fbstate.release();
-  b->hp_rows.release();
-  b->result.release();
   if (b->staged) (void)hipEventDestroy(b->staged);
   if (b->t_begin) (void)hipEventDestroy(b->t_begin);
   if (b->t_end) (void)hipEventDestroy(b->t_end);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   for (BrokerSlot* s : b->slots) delete s;
-  delete b;
+  delete b;                         // (the staging and device buffers go with it)
 }
 
 extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
@@ -681,10 +588,7 @@ extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
                              (size_t)b->channels * 2 * sizeof(FbSignalState), b->stream));
     sl.open = true;
     sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
-    sl.pad[0] = PadFifo();
-    sl.pad[1] = PadFifo();
-    sl.fft_pos[0] = sl.fft_pos[1] = sl.fb_pos[0] = sl.fb_pos[1] = 0;
-    sl.frames_done = sl.blocks_done = sl.fb_prev_blocks = 0;
+    sl.framer.reset(b->advanced, b->channels);
     sl.t_ready_us = -1.;
     *session_id = sid;
     return PEAQ_OK;
@@ -715,8 +619,7 @@ extern "C" int peaq_broker_close(peaq_broker* b, int session_id) {
   std::lock_guard<std::mutex> lock(sl->mu);
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_close: session is not open");
   sl->open = false;
-  sl->pad[0] = PadFifo();
-  sl->pad[1] = PadFifo();
+  sl->framer.reset(b->advanced, b->channels);
   return PEAQ_OK;
 }
 
@@ -735,25 +638,17 @@ extern "C" int peaq_broker_push(peaq_broker* b, int session_id, int pad, const f
   if (!data) return fail(PEAQ_ERR_ARG, "peaq_broker_push: data is NULL");
   auto backlog = [&]() {
     std::lock_guard<std::mutex> lock(sl->mu);
-    uint64_t r = std::min(sl->pad[0].total - sl->fft_pos[0], sl->pad[1].total - sl->fft_pos[1]);
-    if (b->advanced) r = std::max(r, std::min(sl->pad[0].total - sl->fb_pos[0], sl->pad[1].total - sl->fb_pos[1]));
-    return r;
+    return sl->framer.backlog();
   };
   {
     std::lock_guard<std::mutex> lock(sl->mu);
     if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_push: session is not open");
-    PadFifo& f = sl->pad[pad];
     try {
-      f.append(data, n * b->channels);
+      sl->framer.append(pad, data, n);
     } catch (const std::bad_alloc&) {
       return fail(PEAQ_ERR_NOMEM, "out of host memory");
     }
-    f.total += n;
-    if (sl->t_ready_us < 0.) {
-      const uint64_t av = std::min(sl->pad[0].total - sl->fft_pos[0], sl->pad[1].total - sl->fft_pos[1]);
-      const uint64_t avb = b->advanced ? std::min(sl->pad[0].total - sl->fb_pos[0], sl->pad[1].total - sl->fb_pos[1]) : 0;
-      if (av >= (uint64_t)kFrame || avb >= (uint64_t)kFbFrame) sl->t_ready_us = now_us();
-    }
+    if (sl->t_ready_us < 0. && sl->framer.ready()) sl->t_ready_us = now_us();
   }
   // back-pressure (the reference processes inside pad_chain, so its caller can never run ahead):
   // wait for the tick thread, or tick right here when there is none
@@ -813,15 +708,9 @@ extern "C" int peaq_broker_tick(peaq_broker* b, unsigned* n_active) {
 }
 
 // true while the session has whole frames / blocks (or a requested flush) not yet launched
-static bool broker_slot_busy(const peaq_broker* b, BrokerSlot* sl) {
+static bool broker_slot_busy(BrokerSlot* sl) {
   std::lock_guard<std::mutex> lock(sl->mu);
-  const uint64_t av = std::min(sl->pad[0].total - sl->fft_pos[0], sl->pad[1].total - sl->fft_pos[1]);
-  if (av >= (uint64_t)kFrame || sl->flush_requested) return true;
-  if (b->advanced) {
-    const uint64_t avb = std::min(sl->pad[0].total - sl->fb_pos[0], sl->pad[1].total - sl->fb_pos[1]);
-    if (avb >= (uint64_t)kFbFrame) return true;
-  }
-  return false;
+  return sl->framer.ready() || sl->flush_requested;
 }
 
 extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* out) {
@@ -838,7 +727,7 @@ extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* 
     if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_results: session is not open");
   }
   if (b->failed.load()) return broker_failed(b, "peaq_broker_results");
-  while (broker_slot_busy(b, sl)) {
+  while (broker_slot_busy(sl)) {
     const int rc = broker_tick_checked(b, nullptr);
     if (rc != PEAQ_OK) return rc;
   }

@@ -153,26 +153,15 @@ extern "C" void peaq_ctx_destroy(peaq_ctx* c) {
   (void)hipFree(c->d_bands40);
   (void)hipFree(c->d_fb);
   (void)hipFree(c->d_prof);
-  c->records.release();
-  c->records2.release();
   if (c->aux) (void)hipStreamDestroy(c->aux);
   if (c->aux2) (void)hipStreamDestroy(c->aux2);
   if (c->aux3) (void)hipStreamDestroy(c->aux3);
   if (c->aux4) (void)hipStreamDestroy(c->aux4);
-  c->fb_records2.release();
-  c->hp_scratch2.release();
-  c->fb_records.release();
-  c->state.release();
-  c->fbstate.release();
-  c->hp_scratch.release();
-  c->counts.release();
-  c->clk.release();
-  c->snaps.release();
   resample_release(c);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->batch_begin) (void)hipEventDestroy(c->batch_begin);
   if (c->batch_end) (void)hipEventDestroy(c->batch_end);
-  delete c;
+  delete c;                         // (the workspaces go with it)
 }
 
 extern "C" int peaq_ctx_device(const peaq_ctx* c) { return c ? c->device : -1; }
@@ -308,7 +297,7 @@ extern "C" int peaq_calibrate(peaq_ctx* c, int iterations, peaq_calibration* out
   int wall_khz = 100000;
   (void)hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, c->device);
   const int waves = prop.multiProcessorCount * 4;      // one per SIMD
-  TmpBuf sink, ticks;
+  DevBuf sink, ticks;
   HIP_TRY(sink.reserve((size_t)waves * 64 * sizeof(double)));
   HIP_TRY(ticks.reserve((size_t)waves * 6 * sizeof(unsigned long long)));
   // "The clock under a fixed load" means NOTHING else on the device: this context's batch, and whatever its sessions,

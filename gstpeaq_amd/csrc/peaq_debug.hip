@@ -12,13 +12,13 @@ extern "C" int peaq_debug_frontend(peaq_ctx* c, int bands, int channels, double 
                                    double* host_out) {
   if (!c || !d_ref || !d_test || !host_out) return fail(PEAQ_ERR_ARG, "peaq_debug_frontend: NULL argument");
   if (bands != 109 && bands != 55) return fail(PEAQ_ERR_ARG, "peaq_debug_frontend: bands must be 109 or 55");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_debug_frontend: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_debug_frontend", channels)) return rc;
   const uint32_t total = count_frames(n_ref, n_test, kFrame, kHop);
   if (n_frames < 0 || (uint32_t)n_frames > total) return fail(PEAQ_ERR_ARG, "peaq_debug_frontend: too many frames");
   if (n_frames == 0) return PEAQ_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)n_frames * channels * kRecDoubles * sizeof(double);
-  TmpBuf rec_buf, n_buf;
+  DevBuf rec_buf, n_buf;
   HIP_TRY(rec_buf.reserve(bytes));
   double* d_rec = rec_buf.as<double>();
   HIP_TRY(hipMemset(d_rec, 0, bytes));
@@ -26,8 +26,7 @@ extern "C" int peaq_debug_frontend(peaq_ctx* c, int bands, int channels, double 
   HIP_TRY(n_buf.reserve(sizeof h_n));
   uint32_t* d_n = n_buf.as<uint32_t>();
   HIP_TRY(hipMemcpy(d_n, h_n, sizeof h_n, hipMemcpyHostToDevice));
-  FrontendArgs fa{};
-  fa.cfg = c->settings;
+  FrontendArgs fa = ModelSetup{c, c->settings, bands == 55, channels, level_db}.frontend();
   fa.ref = d_ref;
   fa.test = d_test;
   fa.pair_stride = std::max(n_ref, n_test);
@@ -35,12 +34,8 @@ extern "C" int peaq_debug_frontend(peaq_ctx* c, int bands, int channels, double 
   fa.n_test = d_n + 1;
   fa.n_frames = nullptr;
   fa.n_frames_uniform = total;
-  fa.channels = channels;
   fa.frame0 = 0;
   fa.frames_per_launch = n_frames;
-  fa.level_factor = fft_level_factor(level_db);
-  fa.common = c->d_common;
-  fa.bands = bands == 109 ? c->d_bands109 : c->d_bands55;
   fa.records = d_rec;
   std::vector<double> h_rec((size_t)n_frames * channels * kRecDoubles);
   // one pair: launches of at most max_frames_per_launch(1) frames, the records of a launch follow the previous one's
@@ -76,7 +71,7 @@ extern "C" int peaq_debug_filterbank(peaq_ctx* c, int channels, double level_db,
                                      const float* d_test, uint32_t n_ref, uint32_t n_test, int n_blocks,
                                      int blocks_per_launch, double* host_out) {
   if (!c || !d_ref || !d_test || !host_out) return fail(PEAQ_ERR_ARG, "peaq_debug_filterbank: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_debug_filterbank: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_debug_filterbank", channels)) return rc;
   const uint32_t total = count_frames(n_ref, n_test, kFbFrame, kFbFrame);
   if (n_blocks < 0 || (uint32_t)n_blocks > total || blocks_per_launch < 1)
     return fail(PEAQ_ERR_ARG, "peaq_debug_filterbank: bad block counts");
@@ -84,25 +79,18 @@ extern "C" int peaq_debug_filterbank(peaq_ctx* c, int channels, double level_db,
   HIP_TRY(hipSetDevice(c->device));
   const unsigned n_signals = 2 * channels;
   const size_t row_stride = (size_t)kFbRing + (size_t)blocks_per_launch * kFbFrame;
-  TmpBuf rows, recs, st;
+  DevBuf rows, recs, st;
   HIP_TRY(rows.reserve(n_signals * row_stride * sizeof(double)));
   HIP_TRY(recs.reserve((size_t)blocks_per_launch * channels * kFbRecDoubles * sizeof(double)));
   HIP_TRY(st.reserve(n_signals * sizeof(FbSignalState)));
   HIP_TRY(hipMemset(st.p, 0, n_signals * sizeof(FbSignalState)));
-  FbFrontArgs ff{};
-  ff.cfg = c->settings;
-  ff.fir_fp64 = c->fir_fp64;
+  FbFrontArgs ff = ModelSetup{c, c->settings, 1, channels, level_db}.fb_frontend();
   ff.ref = d_ref;
   ff.test = d_test;
   ff.pair_stride = std::max(n_ref, n_test);
   ff.n_uniform_ref = n_ref;
   ff.n_uniform_test = n_test;
   ff.n_blocks_uniform = n_blocks;
-  ff.channels = channels;
-  ff.level_factor = fb_level_factor(level_db);
-  set_fir_scale(ff);
-  ff.bands = c->d_bands40;
-  ff.fb = c->d_fb;
   ff.fbstate = st.as<FbSignalState>();
   ff.hp_scratch = rows.as<double>();
   ff.hp_row_stride = row_stride;
@@ -127,6 +115,9 @@ extern "C" int peaq_debug_filterbank(peaq_ctx* c, int channels, double level_db,
   return PEAQ_OK;
 }
 
+// the back ends on their own take records, not samples: the playback level has gone into those already
+constexpr double kNoLevel = 92.;
+
 // test-facing layout (kPub*) -> the record the kernels exchange: root = (E norm)^(1/10); the E^0.3 vector of the
 // input is implied by E (the back end derives both from the root)
 static hipError_t upload_public_records(int bands, int channels, int n_frames, const double* host_records, void* d_recs) {
@@ -149,12 +140,12 @@ static hipError_t upload_public_records(int bands, int channels, int n_frames, c
 extern "C" int peaq_debug_backend(peaq_ctx* c, int channels, int n_frames, const double* host_records,
                                   double* host_out, peaq_result* result) {
   if (!c || !host_records || !host_out) return fail(PEAQ_ERR_ARG, "peaq_debug_backend: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_debug_backend: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_debug_backend", channels)) return rc;
   if (n_frames < 1) return fail(PEAQ_ERR_ARG, "peaq_debug_backend: n_frames < 1");
   HIP_TRY(hipSetDevice(c->device));
   const size_t rec_bytes = (size_t)n_frames * channels * kRecDoubles * sizeof(double);
   const size_t dbg_bytes = (size_t)n_frames * channels * kDbgDoubles * sizeof(double);
-  TmpBuf recs, dbg, st, res;
+  DevBuf recs, dbg, st, res;
   HIP_TRY(recs.reserve(rec_bytes));
   HIP_TRY(dbg.reserve(dbg_bytes));
   HIP_TRY(st.reserve(sizeof(PairState)));
@@ -162,16 +153,12 @@ extern "C" int peaq_debug_backend(peaq_ctx* c, int channels, int n_frames, const
   HIP_TRY(upload_public_records(109, channels, n_frames, host_records, recs.p));
   HIP_TRY(hipMemset(dbg.p, 0, dbg_bytes));
   HIP_TRY(launch_state_init(st.as<PairState>(), 0, 1, nullptr));
-  BackendArgs ba{};
-  ba.cfg = c->settings;
+  const ModelSetup m{c, c->settings, 0, channels, kNoLevel};
+  BackendArgs ba = m.backend(m.frontend());
   ba.records = recs.as<double>();
   ba.frame0 = 0;
   ba.frames_per_launch = n_frames;
   ba.n_frames_uniform = n_frames;
-  ba.channels = channels;
-  ba.advanced = 0;
-  ba.bands = c->d_bands109;
-  ba.common = c->d_common;
   ba.state = st.as<PairState>();
   ba.debug = dbg.as<double>();
   HIP_TRY(launch_backend(ba, 1, nullptr));
@@ -191,14 +178,14 @@ extern "C" int peaq_debug_backend_advanced(peaq_ctx* c, int channels, int n_bloc
                                            double* out_frames, peaq_result* result) {
   if (!c || !host_fb_records || !host_fft_records || !out_blocks || !out_frames)
     return fail(PEAQ_ERR_ARG, "peaq_debug_backend_advanced: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_debug_backend_advanced: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_debug_backend_advanced", channels)) return rc;
   if (n_blocks < 1 || n_frames < 1) return fail(PEAQ_ERR_ARG, "peaq_debug_backend_advanced: n_blocks, n_frames must be >= 1");
   HIP_TRY(hipSetDevice(c->device));
   const size_t fbrec_bytes = (size_t)n_blocks * channels * kFbRecDoubles * sizeof(double);
   const size_t fbdbg_bytes = (size_t)n_blocks * channels * kDbgFbDoubles * sizeof(double);
   const size_t rec_bytes = (size_t)n_frames * channels * kRecDoubles * sizeof(double);
   const size_t dbg_bytes = (size_t)n_frames * channels * kDbgDoubles * sizeof(double);
-  TmpBuf fbrecs, fbdbg, recs, dbg, st, res;
+  DevBuf fbrecs, fbdbg, recs, dbg, st, res;
   HIP_TRY(fbrecs.reserve(fbrec_bytes));
   HIP_TRY(fbdbg.reserve(fbdbg_bytes));
   HIP_TRY(recs.reserve(rec_bytes));
@@ -210,28 +197,20 @@ extern "C" int peaq_debug_backend_advanced(peaq_ctx* c, int channels, int n_bloc
   HIP_TRY(hipMemset(fbdbg.p, 0, fbdbg_bytes));
   HIP_TRY(hipMemset(dbg.p, 0, dbg_bytes));
   HIP_TRY(launch_state_init(st.as<PairState>(), 1, 1, nullptr));
-  BackendArgs ba{};
-  ba.cfg = c->settings;
+  const ModelSetup m{c, c->settings, 1, channels, kNoLevel};
+  BackendArgs ba = m.backend(m.frontend());
   ba.records = recs.as<double>();
   ba.frame0 = 0;
   ba.frames_per_launch = n_frames;
   ba.n_frames_uniform = n_frames;
-  ba.channels = channels;
-  ba.advanced = 1;
-  ba.bands = c->d_bands55;
-  ba.common = c->d_common;
   ba.state = st.as<PairState>();
   ba.debug = dbg.as<double>();
   HIP_TRY(launch_backend(ba, 1, nullptr));
-  FbBackendArgs fbk{};
-  fbk.cfg = c->settings;
+  FbBackendArgs fbk = m.fb_backend(m.fb_frontend());
   fbk.records = fbrecs.as<double>();
   fbk.block0 = 0;
   fbk.blocks_per_launch = n_blocks;
   fbk.n_blocks_uniform = n_blocks;
-  fbk.channels = channels;
-  fbk.common = c->d_common;
-  fbk.bands = c->d_bands40;
   fbk.state = st.as<PairState>();
   fbk.debug = fbdbg.as<double>();
   HIP_TRY(launch_fb_backend(fbk, 1, nullptr));
@@ -247,5 +226,38 @@ extern "C" int peaq_debug_backend_advanced(peaq_ctx* c, int channels, int n_bloc
     }
   }
   if (result) HIP_TRY(hipMemcpy(result, res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
+// Host only: a StreamFramer fed with sample counts alone, drained the way peaq_session_push / _flush drain theirs.
+extern "C" int peaq_debug_stream_plan(int advanced, unsigned max_frames, unsigned max_blocks, int drain_every_push,
+                                      size_t n_pushes, const int* pad, const uint64_t* n_samples, size_t max_windows,
+                                      uint64_t* windows, size_t* n_windows) {
+  if (!n_windows || (n_pushes && (!pad || !n_samples)) || (max_windows && !windows))
+    return fail(PEAQ_ERR_ARG, "peaq_debug_stream_plan: NULL argument");
+  if (max_frames < 1 || max_blocks < 1) return fail(PEAQ_ERR_ARG, "peaq_debug_stream_plan: a cap is 0");
+  for (size_t k = 0; k < n_pushes; ++k)
+    if (pad[k] < -1 || pad[k] > 1) return fail(PEAQ_ERR_ARG, "peaq_debug_stream_plan: pad must be 0 (ref), 1 (test) or -1 (flush)");
+  StreamFramer fr;
+  fr.reset(advanced != 0, 1);
+  size_t n = 0;
+  auto note = [&](StreamUnit kind, const StreamWindow& w) {
+    if (n < max_windows) {
+      uint64_t* o = windows + n * PEAQ_DEBUG_STREAM_WINDOW_FIELDS;
+      o[0] = kind;
+      o[1] = w.first;
+      o[2] = w.count;
+      o[3] = w.valid[0];
+      o[4] = w.valid[1];
+    }
+    ++n;
+    return (int)PEAQ_OK;
+  };
+  for (size_t k = 0; k < n_pushes; ++k) {
+    if (pad[k] >= 0) fr.append(pad[k], nullptr, n_samples[k]);
+    if (pad[k] < 0 || drain_every_push) (void)drain_stream(fr, max_frames, max_blocks, pad[k] < 0, note);
+  }
+  (void)drain_stream(fr, max_frames, max_blocks, true, note);
+  *n_windows = n;
   return PEAQ_OK;
 }

@@ -223,7 +223,7 @@ extern "C" int peaq_debug_wave(peaq_ctx* c, const char* op, size_t n, int planes
   if (n == 0) return PEAQ_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t n_pad = (n + kWgThreads - 1) / kWgThreads * kWgThreads;   // whole workgroups: every lane of every wave active
-  TmpBuf d_in, d_out;
+  DevBuf d_in, d_out;
   HIP_TRY(d_in.reserve((size_t)planes_in * n_pad * sizeof(double)));
   HIP_TRY(d_out.reserve((size_t)planes_out * n_pad * sizeof(double)));
   HIP_TRY(hipMemset(d_in.p, 0, (size_t)planes_in * n_pad * sizeof(double)));    // the padding reads 0.

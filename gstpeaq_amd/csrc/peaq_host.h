@@ -1,14 +1,15 @@
-// peaq_host.h -- what the host-side translation units behind include/peaq_amd.h share: the error convention, the
-// framing arithmetic, device buffers, the context, the host-side stand-in for a GstAdapter, and the pieces of the
-// batch driver that sessions, brokers and the stage-level entry points call.  Host code only; the kernels are in
-// peaq_frontend.hip / peaq_backend.hip / peaq_fb.hip / peaq_synth.hip.
+// peaq_host.h -- what the host-side translation units behind include/peaq_amd.h share: the error convention and the
+// argument checks every entry point repeats, the framing arithmetic, device buffers, the context, the model half of
+// the kernels' argument blocks (ModelSetup), and the stream framer (StreamFramer: the element's do_processing /
+// do_flush on the host-side stand-ins for its two GstAdapters) that sessions, the broker and peaq_debug_stream_plan
+// run.  Host code only; the kernels are in peaq_frontend.hip / peaq_backend.hip / peaq_fb.hip / peaq_synth.hip.
 //   peaq_ctx.hip      errors, version, framing, context, settings, calibration
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
 //   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
-//   peaq_debug.hip    stage-level entry points for the parity tests
+//   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
-//   peaq_session.hip  streaming sessions (one per `peaq` element)
-//   peaq_broker.hip   live-pipeline broker (many sessions, one launch per tick), one or several devices
+//   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
+//   peaq_broker.hip   live-pipeline broker (a StreamFramer per session, one launch per tick), one or several devices
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +66,16 @@ inline int fail(int code, const std::string& msg) {
                   std::string(#expr) + ": " + hipGetErrorString(e_));                                     \
   } while (0)
 
+// the two argument checks most entry points share (`who` names the entry point in the message)
+inline int check_channels(const std::string& who, int channels) {
+  return channels == 1 || channels == 2 ? PEAQ_OK : fail(PEAQ_ERR_ARG, who + ": channels must be 1 or 2");
+}
+inline int check_level(const std::string& who, double level_db) {
+  return level_db >= 0. && level_db <= 130.
+             ? PEAQ_OK
+             : fail(PEAQ_ERR_ARG, who + ": playback level outside 0..130 dB (gstpeaq.c:275-281)");
+}
+
 // ---------------------------------------------------------------------------
 // framing arithmetic
 // ---------------------------------------------------------------------------
@@ -79,11 +90,15 @@ inline uint32_t count_frames(uint64_t n_ref, uint64_t n_test, uint32_t frame, ui
 }
 
 // ---------------------------------------------------------------------------
-// growable device buffer
+// growable device buffer; frees itself (its owner selects the device and drains its streams first)
 // ---------------------------------------------------------------------------
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -108,11 +123,6 @@ struct DevBuf {
   }
   template <typename T>
   T* as() const { return static_cast<T*>(p); }
-};
-
-// a DevBuf that frees itself on every way out of a function (the debug entry points)
-struct TmpBuf : DevBuf {
-  ~TmpBuf() { release(); }
 };
 
 // ---------------------------------------------------------------------------
@@ -164,14 +174,69 @@ void resample_release(peaq_ctx* c);
 // ---- batch driver pieces used elsewhere (peaq_batch.hip) --------------------------------------------------
 unsigned fb_blocks_per_chunk(int n_pairs, int channels, uint32_t max_blocks);
 unsigned frames_per_chunk(int n_pairs, int channels, uint32_t max_frames);
-// split-FP16 FIR (FbFrontArgs.fir_fp64 == 2): the power of two that puts the filtered signal's full scale --
-// |x| = 1 times the playback-level factor -- between 2^10 and 2^11 of FP16's 65504 (30 dB of headroom for
-// samples beyond full scale and for the high-pass filter's overshoot)
-inline void set_fir_scale(peaq::FbFrontArgs& ff) {
-  const int e = 10 - std::ilogb(ff.level_factor);
-  ff.hf_xscale = std::ldexp(1., e);
-  ff.hf_xunscale = std::ldexp(1., -e);
-}
+
+// ---------------------------------------------------------------------------
+// The model half of the four kernel argument blocks: what follows from the context, the settings, the version, the
+// channel count and the playback level, whoever launches.  Geometry -- buffers, strides, counts, origins, windows,
+// launch index, state, debug and clock pointers -- is the caller's.
+// ---------------------------------------------------------------------------
+struct ModelSetup {
+  const peaq_ctx* ctx;
+  peaq::Settings cfg;
+  int advanced, channels;
+  double level_db;
+
+  int fft_bands() const { return advanced ? 55 : 109; }   // gstpeaq.c:521-526
+  peaq::FrontendArgs frontend() const {
+    peaq::FrontendArgs fa{};
+    fa.cfg = cfg;
+    fa.channels = channels;
+    fa.level_factor = peaq::fft_level_factor(level_db);
+    fa.common = ctx->d_common;
+    fa.bands = advanced ? ctx->d_bands55 : ctx->d_bands109;
+    fa.prof = ctx->d_prof;
+    return fa;
+  }
+  // the back end of the front end `fa`: its records, its bands and (broker launches) its per-pair frame windows
+  peaq::BackendArgs backend(const peaq::FrontendArgs& fa) const {
+    peaq::BackendArgs ba{};
+    ba.cfg = fa.cfg;
+    ba.channels = fa.channels;
+    ba.advanced = advanced;
+    ba.common = fa.common;
+    ba.bands = fa.bands;
+    ba.records = fa.records;
+    ba.pair_frame0 = fa.pair_frame0;
+    ba.pair_nframes = fa.pair_nframes;
+    return ba;
+  }
+  peaq::FbFrontArgs fb_frontend() const {
+    peaq::FbFrontArgs ff{};
+    ff.cfg = cfg;
+    ff.fir_fp64 = ctx->fir_fp64;
+    ff.channels = channels;
+    ff.level_factor = peaq::fb_level_factor(level_db);
+    // split-FP16 FIR (fir_fp64 == 2): the power of two that puts the filtered signal's full scale -- |x| = 1 times
+    // the playback-level factor -- between 2^10 and 2^11 of FP16's 65504 (30 dB of headroom for samples beyond full
+    // scale and for the high-pass filter's overshoot)
+    const int e = 10 - std::ilogb(ff.level_factor);
+    ff.hf_xscale = std::ldexp(1., e);
+    ff.hf_xunscale = std::ldexp(1., -e);
+    ff.bands = ctx->d_bands40;
+    ff.fb = ctx->d_fb;
+    return ff;
+  }
+  peaq::FbBackendArgs fb_backend(const peaq::FbFrontArgs& ff) const {
+    peaq::FbBackendArgs fbk{};
+    fbk.cfg = ff.cfg;
+    fbk.channels = ff.channels;
+    fbk.common = ctx->d_common;
+    fbk.bands = ff.bands;
+    fbk.records = ff.records;
+    fbk.windows = ff.windows;
+    return fbk;
+  }
+};
 
 constexpr unsigned kSessionMaxFrames = 64;   // FFT frames per launch of a session
 constexpr unsigned kSessionMaxBlocks = 120;  // filter-bank blocks per launch of a session
@@ -202,3 +267,117 @@ struct PadFifo {
     }
   }
 };
+
+// ---------------------------------------------------------------------------
+// The element's framing policy, do_processing / do_flush (gstpeaq.c:596-611, 716-745, 769-771), for one (ref, test)
+// stream: whole FFT frames of 2048 every 1024 while BOTH pads hold one, whole filter-bank blocks of 192 (advanced
+// version), and at a flush ONE zero-padded unit per kind from whatever is left on either pad.  Host only, no lock
+// and no device work: the owner (a session, a broker slot) holds its own lock around every call.
+// ---------------------------------------------------------------------------
+enum StreamUnit { kUnitFrame = 0, kUnitBlock = 1 };
+
+// one launch's worth of one kind of unit
+struct StreamWindow {
+  uint32_t first = 0, count = 0;    // index of the first unit and how many (0: nothing to launch)
+  uint32_t prev_blocks = 0;         // blocks: the count of the previous window (where the kernel's history tail sits)
+  bool flush = false;               // the zero-padded unit of the flush: nothing of this kind follows it
+  uint64_t pos[2] = {0, 0};         // stream sample the window starts at, per pad
+  uint64_t valid[2] = {0, 0};       // samples present from there, per pad (short of whole units only in the flush unit)
+};
+
+struct StreamFramer {
+  bool advanced = false;
+  int channels = 1;
+  PadFifo pad[2];
+  uint64_t pos[2][2] = {{0, 0}, {0, 0}};   // [kind][pad]: stream sample where the next unit starts
+  uint32_t done[2] = {0, 0};               // [kind]: units handed out so far
+  uint32_t prev_blocks = 0;
+
+  void reset(bool advanced_, int channels_) {
+    *this = StreamFramer();
+    advanced = advanced_;
+    channels = channels_;
+  }
+  // n samples (per channel) more on pad p; data == nullptr: counted but not stored (peaq_debug_stream_plan)
+  void append(int p, const float* data, size_t n) {
+    if (data) pad[p].append(data, n * channels);
+    pad[p].total += n;
+  }
+  uint64_t left(StreamUnit kind, int p) const { return pad[p].total - pos[kind][p]; }
+  // samples present on both pads and not yet framed: of one kind, and the larger of the kinds in use (what the
+  // broker's back-pressure counts)
+  uint64_t backlog(StreamUnit kind) const { return std::min(left(kind, 0), left(kind, 1)); }
+  uint64_t backlog() const {
+    return advanced ? std::max(backlog(kUnitFrame), backlog(kUnitBlock)) : backlog(kUnitFrame);
+  }
+  // a whole frame, or (advanced) a whole block, is waiting
+  bool ready(StreamUnit kind) const {
+    return backlog(kind) >= (uint64_t)(kind == kUnitBlock ? peaq::kFbFrame : peaq::kFrame);
+  }
+  bool ready() const { return ready(kUnitFrame) || (advanced && ready(kUnitBlock)); }
+
+  // The next window of `kind`, at most `cap` units, and the stream moves on past it.  Whole units first; with
+  // `flushing`, once no whole unit is left and something remains on either pad, the one zero-padded unit: each pad
+  // contributes, and moves on by, min(left, unit).
+  StreamWindow take(StreamUnit kind, unsigned cap, bool flushing) {
+    const uint64_t unit = kind == kUnitBlock ? peaq::kFbFrame : peaq::kFrame;
+    const uint64_t hop = kind == kUnitBlock ? peaq::kFbFrame : peaq::kHop;
+    const uint64_t l[2] = {left(kind, 0), left(kind, 1)}, av = std::min(l[0], l[1]);
+    StreamWindow w;
+    uint64_t adv[2];
+    if (av >= unit) {
+      w.count = static_cast<uint32_t>(std::min<uint64_t>((av - unit) / hop + 1, cap));
+      w.valid[0] = w.valid[1] = (uint64_t)(w.count - 1) * hop + unit;
+      adv[0] = adv[1] = (uint64_t)w.count * hop;
+    } else if (flushing && (l[0] || l[1])) {
+      w.count = 1;
+      w.flush = true;
+      for (int p = 0; p < 2; ++p) w.valid[p] = adv[p] = std::min(l[p], unit);
+    } else {
+      return w;
+    }
+    w.first = done[kind];
+    done[kind] += w.count;
+    for (int p = 0; p < 2; ++p) {
+      w.pos[p] = pos[kind][p];
+      pos[kind][p] += adv[p];
+    }
+    if (kind == kUnitBlock) {
+      w.prev_blocks = prev_blocks;
+      prev_blocks = w.count;
+    }
+    return w;
+  }
+  // drops what both consumers are done with (windows taken before are no longer readable: copy first)
+  void trim() {
+    for (int p = 0; p < 2; ++p)
+      pad[p].drop_until(advanced ? std::min(pos[kUnitFrame][p], pos[kUnitBlock][p]) : pos[kUnitFrame][p], channels);
+  }
+};
+
+// the samples of window w, from the framer's FIFOs into dst[pad] (pinned staging)
+inline void stage_window(const StreamFramer& fr, const StreamWindow& w, float* const dst[2]) {
+  for (int p = 0; p < 2; ++p)
+    if (w.valid[p])
+      std::memcpy(dst[p], fr.pad[p].at(w.pos[p], fr.channels), (size_t)w.valid[p] * fr.channels * sizeof(float));
+}
+
+// What a session does after every push and, with `flushing`, at its flush: frames, then (advanced) blocks, in
+// windows of at most max_frames / max_blocks until nothing comes back or the flush unit has, then trim.
+// run(kind, window) launches a window; a result other than PEAQ_OK ends the walk.
+template <typename Run>
+int drain_stream(StreamFramer& fr, unsigned max_frames, unsigned max_blocks, bool flushing, Run&& run) {
+  for (StreamUnit kind : {kUnitFrame, kUnitBlock}) {
+    if (kind == kUnitBlock && !fr.advanced) break;
+    const unsigned cap = kind == kUnitBlock ? max_blocks : max_frames;
+    for (;;) {
+      const StreamWindow w = fr.take(kind, cap, flushing);
+      if (!w.count) break;
+      const int rc = run(kind, w);
+      if (rc != PEAQ_OK) return rc;
+      if (w.flush) break;
+    }
+  }
+  fr.trim();
+  return PEAQ_OK;
+}

@@ -214,10 +214,6 @@ struct RsPlan {
   size_t lds_bytes = 0;
   uint32_t zero_taps = 0;       // tiled: W - 2K, taps evaluated beside the filter's own (all zero)
   DevBuf taps, off;
-  ~RsPlan() {                   // (also on the error paths of get_plan: DevBuf does not free itself)
-    taps.release();
-    off.release();
-  }
 };
 
 // Per-pair lengths of one call, [n_in | n_out]: staged in pinned host memory and copied on the caller's stream, so the
@@ -243,10 +239,9 @@ void resample_release(peaq_ctx* c) {
   if (!c->rs) return;
   for (LenSlot& sl : c->rs->slots) {
     if (sl.host) (void)hipHostFree(sl.host);
-    sl.dev.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
   }
-  delete c->rs;                 // (the plans free their tables)
+  delete c->rs;                 // (the plans' tables and the slots' device buffers go with it)
   c->rs = nullptr;
 }
 
@@ -434,7 +429,7 @@ extern "C" int peaq_batch_resample(peaq_ctx* c, int channels, uint32_t rate, int
                                    size_t out_stride, uint32_t* n_out, void* stream_) {
   // (what needs no context first)
   if (int rc = check_rate("peaq_batch_resample", rate)) return rc;
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_batch_resample", channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: n_pairs < 0");
   if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: more than 65535 pairs in one call");
   if (!c) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: ctx is NULL");
@@ -537,7 +532,7 @@ extern "C" int peaq_run_pair_rate(peaq_ctx* c, int advanced, int channels, doubl
   if (rate == 48000) return peaq_run_pair(c, advanced, channels, level_db, ref, n_ref, test, n_test, out);
   if (int rc = check_rate("peaq_run_pair_rate", rate)) return rc;
   if (!c || !out) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: NULL argument");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: channels must be 1 or 2");
+  if (int rc = check_channels("peaq_run_pair_rate", channels)) return rc;
   if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: NULL samples");
   if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: more than 2^32 samples");
   const size_t n[2] = {n_ref, n_test};
@@ -549,7 +544,7 @@ extern "C" int peaq_run_pair_rate(peaq_ctx* c, int advanced, int channels, doubl
   HIP_TRY(hipSetDevice(c->device));
   size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
   stride += stride & 1;                              // 8-byte rows, as in peaq_run_pair
-  TmpBuf d_raw[2], d_48[2], d_res;
+  DevBuf d_raw[2], d_48[2], d_res;
   const size_t bytes = stride * channels * sizeof(float);
   HIP_TRY(d_res.reserve(sizeof(peaq_result)));
   for (int i = 0; i < 2; ++i) {

@@ -496,6 +496,22 @@ int peaq_debug_wave (peaq_ctx *ctx, const char *op, size_t n, int planes_in, con
  * every context uploads (csrc/peaq_device.h, CommonTables). */
 int peaq_debug_common_tables (double *log_tab /* [260] */, double *exp_tab /* [64] */);
 
+/* Host only, no device, no samples: the code that cuts a session's two streams into launches (csrc/peaq_host.h,
+ * StreamFramer), run the way a session runs it -- push k adds n_samples[k] samples to pad[k] (0 = ref, 1 = test), and
+ * after every push windows of at most max_frames FFT frames, then (advanced) of at most max_blocks filter-bank blocks,
+ * are taken until nothing comes back; after the last push the stream is flushed.  pad[k] = -1 flushes in mid-stream
+ * as well (n_samples[k] is ignored).  drain_every_push = 0 takes windows at the flushes only, with everything pushed
+ * before still waiting -- a broker's session whose flush is requested before the ticks have caught up.  Every window
+ * is one launch:
+ *   windows[w] = { kind (0 = FFT frames, 1 = filter-bank blocks), first unit, units, valid samples on ref, on test }
+ * where the valid samples fall short of whole units only in the zero-padded unit of the flush.  *n_windows is the
+ * number of windows the stream has; the first max_windows of them are written (windows may be NULL if that is 0).
+ * A session runs this with 64 / 120 units per launch, the broker with 8 / 48. */
+#define PEAQ_DEBUG_STREAM_WINDOW_FIELDS 5
+int peaq_debug_stream_plan (int advanced, unsigned max_frames, unsigned max_blocks, int drain_every_push,
+                            size_t n_pushes, const int *pad, const uint64_t *n_samples, size_t max_windows,
+                            uint64_t *windows, size_t *n_windows);
+
 #ifdef __cplusplus
 }
 #endif
