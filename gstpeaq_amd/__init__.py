@@ -9,8 +9,10 @@ every entry point raises if the HIP library or the GPU is missing.
 """
 from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_trajectory, build_library, debug_backend, debug_frontend, debug_filterbank, debug_wave, debug_common_tables, run_pair,  # noqa: F401
                    run_pair_trajectory, library_path, load_library, synth_fill, resample, resample_plan, resampled_length, resample_supported,
+                   estimate_delay, cut, align, aligned_lengths, align_workspace_bytes, Delay,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
 __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
            "run_pair_trajectory", "library_path", "load_library", "synth_fill", "resample", "resample_plan", "resampled_length",
-           "resample_supported", "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]
+           "resample_supported", "estimate_delay", "cut", "align", "aligned_lengths", "align_workspace_bytes", "Delay",
+           "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

@@ -36,6 +36,12 @@ class ResamplePlan(C.Structure):
                 ("lds_bytes", C.c_uint32), ("table_bytes", C.c_uint64), ("max_sum_abs_taps", C.c_double)]
 
 
+class Delay(C.Structure):
+    """mirrors peaq_delay (include/peaq_amd.h)"""
+    _fields_ = [("lag", C.c_int32), ("reserved", C.c_int32), ("peak", C.c_double), ("runner_up", C.c_double),
+                ("norm", C.c_double)]
+
+
 class _Calibration(C.Structure):
     _fields_ = [("elapsed_ms", C.c_double), ("shader_clock_mhz", C.c_double), ("fp64_tflops", C.c_double),
                 ("cycles_per_fma", C.c_double), ("max_clock_mhz", C.c_double), ("compute_units", C.c_int),
@@ -139,6 +145,16 @@ def load_library():
                                           vp, C.c_size_t, u32p, vp]
         L.peaq_run_pair_rate.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, fp, C.c_size_t, fp, C.c_size_t, dp]
         L.peaq_resample_plan_info.argtypes = [C.c_uint32, C.POINTER(ResamplePlan)]
+    if hasattr(L, "peaq_batch_estimate_delay"):      # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_batch_estimate_delay.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32,
+                                                C.c_uint32, vp, vp]
+        L.peaq_align_workspace_bytes.restype = C.c_size_t
+        L.peaq_align_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+        L.peaq_batch_cut.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, vp, C.c_size_t, vp]
+        L.peaq_aligned_lengths.restype = None
+        L.peaq_aligned_lengths.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+        L.peaq_run_pair_aligned.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t,
+                                            fp, C.c_size_t, C.POINTER(Delay), dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -460,15 +476,113 @@ def _to_48k(ctx, ref, test, n_ref, n_test, rate, stream):
     return bufs[0], bufs[1], o_ref, o_test
 
 
+def aligned_lengths(lag, n_ref, n_test):
+    """(skip_ref, skip_test, n_common) for one pair's lag (peaq_aligned_lengths, host arithmetic)"""
+    sr, st, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    load_library().peaq_aligned_lengths(int(lag), int(n_ref), int(n_test), C.byref(sr), C.byref(st), C.byref(n))
+    return sr.value, st.value, n.value
+
+
+def align_workspace_bytes(channels, n_pairs, n_max, max_lag):
+    """scratch of estimate_delay for a shape (peaq_align_workspace_bytes)"""
+    return int(load_library().peaq_align_workspace_bytes(int(channels), int(n_pairs), int(n_max), int(max_lag)))
+
+
+def estimate_delay(ctx, ref, test, max_lag, n_ref=None, n_test=None, stream=None):
+    """Delay of every pair of a batch (peaq_batch_estimate_delay): ref/test CUDA float32 [n_pairs, n_samples, channels],
+    n_ref/n_test optional per-pair lengths.  Returns a dict of numpy arrays [n_pairs]: lag (int32; positive: the test
+    signal is late), peak, runner_up, norm.  Synchronises the stream it ran on."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    with _torch_stream(stream):
+        rec = torch.zeros((max(n_pairs, 1), C.sizeof(Delay)), dtype=torch.uint8, device=ref.device)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_estimate_delay(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()),
+                                           C.c_void_p(test.data_ptr()), stride,
+                                           a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                           a_test.ctypes.data_as(u32p) if a_test is not None else None,
+                                           stride, int(max_lag), C.c_void_p(rec.data_ptr()), _stream_ptr(stream)))
+    if stream is None:
+        torch.cuda.current_stream(ref.device).synchronize()
+    elif hasattr(stream, "synchronize"):
+        stream.synchronize()
+    else:
+        torch.cuda.ExternalStream(int(stream)).synchronize()
+    rows = rec.cpu().numpy()[:n_pairs].copy().view(
+        np.dtype([("lag", "<i4"), ("reserved", "<i4"), ("peak", "<f8"), ("runner_up", "<f8"), ("norm", "<f8")]))[:, 0]
+    return {k: np.ascontiguousarray(rows[k]) for k in ("lag", "peak", "runner_up", "norm")}
+
+
+def cut(ctx, x, skip, n_keep, out=None, stream=None):
+    """out[p, i] = x[p, skip[p] + i] for i < n_keep[p] (peaq_batch_cut); x: CUDA float32 [n_pairs, n_samples, channels].
+    out: optional tensor [n_pairs, stride, channels] to write into (samples past n_keep[p] keep what they held); without
+    it a zero-filled one with an even stride is made.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,)
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the copy runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_cut(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_skip.ctypes.data_as(u32p),
+                                a_keep.ctypes.data_as(u32p), C.c_void_p(out.data_ptr()), out.shape[1],
+                                _stream_ptr(stream)))
+    return out
+
+
+def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None):
+    """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
+    Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
+    n_pairs, stride, _ = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
+    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
+    cuts = np.array([aligned_lengths(int(lags[p]), int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)],
+                    dtype=np.uint32).reshape(n_pairs, 3)
+    import torch
+    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
+    with _torch_stream(stream):
+        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
+                for _ in (0, 1)]
+    cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
+    cut(ctx, test, cuts[:, 1], cuts[:, 2], out=bufs[1], stream=stream)
+    n = np.ascontiguousarray(cuts[:, 2])
+    return bufs[0], bufs[1], n, n.copy()
+
+
+def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream):
+    """the `align=` keyword of batch_run / batch_trajectory: estimate, then cut"""
+    d = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)
+    return align(ctx, ref, test, d["lag"], n_ref, n_test, stream=stream)
+
+
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
-              stream=None, sync=True, rate=48000):
+              stream=None, sync=True, rate=48000, align=None):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
     n_ref/n_test: optional per-pair lengths (samples per channel).
     rate: sampling rate of ref/test; anything but 48000 is converted on the device first (resample).
+    align: a max_lag in 48 kHz samples: every pair's delay is estimated and both signals are cut to their common,
+    aligned part first (estimate_delay, align), after the rate conversion.
     Returns a list of result dicts (sync=True) or the device result tensor."""
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
     n_pairs, stride, channels = ref.shape
@@ -492,15 +606,17 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
 
 
 def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n_test=None, playback_level=92.0,
-                     stream=None, sync=True, rate=48000):
+                     stream=None, sync=True, rate=48000, align=None):
     """Readings every `interval` samples per channel through each pair (peaq_batch_run_trajectory): point k of pair p
     is what a session pushed the first min((k + 1) interval, n) samples of each signal reads, unflushed.
-    ref/test and rate as for batch_run; `interval` counts samples at 48 kHz whatever the rate.  Returns
+    ref/test, rate and align as for batch_run; `interval` counts samples at 48 kHz whatever the rate.  Returns
     (points, results): lists of result dicts, points[p][k], (sync=True) or the device tensors [n_pairs, n_points, 16]
     and [n_pairs, 16]."""
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
     n_pairs, stride, channels = ref.shape
@@ -553,14 +669,24 @@ def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_l
     return [_result_dict(r, bool(advanced)) for r in pts], _result_dict(out, bool(advanced))
 
 
-def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000):
+def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
-    other than 48000 they are converted on the device first (peaq_run_pair_rate)"""
+    other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
+    the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
+    if align is not None:
+        rec = Delay()
+        _check(ctx.L.peaq_run_pair_aligned(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
+                                           ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                           test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
+                                           out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        return res
     if int(rate) != 48000:
         _check(ctx.L.peaq_run_pair_rate(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),
                                         ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),

@@ -264,7 +264,9 @@ usage (const char *prog)
       "  --no-resample refuse files that are not sampled at 48 kHz instead of converting them\n"
       "  --device-resample convert files at other rates on the GPU instead of on the host\n"
       "                (the plain one-call mode only: not with --interval; both files at one rate)\n"
-      "  --interval=S  also print ODG and DI read every S seconds through the files\n", prog);
+      "  --interval=S  also print ODG and DI read every S seconds through the files\n"
+      "  --align[=SAMPLES] find the test file's delay within +-SAMPLES (48 kHz samples, 1..16384, default 4096)\n"
+      "                on the GPU and compare the aligned parts (the plain one-call mode only)\n", prog);
 }
 
 int
@@ -272,6 +274,8 @@ main (int argc, char **argv)
 {
   int advanced = 0, i, nfiles = 0, rc, allow_resample = 1, device_resample = 0;
   uint32_t device_rate = 0;     /* != 0: both files stay at this rate, peaq_run_pair_rate converts them */
+  uint32_t align_lag = 0;       /* != 0: --align, peaq_run_pair_aligned */
+  peaq_delay delay;
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   wav_t ref, test;
@@ -291,6 +295,17 @@ main (int argc, char **argv)
       allow_resample = 0;
     else if (!strcmp (argv[i], "--device-resample"))
       device_resample = 1;
+    else if (!strcmp (argv[i], "--align"))
+      align_lag = 4096;
+    else if (!strncmp (argv[i], "--align=", 8)) {
+      char *end;
+      const long v = strtol (argv[i] + 8, &end, 10);
+      if (*end || end == argv[i] + 8 || v < 1 || v > 16384) {
+        fprintf (stderr, "Failed to initialize: invalid alignment range %s (1 .. 16384 samples)\n", argv[i] + 8);
+        return 1;
+      }
+      align_lag = (uint32_t) v;
+    }
     else if (!strncmp (argv[i], "--interval=", 11)) {
       char *end;
       interval_s = strtod (argv[i] + 11, &end);
@@ -339,6 +354,10 @@ main (int argc, char **argv)
       fprintf (stderr, "Error: out of memory while resampling\n");
       return 2;
     }
+  }
+  if (align_lag && (interval_s > 0. || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Note: --align does not apply to this mode: comparing the files as they are\n");
+    align_lag = 0;
   }
   if (ref.channels != test.channels) {
     /* the element negotiates equal channel counts via audioconvert; up-mix the mono side */
@@ -400,7 +419,14 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if ((device_rate ? peaq_run_pair_rate (ctx, advanced, ref.channels, level, device_rate, ref.samples, ref.frames,
+    if (align_lag) {
+      if (peaq_run_pair_aligned (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag,
+              ref.samples, ref.frames, test.samples, test.frames, &delay, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+    } else if ((device_rate ? peaq_run_pair_rate (ctx, advanced, ref.channels, level, device_rate, ref.samples, ref.frames,
                 test.samples, test.frames, &r)
             : peaq_run_pair (ctx, advanced, ref.channels, level, ref.samples, ref.frames, test.samples, test.frames,
                 &r)) != PEAQ_OK) {

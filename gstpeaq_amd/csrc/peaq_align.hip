@@ -1,0 +1,661 @@
+// peaq_align.hip -- time alignment in front of the batch driver (peaq_batch_estimate_delay, peaq_batch_cut,
+// peaq_aligned_lengths, peaq_run_pair_aligned; include/peaq_amd.h).  The delay of a pair is the integer lag of the
+// largest |cross-correlation| of the two mono sums over [-max_lag, max_lag]; the correlation is evaluated in the
+// blocked frequency-domain form, which is exact for linear correlation:
+//
+//   H = 512.  Reference block j = r[jH .. jH + H) zero-padded to 2H, test window k = t[kH .. kH + 2H).
+//   A_s[b] = sum_j conj(R_j[b]) T_{j+s}[b];  the inverse transform of A_s holds, at m = 0 .. H, the lags sH + m
+//   (m + n <= 2H - 1 for n < H: nothing wraps).  Segments s = -S .. S - 1, S = ceil(max_lag / H), cover every lag
+//   of [-SH, SH]; samples outside a signal are zeros, which is the definition's "over all n where both exist".
+//
+// Four kernels per group of pairs, all FP64 after the samples' conversion:
+//   align_spectra_kernel     one wave per transform: a 1024-point complex transform (the front end's three passes, from
+//       dft16 / dft4 / rows_transpose4 of peaq_wave.h) carries reference block i in its real part and test window
+//       i - S in its imaginary part; split by symmetry into the half-spectra R_i and T_i, bins 0 .. 511 with the
+//       (real) bin 512 in bin 0's imaginary part, written to the scratch.  Also the block's share of sum r^2, sum t^2.
+//   align_accumulate_kernel  one thread per bin, chunk of 128 blocks and group of 16 segments: the 16 products per
+//       block accumulate in registers, the 16 test spectra a block meets sit in a register ring (one new spectrum per
+//       block), so every spectrum is read once per chunk and segment group.  Partial sums per chunk, to the scratch.
+//   align_inverse_kernel     one wave per segment: the chunks' partial sums added in chunk order, the Hermitian
+//       spectrum rebuilt, one transform back, lags to the scratch.
+//   align_pick_kernel        one workgroup per pair: norm, arg-max with the tie rule, runner-up.
+// Every sum has a fixed order and every reduction across threads is a max or a min, so the record of a pair does
+// not depend on the batch it is in, and is the same run to run.
+//   align_cut_kernel         peaq_batch_cut: a strided copy, 16 bytes per lane where the alignment allows.
+#include "peaq_host.h"
+#include "peaq_wave.h"
+
+namespace {
+
+using peaq::cplx;
+using peaq::cmul;
+
+constexpr int kAlH = 512;                        // block length; transforms are 2H = 1024 points
+constexpr int kAlBins = 512;                     // stored bins per half-spectrum (bin 512 rides in bin 0)
+constexpr int kAlG = 16;                         // segments per group = products per thread and block
+constexpr int kAlChunk = 128;                    // blocks per partial sum (a multiple of kAlG)
+constexpr int kAlExch = 1088;                    // doubles of exchange buffer per wave (8.5 KiB)
+constexpr uint32_t kAlMaxLag = 16384;
+// Tie tolerance of the arg-max, in units of norm.  The rounding error of c[d] is a few times 2^-53 log2(1024) norm per
+// transform it passes (three), some 1e-14 norm at worst; 1e-12 is two orders above that and three below
+// the bound the header states for c.
+constexpr double kAlTie = 1e-12;
+constexpr size_t kAlScratchBudget = (size_t)1 << 30;   // pairs are taken in groups whose scratch stays below this
+
+struct AlignArgs {
+  const float* ref;             // first pair of the group
+  const float* test;
+  size_t stride;
+  const uint32_t* n_ref;        // device, first pair of the group; nullptr: n_uniform
+  const uint32_t* n_test;
+  uint32_t n_uniform;
+  int channels;
+  uint32_t D;                   // max_lag
+  uint32_t S;                   // segments each side: lags [-S H, S H]
+  uint32_t NB, NT;              // reference blocks, test windows (= transforms) per pair
+  uint32_t NSEG, NCH;           // segments computed (a multiple of kAlG, >= 2 S), chunks
+  double2* rspec;               // [pair][NB][512]
+  double2* tspec;               // [pair][NT][512]
+  double2* part;                // [pair][NSEG][NCH][512]
+  double* corr;                 // [pair][2 S H + 1]
+  double* energy;               // [pair][NT][2]: sum r^2 of block i, sum t^2 of the first half of window i
+  peaq_delay* out;              // first pair of the group
+  const peaq::CommonTables* ct;
+};
+
+__device__ __forceinline__ int al_pad16(int i) { return i + (i >> 4); }
+__device__ __forceinline__ cplx al_tw_lane(const peaq::CommonTables* __restrict__ ct, int e, int lane) {
+  const double2 v = *reinterpret_cast<const double2*>(ct->tw_lane[e][lane]);
+  return {v.x, v.y};
+}
+__device__ __forceinline__ cplx al_csqr(cplx a) { return {a.re * a.re - a.im * a.im, 2. * (a.re * a.im)}; }
+
+template <typename WR, typename RD>
+__device__ __forceinline__ void al_exchange16(cplx (&z)[16], double* buf, WR wr, RD rd) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) buf[al_pad16(wr(r))] = z[r].re;
+  peaq::wave_lds_fence();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[r].re = buf[al_pad16(rd(r))];
+  peaq::wave_lds_fence();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) buf[al_pad16(wr(r))] = z[r].im;
+  peaq::wave_lds_fence();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[r].im = buf[al_pad16(rd(r))];
+  peaq::wave_lds_fence();
+}
+
+// 1024-point forward complex DFT of one wave, 16 x 16 x 4 Stockham: in z[r] = x[lane + 64 r], out z[q] = X[lane + 64 q]
+// (the three passes of the front end's frame_power_spectrum; buf: kAlExch doubles of LDS of this wave's own)
+__device__ __forceinline__ void al_fft1024(cplx (&z)[16], double* buf, int lane, const peaq::CommonTables* __restrict__ ct) {
+  peaq::dft16(z);
+  al_exchange16(z, buf, [&](int r) { return 16 * lane + r; }, [&](int r) { return lane + 64 * r; });
+  {
+    cplx w[9];
+    w[1] = al_tw_lane(ct, 2, lane);                  // W_256^(lane & 15)
+    w[2] = al_csqr(w[1]);
+    w[4] = al_csqr(w[2]);
+    w[8] = al_csqr(w[4]);
+    w[3] = cmul(w[1], w[2]);
+    w[5] = cmul(w[4], w[1]);
+    w[6] = cmul(w[4], w[2]);
+    w[7] = cmul(w[4], w[3]);
+#pragma unroll
+    for (int r = 1; r < 8; ++r) {
+      z[8 + r] = cmul(z[8 + r], cmul(w[8], w[r]));
+      z[r] = cmul(z[r], w[r]);
+    }
+    z[8] = cmul(z[8], w[8]);
+  }
+  peaq::dft16(z);
+  // rows and registers trade places (see frame_power_spectrum): four 4 x 4 transposes and a renaming
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    peaq::rows_transpose4(z[4 * g].re, z[4 * g + 1].re, z[4 * g + 2].re, z[4 * g + 3].re);
+    peaq::rows_transpose4(z[4 * g].im, z[4 * g + 1].im, z[4 * g + 2].im, z[4 * g + 3].im);
+  }
+#pragma unroll
+  for (int a2 = 0; a2 < 4; ++a2)
+#pragma unroll
+    for (int g = a2 + 1; g < 4; ++g) {
+      const cplx t = z[4 * a2 + g];
+      z[4 * a2 + g] = z[4 * g + a2];
+      z[4 * g + a2] = t;
+    }
+  {
+    constexpr double c1 = 0.92387953251128673848, s1 = 0.38268343236508977173, c2 = 0.70710678118654752440;
+    const cplx wb = al_tw_lane(ct, 1, lane);         // W_1024^lane
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const cplx w1 = m == 0 ? wb : m == 1 ? cmul(wb, {c1, -s1}) : m == 2 ? cmul(wb, {c2, -c2}) : cmul(wb, {s1, -c1});
+      const cplx w2 = al_csqr(w1), w3 = cmul(w2, w1);
+      z[m + 4] = cmul(z[m + 4], w1);
+      z[m + 8] = cmul(z[m + 8], w2);
+      z[m + 12] = cmul(z[m + 12], w3);
+      peaq::dft4(z[m], z[m + 4], z[m + 8], z[m + 12]);
+    }
+  }
+}
+
+// mono sum of sample s, in double
+__device__ __forceinline__ double al_mono(const float* __restrict__ x, long long s, int channels) {
+  return channels == 2 ? (double)x[2 * s] + (double)x[2 * s + 1] : (double)x[s];
+}
+
+__global__ __launch_bounds__(256) void align_spectra_kernel(const AlignArgs a) {
+  __shared__ double al_lds[4 * kAlExch];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned i = blockIdx.x * 4 + wave, pair = blockIdx.y;
+  if (i >= a.NT) return;                             // (the whole wave; no workgroup barrier below)
+  const long long n_ref = a.n_ref ? a.n_ref[pair] : a.n_uniform;
+  const long long n_test = a.n_test ? a.n_test[pair] : a.n_uniform;
+  const int C = a.channels;
+  const float* ref = a.ref + (size_t)pair * a.stride * C;
+  const float* test = a.test + (size_t)pair * a.stride * C;
+  const long long r0 = (long long)i * kAlH, t0 = ((long long)i - (long long)a.S) * kAlH;
+  cplx z[16];
+  double er = 0., et = 0.;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int n = lane + 64 * r;
+    double xr = 0., xt = 0.;
+    if (r < 8 && r0 + n < n_ref) xr = al_mono(ref, r0 + n, C);
+    if (t0 + n >= 0 && t0 + n < n_test) xt = al_mono(test, t0 + n, C);
+    z[r] = {xr, xt};
+    if (r < 8) {
+      er = __builtin_fma(xr, xr, er);
+      et = __builtin_fma(xt, xt, et);
+    }
+  }
+  er = peaq::wave_sum(er);
+  et = peaq::wave_sum(et);
+  if (lane == 0) {
+    double* e = a.energy + ((size_t)pair * a.NT + i) * 2;
+    e[0] = er;
+    e[1] = et;
+  }
+  al_fft1024(z, al_lds + wave * kAlExch, lane, a.ct);
+  // Z = R + i T with R, T the spectra of two real signals: R[k] = (Z[k] + conj Z[1024 - k]) / 2,
+  // T[k] = (Z[k] - conj Z[1024 - k]) / 2i.  Z[1024 - k], k = lane + 64 q, sits in lane 64 - lane, slot 15 - q
+  // (lane 0: its own slot 16 - q).
+  const int partner = (64 - lane) & 63;
+  double2* R = a.rspec + ((size_t)pair * a.NB + i) * kAlBins;
+  double2* T = a.tspec + ((size_t)pair * a.NT + i) * kAlBins;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int k = lane + 64 * q;
+    cplx zm = {__shfl(z[15 - q].re, partner, 64), __shfl(z[15 - q].im, partner, 64)};
+    if (lane == 0) zm = z[(16 - q) & 15];
+    double2 rr = {0.5 * (z[q].re + zm.re), 0.5 * (z[q].im - zm.im)};
+    double2 tt = {0.5 * (z[q].im + zm.im), 0.5 * (zm.re - z[q].re)};
+    if (q == 0 && lane == 0) {                       // bins 0 and 512 are real: they share a slot
+      rr = {z[0].re, z[8].re};
+      tt = {z[0].im, z[8].im};
+    }
+    if (i < a.NB) R[k] = rr;
+    T[k] = tt;
+  }
+}
+
+__global__ __launch_bounds__(256) void align_accumulate_kernel(const AlignArgs a) {
+  const unsigned k = (blockIdx.x & 1) * 256 + threadIdx.x;
+  const unsigned chunk = blockIdx.x >> 1, pair = blockIdx.y, g = blockIdx.z;
+  const double2* __restrict__ R = a.rspec + (size_t)pair * a.NB * kAlBins + k;
+  const double2* __restrict__ T = a.tspec + ((size_t)pair * a.NT + (size_t)g * kAlG) * kAlBins + k;
+  const unsigned j0 = chunk * kAlChunk, j1 = min(j0 + kAlChunk, a.NB);
+  // segment u of the group meets, at block j, test window j + u (relative to the group's first): slot (j + u) mod G
+  double2 t[kAlG], acc[kAlG];
+#pragma unroll
+  for (int u = 0; u < kAlG; ++u) acc[u] = {0., 0.};
+#pragma unroll
+  for (int u = 0; u < kAlG - 1; ++u) t[u] = T[(size_t)(j0 + u) * kAlBins];   // (j0 is a multiple of G)
+  // bin 0 carries two real bins: its "product" is component by component
+  const bool k0 = k == 0;
+  const double m = k0 ? 0. : 1.;
+  for (unsigned jb = j0; jb < j1; jb += kAlG) {
+#pragma unroll
+    for (int jj = 0; jj < kAlG; ++jj) {
+      const unsigned j = jb + jj;
+      if (j < j1) {
+        t[(jj + kAlG - 1) % kAlG] = T[(size_t)(j + kAlG - 1) * kAlBins];
+        const double2 r = R[(size_t)j * kAlBins];
+        const double mry = m * r.y, p = k0 ? r.y : r.x;
+#pragma unroll
+        for (int u = 0; u < kAlG; ++u) {             // conj(r) t = (rx tx + ry ty, rx ty - ry tx)
+          const double2 tt = t[(jj + u) % kAlG];
+          acc[u].x = __builtin_fma(r.x, tt.x, acc[u].x);
+          acc[u].x = __builtin_fma(mry, tt.y, acc[u].x);
+          acc[u].y = __builtin_fma(p, tt.y, acc[u].y);
+          acc[u].y = __builtin_fma(-mry, tt.x, acc[u].y);
+        }
+      }
+    }
+  }
+  double2* P = a.part + (((size_t)pair * a.NSEG + (size_t)g * kAlG) * a.NCH + chunk) * kAlBins + k;
+#pragma unroll
+  for (int u = 0; u < kAlG; ++u) P[(size_t)u * a.NCH * kAlBins] = acc[u];
+}
+
+__global__ __launch_bounds__(256) void align_inverse_kernel(const AlignArgs a) {
+  __shared__ double al_lds[4 * kAlExch];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned seg = blockIdx.x * 4 + wave, pair = blockIdx.y;
+  if (seg >= 2 * a.S) return;                        // (the whole wave)
+  const double2* __restrict__ P = a.part + ((size_t)pair * a.NSEG + seg) * a.NCH * kAlBins;
+  // c[m] = (1 / N) sum_b A[b] W^(-b m) = (1 / N) Re sum_b conj(A[b]) W^(b m): the forward transform of conj A, with
+  // A[1024 - b] = conj A[b] for the upper half
+  cplx z[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int n = lane + 64 * r;
+    const int b = (n < 512 ? n : 1024 - n) & 511;    // (bin 512 rides in bin 0)
+    double sx = 0., sy = 0.;
+    for (unsigned ch = 0; ch < a.NCH; ++ch) {        // chunk order
+      const double2 v = P[(size_t)ch * kAlBins + b];
+      sx += v.x;
+      sy += v.y;
+    }
+    z[r] = n == 0 ? cplx{sx, 0.} : n == 512 ? cplx{sy, 0.} : n < 512 ? cplx{sx, -sy} : cplx{sx, sy};
+  }
+  al_fft1024(z, al_lds + wave * kAlExch, lane, a.ct);
+  double* c = a.corr + (size_t)pair * (2 * (size_t)a.S * kAlH + 1) + (size_t)seg * kAlH;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c[lane + 64 * q] = z[q].re * (1. / 1024.);
+  if (seg == 2 * a.S - 1 && lane == 0) c[kAlH] = z[8].re * (1. / 1024.);   // the lag S H itself
+}
+
+// workgroup reductions of align_pick_kernel (256 threads; sh: 256 entries)
+template <typename T, typename OP>
+__device__ __forceinline__ T al_block_reduce(T v, T* sh, OP op) {
+  __syncthreads();                                   // (sh may still be read from the reduction before)
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] = op(sh[threadIdx.x], sh[threadIdx.x + w]);
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__global__ __launch_bounds__(256) void align_pick_kernel(const AlignArgs a) {
+  __shared__ double sh_d[256];
+  __shared__ unsigned sh_u[256];
+  const unsigned pair = blockIdx.x, tid = threadIdx.x;
+  // energies: every thread its own blocks in index order, then a fixed tree
+  double er = 0., et = 0.;
+  const double* e = a.energy + (size_t)pair * a.NT * 2;
+  for (unsigned i = tid; i < a.NT; i += 256) {
+    er += e[2 * i];
+    et += e[2 * i + 1];
+  }
+  const auto add = [](double x, double y) { return x + y; };
+  er = al_block_reduce(er, sh_d, add);
+  et = al_block_reduce(et, sh_d, add);
+  peaq_delay rec;
+  rec.lag = 0;
+  rec.reserved = 0;
+  rec.peak = rec.runner_up = rec.norm = 0.;
+  const double e2 = er * et;
+  if (!isfinite(e2)) {                               // (uniform) a NaN or Inf sample, or energies beyond FP64: no estimate
+    rec.norm = __builtin_nan("");
+  } else if (e2 > 0.) {
+    const double norm = sqrt(e2);
+    const int D = (int)a.D;
+    const double* c = a.corr + (size_t)pair * (2 * (size_t)a.S * kAlH + 1) + (size_t)a.S * kAlH;   // c[d], d = -SH .. SH
+    const auto fmx = [](double x, double y) { return fmax(x, y); };
+    double best = 0.;
+    for (int d = -D + (int)tid; d <= D; d += 256) best = fmax(best, fabs(c[d]));
+    best = al_block_reduce(best, sh_d, fmx);
+    // values within kAlTie norm of the largest are not told apart (the transforms' rounding gives the lags of an exact
+    // tie different last bits): among them the smaller |d|, then the positive
+    const double floor_ = best - kAlTie * norm;
+    unsigned key = 0xFFFFFFFFu;                      // 2 |d| + (d < 0)
+    for (int d = -D + (int)tid; d <= D; d += 256)
+      if (fabs(c[d]) >= floor_) key = min(key, 2u * (unsigned)abs(d) + (d < 0 ? 1u : 0u));
+    key = al_block_reduce(key, sh_u, [](unsigned x, unsigned y) { return min(x, y); });
+    if (key == 0xFFFFFFFFu) {                        // (uniform) no lag selected: nothing of c is a number
+      rec.norm = __builtin_nan("");
+    } else {
+      const int lag = (key & 1u) ? -(int)(key >> 1) : (int)(key >> 1);   // |lag| <= D by construction
+      double second = 0.;
+      for (int d = -D + (int)tid; d <= D; d += 256)
+        if (d != lag) second = fmax(second, fabs(c[d]));
+      second = al_block_reduce(second, sh_d, fmx);
+      rec.lag = lag;
+      rec.peak = c[lag];
+      rec.runner_up = second;
+      rec.norm = norm;
+    }
+  }
+  if (tid == 0) a.out[pair] = rec;
+}
+
+struct CutArgs {
+  const float* in;
+  float* out;
+  size_t in_stride, out_stride;  // samples per channel between pairs
+  const uint32_t* skip;          // device [n_pairs]
+  const uint32_t* n_keep;        // device [n_pairs]
+  int channels;
+};
+
+// floats, not samples: a pair's run is n_keep x channels consecutive floats.  Stores are 16 bytes from the first
+// aligned float of the destination on; loads are 16 bytes too where the source is aligned alike, else four dwords.
+__global__ __launch_bounds__(256) void align_cut_kernel(const CutArgs a) {
+  const unsigned pair = blockIdx.y;
+  const size_t count = (size_t)a.n_keep[pair] * a.channels;
+  const float* __restrict__ src = a.in + ((size_t)pair * a.in_stride + a.skip[pair]) * a.channels;
+  float* __restrict__ dst = a.out + (size_t)pair * a.out_stride * a.channels;
+  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
+  const size_t vecs = (count - head) / 4;
+  const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (v < vecs) {
+    const float* s = src + head + 4 * v;
+    float4 x;
+    if (((uintptr_t)s & 15) == 0)
+      x = *reinterpret_cast<const float4*>(s);
+    else
+      x = {s[0], s[1], s[2], s[3]};
+    *reinterpret_cast<float4*>(dst + head + 4 * v) = x;
+  }
+  if (blockIdx.x == 0) {                             // the unaligned head and the tail: at most 3 floats each
+    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+    const size_t tail0 = head + 4 * vecs;
+    if (tail0 + threadIdx.x < count) dst[tail0 + threadIdx.x] = src[tail0 + threadIdx.x];
+  }
+}
+
+// what one call's shape needs
+struct AlignPlan {
+  uint32_t S, NB, NT, NSEG, NCH;
+  size_t rspec, tspec, part, corr, energy;           // bytes per pair
+  size_t per_pair;
+};
+
+size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+AlignPlan align_plan(uint32_t n_max, uint32_t max_lag) {
+  AlignPlan p;
+  p.S = (max_lag + kAlH - 1) / kAlH;
+  p.NB = std::max<uint32_t>(1, (uint32_t)(((uint64_t)n_max + kAlH - 1) / kAlH));
+  p.NSEG = (2 * p.S + kAlG - 1) / kAlG * kAlG;
+  p.NT = p.NB + p.NSEG - 1;
+  p.NCH = (p.NB + kAlChunk - 1) / kAlChunk;
+  p.rspec = round256((size_t)p.NB * kAlBins * sizeof(double2));
+  p.tspec = round256((size_t)p.NT * kAlBins * sizeof(double2));
+  p.part = round256((size_t)p.NSEG * p.NCH * kAlBins * sizeof(double2));
+  p.corr = round256((2 * (size_t)p.S * kAlH + 1) * sizeof(double));
+  p.energy = round256((size_t)p.NT * 2 * sizeof(double));
+  p.per_pair = p.rspec + p.tspec + p.part + p.corr + p.energy;
+  return p;
+}
+
+size_t align_scratch_bytes(const AlignPlan& p, int n_pairs) {
+  if (n_pairs <= 0) return 0;
+  return std::min((size_t)n_pairs * p.per_pair, std::max(kAlScratchBudget, p.per_pair));
+}
+
+int check_max_lag(const char* who, uint32_t max_lag) {
+  if (max_lag < 1 || max_lag > kAlMaxLag)
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": max_lag " + std::to_string(max_lag) + " is outside 1 .. " +
+                                  std::to_string(kAlMaxLag));
+  return PEAQ_OK;
+}
+
+}  // namespace
+
+struct AlignState {
+  DevBuf scratch;
+  LenStage lens;                // estimate: [n_ref | n_test]; cut: [skip | n_keep]
+  hipEvent_t scratch_free = nullptr;   // behind the last kernel that used the scratch
+  bool scratch_busy = false;
+};
+
+void align_release(peaq_ctx* c) {
+  if (!c->al) return;
+  c->al->lens.release();
+  if (c->al->scratch_free) (void)hipEventDestroy(c->al->scratch_free);
+  delete c->al;
+  c->al = nullptr;
+}
+
+extern "C" size_t peaq_align_workspace_bytes(int channels, int n_pairs, uint32_t n_max, uint32_t max_lag) {
+  (void)channels;                                    // (the mono sum is taken while loading)
+  if (n_pairs <= 0 || max_lag < 1 || max_lag > kAlMaxLag) return 0;
+  return align_scratch_bytes(align_plan(n_max, max_lag), n_pairs);
+}
+
+extern "C" void peaq_aligned_lengths(int32_t lag, uint32_t n_ref, uint32_t n_test, uint32_t* skip_ref,
+                                     uint32_t* skip_test, uint32_t* n_common) {
+  const uint64_t late = lag > 0 ? (uint64_t)lag : 0, early = lag < 0 ? (uint64_t)(-(int64_t)lag) : 0;
+  const uint32_t sr = (uint32_t)std::min<uint64_t>(early, n_ref), st = (uint32_t)std::min<uint64_t>(late, n_test);
+  if (skip_ref) *skip_ref = sr;
+  if (skip_test) *skip_test = st;
+  if (n_common) *n_common = std::min(n_ref - sr, n_test - st);
+}
+
+extern "C" int peaq_batch_estimate_delay(peaq_ctx* c, int channels, int n_pairs, const float* d_ref,
+                                         const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                         const uint32_t* n_test, uint32_t n_uniform, uint32_t max_lag,
+                                         peaq_delay* d_out, void* stream_) {
+  const char* who = "peaq_batch_estimate_delay";
+  // (what needs no context first)
+  if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, std::string(who) + ": n_pairs < 0");
+  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 65535 pairs in one call");
+  if (n_pairs > 0 && (!d_ref || !d_test || !d_out)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL buffer");
+  if (!c) return fail(PEAQ_ERR_ARG, std::string(who) + ": ctx is NULL");
+  if (n_pairs == 0) return PEAQ_OK;
+  if ((n_ref == nullptr) != (n_test == nullptr))
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": n_ref and n_test must both be given or both be NULL");
+  std::vector<uint32_t> h;
+  uint32_t n_max = n_uniform;
+  if (n_ref) {
+    h.resize(2 * (size_t)n_pairs);
+    n_max = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+      if (n_ref[p] > pair_stride || n_test[p] > pair_stride)
+        return fail(PEAQ_ERR_ARG, std::string(who) + ": a pair is longer than pair_stride");
+      h[p] = n_ref[p];
+      h[(size_t)n_pairs + p] = n_test[p];
+      n_max = std::max(n_max, std::max(n_ref[p], n_test[p]));
+    }
+  } else if (n_uniform > pair_stride) {
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": n_uniform > pair_stride");
+  }
+
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->al) c->al = new AlignState;
+  AlignState* st = c->al;
+  const AlignPlan pl = align_plan(n_max, max_lag);
+  const size_t bytes = align_scratch_bytes(pl, n_pairs);
+  const int group = (int)std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, bytes / pl.per_pair));
+  if (!st->scratch_free) HIP_TRY(hipEventCreateWithFlags(&st->scratch_free, hipEventDisableTiming));
+  if (bytes > st->scratch.cap && st->scratch_busy) {   // growing frees the old scratch: its last user has to be done
+    HIP_TRY(hipEventSynchronize(st->scratch_free));
+    st->scratch_busy = false;
+  }
+  HIP_TRY(st->scratch.reserve(bytes));
+  if (st->scratch_busy) HIP_TRY(hipStreamWaitEvent(stream, st->scratch_free, 0));   // (a call on another stream)
+  LenSlot* slot = nullptr;
+  if (n_ref) {
+    if (int rc = st->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
+  }
+  char* base = st->scratch.as<char>();
+  AlignArgs a{};
+  a.stride = pair_stride;
+  a.n_uniform = n_uniform;
+  a.channels = channels;
+  a.D = max_lag;
+  a.S = pl.S;
+  a.NB = pl.NB;
+  a.NT = pl.NT;
+  a.NSEG = pl.NSEG;
+  a.NCH = pl.NCH;
+  a.ct = c->d_common;
+  hipError_t launched = hipSuccess;
+  for (int p0 = 0; p0 < n_pairs; p0 += group) {
+    const unsigned np = (unsigned)std::min(group, n_pairs - p0);
+    a.ref = d_ref + (size_t)p0 * pair_stride * channels;
+    a.test = d_test + (size_t)p0 * pair_stride * channels;
+    a.n_ref = slot ? slot->dev.as<uint32_t>() + p0 : nullptr;
+    a.n_test = slot ? slot->dev.as<uint32_t>() + n_pairs + p0 : nullptr;
+    a.out = d_out + p0;
+    char* q = base;                                  // the group's arrays one after the other, each [np][...]
+    a.rspec = reinterpret_cast<double2*>(q);
+    q += (size_t)group * pl.rspec;
+    a.tspec = reinterpret_cast<double2*>(q);
+    q += (size_t)group * pl.tspec;
+    a.part = reinterpret_cast<double2*>(q);
+    q += (size_t)group * pl.part;
+    a.corr = reinterpret_cast<double*>(q);
+    q += (size_t)group * pl.corr;
+    a.energy = reinterpret_cast<double*>(q);
+    hipLaunchKernelGGL(align_spectra_kernel, dim3((pl.NT + 3) / 4, np), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(align_accumulate_kernel, dim3(2 * pl.NCH, np, pl.NSEG / kAlG), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(align_inverse_kernel, dim3((2 * pl.S + 3) / 4, np), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(align_pick_kernel, dim3(np), dim3(256), 0, stream, a);
+    launched = hipGetLastError();
+    if (launched != hipSuccess) break;
+  }
+  // (also after a failed launch: what was enqueued before it still reads the slot and the scratch)
+  const hipError_t marked = hipEventRecord(st->scratch_free, stream);
+  st->scratch_busy = marked == hipSuccess;
+  const int sent = slot ? st->lens.sent(slot, stream) : PEAQ_OK;
+  HIP_TRY(launched);
+  HIP_TRY(marked);
+  return sent;
+}
+
+extern "C" int peaq_batch_cut(peaq_ctx* c, int channels, int n_pairs, const float* d_in, size_t in_stride,
+                              const uint32_t* skip, const uint32_t* n_keep, float* d_out, size_t out_stride,
+                              void* stream_) {
+  const char* who = "peaq_batch_cut";
+  if (int rc = check_channels(who, channels)) return rc;
+  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, std::string(who) + ": n_pairs < 0");
+  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 65535 pairs in one call");
+  if (n_pairs > 0 && (!d_in || !d_out)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL buffer");
+  if (n_pairs > 0 && (!skip || !n_keep)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL skip or n_keep");
+  if (!c) return fail(PEAQ_ERR_ARG, std::string(who) + ": ctx is NULL");
+  if (n_pairs == 0) return PEAQ_OK;
+  std::vector<uint32_t> h(2 * (size_t)n_pairs);
+  uint32_t keep_max = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
+      return fail(PEAQ_ERR_ARG, std::string(who) + ": skip + n_keep of a pair passes in_stride");
+    h[p] = skip[p];
+    h[(size_t)n_pairs + p] = n_keep[p];
+    keep_max = std::max(keep_max, n_keep[p]);
+  }
+  if (keep_max > out_stride)
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": out_stride " + std::to_string(out_stride) +
+                                  " is smaller than the longest n_keep (" + std::to_string(keep_max) + " samples)");
+  {
+    const char* i0 = reinterpret_cast<const char*>(d_in);
+    const char* o0 = reinterpret_cast<const char*>(d_out);
+    const size_t ib = (size_t)n_pairs * in_stride * channels * sizeof(float);
+    const size_t ob = (size_t)n_pairs * out_stride * channels * sizeof(float);
+    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, std::string(who) + ": d_out overlaps d_in");
+  }
+  if (keep_max == 0) return PEAQ_OK;
+
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->al) c->al = new AlignState;
+  LenSlot* slot = nullptr;
+  if (int rc = c->al->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
+  CutArgs a{};
+  a.in = d_in;
+  a.out = d_out;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.skip = slot->dev.as<uint32_t>();
+  a.n_keep = a.skip + n_pairs;
+  a.channels = channels;
+  const size_t vecs = ((size_t)keep_max * channels + 3) / 4;
+  hipLaunchKernelGGL(align_cut_kernel, dim3((unsigned)((vecs + 255) / 256), (unsigned)n_pairs), dim3(256), 0, stream, a);
+  const hipError_t launched = hipGetLastError();
+  const int sent = c->al->lens.sent(slot, stream);   // (also after a failed launch: the copy into the slot is enqueued)
+  HIP_TRY(launched);
+  return sent;
+}
+
+extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
+                                     uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                     peaq_delay* delay, peaq_result* out) {
+  const char* who = "peaq_run_pair_aligned";
+  if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  if (int rc = check_level(who, level_db)) return rc;
+  if (rate != 48000 && !peaq_resample_supported(rate))
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
+  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
+  const size_t n[2] = {n_ref, n_test};
+  const float* src[2] = {ref, test};
+  uint32_t len[2];
+  for (int i = 0; i < 2; ++i) {
+    len[i] = (uint32_t)n[i];
+    if (rate != 48000) {
+      len[i] = peaq_resampled_length(n[i], rate);
+      if (n[i] && !len[i]) return PEAQ_ERR_ARG;      // (the message is peaq_resampled_length's)
+    }
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
+  stride += stride & 1;                              // 8-byte rows, as in peaq_run_pair
+  const size_t bytes = stride * channels * sizeof(float);
+  DevBuf d_raw[2], d_48[2], d_cut[2], d_rec, d_res;
+  HIP_TRY(d_rec.reserve(sizeof(peaq_delay)));
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(d_48[i].reserve(bytes));
+    HIP_TRY(hipMemset(d_48[i].p, 0, bytes));
+    if (!n[i]) continue;
+    if (rate == 48000) {
+      HIP_TRY(hipMemcpy(d_48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+      continue;
+    }
+    HIP_TRY(d_raw[i].reserve(n[i] * channels * sizeof(float)));
+    HIP_TRY(hipMemcpy(d_raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = peaq_batch_resample(c, channels, rate, 1, d_raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
+                                     d_48[i].as<float>(), stride, nullptr, nullptr))
+      return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = peaq_batch_estimate_delay(c, channels, 1, d_48[0].as<float>(), d_48[1].as<float>(), stride, len, len + 1,
+                                         0, max_lag, d_rec.as<peaq_delay>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  peaq_delay rec;
+  HIP_TRY(hipMemcpy(&rec, d_rec.p, sizeof rec, hipMemcpyDeviceToHost));
+  if (delay) *delay = rec;
+  uint32_t skip[2], common = 0;
+  peaq_aligned_lengths(rec.lag, len[0], len[1], &skip[0], &skip[1], &common);
+  size_t cstride = std::max<size_t>(common, 2);
+  cstride += cstride & 1;
+  const size_t cbytes = cstride * channels * sizeof(float);
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(d_cut[i].reserve(cbytes));
+    HIP_TRY(hipMemset(d_cut[i].p, 0, cbytes));
+    if (int rc = peaq_batch_cut(c, channels, 1, d_48[i].as<float>(), stride, &skip[i], &common, d_cut[i].as<float>(),
+                                cstride, nullptr))
+      return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  const uint32_t h_n[2] = {common, common};
+  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, d_cut[0].as<float>(), d_cut[1].as<float>(), cstride,
+                              h_n, h_n + 1, 0, d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}

@@ -6,6 +6,7 @@
 //   peaq_ctx.hip      errors, version, framing, context, settings, calibration
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
 //   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
+//   peaq_align.hip    delay estimation and cutting in front of the batch driver (kernels and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -157,6 +158,7 @@ struct peaq_ctx {
   int fir_fp64 = 1;                       // advanced version: arithmetic of the FIR bank (PEAQ_FIR_*; default the reference's FP64)
   peaq::Settings settings;                      // the reference's settings.h switches (peaq_ctx_set_settings)
   struct RsState* rs = nullptr;           // rate converter: tap tables per rate, length scratch (peaq_resample.hip)
+  struct AlignState* al = nullptr;        // aligner: spectra scratch, length scratch (peaq_align.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -170,6 +172,62 @@ struct peaq_ctx {
 
 // frees what peaq_batch_resample has cached in the context (peaq_resample.hip); the device is idle
 void resample_release(peaq_ctx* c);
+// the same for peaq_batch_estimate_delay / peaq_batch_cut (peaq_align.hip)
+void align_release(peaq_ctx* c);
+
+// ---------------------------------------------------------------------------
+// Per-pair host arrays of one call (lengths, skips): staged in pinned host memory and copied on the caller's stream,
+// so the call enqueues and returns.  A slot is reused kLenSlots calls later, after the event recorded behind the
+// kernel that read it.  The owner holds the context's lock around upload() and sent().
+// ---------------------------------------------------------------------------
+constexpr int kLenSlots = 4;
+struct LenSlot {
+  uint32_t* host = nullptr;     // pinned
+  size_t host_cap = 0;          // entries
+  DevBuf dev;
+  hipEvent_t done = nullptr;
+  bool pending = false;
+};
+struct LenStage {
+  LenSlot slots[kLenSlots];
+  unsigned next_slot = 0;
+
+  // `count` entries from h into the next slot, copied to its device buffer on `stream`; *out: the slot
+  int upload(const uint32_t* h, size_t count, hipStream_t stream, LenSlot** out) {
+    LenSlot* slot = &slots[next_slot++ % kLenSlots];
+    if (slot->pending) {                               // the call kLenSlots calls ago still reads this slot
+      HIP_TRY(hipEventSynchronize(slot->done));
+      slot->pending = false;
+    }
+    if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    if (count > slot->host_cap) {
+      if (slot->host) (void)hipHostFree(slot->host);
+      slot->host = nullptr;
+      slot->host_cap = 0;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&slot->host), count * sizeof(uint32_t), hipHostMallocDefault));
+      slot->host_cap = count;
+    }
+    HIP_TRY(slot->dev.reserve(count * sizeof(uint32_t)));
+    std::memcpy(slot->host, h, count * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(slot->dev.p, slot->host, count * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    *out = slot;
+    return PEAQ_OK;
+  }
+  // behind the last kernel that reads the slot
+  int sent(LenSlot* slot, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(slot->done, stream));
+    slot->pending = true;
+    return PEAQ_OK;
+  }
+  void release() {                                     // (the device is idle; the device buffers free themselves)
+    for (LenSlot& sl : slots) {
+      if (sl.host) (void)hipHostFree(sl.host);
+      if (sl.done) (void)hipEventDestroy(sl.done);
+      sl.host = nullptr;
+      sl.done = nullptr;
+    }
+  }
+};
 
 // ---- batch driver pieces used elsewhere (peaq_batch.hip) --------------------------------------------------
 unsigned fb_blocks_per_chunk(int n_pairs, int channels, uint32_t max_blocks);

@@ -216,31 +216,16 @@ struct RsPlan {
   DevBuf taps, off;
 };
 
-// Per-pair lengths of one call, [n_in | n_out]: staged in pinned host memory and copied on the caller's stream, so the
-// call enqueues and returns.  A slot is reused kLenSlots calls later, after the event recorded behind its kernel.
-constexpr int kLenSlots = 4;
-struct LenSlot {
-  uint32_t* host = nullptr;     // pinned
-  size_t host_cap = 0;          // entries
-  DevBuf dev;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
-
 }  // namespace
 
 struct RsState {
   std::map<uint32_t, std::unique_ptr<RsPlan>> plans;
-  LenSlot slots[kLenSlots];
-  unsigned next_slot = 0;
+  LenStage lens;                // per-pair lengths of one call, [n_in | n_out] (peaq_host.h)
 };
 
 void resample_release(peaq_ctx* c) {
   if (!c->rs) return;
-  for (LenSlot& sl : c->rs->slots) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
+  c->rs->lens.release();
   delete c->rs;                 // (the plans' tables and the slots' device buffers go with it)
   c->rs = nullptr;
 }
@@ -469,22 +454,7 @@ extern "C" int peaq_batch_resample(peaq_ctx* c, int channels, uint32_t rate, int
   const uint32_t* d_nout = nullptr;
   LenSlot* slot = nullptr;
   if (n_in) {
-    slot = &c->rs->slots[c->rs->next_slot++ % kLenSlots];
-    if (slot->pending) {                               // the call kLenSlots calls ago still reads this slot
-      HIP_TRY(hipEventSynchronize(slot->done));
-      slot->pending = false;
-    }
-    if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-    if (h.size() > slot->host_cap) {
-      if (slot->host) (void)hipHostFree(slot->host);
-      slot->host = nullptr;
-      slot->host_cap = 0;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&slot->host), h.size() * sizeof(uint32_t), hipHostMallocDefault));
-      slot->host_cap = h.size();
-    }
-    HIP_TRY(slot->dev.reserve(h.size() * sizeof(uint32_t)));
-    std::memcpy(slot->host, h.data(), h.size() * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(slot->dev.p, slot->host, h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (int rc = c->rs->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
     d_nin = slot->dev.as<uint32_t>();
     d_nout = d_nin + n_pairs;
   }
@@ -520,10 +490,7 @@ extern "C" int peaq_batch_resample(peaq_ctx* c, int channels, uint32_t rate, int
     hipLaunchKernelGGL(resample_any_kernel, grid, dim3(256), 0, stream, a);
   }
   HIP_TRY(hipGetLastError());
-  if (slot) {
-    HIP_TRY(hipEventRecord(slot->done, stream));
-    slot->pending = true;
-  }
+  if (slot) return c->rs->lens.sent(slot, stream);
   return PEAQ_OK;
 }
 

@@ -365,6 +365,70 @@ int peaq_resample_plan_info (uint32_t rate, peaq_resample_plan *out);
 int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
                         const float *ref, size_t n_ref, const float *test, size_t n_test, peaq_result *out);
 
+/* ---- time alignment on the device ------------------------------------------------
+ * PEAQ compares frame against frame and takes the two signals as sample-aligned (BS.1387; the reference has no
+ * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
+ * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only:
+ * no fractional delay, no gain matching, no drift, one lag per pair for all channels.
+ *
+ *   For one pair with n_ref / n_test samples per channel:
+ *   r[n] = sum_c (double) ref[n][c], t[n] likewise: the mono sum, no 1 / channels factor.
+ *   c[d] = sum_n r[n] t[n + d] over all n with 0 <= n < n_ref and 0 <= n + d < n_test, for every integer d in
+ *   [-D, D], D = max_lag, 1 <= D <= 16384 (anything else: PEAQ_ERR_ARG with a message that names it).
+ *   lag = the d with the largest |c[d]|; ties go to the smaller |d|, then to the positive one.  Positive lag: the
+ *   test signal is late, test[n + lag] belongs to ref[n].  The absolute value lets a polarity-inverted test signal
+ *   align too; the sign shows in `peak`.
+ *   peak = c[lag] (signed), runner_up = the largest |c[d]| over d != lag, norm = sqrt (sum r^2 sum t^2) over the
+ *   whole signals.  A pair in which either signal is empty or all zero gets lag = 0, peak = runner_up = 0 (and norm 0).
+ *   Arithmetic: samples FP32 as stored, everything after the conversion in FP64.  c is evaluated in the blocked
+ *   frequency-domain form (1024-point FP64 transforms over blocks of 512 samples, exact for linear correlation);
+ *   every c[d] used is within 1e-9 norm of the exact sum, peak and runner_up with it.
+ *   The arg-max is taken over these computed values, and values of |c| within 1e-12 norm of the largest count as
+ *   tied with it (the transforms' rounding, some 1e-14 norm, gives the lags of an exact tie different last bits; the
+ *   tolerance is what makes the tie rule hold for them).  So `lag` IS the exact arg-max whenever the exact largest
+ *   |c| leads every other by more than 1e-12 norm; where two are closer than that, the smaller |d| wins even if the
+ *   other is the larger by that little, and runner_up may then equal or pass |peak| by up to 1e-12 norm.
+ *   A pair with a NaN or infinite sample (or whose sum r^2 sum t^2 is not finite) has no estimate: lag = 0,
+ *   peak = runner_up = 0 and norm = NaN, which is how a caller tells it from silence (norm 0).  The record of a pair
+ *   does not depend on the other pairs of the call and is the same bit for bit run to run. */
+typedef struct {
+  int32_t lag;
+  int32_t reserved;
+  double  peak;
+  double  runner_up;
+  double  norm;
+} peaq_delay;
+/* Batch layout and lengths as for peaq_batch_run (n_ref / n_test: host arrays, both or neither; NULL = n_uniform).
+ * d_out: device array of n_pairs peaq_delay.  Enqueues on `stream` and returns; lengths travel as
+ * peaq_batch_resample's do.  The scratch (peaq_align_workspace_bytes) lives in the context and is reused across
+ * calls; a call on another stream waits, on the device, for the previous call's kernels.  channels other than 1 or
+ * 2, more than 65535 pairs, NULL buffers, a pair longer than pair_stride: PEAQ_ERR_ARG. */
+int peaq_batch_estimate_delay (peaq_ctx *ctx, int channels, int n_pairs,
+                               const float *d_ref, const float *d_test, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                               uint32_t max_lag, peaq_delay *d_out /* device, [n_pairs] */, void *stream);
+/* Scratch of peaq_batch_estimate_delay for a shape, in bytes (n_max: the longest signal of either side).  Pairs are
+ * taken in groups, so it stops growing with n_pairs at about 1 GiB.  0 for no pairs or a max_lag out of range. */
+size_t peaq_align_workspace_bytes (int channels, int n_pairs, uint32_t n_max, uint32_t max_lag);
+/* out[p][i][c] = in[p][skip[p] + i][c] for i < n_keep[p]; samples of d_out past n_keep[p] are left as they were.
+ * skip / n_keep: host arrays of n_pairs entries (pinned staging, copied on `stream`).  d_out must not overlap d_in.
+ * A pair whose skip + n_keep passes in_stride, an out_stride below the longest n_keep, NULL buffers or arrays,
+ * channels other than 1 or 2, more than 65535 pairs: PEAQ_ERR_ARG. */
+int peaq_batch_cut (peaq_ctx *ctx, int channels, int n_pairs,
+                    const float *d_in, size_t in_stride, const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                    float *d_out, size_t out_stride, void *stream);
+/* What to cut for a lag (host arithmetic): lag >= 0: the reference keeps its start, the test signal drops its first
+ * `lag` samples; lag < 0: the reference drops -lag, the test signal keeps its start (a skip stops at its signal's
+ * length).  Both are then cut to n_common = min (n_ref - skip_ref, n_test - skip_test). */
+void peaq_aligned_lengths (int32_t lag, uint32_t n_ref, uint32_t n_test,
+                           uint32_t *skip_ref, uint32_t *skip_test, uint32_t *n_common);
+/* One pair from HOST memory: upload, conversion of both to 48 kHz on the device if rate != 48000, estimate, cut, then
+ * the one-pair path of peaq_run_pair.  The lag counts 48 kHz samples (after the conversion).  delay (host, may be
+ * NULL) receives the record. */
+int peaq_run_pair_aligned (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                           uint32_t max_lag, const float *ref, size_t n_ref, const float *test, size_t n_test,
+                           peaq_delay *delay /* host */, peaq_result *out);
+
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
  * multiply-adds per wave, <= 0: about 70 ms) on the context's device -- alone: it waits for everything this PROCESS has
