@@ -10,9 +10,13 @@ every entry point raises if the HIP library or the GPU is missing.
 from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_trajectory, build_library, debug_backend, debug_frontend, debug_filterbank, debug_wave, debug_common_tables, run_pair,  # noqa: F401
                    run_pair_trajectory, library_path, load_library, synth_fill, resample, resample_plan, resampled_length, resample_supported,
                    estimate_delay, cut, align, aligned_lengths, align_workspace_bytes, Delay,
+                   decode_pcm, run_host, run_files, make_feed, feed_workspace_bytes, pcm_format, pcm_sample_bytes, Feed, HostPair,
+                   PCM_FORMATS, PCM_DTYPES,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
 __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
            "run_pair_trajectory", "library_path", "load_library", "synth_fill", "resample", "resample_plan", "resampled_length",
            "resample_supported", "estimate_delay", "cut", "align", "aligned_lengths", "align_workspace_bytes", "Delay",
+           "decode_pcm", "run_host", "run_files", "make_feed", "feed_workspace_bytes", "pcm_format", "pcm_sample_bytes", "Feed",
+           "HostPair", "PCM_FORMATS", "PCM_DTYPES",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

@@ -42,6 +42,23 @@ class Delay(C.Structure):
                 ("norm", C.c_double)]
 
 
+class HostPair(C.Structure):
+    """mirrors peaq_host_pair (include/peaq_amd.h)"""
+    _fields_ = [("ref", C.c_void_p), ("test", C.c_void_p), ("n_ref", C.c_uint64), ("n_test", C.c_uint64)]
+
+
+class Feed(C.Structure):
+    """mirrors peaq_feed (include/peaq_amd.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int), ("channels", C.c_int), ("rate", C.c_uint32),
+                ("align_max_lag", C.c_uint32), ("chunk_pairs", C.c_uint32)]
+
+
+# PEAQ_PCM_* (include/peaq_amd.h) by name, and the numpy dtype a file's samples are held in (S24: its bytes)
+PCM_FORMATS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5}
+PCM_DTYPES = {0: np.dtype(np.uint8), 1: np.dtype("<i2"), 2: np.dtype(np.uint8), 3: np.dtype("<i4"), 4: np.dtype("<f4"),
+              5: np.dtype("<f8")}
+
+
 class _Calibration(C.Structure):
     _fields_ = [("elapsed_ms", C.c_double), ("shader_clock_mhz", C.c_double), ("fp64_tflops", C.c_double),
                 ("cycles_per_fma", C.c_double), ("max_clock_mhz", C.c_double), ("compute_units", C.c_int),
@@ -155,6 +172,15 @@ def load_library():
         L.peaq_aligned_lengths.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
         L.peaq_run_pair_aligned.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t,
                                             fp, C.c_size_t, C.POINTER(Delay), dp]
+    L.peaq_pcm_sample_bytes.restype = C.c_size_t
+    L.peaq_pcm_sample_bytes.argtypes = [C.c_int]
+    L.peaq_feed_size.restype = C.c_size_t
+    L.peaq_feed_size.argtypes = []
+    L.peaq_batch_decode_pcm.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, u32p, C.c_uint32, vp, C.c_size_t, vp]
+    L.peaq_batch_run_host.argtypes = [vp, C.c_int, C.c_double, C.POINTER(Feed), C.c_size_t, C.POINTER(HostPair), dp,
+                                      C.POINTER(Delay)]
+    L.peaq_feed_workspace_bytes.restype = C.c_size_t
+    L.peaq_feed_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_size_t, C.c_uint64]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -698,6 +724,122 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
                                out.ctypes.data_as(C.POINTER(C.c_double))))
     return _result_dict(out, bool(advanced))
+
+
+def pcm_format(format):
+    """PEAQ_PCM_* of a name ('u8' 's16' 's24' 's32' 'f32' 'f64') or of the number itself"""
+    return PCM_FORMATS[format] if isinstance(format, str) else int(format)
+
+
+def pcm_sample_bytes(format):
+    """bytes per sample of a format, 0 for an unknown one (peaq_pcm_sample_bytes)"""
+    return int(load_library().peaq_pcm_sample_bytes(pcm_format(format)))
+
+
+def decode_pcm(ctx, raw, format, channels, n=None, out=None, stream=None):
+    """Decodes a batch in a file's own sample format on the device (peaq_batch_decode_pcm).  raw: CUDA uint8 tensor
+    [pairs, stride * channels * sample_bytes], pair p's samples from its row's first byte on.  n: optional per-pair lengths
+    (samples per channel; without them every pair has `stride`).  out: optional float32 tensor [pairs, out_stride, channels]
+    to write into (samples past a pair's length keep what they held); without it a zero-filled one with an even stride
+    is made.  Returns out."""
+    import torch
+    fmt = pcm_format(format)
+    sb = pcm_sample_bytes(fmt)
+    assert raw.is_cuda and raw.dtype == torch.uint8 and raw.is_contiguous() and raw.dim() == 2 and sb
+    n_pairs, row = raw.shape
+    assert row % (channels * sb) == 0, "a row is stride * channels * sample_bytes bytes"
+    stride = row // (channels * sb)
+    a_n = None if n is None else np.ascontiguousarray(n, dtype=np.uint32)
+    if out is None:
+        o_stride = max(stride, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the decoder runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=raw.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_decode_pcm(ctx.h, fmt, int(channels), n_pairs, C.c_void_p(raw.data_ptr()), stride,
+                                       a_n.ctypes.data_as(u32p) if a_n is not None else None, stride,
+                                       C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
+
+
+def make_feed(format, channels, rate=48000, align=None, chunk_pairs=0):
+    """a peaq_feed (include/peaq_amd.h) with this library's struct_size"""
+    return Feed(C.sizeof(Feed), pcm_format(format), int(channels), int(rate), 0 if align is None else int(align),
+                int(chunk_pairs))
+
+
+def feed_workspace_bytes(feed, advanced, n_pairs, n_max):
+    """staging, device buffers and workspaces of a run_host call (peaq_feed_workspace_bytes)"""
+    return int(load_library().peaq_feed_workspace_bytes(C.byref(feed), int(bool(advanced)), int(n_pairs), int(n_max)))
+
+
+def _run_host_rows(ctx, advanced, pairs, format, channels, rate, align, chunk_pairs, playback_level):
+    """peaq_batch_run_host on numpy arrays -> (rows float64 [n_pairs, 16], the Delay records or None)"""
+    fmt = pcm_format(format)
+    unit = pcm_sample_bytes(fmt) * int(channels)
+    assert unit, "unknown sample format"
+    keep, rows = [], (HostPair * max(len(pairs), 1))()
+    for p, pair in enumerate(pairs):
+        for i, x in enumerate(pair):
+            x = np.asarray(x)
+            assert x.dtype == PCM_DTYPES[fmt], f"pair {p}: {x.dtype} is not the dtype of this format ({PCM_DTYPES[fmt]})"
+            if not x.flags.c_contiguous:
+                x = np.ascontiguousarray(x)
+            assert x.nbytes % unit == 0, f"pair {p}: not a whole number of samples per channel"
+            keep.append(x)                             # (the arrays stay alive until the call has returned)
+            setattr(rows[p], ("ref", "test")[i], x.ctypes.data if x.nbytes else None)
+            setattr(rows[p], ("n_ref", "n_test")[i], x.nbytes // unit)
+    feed = make_feed(fmt, channels, rate, align, chunk_pairs)
+    out = np.zeros((max(len(pairs), 1), RESULT_DOUBLES))
+    rec = (Delay * max(len(pairs), 1))() if align is not None else None
+    _check(ctx.L.peaq_batch_run_host(ctx.h, int(bool(advanced)), float(playback_level), C.byref(feed), len(pairs), rows,
+                                     out.ctypes.data_as(C.POINTER(C.c_double)), rec))
+    del keep
+    return out[:len(pairs)], rec
+
+
+def run_host(ctx, advanced, pairs, format, channels, rate=48000, align=None, chunk_pairs=0, playback_level=92.0):
+    """Scores a list of pairs that sit in host memory in a file's own sample format (peaq_batch_run_host): upload, decode,
+    rate conversion, alignment and scoring on the device, chunk by chunk.  pairs: [(ref, test)] numpy arrays in the
+    file's dtype (PCM_DTYPES; S24: the bytes), interleaved, any shape; they may be unaligned views.  rate: sampling rate
+    of all of them.  align: a max_lag in 48 kHz samples.  Returns the result dicts in list order, and with `align`
+    (results, delays): delays a dict of numpy arrays lag / peak / runner_up / norm as estimate_delay's."""
+    out, rec = _run_host_rows(ctx, advanced, pairs, format, channels, rate, align, chunk_pairs, playback_level)
+    res = [_result_dict(r, bool(advanced)) for r in out]
+    if align is None:
+        return res
+    delays = {k: np.array([getattr(rec[p], k) for p in range(len(pairs))], dtype=np.int32 if k == "lag" else np.float64)
+              for k in ("lag", "peak", "runner_up", "norm")}
+    return res, delays
+
+
+def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92.0):
+    """Scores a list of (ref_path, test_path) RIFF/WAVE files: the data chunks are read as they are (wavio.read_wav_raw),
+    the pairs grouped by (format, channels, rate) and each group run through run_host.  Returns the result dicts in
+    list order, and with `align` (results, delays), delays a list of dicts.  ValueError, naming the file, if the two
+    files of a pair differ in channels, rate or format."""
+    from . import wavio
+    groups, loaded = {}, []
+    for p, (ref_path, test_path) in enumerate(files):
+        r = wavio.read_wav_raw(ref_path)
+        t = wavio.read_wav_raw(test_path)
+        for what, a, b in (("format", r[1], t[1]), ("channel count", r[2], t[2]), ("rate", r[3], t[3])):
+            if a != b:
+                raise ValueError(f"{test_path}: {what} {b} differs from {ref_path}'s ({a})")
+        loaded.append((r[0], t[0]))
+        groups.setdefault((r[1], r[2], r[3]), []).append(p)
+    results, delays = [None] * len(files), [None] * len(files)
+    for (fmt, channels, rate), members in groups.items():
+        arrays = [tuple(np.frombuffer(b, dtype=PCM_DTYPES[fmt]) for b in loaded[p]) for p in members]
+        got = run_host(ctx, advanced, arrays, fmt, channels, rate=rate, align=align, chunk_pairs=chunk_pairs,
+                       playback_level=playback_level)
+        res, dl = got if align is not None else (got, None)
+        for i, p in enumerate(members):
+            results[p] = res[i]
+            if dl is not None:
+                delays[p] = {k: dl[k][i].item() for k in dl}
+    return (results, delays) if align is not None else results
 
 
 def synth_fill(ctx, seed0, n_pairs, channels, n_samples, device="cuda:0", stream=None, out=None):

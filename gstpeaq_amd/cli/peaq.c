@@ -28,6 +28,12 @@
  * --interval=SECONDS also prints, before those two lines, one line per reading taken every SECONDS of the (resampled)
  * signals, "Time %.3f s: ODG %.3f, DI %.3f" -- what the element's odg / di properties read at that point of the stream
  * (gstpeaq.c:484-497; peaq_run_pair_trajectory).
+ * --list=FILE scores many pairs in one run: FILE holds one pair per line, REF<TAB>TEST (empty lines and lines that
+ * start with # are skipped).  The files' data chunks are handed to the engine as they are, in their own sample format
+ * (peaq_batch_run_host: decoded, converted to 48 kHz and, with --align, aligned on the device), grouped by format,
+ * channel count and rate; one line per pair in list order, REF<TAB>TEST<TAB>ODG<TAB>DI.  Nothing is scored (exit
+ * status 2) if a file cannot be read, the two files of a pair differ in format, or a rate is one the device converter
+ * does not take.
  */
 #include <math.h>
 #include <stdint.h>
@@ -134,6 +140,177 @@ wav_read (const char *path, wav_t * w)
   fprintf (stderr, "Error: %s: no usable fmt/data chunks\n", path);
   fclose (f);
   return -1;
+}
+
+/* ---- --list: the data chunk as it is, for peaq_batch_run_host ---- */
+typedef struct
+{
+  unsigned char *bytes;         /* the data chunk, whole samples per channel only */
+  size_t frames;                /* samples per channel */
+  int format;                   /* PEAQ_PCM_* */
+  int channels, rate;
+} raw_t;
+
+static int
+wav_read_raw (const char *path, raw_t * w)
+{
+  FILE *f = fopen (path, "rb");
+  unsigned char hdr[12], ck[8];
+  int fmt_tag = 0, bits = 0, have_fmt = 0, block_align = 0;
+  memset (w, 0, sizeof *w);
+  if (!f) {
+    fprintf (stderr, "Error: cannot open %s\n", path);
+    return -1;
+  }
+  if (fread (hdr, 1, 12, f) != 12 || memcmp (hdr, "RIFF", 4) || memcmp (hdr + 8, "WAVE", 4)) {
+    fprintf (stderr, "Error: %s is not a RIFF/WAVE file\n", path);
+    fclose (f);
+    return -1;
+  }
+  while (fread (ck, 1, 8, f) == 8) {
+    uint32_t size = rd32 (ck + 4);
+    if (!memcmp (ck, "fmt ", 4)) {
+      unsigned char fmt[40];
+      uint32_t n = size < sizeof fmt ? size : sizeof fmt;
+      if (size < 16 || fread (fmt, 1, n, f) != n)
+        break;
+      fmt_tag = fmt[0] | (fmt[1] << 8);
+      w->channels = fmt[2] | (fmt[3] << 8);
+      w->rate = (int) rd32 (fmt + 4);
+      block_align = fmt[12] | (fmt[13] << 8);
+      bits = fmt[14] | (fmt[15] << 8);
+      if (fmt_tag == 0xFFFE && size >= 26)
+        fmt_tag = fmt[24] | (fmt[25] << 8);
+      have_fmt = 1;
+      if (size > n)
+        fseek (f, (long) (size - n), SEEK_CUR);
+      if (size & 1)
+        fseek (f, 1, SEEK_CUR);
+    } else if (!memcmp (ck, "data", 4) && have_fmt) {
+      size_t bytes_per = (size_t) bits / 8, total;
+      w->format = fmt_tag == 3 ? (bits == 32 ? PEAQ_PCM_F32 : bits == 64 ? PEAQ_PCM_F64 : -1)
+          : fmt_tag == 1 ? (bits == 8 ? PEAQ_PCM_U8 : bits == 16 ? PEAQ_PCM_S16 : bits == 24 ? PEAQ_PCM_S24 : bits ==
+          32 ? PEAQ_PCM_S32 : -1) : -1;
+      if (w->channels < 1 || w->channels > 2 || block_align != (int) bytes_per * w->channels || w->format < 0) {
+        fprintf (stderr, "Error: %s: unsupported WAVE format (tag %d, %d bit, %d channels)\n", path,
+            fmt_tag, bits, w->channels);
+        fclose (f);
+        return -1;
+      }
+      w->bytes = malloc (size ? size : 1);
+      total = fread (w->bytes, 1, size, f) / bytes_per;        /* tolerate a truncated data chunk */
+      w->frames = total / w->channels;
+      fclose (f);
+      return 0;
+    } else {
+      fseek (f, (long) (size + (size & 1)), SEEK_CUR);
+    }
+  }
+  fprintf (stderr, "Error: %s: no usable fmt/data chunks\n", path);
+  fclose (f);
+  return -1;
+}
+
+/* scores the pairs of `list_path`; the exit status */
+static int
+run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
+{
+  FILE *f = fopen (list_path, "r");
+  char *line = NULL, **names = NULL;
+  size_t cap = 0, n_pairs = 0, room = 0, p, q;
+  raw_t *raw = NULL;
+  peaq_result *res = NULL;
+  peaq_host_pair *hp = NULL;
+  size_t *members = NULL;
+  char *done = NULL;
+  peaq_ctx *ctx = NULL;
+  ssize_t len;
+  if (!f) {
+    fprintf (stderr, "Error: cannot open %s\n", list_path);
+    return 2;
+  }
+  while ((len = getline (&line, &cap, f)) >= 0) {
+    char *tab;
+    while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r'))
+      line[--len] = 0;
+    if (!len || line[0] == '#')
+      continue;
+    tab = strchr (line, '\t');
+    if (!tab || !tab[1] || tab == line || strchr (tab + 1, '\t')) {
+      fprintf (stderr, "Error: %s: a line is not REF<TAB>TEST: %s\n", list_path, line);
+      return 2;
+    }
+    if (n_pairs == room) {
+      room = room ? 2 * room : 64;
+      names = realloc (names, 2 * room * sizeof *names);
+    }
+    *tab = 0;
+    names[2 * n_pairs] = strdup (line);
+    names[2 * n_pairs + 1] = strdup (tab + 1);
+    n_pairs++;
+  }
+  free (line);
+  fclose (f);
+  raw = calloc (2 * n_pairs + 1, sizeof *raw);
+  res = calloc (n_pairs + 1, sizeof *res);
+  hp = calloc (n_pairs + 1, sizeof *hp);
+  members = calloc (n_pairs + 1, sizeof *members);
+  done = calloc (n_pairs + 1, 1);
+  for (p = 0; p < n_pairs; p++) {
+    const raw_t *r = &raw[2 * p], *t = &raw[2 * p + 1];
+    if (wav_read_raw (names[2 * p], &raw[2 * p]) || wav_read_raw (names[2 * p + 1], &raw[2 * p + 1]))
+      return 2;
+    if (r->format != t->format || r->channels != t->channels || r->rate != t->rate) {
+      fprintf (stderr, "Error: %s and %s differ in sample format, channel count or rate\n", names[2 * p], names[2 * p + 1]);
+      return 2;
+    }
+    if (r->rate != 48000 && !peaq_resample_supported ((uint32_t) r->rate)) {
+      fprintf (stderr, "Note: the device converter does not take %d Hz (%s)\n", r->rate, names[2 * p]);
+      return 2;
+    }
+  }
+  if (n_pairs && peaq_ctx_create (getenv ("PEAQ_AMD_DEVICE") ? atoi (getenv ("PEAQ_AMD_DEVICE")) : 0, &ctx) != PEAQ_OK) {
+    printf ("Error: peaq engine could not be instantiated - %s\n", peaq_last_error ());
+    return 2;
+  }
+  for (p = 0; p < n_pairs; p++) {
+    /* the pairs that share this one's format, channel count and rate: one call */
+    peaq_feed feed;
+    size_t n = 0;
+    if (done[p])
+      continue;
+    for (q = p; q < n_pairs; q++)
+      if (!done[q] && raw[2 * q].format == raw[2 * p].format && raw[2 * q].channels == raw[2 * p].channels
+          && raw[2 * q].rate == raw[2 * p].rate) {
+        hp[n].ref = raw[2 * q].bytes;
+        hp[n].test = raw[2 * q + 1].bytes;
+        hp[n].n_ref = raw[2 * q].frames;
+        hp[n].n_test = raw[2 * q + 1].frames;
+        members[n++] = q;
+        done[q] = 1;
+      }
+    memset (&feed, 0, sizeof feed);
+    feed.struct_size = (uint32_t) sizeof feed;
+    feed.format = raw[2 * p].format;
+    feed.channels = raw[2 * p].channels;
+    feed.rate = (uint32_t) raw[2 * p].rate;
+    feed.align_max_lag = align_lag;
+    {
+      peaq_result *out = malloc (n * sizeof *out);
+      if (peaq_batch_run_host (ctx, advanced, level, &feed, n, hp, out, NULL) != PEAQ_OK) {
+        fprintf (stderr, "Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      for (q = 0; q < n; q++)
+        res[members[q]] = out[q];
+      free (out);
+    }
+  }
+  for (p = 0; p < n_pairs; p++)
+    printf ("%s\t%s\t%.3f\t%.3f\n", names[2 * p], names[2 * p + 1], res[p].odg, res[p].di);
+  if (ctx)
+    peaq_ctx_destroy (ctx);
+  return 0;
 }
 
 /* ---- sample-rate conversion to 48 kHz (stands in for audioresample, peaq.c:154-209) ----
@@ -266,7 +443,9 @@ usage (const char *prog)
       "                (the plain one-call mode only: not with --interval; both files at one rate)\n"
       "  --interval=S  also print ODG and DI read every S seconds through the files\n"
       "  --align[=SAMPLES] find the test file's delay within +-SAMPLES (48 kHz samples, 1..16384, default 4096)\n"
-      "                on the GPU and compare the aligned parts (the plain one-call mode only)\n", prog);
+      "                on the GPU and compare the aligned parts (the plain one-call mode only)\n"
+      "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
+      "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n", prog);
 }
 
 int
@@ -278,6 +457,7 @@ main (int argc, char **argv)
   peaq_delay delay;
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
+  const char *list_path = NULL;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
   peaq_session *s = NULL;
@@ -314,6 +494,8 @@ main (int argc, char **argv)
         return 1;
       }
     }
+    else if (!strncmp (argv[i], "--list=", 7))
+      list_path = argv[i] + 7;
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -327,6 +509,13 @@ main (int argc, char **argv)
       files[nfiles++] = argv[i];
     else
       nfiles++;
+  }
+  if (list_path) {
+    if (nfiles || interval_s > 0.) {
+      fprintf (stderr, "Failed to initialize: --list takes no REFFILE TESTFILE and no --interval\n");
+      return 1;
+    }
+    return run_list (list_path, advanced, level, align_lag);
   }
   if (nfiles != 2) {
     usage (argv[0]);

@@ -52,3 +52,41 @@ def read_wav(path):
     else:
         raise ValueError(f"{path}: unsupported WAVE format (tag {tag}, {bits} bit)")
     return np.ascontiguousarray(x.reshape(-1, ch)), rate
+
+
+# (fmt tag, bits) -> PEAQ_PCM_* (include/peaq_amd.h)
+_PCM_FORMAT = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
+
+
+def read_wav_raw(path):
+    """-> (data, format, channels, sample_rate, n): the data chunk's bytes as they are (a memoryview, whole samples per
+    channel only), the PEAQ_PCM_* format they are in, and n samples per channel -- what gstpeaq_amd.run_host and
+    decode_pcm take.  Same chunk walk and checks as read_wav."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    pos, fmt, body = 12, None, None
+    view = memoryview(data)
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], struct.unpack_from("<I", data, pos + 4)[0]
+        if cid == b"fmt ":
+            chunk = data[pos + 8:pos + 8 + size]
+            tag, ch, rate, _, _, bits = struct.unpack_from("<HHIIHH", chunk, 0)
+            if tag == 0xFFFE and len(chunk) >= 26:
+                tag = struct.unpack_from("<H", chunk, 24)[0]
+            fmt = (tag, ch, rate, bits)
+        elif cid == b"data":
+            body = view[pos + 8:pos + 8 + size]
+            break
+        pos += 8 + size + (size & 1)
+    if fmt is None or body is None:
+        raise ValueError(f"{path}: fmt or data chunk missing")
+    tag, ch, rate, bits = fmt
+    if ch < 1:
+        raise ValueError(f"{path}: no channels")
+    if (tag, bits) not in _PCM_FORMAT:
+        raise ValueError(f"{path}: unsupported WAVE format (tag {tag}, {bits} bit)")
+    nbytes = bits // 8
+    n = len(body) // (nbytes * ch)
+    return body[:n * ch * nbytes], _PCM_FORMAT[(tag, bits)], ch, rate, n

@@ -429,6 +429,73 @@ int peaq_run_pair_aligned (peaq_ctx *ctx, int advanced, int channels, double pla
                            uint32_t max_lag, const float *ref, size_t n_ref, const float *test, size_t n_test,
                            peaq_delay *delay /* host */, peaq_result *out);
 
+/* ---- PCM from host memory: device decoder and host-fed batch ------------------------
+ * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
+ * memory.  peaq_batch_decode_pcm converts a batch in the file's own sample format on the device, and
+ * peaq_batch_run_host scores a list of pairs that sit in host memory in that format: upload, decode, rate conversion,
+ * alignment and scoring, chunk by chunk, the next chunk's upload beside the running chunk's kernels.
+ *
+ * The decoded sample is bit for bit what gstpeaq_amd/cli/peaq.c (wav_read) and gstpeaq_amd/wavio.py (read_wav)
+ * produce: the value in double, divided, rounded ONCE to FP32.  U8, S16 and S24 are exact; S32 and F64 round to
+ * nearest even; an F64 beyond the FP32 range becomes +-Inf as the C cast does; F32 copies the bits (NaN payloads too). */
+#define PEAQ_PCM_U8  0   /* unsigned 8 bit            (x - 128) / 128        */
+#define PEAQ_PCM_S16 1   /* little endian             x / 32768              */
+#define PEAQ_PCM_S24 2   /* packed, 3 bytes, LE       x / 8388608            */
+#define PEAQ_PCM_S32 3   /*                           x / 2147483648         */
+#define PEAQ_PCM_F32 4   /* IEEE float, bits copied as they are              */
+#define PEAQ_PCM_F64 5   /* IEEE double, one rounding to FP32 (nearest even) */
+size_t peaq_pcm_sample_bytes (int format);          /* 1 2 3 4 4 8; 0 for an unknown format */
+/* d_in: the batch layout in the file's own sample format, interleaved [pair][sample][channel]; pair p starts at BYTE
+ * p * in_stride * channels * sample_bytes, so with S24 (and U8, S16) pair bases fall on any byte phase.  d_in itself
+ * must be at least 4-byte aligned.  Lengths as for peaq_batch_resample: n_in (host array of n_pairs entries, through
+ * pinned staging slots; NULL = n_uniform each).  d_out: interleaved F32 with out_stride samples per channel between
+ * pairs; samples of d_out past a pair's length are left untouched.  Enqueues on `stream` and synchronises nothing.
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: an unknown format,
+ * channels other than 1 or 2, more than 65535 pairs, NULL buffers, a d_in that is not 4-byte aligned, a pair longer
+ * than in_stride, an out_stride below the longest pair. */
+int peaq_batch_decode_pcm (peaq_ctx *ctx, int format, int channels, int n_pairs,
+                           const void *d_in, size_t in_stride, const uint32_t *n_in, uint32_t n_uniform,
+                           float *d_out, size_t out_stride, void *stream);
+
+typedef struct { const void *ref, *test; uint64_t n_ref, n_test; } peaq_host_pair;   /* samples per channel */
+typedef struct peaq_feed {
+  uint32_t struct_size;     /* sizeof (peaq_feed) of the CALLER; anything else than this library's: PEAQ_ERR_ARG */
+  int      format, channels;
+  uint32_t rate;            /* 48000, or a rate peaq_resample_supported takes */
+  uint32_t align_max_lag;   /* 0: no alignment; else 1..16384 as peaq_batch_estimate_delay */
+  uint32_t chunk_pairs;     /* 0: the library chooses; else pairs per chunk (1..65535) */
+} peaq_feed;
+size_t peaq_feed_size (void);
+/* results[p] is bit for bit what this sequence writes for pair p, whatever the chunking and whatever the other pairs
+ * of the call are: (1) peaq_batch_decode_pcm of both buffers; (2) if rate != 48000, peaq_batch_resample of both;
+ * (3) if align_max_lag, peaq_batch_estimate_delay, peaq_aligned_lengths and peaq_batch_cut of both -- delays[p]
+ * (host, may be NULL) is that record, its lag in 48 kHz samples; without alignment delays[] is zeroed; (4)
+ * peaq_batch_run with the context's settings and FIR mode.  Source buffers may be pageable and unaligned.  Synchronous:
+ * returns when `results` (host, n_pairs records) is complete.  On a device error it stops, starts nothing more, waits
+ * for what runs and returns the error.
+ * Pipeline: pairs are taken in chunks; a chunk's raw bytes are packed into one of two pinned staging sets at the
+ * chunk's own stride (its longest signal) and copied on a copy stream, decode through score run on a compute stream,
+ * events order the two, results come back per chunk.  Chunk size: as many pairs as fit PEAQ_FEED_BUDGET_BYTES (4 GiB)
+ * of staging plus device buffers -- per pair four raw signals in pinned memory (two sets), four in device memory, two
+ * decoded F32 signals, two converted ones if rate != 48000 and two cut ones if aligned; the batch and aligner
+ * workspaces are their own (peaq_feed_workspace_bytes counts them) --, never more than 65535, and a pair that alone
+ * exceeds the budget runs as a chunk of one.  All buffers live in the context, are reused across calls and freed with
+ * it.  The copy into the staging set is shared by PEAQ_FEED_DEFAULT_THREADS (8) host threads, started per chunk;
+ * the environment variable PEAQ_AMD_FEED_THREADS = 1 .. 16 sets another count (anything else: PEAQ_ERR_ARG that names
+ * it); the count never follows the machine's CPU count.
+ * PEAQ_ERR_ARG before any device is touched: a wrong struct_size, an unknown format, channels other than 1 or 2, a
+ * rate the device converter does not take, align_max_lag above 16384, chunk_pairs above 65535, a playback level
+ * outside 0..130, NULL arguments, a pair with samples but no buffer, a pair of more than 2^32 - 1 samples (before or
+ * after the conversion). */
+#define PEAQ_FEED_BUDGET_BYTES   ((size_t) 4 << 30)
+#define PEAQ_FEED_DEFAULT_THREADS 8
+int peaq_batch_run_host (peaq_ctx *ctx, int advanced, double playback_level_db, const peaq_feed *feed,
+                         size_t n_pairs, const peaq_host_pair *pairs,
+                         peaq_result *results /* host, [n_pairs] */, peaq_delay *delays /* host, may be NULL */);
+/* Staging, device buffers and the batch (and aligner) workspace of a call of n_pairs pairs of at most n_max samples
+ * per channel (at the feed's rate), in bytes; 0 for a feed peaq_batch_run_host would refuse. */
+size_t peaq_feed_workspace_bytes (const peaq_feed *feed, int advanced, size_t n_pairs, uint64_t n_max);
+
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
  * multiply-adds per wave, <= 0: about 70 ms) on the context's device -- alone: it waits for everything this PROCESS has
