@@ -12,6 +12,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    estimate_delay, cut, align, aligned_lengths, align_workspace_bytes, Delay,
                    decode_pcm, run_host, run_files, make_feed, feed_workspace_bytes, pcm_format, pcm_sample_bytes, Feed, HostPair,
                    PCM_FORMATS, PCM_DTYPES,
+                   batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
+                   TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
 __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
@@ -19,4 +21,6 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "resample_supported", "estimate_delay", "cut", "align", "aligned_lengths", "align_workspace_bytes", "Delay",
            "decode_pcm", "run_host", "run_files", "make_feed", "feed_workspace_bytes", "pcm_format", "pcm_sample_bytes", "Feed",
            "HostPair", "PCM_FORMATS", "PCM_DTYPES",
+           "batch_trace", "run_pair_trace", "frame_count", "FrameTrace", "BlockTrace", "FRAME_TRACE_DTYPE", "BLOCK_TRACE_DTYPE",
+           "TRACE_ABOVE", "TRACE_MOD_OPEN", "TRACE_LOUD_OPEN", "TRACE_FLUSH",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

@@ -42,6 +42,27 @@ class Delay(C.Structure):
                 ("norm", C.c_double)]
 
 
+class FrameTrace(C.Structure):
+    """mirrors peaq_frame_trace (include/peaq_amd.h)"""
+    _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
+                ("frame", C.c_uint32), ("reserved", C.c_double)]
+
+
+class BlockTrace(C.Structure):
+    """mirrors peaq_block_trace (include/peaq_amd.h)"""
+    _fields_ = [("ch", (C.c_double * 5) * 2), ("flags", C.c_uint32), ("block", C.c_uint32), ("reserved", C.c_double)]
+
+
+# PEAQ_TRACE_* (include/peaq_amd.h) and the records as numpy structured dtypes; the names of the values in `ch`
+TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH = 1, 2, 4, 8
+FRAME_TRACE_DTYPE = np.dtype([("ch", "<f8", (2, 6)), ("p_detect", "<f8"), ("steps", "<f8"), ("flags", "<u4"),
+                              ("frame", "<u4"), ("reserved", "<f8")])
+BLOCK_TRACE_DTYPE = np.dtype([("ch", "<f8", (2, 5)), ("flags", "<u4"), ("block", "<u4"), ("reserved", "<f8")])
+FRAME_TRACE_VALUES = ["moddiff1", "moddiff2", "tempwt", "noiseloud", "nmr_mean", "nmr_max"]
+FRAME_TRACE_VALUES_ADVANCED = ["segnmr_db", "nmr_mean"]
+BLOCK_TRACE_VALUES = ["rmsmoddiff", "tempwt", "noiseloud", "missing", "lindist"]
+
+
 class HostPair(C.Structure):
     """mirrors peaq_host_pair (include/peaq_amd.h)"""
     _fields_ = [("ref", C.c_void_p), ("test", C.c_void_p), ("n_ref", C.c_uint64), ("n_test", C.c_uint64)]
@@ -154,6 +175,13 @@ def load_library():
         L.peaq_batch_trajectory_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.peaq_run_pair_trajectory.argtypes = [vp, C.c_int, C.c_int, C.c_double, fp, C.c_size_t, fp, C.c_size_t,
                                                C.c_uint32, C.c_int, dp, dp]
+    if hasattr(L, "peaq_batch_run_trace"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_batch_run_trace.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p,
+                                           C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        L.peaq_trace_sizes.restype = C.c_size_t
+        L.peaq_trace_sizes.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.peaq_run_pair_trace.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
+                                          C.c_size_t, vp, C.c_size_t, u32p, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_resample_supported.argtypes = [C.c_uint32]
         L.peaq_resampled_length.restype = C.c_uint32
@@ -693,6 +721,108 @@ def run_pair_trajectory(ctx, advanced, ref, test, interval, n_points, playback_l
                                           test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
                                           int(interval), int(n_points), pts.ctypes.data_as(dp), out.ctypes.data_as(dp)))
     return [_result_dict(r, bool(advanced)) for r in pts], _result_dict(out, bool(advanced))
+
+
+def _check_trace_sizes(L):
+    fb, bb = C.c_size_t(0), C.c_size_t(0)
+    L.peaq_trace_sizes(C.byref(fb), C.byref(bb))
+    if (fb.value, bb.value) != (C.sizeof(FrameTrace), C.sizeof(BlockTrace)) or \
+            (fb.value, bb.value) != (FRAME_TRACE_DTYPE.itemsize, BLOCK_TRACE_DTYPE.itemsize):
+        raise PeaqError(f"the library's trace records are {fb.value} and {bb.value} bytes, this binding's "
+                        f"{C.sizeof(FrameTrace)} and {C.sizeof(BlockTrace)}")
+
+
+def frame_count(n_ref, n_test, filter_bank=False):
+    """frames (filter_bank: blocks) of a pair with these lengths, the flush's included (peaq_frame_count)"""
+    return int(load_library().peaq_frame_count(int(n_ref), int(n_test), int(bool(filter_bank))))
+
+
+def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
+                stream=None, sync=True, d_frames=None, d_blocks=None):
+    """The MOV layer's values of every frame and block of every pair, in the run that scores them
+    (peaq_batch_run_trace).  ref/test, n_ref/n_test, rate and align as for batch_run.  d_frames / d_blocks: optional
+    record tensors to write into (CUDA uint8 [n_pairs, stride, 128] / [.., 96]; records past a pair's count keep what
+    they held); without them zero-filled ones of the longest pair's count are made.
+    Returns a dict: d_frames / d_blocks, the record tensors (CUDA uint8 [n_pairs, stride, 128] / [n_pairs, stride, 96],
+    zero-filled past each pair's count; d_blocks None in the basic version), d_results [n_pairs, 16], n_frames /
+    n_blocks (numpy, the counts per pair), and with sync=True frames / blocks (numpy structured views of the records by
+    field name, FRAME_TRACE_DTYPE / BLOCK_TRACE_DTYPE, [n_pairs, stride]) and results (result dicts)."""
+    import torch
+    _check_trace_sizes(ctx.L)
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
+    cnt = {rt: (frame_count(*rt), frame_count(*rt, True) if advanced else 0) for rt in set(lens)}   # once per distinct pair of lengths
+    n_frames = np.array([cnt[rt][0] for rt in lens], dtype=np.uint32)
+    n_blocks = np.array([cnt[rt][1] for rt in lens], dtype=np.uint32)
+    f_stride = max(int(n_frames.max()) if n_pairs else 0, 1)
+    b_stride = max(int(n_blocks.max()) if n_pairs else 0, 1)
+    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
+        if d_frames is None:
+            d_frames = torch.zeros((n_pairs, f_stride, C.sizeof(FrameTrace)), dtype=torch.uint8, device=ref.device)
+        if d_blocks is None and advanced:
+            d_blocks = torch.zeros((n_pairs, b_stride, C.sizeof(BlockTrace)), dtype=torch.uint8, device=ref.device)
+        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    for t, size in ((d_frames, C.sizeof(FrameTrace)),) + (((d_blocks, C.sizeof(BlockTrace)),) if advanced else ()):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3
+        assert t.shape[0] == n_pairs and t.shape[2] == size
+    f_stride, b_stride = d_frames.shape[1], d_blocks.shape[1] if advanced else 0
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_run_trace(ctx.h, int(bool(advanced)), channels, float(playback_level), n_pairs,
+                                      C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                      a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                      a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                      C.c_void_p(d_frames.data_ptr()), f_stride,
+                                      C.c_void_p(d_blocks.data_ptr()) if advanced else None, b_stride,
+                                      C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    out = dict(d_frames=d_frames, d_blocks=d_blocks if advanced else None, d_results=results, n_frames=n_frames, n_blocks=n_blocks)
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    out["frames"] = d_frames.cpu().numpy().view(FRAME_TRACE_DTYPE)[:, :, 0]
+    out["blocks"] = d_blocks.cpu().numpy().view(BLOCK_TRACE_DTYPE)[:, :, 0] if advanced else None
+    out["results"] = [_result_dict(r, advanced) for r in results.cpu().numpy()]
+    return out
+
+
+def run_pair_trace(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_trace: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
+    first with align = a max_lag in 48 kHz samples.  Returns a dict: frames / blocks (numpy structured arrays
+    FRAME_TRACE_DTYPE / BLOCK_TRACE_DTYPE of the counts written; blocks None in the basic version), result (a result
+    dict) and, with align, delay."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    ch = ref.shape[1]
+    assert test.shape[1] == ch
+    _check_trace_sizes(ctx.L)
+    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
+    f_cap = max(frame_count(*lens), 1)
+    b_cap = max(frame_count(*lens, True), 1) if advanced else 0
+    frames = np.zeros(f_cap, dtype=FRAME_TRACE_DTYPE)
+    blocks = np.zeros(b_cap, dtype=BLOCK_TRACE_DTYPE) if advanced else None
+    nf, nb, rec, out = C.c_uint32(0), C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_trace(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),
+                                     0 if align is None else int(align),
+                                     ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                     test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                     C.c_void_p(frames.ctypes.data), f_cap, C.byref(nf),
+                                     C.c_void_p(blocks.ctypes.data) if advanced else None, b_cap, C.byref(nb),
+                                     C.byref(rec), out.ctypes.data_as(C.POINTER(C.c_double))))
+    res = dict(frames=frames[:nf.value], blocks=blocks[:nb.value] if advanced else None,
+               result=_result_dict(out, bool(advanced)))
+    if align is not None:
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+    return res
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None):

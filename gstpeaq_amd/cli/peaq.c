@@ -444,8 +444,81 @@ usage (const char *prog)
       "  --interval=S  also print ODG and DI read every S seconds through the files\n"
       "  --align[=SAMPLES] find the test file's delay within +-SAMPLES (48 kHz samples, 1..16384, default 4096)\n"
       "                on the GPU and compare the aligned parts (the plain one-call mode only)\n"
+      "  --trace=FILE  also write the MOV layer's values of every frame (and, with --advanced, every filter-bank\n"
+      "                block) to FILE as CSV (the plain one-call mode; with --advanced, --device-resample, --align)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n", prog);
+}
+
+/* --trace=FILE: the pair through peaq_run_pair_trace, its records as CSV -- a header line, then one line per FFT frame
+ * (kind "frame") and, in the advanced version, per filter-bank block (kind "block"); every value as %.17g, which reads
+ * back to the same double.  Columns a kind does not have stay empty.  Prints the delay line of --align. */
+static int
+write_trace (const char *path, peaq_ctx *ctx, int advanced, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  /* enough for any cut: the counts of the two signals at 48 kHz */
+  const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
+    rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
+  const size_t frame_cap = (size_t) peaq_frame_count (n48[0], n48[1], 0) + 1;
+  const size_t block_cap = advanced ? (size_t) peaq_frame_count (n48[0], n48[1], 1) + 1 : 0;
+  peaq_frame_trace *fr = malloc (frame_cap * sizeof *fr);
+  peaq_block_trace *bl = advanced ? malloc (block_cap * sizeof *bl) : NULL;
+  uint32_t nf = 0, nb = 0, k;
+  peaq_delay delay;
+  size_t fb = 0, bb = 0;
+  int c, v, rc = 1;
+  FILE *f;
+  if (!fr || (advanced && !bl)) {
+    printf ("Error: out of memory for the trace\n");
+    goto done;
+  }
+  peaq_trace_sizes (&fb, &bb);
+  if (fb != sizeof *fr || bb != sizeof *bl) {
+    printf ("Error: the library's trace records are not this program's\n");
+    goto done;
+  }
+  if (peaq_run_pair_trace (ctx, advanced, ref->channels, level, rate, align_lag, ref->samples, ref->frames, test->samples,
+          test->frames, fr, frame_cap, &nf, bl, block_cap, &nb, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag)
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+  if (!(f = fopen (path, "w"))) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  fprintf (f, "kind,index,flags");
+  for (c = 0; c < 2; c++)
+    for (v = 0; v < 6; v++)
+      fprintf (f, ",ch%d_v%d", c, v);
+  fprintf (f, ",p_detect,steps\n");
+  for (k = 0; k < nf; k++) {
+    fprintf (f, "frame,%u,%u", fr[k].frame, fr[k].flags);
+    for (c = 0; c < 2; c++)
+      for (v = 0; v < 6; v++)
+        fprintf (f, ",%.17g", fr[k].ch[c][v]);
+    fprintf (f, ",%.17g,%.17g\n", fr[k].p_detect, fr[k].steps);
+  }
+  for (k = 0; k < nb; k++) {
+    fprintf (f, "block,%u,%u", bl[k].block, bl[k].flags);
+    for (c = 0; c < 2; c++) {
+      for (v = 0; v < 5; v++)
+        fprintf (f, ",%.17g", bl[k].ch[c][v]);
+      fprintf (f, ",");
+    }
+    fprintf (f, ",,\n");
+  }
+  if (fclose (f)) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  rc = 0;
+done:
+  free (fr);
+  free (bl);
+  return rc;
 }
 
 int
@@ -457,7 +530,7 @@ main (int argc, char **argv)
   peaq_delay delay;
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
-  const char *list_path = NULL;
+  const char *list_path = NULL, *trace_path = NULL;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
   peaq_session *s = NULL;
@@ -496,6 +569,11 @@ main (int argc, char **argv)
     }
     else if (!strncmp (argv[i], "--list=", 7))
       list_path = argv[i] + 7;
+    else if (!strcmp (argv[i], "--trace") || !strcmp (argv[i], "--trace=")) {
+      fprintf (stderr, "Failed to initialize: --trace needs a file name (--trace=FILE)\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--trace=", 8))
+      trace_path = argv[i] + 8;
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -511,14 +589,18 @@ main (int argc, char **argv)
       nfiles++;
   }
   if (list_path) {
-    if (nfiles || interval_s > 0.) {
-      fprintf (stderr, "Failed to initialize: --list takes no REFFILE TESTFILE and no --interval\n");
+    if (nfiles || interval_s > 0. || trace_path) {
+      fprintf (stderr, "Failed to initialize: --list takes no REFFILE TESTFILE, no --interval and no --trace\n");
       return 1;
     }
     return run_list (list_path, advanced, level, align_lag);
   }
   if (nfiles != 2) {
     usage (argv[0]);
+    return 1;
+  }
+  if (trace_path && (interval_s > 0. || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --trace belongs to the plain one-call mode (not with --interval)\n");
     return 1;
   }
   if (wav_read (files[0], &ref) || wav_read (files[1], &test))
@@ -608,7 +690,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (align_lag) {
+    if (trace_path) {
+      if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (align_lag) {
       if (peaq_run_pair_aligned (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag,
               ref.samples, ref.frames, test.samples, test.frames, &delay, &r) != PEAQ_OK) {
         printf ("Error: %s\n", peaq_last_error ());

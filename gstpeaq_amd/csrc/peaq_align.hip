@@ -587,18 +587,17 @@ extern "C" int peaq_batch_cut(peaq_ctx* c, int channels, int n_pairs, const floa
   return sent;
 }
 
-extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
-                                     uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
-                                     peaq_delay* delay, peaq_result* out) {
-  const char* who = "peaq_run_pair_aligned";
-  if (int rc = check_max_lag(who, max_lag)) return rc;
-  if (int rc = check_channels(who, channels)) return rc;
-  if (int rc = check_level(who, level_db)) return rc;
-  if (rate != 48000 && !peaq_resample_supported(rate))
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
-  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
+// One host pair made ready to score: upload, conversion of both signals to 48 kHz if rate != 48000 and, with max_lag,
+// estimate and cut (peaq_run_pair_aligned, peaq_run_pair_trace).  d[0], d[1]: the signals to score, `stride` samples per
+// channel long, len[] their lengths.  The arguments have been checked by the caller.
+struct PreparedPair {
+  DevBuf raw[2], s48[2], cut[2], rec;
+  const float* d[2] = {nullptr, nullptr};
+  size_t stride = 0;
+  uint32_t len[2] = {0, 0};
+};
+static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_lag, const float* ref, size_t n_ref,
+                        const float* test, size_t n_test, peaq_delay* delay, PreparedPair& pp) {
   const size_t n[2] = {n_ref, n_test};
   const float* src[2] = {ref, test};
   uint32_t len[2];
@@ -613,30 +612,37 @@ extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, do
   size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
   stride += stride & 1;                              // 8-byte rows, as in peaq_run_pair
   const size_t bytes = stride * channels * sizeof(float);
-  DevBuf d_raw[2], d_48[2], d_cut[2], d_rec, d_res;
-  HIP_TRY(d_rec.reserve(sizeof(peaq_delay)));
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  HIP_TRY(pp.rec.reserve(sizeof(peaq_delay)));
   for (int i = 0; i < 2; ++i) {
-    HIP_TRY(d_48[i].reserve(bytes));
-    HIP_TRY(hipMemset(d_48[i].p, 0, bytes));
+    HIP_TRY(pp.s48[i].reserve(bytes));
+    HIP_TRY(hipMemset(pp.s48[i].p, 0, bytes));
     if (!n[i]) continue;
     if (rate == 48000) {
-      HIP_TRY(hipMemcpy(d_48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(pp.s48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
       continue;
     }
-    HIP_TRY(d_raw[i].reserve(n[i] * channels * sizeof(float)));
-    HIP_TRY(hipMemcpy(d_raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = peaq_batch_resample(c, channels, rate, 1, d_raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
-                                     d_48[i].as<float>(), stride, nullptr, nullptr))
+    HIP_TRY(pp.raw[i].reserve(n[i] * channels * sizeof(float)));
+    HIP_TRY(hipMemcpy(pp.raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = peaq_batch_resample(c, channels, rate, 1, pp.raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
+                                     pp.s48[i].as<float>(), stride, nullptr, nullptr))
       return rc;
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (int rc = peaq_batch_estimate_delay(c, channels, 1, d_48[0].as<float>(), d_48[1].as<float>(), stride, len, len + 1,
-                                         0, max_lag, d_rec.as<peaq_delay>(), nullptr))
+  if (!max_lag) {                                    // the signals as they are
+    if (delay) std::memset(delay, 0, sizeof *delay);
+    for (int i = 0; i < 2; ++i) {
+      pp.d[i] = pp.s48[i].as<float>();
+      pp.len[i] = len[i];
+    }
+    pp.stride = stride;
+    return PEAQ_OK;
+  }
+  if (int rc = peaq_batch_estimate_delay(c, channels, 1, pp.s48[0].as<float>(), pp.s48[1].as<float>(), stride, len,
+                                         len + 1, 0, max_lag, pp.rec.as<peaq_delay>(), nullptr))
     return rc;
   HIP_TRY(hipDeviceSynchronize());
   peaq_delay rec;
-  HIP_TRY(hipMemcpy(&rec, d_rec.p, sizeof rec, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&rec, pp.rec.p, sizeof rec, hipMemcpyDeviceToHost));
   if (delay) *delay = rec;
   uint32_t skip[2], common = 0;
   peaq_aligned_lengths(rec.lag, len[0], len[1], &skip[0], &skip[1], &common);
@@ -644,18 +650,83 @@ extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, do
   cstride += cstride & 1;
   const size_t cbytes = cstride * channels * sizeof(float);
   for (int i = 0; i < 2; ++i) {
-    HIP_TRY(d_cut[i].reserve(cbytes));
-    HIP_TRY(hipMemset(d_cut[i].p, 0, cbytes));
-    if (int rc = peaq_batch_cut(c, channels, 1, d_48[i].as<float>(), stride, &skip[i], &common, d_cut[i].as<float>(),
+    HIP_TRY(pp.cut[i].reserve(cbytes));
+    HIP_TRY(hipMemset(pp.cut[i].p, 0, cbytes));
+    if (int rc = peaq_batch_cut(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common, pp.cut[i].as<float>(),
                                 cstride, nullptr))
       return rc;
+    pp.d[i] = pp.cut[i].as<float>();
+    pp.len[i] = common;
   }
   HIP_TRY(hipDeviceSynchronize());
-  const uint32_t h_n[2] = {common, common};
-  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, d_cut[0].as<float>(), d_cut[1].as<float>(), cstride,
-                              h_n, h_n + 1, 0, d_res.as<peaq_result>(), nullptr))
+  pp.stride = cstride;
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
+                                     uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                     peaq_delay* delay, peaq_result* out) {
+  const char* who = "peaq_run_pair_aligned";
+  if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  if (int rc = check_level(who, level_db)) return rc;
+  if (rate != 48000 && !peaq_resample_supported(rate))
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
+  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
+  PreparedPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp)) return rc;
+  DevBuf d_res;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
+                              d_res.as<peaq_result>(), nullptr))
     return rc;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_run_pair_trace(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
+                                   uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                   peaq_frame_trace* frames, size_t frame_cap, uint32_t* n_frames,
+                                   peaq_block_trace* blocks, size_t block_cap, uint32_t* n_blocks, peaq_delay* delay,
+                                   peaq_result* out) {
+  const char* who = "peaq_run_pair_trace";
+  const std::string w(who);
+  if (!frames) return fail(PEAQ_ERR_ARG, w + ": frames is NULL");
+  if (advanced && !blocks) return fail(PEAQ_ERR_ARG, w + ": blocks is NULL (the advanced version writes block records)");
+  if (!advanced && blocks) return fail(PEAQ_ERR_ARG, w + ": blocks must be NULL in the basic version (it has no filter-bank blocks)");
+  if (max_lag)
+    if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  if (int rc = check_level(who, level_db)) return rc;
+  if (rate != 48000 && !peaq_resample_supported(rate))
+    return fail(PEAQ_ERR_ARG, w + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
+  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, w + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, w + ": more than 2^32 samples");
+  PreparedPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp)) return rc;
+  const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
+  const uint32_t nb = advanced ? peaq_frame_count(pp.len[0], pp.len[1], 1) : 0;
+  if (nf > frame_cap)
+    return fail(PEAQ_ERR_ARG, w + ": frame_cap " + std::to_string(frame_cap) + " is below the pair's " + std::to_string(nf) + " frames");
+  if (nb > block_cap)
+    return fail(PEAQ_ERR_ARG, w + ": block_cap " + std::to_string(block_cap) + " is below the pair's " + std::to_string(nb) + " blocks");
+  DevBuf d_res, d_fr, d_bl;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  HIP_TRY(d_fr.reserve(std::max<size_t>(nf, 1) * sizeof(peaq_frame_trace)));
+  if (advanced) HIP_TRY(d_bl.reserve(std::max<size_t>(nb, 1) * sizeof(peaq_block_trace)));
+  if (int rc = peaq_batch_run_trace(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
+                                    d_fr.as<peaq_frame_trace>(), nf, advanced ? d_bl.as<peaq_block_trace>() : nullptr, nb,
+                                    d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (nf) HIP_TRY(hipMemcpy(frames, d_fr.p, (size_t)nf * sizeof(peaq_frame_trace), hipMemcpyDeviceToHost));
+  if (nb) HIP_TRY(hipMemcpy(blocks, d_bl.p, (size_t)nb * sizeof(peaq_block_trace), hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  if (n_frames) *n_frames = nf;
+  if (n_blocks) *n_blocks = nb;
   return PEAQ_OK;
 }

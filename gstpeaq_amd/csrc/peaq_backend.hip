@@ -470,25 +470,41 @@ struct BackendShared {
 // a.debug for the stage-level parity tests; the arithmetic is the same instantiation otherwise.
 // PTS = true (backend_points_kernel, trajectory launches only): after each frame the reading points that fall on it
 // get a snapshot (PointWalk); the arithmetic is the same as the plain instantiation's.
+// TRC = true (backend_trace_kernel, trace launches only): the MOV values are computed for every frame, as with DBG, and
+// one lane per (frame, channel) writes them as a compact record (TraceArgs) -- no pattern dump.
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false;
+  constexpr bool PTS = false, TRC = false;
   constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
 #include "peaq_backend_fft.inc"
 }
 // The points instantiation is a kernel of its own name with the same body (not a fourth template parameter of
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true;
+  constexpr bool DBG = false, PTS = true, TRC = false;
+  constexpr TraceArgs trc{};
+#include "peaq_backend_fft.inc"
+}
+// the trace instantiation: a third kernel of its own name with the same body
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
+  constexpr bool DBG = false, PTS = false, TRC = true;
+  constexpr PointArgs pts{};
 #include "peaq_backend_fft.inc"
 }
 
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts) {
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
+                          const TraceArgs* trc) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
-  if (pts && !a.advanced)
+  if (trc && !a.advanced)
+    hipLaunchKernelGGL((backend_trace_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *trc);
+  else if (trc)
+    hipLaunchKernelGGL((backend_trace_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *trc);
+  else if (pts && !a.advanced)
     hipLaunchKernelGGL((backend_points_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pts);
   else if (pts)
     hipLaunchKernelGGL((backend_points_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *pts);
@@ -520,21 +536,34 @@ struct FbBackendShared {
 // instead of one: + 0.5 % on the advanced pass)
 // PTS = true (fb_backend_points_kernel, trajectory launches only): after each block the reading points that fall on it
 // get the snapshot of the accumulators this path owns (0, 1, 4).
+// TRC = true (fb_backend_trace_kernel, trace launches only): the block's MOV values are computed for every block, as
+// with DBG, and one lane per (block, channel) writes them into the pair's block record (TraceArgs).
 template <bool DBG>
 __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
-  constexpr bool PTS = false;
+  constexpr bool PTS = false, TRC = false;
   constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
 #include "peaq_backend_fb.inc"
 }
 // the points instantiation (see backend_points_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true;
+  constexpr bool DBG = false, PTS = true, TRC = false;
+  constexpr TraceArgs trc{};
+#include "peaq_backend_fb.inc"
+}
+// the trace instantiation (see backend_trace_kernel)
+__global__ __launch_bounds__(128, 4) void fb_backend_trace_kernel(FbBackendArgs a, TraceArgs trc) {
+  constexpr bool DBG = false, PTS = false, TRC = true;
+  constexpr PointArgs pts{};
 #include "peaq_backend_fb.inc"
 }
 
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts) {
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
+                             const TraceArgs* trc) {
   if (n_pairs == 0) return hipSuccess;
-  if (pts)
+  if (trc)
+    hipLaunchKernelGGL(fb_backend_trace_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *trc);
+  else if (pts)
     hipLaunchKernelGGL(fb_backend_points_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *pts);
   else if (a.debug)
     hipLaunchKernelGGL(fb_backend_kernel<true>, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a);

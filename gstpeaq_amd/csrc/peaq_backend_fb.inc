@@ -1,5 +1,6 @@
-// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = false) and
-// fb_backend_points_kernel (PTS = true) in peaq_backend.hip: one text, two kernels of their own names.
+// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = false),
+// fb_backend_points_kernel (PTS = true) and fb_backend_trace_kernel (TRC = true) in peaq_backend.hip: one text, three
+// kernels of their own names.
   __shared__ FbBackendShared sh;
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
   __shared__ double sh_etab[kExpTabEntries];
@@ -11,7 +12,7 @@
   for (int i = threadIdx.x; i < 2 * kLogTabEntries; i += blockDim.x) sh_ltab[i] = a.common->log_tab[i >> 1][i & 1];
   if (threadIdx.x < kExpTabEntries) sh_etab[threadIdx.x] = a.common->exp_tab[threadIdx.x];
   __syncthreads();
-  const GlobalTabs bt{a.bands, sh_ltab, sh_etab};
+  GlobalTabs bt{a.bands, sh_ltab, sh_etab};
   const BandLane<NB, SLOTS> bl{lane};
   unsigned b_begin, b_end, slot = pair;
   if (a.windows) {                                   // broker launch: this session's own window and state
@@ -51,6 +52,15 @@
   __shared__ PointWalk<true> sh_pw[2];                  // (points instantiation only)
   PointWalk<true>& pw = sh_pw[wave_uniform(chan)];
   if (PTS) pw.init(pts, pair, b_begin);
+  // (trace instantiation only) this block's values as they come up, one row per channel.  Value k of channel c sits at
+  // [c][c + k]: BlockTrace::ch[1] starts on an odd double, so the pairs of doubles that share a 16-byte store in the
+  // record share one here too.  Lane 0 writes them, lane 0 stores the record at the end of the block.
+  __shared__ __attribute__((aligned(16))) double sh_trc[2][8];
+  unsigned trc_full = 0;                             // full blocks of the pair: the one after them is the flush block
+  if (TRC) {
+    const uint32_t nr = trc.n_ref ? trc.n_ref[pair] : trc.n_uniform, nt = trc.n_test ? trc.n_test[pair] : trc.n_uniform;
+    trc_full = PointWalk<true>::count(nr < nt ? nr : nt);
+  }
 
   // the block's values are requested one block ahead: the walk is a chain of dependent transcendental
   // arithmetic, a record load per block would add its full memory latency 320 times per launch
@@ -71,10 +81,15 @@
     in.f1 = channels == 2 ? rec0[kFbRecDoubles + kFbRecFlags] : 0.;
     return in;
   };
-  BlockIn nxt = fetch(b_begin);
+  // (the trace instantiation loads each block as it comes to it: the twelve registers of the block held ahead are what
+  // it needs to keep every block's values without scratch)
+  BlockIn nxt = TRC ? BlockIn{} : fetch(b_begin);
   for (unsigned blk = b_begin; blk < b_end; ++blk) {
-    const BlockIn cur = nxt;
-    if (blk + 1 < b_end) nxt = fetch(blk + 1);
+    const BlockIn cur = TRC ? fetch(blk) : nxt;
+    // (... and re-reads the per-band constants from the tables in every block: held across the loop they are the ten
+    // registers the other instantiations keep in scratch)
+    if (TRC) asm volatile("" : "+s"(bt.p));
+    if (!TRC && blk + 1 < b_end) nxt = fetch(blk + 1);
     // boundary detector on the 192-sample block, any reference channel (gstpeaq.c:971-979)
     const bool above = cur.f0 != 0. || cur.f1 != 0.;
     if (owns) acc.set_tentative(!above);
@@ -109,7 +124,7 @@
     }
     double v0 = 0., w0 = 1.;
     bool hit = false;
-    if (DBG || blk >= 125) {                         // gstpeaq.c:988-993
+    if (DBG || TRC || blk >= 125) {                  // gstpeaq.c:988-993
       double d1, d2, wt;
       mod_difference<NB, SLOTS>(bl, bt, 1., mr, mt, mdr[1], d1, d2, wt);
       d1 *= 100. / sqrt((double)NB);                 // MODE_RMS variant, movs.c:243-244
@@ -122,8 +137,12 @@
         dbg[0] = d1;
         dbg[1] = wt;
       }
+      if (TRC && lane == 0) {
+        sh_trc[chan][chan + 0] = d1;
+        sh_trc[chan][chan + 1] = wt;
+      }
     }
-    if (DBG || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
+    if (DBG || TRC || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
       // movs.c:551-577; SWAP_MOD_PATTS_FOR_NOISE_LOUDNESS_MOVS (shipped: 1) exchanges the modulation
       // patterns of the missing-components term ...
       const bool swap = a.cfg.swap_mod_patts != 0;   // workgroup-uniform
@@ -155,8 +174,39 @@
         dbg[3] = mc;
         dbg[4] = ld;
       }
+      if (TRC && lane == 0) {
+        sh_trc[chan][chan + 2] = nl;
+        sh_trc[chan][chan + 3] = mc;
+        sh_trc[chan][chan + 4] = ld;
+      }
     }
     if (hit) acc.add(v0, w0);
+    // ---- trace: lane 0 of each channel's wave stores that channel's five values, channel 0's also the block's own
+    // fields (and a mono pair's zero ch[1]), at the pair's absolute block index.  Doubles 0-3 and 6-9 of the record and
+    // the flags go out as 16-byte stores; doubles 4 and 5, the two that straddle the channels, as single ones.
+    if (TRC && lane == 0) {
+      double* __restrict__ od = reinterpret_cast<double*>(trc.blocks + (size_t)pair * trc.block_stride + blk);
+      double2* __restrict__ o = reinterpret_cast<double2*>(od);
+      const double2* __restrict__ s = reinterpret_cast<const double2*>(sh_trc[chan]);
+      if (chan == 0) {
+        // gstpeaq.c:988 and :996-997 (unsigned compare with the UINT_MAX sentinel)
+        const uint32_t fl = (above ? kTraceAbove : 0u) | (blk >= 125 ? kTraceModOpen : 0u) |
+                            (blk >= 125 && blk - 13 >= loud_reached ? kTraceLoudOpen : 0u) |
+                            (blk >= trc_full ? kTraceFlush : 0u);
+        o[0] = s[0];
+        o[1] = s[1];
+        od[4] = sh_trc[0][4];
+        if (channels == 1) {
+          od[5] = 0.;
+          o[3] = o[4] = make_double2(0., 0.);
+        }
+        o[5] = make_double2(__hiloint2double((int)blk, (int)fl), 0.);
+      } else {
+        od[5] = sh_trc[1][1];
+        o[3] = s[1];
+        o[4] = s[2];
+      }
+    }
     if (PTS) {                                       // reading points after this block (see backend_kernel)
       while (PointSnap* __restrict__ sp = pw.take(blk + 1)) {
         if (owns) {

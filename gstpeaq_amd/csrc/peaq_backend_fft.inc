@@ -1,5 +1,6 @@
-// peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = false) and
-// backend_points_kernel<NB, ADV> (PTS = true) in peaq_backend.hip: one text, two kernels of their own names.
+// peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = false),
+// backend_points_kernel<NB, ADV> (PTS = true) and backend_trace_kernel<NB, ADV> (TRC = true) in peaq_backend.hip: one
+// text, three kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -70,6 +71,18 @@
   __shared__ PointWalk<false> sh_pw[2];                  // (points instantiation only)
   PointWalk<false>& pw = sh_pw[chan];
   if (PTS) pw.init(pts, pair, f_begin);
+  // (trace instantiation only) this frame's values as they come up, one row per channel: the six of FrameTrace::ch,
+  // then p_detect and steps (channel 0's row) -- lane 0 writes them, lane 0 stores the record at the end of the frame
+  __shared__ __attribute__((aligned(16))) double sh_trc[2][8];
+  unsigned trc_full = 0;                             // full frames of the pair: the one after them is the flush frame
+  if (TRC) {
+    const uint32_t nr = trc.n_ref ? trc.n_ref[pair] : trc.n_uniform, nt = trc.n_test ? trc.n_test[pair] : trc.n_uniform;
+    trc_full = PointWalk<false>::count(nr < nt ? nr : nt);
+    if (ADV && lane == 0) {                          // the 55-band path has two values; the rest of the row stays zero
+#pragma unroll
+      for (int k = 2; k < 8; ++k) sh_trc[chan][k] = 0.;
+    }
+  }
   if (chan == 0 && lane == 0) {
     sh.energy[0] = ps->sig_energy;
     sh.energy[1] = ps->noise_energy;
@@ -211,7 +224,7 @@
           DBG ? a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov
               : nullptr;
       // ---- modulation difference (gstpeaq.c:871-877) --------------------------------
-      if (DBG || frame >= 24) {
+      if (DBG || TRC || frame >= 24) {
         double d1, d2, wt;
         mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
         d1 *= 100. / NB;
@@ -226,10 +239,15 @@
           dmov[1] = d2;
           dmov[2] = wt;
         }
+        if (TRC && lane == 0) {
+          sh_trc[chan][0] = d1;
+          sh_trc[chan][1] = d2;
+          sh_trc[chan][2] = wt;
+        }
       }
       // ---- noise loudness (gstpeaq.c:880-886; unsigned compare with UINT_MAX sentinel)
       // (its sum over the bands goes through the reduction of the noise-to-mask ratio below)
-      nl_open = DBG || (frame >= 24 && frame - 3 >= loud_reached);
+      nl_open = DBG || TRC || (frame >= 24 && frame - 3 >= loud_reached);
       if (nl_open) nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
       // ---- bandwidth (movs.c:797-807) ------------------------------------------------------
       {
@@ -276,18 +294,23 @@
       nsum /= NB;
       // RelDistFrames asks whether ANY band's ratio is above 1.5 dB: a vote, not a maximum (the debug build reports the value)
       const bool disturbed = __any(nmax > 1.41253754462275);
-      if (DBG) nmax = wave_max(nmax);
+      if (DBG || TRC) nmax = wave_max(nmax);
       if (!ADV && nl_open) {
         const double nl = noise_loudness_total<NB>(nl_sum, 0.);
         if (frame >= 24 && frame - 3 >= loud_reached) route(MB_NOISELOUD, nl, 1.);
         if (DBG && lane == 0)
           a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = nl;
+        if (TRC && lane == 0) sh_trc[chan][3] = nl;
       }
       if (DBG && lane == 0) {
         double* __restrict__ d =
             a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov;
         d[4] = nsum;
         d[5] = nmax;
+      }
+      if (TRC && !ADV && lane == 0) {
+        sh_trc[chan][4] = nsum;
+        sh_trc[chan][5] = nmax;
       }
       if (!ADV) {
         route(MB_NMR, nsum, 1.);                                    // MODE_AVG_LOG
@@ -297,6 +320,10 @@
         route(MA_SEGNMR, seg, 1.);
         if (DBG && lane == 0)
           a.debug[((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov + 3] = seg;
+        if (TRC && lane == 0) {
+          sh_trc[chan][0] = seg;
+          sh_trc[chan][1] = nsum;
+        }
       }
       if (!ADV && chan == 0) {
         const double p_bin = 1. - bt.exp(-kLn2 * xsum);             // 1 - prod_b 0.5^xb (movs.c:1263-1270)
@@ -305,6 +332,10 @@
               a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels) * kDbgDoubles + kDbgMov;
           d[6] = p_bin;
           d[7] = qsum;
+        }
+        if (TRC && lane == 0) {
+          sh_trc[0][6] = p_bin;
+          sh_trc[0][7] = qsum;
         }
         if (p_bin > 0.5) route(MB_ADB, qsum, 1.);
         route(MB_MFPD, p_bin, 1.);
@@ -335,6 +366,26 @@
           sp->sig_energy = sh.energy[0];
           sp->noise_energy = sh.energy[1];
         }
+      }
+    }
+    // ---- trace: lane 0 of each channel's wave stores that channel's six values, channel 0's also the frame's own
+    // fields (and a mono pair's zero ch[1]) -- eight 16-byte stores per record, at the pair's absolute frame index
+    if (TRC && lane == 0) {
+      const double2* __restrict__ s = reinterpret_cast<const double2*>(sh_trc[chan]);
+      double2* __restrict__ o = reinterpret_cast<double2*>(trc.frames + (size_t)pair * trc.frame_stride + frame);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[3 * chan + k] = s[k];
+      if (chan == 0) {
+        // gstpeaq.c:871 and :880-881 (unsigned compare with the UINT_MAX sentinel); the 55-band path has neither gate
+        const uint32_t fl = (above ? kTraceAbove : 0u) | (!ADV && frame >= 24 ? kTraceModOpen : 0u) |
+                            (!ADV && frame >= 24 && frame - 3 >= loud_reached ? kTraceLoudOpen : 0u) |
+                            (frame >= trc_full ? kTraceFlush : 0u);
+        if (channels == 1) {
+#pragma unroll
+          for (int k = 3; k < 6; ++k) o[k] = make_double2(0., 0.);
+        }
+        o[6] = s[3];
+        o[7] = make_double2(__hiloint2double((int)frame, (int)fl), 0.);
       }
     }
     if (!ADV) __syncthreads();                       // sh.pc/qc/gate are rewritten next frame

@@ -72,7 +72,8 @@ extern "C" size_t peaq_batch_workspace_bytes(int advanced, int channels, int n_p
 static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
                                const float* d_test, size_t pair_stride, const uint32_t* d_nref,
                                const uint32_t* d_ntest, uint32_t n_uniform, const uint32_t* d_nblocks,
-                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const PointArgs* pts) {
+                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const PointArgs* pts,
+                               const TraceArgs* trc) {
     // ---- filter-bank path: blocks of 192 samples (gstpeaq.c:648-652) ------------------
     const unsigned n_signals = (unsigned)n_pairs * channels * 2;
     const unsigned bc = fb_blocks_per_chunk(n_pairs, channels, max_blocks);
@@ -149,7 +150,7 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
       HIP_TRY(hipEventRecord(e1, s_bank));
       bank_done[b] = e1;
       if (piped) HIP_TRY(hipStreamWaitEvent(s_be, e1, 0));
-      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts));
+      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts, trc));
       if (piped) {
         HIP_TRY(hipEventRecord(e_be, s_be));
         be_done[b] = e_be;
@@ -172,21 +173,40 @@ struct TrajectoryOut {
   peaq_result* d_points;        // [n_pairs][n_points]
 };
 
-static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs, const float* d_ref,
-                            const float* d_test, size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
-                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream, const TrajectoryOut* tr);
+// Records of a trace (peaq_batch_run_trace): nullptr for a plain batch.  Never together with a trajectory.
+struct TraceOut {
+  peaq_frame_trace* d_frames;   // [n_pairs][frame_stride]
+  size_t frame_stride;
+  peaq_block_trace* d_blocks;   // [n_pairs][block_stride], advanced only
+  size_t block_stride;
+};
+static_assert(sizeof(peaq_frame_trace) == 128 && sizeof(FrameTrace) == 128 && sizeof(peaq_block_trace) == 96 &&
+                  sizeof(BlockTrace) == 96,
+              "the trace records of include/peaq_amd.h and peaq_kernels.h");
+static_assert(offsetof(peaq_frame_trace, flags) == offsetof(FrameTrace, flags) && offsetof(FrameTrace, flags) == 112 &&
+                  offsetof(peaq_block_trace, flags) == offsetof(BlockTrace, flags) && offsetof(BlockTrace, flags) == 80,
+              "the kernels store the records as eight / six 16-byte words");
+static_assert(PEAQ_TRACE_ABOVE == kTraceAbove && PEAQ_TRACE_MOD_OPEN == kTraceModOpen &&
+                  PEAQ_TRACE_LOUD_OPEN == kTraceLoudOpen && PEAQ_TRACE_FLUSH == kTraceFlush,
+              "the flags of include/peaq_amd.h and peaq_kernels.h");
 
-// peaq_batch_run and peaq_batch_run_trajectory: one driver, the points optional (`who` names the entry in messages)
+static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
+                            const TrajectoryOut* tr, const TraceOut* to);
+
+// peaq_batch_run, peaq_batch_run_trajectory and peaq_batch_run_trace: one driver, the points and the trace records
+// optional (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
-                           const TrajectoryOut* tr) {
+                           const TrajectoryOut* tr, const TraceOut* to = nullptr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr && !to)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -198,8 +218,8 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   }
   c->spans.clear();
   c->events_used = 0;
-  const int rc = batch_run_locked(c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref, n_test,
-                                  n_uniform, d_results, stream, tr);
+  const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
+                                  n_test, n_uniform, d_results, stream, tr, to);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -238,6 +258,46 @@ extern "C" int peaq_batch_run_trajectory(peaq_ctx* c, int advanced, int channels
   const TrajectoryOut tr{interval, n_points, d_points};
   return batch_run_entry("peaq_batch_run_trajectory", c, advanced, channels, level_db, n_pairs, d_ref, d_test,
                          pair_stride, n_ref, n_test, n_uniform, d_results, stream_, &tr);
+}
+
+// The trace's own arguments first: they need no context (and no device: the strides are held against counts made
+// from the host's lengths).
+extern "C" int peaq_batch_run_trace(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                                    const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                    const uint32_t* n_test, uint32_t n_uniform, peaq_frame_trace* d_frames,
+                                    size_t frame_stride, peaq_block_trace* d_blocks, size_t block_stride,
+                                    peaq_result* d_results, void* stream_) {
+  const std::string w("peaq_batch_run_trace");
+  if (!d_frames) return fail(PEAQ_ERR_ARG, w + ": d_frames is NULL");
+  if (advanced && !d_blocks) return fail(PEAQ_ERR_ARG, w + ": d_blocks is NULL (the advanced version writes block records)");
+  if (!advanced && d_blocks) return fail(PEAQ_ERR_ARG, w + ": d_blocks must be NULL in the basic version (it has no filter-bank blocks)");
+  if (reinterpret_cast<uintptr_t>(d_frames) % 16 || reinterpret_cast<uintptr_t>(d_blocks) % 16)
+    return fail(PEAQ_ERR_ARG, w + ": " + (reinterpret_cast<uintptr_t>(d_frames) % 16 ? "d_frames" : "d_blocks") +
+                                  " is not 16-byte aligned");
+  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
+    uint32_t max_frames = 0, max_blocks = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
+      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
+      max_blocks = std::max(max_blocks, count_frames(nr, nt, kFbFrame, kFbFrame));
+      if (!n_ref) break;
+    }
+    if (frame_stride < max_frames)
+      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
+                                    std::to_string(max_frames) + " frames");
+    if (advanced && block_stride < max_blocks)
+      return fail(PEAQ_ERR_ARG, w + ": block_stride " + std::to_string(block_stride) + " is below the longest pair's " +
+                                    std::to_string(max_blocks) + " blocks");
+  }
+  const TraceOut to{d_frames, frame_stride, d_blocks, block_stride};
+  return batch_run_entry("peaq_batch_run_trace", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
+                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, &to);
+}
+
+extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
+  if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
+  if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
+  return sizeof(peaq_frame_trace);
 }
 
 extern "C" size_t peaq_batch_trajectory_workspace_bytes(int advanced, int channels, int n_pairs, uint32_t n_max,
@@ -300,9 +360,10 @@ extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels,
                        n_points, points, out);
 }
 
-static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs, const float* d_ref,
-                            const float* d_test, size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
-                            uint32_t n_uniform, peaq_result* d_results, hipStream_t stream, const TrajectoryOut* tr) {
+static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
+                            const TrajectoryOut* tr, const TraceOut* to) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -314,8 +375,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     std::vector<uint32_t> h(4 * (size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
       if (n_ref[p] > pair_stride || n_test[p] > pair_stride)
-        return fail(PEAQ_ERR_ARG, std::string(tr ? "peaq_batch_run_trajectory" : "peaq_batch_run") +
-                                      ": a pair is longer than pair_stride");
+        return fail(PEAQ_ERR_ARG, std::string(who) + ": a pair is longer than pair_stride");
       h[p] = n_ref[p];
       h[n_pairs + p] = n_test[p];
       h[2 * (size_t)n_pairs + p] = count_frames(n_ref[p], n_test[p], kFrame, kHop);
@@ -332,8 +392,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     d_nblocks = d_nref + 3 * (size_t)n_pairs;
   } else {
     if (n_uniform > pair_stride)
-      return fail(PEAQ_ERR_ARG, std::string(tr ? "peaq_batch_run_trajectory" : "peaq_batch_run") +
-                                    ": n_uniform > pair_stride");
+      return fail(PEAQ_ERR_ARG, std::string(who) + ": n_uniform > pair_stride");
     max_frames = count_frames(n_uniform, n_uniform, kFrame, kHop);
     max_blocks = count_frames(n_uniform, n_uniform, kFbFrame, kFbFrame);
   }
@@ -356,6 +415,18 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     pa.n_points = tr->n_points;
   }
   const PointArgs* pts = tr ? &pa : nullptr;
+  // trace: the back ends write the caller's record arrays directly -- no scratch of its own
+  TraceArgs ta{};
+  if (to) {
+    ta.frames = reinterpret_cast<FrameTrace*>(to->d_frames);
+    ta.frame_stride = to->frame_stride;
+    ta.blocks = reinterpret_cast<BlockTrace*>(to->d_blocks);
+    ta.block_stride = to->block_stride;
+    ta.n_ref = d_nref;
+    ta.n_test = d_ntest;
+    ta.n_uniform = n_uniform;
+  }
+  const TraceArgs* trc = to ? &ta : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
@@ -375,7 +446,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
   auto issue_filterbank_path = [&](hipEvent_t bank_gate) -> int {
     hipStream_t s_fb = PEAQ_DEV_SERIAL_KERNELS ? stream : c->aux2;
     const int rc = run_filterbank_path(c, channels, level_db, n_pairs, d_ref, d_test, pair_stride, d_nref, d_ntest,
-                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts);
+                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts, trc);
     if (rc != PEAQ_OK) return rc;
     fb_done = c->next_event();
     if (!fb_done) return fail(PEAQ_ERR_DEVICE, "hipEventCreate failed");
@@ -450,7 +521,7 @@ static int batch_run_locked(peaq_ctx* c, int advanced, int channels, double leve
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;

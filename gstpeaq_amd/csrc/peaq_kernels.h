@@ -62,6 +62,31 @@ struct PointArgs {
   int n_points;
 };
 
+// ---- per-frame and per-block MOV traces (peaq_batch_run_trace) -------------------
+// The records mirror peaq_frame_trace / peaq_block_trace in include/peaq_amd.h (peaq_batch.hip asserts the sizes and
+// the flag values).  A kernel argument of the trace instantiations only, like PointArgs.
+constexpr uint32_t kTraceAbove = 1u, kTraceModOpen = 2u, kTraceLoudOpen = 4u, kTraceFlush = 8u;
+struct FrameTrace {             // 128 bytes = eight 16-byte stores
+  double ch[2][6];
+  double p_detect, steps;
+  uint32_t flags, frame;
+  double reserved;
+};
+struct BlockTrace {             // 96 bytes; ch[1] starts on an odd double
+  double ch[2][5];
+  uint32_t flags, block;
+  double reserved;
+};
+struct TraceArgs {
+  FrameTrace* frames;           // [pair][frame_stride], 16-byte aligned; record f of a pair at its ABSOLUTE frame index
+  size_t frame_stride;
+  BlockTrace* blocks;           // [pair][block_stride] (filter-bank back end)
+  size_t block_stride;
+  const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform -- the flush frame / block is the one
+  const uint32_t* n_test;       // after the full ones of min(n_ref, n_test)
+  uint32_t n_uniform;
+};
+
 // ---- pattern back end (time smearing .. MOV accumulation) -------------------
 struct BackendArgs {
   const double* records;        // as written by the front end
@@ -84,7 +109,9 @@ struct BackendArgs {
   unsigned long long* clk;
 };
 // pts != nullptr (trajectory launches only): the points instantiation, snapshots after frames (PointArgs)
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr);
+// trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per frame (TraceArgs)
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
+                          const TraceArgs* trc = nullptr);
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h
@@ -159,7 +186,9 @@ struct FbBackendArgs {
   double* debug;
 };
 // pts != nullptr (trajectory launches only): the points instantiation, snapshots after blocks (PointArgs)
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr);
+// trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per block (TraceArgs)
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
+                             const TraceArgs* trc = nullptr);
 
 // ---- synthetic workload --------------------------------------------------------------
 hipError_t launch_synth(uint32_t seed0, unsigned n_pairs, int channels, uint32_t n_samples, size_t pair_stride,

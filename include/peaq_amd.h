@@ -274,6 +274,66 @@ int peaq_batch_run_trajectory (peaq_ctx *ctx, int advanced, int channels, double
 /* peaq_batch_workspace_bytes plus the snapshot scratch of n_points readings per pair. */
 size_t peaq_batch_trajectory_workspace_bytes (int advanced, int channels, int n_pairs, uint32_t n_max, int n_points);
 
+/* ---- traces: the MOV layer's values of every frame and block --------------------
+ * A result says how good an item is, a trajectory how the reading developed; a trace says WHERE the score was lost:
+ * peaq_batch_run_trace writes, in the same run that scores the batch, one record per FFT frame of every pair and, in
+ * the advanced version, one per filter-bank block.
+ *
+ *   Frame record f of pair p holds the MOV layer's values of that frame BEFORE accumulation (the functions of movs.c
+ *   named at the fields), computed for every frame whether or not the gates of gstpeaq.c let the accumulators see
+ *   them; `flags` says which gates were open, so that a caller can reproduce what was counted:
+ *     PEAQ_TRACE_ABOVE      the reference was above the data-boundary threshold in this frame / block
+ *                           (is_frame_above_threshold, gstpeaq.c:1081-1099): the accumulators were NOT set tentative
+ *     PEAQ_TRACE_MOD_OPEN   frame >= 24 (block >= 125): gstpeaq.c:871 / :988 let the modulation differences through
+ *     PEAQ_TRACE_LOUD_OPEN  gstpeaq.c:880-881 / :996-997 let the noise loudness through: frame >= 24 and
+ *                           frame - 3 >= loudness_reached_frame (block >= 125 and block - 13 >= ...), the subtraction
+ *                           and the comparison unsigned, the frame in which the gate of :841-845 opens included
+ *     PEAQ_TRACE_FLUSH      the zero-padded frame / block of the flush (gstpeaq.c:716-745)
+ *   The frame records of the advanced version (its 55-band path has neither gate) carry ABOVE and FLUSH only.
+ *   Pair p has peaq_frame_count (n_ref[p], n_test[p], 0) frame records, d_frames[p * frame_stride + f], and
+ *   peaq_frame_count (n_ref[p], n_test[p], 1) block records, d_blocks[p * block_stride + b]; `frame` / `block` is the
+ *   index.  Entries of the arrays past a pair's count are left untouched.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs.  Arguments otherwise as for
+ * peaq_batch_run; the context's settings and FIR mode apply as they do there.  PEAQ_ERR_ARG, before any device is
+ * touched and with a message that names the value: d_frames NULL or not 16-byte aligned (the records go out as
+ * 16-byte stores; so d_blocks), a stride below the longest pair's count, d_blocks NULL in the advanced version or
+ * non-NULL in the basic version, and everything peaq_batch_run refuses.  Trace and trajectory are separate calls. */
+#define PEAQ_TRACE_ABOVE      1u
+#define PEAQ_TRACE_MOD_OPEN   2u
+#define PEAQ_TRACE_LOUD_OPEN  4u
+#define PEAQ_TRACE_FLUSH      8u
+
+typedef struct {            /* 128 bytes, one per (pair, FFT frame) */
+  double   ch[2][6];        /* basic, per channel: ModDiff1, ModDiff2, TempWt (movs.c:205-254, with the factor 100 the
+                             * accumulators see), noise loudness (:354-371), mean and maximum of the band noise-to-mask
+                             * ratios, linear (:971-1023).  advanced (55-band path), per channel: 10 log10 of the mean
+                             * band NMR (:1010-1020), that mean, four zeros.  mono: ch[1] is zero */
+  double   p_detect, steps; /* basic: detection probability and steps above threshold of the frame, all channels
+                             * (:1224-1276); advanced: 0 */
+  uint32_t flags, frame;
+  double   reserved;        /* 0 */
+} peaq_frame_trace;
+
+typedef struct {            /* 96 bytes, one per (pair, filter-bank block); advanced only */
+  double   ch[2][5];        /* RmsModDiff and its weight (movs.c:205-254, :243-244), noise loudness and
+                             * missing-components term of RmsNoiseLoudAsym (:551-577), AvgLinDist (:679-706).
+                             * mono: ch[1] is zero */
+  uint32_t flags, block;
+  double   reserved;        /* 0 */
+} peaq_block_trace;
+
+int peaq_batch_run_trace (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, int n_pairs,
+                          const float *d_ref, const float *d_test, size_t pair_stride,
+                          const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                          peaq_frame_trace *d_frames, size_t frame_stride,     /* device, [n_pairs][frame_stride] */
+                          peaq_block_trace *d_blocks, size_t block_stride,     /* device; advanced: required, basic: must be NULL */
+                          peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+/* sizeof of both records in THIS library (returns the frame record's; either pointer may be NULL): a caller built
+ * against another header compares before it hands over a buffer, as with peaq_broker_stats_size */
+size_t peaq_trace_sizes (size_t *frame_bytes, size_t *block_bytes);
+/* (peaq_run_pair_trace, the same for one pair from host memory: after peaq_run_pair_aligned below) */
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -428,6 +488,19 @@ void peaq_aligned_lengths (int32_t lag, uint32_t n_ref, uint32_t n_test,
 int peaq_run_pair_aligned (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
                            uint32_t max_lag, const float *ref, size_t n_ref, const float *test, size_t n_test,
                            peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_trace (above) for one pair from HOST memory, records into host arrays: upload, conversion of both
+ * signals to 48 kHz on the device if rate != 48000, alignment as in peaq_run_pair_aligned if max_lag != 0 (0: none; delay, may be NULL, receives the
+ * record, zeroed without alignment), then peaq_batch_run_trace with one pair.  n_frames / n_blocks (may be NULL)
+ * receive the counts written -- those of the signals as scored, after conversion and cut; frame_cap / block_cap are
+ * the arrays' sizes in records, and a cap below the count is PEAQ_ERR_ARG with both numbers in the message
+ * (peaq_frame_count of the two 48 kHz lengths is always enough: the cut only shortens).  blocks: required in the
+ * advanced version, NULL in the basic one.  out (may be NULL): the pair's result. */
+int peaq_run_pair_trace (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
+                         uint32_t rate, uint32_t max_lag,
+                         const float *ref, size_t n_ref, const float *test, size_t n_test,
+                         peaq_frame_trace *frames /* host */, size_t frame_cap, uint32_t *n_frames,
+                         peaq_block_trace *blocks /* host */, size_t block_cap, uint32_t *n_blocks,
+                         peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
