@@ -11,6 +11,7 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    run_pair_trajectory, library_path, load_library, synth_fill, resample, resample_plan, resampled_length, resample_supported,
                    estimate_delay, cut, align, aligned_lengths, align_workspace_bytes, Delay,
                    decode_pcm, run_host, run_files, make_feed, feed_workspace_bytes, pcm_format, pcm_sample_bytes, Feed, HostPair,
+                   gather, run_host_refs, feed_refs_workspace_bytes, HostSignal, HostTest,
                    PCM_FORMATS, PCM_DTYPES,
                    batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
@@ -20,7 +21,7 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "run_pair_trajectory", "library_path", "load_library", "synth_fill", "resample", "resample_plan", "resampled_length",
            "resample_supported", "estimate_delay", "cut", "align", "aligned_lengths", "align_workspace_bytes", "Delay",
            "decode_pcm", "run_host", "run_files", "make_feed", "feed_workspace_bytes", "pcm_format", "pcm_sample_bytes", "Feed",
-           "HostPair", "PCM_FORMATS", "PCM_DTYPES",
+           "HostPair", "PCM_FORMATS", "PCM_DTYPES", "gather", "run_host_refs", "feed_refs_workspace_bytes", "HostSignal", "HostTest",
            "batch_trace", "run_pair_trace", "frame_count", "FrameTrace", "BlockTrace", "FRAME_TRACE_DTYPE", "BLOCK_TRACE_DTYPE",
            "TRACE_ABOVE", "TRACE_MOD_OPEN", "TRACE_LOUD_OPEN", "TRACE_FLUSH",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

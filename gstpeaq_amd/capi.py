@@ -68,6 +68,16 @@ class HostPair(C.Structure):
     _fields_ = [("ref", C.c_void_p), ("test", C.c_void_p), ("n_ref", C.c_uint64), ("n_test", C.c_uint64)]
 
 
+class HostSignal(C.Structure):
+    """mirrors peaq_host_signal (include/peaq_amd.h)"""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_uint64)]
+
+
+class HostTest(C.Structure):
+    """mirrors peaq_host_test (include/peaq_amd.h)"""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_uint64), ("ref", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Feed(C.Structure):
     """mirrors peaq_feed (include/peaq_amd.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int), ("channels", C.c_int), ("rate", C.c_uint32),
@@ -209,6 +219,12 @@ def load_library():
                                       C.POINTER(Delay)]
     L.peaq_feed_workspace_bytes.restype = C.c_size_t
     L.peaq_feed_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_size_t, C.c_uint64]
+    if hasattr(L, "peaq_batch_gather"):              # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_batch_gather.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, vp, C.c_size_t, vp]
+        L.peaq_batch_run_host_refs.argtypes = [vp, C.c_int, C.c_double, C.POINTER(Feed), C.c_size_t, C.POINTER(HostSignal),
+                                               C.c_size_t, C.POINTER(HostTest), dp, C.POINTER(Delay)]
+        L.peaq_feed_refs_workspace_bytes.restype = C.c_size_t
+        L.peaq_feed_refs_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_size_t, C.c_size_t, C.c_uint64]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -598,6 +614,33 @@ def cut(ctx, x, skip, n_keep, out=None, stream=None):
     return out
 
 
+def gather(ctx, x, src, skip=None, n_keep=None, out=None, stream=None):
+    """out[p, i] = x[src[p], skip[p] + i] for i < n_keep[p] (peaq_batch_gather); x: CUDA float32 [n_rows, n_samples,
+    channels], src: a row of x per output, any row any number of times.  skip: zeros without it; n_keep: what is left
+    of the row behind the skip.  out: optional tensor [n_out, stride, channels] to write into (samples past n_keep[p]
+    keep what they held); without it a zero-filled one with an even stride is made.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_rows, stride, channels = x.shape
+    a_src = np.ascontiguousarray(src, dtype=np.uint32)
+    assert a_src.ndim == 1
+    n_out = len(a_src)
+    a_skip = np.zeros(n_out, np.uint32) if skip is None else np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = (stride - np.minimum(a_skip, stride)).astype(np.uint32) if n_keep is None else np.ascontiguousarray(n_keep, dtype=np.uint32)
+    assert a_skip.shape == (n_out,) and a_keep.shape == (n_out,)
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_out else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the copy runs on
+            out = torch.zeros((n_out, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_out and out.shape[2] == channels
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_gather(ctx.h, channels, n_rows, n_out, C.c_void_p(x.data_ptr()), stride,
+                                   a_src.ctypes.data_as(u32p), a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p),
+                                   C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
+
+
 def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
@@ -944,26 +987,105 @@ def run_host(ctx, advanced, pairs, format, channels, rate=48000, align=None, chu
     return res, delays
 
 
-def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92.0):
+def _delay_arrays(rec, n):
+    return {k: np.array([getattr(rec[p], k) for p in range(n)], dtype=np.int32 if k == "lag" else np.float64)
+            for k in ("lag", "peak", "runner_up", "norm")}
+
+
+def feed_refs_workspace_bytes(feed, advanced, n_refs, n_tests, n_max):
+    """staging, device buffers and workspaces of a run_host_refs call (peaq_feed_refs_workspace_bytes)"""
+    return int(load_library().peaq_feed_refs_workspace_bytes(C.byref(feed), int(bool(advanced)), int(n_refs), int(n_tests),
+                                                             int(n_max)))
+
+
+def _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs, playback_level):
+    """peaq_batch_run_host_refs on numpy arrays -> (rows float64 [n_tests, 16], the Delay records or None); a reference
+    may be None (no buffer, no samples)"""
+    fmt = pcm_format(format)
+    unit = pcm_sample_bytes(fmt) * int(channels)
+    assert unit, "unknown sample format"
+    assert len(ref_index) == len(tests), "one reference index per test"
+    keep = []
+
+    def fill(row, x, what):
+        if x is None:
+            row.data, row.n = None, 0
+            return
+        x = np.asarray(x)
+        assert x.dtype == PCM_DTYPES[fmt], f"{what}: {x.dtype} is not the dtype of this format ({PCM_DTYPES[fmt]})"
+        if not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x)
+        assert x.nbytes % unit == 0, f"{what}: not a whole number of samples per channel"
+        keep.append(x)                                 # (the arrays stay alive until the call has returned)
+        row.data, row.n = (x.ctypes.data if x.nbytes else None), x.nbytes // unit
+
+    r_rows, t_rows = (HostSignal * max(len(refs), 1))(), (HostTest * max(len(tests), 1))()
+    for r, x in enumerate(refs):
+        fill(r_rows[r], x, f"reference {r}")
+    for t, x in enumerate(tests):
+        fill(t_rows[t], x, f"test {t}")
+        t_rows[t].ref = int(ref_index[t])
+    feed = make_feed(fmt, channels, rate, align, chunk_pairs)
+    out = np.zeros((max(len(tests), 1), RESULT_DOUBLES))
+    rec = (Delay * max(len(tests), 1))() if align is not None else None
+    _check(ctx.L.peaq_batch_run_host_refs(ctx.h, int(bool(advanced)), float(playback_level), C.byref(feed), len(refs), r_rows,
+                                          len(tests), t_rows, out.ctypes.data_as(C.POINTER(C.c_double)), rec))
+    del keep
+    return out[:len(tests)], rec
+
+
+def run_host_refs(ctx, advanced, refs, tests, ref_index, format, channels, rate=48000, align=None, chunk_pairs=0,
+                  playback_level=92.0):
+    """run_host for tests that share references (peaq_batch_run_host_refs): tests[t] is scored against
+    refs[ref_index[t]], and a reference is uploaded, decoded and converted once per chunk, not once per test -- keep the
+    tests of a reference next to each other.  A reference no test names may be None.  Returns what run_host returns for
+    the pairs (refs[ref_index[t]], tests[t]), bit for bit."""
+    out, rec = _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs,
+                                   playback_level)
+    res = [_result_dict(r, bool(advanced)) for r in out]
+    return res if align is None else (res, _delay_arrays(rec, len(tests)))
+
+
+def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92.0, share_refs=True):
     """Scores a list of (ref_path, test_path) RIFF/WAVE files: the data chunks are read as they are (wavio.read_wav_raw),
-    the pairs grouped by (format, channels, rate) and each group run through run_host.  Returns the result dicts in
-    list order, and with `align` (results, delays), delays a list of dicts.  ValueError, naming the file, if the two
-    files of a pair differ in channels, rate or format."""
+    the pairs grouped by (format, channels, rate) and each group run through run_host_refs: within a group every distinct
+    reference path (compared as the exact string) is read once and the tests are ordered by reference (a stable sort), so
+    that a reference shared by several pairs is uploaded once per chunk.  share_refs=False: every line's reference is
+    read again and the group goes through run_host.  Returns the result dicts in list order, and with `align`
+    (results, delays), delays a list of dicts.  ValueError, naming the file, if the two files of a pair differ in
+    channels, rate or format."""
     from . import wavio
-    groups, loaded = {}, []
+    groups, loaded, read = {}, [], {}
     for p, (ref_path, test_path) in enumerate(files):
-        r = wavio.read_wav_raw(ref_path)
+        key = str(ref_path)
+        r = read.get(key) if share_refs else None
+        if r is None:
+            r = wavio.read_wav_raw(ref_path)
+            read[key] = r
         t = wavio.read_wav_raw(test_path)
         for what, a, b in (("format", r[1], t[1]), ("channel count", r[2], t[2]), ("rate", r[3], t[3])):
             if a != b:
                 raise ValueError(f"{test_path}: {what} {b} differs from {ref_path}'s ({a})")
-        loaded.append((r[0], t[0]))
+        loaded.append((r[0], t[0], key))
         groups.setdefault((r[1], r[2], r[3]), []).append(p)
     results, delays = [None] * len(files), [None] * len(files)
     for (fmt, channels, rate), members in groups.items():
-        arrays = [tuple(np.frombuffer(b, dtype=PCM_DTYPES[fmt]) for b in loaded[p]) for p in members]
-        got = run_host(ctx, advanced, arrays, fmt, channels, rate=rate, align=align, chunk_pairs=chunk_pairs,
-                       playback_level=playback_level)
+        as_array = lambda b: np.frombuffer(b, dtype=PCM_DTYPES[fmt])   # noqa: E731
+        if share_refs:
+            index = {}
+            for p in members:
+                index.setdefault(loaded[p][2], len(index))
+            members = sorted(members, key=lambda p: index[loaded[p][2]])
+            refs = [None] * len(index)
+            for p in members:
+                refs[index[loaded[p][2]]] = as_array(loaded[p][0])
+            got = run_host_refs(ctx, advanced, refs, [as_array(loaded[p][1]) for p in members],
+                                [index[loaded[p][2]] for p in members], fmt, channels, rate=rate, align=align,
+                                chunk_pairs=chunk_pairs, playback_level=playback_level)
+        else:
+            arrays = [(as_array(loaded[p][0]), as_array(loaded[p][1])) for p in members]
+            got = run_host(ctx, advanced, arrays, fmt, channels, rate=rate, align=align, chunk_pairs=chunk_pairs,
+                           playback_level=playback_level)
         res, dl = got if align is not None else (got, None)
         for i, p in enumerate(members):
             results[p] = res[i]

@@ -33,7 +33,10 @@
  * (peaq_batch_run_host: decoded, converted to 48 kHz and, with --align, aligned on the device), grouped by format,
  * channel count and rate; one line per pair in list order, REF<TAB>TEST<TAB>ODG<TAB>DI.  Nothing is scored (exit
  * status 2) if a file cannot be read, the two files of a pair differ in format, or a rate is one the device converter
- * does not take.
+ * does not take.  Within such a group a reference path that several lines name (compared as the exact string) is read once
+ * and uploaded once per chunk, the lines ordered by reference for the call and printed in list order all the same
+ * (peaq_batch_run_host_refs); --no-share-refs reads every line's reference again and hands plain pairs to
+ * peaq_batch_run_host.  Behind the results one line on stderr says how many references were read for how many pairs.
  */
 #include <math.h>
 #include <stdint.h>
@@ -211,9 +214,28 @@ wav_read_raw (const char *path, raw_t * w)
   return -1;
 }
 
+/* --list with shared references: an order of the lines by a key and, among equal keys, by line */
+static char **sort_names;       /* [2 * line]: the reference's path */
+static const size_t *sort_key;  /* [line] */
+
+static int
+by_ref_name (const void *a, const void *b)
+{
+  const size_t x = *(const size_t *) a, y = *(const size_t *) b;
+  const int c = strcmp (sort_names[2 * x], sort_names[2 * y]);
+  return c ? c : (x > y) - (x < y);
+}
+
+static int
+by_key (const void *a, const void *b)
+{
+  const size_t x = *(const size_t *) a, y = *(const size_t *) b;
+  return sort_key[x] != sort_key[y] ? (sort_key[x] > sort_key[y]) - (sort_key[x] < sort_key[y]) : (x > y) - (x < y);
+}
+
 /* scores the pairs of `list_path`; the exit status */
 static int
-run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
+run_list (const char *list_path, int advanced, double level, uint32_t align_lag, int share_refs)
 {
   FILE *f = fopen (list_path, "r");
   char *line = NULL, **names = NULL;
@@ -223,6 +245,10 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
   peaq_host_pair *hp = NULL;
   size_t *members = NULL;
   char *done = NULL;
+  size_t *first = NULL;         /* [line]: the first line that names the same reference path (share_refs) */
+  size_t n_read = 0;
+  peaq_host_signal *hs = NULL;
+  peaq_host_test *ht = NULL;
   peaq_ctx *ctx = NULL;
   ssize_t len;
   if (!f) {
@@ -256,9 +282,29 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
   hp = calloc (n_pairs + 1, sizeof *hp);
   members = calloc (n_pairs + 1, sizeof *members);
   done = calloc (n_pairs + 1, 1);
+  first = calloc (n_pairs + 1, sizeof *first);
+  hs = calloc (n_pairs + 1, sizeof *hs);
+  ht = calloc (n_pairs + 1, sizeof *ht);
+  for (p = 0; p < n_pairs; p++)
+    first[p] = p;
+  if (share_refs) {
+    for (p = 0; p < n_pairs; p++)
+      members[p] = p;
+    sort_names = names;
+    qsort (members, n_pairs, sizeof *members, by_ref_name);
+    for (p = 1; p < n_pairs; p++)
+      if (!strcmp (names[2 * members[p]], names[2 * members[p - 1]]))
+        first[members[p]] = first[members[p - 1]];
+  }
   for (p = 0; p < n_pairs; p++) {
     const raw_t *r = &raw[2 * p], *t = &raw[2 * p + 1];
-    if (wav_read_raw (names[2 * p], &raw[2 * p]) || wav_read_raw (names[2 * p + 1], &raw[2 * p + 1]))
+    if (first[p] != p)
+      raw[2 * p] = raw[2 * first[p]];   /* (the same bytes: nothing is freed before the process ends) */
+    else if (wav_read_raw (names[2 * p], &raw[2 * p]))
+      return 2;
+    else
+      n_read++;
+    if (wav_read_raw (names[2 * p + 1], &raw[2 * p + 1]))
       return 2;
     if (r->format != t->format || r->channels != t->channels || r->rate != t->rate) {
       fprintf (stderr, "Error: %s and %s differ in sample format, channel count or rate\n", names[2 * p], names[2 * p + 1]);
@@ -282,13 +328,19 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
     for (q = p; q < n_pairs; q++)
       if (!done[q] && raw[2 * q].format == raw[2 * p].format && raw[2 * q].channels == raw[2 * p].channels
           && raw[2 * q].rate == raw[2 * p].rate) {
-        hp[n].ref = raw[2 * q].bytes;
-        hp[n].test = raw[2 * q + 1].bytes;
-        hp[n].n_ref = raw[2 * q].frames;
-        hp[n].n_test = raw[2 * q + 1].frames;
         members[n++] = q;
         done[q] = 1;
       }
+    if (share_refs) {           /* the group's lines by reference, a reference's lines in list order */
+      sort_key = first;
+      qsort (members, n, sizeof *members, by_key);
+    }
+    for (q = 0; q < n; q++) {
+      hp[q].ref = raw[2 * members[q]].bytes;
+      hp[q].test = raw[2 * members[q] + 1].bytes;
+      hp[q].n_ref = raw[2 * members[q]].frames;
+      hp[q].n_test = raw[2 * members[q] + 1].frames;
+    }
     memset (&feed, 0, sizeof feed);
     feed.struct_size = (uint32_t) sizeof feed;
     feed.format = raw[2 * p].format;
@@ -297,7 +349,18 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
     feed.align_max_lag = align_lag;
     {
       peaq_result *out = malloc (n * sizeof *out);
-      if (peaq_batch_run_host (ctx, advanced, level, &feed, n, hp, out, NULL) != PEAQ_OK) {
+      size_t n_refs = 0;
+      for (q = 0; share_refs && q < n; q++) {
+        if (!q || first[members[q]] != first[members[q - 1]]) {
+          hs[n_refs].data = hp[q].ref;
+          hs[n_refs++].n = hp[q].n_ref;
+        }
+        ht[q].data = hp[q].test;
+        ht[q].n = hp[q].n_test;
+        ht[q].ref = (uint32_t) (n_refs - 1);
+      }
+      if ((share_refs ? peaq_batch_run_host_refs (ctx, advanced, level, &feed, n_refs, hs, n, ht, out, NULL)
+              : peaq_batch_run_host (ctx, advanced, level, &feed, n, hp, out, NULL)) != PEAQ_OK) {
         fprintf (stderr, "Error: %s\n", peaq_last_error ());
         return 2;
       }
@@ -308,6 +371,8 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag)
   }
   for (p = 0; p < n_pairs; p++)
     printf ("%s\t%s\t%.3f\t%.3f\n", names[2 * p], names[2 * p + 1], res[p].odg, res[p].di);
+  fflush (stdout);
+  fprintf (stderr, "Note: %zu %s read for %zu pairs\n", n_read, share_refs ? "distinct references" : "references", n_pairs);
   if (ctx)
     peaq_ctx_destroy (ctx);
   return 0;
@@ -447,7 +512,8 @@ usage (const char *prog)
       "  --trace=FILE  also write the MOV layer's values of every frame (and, with --advanced, every filter-bank\n"
       "                block) to FILE as CSV (the plain one-call mode; with --advanced, --device-resample, --align)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
-      "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n", prog);
+      "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
+      "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
 }
 
 /* --trace=FILE: the pair through peaq_run_pair_trace, its records as CSV -- a header line, then one line per FFT frame
@@ -531,6 +597,7 @@ main (int argc, char **argv)
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   const char *list_path = NULL, *trace_path = NULL;
+  int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
   peaq_session *s = NULL;
@@ -569,6 +636,8 @@ main (int argc, char **argv)
     }
     else if (!strncmp (argv[i], "--list=", 7))
       list_path = argv[i] + 7;
+    else if (!strcmp (argv[i], "--no-share-refs"))
+      share_refs = 0;
     else if (!strcmp (argv[i], "--trace") || !strcmp (argv[i], "--trace=")) {
       fprintf (stderr, "Failed to initialize: --trace needs a file name (--trace=FILE)\n");
       return 1;
@@ -593,7 +662,7 @@ main (int argc, char **argv)
       fprintf (stderr, "Failed to initialize: --list takes no REFFILE TESTFILE, no --interval and no --trace\n");
       return 1;
     }
-    return run_list (list_path, advanced, level, align_lag);
+    return run_list (list_path, advanced, level, align_lag, share_refs);
   }
   if (nfiles != 2) {
     usage (argv[0]);

@@ -7,7 +7,9 @@
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
 //   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
 //   peaq_align.hip    delay estimation and cutting in front of the batch driver (kernels and host side)
-//   peaq_pcm.hip      PCM decoder in front of them (kernels and host side) and the host-fed batch (peaq_batch_run_host)
+//   peaq_pcm.hip      PCM decoder in front of them (kernels and host side) and the host-fed batches (peaq_batch_run_host,
+//                     peaq_batch_run_host_refs)
+//   peaq_gather.hip   copy by source index, what shares one uploaded reference among its tests (kernel and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -161,6 +163,7 @@ struct peaq_ctx {
   struct RsState* rs = nullptr;           // rate converter: tap tables per rate, length scratch (peaq_resample.hip)
   struct AlignState* al = nullptr;        // aligner: spectra scratch, length scratch (peaq_align.hip)
   struct FeedState* feed = nullptr;       // PCM decoder and host feed: length scratch, staging sets, streams (peaq_pcm.hip)
+  struct GatherState* ga = nullptr;       // gather: index and length scratch (peaq_gather.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -178,6 +181,8 @@ void resample_release(peaq_ctx* c);
 void align_release(peaq_ctx* c);
 // the same for peaq_batch_decode_pcm / peaq_batch_run_host (peaq_pcm.hip)
 void feed_release(peaq_ctx* c);
+// the same for peaq_batch_gather (peaq_gather.hip)
+void gather_release(peaq_ctx* c);
 
 // ---------------------------------------------------------------------------
 // Per-pair host arrays of one call (lengths, skips): staged in pinned host memory and copied on the caller's stream,

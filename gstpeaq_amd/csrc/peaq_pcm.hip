@@ -1,6 +1,8 @@
 // peaq_pcm.hip -- PCM from host memory (peaq_batch_decode_pcm, peaq_batch_run_host, peaq_feed_workspace_bytes;
 // include/peaq_amd.h): the sample-format conversion as a kernel, and the feed that scores a list of host pairs chunk
-// by chunk, the next chunk's packing and upload beside the running chunk's kernels.
+// by chunk, the next chunk's packing and upload beside the running chunk's kernels.  At the end the
+// same feed for tests that name shared references, each uploaded, decoded and converted once per chunk
+// (peaq_batch_run_host_refs, peaq_feed_refs_workspace_bytes); it adds host code only.
 //
 //   pcm_decode_kernel<F>     one per format.  A thread turns 4 sb input bytes (sb = bytes per sample) into one aligned
 //       16-byte store, from the first 16-byte aligned float of the pair's destination on.  Its input starts at byte
@@ -269,6 +271,7 @@ struct FeedState {
   std::mutex run_mu;            // one peaq_batch_run_host at a time; everything below is its own
   FeedSet set[2];
   DevBuf f_dec[2], f_48[2], f_cut[2], d_res, d_del;
+  DevBuf u_dec, u_48;           // peaq_batch_run_host_refs: a chunk's distinct references, decoded and at 48 kHz
   hipStream_t copy_s = nullptr, comp_s = nullptr;
   hipEvent_t del_done = nullptr;
 };
@@ -621,4 +624,348 @@ extern "C" int peaq_batch_run_host(peaq_ctx* c, int advanced, double level_db, c
   // (every chunk's results have been collected: both streams are idle, the staging sets free)
   for (FeedSet& s : st->set) s.upload_pending = s.raw_pending = false;
   return PEAQ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host-fed batch, references shared: tests[t] is scored against refs[tests[t].ref]
+// ---------------------------------------------------------------------------
+namespace {
+
+// what one distinct reference of a chunk takes: its raw bytes in two pinned sets and two device buffers, decoded once
+// and, if rate != 48000, converted once
+size_t feed_ref_bytes(const peaq_feed& f, uint64_t n, uint64_t n48) {
+  const size_t f32 = sizeof(float) * f.channels;
+  size_t b = 4 * (size_t)n * f.channels * kPcmBytes[f.format] + even_stride((size_t)n) * f32;
+  if (f.rate != 48000) b += even_stride((size_t)n48) * f32;
+  return b;
+}
+
+// ... and one test: a pair of peaq_batch_run_host (the reference's copy in the pair layout among it) less the
+// reference's four raw signals
+size_t feed_test_bytes(const peaq_feed& f, uint64_t n, uint64_t n48) {
+  return feed_pair_bytes(f, n, n48) - 4 * (size_t)n * f.channels * kPcmBytes[f.format];
+}
+
+struct RefsPlan {
+  std::vector<size_t> starts;    // first test of every chunk, and one entry behind the last
+  std::vector<size_t> ustarts;   // the same into uniq
+  std::vector<uint32_t> uniq;    // per chunk: the references its tests name, each once, in the order they first appear
+  std::vector<uint32_t> row;     // [n_tests]: where the test's reference stands among its chunk's
+};
+
+void plan_ref_chunks(const peaq_feed& f, size_t n_refs, const peaq_host_signal* refs, size_t n_tests,
+                     const peaq_host_test* tests, const std::vector<uint32_t>& r48, const std::vector<uint32_t>& t48,
+                     RefsPlan* pl) {
+  std::vector<size_t> stamp(n_refs, (size_t)-1);     // the chunk that listed the reference last
+  std::vector<uint32_t> row_of(n_refs, 0);
+  pl->row.resize(n_tests);
+  const size_t most = f.chunk_pairs ? f.chunk_pairs : 65535;
+  size_t p = 0;
+  for (size_t k = 0; p < n_tests; ++k) {
+    pl->starts.push_back(p);
+    pl->ustarts.push_back(pl->uniq.size());
+    uint64_t longest = 0, longest48 = 0;
+    size_t np = 0, nu = 0;
+    while (p + np < n_tests && np < most) {
+      const peaq_host_test& t = tests[p + np];
+      const bool fresh = stamp[t.ref] != k;
+      const uint64_t l = std::max(longest, std::max(t.n, refs[t.ref].n));
+      const uint64_t l48 = std::max<uint64_t>(longest48, std::max(t48[p + np], r48[t.ref]));
+      if (!f.chunk_pairs && np &&                      // (a test beyond the budget: a chunk of one)
+          (np + 1) * feed_test_bytes(f, l, l48) + (nu + fresh) * feed_ref_bytes(f, l, l48) > PEAQ_FEED_BUDGET_BYTES)
+        break;
+      if (fresh) {
+        stamp[t.ref] = k;
+        row_of[t.ref] = (uint32_t)nu++;
+        pl->uniq.push_back(t.ref);
+      }
+      pl->row[p + np] = row_of[t.ref];
+      longest = l;
+      longest48 = l48;
+      ++np;
+    }
+    p += np;
+  }
+  pl->starts.push_back(n_tests);
+  pl->ustarts.push_back(pl->uniq.size());
+}
+
+int reserve_dev(DevBuf& d, size_t bytes) {
+  if (bytes > d.cap) HIP_TRY(hipDeviceSynchronize());                // (growing frees the old buffer)
+  HIP_TRY(d.reserve(std::max<size_t>(bytes, 16)));
+  return PEAQ_OK;
+}
+
+// FeedRun with side 0 of a staging set holding the chunk's distinct references instead of one reference per pair
+struct RefsRun {
+  peaq_ctx* c;
+  FeedState* st;
+  peaq_feed f;
+  int advanced, threads;
+  double level_db;
+  const peaq_host_signal* refs;
+  const peaq_host_test* tests;
+  const std::vector<uint32_t>* r48;                   // [n_refs], [n_tests]: lengths at 48 kHz
+  const std::vector<uint32_t>* t48;
+  const RefsPlan* pl;
+  peaq_result* results;
+  peaq_delay* delays;
+
+  size_t first(size_t k) const { return pl->starts[k]; }
+  size_t count(size_t k) const { return pl->starts[k + 1] - pl->starts[k]; }
+  const uint32_t* uniq(size_t k) const { return pl->uniq.data() + pl->ustarts[k]; }
+  size_t ucount(size_t k) const { return pl->ustarts[k + 1] - pl->ustarts[k]; }
+  // samples per channel: the chunk's longest reference (side 0) or test (side 1)
+  size_t raw_stride(size_t k, int side) const {
+    uint64_t l = 0;
+    if (side)
+      for (size_t p = first(k); p < first(k) + count(k); ++p) l = std::max(l, tests[p].n);
+    else
+      for (size_t u = 0; u < ucount(k); ++u) l = std::max(l, refs[uniq(k)[u]].n);
+    return (size_t)l;
+  }
+
+  // chunk k's raw bytes into its staging set, each side at its own stride, then to the device on the copy stream
+  int stage(size_t k) {
+    FeedSet& s = st->set[k & 1];
+    const size_t unit = f.channels * kPcmBytes[f.format], cnt[2] = {ucount(k), count(k)};
+    const size_t row_bytes[2] = {raw_stride(k, 0) * unit, raw_stride(k, 1) * unit};
+    if (s.upload_pending) {                            // chunk k - 2's copies still read the pinned buffers
+      HIP_TRY(hipEventSynchronize(s.uploaded));
+      s.upload_pending = false;
+    }
+    std::vector<CopyJob> jobs;
+    for (int i = 0; i < 2; ++i) {
+      HIP_TRY(s.h_raw[i].reserve(std::max<size_t>(cnt[i] * row_bytes[i], 16)));
+      for (size_t q = 0; q < cnt[i]; ++q) {
+        const char* src = static_cast<const char*>(i ? tests[first(k) + q].data : refs[uniq(k)[q]].data);
+        const size_t len = (size_t)(i ? tests[first(k) + q].n : refs[uniq(k)[q]].n) * unit;
+        char* dst = s.h_raw[i].as<char>() + q * row_bytes[i];
+        for (size_t o = 0; o < len; o += kFeedSlice) jobs.push_back({src + o, dst + o, std::min(kFeedSlice, len - o)});
+      }
+    }
+    run_copies(jobs, threads);
+    if (s.raw_pending) {                               // chunk k - 2's decoder still reads the device buffers
+      HIP_TRY(hipStreamWaitEvent(st->copy_s, s.raw_free, 0));
+      s.raw_pending = false;
+    }
+    for (int i = 0; i < 2; ++i) {
+      if (int rc = reserve_dev(s.d_raw[i], cnt[i] * row_bytes[i])) return rc;
+      if (cnt[i] * row_bytes[i])
+        HIP_TRY(hipMemcpyAsync(s.d_raw[i].p, s.h_raw[i].p, cnt[i] * row_bytes[i], hipMemcpyHostToDevice, st->copy_s));
+    }
+    HIP_TRY(hipEventRecord(s.uploaded, st->copy_s));
+    s.upload_pending = true;
+    return PEAQ_OK;
+  }
+
+  // decode through score for chunk k on the compute stream; the results travel to the set's pinned buffer
+  int compute(size_t k) {
+    FeedSet& s = st->set[k & 1];
+    const size_t p0 = first(k), np = count(k), nu = ucount(k), C = (size_t)f.channels;
+    const size_t rs_ref = raw_stride(k, 0), rs_test = raw_stride(k, 1);
+    const uint32_t* row = pl->row.data() + p0;
+    hipStream_t cs = st->comp_s;
+    std::vector<uint32_t> n_u(nu), m_u(nu), n_t(np), m[2];   // lengths as uploaded, and as they stand after each stage
+    for (size_t u = 0; u < nu; ++u) n_u[u] = (uint32_t)refs[uniq(k)[u]].n;
+    for (size_t q = 0; q < np; ++q) n_t[q] = (uint32_t)tests[p0 + q].n;
+    m_u = n_u;
+    m[1] = n_t;
+    HIP_TRY(hipStreamWaitEvent(cs, s.uploaded, 0));
+    size_t stride = even_stride(std::max(rs_ref, rs_test)), ustride = even_stride(rs_ref);   // pairs; the distinct references
+    if (int rc = reserve_dev(st->f_dec[1], np * stride * C * sizeof(float))) return rc;
+    if (int rc = reserve_dev(st->u_dec, nu * ustride * C * sizeof(float))) return rc;
+    const float* cur_u = st->u_dec.as<float>();
+    float* cur[2] = {nullptr, st->f_dec[1].as<float>()};
+    if (int rc = peaq_batch_decode_pcm(c, f.format, f.channels, (int)np, s.d_raw[1].p, rs_test, n_t.data(), 0, cur[1], stride, cs))
+      return rc;
+    if (int rc = peaq_batch_decode_pcm(c, f.format, f.channels, (int)nu, s.d_raw[0].p, rs_ref, n_u.data(), 0, st->u_dec.as<float>(),
+                                       ustride, cs))
+      return rc;
+    HIP_TRY(hipEventRecord(s.raw_free, cs));
+    s.raw_pending = true;
+    DevBuf* paired = &st->f_dec[0];                    // where the references stand in the pair layout
+    if (f.rate != 48000) {
+      uint32_t longest = 0, ulongest = 0;
+      for (size_t u = 0; u < nu; ++u) ulongest = std::max(ulongest, (*r48)[uniq(k)[u]]);
+      for (size_t q = 0; q < np; ++q) longest = std::max(longest, (*t48)[p0 + q]);
+      const size_t s48 = even_stride(std::max(longest, ulongest)), us48 = even_stride(ulongest);
+      if (int rc = reserve_dev(st->f_48[1], np * s48 * C * sizeof(float))) return rc;
+      if (int rc = reserve_dev(st->u_48, nu * us48 * C * sizeof(float))) return rc;
+      if (int rc = peaq_batch_resample(c, f.channels, f.rate, (int)np, cur[1], stride, n_t.data(), 0, st->f_48[1].as<float>(),
+                                       s48, m[1].data(), cs))
+        return rc;
+      if (int rc = peaq_batch_resample(c, f.channels, f.rate, (int)nu, cur_u, ustride, n_u.data(), 0, st->u_48.as<float>(), us48,
+                                       m_u.data(), cs))
+        return rc;
+      cur[1] = st->f_48[1].as<float>();
+      cur_u = st->u_48.as<float>();
+      stride = s48;
+      ustride = us48;
+      paired = &st->f_48[0];
+    }
+    // every test's reference from the distinct rows into the pair layout
+    std::vector<uint32_t> src(row, row + np), none(np, 0);
+    m[0].resize(np);
+    for (size_t q = 0; q < np; ++q) m[0][q] = m_u[row[q]];
+    if (int rc = reserve_dev(*paired, np * stride * C * sizeof(float))) return rc;
+    cur[0] = paired->as<float>();
+    if (int rc = peaq_batch_gather(c, f.channels, (int)nu, (int)np, cur_u, ustride, src.data(), none.data(), m[0].data(), cur[0],
+                                   stride, cs))
+      return rc;
+    if (f.align_max_lag) {
+      if (np * sizeof(peaq_delay) > st->d_del.cap) HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(st->d_del.reserve(np * sizeof(peaq_delay)));
+      HIP_TRY(s.h_del.reserve(np * sizeof(peaq_delay)));
+      if (int rc = peaq_batch_estimate_delay(c, f.channels, (int)np, cur[0], cur[1], stride, m[0].data(), m[1].data(), 0,
+                                             f.align_max_lag, st->d_del.as<peaq_delay>(), cs))
+        return rc;
+      HIP_TRY(hipMemcpyAsync(s.h_del.p, st->d_del.p, np * sizeof(peaq_delay), hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipEventRecord(st->del_done, cs));
+      HIP_TRY(hipEventSynchronize(st->del_done));    // the cut needs the lags on the host
+      std::vector<uint32_t> skip[2], common(np);
+      skip[0].resize(np);
+      skip[1].resize(np);
+      uint32_t longest = 0;
+      for (size_t q = 0; q < np; ++q) {
+        const peaq_delay& rec = s.h_del.as<peaq_delay>()[q];
+        if (delays) delays[p0 + q] = rec;
+        peaq_aligned_lengths(rec.lag, m[0][q], m[1][q], &skip[0][q], &skip[1][q], &common[q]);
+        longest = std::max(longest, common[q]);
+      }
+      const size_t sc = even_stride(longest);
+      for (DevBuf& d : st->f_cut)
+        if (int rc = reserve_dev(d, np * sc * C * sizeof(float))) return rc;
+      // the reference's cut: again from the distinct rows, each test's own skip
+      if (int rc = peaq_batch_gather(c, f.channels, (int)nu, (int)np, cur_u, ustride, src.data(), skip[0].data(), common.data(),
+                                     st->f_cut[0].as<float>(), sc, cs))
+        return rc;
+      if (int rc = peaq_batch_cut(c, f.channels, (int)np, cur[1], stride, skip[1].data(), common.data(), st->f_cut[1].as<float>(),
+                                  sc, cs))
+        return rc;
+      for (int i = 0; i < 2; ++i) {
+        cur[i] = st->f_cut[i].as<float>();
+        m[i] = common;
+      }
+      stride = sc;
+    }
+    if (np * sizeof(peaq_result) > st->d_res.cap) HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(st->d_res.reserve(np * sizeof(peaq_result)));
+    HIP_TRY(s.h_res.reserve(np * sizeof(peaq_result)));
+    if (int rc = peaq_batch_run(c, advanced, f.channels, level_db, (int)np, cur[0], cur[1], stride, m[0].data(), m[1].data(),
+                                0, st->d_res.as<peaq_result>(), cs))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(s.h_res.p, st->d_res.p, np * sizeof(peaq_result), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipEventRecord(s.res_done, cs));
+    return PEAQ_OK;
+  }
+
+  int collect(size_t k) {
+    FeedSet& s = st->set[k & 1];
+    HIP_TRY(hipEventSynchronize(s.res_done));
+    std::memcpy(results + first(k), s.h_res.p, count(k) * sizeof(peaq_result));
+    return PEAQ_OK;
+  }
+
+  int run() {
+    const size_t n_chunks = pl->starts.size() - 1;
+    if (int rc = stage(0)) return rc;
+    for (size_t k = 0; k < n_chunks; ++k) {
+      if (int rc = compute(k)) return rc;
+      if (k + 1 < n_chunks)                            // packing and upload beside chunk k's kernels
+        if (int rc = stage(k + 1)) return rc;
+      if (k)
+        if (int rc = collect(k - 1)) return rc;
+    }
+    return collect(n_chunks - 1);
+  }
+};
+
+}  // namespace
+
+extern "C" size_t peaq_feed_refs_workspace_bytes(const peaq_feed* feed, int advanced, size_t n_refs, size_t n_tests,
+                                                 uint64_t n_max) {
+  if (check_feed("peaq_feed_refs_workspace_bytes", feed) != PEAQ_OK || n_refs == 0 || n_tests == 0 || n_max > 0xFFFFFFFFull)
+    return 0;
+  uint64_t n48 = n_max;
+  if (feed->rate != 48000) {
+    n48 = peaq_resampled_length(n_max, feed->rate);
+    if (n_max && !n48) return 0;
+  }
+  const size_t per_test = feed_test_bytes(*feed, n_max, n48), per_ref = feed_ref_bytes(*feed, n_max, n48);
+  // the most distinct references a chunk of `chunk` tests can name is min (chunk, n_refs)
+  size_t chunk = feed->chunk_pairs;
+  if (!chunk) {
+    chunk = PEAQ_FEED_BUDGET_BYTES / (per_test + per_ref);
+    if (chunk > n_refs) chunk = std::max(n_refs, (PEAQ_FEED_BUDGET_BYTES - std::min(PEAQ_FEED_BUDGET_BYTES, n_refs * per_ref)) / per_test);
+    chunk = std::max<size_t>(chunk, 1);
+  }
+  chunk = std::min<size_t>(std::min<size_t>(chunk, n_tests), 65535);
+  size_t b = chunk * per_test + std::min(chunk, n_refs) * per_ref +
+             peaq_batch_workspace_bytes(advanced, feed->channels, (int)chunk, (uint32_t)n48);
+  if (feed->align_max_lag) b += peaq_align_workspace_bytes(feed->channels, (int)chunk, (uint32_t)n48, feed->align_max_lag);
+  return b;
+}
+
+extern "C" int peaq_batch_run_host_refs(peaq_ctx* c, int advanced, double level_db, const peaq_feed* feed, size_t n_refs,
+                                        const peaq_host_signal* refs, size_t n_tests, const peaq_host_test* tests,
+                                        peaq_result* results, peaq_delay* delays) {
+  const char* who = "peaq_batch_run_host_refs";
+  const std::string w(who);
+  if (int rc = check_feed(who, feed)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  int threads = 0;
+  if (int rc = feed_threads(&threads)) return rc;
+  if (n_tests && (!tests || !results)) return fail(PEAQ_ERR_ARG, w + ": NULL tests or results");
+  if (n_tests && n_refs && !refs) return fail(PEAQ_ERR_ARG, w + ": NULL refs");
+  std::vector<uint32_t> r48(n_refs, 0), t48(n_tests);
+  std::vector<char> named(n_refs, 0);
+  const auto length48 = [&](const char* what, size_t i, uint64_t n, const void* data, uint32_t* out) {
+    if (n && !data)
+      return fail(PEAQ_ERR_ARG, w + ": " + what + " " + std::to_string(i) + " has " + std::to_string(n) + " samples and a NULL buffer");
+    if (n > 0xFFFFFFFFull)
+      return fail(PEAQ_ERR_ARG, w + ": " + what + " " + std::to_string(i) + " has " + std::to_string(n) + " samples, more than 2^32 - 1");
+    *out = (uint32_t)n;
+    if (feed->rate != 48000) {
+      *out = peaq_resampled_length(n, feed->rate);
+      if (n && !*out) return (int)PEAQ_ERR_ARG;          // (the message is peaq_resampled_length's)
+    }
+    return (int)PEAQ_OK;
+  };
+  for (size_t t = 0; t < n_tests; ++t) {
+    if (tests[t].ref >= n_refs)
+      return fail(PEAQ_ERR_ARG, w + ": test " + std::to_string(t) + " names reference " + std::to_string(tests[t].ref) + " of " +
+                                    std::to_string(n_refs));
+    if (int rc = length48("test", t, tests[t].n, tests[t].data, &t48[t])) return rc;
+    named[tests[t].ref] = 1;
+  }
+  for (size_t r = 0; r < n_refs; ++r)                   // (a reference nobody names is not looked at)
+    if (named[r])
+      if (int rc = length48("reference", r, refs[r].n, refs[r].data, &r48[r])) return rc;
+  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
+  if (n_tests == 0) return PEAQ_OK;
+  if (delays && !feed->align_max_lag) std::memset(delays, 0, n_tests * sizeof(peaq_delay));
+
+  FeedState* st;
+  {
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (!c->feed) c->feed = new FeedState;
+    st = c->feed;
+  }
+  std::lock_guard<std::mutex> run_lock(st->run_mu);   // (the lock, streams, events and staging sets of peaq_batch_run_host)
+  HIP_TRY(hipSetDevice(c->device));
+  if (!st->copy_s) HIP_TRY(hipStreamCreateWithFlags(&st->copy_s, hipStreamNonBlocking));
+  if (!st->comp_s) HIP_TRY(hipStreamCreateWithFlags(&st->comp_s, hipStreamNonBlocking));
+  if (!st->del_done) HIP_TRY(hipEventCreateWithFlags(&st->del_done, hipEventDisableTiming));
+  for (FeedSet& s : st->set)
+    for (hipEvent_t* e : {&s.uploaded, &s.raw_free, &s.res_done})
+      if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  RefsPlan plan;
+  plan_ref_chunks(*feed, n_refs, refs, n_tests, tests, r48, t48, &plan);
+  RefsRun run{c, st, *feed, advanced ? 1 : 0, threads, level_db, refs, tests, &r48, &t48, &plan, results, delays};
+  const int rc = run.run();
+  const std::string msg = rc != PEAQ_OK ? peaq_err_string() : std::string();
+  if (rc != PEAQ_OK) (void)hipDeviceSynchronize();    // stop: nothing more is started, what runs drains before the buffers are reused
+  for (FeedSet& s : st->set) s.upload_pending = s.raw_pending = false;
+  return rc != PEAQ_OK ? fail(rc, msg) : PEAQ_OK;
 }

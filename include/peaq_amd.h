@@ -569,6 +569,52 @@ int peaq_batch_run_host (peaq_ctx *ctx, int advanced, double playback_level_db, 
  * per channel (at the feed's rate), in bytes; 0 for a feed peaq_batch_run_host would refuse. */
 size_t peaq_feed_workspace_bytes (const peaq_feed *feed, int advanced, size_t n_pairs, uint64_t n_max);
 
+/* ---- one reference, many tests: gather and the host-fed batch with shared references ------------------------
+ * Codec and listening-test corpora are one reference against K coded versions.  peaq_batch_run_host_refs takes the
+ * references and the tests as two lists, each test naming its reference, and uploads, decodes and rate-converts a
+ * reference once per chunk instead of once per test; peaq_batch_gather is the device copy that then puts it in front of
+ * every test that names it.
+ *
+ * out[p][i][c] = in[src[p]][skip[p] + i][c]  for i < n_keep[p], p < n_out; samples of d_out past n_keep[p] untouched.
+ * d_in holds n_rows signals, in_stride samples per channel apart; src / skip / n_keep: host arrays of n_out entries
+ * (pinned staging slots, copied on `stream`, as peaq_batch_cut's).  A row may be named by any number of outputs, or none.
+ * It is peaq_batch_cut with a source index: with src[p] = p and n_rows = n_out it writes bit for bit what
+ * peaq_batch_cut writes.  Bits are moved as they are, NaN payloads included.  Enqueues on `stream` and synchronises
+ * nothing.  PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: a src[p] that is
+ * not below n_rows, a skip[p] + n_keep[p] that passes in_stride, an out_stride below the longest n_keep, NULL buffers or
+ * arrays, channels other than 1 or 2, n_out or n_rows above 65535, a d_out that overlaps d_in. */
+int peaq_batch_gather (peaq_ctx *ctx, int channels, int n_rows, int n_out,
+                       const float *d_in, size_t in_stride,
+                       const uint32_t *src /* host */, const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                       float *d_out, size_t out_stride, void *stream);
+
+typedef struct { const void *data; uint64_t n; } peaq_host_signal;                    /* samples per channel */
+typedef struct { const void *data; uint64_t n; uint32_t ref, reserved; } peaq_host_test;   /* ref: index into refs[] */
+/* results[t] and delays[t] are bit for bit what peaq_batch_run_host writes for the pair { refs[tests[t].ref], tests[t] }
+ * with the same feed, whatever the chunking, the order of the tests, and the other tests and references of the call.
+ * Pipeline: as peaq_batch_run_host's (two streams, two staging sets, the same packing threads and error handling; one
+ * call of either kind per context at a time).  Tests are taken in the caller's order, in chunks; feed->chunk_pairs
+ * counts tests.  A chunk's staging set holds its tests and each distinct reference the chunk names, once; on the
+ * device: decode the tests, decode the references once each; if rate != 48000 convert the tests, convert the
+ * references once each; peaq_batch_gather the references into the pair layout; if aligned estimate the delays and cut
+ * (the reference's cut is a gather with each test's skip); peaq_batch_run.
+ * A reference named by tests of two chunks is uploaded in both: the saving is there when the tests of a reference
+ * stand next to each other in tests[], so sort by reference where the order is free.  A reference nobody names is
+ * never touched, and its data may be NULL.
+ * Chunk size: PEAQ_FEED_BUDGET_BYTES as for peaq_batch_run_host, with a reference counted once per chunk -- its raw
+ * bytes in two pinned sets and two device buffers, its decoded signal, its converted one if rate != 48000 -- and a test
+ * as a pair there less the reference's four raw signals (the reference's copy in the pair layout stays per test).
+ * PEAQ_ERR_ARG before any device is touched: what peaq_batch_run_host refuses, a tests[t].ref that is not below n_refs
+ * (the message names t and the index), a named reference with samples but no buffer. */
+int peaq_batch_run_host_refs (peaq_ctx *ctx, int advanced, double playback_level_db, const peaq_feed *feed,
+                              size_t n_refs, const peaq_host_signal *refs,
+                              size_t n_tests, const peaq_host_test *tests,
+                              peaq_result *results /* host, [n_tests] */, peaq_delay *delays /* host, may be NULL */);
+/* peaq_feed_workspace_bytes for a call of n_tests tests that name n_refs references, none longer than n_max samples
+ * per channel, a chunk taken to name as many distinct references as it can; 0 for a feed it would refuse, no tests or
+ * no references. */
+size_t peaq_feed_refs_workspace_bytes (const peaq_feed *feed, int advanced, size_t n_refs, size_t n_tests, uint64_t n_max);
+
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
  * multiply-adds per wave, <= 0: about 70 ms) on the context's device -- alone: it waits for everything this PROCESS has
