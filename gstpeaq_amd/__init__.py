@@ -12,6 +12,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    estimate_delay, cut, align, aligned_lengths, align_workspace_bytes, Delay,
                    decode_pcm, run_host, run_files, make_feed, feed_workspace_bytes, pcm_format, pcm_sample_bytes, Feed, HostPair,
                    gather, run_host_refs, feed_refs_workspace_bytes, HostSignal, HostTest,
+                   Gain, measure_gain, cut_scaled, gain_workspace_bytes, gain_records, gain_mode, GAIN_DTYPE, GAIN_MODES,
+                   GAIN_PER_CHANNEL, GAIN_F_SILENT, GAIN_F_NONFINITE, GAIN_F_ZERO, GAIN_F_RANGE,
                    PCM_FORMATS, PCM_DTYPES,
                    batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
@@ -24,4 +26,6 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "HostPair", "PCM_FORMATS", "PCM_DTYPES", "gather", "run_host_refs", "feed_refs_workspace_bytes", "HostSignal", "HostTest",
            "batch_trace", "run_pair_trace", "frame_count", "FrameTrace", "BlockTrace", "FRAME_TRACE_DTYPE", "BLOCK_TRACE_DTYPE",
            "TRACE_ABOVE", "TRACE_MOD_OPEN", "TRACE_LOUD_OPEN", "TRACE_FLUSH",
+           "Gain", "measure_gain", "cut_scaled", "gain_workspace_bytes", "gain_records", "gain_mode", "GAIN_DTYPE", "GAIN_MODES",
+           "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

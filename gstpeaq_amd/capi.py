@@ -42,6 +42,20 @@ class Delay(C.Structure):
                 ("norm", C.c_double)]
 
 
+class Gain(C.Structure):
+    """mirrors peaq_gain (include/peaq_amd.h)"""
+    _fields_ = [("gain", C.c_double * 2), ("srr", C.c_double * 2), ("stt", C.c_double * 2), ("srt", C.c_double * 2),
+                ("flags", C.c_uint32 * 2), ("n", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# PEAQ_GAIN_* (include/peaq_amd.h) and the record as a numpy structured dtype
+GAIN_MODES = {None: 0, "off": 0, "lsq": 1, "rms": 2, "polarity": 3}
+GAIN_PER_CHANNEL = 0x10
+GAIN_F_SILENT, GAIN_F_NONFINITE, GAIN_F_ZERO, GAIN_F_RANGE = 1, 2, 4, 8
+GAIN_DTYPE = np.dtype([("gain", "<f8", (2,)), ("srr", "<f8", (2,)), ("stt", "<f8", (2,)), ("srt", "<f8", (2,)),
+                       ("flags", "<u4", (2,)), ("n", "<u4"), ("reserved", "<u4")])
+
+
 class FrameTrace(C.Structure):
     """mirrors peaq_frame_trace (include/peaq_amd.h)"""
     _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
@@ -225,6 +239,21 @@ def load_library():
                                                C.c_size_t, C.POINTER(HostTest), dp, C.POINTER(Delay)]
         L.peaq_feed_refs_workspace_bytes.restype = C.c_size_t
         L.peaq_feed_refs_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_size_t, C.c_size_t, C.c_uint64]
+    if hasattr(L, "peaq_batch_measure_gain"):        # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_gain_size.restype = C.c_size_t
+        L.peaq_gain_size.argtypes = []
+        L.peaq_batch_measure_gain.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, vp, C.c_size_t, u32p, u32p, C.c_int,
+                                              C.c_double, vp, vp]
+        L.peaq_gain_workspace_bytes.restype = C.c_size_t
+        L.peaq_gain_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32]
+        L.peaq_batch_cut_scaled.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, vp, vp, C.c_size_t, vp]
+        L.peaq_run_pair_matched.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_double, fp,
+                                            C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Gain), dp]
+        L.peaq_batch_run_host_matched.argtypes = [vp, C.c_int, C.c_double, C.POINTER(Feed), C.c_int, C.c_double, C.c_size_t,
+                                                  C.POINTER(HostSignal), C.c_size_t, C.POINTER(HostTest), dp, C.POINTER(Delay),
+                                                  C.POINTER(Gain)]
+        L.peaq_feed_matched_workspace_bytes.restype = C.c_size_t
+        L.peaq_feed_matched_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint64]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -641,8 +670,94 @@ def gather(ctx, x, src, skip=None, n_keep=None, out=None, stream=None):
     return out
 
 
-def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None):
+def gain_mode(gain, per_channel=False):
+    """PEAQ_GAIN_* of a name (None 'lsq' 'rms' 'polarity') or of the number itself, PEAQ_GAIN_PER_CHANNEL or-ed in"""
+    if not isinstance(gain, (int, np.integer)):
+        if gain not in GAIN_MODES:
+            raise PeaqError(f"unknown gain mode {gain!r}: None, 'lsq', 'rms' or 'polarity'")
+        gain = GAIN_MODES[gain]
+    return int(gain) | (GAIN_PER_CHANNEL if per_channel else 0)
+
+
+def gain_workspace_bytes(channels, n_pairs, n_max):
+    """partial sums of measure_gain for a shape (peaq_gain_workspace_bytes)"""
+    return int(load_library().peaq_gain_workspace_bytes(int(channels), int(n_pairs), int(n_max)))
+
+
+def gain_records(rec, n_pairs=None):
+    """a device record tensor of measure_gain (or a ctypes Gain array) as a dict of numpy arrays: gain, srr, stt, srt,
+    flags [n_pairs, 2] and n [n_pairs]; synchronises the device the tensor is on"""
+    if hasattr(rec, "is_cuda"):
+        import torch
+        torch.cuda.synchronize(rec.device)
+        rows = rec.cpu().numpy().copy().view(GAIN_DTYPE)[:, 0]
+    else:
+        rows = np.frombuffer(bytes(rec), dtype=GAIN_DTYPE)
+    rows = rows[:len(rows) if n_pairs is None else n_pairs]
+    return {k: np.ascontiguousarray(rows[k]) for k in ("gain", "srr", "stt", "srt", "flags", "n")}
+
+
+def measure_gain(ctx, ref, test, mode, skip_ref=None, skip_test=None, n=None, max_gain_db=40.0, per_channel=False,
+                 stream=None):
+    """Gain of every pair's test signal against its reference over n[p] samples from skip_ref[p] / skip_test[p] on
+    (peaq_batch_measure_gain): ref/test CUDA float32 [n_pairs, n_samples, channels], each with its own n_samples.
+    Without skips: zeros; without n: what both buffers hold behind their skips.  mode: 'lsq' 'rms' 'polarity' (or None:
+    sums only).  Enqueues and returns (rec, read): the device record tensor (uint8 [n_pairs, 80], what cut_scaled
+    takes) and a function that synchronises and returns the records as numpy arrays (gain_records)."""
+    import torch
+    for x in (ref, test):
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, channels = ref.shape[0], ref.shape[2]
+    assert test.shape[0] == n_pairs and test.shape[2] == channels
+    a_sr = np.zeros(n_pairs, np.uint32) if skip_ref is None else np.ascontiguousarray(skip_ref, dtype=np.uint32)
+    a_st = np.zeros(n_pairs, np.uint32) if skip_test is None else np.ascontiguousarray(skip_test, dtype=np.uint32)
+    if n is None:
+        a_n = np.minimum(ref.shape[1] - np.minimum(a_sr, ref.shape[1]), test.shape[1] - np.minimum(a_st, test.shape[1])).astype(np.uint32)
+    else:
+        a_n = np.ascontiguousarray(n, dtype=np.uint32)
+    assert a_sr.shape == (n_pairs,) and a_st.shape == (n_pairs,) and a_n.shape == (n_pairs,)
+    assert ctx.L.peaq_gain_size() == C.sizeof(Gain) == GAIN_DTYPE.itemsize
+    with _torch_stream(stream):
+        rec = torch.zeros((max(n_pairs, 1), C.sizeof(Gain)), dtype=torch.uint8, device=ref.device)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_measure_gain(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), ref.shape[1],
+                                         a_sr.ctypes.data_as(u32p), C.c_void_p(test.data_ptr()), test.shape[1],
+                                         a_st.ctypes.data_as(u32p), a_n.ctypes.data_as(u32p),
+                                         gain_mode(mode, per_channel), float(max_gain_db), C.c_void_p(rec.data_ptr()),
+                                         _stream_ptr(stream)))
+    return rec, (lambda: gain_records(rec, n_pairs))
+
+
+def cut_scaled(ctx, x, skip, n_keep, gain, out=None, stream=None):
+    """cut with every pair's and channel's factor from the device records of measure_gain (peaq_batch_cut_scaled):
+    out[p, i, c] = float32(float64(x[p, skip[p] + i, c]) * gain[p].gain[c]); a factor of exactly 1.0 moves the bits.
+    gain: CUDA uint8 [n_pairs, 80].  out as for cut.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,)
+    assert gain.is_cuda and gain.dtype == torch.uint8 and gain.is_contiguous() and gain.shape[0] >= n_pairs
+    assert gain.shape[1] == C.sizeof(Gain)
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the copy runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_cut_scaled(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride,
+                                       a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p),
+                                       C.c_void_p(gain.data_ptr()), C.c_void_p(out.data_ptr()), out.shape[1],
+                                       _stream_ptr(stream)))
+    return out
+
+
+def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
+    gain: 'lsq' 'rms' 'polarity': the test signal's gain is measured over that part and applied in its cut
+    (measure_gain, cut_scaled); the record tensor is kept as align.last_gain.
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
     n_pairs, stride, _ = ref.shape
     assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
@@ -655,21 +770,37 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None):
     with _torch_stream(stream):
         bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
                 for _ in (0, 1)]
-    cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
-    cut(ctx, test, cuts[:, 1], cuts[:, 2], out=bufs[1], stream=stream)
+    if gain is None:
+        cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
+        cut(ctx, test, cuts[:, 1], cuts[:, 2], out=bufs[1], stream=stream)
+    else:
+        rec, _ = measure_gain(ctx, ref, test, gain, cuts[:, 0], cuts[:, 1], cuts[:, 2], max_gain_db=max_gain_db,
+                              per_channel=gain_per_channel, stream=stream)
+        cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
+        cut_scaled(ctx, test, cuts[:, 1], cuts[:, 2], rec, out=bufs[1], stream=stream)
+        align.last_gain = rec
     n = np.ascontiguousarray(cuts[:, 2])
     return bufs[0], bufs[1], n, n.copy()
 
 
-def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream):
-    """the `align=` keyword of batch_run / batch_trajectory: estimate, then cut"""
-    d = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)
-    return align(ctx, ref, test, d["lag"], n_ref, n_test, stream=stream)
+def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0):
+    """the `align=` and `gain=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without align: lags of
+    0), then match and cut"""
+    if max_lag is not None:
+        lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
+    else:
+        lags = np.zeros(ref.shape[0], dtype=np.int32)
+    if gain is None:
+        return align(ctx, ref, test, lags, n_ref, n_test, stream=stream)
+    return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
+                 max_gain_db=max_gain_db)
 
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
-              stream=None, sync=True, rate=48000, align=None):
+              stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    gain: 'lsq' 'rms' 'polarity': the test signal's level (polarity) is matched to the reference's over the common part,
+    after the alignment if there is one (measure_gain, cut_scaled); gain_per_channel, max_gain_db as measure_gain's.
     n_ref/n_test: optional per-pair lengths (samples per channel).
     rate: sampling rate of ref/test; anything but 48000 is converted on the device first (resample).
     align: a max_lag in 48 kHz samples: every pair's delay is estimated and both signals are cut to their common,
@@ -678,7 +809,9 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
+    if gain is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
+    elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
@@ -703,7 +836,7 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
 
 
 def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n_test=None, playback_level=92.0,
-                     stream=None, sync=True, rate=48000, align=None):
+                     stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
     """Readings every `interval` samples per channel through each pair (peaq_batch_run_trajectory): point k of pair p
     is what a session pushed the first min((k + 1) interval, n) samples of each signal reads, unflushed.
     ref/test, rate and align as for batch_run; `interval` counts samples at 48 kHz whatever the rate.  Returns
@@ -712,7 +845,9 @@ def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
+    if gain is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
+    elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
@@ -781,7 +916,7 @@ def frame_count(n_ref, n_test, filter_bank=False):
 
 
 def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
-                stream=None, sync=True, d_frames=None, d_blocks=None):
+                stream=None, sync=True, d_frames=None, d_blocks=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
     """The MOV layer's values of every frame and block of every pair, in the run that scores them
     (peaq_batch_run_trace).  ref/test, n_ref/n_test, rate and align as for batch_run.  d_frames / d_blocks: optional
     record tensors to write into (CUDA uint8 [n_pairs, stride, 128] / [.., 96]; records past a pair's count keep what
@@ -794,7 +929,9 @@ def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_leve
     _check_trace_sizes(ctx.L)
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
+    if gain is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
+    elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
@@ -868,7 +1005,12 @@ def run_pair_trace(ctx, advanced, ref, test, playback_level=92.0, rate=48000, al
     return res
 
 
-def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None):
+def _gain_dict(rec):
+    return dict(gain=list(rec.gain), srr=list(rec.srr), stt=list(rec.stt), srt=list(rec.srt), flags=list(rec.flags), n=int(rec.n))
+
+
+def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
+             max_gain_db=40.0):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
     the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`."""
@@ -877,6 +1019,18 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
+    if gain is not None:                               # peaq_run_pair_matched; the result dict carries the record as `gain`
+        rec, grec = Delay(), Gain()
+        _check(ctx.L.peaq_run_pair_matched(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),
+                                           0 if align is None else int(align), gain_mode(gain, gain_per_channel),
+                                           float(max_gain_db), ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                           test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec), C.byref(grec),
+                                           out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["gain"] = _gain_dict(grec)
+        if align is not None:
+            res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        return res
     if align is not None:
         rec = Delay()
         _check(ctx.L.peaq_run_pair_aligned(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
@@ -972,12 +1126,18 @@ def _run_host_rows(ctx, advanced, pairs, format, channels, rate, align, chunk_pa
     return out[:len(pairs)], rec
 
 
-def run_host(ctx, advanced, pairs, format, channels, rate=48000, align=None, chunk_pairs=0, playback_level=92.0):
+def run_host(ctx, advanced, pairs, format, channels, rate=48000, align=None, chunk_pairs=0, playback_level=92.0,
+             gain=None, gain_per_channel=False, max_gain_db=40.0):
     """Scores a list of pairs that sit in host memory in a file's own sample format (peaq_batch_run_host): upload, decode,
     rate conversion, alignment and scoring on the device, chunk by chunk.  pairs: [(ref, test)] numpy arrays in the
     file's dtype (PCM_DTYPES; S24: the bytes), interleaved, any shape; they may be unaligned views.  rate: sampling rate
     of all of them.  align: a max_lag in 48 kHz samples.  Returns the result dicts in list order, and with `align`
-    (results, delays): delays a dict of numpy arrays lag / peak / runner_up / norm as estimate_delay's."""
+    (results, delays): delays a dict of numpy arrays lag / peak / runner_up / norm as estimate_delay's.  gain: as
+    run_host_refs's, which scores the pairs then, one test per reference."""
+    if gain is not None:
+        return run_host_refs(ctx, advanced, [p[0] for p in pairs], [p[1] for p in pairs], list(range(len(pairs))), format,
+                             channels, rate=rate, align=align, chunk_pairs=chunk_pairs, playback_level=playback_level,
+                             gain=gain, gain_per_channel=gain_per_channel, max_gain_db=max_gain_db)
     out, rec = _run_host_rows(ctx, advanced, pairs, format, channels, rate, align, chunk_pairs, playback_level)
     res = [_result_dict(r, bool(advanced)) for r in out]
     if align is None:
@@ -998,9 +1158,10 @@ def feed_refs_workspace_bytes(feed, advanced, n_refs, n_tests, n_max):
                                                              int(n_max)))
 
 
-def _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs, playback_level):
-    """peaq_batch_run_host_refs on numpy arrays -> (rows float64 [n_tests, 16], the Delay records or None); a reference
-    may be None (no buffer, no samples)"""
+def _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs, playback_level,
+                        gain=None, gain_per_channel=False, max_gain_db=40.0):
+    """peaq_batch_run_host_refs (with gain: peaq_batch_run_host_matched) on numpy arrays -> (rows float64 [n_tests, 16],
+    the Delay records or None[, the Gain records]); a reference may be None (no buffer, no samples)"""
     fmt = pcm_format(format)
     unit = pcm_sample_bytes(fmt) * int(channels)
     assert unit, "unknown sample format"
@@ -1028,6 +1189,13 @@ def _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels,
     feed = make_feed(fmt, channels, rate, align, chunk_pairs)
     out = np.zeros((max(len(tests), 1), RESULT_DOUBLES))
     rec = (Delay * max(len(tests), 1))() if align is not None else None
+    if gain is not None:
+        grec = (Gain * max(len(tests), 1))()
+        _check(ctx.L.peaq_batch_run_host_matched(ctx.h, int(bool(advanced)), float(playback_level), C.byref(feed),
+                                                 gain_mode(gain, gain_per_channel), float(max_gain_db), len(refs), r_rows,
+                                                 len(tests), t_rows, out.ctypes.data_as(C.POINTER(C.c_double)), rec, grec))
+        del keep
+        return out[:len(tests)], rec, grec
     _check(ctx.L.peaq_batch_run_host_refs(ctx.h, int(bool(advanced)), float(playback_level), C.byref(feed), len(refs), r_rows,
                                           len(tests), t_rows, out.ctypes.data_as(C.POINTER(C.c_double)), rec))
     del keep
@@ -1035,25 +1203,34 @@ def _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels,
 
 
 def run_host_refs(ctx, advanced, refs, tests, ref_index, format, channels, rate=48000, align=None, chunk_pairs=0,
-                  playback_level=92.0):
+                  playback_level=92.0, gain=None, gain_per_channel=False, max_gain_db=40.0):
     """run_host for tests that share references (peaq_batch_run_host_refs): tests[t] is scored against
     refs[ref_index[t]], and a reference is uploaded, decoded and converted once per chunk, not once per test -- keep the
     tests of a reference next to each other.  A reference no test names may be None.  Returns what run_host returns for
-    the pairs (refs[ref_index[t]], tests[t]), bit for bit."""
+    the pairs (refs[ref_index[t]], tests[t]), bit for bit.  gain: 'lsq' 'rms' 'polarity': every test's level is matched
+    to its reference's on the device (peaq_batch_run_host_matched), and the gain records (gain_records) are returned
+    last: (results, gains) or (results, delays, gains)."""
+    if gain is not None:
+        out, rec, grec = _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs,
+                                             playback_level, gain, gain_per_channel, max_gain_db)
+        res = [_result_dict(r, bool(advanced)) for r in out]
+        gains = gain_records(grec, len(tests))
+        return (res, gains) if align is None else (res, _delay_arrays(rec, len(tests)), gains)
     out, rec = _run_host_refs_rows(ctx, advanced, refs, tests, ref_index, format, channels, rate, align, chunk_pairs,
                                    playback_level)
     res = [_result_dict(r, bool(advanced)) for r in out]
     return res if align is None else (res, _delay_arrays(rec, len(tests)))
 
 
-def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92.0, share_refs=True):
+def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92.0, share_refs=True, gain=None,
+              gain_per_channel=False, max_gain_db=40.0):
     """Scores a list of (ref_path, test_path) RIFF/WAVE files: the data chunks are read as they are (wavio.read_wav_raw),
     the pairs grouped by (format, channels, rate) and each group run through run_host_refs: within a group every distinct
     reference path (compared as the exact string) is read once and the tests are ordered by reference (a stable sort), so
     that a reference shared by several pairs is uploaded once per chunk.  share_refs=False: every line's reference is
     read again and the group goes through run_host.  Returns the result dicts in list order, and with `align`
     (results, delays), delays a list of dicts.  ValueError, naming the file, if the two files of a pair differ in
-    channels, rate or format."""
+    channels, rate or format.  gain: as run_host_refs's; the gain records come last, a list of dicts."""
     from . import wavio
     groups, loaded, read = {}, [], {}
     for p, (ref_path, test_path) in enumerate(files):
@@ -1068,7 +1245,8 @@ def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92
                 raise ValueError(f"{test_path}: {what} {b} differs from {ref_path}'s ({a})")
         loaded.append((r[0], t[0], key))
         groups.setdefault((r[1], r[2], r[3]), []).append(p)
-    results, delays = [None] * len(files), [None] * len(files)
+    results, delays, gains = [None] * len(files), [None] * len(files), [None] * len(files)
+    gkw = {} if gain is None else dict(gain=gain, gain_per_channel=gain_per_channel, max_gain_db=max_gain_db)
     for (fmt, channels, rate), members in groups.items():
         as_array = lambda b: np.frombuffer(b, dtype=PCM_DTYPES[fmt])   # noqa: E731
         if share_refs:
@@ -1081,17 +1259,25 @@ def run_files(ctx, advanced, files, align=None, chunk_pairs=0, playback_level=92
                 refs[index[loaded[p][2]]] = as_array(loaded[p][0])
             got = run_host_refs(ctx, advanced, refs, [as_array(loaded[p][1]) for p in members],
                                 [index[loaded[p][2]] for p in members], fmt, channels, rate=rate, align=align,
-                                chunk_pairs=chunk_pairs, playback_level=playback_level)
+                                chunk_pairs=chunk_pairs, playback_level=playback_level, **gkw)
         else:
             arrays = [(as_array(loaded[p][0]), as_array(loaded[p][1])) for p in members]
             got = run_host(ctx, advanced, arrays, fmt, channels, rate=rate, align=align, chunk_pairs=chunk_pairs,
-                           playback_level=playback_level)
+                           playback_level=playback_level, **gkw)
+        gn = None
+        if gain is not None:
+            got, gn = (got[0], got[-1]) if align is None else (got[:2], got[-1])
         res, dl = got if align is not None else (got, None)
         for i, p in enumerate(members):
             results[p] = res[i]
             if dl is not None:
                 delays[p] = {k: dl[k][i].item() for k in dl}
-    return (results, delays) if align is not None else results
+            if gn is not None:
+                gains[p] = {k: gn[k][i].tolist() for k in gn}
+    out = (results, delays) if align is not None else results
+    if gain is None:
+        return out
+    return out + (gains,) if align is not None else (out, gains)
 
 
 def synth_fill(ctx, seed0, n_pairs, channels, n_samples, device="cuda:0", stream=None, out=None):

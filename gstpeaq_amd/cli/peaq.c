@@ -233,15 +233,35 @@ by_key (const void *a, const void *b)
   return sort_key[x] != sort_key[y] ? (sort_key[x] > sort_key[y]) - (sort_key[x] < sort_key[y]) : (x > y) - (x < y);
 }
 
+/* --match-gain: the record as text, in the style of the delay line: per channel the gain applied in dB, "inverted" for
+ * a negative factor, and the flags of a channel left unmatched by name */
+static void
+format_gain (char *buf, size_t size, const peaq_gain * g, int channels)
+{
+  static const char *const names[4] = { "silent", "nonfinite", "zero", "range" };
+  size_t used = 0;
+  int c, b;
+  buf[0] = 0;
+  for (c = 0; c < channels && used < size; c++) {
+    used += (size_t) snprintf (buf + used, size - used, "%s%+.2f dB%s", c ? ", " : "", 20. * log10 (fabs (g->gain[c])),
+        g->gain[c] < 0. ? " inverted" : "");
+    for (b = 0; b < 4 && used < size; b++)
+      if (g->flags[c] & (1u << b))
+        used += (size_t) snprintf (buf + used, size - used, " [%s]", names[b]);
+  }
+}
+
 /* scores the pairs of `list_path`; the exit status */
 static int
-run_list (const char *list_path, int advanced, double level, uint32_t align_lag, int share_refs)
+run_list (const char *list_path, int advanced, double level, uint32_t align_lag, int share_refs, int gain_mode,
+    double max_gain_db)
 {
   FILE *f = fopen (list_path, "r");
   char *line = NULL, **names = NULL;
   size_t cap = 0, n_pairs = 0, room = 0, p, q;
   raw_t *raw = NULL;
   peaq_result *res = NULL;
+  peaq_gain *gains = NULL;
   peaq_host_pair *hp = NULL;
   size_t *members = NULL;
   char *done = NULL;
@@ -279,6 +299,7 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag,
   fclose (f);
   raw = calloc (2 * n_pairs + 1, sizeof *raw);
   res = calloc (n_pairs + 1, sizeof *res);
+  gains = calloc (n_pairs + 1, sizeof *gains);
   hp = calloc (n_pairs + 1, sizeof *hp);
   members = calloc (n_pairs + 1, sizeof *members);
   done = calloc (n_pairs + 1, 1);
@@ -349,9 +370,10 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag,
     feed.align_max_lag = align_lag;
     {
       peaq_result *out = malloc (n * sizeof *out);
+      peaq_gain *gout = malloc ((n + 1) * sizeof *gout);
       size_t n_refs = 0;
-      for (q = 0; share_refs && q < n; q++) {
-        if (!q || first[members[q]] != first[members[q - 1]]) {
+      for (q = 0; (share_refs || gain_mode) && q < n; q++) {   /* (matched pairs not shared: one test per reference) */
+        if (!q || !share_refs || first[members[q]] != first[members[q - 1]]) {
           hs[n_refs].data = hp[q].ref;
           hs[n_refs++].n = hp[q].n_ref;
         }
@@ -359,18 +381,30 @@ run_list (const char *list_path, int advanced, double level, uint32_t align_lag,
         ht[q].n = hp[q].n_test;
         ht[q].ref = (uint32_t) (n_refs - 1);
       }
-      if ((share_refs ? peaq_batch_run_host_refs (ctx, advanced, level, &feed, n_refs, hs, n, ht, out, NULL)
+      if ((gain_mode ? peaq_batch_run_host_matched (ctx, advanced, level, &feed, gain_mode, max_gain_db, n_refs, hs, n, ht,
+                  out, NULL, gout)
+              : share_refs ? peaq_batch_run_host_refs (ctx, advanced, level, &feed, n_refs, hs, n, ht, out, NULL)
               : peaq_batch_run_host (ctx, advanced, level, &feed, n, hp, out, NULL)) != PEAQ_OK) {
         fprintf (stderr, "Error: %s\n", peaq_last_error ());
         return 2;
       }
-      for (q = 0; q < n; q++)
+      for (q = 0; q < n; q++) {
         res[members[q]] = out[q];
+        if (gain_mode)
+          gains[members[q]] = gout[q];
+      }
       free (out);
+      free (gout);
     }
   }
-  for (p = 0; p < n_pairs; p++)
-    printf ("%s\t%s\t%.3f\t%.3f\n", names[2 * p], names[2 * p + 1], res[p].odg, res[p].di);
+  for (p = 0; p < n_pairs; p++) {
+    if (gain_mode) {
+      char text[256];
+      format_gain (text, sizeof text, &gains[p], raw[2 * p].channels);
+      printf ("%s\t%s\t%.3f\t%.3f\tGain: %s\n", names[2 * p], names[2 * p + 1], res[p].odg, res[p].di, text);
+    } else
+      printf ("%s\t%s\t%.3f\t%.3f\n", names[2 * p], names[2 * p + 1], res[p].odg, res[p].di);
+  }
   fflush (stdout);
   fprintf (stderr, "Note: %zu %s read for %zu pairs\n", n_read, share_refs ? "distinct references" : "references", n_pairs);
   if (ctx)
@@ -509,6 +543,11 @@ usage (const char *prog)
       "  --interval=S  also print ODG and DI read every S seconds through the files\n"
       "  --align[=SAMPLES] find the test file's delay within +-SAMPLES (48 kHz samples, 1..16384, default 4096)\n"
       "                on the GPU and compare the aligned parts (the plain one-call mode only)\n"
+      "  --match-gain[=lsq|rms|polarity] match the test file's level (polarity) to the reference's on the GPU, after\n"
+      "                --align if given, and print the gain applied (default lsq; the plain one-call mode and --list;\n"
+      "                not with --interval or --trace)\n"
+      "  --gain-per-channel  each channel its own gain\n"
+      "  --max-gain=DB leave a pair unmatched whose gain is beyond +-DB (0 < DB <= 120, default 40)\n"
       "  --trace=FILE  also write the MOV layer's values of every frame (and, with --advanced, every filter-bank\n"
       "                block) to FILE as CSV (the plain one-call mode; with --advanced, --device-resample, --align)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
@@ -594,6 +633,9 @@ main (int argc, char **argv)
   uint32_t device_rate = 0;     /* != 0: both files stay at this rate, peaq_run_pair_rate converts them */
   uint32_t align_lag = 0;       /* != 0: --align, peaq_run_pair_aligned */
   peaq_delay delay;
+  peaq_gain gain;
+  int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
+  double max_gain_db = 40.;
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   const char *list_path = NULL, *trace_path = NULL;
@@ -626,6 +668,26 @@ main (int argc, char **argv)
       }
       align_lag = (uint32_t) v;
     }
+    else if (!strcmp (argv[i], "--match-gain") || !strcmp (argv[i], "--match-gain=lsq"))
+      gain_mode = PEAQ_GAIN_LSQ;
+    else if (!strcmp (argv[i], "--match-gain=rms"))
+      gain_mode = PEAQ_GAIN_RMS;
+    else if (!strcmp (argv[i], "--match-gain=polarity"))
+      gain_mode = PEAQ_GAIN_POLARITY;
+    else if (!strncmp (argv[i], "--match-gain=", 13)) {
+      fprintf (stderr, "Failed to initialize: invalid gain mode %s (lsq, rms or polarity)\n", argv[i] + 13);
+      return 1;
+    }
+    else if (!strcmp (argv[i], "--gain-per-channel"))
+      gain_per_channel = 1;
+    else if (!strncmp (argv[i], "--max-gain=", 11)) {
+      char *end;
+      max_gain_db = strtod (argv[i] + 11, &end);
+      if (*end || end == argv[i] + 11 || !(max_gain_db > 0. && max_gain_db <= 120.)) {
+        fprintf (stderr, "Failed to initialize: invalid gain limit %s (0 < DB <= 120)\n", argv[i] + 11);
+        return 1;
+      }
+    }
     else if (!strncmp (argv[i], "--interval=", 11)) {
       char *end;
       interval_s = strtod (argv[i] + 11, &end);
@@ -657,12 +719,18 @@ main (int argc, char **argv)
     else
       nfiles++;
   }
+  if (gain_mode && gain_per_channel)
+    gain_mode |= PEAQ_GAIN_PER_CHANNEL;
+  if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
   if (list_path) {
     if (nfiles || interval_s > 0. || trace_path) {
       fprintf (stderr, "Failed to initialize: --list takes no REFFILE TESTFILE, no --interval and no --trace\n");
       return 1;
     }
-    return run_list (list_path, advanced, level, align_lag, share_refs);
+    return run_list (list_path, advanced, level, align_lag, share_refs, gain_mode, max_gain_db);
   }
   if (nfiles != 2) {
     usage (argv[0]);
@@ -762,6 +830,17 @@ main (int argc, char **argv)
     if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
+    } else if (gain_mode) {
+      char text[256];
+      if (peaq_run_pair_matched (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, gain_mode,
+              max_gain_db, ref.samples, ref.frames, test.samples, test.frames, &delay, &gain, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      if (align_lag)
+        printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+      format_gain (text, sizeof text, &gain, ref.channels);
+      printf ("Gain: %s\n", text);
     } else if (align_lag) {
       if (peaq_run_pair_aligned (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag,
               ref.samples, ref.frames, test.samples, test.frames, &delay, &r) != PEAQ_OK) {

@@ -588,16 +588,20 @@ extern "C" int peaq_batch_cut(peaq_ctx* c, int channels, int n_pairs, const floa
 }
 
 // One host pair made ready to score: upload, conversion of both signals to 48 kHz if rate != 48000 and, with max_lag,
-// estimate and cut (peaq_run_pair_aligned, peaq_run_pair_trace).  d[0], d[1]: the signals to score, `stride` samples per
-// channel long, len[] their lengths.  The arguments have been checked by the caller.
+// estimate and cut (peaq_run_pair_aligned, peaq_run_pair_trace) and, with a gain_mode other than PEAQ_GAIN_OFF, the gain
+// measured over the common part and applied in the test signal's cut (peaq_run_pair_matched; without max_lag the
+// skips are 0).  d[0], d[1]: the signals to score, `stride` samples per channel long, len[] their lengths.  The
+// arguments have been checked by the caller.
 struct PreparedPair {
-  DevBuf raw[2], s48[2], cut[2], rec;
+  DevBuf raw[2], s48[2], cut[2], rec, grec;
   const float* d[2] = {nullptr, nullptr};
   size_t stride = 0;
   uint32_t len[2] = {0, 0};
 };
 static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_lag, const float* ref, size_t n_ref,
-                        const float* test, size_t n_test, peaq_delay* delay, PreparedPair& pp) {
+                        const float* test, size_t n_test, peaq_delay* delay, PreparedPair& pp, int gain_mode = PEAQ_GAIN_OFF,
+                        double max_gain_db = 40., peaq_gain* gain = nullptr) {
+  const bool match = (gain_mode & 0xF) != PEAQ_GAIN_OFF;
   const size_t n[2] = {n_ref, n_test};
   const float* src[2] = {ref, test};
   uint32_t len[2];
@@ -628,7 +632,7 @@ static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_l
       return rc;
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (!max_lag) {                                    // the signals as they are
+  if (!max_lag && !match) {                          // the signals as they are
     if (delay) std::memset(delay, 0, sizeof *delay);
     for (int i = 0; i < 2; ++i) {
       pp.d[i] = pp.s48[i].as<float>();
@@ -637,28 +641,41 @@ static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_l
     pp.stride = stride;
     return PEAQ_OK;
   }
-  if (int rc = peaq_batch_estimate_delay(c, channels, 1, pp.s48[0].as<float>(), pp.s48[1].as<float>(), stride, len,
-                                         len + 1, 0, max_lag, pp.rec.as<peaq_delay>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
   peaq_delay rec;
-  HIP_TRY(hipMemcpy(&rec, pp.rec.p, sizeof rec, hipMemcpyDeviceToHost));
+  std::memset(&rec, 0, sizeof rec);
+  if (max_lag) {
+    if (int rc = peaq_batch_estimate_delay(c, channels, 1, pp.s48[0].as<float>(), pp.s48[1].as<float>(), stride, len,
+                                           len + 1, 0, max_lag, pp.rec.as<peaq_delay>(), nullptr))
+      return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&rec, pp.rec.p, sizeof rec, hipMemcpyDeviceToHost));
+  }
   if (delay) *delay = rec;
   uint32_t skip[2], common = 0;
   peaq_aligned_lengths(rec.lag, len[0], len[1], &skip[0], &skip[1], &common);
   size_t cstride = std::max<size_t>(common, 2);
   cstride += cstride & 1;
   const size_t cbytes = cstride * channels * sizeof(float);
+  if (match) {
+    HIP_TRY(pp.grec.reserve(sizeof(peaq_gain)));
+    if (int rc = peaq_batch_measure_gain(c, channels, 1, pp.s48[0].as<float>(), stride, &skip[0], pp.s48[1].as<float>(), stride,
+                                         &skip[1], &common, gain_mode, max_gain_db, pp.grec.as<peaq_gain>(), nullptr))
+      return rc;
+  }
   for (int i = 0; i < 2; ++i) {
     HIP_TRY(pp.cut[i].reserve(cbytes));
     HIP_TRY(hipMemset(pp.cut[i].p, 0, cbytes));
-    if (int rc = peaq_batch_cut(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common, pp.cut[i].as<float>(),
-                                cstride, nullptr))
+    if (int rc = match && i == 1
+                     ? peaq_batch_cut_scaled(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common,
+                                             pp.grec.as<peaq_gain>(), pp.cut[i].as<float>(), cstride, nullptr)
+                     : peaq_batch_cut(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common, pp.cut[i].as<float>(),
+                                      cstride, nullptr))
       return rc;
     pp.d[i] = pp.cut[i].as<float>();
     pp.len[i] = common;
   }
   HIP_TRY(hipDeviceSynchronize());
+  if (match && gain) HIP_TRY(hipMemcpy(gain, pp.grec.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
   pp.stride = cstride;
   return PEAQ_OK;
 }
@@ -677,6 +694,33 @@ extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, do
   if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
   PreparedPair pp;
   if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp)) return rc;
+  DevBuf d_res;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
+                              d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_run_pair_matched(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
+                                     uint32_t max_lag, int mode, double max_gain_db, const float* ref, size_t n_ref,
+                                     const float* test, size_t n_test, peaq_delay* delay, peaq_gain* gain, peaq_result* out) {
+  const char* who = "peaq_run_pair_matched";
+  if (int rc = check_gain_mode(who, mode, max_gain_db)) return rc;
+  if (max_lag)
+    if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  if (int rc = check_level(who, level_db)) return rc;
+  if (rate != 48000 && !peaq_resample_supported(rate))
+    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
+  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
+  if (gain) std::memset(gain, 0, sizeof *gain);
+  PreparedPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp, mode, max_gain_db, gain)) return rc;
   DevBuf d_res;
   HIP_TRY(d_res.reserve(sizeof(peaq_result)));
   if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,

@@ -10,6 +10,7 @@
 //   peaq_pcm.hip      PCM decoder in front of them (kernels and host side) and the host-fed batches (peaq_batch_run_host,
 //                     peaq_batch_run_host_refs)
 //   peaq_gather.hip   copy by source index, what shares one uploaded reference among its tests (kernel and host side)
+//   peaq_gain.hip     level and polarity matching between delay estimation and the cut (kernels and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -164,6 +165,7 @@ struct peaq_ctx {
   struct AlignState* al = nullptr;        // aligner: spectra scratch, length scratch (peaq_align.hip)
   struct FeedState* feed = nullptr;       // PCM decoder and host feed: length scratch, staging sets, streams (peaq_pcm.hip)
   struct GatherState* ga = nullptr;       // gather: index and length scratch (peaq_gather.hip)
+  struct GainState* gn = nullptr;         // gain matching: partial sums, length scratch (peaq_gain.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -183,6 +185,10 @@ void align_release(peaq_ctx* c);
 void feed_release(peaq_ctx* c);
 // the same for peaq_batch_gather (peaq_gather.hip)
 void gather_release(peaq_ctx* c);
+// the same for peaq_batch_measure_gain / peaq_batch_cut_scaled (peaq_gain.hip)
+void gain_release(peaq_ctx* c);
+// mode (PEAQ_GAIN_* with or without PEAQ_GAIN_PER_CHANNEL) and max_gain_db as every entry point of the stage takes them
+int check_gain_mode(const std::string& who, int mode, double max_gain_db);
 
 // ---------------------------------------------------------------------------
 // Per-pair host arrays of one call (lengths, skips): staged in pinned host memory and copied on the caller's stream,

@@ -188,7 +188,7 @@ struct PinBuf {
 };
 
 struct FeedSet {
-  PinBuf h_raw[2], h_res, h_del;                     // ref, test; the chunk's results and delay records
+  PinBuf h_raw[2], h_res, h_del, h_gain;             // ref, test; the chunk's results, delay and gain records
   DevBuf d_raw[2];
   hipEvent_t uploaded = nullptr;                     // behind the copies out of h_raw into d_raw
   hipEvent_t raw_free = nullptr;                     // behind the decoder that read d_raw
@@ -272,6 +272,7 @@ struct FeedState {
   FeedSet set[2];
   DevBuf f_dec[2], f_48[2], f_cut[2], d_res, d_del;
   DevBuf u_dec, u_48;           // peaq_batch_run_host_refs: a chunk's distinct references, decoded and at 48 kHz
+  DevBuf d_gain;                // peaq_batch_run_host_matched: the chunk's gain records
   hipStream_t copy_s = nullptr, comp_s = nullptr;
   hipEvent_t del_done = nullptr;
 };
@@ -284,6 +285,7 @@ void feed_release(peaq_ctx* c) {
     for (PinBuf& b : s.h_raw) b.release();
     s.h_res.release();
     s.h_del.release();
+    s.h_gain.release();
     for (hipEvent_t e : {s.uploaded, s.raw_free, s.res_done})
       if (e) (void)hipEventDestroy(e);
   }
@@ -710,6 +712,10 @@ struct RefsRun {
   const RefsPlan* pl;
   peaq_result* results;
   peaq_delay* delays;
+  int gain_mode = PEAQ_GAIN_OFF;                     // peaq_batch_run_host_matched: the stage between estimate and cut
+  double max_gain_db = 40.;
+  peaq_gain* gains = nullptr;
+  bool match() const { return (gain_mode & 0xF) != PEAQ_GAIN_OFF; }
 
   size_t first(size_t k) const { return pl->starts[k]; }
   size_t count(size_t k) const { return pl->starts[k + 1] - pl->starts[k]; }
@@ -813,35 +819,51 @@ struct RefsRun {
     if (int rc = peaq_batch_gather(c, f.channels, (int)nu, (int)np, cur_u, ustride, src.data(), none.data(), m[0].data(), cur[0],
                                    stride, cs))
       return rc;
-    if (f.align_max_lag) {
-      if (np * sizeof(peaq_delay) > st->d_del.cap) HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(st->d_del.reserve(np * sizeof(peaq_delay)));
-      HIP_TRY(s.h_del.reserve(np * sizeof(peaq_delay)));
-      if (int rc = peaq_batch_estimate_delay(c, f.channels, (int)np, cur[0], cur[1], stride, m[0].data(), m[1].data(), 0,
-                                             f.align_max_lag, st->d_del.as<peaq_delay>(), cs))
-        return rc;
-      HIP_TRY(hipMemcpyAsync(s.h_del.p, st->d_del.p, np * sizeof(peaq_delay), hipMemcpyDeviceToHost, cs));
-      HIP_TRY(hipEventRecord(st->del_done, cs));
-      HIP_TRY(hipEventSynchronize(st->del_done));    // the cut needs the lags on the host
+    if (f.align_max_lag || match()) {
       std::vector<uint32_t> skip[2], common(np);
-      skip[0].resize(np);
-      skip[1].resize(np);
+      skip[0].assign(np, 0);
+      skip[1].assign(np, 0);
       uint32_t longest = 0;
+      if (f.align_max_lag) {
+        if (np * sizeof(peaq_delay) > st->d_del.cap) HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(st->d_del.reserve(np * sizeof(peaq_delay)));
+        HIP_TRY(s.h_del.reserve(np * sizeof(peaq_delay)));
+        if (int rc = peaq_batch_estimate_delay(c, f.channels, (int)np, cur[0], cur[1], stride, m[0].data(), m[1].data(), 0,
+                                               f.align_max_lag, st->d_del.as<peaq_delay>(), cs))
+          return rc;
+        HIP_TRY(hipMemcpyAsync(s.h_del.p, st->d_del.p, np * sizeof(peaq_delay), hipMemcpyDeviceToHost, cs));
+        HIP_TRY(hipEventRecord(st->del_done, cs));
+        HIP_TRY(hipEventSynchronize(st->del_done));    // the cut needs the lags on the host
+      }
       for (size_t q = 0; q < np; ++q) {
-        const peaq_delay& rec = s.h_del.as<peaq_delay>()[q];
-        if (delays) delays[p0 + q] = rec;
-        peaq_aligned_lengths(rec.lag, m[0][q], m[1][q], &skip[0][q], &skip[1][q], &common[q]);
+        int32_t lag = 0;
+        if (f.align_max_lag) {
+          const peaq_delay& rec = s.h_del.as<peaq_delay>()[q];
+          if (delays) delays[p0 + q] = rec;
+          lag = rec.lag;
+        }
+        peaq_aligned_lengths(lag, m[0][q], m[1][q], &skip[0][q], &skip[1][q], &common[q]);
         longest = std::max(longest, common[q]);
       }
       const size_t sc = even_stride(longest);
       for (DevBuf& d : st->f_cut)
         if (int rc = reserve_dev(d, np * sc * C * sizeof(float))) return rc;
+      if (match()) {                                   // over the common part of the uncut buffers; the records stay on the device
+        if (int rc = reserve_dev(st->d_gain, np * sizeof(peaq_gain))) return rc;
+        HIP_TRY(s.h_gain.reserve(np * sizeof(peaq_gain)));
+        if (int rc = peaq_batch_measure_gain(c, f.channels, (int)np, cur[0], stride, skip[0].data(), cur[1], stride,
+                                             skip[1].data(), common.data(), gain_mode, max_gain_db, st->d_gain.as<peaq_gain>(), cs))
+          return rc;
+        HIP_TRY(hipMemcpyAsync(s.h_gain.p, st->d_gain.p, np * sizeof(peaq_gain), hipMemcpyDeviceToHost, cs));
+      }
       // the reference's cut: again from the distinct rows, each test's own skip
       if (int rc = peaq_batch_gather(c, f.channels, (int)nu, (int)np, cur_u, ustride, src.data(), skip[0].data(), common.data(),
                                      st->f_cut[0].as<float>(), sc, cs))
         return rc;
-      if (int rc = peaq_batch_cut(c, f.channels, (int)np, cur[1], stride, skip[1].data(), common.data(), st->f_cut[1].as<float>(),
-                                  sc, cs))
+      if (int rc = match() ? peaq_batch_cut_scaled(c, f.channels, (int)np, cur[1], stride, skip[1].data(), common.data(),
+                                                   st->d_gain.as<peaq_gain>(), st->f_cut[1].as<float>(), sc, cs)
+                           : peaq_batch_cut(c, f.channels, (int)np, cur[1], stride, skip[1].data(), common.data(),
+                                            st->f_cut[1].as<float>(), sc, cs))
         return rc;
       for (int i = 0; i < 2; ++i) {
         cur[i] = st->f_cut[i].as<float>();
@@ -864,6 +886,7 @@ struct RefsRun {
     FeedSet& s = st->set[k & 1];
     HIP_TRY(hipEventSynchronize(s.res_done));
     std::memcpy(results + first(k), s.h_res.p, count(k) * sizeof(peaq_result));
+    if (match() && gains) std::memcpy(gains + first(k), s.h_gain.p, count(k) * sizeof(peaq_gain));   // (copied before the results)
     return PEAQ_OK;
   }
 
@@ -907,10 +930,10 @@ extern "C" size_t peaq_feed_refs_workspace_bytes(const peaq_feed* feed, int adva
   return b;
 }
 
-extern "C" int peaq_batch_run_host_refs(peaq_ctx* c, int advanced, double level_db, const peaq_feed* feed, size_t n_refs,
-                                        const peaq_host_signal* refs, size_t n_tests, const peaq_host_test* tests,
-                                        peaq_result* results, peaq_delay* delays) {
-  const char* who = "peaq_batch_run_host_refs";
+// peaq_batch_run_host_refs and, with a gain mode, peaq_batch_run_host_matched
+static int run_host_refs(const char* who, peaq_ctx* c, int advanced, double level_db, const peaq_feed* feed, int gain_mode,
+                         double max_gain_db, size_t n_refs, const peaq_host_signal* refs, size_t n_tests,
+                         const peaq_host_test* tests, peaq_result* results, peaq_delay* delays, peaq_gain* gains) {
   const std::string w(who);
   if (int rc = check_feed(who, feed)) return rc;
   if (int rc = check_level(w, level_db)) return rc;
@@ -945,6 +968,7 @@ extern "C" int peaq_batch_run_host_refs(peaq_ctx* c, int advanced, double level_
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (n_tests == 0) return PEAQ_OK;
   if (delays && !feed->align_max_lag) std::memset(delays, 0, n_tests * sizeof(peaq_delay));
+  if (gains) std::memset(gains, 0, n_tests * sizeof(peaq_gain));
 
   FeedState* st;
   {
@@ -961,11 +985,49 @@ extern "C" int peaq_batch_run_host_refs(peaq_ctx* c, int advanced, double level_
     for (hipEvent_t* e : {&s.uploaded, &s.raw_free, &s.res_done})
       if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
   RefsPlan plan;
-  plan_ref_chunks(*feed, n_refs, refs, n_tests, tests, r48, t48, &plan);
+  peaq_feed budget = *feed;                          // the cut buffers count as with alignment (feed_pair_bytes)
+  if ((gain_mode & 0xF) != PEAQ_GAIN_OFF && !budget.align_max_lag) budget.align_max_lag = 1;
+  plan_ref_chunks(budget, n_refs, refs, n_tests, tests, r48, t48, &plan);
   RefsRun run{c, st, *feed, advanced ? 1 : 0, threads, level_db, refs, tests, &r48, &t48, &plan, results, delays};
+  run.gain_mode = gain_mode;
+  run.max_gain_db = max_gain_db;
+  run.gains = gains;
   const int rc = run.run();
   const std::string msg = rc != PEAQ_OK ? peaq_err_string() : std::string();
   if (rc != PEAQ_OK) (void)hipDeviceSynchronize();    // stop: nothing more is started, what runs drains before the buffers are reused
   for (FeedSet& s : st->set) s.upload_pending = s.raw_pending = false;
   return rc != PEAQ_OK ? fail(rc, msg) : PEAQ_OK;
+}
+
+extern "C" int peaq_batch_run_host_refs(peaq_ctx* c, int advanced, double level_db, const peaq_feed* feed, size_t n_refs,
+                                        const peaq_host_signal* refs, size_t n_tests, const peaq_host_test* tests,
+                                        peaq_result* results, peaq_delay* delays) {
+  return run_host_refs("peaq_batch_run_host_refs", c, advanced, level_db, feed, PEAQ_GAIN_OFF, 40., n_refs, refs, n_tests, tests,
+                       results, delays, nullptr);
+}
+
+extern "C" int peaq_batch_run_host_matched(peaq_ctx* c, int advanced, double level_db, const peaq_feed* feed, int mode,
+                                           double max_gain_db, size_t n_refs, const peaq_host_signal* refs, size_t n_tests,
+                                           const peaq_host_test* tests, peaq_result* results, peaq_delay* delays,
+                                           peaq_gain* gains) {
+  if (int rc = check_gain_mode("peaq_batch_run_host_matched", mode, max_gain_db)) return rc;
+  return run_host_refs("peaq_batch_run_host_matched", c, advanced, level_db, feed, mode, max_gain_db, n_refs, refs, n_tests,
+                       tests, results, delays, gains);
+}
+
+extern "C" size_t peaq_feed_matched_workspace_bytes(const peaq_feed* feed, int advanced, int mode, size_t n_refs, size_t n_tests,
+                                                    uint64_t n_max) {
+  if (mode < 0 || (mode & ~(0xF | PEAQ_GAIN_PER_CHANNEL)) || (mode & 0xF) > PEAQ_GAIN_POLARITY) return 0;
+  if ((mode & 0xF) == PEAQ_GAIN_OFF) return peaq_feed_refs_workspace_bytes(feed, advanced, n_refs, n_tests, n_max);
+  if (check_feed("peaq_feed_matched_workspace_bytes", feed) != PEAQ_OK) return 0;
+  const peaq_feed& f = *feed;
+  size_t b = peaq_feed_refs_workspace_bytes(feed, advanced, n_refs, n_tests, n_max);
+  if (!b) return 0;
+  uint64_t n48 = n_max;
+  if (f.rate != 48000) n48 = peaq_resampled_length(n_max, f.rate);
+  size_t chunk = f.chunk_pairs ? f.chunk_pairs : std::max<size_t>(1, PEAQ_FEED_BUDGET_BYTES / feed_test_bytes(f, n_max, n48));
+  chunk = std::min<size_t>(std::min<size_t>(chunk, n_tests), 65535);
+  if (!f.align_max_lag) b += 2 * chunk * even_stride((size_t)n48) * sizeof(float) * f.channels;   // the cut buffers
+  // per test: the record on the device and in both pinned sets; the partials of the largest chunk there can be
+  return b + 3 * chunk * sizeof(peaq_gain) + peaq_gain_workspace_bytes(f.channels, (int)chunk, (uint32_t)n48);
 }

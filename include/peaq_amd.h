@@ -429,7 +429,8 @@ int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playba
  * PEAQ compares frame against frame and takes the two signals as sample-aligned (BS.1387; the reference has no
  * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
  * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only:
- * no fractional delay, no gain matching, no drift, one lag per pair for all channels.
+ * no fractional delay, no drift, one lag per pair for all channels; level and polarity are matched by the stage
+ * further down ("level and polarity matching on the device").
  *
  *   For one pair with n_ref / n_test samples per channel:
  *   r[n] = sum_c (double) ref[n][c], t[n] likewise: the mono sum, no 1 / channels factor.
@@ -614,6 +615,96 @@ int peaq_batch_run_host_refs (peaq_ctx *ctx, int advanced, double playback_level
  * per channel, a chunk taken to name as many distinct references as it can; 0 for a feed it would refuse, no tests or
  * no references. */
 size_t peaq_feed_refs_workspace_bytes (const peaq_feed *feed, int advanced, size_t n_refs, size_t n_tests, uint64_t n_max);
+
+/* ---- level and polarity matching on the device ------------------------------------------------
+ * PEAQ compares loudness patterns, so a test signal that is a few dB quieter than its reference, or inverted, is
+ * scored as degraded.  This stage sits between delay estimation and the cut: peaq_batch_measure_gain measures each
+ * pair's gain over the aligned part of the UNCUT buffers, and peaq_batch_cut_scaled applies it to the test signal
+ * inside the copy the cut makes anyway.  The record stays on the device between the two.  Not done, here or anywhere:
+ * fractional delay, DC offset removal, time-varying or per-band gain; the reference signal is never changed.
+ *
+ *   For pair p and channel c, with the host arrays skip_ref[p], skip_test[p], n[p]:
+ *   r_i = (double) ref[p][skip_ref[p] + i][c], t_i = (double) test[p][skip_test[p] + i][c], i < n[p];
+ *   Srr = sum r_i^2, Stt = sum t_i^2, Srt = sum r_i t_i, in FP64 (the products are exact: 24 x 24 bits).
+ *   Order: a workgroup covers PEAQ_GAIN_CHUNK samples per channel and writes one partial per sum; there a lane adds at
+ *   most 16 terms one after the other, then a fixed tree over the 256 lanes (8 levels); a second kernel adds the
+ *   pair's partials, a lane every 256th in chunk order (at most 4096 for 2^32 - 1 samples), then the same tree.  No
+ *   floating-point atomics, and the order depends on the index within the pair alone, never on an address.  A term
+ *   passes at most 15 + 8 + 4095 + 8 additions, so |S - exact| <= 4126 * 2^-53 * sum |term| < 1e-12 sum |term| for
+ *   every length up to 2^32 - 1.  The record of a pair does not depend on the other pairs of the call or on where its
+ *   buffers lie, and is the same bit for bit run to run.
+ *   The gain g is derived in FP64 by the IEEE quotient and square root on the record's own sums (mode below); without
+ *   PEAQ_GAIN_PER_CHANNEL the sums of channel 0 and 1 are added first (0 first) and both channels get that g.
+ *   A channel that cannot be matched is flagged and keeps gain = 1.0: the pair is scored unmatched and the flags say
+ *   why.  Checked in this order, the first that holds: NONFINITE, SILENT, ZERO, RANGE.  RANGE is evaluated as |g|
+ *   outside [10^(-max_gain_db / 20), 10^(max_gain_db / 20)], the two bounds computed once per call in FP64 (pow);
+ *   a g of 0 or Inf is out of range.  PEAQ_GAIN_OFF measures the sums and the first two flags and leaves g = 1.0. */
+#define PEAQ_GAIN_CHUNK     4096   /* samples per channel per workgroup of the measure kernel */
+#define PEAQ_GAIN_OFF       0
+#define PEAQ_GAIN_LSQ       1   /* g = Srt / Stt: minimises sum (r - g t)^2; negative for an inverted test signal */
+#define PEAQ_GAIN_RMS       2   /* g = +-sqrt (Srr / Stt), the sign of Srt (+ for Srt == 0): equal energy */
+#define PEAQ_GAIN_POLARITY  3   /* g = +-1, the sign of Srt: nothing but the inversion is undone */
+#define PEAQ_GAIN_PER_CHANNEL 0x10   /* or-ed in: each channel its own g; otherwise the sums of channel 0 and 1
+                                        are added (0 first) and both channels get one g */
+#define PEAQ_GAIN_F_SILENT     1   /* Stt == 0 (or n == 0) */
+#define PEAQ_GAIN_F_NONFINITE  2   /* a sum is NaN or Inf */
+#define PEAQ_GAIN_F_ZERO       4   /* LSQ with Srt == 0: g would be 0 */
+#define PEAQ_GAIN_F_RANGE      8   /* |20 log10 |g|| > max_gain_db */
+typedef struct {                   /* 80 bytes */
+  double   gain[2];                /* the factor APPLIED; 1.0 for a flagged channel; [1] = [0] for mono */
+  double   srr[2], stt[2], srt[2]; /* per channel as measured; [1] = 0 for mono */
+  uint32_t flags[2];               /* per channel; both alike without PER_CHANNEL */
+  uint32_t n, reserved;
+} peaq_gain;
+size_t peaq_gain_size (void);
+/* d_ref / d_test: interleaved F32 in the batch layout, each with its own stride (samples per channel between pairs).
+ * skip_ref / skip_test / n: host arrays of n_pairs entries (pinned staging slots, copied on `stream`, as
+ * peaq_batch_cut's).  d_out: device array of n_pairs peaq_gain.  Enqueues on `stream` and returns.  The partials
+ * (peaq_gain_workspace_bytes) live in the context and are reused; a call on another stream waits, on the device, for
+ * the previous call's kernels.  max_gain_db: 0 < x <= 120 (checked for every mode).
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: an unknown mode or flag
+ * bit, max_gain_db out of range or NaN, channels other than 1 or 2, more than 65535 pairs, NULL buffers or arrays, a
+ * pair whose skip + n passes its stride. */
+int peaq_batch_measure_gain (peaq_ctx *ctx, int channels, int n_pairs,
+                             const float *d_ref, size_t ref_stride, const uint32_t *skip_ref /* host */,
+                             const float *d_test, size_t test_stride, const uint32_t *skip_test /* host */,
+                             const uint32_t *n /* host */, int mode, double max_gain_db,
+                             peaq_gain *d_out /* device, [n_pairs] */, void *stream);
+/* Partials of peaq_batch_measure_gain for a shape, in bytes: 48 per chunk and pair.  Pairs are taken in groups, so
+ * it stops growing with n_pairs at 256 MiB (or one pair's partials, if those are more).  0 for no pairs. */
+size_t peaq_gain_workspace_bytes (int channels, int n_pairs, uint32_t n_max);
+/* peaq_batch_cut with a factor per pair and channel, read from the device records:
+ * out[p][i][c] = (float) ((double) in[p][skip[p] + i][c] * d_gain[p].gain[c]), rounded once (mono: gain[0]).  Where
+ * the factor is exactly 1.0 the bits are moved as they are, NaN payloads included: a pair left unmatched is bit for
+ * bit peaq_batch_cut's output.  Samples of d_out past n_keep[p] are left as they were.  Refusals as peaq_batch_cut's,
+ * and a NULL d_gain. */
+int peaq_batch_cut_scaled (peaq_ctx *ctx, int channels, int n_pairs,
+                           const float *d_in, size_t in_stride, const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                           const peaq_gain *d_gain /* device, [n_pairs] */, float *d_out, size_t out_stride, void *stream);
+/* peaq_run_pair_aligned with the stage in it: upload, conversion to 48 kHz if rate != 48000, estimate if max_lag != 0
+ * (0: no alignment, skips 0 and n = min (n_ref, n_test); delay is zeroed), peaq_batch_measure_gain over the common
+ * part, cut of the reference, peaq_batch_cut_scaled of the test signal, the one-pair path.  gain (host, may be NULL)
+ * receives the record.  mode PEAQ_GAIN_OFF scores what peaq_run_pair_aligned scores. */
+int peaq_run_pair_matched (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                           uint32_t max_lag, int mode, double max_gain_db,
+                           const float *ref, size_t n_ref, const float *test, size_t n_test,
+                           peaq_delay *delay /* host */, peaq_gain *gain /* host */, peaq_result *out);
+/* peaq_batch_run_host_refs with the stage in it (plain pairs: one test per reference).  peaq_feed keeps its size, so
+ * the two values are arguments.  results[t] is bit for bit what this sequence writes, whatever the chunking and order:
+ * decode; convert if rate != 48000; gather; if align_max_lag, estimate and peaq_aligned_lengths (otherwise skips 0 and
+ * n = min (n_ref, n_test)); peaq_batch_measure_gain over the common part; the reference's cut (a gather with each
+ * test's skip); peaq_batch_cut_scaled of the test; peaq_batch_run.  gains (host, may be NULL): the records.  With
+ * mode PEAQ_GAIN_OFF it is peaq_batch_run_host_refs itself (gains zeroed).  Refuses what that refuses, an unknown
+ * mode and a max_gain_db out of range. */
+int peaq_batch_run_host_matched (peaq_ctx *ctx, int advanced, double playback_level_db, const peaq_feed *feed,
+                                 int mode, double max_gain_db,
+                                 size_t n_refs, const peaq_host_signal *refs, size_t n_tests, const peaq_host_test *tests,
+                                 peaq_result *results /* host, [n_tests] */, peaq_delay *delays /* host, may be NULL */,
+                                 peaq_gain *gains /* host, may be NULL */);
+/* peaq_feed_refs_workspace_bytes for peaq_batch_run_host_matched: with a mode other than PEAQ_GAIN_OFF the cut buffers
+ * (also without alignment), the records and the partials are counted. */
+size_t peaq_feed_matched_workspace_bytes (const peaq_feed *feed, int advanced, int mode, size_t n_refs, size_t n_tests,
+                                          uint64_t n_max);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
