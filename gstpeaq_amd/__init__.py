@@ -14,6 +14,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    gather, run_host_refs, feed_refs_workspace_bytes, HostSignal, HostTest,
                    Gain, measure_gain, cut_scaled, gain_workspace_bytes, gain_records, gain_mode, GAIN_DTYPE, GAIN_MODES,
                    GAIN_PER_CHANNEL, GAIN_F_SILENT, GAIN_F_NONFINITE, GAIN_F_ZERO, GAIN_F_RANGE,
+                   SubDelay, refine_delay, cut_shifted, subsample_tables, subdelay_workspace_bytes, SUBDELAY_DTYPE, SUB_STEPS,
+                   SUB_LAGS, SUB_HALF, SUB_F_NONE, SUB_F_EDGE,
                    PCM_FORMATS, PCM_DTYPES,
                    batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
@@ -28,4 +30,6 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "TRACE_ABOVE", "TRACE_MOD_OPEN", "TRACE_LOUD_OPEN", "TRACE_FLUSH",
            "Gain", "measure_gain", "cut_scaled", "gain_workspace_bytes", "gain_records", "gain_mode", "GAIN_DTYPE", "GAIN_MODES",
            "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
+           "SubDelay", "refine_delay", "cut_shifted", "subsample_tables", "subdelay_workspace_bytes", "SUBDELAY_DTYPE", "SUB_STEPS",
+           "SUB_LAGS", "SUB_HALF", "SUB_F_NONE", "SUB_F_EDGE",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

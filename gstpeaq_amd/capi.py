@@ -56,6 +56,19 @@ GAIN_DTYPE = np.dtype([("gain", "<f8", (2,)), ("srr", "<f8", (2,)), ("stt", "<f8
                        ("flags", "<u4", (2,)), ("n", "<u4"), ("reserved", "<u4")])
 
 
+class SubDelay(C.Structure):
+    """mirrors peaq_subdelay (include/peaq_amd.h)"""
+    _fields_ = [("lag", C.c_int32), ("q", C.c_int32), ("frac", C.c_double), ("peak", C.c_double), ("c0", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# PEAQ_SUB_* (include/peaq_amd.h) and the record as a numpy structured dtype
+SUB_STEPS, SUB_LAGS, SUB_HALF = 256, 16, 32
+SUB_F_NONE, SUB_F_EDGE = 1, 2
+SUBDELAY_DTYPE = np.dtype([("lag", "<i4"), ("q", "<i4"), ("frac", "<f8"), ("peak", "<f8"), ("c0", "<f8"), ("flags", "<u4"),
+                           ("reserved", "<u4")])
+
+
 class FrameTrace(C.Structure):
     """mirrors peaq_frame_trace (include/peaq_amd.h)"""
     _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
@@ -254,6 +267,18 @@ def load_library():
                                                   C.POINTER(Gain)]
         L.peaq_feed_matched_workspace_bytes.restype = C.c_size_t
         L.peaq_feed_matched_workspace_bytes.argtypes = [C.POINTER(Feed), C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint64]
+    if hasattr(L, "peaq_batch_refine_delay"):        # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        i32p = C.POINTER(C.c_int32)
+        L.peaq_subdelay_size.restype = C.c_size_t
+        L.peaq_subdelay_size.argtypes = []
+        L.peaq_subsample_tables.argtypes = [dp, dp]
+        L.peaq_batch_refine_delay.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32, i32p, vp, vp]
+        L.peaq_subdelay_workspace_bytes.restype = C.c_size_t
+        L.peaq_subdelay_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32]
+        L.peaq_batch_cut_shifted.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, i32p, vp, C.c_size_t, vp]
+        L.peaq_run_pair_subsample.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_double, fp,
+                                              C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(SubDelay),
+                                              C.POINTER(Gain), dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -754,10 +779,100 @@ def cut_scaled(ctx, x, skip, n_keep, gain, out=None, stream=None):
     return out
 
 
-def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
+def subsample_tables():
+    """(corr [256, 33], shift [256, 65]): the two tables of the sub-sample stage exactly as uploaded
+    (peaq_subsample_tables, host arithmetic, no GPU); row q + 128, column k + 16 / o + 32"""
+    corr, shift = np.zeros((SUB_STEPS, 2 * SUB_LAGS + 1)), np.zeros((SUB_STEPS, 2 * SUB_HALF + 1))
+    dp = C.POINTER(C.c_double)
+    _check(load_library().peaq_subsample_tables(corr.ctypes.data_as(dp), shift.ctypes.data_as(dp)))
+    return corr, shift
+
+
+def subdelay_workspace_bytes(channels, n_pairs, n_max):
+    """partial sums of refine_delay for a shape (peaq_subdelay_workspace_bytes)"""
+    return int(load_library().peaq_subdelay_workspace_bytes(int(channels), int(n_pairs), int(n_max)))
+
+
+def _sync_stream(stream, device):
+    import torch
+    if stream is None:
+        torch.cuda.current_stream(device).synchronize()
+    elif hasattr(stream, "synchronize"):
+        stream.synchronize()
+    else:
+        torch.cuda.ExternalStream(int(stream)).synchronize()
+
+
+def refine_delay(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None):
+    """The sub-sample part of every pair's delay around its integer lag (peaq_batch_refine_delay): ref/test CUDA float32
+    [n_pairs, n_samples, channels], lags as estimate_delay's, n_ref/n_test optional per-pair lengths.  Returns a dict of
+    numpy arrays [n_pairs]: lag, q (int32, grid point of 1/256 sample), frac (q / 256), peak, c0, flags (SUB_F_*).  The
+    total delay is lag + frac; positive: the test signal is late.  Synchronises the stream it ran on."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    a_lag = np.ascontiguousarray(lags, dtype=np.int32)
+    assert a_lag.shape == (n_pairs,)
+    assert ctx.L.peaq_subdelay_size() == C.sizeof(SubDelay) == SUBDELAY_DTYPE.itemsize
+    with _torch_stream(stream):
+        rec = torch.zeros((max(n_pairs, 1), C.sizeof(SubDelay)), dtype=torch.uint8, device=ref.device)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_refine_delay(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()),
+                                         stride, a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                         a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                         a_lag.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(rec.data_ptr()),
+                                         _stream_ptr(stream)))
+    _sync_stream(stream, ref.device)
+    rows = rec.cpu().numpy()[:n_pairs].copy().view(SUBDELAY_DTYPE)[:, 0]
+    return {k: np.ascontiguousarray(rows[k]) for k in ("lag", "q", "frac", "peak", "c0", "flags")}
+
+
+def cut_shifted(ctx, x, skip, n_keep, q, n_in=None, out=None, stream=None):
+    """cut through the fractional-delay filter of every pair's grid point q[p] (peaq_batch_cut_shifted):
+    out[p, i, c] = float32(sum_o shift_tab[q[p]][o] float64(x[p, skip[p] + i + o, c])), o = -32 .. 32; samples outside
+    [0, n_in[p]) (without n_in: the buffer) contribute nothing; q[p] == 0 moves the bits.  out as for cut.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    a_q = np.ascontiguousarray(q, dtype=np.int32)
+    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_q.shape == (n_pairs,) and a_in.shape == (n_pairs,)
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_cut_shifted(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
+                                        a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p),
+                                        a_q.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out.data_ptr()), out.shape[1],
+                                        _stream_ptr(stream)))
+    return out
+
+
+def _need_align(subsample, align):
+    if subsample and align is None:
+        raise PeaqError("subsample=True requires align= (a max_lag): the sub-sample estimate refines an integer lag")
+
+
+def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
+          subsample=False):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
     gain: 'lsq' 'rms' 'polarity': the test signal's gain is measured over that part and applied in its cut
     (measure_gain, cut_scaled); the record tensor is kept as align.last_gain.
+    subsample: the sub-sample part of each pair's delay is estimated around its lag (refine_delay, records kept as
+    align.last_subdelay) and the test signal is cut through the shift filter (cut_shifted); a gain is then measured on
+    the two CUT buffers and applied into a further buffer.
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
     n_pairs, stride, _ = ref.shape
     assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
@@ -769,8 +884,20 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None,
     o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
     with _torch_stream(stream):
         bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
-                for _ in (0, 1)]
-    if gain is None:
+                for _ in range(3 if subsample and gain is not None else 2)]
+    n = np.ascontiguousarray(cuts[:, 2])
+    if subsample:
+        sub = refine_delay(ctx, ref, test, lags, n_ref, n_test, stream=stream)
+        align.last_subdelay = sub
+        cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
+        cut_shifted(ctx, test, cuts[:, 1], n, sub["q"], n_in=a_test, out=bufs[1], stream=stream)
+        if gain is not None:
+            rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
+                                  per_channel=gain_per_channel, stream=stream)
+            cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
+            align.last_gain = rec
+            return bufs[0], bufs[2], n, n.copy()
+    elif gain is None:
         cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
         cut(ctx, test, cuts[:, 1], cuts[:, 2], out=bufs[1], stream=stream)
     else:
@@ -779,17 +906,21 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None,
         cut(ctx, ref, cuts[:, 0], cuts[:, 2], out=bufs[0], stream=stream)
         cut_scaled(ctx, test, cuts[:, 1], cuts[:, 2], rec, out=bufs[1], stream=stream)
         align.last_gain = rec
-    n = np.ascontiguousarray(cuts[:, 2])
     return bufs[0], bufs[1], n, n.copy()
 
 
-def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0):
-    """the `align=` and `gain=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without align: lags of
-    0), then match and cut"""
+def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
+             subsample=False):
+    """the `align=`, `gain=` and `subsample=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without
+    align: lags of 0), then refine, match and cut"""
+    _need_align(subsample, max_lag)
     if max_lag is not None:
         lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
     else:
         lags = np.zeros(ref.shape[0], dtype=np.int32)
+    if subsample:
+        return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
+                     max_gain_db=max_gain_db, subsample=True)
     if gain is None:
         return align(ctx, ref, test, lags, n_ref, n_test, stream=stream)
     return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
@@ -797,8 +928,11 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
 
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
-              stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
+              stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
+              subsample=False):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    subsample: with align, the sub-sample part of every pair's delay is estimated and removed from the test signal too
+    (refine_delay, cut_shifted; align.last_subdelay); a gain is then measured after the shift.
     gain: 'lsq' 'rms' 'polarity': the test signal's level (polarity) is matched to the reference's over the common part,
     after the alignment if there is one (measure_gain, cut_scaled); gain_per_channel, max_gain_db as measure_gain's.
     n_ref/n_test: optional per-pair lengths (samples per channel).
@@ -809,7 +943,11 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if gain is not None:
+    _need_align(subsample, align)
+    if subsample:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            subsample=True)
+    elif gain is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
     elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
@@ -836,7 +974,8 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
 
 
 def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n_test=None, playback_level=92.0,
-                     stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
+                     stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
+                     subsample=False):
     """Readings every `interval` samples per channel through each pair (peaq_batch_run_trajectory): point k of pair p
     is what a session pushed the first min((k + 1) interval, n) samples of each signal reads, unflushed.
     ref/test, rate and align as for batch_run; `interval` counts samples at 48 kHz whatever the rate.  Returns
@@ -845,7 +984,11 @@ def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if gain is not None:
+    _need_align(subsample, align)
+    if subsample:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            subsample=True)
+    elif gain is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
     elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
@@ -916,7 +1059,8 @@ def frame_count(n_ref, n_test, filter_bank=False):
 
 
 def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
-                stream=None, sync=True, d_frames=None, d_blocks=None, gain=None, gain_per_channel=False, max_gain_db=40.0):
+                stream=None, sync=True, d_frames=None, d_blocks=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
+                subsample=False):
     """The MOV layer's values of every frame and block of every pair, in the run that scores them
     (peaq_batch_run_trace).  ref/test, n_ref/n_test, rate and align as for batch_run.  d_frames / d_blocks: optional
     record tensors to write into (CUDA uint8 [n_pairs, stride, 128] / [.., 96]; records past a pair's count keep what
@@ -929,7 +1073,11 @@ def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_leve
     _check_trace_sizes(ctx.L)
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if gain is not None:
+    _need_align(subsample, align)
+    if subsample:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            subsample=True)
+    elif gain is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
     elif align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
@@ -1009,8 +1157,12 @@ def _gain_dict(rec):
     return dict(gain=list(rec.gain), srr=list(rec.srr), stt=list(rec.stt), srt=list(rec.srt), flags=list(rec.flags), n=int(rec.n))
 
 
+def _subdelay_dict(rec):
+    return dict(lag=int(rec.lag), q=int(rec.q), frac=rec.frac, peak=rec.peak, c0=rec.c0, flags=int(rec.flags))
+
+
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
-             max_gain_db=40.0):
+             max_gain_db=40.0, subsample=False):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
     the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`."""
@@ -1019,6 +1171,20 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
+    _need_align(subsample, align)
+    if subsample:                                      # peaq_run_pair_subsample; the records as `delay`, `subdelay`, `gain`
+        rec, srec, grec = Delay(), SubDelay(), Gain()
+        _check(ctx.L.peaq_run_pair_subsample(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
+                                             gain_mode(gain, gain_per_channel), float(max_gain_db),
+                                             ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                             test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
+                                             C.byref(srec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["subdelay"] = _subdelay_dict(srec)
+        if gain is not None:
+            res["gain"] = _gain_dict(grec)
+        return res
     if gain is not None:                               # peaq_run_pair_matched; the result dict carries the record as `gain`
         rec, grec = Delay(), Gain()
         _check(ctx.L.peaq_run_pair_matched(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),

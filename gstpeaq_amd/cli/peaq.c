@@ -543,6 +543,9 @@ usage (const char *prog)
       "  --interval=S  also print ODG and DI read every S seconds through the files\n"
       "  --align[=SAMPLES] find the test file's delay within +-SAMPLES (48 kHz samples, 1..16384, default 4096)\n"
       "                on the GPU and compare the aligned parts (the plain one-call mode only)\n"
+      "  --align-subsample[=SAMPLES] --align, and the sub-sample part of the delay too: estimated on a grid of 1/256\n"
+      "                sample and removed from the test signal by a 65-tap shift filter; prints the fraction beside\n"
+      "                the lag; --match-gain then measures after the shift (the plain one-call mode; not with --list)\n"
       "  --match-gain[=lsq|rms|polarity] match the test file's level (polarity) to the reference's on the GPU, after\n"
       "                --align if given, and print the gain applied (default lsq; the plain one-call mode and --list;\n"
       "                not with --interval or --trace)\n"
@@ -632,6 +635,8 @@ main (int argc, char **argv)
   int advanced = 0, i, nfiles = 0, rc, allow_resample = 1, device_resample = 0;
   uint32_t device_rate = 0;     /* != 0: both files stay at this rate, peaq_run_pair_rate converts them */
   uint32_t align_lag = 0;       /* != 0: --align, peaq_run_pair_aligned */
+  int subsample = 0;            /* --align-subsample: peaq_run_pair_subsample (implies --align) */
+  peaq_subdelay subdelay;
   peaq_delay delay;
   peaq_gain gain;
   int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
@@ -666,6 +671,20 @@ main (int argc, char **argv)
         fprintf (stderr, "Failed to initialize: invalid alignment range %s (1 .. 16384 samples)\n", argv[i] + 8);
         return 1;
       }
+      align_lag = (uint32_t) v;
+    }
+    else if (!strcmp (argv[i], "--align-subsample")) {
+      subsample = 1;
+      if (!align_lag)
+        align_lag = 4096;
+    } else if (!strncmp (argv[i], "--align-subsample=", 18)) {
+      char *end;
+      const long v = strtol (argv[i] + 18, &end, 10);
+      if (*end || end == argv[i] + 18 || v < 1 || v > 16384) {
+        fprintf (stderr, "Failed to initialize: invalid alignment range %s (1 .. 16384 samples)\n", argv[i] + 18);
+        return 1;
+      }
+      subsample = 1;
       align_lag = (uint32_t) v;
     }
     else if (!strcmp (argv[i], "--match-gain") || !strcmp (argv[i], "--match-gain=lsq"))
@@ -723,6 +742,14 @@ main (int argc, char **argv)
     gain_mode |= PEAQ_GAIN_PER_CHANNEL;
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
+  if (subsample && list_path) {
+    fprintf (stderr, "Failed to initialize: --align-subsample is not taken with --list: the host-fed path does not take it yet (whole-sample --align only)\n");
+    return 1;
+  }
+  if (subsample && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --align-subsample belongs to the plain one-call mode (not with --interval or --trace)\n");
     return 1;
   }
   if (list_path) {
@@ -830,6 +857,20 @@ main (int argc, char **argv)
     if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
+    } else if (subsample) {
+      char text[256];
+      if (peaq_run_pair_subsample (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, gain_mode,
+              max_gain_db, ref.samples, ref.frames, test.samples, test.frames, &delay, &subdelay, &gain, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d %+.4f samples (correlation %.3f%s)\n", (int) delay.lag, subdelay.frac,
+          delay.norm > 0. ? subdelay.peak / delay.norm : 0.,
+          (subdelay.flags & PEAQ_SUB_F_NONE) ? ", no sub-sample estimate" : (subdelay.flags & PEAQ_SUB_F_EDGE) ? ", at the edge of the interval" : "");
+      if (gain_mode) {
+        format_gain (text, sizeof text, &gain, ref.channels);
+        printf ("Gain: %s\n", text);
+      }
     } else if (gain_mode) {
       char text[256];
       if (peaq_run_pair_matched (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, gain_mode,

@@ -11,6 +11,7 @@
 //                     peaq_batch_run_host_refs)
 //   peaq_gather.hip   copy by source index, what shares one uploaded reference among its tests (kernel and host side)
 //   peaq_gain.hip     level and polarity matching between delay estimation and the cut (kernels and host side)
+//   peaq_frac.hip     sub-sample delay estimate and fractional-delay cut behind the integer aligner (kernels and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -166,6 +167,7 @@ struct peaq_ctx {
   struct FeedState* feed = nullptr;       // PCM decoder and host feed: length scratch, staging sets, streams (peaq_pcm.hip)
   struct GatherState* ga = nullptr;       // gather: index and length scratch (peaq_gather.hip)
   struct GainState* gn = nullptr;         // gain matching: partial sums, length scratch (peaq_gain.hip)
+  struct FracState* fr = nullptr;         // sub-sample stage: the two tables, partial sums, length scratch (peaq_frac.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -187,6 +189,8 @@ void feed_release(peaq_ctx* c);
 void gather_release(peaq_ctx* c);
 // the same for peaq_batch_measure_gain / peaq_batch_cut_scaled (peaq_gain.hip)
 void gain_release(peaq_ctx* c);
+// the same for peaq_batch_refine_delay / peaq_batch_cut_shifted (peaq_frac.hip)
+void frac_release(peaq_ctx* c);
 // mode (PEAQ_GAIN_* with or without PEAQ_GAIN_PER_CHANNEL) and max_gain_db as every entry point of the stage takes them
 int check_gain_mode(const std::string& who, int mode, double max_gain_db);
 

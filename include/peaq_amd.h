@@ -428,9 +428,9 @@ int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playba
 /* ---- time alignment on the device ------------------------------------------------
  * PEAQ compares frame against frame and takes the two signals as sample-aligned (BS.1387; the reference has no
  * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
- * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only:
- * no fractional delay, no drift, one lag per pair for all channels; level and polarity are matched by the stage
- * further down ("level and polarity matching on the device").
+ * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only
+ * here (the constant sub-sample part: "sub-sample delay on the device" further down), no drift, one lag per pair for
+ * all channels; level and polarity are matched by the stage further down ("level and polarity matching on the device").
  *
  *   For one pair with n_ref / n_test samples per channel:
  *   r[n] = sum_c (double) ref[n][c], t[n] likewise: the mono sum, no 1 / channels factor.
@@ -621,7 +621,8 @@ size_t peaq_feed_refs_workspace_bytes (const peaq_feed *feed, int advanced, size
  * scored as degraded.  This stage sits between delay estimation and the cut: peaq_batch_measure_gain measures each
  * pair's gain over the aligned part of the UNCUT buffers, and peaq_batch_cut_scaled applies it to the test signal
  * inside the copy the cut makes anyway.  The record stays on the device between the two.  Not done, here or anywhere:
- * fractional delay, DC offset removal, time-varying or per-band gain; the reference signal is never changed.
+ * DC offset removal, time-varying or per-band gain (fractional delay: the stage after this one); the reference signal
+ * is never changed.
  *
  *   For pair p and channel c, with the host arrays skip_ref[p], skip_test[p], n[p]:
  *   r_i = (double) ref[p][skip_ref[p] + i][c], t_i = (double) test[p][skip_test[p] + i][c], i < n[p];
@@ -705,6 +706,97 @@ int peaq_batch_run_host_matched (peaq_ctx *ctx, int advanced, double playback_le
  * (also without alignment), the records and the partials are counted. */
 size_t peaq_feed_matched_workspace_bytes (const peaq_feed *feed, int advanced, int mode, size_t n_refs, size_t n_tests,
                                           uint64_t n_max);
+
+/* ---- sub-sample delay on the device ------------------------------------------------
+ * A codec, a resampler or a DA/AD loop rarely delays by a whole number of 48 kHz samples, and the residue the integer
+ * aligner leaves -- up to half a sample -- is scored as coding noise.  This stage sits behind peaq_batch_estimate_delay:
+ * peaq_batch_refine_delay finds the constant sub-sample part of each pair's delay on a grid of 1 / PEAQ_SUB_STEPS
+ * samples around the given integer lag, and peaq_batch_cut_shifted is peaq_batch_cut of the test signal through the
+ * fractional-delay filter of that grid point.  Only the test signal is ever shifted; the reference is never changed.
+ * With lag < 0 the test signal keeps skip = 0 and is still shifted by q.  Not done, here or anywhere: drift and
+ * per-window delay tracks, shifts finer than the grid, and the host-fed pipelines (peaq_batch_run_host*, the CLI's
+ * --list), which align to whole samples only.
+ *
+ *   w_H (x) = I0 (beta sqrt (1 - (x / H)^2)) / I0 (beta) for |x| < H, else 0; beta = 8.49, the converter's Kaiser window.
+ *   sinc (x) = sin (pi x) / (pi x), sinc (0) = 1.  I0 is evaluated in double by the Chebyshev expansions of the Cephes
+ *   library (what numpy.i0 evaluates): a table rebuilt from these formulas with numpy agrees to 1e-15 absolute.
+ *   Two tables, built on the host in double once per process and uploaded once per context (peaq_subsample_tables
+ *   hands out exactly what is uploaded), q in [-128, 127], k in [-16, 16], o in [-32, 32]:
+ *     corr_tab[q + 128][k + 16]  = sinc (q / 256 - k) w_17 (q / 256 - k)
+ *     shift_tab[q + 128][o + 32] = sinc (o - q / 256) w_33 (o - q / 256); row q = 0 is the exact unit impulse by
+ *     construction, not by evaluating sin (pi o).
+ *
+ *   Estimate, per pair, with the integer lag of peaq_batch_estimate_delay (a host array):
+ *   c_k = sum_n r[n] t[n + lag + k], r and t the FP64 mono sums as there, over all n with both indices inside their
+ *   signals, for k in [-16, 16]: direct time-domain sums in a fixed order, built the way the gain stage builds its
+ *   sums.  A workgroup covers 4096 n; there a lane adds at most 16 terms of one k one after the other (each term one
+ *   fused multiply-add), then a fixed tree over the 256 lanes; a second kernel adds the pair's partials, a lane every
+ *   256th in chunk order, then the same tree.  No floating-point atomics; the order depends on the index within the
+ *   pair alone.  |c_k - exact| < 1e-12 sum |term| for every length up to 2^32 - 1 (the gain stage's count of additions).
+ *   s = the sign of c_0 (+ for 0); v (q) = s sum_k c_k corr_tab[q][k], summed in the order k = -16 .. 16 in FP64, every
+ *   product and every sum rounded on its own; q = the grid point with the largest v, values within 1e-12 max_k |c_k| of
+ *   the largest counting as tied, ties to the smaller |q|, then to the positive one.  The total delay is lag + q / 256;
+ *   positive still means that the test signal is late.
+ *   The record of a pair does not depend on the other pairs of the call or on where its buffers lie, and is the same
+ *   bit for bit run to run. */
+#define PEAQ_SUB_STEPS   256   /* grid steps per sample */
+#define PEAQ_SUB_LAGS    16    /* R: integer lags on each side of the given one */
+#define PEAQ_SUB_HALF    32    /* K: the shift filter has 2 K + 1 = 65 taps */
+#define PEAQ_SUB_F_NONE  1     /* no estimate: every c_k is 0, the overlap is empty (|lag| reaches a signal's length), or a
+                                  sum is not finite; q = 0 and peak = 0 */
+#define PEAQ_SUB_F_EDGE  2     /* q is -128 or 127: the maximum is not inside the interval, the integer lag is
+                                  probably off by one */
+typedef struct {               /* 40 bytes */
+  int32_t  lag;                /* as given */
+  int32_t  q;                  /* grid point, -128 .. 127 */
+  double   frac;               /* q / 256 */
+  double   peak;               /* v (q) s: the interpolated correlation at lag + frac, signed */
+  double   c0;                 /* c_0 */
+  uint32_t flags;
+  uint32_t reserved;
+} peaq_subdelay;
+size_t peaq_subdelay_size (void);
+/* corr: [256][33] doubles, shift: [256][65] doubles, the two tables exactly as uploaded; either may be NULL (both:
+ * PEAQ_ERR_ARG).  Host only, no device. */
+int peaq_subsample_tables (double *corr, double *shift);
+/* Batch layout and lengths as for peaq_batch_estimate_delay (n_ref / n_test: host arrays, both or neither; NULL =
+ * n_uniform); lag: host array of n_pairs entries.  All per-pair arrays travel through pinned staging slots, copied on
+ * `stream`, as peaq_batch_cut's.  d_out: device array of n_pairs peaq_subdelay.  Enqueues on `stream` and returns,
+ * synchronising nothing (a context's FIRST call of this stage copies the two tables to its device, blocking, once).
+ * The partials (peaq_subdelay_workspace_bytes) live in the context and are reused; a call on another stream waits, on
+ * the device, for the previous call's kernels.  A lag whose magnitude reaches either signal's length is no error: the
+ * pair gets PEAQ_SUB_F_NONE.
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: channels other than 1 or
+ * 2, more than 65535 pairs, NULL buffers, a NULL lag, n_ref without n_test, a pair longer than pair_stride. */
+int peaq_batch_refine_delay (peaq_ctx *ctx, int channels, int n_pairs,
+                             const float *d_ref, const float *d_test, size_t pair_stride,
+                             const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                             const int32_t *lag /* host */, peaq_subdelay *d_out /* device, [n_pairs] */, void *stream);
+/* Partials and sums of peaq_batch_refine_delay for a shape, in bytes: 264 per chunk of 4096 reference samples and
+ * pair, and 264 more per pair.  Pairs are taken in groups, so it stops growing with n_pairs at 256 MiB (or one pair's
+ * row, if that is more).  0 for no pairs. */
+size_t peaq_subdelay_workspace_bytes (int channels, int n_pairs, uint32_t n_max);
+/* peaq_batch_cut through the shift filter of each pair's grid point q[p] (host array):
+ * out[p][i][c] = (float) sum_{o = -32 .. 32} shift_tab[q[p]][o] (double) in[p][skip[p] + i + o][c] for i < n_keep[p]:
+ * fused multiply-adds in the order o = -32 .. 32 in FP64, rounded once to FP32.  A tap whose index falls outside
+ * [0, n_in[p]) contributes nothing.  Samples of d_out past n_keep[p] are left as they were.  A pair with q[p] == 0 has
+ * its bits moved as they are, NaN payloads included: that output is bit for bit peaq_batch_cut's.
+ * Refusals as peaq_batch_cut's (with the offending value in the message), and: a q outside [-128, 127], an n_in beyond
+ * in_stride, a NULL n_in or q. */
+int peaq_batch_cut_shifted (peaq_ctx *ctx, int channels, int n_pairs,
+                            const float *d_in, size_t in_stride, const uint32_t *n_in /* host */,
+                            const uint32_t *skip /* host */, const uint32_t *n_keep /* host */, const int32_t *q /* host */,
+                            float *d_out, size_t out_stride, void *stream);
+/* peaq_run_pair_matched with the stage in it, in this order: upload; conversion to 48 kHz if rate != 48000; estimate
+ * (max_lag at least 1 is required); refine; plain cut of the reference; shifted cut of the test signal; if mode is not
+ * PEAQ_GAIN_OFF, peaq_batch_measure_gain on the two CUT buffers with skips of 0 and peaq_batch_cut_scaled into a second
+ * buffer; the one-pair path.  Measuring the gain after the shift is the point of the order: a residue of tau samples
+ * lowers Srt by sinc (tau), which biases the LSQ gain.  delay, subdelay and gain (host) may be NULL. */
+int peaq_run_pair_subsample (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                             uint32_t max_lag, int mode, double max_gain_db,
+                             const float *ref, size_t n_ref, const float *test, size_t n_test,
+                             peaq_delay *delay /* host */, peaq_subdelay *subdelay /* host */, peaq_gain *gain /* host */,
+                             peaq_result *out);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
