@@ -21,9 +21,10 @@
 //   align_pick_kernel        one workgroup per pair: norm, arg-max with the tie rule, runner-up.
 // Every sum has a fixed order and every reduction across threads is a max or a min, so the record of a pair does
 // not depend on the batch it is in, and is the same run to run.
-//   align_cut_kernel         peaq_batch_cut: a strided copy, 16 bytes per lane where the alignment allows.
+//   align_cut_kernel         peaq_batch_cut: a strided copy, 16 bytes per lane where the alignment allows (copy_run,
+//       peaq_host.h).
+// The file also defines the steps the one-pair conveniences of every stage are built from (peaq_host.h).
 #include "peaq_host.h"
-#include "peaq_wave.h"
 
 namespace {
 
@@ -342,30 +343,13 @@ struct CutArgs {
   int channels;
 };
 
-// floats, not samples: a pair's run is n_keep x channels consecutive floats.  Stores are 16 bytes from the first
-// aligned float of the destination on; loads are 16 bytes too where the source is aligned alike, else four dwords.
+// floats, not samples: a pair's run is n_keep x channels consecutive floats
 __global__ __launch_bounds__(256) void align_cut_kernel(const CutArgs a) {
   const unsigned pair = blockIdx.y;
   const size_t count = (size_t)a.n_keep[pair] * a.channels;
   const float* __restrict__ src = a.in + ((size_t)pair * a.in_stride + a.skip[pair]) * a.channels;
   float* __restrict__ dst = a.out + (size_t)pair * a.out_stride * a.channels;
-  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
-  const size_t vecs = (count - head) / 4;
-  const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < vecs) {
-    const float* s = src + head + 4 * v;
-    float4 x;
-    if (((uintptr_t)s & 15) == 0)
-      x = *reinterpret_cast<const float4*>(s);
-    else
-      x = {s[0], s[1], s[2], s[3]};
-    *reinterpret_cast<float4*>(dst + head + 4 * v) = x;
-  }
-  if (blockIdx.x == 0) {                             // the unaligned head and the tail: at most 3 floats each
-    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
-    const size_t tail0 = head + 4 * vecs;
-    if (tail0 + threadIdx.x < count) dst[tail0 + threadIdx.x] = src[tail0 + threadIdx.x];
-  }
+  copy_run(src, dst, count, (size_t)blockIdx.x * 256, blockIdx.x == 0, CopyBits());
 }
 
 // what one call's shape needs
@@ -393,39 +377,25 @@ AlignPlan align_plan(uint32_t n_max, uint32_t max_lag) {
   return p;
 }
 
-size_t align_scratch_bytes(const AlignPlan& p, int n_pairs) {
-  if (n_pairs <= 0) return 0;
-  return std::min((size_t)n_pairs * p.per_pair, std::max(kAlScratchBudget, p.per_pair));
-}
+}  // namespace
 
-int check_max_lag(const char* who, uint32_t max_lag) {
+int check_max_lag(const std::string& who, uint32_t max_lag) {
   if (max_lag < 1 || max_lag > kAlMaxLag)
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": max_lag " + std::to_string(max_lag) + " is outside 1 .. " +
-                                  std::to_string(kAlMaxLag));
+    return fail(PEAQ_ERR_ARG, who + ": max_lag " + std::to_string(max_lag) + " is outside 1 .. " + std::to_string(kAlMaxLag));
   return PEAQ_OK;
 }
 
-}  // namespace
-
 struct AlignState {
-  DevBuf scratch;
+  StageScratch scratch;
   LenStage lens;                // estimate: [n_ref | n_test]; cut: [skip | n_keep]
-  hipEvent_t scratch_free = nullptr;   // behind the last kernel that used the scratch
-  bool scratch_busy = false;
 };
 
-void align_release(peaq_ctx* c) {
-  if (!c->al) return;
-  c->al->lens.release();
-  if (c->al->scratch_free) (void)hipEventDestroy(c->al->scratch_free);
-  delete c->al;
-  c->al = nullptr;
-}
+void align_release(peaq_ctx* c) { release_stage(c->al); }
 
 extern "C" size_t peaq_align_workspace_bytes(int channels, int n_pairs, uint32_t n_max, uint32_t max_lag) {
   (void)channels;                                    // (the mono sum is taken while loading)
   if (n_pairs <= 0 || max_lag < 1 || max_lag > kAlMaxLag) return 0;
-  return align_scratch_bytes(align_plan(n_max, max_lag), n_pairs);
+  return pair_groups(align_plan(n_max, max_lag).per_pair, n_pairs, kAlScratchBudget).bytes;
 }
 
 extern "C" void peaq_aligned_lengths(int32_t lag, uint32_t n_ref, uint32_t n_test, uint32_t* skip_ref,
@@ -441,31 +411,23 @@ extern "C" int peaq_batch_estimate_delay(peaq_ctx* c, int channels, int n_pairs,
                                          const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                                          const uint32_t* n_test, uint32_t n_uniform, uint32_t max_lag,
                                          peaq_delay* d_out, void* stream_) {
-  const char* who = "peaq_batch_estimate_delay";
+  const std::string who("peaq_batch_estimate_delay");
   // (what needs no context first)
   if (int rc = check_max_lag(who, max_lag)) return rc;
-  if (int rc = check_channels(who, channels)) return rc;
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, std::string(who) + ": n_pairs < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 65535 pairs in one call");
-  if (n_pairs > 0 && (!d_ref || !d_test || !d_out)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL buffer");
-  if (!c) return fail(PEAQ_ERR_ARG, std::string(who) + ": ctx is NULL");
+  if (int rc = check_shape(who, channels, n_pairs)) return rc;
+  if (n_pairs > 0 && (!d_ref || !d_test || !d_out)) return fail(PEAQ_ERR_ARG, who + ": NULL buffer");
+  if (!c) return fail(PEAQ_ERR_ARG, who + ": ctx is NULL");
   if (n_pairs == 0) return PEAQ_OK;
   if ((n_ref == nullptr) != (n_test == nullptr))
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": n_ref and n_test must both be given or both be NULL");
+    return fail(PEAQ_ERR_ARG, who + ": n_ref and n_test must both be given or both be NULL");
+  uint32_t nr_max = 0, nt_max = 0;
+  if (int rc = check_lengths(who, n_pairs, n_ref, n_uniform, "n_ref", pair_stride, "pair_stride", &nr_max)) return rc;
+  if (int rc = check_lengths(who, n_pairs, n_test, n_uniform, "n_test", pair_stride, "pair_stride", &nt_max)) return rc;
+  const uint32_t n_max = std::max(nr_max, nt_max);
   std::vector<uint32_t> h;
-  uint32_t n_max = n_uniform;
   if (n_ref) {
-    h.resize(2 * (size_t)n_pairs);
-    n_max = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-      if (n_ref[p] > pair_stride || n_test[p] > pair_stride)
-        return fail(PEAQ_ERR_ARG, std::string(who) + ": a pair is longer than pair_stride");
-      h[p] = n_ref[p];
-      h[(size_t)n_pairs + p] = n_test[p];
-      n_max = std::max(n_max, std::max(n_ref[p], n_test[p]));
-    }
-  } else if (n_uniform > pair_stride) {
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": n_uniform > pair_stride");
+    h.assign(n_ref, n_ref + n_pairs);
+    h.insert(h.end(), n_test, n_test + n_pairs);
   }
 
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -474,20 +436,14 @@ extern "C" int peaq_batch_estimate_delay(peaq_ctx* c, int channels, int n_pairs,
   if (!c->al) c->al = new AlignState;
   AlignState* st = c->al;
   const AlignPlan pl = align_plan(n_max, max_lag);
-  const size_t bytes = align_scratch_bytes(pl, n_pairs);
-  const int group = (int)std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, bytes / pl.per_pair));
-  if (!st->scratch_free) HIP_TRY(hipEventCreateWithFlags(&st->scratch_free, hipEventDisableTiming));
-  if (bytes > st->scratch.cap && st->scratch_busy) {   // growing frees the old scratch: its last user has to be done
-    HIP_TRY(hipEventSynchronize(st->scratch_free));
-    st->scratch_busy = false;
-  }
-  HIP_TRY(st->scratch.reserve(bytes));
-  if (st->scratch_busy) HIP_TRY(hipStreamWaitEvent(stream, st->scratch_free, 0));   // (a call on another stream)
+  const PairGroups pg = pair_groups(pl.per_pair, n_pairs, kAlScratchBudget);
+  const int group = pg.group;
+  if (int rc = st->scratch.acquire(pg.bytes, stream)) return rc;
   LenSlot* slot = nullptr;
   if (n_ref) {
     if (int rc = st->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
   }
-  char* base = st->scratch.as<char>();
+  char* base = st->scratch.buf.as<char>();
   AlignArgs a{};
   a.stride = pair_stride;
   a.n_uniform = n_uniform;
@@ -525,8 +481,7 @@ extern "C" int peaq_batch_estimate_delay(peaq_ctx* c, int channels, int n_pairs,
     if (launched != hipSuccess) break;
   }
   // (also after a failed launch: what was enqueued before it still reads the slot and the scratch)
-  const hipError_t marked = hipEventRecord(st->scratch_free, stream);
-  st->scratch_busy = marked == hipSuccess;
+  const hipError_t marked = st->scratch.mark(stream);
   const int sent = slot ? st->lens.sent(slot, stream) : PEAQ_OK;
   HIP_TRY(launched);
   HIP_TRY(marked);
@@ -536,34 +491,17 @@ extern "C" int peaq_batch_estimate_delay(peaq_ctx* c, int channels, int n_pairs,
 extern "C" int peaq_batch_cut(peaq_ctx* c, int channels, int n_pairs, const float* d_in, size_t in_stride,
                               const uint32_t* skip, const uint32_t* n_keep, float* d_out, size_t out_stride,
                               void* stream_) {
-  const char* who = "peaq_batch_cut";
-  if (int rc = check_channels(who, channels)) return rc;
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, std::string(who) + ": n_pairs < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 65535 pairs in one call");
-  if (n_pairs > 0 && (!d_in || !d_out)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL buffer");
-  if (n_pairs > 0 && (!skip || !n_keep)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL skip or n_keep");
-  if (!c) return fail(PEAQ_ERR_ARG, std::string(who) + ": ctx is NULL");
-  if (n_pairs == 0) return PEAQ_OK;
-  std::vector<uint32_t> h(2 * (size_t)n_pairs);
+  const std::string who("peaq_batch_cut");
+  if (int rc = check_shape(who, channels, n_pairs)) return rc;
+  if (n_pairs > 0 && (!skip || !n_keep)) return fail(PEAQ_ERR_ARG, who + ": NULL skip or n_keep");
   uint32_t keep_max = 0;
-  for (int p = 0; p < n_pairs; ++p) {
-    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
-      return fail(PEAQ_ERR_ARG, std::string(who) + ": skip + n_keep of a pair passes in_stride");
-    h[p] = skip[p];
-    h[(size_t)n_pairs + p] = n_keep[p];
-    keep_max = std::max(keep_max, n_keep[p]);
-  }
-  if (keep_max > out_stride)
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": out_stride " + std::to_string(out_stride) +
-                                  " is smaller than the longest n_keep (" + std::to_string(keep_max) + " samples)");
-  {
-    const char* i0 = reinterpret_cast<const char*>(d_in);
-    const char* o0 = reinterpret_cast<const char*>(d_out);
-    const size_t ib = (size_t)n_pairs * in_stride * channels * sizeof(float);
-    const size_t ob = (size_t)n_pairs * out_stride * channels * sizeof(float);
-    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, std::string(who) + ": d_out overlaps d_in");
-  }
-  if (keep_max == 0) return PEAQ_OK;
+  if (int rc = check_cut_geometry(who, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
+                                  &keep_max))
+    return rc;
+  if (!c) return fail(PEAQ_ERR_ARG, who + ": ctx is NULL");
+  if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
+  std::vector<uint32_t> h(skip, skip + n_pairs);
+  h.insert(h.end(), n_keep, n_keep + n_pairs);
 
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::lock_guard<std::mutex> lock(c->mu);
@@ -587,148 +525,163 @@ extern "C" int peaq_batch_cut(peaq_ctx* c, int channels, int n_pairs, const floa
   return sent;
 }
 
-// One host pair made ready to score: upload, conversion of both signals to 48 kHz if rate != 48000 and, with max_lag,
-// estimate and cut (peaq_run_pair_aligned, peaq_run_pair_trace) and, with a gain_mode other than PEAQ_GAIN_OFF, the gain
-// measured over the common part and applied in the test signal's cut (peaq_run_pair_matched; without max_lag the
-// skips are 0).  d[0], d[1]: the signals to score, `stride` samples per channel long, len[] their lengths.  The
-// arguments have been checked by the caller.
-struct PreparedPair {
-  DevBuf raw[2], s48[2], cut[2], rec, grec;
+// ---------------------------------------------------------------------------
+// the steps of the one-pair conveniences (peaq_host.h)
+// ---------------------------------------------------------------------------
+int check_pair_args(const std::string& who, const peaq_ctx* c, int channels, uint32_t rate, const float* ref,
+                    size_t n_ref, const float* test, size_t n_test, const void* out, bool need_out) {
+  if (int rc = check_channels(who, channels)) return rc;
+  if (rate != 48000 && !peaq_resample_supported(rate))
+    return fail(PEAQ_ERR_ARG, who + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
+  if (!c) return fail(PEAQ_ERR_ARG, who + ": NULL argument: ctx is NULL");
+  if (need_out && !out) return fail(PEAQ_ERR_ARG, who + ": NULL argument: out is NULL");
+  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, who + ": NULL samples");
+  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, who + ": more than 2^32 samples");
+  return PEAQ_OK;
+}
+
+int upload_pair_48k(peaq_ctx* c, int channels, uint32_t rate, const float* ref, size_t n_ref, const float* test,
+                    size_t n_test, PairBuffers& pb) {
+  const size_t n[2] = {n_ref, n_test};
+  const float* src[2] = {ref, test};
+  for (int i = 0; i < 2; ++i) {
+    pb.len[i] = (uint32_t)n[i];
+    if (rate != 48000) {
+      pb.len[i] = peaq_resampled_length(n[i], rate);
+      if (n[i] && !pb.len[i]) return PEAQ_ERR_ARG;   // (the message is peaq_resampled_length's)
+    }
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  pb.stride = std::max<size_t>(std::max(pb.len[0], pb.len[1]), 2);
+  pb.stride += pb.stride & 1;                        // 8-byte rows, as in peaq_run_pair
+  const size_t bytes = pb.stride * channels * sizeof(float);
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(pb.s48[i].reserve(bytes));
+    HIP_TRY(hipMemset(pb.s48[i].p, 0, bytes));
+    if (!n[i]) continue;
+    if (rate == 48000) {
+      HIP_TRY(hipMemcpy(pb.s48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+      continue;
+    }
+    HIP_TRY(pb.raw[i].reserve(n[i] * channels * sizeof(float)));
+    HIP_TRY(hipMemcpy(pb.raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = peaq_batch_resample(c, channels, rate, 1, pb.raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
+                                     pb.s48[i].as<float>(), pb.stride, nullptr, nullptr))
+      return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return PEAQ_OK;
+}
+
+int estimate_one_delay(peaq_ctx* c, int channels, const PairBuffers& pb, uint32_t max_lag, peaq_delay* rec) {
+  DevBuf d_rec;
+  HIP_TRY(d_rec.reserve(sizeof(peaq_delay)));
+  if (int rc = peaq_batch_estimate_delay(c, channels, 1, pb.d(0), pb.d(1), pb.stride, pb.len, pb.len + 1, 0, max_lag,
+                                         d_rec.as<peaq_delay>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(rec, d_rec.p, sizeof *rec, hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
+int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, const float* d_ref, const float* d_test,
+                   size_t stride, uint32_t len_ref, uint32_t len_test, peaq_result* out) {
+  DevBuf d_res;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, d_ref, d_test, stride, &len_ref, &len_test, 0,
+                              d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
+// What peaq_run_pair_aligned, _matched and _trace score: the pair at 48 kHz as it is (neither max_lag nor a gain
+// mode), or the two signals cut to their common part -- from the estimated lag with max_lag, from 0 without -- with
+// the gain, where a mode other than PEAQ_GAIN_OFF asks for one, measured over that part of the uncut buffers and
+// applied in the test signal's cut.  d[0], d[1]: `stride` samples per channel long, len[] their lengths.
+struct ScoredPair {
+  PairBuffers in;
+  DevBuf cut[2], grec;
   const float* d[2] = {nullptr, nullptr};
   size_t stride = 0;
   uint32_t len[2] = {0, 0};
 };
-static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_lag, const float* ref, size_t n_ref,
-                        const float* test, size_t n_test, peaq_delay* delay, PreparedPair& pp, int gain_mode = PEAQ_GAIN_OFF,
-                        double max_gain_db = 40., peaq_gain* gain = nullptr) {
+static int prepare_pair(peaq_ctx* c, int channels, uint32_t rate, uint32_t max_lag, int gain_mode, double max_gain_db,
+                        const float* ref, size_t n_ref, const float* test, size_t n_test, peaq_delay* delay,
+                        peaq_gain* gain, ScoredPair& sp) {
   const bool match = (gain_mode & 0xF) != PEAQ_GAIN_OFF;
-  const size_t n[2] = {n_ref, n_test};
-  const float* src[2] = {ref, test};
-  uint32_t len[2];
-  for (int i = 0; i < 2; ++i) {
-    len[i] = (uint32_t)n[i];
-    if (rate != 48000) {
-      len[i] = peaq_resampled_length(n[i], rate);
-      if (n[i] && !len[i]) return PEAQ_ERR_ARG;      // (the message is peaq_resampled_length's)
-    }
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
-  stride += stride & 1;                              // 8-byte rows, as in peaq_run_pair
-  const size_t bytes = stride * channels * sizeof(float);
-  HIP_TRY(pp.rec.reserve(sizeof(peaq_delay)));
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(pp.s48[i].reserve(bytes));
-    HIP_TRY(hipMemset(pp.s48[i].p, 0, bytes));
-    if (!n[i]) continue;
-    if (rate == 48000) {
-      HIP_TRY(hipMemcpy(pp.s48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-      continue;
-    }
-    HIP_TRY(pp.raw[i].reserve(n[i] * channels * sizeof(float)));
-    HIP_TRY(hipMemcpy(pp.raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = peaq_batch_resample(c, channels, rate, 1, pp.raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
-                                     pp.s48[i].as<float>(), stride, nullptr, nullptr))
-      return rc;
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (!max_lag && !match) {                          // the signals as they are
-    if (delay) std::memset(delay, 0, sizeof *delay);
-    for (int i = 0; i < 2; ++i) {
-      pp.d[i] = pp.s48[i].as<float>();
-      pp.len[i] = len[i];
-    }
-    pp.stride = stride;
-    return PEAQ_OK;
-  }
+  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, sp.in)) return rc;
+  const PairBuffers& in = sp.in;
   peaq_delay rec;
   std::memset(&rec, 0, sizeof rec);
-  if (max_lag) {
-    if (int rc = peaq_batch_estimate_delay(c, channels, 1, pp.s48[0].as<float>(), pp.s48[1].as<float>(), stride, len,
-                                           len + 1, 0, max_lag, pp.rec.as<peaq_delay>(), nullptr))
-      return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(&rec, pp.rec.p, sizeof rec, hipMemcpyDeviceToHost));
-  }
+  if (max_lag)
+    if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
   if (delay) *delay = rec;
+  if (!max_lag && !match) {                          // the signals as they are
+    for (int i = 0; i < 2; ++i) {
+      sp.d[i] = in.d(i);
+      sp.len[i] = in.len[i];
+    }
+    sp.stride = in.stride;
+    return PEAQ_OK;
+  }
   uint32_t skip[2], common = 0;
-  peaq_aligned_lengths(rec.lag, len[0], len[1], &skip[0], &skip[1], &common);
+  peaq_aligned_lengths(rec.lag, in.len[0], in.len[1], &skip[0], &skip[1], &common);
   size_t cstride = std::max<size_t>(common, 2);
   cstride += cstride & 1;
   const size_t cbytes = cstride * channels * sizeof(float);
   if (match) {
-    HIP_TRY(pp.grec.reserve(sizeof(peaq_gain)));
-    if (int rc = peaq_batch_measure_gain(c, channels, 1, pp.s48[0].as<float>(), stride, &skip[0], pp.s48[1].as<float>(), stride,
-                                         &skip[1], &common, gain_mode, max_gain_db, pp.grec.as<peaq_gain>(), nullptr))
+    HIP_TRY(sp.grec.reserve(sizeof(peaq_gain)));
+    if (int rc = peaq_batch_measure_gain(c, channels, 1, in.d(0), in.stride, &skip[0], in.d(1), in.stride, &skip[1], &common,
+                                         gain_mode, max_gain_db, sp.grec.as<peaq_gain>(), nullptr))
       return rc;
   }
   for (int i = 0; i < 2; ++i) {
-    HIP_TRY(pp.cut[i].reserve(cbytes));
-    HIP_TRY(hipMemset(pp.cut[i].p, 0, cbytes));
+    HIP_TRY(sp.cut[i].reserve(cbytes));
+    HIP_TRY(hipMemset(sp.cut[i].p, 0, cbytes));
     if (int rc = match && i == 1
-                     ? peaq_batch_cut_scaled(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common,
-                                             pp.grec.as<peaq_gain>(), pp.cut[i].as<float>(), cstride, nullptr)
-                     : peaq_batch_cut(c, channels, 1, pp.s48[i].as<float>(), stride, &skip[i], &common, pp.cut[i].as<float>(),
-                                      cstride, nullptr))
+                     ? peaq_batch_cut_scaled(c, channels, 1, in.d(i), in.stride, &skip[i], &common, sp.grec.as<peaq_gain>(),
+                                             sp.cut[i].as<float>(), cstride, nullptr)
+                     : peaq_batch_cut(c, channels, 1, in.d(i), in.stride, &skip[i], &common, sp.cut[i].as<float>(), cstride,
+                                      nullptr))
       return rc;
-    pp.d[i] = pp.cut[i].as<float>();
-    pp.len[i] = common;
+    sp.d[i] = sp.cut[i].as<float>();
+    sp.len[i] = common;
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (match && gain) HIP_TRY(hipMemcpy(gain, pp.grec.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
-  pp.stride = cstride;
+  if (match && gain) HIP_TRY(hipMemcpy(gain, sp.grec.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
+  sp.stride = cstride;
   return PEAQ_OK;
 }
 
 extern "C" int peaq_run_pair_aligned(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
                                      uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
                                      peaq_delay* delay, peaq_result* out) {
-  const char* who = "peaq_run_pair_aligned";
+  const std::string who("peaq_run_pair_aligned");
   if (int rc = check_max_lag(who, max_lag)) return rc;
-  if (int rc = check_channels(who, channels)) return rc;
   if (int rc = check_level(who, level_db)) return rc;
-  if (rate != 48000 && !peaq_resample_supported(rate))
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
-  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
-  PreparedPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp)) return rc;
-  DevBuf d_res;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
-                              d_res.as<peaq_result>(), nullptr))
+  if (int rc = check_pair_args(who, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
+  ScoredPair sp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, sp))
     return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  return PEAQ_OK;
+  return score_one_pair(c, advanced, channels, level_db, sp.d[0], sp.d[1], sp.stride, sp.len[0], sp.len[1], out);
 }
 
 extern "C" int peaq_run_pair_matched(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
                                      uint32_t max_lag, int mode, double max_gain_db, const float* ref, size_t n_ref,
                                      const float* test, size_t n_test, peaq_delay* delay, peaq_gain* gain, peaq_result* out) {
-  const char* who = "peaq_run_pair_matched";
+  const std::string who("peaq_run_pair_matched");
   if (int rc = check_gain_mode(who, mode, max_gain_db)) return rc;
   if (max_lag)
     if (int rc = check_max_lag(who, max_lag)) return rc;
-  if (int rc = check_channels(who, channels)) return rc;
   if (int rc = check_level(who, level_db)) return rc;
-  if (rate != 48000 && !peaq_resample_supported(rate))
-    return fail(PEAQ_ERR_ARG, std::string(who) + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
-  if (!c || !out) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, std::string(who) + ": more than 2^32 samples");
+  if (int rc = check_pair_args(who, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
   if (gain) std::memset(gain, 0, sizeof *gain);
-  PreparedPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp, mode, max_gain_db, gain)) return rc;
-  DevBuf d_res;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
-                              d_res.as<peaq_result>(), nullptr))
+  ScoredPair sp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, mode, max_gain_db, ref, n_ref, test, n_test, delay, gain, sp))
     return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  return PEAQ_OK;
+  return score_one_pair(c, advanced, channels, level_db, sp.d[0], sp.d[1], sp.stride, sp.len[0], sp.len[1], out);
 }
 
 extern "C" int peaq_run_pair_trace(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
@@ -736,22 +689,17 @@ extern "C" int peaq_run_pair_trace(peaq_ctx* c, int advanced, int channels, doub
                                    peaq_frame_trace* frames, size_t frame_cap, uint32_t* n_frames,
                                    peaq_block_trace* blocks, size_t block_cap, uint32_t* n_blocks, peaq_delay* delay,
                                    peaq_result* out) {
-  const char* who = "peaq_run_pair_trace";
-  const std::string w(who);
+  const std::string w("peaq_run_pair_trace");
   if (!frames) return fail(PEAQ_ERR_ARG, w + ": frames is NULL");
   if (advanced && !blocks) return fail(PEAQ_ERR_ARG, w + ": blocks is NULL (the advanced version writes block records)");
   if (!advanced && blocks) return fail(PEAQ_ERR_ARG, w + ": blocks must be NULL in the basic version (it has no filter-bank blocks)");
   if (max_lag)
-    if (int rc = check_max_lag(who, max_lag)) return rc;
-  if (int rc = check_channels(who, channels)) return rc;
-  if (int rc = check_level(who, level_db)) return rc;
-  if (rate != 48000 && !peaq_resample_supported(rate))
-    return fail(PEAQ_ERR_ARG, w + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
-  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, w + ": NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, w + ": more than 2^32 samples");
-  PreparedPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, ref, n_ref, test, n_test, delay, pp)) return rc;
+    if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
+  ScoredPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
+    return rc;
   const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
   const uint32_t nb = advanced ? peaq_frame_count(pp.len[0], pp.len[1], 1) : 0;
   if (nf > frame_cap)

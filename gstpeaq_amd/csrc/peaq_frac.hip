@@ -17,9 +17,8 @@
 //       1024 + 64 samples per channel in LDS (absent ones as zeros), a lane owns 4 adjacent outputs per channel and
 //       walks the 68 samples under them once -- 17 reads of 16 bytes per channel, every sample feeding up to 4
 //       multiply-adds per channel -- with the pair's tap row, uniform in the workgroup, from scalar loads.  Pairs with
-//       q == 0 take align_cut_kernel's loads and stores instead: their bits are moved.
+//       q == 0 take align_cut_kernel's copy instead (copy_run, peaq_host.h): their bits are moved.
 #include "peaq_host.h"
-#include "peaq_wave.h"
 
 namespace {
 
@@ -59,27 +58,12 @@ struct RefineArgs {
 
 __device__ __forceinline__ int fr_pad16(int i) { return i + (i >> 4); }
 
-// N sums of one workgroup: wave, then the four waves in a fixed order; valid in every thread
-template <int N>
-__device__ __forceinline__ void fr_block_sum(double (&s)[N], double (*sh)[N]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) s[k] = peaq::wave_sum(s[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) sh[wave][k] = s[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) s[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
-}
-
 constexpr int kFrPass = 11;                            // sums per pass of a lane over its samples
 static_assert(kFrNK % kFrPass == 0, "whole passes");
 
 // mono sum of sample s, in double (C: a constant, so that a load is a load and not a branch)
 template <int C>
-__device__ __forceinline__ double fr_mono(const float* __restrict__ x, long long s, int) {
+__device__ __forceinline__ double fr_mono(const float* __restrict__ x, long long s) {
   if (C == 2) return (double)x[2 * s] + (double)x[2 * s + 1];
   return (double)x[s];
 }
@@ -97,7 +81,7 @@ __device__ __forceinline__ void fr_corr(const RefineArgs& a, double* tw, double 
 #pragma unroll 4
   for (int v = threadIdx.x; v < kFrWin; v += 256) {
     const long long s = t0 + v;
-    tw[fr_pad16(v)] = (s >= 0 && s < n_test) ? fr_mono<CH>(test, s, C) : 0.;
+    tw[fr_pad16(v)] = (s >= 0 && s < n_test) ? fr_mono<CH>(test, s) : 0.;
   }
   const long long m0 = n0 + (long long)kFrOwn * threadIdx.x;      // the lane's first reference sample
   const long long first = t0 + (long long)kFrOwn * threadIdx.x;   // the test sample under its window position 0
@@ -112,7 +96,7 @@ __device__ __forceinline__ void fr_corr(const RefineArgs& a, double* tw, double 
     // 66 registers of accumulators beside the samples and whatever reads are in flight: more than 128.)
     double r[kFrOwn];
 #pragma unroll
-    for (int m = 0; m < kFrOwn; ++m) r[m] = fr_mono<CH>(ref, m0 + m, C);
+    for (int m = 0; m < kFrOwn; ++m) r[m] = fr_mono<CH>(ref, m0 + m);
 #pragma unroll 1
     for (int k0 = 0; k0 < kFrNK; k0 += kFrPass) {
       double acc[kFrPass];
@@ -142,7 +126,7 @@ __device__ __forceinline__ void fr_corr(const RefineArgs& a, double* tw, double 
 #pragma unroll 1
       for (int m = 0; m < kFrOwn; ++m) {
         const long long ti = first + m + k;
-        if (m0 + m < n_ref && ti >= 0 && ti < n_test) s = __builtin_fma(fr_mono<CH>(ref, m0 + m, C), lane_tw[fr_pad16(m + k)], s);
+        if (m0 + m < n_ref && ti >= 0 && ti < n_test) s = __builtin_fma(fr_mono<CH>(ref, m0 + m), lane_tw[fr_pad16(m + k)], s);
       }
       s = peaq::wave_sum(s);
       if (lane == 0) sh[wave][k] = s;
@@ -163,7 +147,7 @@ __global__ __launch_bounds__(256, 4) void frac_corr_kernel(const RefineArgs a) {
     fr_corr<1>(a, tw, sh);
 }
 
-__device__ __forceinline__ uint32_t fr_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + kFrChunk - 1) / kFrChunk); }
+__host__ __device__ inline uint32_t frac_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + kFrChunk - 1) / kFrChunk); }
 
 // (three passes of eleven sums: 33 accumulators beside 33 loads in flight do not fit 128 registers)
 __global__ __launch_bounds__(256, 4) void frac_sum_kernel(const RefineArgs a) {
@@ -171,7 +155,7 @@ __global__ __launch_bounds__(256, 4) void frac_sum_kernel(const RefineArgs a) {
   static_assert(kFrNK % kPass == 0, "whole passes");
   __shared__ double sh[4][kPass];
   const unsigned pair = blockIdx.x;
-  const uint32_t nch = fr_chunks(a.n_ref[pair]);
+  const uint32_t nch = frac_chunks(a.n_ref[pair]);
   double* P = a.part + (size_t)pair * (a.nch_max + 1) * kFrNK;
 #pragma unroll 1
   for (int k0 = 0; k0 < kFrNK; k0 += kPass) {
@@ -182,7 +166,7 @@ __global__ __launch_bounds__(256, 4) void frac_sum_kernel(const RefineArgs a) {
 #pragma unroll
       for (int k = 0; k < kPass; ++k) s[k] += P[(size_t)ch * kFrNK + k0 + k];
     }
-    fr_block_sum(s, sh);
+    block_sum4(s, sh);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int k = 0; k < kPass; ++k) P[(size_t)a.nch_max * kFrNK + k0 + k] = s[k];
@@ -261,28 +245,6 @@ struct ShiftArgs {
   const int32_t* q;
   int channels;
 };
-
-// align_cut_kernel's share of one pair's run for units [v0, v0 + 256): the same loads and stores (peaq_align.hip)
-__device__ __forceinline__ void fr_copy(const float* __restrict__ src, float* __restrict__ dst, size_t count, size_t v0,
-                                        bool first) {
-  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
-  const size_t vecs = (count - head) / 4;
-  const size_t v = v0 + threadIdx.x;
-  if (v < vecs) {
-    const float* s = src + head + 4 * v;
-    float4 x;
-    if (((uintptr_t)s & 15) == 0)
-      x = *reinterpret_cast<const float4*>(s);
-    else
-      x = {s[0], s[1], s[2], s[3]};
-    *reinterpret_cast<float4*>(dst + head + 4 * v) = x;
-  }
-  if (first) {                                         // the unaligned head and the tail: at most 3 floats each
-    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
-    const size_t tail0 = head + 4 * vecs;
-    if (tail0 + threadIdx.x < count) dst[tail0 + threadIdx.x] = src[tail0 + threadIdx.x];
-  }
-}
 
 constexpr int kFrGroups = (kFrTaps + kFrPer - 1 + 3) / 4;   // 17 reads of 16 bytes per channel cover the 68 positions
 
@@ -369,7 +331,7 @@ __global__ __launch_bounds__(256, 4) void frac_cut_kernel(const ShiftArgs a, con
     const float* __restrict__ src = a_in + ((size_t)pair * a.in_stride + a.skip[pair]) * a.channels;
     float* __restrict__ dst = a_out + (size_t)pair * a.out_stride * a.channels;
     for (int sub = 0; sub < a.channels; ++sub)         // a tile is `channels` units of 256 x 4 floats
-      fr_copy(src, dst, count, ((size_t)blockIdx.x * a.channels + sub) * 256, blockIdx.x == 0 && sub == 0);
+      copy_run(src, dst, count, ((size_t)blockIdx.x * a.channels + sub) * 256, blockIdx.x == 0 && sub == 0, CopyBits());
     return;
   }
   const double* __restrict__ h = shift_tab + (size_t)(q + kFrSteps / 2) * kFrTaps;
@@ -459,38 +421,19 @@ const FracTables& frac_tables() {
   return t;
 }
 
-uint32_t frac_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + kFrChunk - 1) / kFrChunk); }
-
-size_t frac_scratch_bytes(uint32_t n_max, int n_pairs) {
-  if (n_pairs <= 0) return 0;
-  const size_t per_pair = ((size_t)std::max<uint32_t>(frac_chunks(n_max), 1) + 1) * kFrPartial;   // partials, then the sums
-  return std::min((size_t)n_pairs * per_pair, std::max(kFrScratchBudget, per_pair));
-}
-
-int frac_check_max_lag(const std::string& w, uint32_t max_lag) {
-  if (max_lag < 1 || max_lag > 16384)
-    return fail(PEAQ_ERR_ARG, w + ": max_lag " + std::to_string(max_lag) + " is outside 1 .. 16384");
-  return PEAQ_OK;
-}
+// partials, then the sums
+size_t frac_per_pair(uint32_t n_max) { return ((size_t)std::max<uint32_t>(frac_chunks(n_max), 1) + 1) * kFrPartial; }
 
 }  // namespace
 
 struct FracState {
   DevBuf corr, shift;           // the two tables, uploaded once
   bool tables = false;
-  DevBuf scratch;               // the partials and sums of a group of pairs
+  StageScratch scratch;         // the partials and sums of a group of pairs
   LenStage lens;                // refine: [n_ref | n_test | lag]; cut_shifted: [n_in | skip | n_keep | q]
-  hipEvent_t scratch_free = nullptr;   // behind the last kernel that used the scratch
-  bool scratch_busy = false;
 };
 
-void frac_release(peaq_ctx* c) {
-  if (!c->fr) return;
-  c->fr->lens.release();
-  if (c->fr->scratch_free) (void)hipEventDestroy(c->fr->scratch_free);
-  delete c->fr;
-  c->fr = nullptr;
-}
+void frac_release(peaq_ctx* c) { release_stage(c->fr); }
 
 // the context's stage state, its tables on the device (the first call of a context copies them, blocking, as the
 // converter does its taps)
@@ -513,7 +456,7 @@ extern "C" size_t peaq_subdelay_size(void) { return sizeof(peaq_subdelay); }
 
 extern "C" size_t peaq_subdelay_workspace_bytes(int channels, int n_pairs, uint32_t n_max) {
   if (channels != 1 && channels != 2) return 0;
-  return frac_scratch_bytes(n_max, n_pairs);
+  return pair_groups(frac_per_pair(n_max), n_pairs, kFrScratchBudget).bytes;
 }
 
 extern "C" int peaq_subsample_tables(double* corr, double* shift) {
@@ -528,30 +471,20 @@ extern "C" int peaq_batch_refine_delay(peaq_ctx* c, int channels, int n_pairs, c
                                        size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
                                        uint32_t n_uniform, const int32_t* lag, peaq_subdelay* d_out, void* stream_) {
   const std::string w("peaq_batch_refine_delay");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs " + std::to_string(n_pairs) + " < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_pairs) + " pairs are more than 65535 in one call");
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
   if (n_pairs > 0 && (!d_ref || !d_test || !d_out)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if (n_pairs > 0 && !lag) return fail(PEAQ_ERR_ARG, w + ": NULL lag");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": n_ref and n_test must both be given or both be NULL");
   const size_t np = (size_t)std::max(n_pairs, 0);
+  uint32_t n_max = 0;                                  // (the chunks are the reference's)
+  if (int rc = check_lengths(w, n_pairs, n_ref, n_uniform, "n_ref", pair_stride, "pair_stride", &n_max)) return rc;
+  if (int rc = check_lengths(w, n_pairs, n_test, n_uniform, "n_test", pair_stride, "pair_stride")) return rc;
   std::vector<uint32_t> h(3 * np);
-  uint32_t n_max = 0;
-  if (!n_ref && np && n_uniform > pair_stride)
-    return fail(PEAQ_ERR_ARG, w + ": n_uniform " + std::to_string(n_uniform) + " passes pair_stride " + std::to_string(pair_stride));
   for (size_t p = 0; p < np; ++p) {
-    const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
-    if (nr > pair_stride)
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": n_ref " + std::to_string(nr) + " passes pair_stride " +
-                                    std::to_string(pair_stride));
-    if (nt > pair_stride)
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": n_test " + std::to_string(nt) + " passes pair_stride " +
-                                    std::to_string(pair_stride));
-    h[p] = nr;
-    h[np + p] = nt;
+    h[p] = n_ref ? n_ref[p] : n_uniform;
+    h[np + p] = n_test ? n_test[p] : n_uniform;
     std::memcpy(&h[2 * np + p], &lag[p], sizeof(uint32_t));
-    n_max = std::max(n_max, nr);
   }
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (n_pairs == 0) return PEAQ_OK;
@@ -562,22 +495,16 @@ extern "C" int peaq_batch_refine_delay(peaq_ctx* c, int channels, int n_pairs, c
   FracState* st = nullptr;
   if (int rc = frac_state(c, &st)) return rc;
   const uint32_t nch = std::max<uint32_t>(frac_chunks(n_max), 1);
-  const size_t per_pair = ((size_t)nch + 1) * kFrPartial, bytes = frac_scratch_bytes(n_max, n_pairs);
-  const int group = (int)std::min<size_t>(np, std::max<size_t>(1, bytes / per_pair));
-  if (!st->scratch_free) HIP_TRY(hipEventCreateWithFlags(&st->scratch_free, hipEventDisableTiming));
-  if (bytes > st->scratch.cap && st->scratch_busy) {   // growing frees the old scratch: its last user has to be done
-    HIP_TRY(hipEventSynchronize(st->scratch_free));
-    st->scratch_busy = false;
-  }
-  HIP_TRY(st->scratch.reserve(bytes));
-  if (st->scratch_busy) HIP_TRY(hipStreamWaitEvent(stream, st->scratch_free, 0));   // (a call on another stream)
+  const PairGroups pg = pair_groups(frac_per_pair(n_max), n_pairs, kFrScratchBudget);
+  const int group = pg.group;
+  if (int rc = st->scratch.acquire(pg.bytes, stream)) return rc;
   LenSlot* slot = nullptr;
   if (int rc = st->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
   RefineArgs a{};
   a.stride = pair_stride;
   a.channels = channels;
   a.nch_max = nch;
-  a.part = st->scratch.as<double>();
+  a.part = st->scratch.buf.as<double>();
   hipError_t launched = hipSuccess;
   for (int p0 = 0; p0 < n_pairs; p0 += group) {
     const unsigned g = (unsigned)std::min(group, n_pairs - p0);
@@ -594,8 +521,7 @@ extern "C" int peaq_batch_refine_delay(peaq_ctx* c, int channels, int n_pairs, c
     if (launched != hipSuccess) break;
   }
   // (also after a failed launch: what was enqueued before it still reads the slot and the scratch)
-  const hipError_t marked = hipEventRecord(st->scratch_free, stream);
-  st->scratch_busy = marked == hipSuccess;
+  const hipError_t marked = st->scratch.mark(stream);
   const int sent = st->lens.sent(slot, stream);
   HIP_TRY(launched);
   HIP_TRY(marked);
@@ -606,38 +532,22 @@ extern "C" int peaq_batch_cut_shifted(peaq_ctx* c, int channels, int n_pairs, co
                                       const uint32_t* n_in, const uint32_t* skip, const uint32_t* n_keep, const int32_t* q,
                                       float* d_out, size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_cut_shifted");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs " + std::to_string(n_pairs) + " < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_pairs) + " pairs are more than 65535 in one call");
-  if (n_pairs > 0 && (!d_in || !d_out)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
   if (n_pairs > 0 && (!n_in || !skip || !n_keep || !q)) return fail(PEAQ_ERR_ARG, w + ": NULL n_in, skip, n_keep or q");
+  uint32_t keep_max = 0;
+  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
+                                  &keep_max))
+    return rc;
+  if (int rc = check_lengths(w, n_pairs, n_in, 0, "n_in", in_stride, "in_stride")) return rc;
   const size_t np = (size_t)std::max(n_pairs, 0);
   std::vector<uint32_t> h(4 * np);
-  uint32_t keep_max = 0;
   for (size_t p = 0; p < np; ++p) {
-    if (n_in[p] > in_stride)
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": n_in " + std::to_string(n_in[p]) + " passes in_stride " +
-                                    std::to_string(in_stride));
-    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": skip " + std::to_string(skip[p]) + " + n_keep " +
-                                    std::to_string(n_keep[p]) + " passes in_stride " + std::to_string(in_stride));
     if (q[p] < -kFrSteps / 2 || q[p] > kFrSteps / 2 - 1)
       return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": q " + std::to_string(q[p]) + " is outside -128 .. 127");
     h[p] = n_in[p];
     h[np + p] = skip[p];
     h[2 * np + p] = n_keep[p];
     std::memcpy(&h[3 * np + p], &q[p], sizeof(uint32_t));
-    keep_max = std::max(keep_max, n_keep[p]);
-  }
-  if (keep_max > out_stride)
-    return fail(PEAQ_ERR_ARG, w + ": out_stride " + std::to_string(out_stride) + " is smaller than the longest n_keep (" +
-                                  std::to_string(keep_max) + " samples)");
-  if (n_pairs > 0) {
-    const char* i0 = reinterpret_cast<const char*>(d_in);
-    const char* o0 = reinterpret_cast<const char*>(d_out);
-    const size_t ib = np * in_stride * channels * sizeof(float);
-    const size_t ob = np * out_stride * channels * sizeof(float);
-    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, w + ": d_out overlaps d_in");
   }
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
@@ -672,58 +582,23 @@ extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, 
                                        peaq_gain* gain, peaq_result* out) {
   const std::string w("peaq_run_pair_subsample");
   if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
-  if (int rc = frac_check_max_lag(w, max_lag)) return rc;
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
+  if (int rc = check_max_lag(w, max_lag)) return rc;
   if (int rc = check_level(w, level_db)) return rc;
-  if (rate != 48000 && !peaq_resample_supported(rate))
-    return fail(PEAQ_ERR_ARG, w + ": rate " + std::to_string(rate) + " Hz is not supported on the device");
-  if (!c || !out) return fail(PEAQ_ERR_ARG, w + ": NULL argument");
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, w + ": NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, w + ": more than 2^32 samples");
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
   if (gain) std::memset(gain, 0, sizeof *gain);
   const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
-  const size_t n[2] = {n_ref, n_test};
-  const float* src[2] = {ref, test};
-  uint32_t len[2];
-  for (int i = 0; i < 2; ++i) {
-    len[i] = (uint32_t)n[i];
-    if (rate != 48000) {
-      len[i] = peaq_resampled_length(n[i], rate);
-      if (n[i] && !len[i]) return PEAQ_ERR_ARG;        // (the message is peaq_resampled_length's)
-    }
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  DevBuf raw[2], s48[2], cut[2], matched, d_delay, d_sub, d_gain, d_res;
-  size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
-  stride += stride & 1;                                // 8-byte rows, as in peaq_run_pair
-  const size_t bytes = stride * channels * sizeof(float);
   // 1, 2: upload, rate conversion
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(s48[i].reserve(bytes));
-    HIP_TRY(hipMemset(s48[i].p, 0, bytes));
-    if (!n[i]) continue;
-    if (rate == 48000) {
-      HIP_TRY(hipMemcpy(s48[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-      continue;
-    }
-    HIP_TRY(raw[i].reserve(n[i] * channels * sizeof(float)));
-    HIP_TRY(hipMemcpy(raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = peaq_batch_resample(c, channels, rate, 1, raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i], s48[i].as<float>(),
-                                     stride, nullptr, nullptr))
-      return rc;
-  }
-  HIP_TRY(hipDeviceSynchronize());
+  PairBuffers in;
+  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  const uint32_t* len = in.len;
+  const size_t stride = in.stride;
   // 3, 4: estimate, refine
-  HIP_TRY(d_delay.reserve(sizeof(peaq_delay)));
-  HIP_TRY(d_sub.reserve(sizeof(peaq_subdelay)));
-  if (int rc = peaq_batch_estimate_delay(c, channels, 1, s48[0].as<float>(), s48[1].as<float>(), stride, len, len + 1, 0, max_lag,
-                                         d_delay.as<peaq_delay>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
+  DevBuf cut[2], matched, d_sub, d_gain;
   peaq_delay rec;
-  HIP_TRY(hipMemcpy(&rec, d_delay.p, sizeof rec, hipMemcpyDeviceToHost));
+  if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
   if (delay) *delay = rec;
-  if (int rc = peaq_batch_refine_delay(c, channels, 1, s48[0].as<float>(), s48[1].as<float>(), stride, len, len + 1, 0, &rec.lag,
+  HIP_TRY(d_sub.reserve(sizeof(peaq_subdelay)));
+  if (int rc = peaq_batch_refine_delay(c, channels, 1, in.d(0), in.d(1), stride, len, len + 1, 0, &rec.lag,
                                        d_sub.as<peaq_subdelay>(), nullptr))
     return rc;
   HIP_TRY(hipDeviceSynchronize());
@@ -740,9 +615,9 @@ extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, 
     HIP_TRY(cut[i].reserve(cbytes));
     HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
   }
-  if (int rc = peaq_batch_cut(c, channels, 1, s48[0].as<float>(), stride, &skip[0], &common, cut[0].as<float>(), cstride, nullptr))
+  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), stride, &skip[0], &common, cut[0].as<float>(), cstride, nullptr))
     return rc;
-  if (int rc = peaq_batch_cut_shifted(c, channels, 1, s48[1].as<float>(), stride, &len[1], &skip[1], &common, &sub.q,
+  if (int rc = peaq_batch_cut_shifted(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &common, &sub.q,
                                       cut[1].as<float>(), cstride, nullptr))
     return rc;
   const float* scored = cut[1].as<float>();
@@ -763,11 +638,5 @@ extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, 
   HIP_TRY(hipDeviceSynchronize());
   if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
   // 8: the one-pair path
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, cut[0].as<float>(), scored, cstride, &common, &common, 0,
-                              d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  return PEAQ_OK;
+  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, common, common, out);
 }

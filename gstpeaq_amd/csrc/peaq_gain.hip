@@ -12,10 +12,9 @@
 //       One partial per sum and channel to the scratch; no atomics.
 //   gain_finish_kernel       one workgroup per pair: thread t adds the partials of chunks t, t + 256, ... in chunk order,
 //       then the same fixed tree; thread 0 derives the gain in FP64 and writes the record.
-//   gain_cut_kernel          peaq_batch_cut_scaled: align_cut_kernel (peaq_align.hip) with the pair's two factors read
-//       from its record; a factor of exactly 1.0 moves the bits.
+//   gain_cut_kernel          peaq_batch_cut_scaled: align_cut_kernel's copy (copy_run, peaq_host.h) with the pair's two
+//       factors read from its record; a factor of exactly 1.0 moves the bits.
 #include "peaq_host.h"
-#include "peaq_wave.h"
 
 namespace {
 
@@ -23,6 +22,8 @@ constexpr uint32_t kGnChunk = PEAQ_GAIN_CHUNK;         // samples per channel pe
 constexpr size_t kGnPartial = 6 * sizeof(double);      // srr[2], stt[2], srt[2] of one chunk
 constexpr size_t kGnScratchBudget = (size_t)256 << 20; // pairs are taken in groups whose partials stay below this
 static_assert(kGnChunk % 1024 == 0, "a chunk is a whole number of vector units per thread, mono and stereo");
+
+__host__ __device__ inline uint32_t gain_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + kGnChunk - 1) / kGnChunk); }
 
 struct GainArgs {
   const float* ref;             // first pair of the group
@@ -38,20 +39,6 @@ struct GainArgs {
   double* part;                 // [pair][nch_max][6]
   peaq_gain* out;               // first pair of the group
 };
-
-// the six sums of one workgroup: lane -> wave -> the four waves, every level in a fixed order; valid in thread 0
-__device__ __forceinline__ void gn_block_sum(double (&s)[6], double (*sh)[6]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) s[k] = peaq::wave_sum(s[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) sh[wave][k] = s[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 6; ++k) s[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
-}
 
 __device__ __forceinline__ float4 gn_load4(const float* __restrict__ s, bool vec) {
   if (vec) return *reinterpret_cast<const float4*>(s);
@@ -105,7 +92,7 @@ __device__ __forceinline__ void gn_measure(const GainArgs& a, double (*sh)[6]) {
     if (rest && threadIdx.x == (vecs & 255))         // the tail, at most 3 floats: the unit's owner, after its whole ones
       for (unsigned e = 0; e < rest; ++e) gn_add<C>(s, (int)e, r[4 * (size_t)vecs + e], t[4 * (size_t)vecs + e]);
   }
-  gn_block_sum(s, sh);
+  block_sum4(s, sh);
   if (threadIdx.x == 0) {
     double* P = a.part + ((size_t)pair * a.nch_max + chunk) * 6;
 #pragma unroll
@@ -151,14 +138,14 @@ __global__ __launch_bounds__(256) void gain_finish_kernel(const GainArgs a) {
   __shared__ double sh[4][6];
   const unsigned pair = blockIdx.x;
   const uint32_t n = a.n[pair];
-  const uint32_t nch = (uint32_t)(((uint64_t)n + kGnChunk - 1) / kGnChunk);
+  const uint32_t nch = gain_chunks(n);
   const double* __restrict__ P = a.part + (size_t)pair * a.nch_max * 6;
   double s[6] = {0., 0., 0., 0., 0., 0.};
   for (uint32_t ch = threadIdx.x; ch < nch; ch += 256) {   // chunk order
 #pragma unroll
     for (int k = 0; k < 6; ++k) s[k] += P[(size_t)ch * 6 + k];
   }
-  gn_block_sum(s, sh);
+  block_sum4(s, sh);
   if (threadIdx.x != 0) return;
   peaq_gain rec;
   for (int c = 0; c < 2; ++c) {
@@ -198,63 +185,42 @@ __device__ __forceinline__ float gn_scale(float x, double g) {
   return __uint_as_float(g == 1. ? __float_as_uint(x) : __float_as_uint(y));
 }
 
-// align_cut_kernel with the factors: float i of a pair's run belongs to channel i mod channels
+// (both factors are read, then one is chosen: a choice between the two members themselves becomes an indexed read of
+// the functor, which then does not dissolve into registers)
+__device__ __forceinline__ double gn_pick(bool odd, double g_even, double g_odd) { return odd ? g_odd : g_even; }
+
+// what copy_run stores: float i of a pair's run belongs to channel i mod channels
+struct GnScale {
+  double g0, g1;
+  bool plain;                   // (uniform) an unmatched pair: peaq_batch_cut's copy
+  __device__ __forceinline__ float4 operator()(float4 x, size_t i) const {
+    if (plain) return x;
+    const double ge = of(i), go = of(i + 1);           // of the unit's even and odd floats
+    return {gn_scale(x.x, ge), gn_scale(x.y, go), gn_scale(x.z, ge), gn_scale(x.w, go)};
+  }
+  __device__ __forceinline__ float operator()(float x, size_t i) const { return plain ? x : gn_scale(x, of(i)); }
+  __device__ __forceinline__ double of(size_t i) const { return gn_pick(i & 1, g0, g1); }
+};
+
 __global__ __launch_bounds__(256) void gain_cut_kernel(const ScaledCutArgs a) {
   const unsigned pair = blockIdx.y;
   const size_t count = (size_t)a.n_keep[pair] * a.channels;
   const float* __restrict__ src = a.in + ((size_t)pair * a.in_stride + a.skip[pair]) * a.channels;
   float* __restrict__ dst = a.out + (size_t)pair * a.out_stride * a.channels;
   const double g0 = a.gain[pair].gain[0], g1 = a.channels == 2 ? a.gain[pair].gain[1] : g0;
-  const bool plain = g0 == 1. && g1 == 1.;           // (uniform) an unmatched pair: peaq_batch_cut's copy
-  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
-  const size_t vecs = (count - head) / 4;
-  const double ge = (head & 1) ? g1 : g0, go = (head & 1) ? g0 : g1;   // of a unit's even and odd floats
-  const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < vecs) {
-    const float* s = src + head + 4 * v;
-    float4 x;
-    if (((uintptr_t)s & 15) == 0)
-      x = *reinterpret_cast<const float4*>(s);
-    else
-      x = {s[0], s[1], s[2], s[3]};
-    if (!plain) x = {gn_scale(x.x, ge), gn_scale(x.y, go), gn_scale(x.z, ge), gn_scale(x.w, go)};
-    *reinterpret_cast<float4*>(dst + head + 4 * v) = x;
-  }
-  if (blockIdx.x == 0) {                             // the unaligned head and the tail: at most 3 floats each
-    const double gt = (threadIdx.x & 1) ? g1 : g0;   // (head + 4 vecs has head's parity)
-    if (threadIdx.x < head) dst[threadIdx.x] = plain ? src[threadIdx.x] : gn_scale(src[threadIdx.x], gt);
-    const size_t tail0 = head + 4 * vecs;
-    if (tail0 + threadIdx.x < count) {
-      const double gq = ((tail0 + threadIdx.x) & 1) ? g1 : g0;
-      dst[tail0 + threadIdx.x] = plain ? src[tail0 + threadIdx.x] : gn_scale(src[tail0 + threadIdx.x], gq);
-    }
-  }
+  copy_run(src, dst, count, (size_t)blockIdx.x * 256, blockIdx.x == 0, GnScale{g0, g1, g0 == 1. && g1 == 1.});
 }
 
-uint32_t gain_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + kGnChunk - 1) / kGnChunk); }
-
-size_t gain_scratch_bytes(uint32_t n_max, int n_pairs) {
-  if (n_pairs <= 0) return 0;
-  const size_t per_pair = std::max<size_t>(gain_chunks(n_max), 1) * kGnPartial;
-  return std::min((size_t)n_pairs * per_pair, std::max(kGnScratchBudget, per_pair));
-}
+size_t gain_per_pair(uint32_t n_max) { return std::max<size_t>(gain_chunks(n_max), 1) * kGnPartial; }
 
 }  // namespace
 
 struct GainState {
-  DevBuf scratch;               // the partials of a group of pairs
+  StageScratch scratch;         // the partials of a group of pairs
   LenStage lens;                // measure: [skip_ref | skip_test | n]; cut_scaled: [skip | n_keep]
-  hipEvent_t scratch_free = nullptr;   // behind the last kernel that used the scratch
-  bool scratch_busy = false;
 };
 
-void gain_release(peaq_ctx* c) {
-  if (!c->gn) return;
-  c->gn->lens.release();
-  if (c->gn->scratch_free) (void)hipEventDestroy(c->gn->scratch_free);
-  delete c->gn;
-  c->gn = nullptr;
-}
+void gain_release(peaq_ctx* c) { release_stage(c->gn); }
 
 int check_gain_mode(const std::string& who, int mode, double max_gain_db) {
   if (mode < 0 || (mode & ~(0xF | PEAQ_GAIN_PER_CHANNEL)) || (mode & 0xF) > PEAQ_GAIN_POLARITY)
@@ -268,7 +234,7 @@ extern "C" size_t peaq_gain_size(void) { return sizeof(peaq_gain); }
 
 extern "C" size_t peaq_gain_workspace_bytes(int channels, int n_pairs, uint32_t n_max) {
   if (channels != 1 && channels != 2) return 0;
-  return gain_scratch_bytes(n_max, n_pairs);
+  return pair_groups(gain_per_pair(n_max), n_pairs, kGnScratchBudget).bytes;
 }
 
 extern "C" int peaq_batch_measure_gain(peaq_ctx* c, int channels, int n_pairs, const float* d_ref, size_t ref_stride,
@@ -277,9 +243,7 @@ extern "C" int peaq_batch_measure_gain(peaq_ctx* c, int channels, int n_pairs, c
                                        peaq_gain* d_out, void* stream_) {
   const std::string w("peaq_batch_measure_gain");
   if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs " + std::to_string(n_pairs) + " < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_pairs) + " pairs are more than 65535 in one call");
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
   if (n_pairs > 0 && (!d_ref || !d_test || !d_out)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if (n_pairs > 0 && (!skip_ref || !skip_test || !n)) return fail(PEAQ_ERR_ARG, w + ": NULL skip_ref, skip_test or n");
   const size_t np = (size_t)n_pairs;
@@ -306,15 +270,9 @@ extern "C" int peaq_batch_measure_gain(peaq_ctx* c, int channels, int n_pairs, c
   if (!c->gn) c->gn = new GainState;
   GainState* st = c->gn;
   const uint32_t nch = std::max<uint32_t>(gain_chunks(n_max), 1);
-  const size_t per_pair = (size_t)nch * kGnPartial, bytes = gain_scratch_bytes(n_max, n_pairs);
-  const int group = (int)std::min<size_t>(np, std::max<size_t>(1, bytes / per_pair));
-  if (!st->scratch_free) HIP_TRY(hipEventCreateWithFlags(&st->scratch_free, hipEventDisableTiming));
-  if (bytes > st->scratch.cap && st->scratch_busy) {   // growing frees the old scratch: its last user has to be done
-    HIP_TRY(hipEventSynchronize(st->scratch_free));
-    st->scratch_busy = false;
-  }
-  HIP_TRY(st->scratch.reserve(bytes));
-  if (st->scratch_busy) HIP_TRY(hipStreamWaitEvent(stream, st->scratch_free, 0));   // (a call on another stream)
+  const PairGroups pg = pair_groups(gain_per_pair(n_max), n_pairs, kGnScratchBudget);
+  const int group = pg.group;
+  if (int rc = st->scratch.acquire(pg.bytes, stream)) return rc;
   LenSlot* slot = nullptr;
   if (int rc = st->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
   GainArgs a{};
@@ -325,7 +283,7 @@ extern "C" int peaq_batch_measure_gain(peaq_ctx* c, int channels, int n_pairs, c
   a.g_lo = std::pow(10., -max_gain_db / 20.);
   a.g_hi = std::pow(10., max_gain_db / 20.);
   a.nch_max = nch;
-  a.part = st->scratch.as<double>();
+  a.part = st->scratch.buf.as<double>();
   hipError_t launched = hipSuccess;
   for (int p0 = 0; p0 < n_pairs; p0 += group) {
     const unsigned g = (unsigned)std::min(group, n_pairs - p0);
@@ -341,8 +299,7 @@ extern "C" int peaq_batch_measure_gain(peaq_ctx* c, int channels, int n_pairs, c
     if (launched != hipSuccess) break;
   }
   // (also after a failed launch: what was enqueued before it still reads the slot and the scratch)
-  const hipError_t marked = hipEventRecord(st->scratch_free, stream);
-  st->scratch_busy = marked == hipSuccess;
+  const hipError_t marked = st->scratch.mark(stream);
   const int sent = st->lens.sent(slot, stream);
   HIP_TRY(launched);
   HIP_TRY(marked);
@@ -353,35 +310,17 @@ extern "C" int peaq_batch_cut_scaled(peaq_ctx* c, int channels, int n_pairs, con
                                      const uint32_t* skip, const uint32_t* n_keep, const peaq_gain* d_gain, float* d_out,
                                      size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_cut_scaled");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs " + std::to_string(n_pairs) + " < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_pairs) + " pairs are more than 65535 in one call");
-  if (n_pairs > 0 && (!d_in || !d_out)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
   if (n_pairs > 0 && !d_gain) return fail(PEAQ_ERR_ARG, w + ": NULL d_gain");
   if (n_pairs > 0 && (!skip || !n_keep)) return fail(PEAQ_ERR_ARG, w + ": NULL skip or n_keep");
-  const size_t np = (size_t)std::max(n_pairs, 0);
-  std::vector<uint32_t> h(2 * np);
   uint32_t keep_max = 0;
-  for (size_t p = 0; p < np; ++p) {
-    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": skip " + std::to_string(skip[p]) + " + n_keep " +
-                                    std::to_string(n_keep[p]) + " passes in_stride " + std::to_string(in_stride));
-    h[p] = skip[p];
-    h[np + p] = n_keep[p];
-    keep_max = std::max(keep_max, n_keep[p]);
-  }
-  if (keep_max > out_stride)
-    return fail(PEAQ_ERR_ARG, w + ": out_stride " + std::to_string(out_stride) + " is smaller than the longest n_keep (" +
-                                  std::to_string(keep_max) + " samples)");
-  if (n_pairs > 0) {
-    const char* i0 = reinterpret_cast<const char*>(d_in);
-    const char* o0 = reinterpret_cast<const char*>(d_out);
-    const size_t ib = np * in_stride * channels * sizeof(float);
-    const size_t ob = np * out_stride * channels * sizeof(float);
-    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, w + ": d_out overlaps d_in");
-  }
+  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
+                                  &keep_max))
+    return rc;
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
+  std::vector<uint32_t> h(skip, skip + n_pairs);
+  h.insert(h.end(), n_keep, n_keep + n_pairs);
 
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::lock_guard<std::mutex> lock(c->mu);

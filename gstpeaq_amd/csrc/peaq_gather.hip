@@ -25,30 +25,13 @@ struct GatherArgs {
   int channels;
 };
 
-// floats, not samples: an output's run is n_keep x channels consecutive floats (as align_cut_kernel, peaq_align.hip)
+// floats, not samples: an output's run is n_keep x channels consecutive floats (copy_run, peaq_host.h)
 __global__ __launch_bounds__(256) void gather_kernel(const GatherArgs a) {
   const unsigned p = a.order[blockIdx.y];
   const size_t count = (size_t)a.n_keep[p] * a.channels;
   const float* __restrict__ src = a.in + ((size_t)a.src[p] * a.in_stride + a.skip[p]) * a.channels;
   float* __restrict__ dst = a.out + (size_t)p * a.out_stride * a.channels;
-  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
-  const size_t vecs = (count - head) / 4;
-  const bool same_phase = ((uintptr_t)(src + head) & 15) == 0;   // of the whole output: units are 16 bytes apart
-  const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < vecs) {
-    const float* s = src + head + 4 * v;
-    float4 x;
-    if (same_phase)
-      x = *reinterpret_cast<const float4*>(s);
-    else
-      x = {s[0], s[1], s[2], s[3]};
-    *reinterpret_cast<float4*>(dst + head + 4 * v) = x;
-  }
-  if (blockIdx.x == 0) {                             // the unaligned head and the tail: at most 3 floats each
-    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
-    const size_t tail0 = head + 4 * vecs;
-    if (tail0 + threadIdx.x < count) dst[tail0 + threadIdx.x] = src[tail0 + threadIdx.x];
-  }
+  copy_run(src, dst, count, (size_t)blockIdx.x * 256, blockIdx.x == 0, CopyBits());
 }
 
 }  // namespace
@@ -68,39 +51,24 @@ extern "C" int peaq_batch_gather(peaq_ctx* c, int channels, int n_rows, int n_ou
                                  const uint32_t* src, const uint32_t* skip, const uint32_t* n_keep, float* d_out,
                                  size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_gather");
-  if (channels != 1 && channels != 2) return fail(PEAQ_ERR_ARG, w + ": channels must be 1 or 2, not " + std::to_string(channels));
-  if (n_rows < 0 || n_out < 0)
-    return fail(PEAQ_ERR_ARG, w + ": n_rows " + std::to_string(n_rows) + " or n_out " + std::to_string(n_out) + " < 0");
-  if (n_rows > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_rows) + " rows are more than 65535 in one call");
-  if (n_out > 65535) return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_out) + " outputs are more than 65535 in one call");
-  if (n_out > 0 && (!d_in || !d_out)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (int rc = check_channels(w, channels)) return rc;
+  if (int rc = check_count(w, n_rows, "n_rows", "rows")) return rc;
+  if (int rc = check_count(w, n_out, "n_out", "outputs")) return rc;
   if (n_out > 0 && (!src || !skip || !n_keep)) return fail(PEAQ_ERR_ARG, w + ": NULL src, skip or n_keep");
-  const size_t no = (size_t)std::max(n_out, 0);
-  std::vector<uint32_t> h(4 * no);                     // order, src, skip, n_keep
-  uint32_t keep_max = 0;
-  for (size_t p = 0; p < no; ++p) {
+  const size_t no = (size_t)n_out;
+  for (size_t p = 0; p < no; ++p)
     if (src[p] >= (uint32_t)n_rows)
       return fail(PEAQ_ERR_ARG, w + ": output " + std::to_string(p) + " names row " + std::to_string(src[p]) + " of " +
                                     std::to_string(n_rows));
-    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
-      return fail(PEAQ_ERR_ARG, w + ": output " + std::to_string(p) + ": skip " + std::to_string(skip[p]) + " + n_keep " +
-                                    std::to_string(n_keep[p]) + " passes in_stride " + std::to_string(in_stride));
-    h[p] = (uint32_t)p;
-    h[no + p] = src[p];
-    h[2 * no + p] = skip[p];
-    h[3 * no + p] = n_keep[p];
-    keep_max = std::max(keep_max, n_keep[p]);
-  }
-  if (keep_max > out_stride)
-    return fail(PEAQ_ERR_ARG, w + ": out_stride " + std::to_string(out_stride) + " is smaller than the longest n_keep (" +
-                                  std::to_string(keep_max) + " samples)");
-  if (n_out > 0) {
-    const char* i0 = reinterpret_cast<const char*>(d_in);
-    const char* o0 = reinterpret_cast<const char*>(d_out);
-    const size_t ib = (size_t)n_rows * in_stride * channels * sizeof(float);
-    const size_t ob = no * out_stride * channels * sizeof(float);
-    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, w + ": d_out overlaps d_in");
-  }
+  uint32_t keep_max = 0;
+  if (int rc = check_cut_geometry(w, "output", channels, n_rows, n_out, d_in, in_stride, skip, n_keep, d_out, out_stride,
+                                  &keep_max))
+    return rc;
+  std::vector<uint32_t> h(4 * no);                     // order, src, skip, n_keep
+  for (size_t p = 0; p < no; ++p) h[p] = (uint32_t)p;
+  std::copy(src, src + no, h.begin() + no);
+  std::copy(skip, skip + no, h.begin() + 2 * no);
+  std::copy(n_keep, n_keep + no, h.begin() + 3 * no);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (n_out == 0 || keep_max == 0) return PEAQ_OK;
   // outputs of one row next to each other, in the caller's order among themselves

@@ -2,11 +2,15 @@
 // argument checks every entry point repeats, the framing arithmetic, device buffers, the context, the model half of
 // the kernels' argument blocks (ModelSetup), and the stream framer (StreamFramer: the element's do_processing /
 // do_flush on the host-side stand-ins for its two GstAdapters) that sessions, the broker and peaq_debug_stream_plan
-// run.  Host code only; the kernels are in peaq_frontend.hip / peaq_backend.hip / peaq_fb.hip / peaq_synth.hip.
+// run; and what the stages in front of the batch driver share: their scratch owner, their argument checks, the steps
+// of the one-pair conveniences.  Host code, but for one marked section of device-side pieces of those stages (a copy
+// body and a workgroup sum: no kernel is defined here); the model's kernels are in peaq_frontend.hip /
+// peaq_backend.hip / peaq_fb.hip / peaq_synth.hip.
 //   peaq_ctx.hip      errors, version, framing, context, settings, calibration
 //   peaq_batch.hip    batch driver (peaq_batch_run, peaq_run_pair), timing, synthetic workload
 //   peaq_resample.hip sample-rate conversion to 48 kHz in front of the batch driver (kernels and host side)
-//   peaq_align.hip    delay estimation and cutting in front of the batch driver (kernels and host side)
+//   peaq_align.hip    delay estimation and cutting in front of the batch driver (kernels and host side); the steps of
+//                     the one-pair conveniences (upload and conversion, delay estimate, scoring)
 //   peaq_pcm.hip      PCM decoder in front of them (kernels and host side) and the host-fed batches (peaq_batch_run_host,
 //                     peaq_batch_run_host_refs)
 //   peaq_gather.hip   copy by source index, what shares one uploaded reference among its tests (kernel and host side)
@@ -40,6 +44,7 @@
 #include "peaq_device.h"
 #include "peaq_kernels.h"
 #include "peaq_tables.h"
+#include "peaq_wave.h"
 
 #ifdef PEAQ_DEV_PROBES                               // VARIANT builds only (csrc/Makefile): never in the product library
 #define PEAQ_DEV_TU_CAPI
@@ -74,7 +79,9 @@ inline int fail(int code, const std::string& msg) {
 
 // the two argument checks most entry points share (`who` names the entry point in the message)
 inline int check_channels(const std::string& who, int channels) {
-  return channels == 1 || channels == 2 ? PEAQ_OK : fail(PEAQ_ERR_ARG, who + ": channels must be 1 or 2");
+  return channels == 1 || channels == 2
+             ? PEAQ_OK
+             : fail(PEAQ_ERR_ARG, who + ": channels must be 1 or 2, not " + std::to_string(channels));
 }
 inline int check_level(const std::string& who, double level_db) {
   return level_db >= 0. && level_db <= 130.
@@ -179,20 +186,18 @@ struct peaq_ctx {
   }
 };
 
-// frees what peaq_batch_resample has cached in the context (peaq_resample.hip); the device is idle
+// free what a stage has cached in the context; the device is idle.  peaq_resample.hip, peaq_align.hip, peaq_pcm.hip,
+// peaq_gather.hip, peaq_gain.hip, peaq_frac.hip
 void resample_release(peaq_ctx* c);
-// the same for peaq_batch_estimate_delay / peaq_batch_cut (peaq_align.hip)
 void align_release(peaq_ctx* c);
-// the same for peaq_batch_decode_pcm / peaq_batch_run_host (peaq_pcm.hip)
 void feed_release(peaq_ctx* c);
-// the same for peaq_batch_gather (peaq_gather.hip)
 void gather_release(peaq_ctx* c);
-// the same for peaq_batch_measure_gain / peaq_batch_cut_scaled (peaq_gain.hip)
 void gain_release(peaq_ctx* c);
-// the same for peaq_batch_refine_delay / peaq_batch_cut_shifted (peaq_frac.hip)
 void frac_release(peaq_ctx* c);
 // mode (PEAQ_GAIN_* with or without PEAQ_GAIN_PER_CHANNEL) and max_gain_db as every entry point of the stage takes them
 int check_gain_mode(const std::string& who, int mode, double max_gain_db);
+// max_lag of the aligner, 1 .. 16384 (peaq_align.hip)
+int check_max_lag(const std::string& who, uint32_t max_lag);
 
 // ---------------------------------------------------------------------------
 // Per-pair host arrays of one call (lengths, skips): staged in pinned host memory and copied on the caller's stream,
@@ -247,6 +252,200 @@ struct LenStage {
     }
   }
 };
+
+// ---------------------------------------------------------------------------
+// Scratch of a stage, shared between its calls and their streams: grown only when its last user is done, waited for
+// by a call on another stream, marked behind the last launch of every call.  The owner holds the context's lock.
+// Nothing here reads the buffer: a stage's kernels write what they read (PEAQ_AMD_POISON).
+// ---------------------------------------------------------------------------
+struct StageScratch {
+  DevBuf buf;
+  hipEvent_t free_ev = nullptr;   // behind the last kernel that used the buffer
+  bool busy = false;
+
+  int acquire(size_t bytes, hipStream_t stream) {
+    if (!free_ev) HIP_TRY(hipEventCreateWithFlags(&free_ev, hipEventDisableTiming));
+    if (bytes > buf.cap && busy) {                     // growing frees the old buffer: its last user has to be done
+      HIP_TRY(hipEventSynchronize(free_ev));
+      busy = false;
+    }
+    HIP_TRY(buf.reserve(bytes));
+    if (busy) HIP_TRY(hipStreamWaitEvent(stream, free_ev, 0));   // (a call on another stream)
+    return PEAQ_OK;
+  }
+  // behind a call's last launch -- also after a failed one: what was enqueued before it still uses the buffer
+  hipError_t mark(hipStream_t stream) {
+    const hipError_t e = hipEventRecord(free_ev, stream);
+    busy = e == hipSuccess;
+    return e;
+  }
+  void release() {                                     // (the device is idle)
+    if (free_ev) (void)hipEventDestroy(free_ev);
+    free_ev = nullptr;
+    busy = false;
+    buf.release();
+  }
+};
+
+// a stage's state in the context: `lens` and `scratch`, whatever else it holds frees itself
+template <typename S>
+void release_stage(S*& st) {
+  if (!st) return;
+  st->lens.release();
+  st->scratch.release();
+  delete st;
+  st = nullptr;
+}
+
+// Pairs are taken in groups whose scratch stays below `budget` (or is one pair's, if that is more): the scratch of a
+// call of n_pairs pairs of per_pair bytes each, and the pairs of a group.
+struct PairGroups {
+  size_t bytes;
+  int group;
+};
+inline PairGroups pair_groups(size_t per_pair, int n_pairs, size_t budget) {
+  if (n_pairs <= 0) return {0, 0};
+  const size_t bytes = std::min((size_t)n_pairs * per_pair, std::max(budget, per_pair));
+  return {bytes, (int)std::min<size_t>((size_t)n_pairs, std::max<size_t>(1, bytes / per_pair))};
+}
+
+// ---------------------------------------------------------------------------
+// argument checks of the batch stages (`who` names the entry point); the context is the caller's to look at, last
+// ---------------------------------------------------------------------------
+// the call's shape: channels, and a count of `noun` in 0 .. 65535 (a grid's y extent)
+inline int check_count(const std::string& who, int n, const char* name = "n_pairs", const char* noun = "pairs") {
+  if (n < 0) return fail(PEAQ_ERR_ARG, who + ": " + name + " " + std::to_string(n) + " < 0");
+  if (n > 65535) return fail(PEAQ_ERR_ARG, who + ": " + std::to_string(n) + " " + noun + " are more than 65535 in one call");
+  return PEAQ_OK;
+}
+inline int check_shape(const std::string& who, int channels, int n_pairs) {
+  if (int rc = check_channels(who, channels)) return rc;
+  return check_count(who, n_pairs);
+}
+
+// The cut geometry: n_out runs, run p being n_keep[p] samples from skip[p] on of some row of d_in [n_rows][in_stride],
+// to row p of d_out [n_out][out_stride] (`noun`: what a run is called, "pair" or "output").  skip and n_keep are
+// not NULL where n_out > 0: the caller has looked, it knows their names.  *keep_max: the longest run.
+inline int check_cut_geometry(const std::string& who, const char* noun, int channels, int n_rows, int n_out,
+                              const float* d_in, size_t in_stride, const uint32_t* skip, const uint32_t* n_keep,
+                              const float* d_out, size_t out_stride, uint32_t* keep_max) {
+  *keep_max = 0;
+  if (n_out <= 0) return PEAQ_OK;
+  if (!d_in || !d_out) return fail(PEAQ_ERR_ARG, who + ": NULL buffer");
+  for (int p = 0; p < n_out; ++p) {
+    if ((uint64_t)skip[p] + n_keep[p] > in_stride)
+      return fail(PEAQ_ERR_ARG, who + ": " + noun + " " + std::to_string(p) + ": skip " + std::to_string(skip[p]) +
+                                    " + n_keep " + std::to_string(n_keep[p]) + " passes in_stride " + std::to_string(in_stride));
+    *keep_max = std::max(*keep_max, n_keep[p]);
+  }
+  if (*keep_max > out_stride)
+    return fail(PEAQ_ERR_ARG, who + ": out_stride " + std::to_string(out_stride) + " is smaller than the longest n_keep (" +
+                                  std::to_string(*keep_max) + " samples)");
+  const char* i0 = reinterpret_cast<const char*>(d_in);
+  const char* o0 = reinterpret_cast<const char*>(d_out);
+  const size_t ib = (size_t)n_rows * in_stride * channels * sizeof(float);
+  const size_t ob = (size_t)n_out * out_stride * channels * sizeof(float);
+  if (i0 < o0 + ob && o0 < i0 + ib) return fail(PEAQ_ERR_ARG, who + ": d_out overlaps d_in");
+  return PEAQ_OK;
+}
+
+// per-pair lengths n[p] -- or, n being NULL, n_uniform -- against the stride of their buffer; *n_max: the longest
+inline int check_lengths(const std::string& who, int n_pairs, const uint32_t* n, uint32_t n_uniform, const char* name,
+                         size_t stride, const char* stride_name, uint32_t* n_max = nullptr) {
+  uint32_t longest = 0;
+  if (!n_max) n_max = &longest;
+  *n_max = 0;
+  if (n_pairs <= 0) return PEAQ_OK;
+  if (!n) {
+    *n_max = n_uniform;
+    if (n_uniform > stride)
+      return fail(PEAQ_ERR_ARG, who + ": n_uniform " + std::to_string(n_uniform) + " passes " + stride_name + " " +
+                                    std::to_string(stride));
+    return PEAQ_OK;
+  }
+  for (int p = 0; p < n_pairs; ++p) {
+    if (n[p] > stride)
+      return fail(PEAQ_ERR_ARG, who + ": pair " + std::to_string(p) + ": " + name + " " + std::to_string(n[p]) + " passes " +
+                                    stride_name + " " + std::to_string(stride));
+    *n_max = std::max(*n_max, n[p]);
+  }
+  return PEAQ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The steps of the one-pair conveniences (peaq_run_pair_rate, _aligned, _matched, _trace, _subsample), defined in
+// peaq_align.hip.  Each of them blocks; the stage calls between them are the entry point's own.
+// ---------------------------------------------------------------------------
+// (a) what every peaq_run_pair_* call checks, beside check_level where it looks at the level: channels, rate, ctx and
+//     (need_out) out, samples, their counts
+int check_pair_args(const std::string& who, const peaq_ctx* c, int channels, uint32_t rate, const float* ref,
+                    size_t n_ref, const float* test, size_t n_test, const void* out, bool need_out);
+// (b) a host pair on the device at 48 kHz: s48[0], s48[1] of `stride` samples per channel, zeros behind len[i]
+struct PairBuffers {
+  DevBuf raw[2], s48[2];
+  uint32_t len[2] = {0, 0};
+  size_t stride = 0;
+  const float* d(int i) const { return s48[i].as<float>(); }
+};
+int upload_pair_48k(peaq_ctx* c, int channels, uint32_t rate, const float* ref, size_t n_ref, const float* test,
+                    size_t n_test, PairBuffers& pb);
+// (c) the delay of the pair, estimated and fetched
+int estimate_one_delay(peaq_ctx* c, int channels, const PairBuffers& pb, uint32_t max_lag, peaq_delay* rec);
+// (d) one prepared pair scored with peaq_batch_run, the result fetched
+int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, const float* d_ref, const float* d_test,
+                   size_t stride, uint32_t len_ref, uint32_t len_test, peaq_result* out);
+
+// ---------------------------------------------------------------------------
+// DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip and peaq_gather.hip share
+// (256 threads per workgroup).  No kernel is defined in this header.
+// ---------------------------------------------------------------------------
+// A workgroup's share of the copy of `count` consecutive floats from src to dst: the 16-byte units v0 .. v0 + 255,
+// counted from the first 16-byte aligned float of dst, and with `ends` the unaligned head and the tail, at most 3
+// floats each.  Stores are 16 bytes; loads are too where src + head is aligned alike (the whole run is, or is
+// not), else four dwords.  f(x, i) is what is stored for x, a float4 or a float whose (first) float is float i of
+// the run.
+struct CopyBits {
+  __device__ __forceinline__ float4 operator()(float4 x, size_t) const { return x; }
+  __device__ __forceinline__ float operator()(float x, size_t) const { return x; }
+};
+template <typename F>
+__device__ __forceinline__ void copy_run(const float* __restrict__ src, float* __restrict__ dst, size_t count, size_t v0,
+                                         bool ends, F f) {
+  const size_t head = min(count, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(float));
+  const size_t vecs = (count - head) / 4;
+  const bool same_phase = ((uintptr_t)(src + head) & 15) == 0;   // of the whole run: units are 16 bytes apart
+  const size_t v = v0 + threadIdx.x;
+  if (v < vecs) {
+    const float* s = src + head + 4 * v;
+    float4 x;
+    if (same_phase)
+      x = *reinterpret_cast<const float4*>(s);
+    else
+      x = {s[0], s[1], s[2], s[3]};
+    *reinterpret_cast<float4*>(dst + head + 4 * v) = f(x, head + 4 * v);
+  }
+  if (ends) {
+    if (threadIdx.x < head) dst[threadIdx.x] = f(src[threadIdx.x], (size_t)threadIdx.x);
+    const size_t tail0 = head + 4 * vecs;
+    if (tail0 + threadIdx.x < count) dst[tail0 + threadIdx.x] = f(src[tail0 + threadIdx.x], tail0 + threadIdx.x);
+  }
+}
+
+// N sums of one workgroup: the wave (peaq::wave_sum), then the four waves (0 + 1) + (2 + 3); valid in every thread.
+// sh: [4][N] of LDS, declared in the kernel.
+template <int N>
+__device__ __forceinline__ void block_sum4(double (&s)[N], double (*sh)[N]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) s[k] = peaq::wave_sum(s[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) sh[wave][k] = s[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) s[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
+}
 
 // ---- batch driver pieces used elsewhere (peaq_batch.hip) --------------------------------------------------
 unsigned fb_blocks_per_chunk(int n_pairs, int channels, uint32_t max_blocks);

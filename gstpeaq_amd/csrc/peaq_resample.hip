@@ -412,30 +412,28 @@ extern "C" uint32_t peaq_resampled_length(uint64_t n, uint32_t rate) {
 extern "C" int peaq_batch_resample(peaq_ctx* c, int channels, uint32_t rate, int n_pairs, const float* d_in,
                                    size_t in_stride, const uint32_t* n_in, uint32_t n_uniform, float* d_out,
                                    size_t out_stride, uint32_t* n_out, void* stream_) {
+  const std::string who("peaq_batch_resample");
   // (what needs no context first)
   if (int rc = check_rate("peaq_batch_resample", rate)) return rc;
-  if (int rc = check_channels("peaq_batch_resample", channels)) return rc;
-  if (n_pairs < 0) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: n_pairs < 0");
-  if (n_pairs > 65535) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: more than 65535 pairs in one call");
-  if (!c) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: ctx is NULL");
+  if (int rc = check_shape(who, channels, n_pairs)) return rc;
+  if (!c) return fail(PEAQ_ERR_ARG, who + ": ctx is NULL");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_in || !d_out) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: NULL buffer");
+  if (!d_in || !d_out) return fail(PEAQ_ERR_ARG, who + ": NULL buffer");
   // lengths
+  if (int rc = check_lengths(who, n_pairs, n_in, n_uniform, "n_in", in_stride, "in_stride")) return rc;
   std::vector<uint32_t> h;
   uint32_t len_uniform = 0, len_max = 0;
   if (n_in) {
+    h.assign(n_in, n_in + n_pairs);
     h.resize(2 * (size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
-      if (n_in[p] > in_stride) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: a pair is longer than in_stride");
-      h[p] = n_in[p];
       if (!resampled_length(n_in[p], rate, &h[(size_t)n_pairs + p]))
-        return fail(PEAQ_ERR_ARG, "peaq_batch_resample: a converted length does not fit 32 bits");
+        return fail(PEAQ_ERR_ARG, who + ": a converted length does not fit 32 bits");
       len_max = std::max(len_max, h[(size_t)n_pairs + p]);
     }
   } else {
-    if (n_uniform > in_stride) return fail(PEAQ_ERR_ARG, "peaq_batch_resample: n_uniform > in_stride");
     if (!resampled_length(n_uniform, rate, &len_uniform))
-      return fail(PEAQ_ERR_ARG, "peaq_batch_resample: the converted length does not fit 32 bits");
+      return fail(PEAQ_ERR_ARG, who + ": the converted length does not fit 32 bits");
     len_max = len_uniform;
   }
   if (len_max > out_stride)
@@ -498,37 +496,9 @@ extern "C" int peaq_run_pair_rate(peaq_ctx* c, int advanced, int channels, doubl
                                   const float* ref, size_t n_ref, const float* test, size_t n_test, peaq_result* out) {
   if (rate == 48000) return peaq_run_pair(c, advanced, channels, level_db, ref, n_ref, test, n_test, out);
   if (int rc = check_rate("peaq_run_pair_rate", rate)) return rc;
-  if (!c || !out) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: NULL argument");
-  if (int rc = check_channels("peaq_run_pair_rate", channels)) return rc;
-  if ((n_ref && !ref) || (n_test && !test)) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: NULL samples");
-  if (n_ref > 0xFFFFFFFFu || n_test > 0xFFFFFFFFu) return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: more than 2^32 samples");
-  const size_t n[2] = {n_ref, n_test};
-  const float* src[2] = {ref, test};
-  uint32_t len[2];
-  for (int i = 0; i < 2; ++i)
-    if (!resampled_length(n[i], rate, &len[i]))
-      return fail(PEAQ_ERR_ARG, "peaq_run_pair_rate: the converted length does not fit 32 bits");
-  HIP_TRY(hipSetDevice(c->device));
-  size_t stride = std::max<size_t>(std::max(len[0], len[1]), 2);
-  stride += stride & 1;                              // 8-byte rows, as in peaq_run_pair
-  DevBuf d_raw[2], d_48[2], d_res;
-  const size_t bytes = stride * channels * sizeof(float);
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(d_48[i].reserve(bytes));
-    HIP_TRY(hipMemset(d_48[i].p, 0, bytes));
-    if (!n[i]) continue;
-    HIP_TRY(d_raw[i].reserve(n[i] * channels * sizeof(float)));
-    HIP_TRY(hipMemcpy(d_raw[i].p, src[i], n[i] * channels * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = peaq_batch_resample(c, channels, rate, 1, d_raw[i].as<float>(), n[i], nullptr, (uint32_t)n[i],
-                                     d_48[i].as<float>(), stride, nullptr, nullptr))
-      return rc;
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (int rc = peaq_batch_run(c, advanced, channels, level_db, 1, d_48[0].as<float>(), d_48[1].as<float>(), stride, len,
-                              len + 1, 0, d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  return PEAQ_OK;
+  // (the playback level is not looked at here: peaq_run_pair, which a rate of 48000 goes to, does not either)
+  if (int rc = check_pair_args("peaq_run_pair_rate", c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
+  PairBuffers in;
+  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  return score_one_pair(c, advanced, channels, level_db, in.d(0), in.d(1), in.stride, in.len[0], in.len[1], out);
 }
