@@ -16,6 +16,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    GAIN_PER_CHANNEL, GAIN_F_SILENT, GAIN_F_NONFINITE, GAIN_F_ZERO, GAIN_F_RANGE,
                    SubDelay, refine_delay, cut_shifted, subsample_tables, subdelay_workspace_bytes, SUBDELAY_DTYPE, SUB_STEPS,
                    SUB_LAGS, SUB_HALF, SUB_F_NONE, SUB_F_EDGE,
+                   Drift, estimate_drift, cut_drift, drift_lengths, drift_fit, drift_index, drift_windows, drift_workspace_bytes,
+                   DRIFT_DTYPE, DRIFT_F_NONE, DRIFT_F_RANGE, DRIFT_WINDOW, DRIFT_MIN_CORR, DRIFT_MAX_E, DRIFT_MAX_WINDOWS,
                    PCM_FORMATS, PCM_DTYPES,
                    batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
@@ -32,4 +34,7 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
            "SubDelay", "refine_delay", "cut_shifted", "subsample_tables", "subdelay_workspace_bytes", "SUBDELAY_DTYPE", "SUB_STEPS",
            "SUB_LAGS", "SUB_HALF", "SUB_F_NONE", "SUB_F_EDGE",
+           "Drift", "estimate_drift", "cut_drift", "drift_lengths", "drift_fit", "drift_index", "drift_windows",
+           "drift_workspace_bytes", "DRIFT_DTYPE", "DRIFT_F_NONE", "DRIFT_F_RANGE", "DRIFT_WINDOW", "DRIFT_MIN_CORR",
+           "DRIFT_MAX_E", "DRIFT_MAX_WINDOWS",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

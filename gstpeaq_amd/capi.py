@@ -69,6 +69,21 @@ SUBDELAY_DTYPE = np.dtype([("lag", "<i4"), ("q", "<i4"), ("frac", "<f8"), ("peak
                            ("reserved", "<u4")])
 
 
+class Drift(C.Structure):
+    """mirrors peaq_drift (include/peaq_amd.h)"""
+    _fields_ = [("lag0", C.c_int32), ("flags", C.c_uint32), ("a", C.c_double), ("e", C.c_double), ("ppm", C.c_double),
+                ("resid_rms", C.c_double), ("n_windows", C.c_uint32), ("n_valid", C.c_uint32)]
+
+
+# PEAQ_DRIFT_* (include/peaq_amd.h), the record as a numpy structured dtype, and this binding's defaults
+DRIFT_F_NONE, DRIFT_F_RANGE = 1, 2
+DRIFT_MIN_WINDOW, DRIFT_MAX_WINDOW, DRIFT_MAX_WINDOWS, DRIFT_MAX_E = 4096, 1 << 20, 4096, 1e-3
+DRIFT_WINDOW, DRIFT_MIN_CORR = 32768, 0.5
+DRIFT_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("a", "<f8"), ("e", "<f8"), ("ppm", "<f8"), ("resid_rms", "<f8"),
+                        ("n_windows", "<u4"), ("n_valid", "<u4")])
+DELAY_DTYPE = np.dtype([("lag", "<i4"), ("reserved", "<i4"), ("peak", "<f8"), ("runner_up", "<f8"), ("norm", "<f8")])
+
+
 class FrameTrace(C.Structure):
     """mirrors peaq_frame_trace (include/peaq_amd.h)"""
     _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
@@ -279,6 +294,26 @@ def load_library():
         L.peaq_run_pair_subsample.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_double, fp,
                                               C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(SubDelay),
                                               C.POINTER(Gain), dp]
+    if hasattr(L, "peaq_batch_cut_drift"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        i32p = C.POINTER(C.c_int32)
+        L.peaq_drift_size.restype = C.c_size_t
+        L.peaq_drift_size.argtypes = []
+        L.peaq_drift_fit.argtypes = [dp, dp, C.POINTER(C.c_uint8), C.c_size_t, dp, dp]
+        L.peaq_drift_index.restype = None
+        L.peaq_drift_index.argtypes = [C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), i32p]
+        L.peaq_drift_lengths.restype = None
+        L.peaq_drift_lengths.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+        L.peaq_drift_windows.restype = C.c_uint32
+        L.peaq_drift_windows.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.peaq_drift_workspace_bytes.restype = C.c_size_t
+        L.peaq_drift_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+        L.peaq_batch_estimate_drift.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32, i32p,
+                                                C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, vp, vp,
+                                                C.POINTER(Drift), vp]
+        L.peaq_batch_cut_drift.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, dp, dp, vp, C.c_size_t, vp]
+        L.peaq_run_pair_drift.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_double, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Drift),
+                                          C.POINTER(Gain), dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -860,20 +895,155 @@ def cut_shifted(ctx, x, skip, n_keep, q, n_in=None, out=None, stream=None):
     return out
 
 
-def _need_align(subsample, align):
+def drift_fit(d, x, valid=None):
+    """(a, e, n_valid): the Theil-Sen line through the valid points (peaq_drift_fit, host arithmetic, no GPU)"""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    assert d.ndim == 1 and d.shape == x.shape
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(valid, dtype=np.uint8)
+        assert v.shape == d.shape
+    a, e = C.c_double(0), C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    n = load_library().peaq_drift_fit(d.ctypes.data_as(dp), x.ctypes.data_as(dp),
+                                      v.ctypes.data_as(C.POINTER(C.c_uint8)) if v is not None else None, len(d),
+                                      C.byref(a), C.byref(e))
+    _check(min(n, 0))
+    return a.value, e.value, n
+
+
+def drift_index(a, e, i):
+    """(m, phi): where output i of the drift cut reads (peaq_drift_index, host arithmetic, no GPU)"""
+    m, phi = C.c_int64(0), C.c_int32(0)
+    load_library().peaq_drift_index(float(a), float(e), int(i), C.byref(m), C.byref(phi))
+    return m.value, phi.value
+
+
+def drift_lengths(lag0, a, e, n_ref, n_test):
+    """(skip_ref, skip_test, n_keep) for one pair's lag and line (peaq_drift_lengths, host arithmetic, no GPU)"""
+    sr, st, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    load_library().peaq_drift_lengths(int(lag0), float(a), float(e), int(n_ref), int(n_test), C.byref(sr), C.byref(st),
+                                      C.byref(n))
+    return sr.value, st.value, n.value
+
+
+def drift_windows(lag0, n_ref, n_test, window=DRIFT_WINDOW):
+    """whole windows of one pair's aligned part (peaq_drift_windows)"""
+    return int(load_library().peaq_drift_windows(int(lag0), int(n_ref), int(n_test), int(window)))
+
+
+def drift_workspace_bytes(channels, n_pairs, window, w_max):
+    """the two staging buffers of estimate_drift for a shape (peaq_drift_workspace_bytes)"""
+    return int(load_library().peaq_drift_workspace_bytes(int(channels), int(n_pairs), int(window), int(w_max)))
+
+
+def _drift_window(drift):
+    """the window of a `drift=` keyword: True is the default window"""
+    return DRIFT_WINDOW if drift is True else int(drift)
+
+
+def estimate_drift(ctx, ref, test, lags, n_ref=None, n_test=None, window=DRIFT_WINDOW, R=None, min_corr=DRIFT_MIN_CORR,
+                   max_e=DRIFT_MAX_E, stream=None):
+    """Every pair's delay as a line a + e i in the coordinates its lag aligns (peaq_batch_estimate_drift): ref/test CUDA
+    float32 [n_pairs, n_samples, channels], lags as estimate_delay's (over the whole signals), n_ref/n_test optional
+    per-pair lengths.  window: samples per window; R: the windows' max_lag (default min(window // 4, 1024)).  Returns a
+    dict of numpy arrays [n_pairs]: lag0, flags (DRIFT_F_*), a, e, ppm, resid_rms, n_windows, n_valid, and `windows`:
+    the per-window records as a dict of arrays [n_pairs, w_max] (lag, peak, runner_up, norm of the delay records; q,
+    sub_peak, c0, sub_flags of the sub-delay records).  Blocks until the records are there."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    a_lag = np.ascontiguousarray(lags, dtype=np.int32)
+    assert a_lag.shape == (n_pairs,)
+    window = int(window)
+    R = min(window // 4, 1024) if R is None else int(R)
+    L = ctx.L
+    assert L.peaq_drift_size() == C.sizeof(Drift) == DRIFT_DTYPE.itemsize
+    w_max = max([1] + [int(L.peaq_drift_windows(int(a_lag[p]), int(stride if a_ref is None else a_ref[p]),
+                                                int(stride if a_test is None else a_test[p]), window))
+                       for p in range(n_pairs)])
+    with _torch_stream(stream):
+        d_dl = torch.zeros((max(n_pairs, 1), w_max, C.sizeof(Delay)), dtype=torch.uint8, device=ref.device)
+        d_sb = torch.zeros((max(n_pairs, 1), w_max, C.sizeof(SubDelay)), dtype=torch.uint8, device=ref.device)
+    out = np.zeros(max(n_pairs, 1), dtype=DRIFT_DTYPE)
+    u32p = C.POINTER(C.c_uint32)
+    _check(L.peaq_batch_estimate_drift(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()),
+                                       stride, a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                       a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                       a_lag.ctypes.data_as(C.POINTER(C.c_int32)), window, R, float(min_corr), float(max_e),
+                                       w_max, C.c_void_p(d_dl.data_ptr()), C.c_void_p(d_sb.data_ptr()),
+                                       out.ctypes.data_as(C.POINTER(Drift)), _stream_ptr(stream)))
+    _sync_stream(stream, ref.device)
+    res = {k: np.ascontiguousarray(out[k][:n_pairs]) for k in DRIFT_DTYPE.names}
+    dl = d_dl.cpu().numpy()[:n_pairs].copy().view(DELAY_DTYPE)[:, :, 0]
+    sb = d_sb.cpu().numpy()[:n_pairs].copy().view(SUBDELAY_DTYPE)[:, :, 0]
+    res["windows"] = dict(lag=np.ascontiguousarray(dl["lag"]), peak=np.ascontiguousarray(dl["peak"]),
+                          runner_up=np.ascontiguousarray(dl["runner_up"]), norm=np.ascontiguousarray(dl["norm"]),
+                          q=np.ascontiguousarray(sb["q"]), sub_peak=np.ascontiguousarray(sb["peak"]),
+                          c0=np.ascontiguousarray(sb["c0"]), sub_flags=np.ascontiguousarray(sb["flags"]))
+    return res
+
+
+def cut_drift(ctx, x, skip, n_keep, a, e, n_in=None, out=None, stream=None):
+    """cut along every pair's line (peaq_batch_cut_drift): out[p, i, c] = float32(sum_o shift_tab[phi_i][o]
+    float64(x[p, skip[p] + i + m_i + o, c])), o = -32 .. 32, (m_i, phi_i) = drift_index(a[p], e[p], i); samples outside
+    [0, n_in[p]) (without n_in: the buffer) contribute nothing; a[p] == e[p] == 0 moves the bits.  out as for cut.
+    Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    a_a = np.ascontiguousarray(a, dtype=np.float64)
+    a_e = np.ascontiguousarray(e, dtype=np.float64)
+    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,)
+    assert a_a.shape == (n_pairs,) and a_e.shape == (n_pairs,)
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    _check(ctx.L.peaq_batch_cut_drift(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
+                                      a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), a_a.ctypes.data_as(dp),
+                                      a_e.ctypes.data_as(dp), C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
+
+
+def _need_align(subsample, align, drift=False):
+    if subsample and drift:
+        raise PeaqError("drift= and subsample=True exclude each other: the line's offset a carries the sub-sample part")
     if subsample and align is None:
         raise PeaqError("subsample=True requires align= (a max_lag): the sub-sample estimate refines an integer lag")
+    if drift and align is None:
+        raise PeaqError("drift= requires align= (a max_lag): the line is fitted around an integer lag")
 
 
 def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-          subsample=False):
+          subsample=False, drift=False):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
     gain: 'lsq' 'rms' 'polarity': the test signal's gain is measured over that part and applied in its cut
     (measure_gain, cut_scaled); the record tensor is kept as align.last_gain.
     subsample: the sub-sample part of each pair's delay is estimated around its lag (refine_delay, records kept as
     align.last_subdelay) and the test signal is cut through the shift filter (cut_shifted); a gain is then measured on
     the two CUT buffers and applied into a further buffer.
+    drift: True or a window: each pair's delay is fitted as a line around its lag (estimate_drift, records kept as
+    align.last_drift), both signals are cut to drift_lengths and the test signal is resampled along the line
+    (cut_drift); a gain is then measured on the two CUT buffers, as with subsample, which drift excludes.
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
+    if drift:
+        return _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db,
+                            _drift_window(drift), subsample)
     n_pairs, stride, _ = ref.shape
     assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
     a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
@@ -909,15 +1079,47 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None,
     return bufs[0], bufs[1], n, n.copy()
 
 
+def _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window, subsample=False):
+    """align(..., drift=window)"""
+    if subsample:
+        _need_align(True, 0, True)
+    import torch
+    n_pairs, stride, _ = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
+    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
+    dr = estimate_drift(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
+    align.last_drift = dr
+    cuts = np.array([drift_lengths(int(lags[p]), dr["a"][p], dr["e"][p], int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)],
+                    dtype=np.uint32).reshape(n_pairs, 3)
+    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
+    with _torch_stream(stream):
+        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
+                for _ in range(3 if gain is not None else 2)]
+    n = np.ascontiguousarray(cuts[:, 2])
+    cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
+    cut_drift(ctx, test, cuts[:, 1], n, dr["a"], dr["e"], n_in=a_test, out=bufs[1], stream=stream)
+    if gain is not None:
+        rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
+                              per_channel=gain_per_channel, stream=stream)
+        cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
+        align.last_gain = rec
+        return bufs[0], bufs[2], n, n.copy()
+    return bufs[0], bufs[1], n, n.copy()
+
+
 def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
-             subsample=False):
+             subsample=False, drift=False):
     """the `align=`, `gain=` and `subsample=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without
     align: lags of 0), then refine, match and cut"""
-    _need_align(subsample, max_lag)
+    _need_align(subsample, max_lag, drift)
     if max_lag is not None:
         lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
     else:
         lags = np.zeros(ref.shape[0], dtype=np.int32)
+    if drift:
+        return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
+                     max_gain_db=max_gain_db, drift=drift)
     if subsample:
         return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
                      max_gain_db=max_gain_db, subsample=True)
@@ -929,8 +1131,10 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
               stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-              subsample=False):
+              subsample=False, drift=False):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    drift: True or a window, with align: every pair's delay is fitted as a line and the test signal is resampled along
+    it (estimate_drift, cut_drift; align.last_drift); a gain is then measured after that cut.  Excludes subsample.
     subsample: with align, the sub-sample part of every pair's delay is estimated and removed from the test signal too
     (refine_delay, cut_shifted; align.last_subdelay); a gain is then measured after the shift.
     gain: 'lsq' 'rms' 'polarity': the test signal's level (polarity) is matched to the reference's over the common part,
@@ -943,8 +1147,11 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align)
-    if subsample:
+    _need_align(subsample, align, drift)
+    if drift:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            drift=drift)
+    elif subsample:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
                                             subsample=True)
     elif gain is not None:
@@ -1162,16 +1369,31 @@ def _subdelay_dict(rec):
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
-             max_gain_db=40.0, subsample=False):
+             max_gain_db=40.0, subsample=False, drift=False):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
-    the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`."""
+    the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`.
+    drift: True or a window, with align: peaq_run_pair_drift; the result dict carries the line's record as `drift`."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
-    _need_align(subsample, align)
+    _need_align(subsample, align, drift)
+    if drift:                                          # peaq_run_pair_drift; the records as `delay`, `drift`, `gain`
+        rec, drec, grec = Delay(), Drift(), Gain()
+        _check(ctx.L.peaq_run_pair_drift(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
+                                         _drift_window(drift), gain_mode(gain, gain_per_channel), float(max_gain_db),
+                                         ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                         test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
+                                         C.byref(drec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["drift"] = dict(lag0=int(drec.lag0), flags=int(drec.flags), a=drec.a, e=drec.e, ppm=drec.ppm,
+                            resid_rms=drec.resid_rms, n_windows=int(drec.n_windows), n_valid=int(drec.n_valid))
+        if gain is not None:
+            res["gain"] = _gain_dict(grec)
+        return res
     if subsample:                                      # peaq_run_pair_subsample; the records as `delay`, `subdelay`, `gain`
         rec, srec, grec = Delay(), SubDelay(), Gain()
         _check(ctx.L.peaq_run_pair_subsample(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),

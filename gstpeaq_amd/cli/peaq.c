@@ -546,6 +546,10 @@ usage (const char *prog)
       "  --align-subsample[=SAMPLES] --align, and the sub-sample part of the delay too: estimated on a grid of 1/256\n"
       "                sample and removed from the test signal by a 65-tap shift filter; prints the fraction beside\n"
       "                the lag; --match-gain then measures after the shift (the plain one-call mode; not with --list)\n"
+      "  --align-drift[=WINDOW] --align, and a steadily growing delay too (a second clock): the delay of every WINDOW\n"
+      "                samples (4096..1048576, default 32768) is measured, one line fitted through them and the test\n"
+      "                signal resampled along it; prints the line; excludes --align-subsample, which it subsumes\n"
+      "                (the plain one-call mode; not with --list, --interval or --trace)\n"
       "  --match-gain[=lsq|rms|polarity] match the test file's level (polarity) to the reference's on the GPU, after\n"
       "                --align if given, and print the gain applied (default lsq; the plain one-call mode and --list;\n"
       "                not with --interval or --trace)\n"
@@ -637,6 +641,8 @@ main (int argc, char **argv)
   uint32_t align_lag = 0;       /* != 0: --align, peaq_run_pair_aligned */
   int subsample = 0;            /* --align-subsample: peaq_run_pair_subsample (implies --align) */
   peaq_subdelay subdelay;
+  uint32_t drift_window = 0;    /* != 0: --align-drift, peaq_run_pair_drift (implies --align) */
+  peaq_drift drift;
   peaq_delay delay;
   peaq_gain gain;
   int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
@@ -686,6 +692,21 @@ main (int argc, char **argv)
       }
       subsample = 1;
       align_lag = (uint32_t) v;
+    }
+    else if (!strcmp (argv[i], "--align-drift")) {
+      drift_window = 32768;
+      if (!align_lag)
+        align_lag = 4096;
+    } else if (!strncmp (argv[i], "--align-drift=", 14)) {
+      char *end;
+      const long v = strtol (argv[i] + 14, &end, 10);
+      if (*end || end == argv[i] + 14 || v < 4096 || v > 1048576) {
+        fprintf (stderr, "Failed to initialize: invalid drift window %s (4096 .. 1048576 samples)\n", argv[i] + 14);
+        return 1;
+      }
+      drift_window = (uint32_t) v;
+      if (!align_lag)
+        align_lag = 4096;
     }
     else if (!strcmp (argv[i], "--match-gain") || !strcmp (argv[i], "--match-gain=lsq"))
       gain_mode = PEAQ_GAIN_LSQ;
@@ -742,6 +763,18 @@ main (int argc, char **argv)
     gain_mode |= PEAQ_GAIN_PER_CHANNEL;
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
+  if (drift_window && subsample) {
+    fprintf (stderr, "Failed to initialize: --align-drift and --align-subsample exclude each other: the line's offset carries the sub-sample part\n");
+    return 1;
+  }
+  if (drift_window && list_path) {
+    fprintf (stderr, "Failed to initialize: --align-drift is not taken with --list: the host-fed path does not take it yet (whole-sample --align only)\n");
+    return 1;
+  }
+  if (drift_window && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --align-drift belongs to the plain one-call mode (not with --interval or --trace)\n");
     return 1;
   }
   if (subsample && list_path) {
@@ -857,6 +890,20 @@ main (int argc, char **argv)
     if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
+    } else if (drift_window) {
+      char text[256];
+      if (peaq_run_pair_drift (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, drift_window,
+              gain_mode, max_gain_db, ref.samples, ref.frames, test.samples, test.frames, &delay, &drift, &gain, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d %+.4f samples, drift %+.2f ppm (%u of %u windows%s)\n", (int) delay.lag, drift.a, drift.ppm,
+          (unsigned) drift.n_valid, (unsigned) drift.n_windows,
+          (drift.flags & PEAQ_DRIFT_F_NONE) ? ", no line: too few valid windows" : (drift.flags & PEAQ_DRIFT_F_RANGE) ? ", slope out of range: not corrected" : "");
+      if (gain_mode) {
+        format_gain (text, sizeof text, &gain, ref.channels);
+        printf ("Gain: %s\n", text);
+      }
     } else if (subsample) {
       char text[256];
       if (peaq_run_pair_subsample (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, gain_mode,

@@ -1,0 +1,444 @@
+// peaq_drift.hip -- a pair's delay as one straight line a + e i: per-window delays through the aligner and the sub-sample
+// stage, the robust fit on the host, and the test signal's cut along the line (peaq_drift_fit, peaq_drift_index,
+// peaq_drift_lengths, peaq_batch_estimate_drift, peaq_batch_cut_drift, peaq_run_pair_drift; include/peaq_amd.h,
+// DESIGN.md 17).
+//
+//   drift_cut_kernel   peaq_batch_cut_drift: a workgroup owns 1024 consecutive outputs of one pair, both channels.  The
+//       outputs of a tile read the input from i0 + m_lo - 32 on, m_lo the smaller of the tile's first and last m (m is
+//       monotone in i and moves by at most 2 over 1024 outputs at |e| <= 1e-3); the workgroup stages 1024 + 64 + 4
+//       samples in LDS, the channels of a sample side by side (absent samples as zeros).  Lane l owns outputs l, l + 256,
+//       l + 512, l + 768: neighbouring lanes read neighbouring samples (one LDS read per tap fetches both channels, no
+//       bank conflicts) and, the phase stepping every 1 / (256 |e|) outputs, mostly the same tap row.  The tap row is
+//       per output: each lane loads its taps from the table in device memory (133 KB, resident in L2; the rows of a tile
+//       in the vector L1) with vector loads -- DESIGN.md 17 says why not through LDS.  Pairs with a == 0 and e == 0 take
+//       align_cut_kernel's copy (copy_run, peaq_host.h): their bits are moved.
+//   No other kernel: the estimate runs the aligner's and the sub-sample stage's kernels on copies of the windows
+//   (peaq_batch_gather, peaq_batch_estimate_delay, peaq_batch_refine_delay).
+#include "peaq_host.h"
+#include "peaq_drift_math.h"
+
+namespace {
+
+constexpr int kDrK = PEAQ_SUB_HALF;                    // taps each side
+constexpr int kDrTaps = 2 * kDrK + 1;                  // 65
+constexpr int kDrSteps = PEAQ_SUB_STEPS;               // rows of the table
+constexpr int kDrTile = 1024;                          // outputs per workgroup
+constexpr int kDrPer = 4;                              // ... per lane, 256 apart
+constexpr int kDrSpread = 4;                           // m_i - m_lo within a tile stays below this (2 at |e| = 1e-3)
+constexpr int kDrStage = kDrTile + 2 * kDrK + kDrSpread;   // staged samples
+constexpr size_t kDrStagingBudget = (size_t)1 << 30;   // estimate: pairs are taken in groups whose window copies stay below this
+static_assert(kDrTile == 256 * kDrPer, "a lane's share");
+static_assert(kDrSteps == 256, "peaq_drift_index: 256 phases per sample");
+static_assert(kDrTile * PEAQ_DRIFT_MAX_E * kDrSteps + 2 < (kDrSpread - 1) * kDrSteps, "the spread of m over a tile");
+
+struct DriftArgs {
+  size_t in_stride, out_stride; // samples per channel between pairs
+  const uint32_t* n_in;         // device [n_pairs]
+  const uint32_t* skip;
+  const uint32_t* n_keep;
+  const double* a;
+  const double* e;
+  int channels;
+};
+
+template <int C>
+__device__ __forceinline__ void dr_cut(const DriftArgs& args, const float* __restrict__ in, float* __restrict__ out,
+                                       const double* __restrict__ tab, float* lds, double a, double e) {
+  const unsigned pair = blockIdx.y;
+  const long long n_in = args.n_in[pair], n_keep = args.n_keep[pair];
+  const long long i0 = (long long)blockIdx.x * kDrTile;            // the tile's first output (below n_keep)
+  const long long i_last = min(i0 + kDrTile, n_keep) - 1;          // ... and its last
+  long long m_a, m_b;
+  int phi;
+  drift_index(a, e, i0, &m_a, &phi);
+  drift_index(a, e, i_last, &m_b, &phi);
+  const long long m_lo = min(m_a, m_b);
+  const long long s0 = (long long)args.skip[pair] + i0 + m_lo - kDrK;   // input sample under staged position 0
+  const float* __restrict__ src = in + (size_t)pair * args.in_stride * C;
+  // ---- stage: consecutive lanes read consecutive floats; staged sample v, channel c at lds[C v + c] ----
+  for (int f = threadIdx.x; f < kDrStage * C; f += 256) {
+    const long long s = s0 + (C == 2 ? f >> 1 : f);
+    lds[f] = (s >= 0 && s < n_in) ? src[(size_t)s * C + (C == 2 ? f & 1 : 0)] : 0.f;
+  }
+  __syncthreads();
+  // ---- output j of the lane: i = i0 + l + 256 j; tap o of it meets staged position l + 256 j + (m_i - m_lo) + o ----
+  const double* __restrict__ row[kDrPer];
+  const float* x[kDrPer];
+#pragma unroll
+  for (int j = 0; j < kDrPer; ++j) {
+    const long long i = min(i0 + (long long)threadIdx.x + 256 * j, i_last);   // (an output past n_keep: computed, not stored)
+    long long m;
+    drift_index(a, e, i, &m, &phi);
+    const int dm = max(0, min((int)(m - m_lo), kDrSpread - 1));    // (0 .. 2 by the bound on e: the clamp never acts)
+    row[j] = tab + (size_t)(phi + kDrSteps / 2) * kDrTaps;
+    x[j] = lds + C * ((int)(i - i0) + dm);
+  }
+  double acc[C][kDrPer];
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+#pragma unroll
+    for (int j = 0; j < kDrPer; ++j) acc[c][j] = 0.;
+#pragma unroll 5
+  for (int o = 0; o < kDrTaps; ++o) {                              // o = -32 .. 32 of the definition, in that order
+#pragma unroll
+    for (int j = 0; j < kDrPer; ++j) {
+      const double h = row[j][o];
+      if (C == 2) {
+        const float2 v = *reinterpret_cast<const float2*>(x[j] + 2 * o);
+        acc[0][j] = __builtin_fma(h, (double)v.x, acc[0][j]);
+        acc[C - 1][j] = __builtin_fma(h, (double)v.y, acc[C - 1][j]);
+      } else {
+        acc[0][j] = __builtin_fma(h, (double)x[j][o], acc[0][j]);
+      }
+    }
+  }
+  // ---- consecutive lanes store consecutive samples ----
+  float* __restrict__ dst = out + (size_t)pair * args.out_stride * C;
+  const bool pairs8 = C == 2 && ((uintptr_t)dst & 7) == 0;         // (uniform) both channels in one store
+#pragma unroll
+  for (int j = 0; j < kDrPer; ++j) {
+    const long long i = i0 + (long long)threadIdx.x + 256 * j;
+    if (i >= n_keep) continue;
+    if (pairs8) {
+      reinterpret_cast<float2*>(dst)[i] = {(float)acc[0][j], (float)acc[C - 1][j]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) dst[(size_t)i * C + c] = (float)acc[c][j];
+    }
+  }
+}
+
+// (the buffers and the table as parameters of their own, as frac_cut_kernel's)
+__global__ __launch_bounds__(256, 4) void drift_cut_kernel(const DriftArgs args, const float* __restrict__ a_in,
+                                                        float* __restrict__ a_out, const double* __restrict__ shift_tab) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * kDrStage];
+  const unsigned pair = blockIdx.y;
+  const uint32_t n_keep = args.n_keep[pair];
+  if ((unsigned long long)blockIdx.x * kDrTile >= n_keep) return;  // (the whole workgroup)
+  const double a = args.a[pair], e = args.e[pair];
+  if (a == 0. && e == 0.) {                            // (uniform) peaq_batch_cut's copy of this tile's floats
+    const size_t count = (size_t)n_keep * args.channels;
+    const float* __restrict__ src = a_in + ((size_t)pair * args.in_stride + args.skip[pair]) * args.channels;
+    float* __restrict__ dst = a_out + (size_t)pair * args.out_stride * args.channels;
+    for (int sub = 0; sub < args.channels; ++sub)      // a tile is `channels` units of 256 x 4 floats
+      copy_run(src, dst, count, ((size_t)blockIdx.x * args.channels + sub) * 256, blockIdx.x == 0 && sub == 0, CopyBits());
+    return;
+  }
+  if (args.channels == 2)
+    dr_cut<2>(args, a_in, a_out, shift_tab, lds, a, e);
+  else
+    dr_cut<1>(args, a_in, a_out, shift_tab, lds, a, e);
+}
+
+#pragma clang fp contract(off)                        // host arithmetic from here on: every operation rounded on its own
+
+struct DriftParams {
+  uint32_t window, R;
+  double min_corr, max_e;
+};
+
+int check_drift_params(const std::string& w, const DriftParams& p) {
+  if (p.window < PEAQ_DRIFT_MIN_WINDOW || p.window > PEAQ_DRIFT_MAX_WINDOW)
+    return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(p.window) + " is outside 4096 .. 1048576");
+  if (p.R < 1 || p.R > p.window / 4 || p.R > 16384)
+    return fail(PEAQ_ERR_ARG, w + ": R " + std::to_string(p.R) + " is outside 1 .. min (window / 4, 16384) = " +
+                                  std::to_string(std::min<uint32_t>(p.window / 4, 16384)));
+  if (!(p.min_corr >= 0. && p.min_corr <= 1.))
+    return fail(PEAQ_ERR_ARG, w + ": min_corr " + std::to_string(p.min_corr) + " is outside 0 .. 1");
+  if (!(p.max_e > 0. && p.max_e <= PEAQ_DRIFT_MAX_E))
+    return fail(PEAQ_ERR_ARG, w + ": max_e " + std::to_string(p.max_e) + " is outside (0, 0.001]");
+  return PEAQ_OK;
+}
+
+// the record of one pair from its windows' records
+void drift_record(int32_t lag0, uint32_t W, const peaq_delay* dl, const peaq_subdelay* sb, const DriftParams& p,
+                  peaq_drift* out) {
+  std::vector<double> d(W), x(W);
+  std::vector<uint8_t> valid(W);
+  for (uint32_t w = 0; w < W; ++w) {
+    d[w] = (double)dl[w].lag + (double)sb[w].q / 256.;
+    x[w] = (double)w * p.window + (double)(p.window / 2);
+    valid[w] = std::isfinite(dl[w].norm) && dl[w].norm > 0. && sb[w].flags == 0 &&
+               std::fabs(dl[w].peak) >= p.min_corr * dl[w].norm;
+  }
+  peaq_drift r;
+  std::memset(&r, 0, sizeof r);
+  r.lag0 = lag0;
+  r.n_windows = W;
+  r.n_valid = (uint32_t)theil_sen(d.data(), x.data(), valid.data(), W, &r.a, &r.e);
+  if (r.n_valid < 3) {
+    r.flags = PEAQ_DRIFT_F_NONE;
+  } else {
+    double ss = 0.;
+    for (uint32_t w = 0; w < W; ++w)
+      if (valid[w]) {
+        const double res = d[w] - r.a - r.e * x[w];
+        ss += res * res;
+      }
+    r.resid_rms = std::sqrt(ss / r.n_valid);
+    if (std::fabs(r.e) > p.max_e) {
+      r.flags = PEAQ_DRIFT_F_RANGE;
+      r.a = r.e = 0.;
+    }
+  }
+  r.ppm = 1e6 * r.e;
+  *out = r;
+}
+
+// pairs of a group of the estimate, and the bytes of its two staging buffers
+PairGroups drift_groups(int channels, int n_pairs, uint32_t window, uint32_t w_max) {
+  const size_t per_pair = 2 * (size_t)w_max * window * channels * sizeof(float);
+  PairGroups pg = pair_groups(per_pair, n_pairs, kDrStagingBudget);
+  pg.group = std::max(1, std::min<int>(pg.group, 65535 / (int)w_max));
+  pg.bytes = (size_t)pg.group * per_pair;
+  return pg;
+}
+
+}  // namespace
+
+extern "C" size_t peaq_drift_size(void) { return sizeof(peaq_drift); }
+
+extern "C" int peaq_drift_fit(const double* d, const double* x, const uint8_t* valid, size_t n, double* a, double* e) {
+  const std::string w("peaq_drift_fit");
+  if (!a || !e) return fail(PEAQ_ERR_ARG, w + ": a or e is NULL");
+  *a = *e = 0.;
+  if (n && (!d || !x)) return fail(PEAQ_ERR_ARG, w + ": d or x is NULL");
+  if (n > PEAQ_DRIFT_MAX_WINDOWS)
+    return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n) + " points are more than " + std::to_string(PEAQ_DRIFT_MAX_WINDOWS));
+  return (int)theil_sen(d, x, valid, n, a, e);
+}
+
+extern "C" void peaq_drift_index(double a, double e, int64_t i, int64_t* m, int32_t* phi) {
+  long long mm;
+  int pp;
+  drift_index(a, e, i, &mm, &pp);
+  if (m) *m = mm;
+  if (phi) *phi = pp;
+}
+
+extern "C" void peaq_drift_lengths(int32_t lag0, double a, double e, uint32_t n_ref, uint32_t n_test, uint32_t* skip_ref,
+                                   uint32_t* skip_test, uint32_t* n_keep) {
+  uint32_t sr, st, common;
+  peaq_aligned_lengths(lag0, n_ref, n_test, &sr, &st, &common);
+  if (skip_ref) *skip_ref = sr;
+  if (skip_test) *skip_test = st;
+  if (!n_keep) return;
+  *n_keep = drift_keep(a, e, st, common, n_test);
+}
+
+extern "C" uint32_t peaq_drift_windows(int32_t lag0, uint32_t n_ref, uint32_t n_test, uint32_t window) {
+  if (window < PEAQ_DRIFT_MIN_WINDOW || window > PEAQ_DRIFT_MAX_WINDOW) return 0;
+  uint32_t common = 0;
+  peaq_aligned_lengths(lag0, n_ref, n_test, nullptr, nullptr, &common);
+  return common / window;
+}
+
+extern "C" size_t peaq_drift_workspace_bytes(int channels, int n_pairs, uint32_t window, uint32_t w_max) {
+  if ((channels != 1 && channels != 2) || n_pairs <= 0 || n_pairs > 65535) return 0;
+  if (window < PEAQ_DRIFT_MIN_WINDOW || window > PEAQ_DRIFT_MAX_WINDOW || w_max < 1 || w_max > PEAQ_DRIFT_MAX_WINDOWS) return 0;
+  return drift_groups(channels, n_pairs, window, w_max).bytes;
+}
+
+extern "C" int peaq_batch_estimate_drift(peaq_ctx* c, int channels, int n_pairs, const float* d_ref, const float* d_test,
+                                         size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
+                                         uint32_t n_uniform, const int32_t* lag0, uint32_t window, uint32_t R,
+                                         double min_corr, double max_e, uint32_t w_max, peaq_delay* d_win_delay,
+                                         peaq_subdelay* d_win_sub, peaq_drift* out, void* stream_) {
+  const std::string w("peaq_batch_estimate_drift");
+  const DriftParams prm{window, R, min_corr, max_e};
+  if (int rc = check_drift_params(w, prm)) return rc;
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
+  if (w_max < 1 || w_max > PEAQ_DRIFT_MAX_WINDOWS)
+    return fail(PEAQ_ERR_ARG, w + ": w_max " + std::to_string(w_max) + " is outside 1 .. " + std::to_string(PEAQ_DRIFT_MAX_WINDOWS));
+  if (n_pairs > 0 && (!d_ref || !d_test || !d_win_delay || !d_win_sub)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (n_pairs > 0 && (!lag0 || !out)) return fail(PEAQ_ERR_ARG, w + ": NULL lag0 or out");
+  if ((n_ref == nullptr) != (n_test == nullptr))
+    return fail(PEAQ_ERR_ARG, w + ": n_ref and n_test must both be given or both be NULL");
+  if (int rc = check_lengths(w, n_pairs, n_ref, n_uniform, "n_ref", pair_stride, "pair_stride")) return rc;
+  if (int rc = check_lengths(w, n_pairs, n_test, n_uniform, "n_test", pair_stride, "pair_stride")) return rc;
+  const size_t np = (size_t)std::max(n_pairs, 0);
+  std::vector<uint32_t> skip_r(np), skip_t(np), W(np);
+  for (size_t p = 0; p < np; ++p) {
+    uint32_t common = 0;
+    peaq_aligned_lengths(lag0[p], n_ref ? n_ref[p] : n_uniform, n_test ? n_test[p] : n_uniform, &skip_r[p], &skip_t[p], &common);
+    W[p] = common / window;
+    if (W[p] > w_max)
+      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": " + std::to_string(W[p]) + " windows are more than w_max " +
+                                    std::to_string(w_max));
+  }
+  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
+  if (n_pairs == 0) return PEAQ_OK;
+
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIP_TRY(hipSetDevice(c->device));
+  const PairGroups pg = drift_groups(channels, n_pairs, window, w_max);
+  const size_t slots = (size_t)pg.group * w_max;       // window slots of a group: at most 65535
+  DevBuf stage[2];                                      // (the call's own: the stages it calls take the context's lock)
+  for (DevBuf& b : stage) HIP_TRY(b.reserve(pg.bytes / 2));
+  std::vector<uint32_t> src(slots), skip(slots), keep(slots);
+  std::vector<int32_t> lag(slots);
+  std::vector<peaq_delay> dl(slots);
+  std::vector<peaq_subdelay> sb(slots);
+  for (int p0 = 0; p0 < n_pairs; p0 += pg.group) {
+    const int g = std::min(pg.group, n_pairs - p0);
+    const int ns = g * (int)w_max;
+    for (int side = 0; side < 2; ++side) {
+      for (int p = 0; p < g; ++p)
+        for (uint32_t k = 0; k < w_max; ++k) {
+          const size_t s = (size_t)p * w_max + k;
+          const bool there = k < W[p0 + p];
+          src[s] = (uint32_t)p;
+          skip[s] = there ? (side ? skip_t : skip_r)[p0 + p] + k * window : 0;
+          keep[s] = there ? window : 0;
+        }
+      if (int rc = peaq_batch_gather(c, channels, g, ns, (side ? d_test : d_ref) + (size_t)p0 * pair_stride * channels,
+                                     pair_stride, src.data(), skip.data(), keep.data(), stage[side].as<float>(), window, stream))
+        return rc;
+    }
+    peaq_delay* d_dl = d_win_delay + (size_t)p0 * w_max;
+    peaq_subdelay* d_sb = d_win_sub + (size_t)p0 * w_max;
+    if (int rc = peaq_batch_estimate_delay(c, channels, ns, stage[0].as<float>(), stage[1].as<float>(), window, keep.data(),
+                                           keep.data(), 0, R, d_dl, stream))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(dl.data(), d_dl, (size_t)ns * sizeof(peaq_delay), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int s = 0; s < ns; ++s) lag[s] = dl[s].lag;
+    if (int rc = peaq_batch_refine_delay(c, channels, ns, stage[0].as<float>(), stage[1].as<float>(), window, keep.data(),
+                                         keep.data(), 0, lag.data(), d_sb, stream))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(sb.data(), d_sb, (size_t)ns * sizeof(peaq_subdelay), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));             // (the staging buffers are free again, too)
+    for (int p = 0; p < g; ++p)
+      drift_record(lag0[p0 + p], W[p0 + p], &dl[(size_t)p * w_max], &sb[(size_t)p * w_max], prm, &out[p0 + p]);
+  }
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_batch_cut_drift(peaq_ctx* c, int channels, int n_pairs, const float* d_in, size_t in_stride,
+                                    const uint32_t* n_in, const uint32_t* skip, const uint32_t* n_keep, const double* a,
+                                    const double* e, float* d_out, size_t out_stride, void* stream_) {
+  const std::string w("peaq_batch_cut_drift");
+  if (int rc = check_shape(w, channels, n_pairs)) return rc;
+  if (n_pairs > 0 && (!n_in || !skip || !n_keep || !a || !e)) return fail(PEAQ_ERR_ARG, w + ": NULL n_in, skip, n_keep, a or e");
+  uint32_t keep_max = 0;
+  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
+                                  &keep_max))
+    return rc;
+  if (int rc = check_lengths(w, n_pairs, n_in, 0, "n_in", in_stride, "in_stride")) return rc;
+  const size_t np = (size_t)std::max(n_pairs, 0);
+  const size_t words = 3 * np + (np & 1);              // the doubles behind them start on 8 bytes
+  std::vector<uint32_t> h(words + 4 * np);
+  for (size_t p = 0; p < np; ++p) {
+    if (!(std::fabs(a[p]) <= PEAQ_DRIFT_MAX_A))
+      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": a " + std::to_string(a[p]) + " is outside -1048576 .. 1048576");
+    if (!(std::fabs(e[p]) <= PEAQ_DRIFT_MAX_E))
+      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": e " + std::to_string(e[p]) + " is outside -0.001 .. 0.001");
+    h[p] = n_in[p];
+    h[np + p] = skip[p];
+    h[2 * np + p] = n_keep[p];
+    std::memcpy(&h[words + 2 * p], &a[p], sizeof(double));
+    std::memcpy(&h[words + 2 * np + 2 * p], &e[p], sizeof(double));
+  }
+  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
+  if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
+
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const double* tab = nullptr;
+  LenStage* lens = nullptr;
+  if (int rc = frac_shift_table(c, &tab, &lens)) return rc;
+  LenSlot* slot = nullptr;
+  if (int rc = lens->upload(h.data(), h.size(), stream, &slot)) return rc;
+  DriftArgs args{};
+  args.in_stride = in_stride;
+  args.out_stride = out_stride;
+  args.n_in = slot->dev.as<uint32_t>();
+  args.skip = args.n_in + np;
+  args.n_keep = args.skip + np;
+  args.a = reinterpret_cast<const double*>(args.n_in + words);
+  args.e = args.a + np;
+  args.channels = channels;
+  const unsigned tiles = (unsigned)(((uint64_t)keep_max + kDrTile - 1) / kDrTile);
+  hipLaunchKernelGGL(drift_cut_kernel, dim3(tiles, (unsigned)n_pairs), dim3(256), 0, stream, args, d_in, d_out, tab);
+  const hipError_t launched = hipGetLastError();
+  const int sent = lens->sent(slot, stream);           // (also after a failed launch: the copy into the slot is enqueued)
+  HIP_TRY(launched);
+  return sent;
+}
+
+extern "C" int peaq_run_pair_drift(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                   uint32_t window, int mode, double max_gain_db, const float* ref, size_t n_ref,
+                                   const float* test, size_t n_test, peaq_delay* delay, peaq_drift* drift, peaq_gain* gain,
+                                   peaq_result* out) {
+  const std::string w("peaq_run_pair_drift");
+  const DriftParams prm{window, std::min<uint32_t>(window / 4, 1024), 0.5, PEAQ_DRIFT_MAX_E};
+  if (int rc = check_drift_params(w, prm)) return rc;
+  if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
+  if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
+  if (gain) std::memset(gain, 0, sizeof *gain);
+  const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
+  // 1, 2: upload, rate conversion
+  PairBuffers in;
+  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  const uint32_t* len = in.len;
+  const size_t stride = in.stride;
+  // 3, 4: estimate, the line
+  DevBuf cut[2], matched, d_dl, d_sb, d_gain;
+  peaq_delay rec;
+  if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
+  if (delay) *delay = rec;
+  const uint32_t W = peaq_drift_windows(rec.lag, len[0], len[1], window);
+  peaq_drift dr;
+  std::memset(&dr, 0, sizeof dr);
+  dr.lag0 = rec.lag;
+  dr.n_windows = W;
+  dr.flags = PEAQ_DRIFT_F_NONE;
+  if (W > PEAQ_DRIFT_MAX_WINDOWS)
+    return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(W) + " windows of " + std::to_string(window) + " samples are more than " +
+                                  std::to_string(PEAQ_DRIFT_MAX_WINDOWS) + ": take a longer window");
+  if (W >= 3) {                                        // (fewer: no line whatever they measure)
+    HIP_TRY(d_dl.reserve((size_t)W * sizeof(peaq_delay)));
+    HIP_TRY(d_sb.reserve((size_t)W * sizeof(peaq_subdelay)));
+    if (int rc = peaq_batch_estimate_drift(c, channels, 1, in.d(0), in.d(1), stride, len, len + 1, 0, &rec.lag, prm.window, prm.R,
+                                           prm.min_corr, prm.max_e, W, d_dl.as<peaq_delay>(), d_sb.as<peaq_subdelay>(), &dr,
+                                           nullptr))
+      return rc;
+  }
+  if (drift) *drift = dr;
+  // 5, 6: plain cut of the reference, drift cut of the test signal
+  uint32_t skip[2], keep = 0;
+  peaq_drift_lengths(rec.lag, dr.a, dr.e, len[0], len[1], &skip[0], &skip[1], &keep);
+  size_t cstride = std::max<size_t>(keep, 2);
+  cstride += cstride & 1;
+  const size_t cbytes = cstride * channels * sizeof(float);
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(cut[i].reserve(cbytes));
+    HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
+  }
+  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), stride, &skip[0], &keep, cut[0].as<float>(), cstride, nullptr)) return rc;
+  if (int rc = peaq_batch_cut_drift(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &keep, &dr.a, &dr.e, cut[1].as<float>(),
+                                    cstride, nullptr))
+    return rc;
+  const float* scored = cut[1].as<float>();
+  // 7: the gain of the RESAMPLED test signal, applied into a second buffer
+  if (match) {
+    const uint32_t zero = 0;
+    HIP_TRY(d_gain.reserve(sizeof(peaq_gain)));
+    HIP_TRY(matched.reserve(cbytes));
+    HIP_TRY(hipMemset(matched.p, 0, cbytes));
+    if (int rc = peaq_batch_measure_gain(c, channels, 1, cut[0].as<float>(), cstride, &zero, cut[1].as<float>(), cstride, &zero,
+                                         &keep, mode, max_gain_db, d_gain.as<peaq_gain>(), nullptr))
+      return rc;
+    if (int rc = peaq_batch_cut_scaled(c, channels, 1, cut[1].as<float>(), cstride, &zero, &keep, d_gain.as<peaq_gain>(),
+                                       matched.as<float>(), cstride, nullptr))
+      return rc;
+    scored = matched.as<float>();
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
+  // 8: the one-pair path
+  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, keep, keep, out);
+}

@@ -452,6 +452,16 @@ static int frac_state(peaq_ctx* c, FracState** out) {
   return PEAQ_OK;
 }
 
+// what the drift cut (peaq_drift.hip) shares with this stage: the shift table on the context's device and the length
+// slots.  The caller holds the context's lock and has selected the device.
+int frac_shift_table(peaq_ctx* c, const double** shift, LenStage** lens) {
+  FracState* st = nullptr;
+  if (int rc = frac_state(c, &st)) return rc;
+  *shift = st->shift.as<double>();
+  *lens = &st->lens;
+  return PEAQ_OK;
+}
+
 extern "C" size_t peaq_subdelay_size(void) { return sizeof(peaq_subdelay); }
 
 extern "C" size_t peaq_subdelay_workspace_bytes(int channels, int n_pairs, uint32_t n_max) {

@@ -429,7 +429,8 @@ int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playba
  * PEAQ compares frame against frame and takes the two signals as sample-aligned (BS.1387; the reference has no
  * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
  * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only
- * here (the constant sub-sample part: "sub-sample delay on the device" further down), no drift, one lag per pair for
+ * here (the constant sub-sample part: "sub-sample delay on the device", a constant drift: "constant drift on the
+ * device", both further down; delays that are no straight line are not handled anywhere), one lag per pair for
  * all channels; level and polarity are matched by the stage further down ("level and polarity matching on the device").
  *
  *   For one pair with n_ref / n_test samples per channel:
@@ -713,9 +714,10 @@ size_t peaq_feed_matched_workspace_bytes (const peaq_feed *feed, int advanced, i
  * peaq_batch_refine_delay finds the constant sub-sample part of each pair's delay on a grid of 1 / PEAQ_SUB_STEPS
  * samples around the given integer lag, and peaq_batch_cut_shifted is peaq_batch_cut of the test signal through the
  * fractional-delay filter of that grid point.  Only the test signal is ever shifted; the reference is never changed.
- * With lag < 0 the test signal keeps skip = 0 and is still shifted by q.  Not done, here or anywhere: drift and
- * per-window delay tracks, shifts finer than the grid, and the host-fed pipelines (peaq_batch_run_host*, the CLI's
- * --list), which align to whole samples only.
+ * With lag < 0 the test signal keeps skip = 0 and is still shifted by q.  A delay that grows steadily is the next
+ * stage's ("constant drift on the device").  Not done, here or anywhere: delay tracks that are no straight line,
+ * shifts finer than the grid, and the host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to
+ * whole samples only.
  *
  *   w_H (x) = I0 (beta sqrt (1 - (x / H)^2)) / I0 (beta) for |x| < H, else 0; beta = 8.49, the converter's Kaiser window.
  *   sinc (x) = sin (pi x) / (pi x), sinc (0) = 1.  I0 is evaluated in double by the Chebyshev expansions of the Cephes
@@ -797,6 +799,108 @@ int peaq_run_pair_subsample (peaq_ctx *ctx, int advanced, int channels, double p
                              const float *ref, size_t n_ref, const float *test, size_t n_test,
                              peaq_delay *delay /* host */, peaq_subdelay *subdelay /* host */, peaq_gain *gain /* host */,
                              peaq_result *out);
+
+/* ---- constant drift on the device ------------------------------------------------
+ * Material that passed through a second clock (a DA/AD loop, a USB or Bluetooth device) has a delay that grows
+ * steadily: at 100 ppm by 48 samples over 10 s.  One lag leaves most of such an item misaligned, and PEAQ scores that as
+ * distortion.  This stage models the delay of a pair as ONE straight line, fits it robustly from per-window delays that
+ * the two stages above measure, and resamples the test signal along it through shift_tab.  Only the test signal is
+ * changed.  Not done, here or anywhere: delays that are no straight line (per-window tracks, piecewise cuts), and the
+ * host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
+ *
+ *   Coordinates.  lag0 = the pair's lag from peaq_batch_estimate_delay over the whole signals; peaq_aligned_lengths
+ *   (lag0, ...) gives skip_ref, skip_test and n_common; A_ref[i] = ref[skip_ref + i], A_test[i] = test[skip_test + i].
+ *   The model: A_test at position i + a + e i belongs to A_ref[i].
+ *   Windows.  W = n_common / window whole windows, 4096 <= window <= 2^20; window w is [w window, (w + 1) window) of
+ *   A_ref and of A_test.  Its delay record is what peaq_batch_estimate_delay writes for that pair of slices with
+ *   max_lag = R (1 <= R <= window / 4, R <= 16384), its sub-delay record what peaq_batch_refine_delay writes for the
+ *   slices and that lag: the stage copies the slices (peaq_batch_gather) and calls those two entry points, so the
+ *   records are theirs bit for bit.  d_w = lag_w + q_w / 256, x_w = w window + window / 2.
+ *   A window is valid when its norm is finite and > 0, its sub-delay flags are 0 and |peak_w| >= min_corr norm_w (peak
+ *   and norm of the DELAY record).
+ *   Fit (host, FP64, every operation rounded on its own): Theil-Sen.  e = the median of (d_j - d_i) / (x_j - x_i) over
+ *   all valid i < j; a = the median of d_w - e x_w over the valid w; a median is the middle one of the sorted doubles,
+ *   the mean of the two middle ones for an even count.  resid_rms = sqrt (sum (d_w - a - e x_w)^2 / n_valid), summed
+ *   in the order of w.  Fewer than 3 valid windows: PEAQ_DRIFT_F_NONE, a = e = 0.  |e| > max_e (0 < max_e <= 1e-3):
+ *   PEAQ_DRIFT_F_RANGE, a = e = 0 (resid_rms stays that of the fitted line).  A pair's record depends on nothing but
+ *   the pair and repeats bit for bit. */
+#define PEAQ_DRIFT_MIN_WINDOW   4096u
+#define PEAQ_DRIFT_MAX_WINDOW   (1u << 20)
+#define PEAQ_DRIFT_MAX_WINDOWS  4096u   /* windows of one pair (the fit looks at every pair of them) */
+#define PEAQ_DRIFT_MAX_E        1e-3
+#define PEAQ_DRIFT_MAX_A        1048576.   /* |a| peaq_batch_cut_drift takes */
+#define PEAQ_DRIFT_F_NONE   1   /* fewer than 3 valid windows */
+#define PEAQ_DRIFT_F_RANGE  2   /* |e| > max_e */
+typedef struct {               /* 48 bytes */
+  int32_t  lag0;               /* as given */
+  uint32_t flags;
+  double   a, e;               /* samples, samples per sample */
+  double   ppm;                /* 1e6 e */
+  double   resid_rms;          /* samples */
+  uint32_t n_windows, n_valid;
+} peaq_drift;
+size_t peaq_drift_size (void);
+/* Host only.  The fit above over the n points (d[w], x[w]) with valid[w] != 0 (valid == NULL: all); n <=
+ * PEAQ_DRIFT_MAX_WINDOWS.  Returns the number of valid points; with fewer than 3, *a = *e = 0.  PEAQ_ERR_ARG: NULL d,
+ * x, a or e, an n beyond the limit. */
+int peaq_drift_fit (const double *d, const double *x, const uint8_t *valid, size_t n, double *a, double *e);
+/* Host only.  Where output i of the drift cut reads: g = (int64) rint (256 fma (e, (double) i, a)), to nearest even;
+ * *m = floor ((g + 128) / 256); *phi = g - 256 m, in [-128, 127].  The device evaluates the same FP64 operations. */
+void peaq_drift_index (double a, double e, int64_t i, int64_t *m, int32_t *phi);
+/* Host only.  skip_ref, skip_test: peaq_aligned_lengths (lag0, ...)'s.  *n_keep: the largest count <= n_common such
+ * that skip_test + i + m_i < n_test for every i < n_keep, i.e. no kept output is centred behind the test signal's end
+ * (i + m_i never decreases with i, so these are the first n_keep).  An output centred before the test signal's first
+ * sample -- at most the first -a of them, and only where skip_test < -a -- is kept: its taps outside the signal
+ * contribute nothing, as in peaq_batch_cut_shifted. */
+void peaq_drift_lengths (int32_t lag0, double a, double e, uint32_t n_ref, uint32_t n_test,
+                         uint32_t *skip_ref, uint32_t *skip_test, uint32_t *n_keep);
+/* Windows of a pair: n_common / window (0 for a window out of range). */
+uint32_t peaq_drift_windows (int32_t lag0, uint32_t n_ref, uint32_t n_test, uint32_t window);
+/* Batch layout and lengths as for peaq_batch_estimate_delay; lag0: host array.  d_win_delay / d_win_sub: device arrays
+ * [n_pairs][w_max] that receive the per-window records, row p holding peaq_drift_windows of pair p and, behind them,
+ * the records of empty slices (lag 0, norm 0; PEAQ_SUB_F_NONE).  out: HOST array of n_pairs records.  The call BLOCKS: it
+ * copies the slices into two staging buffers of its own (peaq_drift_workspace_bytes; allocated and freed by the call),
+ * runs peaq_batch_estimate_delay on them, reads the lags, runs peaq_batch_refine_delay, reads both record arrays and
+ * fits.  Pairs are taken in groups of at most 1 GiB of staging (or one pair's), which is fewer than 65535 window slots.
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: a window, R, min_corr (0 ..
+ * 1) or max_e out of range, a w_max of 0, beyond PEAQ_DRIFT_MAX_WINDOWS or below a pair's windows, channels other than
+ * 1 or 2, more than 65535 pairs, NULL buffers or arrays, n_ref without n_test, a pair longer than pair_stride. */
+int peaq_batch_estimate_drift (peaq_ctx *ctx, int channels, int n_pairs,
+                               const float *d_ref, const float *d_test, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                               const int32_t *lag0 /* host */, uint32_t window, uint32_t R, double min_corr, double max_e,
+                               uint32_t w_max, peaq_delay *d_win_delay /* device */, peaq_subdelay *d_win_sub /* device */,
+                               peaq_drift *out /* host, [n_pairs] */, void *stream);
+/* The two staging buffers of a call, in bytes: 2 x window x channels x 4 per window slot, w_max slots per pair, the
+ * pairs of one group.  The aligner's and the sub-sample stage's own scratch for the slices (peaq_align_workspace_bytes,
+ * peaq_subdelay_workspace_bytes with n_pairs x w_max "pairs" of `window` samples) comes on top.  0 for arguments the
+ * call would refuse. */
+size_t peaq_drift_workspace_bytes (int channels, int n_pairs, uint32_t window, uint32_t w_max);
+/* peaq_batch_cut of the test signal along each pair's line (a[p], e[p]: host arrays of doubles):
+ * out[p][i][c] = (float) sum_{o = -32 .. 32} shift_tab[phi_i][o] (double) in[p][skip[p] + i + m_i + o][c] for
+ * i < n_keep[p], (m_i, phi_i) = peaq_drift_index (a[p], e[p], i): fused multiply-adds in the order o = -32 .. 32 in
+ * FP64, rounded once to FP32.  A tap whose index falls outside [0, n_in[p]) contributes nothing.  Samples of d_out past
+ * n_keep[p] are left as they were.  With e[p] == 0 and a[p] = q / 256, q in [-128, 127], the output is bit for bit
+ * peaq_batch_cut_shifted's; a pair with a[p] == 0 and e[p] == 0 has its bits moved as they are (peaq_batch_cut's) and, like
+ * peaq_batch_cut_shifted at q == 0, does not look at n_in[p]: it copies what the buffer holds.
+ * Refusals as peaq_batch_cut_shifted's, and: an a or e that is not finite, |a| > PEAQ_DRIFT_MAX_A, |e| >
+ * PEAQ_DRIFT_MAX_E, NULL a or e. */
+int peaq_batch_cut_drift (peaq_ctx *ctx, int channels, int n_pairs,
+                          const float *d_in, size_t in_stride, const uint32_t *n_in /* host */,
+                          const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                          const double *a /* host */, const double *e /* host */,
+                          float *d_out, size_t out_stride, void *stream);
+/* peaq_run_pair_subsample with this stage in the sub-sample stage's place, in this order: upload; conversion to 48 kHz
+ * if rate != 48000; estimate (max_lag at least 1); peaq_batch_estimate_drift (window, R = min (window / 4, 1024),
+ * min_corr 0.5, max_e 1e-3); peaq_drift_lengths; plain cut of the reference to n_keep; drift cut of the test signal; if
+ * mode is not PEAQ_GAIN_OFF, the gain measured AFTER the drift cut on the two cut buffers and applied into a second
+ * buffer; the one-pair path.  A flagged record (a = e = 0) scores what peaq_run_pair_aligned scores.  delay, drift and
+ * gain (host) may be NULL. */
+int peaq_run_pair_drift (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                         uint32_t max_lag, uint32_t window, int mode, double max_gain_db,
+                         const float *ref, size_t n_ref, const float *test, size_t n_test,
+                         peaq_delay *delay /* host */, peaq_drift *drift /* host */, peaq_gain *gain /* host */,
+                         peaq_result *out);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
  * Runs a fixed FP64 multiply-add kernel (ONE wave per SIMD, sixteen independent chains; `iterations` x 512
