@@ -152,6 +152,22 @@ def mov_trace_advanced(ref, test, n_blocks, n_frames, level=92.0):
             dict(zip(MOV_TRACE_ADV_FRAME, np.moveaxis(of, 2, 0))))
 
 
+BAND_POWER_FLOOR = 1e-12        # orc_fftmodel_group (fftearmodel.c:604-620): no band of a grouped spectrum goes below
+
+
+def frontend_records(bands, ref, test, n_frames, level=92.0):
+    """the per-frame records of the FFT ear model's front end, in the layout of the HIP front end's:
+    -> np [frames, channels, 576]"""
+    L = lib()
+    ch = ref.shape[1]
+    out = np.zeros((n_frames, ch, 576))
+    L.orc_flat_frontend_records.argtypes = [C.c_int, C.c_int, C.c_double, _fp, C.c_size_t, _fp, C.c_size_t, C.c_int, _dp]
+    r = np.ascontiguousarray(ref, dtype=np.float32)
+    t = np.ascontiguousarray(test, dtype=np.float32)
+    L.orc_flat_frontend_records(bands, ch, level, _ptr(r, _fp), len(r), _ptr(t, _fp), len(t), n_frames, _ptr(out, _dp))
+    return out
+
+
 def fftear(bands, x, n_frames, hop, level=92.0):
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = dict(power=np.zeros((n_frames, 1025)), weighted=np.zeros((n_frames, 1025)),

@@ -1,7 +1,8 @@
 """-m gpu: input classes beyond a clean seeded pair (tests/cases.py:input_class_cases) -- digital silence in
 MID-stream (the accumulators' NORMAL -> TENTATIVE -> NORMAL recovery, movaccum.c:317-352, driven by the data-boundary
 detector on the reference signal, gstpeaq.c:861,1081-1099), hard clipping at full scale, DC offsets, an inverted test
-signal, channels 40 dB apart (binaural maxima, movs.c:1224-1276) -- through all three ways into the HIP path
+signal, channels 40 dB apart (binaural maxima, movs.c:1224-1276), and severe degradation down to the ODG floor with
+saturated and NaN results (tests/cases.py:severe_cases) -- through all three ways into the HIP path
 (batch: test_gpu_parity.py's golden tests pick the records up by themselves; here: one session per stream fed in
 arbitrary buffer sizes, and all streams of a channel count as concurrent sessions of one broker), each against the
 outputs of the REAL reference element (tests/golden/ref_e2e.json, tools/make_golden.py)."""
@@ -13,7 +14,7 @@ import gpu_common as gpu
 
 pytestmark = pytest.mark.gpu
 
-NAMES = {c["name"] for c in case_defs.input_class_cases()}
+NAMES = {c["name"] for c in case_defs.input_class_cases() + case_defs.severe_cases()}
 
 
 def _records(advanced, channels=None):
@@ -29,6 +30,7 @@ def _tols(advanced):
 
 
 def test_the_goldens_hold_every_class():
+    assert len(NAMES) == 11 + 20
     for adv in (0, 1):
         assert {r["case"]["name"] for r in _records(adv)} == NAMES
     # the gaps are long enough to silence whole frames: the reference itself must have seen fewer loud frames
@@ -75,7 +77,7 @@ def test_concurrent_broker_sessions_match_the_reference(channels, advanced, fir_
     import gstpeaq_amd
     recs = _records(advanced, channels)
     streams = [case_defs.make_inputs(r["case"]) for r in recs]
-    b = gstpeaq_amd.Broker(gpu.ctx(), channels, max_sessions=16, advanced=bool(advanced))
+    b = gstpeaq_amd.Broker(gpu.ctx(), channels, max_sessions=24, advanced=bool(advanced))
     sids = [b.open() for _ in recs]
     rng = np.random.default_rng(3)
     pos = [[0, 0] for _ in recs]

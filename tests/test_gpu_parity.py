@@ -37,21 +37,6 @@ def test_device_synth_matches_header(gpu, channels):
         assert np.array_equal(test[p].cpu().numpy(), t)
 
 
-def oracle_records(bands, ref, test, n_frames):
-    import ctypes as C
-    L = orc.lib()
-    ch = ref.shape[1]
-    out = np.zeros((n_frames, ch, 576))
-    L.orc_flat_frontend_records.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_float), C.c_size_t,
-                                            C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_double)]
-    r = np.ascontiguousarray(ref, dtype=np.float32)
-    t = np.ascontiguousarray(test, dtype=np.float32)
-    L.orc_flat_frontend_records(bands, ch, 92.0, r.ctypes.data_as(C.POINTER(C.c_float)), len(r),
-                                t.ctypes.data_as(C.POINTER(C.c_float)), len(t), n_frames,
-                                out.ctypes.data_as(C.POINTER(C.c_double)))
-    return out
-
-
 @pytest.mark.parametrize("bands", [109, 55])
 @pytest.mark.parametrize("case", [
     dict(kind="synth", seed=5, channels=1, n=20000),
@@ -61,7 +46,9 @@ def oracle_records(bands, ref, test, n_frames):
     dict(kind="synth", seed=26, channels=2, n=12000, identical=1),
     dict(kind="ats", wave_ref="saw", wave_test="triangle", n=16384, channels=1),
     dict(kind="synth", seed=41, channels=2, n=30000, gaps=[(8000, 9000)]),   # digital silence in mid-stream
-], ids=["mono", "stereo-ragged", "lead-silence", "quiet", "identical", "saw-triangle", "mid-gap"])
+    *case_defs.severe_stage_cases(),                             # sev_box8x3: the two bandwidths differ by design
+], ids=["mono", "stereo-ragged", "lead-silence", "quiet", "identical", "saw-triangle", "mid-gap",
+        *case_defs.SEVERE_STAGE_NAMES])
 def test_frontend_records_match_oracle(gpu, bands, case):
     """stage-level: every field of the per-frame record (unsmeared excitation,
     loudness^0.3, noise in bands, bandwidths, EHS, flags, energies)"""
@@ -72,7 +59,7 @@ def test_frontend_records_match_oracle(gpu, bands, case):
     n_frames = (n - 2048) // 1024 + 2           # all full frames + the flush frame
     got = gstpeaq_amd.debug_frontend(gpu.ctx(), bands, torch.from_numpy(ref).cuda(), torch.from_numpy(test).cuda(),
                                      n_frames)
-    exp = oracle_records(bands, ref, test, n_frames)
+    exp = orc.frontend_records(bands, ref, test, n_frames)
     # The 55-band kernel is the advanced version's FFT path: that version reads neither the test signal's
     # excitation nor the bandwidths (process_fft_block_advanced, gstpeaq.c:924-959), so the kernel does
     # not compute them and the record carries zeros there.
@@ -85,7 +72,22 @@ def test_frontend_records_match_oracle(gpu, bands, case):
                                    err_msg=name)
     # noise = Pr - 2 sqrt(Pr Pt) + Pt cancels heavily where the signals are close: the rounding of
     # the two DFT implementations (kissfft-like radix-2 in the oracle, 16x16x4 Stockham here) shows
-    np.testing.assert_allclose(got[:, :, 448:448 + bands], exp[:, :, 448:448 + bands], rtol=1e-6, atol=0,
+    usual = np.ones(n_frames, bool)
+    if case.get("name") == "sev_dropouts_mono":
+        # frame 22 overlaps a dropout by 32 samples at the window's foot: ill-conditioned in every band (tests/cases.py).
+        # Each band's bound is 4 x the movement of the oracle's OWN value of that band when 1 % of the test signal's
+        # samples move by one float32 ulp, and never below the usual 1e-6.  The movements: 1.0e-6 .. 2.32e-3 at 109
+        # bands (median 4.7e-5), 1.2e-7 .. 4.97e-4 at 55 (median 3.2e-5); tests/test_severe_cases_host.py pins them.
+        usual[22] = False
+        want = exp[22, :, 448:448 + bands]
+        moved = orc.frontend_records(bands, ref, case_defs.ulp_perturbed(test), n_frames)[22, :, 448:448 + bands]
+        bound = np.maximum(1e-6, 4 * np.abs(moved - want) / want)
+        err = np.abs(got[22, :, 448:448 + bands] - want) / want
+        worst = int(np.argmax(err / bound))
+        print(f"noise of frame 22, {bands} bands: {(err > 1e-6).sum()} beyond 1e-6, largest error {err.max():.3e}, "
+              f"nearest to its bound: band {worst % bands}, {err.flat[worst]:.3e} of {bound.flat[worst]:.3e}")
+        assert (err <= bound).all(), ("noise, frame 22", np.flatnonzero(err > bound), err[err > bound], bound[err > bound])
+    np.testing.assert_allclose(got[usual, :, 448:448 + bands], exp[usual, :, 448:448 + bands], rtol=1e-6, atol=0,
                                err_msg="noise")
     if bands == 109:
         assert np.array_equal(got[:, :, 560:562], exp[:, :, 560:562]), "bandwidths"
@@ -125,7 +127,7 @@ def test_energy_threshold_at_the_boundary(gpu, bands):
         sig[idx[77], 0] = special
         ref = torch.from_numpy(sig).cuda()
         got = gstpeaq_amd.debug_frontend(gpu.ctx(), bands, ref, ref, n_frames)
-        exp = oracle_records(bands, sig, sig, n_frames)
+        exp = orc.frontend_records(bands, sig, sig, n_frames)
         assert np.array_equal(got[:, :, 563:565], exp[:, :, 563:565]), name
         # bit 1 of the flag words = energy threshold reached (ref, test)
         flags = got[:, 0, 563].astype(int)
@@ -139,7 +141,8 @@ def test_energy_threshold_at_the_boundary(gpu, bands):
     dict(kind="synth", seed=5, channels=1, n=30000),
     dict(kind="synth", seed=6, channels=2, n=25000, test_trim=1000),
     dict(kind="ats", wave_ref="saw", wave_test="triangle", n=20000, channels=1),
-], ids=["mono", "stereo-ragged", "saw-triangle"])
+    *case_defs.severe_stage_cases(),
+], ids=["mono", "stereo-ragged", "saw-triangle", *case_defs.SEVERE_STAGE_NAMES])
 def test_filterbank_records_match_oracle(gpu, case, bpl, fir_mode):
     """stage-level, advanced: unsmeared + forward-masked excitation of the 40-band filter bank per
     192-sample block (fbearmodel.c:276-396) and the block boundary flag, for whole-chunk launches
@@ -191,6 +194,39 @@ def test_batch_advanced_matches_reference_goldens(gpu, channels, fir_mode):
         if not np.isnan(float(rec["odg"])):
             worst = max(worst, abs(g["odg"] - float(rec["odg"])))
     print(f"max |dODG| vs reference over {len(recs)} advanced cases: {worst:.3e}")
+
+
+def test_saturated_index_and_nan_results_are_the_references(gpu):
+    """The severe cases (tests/cases.py:severe_cases), one batch per version and channel count, default engine.  Where
+    every hidden sigmoid of the advanced network is exactly 0 or 1 the distortion index is a sum of weights: the device
+    must give the reference's to 1e-12, tighter than the general bound -- anything more means a hidden unit did not
+    saturate the way the reference's did.  Where an accumulator never received a frame (or the test signal is digital
+    silence) the reference's MOV, DI and ODG are NaN: NaN on the device in the same places, and every other MOV of
+    such a record within the standard tolerance."""
+    names = {c["name"] for c in case_defs.severe_cases()}
+    saturated, nan = [], []
+    for adv in (0, 1):
+        rtol = gpu.tol("movs") if adv else 1e-7
+        for channels in (1, 2):
+            recs = [r for r in gpu.e2e_records(adv) if r["case"]["name"] in names and r["case"]["channels"] == channels]
+            assert len(recs) == 10
+            got = gpu.run_batch([case_defs.make_inputs(r["case"]) for r in recs], adv, channels)
+            for g, rec in zip(got, recs):
+                name = f"{rec['case']['name']} advanced={adv}"
+                assert g["frames"] == rec["frames"], name
+                if adv and float(rec["di"]) == case_defs.DI_SATURATED:
+                    print(f"{name}: saturated DI, device - reference {g['di'] - case_defs.DI_SATURATED:.3e}")
+                    assert abs(g["di"] - case_defs.DI_SATURATED) <= 1e-12, (name, g["di"])
+                    saturated.append(name)
+                if np.isnan(float(rec["odg"])):
+                    assert np.isnan(float(rec["di"])) and np.isnan(g["di"]) and np.isnan(g["odg"]), (name, g["di"], g["odg"])
+                    exp = np.array([float(v) for v in rec["movs"]])
+                    assert np.array_equal(np.isnan(g["movs"]), np.isnan(exp)), (name, g["movs"], exp)
+                    fin = ~np.isnan(exp)
+                    assert fin.any() and not fin.all(), name
+                    np.testing.assert_allclose(g["movs"][fin], exp[fin], rtol=rtol, atol=1e-9, err_msg=name)
+                    nan.append(name)
+    assert len(saturated) == 6 and len(nan) == 6 + 2, (saturated, nan)
 
 
 def test_reference_odg_regression_strings_on_gpu(gpu):
@@ -367,7 +403,7 @@ def test_run_pair_from_host_memory_equals_the_goldens(gpu, fir_mode):
     """peaq_run_pair (upload + one-pair batch + result): ragged, sub-frame, silent and empty pairs included"""
     import gstpeaq_amd
     for adv in (0, 1):
-        for rec in gpu.e2e_records(adv)[:40]:
+        for rec in gpu.e2e_records(adv):
             ref, test = case_defs.make_inputs(rec["case"])
             got = gstpeaq_amd.run_pair(gpu.ctx(), adv, ref, test)
             gpu.compare_result(got, rec, rtol=gpu.tol("movs", adv), atol=1e-9, odg_atol=gpu.tol("odg", adv))
