@@ -85,6 +85,23 @@ __device__ __forceinline__ cplx tw_lane(const CommonTables* __restrict__ ct, int
 }
 __device__ __forceinline__ cplx csqr(cplx a) { return {a.re * a.re - a.im * a.im, 2. * (a.re * a.im)}; }
 
+// dft8 (peaq_wave.h) for inputs whose upper half is purely imaginary: x[4..7].re are taken as zero and never read.
+// Same values as dft8 on {0, x[4 + n].im}, bar the sign of a zero (x.re + 0 turns -0 into +0, this does not).
+__device__ __forceinline__ void dft8_imag_upper(cplx (&x)[8]) {
+  constexpr double c = 0.70710678118654752440;
+  cplx a0 = {x[0].re, x[0].im + x[4].im}, a1 = {x[1].re, x[1].im + x[5].im};
+  cplx a2 = {x[2].re, x[2].im + x[6].im}, a3 = {x[3].re, x[3].im + x[7].im};
+  cplx b0 = {x[0].re, x[0].im - x[4].im}, b1 = {x[1].re, x[1].im - x[5].im};
+  cplx b2 = {x[2].re, x[2].im - x[6].im}, b3 = {x[3].re, x[3].im - x[7].im};
+  b1 = {c * (b1.re + b1.im), c * (b1.im - b1.re)};      // * W8^1 = (1 - i) / sqrt 2
+  b2 = cmul_mi(b2);                                       // * W8^2 = -i
+  b3 = {c * (b3.im - b3.re), -c * (b3.re + b3.im)};      // * W8^3 = (-1 - i) / sqrt 2
+  dft4(a0, a1, a2, a3);
+  dft4(b0, b1, b2, b3);
+  x[0] = a0; x[2] = a1; x[4] = a2; x[6] = a3;
+  x[1] = b0; x[3] = b1; x[5] = b2; x[7] = b3;
+}
+
 // One exchange step of the Stockham FFT through the wave's 8.5 KiB buffer: all 16 points
 // go out at wr(r) and come back from rd(r), first the real then the imaginary parts.
 template <typename WR, typename RD>
@@ -108,9 +125,17 @@ __device__ __forceinline__ void exchange16(cplx (&z)[16], double* buf, WR wr, RD
 // On return p[s] is the power spectrum at bin spec_bin(s, lane) (registers) and Pw of the unit
 // holds the weighted power spectrum of bins 0..775.
 // ---------------------------------------------------------------------------
+// `before_split` is called ahead of the fence in front of the split: the caller's place for requests whose values it
+// needs right behind this function (a callback and not an array handed back: the compiler keeps such an array in
+// scratch, 64 bytes per lane in both instantiations).
+template <typename F>
 __device__ __forceinline__ void frame_power_spectrum(cplx (&z)[16], double (&p)[16], double* unit, int lane,
                                                      const CommonTables* __restrict__ ct,
-                                                     double level_factor) {
+                                                     double level_factor, F&& before_split) {
+  // Table values whose use lies behind an LDS exchange are requested BEFORE it, by hand: wave_lds_fence() is an
+  // acquire-release fence, the compiler may not lift a later global load over it, and a load issued behind the fence is
+  // waited for a few instructions later -- a full round trip through the vector-memory pipe with nothing to cover it.
+  const cplx w256 = tw_lane(ct, 2, lane);            // pass 2's W_256^k: has pass 1 and the exchange to arrive
   // pass 1: radix 16, sub-transform size 1 -> out[16 lane + r]; pass 2 reads in[lane + 64 r]
   dft16(z);
   exchange16(z, unit, [&](int r) { return 16 * lane + r; }, [&](int r) { return lane + 64 * r; });
@@ -121,7 +146,7 @@ __device__ __forceinline__ void frame_power_spectrum(cplx (&z)[16], double (&p)[
       // the rest as products
       // (applied as soon as they exist: only w1..w8 stay live, the register budget is 168)
       cplx w[9];
-      w[1] = tw_lane(ct, 2, lane);                   // W_256^k; the other powers by squaring
+      w[1] = w256;                                   // W_256^k; the other powers by squaring
       w[2] = csqr(w[1]);
       w[4] = csqr(w[2]);
       w[8] = csqr(w[4]);
@@ -163,6 +188,12 @@ __device__ __forceinline__ void frame_power_spectrum(cplx (&z)[16], double (&p)[
                [&](int s) { return lane + 64 * (s & 3) + 256 * (s >> 2); });
 #endif
   }
+  // the split's W_2048^lane and ear weights (fftearmodel.c:470-472), requested ahead of the fence in front of the split:
+  // they have pass 3 to arrive
+  const cplx wl = tw_lane(ct, 0, lane);
+  double2 ew[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) ew[q] = *reinterpret_cast<const double2*>(ct->ear_w2_pair[q][lane]);
   {
     // W_1024^(r i), i = lane + 64 m: W_1024^lane from the table, times W_16^m (constants), squared and cubed
     constexpr double c1 = 0.92387953251128673848, s1 = 0.38268343236508977173, c2 = 0.70710678118654752440;
@@ -186,8 +217,8 @@ __device__ __forceinline__ void frame_power_spectrum(cplx (&z)[16], double (&p)[
   // W_2048^k = W_2048^lane * W_32^q, the second factor is a compile-time constant.
   // Slot q of p[] holds bin lane + 64 q, slot 8 + q the mirror bin (spec_bin() below); lane 0's
   // q = 0 mirror would be bin 1024, which nothing reads: it carries the self-mirrored bin 512.
+  before_split();
   wave_lds_fence();                                  // the exchange buffer is about to become Pw
-  const cplx wl = tw_lane(ct, 0, lane);
   const int partner = (64 - lane) & 63;
   const double lf4 = 0.25 * level_factor;
 #pragma unroll
@@ -208,9 +239,8 @@ __device__ __forceinline__ void frame_power_spectrum(cplx (&z)[16], double (&p)[
       km = 512;
     }
     p[8 + q] = pm;
-    const double2 ew = *reinterpret_cast<const double2*>(ct->ear_w2_pair[q][lane]);
-    unit[kOffPw + k] = p[q] * ew.x;                                   // fftearmodel.c:470-472
-    if (km < kPwLen) unit[kOffPw + km] = pm * ew.y;
+    unit[kOffPw + k] = p[q] * ew[q].x;                                // fftearmodel.c:470-472
+    if (km < kPwLen) unit[kOffPw + km] = pm * ew[q].y;
   }
   wave_lds_fence();
 }
@@ -535,21 +565,23 @@ void frontend_kernel(FrontendArgs a) {
 
   FE_MARK(0);                                        // load, window, flags
   double pspec[16];                                  // unweighted power spectrum, bin lane + 64 q
-  frame_power_spectrum(z, pspec, unit, lane, ct, a.level_factor);
-
+  // This wave's share of the logarithm table is requested ahead of the split's fences (behind them it would be waited
+  // for at once; at the start of the kernel the three loads would sit in front of the frame's own) ...
+  double2 lt0, lt1, lt2;
+  frame_power_spectrum(z, pspec, unit, lane, ct, a.level_factor, [&] {
+    lt0 = *reinterpret_cast<const double2*>(ct->log_tab[lane]);
+    lt1 = *reinterpret_cast<const double2*>(ct->log_tab[64 + lane]);
+    lt2 = *reinterpret_cast<const double2*>(ct->log_tab[128]);
+  });
   // the band edges of this lane's two band sums (a narrow and a wide band, see below), requested now
   const int gb1 = lane < (NB + 1) / 2 ? lane : 0, gb2 = lane < (NB + 1) / 2 ? NB - 1 - lane : 0;
   const BandEdge edge1 = load_band_edge(bt, gb1), edge2 = load_band_edge(bt, gb2);
-  // The logarithm table (log_tab, peaq_wave.h) into LDS: every wave fills its OWN copy -- no workgroup barrier
-  // stands between the transform and the first logarithm any more -- and does so here, where its registers have
-  // just become free (at the start of the kernel the three loads would sit in front of the frame's own).
+  // ... and goes into LDS here (log_tab, peaq_wave.h): every wave fills its OWN copy -- no workgroup barrier stands
+  // between the transform and the first logarithm any more.
   {
-    const double2 t0 = *reinterpret_cast<const double2*>(ct->log_tab[lane]);
-    const double2 t1 = *reinterpret_cast<const double2*>(ct->log_tab[64 + lane]);
-    const double2 t2 = *reinterpret_cast<const double2*>(ct->log_tab[128]);
-    reinterpret_cast<double2*>(ltab)[lane] = t0;
-    reinterpret_cast<double2*>(ltab)[64 + lane] = t1;
-    if (lane == 0) reinterpret_cast<double2*>(ltab)[128] = t2;
+    reinterpret_cast<double2*>(ltab)[lane] = lt0;
+    reinterpret_cast<double2*>(ltab)[64 + lane] = lt1;
+    if (lane == 0) reinterpret_cast<double2*>(ltab)[128] = lt2;
     wave_lds_fence();
   }
   FE_MARK(1);                                        // FFT + split
@@ -567,28 +599,32 @@ void frontend_kernel(FrontendArgs a) {
   double thr = 0.;                                   // powers are >= 0
   // One compare per slot; the rest is scalar: the compare's lane mask says which bins of the slot
   // pass, its highest (slots 0..7: bin = 64 q + lane) or lowest (mirror slots: bin = 1024 - 64 q - lane)
-  // set bit below the limit is the slot's top bin.  Returns that bin + 1 over all slots, 0 if none.
+  // set bit below the limit is the slot's top bin.  Returns the highest such bin + 1 over all slots, 0 if none.
+  // The slots are walked from the top of the spectrum down -- mirror slots q = 0..7 (bins 1023..513), bin 512 (lane 0
+  // of mirror slot 0, spec_bin), direct slots q = 7..0 -- and the first slot with a hit ends the search, as the
+  // reference's own loop does (movs.c:776-809); the ballot is wave-uniform, so the exit is a scalar branch.
   auto top_bin = [&](double level, int limit, bool or_equal) {
-    int best = 0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      unsigned long long m = __ballot(or_equal ? pspec[q] >= level : pspec[q] > level);
-      const int nl = limit - 64 * q;               // lanes 0 .. nl - 1 hold bins below the limit
-      m &= nl >= 64 ? ~0ull : nl <= 0 ? 0ull : (1ull << nl) - 1ull;
-      if (m) best = max(best, 64 * q + 64 - __builtin_clzll(m));
-    }
+    bool hit512 = false;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       unsigned long long m = __ballot(or_equal ? pspec[8 + q] >= level : pspec[8 + q] > level);
-      if (q == 0) {                                // lane 0 carries bin 512 here (spec_bin)
-        if ((m & 1ull) && 512 < limit) best = max(best, 513);
+      if (q == 0) {                                // lane 0 carries bin 512 here: its turn comes behind slot 7
+        hit512 = (m & 1ull) && 512 < limit;
         m &= ~1ull;
       }
       const int lo = 1024 - 64 * q - limit + 1;    // lanes lo .. 63 hold bins below the limit
       m &= lo >= 64 ? 0ull : lo <= 0 ? ~0ull : ~0ull << lo;
-      if (m) best = max(best, 1024 - 64 * q - __builtin_ctzll(m) + 1);
+      if (m) return 1024 - 64 * q - __builtin_ctzll(m) + 1;
     }
-    return best;
+    if (hit512) return 513;
+#pragma unroll
+    for (int q = 7; q >= 0; --q) {
+      unsigned long long m = __ballot(or_equal ? pspec[q] >= level : pspec[q] > level);
+      const int nl = limit - 64 * q;               // lanes 0 .. nl - 1 hold bins below the limit
+      m &= nl >= 64 ? ~0ull : nl <= 0 ? 0ull : (1ull << nl) - 1ull;
+      if (m) return 64 * q + 64 - __builtin_clzll(m);
+    }
+    return 0;
   };
   if (!kAdvanced && sig == 1) {
     // zero threshold = max over bins 921..1023 of the test spectrum: the mirror bins 1024 - (lane + 64 q)
@@ -666,6 +702,7 @@ void frontend_kernel(FrontendArgs a) {
     // ... and the per-band constants of the spreading phase, requested before the band sums run
     const int b0 = 2 * lane;
     double c_noise[2], c_lnauc[2], c_gil[2];
+    const double c_dz02 = bt->dz02, c_ale = bt->aLe;   // (two scalars of the same tables, used behind the band sums' fences)
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       const int b = b0 + s2 < NB ? b0 + s2 : 0;
@@ -701,7 +738,7 @@ void frontend_kernel(FrontendArgs a) {
         // aUCE share one exponential (t = aUCE^0.2: aUCE^0.4 = t^2, aUCE = t^5), and En^0.4 takes its
         // logarithm as ln Pp - ln(gIL + gIU - 1) instead of dividing first
         const double ln_pp = FE_LOG(pp, ltab);
-        const double ln_a = c_lnauc[s] + bt->dz02 * ln_pp;
+        const double ln_a = c_lnauc[s] + c_dz02 * ln_pp;
         const double t = exp_fast(0.2 * ln_a), t2 = t * t;
         const double a_uce = t2 * t2 * t;
         const double g_iu = div_fast(1. - exp_fast((double)(NB - b) * ln_a), 1. - a_uce);
@@ -749,7 +786,7 @@ void frontend_kernel(FrontendArgs a) {
     // downward spreading, Kabal (28): E2[i-1] = aLe E2[i] + Ene[i-1]  (suffix scan)
     double dn0, dn1;
     {
-      const double al = bt->aLe;
+      const double al = c_ale;
       const double v = wave_suffix_geometric(ene[0] + al * ene[1], al * al, lane);   // pair-local, then over the lanes
       const double nxt = lane_above(v);                // E2down[2 lane + 2]; 0 beyond the last lane
       dn0 = v;
@@ -808,6 +845,7 @@ void frontend_kernel(FrontendArgs a) {
 #define PEAQ_FE_RATIOS_REF 3                         // (2 / 3 / 4 / 1 of the 8: 28.81 / 28.95 / 28.90 / 28.69 M, profiles/r06_ab_basic.txt)
 #endif
     constexpr int kRefRatios = PEAQ_FE_RATIOS_REF;
+    static_assert(kRefRatios >= 1 && kRefRatios <= 4, "the reference wave takes 1..4 of the 8 ratios per lane, the test wave the rest");
 #pragma unroll
     for (int j = 0; j < 8 - kRefRatios; ++j) {
       if (sig == 0 && j >= kRefRatios) break;
@@ -868,6 +906,14 @@ void frontend_kernel(FrontendArgs a) {
     // come out of ONE complex 512-point FFT of a + i b (8 points per lane, radix 8 x 8 x 8, real and
     // imaginary parts exchanged through the two scratch areas); the Hermitian product goes back
     // through a 256-point complex FFT (the inverse real transform by the half-size trick).
+    // All five twiddle entries of the transforms below are requested here, ahead of the exchanges and fences their
+    // uses sit behind (see frame_power_spectrum): register pressure is at its lowest on this wave, and the first of
+    // them is needed a whole dft8 and an exchange from now.
+    const cplx w64 = tw_lane(ct, 4, lane);                             // W_64^(lane & 7)
+    const cplx w512 = tw_lane(ct, 3, lane);                            // W_512^lane
+    cplx ft1[3];                                                     // fft256's passes 1..3, see there
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ft1[i] = tw_lane(ct, 5 + i, lane);
     cplx u[8];
     double g[4], run_in;                             // window-energy increments of this lane's four lags
     {
@@ -919,19 +965,23 @@ void frontend_kernel(FrontendArgs a) {
 #pragma unroll
       for (int r = 1; r < 8; ++r) u[r] = cmul(u[r], w[r]);
     };
-    dft8(u);                                                         // sub-transform size 1 -> out[8 lane + r]
+    dft8_imag_upper(u);                                              // sub-transform size 1 -> out[8 lane + r]; Re u[4..7] = 0
     exchange8([&](int r) { return 8 * lane + r; }, [](int i) { return i ^ ((i >> 4) & 7); });
     {
       const int k = lane & 7;
-      twiddle8(tw_lane(ct, 4, lane));                                // W_64^(r k)
+      twiddle8(w64);                                                 // W_64^(r k)
       dft8(u);                                                       // size 8 -> out[8 (lane - k) + k + 8 r]
       const int j = (lane - k) * 8 + k;
       exchange8([&](int r) { return j + 8 * r; }, [](int i) { return i ^ (((i >> 6) & 1) << 3); });
     }
-    const cplx w512 = tw_lane(ct, 3, lane);                          // W_512^lane
     twiddle8(w512);                                                  // W_512^(r lane)
     dft8(u);                                                         // u[r] = (A + i B)[lane + 64 r]
     FE_MARK(10);                                     // reference wave: 512-point FFT
+    // the window of part 3 (one of two tables, see there), requested two transforms ahead of its use
+    const double* __restrict__ win = a.cfg.centre_ehs_window ? ct->ehs_window_centred : ct->ehs_window;
+    double wv[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) wv[m] = win[lane + 64 * m];
     // Separate the two spectra and multiply, bins k = lane + 64 r < 256 (and 256 itself in lane 0);
     // the mirror bin 512 - k sits in lane 64 - lane, slot 7 - r (lane 0: own slot 8 - r).
     // 2A = Z[k] + conj Z[512-k], 2B = (Z[k] - conj Z[512-k]) / i, C = B conj(A); all factors of two
@@ -965,6 +1015,15 @@ void frontend_kernel(FrontendArgs a) {
       const cplx o = cmul(od, {wkf.re, -wkf.im});
       v[r] = {e.re - o.im, -(e.im + o.re)};                          // conj(E + i O)
     }
+    // twiddles of fft256's passes 1..3, W_{4p}^(r k): W_16^(lane & 3), W_64^(lane & 15), W_256^lane from the table,
+    // squared and cubed -- ONE set for both runs of the transform (the fences between the runs keep the compiler
+    // from seeing that the second run's loads and products repeat the first's)
+    cplx ft2[3], ft3[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      ft2[i] = csqr(ft1[i]);
+      ft3[i] = cmul(ft2[i], ft1[i]);
+    }
     wave_lds_fence();
     double2* xb = reinterpret_cast<double2*>(sa);        // 256 complex
     auto fft256 = [&](cplx (&w)[4]) {
@@ -980,11 +1039,9 @@ void frontend_kernel(FrontendArgs a) {
               w[r] = {x.x, x.y};
             }
           }
-          // W_{4p}^(r k): W_16^(lane & 3), W_64^(lane & 15), W_256^lane from the table, squared and cubed
-          const cplx t1 = tw_lane(ct, 4 + pass, lane), t2 = csqr(t1), t3 = cmul(t2, t1);
-          w[1] = cmul(w[1], t1);
-          w[2] = cmul(w[2], t2);
-          w[3] = cmul(w[3], t3);
+          w[1] = cmul(w[1], ft1[pass - 1]);
+          w[2] = cmul(w[2], ft2[pass - 1]);
+          w[3] = cmul(w[3], ft3[pass - 1]);
         }
         dft4(w[0], w[1], w[2], w[3]);
         if (pass < 2) {
@@ -1044,10 +1101,9 @@ void frontend_kernel(FrontendArgs a) {
     // as the DC bin after the transform (:1429-1433); the window is the one of :1366-1367 or the centred
     // one of :1363-1364 (settings.h:56, 66 as run-time switches)
     cavg = a.cfg.ehs_dc_before_window ? wave_sum(cavg) / 256. : 0.;
-    const double* __restrict__ win = a.cfg.centre_ehs_window ? ct->ehs_window_centred : ct->ehs_window;
     cplx w4[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) w4[m] = {(c[m] - cavg) * win[lane + 64 * m], 0.};
+    for (int m = 0; m < 4; ++m) w4[m] = {(c[m] - cavg) * wv[m], 0.};
     wave_lds_fence();
     fft256(w4);
     if (!a.cfg.ehs_dc_before_window && lane == 0) w4[0].re = 0.;   // bin 0 sits in slot 0 of lane 0
