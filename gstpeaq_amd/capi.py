@@ -213,6 +213,7 @@ def load_library():
     L.peaq_session_reset.argtypes = [vp]
     L.peaq_session_set_level.argtypes = [vp, C.c_double]
     L.peaq_debug_backend.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
+    L.peaq_debug_backend_plain.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, dp]
     if hasattr(L, "peaq_debug_backend_advanced"):
         L.peaq_debug_backend_advanced.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, dp]
     L.peaq_batch_run.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t,
@@ -1763,6 +1764,29 @@ def debug_backend_advanced(ctx, fb_records, fft_records):
                                              ob.ctypes.data_as(dp), of.ctypes.data_as(dp), res.ctypes.data_as(dp)))
     return (dict(zip(ADVANCED_DEBUG_BLOCK, np.moveaxis(ob[:, :, :7], 2, 0))),
             dict(zip(ADVANCED_DEBUG_FRAME, np.moveaxis(of, 2, 0))), _result_dict(res, True))
+
+
+def debug_backend_plain(ctx, fft_records, frames_per_launch=None, fb_records=None, blocks_per_launch=None):
+    """The shipped instantiations of the back ends on records, from a fresh state, cut into launches of
+    frames_per_launch frames (and blocks_per_launch blocks); None = one launch.  fb_records None: basic version
+    (fft_records np [frames, channels, 576], 109 bands); else the advanced version (55-band fft_records and
+    fb_records np [blocks, channels, 168]).  -> result dict (include/peaq_amd.h, peaq_debug_backend_plain)."""
+    ff = np.ascontiguousarray(fft_records, dtype=np.float64)
+    n_frames, channels, w = ff.shape
+    assert w == RECORD_DOUBLES
+    adv = fb_records is not None
+    dp = C.POINTER(C.c_double)
+    fb, n_blocks = None, 0
+    if adv:
+        fb = np.ascontiguousarray(fb_records, dtype=np.float64)
+        n_blocks = fb.shape[0]
+        assert fb.shape[1:] == (channels, 168)
+    res = np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_debug_backend_plain(ctx.h, int(adv), channels, n_frames, ff.ctypes.data_as(dp),
+                                          int(frames_per_launch or n_frames), n_blocks,
+                                          fb.ctypes.data_as(dp) if adv else None, int(blocks_per_launch or max(n_blocks, 1)),
+                                          res.ctypes.data_as(dp)))
+    return _result_dict(res, adv)
 
 
 # planes in / out of the ops of peaq_debug_wave (include/peaq_amd.h); every other op is 1 -> 1

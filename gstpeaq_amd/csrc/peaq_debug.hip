@@ -229,6 +229,61 @@ extern "C" int peaq_debug_backend_advanced(peaq_ctx* c, int channels, int n_bloc
   return PEAQ_OK;
 }
 
+// The SHIPPED instantiations of the back ends (no debug dump, no points, no trace) on records, from a fresh state, cut
+// into launches of the given sizes: launch k takes frames [k frames_per_launch, (k + 1) frames_per_launch) with frame0
+// advancing, and everything a launch leaves to the next goes through the PairState (the accumulators' status and
+// fields, loudness_reached, the filters).  Then the read-out; only the result comes back.
+extern "C" int peaq_debug_backend_plain(peaq_ctx* c, int advanced, int channels, int n_frames,
+                                        const double* host_fft_records, int frames_per_launch, int n_blocks,
+                                        const double* host_fb_records, int blocks_per_launch, peaq_result* result) {
+  if (!c || !host_fft_records || !result || (advanced && !host_fb_records))
+    return fail(PEAQ_ERR_ARG, "peaq_debug_backend_plain: NULL argument");
+  if (int rc = check_channels("peaq_debug_backend_plain", channels)) return rc;
+  if (n_frames < 1 || frames_per_launch < 1)
+    return fail(PEAQ_ERR_ARG, "peaq_debug_backend_plain: n_frames, frames_per_launch must be >= 1");
+  if (advanced && (n_blocks < 1 || blocks_per_launch < 1))
+    return fail(PEAQ_ERR_ARG, "peaq_debug_backend_plain: n_blocks, blocks_per_launch must be >= 1");
+  HIP_TRY(hipSetDevice(c->device));
+  const int adv = advanced ? 1 : 0;
+  const size_t rec_bytes = (size_t)n_frames * channels * kRecDoubles * sizeof(double);
+  const size_t fbrec_bytes = adv ? (size_t)n_blocks * channels * kFbRecDoubles * sizeof(double) : 0;
+  DevBuf recs, fbrecs, st, res;
+  HIP_TRY(recs.reserve(rec_bytes));
+  if (adv) HIP_TRY(fbrecs.reserve(fbrec_bytes));
+  HIP_TRY(st.reserve(sizeof(PairState)));
+  HIP_TRY(res.reserve(sizeof(ResultRecord)));
+  HIP_TRY(upload_public_records(adv ? 55 : 109, channels, n_frames, host_fft_records, recs.p));
+  if (adv) HIP_TRY(hipMemcpy(fbrecs.p, host_fb_records, fbrec_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(launch_state_init(st.as<PairState>(), adv, 1, nullptr));
+  const ModelSetup m{c, c->settings, adv, channels, kNoLevel};
+  BackendArgs ba = m.backend(m.frontend());
+  ba.n_frames_uniform = n_frames;
+  ba.state = st.as<PairState>();
+  ba.debug = nullptr;
+  for (int f0 = 0; f0 < n_frames; f0 += frames_per_launch) {
+    ba.frame0 = f0;
+    ba.frames_per_launch = std::min(frames_per_launch, n_frames - f0);
+    ba.records = recs.as<double>() + (size_t)f0 * channels * kRecDoubles;   // a launch indexes its records from its own frame0
+    HIP_TRY(launch_backend(ba, 1, nullptr));
+  }
+  if (adv) {
+    FbBackendArgs fbk = m.fb_backend(m.fb_frontend());
+    fbk.n_blocks_uniform = n_blocks;
+    fbk.state = st.as<PairState>();
+    fbk.debug = nullptr;
+    for (int b0 = 0; b0 < n_blocks; b0 += blocks_per_launch) {
+      fbk.block0 = b0;
+      fbk.blocks_per_launch = std::min(blocks_per_launch, n_blocks - b0);
+      fbk.records = fbrecs.as<double>() + (size_t)b0 * channels * kFbRecDoubles;
+      HIP_TRY(launch_fb_backend(fbk, 1, nullptr));
+    }
+  }
+  HIP_TRY(launch_finalize(st.as<PairState>(), adv, channels, 1, res.as<ResultRecord>(), nullptr, c->settings));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(result, res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}
+
 // Host only: a StreamFramer fed with sample counts alone, drained the way peaq_session_push / _flush drain theirs.
 extern "C" int peaq_debug_stream_plan(int advanced, unsigned max_frames, unsigned max_blocks, int drain_every_push,
                                       size_t n_pushes, const int* pad, const uint64_t* n_samples, size_t max_windows,

@@ -1002,6 +1002,21 @@ int peaq_debug_backend_advanced (peaq_ctx *ctx, int channels, int n_blocks, cons
                                  int n_frames, const double *fft_records, double *out_blocks,
                                  double *out_frames, peaq_result *result);
 
+/* The SHIPPED instantiations of the back ends on records, cut into launches (tests/test_gpu_backend_gates.py).
+ * peaq_debug_backend and peaq_debug_backend_advanced run the debug instantiations, in one launch.  This entry runs
+ * the kernels every product path runs -- no per-frame dump, no reading points, no trace -- from a fresh state:
+ *   advanced == 0: fft_records [n_frames][channels][PEAQ_DEBUG_RECORD_DOUBLES] with 109 bands; n_blocks, fb_records
+ *                  and blocks_per_launch are ignored (fb_records may be NULL)
+ *   advanced != 0: fft_records with 55 bands and fb_records [n_blocks][channels][PEAQ_DEBUG_FB_RECORD_DOUBLES]
+ * in launches of frames_per_launch frames (blocks_per_launch blocks; the last launch takes what is left).  Between
+ * two launches everything the back end carries -- the accumulators' status and fields, the frame on which the
+ * loudness gate opened, the filters' state -- goes through the pair's state in device memory, as it does between the
+ * chunks of a batch and the windows of a session.  Then the read-out: only `result` (required) comes back.  A result
+ * that depends on where the launches are cut is a bug in that hand-over. */
+int peaq_debug_backend_plain (peaq_ctx *ctx, int advanced, int channels, int n_frames, const double *fft_records,
+                              int frames_per_launch, int n_blocks, const double *fb_records, int blocks_per_launch,
+                              peaq_result *result);
+
 /* The primitives of csrc/peaq_wave.h on their own (tests/test_gpu_wave_primitives.py): the inline functions every
  * kernel is made of -- logarithm, exponential, quotient and roots, the wave reductions and scans, the lane moves,
  * the register DFTs -- called by one small kernel on host arrays.

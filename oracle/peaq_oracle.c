@@ -274,6 +274,18 @@ orc_fftmodel_group (const orc_fftmodel *m, const double *spec, double *out)
   }
 }
 
+/* fftearmodel.c:496-504: time smearing of s->unsmeared (also run on its own by the records entries below) */
+static void
+fft_smear (const orc_fftmodel *m, orc_fftstate *s)
+{
+  int i;
+  for (i = 0; i < m->b.bands; i++) {
+    double a = m->b.ear_tc[i];
+    s->filtered[i] = a * s->filtered[i] + (1. - a) * s->unsmeared[i];
+    s->excitation[i] = s->filtered[i] > s->unsmeared[i] ? s->filtered[i] : s->unsmeared[i];
+  }
+}
+
 void
 orc_fftmodel_process (const orc_fftmodel *m, orc_fftstate *s, const float *x)
 {
@@ -293,11 +305,7 @@ orc_fftmodel_process (const orc_fftmodel *m, orc_fftstate *s, const float *x)
   for (i = 0; i < nb; i++)
     pp[i] = bp[i] + m->b.internal_noise[i];
   spread_bands (m, pp, s->unsmeared);
-  for (i = 0; i < nb; i++) {
-    double a = m->b.ear_tc[i];
-    s->filtered[i] = a * s->filtered[i] + (1. - a) * s->unsmeared[i];
-    s->excitation[i] = s->filtered[i] > s->unsmeared[i] ? s->filtered[i] : s->unsmeared[i];
-  }
+  fft_smear (m, s);
   /* fftearmodel.c:508-514; the product is formed in single precision there
    * (gfloat * gfloat) and accumulated in double */
   for (k = ORC_FFT_FRAME / 2; k < ORC_FFT_FRAME; k++) {
@@ -784,8 +792,20 @@ enum { MB_BW_REF, MB_BW_TEST, MB_NMR, MB_WINMOD, MB_ADB, MB_EHS, MB_AVGMOD1, MB_
   MB_NOISELOUD, MB_MFPD, MB_RELDIST, MB_COUNT };            /* gstpeaq.c:95-108 */
 enum { MA_RMSMOD, MA_NLASYM, MA_SEGNMR, MA_EHS, MA_LINDIST, MA_COUNT };   /* gstpeaq.c:86-93 */
 
+/* What the MOV layer takes from one channel's FFT frame besides the patterns and energy flags in orc_fftstate:
+ * the first step of a frame (ear models, or a record) fills it, the second (pattern layer, MOVs, accumulators)
+ * reads nothing else of the frame. */
+typedef struct {
+  double nib[ORC_MAXBANDS];            /* noise in bands, movs.c:992-1000 */
+  double bw_ref, bw_test;              /* movs.c:783-805 (basic version) */
+  double ehs;                          /* movs.c:1383-1441; only read where mov_ehs admits the frame */
+  double sig_e, noise_e;               /* gstpeaq.c:913-918, this channel's part */
+} orc_framein;
+
 struct orc_session {
   int advanced, channels;
+  orc_framein fin[2];
+  int above, above_fb;                 /* gstpeaq.c:858, :971: the boundary detector on this frame / block */
   fifo ref_fft, test_fft, ref_fb, test_fb;
   unsigned frame_counter, frame_counter_fb, loudness_reached;
   orc_fftmodel fftm;
@@ -806,6 +826,9 @@ struct orc_session {
    *   total loudness of ref, test while the loudness gate is closed, pad } */
   double *trace_fb;
   unsigned trace_blocks;
+  /* basic version: per FFT frame and channel the gate's two loudness values (reference, test) of the frames
+   * that begin with the loudness gate closed; the others are left as the caller set them */
+  double *trace_gate;
 };
 
 static int
@@ -901,7 +924,7 @@ mov_moddiff (orc_session *s, const orc_bands *b, orc_movaccum *a1, orc_movaccum 
 }
 
 static void
-bandwidth_of_frame (const double *pr, const double *pt, int *bw_ref_out, int *bw_test_out)
+bandwidth_of_frame (const double *pr, const double *pt, double *bw_ref_out, double *bw_test_out)
 {
   /* movs.c:783-805: unweighted power spectrum */
   double thr = pt[921];
@@ -931,11 +954,9 @@ mov_bandwidth (orc_session *s, orc_movaccum *aref, orc_movaccum *atest)
   /* movs.c:776-809 */
   int c;
   for (c = 0; c < aref->channels; c++) {
-    int bw_ref, bw_test;
-    bandwidth_of_frame (s->ref_fft_st[c].power, s->test_fft_st[c].power, &bw_ref, &bw_test);
-    if (bw_ref > 346) {
-      orc_acc_add (aref, c, bw_ref, 1.);
-      orc_acc_add (atest, c, bw_test, 1.);
+    if (s->fin[c].bw_ref > 346) {
+      orc_acc_add (aref, c, s->fin[c].bw_ref, 1.);
+      orc_acc_add (atest, c, s->fin[c].bw_test, 1.);
     }
   }
 }
@@ -954,12 +975,11 @@ noise_in_bands (const orc_fftmodel *m, const double *wr, const double *wt, doubl
 static void
 nmr_of_channel (const orc_session *s, int c, double *mean_out, double *max_out)
 {
-  /* movs.c:987-1012, one channel: weighted spectra, smeared ref excitation */
+  /* movs.c:987-1012, one channel: noise in bands of the weighted spectra, smeared ref excitation */
   const orc_fftmodel *m = &s->fftm;
-  const double *wr = s->ref_fft_st[c].weighted, *wt = s->test_fft_st[c].weighted;
-  double nib[ORC_MAXBANDS], nmr = 0., nmr_max = 0.;
+  const double *nib = s->fin[c].nib;
+  double nmr = 0., nmr_max = 0.;
   int i, nb = m->b.bands;
-  noise_in_bands (m, wr, wt, nib);
   for (i = 0; i < nb; i++) {
     double mask = s->ref_fft_st[c].excitation[i] / m->mask_diff[i];
     double r = nib[i] / mask;
@@ -1095,19 +1115,19 @@ mov_ehs (orc_session *s, orc_movaccum *aehs)
   if (!valid)
     return;
   for (c = 0; c < aehs->channels; c++)
-    orc_acc_add (aehs, c, 1000. * ehs_of_frame (s->ref_fft_st[c].weighted, s->test_fft_st[c].weighted), 1.);
+    orc_acc_add (aehs, c, 1000. * s->fin[c].ehs, 1.);
 }
 
 static void
-snr_accumulate (orc_session *s, const float *ref, const float *test, int frame)
+snr_accumulate (orc_session *s)
 {
-  /* gstpeaq.c:913-918: float products, double sums, first half of the interleaved frame */
-  int i, n = s->channels * frame / 2;
-  for (i = 0; i < n; i++) {
-    float sq = ref[i] * ref[i];
-    float df = (ref[i] - test[i]) * (ref[i] - test[i]);
-    s->sig_energy += sq;
-    s->noise_energy += df;
+  /* gstpeaq.c:913-918: the frame's energies per channel (fft_frame_fill, or a record) go to the running sums.
+   * The reference adds sample by sample into the running sums; adding a frame's own sum differs from that in the
+   * rounding of a double sum of float products only. */
+  int c;
+  for (c = 0; c < s->channels; c++) {
+    s->sig_energy += s->fin[c].sig_e;
+    s->noise_energy += s->fin[c].noise_e;
   }
 }
 
@@ -1124,15 +1144,13 @@ preprocess (orc_session *s, const orc_bands *b, int c, const double *er, const d
       s->loudness_reached = counter;
 }
 
+/* ---- first step of an FFT frame: the ear models fill the per-channel state (gstpeaq.c:850-869, 924-940) ---- */
 static void
-fft_frame_basic (orc_session *s, const float *ref, const float *test)
+fft_frame_fill (orc_session *s, const float *ref, const float *test)
 {
-  /* gstpeaq.c:850-921 */
   float ch[ORC_FFT_FRAME];
-  const orc_bands *b = &s->fftm.b;
-  int c, i, above = frame_above_threshold (ref, ORC_FFT_FRAME, s->channels);
-  for (i = 0; i < MB_COUNT; i++)
-    orc_acc_set_tentative (&s->acc[i], !above);
+  int c, i, valid = 0;
+  s->above = frame_above_threshold (ref, ORC_FFT_FRAME, s->channels);
   for (c = 0; c < s->channels; c++) {
     deinterleave (ref, ORC_FFT_FRAME, s->channels, c, ch);
     orc_fftmodel_process (&s->fftm, &s->ref_fft_st[c], ch);
@@ -1141,6 +1159,71 @@ fft_frame_basic (orc_session *s, const float *ref, const float *test)
     deinterleave (test, ORC_FFT_FRAME, s->channels, c, ch);
     orc_fftmodel_process (&s->fftm, &s->test_fft_st[c], ch);
   }
+  for (c = 0; c < s->channels; c++)
+    if (s->ref_fft_st[c].energy_reached || s->test_fft_st[c].energy_reached)
+      valid = 1;                                 /* movs.c:1374-1381 */
+  for (c = 0; c < s->channels; c++) {
+    orc_framein *in = &s->fin[c];
+    double se = 0., ne = 0.;
+    noise_in_bands (&s->fftm, s->ref_fft_st[c].weighted, s->test_fft_st[c].weighted, in->nib);
+    in->bw_ref = in->bw_test = 0.;
+    if (!s->advanced)
+      bandwidth_of_frame (s->ref_fft_st[c].power, s->test_fft_st[c].power, &in->bw_ref, &in->bw_test);
+    in->ehs = valid ? ehs_of_frame (s->ref_fft_st[c].weighted, s->test_fft_st[c].weighted) : 0.;
+    /* gstpeaq.c:913-918: float products, double sums, first half of the frame */
+    for (i = 0; i < ORC_FFT_FRAME / 2; i++) {
+      float a = ref[i * s->channels + c], b = test[i * s->channels + c];
+      float sq = a * a, df = (a - b) * (a - b);
+      se += sq;
+      ne += df;
+    }
+    in->sig_e = se;
+    in->noise_e = ne;
+  }
+}
+
+/* The same step from the front end's public records rec[channel][576] (gstpeaq_amd/csrc/peaq_device.h kPub*): the
+ * unsmeared excitations go through the smearing filter, everything else is taken as it stands. */
+static void
+fft_frame_fill_from_records (orc_session *s, const double *rec)
+{
+  int c, nb = s->fftm.b.bands;
+  s->above = 0;
+  for (c = 0; c < s->channels; c++) {
+    const double *r = rec + (size_t) c * 576;
+    orc_framein *in = &s->fin[c];
+    int fl_ref = (int) r[563], fl_test = (int) r[564];
+    memcpy (s->ref_fft_st[c].unsmeared, r, nb * sizeof (double));
+    memcpy (s->test_fft_st[c].unsmeared, r + 112, nb * sizeof (double));
+    fft_smear (&s->fftm, &s->ref_fft_st[c]);
+    fft_smear (&s->fftm, &s->test_fft_st[c]);
+    memcpy (in->nib, r + 448, nb * sizeof (double));
+    in->bw_ref = r[560];
+    in->bw_test = r[561];
+    in->ehs = r[562];
+    s->above |= fl_ref & 1;
+    s->ref_fft_st[c].energy_reached = (fl_ref >> 1) & 1;
+    s->test_fft_st[c].energy_reached = (fl_test >> 1) & 1;
+    in->sig_e = r[565];
+    in->noise_e = r[566];
+  }
+}
+
+/* ---- second step: pattern layer, MOVs and accumulators on that state ---- */
+static void
+fft_frame_basic_movs (orc_session *s)
+{
+  /* gstpeaq.c:858-862, 870-921 */
+  const orc_bands *b = &s->fftm.b;
+  int c, i;
+  for (i = 0; i < MB_COUNT; i++)
+    orc_acc_set_tentative (&s->acc[i], !s->above);
+  if (s->trace_gate && s->frame_counter < s->trace_frames && s->loudness_reached == UINT_MAX)
+    for (c = 0; c < s->channels; c++) {
+      double *t = s->trace_gate + ((size_t) s->frame_counter * s->channels + c) * 2;
+      t[0] = orc_loudness (b, s->ref_fft_st[c].excitation);
+      t[1] = orc_loudness (b, s->test_fft_st[c].excitation);
+    }
   for (c = 0; c < s->channels; c++)
     preprocess (s, b, c, s->ref_fft_st[c].excitation, s->test_fft_st[c].excitation,
                 s->ref_fft_st[c].unsmeared, s->test_fft_st[c].unsmeared, s->frame_counter);
@@ -1158,7 +1241,7 @@ fft_frame_basic (orc_session *s, const float *ref, const float *test)
   mov_nmr (s, &s->acc[MB_NMR], &s->acc[MB_RELDIST]);
   mov_prob_detect (s, &s->acc[MB_ADB], &s->acc[MB_MFPD]);
   mov_ehs (s, &s->acc[MB_EHS]);
-  snr_accumulate (s, ref, test, ORC_FFT_FRAME);
+  snr_accumulate (s);
   if (s->trace && s->frame_counter < s->trace_frames)
     for (c = 0; c < s->channels; c++) {
       double *t = s->trace + ((size_t) s->frame_counter * s->channels + c) * 8;
@@ -1173,24 +1256,15 @@ fft_frame_basic (orc_session *s, const float *ref, const float *test)
 }
 
 static void
-fft_frame_advanced (orc_session *s, const float *ref, const float *test)
+fft_frame_advanced_movs (orc_session *s)
 {
-  /* gstpeaq.c:924-962 */
-  float ch[ORC_FFT_FRAME];
-  int c, above = frame_above_threshold (ref, ORC_FFT_FRAME, s->channels);
-  orc_acc_set_tentative (&s->acc[MA_SEGNMR], !above);
-  orc_acc_set_tentative (&s->acc[MA_EHS], !above);
-  for (c = 0; c < s->channels; c++) {
-    deinterleave (ref, ORC_FFT_FRAME, s->channels, c, ch);
-    orc_fftmodel_process (&s->fftm, &s->ref_fft_st[c], ch);
-  }
-  for (c = 0; c < s->channels; c++) {
-    deinterleave (test, ORC_FFT_FRAME, s->channels, c, ch);
-    orc_fftmodel_process (&s->fftm, &s->test_fft_st[c], ch);
-  }
+  /* gstpeaq.c:932-936, 941-962 */
+  int c;
+  orc_acc_set_tentative (&s->acc[MA_SEGNMR], !s->above);
+  orc_acc_set_tentative (&s->acc[MA_EHS], !s->above);
   mov_nmr (s, &s->acc[MA_SEGNMR], NULL);
   mov_ehs (s, &s->acc[MA_EHS]);
-  snr_accumulate (s, ref, test, ORC_FFT_FRAME);
+  snr_accumulate (s);
   if (s->trace && s->frame_counter < s->trace_frames)
     for (c = 0; c < s->channels; c++) {
       double *t = s->trace + ((size_t) s->frame_counter * s->channels + c) * 2, mx;
@@ -1201,15 +1275,28 @@ fft_frame_advanced (orc_session *s, const float *ref, const float *test)
 }
 
 static void
-fb_block (orc_session *s, const float *ref, const float *test)
+fft_frame_basic (orc_session *s, const float *ref, const float *test)
 {
-  /* gstpeaq.c:965-1010 */
+  /* gstpeaq.c:850-921 */
+  fft_frame_fill (s, ref, test);
+  fft_frame_basic_movs (s);
+}
+
+static void
+fft_frame_advanced (orc_session *s, const float *ref, const float *test)
+{
+  /* gstpeaq.c:924-962 */
+  fft_frame_fill (s, ref, test);
+  fft_frame_advanced_movs (s);
+}
+
+/* ---- filter-bank block, first step (gstpeaq.c:965-985) ---- */
+static void
+fb_block_fill (orc_session *s, const float *ref, const float *test)
+{
   float ch[ORC_FB_FRAME];
-  const orc_bands *b = &s->fbm.b;
-  int c, above = frame_above_threshold (ref, ORC_FB_FRAME, s->channels);
-  orc_acc_set_tentative (&s->acc[MA_RMSMOD], !above);
-  orc_acc_set_tentative (&s->acc[MA_NLASYM], !above);
-  orc_acc_set_tentative (&s->acc[MA_LINDIST], !above);
+  int c;
+  s->above_fb = frame_above_threshold (ref, ORC_FB_FRAME, s->channels);
   for (c = 0; c < s->channels; c++) {
     deinterleave (ref, ORC_FB_FRAME, s->channels, c, ch);
     orc_fbmodel_process (&s->fbm, &s->ref_fb_st[c], ch);
@@ -1218,6 +1305,36 @@ fb_block (orc_session *s, const float *ref, const float *test)
     deinterleave (test, ORC_FB_FRAME, s->channels, c, ch);
     orc_fbmodel_process (&s->fbm, &s->test_fb_st[c], ch);
   }
+}
+
+/* the same step from block records rec[channel][168] (peaq_device.h kFbRec*): both patterns of both signals as
+ * they stand, the flag OR-ed over the channels */
+static void
+fb_block_fill_from_records (orc_session *s, const double *rec)
+{
+  int c;
+  s->above_fb = 0;
+  for (c = 0; c < s->channels; c++) {
+    const double *r = rec + (size_t) c * 168;
+    memcpy (s->ref_fb_st[c].unsmeared, r, ORC_FB_BANDS * sizeof (double));
+    memcpy (s->test_fb_st[c].unsmeared, r + 40, ORC_FB_BANDS * sizeof (double));
+    memcpy (s->ref_fb_st[c].excitation, r + 80, ORC_FB_BANDS * sizeof (double));
+    memcpy (s->test_fb_st[c].excitation, r + 120, ORC_FB_BANDS * sizeof (double));
+    if (r[160] != 0.)
+      s->above_fb = 1;
+  }
+}
+
+/* ---- second step ---- */
+static void
+fb_block_movs (orc_session *s)
+{
+  /* gstpeaq.c:980-984, 986-1010 */
+  const orc_bands *b = &s->fbm.b;
+  int c;
+  orc_acc_set_tentative (&s->acc[MA_RMSMOD], !s->above_fb);
+  orc_acc_set_tentative (&s->acc[MA_NLASYM], !s->above_fb);
+  orc_acc_set_tentative (&s->acc[MA_LINDIST], !s->above_fb);
   if (s->trace_fb && s->frame_counter_fb < s->trace_blocks && s->loudness_reached == UINT_MAX)
     for (c = 0; c < s->channels; c++) {         /* the gate's two loudness values of this block, every channel */
       double *t = s->trace_fb + ((size_t) s->frame_counter_fb * s->channels + c) * 8;
@@ -1257,6 +1374,14 @@ fb_block (orc_session *s, const float *ref, const float *test)
     }
   }
   s->frame_counter_fb++;
+}
+
+static void
+fb_block (orc_session *s, const float *ref, const float *test)
+{
+  /* gstpeaq.c:965-1010 */
+  fb_block_fill (s, ref, test);
+  fb_block_movs (s);
 }
 
 typedef void (*frame_fn) (orc_session *, const float *, const float *);
@@ -1611,8 +1736,8 @@ orc_flat_frontend_records (int bands, int channels, double level_db, const float
     }
     for (c = 0; c < channels; c++) {
       double *rec = out + ((size_t) f * channels + c) * 576;
-      int bw_ref, bw_test, above_c;
-      double se = 0., ne = 0.;
+      int above_c;
+      double bw_ref, bw_test, se = 0., ne = 0.;
       memset (rec, 0, 576 * sizeof (double));
       deinterleave (fr, ORC_FFT_FRAME, channels, c, ch);
       above_c = frame_above_threshold (ch, ORC_FFT_FRAME, 1);
@@ -1647,4 +1772,99 @@ orc_flat_frontend_records (int bands, int channels, double level_db, const float
   free (st);
   free (fr);
   free (ft);
+}
+
+/* ======================================================================== */
+/* the back ends on records (tests only)                                      */
+/* ======================================================================== */
+
+static void
+records_result (const orc_session *s, double *movs, double *di, double *odg, double *totalsnr)
+{
+  orc_session_results (s, movs, di, odg);
+  if (totalsnr)
+    *totalsnr = orc_session_totalsnr (s);
+}
+
+/* The basic version's back end on hand-built or computed front-end records: records[frame][channel][576] in the
+ * layout of orc_flat_frontend_records.  Read from each record: the unsmeared excitations (the smearing filter runs
+ * on them from a zero state), noise in bands, both bandwidths, EHS, the energy bits of both flag words, bit 0 of the
+ * reference's flag word (OR-ed over the channels: the frame is above the boundary detector's threshold) and both
+ * energies.  From there on it is the code the sample path runs (fft_frame_basic_movs).  trace[frame][channel][8] as
+ * orc_flat_mov_trace, gate[frame][channel][2] as orc_session.trace_gate; either may be NULL. */
+void
+orc_flat_backend_records (int channels, int n_frames, const double *records, double *movs, double *di, double *odg,
+                          double *totalsnr, double *trace, double *gate)
+{
+  orc_session *s = orc_session_new (0, channels, 92.);
+  int f;
+  s->trace = trace;
+  s->trace_gate = gate;
+  s->trace_frames = (unsigned) n_frames;
+  for (f = 0; f < n_frames; f++) {
+    fft_frame_fill_from_records (s, records + (size_t) f * channels * 576);
+    fft_frame_basic_movs (s);
+  }
+  records_result (s, movs, di, odg, totalsnr);
+  orc_session_free (s);
+}
+
+/* The advanced version's two back ends: fb_records[block][channel][168] (orc_flat_fb_records) and 55-band
+ * fft_records[frame][channel][576]; traces as orc_flat_mov_trace_advanced. */
+void
+orc_flat_backend_records_advanced (int channels, int n_blocks, const double *fb_records, int n_frames,
+                                   const double *fft_records, double *movs, double *di, double *odg,
+                                   double *totalsnr, double *trace_blocks, double *trace_frames)
+{
+  orc_session *s = orc_session_new (1, channels, 92.);
+  int f;
+  s->trace = trace_frames;
+  s->trace_frames = (unsigned) n_frames;
+  s->trace_fb = trace_blocks;
+  s->trace_blocks = (unsigned) n_blocks;
+  for (f = 0; f < n_frames; f++) {
+    fft_frame_fill_from_records (s, fft_records + (size_t) f * channels * 576);
+    fft_frame_advanced_movs (s);
+  }
+  for (f = 0; f < n_blocks; f++) {
+    fb_block_fill_from_records (s, fb_records + (size_t) f * channels * 168);
+    fb_block_movs (s);
+  }
+  records_result (s, movs, di, odg, totalsnr);
+  orc_session_free (s);
+}
+
+/* Filter-bank records of one pair in the layout of the HIP filter bank (peaq_device.h kFbRec*):
+ * out[block][channel][168] = unsmeared ref, test, forward-masked excitation ref, test (40 each), then the
+ * boundary detector's flag of the reference's block; samples past either end are zeros (do_flush). */
+void
+orc_flat_fb_records (int channels, double level_db, const float *ref, size_t n_ref, const float *test, size_t n_test,
+                     int n_blocks, double *out)
+{
+  orc_fbmodel m;
+  orc_fbstate *sr = (orc_fbstate *) calloc (2, sizeof *sr), *st = (orc_fbstate *) calloc (2, sizeof *st);
+  float cr[ORC_FB_FRAME], ct[ORC_FB_FRAME];
+  int f, c, i;
+  orc_fbmodel_init (&m, level_db);
+  for (f = 0; f < n_blocks; f++) {
+    size_t s0 = (size_t) f * ORC_FB_FRAME;
+    for (c = 0; c < channels; c++) {
+      double *rec = out + ((size_t) f * channels + c) * 168;
+      for (i = 0; i < ORC_FB_FRAME; i++) {
+        cr[i] = s0 + i < n_ref ? ref[(s0 + i) * channels + c] : 0.f;
+        ct[i] = s0 + i < n_test ? test[(s0 + i) * channels + c] : 0.f;
+      }
+      memset (rec, 0, 168 * sizeof (double));
+      orc_fbmodel_process (&m, &sr[c], cr);
+      orc_fbmodel_process (&m, &st[c], ct);
+      memcpy (rec, sr[c].unsmeared, sizeof sr[c].unsmeared);
+      memcpy (rec + 40, st[c].unsmeared, sizeof st[c].unsmeared);
+      memcpy (rec + 80, sr[c].excitation, sizeof sr[c].excitation);
+      memcpy (rec + 120, st[c].excitation, sizeof st[c].excitation);
+      rec[160] = frame_above_threshold (cr, ORC_FB_FRAME, 1);
+    }
+  }
+  orc_fbmodel_free (&m);
+  free (sr);
+  free (st);
 }

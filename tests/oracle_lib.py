@@ -168,6 +168,73 @@ def frontend_records(bands, ref, test, n_frames, level=92.0):
     return out
 
 
+def count_frames(n_ref, n_test):
+    """FFT frames of a pair with n_ref / n_test samples per channel: the full ones of both adapters, then at most one
+    zero-padded frame for what is left in either (gstpeaq.c:596-611, 716-745)"""
+    n = min(n_ref, n_test)
+    full = (n - 2048) // 1024 + 1 if n >= 2048 else 0
+    return full + (1 if max(n_ref, n_test) > full * 1024 else 0)
+
+
+def count_blocks(n_ref, n_test):
+    """the same for the filter bank's blocks of 192 samples"""
+    full = min(n_ref, n_test) // 192
+    return full + (1 if max(n_ref, n_test) > full * 192 else 0)
+
+
+def fb_records(ref, test, n_blocks, level=92.0):
+    """the per-block records of the filter-bank ear model, in the layout of the HIP filter bank's:
+    -> np [blocks, channels, 168]"""
+    L = lib()
+    ch = ref.shape[1]
+    out = np.zeros((n_blocks, ch, 168))
+    L.orc_flat_fb_records.argtypes = [C.c_int, C.c_double, _fp, C.c_size_t, _fp, C.c_size_t, C.c_int, _dp]
+    r = np.ascontiguousarray(ref, dtype=np.float32)
+    t = np.ascontiguousarray(test, dtype=np.float32)
+    L.orc_flat_fb_records(ch, level, _ptr(r, _fp), len(r), _ptr(t, _fp), len(t), n_blocks, _ptr(out, _dp))
+    return out
+
+
+def backend_records(records):
+    """basic version: the back end on front-end records np [frames, channels, 576] (frontend_records' layout, hand-built
+    or computed) -> dict(movs, di, odg, totalsnr, frames, trace = mov_trace's dict, gate = np [frames, channels, 2]: the
+    loudness gate's two values (ref, test) on the frames that begin with the gate closed, NaN elsewhere)"""
+    L = lib()
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    n_frames, ch, w = rec.shape
+    assert w == 576 and ch in (1, 2)
+    movs, trace, gate = np.zeros(11), np.zeros((n_frames, ch, 8)), np.full((n_frames, ch, 2), np.nan)
+    di, odg, snr = C.c_double(), C.c_double(), C.c_double()
+    L.orc_flat_backend_records.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.orc_flat_backend_records(ch, n_frames, _ptr(rec, _dp), _ptr(movs, _dp), C.byref(di), C.byref(odg), C.byref(snr),
+                               _ptr(trace, _dp), _ptr(gate, _dp))
+    return dict(movs=movs, di=di.value, odg=odg.value, totalsnr=snr.value, frames=n_frames,
+                trace=dict(zip(MOV_TRACE, np.moveaxis(trace, 2, 0))), gate=gate)
+
+
+def backend_records_advanced(fb_recs, fft_recs):
+    """advanced version: both back ends on block records np [blocks, channels, 168] (fb_records' layout) and 55-band
+    frame records np [frames, channels, 576] -> dict(movs, di, odg, totalsnr, frames, fb_blocks, trace_blocks,
+    trace_frames = mov_trace_advanced's two dicts, gate = np [blocks, channels, 2] as backend_records')"""
+    L = lib()
+    fb = np.ascontiguousarray(fb_recs, dtype=np.float64)
+    ff = np.ascontiguousarray(fft_recs, dtype=np.float64)
+    n_blocks, ch, w = fb.shape
+    n_frames = ff.shape[0]
+    assert w == 168 and ff.shape[1:] == (ch, 576)
+    movs, ob, of = np.zeros(11), np.zeros((n_blocks, ch, 8)), np.zeros((n_frames, ch, 2))
+    ob[:, :, 5:7] = np.nan                         # written on the blocks that begin with the loudness gate closed only
+    di, odg, snr = C.c_double(), C.c_double(), C.c_double()
+    L.orc_flat_backend_records_advanced.argtypes = [C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.orc_flat_backend_records_advanced(ch, n_blocks, _ptr(fb, _dp), n_frames, _ptr(ff, _dp), _ptr(movs, _dp),
+                                        C.byref(di), C.byref(odg), C.byref(snr), _ptr(ob, _dp), _ptr(of, _dp))
+    gate = ob[:, :, 5:7].copy()
+    ob[:, :, 5:7] = np.nan_to_num(gate, nan=0.)    # mov_trace_advanced's convention
+    return dict(movs=movs[:5].copy(), di=di.value, odg=odg.value, totalsnr=snr.value, frames=n_frames, gate=gate,
+                fb_blocks=n_blocks, trace_blocks=dict(zip(MOV_TRACE_ADV_BLOCK, np.moveaxis(ob[:, :, :7], 2, 0))),
+                trace_frames=dict(zip(MOV_TRACE_ADV_FRAME, np.moveaxis(of, 2, 0))))
+
+
 def fftear(bands, x, n_frames, hop, level=92.0):
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = dict(power=np.zeros((n_frames, 1025)), weighted=np.zeros((n_frames, 1025)),
