@@ -16,6 +16,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    GAIN_PER_CHANNEL, GAIN_F_SILENT, GAIN_F_NONFINITE, GAIN_F_ZERO, GAIN_F_RANGE,
                    SubDelay, refine_delay, cut_shifted, subsample_tables, subdelay_workspace_bytes, SUBDELAY_DTYPE, SUB_STEPS,
                    SUB_LAGS, SUB_HALF, SUB_F_NONE, SUB_F_EDGE,
+                   Track, TRACK_DTYPE, TRACK_F_NONE, TRACK_F_RANGE, TRACK_MAX_E, TRACK_MAX_STEP, TRACK_MAX_SEGMENTS_PER_CALL,
+                   TRACK_WINDOW, track_fit, track_segment, track_index, track_lengths, estimate_track, cut_track,
                    Drift, estimate_drift, cut_drift, drift_lengths, drift_fit, drift_index, drift_windows, drift_workspace_bytes,
                    DRIFT_DTYPE, DRIFT_F_NONE, DRIFT_F_RANGE, DRIFT_WINDOW, DRIFT_MIN_CORR, DRIFT_MAX_E, DRIFT_MAX_WINDOWS,
                    PCM_FORMATS, PCM_DTYPES,
@@ -34,6 +36,9 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
            "SubDelay", "refine_delay", "cut_shifted", "subsample_tables", "subdelay_workspace_bytes", "SUBDELAY_DTYPE", "SUB_STEPS",
            "SUB_LAGS", "SUB_HALF", "SUB_F_NONE", "SUB_F_EDGE",
+           "Track", "TRACK_DTYPE", "TRACK_F_NONE", "TRACK_F_RANGE", "TRACK_MAX_E", "TRACK_MAX_STEP",
+           "TRACK_MAX_SEGMENTS_PER_CALL", "TRACK_WINDOW", "track_fit", "track_segment", "track_index", "track_lengths",
+           "estimate_track", "cut_track",
            "Drift", "estimate_drift", "cut_drift", "drift_lengths", "drift_fit", "drift_index", "drift_windows",
            "drift_workspace_bytes", "DRIFT_DTYPE", "DRIFT_F_NONE", "DRIFT_F_RANGE", "DRIFT_WINDOW", "DRIFT_MIN_CORR",
            "DRIFT_MAX_E", "DRIFT_MAX_WINDOWS",

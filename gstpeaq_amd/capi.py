@@ -84,6 +84,21 @@ DRIFT_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("a", "<f8"), ("e", "
 DELAY_DTYPE = np.dtype([("lag", "<i4"), ("reserved", "<i4"), ("peak", "<f8"), ("runner_up", "<f8"), ("norm", "<f8")])
 
 
+class Track(C.Structure):
+    """mirrors peaq_track (include/peaq_amd.h)"""
+    _fields_ = [("lag0", C.c_int32), ("flags", C.c_uint32), ("n_windows", C.c_uint32), ("n_valid", C.c_uint32),
+                ("n_filled", C.c_uint32), ("n_segments", C.c_uint32), ("d_min", C.c_double), ("d_max", C.c_double),
+                ("max_abs_e", C.c_double)]
+
+
+# PEAQ_TRACK_* (include/peaq_amd.h), the record as a numpy structured dtype, and this binding's default window
+TRACK_F_NONE, TRACK_F_RANGE = 1, 2
+TRACK_MAX_E, TRACK_MAX_STEP, TRACK_MAX_SEGMENTS_PER_CALL = 1 / 64, 1 / 256, 1 << 20
+TRACK_WINDOW = 16384
+TRACK_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("n_windows", "<u4"), ("n_valid", "<u4"), ("n_filled", "<u4"),
+                        ("n_segments", "<u4"), ("d_min", "<f8"), ("d_max", "<f8"), ("max_abs_e", "<f8")])
+
+
 class FrameTrace(C.Structure):
     """mirrors peaq_frame_trace (include/peaq_amd.h)"""
     _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
@@ -314,6 +329,25 @@ def load_library():
         L.peaq_batch_cut_drift.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, dp, dp, vp, C.c_size_t, vp]
         L.peaq_run_pair_drift.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_double, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Drift),
+                                          C.POINTER(Gain), dp]
+    if hasattr(L, "peaq_batch_cut_track"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        L.peaq_track_size.restype = C.c_size_t
+        L.peaq_track_size.argtypes = []
+        L.peaq_track_fit.argtypes = [dp, u8p, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(Track), dp, dp, dp]
+        L.peaq_track_segment.restype = C.c_uint32
+        L.peaq_track_segment.argtypes = [C.c_int64, C.c_uint32, C.c_uint32]
+        L.peaq_track_index.restype = None
+        L.peaq_track_index.argtypes = [C.c_uint32, C.c_uint32, dp, dp, C.c_int64, C.POINTER(C.c_int64), i32p]
+        L.peaq_track_lengths.restype = None
+        L.peaq_track_lengths.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, dp, dp, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+        L.peaq_batch_estimate_track.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32, i32p,
+                                                C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, vp, vp,
+                                                C.POINTER(Drift), C.POINTER(Track), dp, C.c_uint32, dp, dp, vp]
+        L.peaq_batch_cut_track.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, C.c_uint32, u32p,
+                                           C.c_uint32, dp, dp, vp, C.c_size_t, vp]
+        L.peaq_run_pair_track.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_double, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Track),
                                           C.POINTER(Gain), dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
@@ -1021,7 +1055,153 @@ def cut_drift(ctx, x, skip, n_keep, a, e, n_in=None, out=None, stream=None):
     return out
 
 
-def _need_align(subsample, align, drift=False):
+def track_fit(d, valid=None, window=TRACK_WINDOW, max_e=TRACK_MAX_E):
+    """The per-window delays d kept as a track (peaq_track_fit, host arithmetic, no GPU).  Returns a dict: the record's
+    fields (flags, n_windows, n_valid, n_filled, n_segments, d_min, d_max, max_abs_e) and the arrays knots [W], a and e
+    [max(W - 1, 1)]."""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    assert d.ndim == 1
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(valid, dtype=np.uint8)
+        assert v.shape == d.shape
+    W = len(d)
+    knots, a, e = np.zeros(max(W, 1)), np.zeros(max(W - 1, 1)), np.zeros(max(W - 1, 1))
+    rec = Track()
+    dp = C.POINTER(C.c_double)
+    _check(load_library().peaq_track_fit(d.ctypes.data_as(dp), v.ctypes.data_as(C.POINTER(C.c_uint8)) if v is not None else None,
+                                         W, int(window), float(max_e), C.byref(rec), knots.ctypes.data_as(dp),
+                                         a.ctypes.data_as(dp), e.ctypes.data_as(dp)))
+    res = {k: getattr(rec, k) for k, _ in Track._fields_ if k != "lag0"}
+    res.update(knots=knots[:W], a=a, e=e)
+    return res
+
+
+def track_segment(i, window, n_seg):
+    """the segment output i belongs to (peaq_track_segment, host arithmetic, no GPU)"""
+    return int(load_library().peaq_track_segment(int(i), int(window), int(n_seg)))
+
+
+def track_index(window, a, e, i):
+    """(m, phi): where output i of the track cut reads, a and e the pair's segments (peaq_track_index, host arithmetic)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    assert a.ndim == 1 and a.shape == e.shape and len(a) >= 1
+    m, phi = C.c_int64(0), C.c_int32(0)
+    dp = C.POINTER(C.c_double)
+    load_library().peaq_track_index(int(window), len(a), a.ctypes.data_as(dp), e.ctypes.data_as(dp), int(i), C.byref(m),
+                                    C.byref(phi))
+    return m.value, phi.value
+
+
+def track_lengths(lag0, window, a, e, n_ref, n_test):
+    """(skip_ref, skip_test, n_keep) for one pair's lag and segments (peaq_track_lengths, host arithmetic, no GPU)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    assert a.ndim == 1 and a.shape == e.shape and len(a) >= 1
+    sr, st, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    dp = C.POINTER(C.c_double)
+    load_library().peaq_track_lengths(int(lag0), int(window), len(a), a.ctypes.data_as(dp), e.ctypes.data_as(dp), int(n_ref),
+                                      int(n_test), C.byref(sr), C.byref(st), C.byref(n))
+    return sr.value, st.value, n.value
+
+
+def _track_window(track):
+    """the window of a `track=` keyword: True is the default window"""
+    return TRACK_WINDOW if track is True else int(track)
+
+
+def estimate_track(ctx, ref, test, lags, n_ref=None, n_test=None, window=TRACK_WINDOW, R=None, min_corr=DRIFT_MIN_CORR,
+                   max_e=TRACK_MAX_E, stream=None):
+    """Every pair's delay as a track in the coordinates its lag aligns (peaq_batch_estimate_track); arguments as
+    estimate_drift's.  Returns a dict of numpy arrays [n_pairs]: the fields of TRACK_DTYPE; knots [n_pairs, w_max]; a, e
+    [n_pairs, seg_stride] (row p holds n_segments[p] segments); `windows`, the per-window records as estimate_drift's;
+    and `drift`, the line's record as estimate_drift returns it (without windows).  Blocks until the records are there."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    a_lag = np.ascontiguousarray(lags, dtype=np.int32)
+    assert a_lag.shape == (n_pairs,)
+    window = int(window)
+    R = min(window // 4, 1024) if R is None else int(R)
+    L = ctx.L
+    assert L.peaq_track_size() == C.sizeof(Track) == TRACK_DTYPE.itemsize
+    w_max = max([1] + [int(L.peaq_drift_windows(int(a_lag[p]), int(stride if a_ref is None else a_ref[p]),
+                                                int(stride if a_test is None else a_test[p]), window))
+                       for p in range(n_pairs)])
+    seg_stride = max(w_max - 1, 1)
+    with _torch_stream(stream):
+        d_dl = torch.zeros((max(n_pairs, 1), w_max, C.sizeof(Delay)), dtype=torch.uint8, device=ref.device)
+        d_sb = torch.zeros((max(n_pairs, 1), w_max, C.sizeof(SubDelay)), dtype=torch.uint8, device=ref.device)
+    out = np.zeros(max(n_pairs, 1), dtype=TRACK_DTYPE)
+    line = np.zeros(max(n_pairs, 1), dtype=DRIFT_DTYPE)
+    knots = np.zeros((max(n_pairs, 1), w_max))
+    seg_a, seg_e = np.zeros((max(n_pairs, 1), seg_stride)), np.zeros((max(n_pairs, 1), seg_stride))
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    _check(L.peaq_batch_estimate_track(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()),
+                                       stride, a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                       a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                       a_lag.ctypes.data_as(C.POINTER(C.c_int32)), window, R, float(min_corr), float(max_e),
+                                       w_max, C.c_void_p(d_dl.data_ptr()), C.c_void_p(d_sb.data_ptr()),
+                                       line.ctypes.data_as(C.POINTER(Drift)), out.ctypes.data_as(C.POINTER(Track)),
+                                       knots.ctypes.data_as(dp), seg_stride, seg_a.ctypes.data_as(dp), seg_e.ctypes.data_as(dp),
+                                       _stream_ptr(stream)))
+    _sync_stream(stream, ref.device)
+    res = {k: np.ascontiguousarray(out[k][:n_pairs]) for k in TRACK_DTYPE.names}
+    res.update(knots=knots[:n_pairs], a=seg_a[:n_pairs], e=seg_e[:n_pairs], window=window)
+    res["drift"] = {k: np.ascontiguousarray(line[k][:n_pairs]) for k in DRIFT_DTYPE.names}
+    dl = d_dl.cpu().numpy()[:n_pairs].copy().view(DELAY_DTYPE)[:, :, 0]
+    sb = d_sb.cpu().numpy()[:n_pairs].copy().view(SUBDELAY_DTYPE)[:, :, 0]
+    res["windows"] = dict(lag=np.ascontiguousarray(dl["lag"]), peak=np.ascontiguousarray(dl["peak"]),
+                          runner_up=np.ascontiguousarray(dl["runner_up"]), norm=np.ascontiguousarray(dl["norm"]),
+                          q=np.ascontiguousarray(sb["q"]), sub_peak=np.ascontiguousarray(sb["peak"]),
+                          c0=np.ascontiguousarray(sb["c0"]), sub_flags=np.ascontiguousarray(sb["flags"]))
+    return res
+
+
+def cut_track(ctx, x, skip, n_keep, window, n_seg, a, e, n_in=None, out=None, stream=None):
+    """cut along every pair's track (peaq_batch_cut_track): as cut_drift, with (m_i, phi_i) = track_index(window,
+    a[p, :n_seg[p]], e[p, :n_seg[p]], i); a, e: [n_pairs, seg_stride].  A pair whose segments are all (0, 0) has its bits
+    moved.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    a_seg = np.ascontiguousarray(n_seg, dtype=np.uint32)
+    a_a = np.ascontiguousarray(a, dtype=np.float64)
+    a_e = np.ascontiguousarray(e, dtype=np.float64)
+    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,) and a_seg.shape == (n_pairs,)
+    assert a_a.ndim == 2 and a_a.shape[0] == n_pairs and a_a.shape == a_e.shape
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    _check(ctx.L.peaq_batch_cut_track(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
+                                      a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), int(window),
+                                      a_seg.ctypes.data_as(u32p), a_a.shape[1], a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp),
+                                      C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
+
+
+def _need_align(subsample, align, drift=False, track=False):
+    if track and drift:
+        raise PeaqError("track= and drift= exclude each other: the track's segments are the lines, one per window")
+    if track and subsample:
+        raise PeaqError("track= and subsample=True exclude each other: the track's knots carry the sub-sample part")
+    if track and align is None:
+        raise PeaqError("track= requires align= (a max_lag): the track is measured around an integer lag")
     if subsample and drift:
         raise PeaqError("drift= and subsample=True exclude each other: the line's offset a carries the sub-sample part")
     if subsample and align is None:
@@ -1031,7 +1211,7 @@ def _need_align(subsample, align, drift=False):
 
 
 def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-          subsample=False, drift=False):
+          subsample=False, drift=False, track=False):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
     gain: 'lsq' 'rms' 'polarity': the test signal's gain is measured over that part and applied in its cut
     (measure_gain, cut_scaled); the record tensor is kept as align.last_gain.
@@ -1041,7 +1221,14 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None,
     drift: True or a window: each pair's delay is fitted as a line around its lag (estimate_drift, records kept as
     align.last_drift), both signals are cut to drift_lengths and the test signal is resampled along the line
     (cut_drift); a gain is then measured on the two CUT buffers, as with subsample, which drift excludes.
+    track: True or a window: each pair's delay is kept as a track of per-window delays around its lag (estimate_track,
+    records kept as align.last_track), both signals are cut to track_lengths and the test signal is resampled along the
+    track (cut_track); a gain is then measured on the two CUT buffers.  Excludes drift and subsample.
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
+    if track:
+        _need_align(subsample, 0, drift, track)
+        return _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db,
+                            _track_window(track))
     if drift:
         return _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db,
                             _drift_window(drift), subsample)
@@ -1109,15 +1296,46 @@ def _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_cha
     return bufs[0], bufs[1], n, n.copy()
 
 
+def _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
+    """align(..., track=window)"""
+    import torch
+    n_pairs, stride, _ = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
+    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
+    tr = estimate_track(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
+    align.last_track = tr
+    n_seg = tr["n_segments"]
+    cuts = np.array([track_lengths(int(lags[p]), window, tr["a"][p, :n_seg[p]], tr["e"][p, :n_seg[p]], int(a_ref[p]),
+                                   int(a_test[p])) for p in range(n_pairs)], dtype=np.uint32).reshape(n_pairs, 3)
+    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
+    with _torch_stream(stream):
+        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
+                for _ in range(3 if gain is not None else 2)]
+    n = np.ascontiguousarray(cuts[:, 2])
+    cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
+    cut_track(ctx, test, cuts[:, 1], n, window, n_seg, tr["a"], tr["e"], n_in=a_test, out=bufs[1], stream=stream)
+    if gain is not None:
+        rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
+                              per_channel=gain_per_channel, stream=stream)
+        cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
+        align.last_gain = rec
+        return bufs[0], bufs[2], n, n.copy()
+    return bufs[0], bufs[1], n, n.copy()
+
+
 def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
-             subsample=False, drift=False):
+             subsample=False, drift=False, track=False):
     """the `align=`, `gain=` and `subsample=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without
     align: lags of 0), then refine, match and cut"""
-    _need_align(subsample, max_lag, drift)
+    _need_align(subsample, max_lag, drift, track)
     if max_lag is not None:
         lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
     else:
         lags = np.zeros(ref.shape[0], dtype=np.int32)
+    if track:
+        return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
+                     max_gain_db=max_gain_db, track=track)
     if drift:
         return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
                      max_gain_db=max_gain_db, drift=drift)
@@ -1132,8 +1350,11 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
               stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-              subsample=False, drift=False):
+              subsample=False, drift=False, track=False):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    track: True or a window, with align: every pair's delay is kept as a track of per-window delays and the test signal
+    is resampled along it (estimate_track, cut_track; align.last_track); a gain is then measured after that cut.
+    Excludes drift and subsample.
     drift: True or a window, with align: every pair's delay is fitted as a line and the test signal is resampled along
     it (estimate_drift, cut_drift; align.last_drift); a gain is then measured after that cut.  Excludes subsample.
     subsample: with align, the sub-sample part of every pair's delay is estimated and removed from the test signal too
@@ -1148,8 +1369,11 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align, drift)
-    if drift:
+    _need_align(subsample, align, drift, track)
+    if track:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            track=track)
+    elif drift:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
                                             drift=drift)
     elif subsample:
@@ -1370,17 +1594,31 @@ def _subdelay_dict(rec):
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
-             max_gain_db=40.0, subsample=False, drift=False):
+             max_gain_db=40.0, subsample=False, drift=False, track=False):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
     the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`.
-    drift: True or a window, with align: peaq_run_pair_drift; the result dict carries the line's record as `drift`."""
+    drift: True or a window, with align: peaq_run_pair_drift; the result dict carries the line's record as `drift`.
+    track: True or a window, with align: peaq_run_pair_track; the result dict carries the track's record as `track`."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
-    _need_align(subsample, align, drift)
+    _need_align(subsample, align, drift, track)
+    if track:                                          # peaq_run_pair_track; the records as `delay`, `track`, `gain`
+        rec, trec, grec = Delay(), Track(), Gain()
+        _check(ctx.L.peaq_run_pair_track(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
+                                         _track_window(track), gain_mode(gain, gain_per_channel), float(max_gain_db),
+                                         ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                         test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
+                                         C.byref(trec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["track"] = {k: getattr(trec, k) for k, _ in Track._fields_}
+        if gain is not None:
+            res["gain"] = _gain_dict(grec)
+        return res
     if drift:                                          # peaq_run_pair_drift; the records as `delay`, `drift`, `gain`
         rec, drec, grec = Delay(), Drift(), Gain()
         _check(ctx.L.peaq_run_pair_drift(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),

@@ -550,6 +550,11 @@ usage (const char *prog)
       "                samples (4096..1048576, default 32768) is measured, one line fitted through them and the test\n"
       "                signal resampled along it; prints the line; excludes --align-subsample, which it subsumes\n"
       "                (the plain one-call mode; not with --list, --interval or --trace)\n"
+      "  --align-track[=WINDOW] --align, and a delay that bends or steps too (two clocks one after the other, a loop\n"
+      "                whose clock wanders, a player that re-synchronised): the delay of every WINDOW samples\n"
+      "                (4096..1048576, default 16384) is measured and kept as a track, and the test signal is resampled\n"
+      "                along it; prints the track's range; excludes --align-drift and --align-subsample, which it\n"
+      "                subsumes (the plain one-call mode; not with --list, --interval or --trace)\n"
       "  --match-gain[=lsq|rms|polarity] match the test file's level (polarity) to the reference's on the GPU, after\n"
       "                --align if given, and print the gain applied (default lsq; the plain one-call mode and --list;\n"
       "                not with --interval or --trace)\n"
@@ -643,6 +648,8 @@ main (int argc, char **argv)
   peaq_subdelay subdelay;
   uint32_t drift_window = 0;    /* != 0: --align-drift, peaq_run_pair_drift (implies --align) */
   peaq_drift drift;
+  uint32_t track_window = 0;    /* != 0: --align-track, peaq_run_pair_track (implies --align) */
+  peaq_track track;
   peaq_delay delay;
   peaq_gain gain;
   int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
@@ -708,6 +715,21 @@ main (int argc, char **argv)
       if (!align_lag)
         align_lag = 4096;
     }
+    else if (!strcmp (argv[i], "--align-track")) {
+      track_window = 16384;
+      if (!align_lag)
+        align_lag = 4096;
+    } else if (!strncmp (argv[i], "--align-track=", 14)) {
+      char *end;
+      const long v = strtol (argv[i] + 14, &end, 10);
+      if (*end || end == argv[i] + 14 || v < 4096 || v > 1048576) {
+        fprintf (stderr, "Failed to initialize: invalid track window %s (4096 .. 1048576 samples)\n", argv[i] + 14);
+        return 1;
+      }
+      track_window = (uint32_t) v;
+      if (!align_lag)
+        align_lag = 4096;
+    }
     else if (!strcmp (argv[i], "--match-gain") || !strcmp (argv[i], "--match-gain=lsq"))
       gain_mode = PEAQ_GAIN_LSQ;
     else if (!strcmp (argv[i], "--match-gain=rms"))
@@ -763,6 +785,22 @@ main (int argc, char **argv)
     gain_mode |= PEAQ_GAIN_PER_CHANNEL;
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
+  if (track_window && drift_window) {
+    fprintf (stderr, "Failed to initialize: --align-track and --align-drift exclude each other: the track's segments are the lines, one per window\n");
+    return 1;
+  }
+  if (track_window && subsample) {
+    fprintf (stderr, "Failed to initialize: --align-track and --align-subsample exclude each other: the track's knots carry the sub-sample part\n");
+    return 1;
+  }
+  if (track_window && list_path) {
+    fprintf (stderr, "Failed to initialize: --align-track is not taken with --list: the host-fed path does not take it yet (whole-sample --align only)\n");
+    return 1;
+  }
+  if (track_window && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --align-track belongs to the plain one-call mode (not with --interval or --trace)\n");
     return 1;
   }
   if (drift_window && subsample) {
@@ -890,6 +928,20 @@ main (int argc, char **argv)
     if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
+    } else if (track_window) {
+      char text[256];
+      if (peaq_run_pair_track (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, track_window,
+              gain_mode, max_gain_db, ref.samples, ref.frames, test.samples, test.frames, &delay, &track, &gain, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d samples, track %+.4f .. %+.4f (%u of %u windows%s)\n", (int) delay.lag, track.d_min, track.d_max,
+          (unsigned) track.n_valid, (unsigned) track.n_windows,
+          (track.flags & PEAQ_TRACK_F_NONE) ? ", no track: no valid window" : (track.flags & PEAQ_TRACK_F_RANGE) ? ", slope out of range: not corrected" : "");
+      if (gain_mode) {
+        format_gain (text, sizeof text, &gain, ref.channels);
+        printf ("Gain: %s\n", text);
+      }
     } else if (drift_window) {
       char text[256];
       if (peaq_run_pair_drift (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, drift_window,

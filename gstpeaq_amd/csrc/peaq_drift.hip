@@ -239,12 +239,11 @@ extern "C" size_t peaq_drift_workspace_bytes(int channels, int n_pairs, uint32_t
   return drift_groups(channels, n_pairs, window, w_max).bytes;
 }
 
-extern "C" int peaq_batch_estimate_drift(peaq_ctx* c, int channels, int n_pairs, const float* d_ref, const float* d_test,
-                                         size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
-                                         uint32_t n_uniform, const int32_t* lag0, uint32_t window, uint32_t R,
-                                         double min_corr, double max_e, uint32_t w_max, peaq_delay* d_win_delay,
-                                         peaq_subdelay* d_win_sub, peaq_drift* out, void* stream_) {
-  const std::string w("peaq_batch_estimate_drift");
+// peaq_batch_estimate_drift under the name `w` of the entry point that was called (peaq_track.hip's estimate is this one's)
+int drift_estimate(const std::string& w, peaq_ctx* c, int channels, int n_pairs, const float* d_ref, const float* d_test,
+                   size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform, const int32_t* lag0,
+                   uint32_t window, uint32_t R, double min_corr, double max_e, uint32_t w_max, peaq_delay* d_win_delay,
+                   peaq_subdelay* d_win_sub, peaq_drift* out, void* stream_) {
   const DriftParams prm{window, R, min_corr, max_e};
   if (int rc = check_drift_params(w, prm)) return rc;
   if (int rc = check_shape(w, channels, n_pairs)) return rc;
@@ -312,6 +311,15 @@ extern "C" int peaq_batch_estimate_drift(peaq_ctx* c, int channels, int n_pairs,
       drift_record(lag0[p0 + p], W[p0 + p], &dl[(size_t)p * w_max], &sb[(size_t)p * w_max], prm, &out[p0 + p]);
   }
   return PEAQ_OK;
+}
+
+extern "C" int peaq_batch_estimate_drift(peaq_ctx* c, int channels, int n_pairs, const float* d_ref, const float* d_test,
+                                         size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test,
+                                         uint32_t n_uniform, const int32_t* lag0, uint32_t window, uint32_t R,
+                                         double min_corr, double max_e, uint32_t w_max, peaq_delay* d_win_delay,
+                                         peaq_subdelay* d_win_sub, peaq_drift* out, void* stream_) {
+  return drift_estimate("peaq_batch_estimate_drift", c, channels, n_pairs, d_ref, d_test, pair_stride, n_ref, n_test, n_uniform,
+                        lag0, window, R, min_corr, max_e, w_max, d_win_delay, d_win_sub, out, stream_);
 }
 
 extern "C" int peaq_batch_cut_drift(peaq_ctx* c, int channels, int n_pairs, const float* d_in, size_t in_stride,

@@ -18,6 +18,8 @@
 //   peaq_frac.hip     sub-sample delay estimate and fractional-delay cut behind the integer aligner (kernels and host side)
 //   peaq_drift.hip    constant drift: per-window delays through the two stages above, the robust line fit (host), the
 //                     test signal's cut along the line (kernel and host side)
+//   peaq_track.hip    delay track: the drift stage's per-window delays kept as knots and segments (host), the test
+//                     signal's cut along them (kernel and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -199,6 +201,11 @@ void frac_release(peaq_ctx* c);
 // the sub-sample stage's shift table on the device and its length slots, for the drift cut (peaq_frac.hip; the caller
 // holds the context's lock)
 int frac_shift_table(peaq_ctx* c, const double** shift, struct LenStage** lens);
+// peaq_batch_estimate_drift with `who` naming the entry point in its refusals, for the track stage (peaq_drift.hip)
+int drift_estimate(const std::string& who, peaq_ctx* c, int channels, int n_pairs, const float* d_ref, const float* d_test,
+                   size_t pair_stride, const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform, const int32_t* lag0,
+                   uint32_t window, uint32_t R, double min_corr, double max_e, uint32_t w_max, peaq_delay* d_win_delay,
+                   peaq_subdelay* d_win_sub, peaq_drift* out, void* stream);
 // mode (PEAQ_GAIN_* with or without PEAQ_GAIN_PER_CHANNEL) and max_gain_db as every entry point of the stage takes them
 int check_gain_mode(const std::string& who, int mode, double max_gain_db);
 // max_lag of the aligner, 1 .. 16384 (peaq_align.hip)
@@ -378,7 +385,7 @@ inline int check_lengths(const std::string& who, int n_pairs, const uint32_t* n,
 }
 
 // ---------------------------------------------------------------------------
-// The steps of the one-pair conveniences (peaq_run_pair_rate, _aligned, _matched, _trace, _subsample, _drift), defined in
+// The steps of the one-pair conveniences (peaq_run_pair_rate, _aligned, _matched, _trace, _subsample, _drift, _track), defined in
 // peaq_align.hip.  Each of them blocks; the stage calls between them are the entry point's own.
 // ---------------------------------------------------------------------------
 // (a) what every peaq_run_pair_* call checks, beside check_level where it looks at the level: channels, rate, ctx and
@@ -401,7 +408,7 @@ int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, con
                    size_t stride, uint32_t len_ref, uint32_t len_test, peaq_result* out);
 
 // ---------------------------------------------------------------------------
-// DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip, peaq_drift.hip and peaq_gather.hip share
+// DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip, peaq_drift.hip, peaq_track.hip and peaq_gather.hip share
 // (256 threads per workgroup).  No kernel is defined in this header.
 // ---------------------------------------------------------------------------
 // A workgroup's share of the copy of `count` consecutive floats from src to dst: the 16-byte units v0 .. v0 + 255,

@@ -430,7 +430,7 @@ int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playba
  * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
  * their common, aligned part, as a stage in front of peaq_batch_run / peaq_batch_run_trajectory.  Integer lags only
  * here (the constant sub-sample part: "sub-sample delay on the device", a constant drift: "constant drift on the
- * device", both further down; delays that are no straight line are not handled anywhere), one lag per pair for
+ * device", a delay that bends: "delay track on the device", all further down), one lag per pair for
  * all channels; level and polarity are matched by the stage further down ("level and polarity matching on the device").
  *
  *   For one pair with n_ref / n_test samples per channel:
@@ -715,9 +715,9 @@ size_t peaq_feed_matched_workspace_bytes (const peaq_feed *feed, int advanced, i
  * samples around the given integer lag, and peaq_batch_cut_shifted is peaq_batch_cut of the test signal through the
  * fractional-delay filter of that grid point.  Only the test signal is ever shifted; the reference is never changed.
  * With lag < 0 the test signal keeps skip = 0 and is still shifted by q.  A delay that grows steadily is the next
- * stage's ("constant drift on the device").  Not done, here or anywhere: delay tracks that are no straight line,
- * shifts finer than the grid, and the host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to
- * whole samples only.
+ * stage's ("constant drift on the device"), one that bends the one after ("delay track on the device").  Not done,
+ * here or anywhere: steps of the delay sharper than a window of the track, shifts finer than the grid, and the
+ * host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
  *
  *   w_H (x) = I0 (beta sqrt (1 - (x / H)^2)) / I0 (beta) for |x| < H, else 0; beta = 8.49, the converter's Kaiser window.
  *   sinc (x) = sin (pi x) / (pi x), sinc (0) = 1.  I0 is evaluated in double by the Chebyshev expansions of the Cephes
@@ -805,8 +805,9 @@ int peaq_run_pair_subsample (peaq_ctx *ctx, int advanced, int channels, double p
  * steadily: at 100 ppm by 48 samples over 10 s.  One lag leaves most of such an item misaligned, and PEAQ scores that as
  * distortion.  This stage models the delay of a pair as ONE straight line, fits it robustly from per-window delays that
  * the two stages above measure, and resamples the test signal along it through shift_tab.  Only the test signal is
- * changed.  Not done, here or anywhere: delays that are no straight line (per-window tracks, piecewise cuts), and the
- * host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
+ * changed.  A delay that is no straight line is the next stage's ("delay track on the device").  Not done, here or
+ * anywhere: steps of the delay sharper than a window of that track, and the host-fed pipelines
+ * (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
  *
  *   Coordinates.  lag0 = the pair's lag from peaq_batch_estimate_delay over the whole signals; peaq_aligned_lengths
  *   (lag0, ...) gives skip_ref, skip_test and n_common; A_ref[i] = ref[skip_ref + i], A_test[i] = test[skip_test + i].
@@ -900,6 +901,106 @@ int peaq_run_pair_drift (peaq_ctx *ctx, int advanced, int channels, double playb
                          uint32_t max_lag, uint32_t window, int mode, double max_gain_db,
                          const float *ref, size_t n_ref, const float *test, size_t n_test,
                          peaq_delay *delay /* host */, peaq_drift *drift /* host */, peaq_gain *gain /* host */,
+                         peaq_result *out);
+
+/* ---- delay track on the device ------------------------------------------------
+ * Material that passed two clocks one after the other, a loop whose clock wanders, a player that re-synchronised once:
+ * their delay bends or steps, and one line leaves part of the item misaligned.  This stage keeps the per-window delays
+ * that the drift stage measures as a TRACK -- a knot per window, a line from every knot to the next -- and resamples
+ * the test signal along it through shift_tab.  Only the test signal is changed.  Not done, here or anywhere: steps
+ * sharper than a window (a step is spread over the window it falls in), and the host-fed pipelines
+ * (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
+ *
+ *   Coordinates, windows, d_w = lag_w + q_w / 256, x_w = w window + window / 2 (the integer half) and the validity rule
+ *   are those of "constant drift on the device".  The fit takes d[W], valid[W], window and max_e; host, FP64, every
+ *   operation rounded on its own.  line (u1, u2, x1, x2, x0) = u1 + (u1 - u2) / (x1 - x2) * (x0 - x1).
+ *   1. V_0 < ... < V_{nv-1} are the valid windows, u_j = d[V_j].  nv == 0: PEAQ_TRACK_F_NONE, every knot and segment 0.
+ *   2. Outliers (nv >= 3; else t = u): a running median of three over the raw u.  t_j = med3 (u_{j-1}, u_j, u_{j+1})
+ *      inside; t_0 = med3 (u_0, u_1, line (u_1, u_2, x_{V_1}, x_{V_2}, x_{V_0})) and the mirror image at the other end;
+ *      med3 is the middle one by value.  Values on a line (a constant drift) pass unchanged, as does the inside of any
+ *      monotone sequence (an end of one moves at most onto the line through its two neighbours); a step survives,
+ *      one wild window does not.
+ *   3. Knots: s_w = t_j at w = V_j; between V_j and V_{j+1} s_w = line (t_j, t_{j+1}, x_{V_j}, x_{V_{j+1}}, x_w); before
+ *      the first and behind the last valid window that one's value.  n_filled counts the invalid windows.
+ *   4. Segments: S = max (W - 1, 1); e_k = (s_{k+1} - s_k) / (double) window, a_k = s_k - e_k x_k; W == 1: e_0 = 0, a_0 =
+ *      s_0.  Output i belongs to segment k (i) = i < window / 2 ? 0 : min ((i - window / 2) / window, S - 1), integers:
+ *      the first and the last segment extend to the ends of the pair.
+ *   5. Range: any |e_k| > max_e (0 < max_e <= PEAQ_TRACK_MAX_E): PEAQ_TRACK_F_RANGE, every a_k and e_k 0 (the pair is cut
+ *      as peaq_batch_cut cuts it); the knots, d_min, d_max and max_abs_e stay readable.
+ *   6. Output i reads at peaq_drift_index (a_{k (i)}, e_{k (i)}, i): the same FP64 operations on host and device.
+ *   A pair's record depends on nothing but the pair and repeats bit for bit. */
+#define PEAQ_TRACK_MAX_E       0.015625   /* 1 / 64 */
+#define PEAQ_TRACK_MAX_STEP    0.00390625 /* 1 / 256: how far two segments may be apart where they meet, for the cut */
+#define PEAQ_TRACK_F_NONE   1   /* no valid window */
+#define PEAQ_TRACK_F_RANGE  2   /* an |e_k| > max_e */
+#define PEAQ_TRACK_MAX_SEGMENTS_PER_CALL (1u << 20)   /* summed over the pairs of one peaq_batch_cut_track: 16 MiB of staging */
+typedef struct {               /* 48 bytes */
+  int32_t  lag0;               /* as given */
+  uint32_t flags;
+  uint32_t n_windows, n_valid;
+  uint32_t n_filled, n_segments;
+  double   d_min, d_max;       /* over the knots, samples */
+  double   max_abs_e;          /* the steepest segment, also where it is out of range */
+} peaq_track;
+size_t peaq_track_size (void);
+/* Host only.  The fit above: d, valid (NULL: all valid) of n_windows <= PEAQ_DRIFT_MAX_WINDOWS entries, knots of
+ * n_windows, a and e of max (n_windows - 1, 1).  out->lag0 is set to 0.  PEAQ_ERR_ARG: a NULL array, a window out of
+ * 4096 .. 2^20 (odd ones are taken), too many windows, a max_e outside (0, 1 / 64]. */
+int peaq_track_fit (const double *d, const uint8_t *valid, uint32_t n_windows, uint32_t window, double max_e,
+                    peaq_track *out, double *knots, double *a, double *e);
+/* Host only.  k (i) of item 4 for n_seg >= 1 segments (0 for n_seg == 0 or window == 0). */
+uint32_t peaq_track_segment (int64_t i, uint32_t window, uint32_t n_seg);
+/* Host only.  Item 6: peaq_drift_index along the segment of i. */
+void peaq_track_index (uint32_t window, uint32_t n_seg, const double *a, const double *e, int64_t i, int64_t *m,
+                       int32_t *phi);
+/* Host only.  peaq_drift_lengths with the track in the line's place: *n_keep is the largest count <= n_common with
+ * skip_test + i + m_i < n_test for every i below it.  i + m_i does not decrease with i where every |e_k| <= 1 / 64 and
+ * neighbouring segments meet within PEAQ_TRACK_MAX_STEP, as the fit's do (gstpeaq_amd/csrc/peaq_track_math.h has the
+ * argument); for other segments the count is that of a binary search over i. */
+void peaq_track_lengths (int32_t lag0, uint32_t window, uint32_t n_seg, const double *a, const double *e,
+                         uint32_t n_ref, uint32_t n_test, uint32_t *skip_ref, uint32_t *skip_test, uint32_t *n_keep);
+/* peaq_batch_estimate_drift (same arguments up to d_win_sub; its max_e is PEAQ_DRIFT_MAX_E whatever max_e is here),
+ * then the two record arrays are read back and the fit above runs per pair: the window records are
+ * peaq_batch_estimate_delay's and peaq_batch_refine_delay's on the slices bit for bit, and the line's record comes out
+ * beside the track's (drift: host, [n_pairs], may be NULL).  out: host [n_pairs]; knots: host [n_pairs][w_max]; a, e:
+ * host [n_pairs][seg_stride], row p holding out[p].n_segments entries (knots and segments behind a pair's own are 0).
+ * The call BLOCKS, as the drift estimate does.
+ * Refusals as peaq_batch_estimate_drift's, and: a seg_stride below w_max - 1 or below 1, a max_e outside (0, 1 / 64],
+ * NULL out, knots, a or e. */
+int peaq_batch_estimate_track (peaq_ctx *ctx, int channels, int n_pairs,
+                               const float *d_ref, const float *d_test, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                               const int32_t *lag0 /* host */, uint32_t window, uint32_t R, double min_corr, double max_e,
+                               uint32_t w_max, peaq_delay *d_win_delay /* device */, peaq_subdelay *d_win_sub /* device */,
+                               peaq_drift *drift /* host, [n_pairs], may be NULL */, peaq_track *out /* host, [n_pairs] */,
+                               double *knots /* host */, uint32_t seg_stride, double *a /* host */, double *e /* host */,
+                               void *stream);
+/* peaq_batch_cut of the test signal along each pair's track (n_seg[p] segments in row p of a and e, host arrays):
+ * out[p][i][c] = (float) sum_{o = -32 .. 32} shift_tab[phi_i][o] (double) in[p][skip[p] + i + m_i + o][c] for
+ * i < n_keep[p], (m_i, phi_i) = peaq_track_index (window, n_seg[p], a[p], e[p], i): fused multiply-adds in the order
+ * o = -32 .. 32 in FP64, rounded once to FP32.  A tap whose index falls outside [0, n_in[p]) contributes nothing.
+ * Samples of d_out past n_keep[p] are left as they were.  A pair whose segments all hold the same (a, e), |e| <=
+ * PEAQ_DRIFT_MAX_E, is bit for bit peaq_batch_cut_drift's output (so with e = 0 and a = q / 256 peaq_batch_cut_shifted's);
+ * a pair whose segments are all (0, 0) has its bits moved as they are (peaq_batch_cut's) and does not look at n_in[p].
+ * All per-pair arrays and the segments travel through the pinned staging slots.
+ * Refusals as peaq_batch_cut_drift's, and: an a or e that is not finite, |a| > PEAQ_DRIFT_MAX_A, |e| >
+ * PEAQ_TRACK_MAX_E, an n_seg of 0 or above seg_stride, a window out of 4096 .. 2^20, more than
+ * PEAQ_TRACK_MAX_SEGMENTS_PER_CALL segments in all, neighbouring segments more than PEAQ_TRACK_MAX_STEP apart where
+ * they meet (the kernel's staged span is sized for lines that meet), NULL n_seg, a or e. */
+int peaq_batch_cut_track (peaq_ctx *ctx, int channels, int n_pairs,
+                          const float *d_in, size_t in_stride, const uint32_t *n_in /* host */,
+                          const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                          uint32_t window, const uint32_t *n_seg /* host */, uint32_t seg_stride,
+                          const double *a /* host */, const double *e /* host */,
+                          float *d_out, size_t out_stride, void *stream);
+/* peaq_run_pair_drift with the track in the line's place: peaq_batch_estimate_track (window, R = min (window / 4, 1024),
+ * min_corr 0.5, max_e 1 / 64); peaq_track_lengths; plain cut of the reference to n_keep; track cut of the test signal;
+ * the gain, if any, measured AFTER the cut.  A flagged record (every segment 0) scores what peaq_run_pair_aligned
+ * scores.  delay, track and gain (host) may be NULL. */
+int peaq_run_pair_track (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                         uint32_t max_lag, uint32_t window, int mode, double max_gain_db,
+                         const float *ref, size_t n_ref, const float *test, size_t n_test,
+                         peaq_delay *delay /* host */, peaq_track *track /* host */, peaq_gain *gain /* host */,
                          peaq_result *out);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
