@@ -18,6 +18,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    SUB_LAGS, SUB_HALF, SUB_F_NONE, SUB_F_EDGE,
                    Track, TRACK_DTYPE, TRACK_F_NONE, TRACK_F_RANGE, TRACK_MAX_E, TRACK_MAX_STEP, TRACK_MAX_SEGMENTS_PER_CALL,
                    TRACK_WINDOW, track_fit, track_segment, track_index, track_lengths, estimate_track, cut_track,
+                   Step, StepCandidate, Pieces, STEP_DTYPE, STEP_CANDIDATE_DTYPE, PIECES_DTYPE, STEP_F_NONE, STEP_F_SPAN, STEP_F_WEAK, STEP_MAX_SPAN, STEP_MAX_L, STEP_MIN_STEP, STEP_RATIO, STEP_MIN_GAIN,
+                   PIECES_F_RANGE, PIECES_MAX_PER_PAIR, PIECES_MAX_PER_CALL, locate_steps, steps_candidates, steps_fit, pieces_index, pieces_lengths, estimate_steps, cut_pieces, steps_workspace_bytes,
                    Drift, estimate_drift, cut_drift, drift_lengths, drift_fit, drift_index, drift_windows, drift_workspace_bytes,
                    DRIFT_DTYPE, DRIFT_F_NONE, DRIFT_F_RANGE, DRIFT_WINDOW, DRIFT_MIN_CORR, DRIFT_MAX_E, DRIFT_MAX_WINDOWS,
                    PCM_FORMATS, PCM_DTYPES,
@@ -39,6 +41,8 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "Track", "TRACK_DTYPE", "TRACK_F_NONE", "TRACK_F_RANGE", "TRACK_MAX_E", "TRACK_MAX_STEP",
            "TRACK_MAX_SEGMENTS_PER_CALL", "TRACK_WINDOW", "track_fit", "track_segment", "track_index", "track_lengths",
            "estimate_track", "cut_track",
+           "Step", "StepCandidate", "Pieces", "STEP_DTYPE", "STEP_CANDIDATE_DTYPE", "PIECES_DTYPE", "STEP_F_NONE", "STEP_F_SPAN", "STEP_F_WEAK", "STEP_MAX_SPAN", "STEP_MAX_L", "STEP_MIN_STEP", "STEP_RATIO", "STEP_MIN_GAIN",
+           "PIECES_F_RANGE", "PIECES_MAX_PER_PAIR", "PIECES_MAX_PER_CALL", "locate_steps", "steps_candidates", "steps_fit", "pieces_index", "pieces_lengths", "estimate_steps", "cut_pieces", "steps_workspace_bytes",
            "Drift", "estimate_drift", "cut_drift", "drift_lengths", "drift_fit", "drift_index", "drift_windows",
            "drift_workspace_bytes", "DRIFT_DTYPE", "DRIFT_F_NONE", "DRIFT_F_RANGE", "DRIFT_WINDOW", "DRIFT_MIN_CORR",
            "DRIFT_MAX_E", "DRIFT_MAX_WINDOWS",

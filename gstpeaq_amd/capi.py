@@ -99,6 +99,35 @@ TRACK_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("n_windows", "<u4"),
                         ("n_segments", "<u4"), ("d_min", "<f8"), ("d_max", "<f8"), ("max_abs_e", "<f8")])
 
 
+class StepCandidate(C.Structure):
+    """mirrors peaq_step_candidate (include/peaq_amd.h)"""
+    _fields_ = [("pair", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("LA", C.c_int32), ("LB", C.c_int32)]
+
+
+class Step(C.Structure):
+    """mirrors peaq_step (include/peaq_amd.h)"""
+    _fields_ = [("pair", C.c_uint32), ("c", C.c_uint32), ("LA", C.c_int32), ("LB", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("gain_left", C.c_double), ("gain_right", C.c_double), ("norm", C.c_double)]
+
+
+class Pieces(C.Structure):
+    """mirrors peaq_pieces (include/peaq_amd.h)"""
+    _fields_ = [("flags", C.c_uint32), ("n_candidates", C.c_uint32), ("n_accepted", C.c_uint32), ("n_pieces", C.c_uint32),
+                ("max_abs_e", C.c_double)]
+
+
+# PEAQ_STEP_* and PEAQ_PIECES_* (include/peaq_amd.h), the records as numpy structured dtypes
+STEP_F_NONE, STEP_F_SPAN, STEP_F_WEAK = 1, 2, 4
+STEP_MAX_SPAN, STEP_MAX_L = 1 << 22, (1 << 20) + 16384
+STEP_MIN_STEP, STEP_RATIO, STEP_MIN_GAIN = 0.75, 3.0, 0.0021
+PIECES_F_RANGE, PIECES_MAX_PER_PAIR, PIECES_MAX_PER_CALL = 2, 8192, 1 << 20
+STEP_CANDIDATE_DTYPE = np.dtype([("pair", "<u4"), ("lo", "<u4"), ("hi", "<u4"), ("LA", "<i4"), ("LB", "<i4")])
+STEP_DTYPE = np.dtype([("pair", "<u4"), ("c", "<u4"), ("LA", "<i4"), ("LB", "<i4"), ("flags", "<u4"), ("reserved", "<u4"),
+                       ("gain_left", "<f8"), ("gain_right", "<f8"), ("norm", "<f8")])
+PIECES_DTYPE = np.dtype([("flags", "<u4"), ("n_candidates", "<u4"), ("n_accepted", "<u4"), ("n_pieces", "<u4"),
+                         ("max_abs_e", "<f8")])
+
+
 class FrameTrace(C.Structure):
     """mirrors peaq_frame_trace (include/peaq_amd.h)"""
     _fields_ = [("ch", (C.c_double * 6) * 2), ("p_detect", C.c_double), ("steps", C.c_double), ("flags", C.c_uint32),
@@ -349,6 +378,32 @@ def load_library():
         L.peaq_run_pair_track.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_double, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Track),
                                           C.POINTER(Gain), dp]
+    if hasattr(L, "peaq_batch_cut_pieces"):          # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        i32p = C.POINTER(C.c_int32)
+        for f in (L.peaq_step_candidate_size, L.peaq_step_size, L.peaq_pieces_size):
+            f.restype = C.c_size_t
+            f.argtypes = []
+        L.peaq_steps_workspace_bytes.restype = C.c_size_t
+        L.peaq_steps_workspace_bytes.argtypes = [C.c_int, C.c_uint32]
+        L.peaq_batch_locate_steps.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32, i32p, C.c_int,
+                                              C.POINTER(StepCandidate), vp, vp]
+        L.peaq_steps_candidates.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+                                            C.POINTER(StepCandidate), u32p]
+        L.peaq_steps_fit.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.POINTER(Step), C.c_uint32, C.POINTER(Pieces), u32p, dp, dp]
+        L.peaq_pieces_index.restype = None
+        L.peaq_pieces_index.argtypes = [C.c_uint32, u32p, dp, dp, C.c_int64, C.POINTER(C.c_int64), i32p]
+        L.peaq_pieces_lengths.restype = None
+        L.peaq_pieces_lengths.argtypes = [C.c_int32, C.c_uint32, u32p, dp, dp, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+        L.peaq_batch_estimate_steps.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32, i32p,
+                                                C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_uint32, vp, vp, C.POINTER(Drift), C.POINTER(Track), dp,
+                                                C.c_uint32, C.POINTER(Step), C.POINTER(Pieces), C.c_uint32, u32p, dp, dp, vp]
+        L.peaq_batch_cut_pieces.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, u32p, u32p, u32p, C.c_uint32, u32p,
+                                            dp, dp, vp, C.c_size_t, vp]
+        L.peaq_run_pair_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_double, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(Delay), C.POINTER(Track),
+                                          C.POINTER(Pieces), C.POINTER(Step), C.c_uint32, C.POINTER(Gain), dp]
     L.peaq_batch_last_timing.argtypes = [vp, C.POINTER(_Timing)]
     if hasattr(L, "peaq_calibrate"):                 # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_calibrate.argtypes = [vp, C.c_int, C.POINTER(_Calibration)]
@@ -1195,7 +1250,222 @@ def cut_track(ctx, x, skip, n_keep, window, n_seg, a, e, n_in=None, out=None, st
     return out
 
 
-def _need_align(subsample, align, drift=False, track=False):
+def steps_workspace_bytes(n_cand, span_max):
+    """bytes of chunk rows locate_steps keeps in the context (peaq_steps_workspace_bytes)"""
+    return int(load_library().peaq_steps_workspace_bytes(int(n_cand), int(span_max)))
+
+
+def _candidates_array(cand):
+    """candidates as a STEP_CANDIDATE_DTYPE array: that, or rows (pair, lo, hi, LA, LB)"""
+    if isinstance(cand, np.ndarray) and cand.dtype == STEP_CANDIDATE_DTYPE:
+        return np.ascontiguousarray(cand)
+    rows = [tuple(int(v) for v in r) for r in cand]
+    return np.array(rows, dtype=STEP_CANDIDATE_DTYPE).reshape(len(rows))
+
+
+def locate_steps(ctx, ref, test, lags, cand, n_ref=None, n_test=None, stream=None):
+    """Where each candidate's delay steps from LA to LB (peaq_batch_locate_steps).  lags: every pair's lag0, which fixes
+    its coordinates; cand: rows (pair, lo, hi, LA, LB) or a STEP_CANDIDATE_DTYPE array.  Returns a STEP_DTYPE array, one
+    record per candidate.  Blocks until the records are there."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    a_lag = np.ascontiguousarray(lags, dtype=np.int32)
+    assert a_lag.shape == (n_pairs,)
+    cd = _candidates_array(cand)
+    n_cand = len(cd)
+    L = ctx.L
+    assert L.peaq_step_size() == C.sizeof(Step) == STEP_DTYPE.itemsize
+    assert L.peaq_step_candidate_size() == C.sizeof(StepCandidate) == STEP_CANDIDATE_DTYPE.itemsize
+    with _torch_stream(stream):
+        d_out = torch.zeros((max(n_cand, 1), C.sizeof(Step)), dtype=torch.uint8, device=ref.device)
+    u32p = C.POINTER(C.c_uint32)
+    _check(L.peaq_batch_locate_steps(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                     a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                     a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                     a_lag.ctypes.data_as(C.POINTER(C.c_int32)), n_cand,
+                                     cd.ctypes.data_as(C.POINTER(StepCandidate)), C.c_void_p(d_out.data_ptr()),
+                                     _stream_ptr(stream)))
+    _sync_stream(stream, ref.device)
+    return d_out.cpu().numpy()[:n_cand].copy().view(STEP_DTYPE)[:, 0]
+
+
+def steps_candidates(knots, window, n_common, pair=0, min_step=STEP_MIN_STEP, ratio=STEP_RATIO):
+    """the segments of a track that look like a step, as a STEP_CANDIDATE_DTYPE array (peaq_steps_candidates, host
+    arithmetic, no GPU)"""
+    knots = np.ascontiguousarray(knots, dtype=np.float64)
+    assert knots.ndim == 1
+    W = len(knots)
+    out = np.zeros(max(W - 1, 1), dtype=STEP_CANDIDATE_DTYPE)
+    n = C.c_uint32(0)
+    _check(load_library().peaq_steps_candidates(knots.ctypes.data_as(C.POINTER(C.c_double)), W, int(window), int(n_common),
+                                                int(pair), float(min_step), float(ratio),
+                                                out.ctypes.data_as(C.POINTER(StepCandidate)), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def steps_fit(knots, window, n_common, steps, min_step=STEP_MIN_STEP, ratio=STEP_RATIO, min_gain=STEP_MIN_GAIN,
+              max_e=TRACK_MAX_E):
+    """One pair's track rebuilt as pieces (peaq_steps_fit, host arithmetic, no GPU).  steps: the STEP_DTYPE records
+    locate_steps wrote for steps_candidates(knots, ...).  Returns a dict: the record's fields (flags, n_candidates,
+    n_accepted, n_pieces, max_abs_e), the arrays b, a, e [n_pieces], and `steps`, the records with STEP_F_WEAK set where
+    one was not accepted."""
+    knots = np.ascontiguousarray(knots, dtype=np.float64)
+    assert knots.ndim == 1
+    W = len(knots)
+    st = np.array(steps, dtype=STEP_DTYPE).reshape(-1).copy()
+    room = max(W - 1, 1) + len(st)
+    b, a, e = np.zeros(room, np.uint32), np.zeros(room), np.zeros(room)
+    rec = Pieces()
+    dp = C.POINTER(C.c_double)
+    _check(load_library().peaq_steps_fit(knots.ctypes.data_as(dp), W, int(window), int(n_common), float(min_step), float(ratio),
+                                         float(min_gain), float(max_e), st.ctypes.data_as(C.POINTER(Step)), len(st),
+                                         C.byref(rec), b.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(dp),
+                                         e.ctypes.data_as(dp)))
+    res = {k: getattr(rec, k) for k, _ in Pieces._fields_}
+    n = rec.n_pieces
+    res.update(b=b[:n], a=a[:n], e=e[:n], steps=st)
+    return res
+
+
+def _pieces_arrays(b, a, e):
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    assert b.ndim == 1 and b.shape == a.shape == e.shape and len(b) >= 1
+    return b, a, e
+
+
+def pieces_index(b, a, e, i):
+    """(m, phi): where output i of the pieces cut reads (peaq_pieces_index, host arithmetic)"""
+    b, a, e = _pieces_arrays(b, a, e)
+    m, phi = C.c_int64(0), C.c_int32(0)
+    dp = C.POINTER(C.c_double)
+    load_library().peaq_pieces_index(len(b), b.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(dp), e.ctypes.data_as(dp),
+                                     int(i), C.byref(m), C.byref(phi))
+    return m.value, phi.value
+
+
+def pieces_lengths(lag0, b, a, e, n_ref, n_test):
+    """(skip_ref, skip_test, n_keep) for one pair's lag and pieces (peaq_pieces_lengths, host arithmetic, no GPU)"""
+    b, a, e = _pieces_arrays(b, a, e)
+    sr, st, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    dp = C.POINTER(C.c_double)
+    load_library().peaq_pieces_lengths(int(lag0), len(b), b.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(dp),
+                                       e.ctypes.data_as(dp), int(n_ref), int(n_test), C.byref(sr), C.byref(st), C.byref(n))
+    return sr.value, st.value, n.value
+
+
+def _steps_window(steps):
+    """the window of a `steps=` keyword: True is the default window"""
+    return TRACK_WINDOW if steps is True else int(steps)
+
+
+def estimate_steps(ctx, ref, test, lags, n_ref=None, n_test=None, window=TRACK_WINDOW, R=None, min_corr=DRIFT_MIN_CORR,
+                   max_e=TRACK_MAX_E, min_step=STEP_MIN_STEP, ratio=STEP_RATIO, min_gain=STEP_MIN_GAIN, stream=None):
+    """Every pair's delay as pieces: its track, the steps located in it, the track rebuilt around them
+    (peaq_batch_estimate_steps); arguments as estimate_track's.  Returns a dict: `track`, the fields of TRACK_DTYPE
+    [n_pairs]; knots [n_pairs, w_max]; `steps`, STEP_DTYPE [n_pairs, steps_stride] (row p holds n_candidates[p]
+    records); the fields of PIECES_DTYPE [n_pairs]; b, a, e [n_pairs, piece_stride] (row p holds n_pieces[p] pieces);
+    `drift` as estimate_track's.  Blocks until the records are there."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    a_lag = np.ascontiguousarray(lags, dtype=np.int32)
+    assert a_lag.shape == (n_pairs,)
+    window = int(window)
+    R = min(window // 4, 1024) if R is None else int(R)
+    L = ctx.L
+    assert L.peaq_step_size() == C.sizeof(Step) == STEP_DTYPE.itemsize
+    assert L.peaq_pieces_size() == C.sizeof(Pieces) == PIECES_DTYPE.itemsize
+    w_max = max([1] + [int(L.peaq_drift_windows(int(a_lag[p]), int(stride if a_ref is None else a_ref[p]),
+                                                int(stride if a_test is None else a_test[p]), window))
+                       for p in range(n_pairs)])
+    steps_stride = max(w_max - 1, 1)
+    piece_stride = 2 * steps_stride
+    rows = max(n_pairs, 1)
+    with _torch_stream(stream):
+        d_dl = torch.zeros((rows, w_max, C.sizeof(Delay)), dtype=torch.uint8, device=ref.device)
+        d_sb = torch.zeros((rows, w_max, C.sizeof(SubDelay)), dtype=torch.uint8, device=ref.device)
+    track = np.zeros(rows, dtype=TRACK_DTYPE)
+    line = np.zeros(rows, dtype=DRIFT_DTYPE)
+    knots = np.zeros((rows, w_max))
+    steps = np.zeros((rows, steps_stride), dtype=STEP_DTYPE)
+    pieces = np.zeros(rows, dtype=PIECES_DTYPE)
+    b = np.zeros((rows, piece_stride), dtype=np.uint32)
+    a, e = np.zeros((rows, piece_stride)), np.zeros((rows, piece_stride))
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    _check(L.peaq_batch_estimate_steps(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()),
+                                       stride, a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                       a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                       a_lag.ctypes.data_as(C.POINTER(C.c_int32)), window, R, float(min_corr), float(max_e),
+                                       float(min_step), float(ratio), float(min_gain), w_max, C.c_void_p(d_dl.data_ptr()),
+                                       C.c_void_p(d_sb.data_ptr()), line.ctypes.data_as(C.POINTER(Drift)),
+                                       track.ctypes.data_as(C.POINTER(Track)), knots.ctypes.data_as(dp), steps_stride,
+                                       steps.ctypes.data_as(C.POINTER(Step)), pieces.ctypes.data_as(C.POINTER(Pieces)),
+                                       piece_stride, b.ctypes.data_as(u32p), a.ctypes.data_as(dp), e.ctypes.data_as(dp),
+                                       _stream_ptr(stream)))
+    _sync_stream(stream, ref.device)
+    res = {k: np.ascontiguousarray(pieces[k][:n_pairs]) for k in PIECES_DTYPE.names}
+    res["track"] = {k: np.ascontiguousarray(track[k][:n_pairs]) for k in TRACK_DTYPE.names}
+    res["drift"] = {k: np.ascontiguousarray(line[k][:n_pairs]) for k in DRIFT_DTYPE.names}
+    res.update(knots=knots[:n_pairs], steps=steps[:n_pairs], b=b[:n_pairs], a=a[:n_pairs], e=e[:n_pairs], window=window)
+    return res
+
+
+def cut_pieces(ctx, x, skip, n_keep, n_pieces, b, a, e, n_in=None, out=None, stream=None):
+    """cut along every pair's pieces (peaq_batch_cut_pieces): as cut_track, with (m_i, phi_i) = pieces_index(b[p,
+    :n_pieces[p]], a[p, :n_pieces[p]], e[p, :n_pieces[p]], i); b, a, e: [n_pairs, piece_stride].  A pair whose pieces are
+    all (0, 0) has its bits moved.  Returns out."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
+    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
+    a_np = np.ascontiguousarray(n_pieces, dtype=np.uint32)
+    a_b = np.ascontiguousarray(b, dtype=np.uint32)
+    a_a = np.ascontiguousarray(a, dtype=np.float64)
+    a_e = np.ascontiguousarray(e, dtype=np.float64)
+    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,) and a_np.shape == (n_pairs,)
+    assert a_a.ndim == 2 and a_a.shape[0] == n_pairs and a_a.shape == a_e.shape == a_b.shape
+    if out is None:
+        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    _check(ctx.L.peaq_batch_cut_pieces(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
+                                       a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), a_np.ctypes.data_as(u32p),
+                                       a_a.shape[1], a_b.ctypes.data_as(u32p), a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp),
+                                       C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
+
+
+def _need_align(subsample, align, drift=False, track=False, steps=False):
+    if steps and drift:
+        raise PeaqError("steps= and drift= exclude each other: the pieces are the lines, one or two per window")
+    if steps and track:
+        raise PeaqError("steps= and track= exclude each other: the pieces are the track's segments, cut where a step was located")
+    if steps and subsample:
+        raise PeaqError("steps= and subsample=True exclude each other: the track's knots carry the sub-sample part")
+    if steps and align is None:
+        raise PeaqError("steps= requires align= (a max_lag): the track is measured around an integer lag")
     if track and drift:
         raise PeaqError("track= and drift= exclude each other: the track's segments are the lines, one per window")
     if track and subsample:
@@ -1211,7 +1481,7 @@ def _need_align(subsample, align, drift=False, track=False):
 
 
 def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-          subsample=False, drift=False, track=False):
+          subsample=False, drift=False, track=False, steps=False):
     """Cuts both buffers of a batch to each pair's common, aligned part for the given lags (aligned_lengths, cut).
     gain: 'lsq' 'rms' 'polarity': the test signal's gain is measured over that part and applied in its cut
     (measure_gain, cut_scaled); the record tensor is kept as align.last_gain.
@@ -1224,7 +1494,14 @@ def align(ctx, ref, test, lags, n_ref=None, n_test=None, stream=None, gain=None,
     track: True or a window: each pair's delay is kept as a track of per-window delays around its lag (estimate_track,
     records kept as align.last_track), both signals are cut to track_lengths and the test signal is resampled along the
     track (cut_track); a gain is then measured on the two CUT buffers.  Excludes drift and subsample.
+    steps: True or a window: as track, with the steps of the delay located inside their windows and the track rebuilt as
+    pieces that jump there (estimate_steps, records kept as align.last_steps; pieces_lengths; cut_pieces).  Excludes
+    track, drift and subsample.
     Returns (ref', test', n', n'): two new tensors with one common stride and the common lengths (numpy uint32)."""
+    if steps:
+        _need_align(subsample, 0, drift, track, steps)
+        return _align_steps(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db,
+                            _steps_window(steps))
     if track:
         _need_align(subsample, 0, drift, track)
         return _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db,
@@ -1324,15 +1601,46 @@ def _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_cha
     return bufs[0], bufs[1], n, n.copy()
 
 
+def _align_steps(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
+    """align(..., steps=window)"""
+    import torch
+    n_pairs, stride, _ = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
+    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
+    st = estimate_steps(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
+    align.last_steps = st
+    n_pc = st["n_pieces"]
+    cuts = np.array([pieces_lengths(int(lags[p]), st["b"][p, :n_pc[p]], st["a"][p, :n_pc[p]], st["e"][p, :n_pc[p]],
+                                    int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)], dtype=np.uint32).reshape(n_pairs, 3)
+    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
+    with _torch_stream(stream):
+        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
+                for _ in range(3 if gain is not None else 2)]
+    n = np.ascontiguousarray(cuts[:, 2])
+    cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
+    cut_pieces(ctx, test, cuts[:, 1], n, n_pc, st["b"], st["a"], st["e"], n_in=a_test, out=bufs[1], stream=stream)
+    if gain is not None:
+        rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
+                              per_channel=gain_per_channel, stream=stream)
+        cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
+        align.last_gain = rec
+        return bufs[0], bufs[2], n, n.copy()
+    return bufs[0], bufs[1], n, n.copy()
+
+
 def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
-             subsample=False, drift=False, track=False):
+             subsample=False, drift=False, track=False, steps=False):
     """the `align=`, `gain=` and `subsample=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without
     align: lags of 0), then refine, match and cut"""
-    _need_align(subsample, max_lag, drift, track)
+    _need_align(subsample, max_lag, drift, track, steps)
     if max_lag is not None:
         lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
     else:
         lags = np.zeros(ref.shape[0], dtype=np.int32)
+    if steps:
+        return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
+                     max_gain_db=max_gain_db, steps=steps)
     if track:
         return align(ctx, ref, test, lags, n_ref, n_test, stream=stream, gain=gain, gain_per_channel=gain_per_channel,
                      max_gain_db=max_gain_db, track=track)
@@ -1350,8 +1658,10 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
               stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-              subsample=False, drift=False, track=False):
+              subsample=False, drift=False, track=False, steps=False):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    steps: True or a window, with align: as track, with the steps of every pair's delay located and the test signal cut
+    along pieces that jump there (estimate_steps, cut_pieces; align.last_steps).  Excludes track, drift and subsample.
     track: True or a window, with align: every pair's delay is kept as a track of per-window delays and the test signal
     is resampled along it (estimate_track, cut_track; align.last_track); a gain is then measured after that cut.
     Excludes drift and subsample.
@@ -1369,8 +1679,11 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align, drift, track)
-    if track:
+    _need_align(subsample, align, drift, track, steps)
+    if steps:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            steps=steps)
+    elif track:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
                                             track=track)
     elif drift:
@@ -1594,18 +1907,38 @@ def _subdelay_dict(rec):
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
-             max_gain_db=40.0, subsample=False, drift=False, track=False):
+             max_gain_db=40.0, subsample=False, drift=False, track=False, steps=False):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
     the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`.
     drift: True or a window, with align: peaq_run_pair_drift; the result dict carries the line's record as `drift`.
-    track: True or a window, with align: peaq_run_pair_track; the result dict carries the track's record as `track`."""
+    track: True or a window, with align: peaq_run_pair_track; the result dict carries the track's record as `track`.
+    steps: True or a window, with align: peaq_run_pair_steps; the result dict carries the track's record as `track`, the
+    pieces' as `pieces` and the located steps, a STEP_DTYPE array, as `steps`."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
-    _need_align(subsample, align, drift, track)
+    _need_align(subsample, align, drift, track, steps)
+    if steps:                                          # peaq_run_pair_steps; `delay`, `track`, `pieces`, `steps`, `gain`
+        rec, trec, prec, grec = Delay(), Track(), Pieces(), Gain()
+        window = _steps_window(steps)
+        found = np.zeros(max(max(len(ref), len(test)) // max(window, 1), 1), dtype=STEP_DTYPE)
+        _check(ctx.L.peaq_run_pair_steps(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),
+                                         window, gain_mode(gain, gain_per_channel), float(max_gain_db),
+                                         ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                         test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
+                                         C.byref(trec), C.byref(prec), found.ctypes.data_as(C.POINTER(Step)), len(found),
+                                         C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["track"] = {k: getattr(trec, k) for k, _ in Track._fields_}
+        res["pieces"] = {k: getattr(prec, k) for k, _ in Pieces._fields_}
+        res["steps"] = found[:min(len(found), prec.n_candidates)].copy()
+        if gain is not None:
+            res["gain"] = _gain_dict(grec)
+        return res
     if track:                                          # peaq_run_pair_track; the records as `delay`, `track`, `gain`
         rec, trec, grec = Delay(), Track(), Gain()
         _check(ctx.L.peaq_run_pair_track(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(align),

@@ -555,6 +555,11 @@ usage (const char *prog)
       "                (4096..1048576, default 16384) is measured and kept as a track, and the test signal is resampled\n"
       "                along it; prints the track's range; excludes --align-drift and --align-subsample, which it\n"
       "                subsumes (the plain one-call mode; not with --list, --interval or --trace)\n"
+      "  --align-steps[=WINDOW] --align-track, and steps of the delay inside a window too (a dropped or repeated block,\n"
+      "                a concealed packet loss, an edit): every step of the track is located to the sample and the test\n"
+      "                signal is cut along pieces that jump there; prints the track's range and each accepted step's\n"
+      "                position and size; excludes --align-track, --align-drift and --align-subsample (the plain\n"
+      "                one-call mode; not with --list, --interval or --trace)\n"
       "  --match-gain[=lsq|rms|polarity] match the test file's level (polarity) to the reference's on the GPU, after\n"
       "                --align if given, and print the gain applied (default lsq; the plain one-call mode and --list;\n"
       "                not with --interval or --trace)\n"
@@ -650,6 +655,7 @@ main (int argc, char **argv)
   peaq_drift drift;
   uint32_t track_window = 0;    /* != 0: --align-track, peaq_run_pair_track (implies --align) */
   peaq_track track;
+  uint32_t steps_window = 0;    /* != 0: --align-steps, peaq_run_pair_steps (implies --align) */
   peaq_delay delay;
   peaq_gain gain;
   int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
@@ -730,6 +736,21 @@ main (int argc, char **argv)
       if (!align_lag)
         align_lag = 4096;
     }
+    else if (!strcmp (argv[i], "--align-steps")) {
+      steps_window = 16384;
+      if (!align_lag)
+        align_lag = 4096;
+    } else if (!strncmp (argv[i], "--align-steps=", 14)) {
+      char *end;
+      const long v = strtol (argv[i] + 14, &end, 10);
+      if (*end || end == argv[i] + 14 || v < 4096 || v > 1048576) {
+        fprintf (stderr, "Failed to initialize: invalid steps window %s (4096 .. 1048576 samples)\n", argv[i] + 14);
+        return 1;
+      }
+      steps_window = (uint32_t) v;
+      if (!align_lag)
+        align_lag = 4096;
+    }
     else if (!strcmp (argv[i], "--match-gain") || !strcmp (argv[i], "--match-gain=lsq"))
       gain_mode = PEAQ_GAIN_LSQ;
     else if (!strcmp (argv[i], "--match-gain=rms"))
@@ -785,6 +806,26 @@ main (int argc, char **argv)
     gain_mode |= PEAQ_GAIN_PER_CHANNEL;
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
+  if (steps_window && track_window) {
+    fprintf (stderr, "Failed to initialize: --align-steps and --align-track exclude each other: the pieces are the track's segments, cut where a step was located\n");
+    return 1;
+  }
+  if (steps_window && drift_window) {
+    fprintf (stderr, "Failed to initialize: --align-steps and --align-drift exclude each other: the pieces are the lines, one or two per window\n");
+    return 1;
+  }
+  if (steps_window && subsample) {
+    fprintf (stderr, "Failed to initialize: --align-steps and --align-subsample exclude each other: the track's knots carry the sub-sample part\n");
+    return 1;
+  }
+  if (steps_window && list_path) {
+    fprintf (stderr, "Failed to initialize: --align-steps is not taken with --list: the host-fed path does not take it yet (whole-sample --align only)\n");
+    return 1;
+  }
+  if (steps_window && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --align-steps belongs to the plain one-call mode (not with --interval or --trace)\n");
     return 1;
   }
   if (track_window && drift_window) {
@@ -928,6 +969,30 @@ main (int argc, char **argv)
     if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
+    } else if (steps_window) {
+      char text[256];
+      enum { max_steps = 64 };                          /* printed; the count of all of them is in the pieces' record */
+      peaq_step found[max_steps];
+      peaq_pieces pieces;
+      unsigned k;
+      if (peaq_run_pair_steps (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, steps_window,
+              gain_mode, max_gain_db, ref.samples, ref.frames, test.samples, test.frames, &delay, &track, &pieces, found,
+              max_steps, &gain, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d samples, track %+.4f .. %+.4f (%u of %u windows%s), %u of %u steps accepted%s\n", (int) delay.lag,
+          track.d_min, track.d_max, (unsigned) track.n_valid, (unsigned) track.n_windows,
+          (track.flags & PEAQ_TRACK_F_NONE) ? ", no track: no valid window" : "", (unsigned) pieces.n_accepted,
+          (unsigned) pieces.n_candidates, (pieces.flags & PEAQ_PIECES_F_RANGE) ? ", slope out of range: not corrected" : "");
+      for (k = 0; k < pieces.n_candidates && k < max_steps; k++)
+        if (found[k].flags == 0)
+          printf ("Step: at %u by %+d samples (gains %.3f and %.3f)\n", (unsigned) found[k].c, (int) (found[k].LB - found[k].LA),
+              found[k].norm > 0. ? found[k].gain_left / found[k].norm : 0., found[k].norm > 0. ? found[k].gain_right / found[k].norm : 0.);
+      if (gain_mode) {
+        format_gain (text, sizeof text, &gain, ref.channels);
+        printf ("Gain: %s\n", text);
+      }
     } else if (track_window) {
       char text[256];
       if (peaq_run_pair_track (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag, track_window,

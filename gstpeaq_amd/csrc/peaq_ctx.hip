@@ -163,6 +163,7 @@ extern "C" void peaq_ctx_destroy(peaq_ctx* c) {
   gather_release(c);
   gain_release(c);
   frac_release(c);
+  steps_release(c);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->batch_begin) (void)hipEventDestroy(c->batch_begin);
   if (c->batch_end) (void)hipEventDestroy(c->batch_end);

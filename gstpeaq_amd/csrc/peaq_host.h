@@ -20,6 +20,8 @@
 //                     test signal's cut along the line (kernel and host side)
 //   peaq_track.hip    delay track: the drift stage's per-window delays kept as knots and segments (host), the test
 //                     signal's cut along them (kernel and host side)
+//   peaq_steps.hip    delay steps: where inside two windows the delay jumps (kernels), the track rebuilt as pieces that
+//                     jump there (host), the test signal's cut along pieces (kernel and host side)
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -179,6 +181,7 @@ struct peaq_ctx {
   struct GatherState* ga = nullptr;       // gather: index and length scratch (peaq_gather.hip)
   struct GainState* gn = nullptr;         // gain matching: partial sums, length scratch (peaq_gain.hip)
   struct FracState* fr = nullptr;         // sub-sample stage: the two tables, partial sums, length scratch (peaq_frac.hip)
+  struct StepsState* sp = nullptr;        // steps stage: the chunks' rows (peaq_steps.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -191,13 +194,14 @@ struct peaq_ctx {
 };
 
 // free what a stage has cached in the context; the device is idle.  peaq_resample.hip, peaq_align.hip, peaq_pcm.hip,
-// peaq_gather.hip, peaq_gain.hip, peaq_frac.hip
+// peaq_gather.hip, peaq_gain.hip, peaq_frac.hip, peaq_steps.hip
 void resample_release(peaq_ctx* c);
 void align_release(peaq_ctx* c);
 void feed_release(peaq_ctx* c);
 void gather_release(peaq_ctx* c);
 void gain_release(peaq_ctx* c);
 void frac_release(peaq_ctx* c);
+void steps_release(peaq_ctx* c);
 // the sub-sample stage's shift table on the device and its length slots, for the drift cut (peaq_frac.hip; the caller
 // holds the context's lock)
 int frac_shift_table(peaq_ctx* c, const double** shift, struct LenStage** lens);
@@ -385,7 +389,7 @@ inline int check_lengths(const std::string& who, int n_pairs, const uint32_t* n,
 }
 
 // ---------------------------------------------------------------------------
-// The steps of the one-pair conveniences (peaq_run_pair_rate, _aligned, _matched, _trace, _subsample, _drift, _track), defined in
+// The steps of the one-pair conveniences (peaq_run_pair_rate, _aligned, _matched, _trace, _subsample, _drift, _track, _steps), defined in
 // peaq_align.hip.  Each of them blocks; the stage calls between them are the entry point's own.
 // ---------------------------------------------------------------------------
 // (a) what every peaq_run_pair_* call checks, beside check_level where it looks at the level: channels, rate, ctx and
@@ -408,7 +412,7 @@ int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, con
                    size_t stride, uint32_t len_ref, uint32_t len_test, peaq_result* out);
 
 // ---------------------------------------------------------------------------
-// DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip, peaq_drift.hip, peaq_track.hip and peaq_gather.hip share
+// DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip, peaq_drift.hip, peaq_track.hip, peaq_steps.hip and peaq_gather.hip share
 // (256 threads per workgroup).  No kernel is defined in this header.
 // ---------------------------------------------------------------------------
 // A workgroup's share of the copy of `count` consecutive floats from src to dst: the 16-byte units v0 .. v0 + 255,

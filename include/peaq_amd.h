@@ -715,9 +715,9 @@ size_t peaq_feed_matched_workspace_bytes (const peaq_feed *feed, int advanced, i
  * samples around the given integer lag, and peaq_batch_cut_shifted is peaq_batch_cut of the test signal through the
  * fractional-delay filter of that grid point.  Only the test signal is ever shifted; the reference is never changed.
  * With lag < 0 the test signal keeps skip = 0 and is still shifted by q.  A delay that grows steadily is the next
- * stage's ("constant drift on the device"), one that bends the one after ("delay track on the device").  Not done,
- * here or anywhere: steps of the delay sharper than a window of the track, shifts finer than the grid, and the
- * host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
+ * stage's ("constant drift on the device"), one that bends the one after ("delay track on the device").  Steps of the
+ * delay sharper than a window of the track are the stage's after that ("delay steps on the device").  Not done, here
+ * or anywhere: shifts finer than the grid, and the host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
  *
  *   w_H (x) = I0 (beta sqrt (1 - (x / H)^2)) / I0 (beta) for |x| < H, else 0; beta = 8.49, the converter's Kaiser window.
  *   sinc (x) = sin (pi x) / (pi x), sinc (0) = 1.  I0 is evaluated in double by the Chebyshev expansions of the Cephes
@@ -805,8 +805,9 @@ int peaq_run_pair_subsample (peaq_ctx *ctx, int advanced, int channels, double p
  * steadily: at 100 ppm by 48 samples over 10 s.  One lag leaves most of such an item misaligned, and PEAQ scores that as
  * distortion.  This stage models the delay of a pair as ONE straight line, fits it robustly from per-window delays that
  * the two stages above measure, and resamples the test signal along it through shift_tab.  Only the test signal is
- * changed.  A delay that is no straight line is the next stage's ("delay track on the device").  Not done, here or
- * anywhere: steps of the delay sharper than a window of that track, and the host-fed pipelines
+ * changed.  A delay that is no straight line is the next stage's ("delay track on the device").  Steps of the delay
+ * sharper than a window of that track are the stage's after it ("delay steps on the device").  Not done, here or
+ * anywhere: the host-fed pipelines
  * (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
  *
  *   Coordinates.  lag0 = the pair's lag from peaq_batch_estimate_delay over the whole signals; peaq_aligned_lengths
@@ -907,8 +908,9 @@ int peaq_run_pair_drift (peaq_ctx *ctx, int advanced, int channels, double playb
  * Material that passed two clocks one after the other, a loop whose clock wanders, a player that re-synchronised once:
  * their delay bends or steps, and one line leaves part of the item misaligned.  This stage keeps the per-window delays
  * that the drift stage measures as a TRACK -- a knot per window, a line from every knot to the next -- and resamples
- * the test signal along it through shift_tab.  Only the test signal is changed.  Not done, here or anywhere: steps
- * sharper than a window (a step is spread over the window it falls in), and the host-fed pipelines
+ * the test signal along it through shift_tab.  Only the test signal is changed.  A step sharper than a window is spread over
+ * the window it falls in, or flags the pair: locating it is the next stage's ("delay steps on the device").  Not done,
+ * here or anywhere: the host-fed pipelines
  * (peaq_batch_run_host*, the CLI's --list), which align to whole samples only.
  *
  *   Coordinates, windows, d_w = lag_w + q_w / 256, x_w = w window + window / 2 (the integer half) and the validity rule
@@ -1001,6 +1003,185 @@ int peaq_run_pair_track (peaq_ctx *ctx, int advanced, int channels, double playb
                          uint32_t max_lag, uint32_t window, int mode, double max_gain_db,
                          const float *ref, size_t n_ref, const float *test, size_t n_test,
                          peaq_delay *delay /* host */, peaq_track *track /* host */, peaq_gain *gain /* host */,
+                         peaq_result *out);
+
+/* ---- delay steps on the device ------------------------------------------------
+ * A player or a link that drops or repeats a block, a concealed packet loss, an edit that removes a few hundred samples:
+ * from such a point to the item's end the delay differs by a fixed amount.  The track above spreads a small step over a
+ * whole window and is flagged PEAQ_TRACK_F_RANGE by a larger one (more than window / 64 samples).  This stage finds, for
+ * every segment of a track that looks like a step, the POSITION of the step inside the two windows around it
+ * (peaq_batch_locate_steps), rebuilds the track as PIECES -- lines that need not meet, with breakpoints anywhere
+ * (peaq_steps_fit) -- and cuts the test signal along them (peaq_batch_cut_pieces).  Only the test signal is changed; a
+ * positive step drops samples of it and a negative one repeats some, which is what the material did.  Not done, here or
+ * anywhere: the apex of a bend, two steps in neighbouring segments (each masks the other's ratio test), cross-fading at
+ * a step, steps= on trajectories and traces, and the host-fed pipelines (peaq_batch_run_host*, the CLI's --list), which
+ * align to whole samples only.
+ *
+ *   Coordinates are those of "constant drift on the device": lag0, skip_ref, skip_test, n_common = peaq_aligned_lengths
+ *   (lag0, ...); A_ref[i] = ref[skip_ref + i], A_test[j] = test[skip_test + j]; r and t their FP64 mono sums (the two
+ *   channels added in double, left first); a sample outside its signal counts as 0.
+ *   Locate.  A candidate is { pair, lo, hi, LA, LB } with lo < hi <= n_common of its pair and integer delays LA != LB:
+ *   the hypothesis that the delay is LA before some c in [lo, hi] and LB from c on.  With d[i] = t[i + LA] - t[i + LB]
+ *   and h[i] = r[i] d[i] (each rounded once), H[c] = sum over lo <= i < c of h[i], H[lo] = 0:
+ *     s     = the sign of P = sum over lo <= i < hi of r[i] (t[i + LA] + t[i + LB]), + for 0: the polarity;
+ *     c*    = the c in [lo, hi] with the largest s H[c];
+ *     gain_left = s H[c*], gain_right = s (H[c*] - H[hi]), norm = sqrt (R2 D2), R2 = sum r[i]^2, D2 = sum d[i]^2 over
+ *     the interval.  Both gains are >= 0; for a true step each is about the cross-energy the step moves on its side.
+ *   The order of every sum is fixed by the index within the interval alone, in chunks of 4096 positions from lo on:
+ *     in chunk j, lane l (0 .. 255) owns positions 16 l .. 16 l + 15 of the chunk; run_u = h_0 + ... + h_u over its own,
+ *     added one after the other from 0 (a position at or behind hi adds 0); S_l = run_15;
+ *     before_l = the S of the lanes 64 (l / 64) .. l - 1, added one after the other from 0; wave total w_v = before_l +
+ *     S_l at l = 64 v + 63; waves_l = the w of the waves in front of l's, one after the other from 0;
+ *     Hloc = waves_l + (before_l + run_u) is the sum from the chunk's start up to and including that position; the
+ *     chunk's total T_j = ((w_0 + w_1) + w_2) + w_3, which is Hloc at its last position to the bit;
+ *     C_0 = 0, C_{j+1} = C_j + T_j; H[c] = C_j + Hloc for c in chunk j (c - lo in 4096 j + 1 .. 4096 j + 4096), H[hi] =
+ *     C behind the last chunk.  Every H is within (16 + 64 + 4 + 1024) 2^-53 sum |h| < 1.3e-13 sum |h| of the exact sum.
+ *     P, R2 and D2: a lane's terms as fused multiply-adds in the order of u, then the wave (a butterfly), the four waves
+ *     (0 + 1) + (2 + 3), then the chunks one after the other.
+ *   Comparisons are exact, on these values: inside a chunk the largest (s > 0) or smallest (s < 0) Hloc, the smallest c
+ *   among equals; between chunks and against c = lo (value 0) the largest s (C_j + that Hloc), the smallest c among
+ *   equals.  No floating-point atomics.  A candidate's record does not depend on the other candidates of the call or on
+ *   where the buffers lie, and repeats bit for bit. */
+#define PEAQ_STEP_MAX_SPAN  (1u << 22)  /* hi - lo of a candidate that is searched */
+#define PEAQ_STEP_MAX_L     1064960     /* 2^20 + 16384: |LA|, |LB| */
+#define PEAQ_STEP_F_NONE    1   /* norm is 0 or not finite: c = lo, both gains 0 */
+#define PEAQ_STEP_F_SPAN    2   /* hi - lo > PEAQ_STEP_MAX_SPAN: nothing was searched; c = lo, gains and norm 0 */
+#define PEAQ_STEP_F_WEAK    4   /* set by peaq_steps_fit: located, but not accepted */
+#define PEAQ_STEP_MIN_STEP  0.75       /* defaults of min_step, ratio and min_gain (DESIGN.md 19 has the measurements) */
+#define PEAQ_STEP_RATIO     3.
+#define PEAQ_STEP_MIN_GAIN  0.0021
+#define PEAQ_PIECES_MAX_PER_PAIR  (2u * PEAQ_DRIFT_MAX_WINDOWS)
+#define PEAQ_PIECES_MAX_PER_CALL  (1u << 20)   /* summed over the pairs of one peaq_batch_cut_pieces: 20 MiB of staging */
+#define PEAQ_PIECES_F_RANGE 2   /* an |e_j| > max_e among the pieces: every a_j and e_j is 0 */
+typedef struct {               /* 20 bytes */
+  uint32_t pair, lo, hi;
+  int32_t  LA, LB;
+} peaq_step_candidate;
+typedef struct {               /* 48 bytes */
+  uint32_t pair;               /* as given */
+  uint32_t c;                  /* c*, in lo .. hi */
+  int32_t  LA, LB;             /* as given */
+  uint32_t flags;
+  uint32_t reserved;
+  double   gain_left, gain_right, norm;
+} peaq_step;
+typedef struct {               /* 24 bytes */
+  uint32_t flags;              /* PEAQ_PIECES_F_RANGE */
+  uint32_t n_candidates, n_accepted, n_pieces;
+  double   max_abs_e;          /* the steepest piece, also where it is out of range */
+} peaq_pieces;
+size_t peaq_step_candidate_size (void);
+size_t peaq_step_size (void);
+size_t peaq_pieces_size (void);
+/* Batch layout and lengths as for peaq_batch_refine_delay; lag0: host array of n_pairs lags, which fix each pair's
+ * coordinates.  cand: HOST array of n_cand candidates, resolved on the host and sent through the pinned staging slots,
+ * copied on `stream`.  d_out: device array of n_cand peaq_step, in the order of cand.  Enqueues on `stream` and returns,
+ * synchronising nothing.  The chunks' rows (peaq_steps_workspace_bytes) live in the context and are reused; a call on
+ * another stream waits, on the device, for the previous call's kernels.
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: peaq_batch_refine_delay's
+ * refusals (lag0 in the place of lag), and: a NULL cand with n_cand > 0, a pair index >= n_pairs, lo >= hi, hi beyond
+ * the pair's n_common, LA == LB, |LA| or |LB| above PEAQ_STEP_MAX_L, n_cand < 0 or more than 65535 candidates. */
+int peaq_batch_locate_steps (peaq_ctx *ctx, int channels, int n_pairs,
+                             const float *d_ref, const float *d_test, size_t pair_stride,
+                             const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                             const int32_t *lag0 /* host */, int n_cand, const peaq_step_candidate *cand /* host */,
+                             peaq_step *d_out /* device, [n_cand] */, void *stream);
+/* The rows of peaq_batch_locate_steps for n_cand candidates whose longest interval is span_max (above
+ * PEAQ_STEP_MAX_SPAN: that), in bytes: 64 per chunk of 4096 positions and candidate.  Candidates are taken in groups,
+ * so it stops growing with n_cand at 256 MiB.  0 for no candidates. */
+size_t peaq_steps_workspace_bytes (int n_cand, uint32_t span_max);
+/* Host only, FP64, every operation rounded on its own.  The candidates of one pair's track, from its knots s_w (peaq_track_fit's or
+ * peaq_batch_estimate_track's: they stay readable under PEAQ_TRACK_F_RANGE), in the order of k.  D_k = s_{k+1} - s_k
+ * for the S = n_windows - 1 segments (fewer than 2 windows: none).  Segment k is a candidate when |D_k| >= min_step and
+ * |D_k| >= ratio max (|D_{k-1}|, |D_{k+1}|), a neighbour that does not exist counting as 0 (a constant drift has equal
+ * D and gives none); lo = k window, hi = min ((k + 2) window, n_common), LA = (int) rint (s_k), LB = (int) rint
+ * (s_{k+1}), to nearest even; a candidate with LA == LB (or with lo >= hi) is dropped.  out: room for max (n_windows -
+ * 1, 1) entries, their `pair` set to the argument; *n: how many.  PEAQ_ERR_ARG: NULL knots, out or n, a window out of
+ * 4096 .. 2^20, more than PEAQ_DRIFT_MAX_WINDOWS windows, n_windows x window beyond n_common, a min_step or ratio that
+ * is negative or not finite. */
+int peaq_steps_candidates (const double *knots, uint32_t n_windows, uint32_t window, uint32_t n_common, uint32_t pair,
+                           double min_step, double ratio, peaq_step_candidate *out, uint32_t *n);
+/* Host only, FP64, every operation rounded on its own.  One pair's track rebuilt as pieces.  steps: the n_steps records
+ * peaq_batch_locate_steps wrote for peaq_steps_candidates (same knots, window, n_common, min_step, ratio), in that
+ * order; the call derives the candidates again and refuses records that are not theirs.
+ *   Segments: (a_k, e_k) of segment k are item 4 of "delay track on the device" taken from the knots -- the track's own
+ *   bits where it kept them.  Segment k's own outputs are [start_k, start_{k+1}), start_0 = 0, start_k = window / 2 + k
+ *   window, the last one running to the pair's end.
+ *   Accept: a record with flags == 0 and min (gain_left, gain_right) >= min_gain norm is a step at c; any other gets
+ *   PEAQ_STEP_F_WEAK added to its flags (in steps) and its segment stays the track's.
+ *   Pieces (b_j, a_j, e_j), b_0 = 0, b strictly increasing, piece j covering outputs [b_j, b_{j+1}) and the last one
+ *   running to the pair's end, in the order of the segments; a piece that would be empty is left out; neighbours with
+ *   identical (a, e) are not merged.  A segment without a step is one piece with its own line, from start_k -- or from
+ *   the c of a step in segment k - 1 that lies behind start_k -- to start_{k+1} -- or to the c of a step in segment k + 1
+ *   that lies before it.  A step in segment k replaces it by two pieces: the line of segment k - 1 up to c and the line
+ *   of segment k + 1 from c on, where (s_k, 0) stands for the left line if segment k - 1 does not exist or is a step
+ *   itself, and (s_{k+1}, 0) for the right line likewise.  A c outside the segment's own outputs reaches into the
+ *   neighbour as said, unless that neighbour is a step itself: then c is taken as the border between the two.
+ *   Range: any |e_j| > max_e (0 < max_e <= 1 / 64) sets PEAQ_PIECES_F_RANGE and every a_j and e_j to 0; b stays.  A
+ *   pair whose track is PEAQ_TRACK_F_RANGE through a step alone comes out unflagged once the step is accepted.
+ * b, a, e: room for max (n_windows - 1, 1) + n_steps entries; out->n_pieces of them are written.
+ * PEAQ_ERR_ARG: NULL arrays, a window, window count, n_common, min_step, ratio as above, a min_gain that is negative
+ * or not finite, a max_e outside (0, 1 / 64], an n_steps or a record's LA, LB that are not the candidates'. */
+int peaq_steps_fit (const double *knots, uint32_t n_windows, uint32_t window, uint32_t n_common,
+                    double min_step, double ratio, double min_gain, double max_e,
+                    peaq_step *steps, uint32_t n_steps, peaq_pieces *out, uint32_t *b, double *a, double *e);
+/* Host only.  Where output i >= 0 reads: peaq_drift_index (a_j, e_j, i) along the piece j of i, the largest j with
+ * b_j <= i.  The device evaluates the same operations. */
+void peaq_pieces_index (uint32_t n_pieces, const uint32_t *b, const double *a, const double *e, int64_t i, int64_t *m,
+                        int32_t *phi);
+/* Host only.  peaq_track_lengths with pieces in the track's place: *n_keep is the largest count <= n_common with
+ * skip_test + i + m_i < n_test for EVERY i below it.  i + m_i does not decrease inside a piece (|e| <= 1 / 64) but may
+ * fall by any amount across a breakpoint, so the pieces are searched one by one in their order
+ * (gstpeaq_amd/csrc/peaq_steps_math.h has the argument). */
+void peaq_pieces_lengths (int32_t lag0, uint32_t n_pieces, const uint32_t *b, const double *a, const double *e,
+                          uint32_t n_ref, uint32_t n_test, uint32_t *skip_ref, uint32_t *skip_test, uint32_t *n_keep);
+/* peaq_batch_estimate_track (same arguments up to knots; the track's own segments are not handed out), then per pair
+ * peaq_steps_candidates, ONE peaq_batch_locate_steps over all pairs' candidates, a read-back, and peaq_steps_fit.  The
+ * window, delay and sub-delay records, the line's and the track's records are the earlier stages' bit for bit.  steps:
+ * host [n_pairs][steps_stride], row p holding pieces[p].n_candidates records (`pair` = p; the rest 0); pieces: host
+ * [n_pairs]; b, a, e: host [n_pairs][piece_stride], row p holding pieces[p].n_pieces entries (the rest 0).  The call
+ * BLOCKS, as the track estimate does.
+ * Refusals as peaq_batch_estimate_track's and peaq_steps_fit's, and: a steps_stride below max (w_max - 1, 1), a
+ * piece_stride below 2 max (w_max - 1, 1), NULL steps, pieces, b, a or e, more than 65535 candidates in all. */
+int peaq_batch_estimate_steps (peaq_ctx *ctx, int channels, int n_pairs,
+                               const float *d_ref, const float *d_test, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                               const int32_t *lag0 /* host */, uint32_t window, uint32_t R, double min_corr, double max_e,
+                               double min_step, double ratio, double min_gain,
+                               uint32_t w_max, peaq_delay *d_win_delay /* device */, peaq_subdelay *d_win_sub /* device */,
+                               peaq_drift *drift /* host, [n_pairs], may be NULL */, peaq_track *track /* host, [n_pairs] */,
+                               double *knots /* host */, uint32_t steps_stride, peaq_step *steps /* host */,
+                               peaq_pieces *pieces /* host, [n_pairs] */, uint32_t piece_stride,
+                               uint32_t *b /* host */, double *a /* host */, double *e /* host */, void *stream);
+/* peaq_batch_cut_track's definition with peaq_pieces_index in the place of peaq_track_index (n_pieces[p] pieces in row
+ * p of b, a and e, host arrays):
+ * out[p][i][c] = (float) sum_{o = -32 .. 32} shift_tab[phi_i][o] (double) in[p][skip[p] + i + m_i + o][c] for
+ * i < n_keep[p]: fused multiply-adds in the order o = -32 .. 32 in FP64, rounded once to FP32.  A tap whose index falls
+ * outside [0, n_in[p]) contributes nothing.  Samples of d_out past n_keep[p] are left as they were.  Lines need not
+ * meet, breakpoints may sit anywhere, a piece may be one output long, a jump may be thousands of samples either way.
+ * Pieces equal to a track's segments (b_j = the segments' starts) give peaq_batch_cut_track's output bit for bit; one
+ * piece with |e| <= PEAQ_DRIFT_MAX_E gives peaq_batch_cut_drift's; a pair whose pieces are all (0, 0) has its bits
+ * moved as they are (peaq_batch_cut's) and does not look at n_in[p].  All per-pair arrays and the pieces travel through
+ * the pinned staging slots.
+ * Refusals as peaq_batch_cut_drift's, and: an a or e that is not finite, |a| > PEAQ_DRIFT_MAX_A, |e| > PEAQ_TRACK_MAX_E,
+ * an n_pieces of 0, above piece_stride or above PEAQ_PIECES_MAX_PER_PAIR, more than PEAQ_PIECES_MAX_PER_CALL pieces in
+ * all, a b_0 that is not 0, a b_j that is not above b_{j-1}, NULL n_pieces, b, a or e. */
+int peaq_batch_cut_pieces (peaq_ctx *ctx, int channels, int n_pairs,
+                           const float *d_in, size_t in_stride, const uint32_t *n_in /* host */,
+                           const uint32_t *skip /* host */, const uint32_t *n_keep /* host */,
+                           const uint32_t *n_pieces /* host */, uint32_t piece_stride,
+                           const uint32_t *b /* host */, const double *a /* host */, const double *e /* host */,
+                           float *d_out, size_t out_stride, void *stream);
+/* peaq_run_pair_track with this stage in the track's place: peaq_batch_estimate_steps (window, R = min (window / 4,
+ * 1024), min_corr 0.5, max_e 1 / 64, the PEAQ_STEP_* defaults); peaq_pieces_lengths; plain cut of the reference to
+ * n_keep; pieces cut of the test signal; the gain, if any, measured AFTER the cut.  A flagged record (every piece 0)
+ * scores what peaq_run_pair_aligned scores.  steps: host, room for max_steps records, of which min (max_steps,
+ * pieces->n_candidates) are written.  delay, track, pieces, steps and gain (host) may be NULL. */
+int peaq_run_pair_steps (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                         uint32_t max_lag, uint32_t window, int mode, double max_gain_db,
+                         const float *ref, size_t n_ref, const float *test, size_t n_test,
+                         peaq_delay *delay /* host */, peaq_track *track /* host */, peaq_pieces *pieces /* host */,
+                         peaq_step *steps /* host */, uint32_t max_steps, peaq_gain *gain /* host */,
                          peaq_result *out);
 
 /* ---- device calibration (measurement support, bench.py) -----------------------
