@@ -567,6 +567,10 @@ usage (const char *prog)
       "  --max-gain=DB leave a pair unmatched whose gain is beyond +-DB (0 < DB <= 120, default 40)\n"
       "  --trace=FILE  also write the MOV layer's values of every frame (and, with --advanced, every filter-bank\n"
       "                block) to FILE as CSV (the plain one-call mode; with --advanced, --device-resample, --align)\n"
+      "  --bands=FILE[:PLANES] also write the FFT path's values per frame, channel and critical band to FILE as CSV: a\n"
+      "                noise-to-mask spectrogram.  PLANES: a comma-separated list of nmr, exc_ref, exc_test, detect,\n"
+      "                steps (default nmr; with --advanced: nmr, exc_ref).  The header line carries the bands' centre\n"
+      "                frequencies in Hz (the plain one-call mode; with --advanced, --device-resample, --align)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -643,6 +647,93 @@ done:
   return rc;
 }
 
+/* the planes of --bands=FILE[:PLANES] by name, in the order of their bits (PEAQ_BAND_*) */
+static const char *const band_plane_names[5] = { "nmr", "exc_ref", "exc_test", "detect", "steps" };
+
+/* a comma-separated list of plane names -> mask; 0 if a name is not one */
+static uint32_t
+parse_band_planes (const char *list)
+{
+  uint32_t mask = 0;
+  while (*list) {
+    const size_t n = strcspn (list, ",");
+    int k, hit = -1;
+    for (k = 0; k < 5; k++)
+      if (strlen (band_plane_names[k]) == n && !strncmp (list, band_plane_names[k], n))
+        hit = k;
+    if (hit < 0)
+      return 0;
+    mask |= 1u << hit;
+    list += n;
+    if (*list == ',' && !*++list)
+      return 0;
+  }
+  return mask;
+}
+
+/* --bands=FILE[:PLANES]: the pair through peaq_run_pair_bands, its rows as CSV -- a header line (frame, channel, plane,
+ * then the bands' centre frequencies in Hz), then one line per (frame, channel, plane) with the band values; every
+ * value as %.17g, which reads back to the same double.  Prints the delay line of --align. */
+static int
+write_bands (const char *path, uint32_t planes, peaq_ctx *ctx, int advanced, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
+    rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
+  const size_t frame_cap = (size_t) peaq_frame_count (n48[0], n48[1], 0) + 1;
+  const int count = peaq_band_count (advanced), row = peaq_band_row (advanced), ch = ref->channels;
+  int n_planes = 0, c, k, b, slot, rc = 1;
+  double *rows, *fc;
+  uint32_t nf = 0, f;
+  peaq_delay delay;
+  FILE *out;
+  for (k = 0; k < 5; k++)
+    n_planes += (planes >> k) & 1;
+  rows = malloc (frame_cap * ch * (n_planes ? n_planes : 1) * row * sizeof *rows);
+  fc = malloc (count * sizeof *fc);
+  if (!rows || !fc) {
+    printf ("Error: out of memory for the band trace\n");
+    goto done;
+  }
+  if (peaq_band_tables (advanced, fc, NULL) != PEAQ_OK ||
+      peaq_run_pair_bands (ctx, advanced, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
+          planes, rows, frame_cap, &nf, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag)
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+  if (!(out = fopen (path, "w"))) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  fprintf (out, "frame,channel,plane");
+  for (b = 0; b < count; b++)
+    fprintf (out, ",%.17g", fc[b]);
+  fprintf (out, "\n");
+  for (f = 0; f < nf; f++)
+    for (c = 0; c < ch; c++)
+      for (k = 0, slot = 0; k < 5; k++) {
+        const double *v;
+        if (!((planes >> k) & 1))
+          continue;
+        v = rows + (((size_t) f * ch + c) * n_planes + slot++) * row;
+        fprintf (out, "%u,%d,%s", f, c, band_plane_names[k]);
+        for (b = 0; b < count; b++)
+          fprintf (out, ",%.17g", v[b]);
+        fprintf (out, "\n");
+      }
+  if (fclose (out)) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  rc = 0;
+done:
+  free (rows);
+  free (fc);
+  return rc;
+}
+
 int
 main (int argc, char **argv)
 {
@@ -663,6 +754,8 @@ main (int argc, char **argv)
   double level = 92., interval_s = 0.;
   const char *files[2] = { NULL, NULL };
   const char *list_path = NULL, *trace_path = NULL;
+  char *bands_path = NULL;      /* --bands=FILE[:PLANES], peaq_run_pair_bands */
+  uint32_t band_planes = PEAQ_BAND_NMR;
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -788,6 +881,22 @@ main (int argc, char **argv)
       return 1;
     } else if (!strncmp (argv[i], "--trace=", 8))
       trace_path = argv[i] + 8;
+    else if (!strcmp (argv[i], "--bands") || !strcmp (argv[i], "--bands=") || !strncmp (argv[i], "--bands=:", 9)) {
+      fprintf (stderr, "Failed to initialize: --bands needs a file name (--bands=FILE[:PLANES])\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--bands=", 8)) {
+      /* what follows the last colon is the plane list if every name in it is one; a file name otherwise */
+      char *colon = strrchr (argv[i] + 8, ':');
+      bands_path = argv[i] + 8;
+      if (colon && !colon[1]) {
+        fprintf (stderr, "Failed to initialize: --bands: no plane after the colon (nmr, exc_ref, exc_test, detect, steps)\n");
+        return 1;
+      }
+      if (colon && parse_band_planes (colon + 1)) {
+        band_planes = parse_band_planes (colon + 1);
+        *colon = 0;
+      }
+    }
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -804,6 +913,18 @@ main (int argc, char **argv)
   }
   if (gain_mode && gain_per_channel)
     gain_mode |= PEAQ_GAIN_PER_CHANNEL;
+  if (bands_path && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --bands belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (bands_path && (trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --bands is a run of its own (not with --trace, --match-gain or an --align-... beyond --align)\n");
+    return 1;
+  }
+  if (bands_path && advanced && (band_planes & ~(PEAQ_BAND_NMR | PEAQ_BAND_EXC_REF))) {
+    fprintf (stderr, "Failed to initialize: --bands: the advanced version has the planes nmr and exc_ref only\n");
+    return 1;
+  }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
     return 1;
@@ -966,7 +1087,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (trace_path) {
+    if (bands_path) {
+      if (write_bands (bands_path, band_planes, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (steps_window) {

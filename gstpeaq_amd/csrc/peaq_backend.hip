@@ -448,6 +448,23 @@ struct PointWalk {
 };
 
 // ---------------------------------------------------------------------------
+// Band traces (BandArgs, peaq_batch_run_bands): one plane's two values of a lane -- its bands 2 lane and 2 lane + 1 --
+// as one 16-byte store into the row of (pair, frame, channel), `cell` = (pair frame_stride + frame) channels + channel.
+// The plane test is on a kernel argument, so wave-uniform; the row's pad entry (band NB of NB + 1) belongs to the lane
+// that owns band NB - 1, whose v1 the caller hands over as 0, and the lanes beyond it store nothing.
+// ---------------------------------------------------------------------------
+template <int NB>
+__device__ __forceinline__ void band_store(const BandArgs& bnd, uint32_t bit, size_t cell, int lane, double v0, double v1) {
+  if (!(bnd.planes & bit)) return;
+  const unsigned n_planes = __builtin_popcount(bnd.planes), slot = __builtin_popcount(bnd.planes & (bit - 1u));
+  // (a uniform row address and the lane's 32-bit byte offset: the store takes them as they are, no 64-bit lane address)
+  char* __restrict__ row = reinterpret_cast<char*>(bnd.bands + (cell * n_planes + slot) * band_row(NB));
+  unsigned off = (unsigned)lane * 16u;
+  asm volatile("" : "+v"(off));                      // (made here, not kept as a 64-bit lane address across the frame loop)
+  if (2 * lane < NB) *reinterpret_cast<double2*>(row + off) = make_double2(v0, v1);
+}
+
+// ---------------------------------------------------------------------------
 // FFT-model back end.  ADV = false: basic version (109 bands, 11 MOVs).
 // ADV = true: the FFT part of the advanced version (55 bands; SegmentalNMR, EHS).
 // ---------------------------------------------------------------------------
@@ -472,35 +489,53 @@ struct BackendShared {
 // get a snapshot (PointWalk); the arithmetic is the same as the plain instantiation's.
 // TRC = true (backend_trace_kernel, trace launches only): the MOV values are computed for every frame, as with DBG, and
 // one lane per (frame, channel) writes them as a compact record (TraceArgs) -- no pattern dump.
+// BND = true (backend_bands_kernel, band-trace launches only): every lane stores the per-band values of its two bands
+// where they come up (BandArgs, band_store); the arithmetic and the gates are the plain instantiation's.
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false, TRC = false;
+  constexpr bool PTS = false, TRC = false, BND = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
+  constexpr BandArgs bnd{};
 #include "peaq_backend_fft.inc"
 }
 // The points instantiation is a kernel of its own name with the same body (not a fourth template parameter of
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false;
   constexpr TraceArgs trc{};
+  constexpr BandArgs bnd{};
 #include "peaq_backend_fft.inc"
 }
 // the trace instantiation: a third kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false;
   constexpr PointArgs pts{};
+  constexpr BandArgs bnd{};
+#include "peaq_backend_fft.inc"
+}
+// the bands instantiation: a fourth kernel of its own name with the same body
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true;
+  constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
 #include "peaq_backend_fft.inc"
 }
 
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                          const TraceArgs* trc) {
+                          const TraceArgs* trc, const BandArgs* bnd) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
-  if (trc && !a.advanced)
+  if (bnd && (pts || trc || a.debug || a.pair_frame0)) return hipErrorInvalidValue;   // a run's own launches only
+  if (bnd && !a.advanced)
+    hipLaunchKernelGGL((backend_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *bnd);
+  else if (bnd)
+    hipLaunchKernelGGL((backend_bands_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *bnd);
+  else if (trc && !a.advanced)
     hipLaunchKernelGGL((backend_trace_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *trc);
   else if (trc)
     hipLaunchKernelGGL((backend_trace_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *trc);

@@ -1,6 +1,6 @@
-// peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = false),
-// backend_points_kernel<NB, ADV> (PTS = true) and backend_trace_kernel<NB, ADV> (TRC = true) in peaq_backend.hip: one
-// text, three kernels of their own names.
+// peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = BND =
+// false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true) and
+// backend_bands_kernel<NB, ADV> (BND = true) in peaq_backend.hip: one text, four kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -52,7 +52,9 @@
   for (int s = 0; s < SLOTS; ++s) {
     const int b = bl.band(s);
     sm[0][s] = cs->vec[kSmearRef][b < kBandStride ? b : 0];
-    sm[1][s] = cs->vec[kSmearTest][b < kBandStride ? b : 0];
+    // (the 55-band path never changes the test filter; its bands kernel leaves that state in memory: the band stores
+    // take the four registers it would sit in through the frame loop)
+    sm[1][s] = BND && ADV ? 0. : cs->vec[kSmearTest][b < kBandStride ? b : 0];
 #pragma unroll
     for (int v = 0; v < 6; ++v) la[v][s] = cs->vec[kLaFiltRef + v][b < kBandStride ? b : 0];
 #pragma unroll
@@ -139,6 +141,13 @@
       }
     }
 
+    // (bands instantiation only) the row cell of this (pair, frame, channel); the smeared excitations go out here
+    const size_t bnd_cell = BND ? ((size_t)pair * bnd.frame_stride + frame) * channels + chan : 0;
+    if (BND) {
+      band_store<NB>(bnd, kBandExcRef, bnd_cell, lane, er[0], bl.valid(1) ? er[1] : 0.);
+      if (!ADV) band_store<NB>(bnd, kBandExcTest, bnd_cell, lane, et[0], bl.valid(1) ? et[1] : 0.);
+    }
+
     // lane i owns accumulator i: every MOV value of the frame is routed to its owner as soon as
     // it exists (two selects) instead of being kept in a per-lane table
     double my_v = 0., my_w = 1.;
@@ -189,6 +198,7 @@
         }
       }
       // ---- detection probability, per channel part (movs.c:1239-1262) -----------------
+      double bnd_x[SLOTS], bnd_q[SLOTS];             // (bands instantiation only: dead otherwise)
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
         double pc = 0., qc = 0.;
@@ -214,6 +224,12 @@
         }
         sh.pc[chan][bl.band(s)] = pc;
         sh.qc[chan][bl.band(s)] = qc;
+        bnd_x[s] = pc;
+        bnd_q[s] = qc;
+      }
+      if (BND) {
+        band_store<NB>(bnd, kBandDetect, bnd_cell, lane, bnd_x[0], bnd_x[1]);
+        band_store<NB>(bnd, kBandSteps, bnd_cell, lane, bnd_q[0], bnd_q[1]);
       }
       __syncthreads();
       if (loud_reached == UINT_MAX) {
@@ -262,14 +278,17 @@
     // lanes' parts first, then ONE reduction for the three sums of this place (with the noise loudness's from above) ----
     {
       double nsum = 0., nmax = 0.;
+      double bnd_r[SLOTS] = {0., 0.};                  // (bands instantiation only: dead otherwise)
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
         if (bl.valid(s)) {
           const double r = div_fast(nz[s] * bt.mask_diff(bl.band(s)), er[s]);   // noise / (excitation / mask)
           nsum += r;
           if (r > nmax) nmax = r;
+          bnd_r[s] = r;
         }
       }
+      if (BND) band_store<NB>(bnd, kBandNmr, bnd_cell, lane, bnd_r[0], bnd_r[1]);
       double xsum = 0., qsum = 0.;                    // sum of the bands' exponents (pc above), of the steps
       if (!ADV && chan == 0) {
 #pragma unroll
@@ -397,7 +416,7 @@
     const int b = bl.band(s);
     if (b < kBandStride) {
       cs->vec[kSmearRef][b] = sm[0][s];
-      cs->vec[kSmearTest][b] = sm[1][s];
+      if (!(BND && ADV)) cs->vec[kSmearTest][b] = sm[1][s];
       if (!ADV) {                                    // advanced: these belong to the filter-bank back end
 #pragma unroll
         for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][b] = la[v][s];

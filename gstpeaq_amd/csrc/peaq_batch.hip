@@ -190,23 +190,33 @@ static_assert(PEAQ_TRACE_ABOVE == kTraceAbove && PEAQ_TRACE_MOD_OPEN == kTraceMo
                   PEAQ_TRACE_LOUD_OPEN == kTraceLoudOpen && PEAQ_TRACE_FLUSH == kTraceFlush,
               "the flags of include/peaq_amd.h and peaq_kernels.h");
 
+// Rows of a band trace (peaq_batch_run_bands): nullptr for a plain batch.  Never together with a trajectory or a trace.
+struct BandOut {
+  double* d_bands;              // [n_pairs][frame_stride][channels][n_planes][band_row]
+  size_t frame_stride;
+  uint32_t planes;
+};
+static_assert(PEAQ_BAND_NMR == kBandNmr && PEAQ_BAND_EXC_REF == kBandExcRef && PEAQ_BAND_EXC_TEST == kBandExcTest &&
+                  PEAQ_BAND_DETECT == kBandDetect && PEAQ_BAND_STEPS == kBandSteps,
+              "the planes of include/peaq_amd.h and peaq_kernels.h");
+
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to);
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo);
 
-// peaq_batch_run, peaq_batch_run_trajectory and peaq_batch_run_trace: one driver, the points and the trace records
-// optional (`who` names the entry in messages)
+// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace and peaq_batch_run_bands: one driver, the points, the
+// trace records and the band rows optional (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
-                           const TrajectoryOut* tr, const TraceOut* to = nullptr) {
+                           const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr && !to)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -219,7 +229,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                                  n_test, n_uniform, d_results, stream, tr, to);
+                                  n_test, n_uniform, d_results, stream, tr, to, bo);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -294,6 +304,65 @@ extern "C" int peaq_batch_run_trace(peaq_ctx* c, int advanced, int channels, dou
                          n_ref, n_test, n_uniform, d_results, stream_, nullptr, &to);
 }
 
+// ---- band traces ----------------------------------------------------------------------------------------------
+extern "C" int peaq_band_count(int advanced) { return advanced ? 55 : 109; }
+extern "C" int peaq_band_row(int advanced) { return band_row(peaq_band_count(advanced)); }
+
+// what build_fft_band_tables builds (host only: no context, no device)
+extern "C" int peaq_band_tables(int advanced, double* fc, double* mask_diff) {
+  if (!fc && !mask_diff) return fail(PEAQ_ERR_ARG, "peaq_band_tables: NULL argument");
+  static const auto built = [](int bands) {          // once per process, on the first call
+    auto t = std::make_unique<BandTables>();
+    build_fft_band_tables(bands, *t);
+    return t;
+  };
+  static const std::unique_ptr<BandTables> tabs[2] = {built(109), built(55)};
+  const BandTables& t = *tabs[advanced ? 1 : 0];
+  for (int b = 0; b < t.bands; ++b) {
+    if (fc) fc[b] = t.fc[b];
+    if (mask_diff) mask_diff[b] = t.mask_diff[b];
+  }
+  return PEAQ_OK;
+}
+
+// `planes` as the band entries take it; 0 or an error with the value in the message
+int check_band_planes(const std::string& w, int advanced, uint32_t planes) {
+  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
+  if (planes & ~kBandAll)
+    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) + " has a bit above 16 (PEAQ_BAND_STEPS)");
+  if (advanced && (planes & ~kBandAdvanced))
+    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) +
+                                  " asks for a plane the advanced version does not have (" +
+                                  std::to_string(planes & ~kBandAdvanced) +
+                                  ": its 55-band path has PEAQ_BAND_NMR and PEAQ_BAND_EXC_REF only)");
+  return PEAQ_OK;
+}
+
+// The band trace's own arguments first, as the trace's: they need no context and no device.
+extern "C" int peaq_batch_run_bands(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                                    const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                    const uint32_t* n_test, uint32_t n_uniform, uint32_t planes, double* d_bands,
+                                    size_t frame_stride, peaq_result* d_results, void* stream_) {
+  const std::string w("peaq_batch_run_bands");
+  if (int rc = check_band_planes(w, advanced, planes)) return rc;
+  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
+  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
+  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
+    uint32_t max_frames = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
+      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
+      if (!n_ref) break;
+    }
+    if (frame_stride < max_frames)
+      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
+                                    std::to_string(max_frames) + " frames");
+  }
+  const BandOut bo{d_bands, frame_stride, planes};
+  return batch_run_entry("peaq_batch_run_bands", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
+                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, &bo);
+}
+
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
   if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
   if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
@@ -363,7 +432,7 @@ extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels,
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to) {
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -427,6 +496,14 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     ta.n_uniform = n_uniform;
   }
   const TraceArgs* trc = to ? &ta : nullptr;
+  // band trace: the FFT back end writes the caller's rows directly; the filter-bank side runs its plain kernels
+  BandArgs bna{};
+  if (bo) {
+    bna.bands = bo->d_bands;
+    bna.frame_stride = bo->frame_stride;
+    bna.planes = bo->planes;
+  }
+  const BandArgs* bnd = bo ? &bna : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
@@ -521,7 +598,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;

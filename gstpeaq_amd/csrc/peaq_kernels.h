@@ -87,6 +87,19 @@ struct TraceArgs {
   uint32_t n_uniform;
 };
 
+// ---- per-band traces (peaq_batch_run_bands) ------------------------------------------
+// The values the FFT back end has per (frame, channel, band) before it reduces them, stored where they come up.  The
+// bits mirror PEAQ_BAND_* in include/peaq_amd.h (peaq_batch.hip asserts them).  A kernel argument of the bands
+// instantiation only, like PointArgs and TraceArgs.
+constexpr uint32_t kBandNmr = 1u, kBandExcRef = 2u, kBandExcTest = 4u, kBandDetect = 8u, kBandSteps = 16u;
+constexpr uint32_t kBandAll = 31u, kBandAdvanced = kBandNmr | kBandExcRef;   // (the 55-band path has the first two)
+constexpr int band_row(int bands) { return (bands + 1) & ~1; }                // doubles per row: 110 / 56
+struct BandArgs {
+  double* bands;                // [pair][frame_stride][channel][plane slot][band_row], 16-byte aligned; a pair's rows at
+  size_t frame_stride;          // its ABSOLUTE frame index
+  uint32_t planes;              // kBand* bits; the slot of a plane is the rank of its bit among the set ones
+};
+
 // ---- pattern back end (time smearing .. MOV accumulation) -------------------
 struct BackendArgs {
   const double* records;        // as written by the front end
@@ -110,8 +123,9 @@ struct BackendArgs {
 };
 // pts != nullptr (trajectory launches only): the points instantiation, snapshots after frames (PointArgs)
 // trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per frame (TraceArgs)
+// bnd != nullptr (band-trace launches only, never with pts or trc): the bands instantiation, rows per frame (BandArgs)
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
-                          const TraceArgs* trc = nullptr);
+                          const TraceArgs* trc = nullptr, const BandArgs* bnd = nullptr);
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h

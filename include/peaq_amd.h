@@ -334,6 +334,51 @@ int peaq_batch_run_trace (peaq_ctx *ctx, int advanced, int channels, double play
 size_t peaq_trace_sizes (size_t *frame_bytes, size_t *block_bytes);
 /* (peaq_run_pair_trace, the same for one pair from host memory: after peaq_run_pair_aligned below) */
 
+/* ---- band traces: the FFT path's values per frame, channel and BAND ----------------
+ * A frame trace says in which frames the score was lost; a band trace says at which frequency: peaq_batch_run_bands
+ * writes, in the same run that scores the batch, the values the FFT back end has per critical band before it reduces
+ * them to the frame trace's mean, maximum and probability -- a noise-to-mask spectrogram and what goes with it.
+ * `planes` selects them (FP64, before accumulation, for every frame of the pair, the flush frame included):
+ *     PEAQ_BAND_NMR       r = noise * mask_diff / exc_ref (movs.c:1002-1022), linear; its mean over the bands is the
+ *                         frame trace's ch[c][4], its maximum ch[c][5]                          basic, advanced (55 bands)
+ *     PEAQ_BAND_EXC_REF   the smeared reference excitation (fftearmodel.c:496-504), the denominator above; the masking
+ *                         threshold is exc_ref / mask_diff                                       basic, advanced
+ *     PEAQ_BAND_EXC_TEST  the smeared test excitation                                            basic
+ *     PEAQ_BAND_DETECT    the channel's detection exponent x = (e / s)^b (movs.c:1239-1253): the band's probability is
+ *                         1 - 2^-x, the frame's 1 - 2^-(sum_b max_c x)                           basic
+ *     PEAQ_BAND_STEPS     the channel's steps above threshold q = |trunc e| / s (:1256-1260;
+ *                         use_floor_for_steps_above_threshold applies); the frame's: sum_b max_c q   basic
+ *   The 55-band path of the advanced version computes neither the test excitation nor the detection terms; the
+ *   filter-bank path's 40 bands, the per-band modulation differences and noise loudness are not traced.
+ *
+ * Layout: the value of plane slot k -- the rank of the plane's bit among the set bits of `planes` -- sits at
+ *   d_bands[((((p * frame_stride + f) * channels + c) * n_planes + k) * row) + b],  row = peaq_band_row (advanced),
+ * b < peaq_band_count (advanced); the row's last entry (b = 109 of 110, 55 of 56) is written 0.  Pair p has
+ * peaq_frame_count (n_ref[p], n_test[p], 0) frames; rows past a pair's count are left untouched.  peaq_band_tables
+ * (host only, no device) gives the bands' centre frequencies in Hz and the mask_diff factors of the ratio above.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs; the context's settings and, in
+ * the advanced version (whose filter-bank side runs as in peaq_batch_run), its FIR mode apply as they do there.
+ * PEAQ_ERR_ARG, before any device is touched and with a message that names the value: planes zero or with a bit above
+ * 16, a plane the version does not have, d_bands NULL or not 16-byte aligned (the rows go out as 16-byte stores), a
+ * frame_stride below the longest pair's count, and everything peaq_batch_run refuses.  Band trace, trace and
+ * trajectory are separate calls. */
+#define PEAQ_BAND_NMR       1u
+#define PEAQ_BAND_EXC_REF   2u
+#define PEAQ_BAND_EXC_TEST  4u
+#define PEAQ_BAND_DETECT    8u
+#define PEAQ_BAND_STEPS    16u
+
+int peaq_band_count (int advanced);      /* 109 / 55 */
+int peaq_band_row (int advanced);        /* 110 / 56: doubles per row, the count rounded up to even */
+int peaq_band_tables (int advanced, double *fc /* [count] */, double *mask_diff /* [count] */);   /* host only */
+int peaq_batch_run_bands (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, int n_pairs,
+                          const float *d_ref, const float *d_test, size_t pair_stride,
+                          const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                          uint32_t planes, double *d_bands /* device */, size_t frame_stride,
+                          peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+/* (peaq_run_pair_bands, the same for one pair from host memory: after peaq_run_pair_trace below) */
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -502,6 +547,15 @@ int peaq_run_pair_trace (peaq_ctx *ctx, int advanced, int channels, double playb
                          const float *ref, size_t n_ref, const float *test, size_t n_test,
                          peaq_frame_trace *frames /* host */, size_t frame_cap, uint32_t *n_frames,
                          peaq_block_trace *blocks /* host */, size_t block_cap, uint32_t *n_blocks,
+                         peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_bands (above) for one pair from HOST memory, rows into a host array [frame_cap][channels][n_planes][row]:
+ * upload, conversion, alignment and counts as in peaq_run_pair_trace.  n_frames (may be NULL) receives the count of
+ * frames written; a frame_cap below it is PEAQ_ERR_ARG with both numbers in the message.  out (may be NULL): the
+ * pair's result. */
+int peaq_run_pair_bands (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
+                         uint32_t rate, uint32_t max_lag,
+                         const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
+                         double *bands /* host */, size_t frame_cap, uint32_t *n_frames,
                          peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
