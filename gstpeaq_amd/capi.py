@@ -150,6 +150,10 @@ BLOCK_TRACE_VALUES = ["rmsmoddiff", "tempwt", "noiseloud", "missing", "lindist"]
 
 # PEAQ_BAND_* (include/peaq_amd.h) by name, in the order of their bits -- which is the order of the plane slots
 BAND_PLANES = {"nmr": 1, "exc_ref": 2, "exc_test": 4, "detect": 8, "steps": 16}
+# PEAQ_FB_BAND_* (include/peaq_amd.h) by name, in the order of their bits -- which is the order of the plane slots
+FB_BAND_PLANES = {"moddiff": 0x1, "modwt": 0x2, "noiseloud": 0x4, "missing": 0x8, "lindist": 0x10, "unsm_ref": 0x20,
+                  "unsm_test": 0x40, "exc_ref": 0x80, "exc_test": 0x100, "adapt_ref": 0x200, "adapt_test": 0x400,
+                  "mod_ref": 0x800, "mod_test": 0x1000}
 
 
 class HostPair(C.Structure):
@@ -290,6 +294,13 @@ def load_library():
                                            C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.peaq_run_pair_bands.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
                                           C.c_size_t, C.c_uint32, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_fb_bands"):        # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_fb_band_count.argtypes = []
+        L.peaq_fb_band_tables.argtypes = [dp, dp]
+        L.peaq_batch_run_fb_bands.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p,
+                                              C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
+        L.peaq_run_pair_fb_bands.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
+                                             C.c_size_t, C.c_uint32, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_resample_supported.argtypes = [C.c_uint32]
         L.peaq_resampled_length.restype = C.c_uint32
@@ -2017,6 +2028,116 @@ def run_pair_bands(ctx, advanced, ref, test, planes=("nmr",), playback_level=92.
     fc, md = band_tables(adv)
     res = dict(_band_planes_dict(rows[:nf.value], mask, n_bands), result=_result_dict(out, bool(advanced)), fc=fc,
                mask_diff=md, planes=mask)
+    if align is not None:
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+    return res
+
+
+def fb_band_planes_mask(planes):
+    """a PEAQ_FB_BAND_* mask from plane names (FB_BAND_PLANES; one name, or several in any order) or from a mask"""
+    if isinstance(planes, (int, np.integer)):
+        return int(planes)
+    if isinstance(planes, str):
+        planes = [planes]
+    unknown = [p for p in planes if p not in FB_BAND_PLANES]
+    if unknown:
+        raise PeaqError(f"unknown filter-bank band plane {unknown[0]!r} (one of {', '.join(FB_BAND_PLANES)})")
+    mask = 0
+    for p in planes:
+        mask |= FB_BAND_PLANES[p]
+    return mask
+
+
+def fb_band_tables():
+    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 40 bands of the filter-bank
+    path (peaq_fb_band_tables; host only)"""
+    L = load_library()
+    n = L.peaq_fb_band_count()
+    fc, noise = np.zeros(n), np.zeros(n)
+    dp = C.POINTER(C.c_double)
+    _check(L.peaq_fb_band_tables(fc.ctypes.data_as(dp), noise.ctypes.data_as(dp)))
+    return fc, noise
+
+
+def _fb_band_planes_dict(rows, mask):
+    """rows [..., n_planes, 40] -> {name: [..., 40]} in the order of the slots"""
+    names = [name for name, bit in FB_BAND_PLANES.items() if mask & bit]
+    return {name: rows[..., k, :] for k, name in enumerate(names)}
+
+
+def batch_fb_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_test=None, playback_level=92.0, rate=48000,
+                   align=None, stream=None, sync=True, d_bands=None):
+    """The filter-bank path's values per block, channel and band of every pair, in the run that scores them in the
+    advanced version (peaq_batch_run_fb_bands).  planes: names of FB_BAND_PLANES (or a PEAQ_FB_BAND_* mask); ref/test,
+    n_ref/n_test, rate and align as for batch_run.  d_bands: an optional CUDA float64 tensor [n_pairs, stride, channels,
+    n_planes, 40] to write into (rows past a pair's count keep what they held); without it a zero-filled one of the
+    longest pair's count is made.
+    Returns a dict: every requested plane by name, np.ndarray [pairs, blocks_max, channels, 40], counts (numpy, blocks
+    per pair), results (result dicts), fc and internal_noise (fb_band_tables), planes (the mask), and d_bands /
+    d_results, the device tensors.  sync=False: the device tensors, counts, fc, internal_noise and planes only."""
+    import torch
+    mask = fb_band_planes_mask(planes)
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
+    cnt = {rt: frame_count(*rt, True) for rt in set(lens)}   # once per distinct pair of lengths
+    counts = np.array([cnt[rt] for rt in lens], dtype=np.uint32)
+    n_bands, n_planes = ctx.L.peaq_fb_band_count(), bin(mask & 0x1FFF).count("1")
+    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
+        if d_bands is None:
+            b_stride = max(int(counts.max()) if n_pairs else 0, 1)
+            d_bands = torch.zeros((n_pairs, b_stride, channels, max(n_planes, 1), n_bands), dtype=torch.float64, device=ref.device)
+        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
+    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), n_bands)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_run_fb_bands(ctx.h, channels, float(playback_level), n_pairs,
+                                         C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                         a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                         a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                         mask, C.c_void_p(d_bands.data_ptr()), d_bands.shape[1],
+                                         C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    fc, noise = fb_band_tables()
+    out = dict(d_bands=d_bands, d_results=results, counts=counts, fc=fc, internal_noise=noise, planes=mask)
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    out.update(_fb_band_planes_dict(d_bands.cpu().numpy(), mask))
+    out["results"] = [_result_dict(r, True) for r in results.cpu().numpy()]
+    return out
+
+
+def run_pair_fb_bands(ctx, ref, test, planes=("noiseloud",), playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_fb_bands: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
+    first with align = a max_lag in 48 kHz samples.  Returns a dict: every requested plane by name, np.ndarray
+    [blocks, channels, 40], result (a result dict), fc, internal_noise, planes (the mask) and, with align, delay."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    ch = ref.shape[1]
+    assert test.shape[1] == ch
+    mask = fb_band_planes_mask(planes)
+    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
+    b_cap = max(frame_count(*lens, True), 1)
+    rows = np.zeros((b_cap, ch, max(bin(mask & 0x1FFF).count("1"), 1), ctx.L.peaq_fb_band_count()))
+    nb, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_fb_bands(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
+                                        ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                        test.ctypes.data_as(C.POINTER(C.c_float)), len(test), mask,
+                                        C.c_void_p(rows.ctypes.data), b_cap, C.byref(nb), C.byref(rec),
+                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+    fc, noise = fb_band_tables()
+    res = dict(_fb_band_planes_dict(rows[:nb.value], mask), result=_result_dict(out, True), fc=fc,
+               internal_noise=noise, planes=mask)
     if align is not None:
         res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
     return res

@@ -753,3 +753,34 @@ extern "C" int peaq_run_pair_bands(peaq_ctx* c, int advanced, int channels, doub
   if (n_frames) *n_frames = nf;
   return PEAQ_OK;
 }
+
+extern "C" int peaq_run_pair_fb_bands(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                      const float* ref, size_t n_ref, const float* test, size_t n_test, uint32_t planes,
+                                      double* bands, size_t block_cap, uint32_t* n_blocks, peaq_delay* delay,
+                                      peaq_result* out) {
+  const std::string w("peaq_run_pair_fb_bands");
+  if (int rc = check_fb_band_planes(w, planes)) return rc;
+  if (!bands) return fail(PEAQ_ERR_ARG, w + ": bands is NULL");
+  if (max_lag)
+    if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
+  ScoredPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
+    return rc;
+  const uint32_t nb = peaq_frame_count(pp.len[0], pp.len[1], 1);
+  if (nb > block_cap)
+    return fail(PEAQ_ERR_ARG, w + ": block_cap " + std::to_string(block_cap) + " is below the pair's " + std::to_string(nb) + " blocks");
+  const size_t block_bytes = (size_t)channels * __builtin_popcount(planes) * peaq_fb_band_count() * sizeof(double);
+  DevBuf d_res, d_bn;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  HIP_TRY(d_bn.reserve(std::max<size_t>(nb, 1) * block_bytes));
+  if (int rc = peaq_batch_run_fb_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0, planes,
+                                       d_bn.as<double>(), nb, d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (nb) HIP_TRY(hipMemcpy(bands, d_bn.p, (size_t)nb * block_bytes, hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  if (n_blocks) *n_blocks = nb;
+  return PEAQ_OK;
+}

@@ -464,6 +464,18 @@ __device__ __forceinline__ void band_store(const BandArgs& bnd, uint32_t bit, si
   if (2 * lane < NB) *reinterpret_cast<double2*>(row + off) = make_double2(v0, v1);
 }
 
+// Filter-bank band traces (FbBandArgs, peaq_batch_run_fb_bands): one plane's value of a lane -- its band -- into the row
+// of `row0` + the plane's slot, rows of kFbBands doubles.  The plane test is on a kernel argument, so wave-uniform, and
+// so is the row address; the lane adds a 32-bit byte offset, and the lanes beyond the last band store nothing.
+__device__ __forceinline__ void fb_band_store(const FbBandArgs& bnd, uint32_t bit, size_t row0, int lane, double v) {
+  if (!(bnd.planes & bit)) return;
+  const unsigned slot = __builtin_popcount(bnd.planes & (bit - 1u));
+  char* __restrict__ row = reinterpret_cast<char*>(bnd.bands + (row0 + slot) * kFbBands);
+  unsigned off = (unsigned)lane * 8u;
+  asm volatile("" : "+v"(off));                      // (made here, not kept as a 64-bit lane address across the block loop)
+  if (lane < kFbBands) *reinterpret_cast<double*>(row + off) = v;
+}
+
 // ---------------------------------------------------------------------------
 // FFT-model back end.  ADV = false: basic version (109 bands, 11 MOVs).
 // ADV = true: the FFT part of the advanced version (55 bands; SegmentalNMR, EHS).
@@ -573,30 +585,46 @@ struct FbBackendShared {
 // get the snapshot of the accumulators this path owns (0, 1, 4).
 // TRC = true (fb_backend_trace_kernel, trace launches only): the block's MOV values are computed for every block, as
 // with DBG, and one lane per (block, channel) writes them into the pair's block record (TraceArgs).
+// BND = true (fb_backend_bands_kernel, filter-bank band-trace launches only): the block's MOV values are computed for
+// every block, as with TRC, and every lane below 40 stores its band's value of the requested planes where it comes up
+// (FbBandArgs, fb_band_store); the accumulators see what the gates admit, as in the plain instantiation.
 template <bool DBG>
 __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
-  constexpr bool PTS = false, TRC = false;
+  constexpr bool PTS = false, TRC = false, BND = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
+  constexpr FbBandArgs bnd{};
 #include "peaq_backend_fb.inc"
 }
 // the points instantiation (see backend_points_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false;
   constexpr TraceArgs trc{};
+  constexpr FbBandArgs bnd{};
 #include "peaq_backend_fb.inc"
 }
 // the trace instantiation (see backend_trace_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_trace_kernel(FbBackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false;
   constexpr PointArgs pts{};
+  constexpr FbBandArgs bnd{};
+#include "peaq_backend_fb.inc"
+}
+// the bands instantiation (see backend_bands_kernel)
+__global__ __launch_bounds__(128, 4) void fb_backend_bands_kernel(FbBackendArgs a, FbBandArgs bnd) {
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true;
+  constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
 #include "peaq_backend_fb.inc"
 }
 
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                             const TraceArgs* trc) {
+                             const TraceArgs* trc, const FbBandArgs* bnd) {
   if (n_pairs == 0) return hipSuccess;
-  if (trc)
+  if (bnd && (pts || trc || a.debug || a.windows)) return hipErrorInvalidValue;   // a run's own launches only
+  if (bnd)
+    hipLaunchKernelGGL(fb_backend_bands_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *bnd);
+  else if (trc)
     hipLaunchKernelGGL(fb_backend_trace_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *trc);
   else if (pts)
     hipLaunchKernelGGL(fb_backend_points_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *pts);

@@ -1,6 +1,6 @@
-// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = false),
-// fb_backend_points_kernel (PTS = true) and fb_backend_trace_kernel (TRC = true) in peaq_backend.hip: one text, three
-// kernels of their own names.
+// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = BND = false),
+// fb_backend_points_kernel (PTS = true), fb_backend_trace_kernel (TRC = true) and fb_backend_bands_kernel (BND = true)
+// in peaq_backend.hip: one text, four kernels of their own names.
   __shared__ FbBackendShared sh;
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
   __shared__ double sh_etab[kExpTabEntries];
@@ -81,15 +81,21 @@
     in.f1 = channels == 2 ? rec0[kFbRecDoubles + kFbRecFlags] : 0.;
     return in;
   };
-  // (the trace instantiation loads each block as it comes to it: the twelve registers of the block held ahead are what
-  // it needs to keep every block's values without scratch)
-  BlockIn nxt = TRC ? BlockIn{} : fetch(b_begin);
+  // (the trace and bands instantiations load each block as they come to it: the twelve registers of the block held
+  // ahead are what they need to keep every block's values without scratch)
+  constexpr bool ALL = TRC || BND;                   // the block's MOV values for every block, whatever the gates
+  BlockIn nxt = ALL ? BlockIn{} : fetch(b_begin);
+  // (bands instantiation only) the row of plane slot 0 of (pair, block 0, this wave's channel): uniform, like the plane
+  // tests on the kernel argument; a block's rows lie channels * n_planes rows further on
+  const unsigned bnd_planes = BND ? (unsigned)__builtin_popcount(bnd.planes) : 0u;
+  const size_t bnd_cell0 = BND ? ((size_t)pair * bnd.block_stride * channels + wave_uniform(chan)) * bnd_planes : 0;
   for (unsigned blk = b_begin; blk < b_end; ++blk) {
-    const BlockIn cur = TRC ? fetch(blk) : nxt;
-    // (... and re-reads the per-band constants from the tables in every block: held across the loop they are the ten
+    const BlockIn cur = ALL ? fetch(blk) : nxt;
+    // (... and re-read the per-band constants from the tables in every block: held across the loop they are the ten
     // registers the other instantiations keep in scratch)
-    if (TRC) asm volatile("" : "+s"(bt.p));
-    if (!TRC && blk + 1 < b_end) nxt = fetch(blk + 1);
+    if (ALL) asm volatile("" : "+s"(bt.p));
+    if (!ALL && blk + 1 < b_end) nxt = fetch(blk + 1);
+    const size_t bnd_row = BND ? bnd_cell0 + (size_t)blk * channels * bnd_planes : 0;
     // boundary detector on the 192-sample block, any reference channel (gstpeaq.c:971-979)
     const bool above = cur.f0 != 0. || cur.f1 != 0.;
     if (owns) acc.set_tentative(!above);
@@ -99,12 +105,24 @@
     ut[0] = cur.ut;
     er[0] = cur.er;
     et[0] = cur.et;
+    if (BND) {
+      fb_band_store(bnd, kFbBandUnsmRef, bnd_row, lane, ur[0]);
+      fb_band_store(bnd, kFbBandUnsmTest, bnd_row, lane, ut[0]);
+      fb_band_store(bnd, kFbBandExcRef, bnd_row, lane, er[0]);
+      fb_band_store(bnd, kFbBandExcTest, bnd_row, lane, et[0]);
+    }
     lr[0] = bt.pow(ur[0], 0.3);                      // modpatt.c:235
     lt[0] = bt.pow(ut[0], 0.3);
     double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
     level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
     modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
     modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+    if (BND) {
+      fb_band_store(bnd, kFbBandAdaptRef, bnd_row, lane, ad_ref[0]);
+      fb_band_store(bnd, kFbBandAdaptTest, bnd_row, lane, ad_test[0]);
+      fb_band_store(bnd, kFbBandModRef, bnd_row, lane, mr[0]);
+      fb_band_store(bnd, kFbBandModTest, bnd_row, lane, mt[0]);
+    }
     double* __restrict__ dbg =
         DBG ? a.debug + ((size_t)(pair * a.blocks_per_launch + (blk - b_begin)) * channels + chan) * kDbgFbDoubles : nullptr;
     if (loud_reached == UINT_MAX) {                  // workgroup-uniform
@@ -124,9 +142,13 @@
     }
     double v0 = 0., w0 = 1.;
     bool hit = false;
-    if (DBG || TRC || blk >= 125) {                  // gstpeaq.c:988-993
+    if (DBG || ALL || blk >= 125) {                  // gstpeaq.c:988-993
       double d1, d2, wt;
       mod_difference<NB, SLOTS>(bl, bt, 1., mr, mt, mdr[1], d1, d2, wt);
+      if (BND) {                                     // the lane's terms of d1 and wt, as mod_difference forms them
+        fb_band_store(bnd, kFbBandModDiff, bnd_row, lane, div_fast(fabs(mr[0] - mt[0]), 1. + mr[0]));
+        fb_band_store(bnd, kFbBandModWt, bnd_row, lane, div_fast(mdr[1][0], mdr[1][0] + 1. * bt.noise_pow03(bl.band(0))));
+      }
       d1 *= 100. / sqrt((double)NB);                 // MODE_RMS variant, movs.c:243-244
       if (blk >= 125 && lane == MA_RMSMOD) {
         v0 = d1;
@@ -142,7 +164,7 @@
         sh_trc[chan][chan + 1] = wt;
       }
     }
-    if (DBG || TRC || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
+    if (DBG || ALL || (blk >= 125 && blk - 13 >= loud_reached)) {    // gstpeaq.c:996-1007
       // movs.c:551-577; SWAP_MOD_PATTS_FOR_NOISE_LOUDNESS_MOVS (shipped: 1) exchanges the modulation
       // patterns of the missing-components term ...
       const bool swap = a.cfg.swap_mod_patts != 0;   // workgroup-uniform
@@ -153,6 +175,11 @@
       // ... and (movs.c:679-706) takes the reference modulation twice; unadapted FB excitation
       const double ld_p = noise_loudness_part<NB, SLOTS, GlobalTabs, LEAD_USE>(bl, bt, 1.5, 0.15, 1., mr, swap ? mr : mt,
                                                                                ad_ref, er, lead);
+      if (BND) {
+        fb_band_store(bnd, kFbBandNoiseLoud, bnd_row, lane, nl_p);
+        fb_band_store(bnd, kFbBandMissing, bnd_row, lane, mc_p);
+        fb_band_store(bnd, kFbBandLinDist, bnd_row, lane, ld_p);
+      }
       double nl, mc, ld, none;                       // the three sums over the bands in one reduction
       wave_sum4(nl_p, mc_p, ld_p, 0., nl, mc, ld, none);
       nl = noise_loudness_total<NB>(nl, 0.1);

@@ -73,7 +73,7 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
                                const float* d_test, size_t pair_stride, const uint32_t* d_nref,
                                const uint32_t* d_ntest, uint32_t n_uniform, const uint32_t* d_nblocks,
                                uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const PointArgs* pts,
-                               const TraceArgs* trc) {
+                               const TraceArgs* trc, const FbBandArgs* fbnd) {
     // ---- filter-bank path: blocks of 192 samples (gstpeaq.c:648-652) ------------------
     const unsigned n_signals = (unsigned)n_pairs * channels * 2;
     const unsigned bc = fb_blocks_per_chunk(n_pairs, channels, max_blocks);
@@ -150,7 +150,7 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
       HIP_TRY(hipEventRecord(e1, s_bank));
       bank_done[b] = e1;
       if (piped) HIP_TRY(hipStreamWaitEvent(s_be, e1, 0));
-      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts, trc));
+      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts, trc, fbnd));
       if (piped) {
         HIP_TRY(hipEventRecord(e_be, s_be));
         be_done[b] = e_be;
@@ -200,23 +200,40 @@ static_assert(PEAQ_BAND_NMR == kBandNmr && PEAQ_BAND_EXC_REF == kBandExcRef && P
                   PEAQ_BAND_DETECT == kBandDetect && PEAQ_BAND_STEPS == kBandSteps,
               "the planes of include/peaq_amd.h and peaq_kernels.h");
 
+// Rows of a filter-bank band trace (peaq_batch_run_fb_bands): nullptr for a plain batch.  Never together with any of the
+// three above; the back end writes the caller's rows directly -- no scratch of its own.
+struct FbBandOut {
+  double* d_bands;              // [n_pairs][block_stride][channels][n_planes][40]
+  size_t block_stride;
+  uint32_t planes;
+};
+static_assert(PEAQ_FB_BAND_MODDIFF == kFbBandModDiff && PEAQ_FB_BAND_MODWT == kFbBandModWt &&
+                  PEAQ_FB_BAND_NOISELOUD == kFbBandNoiseLoud && PEAQ_FB_BAND_MISSING == kFbBandMissing &&
+                  PEAQ_FB_BAND_LINDIST == kFbBandLinDist && PEAQ_FB_BAND_UNSM_REF == kFbBandUnsmRef &&
+                  PEAQ_FB_BAND_UNSM_TEST == kFbBandUnsmTest && PEAQ_FB_BAND_EXC_REF == kFbBandExcRef &&
+                  PEAQ_FB_BAND_EXC_TEST == kFbBandExcTest && PEAQ_FB_BAND_ADAPT_REF == kFbBandAdaptRef &&
+                  PEAQ_FB_BAND_ADAPT_TEST == kFbBandAdaptTest && PEAQ_FB_BAND_MOD_REF == kFbBandModRef &&
+                  PEAQ_FB_BAND_MOD_TEST == kFbBandModTest,
+              "the filter-bank planes of include/peaq_amd.h and peaq_kernels.h");
+
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo);
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo);
 
-// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace and peaq_batch_run_bands: one driver, the points, the
-// trace records and the band rows optional (`who` names the entry in messages)
+// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands and peaq_batch_run_fb_bands: one
+// driver, the points, the trace records and the band rows optional (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
-                           const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr) {
+                           const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr,
+                           const FbBandOut* fo = nullptr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -229,7 +246,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                                  n_test, n_uniform, d_results, stream, tr, to, bo);
+                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -363,6 +380,58 @@ extern "C" int peaq_batch_run_bands(peaq_ctx* c, int advanced, int channels, dou
                          n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, &bo);
 }
 
+// ---- band traces of the filter-bank path ------------------------------------------------------------------------
+extern "C" int peaq_fb_band_count(void) { return kFbBands; }
+
+// what build_fb_band_tables builds (host only: no context, no device)
+extern "C" int peaq_fb_band_tables(double* fc, double* internal_noise) {
+  if (!fc && !internal_noise) return fail(PEAQ_ERR_ARG, "peaq_fb_band_tables: NULL argument");
+  static const std::unique_ptr<BandTables> tabs = [] {     // once per process, on the first call
+    auto t = std::make_unique<BandTables>();
+    auto fb = std::make_unique<FbTables>();            // (the bank's coefficients come with the bands; not kept)
+    build_fb_band_tables(*t, *fb);
+    return t;
+  }();
+  for (int b = 0; b < kFbBands; ++b) {
+    if (fc) fc[b] = tabs->fc[b];
+    if (internal_noise) internal_noise[b] = tabs->internal_noise[b];
+  }
+  return PEAQ_OK;
+}
+
+// `planes` as the filter-bank band entries take it; 0 or an error with the value in the message
+int check_fb_band_planes(const std::string& w, uint32_t planes) {
+  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
+  if (planes & ~kFbBandAll)
+    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) + " has a bit above 4096 (PEAQ_FB_BAND_MOD_TEST)");
+  return PEAQ_OK;
+}
+
+// The band trace's own arguments first, as peaq_batch_run_bands': they need no context and no device.
+extern "C" int peaq_batch_run_fb_bands(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
+                                       const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                       const uint32_t* n_test, uint32_t n_uniform, uint32_t planes, double* d_bands,
+                                       size_t block_stride, peaq_result* d_results, void* stream_) {
+  const std::string w("peaq_batch_run_fb_bands");
+  if (int rc = check_fb_band_planes(w, planes)) return rc;
+  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
+  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
+  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
+    uint32_t max_blocks = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
+      max_blocks = std::max(max_blocks, count_frames(nr, nt, kFbFrame, kFbFrame));
+      if (!n_ref) break;
+    }
+    if (block_stride < max_blocks)
+      return fail(PEAQ_ERR_ARG, w + ": block_stride " + std::to_string(block_stride) + " is below the longest pair's " +
+                                    std::to_string(max_blocks) + " blocks");
+  }
+  const FbBandOut fo{d_bands, block_stride, planes};
+  return batch_run_entry("peaq_batch_run_fb_bands", c, 1, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
+                         n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, &fo);
+}
+
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
   if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
   if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
@@ -432,7 +501,7 @@ extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels,
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo) {
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -504,6 +573,14 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     bna.planes = bo->planes;
   }
   const BandArgs* bnd = bo ? &bna : nullptr;
+  // filter-bank band trace: the filter-bank back end writes the caller's rows directly; the FFT side runs its plain kernels
+  FbBandArgs fba{};
+  if (fo) {
+    fba.bands = fo->d_bands;
+    fba.block_stride = fo->block_stride;
+    fba.planes = fo->planes;
+  }
+  const FbBandArgs* fbnd = fo ? &fba : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
@@ -523,7 +600,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   auto issue_filterbank_path = [&](hipEvent_t bank_gate) -> int {
     hipStream_t s_fb = PEAQ_DEV_SERIAL_KERNELS ? stream : c->aux2;
     const int rc = run_filterbank_path(c, channels, level_db, n_pairs, d_ref, d_test, pair_stride, d_nref, d_ntest,
-                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts, trc);
+                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts, trc, fbnd);
     if (rc != PEAQ_OK) return rc;
     fb_done = c->next_event();
     if (!fb_done) return fail(PEAQ_ERR_DEVICE, "hipEventCreate failed");

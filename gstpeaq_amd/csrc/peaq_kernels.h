@@ -199,10 +199,25 @@ struct FbBackendArgs {
   // values before accumulation, computed for EVERY block in the debug instantiation -- or nullptr
   double* debug;
 };
+// ---- per-band traces of the filter-bank path (peaq_batch_run_fb_bands) ----------------------
+// The values the filter-bank back end has per (block, channel, band) before it reduces them, stored where they come up.
+// The bits mirror PEAQ_FB_BAND_* in include/peaq_amd.h (peaq_batch.hip asserts them).  A kernel argument of the
+// filter-bank bands instantiation only, like PointArgs and TraceArgs.
+constexpr uint32_t kFbBandModDiff = 0x1u, kFbBandModWt = 0x2u, kFbBandNoiseLoud = 0x4u, kFbBandMissing = 0x8u,
+                   kFbBandLinDist = 0x10u, kFbBandUnsmRef = 0x20u, kFbBandUnsmTest = 0x40u, kFbBandExcRef = 0x80u,
+                   kFbBandExcTest = 0x100u, kFbBandAdaptRef = 0x200u, kFbBandAdaptTest = 0x400u, kFbBandModRef = 0x800u,
+                   kFbBandModTest = 0x1000u, kFbBandAll = 0x1FFFu;
+struct FbBandArgs {
+  double* bands;                // [pair][block_stride][channel][plane slot][kFbBands], 16-byte aligned; a pair's rows at
+  size_t block_stride;          // its ABSOLUTE block index
+  uint32_t planes;              // kFbBand* bits; the slot of a plane is the rank of its bit among the set ones
+};
 // pts != nullptr (trajectory launches only): the points instantiation, snapshots after blocks (PointArgs)
 // trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per block (TraceArgs)
+// bnd != nullptr (filter-bank band-trace launches only, never with pts, trc, a.debug or a.windows): the bands
+// instantiation, rows per block (FbBandArgs)
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
-                             const TraceArgs* trc = nullptr);
+                             const TraceArgs* trc = nullptr, const FbBandArgs* bnd = nullptr);
 
 // ---- synthetic workload --------------------------------------------------------------
 hipError_t launch_synth(uint32_t seed0, unsigned n_pairs, int channels, uint32_t n_samples, size_t pair_stride,

@@ -349,7 +349,7 @@ size_t peaq_trace_sizes (size_t *frame_bytes, size_t *block_bytes);
  *     PEAQ_BAND_STEPS     the channel's steps above threshold q = |trunc e| / s (:1256-1260;
  *                         use_floor_for_steps_above_threshold applies); the frame's: sum_b max_c q   basic
  *   The 55-band path of the advanced version computes neither the test excitation nor the detection terms; the
- *   filter-bank path's 40 bands, the per-band modulation differences and noise loudness are not traced.
+ *   filter-bank path's 40 bands have a trace of their own (peaq_batch_run_fb_bands, below).
  *
  * Layout: the value of plane slot k -- the rank of the plane's bit among the set bits of `planes` -- sits at
  *   d_bands[((((p * frame_stride + f) * channels + c) * n_planes + k) * row) + b],  row = peaq_band_row (advanced),
@@ -378,6 +378,66 @@ int peaq_batch_run_bands (peaq_ctx *ctx, int advanced, int channels, double play
                           uint32_t planes, double *d_bands /* device */, size_t frame_stride,
                           peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
 /* (peaq_run_pair_bands, the same for one pair from host memory: after peaq_run_pair_trace below) */
+
+/* ---- band traces of the filter-bank path: its values per block, channel and BAND ----------------
+ * Three of the advanced version's five MOVs come from the filter-bank path (RmsModDiff, RmsNoiseLoudAsym, AvgLinDist);
+ * the block trace gives their five values per block and channel, peaq_batch_run_fb_bands the 40 per-band terms those
+ * are summed from and the patterns they are made of -- in the same run that scores the batch.  There is no `advanced`
+ * argument: the path exists in the advanced version only.  `planes` selects (FP64, before accumulation, for every
+ * block of the pair, the flush block included, whatever the gates of gstpeaq.c:988/996 let the accumulators see -- the
+ * block trace's convention).  With n the band's internal noise, er / et the excitations after time smearing
+ * (fbearmodel.c:371-395), ur / ut the unsmeared ones, ar / at the level- and pattern-adapted patterns
+ * (leveladapter.c:331-336), mr / mt the modulations (modpatt.c:245-247), lr the reference's average loudness
+ * (modpatt.c:240-243) and, movs.c:709-743,
+ *   T (alpha, f, m_ref, m_test, e_ref, e_test) =
+ *       (n / stest)^0.23 ((1 + max (stest e_test - sref e_ref, 0) / (n + sref e_ref beta))^0.23 - 1),
+ *       sref = f m_ref + 1, stest = f m_test + 1, beta = exp (-alpha (e_test - e_ref) / e_ref):
+ *     PEAQ_FB_BAND_MODDIFF     |mr - mt| / (1 + mr)                                   (movs.c:224-251)
+ *     PEAQ_FB_BAND_MODWT       lr / (lr + n^0.3)
+ *     PEAQ_FB_BAND_NOISELOUD   T (2.5, 0.3, mr, mt, ar, at)
+ *     PEAQ_FB_BAND_MISSING     T (1.5, 0.15, mt, mr, at, ar); with swap_mod_patts_for_noise_loudness_movs = 0:
+ *                              T (1.5, 0.15, mr, mt, at, ar)
+ *     PEAQ_FB_BAND_LINDIST     T (1.5, 0.15, mr, mr, ar, er); with the switch 0 the second modulation is mt
+ *     PEAQ_FB_BAND_UNSM_REF / _UNSM_TEST / _EXC_REF / _EXC_TEST / _ADAPT_REF / _ADAPT_TEST / _MOD_REF / _MOD_TEST
+ *                              ur, ut, er, et, ar, at, mr, mt
+ *   With the block record of the same pair (peaq_block_trace, sums over the 40 bands):
+ *     ch[c][0] = 100 / sqrt (40) sum MODDIFF      ch[c][1] = sum MODWT
+ *     ch[c][2] = 0.6 sum NOISELOUD, and 0 where that is below 0.1
+ *     ch[c][3] = 0.6 sum MISSING                  ch[c][4] = 0.6 sum LINDIST
+ *
+ * Layout: the value of plane slot k -- the rank of the plane's bit among the set bits of `planes` -- sits at
+ *   d_bands[((((p * block_stride + b) * channels + c) * n_planes + k) * 40) + band].
+ * Pair p has peaq_frame_count (n_ref[p], n_test[p], 1) blocks; rows past a pair's count are left untouched.
+ * peaq_fb_band_tables (host only, no device) gives the bands' centre frequencies in Hz and their internal noise; either
+ * pointer may be NULL, not both.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs in the advanced version; the
+ * context's settings and FIR mode apply as they do there.  PEAQ_ERR_ARG, before a context or a device is touched and
+ * with a message that names the value: planes zero or with a bit above 0x1000, d_bands NULL or not 16-byte aligned, a
+ * block_stride below the longest pair's count, and everything peaq_batch_run refuses.  A run of its own, like the band
+ * trace, the trace and the trajectory. */
+#define PEAQ_FB_BAND_MODDIFF     0x0001u
+#define PEAQ_FB_BAND_MODWT       0x0002u
+#define PEAQ_FB_BAND_NOISELOUD   0x0004u
+#define PEAQ_FB_BAND_MISSING     0x0008u
+#define PEAQ_FB_BAND_LINDIST     0x0010u
+#define PEAQ_FB_BAND_UNSM_REF    0x0020u
+#define PEAQ_FB_BAND_UNSM_TEST   0x0040u
+#define PEAQ_FB_BAND_EXC_REF     0x0080u
+#define PEAQ_FB_BAND_EXC_TEST    0x0100u
+#define PEAQ_FB_BAND_ADAPT_REF   0x0200u
+#define PEAQ_FB_BAND_ADAPT_TEST  0x0400u
+#define PEAQ_FB_BAND_MOD_REF     0x0800u
+#define PEAQ_FB_BAND_MOD_TEST    0x1000u
+
+int peaq_fb_band_count (void);           /* 40 */
+int peaq_fb_band_tables (double *fc /* [40] */, double *internal_noise /* [40] */);   /* host only */
+int peaq_batch_run_fb_bands (peaq_ctx *ctx, int channels, double playback_level_db, int n_pairs,
+                             const float *d_ref, const float *d_test, size_t pair_stride,
+                             const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                             uint32_t planes, double *d_bands /* device */, size_t block_stride,
+                             peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+/* (peaq_run_pair_fb_bands, the same for one pair from host memory: after peaq_run_pair_bands below) */
 
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
@@ -557,6 +617,15 @@ int peaq_run_pair_bands (peaq_ctx *ctx, int advanced, int channels, double playb
                          const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
                          double *bands /* host */, size_t frame_cap, uint32_t *n_frames,
                          peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_fb_bands (above) for one pair from HOST memory, rows into a host array
+ * [block_cap][channels][n_planes][40]: upload, conversion and alignment as in peaq_run_pair_bands.  n_blocks (may be
+ * NULL) receives the count of blocks written; a block_cap below it is PEAQ_ERR_ARG with both numbers in the message.
+ * out (may be NULL): the pair's result. */
+int peaq_run_pair_fb_bands (peaq_ctx *ctx, int channels, double playback_level_db,
+                            uint32_t rate, uint32_t max_lag,
+                            const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
+                            double *bands /* host */, size_t block_cap, uint32_t *n_blocks,
+                            peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
