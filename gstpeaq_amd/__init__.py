@@ -27,6 +27,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
                    batch_bands, run_pair_bands, band_tables, band_planes_mask, BAND_PLANES,
                    batch_fb_bands, run_pair_fb_bands, fb_band_tables, fb_band_planes_mask, FB_BAND_PLANES,
+                   batch_pattern_bands, run_pair_pattern_bands, pattern_band_tables, pattern_band_planes_mask,
+                   PATTERN_BAND_PLANES,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
 __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
@@ -38,6 +40,8 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "TRACE_ABOVE", "TRACE_MOD_OPEN", "TRACE_LOUD_OPEN", "TRACE_FLUSH",
            "batch_bands", "run_pair_bands", "band_tables", "band_planes_mask", "BAND_PLANES",
            "batch_fb_bands", "run_pair_fb_bands", "fb_band_tables", "fb_band_planes_mask", "FB_BAND_PLANES",
+           "batch_pattern_bands", "run_pair_pattern_bands", "pattern_band_tables", "pattern_band_planes_mask",
+           "PATTERN_BAND_PLANES",
            "Gain", "measure_gain", "cut_scaled", "gain_workspace_bytes", "gain_records", "gain_mode", "GAIN_DTYPE", "GAIN_MODES",
            "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
            "SubDelay", "refine_delay", "cut_shifted", "subsample_tables", "subdelay_workspace_bytes", "SUBDELAY_DTYPE", "SUB_STEPS",

@@ -154,6 +154,10 @@ BAND_PLANES = {"nmr": 1, "exc_ref": 2, "exc_test": 4, "detect": 8, "steps": 16}
 FB_BAND_PLANES = {"moddiff": 0x1, "modwt": 0x2, "noiseloud": 0x4, "missing": 0x8, "lindist": 0x10, "unsm_ref": 0x20,
                   "unsm_test": 0x40, "exc_ref": 0x80, "exc_test": 0x100, "adapt_ref": 0x200, "adapt_test": 0x400,
                   "mod_ref": 0x800, "mod_test": 0x1000}
+# PEAQ_PAT_BAND_* (include/peaq_amd.h) by name, in the order of their bits -- which is the order of the plane slots
+PATTERN_BAND_PLANES = {"moddiff1": 0x1, "moddiff2": 0x2, "modwt": 0x4, "noiseloud": 0x8, "unsm_ref": 0x10,
+                       "unsm_test": 0x20, "exc_ref": 0x40, "exc_test": 0x80, "adapt_ref": 0x100, "adapt_test": 0x200,
+                       "mod_ref": 0x400, "mod_test": 0x800, "avgloud_ref": 0x1000}
 
 
 class HostPair(C.Structure):
@@ -301,6 +305,12 @@ def load_library():
                                               C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.peaq_run_pair_fb_bands.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
                                              C.c_size_t, C.c_uint32, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_pattern_bands"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_pattern_band_tables.argtypes = [dp, dp]
+        L.peaq_batch_run_pattern_bands.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p,
+                                                   C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
+        L.peaq_run_pair_pattern_bands.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
+                                                  C.c_size_t, C.c_uint32, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_resample_supported.argtypes = [C.c_uint32]
         L.peaq_resampled_length.restype = C.c_uint32
@@ -2137,6 +2147,118 @@ def run_pair_fb_bands(ctx, ref, test, planes=("noiseloud",), playback_level=92.0
                                         out.ctypes.data_as(C.POINTER(C.c_double))))
     fc, noise = fb_band_tables()
     res = dict(_fb_band_planes_dict(rows[:nb.value], mask), result=_result_dict(out, True), fc=fc,
+               internal_noise=noise, planes=mask)
+    if align is not None:
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+    return res
+
+
+def pattern_band_planes_mask(planes):
+    """a PEAQ_PAT_BAND_* mask from plane names (PATTERN_BAND_PLANES; one name, or several in any order) or from a mask"""
+    if isinstance(planes, (int, np.integer)):
+        return int(planes)
+    if isinstance(planes, str):
+        planes = [planes]
+    unknown = [p for p in planes if p not in PATTERN_BAND_PLANES]
+    if unknown:
+        raise PeaqError(f"unknown pattern band plane {unknown[0]!r} (one of {', '.join(PATTERN_BAND_PLANES)})")
+    mask = 0
+    for p in planes:
+        mask |= PATTERN_BAND_PLANES[p]
+    return mask
+
+
+def pattern_band_tables():
+    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 109 bands of the basic
+    version's FFT path (peaq_pattern_band_tables; host only)"""
+    L = load_library()
+    n = L.peaq_band_count(0)
+    fc, noise = np.zeros(n), np.zeros(n)
+    dp = C.POINTER(C.c_double)
+    _check(L.peaq_pattern_band_tables(fc.ctypes.data_as(dp), noise.ctypes.data_as(dp)))
+    return fc, noise
+
+
+def _pattern_band_planes_dict(rows, mask, n_bands):
+    """rows [..., n_planes, 110] -> {name: [..., 109]} in the order of the slots, the pad column removed"""
+    names = [name for name, bit in PATTERN_BAND_PLANES.items() if mask & bit]
+    return {name: rows[..., k, :n_bands] for k, name in enumerate(names)}
+
+
+def batch_pattern_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_test=None, playback_level=92.0, rate=48000,
+                        align=None, stream=None, sync=True, d_bands=None):
+    """The pattern layer's values per frame, channel and band of every pair, in the run that scores them in the basic
+    version (peaq_batch_run_pattern_bands).  planes: names of PATTERN_BAND_PLANES (or a PEAQ_PAT_BAND_* mask); ref/test,
+    n_ref/n_test, rate and align as for batch_run.  d_bands: an optional CUDA float64 tensor [n_pairs, stride, channels,
+    n_planes, 110] to write into (rows past a pair's count keep what they held); without it a zero-filled one of the
+    longest pair's count is made.
+    Returns a dict: every requested plane by name, np.ndarray [pairs, frames_max, channels, 109] (the pad column
+    removed), counts (numpy, frames per pair), results (result dicts), fc and internal_noise (pattern_band_tables),
+    planes (the mask), and d_bands / d_results, the device tensors.  sync=False: the device tensors, counts, fc,
+    internal_noise and planes only."""
+    import torch
+    mask = pattern_band_planes_mask(planes)
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
+    cnt = {rt: frame_count(*rt) for rt in set(lens)}   # once per distinct pair of lengths
+    counts = np.array([cnt[rt] for rt in lens], dtype=np.uint32)
+    n_bands, row, n_planes = ctx.L.peaq_band_count(0), ctx.L.peaq_band_row(0), bin(mask & 0x1FFF).count("1")
+    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
+        if d_bands is None:
+            f_stride = max(int(counts.max()) if n_pairs else 0, 1)
+            d_bands = torch.zeros((n_pairs, f_stride, channels, max(n_planes, 1), row), dtype=torch.float64, device=ref.device)
+        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
+    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), row)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_run_pattern_bands(ctx.h, channels, float(playback_level), n_pairs,
+                                              C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                              a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                              a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                              mask, C.c_void_p(d_bands.data_ptr()), d_bands.shape[1],
+                                              C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    fc, noise = pattern_band_tables()
+    out = dict(d_bands=d_bands, d_results=results, counts=counts, fc=fc, internal_noise=noise, planes=mask)
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    out.update(_pattern_band_planes_dict(d_bands.cpu().numpy(), mask, n_bands))
+    out["results"] = [_result_dict(r, False) for r in results.cpu().numpy()]
+    return out
+
+
+def run_pair_pattern_bands(ctx, ref, test, planes=("noiseloud",), playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_pattern_bands: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`,
+    aligned first with align = a max_lag in 48 kHz samples.  Returns a dict: every requested plane by name, np.ndarray
+    [frames, channels, 109], result (a result dict), fc, internal_noise, planes (the mask) and, with align, delay."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    ch = ref.shape[1]
+    assert test.shape[1] == ch
+    mask = pattern_band_planes_mask(planes)
+    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
+    f_cap = max(frame_count(*lens), 1)
+    n_bands, row = ctx.L.peaq_band_count(0), ctx.L.peaq_band_row(0)
+    rows = np.zeros((f_cap, ch, max(bin(mask & 0x1FFF).count("1"), 1), row))
+    nf, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_pattern_bands(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
+                                             ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                             test.ctypes.data_as(C.POINTER(C.c_float)), len(test), mask,
+                                             C.c_void_p(rows.ctypes.data), f_cap, C.byref(nf), C.byref(rec),
+                                             out.ctypes.data_as(C.POINTER(C.c_double))))
+    fc, noise = pattern_band_tables()
+    res = dict(_pattern_band_planes_dict(rows[:nf.value], mask, n_bands), result=_result_dict(out, False), fc=fc,
                internal_noise=noise, planes=mask)
     if align is not None:
         res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)

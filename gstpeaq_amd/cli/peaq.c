@@ -576,6 +576,12 @@ usage (const char *prog)
       "                lindist, unsm_ref, unsm_test, exc_ref, exc_test, adapt_ref, adapt_test, mod_ref, mod_test\n"
       "                (default noiseloud).  The header line carries the bands' centre frequencies in Hz (the plain\n"
       "                one-call mode; with --device-resample, --align; a run of its own, like --bands)\n"
+      "  --pattern-bands=FILE[:PLANES] basic version: also write the pattern layer's values per frame, channel and\n"
+      "                critical band (109 bands) to FILE as CSV.  PLANES: a comma-separated list of moddiff1, moddiff2,\n"
+      "                modwt, noiseloud, unsm_ref, unsm_test, exc_ref, exc_test, adapt_ref, adapt_test, mod_ref, mod_test,\n"
+      "                avgloud_ref (default noiseloud).  The header line carries the bands' centre frequencies in Hz (the\n"
+      "                plain one-call mode; with --device-resample, --align; a run of its own, like --bands; with\n"
+      "                --advanced see --fb-bands)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -828,6 +834,96 @@ done:
   return rc;
 }
 
+/* the planes of --pattern-bands=FILE[:PLANES] by name, in the order of their bits (PEAQ_PAT_BAND_*) */
+enum { n_pattern_band_planes = 13 };
+static const char *const pattern_band_plane_names[n_pattern_band_planes] = { "moddiff1", "moddiff2", "modwt", "noiseloud",
+  "unsm_ref", "unsm_test", "exc_ref", "exc_test", "adapt_ref", "adapt_test", "mod_ref", "mod_test", "avgloud_ref" };
+
+/* a comma-separated list of plane names -> mask; 0 if a name is not one */
+static uint32_t
+parse_pattern_band_planes (const char *list)
+{
+  uint32_t mask = 0;
+  while (*list) {
+    const size_t n = strcspn (list, ",");
+    int k, hit = -1;
+    for (k = 0; k < n_pattern_band_planes; k++)
+      if (strlen (pattern_band_plane_names[k]) == n && !strncmp (list, pattern_band_plane_names[k], n))
+        hit = k;
+    if (hit < 0)
+      return 0;
+    mask |= 1u << hit;
+    list += n;
+    if (*list == ',' && !*++list)
+      return 0;
+  }
+  return mask;
+}
+
+/* --pattern-bands=FILE[:PLANES]: the pair through peaq_run_pair_pattern_bands, its rows as the CSV of --bands -- a
+ * header line (frame, channel, plane, then the bands' centre frequencies in Hz), then one line per (frame, channel,
+ * plane) with the band values; every value as %.17g, which reads back to the same double.  Prints the delay line of
+ * --align. */
+static int
+write_pattern_bands (const char *path, uint32_t planes, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
+    rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
+  const size_t frame_cap = (size_t) peaq_frame_count (n48[0], n48[1], 0) + 1;
+  const int count = peaq_band_count (0), row = peaq_band_row (0), ch = ref->channels;
+  int n_planes = 0, c, k, b, slot, rc = 1;
+  double *rows, *fc;
+  uint32_t nf = 0, f;
+  peaq_delay delay;
+  FILE *out;
+  for (k = 0; k < n_pattern_band_planes; k++)
+    n_planes += (planes >> k) & 1;
+  rows = malloc (frame_cap * ch * (n_planes ? n_planes : 1) * row * sizeof *rows);
+  fc = malloc (count * sizeof *fc);
+  if (!rows || !fc) {
+    printf ("Error: out of memory for the band trace\n");
+    goto done;
+  }
+  if (peaq_pattern_band_tables (fc, NULL) != PEAQ_OK ||
+      peaq_run_pair_pattern_bands (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
+          planes, rows, frame_cap, &nf, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag)
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+  if (!(out = fopen (path, "w"))) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  fprintf (out, "frame,channel,plane");
+  for (b = 0; b < count; b++)
+    fprintf (out, ",%.17g", fc[b]);
+  fprintf (out, "\n");
+  for (f = 0; f < nf; f++)
+    for (c = 0; c < ch; c++)
+      for (k = 0, slot = 0; k < n_pattern_band_planes; k++) {
+        const double *v;
+        if (!((planes >> k) & 1))
+          continue;
+        v = rows + (((size_t) f * ch + c) * n_planes + slot++) * row;
+        fprintf (out, "%u,%d,%s", f, c, pattern_band_plane_names[k]);
+        for (b = 0; b < count; b++)
+          fprintf (out, ",%.17g", v[b]);
+        fprintf (out, "\n");
+      }
+  if (fclose (out)) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  rc = 0;
+done:
+  free (rows);
+  free (fc);
+  return rc;
+}
+
 int
 main (int argc, char **argv)
 {
@@ -852,6 +948,8 @@ main (int argc, char **argv)
   uint32_t band_planes = PEAQ_BAND_NMR;
   char *fb_bands_path = NULL;   /* --fb-bands=FILE[:PLANES], peaq_run_pair_fb_bands */
   uint32_t fb_band_planes = PEAQ_FB_BAND_NOISELOUD;
+  char *pattern_bands_path = NULL;   /* --pattern-bands=FILE[:PLANES], peaq_run_pair_pattern_bands */
+  uint32_t pattern_band_planes = PEAQ_PAT_BAND_NOISELOUD;
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -1009,6 +1107,22 @@ main (int argc, char **argv)
         *colon = 0;
       }
     }
+    else if (!strcmp (argv[i], "--pattern-bands") || !strcmp (argv[i], "--pattern-bands=") || !strncmp (argv[i], "--pattern-bands=:", 17)) {
+      fprintf (stderr, "Failed to initialize: --pattern-bands needs a file name (--pattern-bands=FILE[:PLANES])\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--pattern-bands=", 16)) {
+      /* what follows the last colon is the plane list if every name in it is one; a file name otherwise */
+      char *colon = strrchr (argv[i] + 16, ':');
+      pattern_bands_path = argv[i] + 16;
+      if (colon && !colon[1]) {
+        fprintf (stderr, "Failed to initialize: --pattern-bands: no plane after the colon (moddiff1, moddiff2, modwt, noiseloud, unsm_ref, unsm_test, exc_ref, exc_test, adapt_ref, adapt_test, mod_ref, mod_test, avgloud_ref)\n");
+        return 1;
+      }
+      if (colon && parse_pattern_band_planes (colon + 1)) {
+        pattern_band_planes = parse_pattern_band_planes (colon + 1);
+        *colon = 0;
+      }
+    }
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -1047,6 +1161,18 @@ main (int argc, char **argv)
   }
   if (fb_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
     fprintf (stderr, "Failed to initialize: --fb-bands is a run of its own (not with --bands, --trace, --match-gain or an --align-... beyond --align)\n");
+    return 1;
+  }
+  if (pattern_bands_path && advanced) {
+    fprintf (stderr, "Failed to initialize: --pattern-bands covers the basic version only (with --advanced the pattern layer is the filter bank's: --fb-bands)\n");
+    return 1;
+  }
+  if (pattern_bands_path && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --pattern-bands belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (pattern_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --pattern-bands is a run of its own (not with --bands, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
@@ -1211,7 +1337,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (fb_bands_path) {
+    if (pattern_bands_path) {
+      if (write_pattern_bands (pattern_bands_path, pattern_band_planes, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (fb_bands_path) {
       if (write_fb_bands (fb_bands_path, fb_band_planes, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (bands_path) {

@@ -784,3 +784,34 @@ extern "C" int peaq_run_pair_fb_bands(peaq_ctx* c, int channels, double level_db
   if (n_blocks) *n_blocks = nb;
   return PEAQ_OK;
 }
+
+extern "C" int peaq_run_pair_pattern_bands(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                           const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                           uint32_t planes, double* bands, size_t frame_cap, uint32_t* n_frames,
+                                           peaq_delay* delay, peaq_result* out) {
+  const std::string w("peaq_run_pair_pattern_bands");
+  if (int rc = check_pattern_band_planes(w, planes)) return rc;
+  if (!bands) return fail(PEAQ_ERR_ARG, w + ": bands is NULL");
+  if (max_lag)
+    if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
+  ScoredPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
+    return rc;
+  const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
+  if (nf > frame_cap)
+    return fail(PEAQ_ERR_ARG, w + ": frame_cap " + std::to_string(frame_cap) + " is below the pair's " + std::to_string(nf) + " frames");
+  const size_t frame_bytes = (size_t)channels * __builtin_popcount(planes) * peaq_band_row(0) * sizeof(double);
+  DevBuf d_res, d_bn;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  HIP_TRY(d_bn.reserve(std::max<size_t>(nf, 1) * frame_bytes));
+  if (int rc = peaq_batch_run_pattern_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
+                                            planes, d_bn.as<double>(), nf, d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (nf) HIP_TRY(hipMemcpy(bands, d_bn.p, (size_t)nf * frame_bytes, hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  if (n_frames) *n_frames = nf;
+  return PEAQ_OK;
+}

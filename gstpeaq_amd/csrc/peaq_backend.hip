@@ -343,15 +343,18 @@ __device__ __forceinline__ double total_loudness_part(const BandLane<NB, SLOTS>&
 enum LeadMode { LEAD_OWN, LEAD_KEEP, LEAD_USE };
 // (the lane's part of the sum over the bands: callers with several sums in a frame take them through ONE reduction,
 // wave_sum2 / wave_sum4, and finish with noise_loudness_total)
-template <int NB, int SLOTS, class TAB, LeadMode LM = LEAD_OWN>
+// TERMS (pattern-bands instantiation only): every slot's term of that sum also goes to terms[s], 0 for a slot beyond the
+// last band -- the very value the sum adds, so a band below the hinge reads exactly 0.
+template <int NB, int SLOTS, class TAB, LeadMode LM = LEAD_OWN, bool TERMS = false>
 __device__ __forceinline__ double noise_loudness_part(const BandLane<NB, SLOTS>& bl, const TAB& bt,
                                                       double alpha, double thres_fac, double s0,
                                                       const double (&mod_ref)[SLOTS], const double (&mod_test)[SLOTS],
                                                       const double (&e_ref)[SLOTS], const double (&e_test)[SLOTS],
-                                                      double* lead = nullptr) {
+                                                      double* lead = nullptr, double* terms = nullptr) {
   double nl = 0.;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
+    if (TERMS) terms[s] = 0.;
     if (bl.valid(s)) {
       const double sref = thres_fac * mod_ref[s] + s0;
       const double stest = thres_fac * mod_test[s] + s0;
@@ -364,9 +367,17 @@ __device__ __forceinline__ double noise_loudness_part(const BandLane<NB, SLOTS>&
       else
         ld = bt.exp(0.23 * (bt.ln_internal_noise(bl.band(s)) - bt.log(stest)));
       if (LM == LEAD_KEEP) lead[s] = ld;
-      nl += ld *
-            (bt.pow(1. + div_fast(fmax(stest * e_test[s] - sref * e_ref[s], 0.), ethres + sref * e_ref[s] * beta), 0.23) -
-             1.);
+      if (!TERMS) {
+        nl += ld *
+              (bt.pow(1. + div_fast(fmax(stest * e_test[s] - sref * e_ref[s], 0.), ethres + sref * e_ref[s] * beta), 0.23) -
+               1.);
+      } else {                                       // the same product, named: the sum adds what the caller stores
+        const double t =
+            ld *
+            (bt.pow(1. + div_fast(fmax(stest * e_test[s] - sref * e_ref[s], 0.), ethres + sref * e_ref[s] * beta), 0.23) - 1.);
+        nl += t;
+        terms[s] = t;
+      }
     }
   }
   return nl;
@@ -378,18 +389,28 @@ __device__ __forceinline__ double noise_loudness_total(double sum, double nl_min
 }
 
 // movs.c:224-251: returns d1 (un-normalised), d2, weight
-template <int NB, int SLOTS, class TAB>
+// TERMS (pattern-bands instantiation only): every slot's terms of the three sums also go to terms[0..2][s], 0 for a slot
+// beyond the last band.
+template <int NB, int SLOTS, class TAB, bool TERMS = false>
 __device__ __forceinline__ void mod_difference(const BandLane<NB, SLOTS>& bl, const TAB& bt,
                                                double lev_wt, const double (&mr)[SLOTS], const double (&mt)[SLOTS],
-                                               const double (&loud_ref)[SLOTS], double& d1, double& d2, double& wt) {
+                                               const double (&loud_ref)[SLOTS], double& d1, double& d2, double& wt,
+                                               double (*terms)[SLOTS] = nullptr) {
   double a1 = 0., a2 = 0., aw = 0.;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
+    if (TERMS) terms[0][s] = terms[1][s] = terms[2][s] = 0.;
     if (bl.valid(s)) {
       const double diff = fabs(mr[s] - mt[s]);
-      a1 += div_fast(diff, 1. + mr[s]);
-      a2 += div_fast((mt[s] >= mr[s] ? 1. : .1) * diff, 0.01 + mr[s]);
-      aw += div_fast(loud_ref[s], loud_ref[s] + lev_wt * bt.noise_pow03(bl.band(s)));
+      if (!TERMS) {
+        a1 += div_fast(diff, 1. + mr[s]);
+        a2 += div_fast((mt[s] >= mr[s] ? 1. : .1) * diff, 0.01 + mr[s]);
+        aw += div_fast(loud_ref[s], loud_ref[s] + lev_wt * bt.noise_pow03(bl.band(s)));
+      } else {                                       // the same quotients, named: the sums add what the caller stores
+        a1 += terms[0][s] = div_fast(diff, 1. + mr[s]);
+        a2 += terms[1][s] = div_fast((mt[s] >= mr[s] ? 1. : .1) * diff, 0.01 + mr[s]);
+        aw += terms[2][s] = div_fast(loud_ref[s], loud_ref[s] + lev_wt * bt.noise_pow03(bl.band(s)));
+      }
     }
   }
   double unused;
@@ -453,8 +474,9 @@ struct PointWalk {
 // The plane test is on a kernel argument, so wave-uniform; the row's pad entry (band NB of NB + 1) belongs to the lane
 // that owns band NB - 1, whose v1 the caller hands over as 0, and the lanes beyond it store nothing.
 // ---------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void band_store(const BandArgs& bnd, uint32_t bit, size_t cell, int lane, double v0, double v1) {
+// (ARGS: BandArgs, or PatternBandArgs of peaq_batch_run_pattern_bands -- the same rows and slots)
+template <int NB, class ARGS>
+__device__ __forceinline__ void band_store(const ARGS& bnd, uint32_t bit, size_t cell, int lane, double v0, double v1) {
   if (!(bnd.planes & bit)) return;
   const unsigned n_planes = __builtin_popcount(bnd.planes), slot = __builtin_popcount(bnd.planes & (bit - 1u));
   // (a uniform row address and the lane's 32-bit byte offset: the store takes them as they are, no 64-bit lane address)
@@ -503,47 +525,67 @@ struct BackendShared {
 // one lane per (frame, channel) writes them as a compact record (TraceArgs) -- no pattern dump.
 // BND = true (backend_bands_kernel, band-trace launches only): every lane stores the per-band values of its two bands
 // where they come up (BandArgs, band_store); the arithmetic and the gates are the plain instantiation's.
+// PBD = true (backend_pattern_bands_kernel, pattern-band launches of the basic version only): the modulation differences
+// and the noise loudness are evaluated for every frame, as with TRC, and every lane stores its two bands' terms and
+// patterns where they come up (PatternBandArgs, band_store); the accumulators see what the gates admit.
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false;
+  constexpr bool PTS = false, TRC = false, BND = false, PBD = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
+  constexpr PatternBandArgs pbd{};
 #include "peaq_backend_fft.inc"
 }
 // The points instantiation is a kernel of its own name with the same body (not a fourth template parameter of
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false;
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
+  constexpr PatternBandArgs pbd{};
 #include "peaq_backend_fft.inc"
 }
 // the trace instantiation: a third kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false;
   constexpr PointArgs pts{};
   constexpr BandArgs bnd{};
+  constexpr PatternBandArgs pbd{};
 #include "peaq_backend_fft.inc"
 }
 // the bands instantiation: a fourth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
+  constexpr PatternBandArgs pbd{};
+#include "peaq_backend_fft.inc"
+}
+// the pattern-bands instantiation (basic version only): a fifth kernel of its own name with the same body
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendArgs a, PatternBandArgs pbd) {
+  static_assert(!ADV, "the 55-band path has no pattern layer");
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true;
+  constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
+  constexpr BandArgs bnd{};
 #include "peaq_backend_fft.inc"
 }
 
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                          const TraceArgs* trc, const BandArgs* bnd) {
+                          const TraceArgs* trc, const BandArgs* bnd, const PatternBandArgs* pbd) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
   if (bnd && (pts || trc || a.debug || a.pair_frame0)) return hipErrorInvalidValue;   // a run's own launches only
-  if (bnd && !a.advanced)
+  if (pbd && (bnd || pts || trc || a.debug || a.pair_frame0 || a.advanced)) return hipErrorInvalidValue;
+  if (pbd)
+    hipLaunchKernelGGL((backend_pattern_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pbd);
+  else if (bnd && !a.advanced)
     hipLaunchKernelGGL((backend_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *bnd);
   else if (bnd)
     hipLaunchKernelGGL((backend_bands_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *bnd);

@@ -1,6 +1,7 @@
 // peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = BND =
-// false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true) and
-// backend_bands_kernel<NB, ADV> (BND = true) in peaq_backend.hip: one text, four kernels of their own names.
+// PBD = false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true),
+// backend_bands_kernel<NB, ADV> (BND = true) and backend_pattern_bands_kernel<NB, false> (PBD = true) in
+// peaq_backend.hip: one text, five kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -123,6 +124,16 @@
       excitation_from_root(v1.y, n1, m1, ut[1], lt[1]);
       nz[0] = v4.x; nz[1] = v4.y;
     }
+    // (pattern-bands instantiation: the noise pattern is read again where the ratio needs it, below -- the four
+    // registers it would sit in through the pattern layer are what the term stores need)
+    if (PBD) nz[0] = nz[1] = 0.;
+    // (pattern-bands instantiation only) the row cell of this (pair, frame, channel); the unsmeared excitations go out
+    // here, every other plane where it comes up
+    const size_t pbd_cell = PBD ? ((size_t)pair * pbd.frame_stride + frame) * channels + chan : 0;
+    if (PBD) {
+      band_store<NB>(pbd, kPatBandUnsmRef, pbd_cell, lane, ur[0], bl.valid(1) ? ur[1] : 0.);
+      band_store<NB>(pbd, kPatBandUnsmTest, pbd_cell, lane, ut[0], bl.valid(1) ? ut[1] : 0.);
+    }
     double nl_part = 0.;                               // basic version: the lane's part of the noise loudness, summed with the NMR's
     bool nl_open = false;
     // time smearing, fftearmodel.c:496-504
@@ -147,6 +158,10 @@
       band_store<NB>(bnd, kBandExcRef, bnd_cell, lane, er[0], bl.valid(1) ? er[1] : 0.);
       if (!ADV) band_store<NB>(bnd, kBandExcTest, bnd_cell, lane, et[0], bl.valid(1) ? et[1] : 0.);
     }
+    if (PBD) {
+      band_store<NB>(pbd, kPatBandExcRef, pbd_cell, lane, er[0], bl.valid(1) ? er[1] : 0.);
+      band_store<NB>(pbd, kPatBandExcTest, pbd_cell, lane, et[0], bl.valid(1) ? et[1] : 0.);
+    }
 
     // lane i owns accumulator i: every MOV value of the frame is routed to its owner as soon as
     // it exists (two selects) instead of being kept in a per-lane table
@@ -166,6 +181,13 @@
       level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
       modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
       modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+      if (PBD) {                                     // (the helpers leave 0 in the slot beyond the last band)
+        band_store<NB>(pbd, kPatBandAdaptRef, pbd_cell, lane, ad_ref[0], ad_ref[1]);
+        band_store<NB>(pbd, kPatBandAdaptTest, pbd_cell, lane, ad_test[0], ad_test[1]);
+        band_store<NB>(pbd, kPatBandModRef, pbd_cell, lane, mr[0], mr[1]);
+        band_store<NB>(pbd, kPatBandModTest, pbd_cell, lane, mt[0], mt[1]);
+        band_store<NB>(pbd, kPatBandAvgLoudRef, pbd_cell, lane, mdr[1][0], bl.valid(1) ? mdr[1][1] : 0.);
+      }
       if (DBG) {
         double* __restrict__ d =
             a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles;
@@ -240,9 +262,17 @@
           DBG ? a.debug + ((size_t)(pair * a.frames_per_launch + (frame - f_begin)) * channels + chan) * kDbgDoubles + kDbgMov
               : nullptr;
       // ---- modulation difference (gstpeaq.c:871-877) --------------------------------
-      if (DBG || TRC || frame >= 24) {
+      if (DBG || TRC || PBD || frame >= 24) {
         double d1, d2, wt;
-        mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
+        if (PBD) {                                   // the terms the three sums add, per slot
+          double md_t[3][SLOTS];
+          mod_difference<NB, SLOTS, LdsTabs, true>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt, md_t);
+          band_store<NB>(pbd, kPatBandModDiff1, pbd_cell, lane, md_t[0][0], md_t[0][1]);
+          band_store<NB>(pbd, kPatBandModDiff2, pbd_cell, lane, md_t[1][0], md_t[1][1]);
+          band_store<NB>(pbd, kPatBandModWt, pbd_cell, lane, md_t[2][0], md_t[2][1]);
+        } else {
+          mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
+        }
         d1 *= 100. / NB;
         d2 *= 100. / NB;
         if (frame >= 24) {
@@ -263,8 +293,15 @@
       }
       // ---- noise loudness (gstpeaq.c:880-886; unsigned compare with UINT_MAX sentinel)
       // (its sum over the bands goes through the reduction of the noise-to-mask ratio below)
-      nl_open = DBG || TRC || (frame >= 24 && frame - 3 >= loud_reached);
-      if (nl_open) nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
+      nl_open = DBG || TRC || PBD || (frame >= 24 && frame - 3 >= loud_reached);
+      if (PBD) {                                     // the terms the sum adds, per slot
+        double nl_t[SLOTS];
+        nl_part = noise_loudness_part<NB, SLOTS, LdsTabs, LEAD_OWN, true>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test,
+                                                                          nullptr, nl_t);
+        band_store<NB>(pbd, kPatBandNoiseLoud, pbd_cell, lane, nl_t[0], nl_t[1]);
+      } else if (nl_open) {
+        nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
+      }
       // ---- bandwidth (movs.c:797-807) ------------------------------------------------------
       {
         const double bw_ref = rec[kRecBwRef];
@@ -279,6 +316,11 @@
     {
       double nsum = 0., nmax = 0.;
       double bnd_r[SLOTS] = {0., 0.};                  // (bands instantiation only: dead otherwise)
+      if (PBD) {
+        const int b0 = bl.band(0);
+        const double2 v4 = *reinterpret_cast<const double2*>(rec + kRecNoise + (b0 < kBandStride ? b0 : 0));
+        nz[0] = v4.x; nz[1] = v4.y;
+      }
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
         if (bl.valid(s)) {

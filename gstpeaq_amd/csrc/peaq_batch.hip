@@ -216,24 +216,42 @@ static_assert(PEAQ_FB_BAND_MODDIFF == kFbBandModDiff && PEAQ_FB_BAND_MODWT == kF
                   PEAQ_FB_BAND_MOD_TEST == kFbBandModTest,
               "the filter-bank planes of include/peaq_amd.h and peaq_kernels.h");
 
+// Rows of a pattern-band trace (peaq_batch_run_pattern_bands, basic version): nullptr for a plain batch.  Never together
+// with any of the four above; the FFT back end writes the caller's rows directly.
+struct PatternBandOut {
+  double* d_bands;              // [n_pairs][frame_stride][channels][n_planes][110]
+  size_t frame_stride;
+  uint32_t planes;
+};
+static_assert(PEAQ_PAT_BAND_MODDIFF1 == kPatBandModDiff1 && PEAQ_PAT_BAND_MODDIFF2 == kPatBandModDiff2 &&
+                  PEAQ_PAT_BAND_MODWT == kPatBandModWt && PEAQ_PAT_BAND_NOISELOUD == kPatBandNoiseLoud &&
+                  PEAQ_PAT_BAND_UNSM_REF == kPatBandUnsmRef && PEAQ_PAT_BAND_UNSM_TEST == kPatBandUnsmTest &&
+                  PEAQ_PAT_BAND_EXC_REF == kPatBandExcRef && PEAQ_PAT_BAND_EXC_TEST == kPatBandExcTest &&
+                  PEAQ_PAT_BAND_ADAPT_REF == kPatBandAdaptRef && PEAQ_PAT_BAND_ADAPT_TEST == kPatBandAdaptTest &&
+                  PEAQ_PAT_BAND_MOD_REF == kPatBandModRef && PEAQ_PAT_BAND_MOD_TEST == kPatBandModTest &&
+                  PEAQ_PAT_BAND_AVGLOUD_REF == kPatBandAvgLoudRef,
+              "the pattern-band planes of include/peaq_amd.h and peaq_kernels.h");
+
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo);
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
+                            const PatternBandOut* po);
 
-// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands and peaq_batch_run_fb_bands: one
-// driver, the points, the trace records and the band rows optional (`who` names the entry in messages)
+// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands and
+// peaq_batch_run_pattern_bands: one driver, the points, the trace records and the band rows optional (`who` names the
+// entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
                            const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr,
-                           const FbBandOut* fo = nullptr) {
+                           const FbBandOut* fo = nullptr, const PatternBandOut* po = nullptr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo && !po)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -246,7 +264,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo);
+                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo, po);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -432,6 +450,57 @@ extern "C" int peaq_batch_run_fb_bands(peaq_ctx* c, int channels, double level_d
                          n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, &fo);
 }
 
+// ---- band traces of the pattern layer (basic version) ----------------------------------------------------------
+// what build_fft_band_tables builds for the 109 bands (host only: no context, no device)
+extern "C" int peaq_pattern_band_tables(double* fc, double* internal_noise) {
+  if (!fc && !internal_noise) return fail(PEAQ_ERR_ARG, "peaq_pattern_band_tables: NULL argument");
+  static const std::unique_ptr<BandTables> tabs = [] {     // once per process, on the first call
+    auto t = std::make_unique<BandTables>();
+    build_fft_band_tables(109, *t);
+    return t;
+  }();
+  for (int b = 0; b < tabs->bands; ++b) {
+    if (fc) fc[b] = tabs->fc[b];
+    if (internal_noise) internal_noise[b] = tabs->internal_noise[b];
+  }
+  return PEAQ_OK;
+}
+
+// `planes` as the pattern-band entries take it; 0 or an error with the value in the message
+int check_pattern_band_planes(const std::string& w, uint32_t planes) {
+  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
+  if (planes & ~kPatBandAll)
+    return fail(PEAQ_ERR_ARG,
+                w + ": planes " + std::to_string(planes) + " has a bit above 4096 (PEAQ_PAT_BAND_AVGLOUD_REF)");
+  return PEAQ_OK;
+}
+
+// The band trace's own arguments first, as peaq_batch_run_bands': they need no context and no device.
+extern "C" int peaq_batch_run_pattern_bands(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
+                                            const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                            const uint32_t* n_test, uint32_t n_uniform, uint32_t planes,
+                                            double* d_bands, size_t frame_stride, peaq_result* d_results,
+                                            void* stream_) {
+  const std::string w("peaq_batch_run_pattern_bands");
+  if (int rc = check_pattern_band_planes(w, planes)) return rc;
+  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
+  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
+  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
+    uint32_t max_frames = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
+      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
+      if (!n_ref) break;
+    }
+    if (frame_stride < max_frames)
+      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
+                                    std::to_string(max_frames) + " frames");
+  }
+  const PatternBandOut po{d_bands, frame_stride, planes};
+  return batch_run_entry("peaq_batch_run_pattern_bands", c, 0, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
+                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, nullptr, &po);
+}
+
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
   if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
   if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
@@ -501,7 +570,8 @@ extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels,
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo) {
+                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
+                            const PatternBandOut* po) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -581,6 +651,14 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     fba.planes = fo->planes;
   }
   const FbBandArgs* fbnd = fo ? &fba : nullptr;
+  // pattern-band trace (basic version): every back-end launch of the run is the pattern-bands instantiation
+  PatternBandArgs pba{};
+  if (po) {
+    pba.bands = po->d_bands;
+    pba.frame_stride = po->frame_stride;
+    pba.planes = po->planes;
+  }
+  const PatternBandArgs* pbd = po ? &pba : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
@@ -675,7 +753,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd, pbd));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;

@@ -217,6 +217,7 @@ int check_max_lag(const std::string& who, uint32_t max_lag);
 // planes of a band trace, PEAQ_BAND_* bits the version has (peaq_batch.hip)
 int check_band_planes(const std::string& who, int advanced, uint32_t planes);
 int check_fb_band_planes(const std::string& who, uint32_t planes);
+int check_pattern_band_planes(const std::string& who, uint32_t planes);
 
 // ---------------------------------------------------------------------------
 // Per-pair host arrays of one call (lengths, skips): staged in pinned host memory and copied on the caller's stream,

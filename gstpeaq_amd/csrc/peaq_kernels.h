@@ -100,6 +100,20 @@ struct BandArgs {
   uint32_t planes;              // kBand* bits; the slot of a plane is the rank of its bit among the set ones
 };
 
+// ---- per-band traces of the pattern layer (peaq_batch_run_pattern_bands, basic version) --------
+// The per-band terms of the modulation differences, their weight and the noise loudness, and the patterns they are made
+// of, stored where they come up.  The bits mirror PEAQ_PAT_BAND_* in include/peaq_amd.h (peaq_batch.hip asserts them).
+// A kernel argument of the pattern-bands instantiation only; rows and slots as BandArgs'.
+constexpr uint32_t kPatBandModDiff1 = 0x1u, kPatBandModDiff2 = 0x2u, kPatBandModWt = 0x4u, kPatBandNoiseLoud = 0x8u,
+                   kPatBandUnsmRef = 0x10u, kPatBandUnsmTest = 0x20u, kPatBandExcRef = 0x40u, kPatBandExcTest = 0x80u,
+                   kPatBandAdaptRef = 0x100u, kPatBandAdaptTest = 0x200u, kPatBandModRef = 0x400u,
+                   kPatBandModTest = 0x800u, kPatBandAvgLoudRef = 0x1000u, kPatBandAll = 0x1FFFu;
+struct PatternBandArgs {
+  double* bands;                // [pair][frame_stride][channel][plane slot][band_row (109)], 16-byte aligned
+  size_t frame_stride;
+  uint32_t planes;              // kPatBand* bits; the slot of a plane is the rank of its bit among the set ones
+};
+
 // ---- pattern back end (time smearing .. MOV accumulation) -------------------
 struct BackendArgs {
   const double* records;        // as written by the front end
@@ -124,8 +138,11 @@ struct BackendArgs {
 // pts != nullptr (trajectory launches only): the points instantiation, snapshots after frames (PointArgs)
 // trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per frame (TraceArgs)
 // bnd != nullptr (band-trace launches only, never with pts or trc): the bands instantiation, rows per frame (BandArgs)
+// pbd != nullptr (pattern-band launches of the basic version only, never with any of the three): the pattern-bands
+// instantiation, rows per frame (PatternBandArgs)
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
-                          const TraceArgs* trc = nullptr, const BandArgs* bnd = nullptr);
+                          const TraceArgs* trc = nullptr, const BandArgs* bnd = nullptr,
+                          const PatternBandArgs* pbd = nullptr);
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h

@@ -439,6 +439,65 @@ int peaq_batch_run_fb_bands (peaq_ctx *ctx, int channels, double playback_level_
                              peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
 /* (peaq_run_pair_fb_bands, the same for one pair from host memory: after peaq_run_pair_bands below) */
 
+/* ---- band traces of the pattern layer: the basic version's modulation and noise-loudness terms per BAND ----------
+ * Most of the basic version's ODG is made of pattern-layer MOVs (WinModDiff1, AvgModDiff1, AvgModDiff2, RmsNoiseLoud);
+ * the frame trace gives their four values per frame and channel, peaq_batch_run_pattern_bands the 109 per-band terms
+ * those are summed from and the patterns they are made of -- in the same run that scores the batch.  There is no
+ * `advanced` argument: the 55-band FFT path of the advanced version computes neither (its pattern MOVs come from the
+ * filter bank, peaq_batch_run_fb_bands above).  `planes` selects (FP64, before accumulation, for every frame of the
+ * pair, the flush frame included, whatever the gates of gstpeaq.c:871 / :880-881 let the accumulators see -- the frame
+ * trace's convention).  With n the band's internal noise, ur / ut the unsmeared excitations, er / et the excitations
+ * after time smearing (fftearmodel.c:496-504), ar / at the level- and pattern-adapted patterns (leveladapter.c:331-336),
+ * mr / mt the modulations (modpatt.c:245-247) and lr the reference's average loudness (modpatt.c:240-243):
+ *     PEAQ_PAT_BAND_MODDIFF1    |mr - mt| / (1 + mr)                                   (movs.c:224-251)
+ *     PEAQ_PAT_BAND_MODDIFF2    w |mr - mt| / (0.01 + mr), w = 1 where mt >= mr, else 0.1
+ *     PEAQ_PAT_BAND_MODWT       lr / (lr + 100 n^0.3)
+ *     PEAQ_PAT_BAND_NOISELOUD   (n / stest)^0.23 ((1 + max (stest at - sref ar, 0) / (n + sref ar beta))^0.23 - 1),
+ *                               sref = 0.15 mr + 0.5, stest = 0.15 mt + 0.5, beta = exp (-1.5 (at - ar) / ar)
+ *                               (movs.c:709-743 as gstpeaq.c:880-886 calls it); exactly 0 where stest at < sref ar
+ *     PEAQ_PAT_BAND_UNSM_REF / _UNSM_TEST / _EXC_REF / _EXC_TEST / _ADAPT_REF / _ADAPT_TEST / _MOD_REF / _MOD_TEST /
+ *     _AVGLOUD_REF              ur, ut, er, et, ar, at, mr, mt, lr; EXC_REF and EXC_TEST are bit for bit the planes of
+ *                               the same name of peaq_batch_run_bands
+ *   With the frame record of the same pair (peaq_frame_trace, basic version; sums over the 109 bands):
+ *     ch[c][0] = 100 / 109 sum MODDIFF1           ch[c][1] = 100 / 109 sum MODDIFF2
+ *     ch[c][2] = sum MODWT                        ch[c][3] = 24 / 109 sum NOISELOUD
+ *   None of the six switches of peaq_settings touches these planes in the basic version
+ *   (swap_mod_patts_for_noise_loudness_movs acts in the filter-bank path only).
+ *
+ * Layout: that of peaq_batch_run_bands for the basic version.  The value of plane slot k -- the rank of the plane's bit
+ * among the set bits of `planes` -- sits at
+ *   d_bands[((((p * frame_stride + f) * channels + c) * n_planes + k) * 110) + b],  b < 109;
+ * the row's last entry (b = 109) is written 0.  Pair p has peaq_frame_count (n_ref[p], n_test[p], 0) frames; rows past
+ * a pair's count are left untouched.  peaq_pattern_band_tables (host only, no device) gives the bands' centre
+ * frequencies in Hz and their internal noise; either pointer may be NULL, not both.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs in the basic version; the
+ * context's settings apply as they do there.  PEAQ_ERR_ARG, before a context or a device is touched and with a message
+ * that names the value: planes zero or with a bit above 0x1000, d_bands NULL or not 16-byte aligned (the rows go out as
+ * 16-byte stores), a frame_stride below the longest pair's count, and everything peaq_batch_run refuses.  A run of its
+ * own, like the other band traces, the trace and the trajectory. */
+#define PEAQ_PAT_BAND_MODDIFF1     0x0001u
+#define PEAQ_PAT_BAND_MODDIFF2     0x0002u
+#define PEAQ_PAT_BAND_MODWT        0x0004u
+#define PEAQ_PAT_BAND_NOISELOUD    0x0008u
+#define PEAQ_PAT_BAND_UNSM_REF     0x0010u
+#define PEAQ_PAT_BAND_UNSM_TEST    0x0020u
+#define PEAQ_PAT_BAND_EXC_REF      0x0040u
+#define PEAQ_PAT_BAND_EXC_TEST     0x0080u
+#define PEAQ_PAT_BAND_ADAPT_REF    0x0100u
+#define PEAQ_PAT_BAND_ADAPT_TEST   0x0200u
+#define PEAQ_PAT_BAND_MOD_REF      0x0400u
+#define PEAQ_PAT_BAND_MOD_TEST     0x0800u
+#define PEAQ_PAT_BAND_AVGLOUD_REF  0x1000u
+
+int peaq_pattern_band_tables (double *fc /* [109] */, double *internal_noise /* [109] */);   /* host only */
+int peaq_batch_run_pattern_bands (peaq_ctx *ctx, int channels, double playback_level_db, int n_pairs,
+                                  const float *d_ref, const float *d_test, size_t pair_stride,
+                                  const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                                  uint32_t planes, double *d_bands /* device */, size_t frame_stride,
+                                  peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+/* (peaq_run_pair_pattern_bands, the same for one pair from host memory: after peaq_run_pair_fb_bands below) */
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -626,6 +685,15 @@ int peaq_run_pair_fb_bands (peaq_ctx *ctx, int channels, double playback_level_d
                             const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
                             double *bands /* host */, size_t block_cap, uint32_t *n_blocks,
                             peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_pattern_bands (above) for one pair from HOST memory, rows into a host array
+ * [frame_cap][channels][n_planes][110]: upload, conversion, alignment and counts as in peaq_run_pair_bands.  n_frames
+ * (may be NULL) receives the count of frames written; a frame_cap below it is PEAQ_ERR_ARG with both numbers in the
+ * message.  out (may be NULL): the pair's result. */
+int peaq_run_pair_pattern_bands (peaq_ctx *ctx, int channels, double playback_level_db,
+                                 uint32_t rate, uint32_t max_lag,
+                                 const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
+                                 double *bands /* host */, size_t frame_cap, uint32_t *n_frames,
+                                 peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
