@@ -39,6 +39,7 @@
 
 #include "peaq_device.h"
 #include "peaq_kernels.h"
+#include "peaq_spread_sched.h"
 #include <type_traits>
 
 #include "peaq_wave.h"
@@ -84,6 +85,16 @@ __device__ __forceinline__ cplx tw_lane(const CommonTables* __restrict__ ct, int
   return {v.x, v.y};
 }
 __device__ __forceinline__ cplx csqr(cplx a) { return {a.re * a.re - a.im * a.im, 2. * (a.re * a.im)}; }
+// x^e by squaring, for an e >= 1 that is a constant where this is inlined
+__device__ __forceinline__ double pow_const(double x, int e) {
+  double pw = 1., sq = x;
+#pragma unroll
+  for (; e; e >>= 1) {
+    if (e & 1) pw *= sq;
+    if (e >> 1) sq *= sq;
+  }
+  return pw;
+}
 
 // dft8 (peaq_wave.h) for inputs whose upper half is purely imaginary: x[4..7].re are taken as zero and never read.
 // Same values as dft8 on {0, x[4 + n].im}, bar the sign of a zero (x.re + 0 turns -0 into +0, this does not).
@@ -727,8 +738,29 @@ void frontend_kernel(FrontendArgs a) {
     // and sums for bands that do not exist leave at the top.  Walking k DOWN means walking each source's sequence
     // from its far end: u = Ene[2L] a^(2k), v = Ene[2L+1] a'^(2k-1) start at k = kLanes from one exponential each
     // and go back two bands per step with 1 / a^2; what a lane adds per step is (u + v, a u + a' v).
-    constexpr int kLanes = (NB - 1) / 2;               // the farthest lane a band reaches: band 0 -> band NB - 1
-    double ene[2], ae[2], far[2], back2[2];            // far: the source's term 2 kLanes (2 kLanes - 1) bands up; back2 = a^-2
+    //
+    // Two streams (peaq_spread_sched.h): at distance K only the sources L <= kLanes - K have a target, so the far
+    // distances K0 + 1 .. kLanes run in the lanes 32 + L, on a copy of source L (v_permlane32_swap), WHILE the lanes
+    // below 32 run the main stream's first steps k = K0 .. kBoundary: the same instructions, kHelper = kLanes - K0 lanes
+    // of distance apart -- K0 = 39 steps instead of 54 at 109 bands, 14 instead of 27 at 55.  While both run, a lane adds
+    // only from its step `act` on, so that no sum of a band that does not exist walks into the helper's lanes; behind
+    // the boundary step the helper's finished sums go home through LDS (fetched behind the loop), its lanes are
+    // cleared, and the lanes >= 32 carry on with their own source at distance kBoundary - 1 -- their first with a target.
+    // -DPEAQ_FE_SPREAD_ONE_STREAM (VARIANT builds): the single stream k = kLanes .. 1 in every lane, as it was.
+    constexpr int kLanes = spread_lanes(NB);           // the farthest lane a band reaches: band 0 -> band NB - 1
+#ifdef PEAQ_FE_SPREAD_ONE_STREAM
+    constexpr int kHelper = 0, kFirst = kLanes, kBoundary = kLanes + 1;
+    constexpr int kExpUpper = 2 * kLanes, kExpHelper = 0;
+    constexpr int kUnrollMain = 9;
+#else
+    constexpr int kUnrollMain = 8;
+    constexpr int kHelper = spread_helper_steps(NB), kFirst = spread_k0(NB), kBoundary = spread_boundary(NB);
+    constexpr int kExpUpper = spread_exp_upper(NB, 0), kExpHelper = spread_exp_helper(NB);
+#endif
+    // far: the source's term at the first distance of its stream (main: 2 kFirst (- 1) bands up; the copies' start is
+    // kExpHelper / 2 lanes farther); upper: the same at distance kBoundary - 1; back2 = a^-2
+    double ene[2], ae[2], far[2], back2[2];
+    [[maybe_unused]] double far_copy[2], upper[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int b = b0 + s;
@@ -744,14 +776,15 @@ void frontend_kernel(FrontendArgs a) {
         const double g_iu = div_fast(1. - exp_fast((double)(NB - b) * ln_a), 1. - a_uce);
         ae[s] = t2;
         ene[s] = exp_fast(0.4 * (ln_pp - FE_LOG(c_gil[s] + g_iu - 1., ltab)));
-        {                                              // a^(0.4 (2 kLanes - s)) = t2^(2 kLanes - s), by squaring: the exponent
-          double pw = 1., sq = t2;                   // is a compile-time constant (ten multiplications for an exponential)
-#pragma unroll
-          for (int e = 2 * kLanes - s; e; e >>= 1) {
-            if (e & 1) pw *= sq;
-            if (e >> 1) sq *= sq;
-          }
-          far[s] = ene[s] * pw;
+        // a^(0.4 e) = t2^e by squaring: the exponents are compile-time constants (about ten multiplications for an
+        // exponential), and the squares are shared between the start terms
+        upper[s] = ene[s] * pow_const(t2, kExpUpper - s);
+        if constexpr (kHelper > 0) {
+          const double ph = pow_const(t2, kExpHelper);
+          far[s] = upper[s] * ph;
+          far_copy[s] = far[s] * ph;
+        } else {
+          far[s] = upper[s];
         }
         // (a^-0.8; 0 where a^0.8 underflows -- never with finite samples, the internal noise bounds Pp from below -- so
         // that such a source sends nothing instead of 0 x inf: the walk's rounding, ~ kLanes ulp on the near terms and
@@ -762,6 +795,8 @@ void frontend_kernel(FrontendArgs a) {
         ae[s] = 0.;
         ene[s] = 0.;
         far[s] = 0.;
+        far_copy[s] = 0.;
+        upper[s] = 0.;
         back2[s] = 0.;
       }
     }
@@ -769,8 +804,42 @@ void frontend_kernel(FrontendArgs a) {
     double up0 = 0., up1 = 0.;                         // E2up of the bands 2 (lane + k), 2 (lane + k) + 1 while in flight
     {
       double u = far[0], v = far[1];
-#pragma unroll 9
-      for (int k = kLanes; k >= 1; --k) {
+      [[maybe_unused]] double2 home = make_double2(0., 0.);
+      if constexpr (kHelper > 0) {
+        // lanes >= 32: source lane - 32 at the helper's first distance
+        u = lower_halves(far[0], far_copy[0]);
+        v = lower_halves(far[1], far_copy[1]);
+        const double wa0 = lower_halves(ae[0], ae[0]), wa1 = lower_halves(ae[1], ae[1]);
+        const double wb0 = lower_halves(back2[0], back2[0]), wb1 = lower_halves(back2[1], back2[1]);
+        const int act = lane < kSpreadHelperBase ? kLanes - lane : kFirst - (lane - kSpreadHelperBase);   // spread_act
+#pragma unroll 5
+        for (int k = kFirst; k >= kBoundary; --k) {
+          if (k <= act) {
+            asm volatile("");                          // keeps this an EXEC mask: as four selects a step it gains 0.4 % instead of 2 % (profiles/r08_ab_basic.txt)
+            up0 += u;
+            up0 += v;
+            up1 = fma(wa0, u, up1);
+            up1 = fma(wa1, v, up1);
+          }
+          up0 = lane_below(up0);
+          up1 = lane_below(up1);
+          u *= wb0;
+          v *= wb1;
+        }
+        // the helper's sums stand spread_home_shift lanes below home; every lane writes (zeros outside the helper's), so
+        // that every lane may read: the band sums' exchange space is free (ppx was read for the last time above)
+        const bool lower = lane < kSpreadHelperBase;
+        double2* hx = reinterpret_cast<double2*>(ppx);
+        hx[(lane + spread_home_shift(NB) + kSpreadWave) & (kSpreadWave - 1)] = lower ? make_double2(0., 0.) : make_double2(up0, up1);
+        wave_lds_fence();
+        home = hx[lane];
+        up0 = lower ? up0 : 0.;
+        up1 = lower ? up1 : 0.;
+        u = lower ? u : upper[0];
+        v = lower ? v : upper[1];
+      }
+#pragma unroll kUnrollMain
+      for (int k = kBoundary - 1; k >= 1; --k) {
         up0 += u;
         up0 += v;
         up1 = fma(ae[0], u, up1);
@@ -779,6 +848,10 @@ void frontend_kernel(FrontendArgs a) {
         up1 = lane_below(up1);
         u *= back2[0];
         v *= back2[1];
+      }
+      if constexpr (kHelper > 0) {
+        up0 += home.x;
+        up1 += home.y;
       }
       up1 = fma(ae[0], ene[0], up1);                   // band 2 lane to its own neighbour 2 lane + 1
     }

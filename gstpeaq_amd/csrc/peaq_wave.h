@@ -293,6 +293,13 @@ __device__ __forceinline__ double fuse_halves_sum(double a, double b) {
   const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
   return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
+// ... and the half it keeps alone: lanes 0 .. 31 get a, lanes 32 .. 63 what b holds 32 lanes below them (a == b: the
+// lower half copied into the upper).  Two VALU instructions per double, no LDS.
+__device__ __forceinline__ double lower_halves(double a, double b) {
+  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+  return __hiloint2double((int)hi[0], (int)lo[0]);
+}
 __device__ __forceinline__ double fuse_rows_sum(double a, double b) {
   const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
   const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
