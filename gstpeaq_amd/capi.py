@@ -158,6 +158,9 @@ FB_BAND_PLANES = {"moddiff": 0x1, "modwt": 0x2, "noiseloud": 0x4, "missing": 0x8
 PATTERN_BAND_PLANES = {"moddiff1": 0x1, "moddiff2": 0x2, "modwt": 0x4, "noiseloud": 0x8, "unsm_ref": 0x10,
                        "unsm_test": 0x20, "exc_ref": 0x40, "exc_test": 0x80, "adapt_ref": 0x100, "adapt_test": 0x200,
                        "mod_ref": 0x400, "mod_test": 0x800, "avgloud_ref": 0x1000}
+# PEAQ_BAND_SUMMARY_* (include/peaq_amd.h) by name, in row order; the advanced version has the first four
+BAND_SUMMARY_ROWS = ("nmr_sum", "nmr_max", "nmr_disturbed", "exc_ref_sum", "exc_test_sum", "moddiff1_wsum",
+                     "moddiff2_wsum", "noiseloud_sum")
 
 
 class HostPair(C.Structure):
@@ -311,6 +314,12 @@ def load_library():
                                                    C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.peaq_run_pair_pattern_bands.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
                                                   C.c_size_t, C.c_uint32, vp, C.c_size_t, u32p, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_band_summary"):    # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_band_summary_rows.argtypes = [C.c_int]
+        L.peaq_batch_run_band_summary.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p,
+                                                  u32p, C.c_uint32, vp, vp, vp]
+        L.peaq_run_pair_band_summary.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t,
+                                                 fp, C.c_size_t, vp, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_resample_supported.argtypes = [C.c_uint32]
         L.peaq_resampled_length.restype = C.c_uint32
@@ -2260,6 +2269,105 @@ def run_pair_pattern_bands(ctx, ref, test, planes=("noiseloud",), playback_level
     fc, noise = pattern_band_tables()
     res = dict(_pattern_band_planes_dict(rows[:nf.value], mask, n_bands), result=_result_dict(out, False), fc=fc,
                internal_noise=noise, planes=mask)
+    if align is not None:
+        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+    return res
+
+
+def _band_summary_views(rows, n_bands):
+    """rows [..., R, row] (peaq_batch_run_band_summary) -> the named views [..., n_bands] and `counted` [...]: every
+    view is its row over the row's denominator (entry n_bands), NaN where that is 0; moddiff1 / moddiff2 carry the
+    factor 100 / n_bands, so that their sum over the bands is the channel's AvgModDiff."""
+    rows = np.asarray(rows)
+
+    def ratio(k, scale=1.0):
+        den = rows[..., k, n_bands:n_bands + 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den != 0., scale * rows[..., k, :n_bands] / den, np.nan)
+
+    out = dict(counted=rows[..., 0, n_bands].astype(np.int64), nmr_mean=ratio(0), nmr_disturbed=ratio(2),
+               exc_ref_mean=ratio(3))
+    out["nmr_max"] = np.where(rows[..., 1, n_bands:n_bands + 1] != 0., rows[..., 1, :n_bands], np.nan)
+    if rows.shape[-2] > 4:
+        out.update(exc_test_mean=ratio(4), moddiff1=ratio(5, 100. / n_bands), moddiff2=ratio(6, 100. / n_bands),
+                   noiseloud_mean=ratio(7))
+    return out
+
+
+def batch_band_summary(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
+                       d_summary=None, results=None, stream=None, sync=True):
+    """Every pair's per-band summary, reduced over the pair's counted frames on the device in the run that scores the
+    batch (peaq_batch_run_band_summary; include/peaq_amd.h has the rows and which frames count).  ref/test,
+    n_ref/n_test, rate and align as for batch_bands.  d_summary: an optional CUDA float64 tensor [n_pairs (or more),
+    channels, R, row] to write into (pairs past the batch keep what they held); results: an optional CUDA float64
+    tensor [n_pairs, RESULT_DOUBLES].
+    Returns a dict: rows, np.ndarray [pairs, channels, R, row] (BAND_SUMMARY_ROWS in row order, the denominators in
+    the last entry of each row); the named views nmr_mean, nmr_max, nmr_disturbed (a fraction), exc_ref_mean and, in the
+    basic version, exc_test_mean, moddiff1, moddiff2 (their sum over the bands is the channel's AvgModDiff) and
+    noiseloud_mean, each [pairs, channels, bands] and NaN where its denominator is 0; counted [pairs, channels]; fc
+    (band_tables); results (result dicts); and d_summary / d_results, the device tensors.  sync=False: the device
+    tensors and fc only."""
+    import torch
+    advanced = bool(advanced)
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    if align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    n_bands, row, n_rows = ctx.L.peaq_band_count(advanced), ctx.L.peaq_band_row(advanced), ctx.L.peaq_band_summary_rows(advanced)
+    with _torch_stream(stream):
+        if d_summary is None:
+            d_summary = torch.empty((n_pairs, channels, n_rows, row), dtype=torch.float64, device=ref.device)
+        if results is None:
+            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_summary.is_cuda and d_summary.dtype == torch.float64 and d_summary.is_contiguous() and d_summary.dim() == 4
+    assert d_summary.shape[0] >= n_pairs and tuple(d_summary.shape[1:]) == (channels, n_rows, row)
+    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_run_band_summary(ctx.h, int(advanced), channels, float(playback_level), n_pairs,
+                                             C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                             a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                             a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                             C.c_void_p(d_summary.data_ptr()), C.c_void_p(results.data_ptr()),
+                                             _stream_ptr(stream)))
+    fc, _ = band_tables(advanced)
+    out = dict(d_summary=d_summary, d_results=results, fc=fc)
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    rows = d_summary[:n_pairs].cpu().numpy()
+    out.update(rows=rows, **_band_summary_views(rows, n_bands))
+    out["results"] = [_result_dict(r, advanced) for r in results.cpu().numpy()]
+    return out
+
+
+def run_pair_band_summary(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_band_summary: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`,
+    aligned first with align = a max_lag in 48 kHz samples.  Returns a dict: rows [channels, R, row], the named views of
+    batch_band_summary [channels, bands], counted [channels], fc, result (a result dict) and, with align, delay."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    advanced = bool(advanced)
+    ch = ref.shape[1]
+    assert test.shape[1] == ch
+    n_bands, row, n_rows = ctx.L.peaq_band_count(advanced), ctx.L.peaq_band_row(advanced), ctx.L.peaq_band_summary_rows(advanced)
+    rows = np.zeros((ch, n_rows, row))
+    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_band_summary(ctx.h, int(advanced), ch, float(playback_level), int(rate),
+                                            0 if align is None else int(align),
+                                            ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                            test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                            C.c_void_p(rows.ctypes.data), C.byref(rec),
+                                            out.ctypes.data_as(C.POINTER(C.c_double))))
+    fc, _ = band_tables(advanced)
+    res = dict(rows=rows, fc=fc, result=_result_dict(out, advanced), **_band_summary_views(rows, n_bands))
     if align is not None:
         res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
     return res

@@ -582,6 +582,12 @@ usage (const char *prog)
       "                avgloud_ref (default noiseloud).  The header line carries the bands' centre frequencies in Hz (the\n"
       "                plain one-call mode; with --device-resample, --align; a run of its own, like --bands; with\n"
       "                --advanced see --fb-bands)\n"
+      "  --band-summary=FILE also write the pair's per-band summary to FILE as CSV: one line per channel and critical\n"
+      "                band with the band's centre frequency in Hz, the band's sums over the counted frames (first to\n"
+      "                last frame above the data boundary) and their denominators: nmr_sum, nmr_max, nmr_disturbed,\n"
+      "                exc_ref_sum and, in the basic version, exc_test_sum, moddiff1_wsum, moddiff2_wsum, noiseloud_sum\n"
+      "                (the plain one-call mode; with --advanced, --device-resample, --align; a run of its own, like\n"
+      "                --bands)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -924,6 +930,72 @@ done:
   return rc;
 }
 
+/* the rows of --band-summary=FILE by name, in row order (PEAQ_BAND_SUMMARY_*), and the name of each row's denominator */
+enum { n_band_summary_rows = 8 };
+static const char *const band_summary_row_names[n_band_summary_rows] = { "nmr_sum", "nmr_max", "nmr_disturbed",
+  "exc_ref_sum", "exc_test_sum", "moddiff1_wsum", "moddiff2_wsum", "noiseloud_sum" };
+
+/* --band-summary=FILE: the pair through peaq_run_pair_band_summary, its rows as CSV -- a header line, then one line per
+ * (channel, band): the band's centre frequency in Hz, the band's value of every row, then the denominators the rows
+ * share (counted: the number of counted frames; in the basic version also modwt_sum, the sum of the frames' weights
+ * under the two modulation-difference rows, and loud_frames, the number of frames under noiseloud_sum); every value as
+ * %.17g, which reads back to the same double.  Prints the delay line of --align. */
+static int
+write_band_summary (const char *path, peaq_ctx *ctx, int advanced, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  const int count = peaq_band_count (advanced), row = peaq_band_row (advanced), n_rows = peaq_band_summary_rows (advanced);
+  const int ch = ref->channels;
+  int c, k, b, rc = 1;
+  double *rows, *fc;
+  peaq_delay delay;
+  FILE *out;
+  rows = malloc ((size_t) ch * n_rows * row * sizeof *rows);
+  fc = malloc (count * sizeof *fc);
+  if (!rows || !fc) {
+    printf ("Error: out of memory for the band summary\n");
+    goto done;
+  }
+  if (peaq_band_tables (advanced, fc, NULL) != PEAQ_OK ||
+      peaq_run_pair_band_summary (ctx, advanced, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples,
+          test->frames, rows, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag)
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+  if (!(out = fopen (path, "w"))) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  fprintf (out, "channel,band,fc");
+  for (k = 0; k < n_rows; k++)
+    fprintf (out, ",%s", band_summary_row_names[k]);
+  fprintf (out, advanced ? ",counted\n" : ",counted,modwt_sum,loud_frames\n");
+  for (c = 0; c < ch; c++) {
+    const double *v = rows + (size_t) c * n_rows * row;
+    for (b = 0; b < count; b++) {
+      fprintf (out, "%d,%d,%.17g", c, b, fc[b]);
+      for (k = 0; k < n_rows; k++)
+        fprintf (out, ",%.17g", v[k * row + b]);
+      fprintf (out, ",%.17g", v[PEAQ_BAND_SUMMARY_NMR_SUM * row + count]);
+      if (!advanced)
+        fprintf (out, ",%.17g,%.17g", v[PEAQ_BAND_SUMMARY_MODDIFF1_WSUM * row + count],
+            v[PEAQ_BAND_SUMMARY_NOISELOUD_SUM * row + count]);
+      fprintf (out, "\n");
+    }
+  }
+  if (fclose (out)) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  rc = 0;
+done:
+  free (rows);
+  free (fc);
+  return rc;
+}
+
 int
 main (int argc, char **argv)
 {
@@ -950,6 +1022,7 @@ main (int argc, char **argv)
   uint32_t fb_band_planes = PEAQ_FB_BAND_NOISELOUD;
   char *pattern_bands_path = NULL;   /* --pattern-bands=FILE[:PLANES], peaq_run_pair_pattern_bands */
   uint32_t pattern_band_planes = PEAQ_PAT_BAND_NOISELOUD;
+  const char *band_summary_path = NULL;   /* --band-summary=FILE, peaq_run_pair_band_summary */
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -1123,6 +1196,11 @@ main (int argc, char **argv)
         *colon = 0;
       }
     }
+    else if (!strcmp (argv[i], "--band-summary") || !strcmp (argv[i], "--band-summary=")) {
+      fprintf (stderr, "Failed to initialize: --band-summary needs a file name (--band-summary=FILE)\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--band-summary=", 15))
+      band_summary_path = argv[i] + 15;
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -1173,6 +1251,14 @@ main (int argc, char **argv)
   }
   if (pattern_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
     fprintf (stderr, "Failed to initialize: --pattern-bands is a run of its own (not with --bands, --trace, --match-gain or an --align-... beyond --align)\n");
+    return 1;
+  }
+  if (band_summary_path && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --band-summary belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
@@ -1337,7 +1423,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (pattern_bands_path) {
+    if (band_summary_path) {
+      if (write_band_summary (band_summary_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (pattern_bands_path) {
       if (write_pattern_bands (pattern_bands_path, pattern_band_planes, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (fb_bands_path) {

@@ -815,3 +815,29 @@ extern "C" int peaq_run_pair_pattern_bands(peaq_ctx* c, int channels, double lev
   if (n_frames) *n_frames = nf;
   return PEAQ_OK;
 }
+
+extern "C" int peaq_run_pair_band_summary(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
+                                          uint32_t max_lag, const float* ref, size_t n_ref, const float* test,
+                                          size_t n_test, double* summary, peaq_delay* delay, peaq_result* out) {
+  const std::string w("peaq_run_pair_band_summary");
+  if (!summary) return fail(PEAQ_ERR_ARG, w + ": summary is NULL");
+  if (max_lag)
+    if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
+  ScoredPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
+    return rc;
+  const size_t bytes =
+      (size_t)channels * peaq_band_summary_rows(advanced) * peaq_band_row(advanced) * sizeof(double);
+  DevBuf d_res, d_sm;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  HIP_TRY(d_sm.reserve(bytes));
+  if (int rc = peaq_batch_run_band_summary(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len,
+                                           pp.len + 1, 0, d_sm.as<double>(), d_res.as<peaq_result>(), nullptr))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(summary, d_sm.p, bytes, hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  return PEAQ_OK;
+}

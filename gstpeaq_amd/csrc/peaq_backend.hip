@@ -302,7 +302,10 @@ __device__ __forceinline__ void level_adapt(const BandLane<NB, SLOTS>& bl, const
 }
 
 // modpatt.c:223-251; st: prev_loud, filt_loud, filt_dloud
-template <int NB, int SLOTS, class TAB>
+// PIN (summary instantiation, whose test-side state comes from LDS): the two filters spelt out as the compiler contracts
+// them where the state sits in registers -- filt_dloud rounds (1 - a) dl and fuses a st, filt_loud rounds a st and fuses
+// (1 - a) loud.  With the state from LDS it fuses a st in both, and the results would not be peaq_batch_run's to the bit.
+template <int NB, int SLOTS, class TAB, bool PIN = false>
 __device__ __forceinline__ void modulation(const BandLane<NB, SLOTS>& bl, const TAB& bt,
                                            const double (&loud)[SLOTS], double (&st)[3][SLOTS],
                                            double (&mod)[SLOTS]) {
@@ -312,8 +315,13 @@ __device__ __forceinline__ void modulation(const BandLane<NB, SLOTS>& bl, const 
     if (bl.valid(s)) {
       const double a = bt.adapt_tc(bl.band(s));
       const double dl = bt.deriv_factor() * fabs(loud[s] - st[0][s]);
-      st[2][s] = a * st[2][s] + (1 - a) * dl;
-      st[1][s] = a * st[1][s] + (1. - a) * loud[s];
+      if (PIN) {
+        st[2][s] = __builtin_fma(a, st[2][s], (1 - a) * dl);
+        st[1][s] = __builtin_fma(1. - a, loud[s], a * st[1][s]);
+      } else {
+        st[2][s] = a * st[2][s] + (1 - a) * dl;
+        st[1][s] = a * st[1][s] + (1. - a) * loud[s];
+      }
       mod[s] = div_fast(st[2][s], 1. + st[1][s] * (1. / 0.3));
       st[0][s] = loud[s];
     }
@@ -343,8 +351,8 @@ __device__ __forceinline__ double total_loudness_part(const BandLane<NB, SLOTS>&
 enum LeadMode { LEAD_OWN, LEAD_KEEP, LEAD_USE };
 // (the lane's part of the sum over the bands: callers with several sums in a frame take them through ONE reduction,
 // wave_sum2 / wave_sum4, and finish with noise_loudness_total)
-// TERMS (pattern-bands instantiation only): every slot's term of that sum also goes to terms[s], 0 for a slot beyond the
-// last band -- the very value the sum adds, so a band below the hinge reads exactly 0.
+// TERMS (pattern-bands and summary instantiations only): every slot's term of that sum also goes to terms[s], 0 for a
+// slot beyond the last band -- the very value the sum adds, so a band below the hinge reads exactly 0.
 template <int NB, int SLOTS, class TAB, LeadMode LM = LEAD_OWN, bool TERMS = false>
 __device__ __forceinline__ double noise_loudness_part(const BandLane<NB, SLOTS>& bl, const TAB& bt,
                                                       double alpha, double thres_fac, double s0,
@@ -389,8 +397,8 @@ __device__ __forceinline__ double noise_loudness_total(double sum, double nl_min
 }
 
 // movs.c:224-251: returns d1 (un-normalised), d2, weight
-// TERMS (pattern-bands instantiation only): every slot's terms of the three sums also go to terms[0..2][s], 0 for a slot
-// beyond the last band.
+// TERMS (pattern-bands and summary instantiations only): every slot's terms of the three sums also go to
+// terms[0..2][s], 0 for a slot beyond the last band.
 template <int NB, int SLOTS, class TAB, bool TERMS = false>
 __device__ __forceinline__ void mod_difference(const BandLane<NB, SLOTS>& bl, const TAB& bt,
                                                double lev_wt, const double (&mr)[SLOTS], const double (&mt)[SLOTS],
@@ -499,6 +507,44 @@ __device__ __forceinline__ void fb_band_store(const FbBandArgs& bnd, uint32_t bi
 }
 
 // ---------------------------------------------------------------------------
+// Band summary (SummaryArgs, peaq_batch_run_band_summary): a channel's running rows sit in LDS, rows of ROW doubles; a
+// lane owns the two entries 2 lane and 2 lane + 1 of every row and is the only one to touch them (no barrier).  NB is
+// odd, so the lane that owns band NB - 1 owns the row's denominator (entry NB) as its second entry: callers hand that
+// lane the denominator's increment in place of a band value (`last`).
+// ---------------------------------------------------------------------------
+// row += (v0, v1): one 16-byte read-modify-write
+__device__ __forceinline__ void summary_add(double* row, bool own, double v0, double v1) {
+  if (!own) return;
+  double2* __restrict__ p = reinterpret_cast<double2*>(row);
+  double2 v = *p;
+  v.x += v0;
+  v.y += v1;
+  *p = v;
+}
+// row = max (row, (v0, v1)); the denominator counts
+__device__ __forceinline__ void summary_max(double* row, bool own, bool last, double v0, double v1) {
+  if (!own) return;
+  double2* __restrict__ p = reinterpret_cast<double2*>(row);
+  double2 v = *p;
+  if (v0 > v.x) v.x = v0;
+  if (last)
+    v.y += 1.;
+  else if (v1 > v.y)
+    v.y = v1;
+  *p = v;
+}
+// the R rows of one channel, a lane's entries of each: LDS <-> the caller's array, LDS -> the saved copy
+template <int R, int ROW>
+__device__ __forceinline__ void summary_copy(double* dst, const double* src, bool own) {
+  if (!own) return;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    asm volatile("" ::: "memory");                   // row by row (rare): one row's registers, not R rows' at once
+    *reinterpret_cast<double2*>(dst + k * ROW) = *reinterpret_cast<const double2*>(src + k * ROW);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // FFT-model back end.  ADV = false: basic version (109 bands, 11 MOVs).
 // ADV = true: the FFT part of the advanced version (55 bands; SegmentalNMR, EHS).
 // ---------------------------------------------------------------------------
@@ -528,9 +574,13 @@ struct BackendShared {
 // PBD = true (backend_pattern_bands_kernel, pattern-band launches of the basic version only): the modulation differences
 // and the noise loudness are evaluated for every frame, as with TRC, and every lane stores its two bands' terms and
 // patterns where they come up (PatternBandArgs, band_store); the accumulators see what the gates admit.
+// SUM = true (backend_summary_kernel, summary launches only): every lane adds its two bands' values of the counted
+// frames to the channel's running rows in LDS where they come up (SummaryArgs, summary_add); the arithmetic and the
+// gates are the plain instantiation's, and a frame whose gate is closed evaluates nothing more than there.
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false, PBD = false;
+  constexpr bool PTS = false, TRC = false, BND = false, PBD = false, SUM = false;
+  constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
@@ -541,7 +591,8 @@ __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false, SUM = false;
+  constexpr SummaryArgs sum{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
   constexpr PatternBandArgs pbd{};
@@ -550,7 +601,8 @@ __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, P
 // the trace instantiation: a third kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false, SUM = false;
+  constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr BandArgs bnd{};
   constexpr PatternBandArgs pbd{};
@@ -559,7 +611,8 @@ __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, Tr
 // the bands instantiation: a fourth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false, SUM = false;
+  constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr PatternBandArgs pbd{};
@@ -569,21 +622,37 @@ __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, Ba
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendArgs a, PatternBandArgs pbd) {
   static_assert(!ADV, "the 55-band path has no pattern layer");
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true, SUM = false;
+  constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
 #include "peaq_backend_fft.inc"
 }
+// the summary instantiation: a sixth kernel of its own name with the same body
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, SummaryArgs sum) {
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = false, SUM = true;
+  constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
+  constexpr BandArgs bnd{};
+  constexpr PatternBandArgs pbd{};
+#include "peaq_backend_fft.inc"
+}
 
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                          const TraceArgs* trc, const BandArgs* bnd, const PatternBandArgs* pbd) {
+                          const TraceArgs* trc, const BandArgs* bnd, const PatternBandArgs* pbd, const SummaryArgs* sum) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
   if (bnd && (pts || trc || a.debug || a.pair_frame0)) return hipErrorInvalidValue;   // a run's own launches only
   if (pbd && (bnd || pts || trc || a.debug || a.pair_frame0 || a.advanced)) return hipErrorInvalidValue;
-  if (pbd)
+  if (sum && (pbd || bnd || pts || trc || a.debug || a.pair_frame0 || a.pair_slot)) return hipErrorInvalidValue;
+  if (sum && !a.advanced)
+    hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *sum);
+  else if (sum)
+    hipLaunchKernelGGL((backend_summary_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *sum);
+  else if (pbd)
     hipLaunchKernelGGL((backend_pattern_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pbd);
   else if (bnd && !a.advanced)
     hipLaunchKernelGGL((backend_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *bnd);
@@ -817,6 +886,26 @@ __global__ void finalize_points_kernel(const PointSnap* __restrict__ snap, int a
   const PointSnap* sp = snap + i;
   out[i] = finalize_state(sp->status, sp->acc[0], sp->acc[1], sp->sig_energy, sp->noise_energy, (double)sp->frames,
                           (double)sp->fb_blocks, advanced, channels, clamp_movs);
+}
+
+// band summary: a pair whose accumulators end tentative counts nothing after its last frame above the data boundary
+// (movaccum.c:443-447 reads data_saved): its rows go back to the copy the back end took when it turned tentative.  One
+// workgroup per pair.
+__global__ void summary_restore_kernel(const PairState* __restrict__ st, int status_idx, double* __restrict__ rows,
+                                       const double* __restrict__ saved, unsigned n_pairs, unsigned pair_doubles) {
+  const unsigned pair = blockIdx.x;
+  if (pair >= n_pairs || st[pair].status[status_idx] != kTentative) return;
+  const size_t base = (size_t)pair * pair_doubles;
+  for (unsigned i = threadIdx.x; i < pair_doubles; i += blockDim.x) rows[base + i] = saved[base + i];
+}
+
+hipError_t launch_summary_restore(const PairState* state, int advanced, const SummaryArgs& sum, unsigned n_pairs,
+                                  unsigned pair_doubles, hipStream_t stream) {
+  if (n_pairs == 0) return hipSuccess;
+  // (the accumulator whose tentative state the back end's summary rows follow)
+  hipLaunchKernelGGL(summary_restore_kernel, dim3(n_pairs), dim3(256), 0, stream, state,
+                     advanced ? (int)MA_SEGNMR : (int)MB_NMR, sum.rows, sum.saved, n_pairs, pair_doubles);
+  return hipGetLastError();
 }
 
 hipError_t launch_finalize(const PairState* state, int advanced, int channels, unsigned n_pairs, ResultRecord* out,

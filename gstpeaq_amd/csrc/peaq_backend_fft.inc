@@ -1,7 +1,7 @@
 // peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = BND =
-// PBD = false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true),
-// backend_bands_kernel<NB, ADV> (BND = true) and backend_pattern_bands_kernel<NB, false> (PBD = true) in
-// peaq_backend.hip: one text, five kernels of their own names.
+// PBD = SUM = false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true),
+// backend_bands_kernel<NB, ADV> (BND = true), backend_pattern_bands_kernel<NB, false> (PBD = true) and
+// backend_summary_kernel<NB, ADV> (SUM = true) in peaq_backend.hip: one text, six kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -45,6 +45,32 @@
   if (lane < kPaPad) sh.pa[chan][0][lane] = sh.pa[chan][1][lane] = 0.;
   __syncthreads();                                   // the table copy is complete
 
+  // (summary instantiation only) the channel's running rows in LDS, this lane's two entries of each: loaded from the
+  // caller's array, where they sit between the launches of a run, and stored back at the end (here, before the band
+  // state comes into its registers, and there after it has left them).  sum_st follows the
+  // accumulators' status (movaccum.c:317-362) as a scalar: kInit until the first frame above the data boundary (nothing
+  // is counted before it), kTentative from a frame below it to the next one above.
+  constexpr int SUM_R = band_summary_rows(ADV), SUM_ROW = band_row(NB);
+  __shared__ __attribute__((aligned(16))) double sh_sum[SUM ? 2 * SUM_R * SUM_ROW : 2];
+  const bool sum_own = SUM && 2 * lane < NB;           // (the last of them owns band NB - 1 and the denominators)
+  const bool sum_last = SUM && 2 * lane + 1 == NB;
+  // (a uniform row address and the lane's 32-bit byte offset, made where it is used: no lane address lives through the
+  // frame loop -- band_store's way)
+  auto sum_at = [&](double* base) -> double* {
+    unsigned off = (unsigned)lane * 16u;
+    asm volatile("" : "+v"(off));
+    return reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off);
+  };
+  auto sum_row = [&](int k) -> double* { return sum_at(sh_sum + (SUM ? (chan * SUM_R + k) * SUM_ROW : 0)); };
+  auto sum_cell = [&](double* base) -> double* {
+    return sum_at(base + ((size_t)pair * channels + chan) * (SUM_R * SUM_ROW));
+  };
+  int sum_st = kInit;
+  if (SUM) {
+    sum_st = __builtin_amdgcn_readfirstlane(ps->status[ADV ? (int)MA_SEGNMR : (int)MB_NMR]);
+    summary_copy<SUM_R, SUM_ROW>(sum_row(0), sum_cell(sum.rows), sum_own);
+  }
+
   // ---- recurrent state -> registers -----------------------------------------------
   double sm[2][SLOTS];                               // smeared excitation filters (ref, test)
   double la[6][SLOTS];
@@ -55,7 +81,7 @@
     sm[0][s] = cs->vec[kSmearRef][b < kBandStride ? b : 0];
     // (the 55-band path never changes the test filter; its bands kernel leaves that state in memory: the band stores
     // take the four registers it would sit in through the frame loop)
-    sm[1][s] = BND && ADV ? 0. : cs->vec[kSmearTest][b < kBandStride ? b : 0];
+    sm[1][s] = (BND || SUM) && ADV ? 0. : cs->vec[kSmearTest][b < kBandStride ? b : 0];
 #pragma unroll
     for (int v = 0; v < 6; ++v) la[v][s] = cs->vec[kLaFiltRef + v][b < kBandStride ? b : 0];
 #pragma unroll
@@ -63,6 +89,19 @@
       mdr[v][s] = cs->vec[kModPrevRef + v][b < kBandStride ? b : 0];
       mdt[v][s] = cs->vec[kModPrevTest + v][b < kBandStride ? b : 0];
     }
+  }
+  // (summary instantiation, basic version) the test side's modulation state -- used once a frame, in modulation<> --
+  // lives in LDS between its uses: the twelve registers it would sit in through the frame loop are what the running
+  // rows' updates need to keep the plain kernel's waves per SIMD.  The same values go through the same arithmetic.
+  constexpr bool MDT_LDS = SUM && !ADV;
+  __shared__ __attribute__((aligned(16))) double sh_mdt[MDT_LDS ? 2 * 3 * kLdsBands : 2];
+  auto mdt_at = [&](int v) -> double2* {
+    return reinterpret_cast<double2*>(sum_at(sh_mdt + (MDT_LDS ? (chan * 3 + v) * kLdsBands : 0)));
+  };
+  if (MDT_LDS) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) *mdt_at(v) = make_double2(mdt[v][0], mdt[v][1]);
+    asm volatile("" ::: "memory");
   }
   LaneAcc acc;
   {
@@ -90,7 +129,6 @@
     sh.energy[0] = ps->sig_energy;
     sh.energy[1] = ps->noise_energy;
   }
-
   for (unsigned frame = f_begin; frame < f_end; ++frame) {
     asm volatile("" : "+v"(bt.off));                 // the tables are re-read from LDS where they are used
     const double* __restrict__ rec0 =
@@ -106,6 +144,19 @@
     const bool above = fl_ref & 1;
     const bool ehs_valid = ((fl_ref | fl_test) & 2) != 0;
     if (!ADV || lane == MA_SEGNMR || lane == MA_EHS) acc.set_tentative(!above);
+    // (summary instantiation only) the rows take the same turns: the copy a pair that ends tentative gets back
+    // (summary_restore_kernel) is taken where the accumulators take theirs -- wave-uniform and rare
+    bool sum_cnt = false;
+    if (SUM) {
+      if (__builtin_amdgcn_readfirstlane((int)above)) {
+        sum_st = kNormal;
+      } else if (sum_st == kNormal) {
+        summary_copy<SUM_R, SUM_ROW>(sum_cell(sum.saved), sum_row(0), sum_own);
+        sum_st = kTentative;
+      }
+      sum_st = __builtin_amdgcn_readfirstlane(sum_st);
+      sum_cnt = sum_st != kInit;
+    }
 
     // ---- this frame's patterns -------------------------------------------------------
     double ur[SLOTS], ut[SLOTS], lr[SLOTS], lt[SLOTS], nz[SLOTS];
@@ -126,7 +177,7 @@
     }
     // (pattern-bands instantiation: the noise pattern is read again where the ratio needs it, below -- the four
     // registers it would sit in through the pattern layer are what the term stores need)
-    if (PBD) nz[0] = nz[1] = 0.;
+    if (PBD || (SUM && !ADV)) nz[0] = nz[1] = 0.;
     // (pattern-bands instantiation only) the row cell of this (pair, frame, channel); the unsmeared excitations go out
     // here, every other plane where it comes up
     const size_t pbd_cell = PBD ? ((size_t)pair * pbd.frame_stride + frame) * channels + chan : 0;
@@ -142,10 +193,19 @@
     for (int s = 0; s < SLOTS; ++s) {
       const int b = bl.band(s) < kBandStride ? bl.band(s) : 0;
       const double ac = bt.ear_tc(b);
-      sm[0][s] = ac * sm[0][s] + (1. - ac) * ur[s];
+      // (summary instantiation, basic version: the two filters spelt out as the compiler contracts them in the plain
+      // instantiation -- the reference's rounds (1 - a) u and fuses a s, the test's rounds a s and fuses (1 - a) u.  Left
+      // to itself it fuses a s in both here, and the results would not be peaq_batch_run's to the bit.)
+      if (SUM && !ADV)
+        sm[0][s] = __builtin_fma(ac, sm[0][s], (1. - ac) * ur[s]);
+      else
+        sm[0][s] = ac * sm[0][s] + (1. - ac) * ur[s];
       er[s] = sm[0][s] > ur[s] ? sm[0][s] : ur[s];
       if (!ADV) {
-        sm[1][s] = ac * sm[1][s] + (1. - ac) * ut[s];
+        if (SUM)
+          sm[1][s] = __builtin_fma(1. - ac, ut[s], ac * sm[1][s]);
+        else
+          sm[1][s] = ac * sm[1][s] + (1. - ac) * ut[s];
         et[s] = sm[1][s] > ut[s] ? sm[1][s] : ut[s];
       } else {
         et[s] = 0.;
@@ -161,6 +221,10 @@
     if (PBD) {
       band_store<NB>(pbd, kPatBandExcRef, pbd_cell, lane, er[0], bl.valid(1) ? er[1] : 0.);
       band_store<NB>(pbd, kPatBandExcTest, pbd_cell, lane, et[0], bl.valid(1) ? et[1] : 0.);
+    }
+    if (SUM && sum_cnt) {
+      summary_add(sum_row(kSumExcRef), sum_own, er[0], sum_last ? 1. : er[1]);
+      if (!ADV) summary_add(sum_row(kSumExcTest), sum_own, et[0], sum_last ? 1. : et[1]);
     }
 
     // lane i owns accumulator i: every MOV value of the frame is routed to its owner as soon as
@@ -180,7 +244,20 @@
       double ad_ref[SLOTS], ad_test[SLOTS], mr[SLOTS], mt[SLOTS];
       level_adapt<NB, SLOTS>(bl, bt, er, et, la, &sh.pa[chan][0][0], ad_ref, ad_test);
       modulation<NB, SLOTS>(bl, bt, lr, mdr, mr);
-      modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+      if (MDT_LDS) {
+        double m[3][SLOTS];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+          const double2 t = *mdt_at(v);
+          m[v][0] = t.x;
+          m[v][1] = t.y;
+        }
+        modulation<NB, SLOTS, LdsTabs, true>(bl, bt, lt, m, mt);
+#pragma unroll
+        for (int v = 0; v < 3; ++v) *mdt_at(v) = make_double2(m[v][0], m[v][1]);
+      } else {
+        modulation<NB, SLOTS>(bl, bt, lt, mdt, mt);
+      }
       if (PBD) {                                     // (the helpers leave 0 in the slot beyond the last band)
         band_store<NB>(pbd, kPatBandAdaptRef, pbd_cell, lane, ad_ref[0], ad_ref[1]);
         band_store<NB>(pbd, kPatBandAdaptTest, pbd_cell, lane, ad_test[0], ad_test[1]);
@@ -270,6 +347,13 @@
           band_store<NB>(pbd, kPatBandModDiff1, pbd_cell, lane, md_t[0][0], md_t[0][1]);
           band_store<NB>(pbd, kPatBandModDiff2, pbd_cell, lane, md_t[1][0], md_t[1][1]);
           band_store<NB>(pbd, kPatBandModWt, pbd_cell, lane, md_t[2][0], md_t[2][1]);
+        } else if (SUM) {                            // (frame >= 24 here) the frame's weight times the terms, per slot
+          double md_t[3][SLOTS];
+          mod_difference<NB, SLOTS, LdsTabs, true>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt, md_t);
+          if (sum_cnt) {
+            summary_add(sum_row(kSumModDiff1), sum_own, wt * md_t[0][0], sum_last ? wt : wt * md_t[0][1]);
+            summary_add(sum_row(kSumModDiff2), sum_own, wt * md_t[1][0], sum_last ? wt : wt * md_t[1][1]);
+          }
         } else {
           mod_difference<NB, SLOTS>(bl, bt, 100., mr, mt, mdr[1], d1, d2, wt);
         }
@@ -299,6 +383,11 @@
         nl_part = noise_loudness_part<NB, SLOTS, LdsTabs, LEAD_OWN, true>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test,
                                                                           nullptr, nl_t);
         band_store<NB>(pbd, kPatBandNoiseLoud, pbd_cell, lane, nl_t[0], nl_t[1]);
+      } else if (SUM && nl_open) {                   // (the gate is open here: nothing is evaluated behind a closed one)
+        double nl_t[SLOTS];
+        nl_part = noise_loudness_part<NB, SLOTS, LdsTabs, LEAD_OWN, true>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test,
+                                                                          nullptr, nl_t);
+        if (sum_cnt) summary_add(sum_row(kSumNoiseLoud), sum_own, nl_t[0], sum_last ? 1. : nl_t[1]);
       } else if (nl_open) {
         nl_part = noise_loudness_part<NB, SLOTS>(bl, bt, 1.5, 0.15, 0.5, mr, mt, ad_ref, ad_test);
       }
@@ -316,7 +405,7 @@
     {
       double nsum = 0., nmax = 0.;
       double bnd_r[SLOTS] = {0., 0.};                  // (bands instantiation only: dead otherwise)
-      if (PBD) {
+      if (PBD || (SUM && !ADV)) {
         const int b0 = bl.band(0);
         const double2 v4 = *reinterpret_cast<const double2*>(rec + kRecNoise + (b0 < kBandStride ? b0 : 0));
         nz[0] = v4.x; nz[1] = v4.y;
@@ -331,6 +420,12 @@
         }
       }
       if (BND) band_store<NB>(bnd, kBandNmr, bnd_cell, lane, bnd_r[0], bnd_r[1]);
+      if (SUM && sum_cnt) {
+        summary_add(sum_row(kSumNmrSum), sum_own, bnd_r[0], sum_last ? 1. : bnd_r[1]);
+        summary_max(sum_row(kSumNmrMax), sum_own, sum_last, bnd_r[0], bnd_r[1]);
+        summary_add(sum_row(kSumNmrDisturbed), sum_own, bnd_r[0] > 1.41253754462275 ? 1. : 0.,
+                    sum_last || bnd_r[1] > 1.41253754462275 ? 1. : 0.);
+      }
       double xsum = 0., qsum = 0.;                    // sum of the bands' exponents (pc above), of the steps
       if (!ADV && chan == 0) {
 #pragma unroll
@@ -453,12 +548,21 @@
   }
 
   // ---- registers -> recurrent state -------------------------------------------------------
+  if (MDT_LDS) {
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      const double2 t = *mdt_at(v);
+      mdt[v][0] = t.x;
+      mdt[v][1] = t.y;
+    }
+  }
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
     const int b = bl.band(s);
     if (b < kBandStride) {
       cs->vec[kSmearRef][b] = sm[0][s];
-      if (!(BND && ADV)) cs->vec[kSmearTest][b] = sm[1][s];
+      if (!((BND || SUM) && ADV)) cs->vec[kSmearTest][b] = sm[1][s];
       if (!ADV) {                                    // advanced: these belong to the filter-bank back end
 #pragma unroll
         for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][b] = la[v][s];
@@ -486,3 +590,5 @@
     a.clk[0] += __builtin_readcyclecounter() - clk_s0;
     a.clk[1] += wall_clock64() - clk_w0;
   }
+  // (last: the band state's registers are free by now)
+  if (SUM) summary_copy<SUM_R, SUM_ROW>(sum_cell(sum.rows), sum_row(0), sum_own);

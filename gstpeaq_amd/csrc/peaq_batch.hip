@@ -232,26 +232,38 @@ static_assert(PEAQ_PAT_BAND_MODDIFF1 == kPatBandModDiff1 && PEAQ_PAT_BAND_MODDIF
                   PEAQ_PAT_BAND_AVGLOUD_REF == kPatBandAvgLoudRef,
               "the pattern-band planes of include/peaq_amd.h and peaq_kernels.h");
 
+// Rows of a band summary (peaq_batch_run_band_summary): nullptr for a plain batch.  Never together with any of the five
+// above; the FFT back end keeps the pair's running rows in the caller's array between its launches.
+struct SummaryOut {
+  double* d_summary;            // [n_pairs][channels][rows][band_row]
+};
+static_assert(PEAQ_BAND_SUMMARY_NMR_SUM == kSumNmrSum && PEAQ_BAND_SUMMARY_NMR_MAX == kSumNmrMax &&
+                  PEAQ_BAND_SUMMARY_NMR_DISTURBED == kSumNmrDisturbed && PEAQ_BAND_SUMMARY_EXC_REF_SUM == kSumExcRef &&
+                  PEAQ_BAND_SUMMARY_EXC_TEST_SUM == kSumExcTest && PEAQ_BAND_SUMMARY_MODDIFF1_WSUM == kSumModDiff1 &&
+                  PEAQ_BAND_SUMMARY_MODDIFF2_WSUM == kSumModDiff2 && PEAQ_BAND_SUMMARY_NOISELOUD_SUM == kSumNoiseLoud,
+              "the summary rows of include/peaq_amd.h and peaq_kernels.h");
+
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
                             const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
-                            const PatternBandOut* po);
+                            const PatternBandOut* po, const SummaryOut* so);
 
-// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands and
-// peaq_batch_run_pattern_bands: one driver, the points, the trace records and the band rows optional (`who` names the
-// entry in messages)
+// peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands,
+// peaq_batch_run_pattern_bands and peaq_batch_run_band_summary: one driver, the points, the trace records, the band
+// rows and the summary optional (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
                            const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr,
-                           const FbBandOut* fo = nullptr, const PatternBandOut* po = nullptr) {
+                           const FbBandOut* fo = nullptr, const PatternBandOut* po = nullptr,
+                           const SummaryOut* so = nullptr) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo && !po)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo && !po && !so)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -264,7 +276,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo, po);
+                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo, po, so);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -501,6 +513,27 @@ extern "C" int peaq_batch_run_pattern_bands(peaq_ctx* c, int channels, double le
                          n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, nullptr, &po);
 }
 
+// ---- band summary ------------------------------------------------------------------------------------------------
+extern "C" int peaq_band_summary_rows(int advanced) { return band_summary_rows(advanced != 0); }
+
+// The summary's own argument first, as the band traces': it needs no context and no device.
+extern "C" int peaq_batch_run_band_summary(peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
+                                           const float* d_ref, const float* d_test, size_t pair_stride,
+                                           const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform,
+                                           double* d_summary, peaq_result* d_results, void* stream_) {
+  const std::string w("peaq_batch_run_band_summary");
+  if (!d_summary) return fail(PEAQ_ERR_ARG, w + ": d_summary is NULL");
+  if (reinterpret_cast<uintptr_t>(d_summary) % 16) {
+    char addr[32];
+    std::snprintf(addr, sizeof addr, "%p", static_cast<void*>(d_summary));
+    return fail(PEAQ_ERR_ARG, w + ": d_summary " + addr + " is not 16-byte aligned");
+  }
+  const SummaryOut so{d_summary};
+  return batch_run_entry("peaq_batch_run_band_summary", c, advanced ? 1 : 0, channels, level_db, n_pairs, d_ref, d_test,
+                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, &so);
+}
+
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
   if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
   if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
@@ -571,7 +604,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
                             const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
-                            const PatternBandOut* po) {
+                            const PatternBandOut* po, const SummaryOut* so) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -659,9 +692,21 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     pba.planes = po->planes;
   }
   const PatternBandArgs* pbd = po ? &pba : nullptr;
+  // band summary: every FFT back-end launch of the run is the summary instantiation.  The caller's rows start from zero
+  // and carry the running sums from launch to launch; the copy a pair takes when it turns tentative goes to scratch of
+  // the same shape (reserved here, so that running out of memory is reported before anything is enqueued).
+  SummaryArgs sma{};
+  const size_t sum_pair_doubles = (size_t)channels * band_summary_rows(advanced != 0) * band_row(advanced ? 55 : 109);
+  if (so) {
+    HIP_TRY(c->sum_saved.reserve((size_t)n_pairs * sum_pair_doubles * sizeof(double)));
+    sma.rows = so->d_summary;
+    sma.saved = c->sum_saved.as<double>();
+  }
+  const SummaryArgs* sum = so ? &sma : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
+  if (so) HIP_TRY(hipMemsetAsync(sma.rows, 0, (size_t)n_pairs * sum_pair_doubles * sizeof(double), stream));
   if (tr) HIP_TRY(launch_points_init(pa.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
@@ -753,7 +798,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd, pbd));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd, pbd, sum));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;
@@ -777,6 +822,8 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   for (int i = 0; i < 2; ++i)
     if (back_done[i]) HIP_TRY(hipStreamWaitEvent(stream, back_done[i], 0));
   if (fb_done) HIP_TRY(hipStreamWaitEvent(stream, fb_done, 0));
+  if (so)
+    HIP_TRY(launch_summary_restore(c->state.as<PairState>(), advanced, sma, n_pairs, (unsigned)sum_pair_doubles, stream));
   if (d_results)
     HIP_TRY(launch_finalize(c->state.as<PairState>(), advanced, channels, n_pairs,
                             reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));

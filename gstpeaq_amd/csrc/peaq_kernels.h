@@ -114,6 +114,22 @@ struct PatternBandArgs {
   uint32_t planes;              // kPatBand* bits; the slot of a plane is the rank of its bit among the set ones
 };
 
+// ---- per-band summary (peaq_batch_run_band_summary) ---------------------------------------------
+// The band values of the two traces above reduced over the pair's COUNTED frames (first .. last frame above the data
+// boundary) where they come up: one row per quantity, band_row doubles, the row's denominator in its last entry.  The
+// rows mirror PEAQ_BAND_SUMMARY_* in include/peaq_amd.h (peaq_batch.hip asserts them).  A kernel argument of the
+// summary instantiation only, like BandArgs.
+enum { kSumNmrSum, kSumNmrMax, kSumNmrDisturbed, kSumExcRef, kSumExcTest, kSumModDiff1, kSumModDiff2, kSumNoiseLoud };
+constexpr int band_summary_rows(bool advanced) { return advanced ? 4 : 8; }   // (the 55-band path has the first four)
+struct SummaryArgs {
+  double* rows;                 // [pair][channel][rows][band_row], 16-byte aligned: the caller's array, and between the
+                                // launches of a run the pair's running rows (loaded at entry, stored at exit)
+  double* saved;                // the same shape (scratch): the rows as they were when the pair last turned tentative
+};
+// after a run's last back-end launch: a pair that ends tentative gets its saved rows back
+hipError_t launch_summary_restore(const PairState* state, int advanced, const SummaryArgs& sum, unsigned n_pairs,
+                                  unsigned pair_doubles, hipStream_t stream);
+
 // ---- pattern back end (time smearing .. MOV accumulation) -------------------
 struct BackendArgs {
   const double* records;        // as written by the front end
@@ -140,9 +156,11 @@ struct BackendArgs {
 // bnd != nullptr (band-trace launches only, never with pts or trc): the bands instantiation, rows per frame (BandArgs)
 // pbd != nullptr (pattern-band launches of the basic version only, never with any of the three): the pattern-bands
 // instantiation, rows per frame (PatternBandArgs)
+// sum != nullptr (summary launches only, never with any of the four): the summary instantiation, running rows per pair
+// (SummaryArgs)
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
                           const TraceArgs* trc = nullptr, const BandArgs* bnd = nullptr,
-                          const PatternBandArgs* pbd = nullptr);
+                          const PatternBandArgs* pbd = nullptr, const SummaryArgs* sum = nullptr);
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h

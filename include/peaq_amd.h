@@ -498,6 +498,69 @@ int peaq_batch_run_pattern_bands (peaq_ctx *ctx, int channels, double playback_l
                                   peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
 /* (peaq_run_pair_pattern_bands, the same for one pair from host memory: after peaq_run_pair_fb_bands below) */
 
+/* ---- band summary: the band traces' values reduced over time on the device, one small row set per pair ----------
+ * A result says how good an item is, a trajectory how the reading developed, a frame trace in which frames the score
+ * was lost, the band traces at which frequency -- at rows per frame.  "In which bands does this coder lose, per item"
+ * needs 109 numbers per item, not 109 per frame: peaq_batch_run_band_summary reduces the per-band values over the
+ * pair's frames in the run that scores the batch, under the accumulators' own gates, and writes R =
+ * peaq_band_summary_rows (advanced) rows of row = peaq_band_row (advanced) doubles per pair and channel:
+ *   d_summary[((p * channels + c) * R + k) * row + b],  b < nb = peaq_band_count (advanced); entry b = nb of every row
+ *   holds that row's denominator.
+ *
+ * Counted frames.  PEAQ_TRACE_ABOVE is defined as in the frame trace (over all channels, flush frame included).  With
+ * A the set of the pair's frames that have it, the counted frames are min A .. max A inclusive -- frames in between
+ * that are not above the data boundary count too -- and none if A is empty.  That is what the reference's
+ * accumulators count (movaccum.c:317-362): nothing before the first frame above the boundary, and a trailing
+ * tentative run dropped.
+ *
+ * Rows.  r, er, et are the values of PEAQ_BAND_NMR / _EXC_REF / _EXC_TEST, the other terms those of PEAQ_PAT_BAND_*:
+ *   k  PEAQ_BAND_SUMMARY_     value at band b < nb                                             entry nb
+ *   0  NMR_SUM                sum over the counted frames of r[b], FP64, in frame order         their number n
+ *   1  NMR_MAX                max over the counted frames of r[b]; 0 if none                    n
+ *   2  NMR_DISTURBED          number of counted frames with r[b] > 1.41253754462275 (1.5 dB,    n
+ *                             the RelDistFrames threshold, per band)
+ *   3  EXC_REF_SUM            sum over the counted frames of er[b]                              n
+ *   4  EXC_TEST_SUM           sum over the counted frames of et[b]                              n
+ *   5  MODDIFF1_WSUM          sum over the counted frames >= 24 (PEAQ_TRACE_MOD_OPEN) of         sum of those W
+ *                             W MODDIFF1[b], W = sum_b MODWT[b] of that frame and channel
+ *                             (the frame trace's ch[c][2])
+ *   6  MODDIFF2_WSUM          the same with MODDIFF2                                            sum of those W
+ *   7  NOISELOUD_SUM          sum over the counted frames with PEAQ_TRACE_LOUD_OPEN of          their number
+ *                             NOISELOUD[b]
+ * The advanced version (its 55-band path) has rows 0 .. 3; rows 4 .. 7 exist in the basic version only.  A pair with no
+ * counted frame reads 0 everywhere, denominators included.  With the MOVs of the same pair (basic version):
+ *   TotalNMR_B   = mean_c 10 log10 (sum_b row0 / (109 n))
+ *   AvgModDiff1_B = mean_c (100 / 109) sum_b row5 / (sum of W);  AvgModDiff2_B likewise with row 6
+ *   sum_b row0 / nb is the sum, over the counted frames, of the frame trace's ch[c][4] (basic) / ch[c][1] (advanced)
+ *   max_b row2 <= (number of disturbed counted frames of the channel) <= sum_b row2
+ *
+ * The call writes every row of the n_pairs pairs completely (no plane mask: a whole summary is 14 KB per stereo pair);
+ * memory past them is left untouched.  d_summary is working memory of the call while it runs -- the pairs' running
+ * rows live there between the launches -- and valid after the stream has been synchronised.  The context keeps a
+ * second array of the same size (the rows as they were when a pair last turned tentative), reserved on the first such
+ * call: PEAQ_ERR_NOMEM if that fails.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs.  PEAQ_ERR_ARG, before a context
+ * or a device is touched and with a message that names the value: d_summary NULL or not 16-byte aligned, and everything
+ * peaq_batch_run refuses.  A run of its own, like the band traces, the trace and the trajectory.  The filter-bank
+ * path's 40 bands have no summary. */
+#define PEAQ_BAND_SUMMARY_NMR_SUM        0
+#define PEAQ_BAND_SUMMARY_NMR_MAX        1
+#define PEAQ_BAND_SUMMARY_NMR_DISTURBED  2
+#define PEAQ_BAND_SUMMARY_EXC_REF_SUM    3
+#define PEAQ_BAND_SUMMARY_EXC_TEST_SUM   4   /* basic version only, like the three below */
+#define PEAQ_BAND_SUMMARY_MODDIFF1_WSUM  5
+#define PEAQ_BAND_SUMMARY_MODDIFF2_WSUM  6
+#define PEAQ_BAND_SUMMARY_NOISELOUD_SUM  7
+
+int peaq_band_summary_rows (int advanced);            /* 8 / 4 */
+int peaq_batch_run_band_summary (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, int n_pairs,
+                                 const float *d_ref, const float *d_test, size_t pair_stride,
+                                 const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                                 double *d_summary /* device */, peaq_result *d_results /* device, may be NULL */,
+                                 void *stream);
+/* (peaq_run_pair_band_summary, the same for one pair from host memory: after peaq_run_pair_pattern_bands below) */
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -694,6 +757,14 @@ int peaq_run_pair_pattern_bands (peaq_ctx *ctx, int channels, double playback_le
                                  const float *ref, size_t n_ref, const float *test, size_t n_test, uint32_t planes,
                                  double *bands /* host */, size_t frame_cap, uint32_t *n_frames,
                                  peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_band_summary (above) for one pair from HOST memory, rows into a host array
+ * [channels][peaq_band_summary_rows (advanced)][peaq_band_row (advanced)]: upload, conversion and alignment as in
+ * peaq_run_pair_pattern_bands; the rows are those of the signals as scored, after conversion and cut.  out (may be
+ * NULL): the pair's result. */
+int peaq_run_pair_band_summary (peaq_ctx *ctx, int advanced, int channels, double playback_level_db,
+                                uint32_t rate, uint32_t max_lag,
+                                const float *ref, size_t n_ref, const float *test, size_t n_test,
+                                double *summary /* host */, peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
