@@ -1,4 +1,5 @@
 """ctypes binding of libpeaq_amd.so (include/peaq_amd.h)."""
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -1697,6 +1698,61 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
                  max_gain_db=max_gain_db)
 
 
+def _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
+                 subsample=False, drift=False, track=False, steps=False, both_lengths=True):
+    """The front the batch_* functions share: convert to 48 kHz, align / match / cut as the keywords ask (_aligned has
+    the order of precedence), hold the tensors against what the library takes, make the host length arrays.
+    both_lengths=False (batch_run, batch_trajectory): n_ref without n_test is left to numpy and the library.
+    Returns ref, test, a_ref, a_test and the two length arguments of the library's entry."""
+    import torch
+    if int(rate) != 48000:
+        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
+    _need_align(subsample, align, drift, track, steps)
+    if steps or track or drift or subsample or gain is not None or align is not None:
+        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
+                                            subsample=bool(subsample), drift=drift, track=track, steps=steps)
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    if both_lengths:
+        assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    len_args = (a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                a_test.ctypes.data_as(u32p) if a_test is not None else None)
+    return ref, test, a_ref, a_test, len_args
+
+
+def _pair_counts(n_pairs, stride, a_ref, a_test, filter_bank=False):
+    """frames (filter_bank: blocks) of every pair of a batch, counted once per distinct pair of lengths"""
+    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
+    cnt = {rt: frame_count(*rt, filter_bank) for rt in set(lens)}
+    return np.array([cnt[rt] for rt in lens], dtype=np.uint32)
+
+
+def _host_pair(ref, test):
+    """the two signals of a run_pair_* call as the library takes them: the arrays, their channel count and the four
+    arguments of the entry"""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    test = np.ascontiguousarray(test, dtype=np.float32)
+    assert test.shape[1] == ref.shape[1]
+    fp = C.POINTER(C.c_float)
+    return ref, test, ref.shape[1], (ref.ctypes.data_as(fp), len(ref), test.ctypes.data_as(fp), len(test))
+
+
+def _lens_48k(ref, test, rate):
+    """the lengths a run_pair_* call's signals have at 48 kHz"""
+    if int(rate) == 48000:
+        return [len(ref), len(test)]
+    return [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
+
+
+def _delay_dict(rec):
+    return dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+
+
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
               stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
               subsample=False, drift=False, track=False, steps=False):
@@ -1718,39 +1774,14 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     aligned part first (estimate_delay, align), after the rate conversion.
     Returns a list of result dicts (sync=True) or the device result tensor."""
     import torch
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align, drift, track, steps)
-    if steps:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            steps=steps)
-    elif track:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            track=track)
-    elif drift:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            drift=drift)
-    elif subsample:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            subsample=True)
-    elif gain is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
-    elif align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample, drift, track, steps,
+                                                      both_lengths=False)
     n_pairs, stride, channels = ref.shape
     if results is None:
         results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    u32p = C.POINTER(C.c_uint32)
     _check(ctx.L.peaq_batch_run(ctx.h, int(bool(advanced)), channels, float(playback_level), n_pairs,
-                                C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                a_test.ctypes.data_as(u32p) if a_test is not None else None,
+                                C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride, *len_args,
                                 stride, C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
     if not sync:
         return results
@@ -1768,31 +1799,14 @@ def batch_trajectory(ctx, advanced, ref, test, interval, n_points, n_ref=None, n
     (points, results): lists of result dicts, points[p][k], (sync=True) or the device tensors [n_pairs, n_points, 16]
     and [n_pairs, 16]."""
     import torch
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align)
-    if subsample:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            subsample=True)
-    elif gain is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
-    elif align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample, both_lengths=False)
     n_pairs, stride, channels = ref.shape
     n_points = int(n_points)
     points = torch.empty((n_pairs, max(n_points, 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
     results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    u32p = C.POINTER(C.c_uint32)
     _check(ctx.L.peaq_batch_run_trajectory(ctx.h, int(bool(advanced)), channels, float(playback_level), n_pairs,
-                                           C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                           a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                           a_test.ctypes.data_as(u32p) if a_test is not None else None,
+                                           C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride, *len_args,
                                            stride, int(interval), n_points, C.c_void_p(points.data_ptr()),
                                            C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
     if not sync:
@@ -1857,28 +1871,11 @@ def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_leve
     field name, FRAME_TRACE_DTYPE / BLOCK_TRACE_DTYPE, [n_pairs, stride]) and results (result dicts)."""
     import torch
     _check_trace_sizes(ctx.L)
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    _need_align(subsample, align)
-    if subsample:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            subsample=True)
-    elif gain is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db)
-    elif align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample)
     n_pairs, stride, channels = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
-    cnt = {rt: (frame_count(*rt), frame_count(*rt, True) if advanced else 0) for rt in set(lens)}   # once per distinct pair of lengths
-    n_frames = np.array([cnt[rt][0] for rt in lens], dtype=np.uint32)
-    n_blocks = np.array([cnt[rt][1] for rt in lens], dtype=np.uint32)
+    n_frames = _pair_counts(n_pairs, stride, a_ref, a_test)
+    n_blocks = _pair_counts(n_pairs, stride, a_ref, a_test, True) if advanced else np.zeros(n_pairs, dtype=np.uint32)
     f_stride = max(int(n_frames.max()) if n_pairs else 0, 1)
     b_stride = max(int(n_blocks.max()) if n_pairs else 0, 1)
     with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
@@ -1891,11 +1888,8 @@ def batch_trace(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_leve
         assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3
         assert t.shape[0] == n_pairs and t.shape[2] == size
     f_stride, b_stride = d_frames.shape[1], d_blocks.shape[1] if advanced else 0
-    u32p = C.POINTER(C.c_uint32)
     _check(ctx.L.peaq_batch_run_trace(ctx.h, int(bool(advanced)), channels, float(playback_level), n_pairs,
-                                      C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                      a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                      a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                      C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride, *len_args, stride,
                                       C.c_void_p(d_frames.data_ptr()), f_stride,
                                       C.c_void_p(d_blocks.data_ptr()) if advanced else None, b_stride,
                                       C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
@@ -1914,61 +1908,155 @@ def run_pair_trace(ctx, advanced, ref, test, playback_level=92.0, rate=48000, al
     first with align = a max_lag in 48 kHz samples.  Returns a dict: frames / blocks (numpy structured arrays
     FRAME_TRACE_DTYPE / BLOCK_TRACE_DTYPE of the counts written; blocks None in the basic version), result (a result
     dict) and, with align, delay."""
-    ref = np.ascontiguousarray(ref, dtype=np.float32)
-    test = np.ascontiguousarray(test, dtype=np.float32)
-    ch = ref.shape[1]
-    assert test.shape[1] == ch
+    ref, test, ch, pair_args = _host_pair(ref, test)
     _check_trace_sizes(ctx.L)
-    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
+    lens = _lens_48k(ref, test, rate)
     f_cap = max(frame_count(*lens), 1)
     b_cap = max(frame_count(*lens, True), 1) if advanced else 0
     frames = np.zeros(f_cap, dtype=FRAME_TRACE_DTYPE)
     blocks = np.zeros(b_cap, dtype=BLOCK_TRACE_DTYPE) if advanced else None
     nf, nb, rec, out = C.c_uint32(0), C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
     _check(ctx.L.peaq_run_pair_trace(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),
-                                     0 if align is None else int(align),
-                                     ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
-                                     test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                     0 if align is None else int(align), *pair_args,
                                      C.c_void_p(frames.ctypes.data), f_cap, C.byref(nf),
                                      C.c_void_p(blocks.ctypes.data) if advanced else None, b_cap, C.byref(nb),
                                      C.byref(rec), out.ctypes.data_as(C.POINTER(C.c_double))))
     res = dict(frames=frames[:nf.value], blocks=blocks[:nb.value] if advanced else None,
                result=_result_dict(out, bool(advanced)))
     if align is not None:
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
     return res
 
 
-def band_planes_mask(planes):
-    """a PEAQ_BAND_* mask from plane names (BAND_PLANES; one name, or several in any order) or from a mask"""
+def _planes_mask(planes, table, what):
     if isinstance(planes, (int, np.integer)):
         return int(planes)
     if isinstance(planes, str):
         planes = [planes]
-    unknown = [p for p in planes if p not in BAND_PLANES]
+    unknown = [p for p in planes if p not in table]
     if unknown:
-        raise PeaqError(f"unknown band plane {unknown[0]!r} (one of {', '.join(BAND_PLANES)})")
+        raise PeaqError(f"unknown {what} {unknown[0]!r} (one of {', '.join(table)})")
     mask = 0
     for p in planes:
-        mask |= BAND_PLANES[p]
+        mask |= table[p]
     return mask
+
+
+def _planes_dict(rows, mask, table, n_bands):
+    """rows [..., n_planes, row] -> {name: [..., n_bands]} in the order of the slots, the pad column (if any) removed"""
+    names = [name for name, bit in table.items() if mask & bit]
+    return {name: rows[..., k, :n_bands] for k, name in enumerate(names)}
+
+
+def _band_tables(entry, n):
+    fc, second = np.zeros(n), np.zeros(n)
+    dp = C.POINTER(C.c_double)
+    _check(entry(fc.ctypes.data_as(dp), second.ctypes.data_as(dp)))
+    return fc, second
+
+
+def band_planes_mask(planes):
+    """a PEAQ_BAND_* mask from plane names (BAND_PLANES; one name, or several in any order) or from a mask"""
+    return _planes_mask(planes, BAND_PLANES, "band plane")
 
 
 def band_tables(advanced):
     """(fc, mask_diff): the centre frequencies in Hz and the mask_diff factors of the 109 (advanced: 55) bands of the
     FFT path (peaq_band_tables; host only)"""
+    L, adv = load_library(), int(bool(advanced))
+    return _band_tables(lambda *a: L.peaq_band_tables(adv, *a), L.peaq_band_count(adv))
+
+
+def fb_band_planes_mask(planes):
+    """a PEAQ_FB_BAND_* mask from plane names (FB_BAND_PLANES; one name, or several in any order) or from a mask"""
+    return _planes_mask(planes, FB_BAND_PLANES, "filter-bank band plane")
+
+
+def fb_band_tables():
+    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 40 bands of the filter-bank
+    path (peaq_fb_band_tables; host only)"""
     L = load_library()
-    n = L.peaq_band_count(int(bool(advanced)))
-    fc, md = np.zeros(n), np.zeros(n)
-    dp = C.POINTER(C.c_double)
-    _check(L.peaq_band_tables(int(bool(advanced)), fc.ctypes.data_as(dp), md.ctypes.data_as(dp)))
-    return fc, md
+    return _band_tables(L.peaq_fb_band_tables, L.peaq_fb_band_count())
 
 
-def _band_planes_dict(rows, mask, n_bands):
-    """rows [..., n_planes, row] -> {name: [..., n_bands]} in the order of the slots, the pad column removed"""
-    names = [name for name, bit in BAND_PLANES.items() if mask & bit]
-    return {name: rows[..., k, :n_bands] for k, name in enumerate(names)}
+def pattern_band_planes_mask(planes):
+    """a PEAQ_PAT_BAND_* mask from plane names (PATTERN_BAND_PLANES; one name, or several in any order) or from a mask"""
+    return _planes_mask(planes, PATTERN_BAND_PLANES, "pattern band plane")
+
+
+def pattern_band_tables():
+    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 109 bands of the basic
+    version's FFT path (peaq_pattern_band_tables; host only)"""
+    L = load_library()
+    return _band_tables(L.peaq_pattern_band_tables, L.peaq_band_count(0))
+
+
+# What tells the three band-row outputs apart (FFT bands, filter-bank bands, pattern bands; _batch_band_rows and
+# _run_pair_band_rows are their common bodies): the plane table, its word in messages and its valid bits; whether a row
+# is a filter-bank block (else an FFT frame); the version it runs in (None: the entry takes `advanced`); (L, adv) ->
+# (band count, row width in doubles); the library entry less its prefix; the tables function and its second key.
+_BandRows = collections.namedtuple("_BandRows", "planes what all_bits blocks advanced shape entry tables second")
+_BAND_ROWS = dict(
+    fft=_BandRows(BAND_PLANES, "band plane", 31, False, None, lambda L, adv: (L.peaq_band_count(adv), L.peaq_band_row(adv)),
+                  "bands", band_tables, "mask_diff"),
+    fb=_BandRows(FB_BAND_PLANES, "filter-bank band plane", 0x1FFF, True, True, lambda L, adv: (L.peaq_fb_band_count(),) * 2,
+                 "fb_bands", lambda adv: fb_band_tables(), "internal_noise"),
+    pattern=_BandRows(PATTERN_BAND_PLANES, "pattern band plane", 0x1FFF, False, False,
+                      lambda L, adv: (L.peaq_band_count(0), L.peaq_band_row(0)), "pattern_bands",
+                      lambda adv: pattern_band_tables(), "internal_noise"))
+
+
+def _batch_band_rows(kind, ctx, advanced, ref, test, planes, n_ref, n_test, playback_level, rate, align, stream, sync, d_bands):
+    """batch_bands, batch_fb_bands and batch_pattern_bands (their docstrings have the arguments and what is returned)"""
+    import torch
+    k = _BAND_ROWS[kind]
+    mask = _planes_mask(planes, k.planes, k.what)
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream)
+    n_pairs, stride, channels = ref.shape
+    counts = _pair_counts(n_pairs, stride, a_ref, a_test, k.blocks)
+    adv = int(bool(advanced)) if k.advanced is None else int(k.advanced)
+    (n_bands, row), n_planes = k.shape(ctx.L, adv), bin(mask & k.all_bits).count("1")
+    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
+        if d_bands is None:
+            d_bands = torch.zeros((n_pairs, max(int(counts.max()) if n_pairs else 0, 1), channels, max(n_planes, 1), row),
+                                  dtype=torch.float64, device=ref.device)
+        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
+    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), row)
+    _check(getattr(ctx.L, "peaq_batch_run_" + k.entry)(
+        ctx.h, *((adv,) if k.advanced is None else ()), channels, float(playback_level), n_pairs,
+        C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride, *len_args, stride, mask,
+        C.c_void_p(d_bands.data_ptr()), d_bands.shape[1], C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    fc, second = k.tables(adv)
+    out = {"d_bands": d_bands, "d_results": results, "counts": counts, "fc": fc, k.second: second, "planes": mask}
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    out.update(_planes_dict(d_bands.cpu().numpy(), mask, k.planes, n_bands))
+    out["results"] = [_result_dict(r, advanced if k.advanced is None else k.advanced) for r in results.cpu().numpy()]
+    return out
+
+
+def _run_pair_band_rows(kind, ctx, advanced, ref, test, planes, playback_level, rate, align):
+    """run_pair_bands, run_pair_fb_bands and run_pair_pattern_bands"""
+    k = _BAND_ROWS[kind]
+    ref, test, ch, pair_args = _host_pair(ref, test)
+    mask = _planes_mask(planes, k.planes, k.what)
+    adv = int(bool(advanced)) if k.advanced is None else int(k.advanced)
+    cap = max(frame_count(*_lens_48k(ref, test, rate), k.blocks), 1)
+    n_bands, row = k.shape(ctx.L, adv)
+    rows = np.zeros((cap, ch, max(bin(mask & k.all_bits).count("1"), 1), row))
+    n, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
+    _check(getattr(ctx.L, "peaq_run_pair_" + k.entry)(
+        ctx.h, *((adv,) if k.advanced is None else ()), ch, float(playback_level), int(rate),
+        0 if align is None else int(align), *pair_args, mask, C.c_void_p(rows.ctypes.data), cap, C.byref(n), C.byref(rec),
+        out.ctypes.data_as(C.POINTER(C.c_double))))
+    fc, second = k.tables(adv)
+    res = {**_planes_dict(rows[:n.value], mask, k.planes, n_bands), "result": _result_dict(out, bool(adv)), "fc": fc,
+           k.second: second, "planes": mask}
+    if align is not None:
+        res["delay"] = _delay_dict(rec)
+    return res
 
 
 def batch_bands(ctx, advanced, ref, test, planes=("nmr",), n_ref=None, n_test=None, playback_level=92.0, rate=48000,
@@ -1982,106 +2070,15 @@ def batch_bands(ctx, advanced, ref, test, planes=("nmr",), n_ref=None, n_test=No
     removed), counts (numpy, frames per pair), results (result dicts), fc and mask_diff (band_tables), planes (the
     mask), and d_bands / d_results, the device tensors.  sync=False: the device tensors, counts, fc, mask_diff and
     planes only."""
-    import torch
-    mask = band_planes_mask(planes)
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
-    n_pairs, stride, channels = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
-    cnt = {rt: frame_count(*rt) for rt in set(lens)}   # once per distinct pair of lengths
-    counts = np.array([cnt[rt] for rt in lens], dtype=np.uint32)
-    adv = int(bool(advanced))
-    n_bands, row, n_planes = ctx.L.peaq_band_count(adv), ctx.L.peaq_band_row(adv), bin(mask & 31).count("1")
-    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
-        if d_bands is None:
-            f_stride = max(int(counts.max()) if n_pairs else 0, 1)
-            d_bands = torch.zeros((n_pairs, f_stride, channels, max(n_planes, 1), row), dtype=torch.float64, device=ref.device)
-        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
-    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), row)
-    u32p = C.POINTER(C.c_uint32)
-    _check(ctx.L.peaq_batch_run_bands(ctx.h, adv, channels, float(playback_level), n_pairs,
-                                      C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                      a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                      a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
-                                      mask, C.c_void_p(d_bands.data_ptr()), d_bands.shape[1],
-                                      C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
-    fc, md = band_tables(adv)
-    out = dict(d_bands=d_bands, d_results=results, counts=counts, fc=fc, mask_diff=md, planes=mask)
-    if not sync:
-        return out
-    torch.cuda.synchronize(ref.device)
-    out.update(_band_planes_dict(d_bands.cpu().numpy(), mask, n_bands))
-    out["results"] = [_result_dict(r, advanced) for r in results.cpu().numpy()]
-    return out
+    return _batch_band_rows("fft", ctx, advanced, ref, test, planes, n_ref, n_test, playback_level, rate, align, stream,
+                            sync, d_bands)
 
 
 def run_pair_bands(ctx, advanced, ref, test, planes=("nmr",), playback_level=92.0, rate=48000, align=None):
     """peaq_run_pair_bands: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
     first with align = a max_lag in 48 kHz samples.  Returns a dict: every requested plane by name, np.ndarray
     [frames, channels, bands], result (a result dict), fc, mask_diff, planes (the mask) and, with align, delay."""
-    ref = np.ascontiguousarray(ref, dtype=np.float32)
-    test = np.ascontiguousarray(test, dtype=np.float32)
-    ch = ref.shape[1]
-    assert test.shape[1] == ch
-    mask, adv = band_planes_mask(planes), int(bool(advanced))
-    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
-    f_cap = max(frame_count(*lens), 1)
-    n_bands, row = ctx.L.peaq_band_count(adv), ctx.L.peaq_band_row(adv)
-    rows = np.zeros((f_cap, ch, max(bin(mask & 31).count("1"), 1), row))
-    nf, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
-    _check(ctx.L.peaq_run_pair_bands(ctx.h, adv, ch, float(playback_level), int(rate), 0 if align is None else int(align),
-                                     ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
-                                     test.ctypes.data_as(C.POINTER(C.c_float)), len(test), mask,
-                                     C.c_void_p(rows.ctypes.data), f_cap, C.byref(nf), C.byref(rec),
-                                     out.ctypes.data_as(C.POINTER(C.c_double))))
-    fc, md = band_tables(adv)
-    res = dict(_band_planes_dict(rows[:nf.value], mask, n_bands), result=_result_dict(out, bool(advanced)), fc=fc,
-               mask_diff=md, planes=mask)
-    if align is not None:
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
-    return res
-
-
-def fb_band_planes_mask(planes):
-    """a PEAQ_FB_BAND_* mask from plane names (FB_BAND_PLANES; one name, or several in any order) or from a mask"""
-    if isinstance(planes, (int, np.integer)):
-        return int(planes)
-    if isinstance(planes, str):
-        planes = [planes]
-    unknown = [p for p in planes if p not in FB_BAND_PLANES]
-    if unknown:
-        raise PeaqError(f"unknown filter-bank band plane {unknown[0]!r} (one of {', '.join(FB_BAND_PLANES)})")
-    mask = 0
-    for p in planes:
-        mask |= FB_BAND_PLANES[p]
-    return mask
-
-
-def fb_band_tables():
-    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 40 bands of the filter-bank
-    path (peaq_fb_band_tables; host only)"""
-    L = load_library()
-    n = L.peaq_fb_band_count()
-    fc, noise = np.zeros(n), np.zeros(n)
-    dp = C.POINTER(C.c_double)
-    _check(L.peaq_fb_band_tables(fc.ctypes.data_as(dp), noise.ctypes.data_as(dp)))
-    return fc, noise
-
-
-def _fb_band_planes_dict(rows, mask):
-    """rows [..., n_planes, 40] -> {name: [..., 40]} in the order of the slots"""
-    names = [name for name, bit in FB_BAND_PLANES.items() if mask & bit]
-    return {name: rows[..., k, :] for k, name in enumerate(names)}
+    return _run_pair_band_rows("fft", ctx, advanced, ref, test, planes, playback_level, rate, align)
 
 
 def batch_fb_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_test=None, playback_level=92.0, rate=48000,
@@ -2094,104 +2091,15 @@ def batch_fb_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_test=Non
     Returns a dict: every requested plane by name, np.ndarray [pairs, blocks_max, channels, 40], counts (numpy, blocks
     per pair), results (result dicts), fc and internal_noise (fb_band_tables), planes (the mask), and d_bands /
     d_results, the device tensors.  sync=False: the device tensors, counts, fc, internal_noise and planes only."""
-    import torch
-    mask = fb_band_planes_mask(planes)
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
-    n_pairs, stride, channels = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
-    cnt = {rt: frame_count(*rt, True) for rt in set(lens)}   # once per distinct pair of lengths
-    counts = np.array([cnt[rt] for rt in lens], dtype=np.uint32)
-    n_bands, n_planes = ctx.L.peaq_fb_band_count(), bin(mask & 0x1FFF).count("1")
-    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
-        if d_bands is None:
-            b_stride = max(int(counts.max()) if n_pairs else 0, 1)
-            d_bands = torch.zeros((n_pairs, b_stride, channels, max(n_planes, 1), n_bands), dtype=torch.float64, device=ref.device)
-        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
-    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), n_bands)
-    u32p = C.POINTER(C.c_uint32)
-    _check(ctx.L.peaq_batch_run_fb_bands(ctx.h, channels, float(playback_level), n_pairs,
-                                         C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                         a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                         a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
-                                         mask, C.c_void_p(d_bands.data_ptr()), d_bands.shape[1],
-                                         C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
-    fc, noise = fb_band_tables()
-    out = dict(d_bands=d_bands, d_results=results, counts=counts, fc=fc, internal_noise=noise, planes=mask)
-    if not sync:
-        return out
-    torch.cuda.synchronize(ref.device)
-    out.update(_fb_band_planes_dict(d_bands.cpu().numpy(), mask))
-    out["results"] = [_result_dict(r, True) for r in results.cpu().numpy()]
-    return out
+    return _batch_band_rows("fb", ctx, True, ref, test, planes, n_ref, n_test, playback_level, rate, align, stream, sync,
+                            d_bands)
 
 
 def run_pair_fb_bands(ctx, ref, test, planes=("noiseloud",), playback_level=92.0, rate=48000, align=None):
     """peaq_run_pair_fb_bands: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
     first with align = a max_lag in 48 kHz samples.  Returns a dict: every requested plane by name, np.ndarray
     [blocks, channels, 40], result (a result dict), fc, internal_noise, planes (the mask) and, with align, delay."""
-    ref = np.ascontiguousarray(ref, dtype=np.float32)
-    test = np.ascontiguousarray(test, dtype=np.float32)
-    ch = ref.shape[1]
-    assert test.shape[1] == ch
-    mask = fb_band_planes_mask(planes)
-    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
-    b_cap = max(frame_count(*lens, True), 1)
-    rows = np.zeros((b_cap, ch, max(bin(mask & 0x1FFF).count("1"), 1), ctx.L.peaq_fb_band_count()))
-    nb, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
-    _check(ctx.L.peaq_run_pair_fb_bands(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
-                                        ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
-                                        test.ctypes.data_as(C.POINTER(C.c_float)), len(test), mask,
-                                        C.c_void_p(rows.ctypes.data), b_cap, C.byref(nb), C.byref(rec),
-                                        out.ctypes.data_as(C.POINTER(C.c_double))))
-    fc, noise = fb_band_tables()
-    res = dict(_fb_band_planes_dict(rows[:nb.value], mask), result=_result_dict(out, True), fc=fc,
-               internal_noise=noise, planes=mask)
-    if align is not None:
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
-    return res
-
-
-def pattern_band_planes_mask(planes):
-    """a PEAQ_PAT_BAND_* mask from plane names (PATTERN_BAND_PLANES; one name, or several in any order) or from a mask"""
-    if isinstance(planes, (int, np.integer)):
-        return int(planes)
-    if isinstance(planes, str):
-        planes = [planes]
-    unknown = [p for p in planes if p not in PATTERN_BAND_PLANES]
-    if unknown:
-        raise PeaqError(f"unknown pattern band plane {unknown[0]!r} (one of {', '.join(PATTERN_BAND_PLANES)})")
-    mask = 0
-    for p in planes:
-        mask |= PATTERN_BAND_PLANES[p]
-    return mask
-
-
-def pattern_band_tables():
-    """(fc, internal_noise): the centre frequencies in Hz and the internal noise of the 109 bands of the basic
-    version's FFT path (peaq_pattern_band_tables; host only)"""
-    L = load_library()
-    n = L.peaq_band_count(0)
-    fc, noise = np.zeros(n), np.zeros(n)
-    dp = C.POINTER(C.c_double)
-    _check(L.peaq_pattern_band_tables(fc.ctypes.data_as(dp), noise.ctypes.data_as(dp)))
-    return fc, noise
-
-
-def _pattern_band_planes_dict(rows, mask, n_bands):
-    """rows [..., n_planes, 110] -> {name: [..., 109]} in the order of the slots, the pad column removed"""
-    names = [name for name, bit in PATTERN_BAND_PLANES.items() if mask & bit]
-    return {name: rows[..., k, :n_bands] for k, name in enumerate(names)}
+    return _run_pair_band_rows("fb", ctx, True, ref, test, planes, playback_level, rate, align)
 
 
 def batch_pattern_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_test=None, playback_level=92.0, rate=48000,
@@ -2205,73 +2113,15 @@ def batch_pattern_bands(ctx, ref, test, planes=("noiseloud",), n_ref=None, n_tes
     removed), counts (numpy, frames per pair), results (result dicts), fc and internal_noise (pattern_band_tables),
     planes (the mask), and d_bands / d_results, the device tensors.  sync=False: the device tensors, counts, fc,
     internal_noise and planes only."""
-    import torch
-    mask = pattern_band_planes_mask(planes)
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
-    n_pairs, stride, channels = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
-    lens = [(stride, stride)] * n_pairs if a_ref is None else list(zip(a_ref.tolist(), a_test.tolist()))
-    cnt = {rt: frame_count(*rt) for rt in set(lens)}   # once per distinct pair of lengths
-    counts = np.array([cnt[rt] for rt in lens], dtype=np.uint32)
-    n_bands, row, n_planes = ctx.L.peaq_band_count(0), ctx.L.peaq_band_row(0), bin(mask & 0x1FFF).count("1")
-    with _torch_stream(stream):                        # the zero fill runs on the stream the batch runs on
-        if d_bands is None:
-            f_stride = max(int(counts.max()) if n_pairs else 0, 1)
-            d_bands = torch.zeros((n_pairs, f_stride, channels, max(n_planes, 1), row), dtype=torch.float64, device=ref.device)
-        results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    assert d_bands.is_cuda and d_bands.dtype == torch.float64 and d_bands.is_contiguous() and d_bands.dim() == 5
-    assert d_bands.shape[0] == n_pairs and tuple(d_bands.shape[2:]) == (channels, max(n_planes, 1), row)
-    u32p = C.POINTER(C.c_uint32)
-    _check(ctx.L.peaq_batch_run_pattern_bands(ctx.h, channels, float(playback_level), n_pairs,
-                                              C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                              a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                              a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
-                                              mask, C.c_void_p(d_bands.data_ptr()), d_bands.shape[1],
-                                              C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
-    fc, noise = pattern_band_tables()
-    out = dict(d_bands=d_bands, d_results=results, counts=counts, fc=fc, internal_noise=noise, planes=mask)
-    if not sync:
-        return out
-    torch.cuda.synchronize(ref.device)
-    out.update(_pattern_band_planes_dict(d_bands.cpu().numpy(), mask, n_bands))
-    out["results"] = [_result_dict(r, False) for r in results.cpu().numpy()]
-    return out
+    return _batch_band_rows("pattern", ctx, False, ref, test, planes, n_ref, n_test, playback_level, rate, align, stream,
+                            sync, d_bands)
 
 
 def run_pair_pattern_bands(ctx, ref, test, planes=("noiseloud",), playback_level=92.0, rate=48000, align=None):
     """peaq_run_pair_pattern_bands: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`,
     aligned first with align = a max_lag in 48 kHz samples.  Returns a dict: every requested plane by name, np.ndarray
     [frames, channels, 109], result (a result dict), fc, internal_noise, planes (the mask) and, with align, delay."""
-    ref = np.ascontiguousarray(ref, dtype=np.float32)
-    test = np.ascontiguousarray(test, dtype=np.float32)
-    ch = ref.shape[1]
-    assert test.shape[1] == ch
-    mask = pattern_band_planes_mask(planes)
-    lens = [len(ref), len(test)] if int(rate) == 48000 else [resampled_length(len(ref), rate), resampled_length(len(test), rate)]
-    f_cap = max(frame_count(*lens), 1)
-    n_bands, row = ctx.L.peaq_band_count(0), ctx.L.peaq_band_row(0)
-    rows = np.zeros((f_cap, ch, max(bin(mask & 0x1FFF).count("1"), 1), row))
-    nf, rec, out = C.c_uint32(0), Delay(), np.zeros(RESULT_DOUBLES)
-    _check(ctx.L.peaq_run_pair_pattern_bands(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
-                                             ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
-                                             test.ctypes.data_as(C.POINTER(C.c_float)), len(test), mask,
-                                             C.c_void_p(rows.ctypes.data), f_cap, C.byref(nf), C.byref(rec),
-                                             out.ctypes.data_as(C.POINTER(C.c_double))))
-    fc, noise = pattern_band_tables()
-    res = dict(_pattern_band_planes_dict(rows[:nf.value], mask, n_bands), result=_result_dict(out, False), fc=fc,
-               internal_noise=noise, planes=mask)
-    if align is not None:
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
-    return res
+    return _run_pair_band_rows("pattern", ctx, False, ref, test, planes, playback_level, rate, align)
 
 
 def _band_summary_views(rows, n_bands):
@@ -2309,18 +2159,8 @@ def batch_band_summary(ctx, advanced, ref, test, n_ref=None, n_test=None, playba
     tensors and fc only."""
     import torch
     advanced = bool(advanced)
-    if int(rate) != 48000:
-        ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
-    if align is not None:
-        ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream)
-    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
-    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream)
     n_pairs, stride, channels = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = a_test = None
-    if n_ref is not None:
-        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
-        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
     n_bands, row, n_rows = ctx.L.peaq_band_count(advanced), ctx.L.peaq_band_row(advanced), ctx.L.peaq_band_summary_rows(advanced)
     with _torch_stream(stream):
         if d_summary is None:
@@ -2330,12 +2170,9 @@ def batch_band_summary(ctx, advanced, ref, test, n_ref=None, n_test=None, playba
     assert d_summary.is_cuda and d_summary.dtype == torch.float64 and d_summary.is_contiguous() and d_summary.dim() == 4
     assert d_summary.shape[0] >= n_pairs and tuple(d_summary.shape[1:]) == (channels, n_rows, row)
     assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
-    u32p = C.POINTER(C.c_uint32)
     _check(ctx.L.peaq_batch_run_band_summary(ctx.h, int(advanced), channels, float(playback_level), n_pairs,
                                              C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
-                                             a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
-                                             a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
-                                             C.c_void_p(d_summary.data_ptr()), C.c_void_p(results.data_ptr()),
+                                             *len_args, stride, C.c_void_p(d_summary.data_ptr()), C.c_void_p(results.data_ptr()),
                                              _stream_ptr(stream)))
     fc, _ = band_tables(advanced)
     out = dict(d_summary=d_summary, d_results=results, fc=fc)
@@ -2352,24 +2189,19 @@ def run_pair_band_summary(ctx, advanced, ref, test, playback_level=92.0, rate=48
     """peaq_run_pair_band_summary: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`,
     aligned first with align = a max_lag in 48 kHz samples.  Returns a dict: rows [channels, R, row], the named views of
     batch_band_summary [channels, bands], counted [channels], fc, result (a result dict) and, with align, delay."""
-    ref = np.ascontiguousarray(ref, dtype=np.float32)
-    test = np.ascontiguousarray(test, dtype=np.float32)
+    ref, test, ch, pair_args = _host_pair(ref, test)
     advanced = bool(advanced)
-    ch = ref.shape[1]
-    assert test.shape[1] == ch
     n_bands, row, n_rows = ctx.L.peaq_band_count(advanced), ctx.L.peaq_band_row(advanced), ctx.L.peaq_band_summary_rows(advanced)
     rows = np.zeros((ch, n_rows, row))
     rec, out = Delay(), np.zeros(RESULT_DOUBLES)
     _check(ctx.L.peaq_run_pair_band_summary(ctx.h, int(advanced), ch, float(playback_level), int(rate),
-                                            0 if align is None else int(align),
-                                            ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
-                                            test.ctypes.data_as(C.POINTER(C.c_float)), len(test),
+                                            0 if align is None else int(align), *pair_args,
                                             C.c_void_p(rows.ctypes.data), C.byref(rec),
                                             out.ctypes.data_as(C.POINTER(C.c_double))))
     fc, _ = band_tables(advanced)
     res = dict(rows=rows, fc=fc, result=_result_dict(out, advanced), **_band_summary_views(rows, n_bands))
     if align is not None:
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
     return res
 
 
@@ -2407,7 +2239,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                          C.byref(trec), C.byref(prec), found.ctypes.data_as(C.POINTER(Step)), len(found),
                                          C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
         res = _result_dict(out, bool(advanced))
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
         res["track"] = {k: getattr(trec, k) for k, _ in Track._fields_}
         res["pieces"] = {k: getattr(prec, k) for k, _ in Pieces._fields_}
         res["steps"] = found[:min(len(found), prec.n_candidates)].copy()
@@ -2422,7 +2254,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                          test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
                                          C.byref(trec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
         res = _result_dict(out, bool(advanced))
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
         res["track"] = {k: getattr(trec, k) for k, _ in Track._fields_}
         if gain is not None:
             res["gain"] = _gain_dict(grec)
@@ -2435,7 +2267,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                          test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
                                          C.byref(drec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
         res = _result_dict(out, bool(advanced))
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
         res["drift"] = dict(lag0=int(drec.lag0), flags=int(drec.flags), a=drec.a, e=drec.e, ppm=drec.ppm,
                             resid_rms=drec.resid_rms, n_windows=int(drec.n_windows), n_valid=int(drec.n_valid))
         if gain is not None:
@@ -2449,7 +2281,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                              test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
                                              C.byref(srec), C.byref(grec), out.ctypes.data_as(C.POINTER(C.c_double))))
         res = _result_dict(out, bool(advanced))
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
         res["subdelay"] = _subdelay_dict(srec)
         if gain is not None:
             res["gain"] = _gain_dict(grec)
@@ -2464,7 +2296,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
         res = _result_dict(out, bool(advanced))
         res["gain"] = _gain_dict(grec)
         if align is not None:
-            res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+            res["delay"] = _delay_dict(rec)
         return res
     if align is not None:
         rec = Delay()
@@ -2473,7 +2305,7 @@ def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=No
                                            test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(rec),
                                            out.ctypes.data_as(C.POINTER(C.c_double))))
         res = _result_dict(out, bool(advanced))
-        res["delay"] = dict(lag=int(rec.lag), peak=rec.peak, runner_up=rec.runner_up, norm=rec.norm)
+        res["delay"] = _delay_dict(rec)
         return res
     if int(rate) != 48000:
         _check(ctx.L.peaq_run_pair_rate(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate),

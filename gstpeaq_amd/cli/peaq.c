@@ -664,197 +664,34 @@ done:
   return rc;
 }
 
-/* the planes of --bands=FILE[:PLANES] by name, in the order of their bits (PEAQ_BAND_*) */
-static const char *const band_plane_names[5] = { "nmr", "exc_ref", "exc_test", "detect", "steps" };
-
-/* a comma-separated list of plane names -> mask; 0 if a name is not one */
-static uint32_t
-parse_band_planes (const char *list)
-{
-  uint32_t mask = 0;
-  while (*list) {
-    const size_t n = strcspn (list, ",");
-    int k, hit = -1;
-    for (k = 0; k < 5; k++)
-      if (strlen (band_plane_names[k]) == n && !strncmp (list, band_plane_names[k], n))
-        hit = k;
-    if (hit < 0)
-      return 0;
-    mask |= 1u << hit;
-    list += n;
-    if (*list == ',' && !*++list)
-      return 0;
-  }
-  return mask;
-}
-
-/* --bands=FILE[:PLANES]: the pair through peaq_run_pair_bands, its rows as CSV -- a header line (frame, channel, plane,
- * then the bands' centre frequencies in Hz), then one line per (frame, channel, plane) with the band values; every
- * value as %.17g, which reads back to the same double.  Prints the delay line of --align. */
-static int
-write_bands (const char *path, uint32_t planes, peaq_ctx *ctx, int advanced, double level, uint32_t rate, uint32_t align_lag,
-    const wav_t *ref, const wav_t *test, peaq_result *r)
-{
-  const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
-    rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
-  const size_t frame_cap = (size_t) peaq_frame_count (n48[0], n48[1], 0) + 1;
-  const int count = peaq_band_count (advanced), row = peaq_band_row (advanced), ch = ref->channels;
-  int n_planes = 0, c, k, b, slot, rc = 1;
-  double *rows, *fc;
-  uint32_t nf = 0, f;
-  peaq_delay delay;
-  FILE *out;
-  for (k = 0; k < 5; k++)
-    n_planes += (planes >> k) & 1;
-  rows = malloc (frame_cap * ch * (n_planes ? n_planes : 1) * row * sizeof *rows);
-  fc = malloc (count * sizeof *fc);
-  if (!rows || !fc) {
-    printf ("Error: out of memory for the band trace\n");
-    goto done;
-  }
-  if (peaq_band_tables (advanced, fc, NULL) != PEAQ_OK ||
-      peaq_run_pair_bands (ctx, advanced, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
-          planes, rows, frame_cap, &nf, &delay, r) != PEAQ_OK) {
-    printf ("Error: %s\n", peaq_last_error ());
-    goto done;
-  }
-  if (align_lag)
-    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
-  if (!(out = fopen (path, "w"))) {
-    printf ("Error: cannot write %s\n", path);
-    goto done;
-  }
-  fprintf (out, "frame,channel,plane");
-  for (b = 0; b < count; b++)
-    fprintf (out, ",%.17g", fc[b]);
-  fprintf (out, "\n");
-  for (f = 0; f < nf; f++)
-    for (c = 0; c < ch; c++)
-      for (k = 0, slot = 0; k < 5; k++) {
-        const double *v;
-        if (!((planes >> k) & 1))
-          continue;
-        v = rows + (((size_t) f * ch + c) * n_planes + slot++) * row;
-        fprintf (out, "%u,%d,%s", f, c, band_plane_names[k]);
-        for (b = 0; b < count; b++)
-          fprintf (out, ",%.17g", v[b]);
-        fprintf (out, "\n");
-      }
-  if (fclose (out)) {
-    printf ("Error: cannot write %s\n", path);
-    goto done;
-  }
-  rc = 0;
-done:
-  free (rows);
-  free (fc);
-  return rc;
-}
-
-/* the planes of --fb-bands=FILE[:PLANES] by name, in the order of their bits (PEAQ_FB_BAND_*) */
-enum { n_fb_band_planes = 13 };
-static const char *const fb_band_plane_names[n_fb_band_planes] = { "moddiff", "modwt", "noiseloud", "missing", "lindist",
+/* The three band-row outputs, --bands, --fb-bands and --pattern-bands =FILE[:PLANES]: the planes of each by name, in the
+ * order of their bits (PEAQ_BAND_*, PEAQ_FB_BAND_*, PEAQ_PAT_BAND_*), and what a row of each is counted in. */
+enum band_kind { BANDS_FFT, BANDS_FB, BANDS_PATTERN };
+static const char *const band_plane_names[] = { "nmr", "exc_ref", "exc_test", "detect", "steps" };
+static const char *const fb_band_plane_names[] = { "moddiff", "modwt", "noiseloud", "missing", "lindist",
   "unsm_ref", "unsm_test", "exc_ref", "exc_test", "adapt_ref", "adapt_test", "mod_ref", "mod_test" };
-
-/* a comma-separated list of plane names -> mask; 0 if a name is not one */
-static uint32_t
-parse_fb_band_planes (const char *list)
-{
-  uint32_t mask = 0;
-  while (*list) {
-    const size_t n = strcspn (list, ",");
-    int k, hit = -1;
-    for (k = 0; k < n_fb_band_planes; k++)
-      if (strlen (fb_band_plane_names[k]) == n && !strncmp (list, fb_band_plane_names[k], n))
-        hit = k;
-    if (hit < 0)
-      return 0;
-    mask |= 1u << hit;
-    list += n;
-    if (*list == ',' && !*++list)
-      return 0;
-  }
-  return mask;
-}
-
-/* --fb-bands=FILE[:PLANES]: the pair through peaq_run_pair_fb_bands, its rows as CSV -- a header line (block, channel,
- * plane, then the bands' centre frequencies in Hz), then one line per (block, channel, plane) with the band values;
- * every value as %.17g, which reads back to the same double.  Prints the delay line of --align. */
-static int
-write_fb_bands (const char *path, uint32_t planes, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
-    const wav_t *ref, const wav_t *test, peaq_result *r)
-{
-  const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
-    rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
-  const size_t block_cap = (size_t) peaq_frame_count (n48[0], n48[1], 1) + 1;
-  const int count = peaq_fb_band_count (), ch = ref->channels;
-  int n_planes = 0, c, k, b, slot, rc = 1;
-  double *rows, *fc;
-  uint32_t nb = 0, blk;
-  peaq_delay delay;
-  FILE *out;
-  for (k = 0; k < n_fb_band_planes; k++)
-    n_planes += (planes >> k) & 1;
-  rows = malloc (block_cap * ch * (n_planes ? n_planes : 1) * count * sizeof *rows);
-  fc = malloc (count * sizeof *fc);
-  if (!rows || !fc) {
-    printf ("Error: out of memory for the band trace\n");
-    goto done;
-  }
-  if (peaq_fb_band_tables (fc, NULL) != PEAQ_OK ||
-      peaq_run_pair_fb_bands (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
-          planes, rows, block_cap, &nb, &delay, r) != PEAQ_OK) {
-    printf ("Error: %s\n", peaq_last_error ());
-    goto done;
-  }
-  if (align_lag)
-    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
-  if (!(out = fopen (path, "w"))) {
-    printf ("Error: cannot write %s\n", path);
-    goto done;
-  }
-  fprintf (out, "block,channel,plane");
-  for (b = 0; b < count; b++)
-    fprintf (out, ",%.17g", fc[b]);
-  fprintf (out, "\n");
-  for (blk = 0; blk < nb; blk++)
-    for (c = 0; c < ch; c++)
-      for (k = 0, slot = 0; k < n_fb_band_planes; k++) {
-        const double *v;
-        if (!((planes >> k) & 1))
-          continue;
-        v = rows + (((size_t) blk * ch + c) * n_planes + slot++) * count;
-        fprintf (out, "%u,%d,%s", blk, c, fb_band_plane_names[k]);
-        for (b = 0; b < count; b++)
-          fprintf (out, ",%.17g", v[b]);
-        fprintf (out, "\n");
-      }
-  if (fclose (out)) {
-    printf ("Error: cannot write %s\n", path);
-    goto done;
-  }
-  rc = 0;
-done:
-  free (rows);
-  free (fc);
-  return rc;
-}
-
-/* the planes of --pattern-bands=FILE[:PLANES] by name, in the order of their bits (PEAQ_PAT_BAND_*) */
-enum { n_pattern_band_planes = 13 };
-static const char *const pattern_band_plane_names[n_pattern_band_planes] = { "moddiff1", "moddiff2", "modwt", "noiseloud",
+static const char *const pattern_band_plane_names[] = { "moddiff1", "moddiff2", "modwt", "noiseloud",
   "unsm_ref", "unsm_test", "exc_ref", "exc_test", "adapt_ref", "adapt_test", "mod_ref", "mod_test", "avgloud_ref" };
+static const struct {
+  const char *unit;             /* the header's first word */
+  const char *const *names;
+  int n_names;
+} band_kinds[] = {
+  { "frame", band_plane_names, 5 },
+  { "block", fb_band_plane_names, 13 },
+  { "frame", pattern_band_plane_names, 13 },
+};
 
 /* a comma-separated list of plane names -> mask; 0 if a name is not one */
 static uint32_t
-parse_pattern_band_planes (const char *list)
+parse_planes (const char *list, const char *const *names, int n_names)
 {
   uint32_t mask = 0;
   while (*list) {
     const size_t n = strcspn (list, ",");
     int k, hit = -1;
-    for (k = 0; k < n_pattern_band_planes; k++)
-      if (strlen (pattern_band_plane_names[k]) == n && !strncmp (list, pattern_band_plane_names[k], n))
+    for (k = 0; k < n_names; k++)
+      if (strlen (names[k]) == n && !strncmp (list, names[k], n))
         hit = k;
     if (hit < 0)
       return 0;
@@ -866,34 +703,53 @@ parse_pattern_band_planes (const char *list)
   return mask;
 }
 
-/* --pattern-bands=FILE[:PLANES]: the pair through peaq_run_pair_pattern_bands, its rows as the CSV of --bands -- a
- * header line (frame, channel, plane, then the bands' centre frequencies in Hz), then one line per (frame, channel,
- * plane) with the band values; every value as %.17g, which reads back to the same double.  Prints the delay line of
- * --align. */
+/* The pair through peaq_run_pair_bands, _fb_bands or _pattern_bands, its rows as CSV -- a header line (frame or block,
+ * channel, plane, then the bands' centre frequencies in Hz), then one line per (frame or block, channel, plane) with
+ * the band values; every value as %.17g, which reads back to the same double.  Prints the delay line of --align.
+ * `advanced`: BANDS_FFT only (the filter bank belongs to the advanced version, the pattern layer to the basic one). */
 static int
-write_pattern_bands (const char *path, uint32_t planes, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
-    const wav_t *ref, const wav_t *test, peaq_result *r)
+write_band_rows (enum band_kind kind, const char *path, uint32_t planes, peaq_ctx *ctx, int advanced, double level,
+    uint32_t rate, uint32_t align_lag, const wav_t *ref, const wav_t *test, peaq_result *r)
 {
   const uint64_t n48[2] = { rate == 48000 ? ref->frames : peaq_resampled_length (ref->frames, rate),
     rate == 48000 ? test->frames : peaq_resampled_length (test->frames, rate) };
-  const size_t frame_cap = (size_t) peaq_frame_count (n48[0], n48[1], 0) + 1;
-  const int count = peaq_band_count (0), row = peaq_band_row (0), ch = ref->channels;
-  int n_planes = 0, c, k, b, slot, rc = 1;
+  const size_t cap = (size_t) peaq_frame_count (n48[0], n48[1], kind == BANDS_FB) + 1;
+  const int adv = kind == BANDS_FFT && advanced, ch = ref->channels;
+  const int count = kind == BANDS_FB ? peaq_fb_band_count () : peaq_band_count (adv);
+  const int row = kind == BANDS_FB ? count : peaq_band_row (adv);
+  const char *const *names = band_kinds[kind].names;
+  const int n_names = band_kinds[kind].n_names;
+  int n_planes = 0, c, k, b, slot, rc = 1, ok = 0;
   double *rows, *fc;
-  uint32_t nf = 0, f;
+  uint32_t n = 0, i;
   peaq_delay delay;
   FILE *out;
-  for (k = 0; k < n_pattern_band_planes; k++)
+  for (k = 0; k < n_names; k++)
     n_planes += (planes >> k) & 1;
-  rows = malloc (frame_cap * ch * (n_planes ? n_planes : 1) * row * sizeof *rows);
+  rows = malloc (cap * ch * (n_planes ? n_planes : 1) * row * sizeof *rows);
   fc = malloc (count * sizeof *fc);
   if (!rows || !fc) {
     printf ("Error: out of memory for the band trace\n");
     goto done;
   }
-  if (peaq_pattern_band_tables (fc, NULL) != PEAQ_OK ||
-      peaq_run_pair_pattern_bands (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
-          planes, rows, frame_cap, &nf, &delay, r) != PEAQ_OK) {
+  switch (kind) {
+  case BANDS_FFT:
+    ok = peaq_band_tables (adv, fc, NULL) == PEAQ_OK &&
+        peaq_run_pair_bands (ctx, adv, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
+            planes, rows, cap, &n, &delay, r) == PEAQ_OK;
+    break;
+  case BANDS_FB:
+    ok = peaq_fb_band_tables (fc, NULL) == PEAQ_OK &&
+        peaq_run_pair_fb_bands (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples, test->frames,
+            planes, rows, cap, &n, &delay, r) == PEAQ_OK;
+    break;
+  case BANDS_PATTERN:
+    ok = peaq_pattern_band_tables (fc, NULL) == PEAQ_OK &&
+        peaq_run_pair_pattern_bands (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples,
+            test->frames, planes, rows, cap, &n, &delay, r) == PEAQ_OK;
+    break;
+  }
+  if (!ok) {
     printf ("Error: %s\n", peaq_last_error ());
     goto done;
   }
@@ -903,18 +759,18 @@ write_pattern_bands (const char *path, uint32_t planes, peaq_ctx *ctx, double le
     printf ("Error: cannot write %s\n", path);
     goto done;
   }
-  fprintf (out, "frame,channel,plane");
+  fprintf (out, "%s,channel,plane", band_kinds[kind].unit);
   for (b = 0; b < count; b++)
     fprintf (out, ",%.17g", fc[b]);
   fprintf (out, "\n");
-  for (f = 0; f < nf; f++)
+  for (i = 0; i < n; i++)
     for (c = 0; c < ch; c++)
-      for (k = 0, slot = 0; k < n_pattern_band_planes; k++) {
+      for (k = 0, slot = 0; k < n_names; k++) {
         const double *v;
         if (!((planes >> k) & 1))
           continue;
-        v = rows + (((size_t) f * ch + c) * n_planes + slot++) * row;
-        fprintf (out, "%u,%d,%s", f, c, pattern_band_plane_names[k]);
+        v = rows + (((size_t) i * ch + c) * n_planes + slot++) * row;
+        fprintf (out, "%u,%d,%s", i, c, names[k]);
         for (b = 0; b < count; b++)
           fprintf (out, ",%.17g", v[b]);
         fprintf (out, "\n");
@@ -1159,8 +1015,8 @@ main (int argc, char **argv)
         fprintf (stderr, "Failed to initialize: --bands: no plane after the colon (nmr, exc_ref, exc_test, detect, steps)\n");
         return 1;
       }
-      if (colon && parse_band_planes (colon + 1)) {
-        band_planes = parse_band_planes (colon + 1);
+      if (colon && parse_planes (colon + 1, band_kinds[BANDS_FFT].names, band_kinds[BANDS_FFT].n_names)) {
+        band_planes = parse_planes (colon + 1, band_kinds[BANDS_FFT].names, band_kinds[BANDS_FFT].n_names);
         *colon = 0;
       }
     }
@@ -1175,8 +1031,8 @@ main (int argc, char **argv)
         fprintf (stderr, "Failed to initialize: --fb-bands: no plane after the colon (moddiff, modwt, noiseloud, missing, lindist, unsm_ref, unsm_test, exc_ref, exc_test, adapt_ref, adapt_test, mod_ref, mod_test)\n");
         return 1;
       }
-      if (colon && parse_fb_band_planes (colon + 1)) {
-        fb_band_planes = parse_fb_band_planes (colon + 1);
+      if (colon && parse_planes (colon + 1, band_kinds[BANDS_FB].names, band_kinds[BANDS_FB].n_names)) {
+        fb_band_planes = parse_planes (colon + 1, band_kinds[BANDS_FB].names, band_kinds[BANDS_FB].n_names);
         *colon = 0;
       }
     }
@@ -1191,8 +1047,8 @@ main (int argc, char **argv)
         fprintf (stderr, "Failed to initialize: --pattern-bands: no plane after the colon (moddiff1, moddiff2, modwt, noiseloud, unsm_ref, unsm_test, exc_ref, exc_test, adapt_ref, adapt_test, mod_ref, mod_test, avgloud_ref)\n");
         return 1;
       }
-      if (colon && parse_pattern_band_planes (colon + 1)) {
-        pattern_band_planes = parse_pattern_band_planes (colon + 1);
+      if (colon && parse_planes (colon + 1, band_kinds[BANDS_PATTERN].names, band_kinds[BANDS_PATTERN].n_names)) {
+        pattern_band_planes = parse_planes (colon + 1, band_kinds[BANDS_PATTERN].names, band_kinds[BANDS_PATTERN].n_names);
         *colon = 0;
       }
     }
@@ -1427,13 +1283,13 @@ main (int argc, char **argv)
       if (write_band_summary (band_summary_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (pattern_bands_path) {
-      if (write_pattern_bands (pattern_bands_path, pattern_band_planes, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+      if (write_band_rows (BANDS_PATTERN, pattern_bands_path, pattern_band_planes, ctx, 0, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (fb_bands_path) {
-      if (write_fb_bands (fb_bands_path, fb_band_planes, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+      if (write_band_rows (BANDS_FB, fb_bands_path, fb_band_planes, ctx, 1, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (bands_path) {
-      if (write_bands (bands_path, band_planes, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+      if (write_band_rows (BANDS_FFT, bands_path, band_planes, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (trace_path) {
       if (write_trace (trace_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))

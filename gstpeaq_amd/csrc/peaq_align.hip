@@ -684,6 +684,58 @@ extern "C" int peaq_run_pair_matched(peaq_ctx* c, int advanced, int channels, do
   return score_one_pair(c, advanced, channels, level_db, sp.d[0], sp.d[1], sp.stride, sp.len[0], sp.len[1], out);
 }
 
+// ---- the one-pair forms of the batch run's optional outputs ---------------------------------------------------------
+// One array of such an output: a record per FFT frame, per filter-bank block or one per pair, `bytes` each, copied into
+// the caller's `host` array of `cap` records (`cap_name` in the message when the pair has more); kNone: this run does
+// not write the array.  run_pair_output fills in `n` and `dev`.
+namespace {
+struct PairRows {
+  enum Per { kNone, kFrame, kBlock, kPair } per;
+  size_t bytes;
+  void* host;
+  size_t cap;
+  const char* cap_name;
+  uint32_t* n_out;              // the count for the caller, or nullptr
+  uint32_t n = 0;
+  DevBuf dev;
+};
+}  // namespace
+
+// What the five entries below share, after their own arguments: max_lag, the level and the pair are checked, the pair
+// is prepared as peaq_run_pair_aligned's, each array's count is held against the caller's capacity, `run` -- the
+// entry's batch call, with the pair and a device result -- fills the device arrays, and everything is copied back.
+template <class Run>
+static int run_pair_output(const std::string& w, peaq_ctx* c, int channels, double level_db, uint32_t rate,
+                           uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
+                           peaq_delay* delay, peaq_result* out, PairRows* rows, int n_rows, Run run) {
+  if (max_lag)
+    if (int rc = check_max_lag(w, max_lag)) return rc;
+  if (int rc = check_level(w, level_db)) return rc;
+  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
+  ScoredPair pp;
+  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
+    return rc;
+  for (PairRows* r = rows; r < rows + n_rows; ++r) {
+    const bool blocks = r->per == PairRows::kBlock;
+    r->n = r->per == PairRows::kNone ? 0 : r->per == PairRows::kPair ? 1 : peaq_frame_count(pp.len[0], pp.len[1], blocks);
+    if (r->n > r->cap)
+      return fail(PEAQ_ERR_ARG, w + ": " + r->cap_name + " " + std::to_string(r->cap) + " is below the pair's " +
+                                    std::to_string(r->n) + (blocks ? " blocks" : " frames"));
+  }
+  DevBuf d_res;
+  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
+  for (PairRows* r = rows; r < rows + n_rows; ++r)
+    if (r->per != PairRows::kNone) HIP_TRY(r->dev.reserve(std::max<size_t>(r->n, 1) * r->bytes));
+  if (int rc = run(pp, d_res.as<peaq_result>())) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  for (PairRows* r = rows; r < rows + n_rows; ++r)
+    if (r->n) HIP_TRY(hipMemcpy(r->host, r->dev.p, (size_t)r->n * r->bytes, hipMemcpyDeviceToHost));
+  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
+  for (PairRows* r = rows; r < rows + n_rows; ++r)
+    if (r->n_out) *r->n_out = r->n;
+  return PEAQ_OK;
+}
+
 extern "C" int peaq_run_pair_trace(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
                                    uint32_t max_lag, const float* ref, size_t n_ref, const float* test, size_t n_test,
                                    peaq_frame_trace* frames, size_t frame_cap, uint32_t* n_frames,
@@ -693,34 +745,16 @@ extern "C" int peaq_run_pair_trace(peaq_ctx* c, int advanced, int channels, doub
   if (!frames) return fail(PEAQ_ERR_ARG, w + ": frames is NULL");
   if (advanced && !blocks) return fail(PEAQ_ERR_ARG, w + ": blocks is NULL (the advanced version writes block records)");
   if (!advanced && blocks) return fail(PEAQ_ERR_ARG, w + ": blocks must be NULL in the basic version (it has no filter-bank blocks)");
-  if (max_lag)
-    if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
-  ScoredPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
-    return rc;
-  const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
-  const uint32_t nb = advanced ? peaq_frame_count(pp.len[0], pp.len[1], 1) : 0;
-  if (nf > frame_cap)
-    return fail(PEAQ_ERR_ARG, w + ": frame_cap " + std::to_string(frame_cap) + " is below the pair's " + std::to_string(nf) + " frames");
-  if (nb > block_cap)
-    return fail(PEAQ_ERR_ARG, w + ": block_cap " + std::to_string(block_cap) + " is below the pair's " + std::to_string(nb) + " blocks");
-  DevBuf d_res, d_fr, d_bl;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  HIP_TRY(d_fr.reserve(std::max<size_t>(nf, 1) * sizeof(peaq_frame_trace)));
-  if (advanced) HIP_TRY(d_bl.reserve(std::max<size_t>(nb, 1) * sizeof(peaq_block_trace)));
-  if (int rc = peaq_batch_run_trace(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
-                                    d_fr.as<peaq_frame_trace>(), nf, advanced ? d_bl.as<peaq_block_trace>() : nullptr, nb,
-                                    d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (nf) HIP_TRY(hipMemcpy(frames, d_fr.p, (size_t)nf * sizeof(peaq_frame_trace), hipMemcpyDeviceToHost));
-  if (nb) HIP_TRY(hipMemcpy(blocks, d_bl.p, (size_t)nb * sizeof(peaq_block_trace), hipMemcpyDeviceToHost));
-  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  if (n_frames) *n_frames = nf;
-  if (n_blocks) *n_blocks = nb;
-  return PEAQ_OK;
+  PairRows rows[2] = {
+      {PairRows::kFrame, sizeof(peaq_frame_trace), frames, frame_cap, "frame_cap", n_frames},
+      {advanced ? PairRows::kBlock : PairRows::kNone, sizeof(peaq_block_trace), blocks, block_cap, "block_cap", n_blocks}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 2,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_trace(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride,
+                                                       pp.len, pp.len + 1, 0, rows[0].dev.as<peaq_frame_trace>(),
+                                                       rows[0].n, rows[1].dev.as<peaq_block_trace>(), rows[1].n, d_res,
+                                                       nullptr);
+                         });
 }
 
 extern "C" int peaq_run_pair_bands(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
@@ -730,28 +764,14 @@ extern "C" int peaq_run_pair_bands(peaq_ctx* c, int advanced, int channels, doub
   const std::string w("peaq_run_pair_bands");
   if (int rc = check_band_planes(w, advanced, planes)) return rc;
   if (!bands) return fail(PEAQ_ERR_ARG, w + ": bands is NULL");
-  if (max_lag)
-    if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
-  ScoredPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
-    return rc;
-  const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
-  if (nf > frame_cap)
-    return fail(PEAQ_ERR_ARG, w + ": frame_cap " + std::to_string(frame_cap) + " is below the pair's " + std::to_string(nf) + " frames");
   const size_t frame_bytes = (size_t)channels * __builtin_popcount(planes) * peaq_band_row(advanced) * sizeof(double);
-  DevBuf d_res, d_bn;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  HIP_TRY(d_bn.reserve(std::max<size_t>(nf, 1) * frame_bytes));
-  if (int rc = peaq_batch_run_bands(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
-                                    planes, d_bn.as<double>(), nf, d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (nf) HIP_TRY(hipMemcpy(bands, d_bn.p, (size_t)nf * frame_bytes, hipMemcpyDeviceToHost));
-  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  if (n_frames) *n_frames = nf;
-  return PEAQ_OK;
+  PairRows rows[1] = {{PairRows::kFrame, frame_bytes, bands, frame_cap, "frame_cap", n_frames}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_bands(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride,
+                                                       pp.len, pp.len + 1, 0, planes, rows[0].dev.as<double>(),
+                                                       rows[0].n, d_res, nullptr);
+                         });
 }
 
 extern "C" int peaq_run_pair_fb_bands(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
@@ -761,28 +781,14 @@ extern "C" int peaq_run_pair_fb_bands(peaq_ctx* c, int channels, double level_db
   const std::string w("peaq_run_pair_fb_bands");
   if (int rc = check_fb_band_planes(w, planes)) return rc;
   if (!bands) return fail(PEAQ_ERR_ARG, w + ": bands is NULL");
-  if (max_lag)
-    if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
-  ScoredPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
-    return rc;
-  const uint32_t nb = peaq_frame_count(pp.len[0], pp.len[1], 1);
-  if (nb > block_cap)
-    return fail(PEAQ_ERR_ARG, w + ": block_cap " + std::to_string(block_cap) + " is below the pair's " + std::to_string(nb) + " blocks");
   const size_t block_bytes = (size_t)channels * __builtin_popcount(planes) * peaq_fb_band_count() * sizeof(double);
-  DevBuf d_res, d_bn;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  HIP_TRY(d_bn.reserve(std::max<size_t>(nb, 1) * block_bytes));
-  if (int rc = peaq_batch_run_fb_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0, planes,
-                                       d_bn.as<double>(), nb, d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (nb) HIP_TRY(hipMemcpy(bands, d_bn.p, (size_t)nb * block_bytes, hipMemcpyDeviceToHost));
-  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  if (n_blocks) *n_blocks = nb;
-  return PEAQ_OK;
+  PairRows rows[1] = {{PairRows::kBlock, block_bytes, bands, block_cap, "block_cap", n_blocks}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_fb_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len,
+                                                          pp.len + 1, 0, planes, rows[0].dev.as<double>(), rows[0].n,
+                                                          d_res, nullptr);
+                         });
 }
 
 extern "C" int peaq_run_pair_pattern_bands(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
@@ -792,52 +798,29 @@ extern "C" int peaq_run_pair_pattern_bands(peaq_ctx* c, int channels, double lev
   const std::string w("peaq_run_pair_pattern_bands");
   if (int rc = check_pattern_band_planes(w, planes)) return rc;
   if (!bands) return fail(PEAQ_ERR_ARG, w + ": bands is NULL");
-  if (max_lag)
-    if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
-  ScoredPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
-    return rc;
-  const uint32_t nf = peaq_frame_count(pp.len[0], pp.len[1], 0);
-  if (nf > frame_cap)
-    return fail(PEAQ_ERR_ARG, w + ": frame_cap " + std::to_string(frame_cap) + " is below the pair's " + std::to_string(nf) + " frames");
   const size_t frame_bytes = (size_t)channels * __builtin_popcount(planes) * peaq_band_row(0) * sizeof(double);
-  DevBuf d_res, d_bn;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  HIP_TRY(d_bn.reserve(std::max<size_t>(nf, 1) * frame_bytes));
-  if (int rc = peaq_batch_run_pattern_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len, pp.len + 1, 0,
-                                            planes, d_bn.as<double>(), nf, d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (nf) HIP_TRY(hipMemcpy(bands, d_bn.p, (size_t)nf * frame_bytes, hipMemcpyDeviceToHost));
-  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  if (n_frames) *n_frames = nf;
-  return PEAQ_OK;
+  PairRows rows[1] = {{PairRows::kFrame, frame_bytes, bands, frame_cap, "frame_cap", n_frames}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_pattern_bands(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride,
+                                                               pp.len, pp.len + 1, 0, planes, rows[0].dev.as<double>(),
+                                                               rows[0].n, d_res, nullptr);
+                         });
 }
 
+// (one record per pair: neither a count nor a capacity of the caller's)
 extern "C" int peaq_run_pair_band_summary(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
                                           uint32_t max_lag, const float* ref, size_t n_ref, const float* test,
                                           size_t n_test, double* summary, peaq_delay* delay, peaq_result* out) {
   const std::string w("peaq_run_pair_band_summary");
   if (!summary) return fail(PEAQ_ERR_ARG, w + ": summary is NULL");
-  if (max_lag)
-    if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, false)) return rc;
-  ScoredPair pp;
-  if (int rc = prepare_pair(c, channels, rate, max_lag, PEAQ_GAIN_OFF, 0., ref, n_ref, test, n_test, delay, nullptr, pp))
-    return rc;
   const size_t bytes =
       (size_t)channels * peaq_band_summary_rows(advanced) * peaq_band_row(advanced) * sizeof(double);
-  DevBuf d_res, d_sm;
-  HIP_TRY(d_res.reserve(sizeof(peaq_result)));
-  HIP_TRY(d_sm.reserve(bytes));
-  if (int rc = peaq_batch_run_band_summary(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len,
-                                           pp.len + 1, 0, d_sm.as<double>(), d_res.as<peaq_result>(), nullptr))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(summary, d_sm.p, bytes, hipMemcpyDeviceToHost));
-  if (out) HIP_TRY(hipMemcpy(out, d_res.p, sizeof(peaq_result), hipMemcpyDeviceToHost));
-  return PEAQ_OK;
+  PairRows rows[1] = {{PairRows::kPair, bytes, summary, 1, "", nullptr}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_band_summary(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1],
+                                                              pp.stride, pp.len, pp.len + 1, 0, rows[0].dev.as<double>(),
+                                                              d_res, nullptr);
+                         });
 }

@@ -640,32 +640,46 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 #include "peaq_backend_fft.inc"
 }
 
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                          const TraceArgs* trc, const BandArgs* bnd, const PatternBandArgs* pbd, const SummaryArgs* sum) {
+// Which outputs may meet which launch (x = refused with hipErrorInvalidValue, . = accepted, and then the first of sum,
+// pbd, bnd, trc, pts, a.debug decides the kernel):
+//
+//                with:  sum  pbd  bnd  trc  pts  a.debug  a.pair_frame0  a.pair_slot  a.advanced
+//   out.sum              -    x    x    x    x      x           x             x            .
+//   out.pbd              x    -    x    x    x      x           x             .            x
+//   out.bnd              x    x    -    x    x      x           x             .            .
+//   out.trc              x    x    x    -    .      .           .             .            .
+//   out.pts              x    x    x    .    -      .           .             .            .
+//
+// The rows-per-band outputs (bnd, pbd, sum) belong to a run's own launches: each stands alone.  The trace and the
+// points are not held against each other, the debug dump or a broker's windows: the trace wins over the points, either
+// wins over a.debug.  out.fbnd is the filter-bank path's and is not looked at here.
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
   PEAQ_DEV_SPIN_INSTEAD_OF_BACKEND(a, block, stream)
-  if (bnd && (pts || trc || a.debug || a.pair_frame0)) return hipErrorInvalidValue;   // a run's own launches only
-  if (pbd && (bnd || pts || trc || a.debug || a.pair_frame0 || a.advanced)) return hipErrorInvalidValue;
-  if (sum && (pbd || bnd || pts || trc || a.debug || a.pair_frame0 || a.pair_slot)) return hipErrorInvalidValue;
+  const bool pts = out.has_pts(), trc = out.has_trc(), bnd = out.has_bnd(), pbd = out.has_pbd(), sum = out.has_sum();
+  const int alone = bnd + pbd + sum;                 // at most one of these, and none with ...
+  if (alone && (alone + pts + trc + (a.debug != nullptr) + (a.pair_frame0 != nullptr) > 1 || (pbd && a.advanced) ||
+                (sum && a.pair_slot)))
+    return hipErrorInvalidValue;
   if (sum && !a.advanced)
-    hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *sum);
+    hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.sum);
   else if (sum)
-    hipLaunchKernelGGL((backend_summary_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *sum);
+    hipLaunchKernelGGL((backend_summary_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.sum);
   else if (pbd)
-    hipLaunchKernelGGL((backend_pattern_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pbd);
+    hipLaunchKernelGGL((backend_pattern_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.pbd);
   else if (bnd && !a.advanced)
-    hipLaunchKernelGGL((backend_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *bnd);
+    hipLaunchKernelGGL((backend_bands_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.bnd);
   else if (bnd)
-    hipLaunchKernelGGL((backend_bands_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *bnd);
+    hipLaunchKernelGGL((backend_bands_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.bnd);
   else if (trc && !a.advanced)
-    hipLaunchKernelGGL((backend_trace_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *trc);
+    hipLaunchKernelGGL((backend_trace_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.trc);
   else if (trc)
-    hipLaunchKernelGGL((backend_trace_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *trc);
+    hipLaunchKernelGGL((backend_trace_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.trc);
   else if (pts && !a.advanced)
-    hipLaunchKernelGGL((backend_points_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, *pts);
+    hipLaunchKernelGGL((backend_points_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.pts);
   else if (pts)
-    hipLaunchKernelGGL((backend_points_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, *pts);
+    hipLaunchKernelGGL((backend_points_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.pts);
   else if (!a.advanced && a.debug)
     hipLaunchKernelGGL((backend_kernel<109, false, true>), dim3(n_pairs), block, 0, stream, a);
   else if (a.debug)
@@ -729,16 +743,21 @@ __global__ __launch_bounds__(128, 4) void fb_backend_bands_kernel(FbBackendArgs 
 #include "peaq_backend_fb.inc"
 }
 
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts,
-                             const TraceArgs* trc, const FbBandArgs* bnd) {
+//                with:  fbnd  trc  pts  a.debug  a.windows
+//   out.fbnd              -    x    x      x         x           (a run's own launches only)
+//   out.trc               x    -    .      .         .
+//   out.pts               x    .    -      .         .
+// out.bnd, out.pbd and out.sum are the FFT path's and are not looked at here.
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
-  if (bnd && (pts || trc || a.debug || a.windows)) return hipErrorInvalidValue;   // a run's own launches only
+  const bool pts = out.has_pts(), trc = out.has_trc(), bnd = out.has_fbnd();
+  if (bnd && (pts || trc || a.debug || a.windows)) return hipErrorInvalidValue;
   if (bnd)
-    hipLaunchKernelGGL(fb_backend_bands_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *bnd);
+    hipLaunchKernelGGL(fb_backend_bands_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.fbnd);
   else if (trc)
-    hipLaunchKernelGGL(fb_backend_trace_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *trc);
+    hipLaunchKernelGGL(fb_backend_trace_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.trc);
   else if (pts)
-    hipLaunchKernelGGL(fb_backend_points_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, *pts);
+    hipLaunchKernelGGL(fb_backend_points_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.pts);
   else if (a.debug)
     hipLaunchKernelGGL(fb_backend_kernel<true>, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a);
   else

@@ -72,8 +72,7 @@ extern "C" size_t peaq_batch_workspace_bytes(int advanced, int channels, int n_p
 static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
                                const float* d_test, size_t pair_stride, const uint32_t* d_nref,
                                const uint32_t* d_ntest, uint32_t n_uniform, const uint32_t* d_nblocks,
-                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const PointArgs* pts,
-                               const TraceArgs* trc, const FbBandArgs* fbnd) {
+                               uint32_t max_blocks, hipStream_t stream, hipEvent_t bank_gate, const RunOutputs& out) {
     // ---- filter-bank path: blocks of 192 samples (gstpeaq.c:648-652) ------------------
     const unsigned n_signals = (unsigned)n_pairs * channels * 2;
     const unsigned bc = fb_blocks_per_chunk(n_pairs, channels, max_blocks);
@@ -150,7 +149,7 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
       HIP_TRY(hipEventRecord(e1, s_bank));
       bank_done[b] = e1;
       if (piped) HIP_TRY(hipStreamWaitEvent(s_be, e1, 0));
-      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, pts, trc, fbnd));
+      HIP_TRY(launch_fb_backend(fbk, n_pairs, s_be, out));
       if (piped) {
         HIP_TRY(hipEventRecord(e_be, s_be));
         be_done[b] = e_be;
@@ -166,20 +165,9 @@ static int run_filterbank_path(peaq_ctx* c, int channels, double level_db, int n
   return PEAQ_OK;
 }
 
-// Reading points of a trajectory (peaq_batch_run_trajectory): nullptr for a plain batch.
-struct TrajectoryOut {
-  uint32_t interval;
-  int n_points;
-  peaq_result* d_points;        // [n_pairs][n_points]
-};
-
-// Records of a trace (peaq_batch_run_trace): nullptr for a plain batch.  Never together with a trajectory.
-struct TraceOut {
-  peaq_frame_trace* d_frames;   // [n_pairs][frame_stride]
-  size_t frame_stride;
-  peaq_block_trace* d_blocks;   // [n_pairs][block_stride], advanced only
-  size_t block_stride;
-};
+// The records and bits of include/peaq_amd.h are those of peaq_kernels.h: the public entries below hand the caller's
+// arrays and masks to the kernels as they are.
+static_assert(sizeof(peaq_result) == sizeof(ResultRecord), "peaq_result of include/peaq_amd.h and ResultRecord");
 static_assert(sizeof(peaq_frame_trace) == 128 && sizeof(FrameTrace) == 128 && sizeof(peaq_block_trace) == 96 &&
                   sizeof(BlockTrace) == 96,
               "the trace records of include/peaq_amd.h and peaq_kernels.h");
@@ -189,24 +177,9 @@ static_assert(offsetof(peaq_frame_trace, flags) == offsetof(FrameTrace, flags) &
 static_assert(PEAQ_TRACE_ABOVE == kTraceAbove && PEAQ_TRACE_MOD_OPEN == kTraceModOpen &&
                   PEAQ_TRACE_LOUD_OPEN == kTraceLoudOpen && PEAQ_TRACE_FLUSH == kTraceFlush,
               "the flags of include/peaq_amd.h and peaq_kernels.h");
-
-// Rows of a band trace (peaq_batch_run_bands): nullptr for a plain batch.  Never together with a trajectory or a trace.
-struct BandOut {
-  double* d_bands;              // [n_pairs][frame_stride][channels][n_planes][band_row]
-  size_t frame_stride;
-  uint32_t planes;
-};
 static_assert(PEAQ_BAND_NMR == kBandNmr && PEAQ_BAND_EXC_REF == kBandExcRef && PEAQ_BAND_EXC_TEST == kBandExcTest &&
                   PEAQ_BAND_DETECT == kBandDetect && PEAQ_BAND_STEPS == kBandSteps,
               "the planes of include/peaq_amd.h and peaq_kernels.h");
-
-// Rows of a filter-bank band trace (peaq_batch_run_fb_bands): nullptr for a plain batch.  Never together with any of the
-// three above; the back end writes the caller's rows directly -- no scratch of its own.
-struct FbBandOut {
-  double* d_bands;              // [n_pairs][block_stride][channels][n_planes][40]
-  size_t block_stride;
-  uint32_t planes;
-};
 static_assert(PEAQ_FB_BAND_MODDIFF == kFbBandModDiff && PEAQ_FB_BAND_MODWT == kFbBandModWt &&
                   PEAQ_FB_BAND_NOISELOUD == kFbBandNoiseLoud && PEAQ_FB_BAND_MISSING == kFbBandMissing &&
                   PEAQ_FB_BAND_LINDIST == kFbBandLinDist && PEAQ_FB_BAND_UNSM_REF == kFbBandUnsmRef &&
@@ -215,14 +188,6 @@ static_assert(PEAQ_FB_BAND_MODDIFF == kFbBandModDiff && PEAQ_FB_BAND_MODWT == kF
                   PEAQ_FB_BAND_ADAPT_TEST == kFbBandAdaptTest && PEAQ_FB_BAND_MOD_REF == kFbBandModRef &&
                   PEAQ_FB_BAND_MOD_TEST == kFbBandModTest,
               "the filter-bank planes of include/peaq_amd.h and peaq_kernels.h");
-
-// Rows of a pattern-band trace (peaq_batch_run_pattern_bands, basic version): nullptr for a plain batch.  Never together
-// with any of the four above; the FFT back end writes the caller's rows directly.
-struct PatternBandOut {
-  double* d_bands;              // [n_pairs][frame_stride][channels][n_planes][110]
-  size_t frame_stride;
-  uint32_t planes;
-};
 static_assert(PEAQ_PAT_BAND_MODDIFF1 == kPatBandModDiff1 && PEAQ_PAT_BAND_MODDIFF2 == kPatBandModDiff2 &&
                   PEAQ_PAT_BAND_MODWT == kPatBandModWt && PEAQ_PAT_BAND_NOISELOUD == kPatBandNoiseLoud &&
                   PEAQ_PAT_BAND_UNSM_REF == kPatBandUnsmRef && PEAQ_PAT_BAND_UNSM_TEST == kPatBandUnsmTest &&
@@ -231,12 +196,6 @@ static_assert(PEAQ_PAT_BAND_MODDIFF1 == kPatBandModDiff1 && PEAQ_PAT_BAND_MODDIF
                   PEAQ_PAT_BAND_MOD_REF == kPatBandModRef && PEAQ_PAT_BAND_MOD_TEST == kPatBandModTest &&
                   PEAQ_PAT_BAND_AVGLOUD_REF == kPatBandAvgLoudRef,
               "the pattern-band planes of include/peaq_amd.h and peaq_kernels.h");
-
-// Rows of a band summary (peaq_batch_run_band_summary): nullptr for a plain batch.  Never together with any of the five
-// above; the FFT back end keeps the pair's running rows in the caller's array between its launches.
-struct SummaryOut {
-  double* d_summary;            // [n_pairs][channels][rows][band_row]
-};
 static_assert(PEAQ_BAND_SUMMARY_NMR_SUM == kSumNmrSum && PEAQ_BAND_SUMMARY_NMR_MAX == kSumNmrMax &&
                   PEAQ_BAND_SUMMARY_NMR_DISTURBED == kSumNmrDisturbed && PEAQ_BAND_SUMMARY_EXC_REF_SUM == kSumExcRef &&
                   PEAQ_BAND_SUMMARY_EXC_TEST_SUM == kSumExcTest && PEAQ_BAND_SUMMARY_MODDIFF1_WSUM == kSumModDiff1 &&
@@ -246,24 +205,21 @@ static_assert(PEAQ_BAND_SUMMARY_NMR_SUM == kSumNmrSum && PEAQ_BAND_SUMMARY_NMR_M
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
-                            const PatternBandOut* po, const SummaryOut* so);
+                            RunOutputs out);
 
 // peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands,
 // peaq_batch_run_pattern_bands and peaq_batch_run_band_summary: one driver, the points, the trace records, the band
-// rows and the summary optional (`who` names the entry in messages)
+// rows and the summary optional -- what `out` holds (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
-                           const TrajectoryOut* tr, const TraceOut* to = nullptr, const BandOut* bo = nullptr,
-                           const FbBandOut* fo = nullptr, const PatternBandOut* po = nullptr,
-                           const SummaryOut* so = nullptr) {
+                           const RunOutputs& out) {
   const std::string w(who);
   if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
   if (int rc = check_channels(w, channels)) return rc;
   if (n_pairs < 0) return fail(PEAQ_ERR_ARG, w + ": n_pairs < 0");
   if (n_pairs == 0) return PEAQ_OK;
-  if (!d_ref || !d_test || (!d_results && !tr && !to && !bo && !fo && !po && !so)) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
+  if (!d_ref || !d_test || (!d_results && !out.any())) return fail(PEAQ_ERR_ARG, w + ": NULL buffer");
   if ((n_ref == nullptr) != (n_test == nullptr))
     return fail(PEAQ_ERR_ARG, w + ": give both n_ref and n_test or neither");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -276,7 +232,7 @@ static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int chann
   c->spans.clear();
   c->events_used = 0;
   const int rc = batch_run_locked(who, c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                                  n_test, n_uniform, d_results, stream, tr, to, bo, fo, po, so);
+                                  n_test, n_uniform, d_results, stream, out);
   if (rc != PEAQ_OK) {
     // part of the pipeline may already run on the context's own streams: nothing may touch the
     // workspace (or free it) before that work has drained
@@ -292,7 +248,88 @@ extern "C" int peaq_batch_run(peaq_ctx* c, int advanced, int channels, double le
                               const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                               const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_) {
   return batch_run_entry("peaq_batch_run", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                         n_test, n_uniform, d_results, stream_, nullptr);
+                         n_test, n_uniform, d_results, stream_, RunOutputs());
+}
+
+// ---- what the output entries check of their own arguments: no context, no device ----------------------------------
+static int check_not_null(const std::string& w, const char* name, const void* p) {
+  return p ? PEAQ_OK : fail(PEAQ_ERR_ARG, w + ": " + name + " is NULL");
+}
+// (with_address: the summary entry's message prints the pointer)
+static int check_aligned(const std::string& w, const char* name, const void* p, bool with_address = false) {
+  if (reinterpret_cast<uintptr_t>(p) % 16 == 0) return PEAQ_OK;
+  char addr[32] = "";
+  if (with_address) std::snprintf(addr, sizeof addr, " %p", const_cast<void*>(p));
+  return fail(PEAQ_ERR_ARG, w + ": " + name + addr + " is not 16-byte aligned");
+}
+static int check_output(const std::string& w, const char* name, const void* p, bool with_address = false) {
+  if (int rc = check_not_null(w, name, p)) return rc;
+  return check_aligned(w, name, p, with_address);
+}
+
+// A stride of the caller's array held against the longest pair's count of FFT frames or of filter-bank blocks, made
+// from the host's lengths.  (Lengths the common driver is going to refuse are left to it.)
+static int check_stride(const std::string& w, const char* name, size_t stride, bool blocks, int n_pairs,
+                        const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform) {
+  if (n_pairs <= 0 || (n_ref == nullptr) != (n_test == nullptr)) return PEAQ_OK;
+  const unsigned frame = blocks ? kFbFrame : kFrame, hop = blocks ? kFbFrame : kHop;
+  uint32_t longest = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    longest = std::max(longest, count_frames(n_ref ? n_ref[p] : n_uniform, n_test ? n_test[p] : n_uniform, frame, hop));
+    if (!n_ref) break;
+  }
+  if (stride < longest)
+    return fail(PEAQ_ERR_ARG, w + ": " + name + " " + std::to_string(stride) + " is below the longest pair's " +
+                                  std::to_string(longest) + (blocks ? " blocks" : " frames"));
+  return PEAQ_OK;
+}
+
+// `planes` as a band entry takes it: bits of `all`, whose top bit `top` names; of these the advanced version of the
+// FFT planes has `advanced_has` only.  0 or an error with the value in the message.
+static int check_planes(const std::string& w, uint32_t planes, uint32_t all, const char* top,
+                        uint32_t advanced_has = ~0u) {
+  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
+  if (planes & ~all) return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) + " has a bit above " + top);
+  if (planes & ~advanced_has)
+    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) +
+                                  " asks for a plane the advanced version does not have (" +
+                                  std::to_string(planes & ~advanced_has) +
+                                  ": its 55-band path has PEAQ_BAND_NMR and PEAQ_BAND_EXC_REF only)");
+  return PEAQ_OK;
+}
+int check_band_planes(const std::string& w, int advanced, uint32_t planes) {
+  return check_planes(w, planes, kBandAll, "16 (PEAQ_BAND_STEPS)", advanced ? kBandAdvanced : ~0u);
+}
+int check_fb_band_planes(const std::string& w, uint32_t planes) {
+  return check_planes(w, planes, kFbBandAll, "4096 (PEAQ_FB_BAND_MOD_TEST)");
+}
+int check_pattern_band_planes(const std::string& w, uint32_t planes) {
+  return check_planes(w, planes, kPatBandAll, "4096 (PEAQ_PAT_BAND_AVGLOUD_REF)");
+}
+
+// What build_fft_band_tables and build_fb_band_tables build (host only: no context, no device), each once per process
+// on its first use; `second` is the row the entry gives beside the centre frequencies.
+enum BandSet { kBands109, kBands55, kBandsFb };
+static int copy_band_tables(const char* who, BandSet set, double* fc, double* second,
+                            const double (BandTables::*second_row)[kBandStride]) {
+  if (!fc && !second) return fail(PEAQ_ERR_ARG, std::string(who) + ": NULL argument");
+  static std::once_flag once[3];
+  static std::unique_ptr<BandTables> tabs[3];
+  std::call_once(once[set], [set] {
+    tabs[set] = std::make_unique<BandTables>();
+    if (set == kBandsFb) {
+      auto fb = std::make_unique<FbTables>();          // (the bank's coefficients come with the bands; not kept)
+      build_fb_band_tables(*tabs[set], *fb);
+    } else {
+      build_fft_band_tables(set == kBands109 ? 109 : 55, *tabs[set]);
+    }
+  });
+  const BandTables& t = *tabs[set];
+  for (int b = 0; b < t.bands; ++b) {
+    if (fc) fc[b] = t.fc[b];
+    if (second) second[b] = (t.*second_row)[b];
+  }
+  return PEAQ_OK;
 }
 
 // snapshot scratch of a trajectory; 0 when it does not fit size_t
@@ -312,9 +349,12 @@ extern "C" int peaq_batch_run_trajectory(peaq_ctx* c, int advanced, int channels
   if (!d_points) return fail(PEAQ_ERR_ARG, "peaq_batch_run_trajectory: d_points is NULL");
   if (n_pairs > 0 && trajectory_snap_bytes(n_pairs, n_points) == 0)
     return fail(PEAQ_ERR_NOMEM, "peaq_batch_run_trajectory: n_pairs x n_points snapshots exceed the address space");
-  const TrajectoryOut tr{interval, n_points, d_points};
+  RunOutputs out;
+  out.pts.interval = interval;
+  out.pts.n_points = n_points;
+  out.d_points = reinterpret_cast<ResultRecord*>(d_points);
   return batch_run_entry("peaq_batch_run_trajectory", c, advanced, channels, level_db, n_pairs, d_ref, d_test,
-                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, &tr);
+                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
 // The trace's own arguments first: they need no context (and no device: the strides are held against counts made
@@ -325,64 +365,29 @@ extern "C" int peaq_batch_run_trace(peaq_ctx* c, int advanced, int channels, dou
                                     size_t frame_stride, peaq_block_trace* d_blocks, size_t block_stride,
                                     peaq_result* d_results, void* stream_) {
   const std::string w("peaq_batch_run_trace");
-  if (!d_frames) return fail(PEAQ_ERR_ARG, w + ": d_frames is NULL");
+  if (int rc = check_not_null(w, "d_frames", d_frames)) return rc;
   if (advanced && !d_blocks) return fail(PEAQ_ERR_ARG, w + ": d_blocks is NULL (the advanced version writes block records)");
   if (!advanced && d_blocks) return fail(PEAQ_ERR_ARG, w + ": d_blocks must be NULL in the basic version (it has no filter-bank blocks)");
-  if (reinterpret_cast<uintptr_t>(d_frames) % 16 || reinterpret_cast<uintptr_t>(d_blocks) % 16)
-    return fail(PEAQ_ERR_ARG, w + ": " + (reinterpret_cast<uintptr_t>(d_frames) % 16 ? "d_frames" : "d_blocks") +
-                                  " is not 16-byte aligned");
-  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
-    uint32_t max_frames = 0, max_blocks = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
-      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
-      max_blocks = std::max(max_blocks, count_frames(nr, nt, kFbFrame, kFbFrame));
-      if (!n_ref) break;
-    }
-    if (frame_stride < max_frames)
-      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
-                                    std::to_string(max_frames) + " frames");
-    if (advanced && block_stride < max_blocks)
-      return fail(PEAQ_ERR_ARG, w + ": block_stride " + std::to_string(block_stride) + " is below the longest pair's " +
-                                    std::to_string(max_blocks) + " blocks");
-  }
-  const TraceOut to{d_frames, frame_stride, d_blocks, block_stride};
+  if (int rc = check_aligned(w, "d_frames", d_frames)) return rc;
+  if (int rc = check_aligned(w, "d_blocks", d_blocks)) return rc;
+  if (int rc = check_stride(w, "frame_stride", frame_stride, false, n_pairs, n_ref, n_test, n_uniform)) return rc;
+  if (advanced)
+    if (int rc = check_stride(w, "block_stride", block_stride, true, n_pairs, n_ref, n_test, n_uniform)) return rc;
+  RunOutputs out;
+  out.trc.frames = reinterpret_cast<FrameTrace*>(d_frames);
+  out.trc.frame_stride = frame_stride;
+  out.trc.blocks = reinterpret_cast<BlockTrace*>(d_blocks);
+  out.trc.block_stride = block_stride;
   return batch_run_entry("peaq_batch_run_trace", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
-                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, &to);
+                         n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
 // ---- band traces ----------------------------------------------------------------------------------------------
 extern "C" int peaq_band_count(int advanced) { return advanced ? 55 : 109; }
 extern "C" int peaq_band_row(int advanced) { return band_row(peaq_band_count(advanced)); }
 
-// what build_fft_band_tables builds (host only: no context, no device)
 extern "C" int peaq_band_tables(int advanced, double* fc, double* mask_diff) {
-  if (!fc && !mask_diff) return fail(PEAQ_ERR_ARG, "peaq_band_tables: NULL argument");
-  static const auto built = [](int bands) {          // once per process, on the first call
-    auto t = std::make_unique<BandTables>();
-    build_fft_band_tables(bands, *t);
-    return t;
-  };
-  static const std::unique_ptr<BandTables> tabs[2] = {built(109), built(55)};
-  const BandTables& t = *tabs[advanced ? 1 : 0];
-  for (int b = 0; b < t.bands; ++b) {
-    if (fc) fc[b] = t.fc[b];
-    if (mask_diff) mask_diff[b] = t.mask_diff[b];
-  }
-  return PEAQ_OK;
-}
-
-// `planes` as the band entries take it; 0 or an error with the value in the message
-int check_band_planes(const std::string& w, int advanced, uint32_t planes) {
-  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
-  if (planes & ~kBandAll)
-    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) + " has a bit above 16 (PEAQ_BAND_STEPS)");
-  if (advanced && (planes & ~kBandAdvanced))
-    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) +
-                                  " asks for a plane the advanced version does not have (" +
-                                  std::to_string(planes & ~kBandAdvanced) +
-                                  ": its 55-band path has PEAQ_BAND_NMR and PEAQ_BAND_EXC_REF only)");
-  return PEAQ_OK;
+  return copy_band_tables("peaq_band_tables", advanced ? kBands55 : kBands109, fc, mask_diff, &BandTables::mask_diff);
 }
 
 // The band trace's own arguments first, as the trace's: they need no context and no device.
@@ -392,49 +397,19 @@ extern "C" int peaq_batch_run_bands(peaq_ctx* c, int advanced, int channels, dou
                                     size_t frame_stride, peaq_result* d_results, void* stream_) {
   const std::string w("peaq_batch_run_bands");
   if (int rc = check_band_planes(w, advanced, planes)) return rc;
-  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
-  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
-  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
-    uint32_t max_frames = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
-      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
-      if (!n_ref) break;
-    }
-    if (frame_stride < max_frames)
-      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
-                                    std::to_string(max_frames) + " frames");
-  }
-  const BandOut bo{d_bands, frame_stride, planes};
+  if (int rc = check_output(w, "d_bands", d_bands)) return rc;
+  if (int rc = check_stride(w, "frame_stride", frame_stride, false, n_pairs, n_ref, n_test, n_uniform)) return rc;
+  RunOutputs out;
+  out.bnd = {d_bands, frame_stride, planes};
   return batch_run_entry("peaq_batch_run_bands", c, advanced, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
-                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, &bo);
+                         n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
 // ---- band traces of the filter-bank path ------------------------------------------------------------------------
 extern "C" int peaq_fb_band_count(void) { return kFbBands; }
 
-// what build_fb_band_tables builds (host only: no context, no device)
 extern "C" int peaq_fb_band_tables(double* fc, double* internal_noise) {
-  if (!fc && !internal_noise) return fail(PEAQ_ERR_ARG, "peaq_fb_band_tables: NULL argument");
-  static const std::unique_ptr<BandTables> tabs = [] {     // once per process, on the first call
-    auto t = std::make_unique<BandTables>();
-    auto fb = std::make_unique<FbTables>();            // (the bank's coefficients come with the bands; not kept)
-    build_fb_band_tables(*t, *fb);
-    return t;
-  }();
-  for (int b = 0; b < kFbBands; ++b) {
-    if (fc) fc[b] = tabs->fc[b];
-    if (internal_noise) internal_noise[b] = tabs->internal_noise[b];
-  }
-  return PEAQ_OK;
-}
-
-// `planes` as the filter-bank band entries take it; 0 or an error with the value in the message
-int check_fb_band_planes(const std::string& w, uint32_t planes) {
-  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
-  if (planes & ~kFbBandAll)
-    return fail(PEAQ_ERR_ARG, w + ": planes " + std::to_string(planes) + " has a bit above 4096 (PEAQ_FB_BAND_MOD_TEST)");
-  return PEAQ_OK;
+  return copy_band_tables("peaq_fb_band_tables", kBandsFb, fc, internal_noise, &BandTables::internal_noise);
 }
 
 // The band trace's own arguments first, as peaq_batch_run_bands': they need no context and no device.
@@ -444,47 +419,18 @@ extern "C" int peaq_batch_run_fb_bands(peaq_ctx* c, int channels, double level_d
                                        size_t block_stride, peaq_result* d_results, void* stream_) {
   const std::string w("peaq_batch_run_fb_bands");
   if (int rc = check_fb_band_planes(w, planes)) return rc;
-  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
-  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
-  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
-    uint32_t max_blocks = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
-      max_blocks = std::max(max_blocks, count_frames(nr, nt, kFbFrame, kFbFrame));
-      if (!n_ref) break;
-    }
-    if (block_stride < max_blocks)
-      return fail(PEAQ_ERR_ARG, w + ": block_stride " + std::to_string(block_stride) + " is below the longest pair's " +
-                                    std::to_string(max_blocks) + " blocks");
-  }
-  const FbBandOut fo{d_bands, block_stride, planes};
+  if (int rc = check_output(w, "d_bands", d_bands)) return rc;
+  if (int rc = check_stride(w, "block_stride", block_stride, true, n_pairs, n_ref, n_test, n_uniform)) return rc;
+  RunOutputs out;
+  out.fbnd = {d_bands, block_stride, planes};
   return batch_run_entry("peaq_batch_run_fb_bands", c, 1, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
-                         n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, &fo);
+                         n_test, n_uniform, d_results, stream_, out);
 }
 
 // ---- band traces of the pattern layer (basic version) ----------------------------------------------------------
-// what build_fft_band_tables builds for the 109 bands (host only: no context, no device)
+// (the 109 bands of peaq_band_tables(0, ...), with the internal noise beside the centre frequencies)
 extern "C" int peaq_pattern_band_tables(double* fc, double* internal_noise) {
-  if (!fc && !internal_noise) return fail(PEAQ_ERR_ARG, "peaq_pattern_band_tables: NULL argument");
-  static const std::unique_ptr<BandTables> tabs = [] {     // once per process, on the first call
-    auto t = std::make_unique<BandTables>();
-    build_fft_band_tables(109, *t);
-    return t;
-  }();
-  for (int b = 0; b < tabs->bands; ++b) {
-    if (fc) fc[b] = tabs->fc[b];
-    if (internal_noise) internal_noise[b] = tabs->internal_noise[b];
-  }
-  return PEAQ_OK;
-}
-
-// `planes` as the pattern-band entries take it; 0 or an error with the value in the message
-int check_pattern_band_planes(const std::string& w, uint32_t planes) {
-  if (planes == 0) return fail(PEAQ_ERR_ARG, w + ": planes is 0 (no plane requested)");
-  if (planes & ~kPatBandAll)
-    return fail(PEAQ_ERR_ARG,
-                w + ": planes " + std::to_string(planes) + " has a bit above 4096 (PEAQ_PAT_BAND_AVGLOUD_REF)");
-  return PEAQ_OK;
+  return copy_band_tables("peaq_pattern_band_tables", kBands109, fc, internal_noise, &BandTables::internal_noise);
 }
 
 // The band trace's own arguments first, as peaq_batch_run_bands': they need no context and no device.
@@ -495,22 +441,12 @@ extern "C" int peaq_batch_run_pattern_bands(peaq_ctx* c, int channels, double le
                                             void* stream_) {
   const std::string w("peaq_batch_run_pattern_bands");
   if (int rc = check_pattern_band_planes(w, planes)) return rc;
-  if (!d_bands) return fail(PEAQ_ERR_ARG, w + ": d_bands is NULL");
-  if (reinterpret_cast<uintptr_t>(d_bands) % 16) return fail(PEAQ_ERR_ARG, w + ": d_bands is not 16-byte aligned");
-  if (n_pairs > 0 && (n_ref == nullptr) == (n_test == nullptr)) {
-    uint32_t max_frames = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-      const uint32_t nr = n_ref ? n_ref[p] : n_uniform, nt = n_test ? n_test[p] : n_uniform;
-      max_frames = std::max(max_frames, count_frames(nr, nt, kFrame, kHop));
-      if (!n_ref) break;
-    }
-    if (frame_stride < max_frames)
-      return fail(PEAQ_ERR_ARG, w + ": frame_stride " + std::to_string(frame_stride) + " is below the longest pair's " +
-                                    std::to_string(max_frames) + " frames");
-  }
-  const PatternBandOut po{d_bands, frame_stride, planes};
+  if (int rc = check_output(w, "d_bands", d_bands)) return rc;
+  if (int rc = check_stride(w, "frame_stride", frame_stride, false, n_pairs, n_ref, n_test, n_uniform)) return rc;
+  RunOutputs out;
+  out.pbd = {d_bands, frame_stride, planes};
   return batch_run_entry("peaq_batch_run_pattern_bands", c, 0, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
-                         n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, nullptr, &po);
+                         n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
 // ---- band summary ------------------------------------------------------------------------------------------------
@@ -521,17 +457,11 @@ extern "C" int peaq_batch_run_band_summary(peaq_ctx* c, int advanced, int channe
                                            const float* d_ref, const float* d_test, size_t pair_stride,
                                            const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform,
                                            double* d_summary, peaq_result* d_results, void* stream_) {
-  const std::string w("peaq_batch_run_band_summary");
-  if (!d_summary) return fail(PEAQ_ERR_ARG, w + ": d_summary is NULL");
-  if (reinterpret_cast<uintptr_t>(d_summary) % 16) {
-    char addr[32];
-    std::snprintf(addr, sizeof addr, "%p", static_cast<void*>(d_summary));
-    return fail(PEAQ_ERR_ARG, w + ": d_summary " + addr + " is not 16-byte aligned");
-  }
-  const SummaryOut so{d_summary};
+  if (int rc = check_output("peaq_batch_run_band_summary", "d_summary", d_summary, true)) return rc;
+  RunOutputs out;
+  out.sum.rows = d_summary;
   return batch_run_entry("peaq_batch_run_band_summary", c, advanced ? 1 : 0, channels, level_db, n_pairs, d_ref, d_test,
-                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, &so);
+                         pair_stride, n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
@@ -603,8 +533,7 @@ extern "C" int peaq_run_pair_trajectory(peaq_ctx* c, int advanced, int channels,
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
-                            const TrajectoryOut* tr, const TraceOut* to, const BandOut* bo, const FbBandOut* fo,
-                            const PatternBandOut* po, const SummaryOut* so) {
+                            RunOutputs out) {
 
   // ---- frame counts -------------------------------------------------------------------
   uint32_t max_frames = 0, max_blocks = 0;
@@ -643,71 +572,36 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   HIP_TRY(c->records.reserve(rec_bytes));
   HIP_TRY(c->records2.reserve(rec_bytes));
   HIP_TRY(c->state.reserve((size_t)n_pairs * sizeof(PairState)));
+  // The band rows (FFT, filter bank, pattern layer) arrive complete: the back end that has them writes the caller's rows
+  // directly and the other path runs its plain kernels.  What only this function knows of the other outputs:
   // trajectory: the snapshots of the reading points, [pair][point] (the back ends write them, finalize_points reads them)
-  PointArgs pa{};
-  const size_t n_snaps = tr ? (size_t)n_pairs * tr->n_points : 0;
-  if (tr) {
+  const size_t n_snaps = out.has_pts() ? (size_t)n_pairs * out.pts.n_points : 0;
+  if (out.has_pts()) {
     HIP_TRY(c->snaps.reserve(n_snaps * sizeof(PointSnap)));
-    pa.snap = c->snaps.as<PointSnap>();
-    pa.n_ref = d_nref;
-    pa.n_test = d_ntest;
-    pa.n_uniform = n_uniform;
-    pa.interval = tr->interval;
-    pa.n_points = tr->n_points;
+    out.pts.snap = c->snaps.as<PointSnap>();
+    out.pts.n_ref = d_nref;
+    out.pts.n_test = d_ntest;
+    out.pts.n_uniform = n_uniform;
   }
-  const PointArgs* pts = tr ? &pa : nullptr;
   // trace: the back ends write the caller's record arrays directly -- no scratch of its own
-  TraceArgs ta{};
-  if (to) {
-    ta.frames = reinterpret_cast<FrameTrace*>(to->d_frames);
-    ta.frame_stride = to->frame_stride;
-    ta.blocks = reinterpret_cast<BlockTrace*>(to->d_blocks);
-    ta.block_stride = to->block_stride;
-    ta.n_ref = d_nref;
-    ta.n_test = d_ntest;
-    ta.n_uniform = n_uniform;
+  if (out.has_trc()) {
+    out.trc.n_ref = d_nref;
+    out.trc.n_test = d_ntest;
+    out.trc.n_uniform = n_uniform;
   }
-  const TraceArgs* trc = to ? &ta : nullptr;
-  // band trace: the FFT back end writes the caller's rows directly; the filter-bank side runs its plain kernels
-  BandArgs bna{};
-  if (bo) {
-    bna.bands = bo->d_bands;
-    bna.frame_stride = bo->frame_stride;
-    bna.planes = bo->planes;
-  }
-  const BandArgs* bnd = bo ? &bna : nullptr;
-  // filter-bank band trace: the filter-bank back end writes the caller's rows directly; the FFT side runs its plain kernels
-  FbBandArgs fba{};
-  if (fo) {
-    fba.bands = fo->d_bands;
-    fba.block_stride = fo->block_stride;
-    fba.planes = fo->planes;
-  }
-  const FbBandArgs* fbnd = fo ? &fba : nullptr;
-  // pattern-band trace (basic version): every back-end launch of the run is the pattern-bands instantiation
-  PatternBandArgs pba{};
-  if (po) {
-    pba.bands = po->d_bands;
-    pba.frame_stride = po->frame_stride;
-    pba.planes = po->planes;
-  }
-  const PatternBandArgs* pbd = po ? &pba : nullptr;
   // band summary: every FFT back-end launch of the run is the summary instantiation.  The caller's rows start from zero
   // and carry the running sums from launch to launch; the copy a pair takes when it turns tentative goes to scratch of
   // the same shape (reserved here, so that running out of memory is reported before anything is enqueued).
-  SummaryArgs sma{};
   const size_t sum_pair_doubles = (size_t)channels * band_summary_rows(advanced != 0) * band_row(advanced ? 55 : 109);
-  if (so) {
+  if (out.has_sum()) {
     HIP_TRY(c->sum_saved.reserve((size_t)n_pairs * sum_pair_doubles * sizeof(double)));
-    sma.rows = so->d_summary;
-    sma.saved = c->sum_saved.as<double>();
+    out.sum.saved = c->sum_saved.as<double>();
   }
-  const SummaryArgs* sum = so ? &sma : nullptr;
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
-  if (so) HIP_TRY(hipMemsetAsync(sma.rows, 0, (size_t)n_pairs * sum_pair_doubles * sizeof(double), stream));
-  if (tr) HIP_TRY(launch_points_init(pa.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
+  if (out.has_sum()) HIP_TRY(hipMemsetAsync(out.sum.rows, 0, (size_t)n_pairs * sum_pair_doubles * sizeof(double), stream));
+  if (out.has_pts()) HIP_TRY(launch_points_init(out.pts.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
   const bool with_fb = advanced && max_blocks > 0;
@@ -723,7 +617,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   auto issue_filterbank_path = [&](hipEvent_t bank_gate) -> int {
     hipStream_t s_fb = PEAQ_DEV_SERIAL_KERNELS ? stream : c->aux2;
     const int rc = run_filterbank_path(c, channels, level_db, n_pairs, d_ref, d_test, pair_stride, d_nref, d_ntest,
-                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, pts, trc, fbnd);
+                                       n_uniform, d_nblocks, max_blocks, s_fb, bank_gate, out);
     if (rc != PEAQ_OK) return rc;
     fb_done = c->next_event();
     if (!fb_done) return fail(PEAQ_ERR_DEVICE, "hipEventCreate failed");
@@ -798,7 +692,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipEventRecord(e1, stream));
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, pts, trc, bnd, pbd, sum));
+    if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, out));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;
@@ -822,14 +716,14 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   for (int i = 0; i < 2; ++i)
     if (back_done[i]) HIP_TRY(hipStreamWaitEvent(stream, back_done[i], 0));
   if (fb_done) HIP_TRY(hipStreamWaitEvent(stream, fb_done, 0));
-  if (so)
-    HIP_TRY(launch_summary_restore(c->state.as<PairState>(), advanced, sma, n_pairs, (unsigned)sum_pair_doubles, stream));
+  if (out.has_sum())
+    HIP_TRY(launch_summary_restore(c->state.as<PairState>(), advanced, out.sum, n_pairs, (unsigned)sum_pair_doubles, stream));
   if (d_results)
     HIP_TRY(launch_finalize(c->state.as<PairState>(), advanced, channels, n_pairs,
                             reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));
-  if (tr)
-    HIP_TRY(launch_finalize_points(pa.snap, advanced, channels, n_pairs, tr->n_points,
-                                   reinterpret_cast<ResultRecord*>(tr->d_points), stream, c->settings));
+  if (out.has_pts())
+    HIP_TRY(launch_finalize_points(out.pts.snap, advanced, channels, n_pairs, out.pts.n_points, out.d_points, stream,
+                                   c->settings));
   HIP_TRY(hipEventRecord(c->batch_end, stream));
   c->batch_pending = true;
   return PEAQ_OK;

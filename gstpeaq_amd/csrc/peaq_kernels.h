@@ -151,16 +151,7 @@ struct BackendArgs {
   // its own lifetime to clk[0], clk[1] -- the clock the device held while the step ran (peaq_batch_last_clock)
   unsigned long long* clk;
 };
-// pts != nullptr (trajectory launches only): the points instantiation, snapshots after frames (PointArgs)
-// trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per frame (TraceArgs)
-// bnd != nullptr (band-trace launches only, never with pts or trc): the bands instantiation, rows per frame (BandArgs)
-// pbd != nullptr (pattern-band launches of the basic version only, never with any of the three): the pattern-bands
-// instantiation, rows per frame (PatternBandArgs)
-// sum != nullptr (summary launches only, never with any of the four): the summary instantiation, running rows per pair
-// (SummaryArgs)
-hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
-                          const TraceArgs* trc = nullptr, const BandArgs* bnd = nullptr,
-                          const PatternBandArgs* pbd = nullptr, const SummaryArgs* sum = nullptr);
+// (launch_backend: below, after RunOutputs)
 
 // ---- read-out: accumulators -> MOVs -> DI -> ODG --------------------------------
 struct ResultRecord {           // mirrors peaq_result in include/peaq_amd.h
@@ -247,12 +238,35 @@ struct FbBandArgs {
   size_t block_stride;          // its ABSOLUTE block index
   uint32_t planes;              // kFbBand* bits; the slot of a plane is the rank of its bit among the set ones
 };
-// pts != nullptr (trajectory launches only): the points instantiation, snapshots after blocks (PointArgs)
-// trc != nullptr (trace launches only, never with pts): the trace instantiation, a record per block (TraceArgs)
-// bnd != nullptr (filter-bank band-trace launches only, never with pts, trc, a.debug or a.windows): the bands
-// instantiation, rows per block (FbBandArgs)
-hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const PointArgs* pts = nullptr,
-                             const TraceArgs* trc = nullptr, const FbBandArgs* bnd = nullptr);
+
+// ---- the optional outputs of a run -------------------------------------------------------------
+// What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
+// array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
+// knows (the device length arrays of `pts` and `trc`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
+// and picks the instantiation; sessions, the broker and the stage entries pass none.
+struct RunOutputs {
+  PointArgs pts{};              // trajectory (peaq_batch_run_trajectory): interval, n_points; snap from batch_run_locked
+  ResultRecord* d_points = nullptr;   // [n_pairs][n_points]: where the read-out of the snapshots goes
+  TraceArgs trc{};              // peaq_batch_run_trace
+  BandArgs bnd{};               // peaq_batch_run_bands
+  FbBandArgs fbnd{};            // peaq_batch_run_fb_bands
+  PatternBandArgs pbd{};        // peaq_batch_run_pattern_bands
+  SummaryArgs sum{};            // peaq_batch_run_band_summary
+  bool has_pts() const { return d_points != nullptr; }
+  bool has_trc() const { return trc.frames != nullptr; }
+  bool has_bnd() const { return bnd.bands != nullptr; }
+  bool has_fbnd() const { return fbnd.bands != nullptr; }
+  bool has_pbd() const { return pbd.bands != nullptr; }
+  bool has_sum() const { return sum.rows != nullptr; }
+  bool any() const { return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum(); }
+};
+// The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first
+// that is present (out.fbnd is the other path's).  launch_backend in peaq_backend.hip has the table of what it refuses.
+hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out = RunOutputs());
+// The instantiation of the filter-bank back end: bands (out.fbnd), trace, points, a.debug, plain -- the first that is
+// present (out.bnd, out.pbd and out.sum are the other path's: this one runs its plain kernels beside them).
+hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream,
+                             const RunOutputs& out = RunOutputs());
 
 // ---- synthetic workload --------------------------------------------------------------
 hipError_t launch_synth(uint32_t seed0, unsigned n_pairs, int channels, uint32_t n_samples, size_t pair_stride,
