@@ -162,6 +162,9 @@ PATTERN_BAND_PLANES = {"moddiff1": 0x1, "moddiff2": 0x2, "modwt": 0x4, "noiselou
 # PEAQ_BAND_SUMMARY_* (include/peaq_amd.h) by name, in row order; the advanced version has the first four
 BAND_SUMMARY_ROWS = ("nmr_sum", "nmr_max", "nmr_disturbed", "exc_ref_sum", "exc_test_sum", "moddiff1_wsum",
                      "moddiff2_wsum", "noiseloud_sum")
+# PEAQ_FB_BAND_SUMMARY_* (include/peaq_amd.h) by name, in row order (advanced version, filter-bank path)
+FB_BAND_SUMMARY_ROWS = ("exc_ref_sum", "exc_test_sum", "moddiff_wsum", "moddiff_sq", "noiseloud_sq", "missing_sq",
+                        "lindist_sum")
 
 
 class HostPair(C.Structure):
@@ -321,6 +324,13 @@ def load_library():
                                                   u32p, C.c_uint32, vp, vp, vp]
         L.peaq_run_pair_band_summary.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t,
                                                  fp, C.c_size_t, vp, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_fb_band_summary"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_fb_band_summary_rows.argtypes = []
+        L.peaq_fb_band_summary_row.argtypes = []
+        L.peaq_batch_run_fb_band_summary.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p,
+                                                     C.c_uint32, vp, vp, vp]
+        L.peaq_run_pair_fb_band_summary.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
+                                                    C.c_size_t, vp, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_resample"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_resample_supported.argtypes = [C.c_uint32]
         L.peaq_resampled_length.restype = C.c_uint32
@@ -2200,6 +2210,87 @@ def run_pair_band_summary(ctx, advanced, ref, test, playback_level=92.0, rate=48
                                             out.ctypes.data_as(C.POINTER(C.c_double))))
     fc, _ = band_tables(advanced)
     res = dict(rows=rows, fc=fc, result=_result_dict(out, advanced), **_band_summary_views(rows, n_bands))
+    if align is not None:
+        res["delay"] = _delay_dict(rec)
+    return res
+
+
+def _fb_band_summary_views(rows, n_bands=40):
+    """rows [..., 7, 42] (peaq_batch_run_fb_band_summary) -> the named views [..., n_bands] and `counted` [...]:
+    exc_ref_mean, exc_test_mean, moddiff (row 2 over the sum of W) and lindist_mean are their row over the row's
+    denominator (entry n_bands); moddiff_sq_share, noiseloud_sq_share and missing_sq_share are their row over its sum
+    over the bands -- the band's share of the square the MOV averages.  A view is NaN where its denominator is 0."""
+    rows = np.asarray(rows)
+
+    def ratio(k):
+        den = rows[..., k, n_bands:n_bands + 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den != 0., rows[..., k, :n_bands] / den, np.nan)
+
+    def share(k):
+        den = rows[..., k, :n_bands].sum(axis=-1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den != 0., rows[..., k, :n_bands] / den, np.nan)
+
+    return dict(counted=rows[..., 0, n_bands].astype(np.int64), exc_ref_mean=ratio(0), exc_test_mean=ratio(1),
+                moddiff=ratio(2), moddiff_sq_share=share(3), noiseloud_sq_share=share(4), missing_sq_share=share(5),
+                lindist_mean=ratio(6))
+
+
+def batch_fb_band_summary(ctx, ref, test, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
+                          d_summary=None, results=None, stream=None, sync=True):
+    """Every pair's per-band summary of the filter-bank path (the 40 bands behind RmsModDiff, RmsNoiseLoudAsym and
+    AvgLinDist), reduced over the pair's counted blocks on the device in the run that scores the batch in the advanced
+    version (peaq_batch_run_fb_band_summary; include/peaq_amd.h has the rows and which blocks count).  ref/test,
+    n_ref/n_test, rate and align as for batch_fb_bands.  d_summary: an optional CUDA float64 tensor [n_pairs (or more),
+    channels, 7, 42] to write into (pairs past the batch keep what they held); results: an optional CUDA float64 tensor
+    [n_pairs, RESULT_DOUBLES].
+    Returns a dict: rows, np.ndarray [pairs, channels, 7, 42] (FB_BAND_SUMMARY_ROWS in row order, the denominator in
+    entry 40 of each row); the named views exc_ref_mean, exc_test_mean, moddiff, moddiff_sq_share, noiseloud_sq_share,
+    missing_sq_share and lindist_mean, each [pairs, channels, 40] and NaN where its denominator is 0; counted [pairs,
+    channels]; fc (fb_band_tables); results (result dicts); and d_summary / d_results, the device tensors.  sync=False:
+    the device tensors and fc only."""
+    import torch
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream)
+    n_pairs, stride, channels = ref.shape
+    n_bands, row, n_rows = ctx.L.peaq_fb_band_count(), ctx.L.peaq_fb_band_summary_row(), ctx.L.peaq_fb_band_summary_rows()
+    with _torch_stream(stream):
+        if d_summary is None:
+            d_summary = torch.empty((n_pairs, channels, n_rows, row), dtype=torch.float64, device=ref.device)
+        if results is None:
+            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_summary.is_cuda and d_summary.dtype == torch.float64 and d_summary.is_contiguous() and d_summary.dim() == 4
+    assert d_summary.shape[0] >= n_pairs and tuple(d_summary.shape[1:]) == (channels, n_rows, row)
+    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
+    _check(ctx.L.peaq_batch_run_fb_band_summary(ctx.h, channels, float(playback_level), n_pairs,
+                                                C.c_void_p(ref.data_ptr()), C.c_void_p(test.data_ptr()), stride,
+                                                *len_args, stride, C.c_void_p(d_summary.data_ptr()),
+                                                C.c_void_p(results.data_ptr()), _stream_ptr(stream)))
+    fc, _ = fb_band_tables()
+    out = dict(d_summary=d_summary, d_results=results, fc=fc)
+    if not sync:
+        return out
+    torch.cuda.synchronize(ref.device)
+    rows = d_summary[:n_pairs].cpu().numpy()
+    out.update(rows=rows, **_fb_band_summary_views(rows, n_bands))
+    out["results"] = [_result_dict(r, True) for r in results.cpu().numpy()]
+    return out
+
+
+def run_pair_fb_band_summary(ctx, ref, test, playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_fb_band_summary: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`,
+    aligned first with align = a max_lag in 48 kHz samples.  Returns a dict: rows [channels, 7, 42], the named views of
+    batch_fb_band_summary [channels, 40], counted [channels], fc, result (a result dict) and, with align, delay."""
+    ref, test, ch, pair_args = _host_pair(ref, test)
+    n_bands, row, n_rows = ctx.L.peaq_fb_band_count(), ctx.L.peaq_fb_band_summary_row(), ctx.L.peaq_fb_band_summary_rows()
+    rows = np.zeros((ch, n_rows, row))
+    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_fb_band_summary(ctx.h, ch, float(playback_level), int(rate),
+                                               0 if align is None else int(align), *pair_args,
+                                               C.c_void_p(rows.ctypes.data), C.byref(rec),
+                                               out.ctypes.data_as(C.POINTER(C.c_double))))
+    fc, _ = fb_band_tables()
+    res = dict(rows=rows, fc=fc, result=_result_dict(out, True), **_fb_band_summary_views(rows, n_bands))
     if align is not None:
         res["delay"] = _delay_dict(rec)
     return res

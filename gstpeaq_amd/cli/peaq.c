@@ -588,6 +588,12 @@ usage (const char *prog)
       "                exc_ref_sum and, in the basic version, exc_test_sum, moddiff1_wsum, moddiff2_wsum, noiseloud_sum\n"
       "                (the plain one-call mode; with --advanced, --device-resample, --align; a run of its own, like\n"
       "                --bands)\n"
+      "  --fb-band-summary=FILE with --advanced: also write the filter-bank path's per-band summary (40 bands, the ones\n"
+      "                behind RmsModDiff, RmsNoiseLoudAsym and AvgLinDist) to FILE as CSV: one line per channel and band\n"
+      "                with the band's centre frequency in Hz, the band's sums over the counted blocks (first to last\n"
+      "                block above the data boundary) and their denominators: exc_ref_sum, exc_test_sum, moddiff_wsum,\n"
+      "                moddiff_sq, noiseloud_sq, missing_sq, lindist_sum (the plain one-call mode; with\n"
+      "                --device-resample, --align; a run of its own, like --bands)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -852,6 +858,70 @@ done:
   return rc;
 }
 
+/* the rows of --fb-band-summary=FILE by name, in row order (PEAQ_FB_BAND_SUMMARY_*) */
+enum { n_fb_band_summary_rows = 7 };
+static const char *const fb_band_summary_row_names[n_fb_band_summary_rows] = { "exc_ref_sum", "exc_test_sum",
+  "moddiff_wsum", "moddiff_sq", "noiseloud_sq", "missing_sq", "lindist_sum" };
+
+/* --fb-band-summary=FILE: the pair through peaq_run_pair_fb_band_summary, its rows as CSV -- a header line, then one
+ * line per (channel, band): the band's centre frequency in Hz, the band's value of the seven rows, then the rows'
+ * denominators (counted: the number of counted blocks; modwt_sum and modwt_sq_sum, the sums of W and W^2 under the two
+ * modulation-difference rows; loud_blocks, the number of blocks under the last three rows); every value as %.17g, which
+ * reads back to the same double.  Prints the delay line of --align. */
+static int
+write_fb_band_summary (const char *path, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  const int count = peaq_fb_band_count (), row = peaq_fb_band_summary_row (), n_rows = peaq_fb_band_summary_rows ();
+  const int ch = ref->channels;
+  int c, k, b, rc = 1;
+  double *rows, *fc;
+  peaq_delay delay;
+  FILE *out;
+  rows = malloc ((size_t) ch * n_rows * row * sizeof *rows);
+  fc = malloc (count * sizeof *fc);
+  if (!rows || !fc) {
+    printf ("Error: out of memory for the band summary\n");
+    goto done;
+  }
+  if (peaq_fb_band_tables (fc, NULL) != PEAQ_OK ||
+      peaq_run_pair_fb_band_summary (ctx, ch, level, rate, align_lag, ref->samples, ref->frames, test->samples,
+          test->frames, rows, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag)
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+  if (!(out = fopen (path, "w"))) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  fprintf (out, "channel,band,fc");
+  for (k = 0; k < n_rows; k++)
+    fprintf (out, ",%s", fb_band_summary_row_names[k]);
+  fprintf (out, ",counted,modwt_sum,modwt_sq_sum,loud_blocks\n");
+  for (c = 0; c < ch; c++) {
+    const double *v = rows + (size_t) c * n_rows * row;
+    for (b = 0; b < count; b++) {
+      fprintf (out, "%d,%d,%.17g", c, b, fc[b]);
+      for (k = 0; k < n_rows; k++)
+        fprintf (out, ",%.17g", v[k * row + b]);
+      fprintf (out, ",%.17g,%.17g,%.17g,%.17g\n", v[PEAQ_FB_BAND_SUMMARY_EXC_REF_SUM * row + count],
+          v[PEAQ_FB_BAND_SUMMARY_MODDIFF_WSUM * row + count], v[PEAQ_FB_BAND_SUMMARY_MODDIFF_SQ * row + count],
+          v[PEAQ_FB_BAND_SUMMARY_NOISELOUD_SQ * row + count]);
+    }
+  }
+  if (fclose (out)) {
+    printf ("Error: cannot write %s\n", path);
+    goto done;
+  }
+  rc = 0;
+done:
+  free (rows);
+  free (fc);
+  return rc;
+}
+
 int
 main (int argc, char **argv)
 {
@@ -879,6 +949,7 @@ main (int argc, char **argv)
   char *pattern_bands_path = NULL;   /* --pattern-bands=FILE[:PLANES], peaq_run_pair_pattern_bands */
   uint32_t pattern_band_planes = PEAQ_PAT_BAND_NOISELOUD;
   const char *band_summary_path = NULL;   /* --band-summary=FILE, peaq_run_pair_band_summary */
+  const char *fb_band_summary_path = NULL;   /* --fb-band-summary=FILE, peaq_run_pair_fb_band_summary */
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -1057,6 +1128,11 @@ main (int argc, char **argv)
       return 1;
     } else if (!strncmp (argv[i], "--band-summary=", 15))
       band_summary_path = argv[i] + 15;
+    else if (!strcmp (argv[i], "--fb-band-summary") || !strcmp (argv[i], "--fb-band-summary=")) {
+      fprintf (stderr, "Failed to initialize: --fb-band-summary needs a file name (--fb-band-summary=FILE)\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--fb-band-summary=", 18))
+      fb_band_summary_path = argv[i] + 18;
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -1115,6 +1191,18 @@ main (int argc, char **argv)
   }
   if (band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
     fprintf (stderr, "Failed to initialize: --band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --trace, --match-gain or an --align-... beyond --align)\n");
+    return 1;
+  }
+  if (fb_band_summary_path && !advanced) {
+    fprintf (stderr, "Failed to initialize: --fb-band-summary needs --advanced (the basic version has no filter-bank path)\n");
+    return 1;
+  }
+  if (fb_band_summary_path && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --fb-band-summary belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (fb_band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --fb-band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
@@ -1279,7 +1367,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (band_summary_path) {
+    if (fb_band_summary_path) {
+      if (write_fb_band_summary (fb_band_summary_path, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (band_summary_path) {
       if (write_band_summary (band_summary_path, ctx, advanced, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (pattern_bands_path) {

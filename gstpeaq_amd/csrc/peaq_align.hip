@@ -701,7 +701,7 @@ struct PairRows {
 };
 }  // namespace
 
-// What the five entries below share, after their own arguments: max_lag, the level and the pair are checked, the pair
+// What the six entries below share, after their own arguments: max_lag, the level and the pair are checked, the pair
 // is prepared as peaq_run_pair_aligned's, each array's count is held against the caller's capacity, `run` -- the
 // entry's batch call, with the pair and a device result -- fills the device arrays, and everything is copied back.
 template <class Run>
@@ -822,5 +822,20 @@ extern "C" int peaq_run_pair_band_summary(peaq_ctx* c, int advanced, int channel
                            return peaq_batch_run_band_summary(c, advanced, channels, level_db, 1, pp.d[0], pp.d[1],
                                                               pp.stride, pp.len, pp.len + 1, 0, rows[0].dev.as<double>(),
                                                               d_res, nullptr);
+                         });
+}
+
+extern "C" int peaq_run_pair_fb_band_summary(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                             const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                             double* summary, peaq_delay* delay, peaq_result* out) {
+  const std::string w("peaq_run_pair_fb_band_summary");
+  if (!summary) return fail(PEAQ_ERR_ARG, w + ": summary is NULL");
+  const size_t bytes = (size_t)channels * peaq_fb_band_summary_rows() * peaq_fb_band_summary_row() * sizeof(double);
+  PairRows rows[1] = {{PairRows::kPair, bytes, summary, 1, "", nullptr}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_fb_band_summary(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride,
+                                                                 pp.len, pp.len + 1, 0, rows[0].dev.as<double>(), d_res,
+                                                                 nullptr);
                          });
 }

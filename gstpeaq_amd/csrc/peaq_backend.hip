@@ -506,6 +506,25 @@ __device__ __forceinline__ void fb_band_store(const FbBandArgs& bnd, uint32_t bi
   if (lane < kFbBands) *reinterpret_cast<double*>(row + off) = v;
 }
 
+// Filter-bank band summary (FbSummaryArgs, peaq_batch_run_fb_band_summary): a channel's running rows sit in LDS, rows of
+// kFbSumRow doubles; lane b owns entry b of every row and is the only one to touch it (no barrier).  Lane 40 owns the
+// denominators and is handed the denominator's increment in place of a band value, lane 41 the zero behind them.
+__device__ __forceinline__ double fb_summary_pick(int lane, double band_value, double den) {
+  return lane < kFbBands ? band_value : lane == kFbBands ? den : 0.;
+}
+__device__ __forceinline__ void fb_summary_add(double* entry, bool own, double v) {
+  if (own) *entry += v;
+}
+// the rows of one channel, a lane's entry of each: LDS <-> the caller's array, LDS -> the saved copy
+__device__ __forceinline__ void fb_summary_copy(double* dst, const double* src, bool own) {
+  if (!own) return;
+#pragma unroll
+  for (int k = 0; k < kFbSumRows; ++k) {
+    asm volatile("" ::: "memory");                   // row by row (rare): one row's register, not seven at once
+    dst[k * kFbSumRow] = src[k * kFbSumRow];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Band summary (SummaryArgs, peaq_batch_run_band_summary): a channel's running rows sit in LDS, rows of ROW doubles; a
 // lane owns the two entries 2 lane and 2 lane + 1 of every row and is the only one to touch them (no barrier).  NB is
@@ -713,46 +732,66 @@ struct FbBackendShared {
 // BND = true (fb_backend_bands_kernel, filter-bank band-trace launches only): the block's MOV values are computed for
 // every block, as with TRC, and every lane below 40 stores its band's value of the requested planes where it comes up
 // (FbBandArgs, fb_band_store); the accumulators see what the gates admit, as in the plain instantiation.
+// FSUM = true (fb_band_summary_kernel, filter-bank summary launches only): every lane below 40 adds its band's terms of
+// the counted blocks to the channel's running rows in LDS where they come up (FbSummaryArgs, fb_summary_add); the
+// arithmetic and the gates are the plain instantiation's, and a block whose gate is closed evaluates nothing more.
 template <bool DBG>
 __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false;
+  constexpr bool PTS = false, TRC = false, BND = false, FSUM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr FbBandArgs bnd{};
+  constexpr FbSummaryArgs fsum{};
 #include "peaq_backend_fb.inc"
 }
 // the points instantiation (see backend_points_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, FSUM = false;
   constexpr TraceArgs trc{};
   constexpr FbBandArgs bnd{};
+  constexpr FbSummaryArgs fsum{};
 #include "peaq_backend_fb.inc"
 }
 // the trace instantiation (see backend_trace_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_trace_kernel(FbBackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, FSUM = false;
   constexpr PointArgs pts{};
   constexpr FbBandArgs bnd{};
+  constexpr FbSummaryArgs fsum{};
 #include "peaq_backend_fb.inc"
 }
 // the bands instantiation (see backend_bands_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_bands_kernel(FbBackendArgs a, FbBandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, FSUM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
+  constexpr FbSummaryArgs fsum{};
+#include "peaq_backend_fb.inc"
+}
+// the summary instantiation (see backend_summary_kernel); a name of its own that the other kernels' names do not contain
+__global__ __launch_bounds__(128, 4) void fb_band_summary_kernel(FbBackendArgs a, FbSummaryArgs fsum) {
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, FSUM = true;
+  constexpr PointArgs pts{};
+  constexpr TraceArgs trc{};
+  constexpr FbBandArgs bnd{};
 #include "peaq_backend_fb.inc"
 }
 
-//                with:  fbnd  trc  pts  a.debug  a.windows
-//   out.fbnd              -    x    x      x         x           (a run's own launches only)
-//   out.trc               x    -    .      .         .
-//   out.pts               x    .    -      .         .
-// out.bnd, out.pbd and out.sum are the FFT path's and are not looked at here.
+//                with:  fsum  fbnd  trc  pts  a.debug  a.windows
+//   out.fsum              -     x    x    x      x         x          (a run's own launches only)
+//   out.fbnd              x     -    x    x      x         x          (a run's own launches only)
+//   out.trc               x     x    -    .      .         .
+//   out.pts               x     x    .    -      .         .
+// out.fsum is also refused together with out.sum: a run has one summary, and the two share the context's saved copy.
+// out.bnd, out.pbd and out.sum are the FFT path's and are otherwise not looked at here.
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
-  const bool pts = out.has_pts(), trc = out.has_trc(), bnd = out.has_fbnd();
-  if (bnd && (pts || trc || a.debug || a.windows)) return hipErrorInvalidValue;
-  if (bnd)
+  const bool pts = out.has_pts(), trc = out.has_trc(), bnd = out.has_fbnd(), fsum = out.has_fsum();
+  if ((bnd || fsum) && (pts || trc || a.debug || a.windows || (bnd && fsum) || (fsum && out.has_sum())))
+    return hipErrorInvalidValue;
+  if (fsum)
+    hipLaunchKernelGGL(fb_band_summary_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.fsum);
+  else if (bnd)
     hipLaunchKernelGGL(fb_backend_bands_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.fbnd);
   else if (trc)
     hipLaunchKernelGGL(fb_backend_trace_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.trc);
@@ -924,6 +963,15 @@ hipError_t launch_summary_restore(const PairState* state, int advanced, const Su
   // (the accumulator whose tentative state the back end's summary rows follow)
   hipLaunchKernelGGL(summary_restore_kernel, dim3(n_pairs), dim3(256), 0, stream, state,
                      advanced ? (int)MA_SEGNMR : (int)MB_NMR, sum.rows, sum.saved, n_pairs, pair_doubles);
+  return hipGetLastError();
+}
+
+// (the filter-bank summary's rows follow the RmsModDiff accumulator: all three of that path see the same set_tentative)
+hipError_t launch_fb_summary_restore(const PairState* state, const FbSummaryArgs& fsum, unsigned n_pairs,
+                                     unsigned pair_doubles, hipStream_t stream) {
+  if (n_pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(summary_restore_kernel, dim3(n_pairs), dim3(256), 0, stream, state, (int)MA_RMSMOD, fsum.rows,
+                     fsum.saved, n_pairs, pair_doubles);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
-// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = BND = false),
-// fb_backend_points_kernel (PTS = true), fb_backend_trace_kernel (TRC = true) and fb_backend_bands_kernel (BND = true)
-// in peaq_backend.hip: one text, four kernels of their own names.
+// peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = BND = FSUM =
+// false), fb_backend_points_kernel (PTS = true), fb_backend_trace_kernel (TRC = true), fb_backend_bands_kernel (BND =
+// true) and fb_band_summary_kernel (FSUM = true) in peaq_backend.hip: one text, five kernels of their own names.
   __shared__ FbBackendShared sh;
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
   __shared__ double sh_etab[kExpTabEntries];
@@ -61,6 +61,30 @@
     const uint32_t nr = trc.n_ref ? trc.n_ref[pair] : trc.n_uniform, nt = trc.n_test ? trc.n_test[pair] : trc.n_uniform;
     trc_full = PointWalk<true>::count(nr < nt ? nr : nt);
   }
+  // (summary instantiation only) the running rows of both channels: loaded from the caller's array here, stored back
+  // after the launch's last block.  Lane = entry: bands 0 .. 39, the denominator, the zero behind it.  The rows follow
+  // the status of the RmsModDiff accumulator (movaccum.c:317-362; the path's three accumulators see the same
+  // set_tentative) as a scalar: kInit until the first block above the data boundary, kTentative from a block below it
+  // to the next one above.
+  __shared__ double sh_fsum[FSUM ? 2 * kFbSumRows * kFbSumRow : 1];
+  const bool fsum_own = FSUM && lane < kFbSumRow;
+  auto fsum_row = [&](int k) -> double* {
+    unsigned off = (unsigned)lane * 8u;
+    asm volatile("" : "+v"(off));                    // (made where it is used, not kept across the block loop)
+    return reinterpret_cast<double*>(reinterpret_cast<char*>(sh_fsum + (wave_uniform(chan) * kFbSumRows + k) * kFbSumRow) +
+                                     off);
+  };
+  auto fsum_cell = [&](double* base) -> double* {
+    unsigned off = (unsigned)lane * 8u;
+    asm volatile("" : "+v"(off));
+    return reinterpret_cast<double*>(
+        reinterpret_cast<char*>(base + ((size_t)pair * channels + wave_uniform(chan)) * (kFbSumRows * kFbSumRow)) + off);
+  };
+  int fsum_st = kInit;
+  if (FSUM) {
+    fsum_st = __builtin_amdgcn_readfirstlane(ps->status[MA_RMSMOD]);
+    fb_summary_copy(fsum_row(0), fsum_cell(fsum.rows), fsum_own);
+  }
 
   // the block's values are requested one block ahead: the walk is a chain of dependent transcendental
   // arithmetic, a record load per block would add its full memory latency 320 times per launch
@@ -92,19 +116,37 @@
   for (unsigned blk = b_begin; blk < b_end; ++blk) {
     const BlockIn cur = ALL ? fetch(blk) : nxt;
     // (... and re-read the per-band constants from the tables in every block: held across the loop they are the ten
-    // registers the other instantiations keep in scratch)
-    if (ALL) asm volatile("" : "+s"(bt.p));
+    // registers the other instantiations keep in scratch.  The summary instantiation re-reads them too, but keeps the
+    // block held ahead: holding the constants as well it spills 16 registers where the plain kernel spills 10; so, 8)
+    if (ALL || FSUM) asm volatile("" : "+s"(bt.p));
     if (!ALL && blk + 1 < b_end) nxt = fetch(blk + 1);
     const size_t bnd_row = BND ? bnd_cell0 + (size_t)blk * channels * bnd_planes : 0;
     // boundary detector on the 192-sample block, any reference channel (gstpeaq.c:971-979)
     const bool above = cur.f0 != 0. || cur.f1 != 0.;
     if (owns) acc.set_tentative(!above);
+    // (summary instantiation only) the rows take the same turns: the copy a pair that ends tentative gets back
+    // (summary_restore_kernel) is taken where the accumulators take theirs -- wave-uniform and rare
+    bool fsum_cnt = false;
+    if (FSUM) {
+      if (__builtin_amdgcn_readfirstlane((int)above)) {
+        fsum_st = kNormal;
+      } else if (fsum_st == kNormal) {
+        fb_summary_copy(fsum_cell(fsum.saved), fsum_row(0), fsum_own);
+        fsum_st = kTentative;
+      }
+      fsum_st = __builtin_amdgcn_readfirstlane(fsum_st);
+      fsum_cnt = fsum_st != kInit;
+    }
 
     double ur[SLOTS], ut[SLOTS], er[SLOTS], et[SLOTS], lr[SLOTS], lt[SLOTS];
     ur[0] = cur.ur;
     ut[0] = cur.ut;
     er[0] = cur.er;
     et[0] = cur.et;
+    if (FSUM && fsum_cnt) {
+      fb_summary_add(fsum_row(kFbSumExcRef), fsum_own, fb_summary_pick(lane, er[0], 1.));
+      fb_summary_add(fsum_row(kFbSumExcTest), fsum_own, fb_summary_pick(lane, et[0], 1.));
+    }
     if (BND) {
       fb_band_store(bnd, kFbBandUnsmRef, bnd_row, lane, ur[0]);
       fb_band_store(bnd, kFbBandUnsmTest, bnd_row, lane, ut[0]);
@@ -149,6 +191,12 @@
         fb_band_store(bnd, kFbBandModDiff, bnd_row, lane, div_fast(fabs(mr[0] - mt[0]), 1. + mr[0]));
         fb_band_store(bnd, kFbBandModWt, bnd_row, lane, div_fast(mdr[1][0], mdr[1][0] + 1. * bt.noise_pow03(bl.band(0))));
       }
+      if (FSUM && fsum_cnt && blk >= 125) {          // the lane's term of d1 as mod_difference forms it, weighted as the
+        const double t = div_fast(fabs(mr[0] - mt[0]), 1. + mr[0]);   // accumulator weights the block: W and W^2 D
+        const double w2 = wt * wt;
+        fb_summary_add(fsum_row(kFbSumModDiffW), fsum_own, fb_summary_pick(lane, wt * t, wt));
+        fb_summary_add(fsum_row(kFbSumModDiffSq), fsum_own, fb_summary_pick(lane, w2 * (d1 * t), w2));
+      }
       d1 *= 100. / sqrt((double)NB);                 // MODE_RMS variant, movs.c:243-244
       if (blk >= 125 && lane == MA_RMSMOD) {
         v0 = d1;
@@ -186,6 +234,11 @@
       mc = noise_loudness_total<NB>(mc, 0.);
       ld = noise_loudness_total<NB>(ld, 0.);
       const bool open = blk >= 125 && blk - 13 >= loud_reached;
+      if (FSUM && fsum_cnt && open) {                // the band's share of the squares RmsNoiseLoudAsym averages
+        fb_summary_add(fsum_row(kFbSumNoiseLoudSq), fsum_own, fb_summary_pick(lane, nl * nl_p, 1.));
+        fb_summary_add(fsum_row(kFbSumMissingSq), fsum_own, fb_summary_pick(lane, mc * mc_p, 1.));
+        fb_summary_add(fsum_row(kFbSumLinDist), fsum_own, fb_summary_pick(lane, ld_p, 1.));
+      }
       if (open && lane == MA_NLASYM) {
         v0 = nl;
         w0 = mc;
@@ -246,6 +299,7 @@
     }
   }
 
+  if (FSUM) fb_summary_copy(fsum_cell(fsum.rows), fsum_row(0), fsum_own);
   if (lane < kBandStride) {
 #pragma unroll
     for (int v = 0; v < 6; ++v) cs->vec[kLaFiltRef + v][lane] = la[v][0];

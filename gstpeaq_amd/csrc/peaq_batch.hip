@@ -201,6 +201,12 @@ static_assert(PEAQ_BAND_SUMMARY_NMR_SUM == kSumNmrSum && PEAQ_BAND_SUMMARY_NMR_M
                   PEAQ_BAND_SUMMARY_EXC_TEST_SUM == kSumExcTest && PEAQ_BAND_SUMMARY_MODDIFF1_WSUM == kSumModDiff1 &&
                   PEAQ_BAND_SUMMARY_MODDIFF2_WSUM == kSumModDiff2 && PEAQ_BAND_SUMMARY_NOISELOUD_SUM == kSumNoiseLoud,
               "the summary rows of include/peaq_amd.h and peaq_kernels.h");
+static_assert(PEAQ_FB_BAND_SUMMARY_EXC_REF_SUM == kFbSumExcRef && PEAQ_FB_BAND_SUMMARY_EXC_TEST_SUM == kFbSumExcTest &&
+                  PEAQ_FB_BAND_SUMMARY_MODDIFF_WSUM == kFbSumModDiffW && PEAQ_FB_BAND_SUMMARY_MODDIFF_SQ == kFbSumModDiffSq &&
+                  PEAQ_FB_BAND_SUMMARY_NOISELOUD_SQ == kFbSumNoiseLoudSq &&
+                  PEAQ_FB_BAND_SUMMARY_MISSING_SQ == kFbSumMissingSq && PEAQ_FB_BAND_SUMMARY_LINDIST_SUM == kFbSumLinDist &&
+                  kFbSumRows == 7 && kFbSumRow == kFbBands + 2,
+              "the filter-bank summary rows of include/peaq_amd.h and peaq_kernels.h");
 
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
@@ -208,7 +214,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
                             RunOutputs out);
 
 // peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands,
-// peaq_batch_run_pattern_bands and peaq_batch_run_band_summary: one driver, the points, the trace records, the band
+// peaq_batch_run_pattern_bands, peaq_batch_run_band_summary and peaq_batch_run_fb_band_summary: one driver, the points, the trace records, the band
 // rows and the summary optional -- what `out` holds (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
@@ -464,6 +470,22 @@ extern "C" int peaq_batch_run_band_summary(peaq_ctx* c, int advanced, int channe
                          pair_stride, n_ref, n_test, n_uniform, d_results, stream_, out);
 }
 
+// ---- band summary of the filter-bank path ---------------------------------------------------------------------
+extern "C" int peaq_fb_band_summary_rows(void) { return kFbSumRows; }
+extern "C" int peaq_fb_band_summary_row(void) { return kFbSumRow; }
+
+// The summary's own argument first, as peaq_batch_run_band_summary's: it needs no context and no device.
+extern "C" int peaq_batch_run_fb_band_summary(peaq_ctx* c, int channels, double level_db, int n_pairs,
+                                              const float* d_ref, const float* d_test, size_t pair_stride,
+                                              const uint32_t* n_ref, const uint32_t* n_test, uint32_t n_uniform,
+                                              double* d_summary, peaq_result* d_results, void* stream_) {
+  if (int rc = check_output("peaq_batch_run_fb_band_summary", "d_summary", d_summary, true)) return rc;
+  RunOutputs out;
+  out.fsum.rows = d_summary;
+  return batch_run_entry("peaq_batch_run_fb_band_summary", c, 1, channels, level_db, n_pairs, d_ref, d_test, pair_stride,
+                         n_ref, n_test, n_uniform, d_results, stream_, out);
+}
+
 extern "C" size_t peaq_trace_sizes(size_t* frame_bytes, size_t* block_bytes) {
   if (frame_bytes) *frame_bytes = sizeof(peaq_frame_trace);
   if (block_bytes) *block_bytes = sizeof(peaq_block_trace);
@@ -597,10 +619,19 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(c->sum_saved.reserve((size_t)n_pairs * sum_pair_doubles * sizeof(double)));
     out.sum.saved = c->sum_saved.as<double>();
   }
+  // ... and the filter-bank summary likewise with the filter-bank back end's launches; a run has one of the two
+  // summaries (launch_fb_backend refuses both), so the saved copy is the same buffer
+  const size_t fsum_pair_doubles = (size_t)channels * kFbSumRows * kFbSumRow;
+  if (out.has_fsum()) {
+    HIP_TRY(c->sum_saved.reserve((size_t)n_pairs * fsum_pair_doubles * sizeof(double)));
+    out.fsum.saved = c->sum_saved.as<double>();
+  }
 
   HIP_TRY(hipEventRecord(c->batch_begin, stream));
   HIP_TRY(launch_state_init(c->state.as<PairState>(), advanced, n_pairs, stream));
   if (out.has_sum()) HIP_TRY(hipMemsetAsync(out.sum.rows, 0, (size_t)n_pairs * sum_pair_doubles * sizeof(double), stream));
+  if (out.has_fsum())                                // (before the fork below: the filter-bank path's stream waits for it)
+    HIP_TRY(hipMemsetAsync(out.fsum.rows, 0, (size_t)n_pairs * fsum_pair_doubles * sizeof(double), stream));
   if (out.has_pts()) HIP_TRY(launch_points_init(out.pts.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
@@ -718,6 +749,8 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   if (fb_done) HIP_TRY(hipStreamWaitEvent(stream, fb_done, 0));
   if (out.has_sum())
     HIP_TRY(launch_summary_restore(c->state.as<PairState>(), advanced, out.sum, n_pairs, (unsigned)sum_pair_doubles, stream));
+  if (out.has_fsum())
+    HIP_TRY(launch_fb_summary_restore(c->state.as<PairState>(), out.fsum, n_pairs, (unsigned)fsum_pair_doubles, stream));
   if (d_results)
     HIP_TRY(launch_finalize(c->state.as<PairState>(), advanced, channels, n_pairs,
                             reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));

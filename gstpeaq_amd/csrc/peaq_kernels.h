@@ -239,6 +239,23 @@ struct FbBandArgs {
   uint32_t planes;              // kFbBand* bits; the slot of a plane is the rank of its bit among the set ones
 };
 
+// ---- per-band summary of the filter-bank path (peaq_batch_run_fb_band_summary) --------------
+// The term planes above reduced over the pair's COUNTED blocks (first .. last block above the data boundary) where they
+// come up: one row per quantity, kFbSumRow doubles -- the 40 bands, the row's denominator, a zero.  The rows mirror
+// PEAQ_FB_BAND_SUMMARY_* in include/peaq_amd.h (peaq_batch.hip asserts them).  A kernel argument of the filter-bank
+// summary instantiation only, like FbBandArgs; the arrays work as SummaryArgs'.
+enum { kFbSumExcRef, kFbSumExcTest, kFbSumModDiffW, kFbSumModDiffSq, kFbSumNoiseLoudSq, kFbSumMissingSq, kFbSumLinDist,
+       kFbSumRows };
+constexpr int kFbSumRow = 42;
+struct FbSummaryArgs {
+  double* rows;                 // [pair][channel][kFbSumRows][kFbSumRow], 16-byte aligned: the caller's array, and between
+                                // the launches of a run the pair's running rows (loaded at entry, stored at exit)
+  double* saved;                // the same shape (scratch): the rows as they were when the pair last turned tentative
+};
+// after a run's last filter-bank launch: a pair that ends tentative gets its saved rows back (summary_restore_kernel)
+hipError_t launch_fb_summary_restore(const PairState* state, const FbSummaryArgs& fsum, unsigned n_pairs,
+                                     unsigned pair_doubles, hipStream_t stream);
+
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
@@ -252,19 +269,24 @@ struct RunOutputs {
   FbBandArgs fbnd{};            // peaq_batch_run_fb_bands
   PatternBandArgs pbd{};        // peaq_batch_run_pattern_bands
   SummaryArgs sum{};            // peaq_batch_run_band_summary
+  FbSummaryArgs fsum{};         // peaq_batch_run_fb_band_summary
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
   bool has_fbnd() const { return fbnd.bands != nullptr; }
   bool has_pbd() const { return pbd.bands != nullptr; }
   bool has_sum() const { return sum.rows != nullptr; }
-  bool any() const { return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum(); }
+  bool has_fsum() const { return fsum.rows != nullptr; }
+  bool any() const {
+    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum();
+  }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first
-// that is present (out.fbnd is the other path's).  launch_backend in peaq_backend.hip has the table of what it refuses.
+// that is present (out.fbnd and out.fsum are the other path's).  launch_backend in peaq_backend.hip has the table of what it refuses.
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out = RunOutputs());
-// The instantiation of the filter-bank back end: bands (out.fbnd), trace, points, a.debug, plain -- the first that is
-// present (out.bnd, out.pbd and out.sum are the other path's: this one runs its plain kernels beside them).
+// The instantiation of the filter-bank back end: summary (out.fsum), bands (out.fbnd), trace, points, a.debug, plain --
+// the first that is present (out.bnd, out.pbd and out.sum are the other path's: this one runs its plain kernels beside
+// them).
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream,
                              const RunOutputs& out = RunOutputs());
 

@@ -543,7 +543,7 @@ int peaq_batch_run_pattern_bands (peaq_ctx *ctx, int channels, double playback_l
  * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs.  PEAQ_ERR_ARG, before a context
  * or a device is touched and with a message that names the value: d_summary NULL or not 16-byte aligned, and everything
  * peaq_batch_run refuses.  A run of its own, like the band traces, the trace and the trajectory.  The filter-bank
- * path's 40 bands have no summary. */
+ * path's 40 bands have a summary of their own: peaq_batch_run_fb_band_summary, below. */
 #define PEAQ_BAND_SUMMARY_NMR_SUM        0
 #define PEAQ_BAND_SUMMARY_NMR_MAX        1
 #define PEAQ_BAND_SUMMARY_NMR_DISTURBED  2
@@ -560,6 +560,67 @@ int peaq_batch_run_band_summary (peaq_ctx *ctx, int advanced, int channels, doub
                                  double *d_summary /* device */, peaq_result *d_results /* device, may be NULL */,
                                  void *stream);
 /* (peaq_run_pair_band_summary, the same for one pair from host memory: after peaq_run_pair_pattern_bands below) */
+
+/* ---- band summary of the filter-bank path: the 40 bands behind RmsModDiff, RmsNoiseLoudAsym and AvgLinDist -------
+ * Three of the advanced version's five MOVs come from the filter-bank path.  peaq_batch_run_fb_band_summary reduces
+ * the term planes of peaq_batch_run_fb_bands over the pair's blocks in the run that scores the batch, under the
+ * accumulators' own gates, and writes peaq_fb_band_summary_rows () = 7 rows of peaq_fb_band_summary_row () = 42
+ * doubles per pair and channel (advanced version only: there is no `advanced` argument):
+ *   d_summary[((p * channels + c) * 7 + k) * 42 + b],  b < 40; entry 40 of every row holds that row's denominator,
+ *   entry 41 is written 0.  A stereo pair takes 4704 bytes.
+ *
+ * Counted blocks.  PEAQ_TRACE_ABOVE is defined as in the block trace (any reference channel, flush block included).
+ * With A the set of the pair's blocks that have it, the counted blocks are min A .. max A inclusive -- blocks in
+ * between that are below the data boundary count too -- and none if A is empty: what the reference's accumulators
+ * count (movaccum.c:317-362), as for the frames of peaq_batch_run_band_summary.
+ *
+ * Rows.  The plane names are those of PEAQ_FB_BAND_*.  Per block and channel W = sum_b MODWT[b] (the block trace's
+ * ch[c][1]), D = sum_b MODDIFF[b], L = the block trace's ch[c][2] (0.6 sum_b NOISELOUD[b], and 0 where that is below
+ * 0.1), M = ch[c][3] (0.6 sum_b MISSING[b]):
+ *   k  PEAQ_FB_BAND_SUMMARY_  value at band b < 40                                              entry 40
+ *   0  EXC_REF_SUM            sum over the counted blocks of EXC_REF[b], FP64, in block order    their number n
+ *   1  EXC_TEST_SUM           the same of EXC_TEST[b]                                           n
+ *   2  MODDIFF_WSUM           sum over the counted blocks with PEAQ_TRACE_MOD_OPEN (>= 125) of   sum of those W
+ *                             W MODDIFF[b]
+ *   3  MODDIFF_SQ             sum over the same blocks of W^2 D MODDIFF[b]: the band's share    sum of those W^2
+ *                             of the square RmsModDiff averages
+ *   4  NOISELOUD_SQ           sum over the counted blocks with PEAQ_TRACE_LOUD_OPEN of          their number m
+ *                             L NOISELOUD[b] (0 for a block whose L is floored to 0)
+ *   5  MISSING_SQ             sum over the same blocks of M MISSING[b]                          m
+ *   6  LINDIST_SUM            sum over the same blocks of LINDIST[b]                            m
+ * A pair with no counted block reads 0 everywhere, denominators included.  The context's
+ * swap_mod_patts_for_noise_loudness_movs acts on MISSING and LINDIST as in the band trace.  With the MOVs of the same
+ * call (order of the advanced version: 0, 1, 4):
+ *   RmsModDiff_A       = mean_c (100 / sqrt 40) sqrt (sum_b row3 / row3[40])
+ *   RmsNoiseLoudAsym_A = mean_c (sqrt (0.6 sum_b row4 / m) + 0.5 sqrt (0.6 sum_b row5 / m))
+ *   AvgLinDist_A       = mean_c 0.6 sum_b row6 / m
+ *   sum_b row2 is the sum over the same blocks of W D; per block, from the block trace: ch[c][1] ch[c][0] sqrt 40 / 100
+ *
+ * Every row of the n_pairs pairs is written completely; memory past them is left untouched.  d_summary is working
+ * memory of the call while it runs and valid after the stream has been synchronised; the context's second array (the
+ * rows as they were when a pair last turned tentative) is the one peaq_batch_run_band_summary uses: PEAQ_ERR_NOMEM if
+ * it cannot be reserved, before anything is enqueued.
+ *
+ * d_results (may be NULL): bit for bit what peaq_batch_run writes for the same inputs in the advanced version; the
+ * context's settings and FIR mode apply as they do there.  PEAQ_ERR_ARG, before a context or a device is touched:
+ * d_summary NULL or not 16-byte aligned (the address is in the message), and everything peaq_batch_run refuses.  A run
+ * of its own, like the other band outputs. */
+#define PEAQ_FB_BAND_SUMMARY_EXC_REF_SUM   0
+#define PEAQ_FB_BAND_SUMMARY_EXC_TEST_SUM  1
+#define PEAQ_FB_BAND_SUMMARY_MODDIFF_WSUM  2
+#define PEAQ_FB_BAND_SUMMARY_MODDIFF_SQ    3
+#define PEAQ_FB_BAND_SUMMARY_NOISELOUD_SQ  4
+#define PEAQ_FB_BAND_SUMMARY_MISSING_SQ    5
+#define PEAQ_FB_BAND_SUMMARY_LINDIST_SUM   6
+
+int peaq_fb_band_summary_rows (void);                 /* 7 */
+int peaq_fb_band_summary_row (void);                  /* 42: doubles per row */
+int peaq_batch_run_fb_band_summary (peaq_ctx *ctx, int channels, double playback_level_db, int n_pairs,
+                                    const float *d_ref, const float *d_test, size_t pair_stride,
+                                    const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                                    double *d_summary /* device */, peaq_result *d_results /* device, may be NULL */,
+                                    void *stream);
+/* (peaq_run_pair_fb_band_summary, the same for one pair from host memory: after peaq_run_pair_band_summary below) */
 
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
@@ -765,6 +826,12 @@ int peaq_run_pair_band_summary (peaq_ctx *ctx, int advanced, int channels, doubl
                                 uint32_t rate, uint32_t max_lag,
                                 const float *ref, size_t n_ref, const float *test, size_t n_test,
                                 double *summary /* host */, peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_fb_band_summary (above) for one pair from HOST memory, rows into a host array [channels][7][42]:
+ * upload, conversion and alignment as in peaq_run_pair_band_summary.  out (may be NULL): the pair's result. */
+int peaq_run_pair_fb_band_summary (peaq_ctx *ctx, int channels, double playback_level_db,
+                                   uint32_t rate, uint32_t max_lag,
+                                   const float *ref, size_t n_ref, const float *test, size_t n_test,
+                                   double *summary /* host */, peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
