@@ -31,6 +31,7 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    PATTERN_BAND_PLANES,
                    batch_band_summary, run_pair_band_summary, BAND_SUMMARY_ROWS,
                    batch_fb_band_summary, run_pair_fb_band_summary, FB_BAND_SUMMARY_ROWS,
+                   batch_windows, run_pair_windows, window_frames, sliding_windows, WINDOWS_MAX,
                    MOV_NAMES_BASIC, MOV_NAMES_ADVANCED)
 
 __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_trajectory", "build_library", "debug_backend", "debug_frontend", "debug_filterbank", "debug_wave", "debug_common_tables", "run_pair",
@@ -46,6 +47,7 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "PATTERN_BAND_PLANES",
            "batch_band_summary", "run_pair_band_summary", "BAND_SUMMARY_ROWS",
            "batch_fb_band_summary", "run_pair_fb_band_summary", "FB_BAND_SUMMARY_ROWS",
+           "batch_windows", "run_pair_windows", "window_frames", "sliding_windows", "WINDOWS_MAX",
            "Gain", "measure_gain", "cut_scaled", "gain_workspace_bytes", "gain_records", "gain_mode", "GAIN_DTYPE", "GAIN_MODES",
            "GAIN_PER_CHANNEL", "GAIN_F_SILENT", "GAIN_F_NONFINITE", "GAIN_F_ZERO", "GAIN_F_RANGE",
            "SubDelay", "refine_delay", "cut_shifted", "subsample_tables", "subdelay_workspace_bytes", "SUBDELAY_DTYPE", "SUB_STEPS",

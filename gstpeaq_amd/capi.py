@@ -96,6 +96,7 @@ class Track(C.Structure):
 TRACK_F_NONE, TRACK_F_RANGE = 1, 2
 TRACK_MAX_E, TRACK_MAX_STEP, TRACK_MAX_SEGMENTS_PER_CALL = 1 / 64, 1 / 256, 1 << 20
 TRACK_WINDOW = 16384
+WINDOWS_MAX = 4096                                # peaq_batch_run_windows: windows per call (PEAQ_WINDOWS_MAX)
 TRACK_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("n_windows", "<u4"), ("n_valid", "<u4"), ("n_filled", "<u4"),
                         ("n_segments", "<u4"), ("d_min", "<f8"), ("d_max", "<f8"), ("max_abs_e", "<f8")])
 
@@ -324,6 +325,14 @@ def load_library():
                                                   u32p, C.c_uint32, vp, vp, vp]
         L.peaq_run_pair_band_summary.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t,
                                                  fp, C.c_size_t, vp, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_windows"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_window_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        L.peaq_batch_run_windows.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32,
+                                             vp, C.c_int, vp, vp, vp]
+        L.peaq_batch_windows_workspace_bytes.restype = C.c_size_t
+        L.peaq_batch_windows_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.peaq_run_pair_windows.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp, C.c_size_t,
+                                            vp, C.c_int, vp, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_run_fb_band_summary"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_fb_band_summary_rows.argtypes = []
         L.peaq_fb_band_summary_row.argtypes = []
@@ -2210,6 +2219,85 @@ def run_pair_band_summary(ctx, advanced, ref, test, playback_level=92.0, rate=48
                                             out.ctypes.data_as(C.POINTER(C.c_double))))
     fc, _ = band_tables(advanced)
     res = dict(rows=rows, fc=fc, result=_result_dict(out, advanced), **_band_summary_views(rows, n_bands))
+    if align is not None:
+        res["delay"] = _delay_dict(rec)
+    return res
+
+
+def window_frames(n_ref, n_test, start, length):
+    """(first, count): the FFT frames the window {start, length} covers of a pair with these lengths (peaq_window_frames;
+    samples per channel at 48 kHz)"""
+    first, count = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().peaq_window_frames(int(n_ref), int(n_test), int(start), int(length), C.byref(first),
+                                             C.byref(count)))
+    return first.value, count.value
+
+
+def sliding_windows(n, length, hop=None):
+    """[start, length] rows (np.uint32 [k, 2]) of the windows of `length` samples every `hop` (default: length) that
+    cover [0, n): all of the same length but the last, which ends at n"""
+    n, length = int(n), int(length)
+    hop = length if hop is None else int(hop)
+    assert n > 0 and length > 0 and hop > 0
+    rows, start = [], 0
+    while True:
+        rows.append((start, min(length, n - start)))
+        if start + length >= n:
+            break
+        start += hop
+    return np.array(rows, dtype=np.uint32).reshape(-1, 2)
+
+
+def _windows_array(windows):
+    w = np.ascontiguousarray(windows, dtype=np.uint32).reshape(-1, 2)
+    return w, C.c_void_p(w.ctypes.data) if len(w) else None
+
+
+def batch_windows(ctx, ref, test, windows, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
+                  stream=None, sync=True, d_windows=None, results=None, gain=None, gain_per_channel=False,
+                  max_gain_db=40.0, subsample=False):
+    """The score of time windows inside every pair, in the run that scores the batch (peaq_batch_run_windows, basic
+    version; include/peaq_amd.h has which frames a window covers and what its reading is: a view into the running
+    stream, not a cold start).  windows: [start, length] rows in samples per channel at 48 kHz, shared by all pairs
+    (sliding_windows makes them).  ref/test, n_ref/n_test, rate, align, gain and subsample as for batch_trace.
+    d_windows / results: optional CUDA float64 tensors [n_pairs, n_windows, 16] / [n_pairs, 16] to write into.
+    Returns (windows, results): lists of result dicts, windows[p][w], (sync=True) or the device tensors."""
+    import torch
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample)
+    n_pairs, stride, channels = ref.shape
+    w, w_ptr = _windows_array(windows)
+    with _torch_stream(stream):
+        if d_windows is None:
+            d_windows = torch.empty((n_pairs, max(len(w), 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+        if results is None:
+            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_windows.is_cuda and d_windows.dtype == torch.float64 and d_windows.is_contiguous()
+    assert tuple(d_windows.shape) == (n_pairs, max(len(w), 1), RESULT_DOUBLES)
+    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
+    _check(ctx.L.peaq_batch_run_windows(ctx.h, channels, float(playback_level), n_pairs, C.c_void_p(ref.data_ptr()),
+                                        C.c_void_p(test.data_ptr()), stride, *len_args, stride, w_ptr, len(w),
+                                        C.c_void_p(d_windows.data_ptr()), C.c_void_p(results.data_ptr()),
+                                        _stream_ptr(stream)))
+    if not sync:
+        return d_windows, results
+    torch.cuda.synchronize(ref.device)
+    return ([[_result_dict(r, False) for r in row] for row in d_windows.cpu().numpy()],
+            [_result_dict(r, False) for r in results.cpu().numpy()])
+
+
+def run_pair_windows(ctx, ref, test, windows, playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_windows: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
+    first with align = a max_lag in 48 kHz samples; the windows count 48 kHz samples of the signals as scored.  Returns
+    a dict: windows (result dicts, one per window), result (a result dict) and, with align, delay."""
+    ref, test, ch, pair_args = _host_pair(ref, test)
+    w, w_ptr = _windows_array(windows)
+    rows = np.zeros((max(len(w), 1), RESULT_DOUBLES))
+    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_windows(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
+                                       *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+    res = dict(windows=[_result_dict(r, False) for r in rows[:len(w)]], result=_result_dict(out, False))
     if align is not None:
         res["delay"] = _delay_dict(rec)
     return res

@@ -28,6 +28,9 @@
  * --interval=SECONDS also prints, before those two lines, one line per reading taken every SECONDS of the (resampled)
  * signals, "Time %.3f s: ODG %.3f, DI %.3f" -- what the element's odg / di properties read at that point of the stream
  * (gstpeaq.c:484-497; peaq_run_pair_trajectory).
+ * --windows=SECONDS[:HOP_SECONDS] (basic version) also prints, before those two lines, one line per window of SECONDS
+ * taken every HOP_SECONDS through the signals as scored, "window START_S END_S FRAMES ODG DI": the reading of the
+ * frames the window covers, in the context of the running stream (peaq_run_pair_windows).
  * --list=FILE scores many pairs in one run: FILE holds one pair per line, REF<TAB>TEST (empty lines and lines that
  * start with # are skipped).  The files' data chunks are handed to the engine as they are, in their own sample format
  * (peaq_batch_run_host: decoded, converted to 48 kHz and, with --align, aligned on the device), grouped by format,
@@ -594,6 +597,11 @@ usage (const char *prog)
       "                block above the data boundary) and their denominators: exc_ref_sum, exc_test_sum, moddiff_wsum,\n"
       "                moddiff_sq, noiseloud_sq, missing_sq, lindist_sum (the plain one-call mode; with\n"
       "                --device-resample, --align; a run of its own, like --bands)\n"
+      "  --windows=S[:HOP] basic version: also print, before the two result lines, the score of every window of S\n"
+      "                seconds taken every HOP seconds (default S) through the files as scored, the last one ending with\n"
+      "                them: one line `window START_S END_S FRAMES ODG DI` each.  A window reads the frames it covers\n"
+      "                in the context of the running stream, not the excerpt from a cold start (the plain one-call mode;\n"
+      "                with --device-resample, --align; a run of its own, like --bands)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -922,6 +930,63 @@ done:
   return rc;
 }
 
+/* --windows=S[:HOP]: the pair through peaq_run_pair_windows with the sliding windows of the scored length -- starts
+ * every `hop` samples from 0, `length` samples each, up to the first that reaches the end, which ends there -- one line
+ * per window.  With --align the scored length is the common part, known after the run: the windows are laid over the
+ * longer file and those of the common part printed (a window that reaches the end of the scored signals reads through
+ * their last frame wherever its own end lies).  Prints the delay line of --align. */
+static int
+print_windows (uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
+    const wav_t *ref, const wav_t *test, peaq_result *r)
+{
+  const uint32_t n_ref = rate == 48000 ? (uint32_t) ref->frames : peaq_resampled_length (ref->frames, rate);
+  const uint32_t n_test = rate == 48000 ? (uint32_t) test->frames : peaq_resampled_length (test->frames, rate);
+  uint32_t n = n_ref > n_test ? n_ref : n_test;
+  size_t n_windows = 1, k;
+  peaq_window *w;
+  peaq_result *rows;
+  peaq_delay delay;
+  int rc = 1;
+  if (n > length)
+    n_windows += ((size_t) n - length + hop - 1) / hop;
+  if (n_windows > PEAQ_WINDOWS_MAX) {
+    printf ("Error: %zu windows are more than %d\n", n_windows, PEAQ_WINDOWS_MAX);
+    return 1;
+  }
+  w = malloc (n_windows * sizeof *w);
+  rows = malloc (n_windows * sizeof *rows);
+  if (!w || !rows) {
+    printf ("Error: out of memory for the windows\n");
+    goto done;
+  }
+  for (k = 0; k < n_windows; k++) {
+    w[k].start = (uint32_t) (k * hop);
+    w[k].length = length;
+  }
+  if (peaq_run_pair_windows (ctx, ref->channels, level, rate, align_lag, ref->samples, ref->frames, test->samples,
+          test->frames, w, (int) n_windows, rows, &delay, r) != PEAQ_OK) {
+    printf ("Error: %s\n", peaq_last_error ());
+    goto done;
+  }
+  if (align_lag) {
+    uint32_t skip_ref, skip_test;
+    printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
+    peaq_aligned_lengths (delay.lag, n_ref, n_test, &skip_ref, &skip_test, &n);
+  }
+  for (k = 0; k < n_windows; k++) {
+    const uint64_t end = (uint64_t) w[k].start + length;
+    printf ("window %.3f %.3f %.0f %.3f %.3f\n", w[k].start / 48000., (end < n ? end : n) / 48000., rows[k].frames,
+        rows[k].odg, rows[k].di);
+    if (end >= n)
+      break;
+  }
+  rc = 0;
+done:
+  free (w);
+  free (rows);
+  return rc;
+}
+
 int
 main (int argc, char **argv)
 {
@@ -950,6 +1015,7 @@ main (int argc, char **argv)
   uint32_t pattern_band_planes = PEAQ_PAT_BAND_NOISELOUD;
   const char *band_summary_path = NULL;   /* --band-summary=FILE, peaq_run_pair_band_summary */
   const char *fb_band_summary_path = NULL;   /* --fb-band-summary=FILE, peaq_run_pair_fb_band_summary */
+  uint32_t windows_length = 0, windows_hop = 0;   /* != 0: --windows=S[:HOP], peaq_run_pair_windows */
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -1133,6 +1199,23 @@ main (int argc, char **argv)
       return 1;
     } else if (!strncmp (argv[i], "--fb-band-summary=", 18))
       fb_band_summary_path = argv[i] + 18;
+    else if (!strcmp (argv[i], "--windows") || !strcmp (argv[i], "--windows=")) {
+      fprintf (stderr, "Failed to initialize: --windows needs a length in seconds (--windows=SECONDS[:HOP_SECONDS])\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--windows=", 10)) {
+      char *end;
+      const double len_s = strtod (argv[i] + 10, &end);
+      double hop_s = len_s;
+      if (end != argv[i] + 10 && *end == ':' && end[1])
+        hop_s = strtod (end + 1, &end);
+      if (end == argv[i] + 10 || *end || !(len_s * 48000. >= 0.5 && len_s * 48000. < 4294967295.) ||
+          !(hop_s * 48000. >= 0.5 && hop_s * 48000. < 4294967295.)) {
+        fprintf (stderr, "Failed to initialize: invalid windows %s\n", argv[i] + 10);
+        return 1;
+      }
+      windows_length = (uint32_t) llround (len_s * 48000.);
+      windows_hop = (uint32_t) llround (hop_s * 48000.);
+    }
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -1203,6 +1286,18 @@ main (int argc, char **argv)
   }
   if (fb_band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
     fprintf (stderr, "Failed to initialize: --fb-band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
+    return 1;
+  }
+  if (windows_length && advanced) {
+    fprintf (stderr, "Failed to initialize: --windows is for the basic version (the advanced version's windows are not built)\n");
+    return 1;
+  }
+  if (windows_length && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --windows belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (windows_length && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || fb_band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --windows is a run of its own (not with --bands, --fb-bands, --pattern-bands, --band-summary, --fb-band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
@@ -1367,7 +1462,10 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (fb_band_summary_path) {
+    if (windows_length) {
+      if (print_windows (windows_length, windows_hop, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (fb_band_summary_path) {
       if (write_fb_band_summary (fb_band_summary_path, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (band_summary_path) {

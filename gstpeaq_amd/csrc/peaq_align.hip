@@ -839,3 +839,25 @@ extern "C" int peaq_run_pair_fb_band_summary(peaq_ctx* c, int channels, double l
                                                                  nullptr);
                          });
 }
+
+// (n_windows records per pair: neither a count nor a capacity of the caller's)
+extern "C" int peaq_run_pair_windows(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                     const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                     const peaq_window* windows, int n_windows, peaq_result* out_windows,
+                                     peaq_delay* delay, peaq_result* out) {
+  const std::string w("peaq_run_pair_windows");
+  if (!windows) return fail(PEAQ_ERR_ARG, w + ": windows is NULL");
+  if (n_windows < 1 || n_windows > PEAQ_WINDOWS_MAX)
+    return fail(PEAQ_ERR_ARG, w + ": n_windows " + std::to_string(n_windows) + " is outside 1 .. " +
+                                  std::to_string(PEAQ_WINDOWS_MAX));
+  for (int i = 0; i < n_windows; ++i)
+    if (windows[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(i) + " has length 0");
+  if (!out_windows) return fail(PEAQ_ERR_ARG, w + ": out_windows is NULL");
+  PairRows rows[1] = {{PairRows::kPair, (size_t)n_windows * sizeof(peaq_result), out_windows, 1, "", nullptr}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_windows(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len,
+                                                         pp.len + 1, 0, windows, n_windows,
+                                                         rows[0].dev.as<peaq_result>(), d_res, nullptr);
+                         });
+}

@@ -208,14 +208,17 @@ static_assert(PEAQ_FB_BAND_SUMMARY_EXC_REF_SUM == kFbSumExcRef && PEAQ_FB_BAND_S
                   kFbSumRows == 7 && kFbSumRow == kFbBands + 2,
               "the filter-bank summary rows of include/peaq_amd.h and peaq_kernels.h");
 
+static_assert(sizeof(peaq_window) == sizeof(WindowSpan) && offsetof(peaq_window, length) == offsetof(WindowSpan, length),
+              "peaq_window of include/peaq_amd.h and WindowSpan");
+
 static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                             const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                             const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, hipStream_t stream,
                             RunOutputs out);
 
 // peaq_batch_run, peaq_batch_run_trajectory, peaq_batch_run_trace, peaq_batch_run_bands, peaq_batch_run_fb_bands,
-// peaq_batch_run_pattern_bands, peaq_batch_run_band_summary and peaq_batch_run_fb_band_summary: one driver, the points, the trace records, the band
-// rows and the summary optional -- what `out` holds (`who` names the entry in messages)
+// peaq_batch_run_pattern_bands, peaq_batch_run_band_summary, peaq_batch_run_fb_band_summary and peaq_batch_run_windows:
+// one driver, the points, the trace records, the band rows, the summary and the windows optional -- what `out` holds (`who` names the entry in messages)
 static int batch_run_entry(const char* who, peaq_ctx* c, int advanced, int channels, double level_db, int n_pairs,
                            const float* d_ref, const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                            const uint32_t* n_test, uint32_t n_uniform, peaq_result* d_results, void* stream_,
@@ -497,6 +500,52 @@ extern "C" size_t peaq_batch_trajectory_workspace_bytes(int advanced, int channe
   return peaq_batch_workspace_bytes(advanced, channels, n_pairs, n_max) + trajectory_snap_bytes(n_pairs, n_points);
 }
 
+// ---- scores of time windows inside each pair (basic version) -------------------------------------------------------
+extern "C" int peaq_window_frames(uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length, uint32_t* first,
+                                  uint32_t* count) {
+  if (!first && !count) return fail(PEAQ_ERR_ARG, "peaq_window_frames: NULL argument");
+  uint32_t f = 0, e = 0;
+  window_frames(n_ref, n_test, start, length, f, e);
+  if (first) *first = f;
+  if (count) *count = e - f;
+  return PEAQ_OK;
+}
+
+// the scratch a windows run adds to the plain run's: the trace records the replay reads, the windows' snapshots, the
+// windows themselves; 0 when it does not fit size_t
+static size_t windows_scratch_bytes(int n_pairs, uint32_t max_frames, int n_windows) {
+  const size_t np = (size_t)std::max(n_pairs, 0), nw = (size_t)std::max(n_windows, 0);
+  const size_t per_pair = (size_t)std::max<uint32_t>(max_frames, 1) * sizeof(FrameTrace) + nw * sizeof(PointSnap);
+  if (np && per_pair > (SIZE_MAX - nw * sizeof(WindowSpan)) / np) return 0;
+  return np * per_pair + nw * sizeof(WindowSpan);
+}
+
+// The windows' own arguments first, as the traces': they need no context and no device.
+extern "C" int peaq_batch_run_windows(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
+                                      const float* d_test, size_t pair_stride, const uint32_t* n_ref,
+                                      const uint32_t* n_test, uint32_t n_uniform, const peaq_window* windows,
+                                      int n_windows, peaq_result* d_windows, peaq_result* d_results, void* stream_) {
+  const std::string w("peaq_batch_run_windows");
+  if (int rc = check_not_null(w, "windows", windows)) return rc;
+  if (n_windows < 1 || n_windows > PEAQ_WINDOWS_MAX)
+    return fail(PEAQ_ERR_ARG, w + ": n_windows " + std::to_string(n_windows) + " is outside 1 .. " +
+                                  std::to_string(PEAQ_WINDOWS_MAX));
+  for (int i = 0; i < n_windows; ++i)
+    if (windows[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(i) + " has length 0");
+  if (int rc = check_output(w, "d_windows", d_windows)) return rc;
+  RunOutputs out;
+  out.win.out = reinterpret_cast<ResultRecord*>(d_windows);
+  out.win.windows = reinterpret_cast<const WindowSpan*>(windows);   // (host: batch_run_locked puts them on the device)
+  out.win.n_windows = n_windows;
+  return batch_run_entry("peaq_batch_run_windows", c, 0, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
+                         n_test, n_uniform, d_results, stream_, out);
+}
+
+extern "C" size_t peaq_batch_windows_workspace_bytes(int channels, int n_pairs, uint32_t n_max, int n_windows) {
+  return peaq_batch_workspace_bytes(0, channels, n_pairs, n_max) +
+         windows_scratch_bytes(n_pairs, count_frames(n_max, n_max, kFrame, kHop), n_windows);
+}
+
 // One whole (ref, test) pair from host memory: the batch path with n_pairs = 1 -- for a caller that holds both
 // files (the CLI).  The same frames and blocks as a session fed with the same samples (count_frames), but every
 // kernel sees the whole stream: one front-end launch, the filter-bank path pipelined over its three streams.
@@ -611,6 +660,31 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     out.trc.n_test = d_ntest;
     out.trc.n_uniform = n_uniform;
   }
+  // windows: every FFT back-end launch of the run is the trace instantiation, writing into scratch of the context, and
+  // is followed by the replay of its frames into the windows' snapshots (peaq_windows.hip).  All of it is reserved here,
+  // so that running out of memory is reported before anything is enqueued.
+  const size_t n_wsnaps = out.has_win() ? (size_t)n_pairs * out.win.n_windows : 0;
+  if (out.has_win()) {
+    if (advanced || out.has_trc() || out.has_pts())
+      return fail(PEAQ_ERR_ARG, std::string(who) + ": windows are a run of their own, of the basic version");
+    if (windows_scratch_bytes(n_pairs, max_frames, out.win.n_windows) == 0)
+      return fail(PEAQ_ERR_NOMEM, std::string(who) + ": the windows' scratch exceeds the address space");
+    const size_t trace_stride = std::max<uint32_t>(max_frames, 1);
+    HIP_TRY(c->win_trace.reserve((size_t)n_pairs * trace_stride * sizeof(FrameTrace)));
+    HIP_TRY(c->snaps.reserve(n_wsnaps * sizeof(PointSnap)));
+    HIP_TRY(c->win_list.reserve((size_t)out.win.n_windows * sizeof(WindowSpan)));
+    HIP_TRY(hipMemcpyAsync(c->win_list.p, out.win.windows, (size_t)out.win.n_windows * sizeof(WindowSpan),
+                           hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));           // the caller's array is read by now
+    out.win.windows = c->win_list.as<WindowSpan>();
+    out.win.snap = c->snaps.as<PointSnap>();
+    out.win.trace = c->win_trace.as<FrameTrace>();
+    out.win.trace_stride = trace_stride;
+    out.win.n_ref = d_nref;
+    out.win.n_test = d_ntest;
+    out.win.n_uniform = n_uniform;
+    out.trc = TraceArgs{c->win_trace.as<FrameTrace>(), trace_stride, nullptr, 0, d_nref, d_ntest, n_uniform};
+  }
   // band summary: every FFT back-end launch of the run is the summary instantiation.  The caller's rows start from zero
   // and carry the running sums from launch to launch; the copy a pair takes when it turns tentative goes to scratch of
   // the same shape (reserved here, so that running out of memory is reported before anything is enqueued).
@@ -633,6 +707,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   if (out.has_fsum())                                // (before the fork below: the filter-bank path's stream waits for it)
     HIP_TRY(hipMemsetAsync(out.fsum.rows, 0, (size_t)n_pairs * fsum_pair_doubles * sizeof(double), stream));
   if (out.has_pts()) HIP_TRY(launch_points_init(out.pts.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
+  if (out.has_win()) HIP_TRY(launch_points_init(out.win.snap, n_wsnaps, stream));   // every window starts fresh
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
   const bool with_fb = advanced && max_blocks > 0;
@@ -724,6 +799,10 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
     if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, out));
+    // (windows: this chunk's frames into the windows that meet them, from the trace records just written and from
+    // `recs` -- which e3 below keeps from being reused before the replay has read it)
+    if (!PEAQ_DEV_SKIP_BACKEND && out.has_win())
+      HIP_TRY(launch_window_replay(out.win, recs, f0, nf, channels, n_pairs, c->aux));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;
@@ -756,6 +835,9 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
                             reinterpret_cast<ResultRecord*>(d_results), stream, c->settings));
   if (out.has_pts())
     HIP_TRY(launch_finalize_points(out.pts.snap, advanced, channels, n_pairs, out.pts.n_points, out.d_points, stream,
+                                   c->settings));
+  if (out.has_win())
+    HIP_TRY(launch_finalize_points(out.win.snap, 0, channels, n_pairs, out.win.n_windows, out.win.out, stream,
                                    c->settings));
   HIP_TRY(hipEventRecord(c->batch_end, stream));
   c->batch_pending = true;

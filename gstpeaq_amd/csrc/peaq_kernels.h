@@ -256,10 +256,47 @@ struct FbSummaryArgs {
 hipError_t launch_fb_summary_restore(const PairState* state, const FbSummaryArgs& fsum, unsigned n_pairs,
                                      unsigned pair_doubles, hipStream_t stream);
 
+// ---- scores of time windows inside each pair (peaq_batch_run_windows, basic version) ----------------------
+// Window w of a pair covers FFT frames [first, end) of it (window_frames below: the device and peaq_window_frames use
+// the one rule) and is the read-out of accumulators that start fresh before frame `first` and are fed what the pair's
+// own were fed in those frames.  The feed is the trace instantiation's records of the same launch (scratch of the
+// context) and the front end's scalars; a window's accumulators sit in a PointSnap between the launches of a run.  A
+// kernel argument of window_replay_kernel only (peaq_windows.hip).
+struct WindowSpan { uint32_t start, length; };       // mirrors peaq_window in include/peaq_amd.h
+struct WindowArgs {
+  ResultRecord* out;            // [pair][n_windows]: where the read-out of the snapshots goes (the caller's d_windows)
+  PointSnap* snap;              // [pair][n_windows] (scratch)
+  const WindowSpan* windows;    // [n_windows] (device), shared by all pairs
+  int n_windows;
+  const FrameTrace* trace;      // [pair][trace_stride] (scratch): record f of a pair at its absolute frame index
+  size_t trace_stride;
+  const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform
+  const uint32_t* n_test;
+  uint32_t n_uniform;
+};
+// frames [first, end) of the window {start, length} of a pair with these lengths; T = count_frames of the pair
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void window_frames(uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length, uint32_t& first,
+                          uint32_t& end) {
+  const uint32_t n = n_ref < n_test ? n_ref : n_test, m = n_ref < n_test ? n_test : n_ref;
+  const uint32_t full = n >= (uint32_t)kFrame ? (n - kFrame) / kHop + 1 : 0u;
+  const uint32_t total = full + (m > (uint64_t)full * kHop ? 1u : 0u);
+  const uint64_t e = (uint64_t)start + length;
+  const uint32_t a0 = start < n ? start : n, a1 = e < n ? (uint32_t)e : n;
+  first = start >= m ? total : a0 >= (uint32_t)kFrame ? (a0 - kFrame) / kHop + 1 : 0u;
+  end = e >= m ? total : a1 >= (uint32_t)kFrame ? (a1 - kFrame) / kHop + 1 : 0u;
+}
+// after launch_backend (its trace instantiation) of the same chunk, on the same stream: frames [frame0, frame0 +
+// frames_per_launch) of every pair replayed into the windows that meet them
+hipError_t launch_window_replay(const WindowArgs& win, const double* records, unsigned frame0, unsigned frames_per_launch,
+                                int channels, unsigned n_pairs, hipStream_t stream);
+
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
-// knows (the device length arrays of `pts` and `trc`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
+// knows (the device length arrays of `pts`, `trc` and `win`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
 // and picks the instantiation; sessions, the broker and the stage entries pass none.
 struct RunOutputs {
   PointArgs pts{};              // trajectory (peaq_batch_run_trajectory): interval, n_points; snap from batch_run_locked
@@ -270,6 +307,8 @@ struct RunOutputs {
   PatternBandArgs pbd{};        // peaq_batch_run_pattern_bands
   SummaryArgs sum{};            // peaq_batch_run_band_summary
   FbSummaryArgs fsum{};         // peaq_batch_run_fb_band_summary
+  WindowArgs win{};             // peaq_batch_run_windows: windows, n_windows, out; the rest from batch_run_locked -- which
+                                // also points `trc` at the context's trace scratch: the replay's feed
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
@@ -277,8 +316,9 @@ struct RunOutputs {
   bool has_pbd() const { return pbd.bands != nullptr; }
   bool has_sum() const { return sum.rows != nullptr; }
   bool has_fsum() const { return fsum.rows != nullptr; }
+  bool has_win() const { return win.out != nullptr; }
   bool any() const {
-    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum();
+    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_win();
   }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first

@@ -622,6 +622,56 @@ int peaq_batch_run_fb_band_summary (peaq_ctx *ctx, int channels, double playback
                                     void *stream);
 /* (peaq_run_pair_fb_band_summary, the same for one pair from host memory: after peaq_run_pair_band_summary below) */
 
+/* ---- windows: the score of a stretch of each pair, replayed on the device (basic version) -------------------------
+ * "The worst five seconds", "ODG per scene", a sliding short-term ODG: the reading of the frames a time window covers,
+ * as a full result record.  A trajectory point cannot give it (it averages everything since sample 0, and two points
+ * cannot be subtracted: WinModDiff1, ADB, MFPD and the tentative/saved logic are no differences of sums, the network is
+ * not linear), and the frame trace leaves bandwidths, EHS, energies, accumulation and read-out to the caller.
+ *
+ * A window {start, length} counts samples per channel at 48 kHz.  With n = min (n_ref, n_test), m = max (n_ref,
+ * n_test), T = peaq_frame_count (n_ref, n_test, 0), F (a) = a >= 2048 ? (a - 2048) / 1024 + 1 : 0 (the trajectory's F)
+ * and e = start + length in 64 bits, its frames are [first, end):
+ *     first = start >= m ? T : F (min (start, n)),      end = e >= m ? T : F (min (e, n)),      count = end - first
+ * -- a window that reaches the end of the longer signal takes the flush frame.  peaq_window_frames returns exactly this
+ * (host arithmetic only; first / count may be NULL, not both), and the device uses the same rule.
+ *
+ * The reading of a window is what peaq_session_results would return if
+ *   - the 11 accumulators had been reset to their initial state just before frame `first` (status initial, every field
+ *     zero, the AVG_WINDOW history at its NaN sentinels),
+ *   - they had then been given, for the frames first .. end - 1 in order, exactly what the pair's own accumulators are
+ *     given in those frames: the same tentative / normal turns, the same values and weights, the same gates, and
+ *   - the two energies of totalsnr had been summed over those frames only.
+ * Everything below the accumulators is the pair's own, IN CONTEXT: time smearing, level and pattern adaptation, the
+ * modulation filters, the gate that keeps the first 24 frames out of the modulation MOVs and the loudness gate are
+ * where the running stream has them.  A window is a view into the running stream, NOT a cold-start score of the
+ * excerpt: for that, score the excerpt as a pair of its own -- a pair_stride view into the same buffers through
+ * peaq_batch_run -- whose ear models, adaptation and gates then start cold, at the price of one front end per window.
+ * `frames` of a window's record is count, `fb_blocks` 0.  An empty window (count == 0) reads what the read-out of an
+ * untouched accumulator set reads, like a trajectory point before the first frame.
+ * It follows (same operations, same order, from 0 + x): a window {0, L} with L < m is bit for bit point k of
+ * peaq_batch_run_trajectory with (k + 1) interval == L; a window {0, L} with L >= m is bit for bit d_results; and
+ * d_results is bit for bit peaq_batch_run's.
+ *
+ * windows (HOST, n_windows of them, 1 .. PEAQ_WINDOWS_MAX, none of length 0) are shared by all pairs; d_windows
+ * (device, 16-byte aligned) receives [n_pairs][n_windows] records; d_results may be NULL.  The other arguments, the
+ * refusals (PEAQ_ERR_ARG before a context or a device is touched, the message naming entry and value), stream and
+ * workspace rules are peaq_batch_run's; PEAQ_ERR_NOMEM when the scratch cannot be reserved --
+ * peaq_batch_windows_workspace_bytes: per pair a 128-byte trace record per frame and a 2184-byte snapshot per window on
+ * top of the plain run's.  The call is a run of its own, like the traces and the trajectory.  There is no `advanced`
+ * argument: the advanced version's windows need the filter-bank back end as a second feed and are not built. */
+typedef struct { uint32_t start, length; } peaq_window;   /* samples per channel at 48 kHz */
+#define PEAQ_WINDOWS_MAX 4096
+int peaq_window_frames (uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length,
+                        uint32_t *first, uint32_t *count);
+int peaq_batch_run_windows (peaq_ctx *ctx, int channels, double playback_level_db, int n_pairs,
+                            const float *d_ref, const float *d_test, size_t pair_stride,
+                            const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                            const peaq_window *windows /* host, shared by all pairs */, int n_windows,
+                            peaq_result *d_windows /* device, [n_pairs][n_windows] */,
+                            peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+size_t peaq_batch_windows_workspace_bytes (int channels, int n_pairs, uint32_t n_max, int n_windows);
+/* (peaq_run_pair_windows, the same for one pair from host memory: after peaq_run_pair_fb_band_summary below) */
+
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
  * dominant kernel (the FFT ear-model front end).  Valid after the stream has
@@ -832,6 +882,14 @@ int peaq_run_pair_fb_band_summary (peaq_ctx *ctx, int channels, double playback_
                                    uint32_t rate, uint32_t max_lag,
                                    const float *ref, size_t n_ref, const float *test, size_t n_test,
                                    double *summary /* host */, peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_windows (above) for one pair from HOST memory, the n_windows records into a host array: upload,
+ * conversion and alignment as in peaq_run_pair_trace; the windows count 48 kHz samples of the signals as scored, after
+ * conversion and cut.  out (may be NULL): the pair's result. */
+int peaq_run_pair_windows (peaq_ctx *ctx, int channels, double playback_level_db,
+                           uint32_t rate, uint32_t max_lag,
+                           const float *ref, size_t n_ref, const float *test, size_t n_test,
+                           const peaq_window *windows, int n_windows, peaq_result *out_windows /* host */,
+                           peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
