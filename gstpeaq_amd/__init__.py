@@ -22,6 +22,8 @@ from .capi import (Broker, Context, PeaqError, Session, batch_run, batch_traject
                    PIECES_F_RANGE, PIECES_MAX_PER_PAIR, PIECES_MAX_PER_CALL, locate_steps, steps_candidates, steps_fit, pieces_index, pieces_lengths, estimate_steps, cut_pieces, steps_workspace_bytes,
                    Drift, estimate_drift, cut_drift, drift_lengths, drift_fit, drift_index, drift_windows, drift_workspace_bytes,
                    DRIFT_DTYPE, DRIFT_F_NONE, DRIFT_F_RANGE, DRIFT_WINDOW, DRIFT_MIN_CORR, DRIFT_MAX_E, DRIFT_MAX_WINDOWS,
+                   WideDelay, WIDE_DELAY_DTYPE, WIDE_WAVEFORM, WIDE_ENVELOPE, WIDE_MODES, WIDE_CHUNK, WIDE_MAX_OFFSET, WIDE_F_NONE,
+                   WIDE_F_RANGE, WIDE_F_EDGE, wide_factor, wide_taps, wide_workspace_bytes, decimate, estimate_delay_wide,
                    PCM_FORMATS, PCM_DTYPES,
                    batch_trace, run_pair_trace, frame_count, FrameTrace, BlockTrace, FRAME_TRACE_DTYPE, BLOCK_TRACE_DTYPE,
                    TRACE_ABOVE, TRACE_MOD_OPEN, TRACE_LOUD_OPEN, TRACE_FLUSH,
@@ -60,4 +62,7 @@ __all__ = ["Broker", "Context", "PeaqError", "Session", "batch_run", "batch_traj
            "Drift", "estimate_drift", "cut_drift", "drift_lengths", "drift_fit", "drift_index", "drift_windows",
            "drift_workspace_bytes", "DRIFT_DTYPE", "DRIFT_F_NONE", "DRIFT_F_RANGE", "DRIFT_WINDOW", "DRIFT_MIN_CORR",
            "DRIFT_MAX_E", "DRIFT_MAX_WINDOWS",
+           "WideDelay", "WIDE_DELAY_DTYPE", "WIDE_WAVEFORM", "WIDE_ENVELOPE", "WIDE_MODES", "WIDE_CHUNK", "WIDE_MAX_OFFSET",
+           "WIDE_F_NONE", "WIDE_F_RANGE", "WIDE_F_EDGE", "wide_factor", "wide_taps", "wide_workspace_bytes", "decimate",
+           "estimate_delay_wide",
            "MOV_NAMES_BASIC", "MOV_NAMES_ADVANCED"]

@@ -85,6 +85,22 @@ DRIFT_DTYPE = np.dtype([("lag0", "<i4"), ("flags", "<u4"), ("a", "<f8"), ("e", "
 DELAY_DTYPE = np.dtype([("lag", "<i4"), ("reserved", "<i4"), ("peak", "<f8"), ("runner_up", "<f8"), ("norm", "<f8")])
 
 
+class WideDelay(C.Structure):
+    """mirrors peaq_wide_delay (include/peaq_amd.h)"""
+    _fields_ = [("lag", C.c_int32), ("coarse_lag", C.c_int32), ("factor", C.c_uint32), ("flags", C.c_uint32),
+                ("fine", Delay), ("coarse", Delay)]
+
+
+# PEAQ_WIDE_* (include/peaq_amd.h) and the record as a numpy structured dtype
+WIDE_WAVEFORM, WIDE_ENVELOPE = 0, 1
+WIDE_MODES = {"waveform": WIDE_WAVEFORM, "envelope": WIDE_ENVELOPE}
+WIDE_CHUNK = 248
+WIDE_MAX_OFFSET = 1 << 20
+WIDE_F_NONE, WIDE_F_RANGE, WIDE_F_EDGE = 1, 2, 4
+WIDE_DELAY_DTYPE = np.dtype([("lag", "<i4"), ("coarse_lag", "<i4"), ("factor", "<u4"), ("flags", "<u4"),
+                             ("fine", DELAY_DTYPE), ("coarse", DELAY_DTYPE)])
+
+
 class Track(C.Structure):
     """mirrors peaq_track (include/peaq_amd.h)"""
     _fields_ = [("lag0", C.c_int32), ("flags", C.c_uint32), ("n_windows", C.c_uint32), ("n_valid", C.c_uint32),
@@ -476,6 +492,19 @@ def load_library():
     if hasattr(L, "peaq_debug_wave"):                # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_debug_wave.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, dp, C.c_int, dp, C.c_int, dp]
         L.peaq_debug_common_tables.argtypes = [dp, dp]
+    if hasattr(L, "peaq_batch_decimate"):            # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_wide_delay_size.restype = C.c_size_t
+        L.peaq_wide_factor.restype = C.c_uint32
+        L.peaq_wide_factor.argtypes = [C.c_uint32]
+        L.peaq_wide_taps.argtypes = [C.c_uint32, dp]
+        L.peaq_batch_decimate.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u32p, C.c_uint32, C.c_uint32, C.c_int, vp,
+                                          C.c_size_t, vp]
+        L.peaq_batch_estimate_delay_wide.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32,
+                                                     C.c_uint32, C.c_int, C.c_uint32, C.POINTER(WideDelay), vp]
+        L.peaq_wide_workspace_bytes.restype = C.c_size_t
+        L.peaq_wide_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+        L.peaq_run_pair_wide.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, fp,
+                                         C.c_size_t, fp, C.c_size_t, C.POINTER(WideDelay), dp]
     ip = C.POINTER(C.c_int)
     L.peaq_broker_create.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(vp)]
     L.peaq_broker_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.c_int,
@@ -1518,6 +1547,99 @@ def cut_pieces(ctx, x, skip, n_keep, n_pieces, b, a, e, n_in=None, out=None, str
     return out
 
 
+def wide_factor(max_offset):
+    """the decimation factor of a wide search of +-max_offset samples, a power of two in 2 .. 64; 0: max_offset is
+    outside 1 .. 2^20 (peaq_wide_factor, host arithmetic, no GPU)"""
+    return int(load_library().peaq_wide_factor(int(max_offset) if 0 <= int(max_offset) <= 0xFFFFFFFF else 0))
+
+
+def wide_taps(M):
+    """the decimator's 16 M + 1 taps exactly as uploaded, float64, tap j = -8M first (peaq_wide_taps, no GPU)"""
+    M = int(M)
+    h = np.zeros(16 * M + 1 if 0 < M <= 64 else 1)
+    n = load_library().peaq_wide_taps(M, h.ctypes.data_as(C.POINTER(C.c_double)))
+    if n < 0:
+        _check(n)
+    assert n == len(h)
+    return h
+
+
+def wide_mode(mode):
+    """PEAQ_WIDE_* of a name ('waveform' 'envelope') or of the number itself"""
+    return WIDE_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def wide_workspace_bytes(channels, n_pairs, n_max, max_offset):
+    """the staging of estimate_delay_wide for a shape (peaq_wide_workspace_bytes)"""
+    return int(load_library().peaq_wide_workspace_bytes(int(channels), int(n_pairs), int(n_max), int(max_offset)))
+
+
+def decimate(ctx, x, M, mode, n=None, out=None, stream=None):
+    """The mono sum of x (its magnitude with mode 'envelope', and then less its mean), low-passed and decimated by M
+    (peaq_batch_decimate): x CUDA float32 [n_pairs, n_samples, channels], n optional per-pair lengths.  out: optional
+    tensor [n_pairs, stride] to write into (entries past ceil (n / M) keep what they held); without it a zero-filled one
+    with an even stride is made.  Returns (y, n_dec): the tensor and the decimated lengths (numpy uint32 [n_pairs])."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_pairs, stride, channels = x.shape
+    M = int(M)
+    a_n = None if n is None else np.ascontiguousarray(n, dtype=np.uint32)
+    assert a_n is None or a_n.shape == (n_pairs,)
+    lens = np.full(n_pairs, stride, dtype=np.uint64) if a_n is None else a_n.astype(np.uint64)
+    n_dec = ((lens + max(M, 1) - 1) // max(M, 1)).astype(np.uint32)
+    if out is None:
+        o_stride = max(int(n_dec.max()) if n_pairs else 0, 2)
+        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
+            out = torch.zeros((n_pairs, o_stride + (o_stride & 1)), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n_pairs
+    _check(ctx.L.peaq_batch_decimate(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride,
+                                     a_n.ctypes.data_as(C.POINTER(C.c_uint32)) if a_n is not None else None, stride, M,
+                                     wide_mode(mode), C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out, n_dec
+
+
+def estimate_delay_wide(ctx, ref, test, max_offset, mode="envelope", max_lag=4096, n_ref=None, n_test=None, stream=None):
+    """Delay of every pair of a batch within +-max_offset samples (up to 2^20), coarse to fine
+    (peaq_batch_estimate_delay_wide): decimate, estimate_delay on the decimated copies, cut by the coarse lag,
+    estimate_delay with max_lag on the cut pair.  Arguments as estimate_delay's.  Returns a dict of numpy arrays
+    [n_pairs]: lag (int32; positive: the test signal is late), coarse_lag, factor, flags (WIDE_F_*), and fine and coarse,
+    the two stages' records as estimate_delay's dicts (coarse's lag counts decimated samples).  Blocks."""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
+    assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
+    n_pairs, stride, channels = ref.shape
+    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
+    a_ref = a_test = None
+    if n_ref is not None:
+        a_ref = np.ascontiguousarray(n_ref, dtype=np.uint32)
+        a_test = np.ascontiguousarray(n_test, dtype=np.uint32)
+        assert a_ref.shape == (n_pairs,) and a_test.shape == (n_pairs,)
+    assert ctx.L.peaq_wide_delay_size() == C.sizeof(WideDelay) == WIDE_DELAY_DTYPE.itemsize
+    rows = np.zeros(max(n_pairs, 1), dtype=WIDE_DELAY_DTYPE)
+    u32p = C.POINTER(C.c_uint32)
+    _check(ctx.L.peaq_batch_estimate_delay_wide(ctx.h, channels, n_pairs, C.c_void_p(ref.data_ptr()),
+                                                C.c_void_p(test.data_ptr()), stride,
+                                                a_ref.ctypes.data_as(u32p) if a_ref is not None else None,
+                                                a_test.ctypes.data_as(u32p) if a_test is not None else None, stride,
+                                                int(max_offset), wide_mode(mode), int(max_lag),
+                                                rows.ctypes.data_as(C.POINTER(WideDelay)), _stream_ptr(stream)))
+    rows = rows[:n_pairs]
+    out = {k: np.ascontiguousarray(rows[k]) for k in ("lag", "coarse_lag", "factor", "flags")}
+    for stage in ("fine", "coarse"):
+        out[stage] = {k: np.ascontiguousarray(rows[stage][k]) for k in ("lag", "peak", "runner_up", "norm")}
+    return out
+
+
+def _need_wide(wide, align, drift=False, track=False, steps=False):
+    if wide is None:
+        return
+    if align is None:
+        raise ValueError("wide= requires align= (a max_lag): the wide estimate ends in a fine search of that range")
+    for name, given in (("drift", drift), ("track", track), ("steps", steps)):
+        if given:
+            raise ValueError("wide= and %s= exclude each other for now: the windows around a wide lag are not covered" % name)
+
+
 def _need_align(subsample, align, drift=False, track=False, steps=False):
     if steps and drift:
         raise PeaqError("steps= and drift= exclude each other: the pieces are the lines, one or two per window")
@@ -1691,11 +1813,15 @@ def _align_steps(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_cha
 
 
 def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
-             subsample=False, drift=False, track=False, steps=False):
+             subsample=False, drift=False, track=False, steps=False, wide=None, wide_mode="envelope"):
     """the `align=`, `gain=` and `subsample=` keywords of batch_run / batch_trajectory / batch_trace: estimate (without
-    align: lags of 0), then refine, match and cut"""
+    align: lags of 0; with wide: the wide estimate, its records kept as align.last_wide), then refine, match and cut"""
     _need_align(subsample, max_lag, drift, track, steps)
-    if max_lag is not None:
+    _need_wide(wide, max_lag, drift, track, steps)
+    if wide is not None:
+        align.last_wide = estimate_delay_wide(ctx, ref, test, wide, wide_mode, max_lag, n_ref, n_test, stream=stream)
+        lags = align.last_wide["lag"]
+    elif max_lag is not None:
         lags = estimate_delay(ctx, ref, test, max_lag, n_ref, n_test, stream=stream)["lag"]
     else:
         lags = np.zeros(ref.shape[0], dtype=np.int32)
@@ -1718,7 +1844,7 @@ def _aligned(ctx, ref, test, n_ref, n_test, max_lag, stream, gain=None, gain_per
 
 
 def _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain=None, gain_per_channel=False, max_gain_db=40.0,
-                 subsample=False, drift=False, track=False, steps=False, both_lengths=True):
+                 subsample=False, drift=False, track=False, steps=False, both_lengths=True, wide=None, wide_mode="envelope"):
     """The front the batch_* functions share: convert to 48 kHz, align / match / cut as the keywords ask (_aligned has
     the order of precedence), hold the tensors against what the library takes, make the host length arrays.
     both_lengths=False (batch_run, batch_trajectory): n_ref without n_test is left to numpy and the library.
@@ -1727,9 +1853,11 @@ def _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain=None, 
     if int(rate) != 48000:
         ref, test, n_ref, n_test = _to_48k(ctx, ref, test, n_ref, n_test, rate, stream)
     _need_align(subsample, align, drift, track, steps)
+    _need_wide(wide, align, drift, track, steps)
     if steps or track or drift or subsample or gain is not None or align is not None:
         ref, test, n_ref, n_test = _aligned(ctx, ref, test, n_ref, n_test, align, stream, gain, gain_per_channel, max_gain_db,
-                                            subsample=bool(subsample), drift=drift, track=track, steps=steps)
+                                            subsample=bool(subsample), drift=drift, track=track, steps=steps, wide=wide,
+                                            wide_mode=wide_mode)
     assert ref.is_cuda and test.is_cuda and ref.dtype == torch.float32 and test.dtype == torch.float32
     assert ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape and ref.dim() == 3
     if both_lengths:
@@ -1774,8 +1902,12 @@ def _delay_dict(rec):
 
 def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=92.0, results=None,
               stream=None, sync=True, rate=48000, align=None, gain=None, gain_per_channel=False, max_gain_db=40.0,
-              subsample=False, drift=False, track=False, steps=False):
+              subsample=False, drift=False, track=False, steps=False, wide=None, wide_mode="envelope"):
     """ref/test: CUDA float32 tensors [n_pairs, n_samples, channels] (contiguous).
+    wide: a max_offset in 48 kHz samples (up to 2^20), with align: every pair's lag comes from the wide estimate, coarse
+    to fine with align as the fine stage's range (estimate_delay_wide; wide_mode 'envelope' or 'waveform';
+    align.last_wide), and goes into the cut as before; gain and subsample work with it unchanged.  Excludes drift, track
+    and steps.
     steps: True or a window, with align: as track, with the steps of every pair's delay located and the test signal cut
     along pieces that jump there (estimate_steps, cut_pieces; align.last_steps).  Excludes track, drift and subsample.
     track: True or a window, with align: every pair's delay is kept as a track of per-window delays and the test signal
@@ -1795,7 +1927,7 @@ def batch_run(ctx, advanced, ref, test, n_ref=None, n_test=None, playback_level=
     import torch
     ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
                                                       gain_per_channel, max_gain_db, subsample, drift, track, steps,
-                                                      both_lengths=False)
+                                                      both_lengths=False, wide=wide, wide_mode=wide_mode)
     n_pairs, stride, channels = ref.shape
     if results is None:
         results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
@@ -2393,20 +2525,38 @@ def _subdelay_dict(rec):
 
 
 def run_pair(ctx, advanced, ref, test, playback_level=92.0, rate=48000, align=None, gain=None, gain_per_channel=False,
-             max_gain_db=40.0, subsample=False, drift=False, track=False, steps=False):
+             max_gain_db=40.0, subsample=False, drift=False, track=False, steps=False, wide=None, wide_mode="envelope"):
     """one whole pair from host memory (peaq_run_pair): ref/test numpy float32 [n, channels]; sampled at a `rate`
     other than 48000 they are converted on the device first (peaq_run_pair_rate).  align: a max_lag in 48 kHz samples:
     the pair is aligned on the device first (peaq_run_pair_aligned) and the result dict carries the record as `delay`.
     drift: True or a window, with align: peaq_run_pair_drift; the result dict carries the line's record as `drift`.
     track: True or a window, with align: peaq_run_pair_track; the result dict carries the track's record as `track`.
     steps: True or a window, with align: peaq_run_pair_steps; the result dict carries the track's record as `track`, the
-    pieces' as `pieces` and the located steps, a STEP_DTYPE array, as `steps`."""
+    pieces' as `pieces` and the located steps, a STEP_DTYPE array, as `steps`.
+    wide: a max_offset in 48 kHz samples (up to 2^20), with align: peaq_run_pair_wide, the lag found coarse to fine with
+    align as the fine stage's range; the result dict carries the fine stage's record with the total lag as `delay` and
+    the whole record as `wide`.  Excludes gain, subsample, drift, track and steps here."""
     ref = np.ascontiguousarray(ref, dtype=np.float32)
     test = np.ascontiguousarray(test, dtype=np.float32)
     ch = ref.shape[1]
     assert test.shape[1] == ch
     out = np.zeros(RESULT_DOUBLES)
     _need_align(subsample, align, drift, track, steps)
+    _need_wide(wide, align, drift, track, steps)
+    if wide is not None:                               # peaq_run_pair_wide; the records as `delay`, `wide`
+        if gain is not None or subsample:
+            raise ValueError("run_pair: wide= is not taken with gain= or subsample=True (batch_run takes them)")
+        wrec = WideDelay()
+        _check(ctx.L.peaq_run_pair_wide(ctx.h, int(bool(advanced)), ch, float(playback_level), int(rate), int(wide),
+                                        WIDE_MODES[wide_mode] if isinstance(wide_mode, str) else int(wide_mode), int(align),
+                                        ref.ctypes.data_as(C.POINTER(C.c_float)), len(ref),
+                                        test.ctypes.data_as(C.POINTER(C.c_float)), len(test), C.byref(wrec),
+                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = _result_dict(out, bool(advanced))
+        res["delay"] = dict(_delay_dict(wrec.fine), lag=int(wrec.lag))
+        res["wide"] = dict(lag=int(wrec.lag), coarse_lag=int(wrec.coarse_lag), factor=int(wrec.factor), flags=int(wrec.flags),
+                           fine=_delay_dict(wrec.fine), coarse=_delay_dict(wrec.coarse))
+        return res
     if steps:                                          # peaq_run_pair_steps; `delay`, `track`, `pieces`, `steps`, `gain`
         rec, trec, prec, grec = Delay(), Track(), Pieces(), Gain()
         window = _steps_window(steps)

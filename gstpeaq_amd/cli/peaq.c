@@ -558,6 +558,11 @@ usage (const char *prog)
       "                (4096..1048576, default 16384) is measured and kept as a track, and the test signal is resampled\n"
       "                along it; prints the track's range; excludes --align-drift and --align-subsample, which it\n"
       "                subsumes (the plain one-call mode; not with --list, --interval or --trace)\n"
+      "  --align-wide[=SECONDS[:waveform|envelope]] --align, with the delay searched within +-SECONDS (default 10, at most\n"
+      "                21.8) coarse to fine: on copies decimated by up to 64, then within --align's range (default 4096)\n"
+      "                around what that finds; envelope (default) also finds material without low frequencies; prints\n"
+      "                the delay and a line with the coarse lag, the factor and the flags; excludes the other\n"
+      "                --align-... options, --match-gain, --list, --interval and --trace\n"
       "  --align-steps[=WINDOW] --align-track, and steps of the delay inside a window too (a dropped or repeated block,\n"
       "                a concealed packet loss, an edit): every step of the track is located to the sample and the test\n"
       "                signal is cut along pieces that jump there; prints the track's range and each accepted step's\n"
@@ -1000,6 +1005,8 @@ main (int argc, char **argv)
   uint32_t track_window = 0;    /* != 0: --align-track, peaq_run_pair_track (implies --align) */
   peaq_track track;
   uint32_t steps_window = 0;    /* != 0: --align-steps, peaq_run_pair_steps (implies --align) */
+  uint32_t wide_offset = 0;     /* != 0: --align-wide, peaq_run_pair_wide (implies --align) */
+  int wide_mode = PEAQ_WIDE_ENVELOPE;
   peaq_delay delay;
   peaq_gain gain;
   int gain_mode = 0, gain_per_channel = 0;   /* != 0: --match-gain, peaq_run_pair_matched */
@@ -1101,6 +1108,23 @@ main (int argc, char **argv)
         return 1;
       }
       steps_window = (uint32_t) v;
+      if (!align_lag)
+        align_lag = 4096;
+    }
+    else if (!strcmp (argv[i], "--align-wide")) {
+      wide_offset = 480000;
+      if (!align_lag)
+        align_lag = 4096;
+    } else if (!strncmp (argv[i], "--align-wide=", 13)) {
+      char *end;
+      const double v = strtod (argv[i] + 13, &end);
+      if (end == argv[i] + 13 || !(v > 0. && v <= 21.8) || (uint32_t) (v * 48000. + 0.5) < 1 ||
+          (*end && strcmp (end, ":envelope") && strcmp (end, ":waveform"))) {
+        fprintf (stderr, "Failed to initialize: invalid wide offset %s (SECONDS[:waveform|envelope], up to 21.8 s)\n", argv[i] + 13);
+        return 1;
+      }
+      wide_offset = (uint32_t) (v * 48000. + 0.5);
+      wide_mode = !strcmp (end, ":waveform") ? PEAQ_WIDE_WAVEFORM : PEAQ_WIDE_ENVELOPE;
       if (!align_lag)
         align_lag = 4096;
     }
@@ -1236,7 +1260,7 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --bands belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (bands_path && (trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (bands_path && (trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --bands is a run of its own (not with --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
@@ -1252,7 +1276,7 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --fb-bands belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (fb_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (fb_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --fb-bands is a run of its own (not with --bands, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
@@ -1264,7 +1288,7 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --pattern-bands belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (pattern_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (pattern_bands_path && (bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --pattern-bands is a run of its own (not with --bands, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
@@ -1272,7 +1296,7 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --band-summary belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
@@ -1284,7 +1308,7 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --fb-band-summary belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (fb_band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (fb_band_summary_path && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --fb-band-summary is a run of its own (not with --bands, --fb-bands, --pattern-bands, --band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
@@ -1296,12 +1320,28 @@ main (int argc, char **argv)
     fprintf (stderr, "Failed to initialize: --windows belongs to the plain one-call mode (not with --list or --interval)\n");
     return 1;
   }
-  if (windows_length && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || fb_band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample)) {
+  if (windows_length && (bands_path || fb_bands_path || pattern_bands_path || band_summary_path || fb_band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
     fprintf (stderr, "Failed to initialize: --windows is a run of its own (not with --bands, --fb-bands, --pattern-bands, --band-summary, --fb-band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (gain_mode && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
     fprintf (stderr, "Failed to initialize: --match-gain belongs to the plain one-call mode and --list (not with --interval or --trace)\n");
+    return 1;
+  }
+  if (wide_offset && (steps_window || track_window || drift_window || subsample)) {
+    fprintf (stderr, "Failed to initialize: --align-wide is not taken with another --align-... option: their windows around a wide lag are not covered\n");
+    return 1;
+  }
+  if (wide_offset && gain_mode) {
+    fprintf (stderr, "Failed to initialize: --align-wide is not taken with --match-gain\n");
+    return 1;
+  }
+  if (wide_offset && list_path) {
+    fprintf (stderr, "Failed to initialize: --align-wide is not taken with --list: the host-fed path does not take it yet (whole-sample --align only)\n");
+    return 1;
+  }
+  if (wide_offset && (interval_s > 0. || trace_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --align-wide belongs to the plain one-call mode (not with --interval or --trace)\n");
     return 1;
   }
   if (steps_window && track_window) {
@@ -1560,6 +1600,20 @@ main (int argc, char **argv)
         printf ("Delay: %d samples (correlation %.3f)\n", (int) delay.lag, delay.norm > 0. ? delay.peak / delay.norm : 0.);
       format_gain (text, sizeof text, &gain, ref.channels);
       printf ("Gain: %s\n", text);
+    } else if (wide_offset) {
+      peaq_wide_delay wide;
+      if (peaq_run_pair_wide (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, wide_offset, wide_mode,
+              align_lag, ref.samples, ref.frames, test.samples, test.frames, &wide, &r) != PEAQ_OK) {
+        printf ("Error: %s\n", peaq_last_error ());
+        return 2;
+      }
+      printf ("Delay: %d samples (correlation %.3f)\n", (int) wide.lag, wide.fine.norm > 0. ? wide.fine.peak / wide.fine.norm : 0.);
+      printf ("Wide: coarse %d samples, factor %u, %s (correlation %.3f)%s%s%s\n", (int) wide.coarse_lag, (unsigned) wide.factor,
+          wide_mode == PEAQ_WIDE_WAVEFORM ? "waveform" : "envelope",
+          wide.coarse.norm > 0. ? wide.coarse.peak / wide.coarse.norm : 0.,
+          (wide.flags & PEAQ_WIDE_F_NONE) ? ", no coarse estimate" : "",
+          (wide.flags & PEAQ_WIDE_F_RANGE) ? ", at the edge of the offset range" : "",
+          (wide.flags & PEAQ_WIDE_F_EDGE) ? ", fine lag at the edge of its range" : "");
     } else if (align_lag) {
       if (peaq_run_pair_aligned (ctx, advanced, ref.channels, level, device_rate ? device_rate : 48000, align_lag,
               ref.samples, ref.frames, test.samples, test.frames, &delay, &r) != PEAQ_OK) {

@@ -164,6 +164,7 @@ extern "C" void peaq_ctx_destroy(peaq_ctx* c) {
   gain_release(c);
   frac_release(c);
   steps_release(c);
+  wide_release(c);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->batch_begin) (void)hipEventDestroy(c->batch_begin);
   if (c->batch_end) (void)hipEventDestroy(c->batch_end);

@@ -22,6 +22,8 @@
 //                     signal's cut along them (kernel and host side)
 //   peaq_steps.hip    delay steps: where inside two windows the delay jumps (kernels), the track rebuilt as pieces that
 //                     jump there (host), the test signal's cut along pieces (kernel and host side)
+//   peaq_wide.hip     wide delay search: the decimator in front of the aligner (kernels and host side), the coarse-to-fine
+//                     estimate through the aligner and the cut
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
@@ -184,6 +186,7 @@ struct peaq_ctx {
   struct GainState* gn = nullptr;         // gain matching: partial sums, length scratch (peaq_gain.hip)
   struct FracState* fr = nullptr;         // sub-sample stage: the two tables, partial sums, length scratch (peaq_frac.hip)
   struct StepsState* sp = nullptr;        // steps stage: the chunks' rows (peaq_steps.hip)
+  struct WideState* wd = nullptr;         // wide search: the decimator's taps, its FP64 outputs, length scratch (peaq_wide.hip)
 
   hipEvent_t next_event() {
     if (events_used == event_pool.size()) {
@@ -196,7 +199,7 @@ struct peaq_ctx {
 };
 
 // free what a stage has cached in the context; the device is idle.  peaq_resample.hip, peaq_align.hip, peaq_pcm.hip,
-// peaq_gather.hip, peaq_gain.hip, peaq_frac.hip, peaq_steps.hip
+// peaq_gather.hip, peaq_gain.hip, peaq_frac.hip, peaq_steps.hip, peaq_wide.hip
 void resample_release(peaq_ctx* c);
 void align_release(peaq_ctx* c);
 void feed_release(peaq_ctx* c);
@@ -204,6 +207,7 @@ void gather_release(peaq_ctx* c);
 void gain_release(peaq_ctx* c);
 void frac_release(peaq_ctx* c);
 void steps_release(peaq_ctx* c);
+void wide_release(peaq_ctx* c);
 // the sub-sample stage's shift table on the device and its length slots, for the drift cut (peaq_frac.hip; the caller
 // holds the context's lock)
 int frac_shift_table(peaq_ctx* c, const double** shift, struct LenStage** lens);

@@ -1187,6 +1187,101 @@ int peaq_run_pair_subsample (peaq_ctx *ctx, int advanced, int channels, double p
                              peaq_delay *delay /* host */, peaq_subdelay *subdelay /* host */, peaq_gain *gain /* host */,
                              peaq_result *out);
 
+/* ---- wide delay search on the device ------------------------------------------------
+ * peaq_batch_estimate_delay searches max_lag <= 16384 samples, 341 ms.  Recordings through a loopback that start
+ * seconds apart, files with a leader of silence, material that passed a broadcast chain lie beyond that, and every
+ * later stage starts from the integer lag.  This stage finds such an offset coarse to fine: both signals are decimated
+ * by a power of two M so that the offset fits the aligner's range on the decimated copies, the aligner runs there, both
+ * signals are cut by the coarse lag, and the aligner runs again on the cut pair with its usual range.
+ *
+ *   M = peaq_wide_factor (max_offset): the smallest power of two in 2 .. 64 with ceil (max_offset / M) <= 16384;
+ *   max_offset in 1 .. 1048576 (2^20 samples, 21.8 s), anything else has no factor (0).
+ *   h[j] = (0.75 / M) sinc (0.75 j / M) I0 (5.65 sqrt (1 - (j / 8M)^2)) / I0 (5.65) for j = -8M .. 8M,
+ *   sinc (x) = sin (pi x) / (pi x), sinc (0) = 1: 16 M + 1 taps, a Kaiser window of about 60 dB, passband to about
+ *   0.26 / M, stopband from about 0.49 / M cycles per sample.  Built in FP64 on the host: 0.75 j / M is exact, the
+ *   sine's argument is reduced to [-1/2, 1/2] half turns exactly, I0 (x) = sum_k ((x / 2)^2k / k!^2) is summed in
+ *   ascending k until a term no longer changes the sum; h[-j] is h[j]'s bits.  Every tap is within 1e-15 h[0] of the
+ *   formula.  peaq_wide_taps hands out exactly what is uploaded.
+ *
+ *   peaq_batch_decimate, per pair with n samples per channel:
+ *   s[i] = sum_c (double) in[i][c]: the aligner's mono sum, no 1 / channels factor.
+ *   u = s (PEAQ_WIDE_WAVEFORM) or u = |s| (PEAQ_WIDE_ENVELOPE).
+ *   y[k] = sum_{j = -8M .. 8M} h[j] u[k M + j] for k < n_dec = ceil (n / M): fused multiply-adds in the order
+ *   j = -8M .. 8M in FP64, starting from 0.  A tap whose index falls outside [0, n) contributes nothing.  The filter is
+ *   zero-phase: both signals of a pair are treated alike and the lag has no bias.
+ *   Waveform: out[k] = (float) y[k].  Envelope: out[k] = (float) (y[k] - m), m = (sum_k y[k]) / n_dec in FP64: the
+ *   correlation of two non-negative envelopes is otherwise a pedestal whose maximum is at the largest overlap.  The
+ *   sum of m: a lane of 256 adds every 256th y one after the other, k ascending, then a fixed tree over the 256 lanes
+ *   (the wave, then (0 + 1) + (2 + 3) over the four waves); no floating-point atomics.
+ *   Entries of d_out past n_dec are left as they were.  A pair's output does not depend on the other pairs of the call
+ *   and is the same bit for bit run to run.  A workgroup computes PEAQ_WIDE_CHUNK consecutive outputs of one pair.
+ *   Envelope mode waits for m: y is kept in FP64 in the context's scratch (pairs in groups below 256 MiB, or one
+ *   pair's row) and a second kernel subtracts. */
+#define PEAQ_WIDE_WAVEFORM   0
+#define PEAQ_WIDE_ENVELOPE   1
+#define PEAQ_WIDE_CHUNK      248       /* outputs per workgroup of the decimator */
+#define PEAQ_WIDE_MAX_OFFSET 1048576   /* 2^20 samples */
+#define PEAQ_WIDE_F_NONE  1  /* the coarse stage had no estimate (coarse.norm 0 or NaN): coarse_lag = 0, the fine stage
+                                ran on the pair cut at lag 0 (signals of one length: the pair as it is), so lag is the
+                                plain estimate */
+#define PEAQ_WIDE_F_RANGE 2  /* |coarse.lag| == ceil (max_offset / factor): the offset may lie outside max_offset */
+#define PEAQ_WIDE_F_EDGE  4  /* |fine.lag| == max_lag: coarse and fine stage disagree */
+typedef struct {            /* 80 bytes */
+  int32_t  lag;             /* coarse_lag + fine.lag: positive = the test signal is late, as peaq_delay's */
+  int32_t  coarse_lag;      /* coarse.lag * factor, input samples */
+  uint32_t factor, flags;
+  peaq_delay fine;          /* the record of the pair cut by coarse_lag */
+  peaq_delay coarse;        /* the record of the decimated pair; its lag counts decimated samples */
+} peaq_wide_delay;
+size_t peaq_wide_delay_size (void);
+/* Host only, no device.  0: max_offset is outside 1 .. PEAQ_WIDE_MAX_OFFSET. */
+uint32_t peaq_wide_factor (uint32_t max_offset);
+/* h: room for 16 M + 1 doubles, h[0] being the tap j = -8M.  Returns the count, 16 M + 1; an M that is not a power of
+ * two in 2 .. 64, or h NULL: PEAQ_ERR_ARG.  Host only, no device. */
+int peaq_wide_taps (uint32_t M, double *h);
+/* d_in: [n_pairs][in_stride][channels] as peaq_batch_cut's; n_in: host array of per-pair lengths (pinned staging,
+ * copied on `stream`), NULL = n_uniform for all.  d_out: device, MONO, [n_pairs][out_stride].  Enqueues on `stream` and
+ * returns (a context's first call with a factor copies that factor's taps to its device, blocking, once).
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: an M that peaq_wide_taps
+ * refuses, a mode other than 0 or 1, an out_stride below the longest n_dec, a pair longer than in_stride, NULL buffers,
+ * channels other than 1 or 2, more than 65535 pairs. */
+int peaq_batch_decimate (peaq_ctx *ctx, int channels, int n_pairs, const float *d_in, size_t in_stride,
+                         const uint32_t *n_in /* host, NULL = n_uniform */, uint32_t n_uniform,
+                         uint32_t M, int mode, float *d_out /* device, mono, [n_pairs][out_stride] */,
+                         size_t out_stride, void *stream);
+/* The wide estimate IS this composition of the entries above, bit for bit; batch layout and lengths as for
+ * peaq_batch_estimate_delay:
+ *   1. peaq_batch_decimate of both signals with M = peaq_wide_factor (max_offset) and `mode`;
+ *   2. peaq_batch_estimate_delay on the two mono buffers with the lengths n_dec and max_lag = ceil (max_offset / M);
+ *   3. the records are read; coarse_lag = coarse.lag M, or 0 under PEAQ_WIDE_F_NONE;
+ *   4. peaq_batch_cut of both signals by peaq_aligned_lengths (coarse_lag, n_ref, n_test) into staging buffers;
+ *   5. peaq_batch_estimate_delay on the staging with the common lengths and `max_lag`;
+ *   6. the records are read; lag = coarse_lag + fine.lag, and the flags.
+ * A pair whose common part is empty gets the estimator's all-zero fine record and lag = coarse_lag.  Pairs are taken
+ * in groups whose staging (peaq_wide_workspace_bytes) stays below 1 GiB, or is one pair's; a pair's record does not
+ * depend on its group.  out: HOST array of n_pairs records.  The call BLOCKS, as peaq_batch_estimate_drift does.
+ * Envelope mode finds material that has nothing below 24000 / M Hz, which waveform mode cannot; neither finds
+ * periodic material (a tone), which defeats any correlation search.
+ * PEAQ_ERR_ARG, before any device is touched and with the offending value in the message: a max_offset that
+ * peaq_wide_factor refuses, a mode other than 0 or 1, max_lag outside 1 .. 16384, and everything
+ * peaq_batch_estimate_delay refuses. */
+int peaq_batch_estimate_delay_wide (peaq_ctx *ctx, int channels, int n_pairs, const float *d_ref, const float *d_test,
+                                    size_t pair_stride, const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                                    uint32_t max_offset, int mode, uint32_t max_lag /* fine stage, 1 .. 16384 */,
+                                    peaq_wide_delay *out /* HOST, [n_pairs] */, void *stream);
+/* The call's own staging for a shape, in bytes (n_max: the longest signal of either side): per pair of a group the
+ * two cut buffers, the two decimated buffers and the two records.  It stops growing with n_pairs at 1 GiB (or one
+ * pair's share).  The scratch of the stages it calls (peaq_align_workspace_bytes, the decimator's FP64 rows) lives in
+ * the context and comes on top.  0 for no pairs, channels other than 1 or 2 or a max_offset without a factor. */
+size_t peaq_wide_workspace_bytes (int channels, int n_pairs, uint32_t n_max, uint32_t max_offset);
+/* peaq_run_pair_aligned with the wide estimate in the plain one's place: upload, conversion to 48 kHz if rate != 48000,
+ * peaq_batch_estimate_delay_wide, cut of both signals by delay->lag, the one-pair path.  The lag counts 48 kHz samples.
+ * The result is bit for bit peaq_run_pair on the two signals cut by hand.  delay (host, may be NULL) receives the
+ * record. */
+int peaq_run_pair_wide (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
+                        uint32_t max_offset, int mode, uint32_t max_lag, const float *ref, size_t n_ref,
+                        const float *test, size_t n_test, peaq_wide_delay *delay /* host */, peaq_result *out);
+
 /* ---- constant drift on the device ------------------------------------------------
  * Material that passed through a second clock (a DA/AD loop, a USB or Bluetooth device) has a delay that grows
  * steadily: at 100 ppm by 48 samples over 10 s.  One lag leaves most of such an item misaligned, and PEAQ scores that as
