@@ -102,10 +102,20 @@ extern "C" int peaq_ctx_create(int device, peaq_ctx** out) {
   }
   {
     BandTables t;
+    // the front end reads a band with a fixed number of LDS reads (peaq_group_sched.h): tables it does not fit are an error
+    auto band_sums_fit = [&]() -> int {
+      const int b = fft_band_sums_misfit(t);
+      return b < 0 ? PEAQ_OK
+                   : fail(PEAQ_ERR_STATE, "peaq_ctx_create: band " + std::to_string(b) + " of the " + std::to_string(t.bands) +
+                                            "-band tables (bins " + std::to_string(t.lo[b]) + " .. " + std::to_string(t.hi[b]) +
+                                            ") does not fit the front end's band-sum schedule (peaq_group_sched.h)");
+    };
     build_fft_band_tables(109, t);
+    if (const int rc_fit = band_sums_fit()) return rc_fit;
     HIP_TRY(hipMalloc(&c->d_bands109, sizeof t));
     HIP_TRY(hipMemcpy(c->d_bands109, &t, sizeof t, hipMemcpyHostToDevice));
     build_fft_band_tables(55, t);
+    if (const int rc_fit = band_sums_fit()) return rc_fit;
     HIP_TRY(hipMalloc(&c->d_bands55, sizeof t));
     HIP_TRY(hipMemcpy(c->d_bands55, &t, sizeof t, hipMemcpyHostToDevice));
     std::vector<FbTables> fb(1);

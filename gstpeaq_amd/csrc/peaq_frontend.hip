@@ -28,7 +28,7 @@
 // What bounds this kernel (measured): not the FP64 pipe and not HBM bandwidth but
 // latency -- of the vector-memory pipe (hence: one coalesced load path, lane-major tables instead
 // of gathers, an L2 prefetch for the workgroups to come) and of the LDS crossbar (hence: DPP /
-// permlane reductions and scans, band sums fetched eight bins at a time).
+// permlane reductions and scans, band sums fetched two bins per read in batches that are in flight together).
 //
 // LDS per wave ("unit"), 10304 B: the 8.5 KiB FFT exchange buffer (real and
 // imaginary parts go through it one after the other) is reused for the weighted
@@ -39,6 +39,7 @@
 
 #include "peaq_device.h"
 #include "peaq_kernels.h"
+#include "peaq_group_sched.h"
 #include "peaq_spread_sched.h"
 #include <type_traits>
 
@@ -57,6 +58,7 @@ constexpr int kUnitDoubles = 1288;
 constexpr int kOffPw = 0;                     // Pw[776]
 constexpr int kOffScratch = 776;              // 512 doubles
 constexpr int kPwLen = 776;
+static_assert(kPwLen == kGroupSpectrumBins, "the band sums' schedule is held against this length (peaq_group_sched.h)");
 constexpr int kOffLogTab = 2 * kUnitDoubles;       // the logarithm table (log_tab, peaq_wave.h) behind both units
 constexpr int kLogTabDoubles = 2 * kLogTabEntries + 2;   // the table + two spare words, per wave
 constexpr int kLdsDoubles = 2 * kUnitDoubles + 2 * kLogTabDoubles;
@@ -295,6 +297,109 @@ __device__ __forceinline__ double group_band(const BandEdge& e, const double* sp
     for (int j = 0; j < 8; ++j) p += v[j];
   }
   return p < 1e-12 ? 1e-12 : p;
+}
+// A lane's two band sums -- band e1 of the narrow half, band e2 of the wide half -- by the schedule of
+// peaq_group_sched.h: no loop, the interior bins two per read (ds_read2_b64: slot j reads base + 2 j and base + 2 j + 1,
+// the constant in the offset fields, one compare and one select per slot), a fixed number of slots per band, the odd
+// bin hi - 1 in a read of its own.  Beyond the band a slot reads zero words: sp[zero .. zero + group_zero_words - 1],
+// which the caller has set.  The first batch is the whole narrow band and the wide band's edges, then the wide band's slots go
+// out group_batch_pairs at a time: all reads of a batch are issued before the first of them is waited for -- the
+// scheduling barrier keeps the sums behind the reads, left to itself the scheduler sinks every read to its addition, a
+// round trip each (the LDS queue returns in order, so the additions then wait with a count that goes down, not for 0).
+// The order of the additions is that of the plain loop and of group_band above, the sums are the same bit for bit.
+// -DPEAQ_FE_GROUP_LOOP (VARIANT builds): the loop of group_band at every site, as it was.
+template <int NB>
+__device__ __forceinline__ void group_bands(const BandEdge& e1, const BandEdge& e2, const double* sp, int zero, double& s1,
+                                            double& s2) {
+#ifdef PEAQ_FE_GROUP_LOOP
+  s1 = group_band(e1, sp, zero);
+  s2 = group_band(e2, sp, zero);
+#else
+  typedef const __attribute__((address_space(3))) double* lds_cptr;
+  constexpr int kNarrow = group_narrow_pairs(NB), kWide = group_wide_pairs(NB), kBatch = group_batch_pairs(NB);
+  static_assert(kNarrow > 0 && kWide > 0, "band sums: no slot counts for this band count");
+  static_assert(2 * kWide + 1 < 256, "band sums: the slot's constant must fit the read's 8-bit offset fields");
+  const lds_cptr base = (lds_cptr)sp, z = base + zero;
+  auto slot = [&](lds_cptr q, int pairs, int j, double& v0, double& v1) {
+    lds_cptr qj = group_slot_live(pairs, j) ? q : z;
+    asm("" : "+v"(qj));                              // (keeps the select on the base, the constant in the offset fields)
+    v0 = qj[2 * j];
+    v1 = qj[2 * j + 1];
+  };
+  const int pairs1 = group_pairs(e1.lo, e1.hi), pairs2 = group_pairs(e2.lo, e2.hi);
+  const lds_cptr q1 = base + e1.lo + 1, q2 = base + e2.lo + 1;
+  {
+    double v[2 * kNarrow];
+    const double lo1 = base[e1.lo], hi1 = base[e1.hi];
+#pragma unroll
+    for (int j = 0; j < kNarrow; ++j) slot(q1, pairs1, j, v[2 * j], v[2 * j + 1]);
+    const double last1 = base[group_leftover_index(e1.lo, e1.hi, zero)];
+    const double lo2 = base[e2.lo], hi2 = base[e2.hi];
+    __builtin_amdgcn_sched_barrier(0);
+    double p = e1.wlo * lo1 + e1.whi * hi1;
+#pragma unroll
+    for (int j = 0; j < 2 * kNarrow; ++j) p += v[j];
+    p += last1;
+    s1 = p < 1e-12 ? 1e-12 : p;
+    s2 = e2.wlo * lo2 + e2.whi * hi2;
+  }
+#pragma unroll
+  for (int j0 = 0; j0 < kWide; j0 += kBatch) {
+    constexpr int kSlots = kBatch;
+    const bool last = j0 + kBatch >= kWide;
+    double v[2 * kSlots], last2 = 0.;
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i)
+      if (j0 + i < kWide) slot(q2, pairs2, j0 + i, v[2 * i], v[2 * i + 1]);
+    if (last) last2 = base[group_leftover_index(e2.lo, e2.hi, zero)];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i)
+      if (j0 + i < kWide) {
+        s2 += v[2 * i];
+        s2 += v[2 * i + 1];
+      }
+    if (last) s2 += last2;
+  }
+  s2 = s2 < 1e-12 ? 1e-12 : s2;
+#endif
+}
+
+// Noise spectrum for the NMR MOVs (movs.c:992-996), r - 2 sqrt(r t) + t bin by bin, in place over the test unit's weighted
+// spectrum: all loads first, then the arithmetic, then the stores.  Two adjacent bins per lane and step: 16-byte LDS
+// operations (the unit is 16-byte aligned), 7 + 7 reads and 7 writes instead of the 13 + 13 and 13 of one bin per lane;
+// the same arithmetic per bin, the same bits.  -DPEAQ_FE_NOISE_SINGLE (VARIANT builds): one bin per lane and step, as it was.
+__device__ __forceinline__ void noise_spectrum_in_place(const double* pw_ref, double* pw_test, int lane) {
+#ifndef PEAQ_FE_NOISE_SINGLE
+  static_assert(kPwLen % 2 == 0, "noise spectrum: two bins per lane");
+  constexpr int kPairs = kPwLen / 2, kSteps = (kPairs + 63) / 64;
+  double2 r[kSteps], t[kSteps];
+#pragma unroll
+  for (int i = 0; i < kSteps; ++i) {
+    const int k = lane + 64 * i < kPairs ? 2 * (lane + 64 * i) : 0;
+    r[i] = *reinterpret_cast<const double2*>(pw_ref + k);
+    t[i] = *reinterpret_cast<const double2*>(pw_test + k);
+  }
+  wave_lds_fence();
+#pragma unroll
+  for (int i = 0; i < kSteps; ++i)
+    if (lane + 64 * i < kPairs)
+      *reinterpret_cast<double2*>(pw_test + 2 * (lane + 64 * i)) =
+          make_double2(r[i].x - 2 * sqrt_pos(r[i].x * t[i].x) + t[i].x, r[i].y - 2 * sqrt_pos(r[i].y * t[i].y) + t[i].y);
+#else
+  constexpr int kSteps = (kPwLen + 63) / 64;
+  double r[kSteps], t[kSteps];
+#pragma unroll
+  for (int i = 0; i < kSteps; ++i) {
+    const int k = lane + 64 * i < kPwLen ? lane + 64 * i : 0;
+    r[i] = pw_ref[k];
+    t[i] = pw_test[k];
+  }
+  wave_lds_fence();
+#pragma unroll
+  for (int i = 0; i < kSteps; ++i)
+    if (lane + 64 * i < kPwLen) pw_test[lane + 64 * i] = r[i] - 2 * sqrt_pos(r[i] * t[i]) + t[i];
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -680,20 +785,7 @@ void frontend_kernel(FrontendArgs a) {
       }
       FE_MARK(8);                                    // log ratios
       wave_lds_fence();
-      {
-        constexpr int kSteps = (kPwLen + 63) / 64;   // movs.c:992-996, as in the basic version below
-        double r[kSteps], t[kSteps];
-#pragma unroll
-        for (int i = 0; i < kSteps; ++i) {
-          const int k = lane + 64 * i < kPwLen ? lane + 64 * i : 0;
-          r[i] = pw_ref[k];
-          t[i] = pw_test[k];
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int i = 0; i < kSteps; ++i)
-          if (lane + 64 * i < kPwLen) pw_test[lane + 64 * i] = r[i] - 2 * sqrt_pos(r[i] * t[i]) + t[i];
-      }
+      noise_spectrum_in_place(pw_ref, pw_test, lane);   // movs.c:992-996, as in the basic version below
       wave_lds_fence();
       if (lane == 0) adv_flag[1] = 1;                // the noise spectrum stands (LDS operations of a wave execute in order)
       FE_MARK(10);                                   // test wave: noise spectrum
@@ -704,7 +796,10 @@ void frontend_kernel(FrontendArgs a) {
     // lane owns bands 2 lane and 2 lane + 1
     const double* pw = unit + kOffPw;
     constexpr int kZeroSlot = kOffScratch + 400 - kOffPw;   // a free word of the scratch area, as an index into Pw
-    if (lane == 0) scratch[400] = 0.;
+    // the zero words of the band sums' idle slots (free: the band sums' exchange space ends at scratch[383]); in the
+    // advanced version they serve the noise spectrum's band sums as well -- nothing writes here in between
+    static_assert(400 + group_zero_words(NB) <= 512 && group_zero_words(NB) / 2 <= 64, "band sums: the zero words lie in the scratch area");
+    if (lane < group_zero_words(NB) / 2) *reinterpret_cast<double2*>(scratch + 400 + 2 * lane) = make_double2(0., 0.);
     wave_lds_fence();
     // Band sums with a balanced assignment -- lane L adds up band L (narrow) and band NB-1-L (wide):
     // the longest loop is ~27 bins instead of the ~50 of two adjacent top bands -- handed over to
@@ -723,8 +818,10 @@ void frontend_kernel(FrontendArgs a) {
     }
     if (lane < (NB + 1) / 2) {
       const int b1 = lane, b2 = NB - 1 - lane;
-      ppx[b1] = group_band(edge1, pw, kZeroSlot);
-      if (b2 != b1) ppx[b2] = group_band(edge2, pw, kZeroSlot);
+      double s1, s2;                                   // (the middle lane's two bands are one: it stores the same sum twice)
+      group_bands<NB>(edge1, edge2, pw, kZeroSlot, s1, s2);
+      ppx[b1] = s1;
+      ppx[b2] = s2;
     }
     wave_lds_fence();
     if (kAdvanced && lane == 0) adv_flag[0] = 1;       // this wave has read its weighted spectrum for the last time
@@ -882,13 +979,14 @@ void frontend_kernel(FrontendArgs a) {
     if (sig == 0) {
       // the band sums of the noise spectrum (movs.c:997-1000), which the test wave has left in its unit
       const BandEdge e1 = load_band_edge(bt, gb1), e2 = load_band_edge(bt, gb2);   // (asked for again, not held since the transform)
-      if (lane == 0) xch[0] = 0.;                    // the band sums' zero slot (no bandwidth exchange in this version)
       wait_flag(1);
-      const int zero_at = (int)(xch - pw_test);
+      const int zero_at = (int)(scratch + 400 - pw_test);   // the zero words of this wave's first band sums, still standing
       if (lane < (NB + 1) / 2) {
         const int b1 = lane, b2 = NB - 1 - lane;
-        rec[kRecNoise + b1] = group_band(e1, pw_test, zero_at);
-        if (b2 != b1) rec[kRecNoise + b2] = group_band(e2, pw_test, zero_at);
+        double s1, s2;
+        group_bands<NB>(e1, e2, pw_test, zero_at, s1, s2);
+        rec[kRecNoise + b1] = s1;
+        rec[kRecNoise + b2] = s2;
       } else if (lane < (NB + 1) / 2 + kBandStride - NB) {
         rec[kRecNoise + NB + lane - (NB + 1) / 2] = 0.;  // padding slots of the band vector
       }
@@ -938,29 +1036,21 @@ void frontend_kernel(FrontendArgs a) {
   }
 
   if (!kAdvanced && sig == 1) {
-    // ---- noise spectrum for the NMR MOVs (movs.c:992-996): one bin per lane and step, in place
+    // ---- noise spectrum for the NMR MOVs (movs.c:992-996): two bins per lane and step, in place
     // over this unit's weighted spectrum (nobody reads it any more); then the band grouping ------
     wave_lds_fence();
     {
-      constexpr int kSteps = (kPwLen + 63) / 64;     // all loads first, then the arithmetic, then the stores
-      double r[kSteps], t[kSteps];
-#pragma unroll
-      for (int i = 0; i < kSteps; ++i) {
-        const int k = lane + 64 * i < kPwLen ? lane + 64 * i : 0;
-        r[i] = pw_ref[k];
-        t[i] = pw_test[k];
-      }
-      wave_lds_fence();
-#pragma unroll
-      for (int i = 0; i < kSteps; ++i)
-        if (lane + 64 * i < kPwLen) pw_test[lane + 64 * i] = r[i] - 2 * sqrt_pos(r[i] * t[i]) + t[i];
-      if (lane == 0) lds[kOffPw] = 0.;               // the reference spectrum is dead now: its first word is the zero slot
+      noise_spectrum_in_place(pw_ref, pw_test, lane);
+      // the reference spectrum is dead now (read for the last time above): its first words are the band sums' zero words
+      if (lane < group_zero_words(NB) / 2) *reinterpret_cast<double2*>(lds + kOffPw + 2 * lane) = make_double2(0., 0.);
     }
     wave_lds_fence();
     if (lane < (NB + 1) / 2) {                        // balanced assignment as above, straight to the record
       const int b1 = lane, b2 = NB - 1 - lane;
-      rec[kRecNoise + b1] = group_band(edge1, pw_test, kOffPw - kUnitDoubles);
-      if (b2 != b1) rec[kRecNoise + b2] = group_band(edge2, pw_test, kOffPw - kUnitDoubles);
+      double s1, s2;
+      group_bands<NB>(edge1, edge2, pw_test, kOffPw - kUnitDoubles, s1, s2);
+      rec[kRecNoise + b1] = s1;
+      rec[kRecNoise + b2] = s2;
     } else if (lane < (NB + 1) / 2 + kBandStride - NB) {
       rec[kRecNoise + NB + lane - (NB + 1) / 2] = 0.;  // padding slots of the band vector
     }

@@ -11,6 +11,7 @@
 //   filter-bank responses  fbearmodel.c:57-61,182-225
 //   EHS window             movs.c:1360-1368
 #include "peaq_tables.h"
+#include "peaq_group_sched.h"
 
 #include <algorithm>
 #include <cmath>
@@ -153,6 +154,16 @@ void build_fft_band_tables(int bands, BandTables& t) {
     t.inv_spread_norm_pow03[i] = 0.0;
     t.mask_diff[i] = 1.0;
   }
+}
+
+// The front end sums a band with a fixed number of LDS reads (peaq_group_sched.h): every band of the tables must fit
+// the slots of its half, and its bins must lie inside the weighted spectrum the kernel keeps.  Returns the first band
+// that does not, -1 if all do (or if the band count has no schedule: the 40-band filter-bank tables are not concerned).
+int fft_band_sums_misfit(const BandTables& t) {
+  if (group_narrow_pairs(t.bands) < 0) return -1;
+  for (int b = 0; b < t.bands; ++b)
+    if (!group_band_fits(t.bands, b, t.lo[b], t.hi[b]) || t.hi[b] >= kGroupSpectrumBins) return b;
+  return -1;
 }
 
 void build_fb_band_tables(BandTables& t, FbTables& fb) {
