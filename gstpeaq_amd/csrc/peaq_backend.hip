@@ -576,7 +576,6 @@ struct BackendShared {
   double pc[2][kLdsBands];          // exponents xb of the detection probabilities 1 - 0.5^xb, per channel
   double qc[2][kLdsBands];
   double acc[2][kAccFields][kAccLdsStride];   // [channel][field][accumulator]
-  double energy[2];                 // totalsnr: signal and noise energy so far (lane 0 of channel 0)
   int gate[2];
 };
 
@@ -596,9 +595,18 @@ struct BackendShared {
 // SUM = true (backend_summary_kernel, summary launches only): every lane adds its two bands' values of the counted
 // frames to the channel's running rows in LDS where they come up (SummaryArgs, summary_add); the arithmetic and the
 // gates are the plain instantiation's, and a frame whose gate is closed evaluates nothing more than there.
+// WARM = true (the plain instantiations, which every scoring run goes through): channel 0's wave asks the next frame's
+// record(s) into L2 behind the frame's own loads.  It holds one register through the frame, which the 109-band
+// instantiations with an output of their own, and the debug one, do not have to spare without spilling: they run
+// without it.  -DPEAQ_BE_NO_WARM (VARIANT builds): no kernel has it, for the A/B of the touch alone.
+#ifdef PEAQ_BE_NO_WARM
+constexpr bool kBackendWarm = false;
+#else
+constexpr bool kBackendWarm = true;
+#endif
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false, PBD = false, SUM = false;
+  constexpr bool PTS = false, TRC = false, BND = false, PBD = false, SUM = false, WARM = kBackendWarm && !DBG;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -610,7 +618,7 @@ __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false, SUM = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
@@ -620,7 +628,7 @@ __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, P
 // the trace instantiation: a third kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false, SUM = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr BandArgs bnd{};
@@ -630,7 +638,7 @@ __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, Tr
 // the bands instantiation: a fourth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false, SUM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -641,7 +649,7 @@ __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, Ba
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendArgs a, PatternBandArgs pbd) {
   static_assert(!ADV, "the 55-band path has no pattern layer");
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true, SUM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -651,7 +659,7 @@ __global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendAr
 // the summary instantiation: a sixth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, SummaryArgs sum) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = false, SUM = true;
+  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = false, SUM = true, WARM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};

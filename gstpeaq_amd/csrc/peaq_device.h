@@ -217,7 +217,10 @@ constexpr int kRecFlagsRef  = kRecScalars + 3;   // bit0 above-threshold (ref), 
 constexpr int kRecFlagsTest = kRecScalars + 4;   // bit1 energy(test)
 constexpr int kRecSigE      = kRecScalars + 5;   // sum ref^2 over the hop (totalsnr)
 constexpr int kRecNoiseE    = kRecScalars + 6;   // sum (ref-test)^2
+constexpr int kRecScalarsUsed = 7;               // the scalars above: 56 bytes inside one 128-byte line of the record
 constexpr int kRecDoubles   = 352;
+static_assert(kRecScalarsUsed <= 8 && (kRecScalars * 8) % 128 == 0 && (kRecDoubles * 8) % 128 == 0,
+              "the back end gathers a channel's scalars into eight lanes, and warms a record line by line");
 
 // E = E2^2.5 / norm = root^10 inv_norm (fftearmodel.c:593-597) and E^0.3 = root^3 inv_norm^0.3
 #if defined(__HIPCC__)
