@@ -2907,6 +2907,38 @@ def debug_frontend(ctx, bands, ref, test, n_frames, playback_level=92.0):
     return out
 
 
+RAW_RECORD_DOUBLES = 352
+
+
+def debug_select_frontend(ctx, two_waves):
+    """Development switch of the basic front end: 0 = the one-wave kernel, 1 = the two-wave kernel, -1 = what
+    PEAQ_AMD_FE says.  -> the previous selection"""
+    ctx.L.peaq_debug_select_frontend.argtypes = [C.c_int]
+    ctx.L.peaq_debug_select_frontend.restype = C.c_int
+    return ctx.L.peaq_debug_select_frontend(int(two_waves))
+
+
+def debug_frontend_pairs(ctx, ref, test, n_ref, n_test, frames_per_launch, n_frames, playback_level=92.0):
+    """Stage-level access: the basic front end over several pairs as the batch path launches it.
+    ref/test: CUDA float32 [pairs, stride, channels]; n_ref/n_test: samples per pair.
+    -> np [pairs, n_frames, channels, 352], the records as the kernels exchange them"""
+    import torch
+    assert ref.is_cuda and test.is_cuda and ref.is_contiguous() and test.is_contiguous() and ref.shape == test.shape
+    n_pairs, stride, channels = ref.shape
+    nr = (C.c_uint32 * n_pairs)(*[int(v) for v in n_ref])
+    nt = (C.c_uint32 * n_pairs)(*[int(v) for v in n_test])
+    out = np.zeros((n_pairs, n_frames, channels, RAW_RECORD_DOUBLES))
+    ctx.L.peaq_debug_frontend_pairs.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int, C.c_int,
+                                                C.POINTER(C.c_double)]
+    ctx.L.peaq_debug_frontend_pairs.restype = C.c_int
+    torch.cuda.synchronize()
+    _check(ctx.L.peaq_debug_frontend_pairs(ctx.h, channels, float(playback_level), C.c_void_p(ref.data_ptr()),
+                                           C.c_void_p(test.data_ptr()), n_pairs, stride, nr, nt, int(frames_per_launch),
+                                           int(n_frames), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
 def debug_filterbank(ctx, ref, test, n_blocks, blocks_per_launch=320, playback_level=92.0):
     """Stage-level access to the filter-bank ear model of ONE pair.
     ref/test: CUDA float32 [n, channels].  -> np [blocks, channels, 168]"""

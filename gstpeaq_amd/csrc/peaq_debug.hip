@@ -67,6 +67,66 @@ extern "C" int peaq_debug_frontend(peaq_ctx* c, int bands, int channels, double 
   return PEAQ_OK;
 }
 
+// Which kernel the basic version's front end is (launch_frontend), whoever launches:
+// 0 = the one-wave kernel, 1 = frontend_kernel<109>, -1 = what PEAQ_AMD_FE says.  Returns the previous selection.
+extern "C" int peaq_debug_select_frontend(int two_waves) { return select_frontend(two_waves); }
+
+// The basic version's front end over SEVERAL pairs the way the batch path launches it -- one grid per launch of
+// frames_per_launch frames over all pairs, per-pair lengths and frame counts -- with the records as the kernels
+// exchange them: out[pair][frame][channel][PEAQ_DEBUG_RAW_RECORD_DOUBLES], frame < n_frames; the records of frames a
+// pair does not have stay zero.
+static_assert(kRecDoubles == PEAQ_DEBUG_RAW_RECORD_DOUBLES, "record layouts must match");
+extern "C" int peaq_debug_frontend_pairs(peaq_ctx* c, int channels, double level_db, const float* d_ref,
+                                         const float* d_test, int n_pairs, size_t pair_stride, const uint32_t* n_ref,
+                                         const uint32_t* n_test, int frames_per_launch, int n_frames, double* host_out) {
+  if (!c || !d_ref || !d_test || !n_ref || !n_test || !host_out)
+    return fail(PEAQ_ERR_ARG, "peaq_debug_frontend_pairs: NULL argument");
+  if (int rc = check_channels("peaq_debug_frontend_pairs", channels)) return rc;
+  if (n_pairs < 1 || n_frames < 1 || frames_per_launch < 1 ||
+      (uint32_t)frames_per_launch > max_frames_per_launch((unsigned)n_pairs))
+    return fail(PEAQ_ERR_ARG, "peaq_debug_frontend_pairs: bad counts");
+  std::vector<uint32_t> h_n(3 * (size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (n_ref[p] > pair_stride || n_test[p] > pair_stride)
+      return fail(PEAQ_ERR_ARG, "peaq_debug_frontend_pairs: a signal is longer than the pair stride");
+    h_n[p] = n_ref[p];
+    h_n[n_pairs + p] = n_test[p];
+    h_n[2 * (size_t)n_pairs + p] = count_frames(n_ref[p], n_test[p], kFrame, kHop);
+    if (h_n[2 * (size_t)n_pairs + p] > (uint32_t)n_frames) return fail(PEAQ_ERR_ARG, "peaq_debug_frontend_pairs: n_frames too small");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t per_frame = (size_t)channels * kRecDoubles;
+  const size_t launch_bytes = (size_t)n_pairs * frames_per_launch * per_frame * sizeof(double);
+  DevBuf rec_buf, n_buf;
+  HIP_TRY(rec_buf.reserve(launch_bytes));
+  HIP_TRY(n_buf.reserve(h_n.size() * sizeof(uint32_t)));
+  uint32_t* d_n = n_buf.as<uint32_t>();
+  HIP_TRY(hipMemcpy(d_n, h_n.data(), h_n.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  FrontendArgs fa = ModelSetup{c, c->settings, 0, channels, level_db}.frontend();
+  fa.ref = d_ref;
+  fa.test = d_test;
+  fa.pair_stride = pair_stride;
+  fa.n_ref = d_n;
+  fa.n_test = d_n + n_pairs;
+  fa.n_frames = d_n + 2 * (size_t)n_pairs;
+  fa.records = rec_buf.as<double>();
+  std::vector<double> h_rec(launch_bytes / sizeof(double));
+  for (int f0 = 0; f0 < n_frames; f0 += frames_per_launch) {
+    const int nf = std::min(frames_per_launch, n_frames - f0);
+    fa.frame0 = f0;
+    fa.frames_per_launch = nf;
+    const size_t bytes = (size_t)n_pairs * nf * per_frame * sizeof(double);
+    HIP_TRY(hipMemset(fa.records, 0, bytes));
+    HIP_TRY(launch_frontend(109, fa, n_pairs, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h_rec.data(), fa.records, bytes, hipMemcpyDeviceToHost));
+    for (int p = 0; p < n_pairs; ++p)
+      std::copy(h_rec.begin() + (size_t)p * nf * per_frame, h_rec.begin() + (size_t)(p + 1) * nf * per_frame,
+                host_out + ((size_t)p * n_frames + f0) * per_frame);
+  }
+  return PEAQ_OK;
+}
+
 extern "C" int peaq_debug_filterbank(peaq_ctx* c, int channels, double level_db, const float* d_ref,
                                      const float* d_test, uint32_t n_ref, uint32_t n_test, int n_blocks,
                                      int blocks_per_launch, double* host_out) {

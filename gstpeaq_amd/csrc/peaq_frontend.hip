@@ -35,12 +35,20 @@
 // spectrum Pw[0..775] and 4 KiB of scratch; the unweighted spectrum never leaves the
 // registers (the bandwidth MOVs are found with two wave reductions).  That is
 // what lets six workgroups = three waves per SIMD share a CU.
+//
+// The basic version launches frontend_pair_kernel<109> instead (further down): ONE wave per
+// (pair, frame, channel) that carries reference and test together -- the window, the twiddle powers, the item decoding
+// and the table reads exist once, there is no barrier and nothing is handed between waves, and each signal's dependent
+// chains have the other's to issue beside them; 251 registers, two waves per SIMD, 18.2 KiB of LDS.  The advanced
+// version stays on frontend_kernel<55>; PEAQ_AMD_FE=two_waves selects frontend_kernel<109> for the basic one again.
 #include <hip/hip_runtime.h>
 
 #include "peaq_device.h"
 #include "peaq_kernels.h"
 #include "peaq_group_sched.h"
 #include "peaq_spread_sched.h"
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "peaq_wave.h"
@@ -1289,7 +1297,757 @@ void frontend_kernel(FrontendArgs a) {
   if (pf_keep == 123456.789f) rec[kRecScalars + 15] = 1.;   // never true (samples lie in [-1, 1]): keeps the prefetch alive
 }
 
-hipError_t launch_frontend(int bands, const FrontendArgs& a, unsigned n_pairs, hipStream_t stream) {
+// ===========================================================================
+// frontend_pair_kernel -- the same frame in ONE wave: a workgroup of 64 lanes carries the reference AND the test signal
+// of its (pair, frame, channel).  What the two waves of frontend_kernel each evaluate for themselves -- the window, the
+// twiddle powers, the item decoding, the table reads, the logarithm table -- exists once; nothing is handed between
+// waves, so there is no barrier and no flag; and every dependent chain of one signal has the other signal's to issue
+// beside it.  The price is registers: both spectra live side by side (<= 256 registers, two waves per SIMD).
+// The arithmetic per signal is frontend_kernel's, instruction for instruction (the same device functions, applied to
+// both signals from one place in the source, so that identical signals keep giving identical spectra).
+//
+// LDS, 18592 B per workgroup (<= 20 KiB: eight workgroups per CU):
+//   [0, 776)      Pw of the reference  -- during the FFT, with the scratch area: the ONE 8.5 KiB exchange buffer both
+//   [776, 1288)   scratch                 signals' first exchanges go through, one after the other
+//   [1288, 2064)  Pw of the test signal, later the noise spectrum in place
+//   [2064, 2324)  the logarithm table
+// ===========================================================================
+constexpr int kPairOffPwRef = 0;
+constexpr int kPairOffScratch = kPwLen;              // 512 doubles
+constexpr int kPairOffPwTest = kPairOffScratch + 512;
+constexpr int kPairOffLogTab = kPairOffPwTest + kPwLen;
+constexpr int kPairLdsDoubles = kPairOffLogTab + kLogTabDoubles;
+static_assert(kPairLdsDoubles * sizeof(double) <= 20480, "one-wave front end: eight workgroups per CU in 160 KiB of LDS");
+static_assert(kPairOffPwTest >= 1088 && kPairOffPwTest % 2 == 0, "the exchange buffer ends before the test spectrum; 16-byte alignment");
+
+// frame_power_spectrum for both signals of a frame: every twiddle set is computed once and applied to both z arrays
+template <typename F>
+__device__ __forceinline__ void pair_power_spectra(cplx (&zr)[16], cplx (&zt)[16], double (&pr)[16], double (&pt)[16],
+                                                   double* buf, double* pw_r, double* pw_t, int lane,
+                                                   const CommonTables* __restrict__ ct, double level_factor,
+                                                   F&& behind_pass2_twiddles) {
+  const cplx w256 = tw_lane(ct, 2, lane);
+  auto wr1 = [&](int r) { return 16 * lane + r; };
+  auto rd1 = [&](int r) { return lane + 64 * r; };
+  // pass 1; the test signal's butterflies have the reference's exchange to run beside
+  dft16(zr);
+  exchange16(zr, buf, wr1, rd1);
+  dft16(zt);
+  exchange16(zt, buf, wr1, rd1);
+  // pass 2
+  {
+    cplx w[9];
+    w[1] = w256;
+    w[2] = csqr(w[1]);
+    w[4] = csqr(w[2]);
+    w[8] = csqr(w[4]);
+    w[3] = cmul(w[1], w[2]);
+    w[5] = cmul(w[4], w[1]);
+    w[6] = cmul(w[4], w[2]);
+    w[7] = cmul(w[4], w[3]);
+#pragma unroll
+    for (int r = 1; r < 8; ++r) {
+      const cplx w8r = cmul(w[8], w[r]);
+      zr[8 + r] = cmul(zr[8 + r], w8r);
+      zt[8 + r] = cmul(zt[8 + r], w8r);
+      zr[r] = cmul(zr[r], w[r]);
+      zt[r] = cmul(zt[r], w[r]);
+    }
+    zr[8] = cmul(zr[8], w[8]);
+    zt[8] = cmul(zt[8], w[8]);
+  }
+  behind_pass2_twiddles();                           // (every global load requested before w256 has arrived by now)
+  auto pass2_tail = [&](cplx (&z)[16]) {
+    dft16(z);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      rows_transpose4(z[4 * g].re, z[4 * g + 1].re, z[4 * g + 2].re, z[4 * g + 3].re);
+      rows_transpose4(z[4 * g].im, z[4 * g + 1].im, z[4 * g + 2].im, z[4 * g + 3].im);
+    }
+#pragma unroll
+    for (int a2 = 0; a2 < 4; ++a2)
+#pragma unroll
+      for (int g = a2 + 1; g < 4; ++g) {
+        const cplx t = z[4 * a2 + g];
+        z[4 * a2 + g] = z[4 * g + a2];
+        z[4 * g + a2] = t;
+      }
+  };
+  pass2_tail(zr);
+  pass2_tail(zt);
+  const cplx wl = tw_lane(ct, 0, lane);
+  // (the ear weights of the first kEwAhead steps of the split only: with both z arrays live there is no room for all
+  // eight over pass 3 -- step q of the split requests those of step q + kEwAhead)
+  constexpr int kEwAhead = 2;
+  double2 ew[8];
+#pragma unroll
+  for (int q = 0; q < kEwAhead; ++q) ew[q] = *reinterpret_cast<const double2*>(ct->ear_w2_pair[q][lane]);
+  {
+    constexpr double c1 = 0.92387953251128673848, s1 = 0.38268343236508977173, c2 = 0.70710678118654752440;
+    const cplx wb = tw_lane(ct, 1, lane);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const cplx w1 = m == 0 ? wb : m == 1 ? cmul(wb, {c1, -s1}) : m == 2 ? cmul(wb, {c2, -c2}) : cmul(wb, {s1, -c1});
+      const cplx w2 = csqr(w1), w3 = cmul(w2, w1);
+      auto pass3 = [&](cplx (&z)[16]) {
+        z[m + 4] = cmul(z[m + 4], w1);
+        z[m + 8] = cmul(z[m + 8], w2);
+        z[m + 12] = cmul(z[m + 12], w3);
+        dft4(z[m], z[m + 4], z[m + 8], z[m + 12]);
+      };
+      pass3(zr);
+      pass3(zt);
+    }
+  }
+  wave_lds_fence();                                  // the exchange buffer is about to become the two Pw
+  const int partner = (64 - lane) & 63;
+  // (wave-uniform: held in scalar registers, the split has no vector register to spare)
+  const double lf4v = 0.25 * level_factor;
+  const double lf4 = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(lf4v)),
+                                      __builtin_amdgcn_readfirstlane(__double2loint(lf4v)));
+  // Lane 0's mirror bins are its OWN slots 16 - q, one up from the slot 15 - q every other lane's partner holds.  Taken
+  // inside the loop, as frontend_kernel does, that keeps slot 16 - q of BOTH signals live a step longer: eight registers
+  // too many here.  So lane 0 moves its upper slots one down beforehand (the same selects, in another place; slot j
+  // takes from j + 1, which is still untouched) and the loop exchanges slot 15 - q for every lane alike.  Bin 512, which
+  // lane 0 forms from its slot 8, first.
+  double p512_r, p512_t;
+  auto lane0_slots = [&](cplx (&z)[16], double& p512) {
+    p512 = (z[8].re * z[8].re + z[8].im * z[8].im) * level_factor;
+#pragma unroll
+    for (int j = 8; j < 16; ++j)
+      if (lane == 0) z[j] = z[(j + 1) & 15];
+  };
+  lane0_slots(zr, p512_r);
+  lane0_slots(zt, p512_t);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    if (q + kEwAhead < 8) ew[q + kEwAhead] = *reinterpret_cast<const double2*>(ct->ear_w2_pair[q + kEwAhead][lane]);
+    const int k = lane + 64 * q;
+    const cplx wq = {kW32re[q], kW32im[q]};
+    const cplx wk = q == 0 ? wl : cmul(wl, wq);
+    auto split = [&](cplx (&z)[16], double (&p)[16], double* pw, double p512) {
+      const cplx zm = {__shfl(z[15 - q].re, partner, 64), __shfl(z[15 - q].im, partner, 64)};
+      const cplx e2 = {z[q].re + zm.re, z[q].im - zm.im};
+      const cplx o2 = {z[q].im + zm.im, zm.re - z[q].re};
+      const cplx t = cmul(wk, o2);
+      const cplx xp = cadd(e2, t), xm = csub(e2, t);
+      p[q] = (xp.re * xp.re + xp.im * xp.im) * lf4;
+      double pm = (xm.re * xm.re + xm.im * xm.im) * lf4;
+      int km = 1024 - k;
+      if (q == 0 && lane == 0) {
+        pm = p512;
+        km = 512;
+      }
+      p[8 + q] = pm;
+      pw[k] = p[q] * ew[q].x;
+      if (km < kPwLen) pw[km] = pm * ew[q].y;
+    };
+    split(zr, pr, pw_r, p512_r);
+    split(zt, pt, pw_t, p512_t);
+  }
+  wave_lds_fence();
+}
+
+// the bandwidth search of frontend_kernel (movs.c:776-809) on a spectrum held as frame_power_spectrum leaves it
+__device__ __forceinline__ int pair_top_bin(const double (&ps)[16], double level, int limit, bool or_equal) {
+  bool hit512 = false;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    unsigned long long m = __ballot(or_equal ? ps[8 + q] >= level : ps[8 + q] > level);
+    if (q == 0) {
+      hit512 = (m & 1ull) && 512 < limit;
+      m &= ~1ull;
+    }
+    const int lo = 1024 - 64 * q - limit + 1;
+    m &= lo >= 64 ? 0ull : lo <= 0 ? ~0ull : ~0ull << lo;
+    if (m) return 1024 - 64 * q - __builtin_ctzll(m) + 1;
+  }
+  if (hit512) return 513;
+#pragma unroll
+  for (int q = 7; q >= 0; --q) {
+    unsigned long long m = __ballot(or_equal ? ps[q] >= level : ps[q] > level);
+    const int nl = limit - 64 * q;
+    m &= nl >= 64 ? ~0ull : nl <= 0 ? 0ull : (1ull << nl) - 1ull;
+    if (m) return 64 * q + 64 - __builtin_clzll(m);
+  }
+  return 0;
+}
+
+// Error harmonic structure from the log ratios d[0..511] (movs.c:1279-1315, 1393-1441): frontend_kernel's parts 2 and 3,
+// exchanging through sa and sb (512 doubles each; d may be sb).  Returns the EHS value (every lane).
+__device__ __forceinline__ double pair_ehs(const double* d, double* sa, double* sb, int lane,
+                                           const CommonTables* __restrict__ ct, const Settings& cfg) {
+  const cplx w64 = tw_lane(ct, 4, lane);
+  const cplx w512 = tw_lane(ct, 3, lane);
+  cplx ft1[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ft1[i] = tw_lane(ct, 5 + i, lane);
+  cplx u[8];
+  double g[4], run_in;
+  {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const double v = d[lane + 64 * r];
+      u[r] = {r < 4 ? v : 0., v};
+    }
+    double tot = 0.;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int j = 4 * lane + t;
+      const double hi = d[j + 256], lo = d[j];
+      g[t] = hi * hi - lo * lo;
+      tot += g[t];
+    }
+    run_in = wave_prefix_sum(tot, lane) - tot;
+  }
+  wave_lds_fence();
+  auto exchange8 = [&](auto wr, auto swz) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int i = swz(wr(r));
+      sa[i] = u[r].re;
+      sb[i] = u[r].im;
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int i = swz(lane + 64 * r);
+      u[r] = {sa[i], sb[i]};
+    }
+    wave_lds_fence();
+  };
+  auto twiddle8 = [&](cplx w1) {
+    cplx w[8];
+    w[1] = w1;
+    w[2] = csqr(w[1]);
+    w[4] = csqr(w[2]);
+    w[3] = cmul(w[1], w[2]);
+    w[5] = cmul(w[4], w[1]);
+    w[6] = cmul(w[4], w[2]);
+    w[7] = cmul(w[4], w[3]);
+#pragma unroll
+    for (int r = 1; r < 8; ++r) u[r] = cmul(u[r], w[r]);
+  };
+  dft8_imag_upper(u);
+  exchange8([&](int r) { return 8 * lane + r; }, [](int i) { return i ^ ((i >> 4) & 7); });
+  {
+    const int k = lane & 7;
+    twiddle8(w64);
+    dft8(u);
+    const int j = (lane - k) * 8 + k;
+    exchange8([&](int r) { return j + 8 * r; }, [](int i) { return i ^ (((i >> 6) & 1) << 3); });
+  }
+  twiddle8(w512);
+  dft8(u);
+  const double* __restrict__ win = cfg.centre_ehs_window ? ct->ehs_window_centred : ct->ehs_window;
+  double wv[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) wv[m] = win[lane + 64 * m];
+  const int partner = (64 - lane) & 63;
+  cplx cc[4];
+  double c256 = 0.;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    cplx zm = {__shfl(u[7 - r].re, partner, 64), __shfl(u[7 - r].im, partner, 64)};
+    if (lane == 0) zm = u[(8 - r) & 7];
+    const cplx a2 = {u[r].re + zm.re, u[r].im - zm.im};
+    const cplx b2 = {u[r].im + zm.im, zm.re - u[r].re};
+    cc[r] = {b2.re * a2.re + b2.im * a2.im, b2.im * a2.re - b2.re * a2.im};
+  }
+  if (lane == 0) c256 = (2. * u[4].re) * (2. * u[4].im);
+  cplx v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    cplx cm = {__shfl(cc[3 - r].re, partner, 64), __shfl(cc[3 - r].im, partner, 64)};
+    if (lane == 0) cm = r == 0 ? cplx{c256, 0.} : cc[4 - r];
+    const cplx e = {cc[r].re + cm.re, cc[r].im - cm.im};
+    const cplx od = {cc[r].re - cm.re, cc[r].im + cm.im};
+    constexpr double c8 = 0.70710678118654752440;
+    const cplx wkf = r == 0 ? w512 : r == 1 ? cmul(w512, {c8, -c8}) : r == 2 ? cmul_mi(w512) : cmul(w512, {-c8, -c8});
+    const cplx o = cmul(od, {wkf.re, -wkf.im});
+    v[r] = {e.re - o.im, -(e.im + o.re)};
+  }
+  cplx ft2[3], ft3[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    ft2[i] = csqr(ft1[i]);
+    ft3[i] = cmul(ft2[i], ft1[i]);
+  }
+  wave_lds_fence();
+  double2* xb = reinterpret_cast<double2*>(sa);
+  auto fft256 = [&](cplx (&w)[4]) {
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+      const int p = 1 << (2 * pass);
+      const int k = lane & (p - 1);
+      if (pass > 0) {
+        if (pass < 3) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double2 x = xb[lane + 64 * r];
+            w[r] = {x.x, x.y};
+          }
+        }
+        w[1] = cmul(w[1], ft1[pass - 1]);
+        w[2] = cmul(w[2], ft2[pass - 1]);
+        w[3] = cmul(w[3], ft3[pass - 1]);
+      }
+      dft4(w[0], w[1], w[2], w[3]);
+      if (pass < 2) {
+        const int j = (lane - k) * 4 + k;
+        wave_lds_fence();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xb[j + r * p] = make_double2(w[r].re, w[r].im);
+        wave_lds_fence();
+      } else if (pass == 2) {
+        rows_transpose4(w[0].re, w[1].re, w[2].re, w[3].re);
+        rows_transpose4(w[0].im, w[1].im, w[2].im, w[3].im);
+      }
+    }
+  };
+  fft256(v);
+  wave_lds_fence();
+  {
+    double2* cb = reinterpret_cast<double2*>(sb);
+    constexpr double kScale = 1. / 2048.;
+    cb[lane] = make_double2(v[0].re * kScale, -v[0].im * kScale);
+    cb[lane + 64] = make_double2(v[1].re * kScale, -v[1].im * kScale);
+    double run = run_in;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      sa[4 * lane + t] = run;
+      run += g[t];
+    }
+  }
+  wave_lds_fence();
+  double c[4], dk[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    c[m] = sb[lane + 64 * m];
+    dk[m] = sa[lane + 64 * m];
+  }
+  const double d0 = read_lane<0>(c[0]);
+  double cavg = 0.;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    c[m] *= rsqrt_pos(d0 * (d0 + dk[m]));
+    cavg += c[m];
+  }
+  cavg = cfg.ehs_dc_before_window ? wave_sum(cavg) / 256. : 0.;
+  cplx w4[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) w4[m] = {(c[m] - cavg) * wv[m], 0.};
+  wave_lds_fence();
+  fft256(w4);
+  if (!cfg.ehs_dc_before_window && lane == 0) w4[0].re = 0.;
+  const double s0 = w4[0].re * w4[0].re + w4[0].im * w4[0].im;
+  const double s1 = w4[1].re * w4[1].re + w4[1].im * w4[1].im;
+  const double s2 = w4[2].re * w4[2].re + w4[2].im * w4[2].im;
+  const double s0_up = lane_below(s0), s1_up = lane_below(s1);
+  const double s0_last = read_lane<63>(s0), s1_last = read_lane<63>(s1);
+  const double prev0 = s0_up;
+  const double prev1 = lane == 0 ? s0_last : s1_up;
+  double best = 0.;
+  if (lane >= 1 && s0 > prev0) best = s0;
+  if (s1 > prev1 && s1 > best) best = s1;
+  if (lane == 0 && s2 > s1_last && s2 > best) best = s2;
+  return wave_max(best);
+}
+
+template <int NB>
+__global__ __launch_bounds__(64, 2) void frontend_pair_kernel(FrontendArgs a) {
+  static_assert(NB == 109, "the one-wave front end is the basic version's (the advanced one has no band phase for the test signal)");
+  extern __shared__ double lds[];
+  __builtin_amdgcn_s_setprio(3);
+  asm volatile("" ::"s"(a.ref), "s"(a.test), "s"(a.pair_stride), "s"(a.n_ref), "s"(a.n_test), "s"(a.n_uniform_ref),
+               "s"(a.n_uniform_test), "s"(a.n_frames), "s"(a.n_frames_uniform), "s"(a.frame_origin), "s"(a.off_ref),
+               "s"(a.off_test), "s"(a.channels), "s"(a.frame0), "s"(a.frames_per_launch), "s"(a.fpl_magic), "s"(a.common),
+               "s"(a.records), "s"(a.pair_frame0), "s"(gridDim.x));
+  const int lane = threadIdx.x;
+  [[maybe_unused]] constexpr int sig = 0;            // (FE_MARK: one role)
+#ifdef PEAQ_FE_PROFILE
+  unsigned long long prof_t_ = __builtin_readcyclecounter();
+  if (a.prof && lane == 0 && (blockIdx.x & 127) == 5) atomicAdd(a.prof + 32, 1ull);
+#endif
+  double* pw_ref = lds + kPairOffPwRef;
+  double* pw_test = lds + kPairOffPwTest;
+  double* scratch = lds + kPairOffScratch;
+  double* ltab = lds + kPairOffLogTab;
+  const CommonTables* __restrict__ ct = a.common;
+  const BandTables* __restrict__ bt = a.bands;
+
+  // ---- which (pair, frame, channel): as frontend_kernel ---------------------------------------------------------
+  auto decode = [&](unsigned it, unsigned& pair_, unsigned& fl_) {
+    const unsigned t = it >> (a.channels - 1);
+    pair_ = a.frames_per_launch == 1 ? t : __umulhi(t, a.fpl_magic);
+    fl_ = t - pair_ * a.frames_per_launch;
+    return (int)(it & (unsigned)(a.channels - 1));
+  };
+  const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
+  unsigned pair, fl;
+  const int chan = decode(item, pair, fl);
+  FE_MARK(15);
+  const unsigned n_ref = a.n_ref ? a.n_ref[pair] : a.n_uniform_ref;
+  const unsigned n_test = a.n_test ? a.n_test[pair] : a.n_uniform_test;
+  unsigned frame, frame_origin;
+  if (a.pair_frame0) {
+    if (fl >= a.pair_nframes[pair]) return;
+    frame_origin = a.pair_frame0[pair];
+    frame = frame_origin + fl;
+  } else {
+    frame = a.frame0 + fl;
+    frame_origin = a.frame_origin;
+    const unsigned n_frames = a.n_frames ? a.n_frames[pair] : a.n_frames_uniform;
+    if (frame >= n_frames) return;
+  }
+  const size_t pair_off = (size_t)pair * a.pair_stride * a.channels;
+  FrameSrc src_ref, src_test;
+  {
+    const long long s0 = (long long)(frame - frame_origin) * kHop;
+    src_ref.set(a.ref + pair_off, s0 + a.off_ref, (long long)n_ref, a.channels, chan);
+    src_test.set(a.test + pair_off, s0 + a.off_test, (long long)n_test, a.channels, chan);
+  }
+  double* __restrict__ rec =
+      a.records + ((size_t)(pair * a.frames_per_launch + fl) * a.channels + chan) * kRecDoubles;
+  // ---- load + window: one lane offset, two buffer resources; the window values once per row -----------------------
+  constexpr double kHannA = 0.81649658092772603273;
+  constexpr double kHannC[16] = {1.0, 0.923806101034885660186, 0.7068354246185547448714, 0.3821516543455241229047,
+                                 -0.0007673650086148258012924, -0.3835694472988822502431, -0.7079202261619581075015,
+                                 -0.9243926006499437062869, -0.9999988223018871071366, -0.9232174254904238786877,
+                                 -0.7057489581976599840459, -0.3807329612736016723471, 0.002302093218395832312485,
+                                 0.3849863367942118830771, 0.7090033602727326108775, 0.9249769229541590372578};
+  constexpr double kHannS[16] = {0.0, 0.382860663545790020567, 0.7073780336597309217442, 0.92409962292005024589,
+                                 0.99999970557542843387, 0.923512035167290059731, 0.7062923993579444458354,
+                                 0.3814424201155840173045, -0.001534729565367423810065, -0.3842780051874341062575,
+                                 -0.7084620018059667117941, -0.924685034052046356158, -0.9999973501798961346679,
+                                 -0.9229222721777677728372, -0.705205101457706221079, -0.3800232782373413192215};
+  const double2 hl0 = *reinterpret_cast<const double2*>(&ct->hann_lane[lane][0]);
+  const double2 hl1 = *reinterpret_cast<const double2*>(&ct->hann_lane[lane][2]);
+  FE_MARK(13);
+  cplx zr[16], zt[16];
+  float amax = 0.f;
+  double energy_r = 0., energy_t = 0., hop_r = 0., hop_t = 0.;   // hop: sum ref^2 / sum (ref - test)^2
+  {
+    const int voff = src_ref.lane_offset(lane);      // same channel count and channel: one lane offset for both
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = lane + 64 * r;
+      float x0, x1, y0, y1;
+      src_ref.load2(r, voff, x0, x1);
+      src_test.load2(r, voff, y0, y1);
+      const double w0 = fma(hl0.y, kHannS[r], fma(-hl0.x, kHannC[r], kHannA));
+      const double w1 = fma(hl1.y, kHannS[r], fma(-hl1.x, kHannC[r], kHannA));
+      zr[r] = {w0 * (double)x0, w1 * (double)x1};
+      zt[r] = {w0 * (double)y0, w1 * (double)y1};
+      if (r >= 8) {
+        energy_r += (double)(x0 * x0);
+        energy_r += (double)(x1 * x1);
+        energy_t += (double)(y0 * y0);
+        energy_t += (double)(y1 * y1);
+      } else {
+        hop_r += (double)(x0 * x0);
+        hop_r += (double)(x1 * x1);
+        hop_t += (double)((x0 - y0) * (x0 - y0));
+        hop_t += (double)((x1 - y1) * (x1 - y1));
+      }
+      amax = fmaxf(amax, n == 0 ? fabsf(x1) : fmaxf(fabsf(x0), fabsf(x1)));
+    }
+  }
+  // ---- L2 prefetch: this wave touches BOTH signals' next frame for the item kPrefetchItems further on ---------------
+  float pf_keep = 0.f;
+  if (chan == 0 && !a.pair_frame0) {
+    const unsigned it2 = item + kPrefetchItems;
+    if (it2 < gridDim.x) {
+      unsigned pair2, fl2;
+      decode(it2, pair2, fl2);
+      const long long s2 = (long long)(a.frame0 + fl2 - a.frame_origin) * kHop + (fl2 == 0 ? 0 : kHop);
+      const size_t off2 = (size_t)pair2 * a.pair_stride * a.channels;
+      FrameSrc pfr, pft;
+      pfr.set(a.ref + off2, s2 + a.off_ref, (long long)(a.n_ref ? a.n_ref[pair2] : a.n_uniform_ref), a.channels, 0);
+      pft.set(a.test + off2, s2 + a.off_test, (long long)(a.n_test ? a.n_test[pair2] : a.n_uniform_test), a.channels, 0);
+      pf_keep = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pfr.rs, lane * 128, 0, 0));
+      pf_keep += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pft.rs, lane * 128, 0, 0));
+      if (fl2 == 0 && a.channels == 2) {
+        pf_keep += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pfr.rs, (64 + lane) * 128, 0, 0));
+        pf_keep += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pft.rs, (64 + lane) * 128, 0, 0));
+      }
+    }
+  }
+  __builtin_amdgcn_s_setprio(0);
+#ifdef PEAQ_FE_PROFILE
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+  FE_MARK(14);
+  // (the reduction tree of wave_sum2, twice over: the sums are frontend_kernel's bit for bit)
+  wave_sum4(hop_r, energy_r, hop_t, energy_t, hop_r, energy_r, hop_t, energy_t);
+  if (lane == 0) {
+    rec[kRecSigE] = hop_r;
+    rec[kRecNoiseE] = hop_t;
+  }
+  const int eflag_r = energy_r >= 8000. / (32768. * 32768.), eflag_t = energy_t >= 8000. / (32768. * 32768.);
+  int above = 0;
+  if (__any((double)amax >= 200. / 32768 + 1e-6)) {
+    above = 1;
+  } else {
+    float* ax = reinterpret_cast<float*>(lds);       // 8 KiB of the still unused exchange buffer
+    int lane_q = lane;
+    asm volatile("" : "+v"(lane_q));
+    const int voff_q = src_ref.lane_offset(lane_q);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = lane_q + 64 * r;
+      float x0, x1;
+      src_ref.load2(r, voff_q, x0, x1);
+      reinterpret_cast<float2*>(ax)[n] = make_float2(fabsf(x0), fabsf(x1));
+    }
+    wave_lds_fence();
+    above = boundary_detect(ax, kFrame, lane);
+    wave_lds_fence();
+  }
+  if (lane == 0) {
+    rec[kRecFlagsRef] = (double)(above | (eflag_r << 1));
+    rec[kRecFlagsTest] = (double)(eflag_t << 1);
+  }
+  FE_MARK(0);
+  constexpr int kGroupLanes = (NB + 1) / 2;
+  int bw_ref = 0, bw_test = 0;
+  {
+    double pr[16], pt[16];                           // the unweighted power spectra: they die with the bandwidths
+    double2 lt0, lt1, lt2;
+    // (the prefetched words end their life where the transform has waited for a younger load anyway -- loads return in
+    // order --: one register less over the split, where there is none to spare)
+    pair_power_spectra(zr, zt, pr, pt, lds, pw_ref, pw_test, lane, ct, a.level_factor,
+                       [&] { asm volatile("" ::"v"(pf_keep)); });
+    // the logarithm table, requested only now (no register is free for it over the transform; the barrier keeps the
+    // scheduler from lifting the loads back up) and stored behind the bandwidth searches, which cover its way
+    __builtin_amdgcn_sched_barrier(0);
+    lt0 = *reinterpret_cast<const double2*>(ct->log_tab[lane]);
+    lt1 = *reinterpret_cast<const double2*>(ct->log_tab[64 + lane]);
+    lt2 = *reinterpret_cast<const double2*>(ct->log_tab[128]);
+    FE_MARK(1);
+    // ---- bandwidths (movs.c:776-809), straight from the registers: zero threshold = max over bins 921..1023 of the
+    // test spectrum, then the two searches
+    double thr = 0.;
+    if (lane >= 1) thr = pt[8];
+    if (lane <= 39) thr = fmax(thr, pt[9]);
+    thr = wave_max(thr);
+    bw_ref = pair_top_bin(pr, 10. * thr, 921, false);
+    if (bw_ref > 346) bw_test = pair_top_bin(pt, 3.16227766016838 * thr, bw_ref, true);
+    if (lane == 0) {
+      rec[kRecBwRef] = (double)bw_ref;
+      rec[kRecBwTest] = (double)bw_test;
+    }
+    reinterpret_cast<double2*>(ltab)[lane] = lt0;
+    reinterpret_cast<double2*>(ltab)[64 + lane] = lt1;
+    if (lane == 0) reinterpret_cast<double2*>(ltab)[128] = lt2;
+  }
+  const int gb1 = lane < kGroupLanes ? lane : 0, gb2 = lane < kGroupLanes ? NB - 1 - lane : 0;
+  const BandEdge edge1 = load_band_edge(bt, gb1), edge2 = load_band_edge(bt, gb2);
+  FE_MARK(2);
+  // ---- critical bands, internal noise, spreading: both signals step by step ------------------------------------------
+  {
+    constexpr int kZeroAt = 400;                     // zero words of the band sums' idle slots: scratch[400 ..]
+    static_assert(kZeroAt + group_zero_words(NB) <= 512 && group_zero_words(NB) / 2 <= 64, "band sums: the zero words lie in the scratch area");
+    if (lane < group_zero_words(NB) / 2) *reinterpret_cast<double2*>(scratch + kZeroAt + 2 * lane) = make_double2(0., 0.);
+    wave_lds_fence();
+    double* const ppx[2] = {scratch + 256, scratch};   // [128] each: band sums, then the helper stream's way home
+    const double* const pw[2] = {pw_ref, pw_test};
+    const int b0 = 2 * lane;
+    double c_noise[2], c_lnauc[2], c_gil[2];
+    const double c_dz02 = bt->dz02, c_ale = bt->aLe;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const int b = b0 + s2 < NB ? b0 + s2 : 0;
+      c_noise[s2] = bt->internal_noise[b];
+      c_lnauc[s2] = bt->ln_aUC[b];
+      c_gil[s2] = bt->gIL[b];
+    }
+    if (lane < kGroupLanes) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        double s1, s2;
+        group_bands<NB>(edge1, edge2, pw[g], (int)(scratch + kZeroAt - pw[g]), s1, s2);
+        ppx[g][lane] = s1;
+        ppx[g][NB - 1 - lane] = s2;
+      }
+    }
+    wave_lds_fence();
+    FE_MARK(3);
+    constexpr int kLanes = spread_lanes(NB);
+    constexpr int kHelper = spread_helper_steps(NB), kFirst = spread_k0(NB), kBoundary = spread_boundary(NB);
+    constexpr int kExpUpper = spread_exp_upper(NB, 0), kExpHelper = spread_exp_helper(NB);
+    static_assert(kHelper > 0, "upward spreading: the two-stream schedule");
+    double ene[2][2], ae[2][2], far[2][2], back2[2][2], far_copy[2][2], upper[2][2];   // [signal][band of the lane]
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int b = b0 + s;
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        if (b < NB) {
+          const double pp = ppx[g][b] + c_noise[s];
+          const double ln_pp = FE_LOG(pp, ltab);
+          const double ln_a = c_lnauc[s] + c_dz02 * ln_pp;
+          const double t = exp_fast(0.2 * ln_a), t2 = t * t;
+          const double a_uce = t2 * t2 * t;
+          const double g_iu = div_fast(1. - exp_fast((double)(NB - b) * ln_a), 1. - a_uce);
+          ae[g][s] = t2;
+          ene[g][s] = exp_fast(0.4 * (ln_pp - FE_LOG(c_gil[s] + g_iu - 1., ltab)));
+          upper[g][s] = ene[g][s] * pow_const(t2, kExpUpper - s);
+          const double ph = pow_const(t2, kExpHelper);
+          far[g][s] = upper[g][s] * ph;
+          far_copy[g][s] = far[g][s] * ph;
+          const double t4 = t2 * t2;
+          back2[g][s] = t4 > 1e-290 ? div_fast(1., t4) : 0.;
+        } else {
+          ae[g][s] = 0.;
+          ene[g][s] = 0.;
+          far[g][s] = 0.;
+          far_copy[g][s] = 0.;
+          upper[g][s] = 0.;
+          back2[g][s] = 0.;
+        }
+      }
+    }
+    FE_MARK(4);
+    // upward spreading (peaq_spread_sched.h, per signal): four accumulators and four walking terms per step
+    double up0[2] = {0., 0.}, up1[2] = {0., 0.};
+    {
+      double u[2], v[2], wa0[2], wa1[2], wb0[2], wb1[2];
+      double2 home[2];
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        u[g] = lower_halves(far[g][0], far_copy[g][0]);
+        v[g] = lower_halves(far[g][1], far_copy[g][1]);
+        wa0[g] = lower_halves(ae[g][0], ae[g][0]);
+        wa1[g] = lower_halves(ae[g][1], ae[g][1]);
+        wb0[g] = lower_halves(back2[g][0], back2[g][0]);
+        wb1[g] = lower_halves(back2[g][1], back2[g][1]);
+      }
+      const int act = lane < kSpreadHelperBase ? kLanes - lane : kFirst - (lane - kSpreadHelperBase);   // spread_act
+#pragma unroll 5
+      for (int k = kFirst; k >= kBoundary; --k) {
+        if (k <= act) {
+          asm volatile("");                          // keeps this an EXEC mask (see frontend_kernel)
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            up0[g] += u[g];
+            up0[g] += v[g];
+            up1[g] = fma(wa0[g], u[g], up1[g]);
+            up1[g] = fma(wa1[g], v[g], up1[g]);
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          up0[g] = lane_below(up0[g]);
+          up1[g] = lane_below(up1[g]);
+          u[g] *= wb0[g];
+          v[g] *= wb1[g];
+        }
+      }
+      const bool lower = lane < kSpreadHelperBase;
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        double2* hx = reinterpret_cast<double2*>(ppx[g]);
+        hx[(lane + spread_home_shift(NB) + kSpreadWave) & (kSpreadWave - 1)] = lower ? make_double2(0., 0.) : make_double2(up0[g], up1[g]);
+      }
+      wave_lds_fence();
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        home[g] = reinterpret_cast<const double2*>(ppx[g])[lane];
+        up0[g] = lower ? up0[g] : 0.;
+        up1[g] = lower ? up1[g] : 0.;
+        u[g] = lower ? u[g] : upper[g][0];
+        v[g] = lower ? v[g] : upper[g][1];
+      }
+#pragma unroll 8
+      for (int k = kBoundary - 1; k >= 1; --k) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          up0[g] += u[g];
+          up0[g] += v[g];
+          up1[g] = fma(ae[g][0], u[g], up1[g]);
+          up1[g] = fma(ae[g][1], v[g], up1[g]);
+          up0[g] = lane_below(up0[g]);
+          up1[g] = lane_below(up1[g]);
+          u[g] *= back2[g][0];
+          v[g] *= back2[g][1];
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        up0[g] += home[g].x;
+        up1[g] += home[g].y;
+        up1[g] = fma(ae[g][0], ene[g][0], up1[g]);
+      }
+    }
+    FE_MARK(5);
+    // downward spreading, Kabal (28), and the roots (25)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const double al = c_ale;
+      const double v = wave_suffix_geometric(ene[g][0] + al * ene[g][1], al * al, lane);
+      const double nxt = lane_above(v);
+      const double dn0 = v, dn1 = ene[g][1] + al * nxt;
+      double root[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const double e2 = (s ? dn1 : dn0) + (s ? up1[g] : up0[g]);
+        root[s] = b0 + s < NB ? sqrt_pos(sqrt_pos(e2)) : 0.;
+      }
+      if (b0 < kBandStride)
+        *reinterpret_cast<double2*>(rec + (g ? kRecRootTest : kRecRootRef) + b0) = make_double2(root[0], root[1]);
+    }
+  }
+  FE_MARK(6);
+  // ---- error harmonic structure, part 1 (movs.c:1383-1391): d[k] = ln(Pw_test / Pw_ref), k < 512, all eight per lane,
+  // into the scratch area (whose band-sum words have been read for the last time)
+  wave_lds_fence();
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = lane + 64 * j;
+    const double fr = pw_ref[k], ft = pw_test[k];
+    scratch[k] = (fr == 0. && ft == 0.) ? 0. : FE_LOG_NONNEG(ft / fr, ltab);   // +-inf when one side is digital silence
+  }
+  FE_MARK(8);
+  // ---- noise spectrum for the NMR MOVs (movs.c:992-996) in place over the test spectrum, and its band sums; the
+  // reference spectrum is dead behind it: its first words become the band sums' zero words, then all of it the EHS's
+  // exchange space
+  wave_lds_fence();
+  noise_spectrum_in_place(pw_ref, pw_test, lane);
+  if (lane < group_zero_words(NB) / 2) *reinterpret_cast<double2*>(pw_ref + 2 * lane) = make_double2(0., 0.);
+  wave_lds_fence();
+  if (lane < kGroupLanes) {
+    double s1, s2;
+    group_bands<NB>(edge1, edge2, pw_test, kPairOffPwRef - kPairOffPwTest, s1, s2);
+    rec[kRecNoise + lane] = s1;
+    rec[kRecNoise + NB - 1 - lane] = s2;
+  } else if (lane < kGroupLanes + kBandStride - NB) {
+    rec[kRecNoise + NB + lane - kGroupLanes] = 0.;   // padding slots of the band vector
+  }
+  wave_lds_fence();
+  FE_MARK(10);
+  const double ehs = pair_ehs(scratch, pw_ref, scratch, lane, ct, a.cfg);
+  if (lane == 0) rec[kRecEhs] = ehs;
+  FE_MARK(12);
+}
+
+// Which front end the basic version launches -- batch, sessions, broker and stage entries alike, so that a stream read
+// through a session and the same samples in a batch stay the same bit for bit (tests/test_gpu_backend_record_fetch.py,
+// the trajectory and broker tests hold them to that; the two kernels agree to a few ulp, not to the bit): the one-wave
+// kernel, or with PEAQ_AMD_FE=two_waves (development: A/B runs and the comparison tests, no variant build)
+// frontend_kernel<109>.  The environment is read once; select_frontend() overrides it within a process.
+static int g_fe_override = -1;                       // -1: the environment decides; 0: one wave; 1: two waves
+int select_frontend(int two_waves) {
+  const int before = g_fe_override;
+  g_fe_override = two_waves < 0 ? -1 : two_waves ? 1 : 0;
+  return before;
+}
+static bool frontend_two_waves() {
+  static const bool env = [] { const char* e = std::getenv("PEAQ_AMD_FE"); return e && std::strcmp(e, "two_waves") == 0; }();
+  return g_fe_override < 0 ? env : g_fe_override != 0;
+}
+
+static hipError_t launch_frontend_as(bool one_wave, int bands, const FrontendArgs& a, unsigned n_pairs, hipStream_t stream) {
   const unsigned grid = n_pairs * a.frames_per_launch * a.channels;
   if (grid == 0) return hipSuccess;
   if ((unsigned long long)n_pairs * a.frames_per_launch * a.channels >= (1ull << 26)) return hipErrorInvalidValue;
@@ -1305,13 +2063,19 @@ hipError_t launch_frontend(int bands, const FrontendArgs& a, unsigned n_pairs, h
 #define PEAQ_FE_LDS_PAD 0                    // occupancy experiments (VARIANT builds): LDS bytes a workgroup claims on top
 #endif
   const size_t lds = kLdsDoubles * sizeof(double) + PEAQ_FE_LDS_PAD;
-  if (bands == 109)
+  if (bands == 109 && one_wave)
+    hipLaunchKernelGGL(frontend_pair_kernel<109>, dim3(grid), dim3(64), kPairLdsDoubles * sizeof(double), stream, args);
+  else if (bands == 109)
     hipLaunchKernelGGL(frontend_kernel<109>, dim3(grid), dim3(128), lds, stream, args);
   else if (bands == 55)
     hipLaunchKernelGGL(frontend_kernel<55>, dim3(grid), dim3(128), lds, stream, args);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
+}
+
+hipError_t launch_frontend(int bands, const FrontendArgs& a, unsigned n_pairs, hipStream_t stream) {
+  return launch_frontend_as(bands == 109 && !frontend_two_waves(), bands, a, n_pairs, stream);
 }
 
 }  // namespace peaq

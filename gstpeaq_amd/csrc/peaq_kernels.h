@@ -41,6 +41,10 @@ struct FrontendArgs {
   Settings cfg;                 // centre_ehs_window, ehs_dc_before_window
 };
 hipError_t launch_frontend(int bands, const FrontendArgs& a, unsigned n_pairs, hipStream_t stream);
+// (109 bands: the one-wave kernel frontend_pair_kernel -- both signals of a frame in one wave --, unless
+// PEAQ_AMD_FE=two_waves (read once) or select_frontend(1) asks for frontend_kernel<109>; select_frontend returns the
+// previous override, -1: the environment decides)
+int select_frontend(int two_waves);
 // Most frames per launch for which the kernel's reciprocal multiplication is exact whatever the divisor:
 // the error term magic d - 2^32 is below d and the dividend below n_pairs d, so n_pairs d^2 <= 2^32 is enough.
 inline unsigned max_frames_per_launch(unsigned n_pairs) {

@@ -1713,6 +1713,26 @@ int peaq_debug_frontend (peaq_ctx *ctx, int bands, int channels, double playback
                          const float *d_ref, const float *d_test, uint32_t n_ref, uint32_t n_test,
                          int n_frames, double *host_out);
 
+/* Development switch of the basic version's front end, for A/B runs and comparison tests within one process:
+ * 0 = one wave per (pair, frame, channel) that carries reference and test together (the default), 1 = the two-wave
+ * kernel the advanced version's FFT path is built on, -1 = what the environment variable PEAQ_AMD_FE says ("two_waves"; read once).
+ * Applies to every launch of the basic version's front end: batch runs, sessions, brokers and the stage entries (one
+ * kernel for all of them, so that a session's reading and a batch over the same samples agree bit for bit).  Returns
+ * the previous value. */
+int peaq_debug_select_frontend (int two_waves);
+
+/* The basic version's front end over n_pairs pairs resident in device memory ([pair][pair_stride][channels]), launched
+ * the way the batch path launches it, frames_per_launch frames of every pair per grid.  Returns the records as the
+ * kernels exchange them, out[pair][frame][channel][PEAQ_DEBUG_RAW_RECORD_DOUBLES] for frame < n_frames (at least the
+ * longest pair's frame count; records of frames a pair does not have are zero):
+ *   { root ref[112], root test[112], noise in bands[112], bandwidth ref, bandwidth test, EHS, flags ref, flags test,
+ *     hop energy ref, hop energy of ref - test, pad[9] },  root = (spread band energy)^(1/4). */
+#define PEAQ_DEBUG_RAW_RECORD_DOUBLES 352
+int peaq_debug_frontend_pairs (peaq_ctx *ctx, int channels, double playback_level_db,
+                               const float *d_ref, const float *d_test, int n_pairs, size_t pair_stride,
+                               const uint32_t *n_ref, const uint32_t *n_test, int frames_per_launch,
+                               int n_frames, double *host_out);
+
 /* The same for the filter-bank ear model (advanced): per-block records
  *   out[block][channel][PEAQ_DEBUG_FB_RECORD_DOUBLES] =
  *   { unsmeared ref[40], unsmeared test[40], excitation ref[40], excitation test[40],

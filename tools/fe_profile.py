@@ -28,8 +28,13 @@ assert ctx.L.peaq_debug_frontend_profile(ctx.h, buf) == 0
 gstpeaq_amd.batch_run(ctx, ADV, ref, test)
 assert ctx.L.peaq_debug_frontend_profile(ctx.h, buf) == 0
 out = {}
+# (the one-wave kernel of the basic version, frontend_pair_kernel<109>, has one role: it reports as "ref", carries both
+# signals through every phase, and its marks 7, 9 and 11 -- barriers, a hand-over -- do not exist; PEAQ_AMD_FE=two_waves
+# selects frontend_kernel<109> and its two roles)
 for sig, name in ((0, "ref"), (1, "test")):
     n = buf[32 + sig]
+    if n == 0:
+        continue
     tot = sum(buf[sig * 16 + i] for i in range(16))
     out[name] = {"waves": n, "total_cycles_per_wave": tot / n,
                  "phases": {f"{i:2d} {PHASES[i]}": round(buf[sig * 16 + i] / n, 1) for i in range(len(PHASES))}}

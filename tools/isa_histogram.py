@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static opcode-class histogram of one kernel of a hipcc -S listing (development tool).
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Igstpeaq_amd/csrc -Iinclude -S --cuda-device-only -o fe.s gstpeaq_amd/csrc/peaq_frontend.hip
-  tools/isa_histogram.py fe.s frontend_kernelILi109E
+  tools/isa_histogram.py fe.s frontend_kernelILi109E      (the one-wave kernel of the batch path: frontend_pair_kernelILi109E)
 Classes: FP64 arithmetic, DPP moves, selects, plain moves, lane reads, permlane swaps, compares, other integer /
 FP32 vector instructions, LDS, vector memory, scalar.  Static counts: both waves' roles and both settings of a
 run-time switch are in the listing, a wave executes about 60 % of it (the PMC profile has the dynamic count)."""

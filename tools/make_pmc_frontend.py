@@ -14,16 +14,21 @@ G = ROOT / "gpurun_out"
 d = json.loads((G / "pmc_hbm_basic.json").read_text())
 mix = json.loads((G / "pmc_mix.json").read_text())
 stats = json.loads((G / "stats_basic.json").read_text())
-fe = next(v for k, v in d.items() if "frontend_kernel<109>" in k)
+# The basic step's front end: the one-wave kernel (reference and test of a frame in ONE wave) where the pass ran it, else
+# the two-wave kernel.  The per-wave figures below keep their meaning -- per (frame, channel, signal), what bench.py
+# multiplies by channels x 2 --: a one-wave kernel's counts are halved (SIGNALS waves' worth of work per wave).
+FE_NAME = "frontend_pair_kernel<109>" if any("frontend_pair_kernel<109>" in k for k in mix) else "frontend_kernel<109>"
+SIGNALS = 2 if FE_NAME.startswith("frontend_pair") else 1
+fe = next(v for k, v in d.items() if FE_NAME in k)
 be = next(v for k, v in d.items() if "backend_kernel<109" in k)
-fm = next(v for k, v in mix.items() if "frontend_kernel<109>" in k)
+fm = next(v for k, v in mix.items() if FE_NAME in k)
 bm = next(v for k, v in mix.items() if "backend_kernel<109" in k)
 launches = fe["FETCH_SIZE"]["dispatches"]
 pairs, frames, algo = 4096, 468, 16384
 algo_launch = pairs * frames * algo / launches
 rd = fe["FETCH_SIZE"]["avg"] * 1024 * 2          # gfx950: FETCH_SIZE reports 1/2 of a wide coalesced stream
 wr = fe["WRITE_SIZE"]["avg"] * 1024
-w = fm["SQ_WAVES"]["avg"]
+w = fm["SQ_WAVES"]["avg"] * SIGNALS               # "waves" = (frame, channel, signal) units
 fp64 = sum(fm[c]["avg"] for c in ("SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64",
                                   "SQ_INSTS_VALU_TRANS_F64")) / w
 sys.path.insert(0, str(ROOT))
@@ -34,7 +39,7 @@ be_valu = bm["SQ_INSTS_VALU"]["sum"] / be_wave_frames
 be_fp64 = sum(bm[c]["sum"] for c in ("SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64",
                                      "SQ_INSTS_VALU_TRANS_F64")) / be_wave_frames
 commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip()
-kavg = next(k["avg_us"] for k in stats["kernels"] if "frontend_kernel<109>" in k["kernel"]) / 1e3
+kavg = next(k["avg_us"] for k in stats["kernels"] if FE_NAME in k["kernel"]) / 1e3
 out = {
     "_command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py "
                 "--steps 1 --warmup 0 --no-cpu-baseline --no-advanced (configs[1]); instruction mix: tools/pmc_mix.sh (1024 pairs)",
@@ -42,7 +47,8 @@ out = {
               "(gfx950 correction, MI355X_MICROARCH.md HBM section), WRITE_SIZE (KiB) as is",
     "commit": commit,
     "source_hash": source_hash(),
-    "kernel": "frontend_kernel<109>",
+    "kernel": FE_NAME,
+    "signals_per_wave": SIGNALS,
     "kernel_avg_ms": kavg,
     "launches": launches,
     "algorithmic_bytes_per_launch": algo_launch,
@@ -56,9 +62,11 @@ out = {
     "valu_fp64_insts_per_wave": fp64,
     "lds_insts_per_wave": fm["SQ_INSTS_LDS"]["avg"] / w,
     "vmem_rd_insts_per_wave": fm["SQ_INSTS_VMEM_RD"]["avg"] / w,
-    "wave_cycles_per_wave": fm["SQ_WAVE_CYCLES"]["avg"] / w * 4,
+    "wave_cycles_per_wave": fm["SQ_WAVE_CYCLES"]["avg"] / fm["SQ_WAVES"]["avg"] * 4,   # (a real wave's lifetime, not halved)
     "wait_any_frac": fm["SQ_WAIT_ANY"]["avg"] / fm["SQ_WAVE_CYCLES"]["avg"],
-    "note": "reads = the input samples once (50 % frame overlap and channel interleave absorbed by the per-XCD L2, "
+    "note": ("per-wave instruction counts are per (frame, channel, signal): the one-wave kernel's counts halved, "
+             "wave_cycles_per_wave is the real wave's lifetime; " if SIGNALS == 2 else "") +
+            "reads = the input samples once (50 % frame overlap and channel interleave absorbed by the per-XCD L2, "
             "plus the L2 prefetch touching every line once more from L2); writes = the per-frame records handed to the "
             "back end (2816 B per frame and channel); no scratch traffic",
     "backend_kernel<109,false>": {
