@@ -349,6 +349,14 @@ def load_library():
         L.peaq_batch_windows_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.peaq_run_pair_windows.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp, C.c_size_t,
                                             vp, C.c_int, vp, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_batch_run_adv_spans"):         # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_span_blocks.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        L.peaq_batch_run_adv_spans.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_size_t, u32p, u32p,
+                                               C.c_uint32, vp, C.c_int, vp, vp, vp]
+        L.peaq_batch_adv_spans_workspace_bytes.restype = C.c_size_t
+        L.peaq_batch_adv_spans_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.peaq_run_pair_adv_spans.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
+                                              C.c_size_t, vp, C.c_int, vp, C.POINTER(Delay), dp]
     if hasattr(L, "peaq_batch_run_fb_band_summary"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_fb_band_summary_rows.argtypes = []
         L.peaq_fb_band_summary_row.argtypes = []
@@ -2430,6 +2438,65 @@ def run_pair_windows(ctx, ref, test, windows, playback_level=92.0, rate=48000, a
                                        *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
                                        out.ctypes.data_as(C.POINTER(C.c_double))))
     res = dict(windows=[_result_dict(r, False) for r in rows[:len(w)]], result=_result_dict(out, False))
+    if align is not None:
+        res["delay"] = _delay_dict(rec)
+    return res
+
+
+def span_blocks(n_ref, n_test, start, length):
+    """(first, count): the filter-bank blocks the span {start, length} covers of a pair with these lengths
+    (peaq_span_blocks; samples per channel at 48 kHz).  Its FFT frames are window_frames'."""
+    first, count = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().peaq_span_blocks(int(n_ref), int(n_test), int(start), int(length), C.byref(first),
+                                           C.byref(count)))
+    return first.value, count.value
+
+
+def batch_adv_spans(ctx, ref, test, spans, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
+                    stream=None, sync=True, d_spans=None, results=None, gain=None, gain_per_channel=False,
+                    max_gain_db=40.0, subsample=False):
+    """The score of time spans inside every pair in the advanced version, in the run that scores the batch
+    (peaq_batch_run_adv_spans; include/peaq_amd.h has which frames and blocks a span covers and what its reading is: a
+    view into the running stream, not a cold start).  spans: [start, length] rows in samples per channel at 48 kHz,
+    shared by all pairs (sliding_windows makes them).  The other arguments as for batch_windows.
+    d_spans / results: optional CUDA float64 tensors [n_pairs, n_spans, 16] / [n_pairs, 16] to write into.
+    Returns (spans, results): lists of result dicts, spans[p][s], (sync=True) or the device tensors."""
+    import torch
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample)
+    n_pairs, stride, channels = ref.shape
+    w, w_ptr = _windows_array(spans)
+    with _torch_stream(stream):
+        if d_spans is None:
+            d_spans = torch.empty((n_pairs, max(len(w), 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+        if results is None:
+            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_spans.is_cuda and d_spans.dtype == torch.float64 and d_spans.is_contiguous()
+    assert tuple(d_spans.shape) == (n_pairs, max(len(w), 1), RESULT_DOUBLES)
+    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
+    _check(ctx.L.peaq_batch_run_adv_spans(ctx.h, channels, float(playback_level), n_pairs, C.c_void_p(ref.data_ptr()),
+                                          C.c_void_p(test.data_ptr()), stride, *len_args, stride, w_ptr, len(w),
+                                          C.c_void_p(d_spans.data_ptr()), C.c_void_p(results.data_ptr()),
+                                          _stream_ptr(stream)))
+    if not sync:
+        return d_spans, results
+    torch.cuda.synchronize(ref.device)
+    return ([[_result_dict(r, True) for r in row] for row in d_spans.cpu().numpy()],
+            [_result_dict(r, True) for r in results.cpu().numpy()])
+
+
+def run_pair_adv_spans(ctx, ref, test, spans, playback_level=92.0, rate=48000, align=None):
+    """peaq_run_pair_adv_spans: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
+    first with align = a max_lag in 48 kHz samples; the spans count 48 kHz samples of the signals as scored.  Returns a
+    dict: spans (result dicts, one per span), result (a result dict) and, with align, delay."""
+    ref, test, ch, pair_args = _host_pair(ref, test)
+    w, w_ptr = _windows_array(spans)
+    rows = np.zeros((max(len(w), 1), RESULT_DOUBLES))
+    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
+    _check(ctx.L.peaq_run_pair_adv_spans(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
+                                         *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
+                                         out.ctypes.data_as(C.POINTER(C.c_double))))
+    res = dict(spans=[_result_dict(r, True) for r in rows[:len(w)]], result=_result_dict(out, True))
     if align is not None:
         res["delay"] = _delay_dict(rec)
     return res

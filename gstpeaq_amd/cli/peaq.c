@@ -31,6 +31,8 @@
  * --windows=SECONDS[:HOP_SECONDS] (basic version) also prints, before those two lines, one line per window of SECONDS
  * taken every HOP_SECONDS through the signals as scored, "window START_S END_S FRAMES ODG DI": the reading of the
  * frames the window covers, in the context of the running stream (peaq_run_pair_windows).
+ * --advanced --spans=SECONDS[:HOP_SECONDS] is the same for the advanced version, "span START_S END_S FRAMES BLOCKS ODG
+ * DI": the reading of the FFT frames and filter-bank blocks the span covers (peaq_run_pair_adv_spans).
  * --list=FILE scores many pairs in one run: FILE holds one pair per line, REF<TAB>TEST (empty lines and lines that
  * start with # are skipped).  The files' data chunks are handed to the engine as they are, in their own sample format
  * (peaq_batch_run_host: decoded, converted to 48 kHz and, with --align, aligned on the device), grouped by format,
@@ -607,6 +609,9 @@ usage (const char *prog)
       "                them: one line `window START_S END_S FRAMES ODG DI` each.  A window reads the frames it covers\n"
       "                in the context of the running stream, not the excerpt from a cold start (the plain one-call mode;\n"
       "                with --device-resample, --align; a run of its own, like --bands)\n"
+      "  --spans=S[:HOP] with --advanced: the same for the advanced version, one line `span START_S END_S FRAMES BLOCKS\n"
+      "                ODG DI` each: a span reads the FFT frames and the filter-bank blocks it covers in the context of\n"
+      "                the running stream (the plain one-call mode; with --device-resample, --align; a run of its own)\n"
       "  --list=FILE   score the pairs listed in FILE, one REF<TAB>TEST per line, instead of REFFILE TESTFILE;\n"
       "                prints REF<TAB>TEST<TAB>ODG<TAB>DI per pair (with --advanced, --level, --align)\n"
       "  --no-share-refs with --list: read and upload a reference file again for every line that names it\n", prog);
@@ -939,9 +944,10 @@ done:
  * every `hop` samples from 0, `length` samples each, up to the first that reaches the end, which ends there -- one line
  * per window.  With --align the scored length is the common part, known after the run: the windows are laid over the
  * longer file and those of the common part printed (a window that reaches the end of the scored signals reads through
- * their last frame wherever its own end lies).  Prints the delay line of --align. */
+ * their last frame wherever its own end lies).  Prints the delay line of --align.
+ * spans != 0: --spans=S[:HOP], the same through peaq_run_pair_adv_spans, the lines with the count of blocks as well. */
 static int
-print_windows (uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
+print_windows (int spans, uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint32_t rate, uint32_t align_lag,
     const wav_t *ref, const wav_t *test, peaq_result *r)
 {
   const uint32_t n_ref = rate == 48000 ? (uint32_t) ref->frames : peaq_resampled_length (ref->frames, rate);
@@ -955,7 +961,7 @@ print_windows (uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint3
   if (n > length)
     n_windows += ((size_t) n - length + hop - 1) / hop;
   if (n_windows > PEAQ_WINDOWS_MAX) {
-    printf ("Error: %zu windows are more than %d\n", n_windows, PEAQ_WINDOWS_MAX);
+    printf ("Error: %zu %s are more than %d\n", n_windows, spans ? "spans" : "windows", PEAQ_WINDOWS_MAX);
     return 1;
   }
   w = malloc (n_windows * sizeof *w);
@@ -968,8 +974,8 @@ print_windows (uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint3
     w[k].start = (uint32_t) (k * hop);
     w[k].length = length;
   }
-  if (peaq_run_pair_windows (ctx, ref->channels, level, rate, align_lag, ref->samples, ref->frames, test->samples,
-          test->frames, w, (int) n_windows, rows, &delay, r) != PEAQ_OK) {
+  if ((spans ? peaq_run_pair_adv_spans : peaq_run_pair_windows) (ctx, ref->channels, level, rate, align_lag, ref->samples,
+          ref->frames, test->samples, test->frames, w, (int) n_windows, rows, &delay, r) != PEAQ_OK) {
     printf ("Error: %s\n", peaq_last_error ());
     goto done;
   }
@@ -980,8 +986,12 @@ print_windows (uint32_t length, uint32_t hop, peaq_ctx *ctx, double level, uint3
   }
   for (k = 0; k < n_windows; k++) {
     const uint64_t end = (uint64_t) w[k].start + length;
-    printf ("window %.3f %.3f %.0f %.3f %.3f\n", w[k].start / 48000., (end < n ? end : n) / 48000., rows[k].frames,
-        rows[k].odg, rows[k].di);
+    if (spans)
+      printf ("span %.3f %.3f %.0f %.0f %.3f %.3f\n", w[k].start / 48000., (end < n ? end : n) / 48000., rows[k].frames,
+          rows[k].fb_blocks, rows[k].odg, rows[k].di);
+    else
+      printf ("window %.3f %.3f %.0f %.3f %.3f\n", w[k].start / 48000., (end < n ? end : n) / 48000., rows[k].frames,
+          rows[k].odg, rows[k].di);
     if (end >= n)
       break;
   }
@@ -1023,6 +1033,7 @@ main (int argc, char **argv)
   const char *band_summary_path = NULL;   /* --band-summary=FILE, peaq_run_pair_band_summary */
   const char *fb_band_summary_path = NULL;   /* --fb-band-summary=FILE, peaq_run_pair_fb_band_summary */
   uint32_t windows_length = 0, windows_hop = 0;   /* != 0: --windows=S[:HOP], peaq_run_pair_windows */
+  uint32_t spans_length = 0, spans_hop = 0;       /* != 0: --spans=S[:HOP], peaq_run_pair_adv_spans (with --advanced) */
   int share_refs = 1;
   wav_t ref, test;
   peaq_ctx *ctx = NULL;
@@ -1240,6 +1251,23 @@ main (int argc, char **argv)
       windows_length = (uint32_t) llround (len_s * 48000.);
       windows_hop = (uint32_t) llround (hop_s * 48000.);
     }
+    else if (!strcmp (argv[i], "--spans") || !strcmp (argv[i], "--spans=")) {
+      fprintf (stderr, "Failed to initialize: --spans needs a length in seconds (--spans=SECONDS[:HOP_SECONDS])\n");
+      return 1;
+    } else if (!strncmp (argv[i], "--spans=", 8)) {
+      char *end;
+      const double len_s = strtod (argv[i] + 8, &end);
+      double hop_s = len_s;
+      if (end != argv[i] + 8 && *end == ':' && end[1])
+        hop_s = strtod (end + 1, &end);
+      if (end == argv[i] + 8 || *end || !(len_s * 48000. >= 0.5 && len_s * 48000. < 4294967295.) ||
+          !(hop_s * 48000. >= 0.5 && hop_s * 48000. < 4294967295.)) {
+        fprintf (stderr, "Failed to initialize: invalid spans %s\n", argv[i] + 8);
+        return 1;
+      }
+      spans_length = (uint32_t) llround (len_s * 48000.);
+      spans_hop = (uint32_t) llround (hop_s * 48000.);
+    }
     else if (!strcmp (argv[i], "--version")) {
       printf ("peaq (gstpeaq_amd) %s\n", peaq_version ());
       return 0;
@@ -1313,7 +1341,19 @@ main (int argc, char **argv)
     return 1;
   }
   if (windows_length && advanced) {
-    fprintf (stderr, "Failed to initialize: --windows is for the basic version (the advanced version's windows are not built)\n");
+    fprintf (stderr, "Failed to initialize: --windows is for the basic version (the advanced version has --spans)\n");
+    return 1;
+  }
+  if (spans_length && !advanced) {
+    fprintf (stderr, "Failed to initialize: --spans is for the advanced version (--advanced --spans=...; the basic version has --windows)\n");
+    return 1;
+  }
+  if (spans_length && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
+    fprintf (stderr, "Failed to initialize: --spans belongs to the plain one-call mode (not with --list or --interval)\n");
+    return 1;
+  }
+  if (spans_length && (windows_length || bands_path || fb_bands_path || pattern_bands_path || band_summary_path || fb_band_summary_path || trace_path || gain_mode || steps_window || track_window || drift_window || subsample || wide_offset)) {
+    fprintf (stderr, "Failed to initialize: --spans is a run of its own (not with --windows, --bands, --fb-bands, --pattern-bands, --band-summary, --fb-band-summary, --trace, --match-gain or an --align-... beyond --align)\n");
     return 1;
   }
   if (windows_length && (interval_s > 0. || list_path || getenv ("PEAQ_AMD_CLI_STREAM") || getenv ("PEAQ_AMD_CLI_DUMP"))) {
@@ -1471,6 +1511,19 @@ main (int argc, char **argv)
     printf ("dumped %zu and %zu frames, %d channels\n", ref.frames, test.frames, ref.channels);
     return 0;
   }
+  if (spans_length) {
+    /* (the count print_windows is going to make, held against the limit before an engine is asked for) */
+    const uint32_t rate = device_rate ? device_rate : 48000;
+    const uint32_t n_r = rate == 48000 ? (uint32_t) ref.frames : peaq_resampled_length (ref.frames, rate);
+    const uint32_t n_t = rate == 48000 ? (uint32_t) test.frames : peaq_resampled_length (test.frames, rate);
+    const uint32_t n = n_r > n_t ? n_r : n_t;
+    const size_t n_spans = 1 + (n > spans_length ? ((size_t) n - spans_length + spans_hop - 1) / spans_hop : 0);
+    if (n_spans > PEAQ_WINDOWS_MAX) {
+      fprintf (stderr, "Failed to initialize: --spans makes %zu spans of these files, more than %d\n", n_spans,
+          PEAQ_WINDOWS_MAX);
+      return 1;
+    }
+  }
   if (peaq_ctx_create (getenv ("PEAQ_AMD_DEVICE") ? atoi (getenv ("PEAQ_AMD_DEVICE")) : 0, &ctx) != PEAQ_OK) {
     printf ("Error: peaq engine could not be instantiated - %s\n", peaq_last_error ());
     return 2;
@@ -1502,8 +1555,11 @@ main (int argc, char **argv)
   } else if (!getenv ("PEAQ_AMD_CLI_STREAM")) {
     /* both files are in memory: one call, every kernel sees the whole stream (a 5-minute pair of the advanced
      * version: 2 s instead of the 4 s of buffer-by-buffer sessions) */
-    if (windows_length) {
-      if (print_windows (windows_length, windows_hop, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+    if (spans_length) {
+      if (print_windows (1, spans_length, spans_hop, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
+        return 2;
+    } else if (windows_length) {
+      if (print_windows (0, windows_length, windows_hop, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))
         return 2;
     } else if (fb_band_summary_path) {
       if (write_fb_band_summary (fb_band_summary_path, ctx, level, device_rate ? device_rate : 48000, align_lag, &ref, &test, &r))

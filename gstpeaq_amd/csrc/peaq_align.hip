@@ -861,3 +861,25 @@ extern "C" int peaq_run_pair_windows(peaq_ctx* c, int channels, double level_db,
                                                          rows[0].dev.as<peaq_result>(), d_res, nullptr);
                          });
 }
+
+// (n_spans records per pair, as above; the advanced version)
+extern "C" int peaq_run_pair_adv_spans(peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                                       const float* ref, size_t n_ref, const float* test, size_t n_test,
+                                       const peaq_window* spans, int n_spans, peaq_result* out_spans, peaq_delay* delay,
+                                       peaq_result* out) {
+  const std::string w("peaq_run_pair_adv_spans");
+  if (!spans) return fail(PEAQ_ERR_ARG, w + ": spans is NULL");
+  if (n_spans < 1 || n_spans > PEAQ_WINDOWS_MAX)
+    return fail(PEAQ_ERR_ARG, w + ": n_spans " + std::to_string(n_spans) + " is outside 1 .. " +
+                                  std::to_string(PEAQ_WINDOWS_MAX));
+  for (int i = 0; i < n_spans; ++i)
+    if (spans[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": span " + std::to_string(i) + " has length 0");
+  if (!out_spans) return fail(PEAQ_ERR_ARG, w + ": out_spans is NULL");
+  PairRows rows[1] = {{PairRows::kPair, (size_t)n_spans * sizeof(peaq_result), out_spans, 1, "", nullptr}};
+  return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
+                         [&](const ScoredPair& pp, peaq_result* d_res) {
+                           return peaq_batch_run_adv_spans(c, channels, level_db, 1, pp.d[0], pp.d[1], pp.stride, pp.len,
+                                                           pp.len + 1, 0, spans, n_spans, rows[0].dev.as<peaq_result>(),
+                                                           d_res, nullptr);
+                         });
+}

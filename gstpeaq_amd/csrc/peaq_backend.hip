@@ -678,12 +678,14 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 //   out.pts              x    x    x    .    -      .           .             .            .
 //
 //   out.win              x    x    x  needs   x      x           x             x            x
+//   out.spn              x    x    x  needs   x      x           x             x          needs
 //
 // The rows-per-band outputs (bnd, pbd, sum) belong to a run's own launches: each stands alone.  The trace and the
 // points are not held against each other, the debug dump or a broker's windows: the trace wins over the points, either
 // wins over a.debug.  out.fbnd is the filter-bank path's and is not looked at here.  out.win (peaq_batch_run_windows)
 // launches nothing here: its replay (peaq_windows.hip) reads what the basic trace instantiation of a run's own launch
-// leaves, so it needs out.trc and nothing else.
+// leaves, so it needs out.trc and nothing else.  out.spn (peaq_batch_run_adv_spans) likewise with the 55-band trace
+// instantiation (peaq_spans.hip); out.win and out.spn exclude each other.
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
@@ -694,6 +696,9 @@ hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t st
                 (sum && a.pair_slot)))
     return hipErrorInvalidValue;
   if (out.has_win() && (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot || a.advanced))
+    return hipErrorInvalidValue;
+  if (out.has_spn() &&
+      (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot || !a.advanced || out.has_win()))
     return hipErrorInvalidValue;
   if (sum && !a.advanced)
     hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.sum);
@@ -796,12 +801,15 @@ __global__ __launch_bounds__(128, 4) void fb_band_summary_kernel(FbBackendArgs a
 //   out.fbnd              x     -    x    x      x         x          (a run's own launches only)
 //   out.trc               x     x    -    .      .         .
 //   out.pts               x     x    .    -      .         .
+//   out.spn               x     x  needs  x      x         x          (a run's own launches only)
 // out.fsum is also refused together with out.sum: a run has one summary, and the two share the context's saved copy.
 // out.bnd, out.pbd and out.sum are the FFT path's and are otherwise not looked at here.
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const bool pts = out.has_pts(), trc = out.has_trc(), bnd = out.has_fbnd(), fsum = out.has_fsum();
   if ((bnd || fsum) && (pts || trc || a.debug || a.windows || (bnd && fsum) || (fsum && out.has_sum())))
+    return hipErrorInvalidValue;
+  if (out.has_spn() && (!trc || !out.trc.blocks || pts || bnd || fsum || a.debug || a.windows))
     return hipErrorInvalidValue;
   if (fsum)
     hipLaunchKernelGGL(fb_band_summary_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.fsum);

@@ -166,6 +166,7 @@ struct peaq_ctx {
   DevBuf records, records2, fb_records, fb_records2, state, fbstate, hp_scratch, hp_scratch2, counts, clk;
   DevBuf snaps;             // trajectories: the reading points' snapshots [pair][point] (peaq_batch_run_trajectory)
   DevBuf win_trace, win_list;   // windows: the trace records the replay reads [pair][frame], the windows on the device (peaq_batch_run_windows; the snapshots are `snaps`)
+  DevBuf spn_blocks;        // spans: the block records the filter-bank replay reads [pair][block] (peaq_batch_run_adv_spans; the frame records, the list and the snapshots are win_trace, win_list and `snaps`)
   DevBuf sum_saved;         // band summaries: the rows as they were when a pair last turned tentative (peaq_batch_run_band_summary, peaq_batch_run_fb_band_summary)
   hipStream_t aux = nullptr;   // the back end runs here, overlapped with the next chunk's front end
   hipStream_t aux2 = nullptr;  // advanced: the filter-bank path runs here, beside the FFT path

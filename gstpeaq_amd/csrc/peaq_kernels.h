@@ -297,6 +297,50 @@ inline void window_frames(uint32_t n_ref, uint32_t n_test, uint32_t start, uint3
 hipError_t launch_window_replay(const WindowArgs& win, const double* records, unsigned frame0, unsigned frames_per_launch,
                                 int channels, unsigned n_pairs, hipStream_t stream);
 
+// ---- scores of time spans inside each pair, advanced version (peaq_batch_run_adv_spans) -------------------
+// Span s of a pair covers FFT frames [first, end) (window_frames above) and filter-bank blocks [first_b, end_b)
+// (span_blocks below: the device and peaq_span_blocks use the one rule) and is the read-out of the advanced version's
+// five accumulators that start fresh before frame `first` / block `first_b` and are fed what the pair's own were fed in
+// those units.  The feed is what the two trace instantiations of the same run leave (scratch of the context) and the
+// FFT front end's scalars; a span's accumulators sit in a PointSnap between the launches of a run.  A kernel argument
+// of span_replay_fft_kernel and span_replay_fb_kernel only (peaq_spans.hip).
+struct SpanArgs {
+  ResultRecord* out;            // [pair][n_spans]: where the read-out of the snapshots goes (the caller's d_spans)
+  PointSnap* snap;              // [pair][n_spans] (scratch)
+  const WindowSpan* spans;      // [n_spans] (device), shared by all pairs
+  int n_spans;
+  const FrameTrace* frames;     // [pair][frame_stride] (scratch): record f of a pair at its absolute frame index
+  size_t frame_stride;
+  const BlockTrace* blocks;     // [pair][block_stride] (scratch): record b of a pair at its absolute block index
+  size_t block_stride;
+  const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform
+  const uint32_t* n_test;
+  uint32_t n_uniform;
+};
+// blocks [first, end) of the span {start, length} of a pair with these lengths; B (a) = a / 192 is the trajectory's
+// (PointWalk<true>::count), TB = count_frames (.., 192, 192) of the pair
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void span_blocks(uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length, uint32_t& first,
+                        uint32_t& end) {
+  const uint32_t n = n_ref < n_test ? n_ref : n_test, m = n_ref < n_test ? n_test : n_ref;
+  const uint32_t full = n / (uint32_t)kFbFrame;
+  const uint32_t total = full + (m > (uint64_t)full * kFbFrame ? 1u : 0u);
+  const uint64_t e = (uint64_t)start + length;
+  const uint32_t a0 = start < n ? start : n, a1 = e < n ? (uint32_t)e : n;
+  first = start >= m ? total : a0 / (uint32_t)kFbFrame;
+  end = e >= m ? total : a1 / (uint32_t)kFbFrame;
+}
+// after launch_backend (its 55-band trace instantiation) of the same chunk, on the same stream: frames [frame0, frame0 +
+// frames_per_launch) of every pair replayed into SegmentalNMR, EHS and the energies of the spans that meet them
+hipError_t launch_span_replay_fft(const SpanArgs& spn, const double* records, unsigned frame0, unsigned frames_per_launch,
+                                  int channels, unsigned n_pairs, hipStream_t stream);
+// after launch_fb_backend (its trace instantiation) of the same chunk, on the same stream: blocks [block0, block0 +
+// blocks_per_launch) of every pair replayed into RmsModDiff, RmsNoiseLoudAsym and AvgLinDist of the spans that meet them
+hipError_t launch_span_replay_fb(const SpanArgs& spn, unsigned block0, unsigned blocks_per_launch, int channels,
+                                 unsigned n_pairs, hipStream_t stream);
+
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
@@ -313,6 +357,8 @@ struct RunOutputs {
   FbSummaryArgs fsum{};         // peaq_batch_run_fb_band_summary
   WindowArgs win{};             // peaq_batch_run_windows: windows, n_windows, out; the rest from batch_run_locked -- which
                                 // also points `trc` at the context's trace scratch: the replay's feed
+  SpanArgs spn{};               // peaq_batch_run_adv_spans: spans, n_spans, out; the rest from batch_run_locked, which
+                                // points `trc` at the context's frame and block scratch: the two replays' feed
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
@@ -321,8 +367,10 @@ struct RunOutputs {
   bool has_sum() const { return sum.rows != nullptr; }
   bool has_fsum() const { return fsum.rows != nullptr; }
   bool has_win() const { return win.out != nullptr; }
+  bool has_spn() const { return spn.out != nullptr; }
   bool any() const {
-    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_win();
+    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_win() ||
+           has_spn();
   }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first

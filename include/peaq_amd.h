@@ -658,7 +658,7 @@ int peaq_batch_run_fb_band_summary (peaq_ctx *ctx, int channels, double playback
  * workspace rules are peaq_batch_run's; PEAQ_ERR_NOMEM when the scratch cannot be reserved --
  * peaq_batch_windows_workspace_bytes: per pair a 128-byte trace record per frame and a 2184-byte snapshot per window on
  * top of the plain run's.  The call is a run of its own, like the traces and the trajectory.  There is no `advanced`
- * argument: the advanced version's windows need the filter-bank back end as a second feed and are not built. */
+ * argument: the advanced version's windows are peaq_batch_run_adv_spans below. */
 typedef struct { uint32_t start, length; } peaq_window;   /* samples per channel at 48 kHz */
 #define PEAQ_WINDOWS_MAX 4096
 int peaq_window_frames (uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length,
@@ -671,6 +671,64 @@ int peaq_batch_run_windows (peaq_ctx *ctx, int channels, double playback_level_d
                             peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
 size_t peaq_batch_windows_workspace_bytes (int channels, int n_pairs, uint32_t n_max, int n_windows);
 /* (peaq_run_pair_windows, the same for one pair from host memory: after peaq_run_pair_fb_band_summary below) */
+
+/* ---- spans: the score of a stretch of each pair in the advanced version, replayed on the device ----------------------
+ * The same reading as the section above gives for the basic version, for the advanced one.  The advanced version has
+ * two feeds with two units: the 55-band FFT path in frames of 2048 samples every 1024 (SegmentalNMR, EHS, the energies of
+ * totalsnr) and the filter-bank path in blocks of 192 samples (RmsModDiff, RmsNoiseLoudAsym, AvgLinDist).
+ *
+ * A span {start, length} is a peaq_window: samples per channel at 48 kHz.  With n = min (n_ref, n_test), m = max (n_ref,
+ * n_test) and e = start + length in 64 bits:
+ *   Frames.  [first, end) exactly as peaq_window_frames gives them: F, T = peaq_frame_count (n_ref, n_test, 0).
+ *   Blocks.  With B (a) = a / 192 (the trajectory's B) and TB = peaq_frame_count (n_ref, n_test, 1), [first_b, end_b):
+ *     first_b = start >= m ? TB : B (min (start, n)),   end_b = e >= m ? TB : B (min (e, n)),   count_b = end_b - first_b
+ * -- a span that reaches the end of the longer signal takes the flush frame and the flush block.  peaq_span_blocks
+ * returns exactly the block rule (host arithmetic only; first / count may be NULL, not both), and the device uses the
+ * same function.
+ *
+ * The reading of a span is what peaq_session_results of an advanced session would return if
+ *   - the five accumulators had been reset to their initial state just before frame `first` / block `first_b` (status
+ *     initial, every field zero),
+ *   - SegmentalNMR and EHS had then been given, for the frames first .. end - 1 in order, and RmsModDiff,
+ *     RmsNoiseLoudAsym and AvgLinDist, for the blocks first_b .. end_b - 1 in order, exactly what the pair's own
+ *     accumulators are given in those frames and blocks: the same tentative / normal turns (from the frame's, the
+ *     block's own data-boundary flag), the same values and weights, the same gates, and
+ *   - the two energies of totalsnr had been summed over those frames only.
+ * What each accumulator is given (PEAQ_TRACE_* are the flags of the unit's trace record):
+ *     RmsModDiff        block   when PEAQ_TRACE_MOD_OPEN    the block record's ch[c][0], weight ch[c][1]
+ *     RmsNoiseLoudAsym  block   when PEAQ_TRACE_LOUD_OPEN   ch[c][2] and ch[c][3] (noise loudness, missing components)
+ *     AvgLinDist        block   when PEAQ_TRACE_LOUD_OPEN   ch[c][4], weight 1
+ *     SegmentalNMR      frame   always                      the frame record's ch[c][0], weight 1
+ *     EHS               frame   when either signal has its energy bit in any channel    1000 ehs, weight 1
+ * Everything below the accumulators is the pair's own, IN CONTEXT: both ear models, time smearing, level and pattern
+ * adaptation, the modulation filters, the gate that keeps the first 125 blocks out of the filter-bank MOVs and the
+ * loudness gate are where the running stream has them.  A span is a view into the running stream, NOT a cold-start
+ * score of the excerpt: for that, score the excerpt as a pair of its own -- a pair_stride view into the same buffers
+ * through peaq_batch_run -- whose ear models, adaptation and gates then start cold, at the price of both front ends per
+ * span (every row of such a view, pair_stride samples from its first one, has to lie inside the caller's allocation: the
+ * kernels may read a row beyond the pair's length, so the last pair needs that much room behind it).  `frames` of a span's record is end - first, `fb_blocks` is count_b.  An empty span reads what the read-out of an
+ * untouched accumulator set reads, like a trajectory point before the first frame.
+ * It follows (same operations, same order, from 0 + x; default FP64 engine): a span {0, L} with L < m is bit for bit
+ * point k of peaq_batch_run_trajectory (advanced = 1) with (k + 1) interval == L; a span {0, L} with L >= m is bit for
+ * bit d_results; and d_results is bit for bit peaq_batch_run's.
+ *
+ * spans (HOST, n_spans of them, 1 .. PEAQ_WINDOWS_MAX, none of length 0) are shared by all pairs; d_spans (device,
+ * 16-byte aligned) receives [n_pairs][n_spans] records; d_results may be NULL.  The other arguments, the refusals
+ * (PEAQ_ERR_ARG before a context or a device is touched, the message naming entry and value), stream and workspace rules
+ * are peaq_batch_run's; PEAQ_ERR_NOMEM when the scratch cannot be reserved, before anything is enqueued --
+ * peaq_batch_adv_spans_workspace_bytes: peaq_batch_workspace_bytes (1, ..) plus, per pair, a 128-byte trace record per
+ * frame, a 96-byte trace record per block and a 2184-byte snapshot per span, plus 8 bytes per span.  The call is a run of
+ * its own, like the traces, the trajectory and the basic version's windows. */
+int peaq_span_blocks (uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_t length,
+                      uint32_t *first, uint32_t *count);
+int peaq_batch_run_adv_spans (peaq_ctx *ctx, int channels, double playback_level_db, int n_pairs,
+                              const float *d_ref, const float *d_test, size_t pair_stride,
+                              const uint32_t *n_ref, const uint32_t *n_test, uint32_t n_uniform,
+                              const peaq_window *spans /* host, shared by all pairs */, int n_spans,
+                              peaq_result *d_spans /* device, [n_pairs][n_spans] */,
+                              peaq_result *d_results /* device, [n_pairs], may be NULL */, void *stream);
+size_t peaq_batch_adv_spans_workspace_bytes (int channels, int n_pairs, uint32_t n_max, int n_spans);
+/* (peaq_run_pair_adv_spans, the same for one pair from host memory: after peaq_run_pair_windows below) */
 
 /* Timing of the last peaq_batch_run on this context, measured with HIP events
  * on `stream`: total milliseconds, and milliseconds / launch count of the
@@ -890,6 +948,14 @@ int peaq_run_pair_windows (peaq_ctx *ctx, int channels, double playback_level_db
                            const float *ref, size_t n_ref, const float *test, size_t n_test,
                            const peaq_window *windows, int n_windows, peaq_result *out_windows /* host */,
                            peaq_delay *delay /* host */, peaq_result *out);
+/* peaq_batch_run_adv_spans (above) for one pair from HOST memory, the n_spans records into a host array: upload,
+ * conversion and alignment as in peaq_run_pair_windows; the spans count 48 kHz samples of the signals as scored, after
+ * conversion and cut.  out (may be NULL): the pair's result. */
+int peaq_run_pair_adv_spans (peaq_ctx *ctx, int channels, double playback_level_db,
+                             uint32_t rate, uint32_t max_lag,
+                             const float *ref, size_t n_ref, const float *test, size_t n_test,
+                             const peaq_window *spans, int n_spans, peaq_result *out_spans /* host */,
+                             peaq_delay *delay /* host */, peaq_result *out);
 
 /* ---- PCM from host memory: device decoder and host-fed batch ------------------------
  * Corpora are 16- or 24-bit PCM files in host memory; the batch entry points above take interleaved F32 in device
