@@ -2393,6 +2393,48 @@ def _windows_array(windows):
     return w, C.c_void_p(w.ctypes.data) if len(w) else None
 
 
+def _batch_spans(entry_name, advanced, ctx, ref, test, spans, n_ref, n_test, playback_level, rate, align, stream, sync,
+                 d_spans, results, gain, gain_per_channel, max_gain_db, subsample):
+    """batch_windows (peaq_batch_run_windows, basic version) and batch_adv_spans (peaq_batch_run_adv_spans)"""
+    import torch
+    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
+                                                      gain_per_channel, max_gain_db, subsample)
+    n_pairs, stride, channels = ref.shape
+    w, w_ptr = _windows_array(spans)
+    with _torch_stream(stream):
+        if d_spans is None:
+            d_spans = torch.empty((n_pairs, max(len(w), 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+        if results is None:
+            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
+    assert d_spans.is_cuda and d_spans.dtype == torch.float64 and d_spans.is_contiguous()
+    assert tuple(d_spans.shape) == (n_pairs, max(len(w), 1), RESULT_DOUBLES)
+    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
+    _check(getattr(ctx.L, entry_name)(ctx.h, channels, float(playback_level), n_pairs, C.c_void_p(ref.data_ptr()),
+                                      C.c_void_p(test.data_ptr()), stride, *len_args, stride, w_ptr, len(w),
+                                      C.c_void_p(d_spans.data_ptr()), C.c_void_p(results.data_ptr()),
+                                      _stream_ptr(stream)))
+    if not sync:
+        return d_spans, results
+    torch.cuda.synchronize(ref.device)
+    return ([[_result_dict(r, advanced) for r in row] for row in d_spans.cpu().numpy()],
+            [_result_dict(r, advanced) for r in results.cpu().numpy()])
+
+
+def _run_pair_spans(entry_name, advanced, key, ctx, ref, test, spans, playback_level, rate, align):
+    """run_pair_windows (peaq_run_pair_windows, basic version) and run_pair_adv_spans (peaq_run_pair_adv_spans)"""
+    ref, test, ch, pair_args = _host_pair(ref, test)
+    w, w_ptr = _windows_array(spans)
+    rows = np.zeros((max(len(w), 1), RESULT_DOUBLES))
+    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
+    _check(getattr(ctx.L, entry_name)(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
+                                      *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
+                                      out.ctypes.data_as(C.POINTER(C.c_double))))
+    res = {key: [_result_dict(r, advanced) for r in rows[:len(w)]], "result": _result_dict(out, advanced)}
+    if align is not None:
+        res["delay"] = _delay_dict(rec)
+    return res
+
+
 def batch_windows(ctx, ref, test, windows, n_ref=None, n_test=None, playback_level=92.0, rate=48000, align=None,
                   stream=None, sync=True, d_windows=None, results=None, gain=None, gain_per_channel=False,
                   max_gain_db=40.0, subsample=False):
@@ -2402,45 +2444,15 @@ def batch_windows(ctx, ref, test, windows, n_ref=None, n_test=None, playback_lev
     (sliding_windows makes them).  ref/test, n_ref/n_test, rate, align, gain and subsample as for batch_trace.
     d_windows / results: optional CUDA float64 tensors [n_pairs, n_windows, 16] / [n_pairs, 16] to write into.
     Returns (windows, results): lists of result dicts, windows[p][w], (sync=True) or the device tensors."""
-    import torch
-    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
-                                                      gain_per_channel, max_gain_db, subsample)
-    n_pairs, stride, channels = ref.shape
-    w, w_ptr = _windows_array(windows)
-    with _torch_stream(stream):
-        if d_windows is None:
-            d_windows = torch.empty((n_pairs, max(len(w), 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-        if results is None:
-            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    assert d_windows.is_cuda and d_windows.dtype == torch.float64 and d_windows.is_contiguous()
-    assert tuple(d_windows.shape) == (n_pairs, max(len(w), 1), RESULT_DOUBLES)
-    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
-    _check(ctx.L.peaq_batch_run_windows(ctx.h, channels, float(playback_level), n_pairs, C.c_void_p(ref.data_ptr()),
-                                        C.c_void_p(test.data_ptr()), stride, *len_args, stride, w_ptr, len(w),
-                                        C.c_void_p(d_windows.data_ptr()), C.c_void_p(results.data_ptr()),
-                                        _stream_ptr(stream)))
-    if not sync:
-        return d_windows, results
-    torch.cuda.synchronize(ref.device)
-    return ([[_result_dict(r, False) for r in row] for row in d_windows.cpu().numpy()],
-            [_result_dict(r, False) for r in results.cpu().numpy()])
+    return _batch_spans("peaq_batch_run_windows", False, ctx, ref, test, windows, n_ref, n_test, playback_level, rate,
+                        align, stream, sync, d_windows, results, gain, gain_per_channel, max_gain_db, subsample)
 
 
 def run_pair_windows(ctx, ref, test, windows, playback_level=92.0, rate=48000, align=None):
     """peaq_run_pair_windows: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
     first with align = a max_lag in 48 kHz samples; the windows count 48 kHz samples of the signals as scored.  Returns
     a dict: windows (result dicts, one per window), result (a result dict) and, with align, delay."""
-    ref, test, ch, pair_args = _host_pair(ref, test)
-    w, w_ptr = _windows_array(windows)
-    rows = np.zeros((max(len(w), 1), RESULT_DOUBLES))
-    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
-    _check(ctx.L.peaq_run_pair_windows(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
-                                       *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
-                                       out.ctypes.data_as(C.POINTER(C.c_double))))
-    res = dict(windows=[_result_dict(r, False) for r in rows[:len(w)]], result=_result_dict(out, False))
-    if align is not None:
-        res["delay"] = _delay_dict(rec)
-    return res
+    return _run_pair_spans("peaq_run_pair_windows", False, "windows", ctx, ref, test, windows, playback_level, rate, align)
 
 
 def span_blocks(n_ref, n_test, start, length):
@@ -2461,45 +2473,15 @@ def batch_adv_spans(ctx, ref, test, spans, n_ref=None, n_test=None, playback_lev
     shared by all pairs (sliding_windows makes them).  The other arguments as for batch_windows.
     d_spans / results: optional CUDA float64 tensors [n_pairs, n_spans, 16] / [n_pairs, 16] to write into.
     Returns (spans, results): lists of result dicts, spans[p][s], (sync=True) or the device tensors."""
-    import torch
-    ref, test, a_ref, a_test, len_args = _batch_front(ctx, ref, test, n_ref, n_test, rate, align, stream, gain,
-                                                      gain_per_channel, max_gain_db, subsample)
-    n_pairs, stride, channels = ref.shape
-    w, w_ptr = _windows_array(spans)
-    with _torch_stream(stream):
-        if d_spans is None:
-            d_spans = torch.empty((n_pairs, max(len(w), 1), RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-        if results is None:
-            results = torch.empty((n_pairs, RESULT_DOUBLES), dtype=torch.float64, device=ref.device)
-    assert d_spans.is_cuda and d_spans.dtype == torch.float64 and d_spans.is_contiguous()
-    assert tuple(d_spans.shape) == (n_pairs, max(len(w), 1), RESULT_DOUBLES)
-    assert results.is_cuda and results.dtype == torch.float64 and results.is_contiguous()
-    _check(ctx.L.peaq_batch_run_adv_spans(ctx.h, channels, float(playback_level), n_pairs, C.c_void_p(ref.data_ptr()),
-                                          C.c_void_p(test.data_ptr()), stride, *len_args, stride, w_ptr, len(w),
-                                          C.c_void_p(d_spans.data_ptr()), C.c_void_p(results.data_ptr()),
-                                          _stream_ptr(stream)))
-    if not sync:
-        return d_spans, results
-    torch.cuda.synchronize(ref.device)
-    return ([[_result_dict(r, True) for r in row] for row in d_spans.cpu().numpy()],
-            [_result_dict(r, True) for r in results.cpu().numpy()])
+    return _batch_spans("peaq_batch_run_adv_spans", True, ctx, ref, test, spans, n_ref, n_test, playback_level, rate,
+                        align, stream, sync, d_spans, results, gain, gain_per_channel, max_gain_db, subsample)
 
 
 def run_pair_adv_spans(ctx, ref, test, spans, playback_level=92.0, rate=48000, align=None):
     """peaq_run_pair_adv_spans: one whole pair from host memory (numpy float32 [n, channels]), sampled at `rate`, aligned
     first with align = a max_lag in 48 kHz samples; the spans count 48 kHz samples of the signals as scored.  Returns a
     dict: spans (result dicts, one per span), result (a result dict) and, with align, delay."""
-    ref, test, ch, pair_args = _host_pair(ref, test)
-    w, w_ptr = _windows_array(spans)
-    rows = np.zeros((max(len(w), 1), RESULT_DOUBLES))
-    rec, out = Delay(), np.zeros(RESULT_DOUBLES)
-    _check(ctx.L.peaq_run_pair_adv_spans(ctx.h, ch, float(playback_level), int(rate), 0 if align is None else int(align),
-                                         *pair_args, w_ptr, len(w), C.c_void_p(rows.ctypes.data), C.byref(rec),
-                                         out.ctypes.data_as(C.POINTER(C.c_double))))
-    res = dict(spans=[_result_dict(r, True) for r in rows[:len(w)]], result=_result_dict(out, True))
-    if align is not None:
-        res["delay"] = _delay_dict(rec)
-    return res
+    return _run_pair_spans("peaq_run_pair_adv_spans", True, "spans", ctx, ref, test, spans, playback_level, rate, align)
 
 
 def _fb_band_summary_views(rows, n_bands=40):

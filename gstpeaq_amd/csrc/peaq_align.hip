@@ -846,13 +846,7 @@ extern "C" int peaq_run_pair_windows(peaq_ctx* c, int channels, double level_db,
                                      const peaq_window* windows, int n_windows, peaq_result* out_windows,
                                      peaq_delay* delay, peaq_result* out) {
   const std::string w("peaq_run_pair_windows");
-  if (!windows) return fail(PEAQ_ERR_ARG, w + ": windows is NULL");
-  if (n_windows < 1 || n_windows > PEAQ_WINDOWS_MAX)
-    return fail(PEAQ_ERR_ARG, w + ": n_windows " + std::to_string(n_windows) + " is outside 1 .. " +
-                                  std::to_string(PEAQ_WINDOWS_MAX));
-  for (int i = 0; i < n_windows; ++i)
-    if (windows[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(i) + " has length 0");
-  if (!out_windows) return fail(PEAQ_ERR_ARG, w + ": out_windows is NULL");
+  if (int rc = check_span_list(w, "windows", "window", windows, n_windows, "out_windows", out_windows)) return rc;
   PairRows rows[1] = {{PairRows::kPair, (size_t)n_windows * sizeof(peaq_result), out_windows, 1, "", nullptr}};
   return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
                          [&](const ScoredPair& pp, peaq_result* d_res) {
@@ -868,13 +862,7 @@ extern "C" int peaq_run_pair_adv_spans(peaq_ctx* c, int channels, double level_d
                                        const peaq_window* spans, int n_spans, peaq_result* out_spans, peaq_delay* delay,
                                        peaq_result* out) {
   const std::string w("peaq_run_pair_adv_spans");
-  if (!spans) return fail(PEAQ_ERR_ARG, w + ": spans is NULL");
-  if (n_spans < 1 || n_spans > PEAQ_WINDOWS_MAX)
-    return fail(PEAQ_ERR_ARG, w + ": n_spans " + std::to_string(n_spans) + " is outside 1 .. " +
-                                  std::to_string(PEAQ_WINDOWS_MAX));
-  for (int i = 0; i < n_spans; ++i)
-    if (spans[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": span " + std::to_string(i) + " has length 0");
-  if (!out_spans) return fail(PEAQ_ERR_ARG, w + ": out_spans is NULL");
+  if (int rc = check_span_list(w, "spans", "span", spans, n_spans, "out_spans", out_spans)) return rc;
   PairRows rows[1] = {{PairRows::kPair, (size_t)n_spans * sizeof(peaq_result), out_spans, 1, "", nullptr}};
   return run_pair_output(w, c, channels, level_db, rate, max_lag, ref, n_ref, test, n_test, delay, out, rows, 1,
                          [&](const ScoredPair& pp, peaq_result* d_res) {

@@ -677,15 +677,14 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 //   out.trc              x    x    x    -    .      .           .             .            .
 //   out.pts              x    x    x    .    -      .           .             .            .
 //
-//   out.win              x    x    x  needs   x      x           x             x            x
-//   out.spn              x    x    x  needs   x      x           x             x          needs
+//   out.spn              x    x    x  needs   x      x           x             x     as spn.blocks
 //
 // The rows-per-band outputs (bnd, pbd, sum) belong to a run's own launches: each stands alone.  The trace and the
 // points are not held against each other, the debug dump or a broker's windows: the trace wins over the points, either
-// wins over a.debug.  out.fbnd is the filter-bank path's and is not looked at here.  out.win (peaq_batch_run_windows)
-// launches nothing here: its replay (peaq_windows.hip) reads what the basic trace instantiation of a run's own launch
-// leaves, so it needs out.trc and nothing else.  out.spn (peaq_batch_run_adv_spans) likewise with the 55-band trace
-// instantiation (peaq_spans.hip); out.win and out.spn exclude each other.
+// wins over a.debug.  out.fbnd is the filter-bank path's and is not looked at here.  out.spn (peaq_batch_run_windows,
+// peaq_batch_run_adv_spans) launches nothing here: its replay (peaq_replay.hip) reads what the trace instantiation of a
+// run's own launch leaves -- the basic or the 55-band one, as a.advanced says --, so it needs out.trc and nothing else of
+// the run's own outputs.
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
@@ -695,10 +694,8 @@ hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t st
   if (alone && (alone + pts + trc + (a.debug != nullptr) + (a.pair_frame0 != nullptr) > 1 || (pbd && a.advanced) ||
                 (sum && a.pair_slot)))
     return hipErrorInvalidValue;
-  if (out.has_win() && (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot || a.advanced))
-    return hipErrorInvalidValue;
-  if (out.has_spn() &&
-      (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot || !a.advanced || out.has_win()))
+  if (out.has_spn() && (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot ||
+                        (a.advanced != 0) != (out.spn.blocks != nullptr)))   // (block records: the advanced version's)
     return hipErrorInvalidValue;
   if (sum && !a.advanced)
     hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.sum);

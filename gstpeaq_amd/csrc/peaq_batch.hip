@@ -513,13 +513,16 @@ extern "C" int peaq_window_frames(uint32_t n_ref, uint32_t n_test, uint32_t star
   return PEAQ_OK;
 }
 
-// the scratch a windows run adds to the plain run's: the trace records the replay reads, the windows' snapshots, the
-// windows themselves; 0 when it does not fit size_t
-static size_t windows_scratch_bytes(int n_pairs, uint32_t max_frames, int n_windows) {
-  const size_t np = (size_t)std::max(n_pairs, 0), nw = (size_t)std::max(n_windows, 0);
-  const size_t per_pair = (size_t)std::max<uint32_t>(max_frames, 1) * sizeof(FrameTrace) + nw * sizeof(PointSnap);
-  if (np && per_pair > (SIZE_MAX - nw * sizeof(WindowSpan)) / np) return 0;
-  return np * per_pair + nw * sizeof(WindowSpan);
+// the scratch a windows or spans run adds to the plain run's: the frame records and (max_blocks: the advanced version's;
+// 0 in the basic) the block records the replays read, the spans' snapshots, the spans themselves; 0 when it does not fit
+// size_t
+static size_t spans_scratch_bytes(bool advanced, int n_pairs, uint32_t max_frames, uint32_t max_blocks, int n_spans) {
+  const size_t np = (size_t)std::max(n_pairs, 0), ns = (size_t)std::max(n_spans, 0);
+  const size_t per_pair = (size_t)std::max<uint32_t>(max_frames, 1) * sizeof(FrameTrace) +
+                          (advanced ? (size_t)std::max<uint32_t>(max_blocks, 1) * sizeof(BlockTrace) : 0) +
+                          ns * sizeof(PointSnap);
+  if (np && per_pair > (SIZE_MAX - ns * sizeof(WindowSpan)) / np) return 0;
+  return np * per_pair + ns * sizeof(WindowSpan);
 }
 
 // The windows' own arguments first, as the traces': they need no context and no device.
@@ -528,24 +531,19 @@ extern "C" int peaq_batch_run_windows(peaq_ctx* c, int channels, double level_db
                                       const uint32_t* n_test, uint32_t n_uniform, const peaq_window* windows,
                                       int n_windows, peaq_result* d_windows, peaq_result* d_results, void* stream_) {
   const std::string w("peaq_batch_run_windows");
-  if (int rc = check_not_null(w, "windows", windows)) return rc;
-  if (n_windows < 1 || n_windows > PEAQ_WINDOWS_MAX)
-    return fail(PEAQ_ERR_ARG, w + ": n_windows " + std::to_string(n_windows) + " is outside 1 .. " +
-                                  std::to_string(PEAQ_WINDOWS_MAX));
-  for (int i = 0; i < n_windows; ++i)
-    if (windows[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(i) + " has length 0");
-  if (int rc = check_output(w, "d_windows", d_windows)) return rc;
+  if (int rc = check_span_list(w, "windows", "window", windows, n_windows, "d_windows", d_windows)) return rc;
+  if (int rc = check_aligned(w, "d_windows", d_windows)) return rc;
   RunOutputs out;
-  out.win.out = reinterpret_cast<ResultRecord*>(d_windows);
-  out.win.windows = reinterpret_cast<const WindowSpan*>(windows);   // (host: batch_run_locked puts them on the device)
-  out.win.n_windows = n_windows;
+  out.spn.out = reinterpret_cast<ResultRecord*>(d_windows);
+  out.spn.spans = reinterpret_cast<const WindowSpan*>(windows);     // (host: batch_run_locked puts them on the device)
+  out.spn.n_spans = n_windows;
   return batch_run_entry("peaq_batch_run_windows", c, 0, channels, level_db, n_pairs, d_ref, d_test, pair_stride, n_ref,
                          n_test, n_uniform, d_results, stream_, out);
 }
 
 extern "C" size_t peaq_batch_windows_workspace_bytes(int channels, int n_pairs, uint32_t n_max, int n_windows) {
   return peaq_batch_workspace_bytes(0, channels, n_pairs, n_max) +
-         windows_scratch_bytes(n_pairs, count_frames(n_max, n_max, kFrame, kHop), n_windows);
+         spans_scratch_bytes(false, n_pairs, count_frames(n_max, n_max, kFrame, kHop), 0, n_windows);
 }
 
 // ---- scores of time spans inside each pair (advanced version) ----------------------------------------------------
@@ -559,29 +557,14 @@ extern "C" int peaq_span_blocks(uint32_t n_ref, uint32_t n_test, uint32_t start,
   return PEAQ_OK;
 }
 
-// the scratch a spans run adds to the plain advanced run's: the frame and block records the replays read, the spans'
-// snapshots, the spans themselves; 0 when it does not fit size_t
-static size_t spans_scratch_bytes(int n_pairs, uint32_t max_frames, uint32_t max_blocks, int n_spans) {
-  const size_t np = (size_t)std::max(n_pairs, 0), ns = (size_t)std::max(n_spans, 0);
-  const size_t per_pair = (size_t)std::max<uint32_t>(max_frames, 1) * sizeof(FrameTrace) +
-                          (size_t)std::max<uint32_t>(max_blocks, 1) * sizeof(BlockTrace) + ns * sizeof(PointSnap);
-  if (np && per_pair > (SIZE_MAX - ns * sizeof(WindowSpan)) / np) return 0;
-  return np * per_pair + ns * sizeof(WindowSpan);
-}
-
 // The spans' own arguments first, as the windows': they need no context and no device.
 extern "C" int peaq_batch_run_adv_spans(peaq_ctx* c, int channels, double level_db, int n_pairs, const float* d_ref,
                                         const float* d_test, size_t pair_stride, const uint32_t* n_ref,
                                         const uint32_t* n_test, uint32_t n_uniform, const peaq_window* spans,
                                         int n_spans, peaq_result* d_spans, peaq_result* d_results, void* stream_) {
   const std::string w("peaq_batch_run_adv_spans");
-  if (int rc = check_not_null(w, "spans", spans)) return rc;
-  if (n_spans < 1 || n_spans > PEAQ_WINDOWS_MAX)
-    return fail(PEAQ_ERR_ARG, w + ": n_spans " + std::to_string(n_spans) + " is outside 1 .. " +
-                                  std::to_string(PEAQ_WINDOWS_MAX));
-  for (int i = 0; i < n_spans; ++i)
-    if (spans[i].length == 0) return fail(PEAQ_ERR_ARG, w + ": span " + std::to_string(i) + " has length 0");
-  if (int rc = check_output(w, "d_spans", d_spans)) return rc;
+  if (int rc = check_span_list(w, "spans", "span", spans, n_spans, "d_spans", d_spans)) return rc;
+  if (int rc = check_aligned(w, "d_spans", d_spans)) return rc;
   RunOutputs out;
   out.spn.out = reinterpret_cast<ResultRecord*>(d_spans);
   out.spn.spans = reinterpret_cast<const WindowSpan*>(spans);       // (host: batch_run_locked puts them on the device)
@@ -592,7 +575,7 @@ extern "C" int peaq_batch_run_adv_spans(peaq_ctx* c, int channels, double level_
 
 extern "C" size_t peaq_batch_adv_spans_workspace_bytes(int channels, int n_pairs, uint32_t n_max, int n_spans) {
   return peaq_batch_workspace_bytes(1, channels, n_pairs, n_max) +
-         spans_scratch_bytes(n_pairs, count_frames(n_max, n_max, kFrame, kHop),
+         spans_scratch_bytes(true, n_pairs, count_frames(n_max, n_max, kFrame, kHop),
                              count_frames(n_max, n_max, kFbFrame, kFbFrame), n_spans);
 }
 
@@ -710,60 +693,39 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     out.trc.n_test = d_ntest;
     out.trc.n_uniform = n_uniform;
   }
-  // windows: every FFT back-end launch of the run is the trace instantiation, writing into scratch of the context, and
-  // is followed by the replay of its frames into the windows' snapshots (peaq_windows.hip).  All of it is reserved here,
-  // so that running out of memory is reported before anything is enqueued.
-  const size_t n_wsnaps = out.has_win() ? (size_t)n_pairs * out.win.n_windows : 0;
-  if (out.has_win()) {
-    if (advanced || out.has_trc() || out.has_pts() || out.has_spn())
-      return fail(PEAQ_ERR_ARG, std::string(who) + ": windows are a run of their own, of the basic version");
-    if (windows_scratch_bytes(n_pairs, max_frames, out.win.n_windows) == 0)
-      return fail(PEAQ_ERR_NOMEM, std::string(who) + ": the windows' scratch exceeds the address space");
-    const size_t trace_stride = std::max<uint32_t>(max_frames, 1);
-    HIP_TRY(c->win_trace.reserve((size_t)n_pairs * trace_stride * sizeof(FrameTrace)));
-    HIP_TRY(c->snaps.reserve(n_wsnaps * sizeof(PointSnap)));
-    HIP_TRY(c->win_list.reserve((size_t)out.win.n_windows * sizeof(WindowSpan)));
-    HIP_TRY(hipMemcpyAsync(c->win_list.p, out.win.windows, (size_t)out.win.n_windows * sizeof(WindowSpan),
-                           hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));           // the caller's array is read by now
-    out.win.windows = c->win_list.as<WindowSpan>();
-    out.win.snap = c->snaps.as<PointSnap>();
-    out.win.trace = c->win_trace.as<FrameTrace>();
-    out.win.trace_stride = trace_stride;
-    out.win.n_ref = d_nref;
-    out.win.n_test = d_ntest;
-    out.win.n_uniform = n_uniform;
-    out.trc = TraceArgs{c->win_trace.as<FrameTrace>(), trace_stride, nullptr, 0, d_nref, d_ntest, n_uniform};
-  }
-  // spans: the same for the advanced version, with two feeds -- every launch of both back ends is the trace
-  // instantiation, writing frame and block records into scratch of the context, and is followed on its own stream by the
-  // replay of its units into the spans' snapshots (peaq_spans.hip).  All of it is reserved here as well.
+  // windows (basic version) and spans (advanced version): every launch of the back end(s) is the trace instantiation,
+  // writing frame records -- and the filter-bank back end block records -- into scratch of the context, and is followed
+  // on its own stream by the replay of its units into the spans' snapshots (peaq_replay.hip).  All of it is reserved
+  // here, so that running out of memory is reported before anything is enqueued.
   const size_t n_ssnaps = out.has_spn() ? (size_t)n_pairs * out.spn.n_spans : 0;
   if (out.has_spn()) {
-    if (!advanced || out.has_trc() || out.has_pts() || out.has_win() || out.has_bnd() || out.has_fbnd() || out.has_pbd() ||
-        out.has_sum() || out.has_fsum())
-      return fail(PEAQ_ERR_ARG, std::string(who) + ": spans are a run of their own, of the advanced version");
-    if (spans_scratch_bytes(n_pairs, max_frames, max_blocks, out.spn.n_spans) == 0)
-      return fail(PEAQ_ERR_NOMEM, std::string(who) + ": the spans' scratch exceeds the address space");
-    const size_t frame_stride = std::max<uint32_t>(max_frames, 1), block_stride = std::max<uint32_t>(max_blocks, 1);
-    HIP_TRY(c->win_trace.reserve((size_t)n_pairs * frame_stride * sizeof(FrameTrace)));
-    HIP_TRY(c->spn_blocks.reserve((size_t)n_pairs * block_stride * sizeof(BlockTrace)));
+    if (out.has_trc() || out.has_pts() || out.has_bnd() || out.has_fbnd() || out.has_pbd() || out.has_sum() ||
+        out.has_fsum())
+      return fail(PEAQ_ERR_ARG, std::string(who) + (advanced ? ": spans are a run of their own, of the advanced version"
+                                                             : ": windows are a run of their own, of the basic version"));
+    if (spans_scratch_bytes(advanced, n_pairs, max_frames, max_blocks, out.spn.n_spans) == 0)
+      return fail(PEAQ_ERR_NOMEM, std::string(who) + (advanced ? ": the spans' scratch exceeds the address space"
+                                                               : ": the windows' scratch exceeds the address space"));
+    const size_t frame_stride = std::max<uint32_t>(max_frames, 1);
+    const size_t block_stride = advanced ? std::max<uint32_t>(max_blocks, 1) : 0;
+    HIP_TRY(c->spn_frames.reserve((size_t)n_pairs * frame_stride * sizeof(FrameTrace)));
+    if (advanced) HIP_TRY(c->spn_blocks.reserve((size_t)n_pairs * block_stride * sizeof(BlockTrace)));
     HIP_TRY(c->snaps.reserve(n_ssnaps * sizeof(PointSnap)));
-    HIP_TRY(c->win_list.reserve((size_t)out.spn.n_spans * sizeof(WindowSpan)));
-    HIP_TRY(hipMemcpyAsync(c->win_list.p, out.spn.spans, (size_t)out.spn.n_spans * sizeof(WindowSpan),
+    HIP_TRY(c->spn_list.reserve((size_t)out.spn.n_spans * sizeof(WindowSpan)));
+    HIP_TRY(hipMemcpyAsync(c->spn_list.p, out.spn.spans, (size_t)out.spn.n_spans * sizeof(WindowSpan),
                            hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));           // the caller's array is read by now
-    out.spn.spans = c->win_list.as<WindowSpan>();
+    out.trc = TraceArgs{c->spn_frames.as<FrameTrace>(), frame_stride, advanced ? c->spn_blocks.as<BlockTrace>() : nullptr,
+                        block_stride, d_nref, d_ntest, n_uniform};
+    out.spn.spans = c->spn_list.as<WindowSpan>();
     out.spn.snap = c->snaps.as<PointSnap>();
-    out.spn.frames = c->win_trace.as<FrameTrace>();
+    out.spn.frames = out.trc.frames;
     out.spn.frame_stride = frame_stride;
-    out.spn.blocks = c->spn_blocks.as<BlockTrace>();
+    out.spn.blocks = out.trc.blocks;
     out.spn.block_stride = block_stride;
     out.spn.n_ref = d_nref;
     out.spn.n_test = d_ntest;
     out.spn.n_uniform = n_uniform;
-    out.trc = TraceArgs{c->win_trace.as<FrameTrace>(), frame_stride, c->spn_blocks.as<BlockTrace>(), block_stride,
-                        d_nref, d_ntest, n_uniform};
   }
   // band summary: every FFT back-end launch of the run is the summary instantiation.  The caller's rows start from zero
   // and carry the running sums from launch to launch; the copy a pair takes when it turns tentative goes to scratch of
@@ -787,8 +749,7 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   if (out.has_fsum())                                // (before the fork below: the filter-bank path's stream waits for it)
     HIP_TRY(hipMemsetAsync(out.fsum.rows, 0, (size_t)n_pairs * fsum_pair_doubles * sizeof(double), stream));
   if (out.has_pts()) HIP_TRY(launch_points_init(out.pts.snap, n_snaps, stream));   // (before the fork: both paths write snapshots)
-  if (out.has_win()) HIP_TRY(launch_points_init(out.win.snap, n_wsnaps, stream));   // every window starts fresh
-  if (out.has_spn()) HIP_TRY(launch_points_init(out.spn.snap, n_ssnaps, stream));   // ... every span (before the fork: both replays write snapshots)
+  if (out.has_spn()) HIP_TRY(launch_points_init(out.spn.snap, n_ssnaps, stream));   // every span starts fresh (before the fork: both replays write snapshots)
   hipEvent_t fb_done = nullptr, forked = nullptr;
   c->fb_last_bank_begin = c->fb_last_bank_end = nullptr;
   const bool with_fb = advanced && max_blocks > 0;
@@ -880,12 +841,10 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
     HIP_TRY(hipStreamWaitEvent(c->aux, e1, 0));
     HIP_TRY(hipEventRecord(e2, c->aux));
     if (!PEAQ_DEV_SKIP_BACKEND) HIP_TRY(launch_backend(ba, n_pairs, c->aux, out));
-    // (windows: this chunk's frames into the windows that meet them, from the trace records just written and from
-    // `recs` -- which e3 below keeps from being reused before the replay has read it)
-    if (!PEAQ_DEV_SKIP_BACKEND && out.has_win())
-      HIP_TRY(launch_window_replay(out.win, recs, f0, nf, channels, n_pairs, c->aux));
-    if (!PEAQ_DEV_SKIP_BACKEND && out.has_spn())     // (spans: the same, with the 55-band trace records)
-      HIP_TRY(launch_span_replay_fft(out.spn, recs, f0, nf, channels, n_pairs, c->aux));
+    // (windows and spans: this chunk's frames into the spans that meet them, from the trace records just written and
+    // from `recs` -- which e3 below keeps from being reused before the replay has read it)
+    if (!PEAQ_DEV_SKIP_BACKEND && out.has_spn())
+      HIP_TRY(launch_span_replay_fft(out.spn, advanced != 0, recs, f0, nf, channels, n_pairs, c->aux));
     HIP_TRY(hipEventRecord(e3, c->aux));
     back_done[chunk & 1] = e3;
     head_done = e1;
@@ -919,11 +878,8 @@ static int batch_run_locked(const char* who, peaq_ctx* c, int advanced, int chan
   if (out.has_pts())
     HIP_TRY(launch_finalize_points(out.pts.snap, advanced, channels, n_pairs, out.pts.n_points, out.d_points, stream,
                                    c->settings));
-  if (out.has_win())
-    HIP_TRY(launch_finalize_points(out.win.snap, 0, channels, n_pairs, out.win.n_windows, out.win.out, stream,
-                                   c->settings));
-  if (out.has_spn())                                 // (both replays have joined `stream` above)
-    HIP_TRY(launch_finalize_points(out.spn.snap, 1, channels, n_pairs, out.spn.n_spans, out.spn.out, stream,
+  if (out.has_spn())                                 // (the replays have joined `stream` above)
+    HIP_TRY(launch_finalize_points(out.spn.snap, advanced, channels, n_pairs, out.spn.n_spans, out.spn.out, stream,
                                    c->settings));
   HIP_TRY(hipEventRecord(c->batch_end, stream));
   c->batch_pending = true;

@@ -96,6 +96,19 @@ inline int check_level(const std::string& who, double level_db) {
              ? PEAQ_OK
              : fail(PEAQ_ERR_ARG, who + ": playback level outside 0..130 dB (gstpeaq.c:275-281)");
 }
+// a caller's list of windows ("windows", "window") or spans and the array their readings go to, as the entries that
+// take one check them: the list, its count, the lengths, the output, in this order
+inline int check_span_list(const std::string& who, const char* plural, const char* singular, const peaq_window* list,
+                           int n, const char* out_name, const void* out) {
+  if (!list) return fail(PEAQ_ERR_ARG, who + ": " + plural + " is NULL");
+  if (n < 1 || n > PEAQ_WINDOWS_MAX)
+    return fail(PEAQ_ERR_ARG, who + ": n_" + plural + " " + std::to_string(n) + " is outside 1 .. " +
+                                  std::to_string(PEAQ_WINDOWS_MAX));
+  for (int i = 0; i < n; ++i)
+    if (list[i].length == 0)
+      return fail(PEAQ_ERR_ARG, who + ": " + singular + " " + std::to_string(i) + " has length 0");
+  return out ? PEAQ_OK : fail(PEAQ_ERR_ARG, who + ": " + out_name + " is NULL");
+}
 
 // ---------------------------------------------------------------------------
 // framing arithmetic
@@ -165,8 +178,8 @@ struct peaq_ctx {
   // batch workspace
   DevBuf records, records2, fb_records, fb_records2, state, fbstate, hp_scratch, hp_scratch2, counts, clk;
   DevBuf snaps;             // trajectories: the reading points' snapshots [pair][point] (peaq_batch_run_trajectory)
-  DevBuf win_trace, win_list;   // windows: the trace records the replay reads [pair][frame], the windows on the device (peaq_batch_run_windows; the snapshots are `snaps`)
-  DevBuf spn_blocks;        // spans: the block records the filter-bank replay reads [pair][block] (peaq_batch_run_adv_spans; the frame records, the list and the snapshots are win_trace, win_list and `snaps`)
+  DevBuf spn_frames, spn_list;   // windows and spans: the frame records the FFT replay reads [pair][frame], the caller's list on the device (peaq_batch_run_windows, peaq_batch_run_adv_spans; the snapshots are `snaps`)
+  DevBuf spn_blocks;        // spans: the block records the filter-bank replay reads [pair][block] (peaq_batch_run_adv_spans)
   DevBuf sum_saved;         // band summaries: the rows as they were when a pair last turned tentative (peaq_batch_run_band_summary, peaq_batch_run_fb_band_summary)
   hipStream_t aux = nullptr;   // the back end runs here, overlapped with the next chunk's front end
   hipStream_t aux2 = nullptr;  // advanced: the filter-bank path runs here, beside the FFT path

@@ -260,25 +260,29 @@ struct FbSummaryArgs {
 hipError_t launch_fb_summary_restore(const PairState* state, const FbSummaryArgs& fsum, unsigned n_pairs,
                                      unsigned pair_doubles, hipStream_t stream);
 
-// ---- scores of time windows inside each pair (peaq_batch_run_windows, basic version) ----------------------
-// Window w of a pair covers FFT frames [first, end) of it (window_frames below: the device and peaq_window_frames use
-// the one rule) and is the read-out of accumulators that start fresh before frame `first` and are fed what the pair's
-// own were fed in those frames.  The feed is the trace instantiation's records of the same launch (scratch of the
-// context) and the front end's scalars; a window's accumulators sit in a PointSnap between the launches of a run.  A
-// kernel argument of window_replay_kernel only (peaq_windows.hip).
+// ---- scores of time spans inside each pair (peaq_batch_run_windows, peaq_batch_run_adv_spans) ------------------------
+// Span s of a pair -- a window of the basic version, a span of the advanced version -- covers FFT frames [first, end)
+// (window_frames below: the device and peaq_window_frames use the one rule) and, in the advanced version, filter-bank
+// blocks [first_b, end_b) (span_blocks below: the device and peaq_span_blocks use the one rule).  It is the read-out of
+// the version's accumulators that start fresh before frame `first` / block `first_b` and are fed what the pair's own
+// were fed in those units.  The feed is what the trace instantiations of the same run leave (scratch of the context) and
+// the FFT front end's scalars; a span's accumulators sit in a PointSnap between the launches of a run.  A kernel
+// argument of window_replay_kernel, span_replay_fft_kernel and span_replay_fb_kernel only (peaq_replay.hip).
 struct WindowSpan { uint32_t start, length; };       // mirrors peaq_window in include/peaq_amd.h
-struct WindowArgs {
-  ResultRecord* out;            // [pair][n_windows]: where the read-out of the snapshots goes (the caller's d_windows)
-  PointSnap* snap;              // [pair][n_windows] (scratch)
-  const WindowSpan* windows;    // [n_windows] (device), shared by all pairs
-  int n_windows;
-  const FrameTrace* trace;      // [pair][trace_stride] (scratch): record f of a pair at its absolute frame index
-  size_t trace_stride;
+struct SpanArgs {
+  ResultRecord* out;            // [pair][n_spans]: where the read-out of the snapshots goes (the caller's d_windows / d_spans)
+  PointSnap* snap;              // [pair][n_spans] (scratch)
+  const WindowSpan* spans;      // [n_spans] (device), shared by all pairs
+  int n_spans;
+  const FrameTrace* frames;     // [pair][frame_stride] (scratch): record f of a pair at its absolute frame index
+  size_t frame_stride;
+  const BlockTrace* blocks;     // [pair][block_stride] (scratch): record b of a pair at its absolute block index;
+  size_t block_stride;          // nullptr, 0 in the basic version
   const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform
   const uint32_t* n_test;
   uint32_t n_uniform;
 };
-// frames [first, end) of the window {start, length} of a pair with these lengths; T = count_frames of the pair
+// frames [first, end) of the span {start, length} of a pair with these lengths; T = count_frames of the pair
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
@@ -292,31 +296,6 @@ inline void window_frames(uint32_t n_ref, uint32_t n_test, uint32_t start, uint3
   first = start >= m ? total : a0 >= (uint32_t)kFrame ? (a0 - kFrame) / kHop + 1 : 0u;
   end = e >= m ? total : a1 >= (uint32_t)kFrame ? (a1 - kFrame) / kHop + 1 : 0u;
 }
-// after launch_backend (its trace instantiation) of the same chunk, on the same stream: frames [frame0, frame0 +
-// frames_per_launch) of every pair replayed into the windows that meet them
-hipError_t launch_window_replay(const WindowArgs& win, const double* records, unsigned frame0, unsigned frames_per_launch,
-                                int channels, unsigned n_pairs, hipStream_t stream);
-
-// ---- scores of time spans inside each pair, advanced version (peaq_batch_run_adv_spans) -------------------
-// Span s of a pair covers FFT frames [first, end) (window_frames above) and filter-bank blocks [first_b, end_b)
-// (span_blocks below: the device and peaq_span_blocks use the one rule) and is the read-out of the advanced version's
-// five accumulators that start fresh before frame `first` / block `first_b` and are fed what the pair's own were fed in
-// those units.  The feed is what the two trace instantiations of the same run leave (scratch of the context) and the
-// FFT front end's scalars; a span's accumulators sit in a PointSnap between the launches of a run.  A kernel argument
-// of span_replay_fft_kernel and span_replay_fb_kernel only (peaq_spans.hip).
-struct SpanArgs {
-  ResultRecord* out;            // [pair][n_spans]: where the read-out of the snapshots goes (the caller's d_spans)
-  PointSnap* snap;              // [pair][n_spans] (scratch)
-  const WindowSpan* spans;      // [n_spans] (device), shared by all pairs
-  int n_spans;
-  const FrameTrace* frames;     // [pair][frame_stride] (scratch): record f of a pair at its absolute frame index
-  size_t frame_stride;
-  const BlockTrace* blocks;     // [pair][block_stride] (scratch): record b of a pair at its absolute block index
-  size_t block_stride;
-  const uint32_t* n_ref;        // per-pair lengths (device), or nullptr: n_uniform
-  const uint32_t* n_test;
-  uint32_t n_uniform;
-};
 // blocks [first, end) of the span {start, length} of a pair with these lengths; B (a) = a / 192 is the trajectory's
 // (PointWalk<true>::count), TB = count_frames (.., 192, 192) of the pair
 #if defined(__HIPCC__)
@@ -332,10 +311,11 @@ inline void span_blocks(uint32_t n_ref, uint32_t n_test, uint32_t start, uint32_
   first = start >= m ? total : a0 / (uint32_t)kFbFrame;
   end = e >= m ? total : a1 / (uint32_t)kFbFrame;
 }
-// after launch_backend (its 55-band trace instantiation) of the same chunk, on the same stream: frames [frame0, frame0 +
-// frames_per_launch) of every pair replayed into SegmentalNMR, EHS and the energies of the spans that meet them
-hipError_t launch_span_replay_fft(const SpanArgs& spn, const double* records, unsigned frame0, unsigned frames_per_launch,
-                                  int channels, unsigned n_pairs, hipStream_t stream);
+// after launch_backend (its trace instantiation) of the same chunk, on the same stream: frames [frame0, frame0 +
+// frames_per_launch) of every pair replayed into the spans that meet them -- all eleven accumulators of the basic
+// version; SegmentalNMR, EHS and the energies of the advanced version
+hipError_t launch_span_replay_fft(const SpanArgs& spn, bool advanced, const double* records, unsigned frame0,
+                                  unsigned frames_per_launch, int channels, unsigned n_pairs, hipStream_t stream);
 // after launch_fb_backend (its trace instantiation) of the same chunk, on the same stream: blocks [block0, block0 +
 // blocks_per_launch) of every pair replayed into RmsModDiff, RmsNoiseLoudAsym and AvgLinDist of the spans that meet them
 hipError_t launch_span_replay_fb(const SpanArgs& spn, unsigned block0, unsigned blocks_per_launch, int channels,
@@ -344,7 +324,7 @@ hipError_t launch_span_replay_fb(const SpanArgs& spn, unsigned block0, unsigned 
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
-// knows (the device length arrays of `pts`, `trc` and `win`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
+// knows (the device length arrays of `pts`, `trc` and `spn`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
 // and picks the instantiation; sessions, the broker and the stage entries pass none.
 struct RunOutputs {
   PointArgs pts{};              // trajectory (peaq_batch_run_trajectory): interval, n_points; snap from batch_run_locked
@@ -355,10 +335,9 @@ struct RunOutputs {
   PatternBandArgs pbd{};        // peaq_batch_run_pattern_bands
   SummaryArgs sum{};            // peaq_batch_run_band_summary
   FbSummaryArgs fsum{};         // peaq_batch_run_fb_band_summary
-  WindowArgs win{};             // peaq_batch_run_windows: windows, n_windows, out; the rest from batch_run_locked -- which
-                                // also points `trc` at the context's trace scratch: the replay's feed
-  SpanArgs spn{};               // peaq_batch_run_adv_spans: spans, n_spans, out; the rest from batch_run_locked, which
-                                // points `trc` at the context's frame and block scratch: the two replays' feed
+  SpanArgs spn{};               // peaq_batch_run_windows, peaq_batch_run_adv_spans: spans, n_spans, out; the rest from
+                                // batch_run_locked, which points `trc` at the context's frame (and, in the advanced
+                                // version, block) scratch: the replays' feed
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
@@ -366,11 +345,9 @@ struct RunOutputs {
   bool has_pbd() const { return pbd.bands != nullptr; }
   bool has_sum() const { return sum.rows != nullptr; }
   bool has_fsum() const { return fsum.rows != nullptr; }
-  bool has_win() const { return win.out != nullptr; }
   bool has_spn() const { return spn.out != nullptr; }
   bool any() const {
-    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_win() ||
-           has_spn();
+    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_spn();
   }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first
