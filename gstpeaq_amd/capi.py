@@ -227,6 +227,21 @@ class _Timing(C.Structure):
 _LIB = None
 
 
+class MeterConfig(C.Structure):
+    """peaq_meter_config: the meter's geometry in FFT frames"""
+    _fields_ = [("window_frames", C.c_uint32), ("hop_frames", C.c_uint32), ("depth", C.c_uint32)]
+
+
+class MeterReading(C.Structure):
+    """peaq_meter_reading"""
+    _fields_ = [("index", C.c_uint64), ("start", C.c_uint64), ("length", C.c_uint64), ("first_frame", C.c_uint32),
+                ("n_frames", C.c_uint32), ("first_block", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("r", C.c_double * RESULT_DOUBLES)]
+
+
+METER_MAX_OPEN, METER_MAX_DEPTH = 64, 4096
+
+
 class _BrokerStats(C.Structure):
     _fields_ = [("ticks", C.c_uint64), ("launches", C.c_uint64), ("frames", C.c_uint64),
                 ("max_active", C.c_uint32), ("worker_failed", C.c_uint32),
@@ -357,6 +372,21 @@ def load_library():
         L.peaq_batch_adv_spans_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.peaq_run_pair_adv_spans.argtypes = [vp, C.c_int, C.c_double, C.c_uint32, C.c_uint32, fp, C.c_size_t, fp,
                                               C.c_size_t, vp, C.c_int, vp, C.POINTER(Delay), dp]
+    if hasattr(L, "peaq_session_set_meter"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_meter_reading_size.restype = C.c_size_t
+        L.peaq_meter_reading_size.argtypes = []
+        L.peaq_meter_frames.argtypes = [C.c_double, u32p]
+        L.peaq_meter_readings.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(MeterConfig), C.POINTER(MeterReading), C.c_int,
+                                         C.POINTER(C.c_int)]
+        L.peaq_session_set_meter.argtypes = [vp, C.POINTER(MeterConfig)]
+        L.peaq_session_meter_read.argtypes = [vp, C.POINTER(MeterReading), C.c_int, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_uint64)]
+        L.peaq_broker_set_meter.argtypes = [vp, C.POINTER(MeterConfig)]
+        L.peaq_broker_meter_read.argtypes = [vp, C.c_int, C.POINTER(MeterReading), C.c_int, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_uint64)]
+        if L.peaq_meter_reading_size() != C.sizeof(MeterReading):
+            raise PeaqError(f"peaq_meter_reading is {L.peaq_meter_reading_size()} bytes in the library, "
+                            f"{C.sizeof(MeterReading)} in this binding")
     if hasattr(L, "peaq_batch_run_fb_band_summary"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_fb_band_summary_rows.argtypes = []
         L.peaq_fb_band_summary_row.argtypes = []
@@ -548,6 +578,37 @@ def _result_dict(row, advanced):
                 frames=int(row[14]), fb_blocks=int(row[15]))
 
 
+_METER_FIELDS = ("index", "start", "length", "first_frame", "n_frames", "first_block", "n_blocks")
+
+
+def _meter_dict(row, advanced=None):
+    """a peaq_meter_reading as a dict; advanced = None: the row's own fields only (peaq_meter_readings leaves r alone)"""
+    d = {k: int(getattr(row, k)) for k in _METER_FIELDS}
+    if advanced is not None:
+        d.update(_result_dict(np.array(row.r[:]), advanced))
+    return d
+
+
+def meter_frames(seconds):
+    """peaq_meter_frames: seconds as FFT frames of the running stream, max(1, round(seconds * 48000 / 1024))"""
+    f = C.c_uint32(0)
+    _check(load_library().peaq_meter_frames(float(seconds), C.byref(f)))
+    return f.value
+
+
+def meter_windows(n_ref, n_test, window, hop=None):
+    """peaq_meter_readings: the readings a metered stream of these lengths delivers up to and at its flush, as dicts of
+    index, first_frame, n_frames, first_block, n_blocks and the equivalent batch window / span {start, length}
+    (length 0: none has exactly these frames).  Host arithmetic only."""
+    L = load_library()
+    cfg = MeterConfig(int(window), int(window if hop is None else hop), 1)
+    n = C.c_int(0)
+    _check(L.peaq_meter_readings(int(n_ref), int(n_test), C.byref(cfg), None, 0, C.byref(n)))
+    rows = (MeterReading * max(n.value, 1))()
+    _check(L.peaq_meter_readings(int(n_ref), int(n_test), C.byref(cfg), rows, n.value, C.byref(n)))
+    return [_meter_dict(rows[i]) for i in range(n.value)]
+
+
 class Context:
     """One per process and GPU: owns the constant tables in HBM."""
 
@@ -654,6 +715,32 @@ class Session:
         _check(self.L.peaq_session_results(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return _result_dict(out, self.advanced)
 
+    def reset(self):
+        """peaq_session_reset: the stream starts over; a meter that is set starts over with it"""
+        _check(self.L.peaq_session_reset(self.h))
+
+    def set_meter(self, window, hop=None, depth=64):
+        """peaq_session_set_meter: sliding-window readings of `window` FFT frames every `hop` (default: window), the
+        `depth` newest kept (meter_frames converts seconds).  window = 0 or None switches the meter off.  Before the
+        first push or right after reset() only."""
+        if not window:
+            _check(self.L.peaq_session_set_meter(self.h, None))
+            self._meter_depth = 0
+            return
+        cfg = MeterConfig(int(window), int(window if hop is None else hop), int(depth))
+        _check(self.L.peaq_session_set_meter(self.h, C.byref(cfg)))
+        self._meter_depth = int(depth)
+
+    def meter_read(self, cap=None):
+        """(readings, dropped): the delivered, not yet read readings, oldest first -- each a dict of the result's
+        fields plus index, start, length, first_frame, n_frames, first_block, n_blocks -- and how many were lost since
+        the previous read (peaq_session_meter_read).  cap: at most so many (default: the depth that was set)."""
+        cap = max(1, getattr(self, "_meter_depth", 0)) if cap is None else int(cap)
+        rows = (MeterReading * cap)()
+        n, dropped = C.c_int(0), C.c_uint64(0)
+        _check(self.L.peaq_session_meter_read(self.h, rows, int(cap), C.byref(n), C.byref(dropped)))
+        return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
+
     def close(self):
         if self.h:
             self.L.peaq_session_destroy(self.h)
@@ -718,6 +805,25 @@ class Broker:
         out = np.zeros(RESULT_DOUBLES)
         _check(self.L.peaq_broker_results(self.h, int(sid), out.ctypes.data_as(C.POINTER(C.c_double))))
         return _result_dict(out, self.advanced)
+
+    def set_meter(self, window, hop=None, depth=64):
+        """peaq_broker_set_meter: one geometry for all sessions of the broker (see Session.set_meter), before the first
+        open() and before start()"""
+        self._meter_depth = int(depth) if window else 0
+        if not window:
+            _check(self.L.peaq_broker_set_meter(self.h, None))
+            return
+        cfg = MeterConfig(int(window), int(window if hop is None else hop), int(depth))
+        _check(self.L.peaq_broker_set_meter(self.h, C.byref(cfg)))
+
+    def meter_read(self, sid, cap=None):
+        """(readings, dropped) of session sid, as Session.meter_read: what was delivered up to the last tick; no tick
+        is forced (peaq_broker_meter_read)"""
+        cap = max(1, getattr(self, "_meter_depth", 0)) if cap is None else int(cap)
+        rows = (MeterReading * cap)()
+        n, dropped = C.c_int(0), C.c_uint64(0)
+        _check(self.L.peaq_broker_meter_read(self.h, int(sid), rows, cap, C.byref(n), C.byref(dropped)))
+        return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
 
     def start(self, period_us=2000):
         _check(self.L.peaq_broker_start(self.h, int(period_us)))

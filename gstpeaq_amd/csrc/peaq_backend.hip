@@ -606,7 +606,7 @@ constexpr bool kBackendWarm = true;
 #endif
 template <int NB, bool ADV, bool DBG = false>
 __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false, PBD = false, SUM = false, WARM = kBackendWarm && !DBG;
+  constexpr bool PTS = false, TRC = false, LIVE = false, BND = false, PBD = false, SUM = false, WARM = kBackendWarm && !DBG;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(128, 3) void backend_kernel(BackendArgs a) {
 // backend_kernel, not a call of a common device function: either would change the plain kernels' code or names).
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, PBD = false, SUM = false, WARM = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, LIVE = false, BND = false, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
@@ -628,7 +628,18 @@ __global__ __launch_bounds__(128, 3) void backend_points_kernel(BackendArgs a, P
 // the trace instantiation: a third kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, PBD = false, SUM = false, WARM = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, LIVE = false, BND = false, PBD = false, SUM = false, WARM = false;
+  constexpr SummaryArgs sum{};
+  constexpr PointArgs pts{};
+  constexpr BandArgs bnd{};
+  constexpr PatternBandArgs pbd{};
+#include "peaq_backend_fft.inc"
+}
+// the live instantiation (a metered session's launches): the trace instantiation, but record f of a launch sits at
+// [launch index][f - first frame of the launch] -- the feed of peaq_meter.hip, in a scratch of one launch
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_live_kernel(BackendArgs a, TraceArgs trc) {
+  constexpr bool DBG = false, PTS = false, TRC = true, LIVE = true, BND = false, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr BandArgs bnd{};
@@ -638,7 +649,7 @@ __global__ __launch_bounds__(128, 3) void backend_trace_kernel(BackendArgs a, Tr
 // the bands instantiation: a fourth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, PBD = false, SUM = false, WARM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, LIVE = false, BND = true, PBD = false, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -649,7 +660,7 @@ __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, Ba
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendArgs a, PatternBandArgs pbd) {
   static_assert(!ADV, "the 55-band path has no pattern layer");
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = true, SUM = false, WARM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, LIVE = false, BND = false, PBD = true, SUM = false, WARM = false;
   constexpr SummaryArgs sum{};
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
@@ -659,7 +670,7 @@ __global__ __launch_bounds__(128, 3) void backend_pattern_bands_kernel(BackendAr
 // the summary instantiation: a sixth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, SummaryArgs sum) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, PBD = false, SUM = true, WARM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, LIVE = false, BND = false, PBD = false, SUM = true, WARM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr BandArgs bnd{};
@@ -678,13 +689,16 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 //   out.pts              x    x    x    .    -      .           .             .            .
 //
 //   out.spn              x    x    x  needs   x      x           x             x     as spn.blocks
+//   out.live             x    x    x    x    x      x           .             .            .
 //
 // The rows-per-band outputs (bnd, pbd, sum) belong to a run's own launches: each stands alone.  The trace and the
 // points are not held against each other, the debug dump or a broker's windows: the trace wins over the points, either
 // wins over a.debug.  out.fbnd is the filter-bank path's and is not looked at here.  out.spn (peaq_batch_run_windows,
 // peaq_batch_run_adv_spans) launches nothing here: its replay (peaq_replay.hip) reads what the trace instantiation of a
 // run's own launch leaves -- the basic or the 55-band one, as a.advanced says --, so it needs out.trc and nothing else of
-// the run's own outputs.
+// the run's own outputs.  out.live (a metered session's launches: the feed of peaq_meter.hip, launch-relative) stands
+// alone among the outputs -- out.spn included -- and is the one that goes with a launch's own frame windows and slots; it
+// needs live.frames.
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
@@ -697,6 +711,14 @@ hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t st
   if (out.has_spn() && (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot ||
                         (a.advanced != 0) != (out.spn.blocks != nullptr)))   // (block records: the advanced version's)
     return hipErrorInvalidValue;
+  if (out.has_live()) {
+    if (alone || pts || trc || out.has_spn() || a.debug || !out.live.frames) return hipErrorInvalidValue;
+    if (!a.advanced)
+      hipLaunchKernelGGL((backend_live_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.live);
+    else
+      hipLaunchKernelGGL((backend_live_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.live);
+    return hipGetLastError();
+  }
   if (sum && !a.advanced)
     hipLaunchKernelGGL((backend_summary_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.sum);
   else if (sum)
@@ -753,7 +775,7 @@ struct FbBackendShared {
 // arithmetic and the gates are the plain instantiation's, and a block whose gate is closed evaluates nothing more.
 template <bool DBG>
 __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
-  constexpr bool PTS = false, TRC = false, BND = false, FSUM = false;
+  constexpr bool PTS = false, TRC = false, LIVE = false, BND = false, FSUM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr FbBandArgs bnd{};
@@ -762,7 +784,7 @@ __global__ __launch_bounds__(128, 4) void fb_backend_kernel(FbBackendArgs a) {
 }
 // the points instantiation (see backend_points_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs a, PointArgs pts) {
-  constexpr bool DBG = false, PTS = true, TRC = false, BND = false, FSUM = false;
+  constexpr bool DBG = false, PTS = true, TRC = false, LIVE = false, BND = false, FSUM = false;
   constexpr TraceArgs trc{};
   constexpr FbBandArgs bnd{};
   constexpr FbSummaryArgs fsum{};
@@ -770,7 +792,15 @@ __global__ __launch_bounds__(128, 4) void fb_backend_points_kernel(FbBackendArgs
 }
 // the trace instantiation (see backend_trace_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_trace_kernel(FbBackendArgs a, TraceArgs trc) {
-  constexpr bool DBG = false, PTS = false, TRC = true, BND = false, FSUM = false;
+  constexpr bool DBG = false, PTS = false, TRC = true, LIVE = false, BND = false, FSUM = false;
+  constexpr PointArgs pts{};
+  constexpr FbBandArgs bnd{};
+  constexpr FbSummaryArgs fsum{};
+#include "peaq_backend_fb.inc"
+}
+// the live instantiation (see backend_live_kernel)
+__global__ __launch_bounds__(128, 4) void fb_backend_live_kernel(FbBackendArgs a, TraceArgs trc) {
+  constexpr bool DBG = false, PTS = false, TRC = true, LIVE = true, BND = false, FSUM = false;
   constexpr PointArgs pts{};
   constexpr FbBandArgs bnd{};
   constexpr FbSummaryArgs fsum{};
@@ -778,7 +808,7 @@ __global__ __launch_bounds__(128, 4) void fb_backend_trace_kernel(FbBackendArgs 
 }
 // the bands instantiation (see backend_bands_kernel)
 __global__ __launch_bounds__(128, 4) void fb_backend_bands_kernel(FbBackendArgs a, FbBandArgs bnd) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = true, FSUM = false;
+  constexpr bool DBG = false, PTS = false, TRC = false, LIVE = false, BND = true, FSUM = false;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr FbSummaryArgs fsum{};
@@ -786,7 +816,7 @@ __global__ __launch_bounds__(128, 4) void fb_backend_bands_kernel(FbBackendArgs 
 }
 // the summary instantiation (see backend_summary_kernel); a name of its own that the other kernels' names do not contain
 __global__ __launch_bounds__(128, 4) void fb_band_summary_kernel(FbBackendArgs a, FbSummaryArgs fsum) {
-  constexpr bool DBG = false, PTS = false, TRC = false, BND = false, FSUM = true;
+  constexpr bool DBG = false, PTS = false, TRC = false, LIVE = false, BND = false, FSUM = true;
   constexpr PointArgs pts{};
   constexpr TraceArgs trc{};
   constexpr FbBandArgs bnd{};
@@ -799,6 +829,7 @@ __global__ __launch_bounds__(128, 4) void fb_band_summary_kernel(FbBackendArgs a
 //   out.trc               x     x    -    .      .         .
 //   out.pts               x     x    .    -      .         .
 //   out.spn               x     x  needs  x      x         x          (a run's own launches only)
+//   out.live              x     x    x    x      x         .          (needs live.blocks; refused with out.spn too)
 // out.fsum is also refused together with out.sum: a run has one summary, and the two share the context's saved copy.
 // out.bnd, out.pbd and out.sum are the FFT path's and are otherwise not looked at here.
 hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
@@ -808,6 +839,11 @@ hipError_t launch_fb_backend(const FbBackendArgs& a, unsigned n_pairs, hipStream
     return hipErrorInvalidValue;
   if (out.has_spn() && (!trc || !out.trc.blocks || pts || bnd || fsum || a.debug || a.windows))
     return hipErrorInvalidValue;
+  if (out.has_live()) {
+    if (bnd || fsum || pts || trc || out.has_spn() || a.debug || !out.live.blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fb_backend_live_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.live);
+    return hipGetLastError();
+  }
   if (fsum)
     hipLaunchKernelGGL(fb_band_summary_kernel, dim3(n_pairs), dim3(64 * a.channels), 0, stream, a, out.fsum);
   else if (bnd)

@@ -1,6 +1,7 @@
 // peaq_backend_fb.inc -- body of the filter-bank back end, included by fb_backend_kernel<DBG> (PTS = TRC = BND = FSUM =
 // false), fb_backend_points_kernel (PTS = true), fb_backend_trace_kernel (TRC = true), fb_backend_bands_kernel (BND =
-// true) and fb_band_summary_kernel (FSUM = true) in peaq_backend.hip: one text, five kernels of their own names.
+// true) and fb_band_summary_kernel (FSUM = true) in peaq_backend.hip, and by fb_backend_live_kernel (TRC = LIVE = true;
+// LIVE is false in all the others): one text, six kernels of their own names.
   __shared__ FbBackendShared sh;
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
   __shared__ double sh_etab[kExpTabEntries];
@@ -264,8 +265,10 @@
     // ---- trace: lane 0 of each channel's wave stores that channel's five values, channel 0's also the block's own
     // fields (and a mono pair's zero ch[1]), at the pair's absolute block index.  Doubles 0-3 and 6-9 of the record and
     // the flags go out as 16-byte stores; doubles 4 and 5, the two that straddle the channels, as single ones.
+    // (LIVE, fb_backend_live_kernel: at the block's index within the launch, block_stride the most blocks of a launch)
     if (TRC && lane == 0) {
-      double* __restrict__ od = reinterpret_cast<double*>(trc.blocks + (size_t)pair * trc.block_stride + blk);
+      double* __restrict__ od =
+          reinterpret_cast<double*>(trc.blocks + (size_t)pair * trc.block_stride + (LIVE ? blk - b_begin : blk));
       double2* __restrict__ o = reinterpret_cast<double2*>(od);
       const double2* __restrict__ s = reinterpret_cast<const double2*>(sh_trc[chan]);
       if (chan == 0) {

@@ -1,7 +1,8 @@
 // peaq_backend_fft.inc -- body of the FFT-model back end, included by backend_kernel<NB, ADV, DBG> (PTS = TRC = BND =
 // PBD = SUM = false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true),
 // backend_bands_kernel<NB, ADV> (BND = true), backend_pattern_bands_kernel<NB, false> (PBD = true) and
-// backend_summary_kernel<NB, ADV> (SUM = true) in peaq_backend.hip: one text, six kernels of their own names.
+// backend_summary_kernel<NB, ADV> (SUM = true) in peaq_backend.hip, and by backend_live_kernel<NB, ADV> (TRC = LIVE =
+// true; LIVE is false in all the others): one text, seven kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -552,9 +553,11 @@
     }
     // ---- trace: lane 0 of each channel's wave stores that channel's six values, channel 0's also the frame's own
     // fields (and a mono pair's zero ch[1]) -- eight 16-byte stores per record, at the pair's absolute frame index
+    // (LIVE, backend_live_kernel: at the frame's index within the launch, frame_stride the most frames of a launch)
     if (TRC && lane == 0) {
       const double2* __restrict__ s = reinterpret_cast<const double2*>(sh_trc[chan]);
-      double2* __restrict__ o = reinterpret_cast<double2*>(trc.frames + (size_t)pair * trc.frame_stride + frame);
+      double2* __restrict__ o =
+          reinterpret_cast<double2*>(trc.frames + (size_t)pair * trc.frame_stride + (LIVE ? frame - f_begin : frame));
 #pragma unroll
       for (int k = 0; k < 3; ++k) o[3 * chan + k] = s[k];
       if (chan == 0) {

@@ -24,6 +24,7 @@ constexpr unsigned kBrokerMaxBlocks = 48;    // filter-bank blocks one session c
 constexpr size_t kBrokerStageSamples = (size_t)(kBrokerMaxFrames - 1) * kHop + kFrame;
 constexpr size_t kBrokerFbStageSamples = (size_t)kBrokerMaxBlocks * kFbFrame;
 constexpr size_t kBrokerRowStride = (size_t)kFbRing + kBrokerFbStageSamples;
+constexpr size_t kMetaRows = 10;          // rows of h_meta; the last three are uploaded with the meter on only
 // back-pressure: a push returns only once its session has no more than this many samples that are
 // READY to be framed (present on both pads) and not yet launched -- four ticks' worth.  Samples one
 // pad holds ahead of the other are never counted: like the reference's adapters they may pile up
@@ -36,6 +37,7 @@ struct BrokerSlot {
   bool flush_requested = false, fft_flushed = false, fb_flushed = false;
   StreamFramer framer;              // the two pads' FIFOs and where the next frame / block starts
   double t_ready_us = -1.;          // when the oldest not yet launched frame / block became whole (-1: none waiting)
+  MeterStream meter;                // the slot's meter (peaq_broker_set_meter), fresh at every open
 };
 
 // microseconds on a monotonic clock (latency bookkeeping of the broker)
@@ -180,6 +182,7 @@ struct peaq_broker {
   bool staged_pending = false;
   BrokerStage fft, fbs;
   uint32_t* h_meta = nullptr;       // pinned: 5 rows of max_sessions (n_ref, n_test, frame0, nframes, slot) + 2 rows (fb n_ref, n_test)
+                                    // + 3 rows of the meter (total frames per FFT pair; total frames, total blocks per fb pair)
   FbPairWindow* h_win = nullptr;    // pinned: one per launch pair of the filter-bank launch
   DevBuf d_meta, d_win, records, fb_records, state, fbstate, hp_rows, result;
   std::thread worker;
@@ -205,6 +208,12 @@ struct peaq_broker {
   std::vector<peaq_broker*> shards;
   std::vector<peaq_ctx*> shard_ctx;
   std::vector<int> shard_open;      // open sessions per shard (guarded by tick_mu)
+  // the meter (peaq_broker_set_meter; peaq_meter.hip): one geometry for all slots, because it shapes the launch
+  MeterGeometry meter;
+  DevBuf m_open, m_ring;            // PointSnap [slot][k_open], [slot][ring]
+  DevBuf m_ftrc, m_btrc;            // one tick's trace records [launch index][kBrokerMaxFrames / kBrokerMaxBlocks]
+  DevBuf m_readout;                 // ResultRecord [ring]
+  std::vector<ResultRecord> m_host;
 
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
 };
@@ -256,6 +265,13 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
   uint32_t* m_slot = b->h_meta + 4 * S;
   uint32_t* m_fb_nref = b->h_meta + 5 * S;
   uint32_t* m_fb_ntest = b->h_meta + 6 * S;
+  // the meter's rows (uploaded with the meter on only): the stream's frame count of each FFT pair, its frame and block
+  // counts of each filter-bank pair -- UINT_MAX until the session's flush is known
+  uint32_t* m_tot_f = b->h_meta + 7 * S;
+  uint32_t* m_fb_tot_f = b->h_meta + 8 * S;
+  uint32_t* m_fb_tot_b = b->h_meta + 9 * S;
+  const bool metered = b->meter.on;
+  unsigned fb_closing = 0;                           // sessions whose blocks ended without a flush block (meter: see below)
   unsigned active = 0, max_nf = 0, fb_active = 0, max_nb = 0;
   uint64_t frames = 0;
   b->jobs.clear();
@@ -268,6 +284,7 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     // ---- at most one window per kind: whole units (do_processing), else, once, the zero-padded unit of
     // do_flush.  The samples are copied further down: only the positions are taken here. ----------------
     const bool flush_fft = sl.flush_requested && !sl.fft_flushed;
+    if (metered && sl.flush_requested && !sl.meter.ended) sl.meter.end(sl.framer);   // the stream's end is known from here on
     job.fft = sl.framer.take(kUnitFrame, kBrokerMaxFrames, flush_fft);
     if (flush_fft && (job.fft.flush || !job.fft.count)) sl.fft_flushed = true;   // (no whole frame was left)
     if (job.fft.count) {
@@ -277,15 +294,42 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
       m_f0[active] = job.fft.first;
       m_nf[active] = job.fft.count;
       m_slot[active] = static_cast<uint32_t>(sid);
+      m_tot_f[active] = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;
       frames += job.fft.count;
       max_nf = std::max(max_nf, job.fft.count);
       ++active;
     }
     if (b->advanced) {
-      const bool flush_fb = sl.flush_requested && !sl.fb_flushed;
-      job.fb = sl.framer.take(kUnitBlock, kBrokerMaxBlocks, flush_fb);
-      if (flush_fb && (job.fb.flush || !job.fb.count)) sl.fb_flushed = true;
+      // With the meter on the two paths of a stream stay at a common sample horizon, so that a window's two halves
+      // meet in the delivered ring: the blocks go no further than the frame after the last one taken, 1024 (frames + 2)
+      // samples.  Whatever blocks are whole while no frame is lie below that, so nothing waits that a tick without the
+      // meter would take unless a frame waits too; and 48 blocks a tick outrun 8 frames.  The cap holds through a
+      // flush's backlog as well, until the stream's last frame has been taken (above, in this tick at the latest):
+      // only the tail of the blocks, and the flush block, run free.
+      const bool capped = metered && (!sl.meter.ended || sl.framer.done[kUnitFrame] < sl.meter.total[kUnitFrame]);
+      const bool flush_fb = sl.flush_requested && !sl.fb_flushed && !capped;
+      unsigned fb_cap = kBrokerMaxBlocks;
+      if (capped) {
+        const uint64_t reach = 1024ull * ((uint64_t)sl.framer.done[kUnitFrame] + 2) / kFbFrame;
+        const uint64_t room = reach > sl.framer.done[kUnitBlock] ? reach - sl.framer.done[kUnitBlock] : 0;
+        fb_cap = (unsigned)std::min<uint64_t>(room, kBrokerMaxBlocks);
+      }
+      if (fb_cap) job.fb = sl.framer.take(kUnitBlock, fb_cap, flush_fb);
+      if (flush_fb && (job.fb.flush || !job.fb.count)) {
+        sl.fb_flushed = true;
+        // the blocks ended without a flush block: the windows that run to the last block are delivered by an entry
+        // without units, behind this tick's own in the meter's launch (the back ends never see it).  (A window whose
+        // streaming end fell on the last block was stored then already; this stores the same fields again.)
+        if (metered && !job.fb.count && sl.meter.total[kUnitFrame]) {
+          const unsigned at = (unsigned)S - 1 - fb_closing++;      // (filled from the far end; moved up below)
+          b->h_win[at] = FbPairWindow{sl.meter.total[kUnitBlock], 0, 0, static_cast<uint32_t>(sid)};
+          m_fb_tot_f[at] = sl.meter.total[kUnitFrame];
+          m_fb_tot_b[at] = sl.meter.total[kUnitBlock];
+        }
+      }
       if (job.fb.count) {
+        m_fb_tot_f[fb_active] = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;
+        m_fb_tot_b[fb_active] = sl.meter.ended ? sl.meter.total[kUnitBlock] : UINT_MAX;
         job.fb_idx = fb_active;
         m_fb_nref[fb_active] = static_cast<uint32_t>(job.fb.valid[0]);
         m_fb_ntest[fb_active] = static_cast<uint32_t>(job.fb.valid[1]);
@@ -305,7 +349,13 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     }
   }
   ++b->n_ticks;
-  if (!active && !fb_active) return PEAQ_OK;
+  if (!active && !fb_active && !fb_closing) return PEAQ_OK;
+  for (unsigned i = 0; i < fb_closing; ++i) {        // the entries without units: behind the tick's own
+    const unsigned at = (unsigned)S - 1 - i, to = fb_active + i;
+    b->h_win[to] = b->h_win[at];
+    m_fb_tot_f[to] = m_fb_tot_f[at];
+    m_fb_tot_b[to] = m_fb_tot_b[at];
+  }
   // ---- the sessions' new samples into the pinned staging buffers; then drop what both consumers are done
   // with.  (Only ticks consume, and ticks are serialised: the positions recorded above stay valid; a
   // concurrent push may reallocate a FIFO, hence the slot lock around each copy.) ----------------------
@@ -318,7 +368,29 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     sl.framer.trim();
   });
   HIP_TRY(hipEventRecord(b->t_begin, b->stream));
-  HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, 7 * S * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, (metered ? kMetaRows : 7) * S * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         b->stream));
+  // the meter's launches: the live back ends leave this tick's records at [launch index][unit of the tick], and one
+  // small kernel behind each back end walks every session's units through its open windows
+  RunOutputs live;
+  MeterArgs ma{};
+  if (metered) {
+    live.live.frames = b->m_ftrc.as<FrameTrace>();
+    live.live.frame_stride = kBrokerMaxFrames;
+    live.live.blocks = b->m_btrc.as<BlockTrace>();
+    live.live.block_stride = kBrokerMaxBlocks;
+    live.live.n_uniform = UINT_MAX;
+    ma.open = b->m_open.as<PointSnap>();
+    ma.ring = b->m_ring.as<PointSnap>();
+    ma.window = b->meter.window;
+    ma.hop = b->meter.hop;
+    ma.k_open = b->meter.k_open;
+    ma.ring_depth = b->meter.ring;
+    ma.frames = live.live.frames;
+    ma.frame_stride = kBrokerMaxFrames;
+    ma.blocks = live.live.blocks;
+    ma.block_stride = kBrokerMaxBlocks;
+  }
   const uint32_t* d_meta = b->d_meta.as<uint32_t>();
   const ModelSetup m = b->model();
   if (active) {
@@ -341,14 +413,26 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     ba.frames_per_launch = max_nf;
     ba.state = b->state.as<PairState>();
     ba.pair_slot = d_meta + 4 * S;
-    HIP_TRY(launch_backend(ba, active, b->stream));
+    HIP_TRY(launch_backend(ba, active, b->stream, live));
+    if (metered) {
+      MeterArgs mf = ma;
+      mf.rec_stride = max_nf;
+      mf.s_unit0 = d_meta + 2 * S;
+      mf.s_nunits = d_meta + 3 * S;
+      mf.s_slot = d_meta + 4 * S;
+      mf.s_total_frames = mf.s_total_units = d_meta + 7 * S;
+      HIP_TRY(launch_meter_fft(mf, b->advanced != 0, b->records.as<double>(), b->channels, active, b->stream));
+    }
   }
+  if (!fb_active && fb_closing)
+    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, fb_closing * sizeof(FbPairWindow), hipMemcpyHostToDevice, b->stream));
   if (fb_active) {
     const size_t stride = b->fbs.samples * b->channels;
     for (int p = 0; p < 2; ++p)
       HIP_TRY(hipMemcpyAsync(b->fbs.d[p].p, b->fbs.h[p], fb_active * stride * sizeof(float), hipMemcpyHostToDevice,
                              b->stream));
-    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, fb_active * sizeof(FbPairWindow), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, (fb_active + fb_closing) * sizeof(FbPairWindow), hipMemcpyHostToDevice,
+                           b->stream));
     FbFrontArgs ff = m.fb_frontend();
     ff.ref = b->fbs.d[0].as<float>();
     ff.test = b->fbs.d[1].as<float>();
@@ -365,7 +449,14 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     FbBackendArgs fbk = m.fb_backend(ff);
     fbk.blocks_per_launch = max_nb;
     fbk.state = b->state.as<PairState>();
-    HIP_TRY(launch_fb_backend(fbk, fb_active, b->stream));
+    HIP_TRY(launch_fb_backend(fbk, fb_active, b->stream, live));
+  }
+  if (metered && fb_active + fb_closing) {
+    MeterArgs mb = ma;
+    mb.s_win = b->d_win.as<FbPairWindow>();
+    mb.s_total_frames = d_meta + 8 * S;
+    mb.s_total_units = d_meta + 9 * S;
+    HIP_TRY(launch_meter_fb(mb, b->channels, fb_active + fb_closing, b->stream));
   }
   HIP_TRY(hipEventRecord(b->t_end, b->stream));
   HIP_TRY(hipEventRecord(b->staged, b->stream));
@@ -428,8 +519,8 @@ extern "C" int peaq_broker_create(peaq_ctx* c, int advanced, int channels, doubl
   int rc = [&]() -> int {
     int r = b->fft.alloc(S, kBrokerStageSamples, channels);
     if (r != PEAQ_OK) return r;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_meta), 7 * S * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(b->d_meta.reserve(7 * S * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_meta), kMetaRows * S * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(b->d_meta.reserve(kMetaRows * S * sizeof(uint32_t)));
     HIP_TRY(b->records.reserve(S * kBrokerMaxFrames * channels * kRecDoubles * sizeof(double)));
     HIP_TRY(b->state.reserve(S * sizeof(PairState)));
     HIP_TRY(b->result.reserve(sizeof(ResultRecord)));
@@ -586,6 +677,11 @@ extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
     if (b->advanced)
       HIP_TRY(hipMemsetAsync(b->fbstate.as<FbSignalState>() + (size_t)sid * b->channels * 2, 0,
                              (size_t)b->channels * 2 * sizeof(FbSignalState), b->stream));
+    if (b->meter.on) {                                 // a fresh meter: every snapshot as launch_points_init leaves it
+      HIP_TRY(launch_points_init(b->m_open.as<PointSnap>() + (size_t)sid * b->meter.k_open, b->meter.k_open, b->stream));
+      HIP_TRY(launch_points_init(b->m_ring.as<PointSnap>() + (size_t)sid * b->meter.ring, b->meter.ring, b->stream));
+    }
+    sl.meter = MeterStream();
     sl.open = true;
     sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
     sl.framer.reset(b->advanced, b->channels);
@@ -737,6 +833,74 @@ extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* 
   HIP_TRY(hipMemcpyAsync(out, b->result.p, sizeof(peaq_result), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
   return PEAQ_OK;
+}
+
+// One geometry for all sessions of the broker, because it shapes the launch: before the first open and before start.
+extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cfg) {
+  if (!b) return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: broker is NULL");
+  const bool off = !cfg || cfg->window_frames == 0;
+  if (!off)
+    if (int rc = check_meter_config("peaq_broker_set_meter", *cfg)) return rc;
+  if (broker_is_multi(b)) {                            // every shard
+    for (peaq_broker* sh : b->shards)
+      if (int rc = peaq_broker_set_meter(sh, cfg)) return rc;
+    return PEAQ_OK;
+  }
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (b->running.load())
+    return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: the tick thread runs; set the meter before peaq_broker_start");
+  for (int sid = 0; sid < b->max_sessions; ++sid) {
+    std::lock_guard<std::mutex> lock(b->slots[sid]->mu);
+    if (b->slots[sid]->open)
+      return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: session " + std::to_string(sid) +
+                                    " is open; set the meter before the first peaq_broker_open");
+  }
+  b->meter.on = false;
+  if (off) return PEAQ_OK;
+  MeterGeometry g;
+  g.set(*cfg);
+  const size_t S = (size_t)b->max_sessions;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
+  HIP_TRY(b->m_open.reserve(S * g.k_open * sizeof(PointSnap)));
+  HIP_TRY(b->m_ring.reserve(S * g.ring * sizeof(PointSnap)));
+  HIP_TRY(b->m_readout.reserve((size_t)g.ring * sizeof(ResultRecord)));
+  HIP_TRY(b->m_ftrc.reserve(S * kBrokerMaxFrames * sizeof(FrameTrace)));
+  if (b->advanced) HIP_TRY(b->m_btrc.reserve(S * kBrokerMaxBlocks * sizeof(BlockTrace)));
+  try {
+    b->m_host.resize(g.ring);
+  } catch (const std::bad_alloc&) {
+    return fail(PEAQ_ERR_NOMEM, "out of host memory");
+  }
+  b->meter = g;
+  b->meter.on = true;
+  return PEAQ_OK;
+}
+
+// What was delivered up to the last tick that has been enqueued (the call waits for it); it does not tick.
+extern "C" int peaq_broker_meter_read(peaq_broker* b, int session_id, peaq_meter_reading* out, int cap, int* n_read,
+                                      uint64_t* dropped) {
+  if (!b || !n_read) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: NULL argument");
+  *n_read = 0;
+  if (dropped) *dropped = 0;
+  if (cap < 0 || (cap > 0 && !out))
+    return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
+  if (broker_is_multi(b)) {
+    int local;
+    peaq_broker* sh = broker_shard_of(b, session_id, &local);
+    return sh ? peaq_broker_meter_read(sh, local, out, cap, n_read, dropped)
+              : fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: bad session id");
+  }
+  BrokerSlot* sl = broker_slot(b, session_id);
+  if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: bad session id " + std::to_string(session_id));
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (!b->meter.on) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: the meter is off (peaq_broker_set_meter)");
+  if (b->failed.load()) return broker_failed(b, "peaq_broker_meter_read");
+  std::lock_guard<std::mutex> lock(sl->mu);
+  if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_meter_read: session is not open");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  return sl->meter.read(sl->framer, b->meter, b->m_ring.as<PointSnap>() + (size_t)session_id * b->meter.ring, b->m_readout,
+                        b->m_host, b->channels, b->stream, b->cfg, out, cap, n_read, dropped);
 }
 
 extern "C" int peaq_broker_start(peaq_broker* b, unsigned period_us) {

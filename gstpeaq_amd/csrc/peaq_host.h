@@ -697,3 +697,126 @@ int drain_stream(StreamFramer& fr, unsigned max_frames, unsigned max_blocks, boo
   fr.trim();
   return PEAQ_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The meter's arithmetic (include/peaq_amd.h, "meter"): W, H in FFT frames, window k covers frames [k H, k H + W).
+// Host only; the device walks the same windows in peaq_meter.hip.
+// ---------------------------------------------------------------------------
+inline int check_meter_config(const std::string& who, const peaq_meter_config& c) {
+  if (c.window_frames < 1 || c.hop_frames < 1)
+    return fail(PEAQ_ERR_ARG, who + ": window_frames " + std::to_string(c.window_frames) + " and hop_frames " +
+                                  std::to_string(c.hop_frames) + " must both be at least 1");
+  const uint64_t k_open = ((uint64_t)c.window_frames + c.hop_frames - 1) / c.hop_frames;
+  if (k_open > peaq::kMeterMaxOpen)
+    return fail(PEAQ_ERR_ARG, who + ": window_frames " + std::to_string(c.window_frames) + " over hop_frames " +
+                                  std::to_string(c.hop_frames) + " keeps " + std::to_string(k_open) +
+                                  " windows open at once, more than " + std::to_string(peaq::kMeterMaxOpen));
+  if (c.depth < 1 || c.depth > peaq::kMeterMaxDepth)
+    return fail(PEAQ_ERR_ARG, who + ": depth " + std::to_string(c.depth) + " is outside 1 .. " +
+                                  std::to_string(peaq::kMeterMaxDepth));
+  return PEAQ_OK;
+}
+// windows that are complete once `units` frames have run: b_k = k H + W <= units
+inline uint64_t meter_complete(uint64_t units, uint32_t W, uint32_t H) { return units >= W ? (units - W) / H + 1 : 0; }
+// readings of a finished stream of T frames: the complete windows and, if the end cuts one short, the oldest such
+inline uint64_t meter_rows(uint64_t T, uint32_t W, uint32_t H) {
+  const uint64_t c = meter_complete(T, W, H);
+  return c + (c * H < T ? 1 : 0);
+}
+// Row k without its result.  `ended`: the stream's lengths are known (its flush has been asked for); before that only
+// complete windows are asked for, and none of them reaches the end.
+inline void meter_row(uint64_t k, uint32_t W, uint32_t H, bool ended, uint64_t n_ref, uint64_t n_test,
+                      peaq_meter_reading* row) {
+  const uint64_t a = k * H, b = a + W;
+  const uint64_t start = a ? 1024 * (a + 1) : 0, e = 1024 * (b + 1);
+  row->index = k;
+  row->start = start;
+  row->first_frame = static_cast<uint32_t>(a);
+  row->first_block = static_cast<uint32_t>(start / peaq::kFbFrame);
+  row->n_frames = W;
+  row->n_blocks = static_cast<uint32_t>(e / peaq::kFbFrame) - row->first_block;
+  row->length = e - start;
+  if (!ended) return;
+  const uint64_t m = std::max(n_ref, n_test);
+  const uint64_t T = count_frames(n_ref, n_test, peaq::kFrame, peaq::kHop);
+  const uint64_t TB = count_frames(n_ref, n_test, peaq::kFbFrame, peaq::kFbFrame);
+  if (b >= T) {                                      // takes the stream's last frame: blocks to the last
+    row->n_frames = static_cast<uint32_t>(T - a);
+    row->n_blocks = static_cast<uint32_t>(TB) - row->first_block;
+    row->length = start >= m ? 0 : m - start;        // (only the flush frame: no sample window has exactly that)
+  } else if (e == m) {
+    row->length = 0;                                 // (the batch rule would add the flush frame)
+  }
+}
+
+// One geometry, and what the host keeps per metered stream (a session, a broker slot): guarded by the owner's lock.
+struct MeterGeometry {
+  bool on = false;
+  uint32_t window = 0, hop = 0, depth = 0, k_open = 0;
+  uint32_t ring = 0;                // depth + 2 slots: at a read the filter-bank path may have finished one window more
+                                    // than the FFT path, and during a flush the FFT path two more than the other
+  void set(const peaq_meter_config& c) {
+    window = c.window_frames;
+    hop = c.hop_frames;
+    depth = c.depth;
+    k_open = (c.window_frames + c.hop_frames - 1) / c.hop_frames;
+    ring = c.depth + 2;
+  }
+};
+struct MeterStream {
+  uint64_t n_taken = 0;             // readings handed out or counted as dropped so far
+  bool ended = false;               // the flush has been asked for: the lengths, T and TB below are the stream's
+  uint64_t n_ref = 0, n_test = 0;
+  uint32_t total[2] = {0, 0};       // [kind]: T, TB
+  void end(const StreamFramer& fr) {
+    ended = true;
+    n_ref = fr.pad[0].total;
+    n_test = fr.pad[1].total;
+    total[kUnitFrame] = count_frames(n_ref, n_test, peaq::kFrame, peaq::kHop);
+    total[kUnitBlock] = count_frames(n_ref, n_test, peaq::kFbFrame, peaq::kFbFrame);
+  }
+  // what both paths have finished of the units handed out so far, by arithmetic alone
+  uint64_t delivered(const StreamFramer& fr, const MeterGeometry& g) const {
+    if (ended && fr.done[kUnitFrame] == total[kUnitFrame] && (!fr.advanced || fr.done[kUnitBlock] == total[kUnitBlock]))
+      return meter_rows(total[kUnitFrame], g.window, g.hop);
+    uint64_t d = meter_complete(fr.done[kUnitFrame], g.window, g.hop);
+    if (fr.advanced) {
+      // block e_k / 192 - 1 has run: e_k = 1024 (b_k + 1) < 192 (blocks + 1)
+      const uint64_t f = (192ull * fr.done[kUnitBlock] + 191u) / 1024u;
+      d = std::min(d, meter_complete(f >= 1 ? f - 1 : 0, g.window, g.hop));
+    }
+    // (a flush under way: the windows that take the last frame count only once both paths are at the end)
+    return ended ? std::min(d, meter_complete(total[kUnitFrame] ? total[kUnitFrame] - 1 : 0, g.window, g.hop)) : d;
+  }
+  // The delivered, not yet read readings of the stream whose ring is `snaps`, oldest first, at most cap: the read-out
+  // of their slots alone (at most two runs of the ring), then the rows' own fields.  Waits for `stream`.
+  int read(const StreamFramer& fr, const MeterGeometry& g, const peaq::PointSnap* snaps, DevBuf& readout,
+           std::vector<peaq::ResultRecord>& host, int channels, hipStream_t stream, const peaq::Settings& cfg,
+           peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped) {
+    const uint64_t have = delivered(fr, g);
+    uint64_t from = n_taken;
+    if (have > g.depth && from < have - g.depth) from = have - g.depth;
+    if (dropped) *dropped = from - n_taken;
+    n_taken = from;
+    const uint64_t n = std::min<uint64_t>(have - from, (uint64_t)cap);
+    if (n == 0) return PEAQ_OK;
+    for (uint64_t done = 0; done < n;) {
+      const uint32_t s0 = static_cast<uint32_t>((from + done) % g.ring);
+      const uint32_t run = static_cast<uint32_t>(std::min<uint64_t>(n - done, g.ring - s0));
+      HIP_TRY(peaq::launch_finalize_points(snaps + s0, fr.advanced, channels, 1, (int)run,
+                                           readout.as<peaq::ResultRecord>() + s0, stream, cfg));
+      HIP_TRY(hipMemcpyAsync(host.data() + s0, readout.as<peaq::ResultRecord>() + s0, run * sizeof(peaq::ResultRecord),
+                             hipMemcpyDeviceToHost, stream));
+      done += run;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    static_assert(sizeof(peaq::ResultRecord) == sizeof(peaq_result), "ResultRecord mirrors peaq_result");
+    for (uint64_t i = 0; i < n; ++i) {
+      meter_row(from + i, g.window, g.hop, ended, n_ref, n_test, out + i);
+      std::memcpy(&out[i].r, &host[(from + i) % g.ring], sizeof(peaq_result));
+    }
+    n_taken = from + n;
+    *n_read = static_cast<int>(n);
+    return PEAQ_OK;
+  }
+};

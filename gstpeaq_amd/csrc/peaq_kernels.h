@@ -83,6 +83,8 @@ struct BlockTrace {             // 96 bytes; ch[1] starts on an odd double
 };
 struct TraceArgs {
   FrameTrace* frames;           // [pair][frame_stride], 16-byte aligned; record f of a pair at its ABSOLUTE frame index
+                                // (as RunOutputs::live, the live instantiations: at its index within the LAUNCH, and
+                                // the strides are the most units of a launch; the same holds for blocks)
   size_t frame_stride;
   BlockTrace* blocks;           // [pair][block_stride] (filter-bank back end)
   size_t block_stride;
@@ -321,11 +323,53 @@ hipError_t launch_span_replay_fft(const SpanArgs& spn, bool advanced, const doub
 hipError_t launch_span_replay_fb(const SpanArgs& spn, unsigned block0, unsigned blocks_per_launch, int channels,
                                  unsigned n_pairs, hipStream_t stream);
 
+// ---- sliding-window scores of a live stream (peaq_session_set_meter, peaq_session_meter_read) ------------------------
+// Window k of a stream covers FFT frames [k hop, k hop + window) and, in the advanced version, the filter-bank blocks
+// [start_k / 192, e_k / 192) with start_k = k ? 1024 (k hop + 1) : 0 and e_k = 1024 (k hop + window + 1); a window that
+// takes the stream's last frame takes the blocks to the last.  K = ceil (window / hop) windows are open at once, window
+// k in slot k % K; a finished window's fields go to the delivered ring at k % ring_depth.  Each path (FFT frames,
+// filter-bank blocks) writes the words of the snapshots that it owns, as the replays of peaq_replay.hip do.  The feed is
+// what the live instantiations of the back ends leave: record u of a launch at [stream][u - first_unit].  A kernel
+// argument of the three kernels of peaq_meter.hip only.
+struct MeterArgs {
+  PointSnap* open;              // [stream][k_open]: the open windows' fields between launches
+  PointSnap* ring;              // [stream][ring_depth]: the delivered windows' fields
+  uint32_t window, hop;         // W, H in frames
+  uint32_t k_open, ring_depth;  // K = ceil (W / H) <= kMeterMaxOpen; the ring's slots
+  const FrameTrace* frames;     // [stream][frame_stride], launch-relative (FFT kernels)
+  size_t frame_stride;
+  const BlockTrace* blocks;     // [stream][block_stride], launch-relative (filter-bank kernel)
+  size_t block_stride;
+  uint32_t unit0, n_units;      // the launch's units of the kernel's own path: [unit0, unit0 + n_units); n_units may be 0
+  uint32_t total_frames;        // T, the stream's frames, once its flush is known; UINT_MAX before
+  uint32_t total_units;         // the stream's units of the kernel's own path, once its flush is known; UINT_MAX before
+  uint32_t rec_stride;          // FFT kernels: frames between the front end's records of consecutive streams of the launch
+  // Broker launches (nullptr otherwise: the uniform fields above apply and stream p's snapshots are at index p): stream
+  // p of the launch is a session at its own position, its snapshots at its slot.  The FFT kernels take the rows the
+  // broker uploads for its back end, the filter-bank kernel its windows; n_units is clamped to the trace stride.
+  const uint32_t* s_unit0;      // [stream] (pair_frame0)
+  const uint32_t* s_nunits;     // [stream] (pair_nframes); may be 0
+  const uint32_t* s_slot;       // [stream] (pair_slot)
+  const FbPairWindow* s_win;    // [stream]: block0, n_blocks (may be 0), slot
+  const uint32_t* s_total_frames;   // [stream]: total_frames of each stream
+  const uint32_t* s_total_units;    // [stream]: total_units of each stream
+};
+constexpr uint32_t kMeterMaxOpen = 64, kMeterMaxDepth = 4096;
+// after launch_backend (its live instantiation) of the same units, on the same stream: frames [unit0, unit0 + n_units)
+// of every stream replayed into the windows that are open in them -- all eleven accumulators of the basic version;
+// SegmentalNMR, EHS and the energies of the advanced version.  records: the FFT front end's of the launch.
+hipError_t launch_meter_fft(const MeterArgs& m, bool advanced, const double* records, int channels, unsigned n_streams,
+                            hipStream_t stream);
+// after launch_fb_backend (its live instantiation): blocks [unit0, unit0 + n_units) into RmsModDiff, RmsNoiseLoudAsym
+// and AvgLinDist of the windows that are open in them
+hipError_t launch_meter_fb(const MeterArgs& m, int channels, unsigned n_streams, hipStream_t stream);
+
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it
 // knows (the device length arrays of `pts`, `trc` and `spn`, the snapshots, `sum.saved`).  A launch takes the whole aggregate
-// and picks the instantiation; sessions, the broker and the stage entries pass none.
+// and picks the instantiation; a metered session passes `live` alone, other sessions, the broker and the stage entries
+// pass none.
 struct RunOutputs {
   PointArgs pts{};              // trajectory (peaq_batch_run_trajectory): interval, n_points; snap from batch_run_locked
   ResultRecord* d_points = nullptr;   // [n_pairs][n_points]: where the read-out of the snapshots goes
@@ -338,6 +382,9 @@ struct RunOutputs {
   SpanArgs spn{};               // peaq_batch_run_windows, peaq_batch_run_adv_spans: spans, n_spans, out; the rest from
                                 // batch_run_locked, which points `trc` at the context's frame (and, in the advanced
                                 // version, block) scratch: the replays' feed
+  TraceArgs live{};             // a metered session's launches: the trace records, but record u of the launch at [launch
+                                // index][u - first unit of the launch] -- the feed of peaq_meter.hip.  Stands alone.
+  bool has_live() const { return live.frames != nullptr || live.blocks != nullptr; }
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
@@ -347,7 +394,8 @@ struct RunOutputs {
   bool has_fsum() const { return fsum.rows != nullptr; }
   bool has_spn() const { return spn.out != nullptr; }
   bool any() const {
-    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_spn();
+    return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_spn() ||
+           has_live();
   }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first

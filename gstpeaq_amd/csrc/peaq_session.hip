@@ -18,8 +18,73 @@ struct peaq_session {
   DevBuf d_sig[2], records, state, result;
   size_t stage_samples = 0;
 
+  // the meter (peaq_session_set_meter; peaq_meter.hip), guarded by mu like the rest
+  struct Meter : MeterGeometry, MeterStream {
+    DevBuf open, delivered;         // PointSnap [k_open], [ring]
+    DevBuf frame_trc, block_trc;    // one launch's trace records, launch-relative (the live back ends' output)
+    DevBuf readout;                 // ResultRecord [ring]
+    std::vector<ResultRecord> h_readout;
+    bool closed[2] = {false, false};   // [kind]: a launch that ends this path's units has gone out
+  } meter;
+
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
+  MeterArgs meter_args(StreamUnit kind, uint32_t first, uint32_t count) const {
+    MeterArgs m{};
+    m.open = meter.open.as<PointSnap>();
+    m.ring = meter.delivered.as<PointSnap>();
+    m.window = meter.window;
+    m.hop = meter.hop;
+    m.k_open = meter.k_open;
+    m.ring_depth = meter.ring;
+    m.frames = meter.frame_trc.as<FrameTrace>();
+    m.frame_stride = kSessionMaxFrames;
+    m.blocks = meter.block_trc.as<BlockTrace>();
+    m.block_stride = kSessionMaxBlocks;
+    m.unit0 = first;
+    m.n_units = count;
+    m.rec_stride = count;
+    m.total_frames = meter.ended ? meter.total[kUnitFrame] : UINT_MAX;
+    m.total_units = meter.ended ? meter.total[kind] : UINT_MAX;
+    return m;
+  }
+  // the live back ends' output: the launch's records at their index within the launch (no flush flag: n_uniform)
+  RunOutputs meter_outputs() const {
+    RunOutputs out;
+    if (meter.on) {
+      out.live.frames = meter.frame_trc.as<FrameTrace>();
+      out.live.frame_stride = kSessionMaxFrames;
+      out.live.blocks = meter.block_trc.as<BlockTrace>();
+      out.live.block_stride = kSessionMaxBlocks;
+      out.live.n_uniform = UINT_MAX;
+    }
+    return out;
+  }
 };
+
+// behind a back-end launch of a metered session: the launch's units into the open windows; a launch that ends the
+// path's units (count may be 0) delivers the windows that run to the stream's end
+static int session_meter_step(peaq_session* s, StreamUnit kind, uint32_t first, uint32_t count) {
+  const MeterArgs m = s->meter_args(kind, first, count);
+  if (kind == kUnitFrame)
+    HIP_TRY(launch_meter_fft(m, s->advanced != 0, s->records.as<double>(), s->channels, 1, s->stream));
+  else
+    HIP_TRY(launch_meter_fb(m, s->channels, 1, s->stream));
+  if (s->meter.ended && first + count == s->meter.total[kind]) s->meter.closed[kind] = true;
+  return PEAQ_OK;
+}
+
+// a fresh meter of the geometry that is set: every snapshot as launch_points_init leaves it, the index at 0
+static int session_meter_restart(peaq_session* s) {
+  peaq_session::Meter& mt = s->meter;
+  HIP_TRY(launch_points_init(mt.open.as<PointSnap>(), mt.k_open, s->stream));
+  HIP_TRY(launch_points_init(mt.delivered.as<PointSnap>(), mt.ring, s->stream));
+  mt.n_taken = 0;
+  mt.ended = false;
+  mt.n_ref = mt.n_test = 0;
+  mt.total[0] = mt.total[1] = 0;
+  mt.closed[0] = mt.closed[1] = false;
+  return PEAQ_OK;
+}
 
 static int session_alloc(peaq_session* s) {
   s->stage_samples = (size_t)(kSessionMaxFrames - 1) * kHop + kFrame;   // >= kSessionMaxBlocks * 192
@@ -118,8 +183,8 @@ static int session_run_frames(peaq_session* s, const StreamWindow& w) {
   ba.frames_per_launch = w.count;
   ba.n_frames_uniform = w.first + w.count;
   ba.state = s->state.as<PairState>();
-  HIP_TRY(launch_backend(ba, 1, s->stream));
-  return PEAQ_OK;
+  HIP_TRY(launch_backend(ba, 1, s->stream, s->meter_outputs()));
+  return s->meter.on ? session_meter_step(s, kUnitFrame, w.first, w.count) : PEAQ_OK;
 }
 
 // run the filter-bank blocks of window w (advanced mode)
@@ -151,8 +216,8 @@ static int session_run_blocks(peaq_session* s, const StreamWindow& w) {
   fbk.blocks_per_launch = w.count;
   fbk.n_blocks_uniform = w.first + w.count;
   fbk.state = s->state.as<PairState>();
-  HIP_TRY(launch_fb_backend(fbk, 1, s->stream));
-  return PEAQ_OK;
+  HIP_TRY(launch_fb_backend(fbk, 1, s->stream, s->meter_outputs()));
+  return s->meter.on ? session_meter_step(s, kUnitBlock, w.first, w.count) : PEAQ_OK;
 }
 
 // do_processing (gstpeaq.c:596-611), and with `flushing` do_flush (gstpeaq.c:716-745, 769-771)
@@ -182,7 +247,27 @@ extern "C" int peaq_session_flush(peaq_session* s) {
   if (!s) return fail(PEAQ_ERR_ARG, "peaq_session_flush: session is NULL");
   std::lock_guard<std::mutex> lock(s->mu);
   HIP_TRY(hipSetDevice(s->ctx->device));
-  return session_drain(s, true);
+  peaq_session::Meter& mt = s->meter;
+  const bool ends_now = mt.on && !mt.ended;
+  if (ends_now) mt.end(s->framer);                   // the stream's end is known from here on: the launches below carry it
+  if (int rc = session_drain(s, true)) {
+    // (a device error: the stream is lost as after any failed call; the meter at least does not report an end)
+    if (ends_now) {
+      mt.ended = false;
+      mt.closed[0] = mt.closed[1] = false;
+    }
+    return rc;
+  }
+  if (mt.on && mt.total[kUnitFrame]) {
+    // a path whose units were all whole ones has no flush unit: its windows that run to the end are delivered by a
+    // launch without units
+    for (StreamUnit kind : {kUnitFrame, kUnitBlock}) {
+      if (kind == kUnitBlock && !s->advanced) break;
+      if (!mt.closed[kind] && s->framer.done[kind] == mt.total[kind])
+        if (int rc = session_meter_step(s, kind, mt.total[kind], 0)) return rc;
+    }
+  }
+  return PEAQ_OK;
 }
 
 extern "C" int peaq_session_results(peaq_session* s, peaq_result* out) {
@@ -213,5 +298,83 @@ extern "C" int peaq_session_reset(peaq_session* s) {
   if (s->advanced)
     HIP_TRY(hipMemsetAsync(s->fbstate.p, 0, 2 * s->channels * sizeof(FbSignalState), s->stream));
   HIP_TRY(launch_state_init(s->state.as<PairState>(), s->advanced, 1, s->stream));
+  return s->meter.on ? session_meter_restart(s) : PEAQ_OK;
+}
+
+extern "C" size_t peaq_meter_reading_size(void) { return sizeof(peaq_meter_reading); }
+
+extern "C" int peaq_meter_frames(double seconds, uint32_t* frames) {
+  if (!frames) return fail(PEAQ_ERR_ARG, "peaq_meter_frames: frames is NULL");
+  if (!(seconds >= 0.) || !(seconds <= 1e6))
+    return fail(PEAQ_ERR_ARG, "peaq_meter_frames: seconds " + std::to_string(seconds) + " is outside 0 .. 1e6");
+  const long long f = std::llround(seconds * 48000. / 1024.);
+  *frames = static_cast<uint32_t>(f < 1 ? 1 : f);
   return PEAQ_OK;
+}
+
+extern "C" int peaq_meter_readings(uint64_t n_ref, uint64_t n_test, const peaq_meter_config* cfg, peaq_meter_reading* rows,
+                                  int cap, int* n) {
+  if (!cfg || !n) return fail(PEAQ_ERR_ARG, "peaq_meter_readings: NULL argument");
+  if (cfg->window_frames < 1 || cfg->hop_frames < 1)
+    return fail(PEAQ_ERR_ARG, "peaq_meter_readings: window_frames " + std::to_string(cfg->window_frames) +
+                                  " and hop_frames " + std::to_string(cfg->hop_frames) + " must both be at least 1");
+  if (cap < 0 || (cap > 0 && !rows))
+    return fail(PEAQ_ERR_ARG, "peaq_meter_readings: cap " + std::to_string(cap) + " with rows " + (rows ? "set" : "NULL"));
+  const uint64_t total = meter_rows(count_frames(n_ref, n_test, kFrame, kHop), cfg->window_frames, cfg->hop_frames);
+  if (total > (uint64_t)INT_MAX) return fail(PEAQ_ERR_ARG, "peaq_meter_readings: more than INT_MAX rows");
+  for (uint64_t k = 0; k < total && k < (uint64_t)cap; ++k)
+    meter_row(k, cfg->window_frames, cfg->hop_frames, true, n_ref, n_test, rows + k);
+  *n = static_cast<int>(total);
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_session_set_meter(peaq_session* s, const peaq_meter_config* cfg) {
+  if (!s) return fail(PEAQ_ERR_ARG, "peaq_session_set_meter: session is NULL");
+  const bool off = !cfg || cfg->window_frames == 0;
+  if (!off)
+    if (int rc = check_meter_config("peaq_session_set_meter", *cfg)) return rc;
+  std::lock_guard<std::mutex> lock(s->mu);
+  const uint64_t pushed = s->framer.pad[0].total + s->framer.pad[1].total;
+  if (pushed)
+    return fail(PEAQ_ERR_ARG, "peaq_session_set_meter: the stream has begun (" + std::to_string(pushed) +
+                                  " samples pushed); set the meter before the first push or right after peaq_session_reset");
+  peaq_session::Meter& mt = s->meter;
+  if (off) {
+    mt.on = false;
+    return PEAQ_OK;
+  }
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  mt.on = false;                                     // (stays off if the workspace cannot be reserved)
+  MeterGeometry g;
+  g.set(*cfg);
+  const uint32_t k_open = g.k_open, ring = g.ring;
+  HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
+  HIP_TRY(mt.open.reserve((size_t)k_open * sizeof(PointSnap)));
+  HIP_TRY(mt.delivered.reserve((size_t)ring * sizeof(PointSnap)));
+  HIP_TRY(mt.readout.reserve((size_t)ring * sizeof(ResultRecord)));
+  HIP_TRY(mt.frame_trc.reserve((size_t)kSessionMaxFrames * sizeof(FrameTrace)));
+  if (s->advanced) HIP_TRY(mt.block_trc.reserve((size_t)kSessionMaxBlocks * sizeof(BlockTrace)));
+  try {
+    mt.h_readout.resize(ring);
+  } catch (const std::bad_alloc&) {
+    return fail(PEAQ_ERR_NOMEM, "out of host memory");
+  }
+  mt.set(*cfg);
+  if (int rc = session_meter_restart(s)) return rc;
+  mt.on = true;
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_session_meter_read(peaq_session* s, peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped) {
+  if (!s || !n_read) return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: NULL argument");
+  *n_read = 0;
+  if (dropped) *dropped = 0;
+  if (cap < 0 || (cap > 0 && !out))
+    return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
+  std::lock_guard<std::mutex> lock(s->mu);
+  peaq_session::Meter& mt = s->meter;
+  if (!mt.on) return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: the meter is off (peaq_session_set_meter)");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  return mt.read(s->framer, mt, mt.delivered.as<PointSnap>(), mt.readout, mt.h_readout, s->channels, s->stream, s->cfg,
+                 out, cap, n_read, dropped);
 }

@@ -48,6 +48,12 @@ typedef struct _GstPeaqAmd
   gboolean failed;              /* a device error was reported already */
   gboolean pushed;              /* the current session / broker slot has received samples */
   gchar *pending_error;         /* set under the object lock, posted after it is released */
+  /* the meter (include/peaq_amd.h, "meter"): sliding-window readings of the running stream */
+  gdouble meter_window, meter_hop;      /* seconds; window 0 = off, hop 0 = the window */
+  guint meter_depth;
+  gboolean metered;             /* the current session / broker slot has its meter on */
+  gboolean meter_flushed;       /* the stream was flushed at EOS already (metered streams only) */
+  gdouble st_odg, st_di, st_totalsnr;   /* the newest delivered reading, NaN before the first */
 } GstPeaqAmd;
 
 typedef struct _GstPeaqAmdClass
@@ -56,7 +62,9 @@ typedef struct _GstPeaqAmdClass
 } GstPeaqAmdClass;
 
 enum
-{ PROP_0, PROP_PLAYBACK_LEVEL, PROP_ADVANCED, PROP_DI, PROP_ODG, PROP_TOTALSNR, PROP_CONSOLE_OUTPUT };
+{ PROP_0, PROP_PLAYBACK_LEVEL, PROP_ADVANCED, PROP_DI, PROP_ODG, PROP_TOTALSNR, PROP_CONSOLE_OUTPUT,
+  PROP_METER_WINDOW, PROP_METER_HOP, PROP_METER_DEPTH, PROP_ST_ODG, PROP_ST_DI, PROP_ST_TOTALSNR
+};
 
 static GstStaticPadTemplate ref_template =
 GST_STATIC_PAD_TEMPLATE ("ref", GST_PAD_SINK, GST_PAD_ALWAYS, GST_STATIC_CAPS (PEAQ_CAPS));
@@ -100,6 +108,34 @@ shared_context (void)
  * broker per (version, channel count) at the default playback level; an element with another
  * level keeps its own session.  PEAQ_AMD_DEVICES=0,1,...: the broker spans those GPUs
  * (peaq_broker_create_multi: one device broker each, elements dealt out to the least loaded). */
+/* PEAQ_AMD_BROKER_METER=WINDOW[:HOP] in seconds: the meter of every broker of the process (one geometry per broker,
+ * because it shapes the launch).  TRUE and the values if it is set and valid. */
+static gboolean
+broker_meter_seconds (gdouble * window, gdouble * hop)
+{
+  const gchar *m = g_getenv ("PEAQ_AMD_BROKER_METER");
+  gchar *end = NULL;
+  if (!m || !*m)
+    return FALSE;
+  *window = g_ascii_strtod (m, &end);
+  *hop = *window;
+  if (end != m && *end == ':') {
+    const gchar *h = end + 1;
+    *hop = g_ascii_strtod (h, &end);
+    if (end == h)
+      return FALSE;
+  }
+  return end != m && !*end && *window > 0. && *hop > 0.;
+}
+
+static gboolean
+meter_config_of (gdouble window, gdouble hop, guint depth, peaq_meter_config * cfg)
+{
+  cfg->depth = depth;
+  return peaq_meter_frames (window, &cfg->window_frames) == PEAQ_OK
+      && peaq_meter_frames (hop > 0. ? hop : window, &cfg->hop_frames) == PEAQ_OK;
+}
+
 static peaq_broker *
 shared_broker (gboolean advanced, gint channels)
 {
@@ -146,6 +182,13 @@ shared_broker (gboolean advanced, gint channels)
       rc = ctx ? peaq_broker_create (ctx, adv, channels, 92., atoi (max), &brokers[adv][channels]) : PEAQ_ERR_DEVICE;
     }
     if (rc == PEAQ_OK) {
+      gdouble mw, mh;
+      peaq_meter_config cfg;
+      if (g_getenv ("PEAQ_AMD_BROKER_METER")) {
+        if (!broker_meter_seconds (&mw, &mh) || !meter_config_of (mw, mh, 64, &cfg)
+            || peaq_broker_set_meter (brokers[adv][channels], &cfg) != PEAQ_OK)
+          GST_WARNING ("PEAQ_AMD_BROKER_METER: no meter (%s)", peaq_last_error ());
+      }
       if (peaq_broker_start (brokers[adv][channels], period ? (unsigned) atoi (period) : 0) != PEAQ_OK)
         GST_WARNING ("libpeaq_amd: %s", peaq_last_error ());
     } else {
@@ -180,12 +223,16 @@ renew_session (GstPeaqAmd * self)
   peaq_ctx *ctx;
   drop_session (self);
   self->pushed = FALSE;
+  self->metered = self->meter_flushed = FALSE;
+  self->st_odg = self->st_di = self->st_totalsnr = NAN;
   if (self->channels <= 0)
     return TRUE;
   if (self->playback_level == 92.) {
     peaq_broker *b = shared_broker (self->advanced, self->channels);
     if (b && peaq_broker_open (b, &self->broker_sid) == PEAQ_OK) {
+      gdouble mw, mh;
       self->broker = b;
+      self->metered = broker_meter_seconds (&mw, &mh);    /* the geometry is the process's, not the element's */
       return TRUE;
     }
   }
@@ -197,7 +244,68 @@ renew_session (GstPeaqAmd * self)
     self->session = NULL;
     return FALSE;
   }
+  if (self->meter_window > 0.) {
+    peaq_meter_config cfg;
+    if (meter_config_of (self->meter_window, self->meter_hop, self->meter_depth, &cfg)
+        && peaq_session_set_meter (self->session, &cfg) == PEAQ_OK)
+      self->metered = TRUE;
+    else
+      GST_WARNING_OBJECT (self, "libpeaq_amd: no meter (%s)", peaq_last_error ());
+  }
   return TRUE;
+}
+
+/* The readings delivered since the last call, each as an element message `peaq-meter` on the bus: index, start and
+ * duration (clock times of the window's first sample and of its samples, frames of 2048 every 1024 at 48 kHz), odg,
+ * di, totalsnr, movs.  Call WITHOUT the object lock (posting takes it). */
+static void
+post_meter_readings (GstPeaqAmd * self)
+{
+  for (;;) {
+    peaq_meter_reading rows[16];
+    gint n = 0, i, rc;
+    gboolean adv;
+    GST_OBJECT_LOCK (self);
+    adv = self->advanced;
+    if (!self->metered)
+      rc = PEAQ_ERR_ARG;
+    else if (self->broker)
+      rc = peaq_broker_meter_read (self->broker, self->broker_sid, rows, 16, &n, NULL);
+    else if (self->session)
+      rc = peaq_session_meter_read (self->session, rows, 16, &n, NULL);
+    else
+      rc = PEAQ_ERR_ARG;
+    if (rc == PEAQ_OK && n > 0) {
+      self->st_odg = rows[n - 1].r.odg;
+      self->st_di = rows[n - 1].r.di;
+      self->st_totalsnr = rows[n - 1].r.totalsnr;
+    }
+    GST_OBJECT_UNLOCK (self);
+    if (rc != PEAQ_OK || n <= 0)
+      return;
+    for (i = 0; i < n; i++) {
+      const peaq_meter_reading *m = &rows[i];
+      GValue movs = G_VALUE_INIT;
+      GstStructure *st;
+      gint k;
+      g_value_init (&movs, GST_TYPE_ARRAY);
+      for (k = 0; k < (adv ? PEAQ_MOVS_ADVANCED : PEAQ_MOVS_BASIC); k++) {
+        GValue v = G_VALUE_INIT;
+        g_value_init (&v, G_TYPE_DOUBLE);
+        g_value_set_double (&v, m->r.movs[k]);
+        gst_value_array_append_value (&movs, &v);
+        g_value_unset (&v);
+      }
+      st = gst_structure_new ("peaq-meter", "index", G_TYPE_UINT64, (guint64) m->index,
+          "start", GST_TYPE_CLOCK_TIME, gst_util_uint64_scale ((guint64) m->first_frame * 1024, GST_SECOND, 48000),
+          "duration", GST_TYPE_CLOCK_TIME, gst_util_uint64_scale (((guint64) m->n_frames + 1) * 1024, GST_SECOND, 48000),
+          "odg", G_TYPE_DOUBLE, m->r.odg, "di", G_TYPE_DOUBLE, m->r.di, "totalsnr", G_TYPE_DOUBLE, m->r.totalsnr, NULL);
+      gst_structure_take_value (st, "movs", &movs);
+      gst_element_post_message (GST_ELEMENT (self), gst_message_new_element (GST_OBJECT (self), st));
+    }
+    if (n < 16)
+      return;
+  }
 }
 
 /* call WITHOUT the object lock */
@@ -286,6 +394,29 @@ gst_peaq_amd_get_property (GObject * obj, guint id, GValue * value, GParamSpec *
       read_results (self, &r);
       g_value_set_double (value, r.totalsnr);
       break;
+    case PROP_METER_WINDOW:
+    case PROP_METER_HOP:{
+      /* an element hosted by the broker reads back the broker's values */
+      gdouble w = self->meter_window, h = self->meter_hop > 0. ? self->meter_hop : self->meter_window, bw, bh;
+      if (self->broker && broker_meter_seconds (&bw, &bh)) {
+        w = bw;
+        h = bh;
+      }
+      g_value_set_double (value, id == PROP_METER_WINDOW ? w : h);
+      break;
+    }
+    case PROP_METER_DEPTH:
+      g_value_set_uint (value, self->broker ? 64 : self->meter_depth);
+      break;
+    case PROP_ST_ODG:
+      g_value_set_double (value, self->st_odg);
+      break;
+    case PROP_ST_DI:
+      g_value_set_double (value, self->st_di);
+      break;
+    case PROP_ST_TOTALSNR:
+      g_value_set_double (value, self->st_totalsnr);
+      break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (obj, id, pspec);
   }
@@ -327,6 +458,24 @@ gst_peaq_amd_set_property (GObject * obj, guint id, const GValue * value, GParam
     case PROP_CONSOLE_OUTPUT:
       self->console_output = g_value_get_boolean (value);
       break;
+    case PROP_METER_WINDOW:
+    case PROP_METER_HOP:
+    case PROP_METER_DEPTH:
+      /* like `advanced`: in NULL / READY; the session is made anew if there is one and it has seen no samples */
+      GST_OBJECT_LOCK (self);
+      if (id == PROP_METER_WINDOW)
+        self->meter_window = g_value_get_double (value);
+      else if (id == PROP_METER_HOP)
+        self->meter_hop = g_value_get_double (value);
+      else
+        self->meter_depth = g_value_get_uint (value);
+      if (self->channels > 0 && !self->pushed)
+        renew_session (self);
+      else if (self->pushed)
+        GST_WARNING_OBJECT (self, "the meter's geometry changed mid-stream: it applies from the next (re)negotiation");
+      GST_OBJECT_UNLOCK (self);
+      post_pending_error (self);
+      break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (obj, id, pspec);
   }
@@ -364,6 +513,8 @@ gst_peaq_amd_chain (GstPad * pad, GstObject * parent, GstBuffer * buffer)
     ret = GST_FLOW_ERROR;
   }
   GST_OBJECT_UNLOCK (self);
+  if (ret == GST_FLOW_OK && self->metered)
+    post_meter_readings (self);         /* what this push completed (a broker: what its ticks have delivered so far) */
   if (ret == GST_FLOW_ERROR && !self->failed) {
     self->failed = TRUE;
     GST_ELEMENT_ERROR (self, LIBRARY, FAILED, ("libpeaq_amd: %s", peaq_last_error ()), (NULL));
@@ -411,6 +562,21 @@ gst_peaq_amd_sink_event (GstPad * pad, GstObject * parent, GstEvent * event)
       both = self->eos[0] && self->eos[1];
       GST_OBJECT_UNLOCK (self);
       ret = TRUE;
+      if (both && self->metered) {
+        /* a metered stream is flushed here, not at PAUSED -> READY, so that its last readings are on the bus before
+         * the EOS message; the flush at the state change then finds nothing left, and the results are the same */
+        peaq_result r;
+        GST_OBJECT_LOCK (self);
+        if (!self->meter_flushed) {
+          self->meter_flushed = TRUE;
+          if ((self->broker && (peaq_broker_flush (self->broker, self->broker_sid) != PEAQ_OK
+                      || peaq_broker_results (self->broker, self->broker_sid, &r) != PEAQ_OK))
+              || (self->session && peaq_session_flush (self->session) != PEAQ_OK))
+            GST_ERROR_OBJECT (self, "libpeaq_amd: %s", peaq_last_error ());
+        }
+        GST_OBJECT_UNLOCK (self);
+        post_meter_readings (self);
+      }
       if (both) {
         GstMessage *msg = gst_message_new_eos (parent);
         gst_message_set_seqnum (msg, gst_event_get_seqnum (event));
@@ -508,6 +674,26 @@ gst_peaq_amd_class_init (GstPeaqAmdClass * klass)
       g_param_spec_boolean ("console-output", "console output", "Enable or disable console output", TRUE,
           G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
 
+  /* the meter: sliding-window readings of the running stream (include/peaq_amd.h, "meter") */
+  g_object_class_install_property (oc, PROP_METER_WINDOW,
+      g_param_spec_double ("meter-window", "meter window", "Length of the meter's window in seconds (0 = off)", 0, 1e6, 0,
+          G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_METER_HOP,
+      g_param_spec_double ("meter-hop", "meter hop", "Seconds between the meter's windows (0 = the window)", 0, 1e6, 0,
+          G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_METER_DEPTH,
+      g_param_spec_uint ("meter-depth", "meter depth", "Readings the meter keeps for a reader that falls behind", 1, 4096,
+          64, G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_ST_ODG,
+      g_param_spec_double ("short-term-odg", "short-term ODG", "ODG of the newest window of the meter (NaN before the first)",
+          -G_MAXDOUBLE, G_MAXDOUBLE, 0, G_PARAM_READABLE));
+  g_object_class_install_property (oc, PROP_ST_DI,
+      g_param_spec_double ("short-term-di", "short-term DI", "Distortion index of the newest window of the meter",
+          -G_MAXDOUBLE, G_MAXDOUBLE, 0, G_PARAM_READABLE));
+  g_object_class_install_property (oc, PROP_ST_TOTALSNR,
+      g_param_spec_double ("short-term-totalsnr", "short-term SNR", "Overall SNR in dB of the newest window of the meter",
+          -G_MAXDOUBLE, G_MAXDOUBLE, 0, G_PARAM_READABLE));
+
   gst_element_class_add_static_pad_template (ec, &ref_template);
   gst_element_class_add_static_pad_template (ec, &test_template);
   gst_element_class_set_static_metadata (ec, "Perceptual evaluation of audio quality (MI355X)", "Sink/Audio",
@@ -534,6 +720,8 @@ gst_peaq_amd_init (GstPeaqAmd * self)
   self->failed = FALSE;
   self->pushed = FALSE;
   self->pending_error = NULL;
+  self->metered = self->meter_flushed = FALSE;
+  self->st_odg = self->st_di = self->st_totalsnr = NAN;
 }
 
 static gboolean

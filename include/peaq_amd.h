@@ -164,6 +164,82 @@ int peaq_session_set_level (peaq_session *s, double playback_level_db);
  * does not call this) */
 int peaq_session_reset (peaq_session *s);
 
+/* ---- meter: sliding-window scores of a live stream ---------------------------------------------------------------------
+ * peaq_session_results reads DI / ODG / totalsnr accumulated since sample 0: the score of a file, but no meter -- after
+ * ten minutes it hardly moves whatever happens to the signal.  The meter reads the running stream the way
+ * peaq_batch_run_windows / peaq_batch_run_adv_spans (below) read a finished pair: "how good were the last five seconds",
+ * continuously, on the device behind the session's own launches, and without disturbing the stream.
+ *
+ * Geometry, in FFT frames of the running stream (1024 samples per channel at 48 kHz apart; peaq_meter_frames converts
+ * seconds: max (1, round (seconds * 48000 / 1024))): a window of W = window_frames, a hop of H = hop_frames, a depth of
+ * D = depth kept readings; W >= 1, H >= 1, K = ceil (W / H) <= 64 windows open at once, 1 <= D <= 4096.
+ *   Frames.  Window k = 0, 1, 2, .. covers frames [a_k, b_k) = [k H, k H + W) of the stream; the flush frame counts as
+ *            a frame like any other.
+ *   Blocks (advanced version).  With start_k = a_k ? 1024 (a_k + 1) : 0 and e_k = 1024 (b_k + 1), the filter-bank
+ *            blocks [start_k / 192, e_k / 192); a window that takes the stream's last frame takes all blocks to the
+ *            last, the flush block included.
+ * The reading of a window is exactly what the sections "windows" (basic version) and "spans" (advanced version) below
+ * define for those frames and blocks: the read-out of accumulators reset just before the window's first unit and then
+ * given what the stream's own accumulators are given in the window's units -- the same tentative / normal turns,
+ * values, weights and gates --, the energies of totalsnr summed over those frames only.  A view into the running
+ * stream, IN CONTEXT, not a cold start.  `frames` / `fb_blocks` of the record are the window's counts.
+ *
+ *   Delivery while streaming.  Window k is delivered once frame b_k - 1 has run and, in the advanced version, block
+ *            e_k / 192 - 1 as well: both need the samples up to e_k on both pads.
+ *   Delivery at the flush.  T = peaq_frame_count frames are then known.  Every window with b_k <= T is delivered, then
+ *            one more: the oldest window with a_k < T < b_k, over frames [a_k, T) and the blocks to the end.  Younger
+ *            open windows are discarded.
+ *   Ring.    A delivered reading never changes.  The D newest delivered readings are kept; a reader that falls behind
+ *            loses the oldest, and the loss is counted.
+ *   Off is the default, and then nothing of a session's launches changes.
+ *
+ * Correspondence to the batch, with n = min (n_ref, n_test), m = max (n_ref, n_test): the reading of a window that does
+ * not reach the stream's end is that of the batch window / span {start_k, e_k - start_k} of the pair; that of a window
+ * that reaches it (the cut one, or a complete one whose last frame is the flush frame) is that of {start_k, m - start_k}.
+ * Two corners have no sample window with exactly these frames: a complete window with e_k == m (the batch rule would add
+ * the flush frame) and a window with start_k >= m, which holds only the flush frame.  peaq_meter_readings lists a finished
+ * stream's readings by host arithmetic alone -- for every row its index k, first frame and frame count, first block and
+ * block count, and the equivalent {start, length}, length == 0 in the two corners --; it leaves `r` of the rows
+ * untouched, fills at most `cap` rows (rows may be NULL when cap is 0) and returns the count of all rows in *n.
+ *
+ * peaq_session_set_meter: NULL or window_frames == 0 switches the meter off.  Accepted only before the first push or
+ * right after peaq_session_reset; otherwise, and for a geometry outside the limits above, PEAQ_ERR_ARG before a device
+ * is touched, the message naming entry and value.  Workspace: (K + D + 2) snapshots of 2184 bytes and one launch's trace
+ * records (64 frames of 128 bytes, 120 blocks of 96 bytes); PEAQ_ERR_NOMEM where that cannot be reserved.
+ * peaq_session_meter_read: the delivered, not yet read readings, oldest first, at most `cap` of them (the rest stays
+ * for the next call); *n_read their count; *dropped (may be NULL) the readings lost since the previous call because
+ * more than D were delivered between two reads.  While the stream runs, a row's {start, length} is {start_k, e_k -
+ * start_k}.  It waits for the session's enqueued work and changes nothing of the stream.  With the meter off:
+ * PEAQ_ERR_ARG.  peaq_session_reset restarts the meter: the index starts at 0 again, unread readings are gone.  After
+ * peaq_session_flush the list of readings is complete; it stays readable until the reset.
+ * peaq_meter_frames refuses a NULL pointer and seconds that are negative, not a number or above 1e6 (PEAQ_ERR_ARG);
+ * 0 seconds gives 1 frame.
+ *
+ * The broker (below): peaq_broker_set_meter sets ONE geometry for all sessions of the broker, because it shapes the
+ * launch; accepted before the first peaq_broker_open and before peaq_broker_start (PEAQ_ERR_ARG otherwise), and for a
+ * broker made by peaq_broker_create_multi in every shard.  A tick then adds one small kernel behind each back-end
+ * launch, no copy and no wait: geometry and flush counts ride in the metadata rows the tick uploads anyway.  While a
+ * metered session streams, a tick takes its filter-bank blocks no further than the frame after the last FFT frame
+ * taken, so both paths stay at one sample horizon (nothing waits that would not wait for that frame anyway); its end
+ * result is then that of the same stream cut into other launches.  peaq_broker_meter_read returns what was delivered up
+ * to the last tick enqueued -- it waits for that tick and does not force one.  Closing a slot and opening it again
+ * starts a fresh meter.  Workspace per slot: (K + D + 2) snapshots and a tick's trace records (8 frames, 48 blocks). */
+typedef struct peaq_meter_config {
+  uint32_t window_frames, hop_frames, depth;
+} peaq_meter_config;
+typedef struct peaq_meter_reading {
+  uint64_t index;            /* k */
+  uint64_t start, length;    /* the equivalent batch window / span in samples per channel; length 0: none (see above) */
+  uint32_t first_frame, n_frames, first_block, n_blocks;
+  peaq_result r;
+} peaq_meter_reading;
+size_t peaq_meter_reading_size (void);  /* sizeof (peaq_meter_reading) in THIS library, as peaq_broker_stats_size */
+int peaq_meter_frames (double seconds, uint32_t *frames);
+int peaq_meter_readings (uint64_t n_ref, uint64_t n_test, const peaq_meter_config *cfg,
+                        peaq_meter_reading *rows, int cap, int *n);
+int peaq_session_set_meter (peaq_session *s, const peaq_meter_config *cfg);
+int peaq_session_meter_read (peaq_session *s, peaq_meter_reading *out, int cap, int *n_read, uint64_t *dropped);
+
 /* ---- broker: many live sessions, one launch per tick -------------------------
  * Replaces, for a process hosting MANY `peaq` elements (BASELINE.json
  * configs[5]), the per-element device work of pad_chain -> do_processing
@@ -218,6 +294,9 @@ int  peaq_broker_results (peaq_broker *b, int session_id, peaq_result *out);  /*
 int  peaq_broker_start   (peaq_broker *b, unsigned period_us);         /* own tick thread (0 = 2000 us)      */
 int  peaq_broker_stop    (peaq_broker *b);
 int  peaq_broker_stats   (peaq_broker *b, peaq_broker_stats_t *out);
+int  peaq_broker_set_meter (peaq_broker *b, const peaq_meter_config *cfg);     /* see "meter" above */
+int  peaq_broker_meter_read (peaq_broker *b, int session_id, peaq_meter_reading *out, int cap, int *n_read,
+                             uint64_t *dropped);
 size_t peaq_broker_stats_size (void);   /* sizeof (peaq_broker_stats_t) in THIS library: a caller built against another
                                          * header compares before it hands over a buffer */
 
