@@ -1,7 +1,8 @@
-"""The engine's reduced-precision arithmetics for the advanced version: the 40 complex FIR filters of the
-filter-bank ear model (fbearmodel.c:399-435) on the FP16 matrix instruction with split operands (the
-DEFAULT, PEAQ_FIR_F16X3) and on the FP32 matrix instruction (PEAQ_FIR_F32), everything else FP64
-(include/peaq_amd.h, peaq_ctx_set_fir_mode; priced in profiles/r02_precision_ledger.json).
+"""The engine's reduced-precision arithmetics for the advanced version, both opt-in (the default is the
+reference's FP64 arithmetic, PEAQ_FIR_F64): the 40 complex FIR filters of the filter-bank ear model
+(fbearmodel.c:399-435) on the FP16 matrix instruction with split operands (PEAQ_FIR_F16X3) and on the FP32
+matrix instruction (PEAQ_FIR_F32), everything else FP64 (include/peaq_amd.h, peaq_ctx_set_fir_mode; priced in
+profiles/r02_precision_ledger.json).
 Tolerances of THESE paths, stated here and nowhere looser:
   * per-block excitation patterns vs the oracle: 1e-4 relative (22..24-bit products and FP32 sums over up to
     1456 taps; measured: 2e-5 on noise-like signals, 5e-5 in the bands between the harmonics of a

@@ -162,6 +162,9 @@ def test_filterbank_records_match_oracle(gpu, case, bpl, fir_mode):
                                        err_msg=f"unsmeared {name} ch{c}")
             np.testing.assert_allclose(got[:, c, 80 + lo:120 + lo], exp["excitation"], rtol=gpu.tol("blocks"),
                                        err_msg=f"excitation {name} ch{c}")
+    flags = orc.fb_records(ref, test, n_blocks)[:, :, 160]           # the boundary flag of the reference's block
+    for c in range(ch):
+        assert np.array_equal(got[:, c, 160], flags[:, c]), (c, got[:, c, 160], flags[:, c])
 
 
 @pytest.mark.parametrize("channels", [1, 2])
@@ -351,8 +354,10 @@ def _threshold_outro_pair(p, n, quiet_blocks, reached):
 
 def test_advanced_data_boundary_at_the_threshold_in_full_waves(gpu, fir_mode):
     """The boundary detector of the 192-sample blocks (gstpeaq.c:1081-1099) sits in the high-pass walk, whose
-    straight-line blocks need a full wave of 64 signals -- the single-pair stage tests above never give it one.  32
-    stereo pairs put the threshold itself to the test (see _threshold_outro_pair), every other one an ulp below it."""
+    straight-line blocks are chosen per wave of 64 signals.  (A single pair reaches them too: the spare lanes walk the
+    last signal again, fb_hp_kernel, so every wave is a full one -- but all its lanes then see the same few signals.)
+    32 stereo pairs, two full waves of 64 different signals, put the threshold itself to the test (see
+    _threshold_outro_pair), every other one an ulp below it."""
     n, pairs, quiet = 192 * 150, 32, 40
     inputs = [_threshold_outro_pair(p, n, quiet, reached=p % 2 == 0) for p in range(pairs)]
     got = gpu.run_batch(inputs, 1, 2)
