@@ -1167,14 +1167,23 @@ def cut_shifted(ctx, x, skip, n_keep, q, n_in=None, out=None, stream=None):
     """cut through the fractional-delay filter of every pair's grid point q[p] (peaq_batch_cut_shifted):
     out[p, i, c] = float32(sum_o shift_tab[q[p]][o] float64(x[p, skip[p] + i + o, c])), o = -32 .. 32; samples outside
     [0, n_in[p]) (without n_in: the buffer) contribute nothing; q[p] == 0 moves the bits.  out as for cut.  Returns out."""
+    a_q = np.ascontiguousarray(q, dtype=np.int32)
+    assert a_q.shape == (len(x),)
+    return _cut_along(ctx, x, skip, n_keep, n_in, out, stream, lambda head, tail: ctx.L.peaq_batch_cut_shifted(
+        *head, a_q.ctypes.data_as(C.POINTER(C.c_int32)), *tail))
+
+
+def _cut_along(ctx, x, skip, n_keep, n_in, out, stream, call):
+    """what cut_shifted, cut_drift, cut_track and cut_pieces share: x, skip, n_keep, n_in (default: the buffer) and out
+    (default: zero-filled, even stride) as the four take them; call(head, tail) is the C entry between its leading
+    arguments (ctx .. n_keep) and its trailing ones (d_out, out_stride, stream).  Returns out."""
     import torch
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
     n_pairs, stride, channels = x.shape
     a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
     a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
-    a_q = np.ascontiguousarray(q, dtype=np.int32)
     a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
-    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_q.shape == (n_pairs,) and a_in.shape == (n_pairs,)
+    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,)
     if out is None:
         o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
         with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
@@ -1182,10 +1191,9 @@ def cut_shifted(ctx, x, skip, n_keep, q, n_in=None, out=None, stream=None):
     assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
     assert out.shape[0] == n_pairs and out.shape[2] == channels
     u32p = C.POINTER(C.c_uint32)
-    _check(ctx.L.peaq_batch_cut_shifted(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
-                                        a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p),
-                                        a_q.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out.data_ptr()), out.shape[1],
-                                        _stream_ptr(stream)))
+    _check(call((ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
+                 a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p)),
+                (C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream))))
     return out
 
 
@@ -1291,27 +1299,12 @@ def cut_drift(ctx, x, skip, n_keep, a, e, n_in=None, out=None, stream=None):
     float64(x[p, skip[p] + i + m_i + o, c])), o = -32 .. 32, (m_i, phi_i) = drift_index(a[p], e[p], i); samples outside
     [0, n_in[p]) (without n_in: the buffer) contribute nothing; a[p] == e[p] == 0 moves the bits.  out as for cut.
     Returns out."""
-    import torch
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
-    n_pairs, stride, channels = x.shape
-    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
-    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
     a_a = np.ascontiguousarray(a, dtype=np.float64)
     a_e = np.ascontiguousarray(e, dtype=np.float64)
-    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
-    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,)
-    assert a_a.shape == (n_pairs,) and a_e.shape == (n_pairs,)
-    if out is None:
-        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
-        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
-            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
-    assert out.shape[0] == n_pairs and out.shape[2] == channels
-    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    _check(ctx.L.peaq_batch_cut_drift(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
-                                      a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), a_a.ctypes.data_as(dp),
-                                      a_e.ctypes.data_as(dp), C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
-    return out
+    assert a_a.shape == (len(x),) and a_e.shape == (len(x),)
+    dp = C.POINTER(C.c_double)
+    return _cut_along(ctx, x, skip, n_keep, n_in, out, stream, lambda head, tail: ctx.L.peaq_batch_cut_drift(
+        *head, a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp), *tail))
 
 
 def track_fit(d, valid=None, window=TRACK_WINDOW, max_e=TRACK_MAX_E):
@@ -1429,29 +1422,13 @@ def cut_track(ctx, x, skip, n_keep, window, n_seg, a, e, n_in=None, out=None, st
     """cut along every pair's track (peaq_batch_cut_track): as cut_drift, with (m_i, phi_i) = track_index(window,
     a[p, :n_seg[p]], e[p, :n_seg[p]], i); a, e: [n_pairs, seg_stride].  A pair whose segments are all (0, 0) has its bits
     moved.  Returns out."""
-    import torch
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
-    n_pairs, stride, channels = x.shape
-    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
-    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
     a_seg = np.ascontiguousarray(n_seg, dtype=np.uint32)
     a_a = np.ascontiguousarray(a, dtype=np.float64)
     a_e = np.ascontiguousarray(e, dtype=np.float64)
-    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
-    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,) and a_seg.shape == (n_pairs,)
-    assert a_a.ndim == 2 and a_a.shape[0] == n_pairs and a_a.shape == a_e.shape
-    if out is None:
-        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
-        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
-            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
-    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    assert a_seg.shape == (len(x),) and a_a.ndim == 2 and a_a.shape[0] == len(x) and a_a.shape == a_e.shape
     u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    _check(ctx.L.peaq_batch_cut_track(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
-                                      a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), int(window),
-                                      a_seg.ctypes.data_as(u32p), a_a.shape[1], a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp),
-                                      C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
-    return out
+    return _cut_along(ctx, x, skip, n_keep, n_in, out, stream, lambda head, tail: ctx.L.peaq_batch_cut_track(
+        *head, int(window), a_seg.ctypes.data_as(u32p), a_a.shape[1], a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp), *tail))
 
 
 def steps_workspace_bytes(n_cand, span_max):
@@ -1635,30 +1612,15 @@ def cut_pieces(ctx, x, skip, n_keep, n_pieces, b, a, e, n_in=None, out=None, str
     """cut along every pair's pieces (peaq_batch_cut_pieces): as cut_track, with (m_i, phi_i) = pieces_index(b[p,
     :n_pieces[p]], a[p, :n_pieces[p]], e[p, :n_pieces[p]], i); b, a, e: [n_pairs, piece_stride].  A pair whose pieces are
     all (0, 0) has its bits moved.  Returns out."""
-    import torch
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
-    n_pairs, stride, channels = x.shape
-    a_skip = np.ascontiguousarray(skip, dtype=np.uint32)
-    a_keep = np.ascontiguousarray(n_keep, dtype=np.uint32)
     a_np = np.ascontiguousarray(n_pieces, dtype=np.uint32)
     a_b = np.ascontiguousarray(b, dtype=np.uint32)
     a_a = np.ascontiguousarray(a, dtype=np.float64)
     a_e = np.ascontiguousarray(e, dtype=np.float64)
-    a_in = np.full(n_pairs, stride, dtype=np.uint32) if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
-    assert a_skip.shape == (n_pairs,) and a_keep.shape == (n_pairs,) and a_in.shape == (n_pairs,) and a_np.shape == (n_pairs,)
-    assert a_a.ndim == 2 and a_a.shape[0] == n_pairs and a_a.shape == a_e.shape == a_b.shape
-    if out is None:
-        o_stride = max(int(a_keep.max()) if n_pairs else 0, 2)
-        with _torch_stream(stream):                    # the zero fill runs on the stream the filter runs on
-            out = torch.zeros((n_pairs, o_stride + (o_stride & 1), channels), dtype=torch.float32, device=x.device)
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
-    assert out.shape[0] == n_pairs and out.shape[2] == channels
+    assert a_np.shape == (len(x),) and a_a.ndim == 2 and a_a.shape[0] == len(x) and a_a.shape == a_e.shape == a_b.shape
     u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    _check(ctx.L.peaq_batch_cut_pieces(ctx.h, channels, n_pairs, C.c_void_p(x.data_ptr()), stride, a_in.ctypes.data_as(u32p),
-                                       a_skip.ctypes.data_as(u32p), a_keep.ctypes.data_as(u32p), a_np.ctypes.data_as(u32p),
-                                       a_a.shape[1], a_b.ctypes.data_as(u32p), a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp),
-                                       C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
-    return out
+    return _cut_along(ctx, x, skip, n_keep, n_in, out, stream, lambda head, tail: ctx.L.peaq_batch_cut_pieces(
+        *head, a_np.ctypes.data_as(u32p), a_a.shape[1], a_b.ctypes.data_as(u32p), a_a.ctypes.data_as(dp), a_e.ctypes.data_as(dp),
+        *tail))
 
 
 def wide_factor(max_offset):
@@ -1845,14 +1807,51 @@ def _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_cha
     """align(..., drift=window)"""
     if subsample:
         _need_align(True, 0, True)
+    return _align_along(
+        ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, "last_drift",
+        lambda: estimate_drift(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream),
+        lambda dr, p, nr, nt: drift_lengths(int(lags[p]), dr["a"][p], dr["e"][p], nr, nt),
+        lambda dr, skip, n, a_test, out: cut_drift(ctx, test, skip, n, dr["a"], dr["e"], n_in=a_test, out=out, stream=stream))
+
+
+def _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
+    """align(..., track=window)"""
+    def lengths(tr, p, nr, nt):
+        k = tr["n_segments"][p]
+        return track_lengths(int(lags[p]), window, tr["a"][p, :k], tr["e"][p, :k], nr, nt)
+    return _align_along(
+        ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, "last_track",
+        lambda: estimate_track(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream), lengths,
+        lambda tr, skip, n, a_test, out: cut_track(ctx, test, skip, n, window, tr["n_segments"], tr["a"], tr["e"], n_in=a_test,
+                                                   out=out, stream=stream))
+
+
+def _align_steps(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
+    """align(..., steps=window)"""
+    def lengths(st, p, nr, nt):
+        k = st["n_pieces"][p]
+        return pieces_lengths(int(lags[p]), st["b"][p, :k], st["a"][p, :k], st["e"][p, :k], nr, nt)
+    return _align_along(
+        ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, "last_steps",
+        lambda: estimate_steps(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream), lengths,
+        lambda st, skip, n, a_test, out: cut_pieces(ctx, test, skip, n, st["n_pieces"], st["b"], st["a"], st["e"], n_in=a_test,
+                                                    out=out, stream=stream))
+
+
+def _align_along(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, keep, estimate, lengths,
+                 cut_test):
+    """what align(..., drift=), (..., track=) and (..., steps=) share.  estimate(): the stage's records, kept as
+    align.<keep>; lengths(records, p, n_ref, n_test): pair p's (skip_ref, skip_test, n_keep); cut_test(records, skip,
+    n_keep, n_test, out): the stage's cut of the test buffer.  The reference is cut plainly; a gain is measured on the
+    two CUT buffers and applied into a third."""
     import torch
     n_pairs, stride, _ = ref.shape
     assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
     a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
     a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
-    dr = estimate_drift(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
-    align.last_drift = dr
-    cuts = np.array([drift_lengths(int(lags[p]), dr["a"][p], dr["e"][p], int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)],
+    est = estimate()
+    setattr(align, keep, est)
+    cuts = np.array([lengths(est, p, int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)],
                     dtype=np.uint32).reshape(n_pairs, 3)
     o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
     with _torch_stream(stream):
@@ -1860,63 +1859,7 @@ def _align_drift(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_cha
                 for _ in range(3 if gain is not None else 2)]
     n = np.ascontiguousarray(cuts[:, 2])
     cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
-    cut_drift(ctx, test, cuts[:, 1], n, dr["a"], dr["e"], n_in=a_test, out=bufs[1], stream=stream)
-    if gain is not None:
-        rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
-                              per_channel=gain_per_channel, stream=stream)
-        cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
-        align.last_gain = rec
-        return bufs[0], bufs[2], n, n.copy()
-    return bufs[0], bufs[1], n, n.copy()
-
-
-def _align_track(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
-    """align(..., track=window)"""
-    import torch
-    n_pairs, stride, _ = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
-    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
-    tr = estimate_track(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
-    align.last_track = tr
-    n_seg = tr["n_segments"]
-    cuts = np.array([track_lengths(int(lags[p]), window, tr["a"][p, :n_seg[p]], tr["e"][p, :n_seg[p]], int(a_ref[p]),
-                                   int(a_test[p])) for p in range(n_pairs)], dtype=np.uint32).reshape(n_pairs, 3)
-    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
-    with _torch_stream(stream):
-        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
-                for _ in range(3 if gain is not None else 2)]
-    n = np.ascontiguousarray(cuts[:, 2])
-    cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
-    cut_track(ctx, test, cuts[:, 1], n, window, n_seg, tr["a"], tr["e"], n_in=a_test, out=bufs[1], stream=stream)
-    if gain is not None:
-        rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
-                              per_channel=gain_per_channel, stream=stream)
-        cut_scaled(ctx, bufs[1], np.zeros(n_pairs, np.uint32), n, rec, out=bufs[2], stream=stream)
-        align.last_gain = rec
-        return bufs[0], bufs[2], n, n.copy()
-    return bufs[0], bufs[1], n, n.copy()
-
-
-def _align_steps(ctx, ref, test, lags, n_ref, n_test, stream, gain, gain_per_channel, max_gain_db, window):
-    """align(..., steps=window)"""
-    import torch
-    n_pairs, stride, _ = ref.shape
-    assert (n_ref is None) == (n_test is None), "n_ref and n_test: both or neither"
-    a_ref = np.full(n_pairs, stride, dtype=np.uint32) if n_ref is None else np.asarray(n_ref, dtype=np.uint32)
-    a_test = np.full(n_pairs, stride, dtype=np.uint32) if n_test is None else np.asarray(n_test, dtype=np.uint32)
-    st = estimate_steps(ctx, ref, test, lags, n_ref, n_test, window=window, stream=stream)
-    align.last_steps = st
-    n_pc = st["n_pieces"]
-    cuts = np.array([pieces_lengths(int(lags[p]), st["b"][p, :n_pc[p]], st["a"][p, :n_pc[p]], st["e"][p, :n_pc[p]],
-                                    int(a_ref[p]), int(a_test[p])) for p in range(n_pairs)], dtype=np.uint32).reshape(n_pairs, 3)
-    o_stride = max(int(cuts[:, 2].max()) if n_pairs else 0, 2)
-    with _torch_stream(stream):
-        bufs = [torch.zeros((n_pairs, o_stride + (o_stride & 1), ref.shape[2]), dtype=torch.float32, device=ref.device)
-                for _ in range(3 if gain is not None else 2)]
-    n = np.ascontiguousarray(cuts[:, 2])
-    cut(ctx, ref, cuts[:, 0], n, out=bufs[0], stream=stream)
-    cut_pieces(ctx, test, cuts[:, 1], n, n_pc, st["b"], st["a"], st["e"], n_in=a_test, out=bufs[1], stream=stream)
+    cut_test(est, cuts[:, 1], n, a_test, bufs[1])
     if gain is not None:
         rec, _ = measure_gain(ctx, bufs[0], bufs[1], gain, None, None, n, max_gain_db=max_gain_db,
                               per_channel=gain_per_channel, stream=stream)

@@ -596,6 +596,64 @@ int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, con
   return PEAQ_OK;
 }
 
+int begin_delay_pair(const std::string& who, peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                     uint32_t window, int mode, double max_gain_db, const float* ref, size_t n_ref, const float* test,
+                     size_t n_test, peaq_delay* delay, peaq_gain* gain, const void* out, PairBuffers& in, peaq_delay* rec,
+                     uint32_t* W) {
+  if (int rc = check_gain_mode(who, mode, max_gain_db)) return rc;
+  if (int rc = check_max_lag(who, max_lag)) return rc;
+  if (int rc = check_level(who, level_db)) return rc;
+  if (int rc = check_pair_args(who, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
+  if (gain) std::memset(gain, 0, sizeof *gain);
+  // 1, 2: upload, rate conversion
+  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  // 3: estimate
+  if (int rc = estimate_one_delay(c, channels, in, max_lag, rec)) return rc;
+  if (delay) *delay = *rec;
+  if (!window) return PEAQ_OK;
+  *W = peaq_drift_windows(rec->lag, in.len[0], in.len[1], window);
+  if (*W > PEAQ_DRIFT_MAX_WINDOWS)
+    return fail(PEAQ_ERR_ARG, who + ": " + std::to_string(*W) + " windows of " + std::to_string(window) + " samples are more than " +
+                                  std::to_string(PEAQ_DRIFT_MAX_WINDOWS) + ": take a longer window");
+  return PEAQ_OK;
+}
+
+int score_cut_pair(peaq_ctx* c, int advanced, int channels, double level_db, const PairBuffers& in, const uint32_t skip[2],
+                   uint32_t keep, int mode, double max_gain_db, peaq_gain* gain,
+                   const std::function<int(float* d_out, size_t out_stride)>& cut_test, peaq_result* out) {
+  // 5, 6: plain cut of the reference, the stage's cut of the test signal
+  DevBuf cut[2], matched, d_gain;
+  size_t cstride = std::max<size_t>(keep, 2);
+  cstride += cstride & 1;
+  const size_t cbytes = cstride * channels * sizeof(float);
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(cut[i].reserve(cbytes));
+    HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
+  }
+  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), in.stride, &skip[0], &keep, cut[0].as<float>(), cstride, nullptr)) return rc;
+  if (int rc = cut_test(cut[1].as<float>(), cstride)) return rc;
+  const float* scored = cut[1].as<float>();
+  // 7: the gain of the CUT test signal, applied into a second buffer
+  const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
+  if (match) {
+    const uint32_t zero = 0;
+    HIP_TRY(d_gain.reserve(sizeof(peaq_gain)));
+    HIP_TRY(matched.reserve(cbytes));
+    HIP_TRY(hipMemset(matched.p, 0, cbytes));
+    if (int rc = peaq_batch_measure_gain(c, channels, 1, cut[0].as<float>(), cstride, &zero, cut[1].as<float>(), cstride, &zero,
+                                         &keep, mode, max_gain_db, d_gain.as<peaq_gain>(), nullptr))
+      return rc;
+    if (int rc = peaq_batch_cut_scaled(c, channels, 1, cut[1].as<float>(), cstride, &zero, &keep, d_gain.as<peaq_gain>(),
+                                       matched.as<float>(), cstride, nullptr))
+      return rc;
+    scored = matched.as<float>();
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
+  // 8: the one-pair path
+  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, keep, keep, out);
+}
+
 // What peaq_run_pair_aligned, _matched and _trace score: the pair at 48 kHz as it is (neither max_lag nor a gain
 // mode), or the two signals cut to their common part -- from the estimated lag with max_lag, from 0 without -- with
 // the gain, where a mode other than PEAQ_GAIN_OFF asks for one, measured over that part of the uncut buffers and

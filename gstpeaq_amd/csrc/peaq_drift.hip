@@ -3,33 +3,25 @@
 // peaq_drift_lengths, peaq_batch_estimate_drift, peaq_batch_cut_drift, peaq_run_pair_drift; include/peaq_amd.h,
 // DESIGN.md 17).
 //
-//   drift_cut_kernel   peaq_batch_cut_drift: a workgroup owns 1024 consecutive outputs of one pair, both channels.  The
-//       outputs of a tile read the input from i0 + m_lo - 32 on, m_lo the smaller of the tile's first and last m (m is
-//       monotone in i and moves by at most 2 over 1024 outputs at |e| <= 1e-3); the workgroup stages 1024 + 64 + 4
-//       samples in LDS, the channels of a sample side by side (absent samples as zeros).  Lane l owns outputs l, l + 256,
-//       l + 512, l + 768: neighbouring lanes read neighbouring samples (one LDS read per tap fetches both channels, no
-//       bank conflicts) and, the phase stepping every 1 / (256 |e|) outputs, mostly the same tap row.  The tap row is
-//       per output: each lane loads its taps from the table in device memory (133 KB, resident in L2; the rows of a tile
-//       in the vector L1) with vector loads -- DESIGN.md 17 says why not through LDS.  Pairs with a == 0 and e == 0 take
-//       align_cut_kernel's copy (copy_run, peaq_host.h): their bits are moved.
+//   drift_cut_kernel   peaq_batch_cut_drift: a workgroup owns 1024 consecutive outputs of one pair, both channels, and
+//       makes them in ONE pass of the cuts' shared body (delay_cut_pass, peaq_delay_cut.h: the staging, the taps per
+//       lane, the 65-tap FP64 sum) along the pair's one line.  The outputs of a tile read the input from i0 + m_lo - 32
+//       on, m_lo the smaller of the tile's first and last m (m is monotone in i and moves by at most 2 over 1024 outputs
+//       at |e| <= 1e-3): 1024 + 64 + 4 staged samples.  The phase stepping every 1 / (256 |e|) outputs, neighbouring
+//       lanes mostly read the same tap row.  Pairs with a == 0 and e == 0 take align_cut_kernel's copy
+//       (cut_tile_copied): their bits are moved.
 //   No other kernel: the estimate runs the aligner's and the sub-sample stage's kernels on copies of the windows
 //   (peaq_batch_gather, peaq_batch_estimate_delay, peaq_batch_refine_delay).
 #include "peaq_host.h"
 #include "peaq_drift_math.h"
+#include "peaq_delay_cut.h"   // (behind the arithmetic: its pass is rounded as that is)
 
 namespace {
 
-constexpr int kDrK = PEAQ_SUB_HALF;                    // taps each side
-constexpr int kDrTaps = 2 * kDrK + 1;                  // 65
-constexpr int kDrSteps = PEAQ_SUB_STEPS;               // rows of the table
-constexpr int kDrTile = 1024;                          // outputs per workgroup
-constexpr int kDrPer = 4;                              // ... per lane, 256 apart
 constexpr int kDrSpread = 4;                           // m_i - m_lo within a tile stays below this (2 at |e| = 1e-3)
-constexpr int kDrStage = kDrTile + 2 * kDrK + kDrSpread;   // staged samples
+constexpr int kDrStage = delay_cut_stage(kDrSpread);   // staged samples
 constexpr size_t kDrStagingBudget = (size_t)1 << 30;   // estimate: pairs are taken in groups whose window copies stay below this
-static_assert(kDrTile == 256 * kDrPer, "a lane's share");
-static_assert(kDrSteps == 256, "peaq_drift_index: 256 phases per sample");
-static_assert(kDrTile * PEAQ_DRIFT_MAX_E * kDrSteps + 2 < (kDrSpread - 1) * kDrSteps, "the spread of m over a tile");
+static_assert(kCutTile * PEAQ_DRIFT_MAX_E * kCutSteps + 2 < (kDrSpread - 1) * kCutSteps, "the spread of m over a tile");
 
 struct DriftArgs {
   size_t in_stride, out_stride; // samples per channel between pairs
@@ -46,66 +38,20 @@ __device__ __forceinline__ void dr_cut(const DriftArgs& args, const float* __res
                                        const double* __restrict__ tab, float* lds, double a, double e) {
   const unsigned pair = blockIdx.y;
   const long long n_in = args.n_in[pair], n_keep = args.n_keep[pair];
-  const long long i0 = (long long)blockIdx.x * kDrTile;            // the tile's first output (below n_keep)
-  const long long i_last = min(i0 + kDrTile, n_keep) - 1;          // ... and its last
+  const long long i0 = (long long)blockIdx.x * kCutTile;           // the tile's first output (below n_keep)
+  const long long i_last = min(i0 + kCutTile, n_keep) - 1;         // ... and its last
   long long m_a, m_b;
   int phi;
   drift_index(a, e, i0, &m_a, &phi);
   drift_index(a, e, i_last, &m_b, &phi);
-  const long long m_lo = min(m_a, m_b);
-  const long long s0 = (long long)args.skip[pair] + i0 + m_lo - kDrK;   // input sample under staged position 0
+  const long long m_lo = min(m_a, m_b);   // (named HERE, ahead of the row pointers: as an argument expression behind them
+                                          //  the compiler keeps more loads in flight, 114 registers instead of 103)
   const float* __restrict__ src = in + (size_t)pair * args.in_stride * C;
-  // ---- stage: consecutive lanes read consecutive floats; staged sample v, channel c at lds[C v + c] ----
-  for (int f = threadIdx.x; f < kDrStage * C; f += 256) {
-    const long long s = s0 + (C == 2 ? f >> 1 : f);
-    lds[f] = (s >= 0 && s < n_in) ? src[(size_t)s * C + (C == 2 ? f & 1 : 0)] : 0.f;
-  }
-  __syncthreads();
-  // ---- output j of the lane: i = i0 + l + 256 j; tap o of it meets staged position l + 256 j + (m_i - m_lo) + o ----
-  const double* __restrict__ row[kDrPer];
-  const float* x[kDrPer];
-#pragma unroll
-  for (int j = 0; j < kDrPer; ++j) {
-    const long long i = min(i0 + (long long)threadIdx.x + 256 * j, i_last);   // (an output past n_keep: computed, not stored)
-    long long m;
-    drift_index(a, e, i, &m, &phi);
-    const int dm = max(0, min((int)(m - m_lo), kDrSpread - 1));    // (0 .. 2 by the bound on e: the clamp never acts)
-    row[j] = tab + (size_t)(phi + kDrSteps / 2) * kDrTaps;
-    x[j] = lds + C * ((int)(i - i0) + dm);
-  }
-  double acc[C][kDrPer];
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int j = 0; j < kDrPer; ++j) acc[c][j] = 0.;
-#pragma unroll 5
-  for (int o = 0; o < kDrTaps; ++o) {                              // o = -32 .. 32 of the definition, in that order
-#pragma unroll
-    for (int j = 0; j < kDrPer; ++j) {
-      const double h = row[j][o];
-      if (C == 2) {
-        const float2 v = *reinterpret_cast<const float2*>(x[j] + 2 * o);
-        acc[0][j] = __builtin_fma(h, (double)v.x, acc[0][j]);
-        acc[C - 1][j] = __builtin_fma(h, (double)v.y, acc[C - 1][j]);
-      } else {
-        acc[0][j] = __builtin_fma(h, (double)x[j][o], acc[0][j]);
-      }
-    }
-  }
-  // ---- consecutive lanes store consecutive samples ----
   float* __restrict__ dst = out + (size_t)pair * args.out_stride * C;
   const bool pairs8 = C == 2 && ((uintptr_t)dst & 7) == 0;         // (uniform) both channels in one store
-#pragma unroll
-  for (int j = 0; j < kDrPer; ++j) {
-    const long long i = i0 + (long long)threadIdx.x + 256 * j;
-    if (i >= n_keep) continue;
-    if (pairs8) {
-      reinterpret_cast<float2*>(dst)[i] = {(float)acc[0][j], (float)acc[C - 1][j]};
-    } else {
-#pragma unroll
-      for (int c = 0; c < C; ++c) dst[(size_t)i * C + c] = (float)acc[c][j];
-    }
-  }
+  delay_cut_pass<C, kDrSpread, false>(src, dst, pairs8, n_in, args.skip[pair], i0, i0, i_last, m_lo, kDrStage,
+                                      [=](long long i, long long* m, int* ph) { drift_index(a, e, i, m, ph); },
+                                      tab, lds);
 }
 
 // (the buffers and the table as parameters of their own, as frac_cut_kernel's)
@@ -113,17 +59,10 @@ __global__ __launch_bounds__(256, 4) void drift_cut_kernel(const DriftArgs args,
                                                         float* __restrict__ a_out, const double* __restrict__ shift_tab) {
   __shared__ __attribute__((aligned(16))) float lds[2 * kDrStage];
   const unsigned pair = blockIdx.y;
-  const uint32_t n_keep = args.n_keep[pair];
-  if ((unsigned long long)blockIdx.x * kDrTile >= n_keep) return;  // (the whole workgroup)
   const double a = args.a[pair], e = args.e[pair];
-  if (a == 0. && e == 0.) {                            // (uniform) peaq_batch_cut's copy of this tile's floats
-    const size_t count = (size_t)n_keep * args.channels;
-    const float* __restrict__ src = a_in + ((size_t)pair * args.in_stride + args.skip[pair]) * args.channels;
-    float* __restrict__ dst = a_out + (size_t)pair * args.out_stride * args.channels;
-    for (int sub = 0; sub < args.channels; ++sub)      // a tile is `channels` units of 256 x 4 floats
-      copy_run(src, dst, count, ((size_t)blockIdx.x * args.channels + sub) * 256, blockIdx.x == 0 && sub == 0, CopyBits());
+  if (cut_tile_copied(a_in, a_out, args.in_stride, args.out_stride, args.skip, args.n_keep[pair], args.channels,
+                      (a == 0.) & (e == 0.)))
     return;
-  }
   if (args.channels == 2)
     dr_cut<2>(args, a_in, a_out, shift_tab, lds, a, e);
   else
@@ -138,8 +77,7 @@ struct DriftParams {
 };
 
 int check_drift_params(const std::string& w, const DriftParams& p) {
-  if (p.window < PEAQ_DRIFT_MIN_WINDOW || p.window > PEAQ_DRIFT_MAX_WINDOW)
-    return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(p.window) + " is outside 4096 .. 1048576");
+  if (int rc = check_delay_window(w, p.window)) return rc;
   if (p.R < 1 || p.R > p.window / 4 || p.R > 16384)
     return fail(PEAQ_ERR_ARG, w + ": R " + std::to_string(p.R) + " is outside 1 .. min (window / 4, 16384) = " +
                                   std::to_string(std::min<uint32_t>(p.window / 4, 16384)));
@@ -155,12 +93,8 @@ void drift_record(int32_t lag0, uint32_t W, const peaq_delay* dl, const peaq_sub
                   peaq_drift* out) {
   std::vector<double> d(W), x(W);
   std::vector<uint8_t> valid(W);
-  for (uint32_t w = 0; w < W; ++w) {
-    d[w] = (double)dl[w].lag + (double)sb[w].q / 256.;
-    x[w] = (double)w * p.window + (double)(p.window / 2);
-    valid[w] = std::isfinite(dl[w].norm) && dl[w].norm > 0. && sb[w].flags == 0 &&
-               std::fabs(dl[w].peak) >= p.min_corr * dl[w].norm;
-  }
+  window_delays(dl, sb, W, p.min_corr, d.data(), valid.data());
+  for (uint32_t w = 0; w < W; ++w) x[w] = (double)w * p.window + (double)(p.window / 2);
   peaq_drift r;
   std::memset(&r, 0, sizeof r);
   r.lag0 = lag0;
@@ -326,53 +260,28 @@ extern "C" int peaq_batch_cut_drift(peaq_ctx* c, int channels, int n_pairs, cons
                                     const uint32_t* n_in, const uint32_t* skip, const uint32_t* n_keep, const double* a,
                                     const double* e, float* d_out, size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_cut_drift");
-  if (int rc = check_shape(w, channels, n_pairs)) return rc;
-  if (n_pairs > 0 && (!n_in || !skip || !n_keep || !a || !e)) return fail(PEAQ_ERR_ARG, w + ": NULL n_in, skip, n_keep, a or e");
-  uint32_t keep_max = 0;
-  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
-                                  &keep_max))
-    return rc;
-  if (int rc = check_lengths(w, n_pairs, n_in, 0, "n_in", in_stride, "in_stride")) return rc;
-  const size_t np = (size_t)std::max(n_pairs, 0);
-  const size_t words = 3 * np + (np & 1);              // the doubles behind them start on 8 bytes
-  std::vector<uint32_t> h(words + 4 * np);
-  for (size_t p = 0; p < np; ++p) {
-    if (!(std::fabs(a[p]) <= PEAQ_DRIFT_MAX_A))
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": a " + std::to_string(a[p]) + " is outside -1048576 .. 1048576");
-    if (!(std::fabs(e[p]) <= PEAQ_DRIFT_MAX_E))
-      return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": e " + std::to_string(e[p]) + " is outside -0.001 .. 0.001");
-    h[p] = n_in[p];
-    h[np + p] = skip[p];
-    h[2 * np + p] = n_keep[p];
-    std::memcpy(&h[words + 2 * p], &a[p], sizeof(double));
-    std::memcpy(&h[words + 2 * np + 2 * p], &e[p], sizeof(double));
-  }
-  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
-  if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
-
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const double* tab = nullptr;
-  LenStage* lens = nullptr;
-  if (int rc = frac_shift_table(c, &tab, &lens)) return rc;
-  LenSlot* slot = nullptr;
-  if (int rc = lens->upload(h.data(), h.size(), stream, &slot)) return rc;
+  DelayCutCall k{w, c, channels, n_pairs, d_in, in_stride, n_in, skip, n_keep, d_out, out_stride, stream};
+  if (int rc = k.check(a && e, ", a or e")) return rc;
+  k.pack(3, k.np, false);
+  bool plain;                                          // (the kernel looks at a and e itself)
+  for (size_t p = 0; p < k.np; ++p)
+    if (int rc = k.add_lines(p, nullptr, 1, a + p, e + p, nullptr, PEAQ_DRIFT_MAX_E, "-0.001 .. 0.001", &plain,
+                             [](uint32_t, const auto&) { return PEAQ_OK; }))
+      return rc;
+  if (int rc = k.upload()) return rc;
+  if (!k.slot) return PEAQ_OK;
   DriftArgs args{};
   args.in_stride = in_stride;
   args.out_stride = out_stride;
-  args.n_in = slot->dev.as<uint32_t>();
-  args.skip = args.n_in + np;
-  args.n_keep = args.skip + np;
-  args.a = reinterpret_cast<const double*>(args.n_in + words);
-  args.e = args.a + np;
+  args.n_in = k.dev_col(0);
+  args.skip = k.dev_col(1);
+  args.n_keep = k.dev_col(2);
+  args.a = k.dev_a();
+  args.e = k.dev_e();
   args.channels = channels;
-  const unsigned tiles = (unsigned)(((uint64_t)keep_max + kDrTile - 1) / kDrTile);
-  hipLaunchKernelGGL(drift_cut_kernel, dim3(tiles, (unsigned)n_pairs), dim3(256), 0, stream, args, d_in, d_out, tab);
-  const hipError_t launched = hipGetLastError();
-  const int sent = lens->sent(slot, stream);           // (also after a failed launch: the copy into the slot is enqueued)
-  HIP_TRY(launched);
-  return sent;
+  hipLaunchKernelGGL(drift_cut_kernel, dim3(k.tiles(), (unsigned)n_pairs), dim3(256), 0, stream, args, d_in, d_out, k.tab);
+  return k.launched();
 }
 
 extern "C" int peaq_run_pair_drift(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate, uint32_t max_lag,
@@ -382,31 +291,22 @@ extern "C" int peaq_run_pair_drift(peaq_ctx* c, int advanced, int channels, doub
   const std::string w("peaq_run_pair_drift");
   const DriftParams prm{window, std::min<uint32_t>(window / 4, 1024), 0.5, PEAQ_DRIFT_MAX_E};
   if (int rc = check_drift_params(w, prm)) return rc;
-  if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
-  if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
-  if (gain) std::memset(gain, 0, sizeof *gain);
-  const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
-  // 1, 2: upload, rate conversion
+  // 1 .. 3: upload, rate conversion, estimate
   PairBuffers in;
-  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  peaq_delay rec;
+  uint32_t W = 0;
+  if (int rc = begin_delay_pair(w, c, channels, level_db, rate, max_lag, window, mode, max_gain_db, ref, n_ref, test, n_test,
+                                delay, gain, out, in, &rec, &W))
+    return rc;
   const uint32_t* len = in.len;
   const size_t stride = in.stride;
-  // 3, 4: estimate, the line
-  DevBuf cut[2], matched, d_dl, d_sb, d_gain;
-  peaq_delay rec;
-  if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
-  if (delay) *delay = rec;
-  const uint32_t W = peaq_drift_windows(rec.lag, len[0], len[1], window);
+  // 4: the line
+  DevBuf d_dl, d_sb;
   peaq_drift dr;
   std::memset(&dr, 0, sizeof dr);
   dr.lag0 = rec.lag;
   dr.n_windows = W;
   dr.flags = PEAQ_DRIFT_F_NONE;
-  if (W > PEAQ_DRIFT_MAX_WINDOWS)
-    return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(W) + " windows of " + std::to_string(window) + " samples are more than " +
-                                  std::to_string(PEAQ_DRIFT_MAX_WINDOWS) + ": take a longer window");
   if (W >= 3) {                                        // (fewer: no line whatever they measure)
     HIP_TRY(d_dl.reserve((size_t)W * sizeof(peaq_delay)));
     HIP_TRY(d_sb.reserve((size_t)W * sizeof(peaq_subdelay)));
@@ -416,37 +316,13 @@ extern "C" int peaq_run_pair_drift(peaq_ctx* c, int advanced, int channels, doub
       return rc;
   }
   if (drift) *drift = dr;
-  // 5, 6: plain cut of the reference, drift cut of the test signal
+  // 5 .. 8: both signals cut to the line's lengths, the test signal along the line; the gain; the score
   uint32_t skip[2], keep = 0;
   peaq_drift_lengths(rec.lag, dr.a, dr.e, len[0], len[1], &skip[0], &skip[1], &keep);
-  size_t cstride = std::max<size_t>(keep, 2);
-  cstride += cstride & 1;
-  const size_t cbytes = cstride * channels * sizeof(float);
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(cut[i].reserve(cbytes));
-    HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
-  }
-  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), stride, &skip[0], &keep, cut[0].as<float>(), cstride, nullptr)) return rc;
-  if (int rc = peaq_batch_cut_drift(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &keep, &dr.a, &dr.e, cut[1].as<float>(),
-                                    cstride, nullptr))
-    return rc;
-  const float* scored = cut[1].as<float>();
-  // 7: the gain of the RESAMPLED test signal, applied into a second buffer
-  if (match) {
-    const uint32_t zero = 0;
-    HIP_TRY(d_gain.reserve(sizeof(peaq_gain)));
-    HIP_TRY(matched.reserve(cbytes));
-    HIP_TRY(hipMemset(matched.p, 0, cbytes));
-    if (int rc = peaq_batch_measure_gain(c, channels, 1, cut[0].as<float>(), cstride, &zero, cut[1].as<float>(), cstride, &zero,
-                                         &keep, mode, max_gain_db, d_gain.as<peaq_gain>(), nullptr))
-      return rc;
-    if (int rc = peaq_batch_cut_scaled(c, channels, 1, cut[1].as<float>(), cstride, &zero, &keep, d_gain.as<peaq_gain>(),
-                                       matched.as<float>(), cstride, nullptr))
-      return rc;
-    scored = matched.as<float>();
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
-  // 8: the one-pair path
-  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, keep, keep, out);
+  return score_cut_pair(c, advanced, channels, level_db, in, skip, keep, mode, max_gain_db, gain,
+                        [&](float* d_out, size_t out_stride) {
+                          return peaq_batch_cut_drift(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &keep, &dr.a, &dr.e,
+                                                      d_out, out_stride, nullptr);
+                        },
+                        out);
 }

@@ -42,6 +42,19 @@ inline uint32_t drift_keep(double a, double e, uint32_t skip_test, uint32_t n_co
   return (uint32_t)lo;
 }
 
+// The delay d[w] of every window and whether it counts, from the windows' records of the aligner (Delay: lag, peak,
+// norm) and of the sub-sample stage (Sub: q, flags) -- the public header's peaq_delay and peaq_subdelay, which this
+// header does not need to know (tools/drift_host_check.cpp runs it on records of its own): a window counts where it
+// has energy, a grid point, and a peak of min_corr of the norm.
+template <typename Delay, typename Sub>
+inline void window_delays(const Delay* dl, const Sub* sb, uint32_t W, double min_corr, double* d, uint8_t* valid) {
+  for (uint32_t w = 0; w < W; ++w) {
+    d[w] = (double)dl[w].lag + (double)sb[w].q / 256.;
+    valid[w] = std::isfinite(dl[w].norm) && dl[w].norm > 0. && sb[w].flags == 0 &&
+               std::fabs(dl[w].peak) >= min_corr * dl[w].norm;
+  }
+}
+
 // the middle one of v's values, the mean of the two middle ones for an even count (what a sort would put there)
 inline double median_of(std::vector<double>& v) {
   const size_t n = v.size(), h = n / 2;

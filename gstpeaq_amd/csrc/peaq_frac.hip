@@ -17,8 +17,8 @@
 //       1024 + 64 samples per channel in LDS (absent ones as zeros), a lane owns 4 adjacent outputs per channel and
 //       walks the 68 samples under them once -- 17 reads of 16 bytes per channel, every sample feeding up to 4
 //       multiply-adds per channel -- with the pair's tap row, uniform in the workgroup, from scalar loads.  Pairs with
-//       q == 0 take align_cut_kernel's copy instead (copy_run, peaq_host.h): their bits are moved.
-#include "peaq_host.h"
+//       q == 0 take align_cut_kernel's copy instead (cut_tile_copied, peaq_delay_cut.h): their bits are moved.
+#include "peaq_delay_cut.h"
 
 namespace {
 
@@ -39,7 +39,7 @@ constexpr int kFrTile = 1024;                          // outputs per channel pe
 constexpr int kFrPer = 4;                              // ... per lane
 constexpr int kFrStage = kFrTile + 2 * kFrK;           // staged samples per channel
 constexpr int kFrPitch = kFrStage + 16;                // floats between the channels' LDS rows: a multiple of 4, 16 mod 32
-static_assert(kFrChunk == 256 * kFrOwn && kFrTile == 256 * kFrPer, "a lane's share");
+static_assert(kFrChunk == 256 * kFrOwn && kFrTile == 256 * kFrPer && kFrTile == kCutTile, "a lane's share; the cuts' tile");
 static_assert(kFrStage % 4 == 0 && kFrPitch % 4 == 0 && kFrPitch % 32 == 16, "16-byte LDS reads; the channels' stores on different banks");
 static_assert(kFrSteps == 256, "frac_pick_kernel: one lane per grid point");
 
@@ -323,17 +323,12 @@ __global__ __launch_bounds__(256, 4) void frac_cut_kernel(const ShiftArgs a, con
                                                        float* __restrict__ a_out, const double* __restrict__ shift_tab) {
   __shared__ __attribute__((aligned(16))) float lds[2 * kFrPitch];
   const unsigned pair = blockIdx.y;
+  // (the helper's own test of the tile, made here in front of q: this kernel's filter tiles are 1.4 % slower when q is
+  // asked for beside n_keep as the other cuts ask for their scalars -- its taps are scalar loads behind the same wait)
   const uint32_t n_keep = a.n_keep[pair];
-  if ((unsigned long long)blockIdx.x * kFrTile >= n_keep) return;  // (the whole workgroup)
+  if ((unsigned long long)blockIdx.x * kFrTile >= n_keep) return;
   const int q = a.q[pair];
-  if (q == 0) {                                        // (uniform) peaq_batch_cut's copy of this tile's floats
-    const size_t count = (size_t)n_keep * a.channels;
-    const float* __restrict__ src = a_in + ((size_t)pair * a.in_stride + a.skip[pair]) * a.channels;
-    float* __restrict__ dst = a_out + (size_t)pair * a.out_stride * a.channels;
-    for (int sub = 0; sub < a.channels; ++sub)         // a tile is `channels` units of 256 x 4 floats
-      copy_run(src, dst, count, ((size_t)blockIdx.x * a.channels + sub) * 256, blockIdx.x == 0 && sub == 0, CopyBits());
-    return;
-  }
+  if (cut_tile_copied(a_in, a_out, a.in_stride, a.out_stride, a.skip, n_keep, a.channels, q == 0)) return;
   const double* __restrict__ h = shift_tab + (size_t)(q + kFrSteps / 2) * kFrTaps;
   if (a.channels == 2)
     fr_shift<2>(a, a_in, a_out, h, lds);
@@ -542,48 +537,27 @@ extern "C" int peaq_batch_cut_shifted(peaq_ctx* c, int channels, int n_pairs, co
                                       const uint32_t* n_in, const uint32_t* skip, const uint32_t* n_keep, const int32_t* q,
                                       float* d_out, size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_cut_shifted");
-  if (int rc = check_shape(w, channels, n_pairs)) return rc;
-  if (n_pairs > 0 && (!n_in || !skip || !n_keep || !q)) return fail(PEAQ_ERR_ARG, w + ": NULL n_in, skip, n_keep or q");
-  uint32_t keep_max = 0;
-  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
-                                  &keep_max))
-    return rc;
-  if (int rc = check_lengths(w, n_pairs, n_in, 0, "n_in", in_stride, "in_stride")) return rc;
-  const size_t np = (size_t)std::max(n_pairs, 0);
-  std::vector<uint32_t> h(4 * np);
-  for (size_t p = 0; p < np; ++p) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  DelayCutCall k{w, c, channels, n_pairs, d_in, in_stride, n_in, skip, n_keep, d_out, out_stride, stream};
+  if (int rc = k.check(q, " or q")) return rc;
+  k.pack(4, 0, false);
+  for (size_t p = 0; p < k.np; ++p) {
     if (q[p] < -kFrSteps / 2 || q[p] > kFrSteps / 2 - 1)
       return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": q " + std::to_string(q[p]) + " is outside -128 .. 127");
-    h[p] = n_in[p];
-    h[np + p] = skip[p];
-    h[2 * np + p] = n_keep[p];
-    std::memcpy(&h[3 * np + p], &q[p], sizeof(uint32_t));
+    std::memcpy(&k.col(3, p), &q[p], sizeof(uint32_t));
   }
-  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
-  if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
-
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  FracState* st = nullptr;
-  if (int rc = frac_state(c, &st)) return rc;
-  LenSlot* slot = nullptr;
-  if (int rc = st->lens.upload(h.data(), h.size(), stream, &slot)) return rc;
+  if (int rc = k.upload()) return rc;
+  if (!k.slot) return PEAQ_OK;
   ShiftArgs a{};
   a.in_stride = in_stride;
   a.out_stride = out_stride;
-  a.n_in = slot->dev.as<uint32_t>();
-  a.skip = a.n_in + np;
-  a.n_keep = a.skip + np;
-  a.q = reinterpret_cast<const int32_t*>(a.n_keep + np);
+  a.n_in = k.dev_col(0);
+  a.skip = k.dev_col(1);
+  a.n_keep = k.dev_col(2);
+  a.q = reinterpret_cast<const int32_t*>(k.dev_col(3));
   a.channels = channels;
-  const unsigned tiles = (unsigned)(((uint64_t)keep_max + kFrTile - 1) / kFrTile);
-  hipLaunchKernelGGL(frac_cut_kernel, dim3(tiles, (unsigned)n_pairs), dim3(256), 0, stream, a, d_in, d_out,
-                     st->shift.as<double>());
-  const hipError_t launched = hipGetLastError();
-  const int sent = st->lens.sent(slot, stream);        // (also after a failed launch: the copy into the slot is enqueued)
-  HIP_TRY(launched);
-  return sent;
+  hipLaunchKernelGGL(frac_cut_kernel, dim3(k.tiles(), (unsigned)n_pairs), dim3(256), 0, stream, a, d_in, d_out, k.tab);
+  return k.launched();
 }
 
 extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate,
@@ -591,22 +565,16 @@ extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, 
                                        const float* test, size_t n_test, peaq_delay* delay, peaq_subdelay* subdelay,
                                        peaq_gain* gain, peaq_result* out) {
   const std::string w("peaq_run_pair_subsample");
-  if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
-  if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
-  if (gain) std::memset(gain, 0, sizeof *gain);
-  const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
-  // 1, 2: upload, rate conversion
+  // 1 .. 3: upload, rate conversion, estimate
   PairBuffers in;
-  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  peaq_delay rec;
+  if (int rc = begin_delay_pair(w, c, channels, level_db, rate, max_lag, 0, mode, max_gain_db, ref, n_ref, test, n_test, delay,
+                                gain, out, in, &rec, nullptr))
+    return rc;
   const uint32_t* len = in.len;
   const size_t stride = in.stride;
-  // 3, 4: estimate, refine
-  DevBuf cut[2], matched, d_sub, d_gain;
-  peaq_delay rec;
-  if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
-  if (delay) *delay = rec;
+  // 4: refine
+  DevBuf d_sub;
   HIP_TRY(d_sub.reserve(sizeof(peaq_subdelay)));
   if (int rc = peaq_batch_refine_delay(c, channels, 1, in.d(0), in.d(1), stride, len, len + 1, 0, &rec.lag,
                                        d_sub.as<peaq_subdelay>(), nullptr))
@@ -615,38 +583,13 @@ extern "C" int peaq_run_pair_subsample(peaq_ctx* c, int advanced, int channels, 
   peaq_subdelay sub;
   HIP_TRY(hipMemcpy(&sub, d_sub.p, sizeof sub, hipMemcpyDeviceToHost));
   if (subdelay) *subdelay = sub;
-  // 5, 6: plain cut of the reference, shifted cut of the test signal
+  // 5 .. 8: both signals cut to their common part, the test signal through the shift filter; the gain; the score
   uint32_t skip[2], common = 0;
   peaq_aligned_lengths(rec.lag, len[0], len[1], &skip[0], &skip[1], &common);
-  size_t cstride = std::max<size_t>(common, 2);
-  cstride += cstride & 1;
-  const size_t cbytes = cstride * channels * sizeof(float);
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(cut[i].reserve(cbytes));
-    HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
-  }
-  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), stride, &skip[0], &common, cut[0].as<float>(), cstride, nullptr))
-    return rc;
-  if (int rc = peaq_batch_cut_shifted(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &common, &sub.q,
-                                      cut[1].as<float>(), cstride, nullptr))
-    return rc;
-  const float* scored = cut[1].as<float>();
-  // 7: the gain of the SHIFTED test signal, applied into a second buffer
-  if (match) {
-    const uint32_t zero = 0;
-    HIP_TRY(d_gain.reserve(sizeof(peaq_gain)));
-    HIP_TRY(matched.reserve(cbytes));
-    HIP_TRY(hipMemset(matched.p, 0, cbytes));
-    if (int rc = peaq_batch_measure_gain(c, channels, 1, cut[0].as<float>(), cstride, &zero, cut[1].as<float>(), cstride, &zero,
-                                         &common, mode, max_gain_db, d_gain.as<peaq_gain>(), nullptr))
-      return rc;
-    if (int rc = peaq_batch_cut_scaled(c, channels, 1, cut[1].as<float>(), cstride, &zero, &common, d_gain.as<peaq_gain>(),
-                                       matched.as<float>(), cstride, nullptr))
-      return rc;
-    scored = matched.as<float>();
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
-  // 8: the one-pair path
-  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, common, common, out);
+  return score_cut_pair(c, advanced, channels, level_db, in, skip, common, mode, max_gain_db, gain,
+                        [&](float* d_out, size_t out_stride) {
+                          return peaq_batch_cut_shifted(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &common, &sub.q, d_out,
+                                                        out_stride, nullptr);
+                        },
+                        out);
 }

@@ -434,10 +434,24 @@ int estimate_one_delay(peaq_ctx* c, int channels, const PairBuffers& pb, uint32_
 // (d) one prepared pair scored with peaq_batch_run, the result fetched
 int score_one_pair(peaq_ctx* c, int advanced, int channels, double level_db, const float* d_ref, const float* d_test,
                    size_t stride, uint32_t len_ref, uint32_t len_test, peaq_result* out);
+// (e) the head of peaq_run_pair_subsample, _drift, _track and _steps, behind the checks of their own parameters: the
+//     gain mode, max_lag, the level and (a); *gain cleared; (b) into `in`; (c) into *rec and, where asked for, *delay.
+//     With a window (0: the entry has none), *W: the whole windows of the common part, at most PEAQ_DRIFT_MAX_WINDOWS.
+int begin_delay_pair(const std::string& who, peaq_ctx* c, int channels, double level_db, uint32_t rate, uint32_t max_lag,
+                     uint32_t window, int mode, double max_gain_db, const float* ref, size_t n_ref, const float* test,
+                     size_t n_test, peaq_delay* delay, peaq_gain* gain, const void* out, PairBuffers& in, peaq_delay* rec,
+                     uint32_t* W);
+// (f) their tail: `keep` samples of the reference from skip[0] on cut plainly, those of the test signal by
+//     cut_test(d_out, out_stride) -- the stage's cut of in.d(1) from skip[1] on --, the gain that `mode` asks for measured
+//     on the two CUT buffers and applied into a third one, fetched into *gain; (d)
+int score_cut_pair(peaq_ctx* c, int advanced, int channels, double level_db, const PairBuffers& in, const uint32_t skip[2],
+                   uint32_t keep, int mode, double max_gain_db, peaq_gain* gain,
+                   const std::function<int(float* d_out, size_t out_stride)>& cut_test, peaq_result* out);
 
 // ---------------------------------------------------------------------------
 // DEVICE SIDE.  The pieces the kernels of peaq_align.hip, peaq_gain.hip, peaq_frac.hip, peaq_drift.hip, peaq_track.hip, peaq_steps.hip and peaq_gather.hip share
-// (256 threads per workgroup).  No kernel is defined in this header.
+// (256 threads per workgroup).  No kernel is defined in this header.  (What only the cuts along a delay share is in
+// peaq_delay_cut.h.)
 // ---------------------------------------------------------------------------
 // A workgroup's share of the copy of `count` consecutive floats from src to dst: the 16-byte units v0 .. v0 + 255,
 // counted from the first 16-byte aligned float of dst, and with `ends` the unaligned head and the tail, at most 3

@@ -11,15 +11,17 @@
 //       known yet), its total and the three side sums: 8 doubles to the scratch.  No atomics.
 //   steps_pick_kernel    one workgroup per candidate: the chunks' totals added in chunk order, the side sums likewise,
 //       the polarity, then the largest s H over the chunks' extremes, ties to the smaller position; the record.
-//   pieces_cut_kernel    peaq_batch_cut_pieces: track_cut_kernel's tile (peaq_track.hip), 1024 outputs of one pair per
-//       workgroup, lane l owning outputs l + 256 j.  The piece of the tile's first output comes from a binary search over
-//       b that is uniform over the workgroup; then a loop, uniform too, over the pieces that meet the tile -- almost
-//       always one.  A pass stages ITS piece's span in LDS (m is monotone along one line, so the smallest m is at one of
-//       the pass's two end outputs; kPcSpread has the arithmetic) and computes the tile's outputs inside the piece, so
-//       lines need not meet and a jump may be of any size.  Pairs whose pieces are all (0, 0) take align_cut_kernel's
-//       copy (copy_run, peaq_host.h): their bits are moved.
+//   pieces_cut_kernel    peaq_batch_cut_pieces: 1024 outputs of one pair per workgroup, made in one pass of the cuts'
+//       shared body (delay_cut_pass, peaq_delay_cut.h) PER PIECE that meets the tile.  The piece of the tile's first
+//       output comes from a binary search over b that is uniform over the workgroup; then a loop, uniform too, over the
+//       pieces that meet the tile -- almost always one.  A pass stages ITS piece's span in LDS (m is monotone along one
+//       line, so the smallest m is at one of the pass's two end outputs; kPcSpread has the arithmetic) and computes the
+//       tile's outputs inside the piece -- a wave that owns none of them skips the sum --, so lines need not meet and a
+//       jump may be of any size.  Pairs whose pieces are all (0, 0) take align_cut_kernel's copy (cut_tile_copied):
+//       their bits are moved.
 #include "peaq_host.h"
 #include "peaq_steps_math.h"
+#include "peaq_delay_cut.h"   // (behind the arithmetic: its pass is rounded as that is)
 
 namespace {
 
@@ -259,20 +261,13 @@ __global__ __launch_bounds__(256, 4) void steps_pick_kernel(const LocateArgs a) 
 // ---------------------------------------------------------------------------
 // cut
 // ---------------------------------------------------------------------------
-constexpr int kPcK = PEAQ_SUB_HALF;                    // taps each side
-constexpr int kPcTaps = 2 * kPcK + 1;                  // 65
-constexpr int kPcSteps = PEAQ_SUB_STEPS;               // rows of the table
-constexpr int kPcTile = 1024;                          // outputs per workgroup
-constexpr int kPcPer = 4;                              // ... per lane, 256 apart
 // m_i - m_lo within one pass stays below this.  A pass follows ONE line: in grid steps of 1/256 sample, g = rint (256 (a
 // + e i)) moves over the pass's outputs by at most 256 |e| per output (4096 in all at 1/64 over a whole tile) and one
 // more for each of the two roundings at its ends: 4098 at the outside.  m = floor ((g + 128) / 256) then moves by at
 // most 4098 / 256 + 1 = 17.  The same span as track_cut_kernel's, so the same LDS.
 constexpr int kPcSpread = 20;
-constexpr int kPcStage = kPcTile + 2 * kPcK + kPcSpread;   // staged samples
-static_assert(kPcTile == 256 * kPcPer, "a lane's share");
-static_assert(kPcSteps == 256, "peaq_drift_index: 256 phases per sample");
-static_assert(kPcTile * PEAQ_TRACK_MAX_E * kPcSteps + 2 <= (kPcSpread - 2) * kPcSteps, "the spread of m over a pass");
+constexpr int kPcStage = delay_cut_stage(kPcSpread);   // staged samples
+static_assert(kCutTile * PEAQ_TRACK_MAX_E * kCutSteps + 2 <= (kPcSpread - 2) * kCutSteps, "the spread of m over a pass");
 
 struct PiecesArgs {
   size_t in_stride, out_stride; // samples per channel between pairs
@@ -292,8 +287,8 @@ __device__ __forceinline__ void pc_cut(const PiecesArgs& args, const float* __re
                                        const double* __restrict__ tab, float* lds, uint32_t n_pieces) {
   const unsigned pair = blockIdx.y;
   const long long n_in = args.n_in[pair], n_keep = args.n_keep[pair];
-  const long long i0 = (long long)blockIdx.x * kPcTile;            // the tile's first output (below n_keep)
-  const long long i_last = min(i0 + kPcTile, n_keep) - 1;          // ... and its last
+  const long long i0 = (long long)blockIdx.x * kCutTile;           // the tile's first output (below n_keep)
+  const long long i_last = min(i0 + kCutTile, n_keep) - 1;         // ... and its last
   const uint32_t* __restrict__ pb = args.b + args.off[pair];
   const double* __restrict__ pa = args.a + args.off[pair];
   const double* __restrict__ pe = args.e + args.off[pair];
@@ -312,64 +307,12 @@ __device__ __forceinline__ void pc_cut(const PiecesArgs& args, const float* __re
     drift_index(a, e, first, &m_a, &phi);
     drift_index(a, e, last, &m_b, &phi);
     const long long m_lo = min(m_a, m_b);
-    const long long s0 = (long long)args.skip[pair] + first + m_lo - kPcK;   // input sample under staged position 0
-    const int n_stage = (int)(last - first) + 1 + 2 * kPcK + kPcSpread;      // (at most kPcStage)
+    const int n_stage = (int)(last - first) + 1 + 2 * kCutK + kPcSpread;     // (at most kPcStage)
     if (staged) __syncthreads();                                   // (uniform) the pass before this one still reads
     staged = true;
-    // ---- stage: consecutive lanes read consecutive floats; staged sample v, channel c at lds[C v + c] ----
-    for (int f = threadIdx.x; f < n_stage * C; f += 256) {
-      const long long s = s0 + (C == 2 ? f >> 1 : f);
-      lds[f] = (s >= 0 && s < n_in) ? src[(size_t)s * C + (C == 2 ? f & 1 : 0)] : 0.f;
-    }
-    __syncthreads();
-    // ---- output j of the lane: i = i0 + l + 256 j; tap o of it meets staged position i - first + (m_i - m_lo) + o ----
-    const double* __restrict__ row[kPcPer];
-    const float* x[kPcPer];
-    bool mine[kPcPer], any = false;
-#pragma unroll
-    for (int j = 0; j < kPcPer; ++j) {
-      const long long own = i0 + (long long)threadIdx.x + 256 * j;
-      mine[j] = own >= first && own <= last;
-      any = any || mine[j];
-      const long long i = min(max(own, first), last);              // (an output of another pass: computed here, not stored)
-      long long m;
-      drift_index(a, e, i, &m, &phi);
-      const int dm = max(0, min((int)(m - m_lo), kPcSpread - 1));  // (0 .. 17 by the bounds above: the clamp never acts)
-      row[j] = tab + (size_t)(phi + kPcSteps / 2) * kPcTaps;
-      x[j] = lds + C * ((int)(i - first) + dm);
-    }
-    if (__builtin_amdgcn_ballot_w64(any) == 0) continue;           // (per wave) none of its outputs lies in this piece
-    double acc[C][kPcPer];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-      for (int j = 0; j < kPcPer; ++j) acc[c][j] = 0.;
-#pragma unroll 5
-    for (int o = 0; o < kPcTaps; ++o) {                            // o = -32 .. 32 of the definition, in that order
-#pragma unroll
-      for (int j = 0; j < kPcPer; ++j) {
-        const double h = row[j][o];
-        if (C == 2) {
-          const float2 v = *reinterpret_cast<const float2*>(x[j] + 2 * o);
-          acc[0][j] = __builtin_fma(h, (double)v.x, acc[0][j]);
-          acc[C - 1][j] = __builtin_fma(h, (double)v.y, acc[C - 1][j]);
-        } else {
-          acc[0][j] = __builtin_fma(h, (double)x[j][o], acc[0][j]);
-        }
-      }
-    }
-    // ---- consecutive lanes store consecutive samples ----
-#pragma unroll
-    for (int j = 0; j < kPcPer; ++j) {
-      if (!mine[j]) continue;
-      const long long i = i0 + (long long)threadIdx.x + 256 * j;
-      if (pairs8) {
-        reinterpret_cast<float2*>(dst)[i] = {(float)acc[0][j], (float)acc[C - 1][j]};
-      } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) dst[(size_t)i * C + c] = (float)acc[c][j];
-      }
-    }
+    delay_cut_pass<C, kPcSpread, true>(src, dst, pairs8, n_in, args.skip[pair], i0, first, last, m_lo, n_stage,
+                                       [=](long long i, long long* m, int* ph) { drift_index(a, e, i, m, ph); },
+                                       tab, lds);
   }
 }
 
@@ -378,17 +321,9 @@ __global__ __launch_bounds__(256, 4) void pieces_cut_kernel(const PiecesArgs arg
                                                          float* __restrict__ a_out, const double* __restrict__ shift_tab) {
   __shared__ __attribute__((aligned(16))) float lds[2 * kPcStage];
   const unsigned pair = blockIdx.y;
-  const uint32_t n_keep = args.n_keep[pair];
-  if ((unsigned long long)blockIdx.x * kPcTile >= n_keep) return;  // (the whole workgroup)
   const uint32_t n_pieces = args.n_pieces[pair];
-  if (n_pieces == 0) {                                 // (uniform) peaq_batch_cut's copy of this tile's floats
-    const size_t count = (size_t)n_keep * args.channels;
-    const float* __restrict__ src = a_in + ((size_t)pair * args.in_stride + args.skip[pair]) * args.channels;
-    float* __restrict__ dst = a_out + (size_t)pair * args.out_stride * args.channels;
-    for (int sub = 0; sub < args.channels; ++sub)      // a tile is `channels` units of 256 x 4 floats
-      copy_run(src, dst, count, ((size_t)blockIdx.x * args.channels + sub) * 256, blockIdx.x == 0 && sub == 0, CopyBits());
+  if (cut_tile_copied(a_in, a_out, args.in_stride, args.out_stride, args.skip, args.n_keep[pair], args.channels, n_pieces == 0))
     return;
-  }
   if (args.channels == 2)
     pc_cut<2>(args, a_in, a_out, shift_tab, lds, n_pieces);
   else
@@ -401,13 +336,8 @@ size_t steps_per_cand(uint32_t span_max) {
   return (size_t)std::max<uint32_t>(steps_chunks(std::min<uint32_t>(span_max, PEAQ_STEP_MAX_SPAN)), 1) * kStRow * sizeof(double);
 }
 
-int check_steps_window(const std::string& w, uint32_t window) {
-  if (window < PEAQ_DRIFT_MIN_WINDOW || window > PEAQ_DRIFT_MAX_WINDOW)
-    return fail(PEAQ_ERR_ARG, w + ": window " + std::to_string(window) + " is outside 4096 .. 1048576");
-  return PEAQ_OK;
-}
 int check_steps_knots(const std::string& w, uint32_t n_windows, uint32_t window, uint32_t n_common) {
-  if (int rc = check_steps_window(w, window)) return rc;
+  if (int rc = check_delay_window(w, window)) return rc;
   if (n_windows > PEAQ_DRIFT_MAX_WINDOWS)
     return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(n_windows) + " windows are more than " + std::to_string(PEAQ_DRIFT_MAX_WINDOWS));
   if ((uint64_t)n_windows * window > n_common)
@@ -688,17 +618,11 @@ extern "C" int peaq_batch_cut_pieces(peaq_ctx* c, int channels, int n_pairs, con
                                      uint32_t piece_stride, const uint32_t* b, const double* a, const double* e, float* d_out,
                                      size_t out_stride, void* stream_) {
   const std::string w("peaq_batch_cut_pieces");
-  if (int rc = check_shape(w, channels, n_pairs)) return rc;
-  if (n_pairs > 0 && (!n_in || !skip || !n_keep || !n_pieces || !b || !a || !e))
-    return fail(PEAQ_ERR_ARG, w + ": NULL n_in, skip, n_keep, n_pieces, b, a or e");
-  uint32_t keep_max = 0;
-  if (int rc = check_cut_geometry(w, "pair", channels, n_pairs, n_pairs, d_in, in_stride, skip, n_keep, d_out, out_stride,
-                                  &keep_max))
-    return rc;
-  if (int rc = check_lengths(w, n_pairs, n_in, 0, "n_in", in_stride, "in_stride")) return rc;
-  const size_t np = (size_t)std::max(n_pairs, 0);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  DelayCutCall k{w, c, channels, n_pairs, d_in, in_stride, n_in, skip, n_keep, d_out, out_stride, stream};
+  if (int rc = k.check(n_pieces && b && a && e, ", n_pieces, b, a or e")) return rc;
   uint64_t total = 0;
-  for (size_t p = 0; p < np; ++p) {
+  for (size_t p = 0; p < k.np; ++p) {
     if (n_pieces[p] < 1 || n_pieces[p] > piece_stride || n_pieces[p] > PEAQ_PIECES_MAX_PER_PAIR)
       return fail(PEAQ_ERR_ARG, w + ": pair " + std::to_string(p) + ": n_pieces " + std::to_string(n_pieces[p]) +
                                     " is outside 1 .. min (piece_stride " + std::to_string(piece_stride) + ", " +
@@ -708,65 +632,39 @@ extern "C" int peaq_batch_cut_pieces(peaq_ctx* c, int channels, int n_pairs, con
   if (total > PEAQ_PIECES_MAX_PER_CALL)
     return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(total) + " pieces are more than " + std::to_string(PEAQ_PIECES_MAX_PER_CALL) +
                                   " in one call");
-  const size_t words = 5 * np + (np & 1);              // the doubles behind them start on 8 bytes
-  std::vector<uint32_t> h(words + 5 * (size_t)total);
-  size_t off = 0;
-  for (size_t p = 0; p < np; ++p) {
+  k.pack(5, (size_t)total, true);
+  for (size_t p = 0; p < k.np; ++p) {
     const uint32_t* pb = b + p * piece_stride;
-    const double* pa = a + p * piece_stride;
-    const double* pe = e + p * piece_stride;
-    bool plain = true;
-    for (uint32_t k = 0; k < n_pieces[p]; ++k) {
-      const std::string where = w + ": pair " + std::to_string(p) + ", piece " + std::to_string(k);
-      if (!(std::fabs(pa[k]) <= PEAQ_DRIFT_MAX_A))
-        return fail(PEAQ_ERR_ARG, where + ": a " + std::to_string(pa[k]) + " is outside -1048576 .. 1048576");
-      if (!(std::fabs(pe[k]) <= PEAQ_TRACK_MAX_E))
-        return fail(PEAQ_ERR_ARG, where + ": e " + std::to_string(pe[k]) + " is outside -0.015625 .. 0.015625");
-      if (k == 0 && pb[0] != 0) return fail(PEAQ_ERR_ARG, where + ": b " + std::to_string(pb[0]) + " is not 0");
-      if (k && pb[k] <= pb[k - 1])
-        return fail(PEAQ_ERR_ARG, where + ": b " + std::to_string(pb[k]) + " is not above the piece before it at " +
-                                      std::to_string(pb[k - 1]));
-      plain = plain && pa[k] == 0. && pe[k] == 0.;
-      std::memcpy(&h[words + 2 * (off + k)], &pa[k], sizeof(double));
-      std::memcpy(&h[words + 2 * (size_t)total + 2 * (off + k)], &pe[k], sizeof(double));
-      h[words + 4 * (size_t)total + off + k] = pb[k];
-    }
-    h[p] = n_in[p];
-    h[np + p] = skip[p];
-    h[2 * np + p] = n_keep[p];
-    h[3 * np + p] = plain ? 0 : n_pieces[p];
-    h[4 * np + p] = (uint32_t)off;
-    off += n_pieces[p];
+    const size_t first = k.next_line;
+    bool plain;
+    if (int rc = k.add_lines(p, "piece", n_pieces[p], a + p * piece_stride, e + p * piece_stride, pb, PEAQ_TRACK_MAX_E,
+                             "-0.015625 .. 0.015625", &plain, [&](uint32_t s, const auto& where) {
+                               if (s == 0 && pb[0] != 0) return fail(PEAQ_ERR_ARG, where() + ": b " + std::to_string(pb[0]) + " is not 0");
+                               if (s && pb[s] <= pb[s - 1])
+                                 return fail(PEAQ_ERR_ARG, where() + ": b " + std::to_string(pb[s]) +
+                                                               " is not above the piece before it at " + std::to_string(pb[s - 1]));
+                               return (int)PEAQ_OK;
+                             }))
+      return rc;
+    k.col(3, p) = plain ? 0 : n_pieces[p];             // (0: every piece is (0, 0), the pair's bits are moved)
+    k.col(4, p) = (uint32_t)first;
   }
-  if (!c) return fail(PEAQ_ERR_ARG, w + ": ctx is NULL");
-  if (n_pairs == 0 || keep_max == 0) return PEAQ_OK;
-
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const double* tab = nullptr;
-  LenStage* lens = nullptr;
-  if (int rc = frac_shift_table(c, &tab, &lens)) return rc;
-  LenSlot* slot = nullptr;
-  if (int rc = lens->upload(h.data(), h.size(), stream, &slot)) return rc;
+  if (int rc = k.upload()) return rc;
+  if (!k.slot) return PEAQ_OK;
   PiecesArgs args{};
   args.in_stride = in_stride;
   args.out_stride = out_stride;
-  args.n_in = slot->dev.as<uint32_t>();
-  args.skip = args.n_in + np;
-  args.n_keep = args.skip + np;
-  args.n_pieces = args.n_keep + np;
-  args.off = args.n_pieces + np;
-  args.a = reinterpret_cast<const double*>(args.n_in + words);
-  args.e = args.a + total;
-  args.b = reinterpret_cast<const uint32_t*>(args.e + total);
+  args.n_in = k.dev_col(0);
+  args.skip = k.dev_col(1);
+  args.n_keep = k.dev_col(2);
+  args.n_pieces = k.dev_col(3);
+  args.off = k.dev_col(4);
+  args.a = k.dev_a();
+  args.e = k.dev_e();
+  args.b = k.dev_b();
   args.channels = channels;
-  const unsigned tiles = (unsigned)(((uint64_t)keep_max + kPcTile - 1) / kPcTile);
-  hipLaunchKernelGGL(pieces_cut_kernel, dim3(tiles, (unsigned)n_pairs), dim3(256), 0, stream, args, d_in, d_out, tab);
-  const hipError_t launched = hipGetLastError();
-  const int sent = lens->sent(slot, stream);           // (also after a failed launch: the copy into the slot is enqueued)
-  HIP_TRY(launched);
-  return sent;
+  hipLaunchKernelGGL(pieces_cut_kernel, dim3(k.tiles(), (unsigned)n_pairs), dim3(256), 0, stream, args, d_in, d_out, k.tab);
+  return k.launched();
 }
 
 extern "C" int peaq_run_pair_steps(peaq_ctx* c, int advanced, int channels, double level_db, uint32_t rate, uint32_t max_lag,
@@ -774,28 +672,19 @@ extern "C" int peaq_run_pair_steps(peaq_ctx* c, int advanced, int channels, doub
                                    const float* test, size_t n_test, peaq_delay* delay, peaq_track* track, peaq_pieces* pieces,
                                    peaq_step* steps, uint32_t max_steps, peaq_gain* gain, peaq_result* out) {
   const std::string w("peaq_run_pair_steps");
-  if (int rc = check_steps_window(w, window)) return rc;
+  if (int rc = check_delay_window(w, window)) return rc;
   const uint32_t R = std::min<uint32_t>(window / 4, 1024);
-  if (int rc = check_gain_mode(w, mode, max_gain_db)) return rc;
-  if (int rc = check_max_lag(w, max_lag)) return rc;
-  if (int rc = check_level(w, level_db)) return rc;
-  if (int rc = check_pair_args(w, c, channels, rate, ref, n_ref, test, n_test, out, true)) return rc;
-  if (gain) std::memset(gain, 0, sizeof *gain);
-  const bool match = (mode & 0xF) != PEAQ_GAIN_OFF;
-  // 1, 2: upload, rate conversion
+  // 1 .. 3: upload, rate conversion, estimate
   PairBuffers in;
-  if (int rc = upload_pair_48k(c, channels, rate, ref, n_ref, test, n_test, in)) return rc;
+  peaq_delay rec;
+  uint32_t W = 0;
+  if (int rc = begin_delay_pair(w, c, channels, level_db, rate, max_lag, window, mode, max_gain_db, ref, n_ref, test, n_test,
+                                delay, gain, out, in, &rec, &W))
+    return rc;
   const uint32_t* len = in.len;
   const size_t stride = in.stride;
-  // 3, 4: estimate, the track, its steps
-  DevBuf cut[2], matched, d_dl, d_sb, d_gain;
-  peaq_delay rec;
-  if (int rc = estimate_one_delay(c, channels, in, max_lag, &rec)) return rc;
-  if (delay) *delay = rec;
-  const uint32_t W = peaq_drift_windows(rec.lag, len[0], len[1], window);
-  if (W > PEAQ_DRIFT_MAX_WINDOWS)
-    return fail(PEAQ_ERR_ARG, w + ": " + std::to_string(W) + " windows of " + std::to_string(window) + " samples are more than " +
-                                  std::to_string(PEAQ_DRIFT_MAX_WINDOWS) + ": take a longer window");
+  // 4: the track, its steps
+  DevBuf d_dl, d_sb;
   const uint32_t n_seg = std::max<uint32_t>(W, 2) - 1, stride_p = 2 * n_seg;
   std::vector<double> knots(std::max<uint32_t>(W, 1)), pa(stride_p, 0.), pe(stride_p, 0.);
   std::vector<uint32_t> pb(stride_p, 0);
@@ -821,37 +710,13 @@ extern "C" int peaq_run_pair_steps(peaq_ctx* c, int advanced, int channels, doub
   if (track) *track = tr;
   if (pieces) *pieces = pc;
   if (steps) std::copy(found.begin(), found.begin() + std::min(max_steps, pc.n_candidates), steps);
-  // 5, 6: plain cut of the reference, pieces cut of the test signal
+  // 5 .. 8: both signals cut to the pieces' lengths, the test signal along the pieces; the gain; the score
   uint32_t skip[2], keep = 0;
   peaq_pieces_lengths(rec.lag, pc.n_pieces, pb.data(), pa.data(), pe.data(), len[0], len[1], &skip[0], &skip[1], &keep);
-  size_t cstride = std::max<size_t>(keep, 2);
-  cstride += cstride & 1;
-  const size_t cbytes = cstride * channels * sizeof(float);
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(cut[i].reserve(cbytes));
-    HIP_TRY(hipMemset(cut[i].p, 0, cbytes));
-  }
-  if (int rc = peaq_batch_cut(c, channels, 1, in.d(0), stride, &skip[0], &keep, cut[0].as<float>(), cstride, nullptr)) return rc;
-  if (int rc = peaq_batch_cut_pieces(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &keep, &pc.n_pieces, stride_p, pb.data(),
-                                     pa.data(), pe.data(), cut[1].as<float>(), cstride, nullptr))
-    return rc;
-  const float* scored = cut[1].as<float>();
-  // 7: the gain of the RESAMPLED test signal, applied into a second buffer
-  if (match) {
-    const uint32_t zero = 0;
-    HIP_TRY(d_gain.reserve(sizeof(peaq_gain)));
-    HIP_TRY(matched.reserve(cbytes));
-    HIP_TRY(hipMemset(matched.p, 0, cbytes));
-    if (int rc = peaq_batch_measure_gain(c, channels, 1, cut[0].as<float>(), cstride, &zero, cut[1].as<float>(), cstride, &zero,
-                                         &keep, mode, max_gain_db, d_gain.as<peaq_gain>(), nullptr))
-      return rc;
-    if (int rc = peaq_batch_cut_scaled(c, channels, 1, cut[1].as<float>(), cstride, &zero, &keep, d_gain.as<peaq_gain>(),
-                                       matched.as<float>(), cstride, nullptr))
-      return rc;
-    scored = matched.as<float>();
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (match && gain) HIP_TRY(hipMemcpy(gain, d_gain.p, sizeof(peaq_gain), hipMemcpyDeviceToHost));
-  // 8: the one-pair path
-  return score_one_pair(c, advanced, channels, level_db, cut[0].as<float>(), scored, cstride, keep, keep, out);
+  return score_cut_pair(c, advanced, channels, level_db, in, skip, keep, mode, max_gain_db, gain,
+                        [&](float* d_out, size_t out_stride) {
+                          return peaq_batch_cut_pieces(c, channels, 1, in.d(1), stride, &len[1], &skip[1], &keep, &pc.n_pieces,
+                                                       stride_p, pb.data(), pa.data(), pe.data(), d_out, out_stride, nullptr);
+                        },
+                        out);
 }

@@ -132,6 +132,8 @@ def test_cut_drift_against_the_numpy_sum(channels):
     cases.append((3.73e-5, 0.49, 4000, 40, None))       # 256 (a + e i) passes 127.5 at i = 215: the wrap, m steps to 1
     cases.append((-1e-3, 0.0, 300, 7, 20))              # n_in = 20 + 7: taps before sample 0 and behind the end
     cases.append((1e-3, -3.0, 50, 3, 50))               # outputs centred before the signal's first sample
+    cases.append((-1e-3, 17.5, 1023, 40, None))         # one output short of a tile
+    cases.append((1e-3, -0.37, 0, 40, None))            # nothing kept, beside the long pairs: the sentinel stays
     in_stride = 40000 + 40 + 25
     x = rng.standard_normal((len(cases), in_stride, channels)).astype(np.float32)
     skip = np.array([c[3] for c in cases], np.uint32)
@@ -147,6 +149,9 @@ def test_cut_drift_against_the_numpy_sum(channels):
     worst = 0.0
     for p, c in enumerate(cases):
         k = int(keep[p])
+        if k == 0:
+            assert (got[p] == sentinel).all(), (p, c)
+            continue
         want, m, phi = drift_model(x[p], int(n_in[p]), int(skip[p]), k, float(a[p]), float(e[p]))
         if c[:2] == (3.73e-5, 0.49):
             j = int(np.argmax(m == 1))

@@ -270,11 +270,14 @@ def jump_cases():
     Pair 0: a breakpoint at a tile border (1024) and in the middle of a tile (1500); three pieces inside one tile (2100,
     2101, 2106: pieces of 1, 5 and 300 outputs); jumps of +5000 and -5000; a piece at 1/64 beside one at -1/64.
     Pair 1: a first piece that reads before the signal's start (a = -59 at skip 0) and a breakpoint three outputs before
-    the pair's end.  Pair 2: one piece, the signal ending inside the last outputs' taps."""
+    the pair's end.  Pair 2: one piece, the signal ending inside the last outputs' taps.  Pair 3: one output short of a
+    tile, breakpoints at 1 and at n_keep - 1.  Pair 4: nothing kept, beside the long pairs."""
     return [([0, 1024, 1500, 2100, 2101, 2106, 2406, 4000], [0.3, 5000.25, 0.75, -4999.5, 17.5, -3.75, 90.25, 26.25],
              [1e-3, -1e-3, 3.73e-5, 0.0, 0.0, MAX_E, MAX_E, -MAX_E], 5200, 6003, 22),
             ([0, 700, 2997], [-59.0, 12.5, 4000.0], [MAX_E, -MAX_E, 0.0], 0, 3000, 22),
-            ([0], [0.3], [1e-3], 7, 2997, 9)]
+            ([0], [0.3], [1e-3], 7, 2997, 9),
+            ([0, 1, 1022], [0.3, 7.25, -2.5], [1e-3, 0.0, -MAX_E], 40, 1023, 22),
+            ([0], [0.3], [1e-3], 40, 0, 22)]
 
 
 @pytest.mark.parametrize("channels", [1, 2])
@@ -293,7 +296,7 @@ def test_cut_pieces_against_the_numpy_sum(channels):
         b[p, :len(pb)], a[p, :len(pa)], e[p, :len(pe)], n_pc[p] = pb, pa, pe, len(pb)
     skip = np.array([c[3] for c in cases], np.uint32)
     keep = np.array([c[4] for c in cases], np.uint32)
-    last_m = [int(sc.pieces_indices(b[p, :n_pc[p]], a[p, :n_pc[p]], e[p, :n_pc[p]], np.array([int(keep[p]) - 1]))[0][0]) for p in range(n)]
+    last_m = [int(sc.pieces_indices(b[p, :n_pc[p]], a[p, :n_pc[p]], e[p, :n_pc[p]], np.array([max(int(keep[p]), 1) - 1]))[0][0]) for p in range(n)]
     n_in = np.array([int(skip[p]) + int(keep[p]) + last_m[p] + cases[p][5] for p in range(n)], np.uint32)
     n_in[1] = 3000 + 2000                               # pair 1: its last piece, 4000 ahead, reads past the end
     x = rng.standard_normal((n, max(int(n_in.max()), int((skip + keep).max())) + 1, channels)).astype(np.float32)
@@ -305,6 +308,9 @@ def test_cut_pieces_against_the_numpy_sum(channels):
     worst = 0.0
     for p in range(n):
         k = int(keep[p])
+        if k == 0:
+            assert (got[p] == sentinel).all(), p                                    # nothing kept: the sentinel stays
+            continue
         pb, pa, pe = b[p, :n_pc[p]], a[p, :n_pc[p]], e[p, :n_pc[p]]
         want, m, phi, piece = sc.pieces_model(x[p], int(n_in[p]), int(skip[p]), k, pb, pa, pe)
         assert set(piece) == set(range(n_pc[p])), (p, set(piece))                   # every piece is met

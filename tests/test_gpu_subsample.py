@@ -75,6 +75,7 @@ def test_cut_shifted_against_the_numpy_sum(channels):
     assert h_abs < 4.2 and 65 * 2.0 ** -53 * h_abs <= SUM_BOUND, h_abs
     rng = np.random.default_rng(40 + channels)
     cases = [(keep, skip, extra) for keep in KEEPS for skip in SKIPS for extra in (0, 40)]
+    cases.append((0, 33, 40))                           # nothing kept, beside the long pairs: the sentinel stays
     qs = np.array([QS[i % len(QS)] for i in range(len(cases))], np.int32)
     in_stride = max(KEEPS) + max(SKIPS) + 40 + 1
     in_stride += 1 - (in_stride & 1)                    # odd
@@ -91,6 +92,9 @@ def test_cut_shifted_against_the_numpy_sum(channels):
     got = out.cpu().numpy()
     worst = 0.0
     for p, (k, s, extra) in enumerate(cases):
+        if k == 0:
+            assert (got[p] == sentinel).all(), (p, s)
+            continue
         want = shifted_model(x[p], int(n_in[p]), s, k, int(qs[p]))
         tol = 2.0 ** -23 * np.abs(want) + SUM_BOUND * np.abs(x[p]).max() + 1.5e-45
         err = np.abs(got[p, :k].astype(np.float64) - want)

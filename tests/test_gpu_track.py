@@ -165,15 +165,22 @@ def sum_cases():
             ([0.3, 0.3 + 1e-3 * SUM_WINDOW], 7, 10997, 9)]                         # 1 segment; the signal ends inside the last taps
 
 
+def edge_cases():
+    """as sum_cases, for the numpy sum alone: the tests that chain the cuts bit for bit keep sum_cases' three pairs"""
+    return [([17.5, 17.5 - 1e-3 * SUM_WINDOW], 40, 1023, 22),                      # one output short of a tile
+            ([0.3, 0.3 + 1e-3 * SUM_WINDOW], 40, 0, 22)]                           # nothing kept, beside the long pairs
+
+
 @pytest.mark.parametrize("channels", [1, 2])
 def test_cut_track_against_the_numpy_sum(channels):
-    """one call of 3 pairs of 3, 2 and 1 segments, window 5001; slopes +1/64 and -1/64 on the two sides of one knot, a
-    negative a with skip = 0, an n_in that ends inside the last outputs' taps; every sample compared, the sentinel
-    behind n_keep kept.  The kernel's staged index, restated in numpy, stays inside 0 .. 19 for every output."""
+    """one call of pairs of 3, 2 and 1 segments, window 5001; slopes +1/64 and -1/64 on the two sides of one knot, a
+    negative a with skip = 0, an n_in that ends inside the last outputs' taps, a pair of 1023 outputs and one of none;
+    every sample compared, the sentinel behind n_keep kept.  The kernel's staged index, restated in numpy, stays inside
+    0 .. 19 for every output."""
     import gstpeaq_amd
     import torch
     rng = np.random.default_rng(60 + channels)
-    cases = sum_cases()
+    cases = sum_cases() + edge_cases()
     n = len(cases)
     a, e = np.zeros((n, 3)), np.zeros((n, 3))
     n_seg = np.zeros(n, np.uint32)
@@ -184,7 +191,7 @@ def test_cut_track_against_the_numpy_sum(channels):
     assert e[0, 0] == -MAX_E and e[0, 1] == MAX_E and e[1, 0] == MAX_E and e[1, 1] < 0 and a[1, 0] < -50
     skip = np.array([c[1] for c in cases], np.uint32)
     keep = np.array([c[2] for c in cases], np.uint32)
-    last_m = [int(track_indices(SUM_WINDOW, a[p, :n_seg[p]], e[p, :n_seg[p]], np.array([int(keep[p]) - 1]))[0][0]) for p in range(n)]
+    last_m = [int(track_indices(SUM_WINDOW, a[p, :n_seg[p]], e[p, :n_seg[p]], np.array([max(int(keep[p]), 1) - 1]))[0][0]) for p in range(n)]
     n_in = np.array([int(skip[p]) + int(keep[p]) + last_m[p] + cases[p][3] for p in range(n)], np.uint32)
     in_stride = int(n_in.max()) + 1
     x = rng.standard_normal((n, in_stride, channels)).astype(np.float32)
@@ -196,6 +203,9 @@ def test_cut_track_against_the_numpy_sum(channels):
     worst = 0.0
     for p in range(n):
         k = int(keep[p])
+        if k == 0:
+            assert (got[p] == sentinel).all(), p                                    # nothing kept: the sentinel stays
+            continue
         pa, pe = a[p, :n_seg[p]], e[p, :n_seg[p]]
         want, m, phi, seg = track_model(x[p], int(n_in[p]), int(skip[p]), k, SUM_WINDOW, pa, pe)
         assert set(seg) == set(range(n_seg[p])), (p, set(seg))                      # every segment is met

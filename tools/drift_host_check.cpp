@@ -1,6 +1,6 @@
 // drift_host_check.cpp -- the host arithmetic of the drift stage (gstpeaq_amd/csrc/peaq_drift_math.h: drift_index,
-// drift_keep, theil_sen, what peaq_drift_index / peaq_drift_lengths / peaq_drift_fit wrap) on its own, for the
-// sanitizers: no device runtime, no library.
+// drift_keep, theil_sen, what peaq_drift_index / peaq_drift_lengths / peaq_drift_fit wrap, and window_delays) on its
+// own, for the sanitizers: no device runtime, no library.
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o drift_host_check drift_host_check.cpp
 //   ./drift_host_check        (prints "drift_host_check ok", exit status 0)
 #include <cstdio>
@@ -95,6 +95,20 @@ int main() {
     double a, e;
     CHECK(theil_sen(d.data(), x.data(), nullptr, d.size(), &a, &e) == 4096);
     CHECK(std::fabs(e - 1. / 16384) < 1e-9 && std::fabs(a + 2.) < 1e-3);
+  }
+  {
+    // the windows' delays and which of them count, on records laid out here (the library's are peaq_delay, peaq_subdelay)
+    struct Delay { int lag; double peak, norm; };
+    struct Sub { int q; unsigned flags; };
+    const Delay dl[] = {{37, 0.9, 1.}, {-3, -0.6, 1.}, {5, 0.49, 1.}, {5, 0.5, 1.}, {1, 1., 0.}, {1, 1., NAN}, {2, 3., INFINITY}, {9, 1., 1.}};
+    const Sub sb[] = {{128, 0}, {-64, 0}, {0, 0}, {1, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 1}};
+    const uint8_t want[] = {1, 1, 0, 1, 0, 0, 0, 0};    // below min_corr; no energy; NaN; Inf; flagged by the refinement
+    double d[8];
+    uint8_t valid[8];
+    window_delays(dl, sb, 8, 0.5, d, valid);
+    for (int w = 0; w < 8; ++w) CHECK(valid[w] == want[w]);
+    CHECK(d[0] == 37.5 && d[1] == -3.25 && d[3] == 5. + 1. / 256);
+    window_delays(dl, sb, 0, 0.5, nullptr, nullptr);   // no window: nothing is touched
   }
   if (failures) return 1;
   std::puts("drift_host_check ok");
