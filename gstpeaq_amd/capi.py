@@ -242,6 +242,27 @@ class MeterReading(C.Structure):
 METER_MAX_OPEN, METER_MAX_DEPTH = 64, 4096
 
 
+class LiveAlignConfig(C.Structure):
+    """peaq_live_align_config: acquisition (max_lag, probe in samples) and watch (watch_frames in FFT frames)"""
+    _fields_ = [("max_lag", C.c_uint32), ("probe", C.c_uint32), ("watch_frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LiveDelay(C.Structure):
+    """peaq_live_delay"""
+    _fields_ = [("acquired", C.c_int32), ("probe_ref", C.c_uint32), ("probe_test", C.c_uint32), ("skip_ref", C.c_uint32),
+                ("skip_test", C.c_uint32), ("reserved", C.c_uint32), ("d", Delay)]
+
+
+WATCH_LAGS = 31
+
+
+class DelayWatch(C.Structure):
+    """peaq_delay_watch"""
+    _fields_ = [("index", C.c_uint64), ("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("offset", C.c_int32),
+                ("reserved", C.c_int32), ("peak", C.c_double), ("runner_up", C.c_double), ("norm", C.c_double),
+                ("e_ref", C.c_double), ("e_test", C.c_double), ("c", C.c_double * (2 * WATCH_LAGS + 1))]
+
+
 class _BrokerStats(C.Structure):
     _fields_ = [("ticks", C.c_uint64), ("launches", C.c_uint64), ("frames", C.c_uint64),
                 ("max_active", C.c_uint32), ("worker_failed", C.c_uint32),
@@ -387,6 +408,25 @@ def load_library():
         if L.peaq_meter_reading_size() != C.sizeof(MeterReading):
             raise PeaqError(f"peaq_meter_reading is {L.peaq_meter_reading_size()} bytes in the library, "
                             f"{C.sizeof(MeterReading)} in this binding")
+    if hasattr(L, "peaq_session_set_align"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        i32p = C.POINTER(C.c_int32)
+        L.peaq_live_delay_size.restype = C.c_size_t
+        L.peaq_live_delay_size.argtypes = []
+        L.peaq_delay_watch_size.restype = C.c_size_t
+        L.peaq_delay_watch_size.argtypes = []
+        L.peaq_live_align_plan.argtypes = [C.POINTER(LiveAlignConfig), C.c_uint64, C.c_uint64, C.c_int32, u32p, u32p, u32p,
+                                           u32p]
+        L.peaq_delay_watch_pick.argtypes = [dp, C.c_double, C.c_double, i32p, dp, dp, dp]
+        L.peaq_session_set_align.argtypes = [vp, C.POINTER(LiveAlignConfig)]
+        L.peaq_session_align_read.argtypes = [vp, C.POINTER(LiveDelay)]
+        L.peaq_session_watch_read.argtypes = [vp, C.POINTER(DelayWatch)]
+        L.peaq_broker_set_align.argtypes = [vp, C.POINTER(LiveAlignConfig)]
+        L.peaq_broker_align_read.argtypes = [vp, C.c_int, C.POINTER(LiveDelay)]
+        L.peaq_broker_watch_read.argtypes = [vp, C.c_int, C.POINTER(DelayWatch)]
+        for what, size, mirror in (("peaq_live_delay", L.peaq_live_delay_size(), LiveDelay),
+                                   ("peaq_delay_watch", L.peaq_delay_watch_size(), DelayWatch)):
+            if size != C.sizeof(mirror):
+                raise PeaqError(f"{what} is {size} bytes in the library, {C.sizeof(mirror)} in this binding")
     if hasattr(L, "peaq_batch_run_fb_band_summary"):   # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_fb_band_summary_rows.argtypes = []
         L.peaq_fb_band_summary_row.argtypes = []
@@ -609,6 +649,44 @@ def meter_windows(n_ref, n_test, window, hop=None):
     return [_meter_dict(rows[i]) for i in range(n.value)]
 
 
+def _align_config(max_lag, probe, watch):
+    return LiveAlignConfig(int(max_lag or 0), int(probe or 0), int(watch or 0), 0)
+
+
+def _live_delay_dict(d):
+    return dict(acquired=bool(d.acquired), probe_ref=int(d.probe_ref), probe_test=int(d.probe_test),
+                skip_ref=int(d.skip_ref), skip_test=int(d.skip_test), lag=int(d.d.lag), peak=float(d.d.peak),
+                runner_up=float(d.d.runner_up), norm=float(d.d.norm))
+
+
+def _watch_dict(w):
+    if not w.n_frames:
+        return None
+    return dict(index=int(w.index), first_frame=int(w.first_frame), n_frames=int(w.n_frames), offset=int(w.offset),
+                peak=float(w.peak), runner_up=float(w.runner_up), norm=float(w.norm), e_ref=float(w.e_ref),
+                e_test=float(w.e_test), c=np.array(w.c[:]))
+
+
+def live_align_plan(max_lag, have_ref, have_test, lag, probe=None):
+    """peaq_live_align_plan: (probe_ref, probe_test, skip_ref, skip_test) of rule A for what the pads hold and a lag.
+    Host arithmetic only."""
+    cfg = _align_config(max_lag, probe, 0)
+    out = [C.c_uint32(0) for _ in range(4)]
+    _check(load_library().peaq_live_align_plan(C.byref(cfg), int(have_ref), int(have_test), int(lag),
+                                               *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
+
+
+def delay_watch_pick(c, e_ref, e_test):
+    """peaq_delay_watch_pick: dict of offset, peak, runner_up, norm for a watch window's sums c[d + 31], d = -31 .. 31"""
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    assert c.shape == (2 * WATCH_LAGS + 1,)
+    offset, out = C.c_int32(0), [C.c_double(0) for _ in range(3)]
+    _check(load_library().peaq_delay_watch_pick(c.ctypes.data_as(C.POINTER(C.c_double)), float(e_ref), float(e_test),
+                                                C.byref(offset), *[C.byref(o) for o in out]))
+    return dict(offset=offset.value, peak=out[0].value, runner_up=out[1].value, norm=out[2].value)
+
+
 class Context:
     """One per process and GPU: owns the constant tables in HBM."""
 
@@ -741,6 +819,28 @@ class Session:
         _check(self.L.peaq_session_meter_read(self.h, rows, int(cap), C.byref(n), C.byref(dropped)))
         return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
 
+    def set_align(self, max_lag, probe=None, watch=None):
+        """peaq_session_set_align: hold the stream until both pads have `probe` samples (default 48000 + 2 max_lag),
+        find the delay within +-max_lag and drop the early pad's head (max_lag 0 or None: no acquisition); watch the
+        delay over tumbling windows of `watch` FFT frames (0 or None: no watch; meter_frames converts seconds).  Before
+        the first push or right after reset() only."""
+        cfg = _align_config(max_lag, probe, watch)
+        _check(self.L.peaq_session_set_align(self.h, C.byref(cfg)))
+
+    def align_read(self):
+        """peaq_session_align_read: dict of acquired (False while the stream holds), probe_ref, probe_test, skip_ref,
+        skip_test and the aligner's lag, peak, runner_up, norm"""
+        d = LiveDelay()
+        _check(self.L.peaq_session_align_read(self.h, C.byref(d)))
+        return _live_delay_dict(d)
+
+    def watch_read(self):
+        """peaq_session_watch_read: the newest complete watch window as a dict (index, first_frame, n_frames, offset,
+        peak, runner_up, norm, e_ref, e_test, c: array of 63), or None while no window is complete"""
+        w = DelayWatch()
+        _check(self.L.peaq_session_watch_read(self.h, C.byref(w)))
+        return _watch_dict(w)
+
     def close(self):
         if self.h:
             self.L.peaq_session_destroy(self.h)
@@ -824,6 +924,26 @@ class Broker:
         n, dropped = C.c_int(0), C.c_uint64(0)
         _check(self.L.peaq_broker_meter_read(self.h, int(sid), rows, cap, C.byref(n), C.byref(dropped)))
         return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
+
+    def set_align(self, max_lag, probe=None, watch=None):
+        """peaq_broker_set_align: one configuration for all sessions of the broker (see Session.set_align), before the
+        first open() and before start()"""
+        cfg = _align_config(max_lag, probe, watch)
+        _check(self.L.peaq_broker_set_align(self.h, C.byref(cfg)))
+
+    def align_read(self, sid):
+        """the delay of session sid, as Session.align_read (peaq_broker_align_read): as of the last tick; a session
+        that still holds with its flush requested is ticked until it is acquired"""
+        d = LiveDelay()
+        _check(self.L.peaq_broker_align_read(self.h, int(sid), C.byref(d)))
+        return _live_delay_dict(d)
+
+    def watch_read(self, sid):
+        """the newest complete watch window of session sid, as Session.watch_read (peaq_broker_watch_read): as of the
+        last tick; no tick is forced"""
+        w = DelayWatch()
+        _check(self.L.peaq_broker_watch_read(self.h, int(sid), C.byref(w)))
+        return _watch_dict(w)
 
     def start(self, period_us=2000):
         _check(self.L.peaq_broker_start(self.h, int(period_us)))

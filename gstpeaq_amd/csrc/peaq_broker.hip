@@ -24,7 +24,9 @@ constexpr unsigned kBrokerMaxBlocks = 48;    // filter-bank blocks one session c
 constexpr size_t kBrokerStageSamples = (size_t)(kBrokerMaxFrames - 1) * kHop + kFrame;
 constexpr size_t kBrokerFbStageSamples = (size_t)kBrokerMaxBlocks * kFbFrame;
 constexpr size_t kBrokerRowStride = (size_t)kFbRing + kBrokerFbStageSamples;
-constexpr size_t kMetaRows = 10;          // rows of h_meta; the last three are uploaded with the meter on only
+constexpr size_t kMetaRows = 11;          // rows of h_meta; rows 7 .. 9 are uploaded with the meter or the watch on only,
+                                          // row 10 with the watch on only
+constexpr unsigned kBrokerAcquirePerTick = 8;   // live alignment: slots whose delay estimate one tick enqueues
 // back-pressure: a push returns only once its session has no more than this many samples that are
 // READY to be framed (present on both pads) and not yet launched -- four ticks' worth.  Samples one
 // pad holds ahead of the other are never counted: like the reference's adapters they may pile up
@@ -38,6 +40,17 @@ struct BrokerSlot {
   StreamFramer framer;              // the two pads' FIFOs and where the next frame / block starts
   double t_ready_us = -1.;          // when the oldest not yet launched frame / block became whole (-1: none waiting)
   MeterStream meter;                // the slot's meter (peaq_broker_set_meter), fresh at every open
+  // live alignment (peaq_broker_set_align): the framer is held until the delay is acquired
+  peaq_live_delay delay{};          // all zero while the stream holds
+  bool acquiring = false;           // the estimate over this slot's probes is enqueued: the next tick reads it
+  uint64_t epoch = 0;               // counts opens and closes: an estimate enqueued for an earlier stream is dropped
+};
+
+// an estimate a tick has enqueued: read by the next tick
+struct BrokerAcquire {
+  int sid = 0;
+  uint64_t epoch = 0;
+  uint64_t have[2] = {0, 0};        // what the pads held when the probes were taken
 };
 
 // microseconds on a monotonic clock (latency bookkeeping of the broker)
@@ -215,8 +228,21 @@ struct peaq_broker {
   DevBuf m_readout;                 // ResultRecord [ring]
   std::vector<ResultRecord> m_host;
 
+  // live alignment (peaq_broker_set_align; peaq_watch.hip): one configuration for all slots
+  LiveAlignGeometry align;
+  float* a_hprobe[2] = {nullptr, nullptr};   // pinned: this tick's probes [kBrokerAcquirePerTick][probe][channels]
+  DevBuf a_probe[2], a_rec;         // the same on the device; peaq_delay [kBrokerAcquirePerTick]
+  peaq_delay* a_hrec = nullptr;     // pinned: the records of the last tick's estimates
+  std::vector<BrokerAcquire> a_pending;      // the estimates the last tick enqueued
+  DevBuf w_rows, w_state;           // watch: one tick's rows [launch pair][kBrokerMaxFrames][kWatchRow]; WatchState [slot]
+
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
 };
+
+// a held slot whose probe is there, or whose flush has been asked for: the next tick with room estimates its delay
+static inline bool broker_probe_ready(const peaq_broker* b, const BrokerSlot& sl) {
+  return sl.flush_requested || std::min(sl.framer.pad[0].total, sl.framer.pad[1].total) >= b->align.probe;
+}
 
 static inline bool broker_is_multi(const peaq_broker* b) { return b && !b->shards.empty(); }
 // -> the device broker that owns session `sid` of b, and the session's id there
@@ -256,6 +282,23 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     b->staged_pending = false;
     broker_settle_timing(b);
   }
+  // live alignment: the records of the estimates the last tick enqueued are in pinned memory now; their framers are
+  // released, and the streams' first units ride in this tick
+  for (size_t i = 0; i < b->a_pending.size(); ++i) {
+    const BrokerAcquire& q = b->a_pending[i];
+    BrokerSlot& sl = *b->slots[q.sid];
+    std::lock_guard<std::mutex> lock(sl.mu);
+    if (!sl.open || sl.epoch != q.epoch || !sl.acquiring) continue;   // (closed, or closed and opened again, meanwhile)
+    peaq_live_delay d{};
+    live_align_plan(b->align.probe, q.have[0], q.have[1], b->a_hrec[i].lag, &d);
+    static_assert(sizeof d.d == sizeof(peaq_delay), "peaq_live_delay::d mirrors peaq_delay");
+    std::memcpy(&d.d, &b->a_hrec[i], sizeof(peaq_delay));
+    d.acquired = 1;
+    sl.delay = d;
+    sl.acquiring = false;
+    sl.framer.release(d.skip_ref, d.skip_test);
+  }
+  b->a_pending.clear();
   const double t_tick = now_us();
   const size_t S = (size_t)b->max_sessions;
   uint32_t* m_nref = b->h_meta;
@@ -270,6 +313,10 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
   uint32_t* m_tot_f = b->h_meta + 7 * S;
   uint32_t* m_fb_tot_f = b->h_meta + 8 * S;
   uint32_t* m_fb_tot_b = b->h_meta + 9 * S;
+  // the watch's row (uploaded with the watch on only): the whole frames of each FFT pair -- 0 for a flush frame
+  uint32_t* m_wf = b->h_meta + 10 * S;
+  const bool watched = b->align.window != 0;
+  uint32_t acq_n[2][kBrokerAcquirePerTick];          // live alignment: the probe lengths of this tick's estimates
   const bool metered = b->meter.on;
   unsigned fb_closing = 0;                           // sessions whose blocks ended without a flush block (meter: see below)
   unsigned active = 0, max_nf = 0, fb_active = 0, max_nb = 0;
@@ -279,6 +326,34 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     BrokerSlot& sl = *b->slots[sid];
     std::lock_guard<std::mutex> lock(sl.mu);
     if (!sl.open) continue;
+    if (sl.framer.held) {
+      // live alignment: nothing is taken from a held stream.  Once its probe is there (or its flush asked for) and no
+      // estimate of it is under way, its probes are staged, at most kBrokerAcquirePerTick slots a tick; the rest wait.
+      const bool empty_pad = !sl.framer.pad[0].total || !sl.framer.pad[1].total;
+      if (!sl.acquiring && empty_pad && broker_probe_ready(b, sl)) {
+        // (a flush with nothing on a pad: the record the aligner documents for an empty signal, no device work)
+        peaq_live_delay d{};
+        live_align_plan(b->align.probe, sl.framer.pad[0].total, sl.framer.pad[1].total, 0, &d);
+        d.acquired = 1;
+        sl.delay = d;
+        sl.framer.release(0, 0);
+      } else if (!sl.acquiring && b->a_pending.size() < kBrokerAcquirePerTick && broker_probe_ready(b, sl)) {
+        const size_t i = b->a_pending.size();
+        BrokerAcquire q;
+        q.sid = sid;
+        q.epoch = sl.epoch;
+        for (int p = 0; p < 2; ++p) {
+          q.have[p] = sl.framer.pad[p].total;
+          acq_n[p][i] = static_cast<uint32_t>(std::min<uint64_t>(q.have[p], b->align.probe));
+          if (acq_n[p][i])
+            std::memcpy(b->a_hprobe[p] + i * (size_t)b->align.probe * b->channels, sl.framer.pad[p].at(0, b->channels),
+                        (size_t)acq_n[p][i] * b->channels * sizeof(float));
+        }
+        b->a_pending.push_back(q);
+        sl.acquiring = true;
+      }
+      if (sl.framer.held) continue;
+    }
     BrokerJob job;
     job.sid = sid;
     // ---- at most one window per kind: whole units (do_processing), else, once, the zero-padded unit of
@@ -295,6 +370,7 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
       m_nf[active] = job.fft.count;
       m_slot[active] = static_cast<uint32_t>(sid);
       m_tot_f[active] = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;
+      m_wf[active] = job.fft.flush ? 0 : job.fft.count;
       frames += job.fft.count;
       max_nf = std::max(max_nf, job.fft.count);
       ++active;
@@ -349,7 +425,8 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     }
   }
   ++b->n_ticks;
-  if (!active && !fb_active && !fb_closing) return PEAQ_OK;
+  const unsigned n_acq = (unsigned)b->a_pending.size();
+  if (!active && !fb_active && !fb_closing && !n_acq) return PEAQ_OK;
   for (unsigned i = 0; i < fb_closing; ++i) {        // the entries without units: behind the tick's own
     const unsigned at = (unsigned)S - 1 - i, to = fb_active + i;
     b->h_win[to] = b->h_win[at];
@@ -368,7 +445,7 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     sl.framer.trim();
   });
   HIP_TRY(hipEventRecord(b->t_begin, b->stream));
-  HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, (metered ? kMetaRows : 7) * S * sizeof(uint32_t), hipMemcpyHostToDevice,
+  HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, (watched ? kMetaRows : metered ? 10 : 7) * S * sizeof(uint32_t), hipMemcpyHostToDevice,
                          b->stream));
   // the meter's launches: the live back ends leave this tick's records at [launch index][unit of the tick], and one
   // small kernel behind each back end walks every session's units through its open windows
@@ -409,6 +486,21 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     fa.frames_per_launch = max_nf;
     fa.records = b->records.as<double>();
     HIP_TRY(launch_frontend(m.fft_bands(), fa, active, b->stream));
+    if (watched) {
+      WatchArgs wa{};
+      wa.ref = fa.ref;
+      wa.test = fa.test;
+      wa.pair_stride = fa.pair_stride;
+      wa.channels = b->channels;
+      wa.n_frames = max_nf;
+      wa.window = b->align.window;
+      wa.rows = b->w_rows.as<double>();
+      wa.row_stride = kBrokerMaxFrames;
+      wa.state = b->w_state.as<WatchState>();
+      wa.s_frames = d_meta + 10 * S;
+      wa.s_slot = d_meta + 4 * S;
+      HIP_TRY(launch_delay_watch(wa, active, b->stream));
+    }
     BackendArgs ba = m.backend(fa);
     ba.frames_per_launch = max_nf;
     ba.state = b->state.as<PairState>();
@@ -457,6 +549,18 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     mb.s_total_frames = d_meta + 8 * S;
     mb.s_total_units = d_meta + 9 * S;
     HIP_TRY(launch_meter_fb(mb, b->channels, fb_active + fb_closing, b->stream));
+  }
+  if (n_acq) {
+    // live alignment: one estimate over this tick's probes, its records copied to pinned memory -- enqueued, not waited
+    // for: the next tick reads them after its wait for `staged`
+    const size_t row = (size_t)b->align.probe * b->channels;
+    for (int p = 0; p < 2; ++p)
+      HIP_TRY(hipMemcpyAsync(b->a_probe[p].p, b->a_hprobe[p], n_acq * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    if (int rc = peaq_batch_estimate_delay(c, b->channels, (int)n_acq, b->a_probe[0].as<float>(), b->a_probe[1].as<float>(),
+                                           b->align.probe, acq_n[0], acq_n[1], 0, b->align.max_lag,
+                                           b->a_rec.as<peaq_delay>(), b->stream))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(b->a_hrec, b->a_rec.p, n_acq * sizeof(peaq_delay), hipMemcpyDeviceToHost, b->stream));
   }
   HIP_TRY(hipEventRecord(b->t_end, b->stream));
   HIP_TRY(hipEventRecord(b->staged, b->stream));
@@ -633,6 +737,9 @@ extern "C" void peaq_broker_destroy(peaq_broker* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->h_meta) (void)hipHostFree(b->h_meta);
   if (b->h_win) (void)hipHostFree(b->h_win);
+  for (int p = 0; p < 2; ++p)
+    if (b->a_hprobe[p]) (void)hipHostFree(b->a_hprobe[p]);
+  if (b->a_hrec) (void)hipHostFree(b->a_hrec);
   if (b->staged) (void)hipEventDestroy(b->staged);
   if (b->t_begin) (void)hipEventDestroy(b->t_begin);
   if (b->t_end) (void)hipEventDestroy(b->t_end);
@@ -681,10 +788,16 @@ extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
       HIP_TRY(launch_points_init(b->m_open.as<PointSnap>() + (size_t)sid * b->meter.k_open, b->meter.k_open, b->stream));
       HIP_TRY(launch_points_init(b->m_ring.as<PointSnap>() + (size_t)sid * b->meter.ring, b->meter.ring, b->stream));
     }
+    if (b->align.window)                               // a fresh watch: index 0, nothing complete
+      HIP_TRY(hipMemsetAsync(b->w_state.as<WatchState>() + sid, 0, sizeof(WatchState), b->stream));
     sl.meter = MeterStream();
     sl.open = true;
     sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
     sl.framer.reset(b->advanced, b->channels);
+    sl.delay = peaq_live_delay{};
+    sl.acquiring = false;
+    ++sl.epoch;
+    if (b->align.max_lag) sl.framer.hold();
     sl.t_ready_us = -1.;
     *session_id = sid;
     return PEAQ_OK;
@@ -716,6 +829,8 @@ extern "C" int peaq_broker_close(peaq_broker* b, int session_id) {
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_close: session is not open");
   sl->open = false;
   sl->framer.reset(b->advanced, b->channels);
+  sl->acquiring = false;
+  ++sl->epoch;
   return PEAQ_OK;
 }
 
@@ -732,9 +847,13 @@ extern "C" int peaq_broker_push(peaq_broker* b, int session_id, int pad, const f
   if (b->failed.load()) return broker_failed(b, "peaq_broker_push");
   if (n == 0) return PEAQ_OK;
   if (!data) return fail(PEAQ_ERR_ARG, "peaq_broker_push: data is NULL");
+  // (a held stream's samples up to the probe do not count: they cannot go before the probe is there, and a push must
+  // be able to bring it)
   auto backlog = [&]() {
     std::lock_guard<std::mutex> lock(sl->mu);
-    return sl->framer.backlog();
+    const uint64_t waiting = sl->framer.backlog();
+    if (!sl->framer.held) return waiting;
+    return waiting > b->align.probe ? waiting - b->align.probe : 0;
   };
   {
     std::lock_guard<std::mutex> lock(sl->mu);
@@ -804,8 +923,10 @@ extern "C" int peaq_broker_tick(peaq_broker* b, unsigned* n_active) {
 }
 
 // true while the session has whole frames / blocks (or a requested flush) not yet launched
-static bool broker_slot_busy(BrokerSlot* sl) {
+// (a held stream: only once its probe is there -- ticks then acquire its delay, release it and go on)
+static bool broker_slot_busy(const peaq_broker* b, BrokerSlot* sl) {
   std::lock_guard<std::mutex> lock(sl->mu);
+  if (sl->framer.held) return sl->acquiring || broker_probe_ready(b, *sl);
   return sl->framer.ready() || sl->flush_requested;
 }
 
@@ -823,7 +944,7 @@ extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* 
     if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_results: session is not open");
   }
   if (b->failed.load()) return broker_failed(b, "peaq_broker_results");
-  while (broker_slot_busy(sl)) {
+  while (broker_slot_busy(b, sl)) {
     const int rc = broker_tick_checked(b, nullptr);
     if (rc != PEAQ_OK) return rc;
   }
@@ -874,6 +995,110 @@ extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cf
   }
   b->meter = g;
   b->meter.on = true;
+  return PEAQ_OK;
+}
+
+// One configuration for all sessions of the broker, where peaq_broker_set_meter is accepted.
+extern "C" int peaq_broker_set_align(peaq_broker* b, const peaq_live_align_config* cfg) {
+  const std::string who("peaq_broker_set_align");
+  if (!b) return fail(PEAQ_ERR_ARG, who + ": broker is NULL");
+  const bool off = !cfg || (cfg->max_lag == 0 && cfg->watch_frames == 0);
+  uint32_t probe = 0;
+  if (cfg)
+    if (int rc = check_live_align(who, *cfg, &probe)) return rc;
+  if (broker_is_multi(b)) {                            // every shard
+    for (peaq_broker* sh : b->shards)
+      if (int rc = peaq_broker_set_align(sh, cfg)) return rc;
+    return PEAQ_OK;
+  }
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (b->running.load())
+    return fail(PEAQ_ERR_ARG, who + ": the tick thread runs; set the alignment before peaq_broker_start");
+  for (int sid = 0; sid < b->max_sessions; ++sid) {
+    std::lock_guard<std::mutex> lock(b->slots[sid]->mu);
+    if (b->slots[sid]->open)
+      return fail(PEAQ_ERR_ARG, who + ": session " + std::to_string(sid) +
+                                    " is open; set the alignment before the first peaq_broker_open");
+  }
+  b->align = LiveAlignGeometry();
+  if (off) return PEAQ_OK;
+  const size_t S = (size_t)b->max_sessions;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
+  if (cfg->max_lag) {
+    const size_t bytes = (size_t)kBrokerAcquirePerTick * probe * b->channels * sizeof(float);
+    for (int p = 0; p < 2; ++p) {
+      if (b->a_hprobe[p]) (void)hipHostFree(b->a_hprobe[p]);
+      b->a_hprobe[p] = nullptr;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->a_hprobe[p]), bytes, hipHostMallocDefault));
+      HIP_TRY(b->a_probe[p].reserve(bytes));
+    }
+    HIP_TRY(b->a_rec.reserve(kBrokerAcquirePerTick * sizeof(peaq_delay)));
+    if (!b->a_hrec)
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->a_hrec), kBrokerAcquirePerTick * sizeof(peaq_delay),
+                            hipHostMallocDefault));
+  }
+  if (cfg->watch_frames) {
+    HIP_TRY(b->w_rows.reserve(S * kBrokerMaxFrames * kWatchRow * sizeof(double)));
+    HIP_TRY(b->w_state.reserve(S * sizeof(WatchState)));
+  }
+  b->align.max_lag = cfg->max_lag;
+  b->align.probe = probe;
+  b->align.window = cfg->watch_frames;
+  return PEAQ_OK;
+}
+
+// The slot's delay as of the last tick enqueued.  A slot that still holds with its flush asked for is driven to its
+// acquisition, as peaq_broker_results drives a session to its end.
+extern "C" int peaq_broker_align_read(peaq_broker* b, int session_id, peaq_live_delay* out) {
+  if (!b || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_align_read: NULL argument");
+  if (broker_is_multi(b)) {
+    int local;
+    peaq_broker* sh = broker_shard_of(b, session_id, &local);
+    return sh ? peaq_broker_align_read(sh, local, out) : fail(PEAQ_ERR_ARG, "peaq_broker_align_read: bad session id");
+  }
+  BrokerSlot* sl = broker_slot(b, session_id);
+  if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_align_read: bad session id " + std::to_string(session_id));
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (!b->align.max_lag)
+    return fail(PEAQ_ERR_ARG, "peaq_broker_align_read: no acquisition is set (peaq_broker_set_align, max_lag)");
+  if (b->failed.load()) return broker_failed(b, "peaq_broker_align_read");
+  for (;;) {
+    {
+      std::lock_guard<std::mutex> lock(sl->mu);
+      if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_align_read: session is not open");
+      if (!(sl->framer.held && sl->flush_requested)) break;
+    }
+    if (int rc = broker_tick_checked(b, nullptr)) return rc;
+  }
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  std::lock_guard<std::mutex> lock(sl->mu);
+  *out = sl->delay;
+  return PEAQ_OK;
+}
+
+// The slot's newest complete watch window as of the last tick enqueued (the call waits for it); it does not tick.
+extern "C" int peaq_broker_watch_read(peaq_broker* b, int session_id, peaq_delay_watch* out) {
+  if (!b || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: NULL argument");
+  if (broker_is_multi(b)) {
+    int local;
+    peaq_broker* sh = broker_shard_of(b, session_id, &local);
+    return sh ? peaq_broker_watch_read(sh, local, out) : fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: bad session id");
+  }
+  BrokerSlot* sl = broker_slot(b, session_id);
+  if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: bad session id " + std::to_string(session_id));
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (!b->align.window)
+    return fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: the watch is off (peaq_broker_set_align, watch_frames)");
+  if (b->failed.load()) return broker_failed(b, "peaq_broker_watch_read");
+  std::lock_guard<std::mutex> lock(sl->mu);
+  if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_watch_read: session is not open");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  WatchState st;
+  HIP_TRY(hipMemcpyAsync(&st, b->w_state.as<WatchState>() + session_id, sizeof st, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  delay_watch_record(st, out);
   return PEAQ_OK;
 }
 

@@ -26,6 +26,7 @@
 //                     estimate through the aligner and the cut
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
+//   peaq_watch.hip    the delay watch of a live stream (kernels; the host side is in the session and the broker)
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
 //   peaq_broker.hip   live-pipeline broker (a StreamFramer per session, one launch per tick), one or several devices
 #pragma once
@@ -622,6 +623,11 @@ struct StreamFramer {
   uint64_t pos[2][2] = {{0, 0}, {0, 0}};   // [kind][pad]: stream sample where the next unit starts
   uint32_t done[2] = {0, 0};               // [kind]: units handed out so far
   uint32_t prev_blocks = 0;
+  // Live alignment (include/peaq_amd.h, "live alignment"): a held stream hands out nothing; release() ends the hold
+  // with the samples each pad drops from its head, before any unit exists.  Units, done[] and left() then count the
+  // stream as scored, pad p from its sample skip[p] on.  Never held and nothing skipped unless the owner asks.
+  bool held = false;
+  uint64_t skip[2] = {0, 0};
 
   void reset(bool advanced_, int channels_) {
     *this = StreamFramer();
@@ -634,6 +640,15 @@ struct StreamFramer {
     pad[p].total += n;
   }
   uint64_t left(StreamUnit kind, int p) const { return pad[p].total - pos[kind][p]; }
+  void hold() { held = true; }
+  void release(uint64_t skip_ref, uint64_t skip_test) {   // (a skip stops at what the pad holds: the caller's plan)
+    skip[0] = skip_ref;
+    skip[1] = skip_test;
+    for (int kind = 0; kind < 2; ++kind)
+      for (int p = 0; p < 2; ++p) pos[kind][p] = skip[p];
+    held = false;
+  }
+  uint64_t scored(int p) const { return pad[p].total - skip[p]; }   // samples of pad p in the stream as scored
   // samples present on both pads and not yet framed: of one kind, and the larger of the kinds in use (what the
   // broker's back-pressure counts)
   uint64_t backlog(StreamUnit kind) const { return std::min(left(kind, 0), left(kind, 1)); }
@@ -654,6 +669,7 @@ struct StreamFramer {
     const uint64_t hop = kind == kUnitBlock ? peaq::kFbFrame : peaq::kHop;
     const uint64_t l[2] = {left(kind, 0), left(kind, 1)}, av = std::min(l[0], l[1]);
     StreamWindow w;
+    if (held) return w;
     uint64_t adv[2];
     if (av >= unit) {
       w.count = static_cast<uint32_t>(std::min<uint64_t>((av - unit) / hop + 1, cap));
@@ -763,6 +779,81 @@ inline void meter_row(uint64_t k, uint32_t W, uint32_t H, bool ended, uint64_t n
   }
 }
 
+// ---------------------------------------------------------------------------
+// Live alignment (include/peaq_amd.h, "live alignment"): the configuration as every entry that takes one checks it,
+// rules A and B on the host, and a watch record from the device's state.  Host only.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLiveProbeMax = 1u << 20, kLiveProbeMargin = 2048;
+// *probe: the probe with the default filled in
+inline int check_live_align(const std::string& who, const peaq_live_align_config& c, uint32_t* probe) {
+  if (c.reserved != 0) return fail(PEAQ_ERR_ARG, who + ": reserved " + std::to_string(c.reserved) + " must be 0");
+  if (c.max_lag > 16384)
+    return fail(PEAQ_ERR_ARG, who + ": max_lag " + std::to_string(c.max_lag) + " is outside 0 .. 16384");
+  const uint32_t p = c.probe ? c.probe : 48000 + 2 * c.max_lag;
+  if (p < c.max_lag + kLiveProbeMargin || p > kLiveProbeMax)
+    return fail(PEAQ_ERR_ARG, who + ": probe " + std::to_string(p) + " is outside max_lag + 2048 = " +
+                                  std::to_string(c.max_lag + kLiveProbeMargin) + " .. " + std::to_string(kLiveProbeMax));
+  if (c.watch_frames > peaq::kWatchMaxFrames)
+    return fail(PEAQ_ERR_ARG, who + ": watch_frames " + std::to_string(c.watch_frames) + " is outside 0 .. " +
+                                  std::to_string(peaq::kWatchMaxFrames));
+  *probe = p;
+  return PEAQ_OK;
+}
+struct LiveAlignGeometry {
+  uint32_t max_lag = 0, probe = 0, window = 0;       // max_lag 0: no acquisition; window 0: no watch
+  bool on() const { return max_lag || window; }
+};
+// rule A for what the pads hold and the lag the aligner found
+inline void live_align_plan(uint32_t probe, uint64_t have_ref, uint64_t have_test, int32_t lag, peaq_live_delay* out) {
+  out->probe_ref = static_cast<uint32_t>(std::min<uint64_t>(have_ref, probe));
+  out->probe_test = static_cast<uint32_t>(std::min<uint64_t>(have_test, probe));
+  const uint64_t late = lag > 0 ? (uint64_t)lag : 0, early = lag < 0 ? (uint64_t)(-(int64_t)lag) : 0;
+  out->skip_ref = static_cast<uint32_t>(std::min(early, have_ref));
+  out->skip_test = static_cast<uint32_t>(std::min(late, have_test));
+}
+// rule B's read-out of a window's sums: norm, the arg-max with the aligner's tie rule, the runner-up
+inline void delay_watch_pick(const double* c, double e_ref, double e_test, int32_t* offset, double* peak,
+                             double* runner_up, double* norm) {
+  constexpr int D = peaq::kWatchLags;
+  *offset = 0;
+  *peak = *runner_up = *norm = 0.;
+  const double e2 = e_ref * e_test;
+  bool finite = std::isfinite(e2);
+  for (int i = 0; i <= 2 * D; ++i) finite = finite && std::isfinite(c[i]);
+  if (!finite) {
+    *norm = std::nan("");
+    return;
+  }
+  if (!(e2 > 0.)) return;
+  const double nrm = std::sqrt(e2);
+  double best = 0.;
+  for (int i = 0; i <= 2 * D; ++i) best = std::max(best, std::fabs(c[i]));
+  const double floor_ = best - 1e-12 * nrm;
+  unsigned key = 0xFFFFFFFFu;                        // 2 |d| + (d < 0), as align_pick_kernel
+  for (int d = -D; d <= D; ++d)
+    if (std::fabs(c[d + D]) >= floor_) key = std::min(key, 2u * (unsigned)std::abs(d) + (d < 0 ? 1u : 0u));
+  const int lag = (key & 1u) ? -(int)(key >> 1) : (int)(key >> 1);
+  double second = 0.;
+  for (int d = -D; d <= D; ++d)
+    if (d != lag) second = std::max(second, std::fabs(c[d + D]));
+  *offset = lag;
+  *peak = c[lag + D];
+  *runner_up = second;
+  *norm = nrm;
+}
+// the public record of a stream's watch state as the device left it
+inline void delay_watch_record(const peaq::WatchState& st, peaq_delay_watch* out) {
+  std::memset(out, 0, sizeof *out);
+  if (!st.latest_frames) return;
+  out->index = st.latest_index;
+  out->first_frame = st.latest_first;
+  out->n_frames = st.latest_frames;
+  std::memcpy(out->c, st.latest, sizeof out->c);
+  out->e_ref = st.latest[peaq::kWatchCols - 2];
+  out->e_test = st.latest[peaq::kWatchCols - 1];
+  delay_watch_pick(out->c, out->e_ref, out->e_test, &out->offset, &out->peak, &out->runner_up, &out->norm);
+}
+
 // One geometry, and what the host keeps per metered stream (a session, a broker slot): guarded by the owner's lock.
 struct MeterGeometry {
   bool on = false;
@@ -784,8 +875,8 @@ struct MeterStream {
   uint32_t total[2] = {0, 0};       // [kind]: T, TB
   void end(const StreamFramer& fr) {
     ended = true;
-    n_ref = fr.pad[0].total;
-    n_test = fr.pad[1].total;
+    n_ref = fr.scored(0);
+    n_test = fr.scored(1);
     total[kUnitFrame] = count_frames(n_ref, n_test, peaq::kFrame, peaq::kHop);
     total[kUnitBlock] = count_frames(n_ref, n_test, peaq::kFbFrame, peaq::kFbFrame);
   }

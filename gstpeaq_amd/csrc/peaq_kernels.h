@@ -364,6 +364,42 @@ hipError_t launch_meter_fft(const MeterArgs& m, bool advanced, const double* rec
 // and AvgLinDist of the windows that are open in them
 hipError_t launch_meter_fb(const MeterArgs& m, int channels, unsigned n_streams, hipStream_t stream);
 
+// ---- delay watch of a live stream (peaq_session_set_align, peaq_session_watch_read; peaq_watch.hip) ----------------
+// Watch window k of a stream covers the whole FFT frames [k W, (k + 1) W).  A frame's row: c[d + 31] for d = -31 .. 31,
+// the sum of r[n] t[n + d] over the frame's own n = 512 .. 1535 (r, t: the mono sums in double), then e_ref and e_test,
+// the sums of r[n]^2 and t[n]^2 over the same n.  A window's record is the sum of its frames' rows in frame order.
+constexpr int kWatchLags = 31, kWatchCols = 2 * kWatchLags + 3;   // 63 lags and the two energies
+constexpr int kWatchRow = 66;                    // doubles between rows (16-byte rows)
+constexpr uint32_t kWatchMaxFrames = 65536;
+struct WatchState {                              // per stream, on the device
+  double acc[kWatchRow];                         // the window that is filling
+  double latest[kWatchRow];                      // the newest complete window
+  uint64_t index;                                // k of the window that is filling
+  uint64_t latest_index;
+  uint32_t count;                                // frames in acc, < W
+  uint32_t latest_first, latest_frames;          // k W, W of `latest`; latest_frames 0: no window is complete yet
+  uint32_t pad_;
+};
+struct WatchArgs {
+  const float* ref;             // [stream][pair_stride][channels]: the staged samples the front end of the launch read,
+  const float* test;            // frame f of the launch at sample 1024 f
+  size_t pair_stride;
+  int channels;
+  uint32_t n_frames;            // whole frames of the launch (never the flush frame): of every stream, or with s_frames
+                                // the most any stream has
+  uint32_t window;              // W
+  double* rows;                 // [stream][row_stride][kWatchRow]: scratch between the two kernels
+  uint32_t row_stride;          // >= n_frames
+  WatchState* state;            // [stream], or with s_slot [slot]
+  // Broker launches (nullptr otherwise): stream p of the launch has its own count of whole frames, which may be 0 (its
+  // unit of this tick is the flush frame), and its state at its slot -- rows the tick uploads
+  const uint32_t* s_frames;     // [stream]
+  const uint32_t* s_slot;       // [stream] (pair_slot)
+};
+// after launch_frontend of the same whole frames, on the same stream: delay_watch_frames_kernel, delay_watch_fold_kernel
+// (a stream's state before its first frame is all zero bytes)
+hipError_t launch_delay_watch(const WatchArgs& a, unsigned n_streams, hipStream_t stream);
+
 // ---- the optional outputs of a run -------------------------------------------------------------
 // What a run writes besides its results, host side: the kernel argument of each output by value, absent while its
 // array is null.  The public entries of peaq_batch.hip fill in what the caller gave; batch_run_locked adds what only it

@@ -27,6 +27,13 @@ struct peaq_session {
     bool closed[2] = {false, false};   // [kind]: a launch that ends this path's units has gone out
   } meter;
 
+  // live alignment (peaq_session_set_align; peaq_watch.hip), guarded by mu like the rest
+  struct Align : LiveAlignGeometry {
+    DevBuf probe_sig[2], rec;       // acquisition: the two probes [probe][channels], the aligner's record
+    peaq_live_delay delay{};        // all zero while the stream holds
+    DevBuf rows, state;             // watch: one launch's rows [kSessionMaxFrames][kWatchRow], WatchState
+  } align;
+
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
   MeterArgs meter_args(StreamUnit kind, uint32_t first, uint32_t count) const {
     MeterArgs m{};
@@ -83,6 +90,44 @@ static int session_meter_restart(peaq_session* s) {
   mt.n_ref = mt.n_test = 0;
   mt.total[0] = mt.total[1] = 0;
   mt.closed[0] = mt.closed[1] = false;
+  return PEAQ_OK;
+}
+
+// a fresh stream for the alignment that is set: held until the delay is acquired, the watch at index 0
+static int session_align_restart(peaq_session* s) {
+  peaq_session::Align& al = s->align;
+  al.delay = peaq_live_delay{};
+  if (al.max_lag) s->framer.hold();
+  if (al.window) HIP_TRY(hipMemsetAsync(al.state.p, 0, sizeof(WatchState), s->stream));
+  return PEAQ_OK;
+}
+
+// Rule A: the delay of the probes the two pads hold, by the batch aligner on the session's stream; the one wait of the
+// stream; the framer released with the skips.  Within the push or the flush that completes the probe.
+static int session_acquire(peaq_session* s) {
+  peaq_session::Align& al = s->align;
+  StreamFramer& fr = s->framer;
+  const uint64_t have[2] = {fr.pad[0].total, fr.pad[1].total};
+  peaq_live_delay d{};
+  live_align_plan(al.probe, have[0], have[1], 0, &d);
+  const uint32_t n[2] = {d.probe_ref, d.probe_test};
+  peaq_delay rec{};                                  // (an empty pad: the record the aligner documents for it)
+  if (n[0] && n[1]) {
+    for (int p = 0; p < 2; ++p)
+      HIP_TRY(hipMemcpyAsync(al.probe_sig[p].p, fr.pad[p].at(0, s->channels), (size_t)n[p] * s->channels * sizeof(float),
+                             hipMemcpyHostToDevice, s->stream));
+    if (int rc = peaq_batch_estimate_delay(s->ctx, s->channels, 1, al.probe_sig[0].as<float>(), al.probe_sig[1].as<float>(),
+                                           al.probe, n, n + 1, 0, al.max_lag, al.rec.as<peaq_delay>(), s->stream))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(&rec, al.rec.p, sizeof rec, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  live_align_plan(al.probe, have[0], have[1], rec.lag, &d);
+  static_assert(sizeof d.d == sizeof rec, "peaq_live_delay::d mirrors peaq_delay");
+  std::memcpy(&d.d, &rec, sizeof rec);
+  d.acquired = 1;
+  al.delay = d;
+  fr.release(d.skip_ref, d.skip_test);
   return PEAQ_OK;
 }
 
@@ -178,6 +223,19 @@ static int session_run_frames(peaq_session* s, const StreamWindow& w) {
   fa.frames_per_launch = w.count;
   fa.records = s->records.as<double>();
   HIP_TRY(launch_frontend(m.fft_bands(), fa, 1, s->stream));
+  if (s->align.window && !w.flush) {
+    WatchArgs wa{};
+    wa.ref = fa.ref;
+    wa.test = fa.test;
+    wa.pair_stride = fa.pair_stride;
+    wa.channels = s->channels;
+    wa.n_frames = w.count;
+    wa.window = s->align.window;
+    wa.rows = s->align.rows.as<double>();
+    wa.row_stride = w.count;
+    wa.state = s->align.state.as<WatchState>();
+    HIP_TRY(launch_delay_watch(wa, 1, s->stream));
+  }
   BackendArgs ba = m.backend(fa);
   ba.frame0 = w.first;
   ba.frames_per_launch = w.count;
@@ -240,6 +298,8 @@ extern "C" int peaq_session_push(peaq_session* s, int pad, const float* data, si
   } catch (const std::bad_alloc&) {
     return fail(PEAQ_ERR_NOMEM, "out of host memory");
   }
+  if (s->framer.held && std::min(s->framer.pad[0].total, s->framer.pad[1].total) >= s->align.probe)
+    if (int rc = session_acquire(s)) return rc;
   return session_drain(s, false);
 }
 
@@ -247,6 +307,8 @@ extern "C" int peaq_session_flush(peaq_session* s) {
   if (!s) return fail(PEAQ_ERR_ARG, "peaq_session_flush: session is NULL");
   std::lock_guard<std::mutex> lock(s->mu);
   HIP_TRY(hipSetDevice(s->ctx->device));
+  if (s->framer.held)                                // the probe is what is there
+    if (int rc = session_acquire(s)) return rc;
   peaq_session::Meter& mt = s->meter;
   const bool ends_now = mt.on && !mt.ended;
   if (ends_now) mt.end(s->framer);                   // the stream's end is known from here on: the launches below carry it
@@ -298,6 +360,8 @@ extern "C" int peaq_session_reset(peaq_session* s) {
   if (s->advanced)
     HIP_TRY(hipMemsetAsync(s->fbstate.p, 0, 2 * s->channels * sizeof(FbSignalState), s->stream));
   HIP_TRY(launch_state_init(s->state.as<PairState>(), s->advanced, 1, s->stream));
+  if (s->align.on())
+    if (int rc = session_align_restart(s)) return rc;
   return s->meter.on ? session_meter_restart(s) : PEAQ_OK;
 }
 
@@ -377,4 +441,96 @@ extern "C" int peaq_session_meter_read(peaq_session* s, peaq_meter_reading* out,
   HIP_TRY(hipSetDevice(s->ctx->device));
   return mt.read(s->framer, mt, mt.delivered.as<PointSnap>(), mt.readout, mt.h_readout, s->channels, s->stream, s->cfg,
                  out, cap, n_read, dropped);
+}
+
+extern "C" size_t peaq_live_delay_size(void) { return sizeof(peaq_live_delay); }
+extern "C" size_t peaq_delay_watch_size(void) { return sizeof(peaq_delay_watch); }
+
+extern "C" int peaq_live_align_plan(const peaq_live_align_config* cfg, uint64_t have_ref, uint64_t have_test, int32_t lag,
+                                    uint32_t* probe_ref, uint32_t* probe_test, uint32_t* skip_ref, uint32_t* skip_test) {
+  const std::string who("peaq_live_align_plan");
+  if (!cfg) return fail(PEAQ_ERR_ARG, who + ": cfg is NULL");
+  uint32_t probe = 0;
+  if (int rc = check_live_align(who, *cfg, &probe)) return rc;
+  if (cfg->max_lag == 0) return fail(PEAQ_ERR_ARG, who + ": max_lag 0 sets no acquisition");
+  if (lag < -(int64_t)cfg->max_lag || lag > (int64_t)cfg->max_lag)
+    return fail(PEAQ_ERR_ARG, who + ": lag " + std::to_string(lag) + " is outside -max_lag .. max_lag = " +
+                                  std::to_string(cfg->max_lag));
+  peaq_live_delay d{};
+  live_align_plan(probe, have_ref, have_test, lag, &d);
+  if (probe_ref) *probe_ref = d.probe_ref;
+  if (probe_test) *probe_test = d.probe_test;
+  if (skip_ref) *skip_ref = d.skip_ref;
+  if (skip_test) *skip_test = d.skip_test;
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_delay_watch_pick(const double* c, double e_ref, double e_test, int32_t* offset, double* peak,
+                                     double* runner_up, double* norm) {
+  if (!c) return fail(PEAQ_ERR_ARG, "peaq_delay_watch_pick: c is NULL");
+  int32_t o;
+  double p, r, n;
+  delay_watch_pick(c, e_ref, e_test, &o, &p, &r, &n);
+  if (offset) *offset = o;
+  if (peak) *peak = p;
+  if (runner_up) *runner_up = r;
+  if (norm) *norm = n;
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_session_set_align(peaq_session* s, const peaq_live_align_config* cfg) {
+  const std::string who("peaq_session_set_align");
+  if (!s) return fail(PEAQ_ERR_ARG, who + ": session is NULL");
+  const bool off = !cfg || (cfg->max_lag == 0 && cfg->watch_frames == 0);
+  uint32_t probe = 0;
+  if (cfg)
+    if (int rc = check_live_align(who, *cfg, &probe)) return rc;
+  std::lock_guard<std::mutex> lock(s->mu);
+  const uint64_t pushed = s->framer.pad[0].total + s->framer.pad[1].total;
+  if (pushed)
+    return fail(PEAQ_ERR_ARG, who + ": the stream has begun (" + std::to_string(pushed) +
+                                  " samples pushed); set the alignment before the first push or right after peaq_session_reset");
+  peaq_session::Align& al = s->align;
+  al.max_lag = al.probe = al.window = 0;             // (stays off if the workspace cannot be reserved)
+  al.delay = peaq_live_delay{};
+  s->framer.held = false;
+  if (off) return PEAQ_OK;
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
+  if (cfg->max_lag) {
+    for (int p = 0; p < 2; ++p) HIP_TRY(al.probe_sig[p].reserve((size_t)probe * s->channels * sizeof(float)));
+    HIP_TRY(al.rec.reserve(sizeof(peaq_delay)));
+  }
+  if (cfg->watch_frames) {
+    HIP_TRY(al.rows.reserve((size_t)kSessionMaxFrames * kWatchRow * sizeof(double)));
+    HIP_TRY(al.state.reserve(sizeof(WatchState)));
+  }
+  al.max_lag = cfg->max_lag;
+  al.probe = probe;
+  al.window = cfg->watch_frames;
+  return session_align_restart(s);
+}
+
+extern "C" int peaq_session_align_read(peaq_session* s, peaq_live_delay* out) {
+  if (!s || !out) return fail(PEAQ_ERR_ARG, "peaq_session_align_read: NULL argument");
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (!s->align.max_lag)
+    return fail(PEAQ_ERR_ARG, "peaq_session_align_read: no acquisition is set (peaq_session_set_align, max_lag)");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *out = s->align.delay;
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_session_watch_read(peaq_session* s, peaq_delay_watch* out) {
+  if (!s || !out) return fail(PEAQ_ERR_ARG, "peaq_session_watch_read: NULL argument");
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (!s->align.window)
+    return fail(PEAQ_ERR_ARG, "peaq_session_watch_read: the watch is off (peaq_session_set_align, watch_frames)");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  WatchState st;
+  HIP_TRY(hipMemcpyAsync(&st, s->align.state.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  delay_watch_record(st, out);
+  return PEAQ_OK;
 }

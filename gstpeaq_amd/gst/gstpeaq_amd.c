@@ -54,6 +54,14 @@ typedef struct _GstPeaqAmd
   gboolean metered;             /* the current session / broker slot has its meter on */
   gboolean meter_flushed;       /* the stream was flushed at EOS already (metered streams only) */
   gdouble st_odg, st_di, st_totalsnr;   /* the newest delivered reading, NaN before the first */
+  /* live alignment (include/peaq_amd.h, "live alignment"): the chain's delay found and cut away, and watched */
+  guint align_max_lag, align_probe;     /* samples at 48 kHz; max-lag 0 = no acquisition, probe 0 = the default */
+  gdouble delay_watch;          /* seconds per watch window; 0 = no watch */
+  gboolean aligning, watching;  /* the current session / broker slot acquires its delay / has its watch on */
+  gboolean delay_acquired;      /* ... and has acquired it: `peaq-delay` has been posted */
+  gint delay, delay_offset;     /* the lag acquired (0 before); the newest watch window's offset */
+  gboolean watch_seen;
+  guint64 watch_index;          /* the newest watch window posted */
 } GstPeaqAmd;
 
 typedef struct _GstPeaqAmdClass
@@ -63,7 +71,8 @@ typedef struct _GstPeaqAmdClass
 
 enum
 { PROP_0, PROP_PLAYBACK_LEVEL, PROP_ADVANCED, PROP_DI, PROP_ODG, PROP_TOTALSNR, PROP_CONSOLE_OUTPUT,
-  PROP_METER_WINDOW, PROP_METER_HOP, PROP_METER_DEPTH, PROP_ST_ODG, PROP_ST_DI, PROP_ST_TOTALSNR
+  PROP_METER_WINDOW, PROP_METER_HOP, PROP_METER_DEPTH, PROP_ST_ODG, PROP_ST_DI, PROP_ST_TOTALSNR,
+  PROP_ALIGN_MAX_LAG, PROP_ALIGN_PROBE, PROP_DELAY_WATCH, PROP_DELAY, PROP_DELAY_ACQUIRED, PROP_DELAY_OFFSET
 };
 
 static GstStaticPadTemplate ref_template =
@@ -136,6 +145,44 @@ meter_config_of (gdouble window, gdouble hop, guint depth, peaq_meter_config * c
       && peaq_meter_frames (hop > 0. ? hop : window, &cfg->hop_frames) == PEAQ_OK;
 }
 
+/* max_lag, probe (samples) and the watch window (seconds) as a configuration; FALSE if the seconds are refused */
+static gboolean
+align_config_of (guint max_lag, guint probe, gdouble watch, peaq_live_align_config * cfg)
+{
+  cfg->max_lag = max_lag;
+  cfg->probe = probe;
+  cfg->watch_frames = cfg->reserved = 0;
+  return !(watch > 0.) || peaq_meter_frames (watch, &cfg->watch_frames) == PEAQ_OK;
+}
+
+/* PEAQ_AMD_BROKER_ALIGN=MAX_LAG[:PROBE[:WATCH_SECONDS]]: the live alignment of every broker of the process (one
+ * configuration per broker).  TRUE and the configuration if it is set and well-formed. */
+static gboolean
+broker_align_config (peaq_live_align_config * cfg)
+{
+  const gchar *a = g_getenv ("PEAQ_AMD_BROKER_ALIGN");
+  gchar **tok;
+  gboolean ok = TRUE;
+  guint64 v[2] = { 0, 0 };
+  gdouble watch = 0.;
+  guint i, n;
+  if (!a || !*a)
+    return FALSE;
+  tok = g_strsplit (a, ":", 4);
+  n = g_strv_length (tok);
+  ok = n >= 1 && n <= 3;
+  for (i = 0; ok && i < n; i++) {
+    gchar *end = NULL;
+    if (i < 2)
+      v[i] = g_ascii_strtoull (tok[i], &end, 10);
+    else
+      watch = g_ascii_strtod (tok[i], &end);
+    ok = end != tok[i] && !*end && v[i < 2 ? i : 0] <= G_MAXUINT32 && watch >= 0.;
+  }
+  g_strfreev (tok);
+  return ok && align_config_of ((guint) v[0], (guint) v[1], watch, cfg) && (cfg->max_lag || cfg->watch_frames);
+}
+
 static peaq_broker *
 shared_broker (gboolean advanced, gint channels)
 {
@@ -189,6 +236,13 @@ shared_broker (gboolean advanced, gint channels)
             || peaq_broker_set_meter (brokers[adv][channels], &cfg) != PEAQ_OK)
           GST_WARNING ("PEAQ_AMD_BROKER_METER: no meter (%s)", peaq_last_error ());
       }
+      if (g_getenv ("PEAQ_AMD_BROKER_ALIGN")) {
+        peaq_live_align_config acfg;
+        if (!broker_align_config (&acfg))
+          GST_WARNING ("PEAQ_AMD_BROKER_ALIGN: no alignment (not MAX_LAG[:PROBE[:WATCH_SECONDS]])");
+        else if (peaq_broker_set_align (brokers[adv][channels], &acfg) != PEAQ_OK)
+          GST_WARNING ("PEAQ_AMD_BROKER_ALIGN: no alignment (%s)", peaq_last_error ());
+      }
       if (peaq_broker_start (brokers[adv][channels], period ? (unsigned) atoi (period) : 0) != PEAQ_OK)
         GST_WARNING ("libpeaq_amd: %s", peaq_last_error ());
     } else {
@@ -225,14 +279,21 @@ renew_session (GstPeaqAmd * self)
   self->pushed = FALSE;
   self->metered = self->meter_flushed = FALSE;
   self->st_odg = self->st_di = self->st_totalsnr = NAN;
+  self->aligning = self->watching = self->delay_acquired = self->watch_seen = FALSE;
+  self->delay = self->delay_offset = 0;
   if (self->channels <= 0)
     return TRUE;
   if (self->playback_level == 92.) {
     peaq_broker *b = shared_broker (self->advanced, self->channels);
     if (b && peaq_broker_open (b, &self->broker_sid) == PEAQ_OK) {
       gdouble mw, mh;
+      peaq_live_align_config acfg;
       self->broker = b;
       self->metered = broker_meter_seconds (&mw, &mh);    /* the geometry is the process's, not the element's */
+      if (broker_align_config (&acfg)) {                /* ... and so is the alignment */
+        self->aligning = acfg.max_lag != 0;
+        self->watching = acfg.watch_frames != 0;
+      }
       return TRUE;
     }
   }
@@ -252,7 +313,63 @@ renew_session (GstPeaqAmd * self)
     else
       GST_WARNING_OBJECT (self, "libpeaq_amd: no meter (%s)", peaq_last_error ());
   }
+  if (self->align_max_lag || self->delay_watch > 0.) {
+    peaq_live_align_config cfg;
+    if (align_config_of (self->align_max_lag, self->align_probe, self->delay_watch, &cfg)
+        && peaq_session_set_align (self->session, &cfg) == PEAQ_OK) {
+      self->aligning = cfg.max_lag != 0;
+      self->watching = cfg.watch_frames != 0;
+    } else
+      GST_WARNING_OBJECT (self, "libpeaq_amd: no alignment (%s)", peaq_last_error ());
+  }
   return TRUE;
+}
+
+/* Live alignment on the bus: once, when the stream's delay has been acquired, an element message `peaq-delay` (lag,
+ * peak, runner-up, norm, skip-ref, skip-test); for every new watch window an element message `peaq-delay-watch` (index,
+ * first-frame, frames, offset, peak, runner-up, norm).  Call WITHOUT the object lock (posting takes it). */
+static void
+post_alignment (GstPeaqAmd * self)
+{
+  peaq_live_delay d;
+  peaq_delay_watch w;
+  gboolean new_delay = FALSE, new_window = FALSE;
+  GST_OBJECT_LOCK (self);
+  if (self->aligning && !self->delay_acquired) {
+    gint rc = self->broker ? peaq_broker_align_read (self->broker, self->broker_sid, &d)
+        : self->session ? peaq_session_align_read (self->session, &d) : PEAQ_ERR_ARG;
+    if (rc == PEAQ_OK && d.acquired) {
+      self->delay_acquired = new_delay = TRUE;
+      self->delay = d.d.lag;
+    }
+  }
+  if (self->watching) {
+    gint rc = self->broker ? peaq_broker_watch_read (self->broker, self->broker_sid, &w)
+        : self->session ? peaq_session_watch_read (self->session, &w) : PEAQ_ERR_ARG;
+    if (rc == PEAQ_OK && w.n_frames && (!self->watch_seen || w.index != self->watch_index)) {
+      self->watch_seen = new_window = TRUE;
+      self->watch_index = w.index;
+      self->delay_offset = w.offset;
+    }
+  }
+  GST_OBJECT_UNLOCK (self);
+  if (new_delay) {
+    g_object_notify (G_OBJECT (self), "delay");
+    g_object_notify (G_OBJECT (self), "delay-acquired");
+  }
+  if (new_window)
+    g_object_notify (G_OBJECT (self), "delay-offset");
+  if (new_delay)
+    gst_element_post_message (GST_ELEMENT (self), gst_message_new_element (GST_OBJECT (self),
+            gst_structure_new ("peaq-delay", "lag", G_TYPE_INT, (gint) d.d.lag, "peak", G_TYPE_DOUBLE, d.d.peak,
+                "runner-up", G_TYPE_DOUBLE, d.d.runner_up, "norm", G_TYPE_DOUBLE, d.d.norm,
+                "skip-ref", G_TYPE_UINT, (guint) d.skip_ref, "skip-test", G_TYPE_UINT, (guint) d.skip_test, NULL)));
+  if (new_window)
+    gst_element_post_message (GST_ELEMENT (self), gst_message_new_element (GST_OBJECT (self),
+            gst_structure_new ("peaq-delay-watch", "index", G_TYPE_UINT64, (guint64) w.index,
+                "first-frame", G_TYPE_UINT, (guint) w.first_frame, "frames", G_TYPE_UINT, (guint) w.n_frames,
+                "offset", G_TYPE_INT, (gint) w.offset, "peak", G_TYPE_DOUBLE, w.peak, "runner-up", G_TYPE_DOUBLE,
+                w.runner_up, "norm", G_TYPE_DOUBLE, w.norm, NULL)));
 }
 
 /* The readings delivered since the last call, each as an element message `peaq-meter` on the bus: index, start and
@@ -417,6 +534,31 @@ gst_peaq_amd_get_property (GObject * obj, guint id, GValue * value, GParamSpec *
     case PROP_ST_TOTALSNR:
       g_value_set_double (value, self->st_totalsnr);
       break;
+    case PROP_ALIGN_MAX_LAG:
+    case PROP_ALIGN_PROBE:
+    case PROP_DELAY_WATCH:{
+      /* an element hosted by the broker reads back the broker's values (the watch window rounded to frames) */
+      peaq_live_align_config b = { self->align_max_lag, self->align_probe, 0, 0 };
+      gdouble watch = self->delay_watch;
+      if (self->broker && broker_align_config (&b))
+        watch = b.watch_frames * 1024. / 48000.;
+      else if (self->broker)
+        b.max_lag = b.probe = 0, watch = 0.;
+      if (id == PROP_DELAY_WATCH)
+        g_value_set_double (value, watch);
+      else
+        g_value_set_uint (value, id == PROP_ALIGN_MAX_LAG ? b.max_lag : b.probe);
+      break;
+    }
+    case PROP_DELAY:
+      g_value_set_int (value, self->delay);
+      break;
+    case PROP_DELAY_ACQUIRED:
+      g_value_set_boolean (value, self->delay_acquired);
+      break;
+    case PROP_DELAY_OFFSET:
+      g_value_set_int (value, self->delay_offset);
+      break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (obj, id, pspec);
   }
@@ -476,6 +618,24 @@ gst_peaq_amd_set_property (GObject * obj, guint id, const GValue * value, GParam
       GST_OBJECT_UNLOCK (self);
       post_pending_error (self);
       break;
+    case PROP_ALIGN_MAX_LAG:
+    case PROP_ALIGN_PROBE:
+    case PROP_DELAY_WATCH:
+      /* like the meter's: in NULL / READY; the session is made anew if there is one and it has seen no samples */
+      GST_OBJECT_LOCK (self);
+      if (id == PROP_ALIGN_MAX_LAG)
+        self->align_max_lag = g_value_get_uint (value);
+      else if (id == PROP_ALIGN_PROBE)
+        self->align_probe = g_value_get_uint (value);
+      else
+        self->delay_watch = g_value_get_double (value);
+      if (self->channels > 0 && !self->pushed)
+        renew_session (self);
+      else if (self->pushed)
+        GST_WARNING_OBJECT (self, "the alignment changed mid-stream: it applies from the next (re)negotiation");
+      GST_OBJECT_UNLOCK (self);
+      post_pending_error (self);
+      break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (obj, id, pspec);
   }
@@ -515,6 +675,8 @@ gst_peaq_amd_chain (GstPad * pad, GstObject * parent, GstBuffer * buffer)
   GST_OBJECT_UNLOCK (self);
   if (ret == GST_FLOW_OK && self->metered)
     post_meter_readings (self);         /* what this push completed (a broker: what its ticks have delivered so far) */
+  if (ret == GST_FLOW_OK && (self->aligning || self->watching))
+    post_alignment (self);
   if (ret == GST_FLOW_ERROR && !self->failed) {
     self->failed = TRUE;
     GST_ELEMENT_ERROR (self, LIBRARY, FAILED, ("libpeaq_amd: %s", peaq_last_error ()), (NULL));
@@ -562,9 +724,10 @@ gst_peaq_amd_sink_event (GstPad * pad, GstObject * parent, GstEvent * event)
       both = self->eos[0] && self->eos[1];
       GST_OBJECT_UNLOCK (self);
       ret = TRUE;
-      if (both && self->metered) {
-        /* a metered stream is flushed here, not at PAUSED -> READY, so that its last readings are on the bus before
-         * the EOS message; the flush at the state change then finds nothing left, and the results are the same */
+      if (both && (self->metered || self->aligning || self->watching)) {
+        /* a metered, aligned or watched stream is flushed here, not at PAUSED -> READY, so that its last readings (and
+         * the delay of a stream that ended before its probe was full) are on the bus before the EOS message; the
+         * flush at the state change then finds nothing left, and the results are the same */
         peaq_result r;
         GST_OBJECT_LOCK (self);
         if (!self->meter_flushed) {
@@ -576,6 +739,7 @@ gst_peaq_amd_sink_event (GstPad * pad, GstObject * parent, GstEvent * event)
         }
         GST_OBJECT_UNLOCK (self);
         post_meter_readings (self);
+        post_alignment (self);
       }
       if (both) {
         GstMessage *msg = gst_message_new_eos (parent);
@@ -694,6 +858,28 @@ gst_peaq_amd_class_init (GstPeaqAmdClass * klass)
       g_param_spec_double ("short-term-totalsnr", "short-term SNR", "Overall SNR in dB of the newest window of the meter",
           -G_MAXDOUBLE, G_MAXDOUBLE, 0, G_PARAM_READABLE));
 
+  /* live alignment: the chain's delay found and cut away, and watched (include/peaq_amd.h, "live alignment") */
+  g_object_class_install_property (oc, PROP_ALIGN_MAX_LAG,
+      g_param_spec_uint ("align-max-lag", "alignment search range",
+          "Largest delay between the pads searched for, in samples at 48 kHz (0 = no alignment)", 0, 16384, 0,
+          G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_ALIGN_PROBE,
+      g_param_spec_uint ("align-probe", "alignment probe",
+          "Samples held on each pad for the delay estimate (0 = 48000 + 2 align-max-lag)", 0, 1 << 20, 0,
+          G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_DELAY_WATCH,
+      g_param_spec_double ("delay-watch", "delay watch window", "Length of the delay watch's window in seconds (0 = off)", 0,
+          1e6, 0, G_PARAM_READWRITE | G_PARAM_CONSTRUCT));
+  g_object_class_install_property (oc, PROP_DELAY,
+      g_param_spec_int ("delay", "delay", "Delay of the test pad against the reference pad in samples (0 until acquired)",
+          -16384, 16384, 0, G_PARAM_READABLE));
+  g_object_class_install_property (oc, PROP_DELAY_ACQUIRED,
+      g_param_spec_boolean ("delay-acquired", "delay acquired", "The stream's delay has been found", FALSE,
+          G_PARAM_READABLE));
+  g_object_class_install_property (oc, PROP_DELAY_OFFSET,
+      g_param_spec_int ("delay-offset", "delay offset", "Offset the newest window of the delay watch reads, in samples",
+          -31, 31, 0, G_PARAM_READABLE));
+
   gst_element_class_add_static_pad_template (ec, &ref_template);
   gst_element_class_add_static_pad_template (ec, &test_template);
   gst_element_class_set_static_metadata (ec, "Perceptual evaluation of audio quality (MI355X)", "Sink/Audio",
@@ -722,6 +908,8 @@ gst_peaq_amd_init (GstPeaqAmd * self)
   self->pending_error = NULL;
   self->metered = self->meter_flushed = FALSE;
   self->st_odg = self->st_di = self->st_totalsnr = NAN;
+  self->aligning = self->watching = self->delay_acquired = self->watch_seen = FALSE;
+  self->delay = self->delay_offset = 0;
 }
 
 static gboolean

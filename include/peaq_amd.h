@@ -240,6 +240,98 @@ int peaq_meter_readings (uint64_t n_ref, uint64_t n_test, const peaq_meter_confi
 int peaq_session_set_meter (peaq_session *s, const peaq_meter_config *cfg);
 int peaq_session_meter_read (peaq_session *s, peaq_meter_reading *out, int cap, int *n_read, uint64_t *dropped);
 
+/* ---- live alignment: find the chain's delay, align the pads, watch it move ---------------------------------------------
+ * A monitored chain -- a codec, a link, a processor between the reference pad and the test pad -- has a delay, and PEAQ
+ * takes the two signals as sample-aligned ("time alignment on the device" below, the batch side's cure).  Two things for a
+ * live stream, both off by default; with both off nothing of a session's launches or a broker's ticks changes.
+ *
+ * Rule A, acquisition (max_lag != 0).  No frame and no block of the stream is taken until both pads hold at least `probe`
+ *   samples per channel (0: 48000 + 2 max_lag), or the flush is called (session) or requested (broker).  At that moment,
+ *   with have_ref / have_test what the pads hold: probe_ref = min (have_ref, probe), probe_test = min (have_test, probe);
+ *   `d` is the record of peaq_batch_estimate_delay for one pair of those leading samples with this max_lag -- the same
+ *   kernels, the same arg-max rule, bit for bit (a pad that holds nothing has the record that entry documents for an
+ *   empty signal: all zero).  skip_* follow peaq_aligned_lengths: for lag >= 0 the test pad drops its first `lag`
+ *   samples, for lag < 0 the reference pad drops -lag; a skip stops at what the pad holds; nothing is cut at the tail --
+ *   a live stream ends when it ends, and the flush pads the leftovers as it always does.  From then on the stream behaves
+ *   as a plain stream that was fed ref[skip_ref:] and test[skip_test:], the STREAM AS SCORED: framing, flush, the `frames`
+ *   and `fb_blocks` counts and, with a meter, its frame indices, {start, length} and end-of-stream totals all count the
+ *   stream as scored.  One device wait per stream, at its start, inside the push or flush that completes the probe.
+ *   A silent or non-finite probe gives the aligner's lag = 0 with norm 0 or NaN: the stream then runs unaligned and the
+ *   caller sees why in `d`.  Nothing retries; retrying is the caller's business, with peaq_session_reset.
+ *   peaq_live_align_plan is rule A's arithmetic on the host, no device: the probe lengths and the skips for a lag
+ *   (output pointers may be NULL).  PEAQ_ERR_ARG for a configuration that set_align would refuse, max_lag == 0, or
+ *   |lag| > max_lag.
+ *
+ * Rule B, watch (watch_frames = W != 0).  r[n], t[n]: the mono sums in double of the stream as scored, as the aligner
+ *   defines them.  Watch window k covers the whole FFT frames [k W, (k + 1) W); the flush frame is never counted and an
+ *   incomplete last window is discarded.  For d = -31 .. 31:
+ *     c[d] = sum r[n] t[n + d] over n = 1024 k W + 512 .. 1024 (k + 1) W + 511,
+ *     e_ref = sum r[n]^2, e_test = sum t[n]^2 over the same n
+ *   (every n + d lies inside the frame that owns n, so the watch reads only what the stream's launches have staged).
+ *   norm = sqrt (e_ref e_test); offset = the d with the largest |c[d]|, values within 1e-12 norm of the largest counting
+ *   as tied, ties to the smaller |d|, then to the positive d -- the aligner's rule; peak = c[offset]; runner_up = the
+ *   largest |c| over the other lags.  A window with norm == 0 reads offset 0, peak 0, runner_up 0; one whose sums are not
+ *   all finite reads the same with norm NaN.  peaq_delay_watch_pick is this rule on the host (PEAQ_ERR_ARG for a NULL c;
+ *   the output pointers may be NULL).
+ *   Arithmetic: samples FP32 as stored, then FP64; per frame a fixed order, frames added in frame order from 0 at each
+ *   window's first frame.  A window's record does not depend on how pushes cut the stream into launches and is the same
+ *   bit for bit from run to run; every c[d], e_ref, e_test is within 1e-9 norm of the exact sum (1024 W products, W <=
+ *   65536: the derived bound is far below that).  The watch reports and never touches the stream.
+ *
+ * peaq_session_set_align: NULL, or max_lag == 0 && watch_frames == 0, switches both off.  Accepted only before the first
+ * push or right after peaq_session_reset; otherwise, and for max_lag > 16384, a probe (after the default is filled in)
+ * outside max_lag + 2048 .. 1 << 20, watch_frames > 65536 or reserved != 0: PEAQ_ERR_ARG before a device is touched, the
+ * message naming entry and value.  The probe buffers are reserved here: PEAQ_ERR_NOMEM where that fails.
+ * peaq_session_align_read (acquisition set) and peaq_session_watch_read (watch set) wait for the session's enqueued work
+ * and change nothing; with their half off: PEAQ_ERR_ARG.  While the stream still holds, align_read gives acquired = 0
+ * and everything else zero.  watch_read gives the newest complete window -- n_frames == 0 and everything else zero while
+ * there is none --, is idempotent, and `index` tells whether the window is new.  peaq_session_reset starts over: the
+ * stream holds again, the watch is at index 0 with nothing complete.
+ *
+ * The broker (below): peaq_broker_set_align sets ONE configuration for all sessions of the broker, accepted where
+ * peaq_broker_set_meter is -- before the first peaq_broker_open and before peaq_broker_start, PEAQ_ERR_ARG otherwise --
+ * and for a broker made by peaq_broker_create_multi in every shard.  No tick waits on the device for an estimate: a tick
+ * finds the held slots whose probe is there (or whose flush has been requested), stages the probes of at most 8 of them
+ * -- the rest wait for later ticks --, and enqueues ONE peaq_batch_estimate_delay over them and the copy of its records
+ * to pinned memory; the next tick, after the wait for the previous tick's staging that every tick begins with, reads the
+ * records and releases those streams, whose first units ride in that tick.  A stream's first result is therefore two
+ * ticks later than without acquisition, more where over 8 streams start at once.  peaq_broker_push does not count a held
+ * stream's samples up to `probe` towards its back-pressure limit.  peaq_broker_results and peaq_broker_align_read on a
+ * slot that still holds with its flush requested tick until it is acquired (results: until it is drained); otherwise the
+ * reads report what the last tick enqueued has left, wait for it, and force none.  The watch adds two small kernels
+ * behind a tick's front-end launch over its FFT pairs, no copy and no wait: the whole-frame counts ride in one more
+ * metadata row, uploaded with the watch on only.  A window's record is the same bit for bit between a session and a
+ * broker slot.  Closing a slot and opening it again starts over. */
+typedef struct peaq_live_align_config {
+  uint32_t max_lag;       /* 0: no acquisition; else 1 .. 16384 as peaq_batch_estimate_delay */
+  uint32_t probe;         /* samples per channel held on each pad for the estimate; 0: 48000 + 2 max_lag */
+  uint32_t watch_frames;  /* W: 0 = no watch; else 1 .. 65536 FFT frames per watch window */
+  uint32_t reserved;      /* 0 */
+} peaq_live_align_config;
+typedef struct peaq_live_delay {
+  int32_t  acquired;               /* 0: still holding (everything else zero), 1: done */
+  uint32_t probe_ref, probe_test;  /* samples the estimate saw */
+  uint32_t skip_ref, skip_test;    /* samples dropped from the head of each pad */
+  uint32_t reserved;
+  struct { int32_t lag, reserved; double peak, runner_up, norm; } d;   /* peaq_delay, the aligner's own record */
+} peaq_live_delay;
+typedef struct peaq_delay_watch {
+  uint64_t index;                  /* k of the newest complete window; valid only if n_frames != 0 */
+  uint32_t first_frame, n_frames;  /* k W, W (n_frames 0: no window complete yet) */
+  int32_t  offset;  int32_t reserved;
+  double   peak, runner_up, norm, e_ref, e_test;
+  double   c[63];                  /* c[d + 31], d = -31 .. 31 */
+} peaq_delay_watch;
+size_t peaq_live_delay_size (void);     /* the struct sizes in THIS library, as peaq_meter_reading_size */
+size_t peaq_delay_watch_size (void);
+int peaq_live_align_plan (const peaq_live_align_config *cfg, uint64_t have_ref, uint64_t have_test, int32_t lag,
+                          uint32_t *probe_ref, uint32_t *probe_test, uint32_t *skip_ref, uint32_t *skip_test);
+int peaq_delay_watch_pick (const double c[63], double e_ref, double e_test, int32_t *offset, double *peak,
+                           double *runner_up, double *norm);
+int peaq_session_set_align (peaq_session *s, const peaq_live_align_config *cfg);
+int peaq_session_align_read (peaq_session *s, peaq_live_delay *out);
+int peaq_session_watch_read (peaq_session *s, peaq_delay_watch *out);
+
 /* ---- broker: many live sessions, one launch per tick -------------------------
  * Replaces, for a process hosting MANY `peaq` elements (BASELINE.json
  * configs[5]), the per-element device work of pad_chain -> do_processing
@@ -297,6 +389,9 @@ int  peaq_broker_stats   (peaq_broker *b, peaq_broker_stats_t *out);
 int  peaq_broker_set_meter (peaq_broker *b, const peaq_meter_config *cfg);     /* see "meter" above */
 int  peaq_broker_meter_read (peaq_broker *b, int session_id, peaq_meter_reading *out, int cap, int *n_read,
                              uint64_t *dropped);
+int  peaq_broker_set_align (peaq_broker *b, const peaq_live_align_config *cfg);   /* see "live alignment" above */
+int  peaq_broker_align_read (peaq_broker *b, int session_id, peaq_live_delay *out);
+int  peaq_broker_watch_read (peaq_broker *b, int session_id, peaq_delay_watch *out);
 size_t peaq_broker_stats_size (void);   /* sizeof (peaq_broker_stats_t) in THIS library: a caller built against another
                                          * header compares before it hands over a buffer */
 
