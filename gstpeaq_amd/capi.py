@@ -3111,16 +3111,21 @@ def synth_fill(ctx, seed0, n_pairs, channels, n_samples, device="cuda:0", stream
     return ref, test
 
 
-def debug_frontend(ctx, bands, ref, test, n_frames, playback_level=92.0):
+def debug_frontend(ctx, bands, ref, test, n_frames, playback_level=92.0, n_ref=None, n_test=None):
     """Stage-level access: per-frame front-end records of ONE pair.
-    ref/test: CUDA float32 [n, channels] (may differ in length).  -> np [frames, channels, 576]"""
+    ref/test: CUDA float32 [n, channels] (may differ in length); n_ref/n_test: the signals' lengths where the tensors
+    are longer (a signal of no samples is a tensor with something behind it: an empty tensor has no address).
+    -> np [frames, channels, 576]"""
     import torch
     assert ref.is_cuda and test.is_cuda and ref.is_contiguous() and test.is_contiguous()
     channels = ref.shape[1]
+    n_ref = ref.shape[0] if n_ref is None else int(n_ref)
+    n_test = test.shape[0] if n_test is None else int(n_test)
+    assert 0 <= n_ref <= ref.shape[0] and 0 <= n_test <= test.shape[0] and test.shape[1] == channels
     out = np.zeros((n_frames, channels, RECORD_DOUBLES))
     torch.cuda.synchronize()
     _check(ctx.L.peaq_debug_frontend(ctx.h, bands, channels, float(playback_level), C.c_void_p(ref.data_ptr()),
-                                     C.c_void_p(test.data_ptr()), ref.shape[0], test.shape[0], n_frames,
+                                     C.c_void_p(test.data_ptr()), n_ref, n_test, n_frames,
                                      out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
 

@@ -21,6 +21,7 @@ import pytest
 
 import gst_env
 import oracle_lib as orc
+from fe_stage_cases import planes_from_records       # (the arithmetic: shared with tests/test_gpu_fe_stage_batches.py)
 from test_conformance_runner import write_wav
 from test_gpu_trajectory import to_device
 
@@ -72,27 +73,7 @@ def expected(bands, channels, p):
         return _EXPECTED[key]
     ref, test = pairs_of(channels)[p]
     nf = orc.count_frames(len(ref), len(test))
-    rec, tab = orc.frontend_records(bands, ref, test, nf), orc.tables(bands)
-    a = tab["ear_tc"]
-    sm = np.zeros((2, channels, bands))
-    e = np.zeros((2, nf, channels, bands))
-    for f in range(nf):                              # fftearmodel.c:496-504
-        for i, off in enumerate((0, 112)):
-            u = rec[f, :, off:off + bands]
-            sm[i] = a * sm[i] + (1 - a) * u
-            e[i, f] = np.maximum(sm[i], u)
-    out = dict(exc_ref=e[0], exc_test=e[1], noise=rec[:, :, 448:448 + bands])
-    out["nmr"] = out["noise"] * tab["mask_diff"] / e[0]              # movs.c:1002-1022
-    if bands == 109:                                 # movs.c:1239-1260 as prob_detect_of_frame (oracle/peaq_oracle.c)
-        er, et = 10. * np.log10(e[0]), 10. * np.log10(e[1])
-        lv = 0.3 * np.maximum(er, et) + 0.7 * et
-        pos = np.where(lv > 0., lv, 1.)
-        sd = np.where(lv > 0., 5.95072 * np.power(6.39468 / pos, 1.71332) + 9.01033e-11 * np.power(pos, 4.) +
-                      5.05622e-6 * np.power(pos, 3.) - 0.00102438 * pos * pos + 0.0550197 * pos - 0.198719, 1e30)
-        d = er - et
-        out["detect"] = np.power(d / sd, np.where(er > et, 4., 6.))
-        out["steps"] = np.abs(np.trunc(d)) / sd
-        out["e_db"] = d
+    out = planes_from_records(bands, orc.frontend_records(bands, ref, test, nf), orc.tables(bands))
     _EXPECTED[key] = out
     return out
 
