@@ -19,13 +19,9 @@ using namespace peaq;
 // The framing per session is that of do_processing / do_flush
 // (gstpeaq.c:596-611, 716-745, 769-771).
 namespace {
-constexpr unsigned kBrokerMaxFrames = 8;     // FFT frames one session contributes to one tick
-constexpr unsigned kBrokerMaxBlocks = 48;    // filter-bank blocks one session contributes to one tick
-constexpr size_t kBrokerStageSamples = (size_t)(kBrokerMaxFrames - 1) * kHop + kFrame;
+constexpr size_t kBrokerStageSamples = (size_t)(kBrokerMaxFrames - 1) * kHop + kFrame;   // (kBrokerMax*: peaq_host.h)
 constexpr size_t kBrokerFbStageSamples = (size_t)kBrokerMaxBlocks * kFbFrame;
 constexpr size_t kBrokerRowStride = (size_t)kFbRing + kBrokerFbStageSamples;
-constexpr size_t kMetaRows = 11;          // rows of h_meta; rows 7 .. 9 are uploaded with the meter or the watch on only,
-                                          // row 10 with the watch on only
 constexpr unsigned kBrokerAcquirePerTick = 8;   // live alignment: slots whose delay estimate one tick enqueues
 // back-pressure: a push returns only once its session has no more than this many samples that are
 // READY to be framed (present on both pads) and not yet launched -- four ticks' worth.  Samples one
@@ -36,7 +32,7 @@ constexpr uint64_t kBrokerBacklog = (uint64_t)4 * kBrokerMaxFrames * kHop;
 struct BrokerSlot {
   std::mutex mu;
   bool open = false;
-  bool flush_requested = false, fft_flushed = false, fb_flushed = false;
+  SlotFlush flush;
   StreamFramer framer;              // the two pads' FIFOs and where the next frame / block starts
   double t_ready_us = -1.;          // when the oldest not yet launched frame / block became whole (-1: none waiting)
   MeterStream meter;                // the slot's meter (peaq_broker_set_meter), fresh at every open
@@ -100,12 +96,68 @@ struct BrokerStage {
   }
 };
 
+// The per-pair scalars of a tick's launches: rows of max_sessions entries each, pinned on the host and uploaded as one
+// prefix of the table.  Entry i of a row belongs to launch pair i of the FFT path or of the filter-bank path.
+struct BrokerMeta {
+  enum Row {
+    kNRef,            // FFT pair: valid samples of the reference in its staging entry      (front end)
+    kNTest,           //           ... of the test signal
+    kFrame0,          //           the session's first frame of this tick                    (front end, back end, meter)
+    kNFrames,         //           its frames of this tick
+    kSlot,            //           the session's slot: PairState, meter snapshots, watch state (back end, meter, watch)
+    kFbNRef,          // filter-bank pair: valid samples of the reference                    (filter-bank front end)
+    kFbNTest,         //           ... of the test signal
+    // uploaded with the meter or the watch on only; UINT_MAX until the session's flush is known:
+    kTotalFrames,     // FFT pair: the stream's frame count                                  (meter, FFT path)
+    kFbTotalFrames,   // filter-bank pair: the stream's frame count                          (meter, filter-bank path)
+    kFbTotalBlocks,   //           the stream's block count
+    // uploaded with the watch on only:
+    kWatchFrames,     // FFT pair: its whole frames of this tick, 0 for a flush frame        (watch)
+    kRows
+  };
+  int alloc(size_t n_sessions) {
+    S = n_sessions;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), kRows * S * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(d.reserve(kRows * S * sizeof(uint32_t)));
+    return PEAQ_OK;
+  }
+  ~BrokerMeta() {
+    if (h) (void)hipHostFree(h);
+  }
+  uint32_t* host(Row r) const { return h + r * S; }
+  const uint32_t* dev(Row r) const { return d.as<uint32_t>() + r * S; }
+  // the leading rows a tick uploads
+  static size_t rows_uploaded(bool metered, bool watched) {
+    return watched ? kRows : metered ? kFbTotalBlocks + 1 : kFbNTest + 1;
+  }
+  hipError_t upload(bool metered, bool watched, hipStream_t stream) const {
+    return hipMemcpyAsync(d.p, h, rows_uploaded(metered, watched) * S * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+  }
+  size_t S = 0;
+  uint32_t* h = nullptr;            // pinned
+  DevBuf d;
+};
+
 // what one session contributes to a tick: decided under the slot lock in the tick's serial scan,
 // copied into the staging buffers afterwards (by the staging threads, several sessions at a time)
 struct BrokerJob {
   int sid = 0;
   unsigned fft_idx = 0, fb_idx = 0;   // staging entries (launch pairs) of the two windows
   StreamWindow fft, fb;               // count 0: none of that kind
+};
+
+// What the scan of the slots decided for one tick; the per-pair rows are in BrokerMeta and h_win.
+struct TickPlan {
+  double t_tick = 0.;                 // when the scan began
+  unsigned active = 0, max_nf = 0;    // FFT path: launch pairs, the most frames any has
+  unsigned fb_active = 0, max_nb = 0; // filter-bank path: launch pairs, the most blocks any has
+  unsigned fb_closing = 0;            // meter: sessions whose blocks ended without a flush block (entries without units)
+  uint64_t frames = 0;
+  std::vector<BrokerJob>& jobs;       // this tick's staging work (the broker keeps the storage)
+  unsigned n_acq = 0;                 // live alignment: this tick's estimates (peaq_broker::a_pending) ...
+  uint32_t acq_n[2][kBrokerAcquirePerTick];   // ... and their probe lengths per pad
+  explicit TickPlan(std::vector<BrokerJob>& storage) : jobs(storage) { jobs.clear(); }
+  bool idle() const { return !active && !fb_active && !fb_closing && !n_acq; }
 };
 
 // A few helper threads for the tick's one heavy host-side step, the copy of every session's new samples
@@ -194,10 +246,9 @@ struct peaq_broker {
   hipEvent_t staged = nullptr;
   bool staged_pending = false;
   BrokerStage fft, fbs;
-  uint32_t* h_meta = nullptr;       // pinned: 5 rows of max_sessions (n_ref, n_test, frame0, nframes, slot) + 2 rows (fb n_ref, n_test)
-                                    // + 3 rows of the meter (total frames per FFT pair; total frames, total blocks per fb pair)
+  BrokerMeta meta;                  // the per-pair scalars of a tick's launches
   FbPairWindow* h_win = nullptr;    // pinned: one per launch pair of the filter-bank launch
-  DevBuf d_meta, d_win, records, fb_records, state, fbstate, hp_rows, result;
+  DevBuf d_win, records, fb_records, state, fbstate, hp_rows, result;
   std::thread worker;
   std::atomic<bool> running{false};
   unsigned period_us = 0;
@@ -214,7 +265,7 @@ struct peaq_broker {
   UsHistogram h_host, h_device, h_latency;
   std::vector<float> parked_wait_us;
   double parked_host_us = 0.;
-  std::vector<BrokerJob> jobs;      // this tick's staging work
+  std::vector<BrokerJob> jobs;      // the storage of TickPlan::jobs
   std::unique_ptr<StagePool> stagers;
   // peaq_broker_create_multi: this broker owns no device; it deals its sessions out to one broker per device
   // (session id = shard + n_shards * the shard's own id) and forwards every call
@@ -223,34 +274,32 @@ struct peaq_broker {
   std::vector<int> shard_open;      // open sessions per shard (guarded by tick_mu)
   // the meter (peaq_broker_set_meter; peaq_meter.hip): one geometry for all slots, because it shapes the launch
   MeterGeometry meter;
-  DevBuf m_open, m_ring;            // PointSnap [slot][k_open], [slot][ring]
-  DevBuf m_ftrc, m_btrc;            // one tick's trace records [launch index][kBrokerMaxFrames / kBrokerMaxBlocks]
-  DevBuf m_readout;                 // ResultRecord [ring]
-  std::vector<ResultRecord> m_host;
+  MeterBuffers m_buf;               // a stream per slot, kBrokerMaxFrames / kBrokerMaxBlocks units a tick
 
   // live alignment (peaq_broker_set_align; peaq_watch.hip): one configuration for all slots
   LiveAlignGeometry align;
+  LiveAlignBuffers a_buf;           // kBrokerAcquirePerTick probes a tick; the watch's rows per launch pair, state per slot
   float* a_hprobe[2] = {nullptr, nullptr};   // pinned: this tick's probes [kBrokerAcquirePerTick][probe][channels]
-  DevBuf a_probe[2], a_rec;         // the same on the device; peaq_delay [kBrokerAcquirePerTick]
   peaq_delay* a_hrec = nullptr;     // pinned: the records of the last tick's estimates
   std::vector<BrokerAcquire> a_pending;      // the estimates the last tick enqueued
-  DevBuf w_rows, w_state;           // watch: one tick's rows [launch pair][kBrokerMaxFrames][kWatchRow]; WatchState [slot]
 
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
 };
 
 // a held slot whose probe is there, or whose flush has been asked for: the next tick with room estimates its delay
 static inline bool broker_probe_ready(const peaq_broker* b, const BrokerSlot& sl) {
-  return sl.flush_requested || std::min(sl.framer.pad[0].total, sl.framer.pad[1].total) >= b->align.probe;
+  return sl.flush.requested || std::min(sl.framer.pad[0].total, sl.framer.pad[1].total) >= b->align.probe;
 }
 
 static inline bool broker_is_multi(const peaq_broker* b) { return b && !b->shards.empty(); }
-// -> the device broker that owns session `sid` of b, and the session's id there
-static inline peaq_broker* broker_shard_of(peaq_broker* b, int sid, int* local) {
+// An entry `who` that takes a session id, on a multi-device broker: call(shard, id there) of the device broker that
+// owns session `sid` -> its result, or the refusal of a bad id.  Nothing: b owns its sessions itself.
+template <typename F>
+static std::optional<int> broker_forward(peaq_broker* b, int sid, const char* who, F&& call) {
+  if (!broker_is_multi(b)) return std::nullopt;
   const int n = (int)b->shards.size();
-  if (sid < 0 || sid >= b->max_sessions) return nullptr;
-  *local = sid / n;
-  return b->shards[sid % n];
+  if (sid < 0 || sid >= b->max_sessions) return fail(PEAQ_ERR_ARG, std::string(who) + ": bad session id");
+  return call(b->shards[sid % n], sid / n);
 }
 
 // window w of the slot's stream into staging entry `idx`
@@ -261,9 +310,13 @@ static void broker_stage_copy(const peaq_broker* b, const BrokerSlot& sl, const 
   stage_window(sl.framer, w, dst);
 }
 
-// the previous tick's device work is complete: its device time is known now, and with it the latency of the
-// sessions it served (wait for the tick + the tick's host part + its device part)
-static void broker_settle_timing(peaq_broker* b) {
+// ---- the phases of a tick, in the order broker_tick_locked runs them -----------------------------------------
+// settle: the last tick's device work, if it is still out, is waited for.  Its device time is known now, and with it
+// the latency of the sessions it served (wait for the tick + the tick's host part + its device part).
+static int broker_settle(peaq_broker* b) {
+  if (!b->staged_pending) return PEAQ_OK;
+  HIP_TRY(hipEventSynchronize(b->staged));
+  b->staged_pending = false;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, b->t_begin, b->t_end) != hipSuccess) ms = 0.f;
   const double dev_us = 1e3 * ms;
@@ -271,173 +324,114 @@ static void broker_settle_timing(peaq_broker* b) {
   b->h_host.add(b->parked_host_us);
   for (float w : b->parked_wait_us) b->h_latency.add((double)w + b->parked_host_us + dev_us);
   b->parked_wait_us.clear();
+  return PEAQ_OK;
 }
 
-static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
-  peaq_ctx* c = b->ctx;
-  if (n_active_out) *n_active_out = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  if (b->staged_pending) {
-    HIP_TRY(hipEventSynchronize(b->staged));
-    b->staged_pending = false;
-    broker_settle_timing(b);
-  }
-  // live alignment: the records of the estimates the last tick enqueued are in pinned memory now; their framers are
-  // released, and the streams' first units ride in this tick
+// release acquired (live alignment): the records of the estimates the last tick enqueued are in pinned memory now;
+// their framers are released, and the streams' first units ride in this tick
+static void broker_release_acquired(peaq_broker* b) {
   for (size_t i = 0; i < b->a_pending.size(); ++i) {
     const BrokerAcquire& q = b->a_pending[i];
     BrokerSlot& sl = *b->slots[q.sid];
     std::lock_guard<std::mutex> lock(sl.mu);
     if (!sl.open || sl.epoch != q.epoch || !sl.acquiring) continue;   // (closed, or closed and opened again, meanwhile)
-    peaq_live_delay d{};
-    live_align_plan(b->align.probe, q.have[0], q.have[1], b->a_hrec[i].lag, &d);
-    static_assert(sizeof d.d == sizeof(peaq_delay), "peaq_live_delay::d mirrors peaq_delay");
-    std::memcpy(&d.d, &b->a_hrec[i], sizeof(peaq_delay));
-    d.acquired = 1;
-    sl.delay = d;
+    sl.delay = live_delay_acquired(b->align.probe, q.have, &b->a_hrec[i]);
     sl.acquiring = false;
-    sl.framer.release(d.skip_ref, d.skip_test);
+    sl.framer.release(sl.delay.skip_ref, sl.delay.skip_test);
   }
   b->a_pending.clear();
-  const double t_tick = now_us();
-  const size_t S = (size_t)b->max_sessions;
-  uint32_t* m_nref = b->h_meta;
-  uint32_t* m_ntest = b->h_meta + S;
-  uint32_t* m_f0 = b->h_meta + 2 * S;
-  uint32_t* m_nf = b->h_meta + 3 * S;
-  uint32_t* m_slot = b->h_meta + 4 * S;
-  uint32_t* m_fb_nref = b->h_meta + 5 * S;
-  uint32_t* m_fb_ntest = b->h_meta + 6 * S;
-  // the meter's rows (uploaded with the meter on only): the stream's frame count of each FFT pair, its frame and block
-  // counts of each filter-bank pair -- UINT_MAX until the session's flush is known
-  uint32_t* m_tot_f = b->h_meta + 7 * S;
-  uint32_t* m_fb_tot_f = b->h_meta + 8 * S;
-  uint32_t* m_fb_tot_b = b->h_meta + 9 * S;
-  // the watch's row (uploaded with the watch on only): the whole frames of each FFT pair -- 0 for a flush frame
-  uint32_t* m_wf = b->h_meta + 10 * S;
-  const bool watched = b->align.window != 0;
-  uint32_t acq_n[2][kBrokerAcquirePerTick];          // live alignment: the probe lengths of this tick's estimates
-  const bool metered = b->meter.on;
-  unsigned fb_closing = 0;                           // sessions whose blocks ended without a flush block (meter: see below)
-  unsigned active = 0, max_nf = 0, fb_active = 0, max_nb = 0;
-  uint64_t frames = 0;
-  b->jobs.clear();
+}
+
+// scan, a held slot (live alignment): nothing is taken from a held stream.  Once its probe is there (or its flush asked
+// for) and no estimate of it is under way, its probes are staged, at most kBrokerAcquirePerTick slots a tick; the rest
+// wait.  A flush with nothing on a pad releases the stream at once: no device work.
+static void broker_scan_held(peaq_broker* b, TickPlan& pl, int sid, BrokerSlot& sl) {
+  if (sl.acquiring || !broker_probe_ready(b, sl)) return;
+  const uint64_t have[2] = {sl.framer.pad[0].total, sl.framer.pad[1].total};
+  if (!have[0] || !have[1]) {
+    sl.delay = live_delay_acquired(b->align.probe, have, nullptr);
+    sl.framer.release(sl.delay.skip_ref, sl.delay.skip_test);   // (0, 0)
+    return;
+  }
+  if (pl.n_acq == kBrokerAcquirePerTick) return;
+  const size_t i = pl.n_acq++;
+  for (int p = 0; p < 2; ++p) {
+    pl.acq_n[p][i] = static_cast<uint32_t>(std::min<uint64_t>(have[p], b->align.probe));
+    std::memcpy(b->a_hprobe[p] + i * (size_t)b->align.probe * b->channels, sl.framer.pad[p].at(0, b->channels),
+                (size_t)pl.acq_n[p][i] * b->channels * sizeof(float));
+  }
+  b->a_pending.push_back(BrokerAcquire{sid, sl.epoch, {have[0], have[1]}});
+  sl.acquiring = true;
+}
+
+// scan, a slot whose stream runs: its windows of this tick (take_slot_windows, peaq_host.h) into the plan, the rows of
+// the meta table and h_win.  The samples are copied by the stage phase: only the positions are taken here.
+static void broker_scan_slot(peaq_broker* b, TickPlan& pl, int sid, BrokerSlot& sl) {
+  const SlotTake t = take_slot_windows(sl.framer, sl.flush, sl.meter, b->meter.on, b->advanced != 0, kBrokerMaxFrames,
+                                       kBrokerMaxBlocks);
+  const BrokerMeta& mt = b->meta;
+  const uint32_t slot = static_cast<uint32_t>(sid);
+  const uint32_t tot_f = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;   // (UINT_MAX: the flush is not known yet)
+  const uint32_t tot_b = sl.meter.ended ? sl.meter.total[kUnitBlock] : UINT_MAX;
+  BrokerJob job{sid, 0, 0, t.fft, t.fb};
+  if (t.fft.count) {
+    const unsigned i = job.fft_idx = pl.active++;
+    mt.host(BrokerMeta::kNRef)[i] = static_cast<uint32_t>(t.fft.valid[0]);
+    mt.host(BrokerMeta::kNTest)[i] = static_cast<uint32_t>(t.fft.valid[1]);
+    mt.host(BrokerMeta::kFrame0)[i] = t.fft.first;
+    mt.host(BrokerMeta::kNFrames)[i] = t.fft.count;
+    mt.host(BrokerMeta::kSlot)[i] = slot;
+    mt.host(BrokerMeta::kTotalFrames)[i] = tot_f;
+    mt.host(BrokerMeta::kWatchFrames)[i] = t.fft.flush ? 0 : t.fft.count;
+    pl.frames += t.fft.count;
+    pl.max_nf = std::max(pl.max_nf, t.fft.count);
+  }
+  if (t.closing) {                                   // (filled from the far end; the stage phase moves it up)
+    const unsigned at = (unsigned)b->max_sessions - 1 - pl.fb_closing++;
+    b->h_win[at] = FbPairWindow{tot_b, 0, 0, slot};
+    mt.host(BrokerMeta::kFbTotalFrames)[at] = tot_f;
+    mt.host(BrokerMeta::kFbTotalBlocks)[at] = tot_b;
+  }
+  if (t.fb.count) {
+    const unsigned i = job.fb_idx = pl.fb_active++;
+    mt.host(BrokerMeta::kFbNRef)[i] = static_cast<uint32_t>(t.fb.valid[0]);
+    mt.host(BrokerMeta::kFbNTest)[i] = static_cast<uint32_t>(t.fb.valid[1]);
+    mt.host(BrokerMeta::kFbTotalFrames)[i] = tot_f;
+    mt.host(BrokerMeta::kFbTotalBlocks)[i] = tot_b;
+    b->h_win[i] = FbPairWindow{t.fb.first, t.fb.count, t.fb.prev_blocks, slot};
+    pl.max_nb = std::max(pl.max_nb, t.fb.count);
+  }
+  if (!t.fft.count && !t.fb.count) return;
+  pl.jobs.push_back(job);
+  if (sl.t_ready_us >= 0.) b->parked_wait_us.push_back((float)(pl.t_tick - sl.t_ready_us));
+  // more whole units left behind (the per-tick cap)?  They have been waiting since now at the latest.
+  sl.t_ready_us = (sl.framer.ready() || sl.flush.requested) ? pl.t_tick : -1.;
+}
+
+// scan: every open slot under its lock
+static void broker_scan(peaq_broker* b, TickPlan& pl) {
+  pl.t_tick = now_us();
   for (int sid = 0; sid < b->max_sessions; ++sid) {
     BrokerSlot& sl = *b->slots[sid];
     std::lock_guard<std::mutex> lock(sl.mu);
     if (!sl.open) continue;
-    if (sl.framer.held) {
-      // live alignment: nothing is taken from a held stream.  Once its probe is there (or its flush asked for) and no
-      // estimate of it is under way, its probes are staged, at most kBrokerAcquirePerTick slots a tick; the rest wait.
-      const bool empty_pad = !sl.framer.pad[0].total || !sl.framer.pad[1].total;
-      if (!sl.acquiring && empty_pad && broker_probe_ready(b, sl)) {
-        // (a flush with nothing on a pad: the record the aligner documents for an empty signal, no device work)
-        peaq_live_delay d{};
-        live_align_plan(b->align.probe, sl.framer.pad[0].total, sl.framer.pad[1].total, 0, &d);
-        d.acquired = 1;
-        sl.delay = d;
-        sl.framer.release(0, 0);
-      } else if (!sl.acquiring && b->a_pending.size() < kBrokerAcquirePerTick && broker_probe_ready(b, sl)) {
-        const size_t i = b->a_pending.size();
-        BrokerAcquire q;
-        q.sid = sid;
-        q.epoch = sl.epoch;
-        for (int p = 0; p < 2; ++p) {
-          q.have[p] = sl.framer.pad[p].total;
-          acq_n[p][i] = static_cast<uint32_t>(std::min<uint64_t>(q.have[p], b->align.probe));
-          if (acq_n[p][i])
-            std::memcpy(b->a_hprobe[p] + i * (size_t)b->align.probe * b->channels, sl.framer.pad[p].at(0, b->channels),
-                        (size_t)acq_n[p][i] * b->channels * sizeof(float));
-        }
-        b->a_pending.push_back(q);
-        sl.acquiring = true;
-      }
-      if (sl.framer.held) continue;
-    }
-    BrokerJob job;
-    job.sid = sid;
-    // ---- at most one window per kind: whole units (do_processing), else, once, the zero-padded unit of
-    // do_flush.  The samples are copied further down: only the positions are taken here. ----------------
-    const bool flush_fft = sl.flush_requested && !sl.fft_flushed;
-    if (metered && sl.flush_requested && !sl.meter.ended) sl.meter.end(sl.framer);   // the stream's end is known from here on
-    job.fft = sl.framer.take(kUnitFrame, kBrokerMaxFrames, flush_fft);
-    if (flush_fft && (job.fft.flush || !job.fft.count)) sl.fft_flushed = true;   // (no whole frame was left)
-    if (job.fft.count) {
-      job.fft_idx = active;
-      m_nref[active] = static_cast<uint32_t>(job.fft.valid[0]);
-      m_ntest[active] = static_cast<uint32_t>(job.fft.valid[1]);
-      m_f0[active] = job.fft.first;
-      m_nf[active] = job.fft.count;
-      m_slot[active] = static_cast<uint32_t>(sid);
-      m_tot_f[active] = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;
-      m_wf[active] = job.fft.flush ? 0 : job.fft.count;
-      frames += job.fft.count;
-      max_nf = std::max(max_nf, job.fft.count);
-      ++active;
-    }
-    if (b->advanced) {
-      // With the meter on the two paths of a stream stay at a common sample horizon, so that a window's two halves
-      // meet in the delivered ring: the blocks go no further than the frame after the last one taken, 1024 (frames + 2)
-      // samples.  Whatever blocks are whole while no frame is lie below that, so nothing waits that a tick without the
-      // meter would take unless a frame waits too; and 48 blocks a tick outrun 8 frames.  The cap holds through a
-      // flush's backlog as well, until the stream's last frame has been taken (above, in this tick at the latest):
-      // only the tail of the blocks, and the flush block, run free.
-      const bool capped = metered && (!sl.meter.ended || sl.framer.done[kUnitFrame] < sl.meter.total[kUnitFrame]);
-      const bool flush_fb = sl.flush_requested && !sl.fb_flushed && !capped;
-      unsigned fb_cap = kBrokerMaxBlocks;
-      if (capped) {
-        const uint64_t reach = 1024ull * ((uint64_t)sl.framer.done[kUnitFrame] + 2) / kFbFrame;
-        const uint64_t room = reach > sl.framer.done[kUnitBlock] ? reach - sl.framer.done[kUnitBlock] : 0;
-        fb_cap = (unsigned)std::min<uint64_t>(room, kBrokerMaxBlocks);
-      }
-      if (fb_cap) job.fb = sl.framer.take(kUnitBlock, fb_cap, flush_fb);
-      if (flush_fb && (job.fb.flush || !job.fb.count)) {
-        sl.fb_flushed = true;
-        // the blocks ended without a flush block: the windows that run to the last block are delivered by an entry
-        // without units, behind this tick's own in the meter's launch (the back ends never see it).  (A window whose
-        // streaming end fell on the last block was stored then already; this stores the same fields again.)
-        if (metered && !job.fb.count && sl.meter.total[kUnitFrame]) {
-          const unsigned at = (unsigned)S - 1 - fb_closing++;      // (filled from the far end; moved up below)
-          b->h_win[at] = FbPairWindow{sl.meter.total[kUnitBlock], 0, 0, static_cast<uint32_t>(sid)};
-          m_fb_tot_f[at] = sl.meter.total[kUnitFrame];
-          m_fb_tot_b[at] = sl.meter.total[kUnitBlock];
-        }
-      }
-      if (job.fb.count) {
-        m_fb_tot_f[fb_active] = sl.meter.ended ? sl.meter.total[kUnitFrame] : UINT_MAX;
-        m_fb_tot_b[fb_active] = sl.meter.ended ? sl.meter.total[kUnitBlock] : UINT_MAX;
-        job.fb_idx = fb_active;
-        m_fb_nref[fb_active] = static_cast<uint32_t>(job.fb.valid[0]);
-        m_fb_ntest[fb_active] = static_cast<uint32_t>(job.fb.valid[1]);
-        b->h_win[fb_active] =
-            FbPairWindow{job.fb.first, job.fb.count, job.fb.prev_blocks, static_cast<uint32_t>(sid)};
-        max_nb = std::max(max_nb, job.fb.count);
-        ++fb_active;
-      }
-    }
-    if (sl.flush_requested && sl.fft_flushed && (!b->advanced || sl.fb_flushed))
-      sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
-    if (job.fft.count || job.fb.count) {
-      b->jobs.push_back(job);
-      if (sl.t_ready_us >= 0.) b->parked_wait_us.push_back((float)(t_tick - sl.t_ready_us));
-      // more whole units left behind (the per-tick cap)?  They have been waiting since now at the latest.
-      sl.t_ready_us = (sl.framer.ready() || sl.flush_requested) ? t_tick : -1.;
-    }
+    if (sl.framer.held) broker_scan_held(b, pl, sid, sl);
+    if (!sl.framer.held) broker_scan_slot(b, pl, sid, sl);
   }
-  ++b->n_ticks;
-  const unsigned n_acq = (unsigned)b->a_pending.size();
-  if (!active && !fb_active && !fb_closing && !n_acq) return PEAQ_OK;
-  for (unsigned i = 0; i < fb_closing; ++i) {        // the entries without units: behind the tick's own
-    const unsigned at = (unsigned)S - 1 - i, to = fb_active + i;
+}
+
+// stage: the meter's entries without units go behind the tick's own; the sessions' new samples into the pinned staging
+// buffers; then drop what both consumers are done with.  (Only ticks consume, and ticks are serialised: the positions
+// the scan recorded stay valid; a concurrent push may reallocate a FIFO, hence the slot lock around each copy.)
+// Then the tick's device time begins, and the meta table's rows go up.
+static int broker_stage(peaq_broker* b, const TickPlan& pl) {
+  for (unsigned i = 0; i < pl.fb_closing; ++i) {
+    const unsigned at = (unsigned)b->max_sessions - 1 - i, to = pl.fb_active + i;
     b->h_win[to] = b->h_win[at];
-    m_fb_tot_f[to] = m_fb_tot_f[at];
-    m_fb_tot_b[to] = m_fb_tot_b[at];
+    for (BrokerMeta::Row r : {BrokerMeta::kFbTotalFrames, BrokerMeta::kFbTotalBlocks}) b->meta.host(r)[to] = b->meta.host(r)[at];
   }
-  // ---- the sessions' new samples into the pinned staging buffers; then drop what both consumers are done
-  // with.  (Only ticks consume, and ticks are serialised: the positions recorded above stay valid; a
-  // concurrent push may reallocate a FIFO, hence the slot lock around each copy.) ----------------------
-  b->stagers->run(b->jobs.size(), [b](size_t i) {
-    const BrokerJob& j = b->jobs[i];
+  b->stagers->run(pl.jobs.size(), [b, &pl](size_t i) {
+    const BrokerJob& j = pl.jobs[i];
     BrokerSlot& sl = *b->slots[j.sid];
     std::lock_guard<std::mutex> lock(sl.mu);
     if (j.fft.count) broker_stage_copy(b, sl, b->fft, j.fft_idx, j.fft);
@@ -445,132 +439,138 @@ static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
     sl.framer.trim();
   });
   HIP_TRY(hipEventRecord(b->t_begin, b->stream));
-  HIP_TRY(hipMemcpyAsync(b->d_meta.p, b->h_meta, (watched ? kMetaRows : metered ? 10 : 7) * S * sizeof(uint32_t), hipMemcpyHostToDevice,
-                         b->stream));
-  // the meter's launches: the live back ends leave this tick's records at [launch index][unit of the tick], and one
-  // small kernel behind each back end walks every session's units through its open windows
-  RunOutputs live;
-  MeterArgs ma{};
-  if (metered) {
-    live.live.frames = b->m_ftrc.as<FrameTrace>();
-    live.live.frame_stride = kBrokerMaxFrames;
-    live.live.blocks = b->m_btrc.as<BlockTrace>();
-    live.live.block_stride = kBrokerMaxBlocks;
-    live.live.n_uniform = UINT_MAX;
-    ma.open = b->m_open.as<PointSnap>();
-    ma.ring = b->m_ring.as<PointSnap>();
-    ma.window = b->meter.window;
-    ma.hop = b->meter.hop;
-    ma.k_open = b->meter.k_open;
-    ma.ring_depth = b->meter.ring;
-    ma.frames = live.live.frames;
-    ma.frame_stride = kBrokerMaxFrames;
-    ma.blocks = live.live.blocks;
-    ma.block_stride = kBrokerMaxBlocks;
-  }
-  const uint32_t* d_meta = b->d_meta.as<uint32_t>();
+  HIP_TRY(b->meta.upload(b->meter.on, b->align.window != 0, b->stream));
+  return PEAQ_OK;
+}
+
+// launch, FFT path: samples up; front end, watch, back end over the tick's `active` pairs.  With the meter on the live
+// back end leaves this tick's records at [launch index][unit of the tick], and one small kernel behind it walks every
+// session's units through its open windows (the filter-bank path below does the same).
+static int broker_launch_fft(peaq_broker* b, const TickPlan& pl) {
+  if (!pl.active) return PEAQ_OK;
+  const BrokerMeta& mt = b->meta;
   const ModelSetup m = b->model();
-  if (active) {
-    const size_t stride = b->fft.samples * b->channels;
-    for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(b->fft.d[p].p, b->fft.h[p], active * stride * sizeof(float), hipMemcpyHostToDevice,
-                             b->stream));
-    FrontendArgs fa = m.frontend();
-    fa.ref = b->fft.d[0].as<float>();
-    fa.test = b->fft.d[1].as<float>();
-    fa.pair_stride = b->fft.samples;
-    fa.n_ref = d_meta;
-    fa.n_test = d_meta + S;
-    fa.pair_frame0 = d_meta + 2 * S;
-    fa.pair_nframes = d_meta + 3 * S;
-    fa.frames_per_launch = max_nf;
-    fa.records = b->records.as<double>();
-    HIP_TRY(launch_frontend(m.fft_bands(), fa, active, b->stream));
-    if (watched) {
-      WatchArgs wa{};
-      wa.ref = fa.ref;
-      wa.test = fa.test;
-      wa.pair_stride = fa.pair_stride;
-      wa.channels = b->channels;
-      wa.n_frames = max_nf;
-      wa.window = b->align.window;
-      wa.rows = b->w_rows.as<double>();
-      wa.row_stride = kBrokerMaxFrames;
-      wa.state = b->w_state.as<WatchState>();
-      wa.s_frames = d_meta + 10 * S;
-      wa.s_slot = d_meta + 4 * S;
-      HIP_TRY(launch_delay_watch(wa, active, b->stream));
-    }
-    BackendArgs ba = m.backend(fa);
-    ba.frames_per_launch = max_nf;
-    ba.state = b->state.as<PairState>();
-    ba.pair_slot = d_meta + 4 * S;
-    HIP_TRY(launch_backend(ba, active, b->stream, live));
-    if (metered) {
-      MeterArgs mf = ma;
-      mf.rec_stride = max_nf;
-      mf.s_unit0 = d_meta + 2 * S;
-      mf.s_nunits = d_meta + 3 * S;
-      mf.s_slot = d_meta + 4 * S;
-      mf.s_total_frames = mf.s_total_units = d_meta + 7 * S;
-      HIP_TRY(launch_meter_fft(mf, b->advanced != 0, b->records.as<double>(), b->channels, active, b->stream));
-    }
+  const size_t stride = b->fft.samples * b->channels;
+  for (int p = 0; p < 2; ++p)
+    HIP_TRY(hipMemcpyAsync(b->fft.d[p].p, b->fft.h[p], pl.active * stride * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  FrontendArgs fa = m.frontend();
+  fa.ref = b->fft.d[0].as<float>();
+  fa.test = b->fft.d[1].as<float>();
+  fa.pair_stride = b->fft.samples;
+  fa.n_ref = mt.dev(BrokerMeta::kNRef);
+  fa.n_test = mt.dev(BrokerMeta::kNTest);
+  fa.pair_frame0 = mt.dev(BrokerMeta::kFrame0);
+  fa.pair_nframes = mt.dev(BrokerMeta::kNFrames);
+  fa.frames_per_launch = pl.max_nf;
+  fa.records = b->records.as<double>();
+  HIP_TRY(launch_frontend(m.fft_bands(), fa, pl.active, b->stream));
+  if (b->align.window) {
+    WatchArgs wa = b->a_buf.watch(fa, b->align.window, pl.max_nf, kBrokerMaxFrames);
+    wa.s_frames = mt.dev(BrokerMeta::kWatchFrames);
+    wa.s_slot = mt.dev(BrokerMeta::kSlot);
+    HIP_TRY(launch_delay_watch(wa, pl.active, b->stream));
   }
-  if (!fb_active && fb_closing)
-    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, fb_closing * sizeof(FbPairWindow), hipMemcpyHostToDevice, b->stream));
-  if (fb_active) {
+  BackendArgs ba = m.backend(fa);
+  ba.frames_per_launch = pl.max_nf;
+  ba.state = b->state.as<PairState>();
+  ba.pair_slot = mt.dev(BrokerMeta::kSlot);
+  HIP_TRY(launch_backend(ba, pl.active, b->stream, b->m_buf.outputs(b->meter)));
+  if (!b->meter.on) return PEAQ_OK;
+  MeterArgs mf = b->m_buf.args(b->meter);
+  mf.rec_stride = pl.max_nf;
+  mf.s_unit0 = mt.dev(BrokerMeta::kFrame0);
+  mf.s_nunits = mt.dev(BrokerMeta::kNFrames);
+  mf.s_slot = mt.dev(BrokerMeta::kSlot);
+  mf.s_total_frames = mf.s_total_units = mt.dev(BrokerMeta::kTotalFrames);
+  HIP_TRY(launch_meter_fft(mf, b->advanced != 0, b->records.as<double>(), b->channels, pl.active, b->stream));
+  return PEAQ_OK;
+}
+
+// launch, filter-bank path: samples and windows up; front end, back end over the tick's `fb_active` pairs; the meter
+// over them and the entries without units behind them (whose windows go up alone in a tick that has no pair)
+static int broker_launch_fb(peaq_broker* b, const TickPlan& pl) {
+  const unsigned n_win = pl.fb_active + pl.fb_closing;
+  const size_t win_bytes = n_win * sizeof(FbPairWindow);
+  if (!pl.fb_active && n_win) HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, win_bytes, hipMemcpyHostToDevice, b->stream));
+  if (pl.fb_active) {
+    const BrokerMeta& mt = b->meta;
+    const ModelSetup m = b->model();
     const size_t stride = b->fbs.samples * b->channels;
     for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(b->fbs.d[p].p, b->fbs.h[p], fb_active * stride * sizeof(float), hipMemcpyHostToDevice,
+      HIP_TRY(hipMemcpyAsync(b->fbs.d[p].p, b->fbs.h[p], pl.fb_active * stride * sizeof(float), hipMemcpyHostToDevice,
                              b->stream));
-    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, (fb_active + fb_closing) * sizeof(FbPairWindow), hipMemcpyHostToDevice,
-                           b->stream));
+    HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, win_bytes, hipMemcpyHostToDevice, b->stream));
     FbFrontArgs ff = m.fb_frontend();
     ff.ref = b->fbs.d[0].as<float>();
     ff.test = b->fbs.d[1].as<float>();
     ff.pair_stride = b->fbs.samples;
-    ff.n_ref = d_meta + 5 * S;
-    ff.n_test = d_meta + 6 * S;
-    ff.blocks_per_launch = max_nb;
+    ff.n_ref = mt.dev(BrokerMeta::kFbNRef);
+    ff.n_test = mt.dev(BrokerMeta::kFbNTest);
+    ff.blocks_per_launch = pl.max_nb;
     ff.fbstate = b->fbstate.as<FbSignalState>();
     ff.hp_scratch = b->hp_rows.as<double>();
     ff.hp_row_stride = kBrokerRowStride;
     ff.records = b->fb_records.as<double>();
     ff.windows = b->d_win.as<FbPairWindow>();
-    HIP_TRY(launch_fb_frontend(ff, fb_active, b->stream));
+    HIP_TRY(launch_fb_frontend(ff, pl.fb_active, b->stream));
     FbBackendArgs fbk = m.fb_backend(ff);
-    fbk.blocks_per_launch = max_nb;
+    fbk.blocks_per_launch = pl.max_nb;
     fbk.state = b->state.as<PairState>();
-    HIP_TRY(launch_fb_backend(fbk, fb_active, b->stream, live));
+    HIP_TRY(launch_fb_backend(fbk, pl.fb_active, b->stream, b->m_buf.outputs(b->meter)));
   }
-  if (metered && fb_active + fb_closing) {
-    MeterArgs mb = ma;
-    mb.s_win = b->d_win.as<FbPairWindow>();
-    mb.s_total_frames = d_meta + 8 * S;
-    mb.s_total_units = d_meta + 9 * S;
-    HIP_TRY(launch_meter_fb(mb, b->channels, fb_active + fb_closing, b->stream));
-  }
-  if (n_acq) {
-    // live alignment: one estimate over this tick's probes, its records copied to pinned memory -- enqueued, not waited
-    // for: the next tick reads them after its wait for `staged`
-    const size_t row = (size_t)b->align.probe * b->channels;
-    for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(b->a_probe[p].p, b->a_hprobe[p], n_acq * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    if (int rc = peaq_batch_estimate_delay(c, b->channels, (int)n_acq, b->a_probe[0].as<float>(), b->a_probe[1].as<float>(),
-                                           b->align.probe, acq_n[0], acq_n[1], 0, b->align.max_lag,
-                                           b->a_rec.as<peaq_delay>(), b->stream))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(b->a_hrec, b->a_rec.p, n_acq * sizeof(peaq_delay), hipMemcpyDeviceToHost, b->stream));
-  }
+  if (!b->meter.on || !n_win) return PEAQ_OK;
+  MeterArgs mb = b->m_buf.args(b->meter);
+  mb.s_win = b->d_win.as<FbPairWindow>();
+  mb.s_total_frames = b->meta.dev(BrokerMeta::kFbTotalFrames);
+  mb.s_total_units = b->meta.dev(BrokerMeta::kFbTotalBlocks);
+  HIP_TRY(launch_meter_fb(mb, b->channels, n_win, b->stream));
+  return PEAQ_OK;
+}
+
+// launch, acquisition (live alignment): one estimate over this tick's probes, its records copied to pinned memory --
+// enqueued, not waited for: the next tick reads them after its wait for `staged`
+static int broker_launch_acquire(peaq_broker* b, const TickPlan& pl) {
+  if (!pl.n_acq) return PEAQ_OK;
+  const LiveAlignBuffers& a = b->a_buf;
+  const size_t row = (size_t)b->align.probe * b->channels;
+  for (int p = 0; p < 2; ++p)
+    HIP_TRY(hipMemcpyAsync(a.probe[p].p, b->a_hprobe[p], pl.n_acq * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  if (int rc = peaq_batch_estimate_delay(b->ctx, b->channels, (int)pl.n_acq, a.probe[0].as<float>(), a.probe[1].as<float>(),
+                                         b->align.probe, pl.acq_n[0], pl.acq_n[1], 0, b->align.max_lag,
+                                         a.rec.as<peaq_delay>(), b->stream))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(b->a_hrec, a.rec.p, pl.n_acq * sizeof(peaq_delay), hipMemcpyDeviceToHost, b->stream));
+  return PEAQ_OK;
+}
+
+// finish: the events the next tick waits for and times by, the counters, the host part of this tick
+static int broker_finish(peaq_broker* b, const TickPlan& pl, unsigned* n_active_out) {
   HIP_TRY(hipEventRecord(b->t_end, b->stream));
   HIP_TRY(hipEventRecord(b->staged, b->stream));
   b->staged_pending = true;
-  b->parked_host_us = now_us() - t_tick;
+  b->parked_host_us = now_us() - pl.t_tick;
   ++b->n_launches;
-  b->n_frames += frames;
-  b->max_active = std::max(b->max_active, std::max(active, fb_active));
-  if (n_active_out) *n_active_out = std::max(active, fb_active);
+  b->n_frames += pl.frames;
+  const unsigned n_active = std::max(pl.active, pl.fb_active);
+  b->max_active = std::max(b->max_active, n_active);
+  if (n_active_out) *n_active_out = n_active;
   return PEAQ_OK;
+}
+
+static int broker_tick_locked(peaq_broker* b, unsigned* n_active_out) {
+  TickPlan pl(b->jobs);
+  if (n_active_out) *n_active_out = 0;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  if (int rc = broker_settle(b)) return rc;
+  broker_release_acquired(b);
+  broker_scan(b, pl);
+  ++b->n_ticks;
+  if (pl.idle()) return PEAQ_OK;
+  if (int rc = broker_stage(b, pl)) return rc;
+  if (int rc = broker_launch_fft(b, pl)) return rc;
+  if (int rc = broker_launch_fb(b, pl)) return rc;
+  if (int rc = broker_launch_acquire(b, pl)) return rc;
+  return broker_finish(b, pl, n_active_out);
 }
 
 // one tick under tick_mu; a failure is remembered and stops the broker for good
@@ -621,10 +621,8 @@ extern "C" int peaq_broker_create(peaq_ctx* c, int advanced, int channels, doubl
   for (int i = 0; i < max_sessions; ++i) b->slots.push_back(new BrokerSlot);
   const size_t S = (size_t)max_sessions;
   int rc = [&]() -> int {
-    int r = b->fft.alloc(S, kBrokerStageSamples, channels);
-    if (r != PEAQ_OK) return r;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_meta), kMetaRows * S * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(b->d_meta.reserve(kMetaRows * S * sizeof(uint32_t)));
+    if (int r = b->fft.alloc(S, kBrokerStageSamples, channels)) return r;
+    if (int r = b->meta.alloc(S)) return r;
     HIP_TRY(b->records.reserve(S * kBrokerMaxFrames * channels * kRecDoubles * sizeof(double)));
     HIP_TRY(b->state.reserve(S * sizeof(PairState)));
     HIP_TRY(b->result.reserve(sizeof(ResultRecord)));
@@ -634,8 +632,7 @@ extern "C" int peaq_broker_create(peaq_ctx* c, int advanced, int channels, doubl
     HIP_TRY(hipEventCreate(&b->t_end));
     HIP_TRY(launch_state_init(b->state.as<PairState>(), b->advanced, max_sessions, b->stream));
     if (b->advanced) {
-      r = b->fbs.alloc(S, kBrokerFbStageSamples, channels);
-      if (r != PEAQ_OK) return r;
+      if (int r = b->fbs.alloc(S, kBrokerFbStageSamples, channels)) return r;
       const size_t n_signals = S * channels * 2;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_win), S * sizeof(FbPairWindow), hipHostMallocDefault));
       HIP_TRY(b->d_win.reserve(S * sizeof(FbPairWindow)));
@@ -735,7 +732,6 @@ extern "C" void peaq_broker_destroy(peaq_broker* b) {
   (void)peaq_broker_stop(b);
   (void)hipSetDevice(b->ctx->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  if (b->h_meta) (void)hipHostFree(b->h_meta);
   if (b->h_win) (void)hipHostFree(b->h_win);
   for (int p = 0; p < 2; ++p)
     if (b->a_hprobe[p]) (void)hipHostFree(b->a_hprobe[p]);
@@ -745,7 +741,7 @@ extern "C" void peaq_broker_destroy(peaq_broker* b) {
   if (b->t_end) (void)hipEventDestroy(b->t_end);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   for (BrokerSlot* s : b->slots) delete s;
-  delete b;                         // (the staging and device buffers go with it)
+  delete b;                         // (the staging buffers, the meta table and the device buffers go with it)
 }
 
 extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
@@ -785,14 +781,14 @@ extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
       HIP_TRY(hipMemsetAsync(b->fbstate.as<FbSignalState>() + (size_t)sid * b->channels * 2, 0,
                              (size_t)b->channels * 2 * sizeof(FbSignalState), b->stream));
     if (b->meter.on) {                                 // a fresh meter: every snapshot as launch_points_init leaves it
-      HIP_TRY(launch_points_init(b->m_open.as<PointSnap>() + (size_t)sid * b->meter.k_open, b->meter.k_open, b->stream));
-      HIP_TRY(launch_points_init(b->m_ring.as<PointSnap>() + (size_t)sid * b->meter.ring, b->meter.ring, b->stream));
+      HIP_TRY(launch_points_init(b->m_buf.open.as<PointSnap>() + (size_t)sid * b->meter.k_open, b->meter.k_open, b->stream));
+      HIP_TRY(launch_points_init(b->m_buf.ring.as<PointSnap>() + (size_t)sid * b->meter.ring, b->meter.ring, b->stream));
     }
     if (b->align.window)                               // a fresh watch: index 0, nothing complete
-      HIP_TRY(hipMemsetAsync(b->w_state.as<WatchState>() + sid, 0, sizeof(WatchState), b->stream));
+      HIP_TRY(hipMemsetAsync(b->a_buf.state.as<WatchState>() + sid, 0, sizeof(WatchState), b->stream));
     sl.meter = MeterStream();
     sl.open = true;
-    sl.flush_requested = sl.fft_flushed = sl.fb_flushed = false;
+    sl.flush.clear();
     sl.framer.reset(b->advanced, b->channels);
     sl.delay = peaq_live_delay{};
     sl.acquiring = false;
@@ -811,16 +807,12 @@ static BrokerSlot* broker_slot(peaq_broker* b, int sid) {
 }
 
 extern "C" int peaq_broker_close(peaq_broker* b, int session_id) {
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    if (!sh) return fail(PEAQ_ERR_ARG, "peaq_broker_close: bad session id");
-    const int rc = peaq_broker_close(sh, local);
-    if (rc == PEAQ_OK) {
+  if (const auto rc = broker_forward(b, session_id, "peaq_broker_close", peaq_broker_close)) {
+    if (*rc == PEAQ_OK) {
       std::lock_guard<std::mutex> place(b->tick_mu);
       --b->shard_open[session_id % (int)b->shards.size()];
     }
-    return rc;
+    return *rc;
   }
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_close: bad broker or session id");
@@ -836,11 +828,9 @@ extern "C" int peaq_broker_close(peaq_broker* b, int session_id) {
 
 // pad_chain (gstpeaq.c:613-640): only queues; the device work happens on the next tick
 extern "C" int peaq_broker_push(peaq_broker* b, int session_id, int pad, const float* data, size_t n) {
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_push(sh, local, pad, data, n) : fail(PEAQ_ERR_ARG, "peaq_broker_push: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_push",
+                       [&](peaq_broker* sh, int id) { return peaq_broker_push(sh, id, pad, data, n); }))
+    return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_push: bad broker or session id");
   if (pad != 0 && pad != 1) return fail(PEAQ_ERR_ARG, "peaq_broker_push: pad must be 0 (ref) or 1 (test)");
@@ -882,18 +872,13 @@ extern "C" int peaq_broker_push(peaq_broker* b, int session_id, int pad, const f
 }
 
 extern "C" int peaq_broker_flush(peaq_broker* b, int session_id) {
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_flush(sh, local) : fail(PEAQ_ERR_ARG, "peaq_broker_flush: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_flush", peaq_broker_flush)) return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_flush: bad broker or session id");
   if (b->failed.load()) return broker_failed(b, "peaq_broker_flush");
   std::lock_guard<std::mutex> lock(sl->mu);
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_flush: session is not open");
-  sl->flush_requested = true;
-  sl->fft_flushed = sl->fb_flushed = false;
+  sl->flush.request();
   if (sl->t_ready_us < 0.) sl->t_ready_us = now_us();
   return PEAQ_OK;
 }
@@ -927,15 +912,13 @@ extern "C" int peaq_broker_tick(peaq_broker* b, unsigned* n_active) {
 static bool broker_slot_busy(const peaq_broker* b, BrokerSlot* sl) {
   std::lock_guard<std::mutex> lock(sl->mu);
   if (sl->framer.held) return sl->acquiring || broker_probe_ready(b, *sl);
-  return sl->framer.ready() || sl->flush_requested;
+  return sl->framer.ready() || sl->flush.requested;
 }
 
 extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* out) {
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_results(sh, local, out) : fail(PEAQ_ERR_ARG, "peaq_broker_results: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_results",
+                       [&](peaq_broker* sh, int id) { return peaq_broker_results(sh, id, out); }))
+    return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_results: bad broker, session id or out");
   std::lock_guard<std::mutex> tick(b->tick_mu);
@@ -956,6 +939,20 @@ extern "C" int peaq_broker_results(peaq_broker* b, int session_id, peaq_result* 
   return PEAQ_OK;
 }
 
+// `what` ("the meter", "the alignment") shapes the launch of every slot: entry `who` sets it while no tick thread runs
+// and no session is open (the caller holds tick_mu)
+static int broker_not_begun(peaq_broker* b, const std::string& who, const char* what) {
+  if (b->running.load())
+    return fail(PEAQ_ERR_ARG, who + ": the tick thread runs; set " + what + " before peaq_broker_start");
+  for (int sid = 0; sid < b->max_sessions; ++sid) {
+    std::lock_guard<std::mutex> lock(b->slots[sid]->mu);
+    if (b->slots[sid]->open)
+      return fail(PEAQ_ERR_ARG, who + ": session " + std::to_string(sid) + " is open; set " + what +
+                                    " before the first peaq_broker_open");
+  }
+  return PEAQ_OK;
+}
+
 // One geometry for all sessions of the broker, because it shapes the launch: before the first open and before start.
 extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cfg) {
   if (!b) return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: broker is NULL");
@@ -968,31 +965,14 @@ extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cf
     return PEAQ_OK;
   }
   std::lock_guard<std::mutex> tick(b->tick_mu);
-  if (b->running.load())
-    return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: the tick thread runs; set the meter before peaq_broker_start");
-  for (int sid = 0; sid < b->max_sessions; ++sid) {
-    std::lock_guard<std::mutex> lock(b->slots[sid]->mu);
-    if (b->slots[sid]->open)
-      return fail(PEAQ_ERR_ARG, "peaq_broker_set_meter: session " + std::to_string(sid) +
-                                    " is open; set the meter before the first peaq_broker_open");
-  }
+  if (int rc = broker_not_begun(b, "peaq_broker_set_meter", "the meter")) return rc;
   b->meter.on = false;
   if (off) return PEAQ_OK;
   MeterGeometry g;
   g.set(*cfg);
-  const size_t S = (size_t)b->max_sessions;
   HIP_TRY(hipSetDevice(b->ctx->device));
   HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
-  HIP_TRY(b->m_open.reserve(S * g.k_open * sizeof(PointSnap)));
-  HIP_TRY(b->m_ring.reserve(S * g.ring * sizeof(PointSnap)));
-  HIP_TRY(b->m_readout.reserve((size_t)g.ring * sizeof(ResultRecord)));
-  HIP_TRY(b->m_ftrc.reserve(S * kBrokerMaxFrames * sizeof(FrameTrace)));
-  if (b->advanced) HIP_TRY(b->m_btrc.reserve(S * kBrokerMaxBlocks * sizeof(BlockTrace)));
-  try {
-    b->m_host.resize(g.ring);
-  } catch (const std::bad_alloc&) {
-    return fail(PEAQ_ERR_NOMEM, "out of host memory");
-  }
+  if (int rc = b->m_buf.reserve(g, (size_t)b->max_sessions, kBrokerMaxFrames, kBrokerMaxBlocks, b->advanced != 0)) return rc;
   b->meter = g;
   b->meter.on = true;
   return PEAQ_OK;
@@ -1012,36 +992,24 @@ extern "C" int peaq_broker_set_align(peaq_broker* b, const peaq_live_align_confi
     return PEAQ_OK;
   }
   std::lock_guard<std::mutex> tick(b->tick_mu);
-  if (b->running.load())
-    return fail(PEAQ_ERR_ARG, who + ": the tick thread runs; set the alignment before peaq_broker_start");
-  for (int sid = 0; sid < b->max_sessions; ++sid) {
-    std::lock_guard<std::mutex> lock(b->slots[sid]->mu);
-    if (b->slots[sid]->open)
-      return fail(PEAQ_ERR_ARG, who + ": session " + std::to_string(sid) +
-                                    " is open; set the alignment before the first peaq_broker_open");
-  }
+  if (int rc = broker_not_begun(b, who, "the alignment")) return rc;
   b->align = LiveAlignGeometry();
   if (off) return PEAQ_OK;
-  const size_t S = (size_t)b->max_sessions;
   HIP_TRY(hipSetDevice(b->ctx->device));
   HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
-  if (cfg->max_lag) {
+  if (cfg->max_lag) {                                  // the pinned side of the probes and of their records
     const size_t bytes = (size_t)kBrokerAcquirePerTick * probe * b->channels * sizeof(float);
     for (int p = 0; p < 2; ++p) {
       if (b->a_hprobe[p]) (void)hipHostFree(b->a_hprobe[p]);
       b->a_hprobe[p] = nullptr;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->a_hprobe[p]), bytes, hipHostMallocDefault));
-      HIP_TRY(b->a_probe[p].reserve(bytes));
     }
-    HIP_TRY(b->a_rec.reserve(kBrokerAcquirePerTick * sizeof(peaq_delay)));
     if (!b->a_hrec)
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->a_hrec), kBrokerAcquirePerTick * sizeof(peaq_delay),
                             hipHostMallocDefault));
   }
-  if (cfg->watch_frames) {
-    HIP_TRY(b->w_rows.reserve(S * kBrokerMaxFrames * kWatchRow * sizeof(double)));
-    HIP_TRY(b->w_state.reserve(S * sizeof(WatchState)));
-  }
+  if (int rc = b->a_buf.reserve(*cfg, probe, b->channels, kBrokerAcquirePerTick, (size_t)b->max_sessions, kBrokerMaxFrames))
+    return rc;
   b->align.max_lag = cfg->max_lag;
   b->align.probe = probe;
   b->align.window = cfg->watch_frames;
@@ -1052,11 +1020,9 @@ extern "C" int peaq_broker_set_align(peaq_broker* b, const peaq_live_align_confi
 // acquisition, as peaq_broker_results drives a session to its end.
 extern "C" int peaq_broker_align_read(peaq_broker* b, int session_id, peaq_live_delay* out) {
   if (!b || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_align_read: NULL argument");
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_align_read(sh, local, out) : fail(PEAQ_ERR_ARG, "peaq_broker_align_read: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_align_read",
+                       [&](peaq_broker* sh, int id) { return peaq_broker_align_read(sh, id, out); }))
+    return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_align_read: bad session id " + std::to_string(session_id));
   std::lock_guard<std::mutex> tick(b->tick_mu);
@@ -1067,7 +1033,7 @@ extern "C" int peaq_broker_align_read(peaq_broker* b, int session_id, peaq_live_
     {
       std::lock_guard<std::mutex> lock(sl->mu);
       if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_align_read: session is not open");
-      if (!(sl->framer.held && sl->flush_requested)) break;
+      if (!(sl->framer.held && sl->flush.requested)) break;
     }
     if (int rc = broker_tick_checked(b, nullptr)) return rc;
   }
@@ -1081,11 +1047,9 @@ extern "C" int peaq_broker_align_read(peaq_broker* b, int session_id, peaq_live_
 // The slot's newest complete watch window as of the last tick enqueued (the call waits for it); it does not tick.
 extern "C" int peaq_broker_watch_read(peaq_broker* b, int session_id, peaq_delay_watch* out) {
   if (!b || !out) return fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: NULL argument");
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_watch_read(sh, local, out) : fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_watch_read",
+                       [&](peaq_broker* sh, int id) { return peaq_broker_watch_read(sh, id, out); }))
+    return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_watch_read: bad session id " + std::to_string(session_id));
   std::lock_guard<std::mutex> tick(b->tick_mu);
@@ -1096,7 +1060,7 @@ extern "C" int peaq_broker_watch_read(peaq_broker* b, int session_id, peaq_delay
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_watch_read: session is not open");
   HIP_TRY(hipSetDevice(b->ctx->device));
   WatchState st;
-  HIP_TRY(hipMemcpyAsync(&st, b->w_state.as<WatchState>() + session_id, sizeof st, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(&st, b->a_buf.state.as<WatchState>() + session_id, sizeof st, hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
   delay_watch_record(st, out);
   return PEAQ_OK;
@@ -1110,12 +1074,10 @@ extern "C" int peaq_broker_meter_read(peaq_broker* b, int session_id, peaq_meter
   if (dropped) *dropped = 0;
   if (cap < 0 || (cap > 0 && !out))
     return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
-  if (broker_is_multi(b)) {
-    int local;
-    peaq_broker* sh = broker_shard_of(b, session_id, &local);
-    return sh ? peaq_broker_meter_read(sh, local, out, cap, n_read, dropped)
-              : fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: bad session id");
-  }
+  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_meter_read", [&](peaq_broker* sh, int id) {
+        return peaq_broker_meter_read(sh, id, out, cap, n_read, dropped);
+      }))
+    return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
   if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: bad session id " + std::to_string(session_id));
   std::lock_guard<std::mutex> tick(b->tick_mu);
@@ -1124,8 +1086,8 @@ extern "C" int peaq_broker_meter_read(peaq_broker* b, int session_id, peaq_meter
   std::lock_guard<std::mutex> lock(sl->mu);
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_meter_read: session is not open");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  return sl->meter.read(sl->framer, b->meter, b->m_ring.as<PointSnap>() + (size_t)session_id * b->meter.ring, b->m_readout,
-                        b->m_host, b->channels, b->stream, b->cfg, out, cap, n_read, dropped);
+  return sl->meter.read(sl->framer, b->meter, b->m_buf.ring.as<PointSnap>() + (size_t)session_id * b->meter.ring,
+                        b->m_buf.readout, b->m_buf.host, b->channels, b->stream, b->cfg, out, cap, n_read, dropped);
 }
 
 extern "C" int peaq_broker_start(peaq_broker* b, unsigned period_us) {
@@ -1168,7 +1130,7 @@ extern "C" int peaq_broker_stats(peaq_broker* b, peaq_broker_stats_t* out) {
     // counts add up over the devices (max_active: the most sessions the node served in one tick period, each
     // device's own maximum); times: the worst device's maximum and 99th percentile, means weighted by their samples
     peaq_broker_stats_t acc{};
-    double host_w = 0., dev_w = 0.;
+    double tick_w = 0.;                                // (both tick means have a sample per launch)
     for (peaq_broker* sh : b->shards) {
       peaq_broker_stats_t s{};
       const int rc = peaq_broker_stats(sh, &s);
@@ -1186,13 +1148,14 @@ extern "C" int peaq_broker_stats(peaq_broker* b, peaq_broker_stats_t* out) {
       acc.latency_us_p99 = std::max(acc.latency_us_p99, s.latency_us_p99);
       acc.tick_host_us_mean += s.tick_host_us_mean * (double)s.launches;
       acc.tick_device_us_mean += s.tick_device_us_mean * (double)s.launches;
-      host_w += (double)s.launches;
-      dev_w += (double)s.launches;
+      tick_w += (double)s.launches;
       acc.latency_us_mean += s.latency_us_mean * (double)s.latency_samples;
       acc.latency_samples += s.latency_samples;
     }
-    if (host_w > 0.) acc.tick_host_us_mean /= host_w;
-    if (dev_w > 0.) acc.tick_device_us_mean /= dev_w;
+    if (tick_w > 0.) {
+      acc.tick_host_us_mean /= tick_w;
+      acc.tick_device_us_mean /= tick_w;
+    }
     if (acc.latency_samples) acc.latency_us_mean /= (double)acc.latency_samples;
     *out = acc;
     return PEAQ_OK;
@@ -1205,9 +1168,7 @@ extern "C" int peaq_broker_stats(peaq_broker* b, peaq_broker_stats_t* out) {
   out->worker_failed = b->failed.load() ? 1 : 0;
   if (b->staged_pending && !b->failed.load()) {        // settle the last tick's timing
     HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipEventSynchronize(b->staged));
-    b->staged_pending = false;
-    broker_settle_timing(b);
+    if (int rc = broker_settle(b)) return rc;
   }
   out->tick_host_us_max = b->h_host.max;
   out->tick_host_us_p99 = b->h_host.quantile(0.99);

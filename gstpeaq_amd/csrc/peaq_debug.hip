@@ -376,3 +376,50 @@ extern "C" int peaq_debug_stream_plan(int advanced, unsigned max_frames, unsigne
   *n_windows = n;
   return PEAQ_OK;
 }
+
+// Host only: one slot of the broker fed with sample counts alone, ticked the way broker_tick_locked ticks it.
+extern "C" int peaq_debug_broker_plan(int advanced, int metered, size_t n_events, const int* pad, const uint64_t* n_samples,
+                                      size_t max_rows, uint64_t* rows, size_t* n_rows) {
+  if (!n_rows || (n_events && (!pad || !n_samples)) || (max_rows && !rows))
+    return fail(PEAQ_ERR_ARG, "peaq_debug_broker_plan: NULL argument");
+  for (size_t k = 0; k < n_events; ++k)
+    if (pad[k] < -2 || pad[k] > 1)
+      return fail(PEAQ_ERR_ARG, "peaq_debug_broker_plan: pad must be 0 (ref), 1 (test), -1 (flush) or -2 (tick)");
+  StreamFramer fr;
+  fr.reset(advanced != 0, 1);
+  SlotFlush flush;
+  MeterStream meter;
+  size_t n = 0;
+  uint64_t n_ticks = 0;
+  auto note = [&](uint64_t kind, uint64_t first, uint64_t count, uint64_t v_ref, uint64_t v_test) {
+    if (n < max_rows) {
+      uint64_t* o = rows + n * PEAQ_DEBUG_BROKER_PLAN_FIELDS;
+      o[0] = n_ticks;
+      o[1] = kind;
+      o[2] = first;
+      o[3] = count;
+      o[4] = v_ref;
+      o[5] = v_test;
+    }
+    ++n;
+  };
+  auto tick = [&]() {                                // -> the tick took something
+    const SlotTake t = take_slot_windows(fr, flush, meter, metered != 0, advanced != 0, kBrokerMaxFrames, kBrokerMaxBlocks);
+    fr.trim();
+    if (t.fft.count) note(kUnitFrame, t.fft.first, t.fft.count, t.fft.valid[0], t.fft.valid[1]);
+    if (t.fb.count) note(kUnitBlock, t.fb.first, t.fb.count, t.fb.valid[0], t.fb.valid[1]);
+    if (t.closing) note(2, meter.total[kUnitBlock], 0, 0, 0);
+    ++n_ticks;
+    return t.fft.count || t.fb.count || t.closing;
+  };
+  for (size_t k = 0; k < n_events; ++k) {
+    if (pad[k] >= 0) fr.append(pad[k], nullptr, n_samples[k]);
+    if (pad[k] == -1) flush.request();
+    if (pad[k] == -2) (void)tick();
+  }
+  if (!flush.requested) flush.request();
+  while (tick() || flush.requested) {
+  }
+  *n_rows = n;
+  return PEAQ_OK;
+}

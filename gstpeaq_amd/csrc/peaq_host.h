@@ -45,6 +45,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -571,6 +572,14 @@ struct ModelSetup {
 
 constexpr unsigned kSessionMaxFrames = 64;   // FFT frames per launch of a session
 constexpr unsigned kSessionMaxBlocks = 120;  // filter-bank blocks per launch of a session
+constexpr unsigned kBrokerMaxFrames = 8;     // FFT frames one session contributes to one tick of the broker
+constexpr unsigned kBrokerMaxBlocks = 48;    // filter-bank blocks one session contributes to one tick
+// a broker slot's flush: asked for by peaq_broker_flush, carried out by the ticks, one path at a time
+struct SlotFlush {
+  bool requested = false, fft_done = false, fb_done = false;
+  void request() { *this = SlotFlush{true, false, false}; }
+  void clear() { *this = SlotFlush{}; }
+};
 
 // host-side stand-in for a GstAdapter: the not yet consumed tail of one pad's stream.
 // Consumed samples are skipped with a read offset and the storage is compacted only once more
@@ -811,6 +820,48 @@ inline void live_align_plan(uint32_t probe, uint64_t have_ref, uint64_t have_tes
   out->skip_ref = static_cast<uint32_t>(std::min(early, have_ref));
   out->skip_test = static_cast<uint32_t>(std::min(late, have_test));
 }
+// the record of an acquisition: rule A for what the pads held, and the aligner's record (nullptr: no estimate ran
+// because a pad was empty -- lag 0 and the all-zero record the aligner documents for an empty signal)
+inline peaq_live_delay live_delay_acquired(uint32_t probe, const uint64_t have[2], const peaq_delay* rec) {
+  peaq_live_delay d{};
+  live_align_plan(probe, have[0], have[1], rec ? rec->lag : 0, &d);
+  static_assert(sizeof d.d == sizeof(peaq_delay), "peaq_live_delay::d mirrors peaq_delay");
+  if (rec) std::memcpy(&d.d, rec, sizeof(peaq_delay));
+  d.acquired = 1;
+  return d;
+}
+// The device workspace of live alignment, a session's or a broker's: `probes` probes a launch of the aligner, `streams`
+// streams of at most max_frames whole frames a launch of the watch.
+struct LiveAlignBuffers {
+  DevBuf probe[2], rec;             // acquisition: the probes [probes][probe][channels], peaq_delay [probes]
+  DevBuf rows, state;               // watch: one launch's rows [streams][max_frames][kWatchRow]; WatchState [streams]
+  int reserve(const peaq_live_align_config& cfg, uint32_t probe_len, int channels, size_t probes, size_t streams,
+              unsigned max_frames) {
+    if (cfg.max_lag) {
+      for (int p = 0; p < 2; ++p) HIP_TRY(probe[p].reserve(probes * probe_len * channels * sizeof(float)));
+      HIP_TRY(rec.reserve(probes * sizeof(peaq_delay)));
+    }
+    if (cfg.watch_frames) {
+      HIP_TRY(rows.reserve(streams * max_frames * peaq::kWatchRow * sizeof(double)));
+      HIP_TRY(state.reserve(streams * sizeof(peaq::WatchState)));
+    }
+    return PEAQ_OK;
+  }
+  // the watch behind the front end `fa`, over n_frames whole frames of every stream (a broker adds s_frames, s_slot)
+  peaq::WatchArgs watch(const peaq::FrontendArgs& fa, uint32_t window, uint32_t n_frames, uint32_t stride) const {
+    peaq::WatchArgs wa{};
+    wa.ref = fa.ref;
+    wa.test = fa.test;
+    wa.pair_stride = fa.pair_stride;
+    wa.channels = fa.channels;
+    wa.n_frames = n_frames;
+    wa.window = window;
+    wa.rows = rows.as<double>();
+    wa.row_stride = stride;
+    wa.state = state.as<peaq::WatchState>();
+    return wa;
+  }
+};
 // rule B's read-out of a window's sums: norm, the arg-max with the aligner's tie rule, the runner-up
 inline void delay_watch_pick(const double* c, double e_ref, double e_test, int32_t* offset, double* peak,
                              double* runner_up, double* norm) {
@@ -866,6 +917,58 @@ struct MeterGeometry {
     depth = c.depth;
     k_open = (c.window_frames + c.hop_frames - 1) / c.hop_frames;
     ring = c.depth + 2;
+  }
+};
+// The meter's device workspace, a session's or a broker's: `streams` streams, each at most max_frames / max_blocks
+// units a launch.  What depends on the launch (unit0, n_units, rec_stride, the totals, the s_* rows) is the caller's.
+struct MeterBuffers {
+  DevBuf open, ring;                // PointSnap [stream][k_open], [stream][ring]
+  DevBuf frame_trc, block_trc;      // one launch's trace records [launch index][max_frames / max_blocks]: the live back
+                                    // ends' output, the meter kernels' feed
+  DevBuf readout;                   // ResultRecord [ring]
+  std::vector<peaq::ResultRecord> host;
+  size_t frame_stride = 0, block_stride = 0;
+  int reserve(const MeterGeometry& g, size_t streams, unsigned max_frames, unsigned max_blocks, bool advanced) {
+    HIP_TRY(open.reserve(streams * g.k_open * sizeof(peaq::PointSnap)));
+    HIP_TRY(ring.reserve(streams * g.ring * sizeof(peaq::PointSnap)));
+    HIP_TRY(readout.reserve((size_t)g.ring * sizeof(peaq::ResultRecord)));
+    HIP_TRY(frame_trc.reserve(streams * max_frames * sizeof(peaq::FrameTrace)));
+    if (advanced) HIP_TRY(block_trc.reserve(streams * max_blocks * sizeof(peaq::BlockTrace)));
+    try {
+      host.resize(g.ring);
+    } catch (const std::bad_alloc&) {
+      return fail(PEAQ_ERR_NOMEM, "out of host memory");
+    }
+    frame_stride = max_frames;
+    block_stride = max_blocks;
+    return PEAQ_OK;
+  }
+  peaq::MeterArgs args(const MeterGeometry& g) const {
+    peaq::MeterArgs m{};
+    m.open = open.as<peaq::PointSnap>();
+    m.ring = ring.as<peaq::PointSnap>();
+    m.window = g.window;
+    m.hop = g.hop;
+    m.k_open = g.k_open;
+    m.ring_depth = g.ring;
+    m.frames = frame_trc.as<peaq::FrameTrace>();
+    m.frame_stride = frame_stride;
+    m.blocks = block_trc.as<peaq::BlockTrace>();
+    m.block_stride = block_stride;
+    return m;
+  }
+  // the live back ends' output: the launch's records at their index within the launch (no flush flag: n_uniform);
+  // nothing with the meter off
+  peaq::RunOutputs outputs(const MeterGeometry& g) const {
+    peaq::RunOutputs out;
+    if (g.on) {
+      out.live.frames = frame_trc.as<peaq::FrameTrace>();
+      out.live.frame_stride = frame_stride;
+      out.live.blocks = block_trc.as<peaq::BlockTrace>();
+      out.live.block_stride = block_stride;
+      out.live.n_uniform = UINT_MAX;
+    }
+    return out;
   }
 };
 struct MeterStream {
@@ -925,3 +1028,48 @@ struct MeterStream {
     return PEAQ_OK;
   }
 };
+
+// ---------------------------------------------------------------------------
+// What one slot of the broker contributes to one tick (peaq_broker.hip, peaq_debug_broker_plan): at most one window
+// per kind -- whole units (do_processing), else, once per flush, the zero-padded unit of do_flush.  Host only; the
+// owner holds the slot's lock, and the stream is not held.  Only positions are taken: the samples are copied later,
+// and trim() is the caller's, behind that copy.
+// ---------------------------------------------------------------------------
+struct SlotTake {
+  StreamWindow fft, fb;             // count 0: none of that kind
+  bool closing = false;             // meter: the blocks ended in this tick without a flush block -- the windows that run to
+                                    // the last block are delivered by an entry without units (block0 = the stream's blocks)
+};
+inline SlotTake take_slot_windows(StreamFramer& fr, SlotFlush& fl, MeterStream& ms, bool metered, bool advanced,
+                                  unsigned max_frames, unsigned max_blocks) {
+  SlotTake t;
+  const bool flush_fft = fl.requested && !fl.fft_done;
+  if (metered && fl.requested && !ms.ended) ms.end(fr);   // the stream's end is known from here on
+  t.fft = fr.take(kUnitFrame, max_frames, flush_fft);
+  if (flush_fft && (t.fft.flush || !t.fft.count)) fl.fft_done = true;   // (no whole frame was left)
+  if (advanced) {
+    // With the meter on the two paths of a stream stay at a common sample horizon, so that a window's two halves
+    // meet in the delivered ring: the blocks go no further than the frame after the last one taken, 1024 (frames + 2)
+    // samples.  Whatever blocks are whole while no frame is lie below that, so nothing waits that a tick without the
+    // meter would take unless a frame waits too; and 48 blocks a tick outrun 8 frames.  The cap holds through a
+    // flush's backlog as well, until the stream's last frame has been taken (above, in this tick at the latest):
+    // only the tail of the blocks, and the flush block, run free.
+    const bool capped = metered && (!ms.ended || fr.done[kUnitFrame] < ms.total[kUnitFrame]);
+    const bool flush_fb = fl.requested && !fl.fb_done && !capped;
+    unsigned fb_cap = max_blocks;
+    if (capped) {
+      const uint64_t reach = 1024ull * ((uint64_t)fr.done[kUnitFrame] + 2) / peaq::kFbFrame;
+      const uint64_t room = reach > fr.done[kUnitBlock] ? reach - fr.done[kUnitBlock] : 0;
+      fb_cap = (unsigned)std::min<uint64_t>(room, max_blocks);
+    }
+    if (fb_cap) t.fb = fr.take(kUnitBlock, fb_cap, flush_fb);
+    if (flush_fb && (t.fb.flush || !t.fb.count)) {
+      fl.fb_done = true;
+      // (a window whose streaming end fell on the last block was stored then already: the closing entry stores the
+      // same fields again)
+      t.closing = metered && !t.fb.count && ms.total[kUnitFrame];
+    }
+  }
+  if (fl.requested && fl.fft_done && (!advanced || fl.fb_done)) fl.clear();
+  return t;
+}

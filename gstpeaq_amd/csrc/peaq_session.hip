@@ -20,58 +20,29 @@ struct peaq_session {
 
   // the meter (peaq_session_set_meter; peaq_meter.hip), guarded by mu like the rest
   struct Meter : MeterGeometry, MeterStream {
-    DevBuf open, delivered;         // PointSnap [k_open], [ring]
-    DevBuf frame_trc, block_trc;    // one launch's trace records, launch-relative (the live back ends' output)
-    DevBuf readout;                 // ResultRecord [ring]
-    std::vector<ResultRecord> h_readout;
+    MeterBuffers buf;               // one stream, kSessionMaxFrames / kSessionMaxBlocks units a launch
     bool closed[2] = {false, false};   // [kind]: a launch that ends this path's units has gone out
   } meter;
 
   // live alignment (peaq_session_set_align; peaq_watch.hip), guarded by mu like the rest
   struct Align : LiveAlignGeometry {
-    DevBuf probe_sig[2], rec;       // acquisition: the two probes [probe][channels], the aligner's record
+    LiveAlignBuffers buf;           // one probe a launch of the aligner, one stream of the watch
     peaq_live_delay delay{};        // all zero while the stream holds
-    DevBuf rows, state;             // watch: one launch's rows [kSessionMaxFrames][kWatchRow], WatchState
   } align;
 
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
-  MeterArgs meter_args(StreamUnit kind, uint32_t first, uint32_t count) const {
-    MeterArgs m{};
-    m.open = meter.open.as<PointSnap>();
-    m.ring = meter.delivered.as<PointSnap>();
-    m.window = meter.window;
-    m.hop = meter.hop;
-    m.k_open = meter.k_open;
-    m.ring_depth = meter.ring;
-    m.frames = meter.frame_trc.as<FrameTrace>();
-    m.frame_stride = kSessionMaxFrames;
-    m.blocks = meter.block_trc.as<BlockTrace>();
-    m.block_stride = kSessionMaxBlocks;
-    m.unit0 = first;
-    m.n_units = count;
-    m.rec_stride = count;
-    m.total_frames = meter.ended ? meter.total[kUnitFrame] : UINT_MAX;
-    m.total_units = meter.ended ? meter.total[kind] : UINT_MAX;
-    return m;
-  }
-  // the live back ends' output: the launch's records at their index within the launch (no flush flag: n_uniform)
-  RunOutputs meter_outputs() const {
-    RunOutputs out;
-    if (meter.on) {
-      out.live.frames = meter.frame_trc.as<FrameTrace>();
-      out.live.frame_stride = kSessionMaxFrames;
-      out.live.blocks = meter.block_trc.as<BlockTrace>();
-      out.live.block_stride = kSessionMaxBlocks;
-      out.live.n_uniform = UINT_MAX;
-    }
-    return out;
-  }
 };
 
 // behind a back-end launch of a metered session: the launch's units into the open windows; a launch that ends the
 // path's units (count may be 0) delivers the windows that run to the stream's end
 static int session_meter_step(peaq_session* s, StreamUnit kind, uint32_t first, uint32_t count) {
-  const MeterArgs m = s->meter_args(kind, first, count);
+  const peaq_session::Meter& mt = s->meter;
+  MeterArgs m = mt.buf.args(mt);
+  m.unit0 = first;
+  m.n_units = count;
+  m.rec_stride = count;
+  m.total_frames = mt.ended ? mt.total[kUnitFrame] : UINT_MAX;
+  m.total_units = mt.ended ? mt.total[kind] : UINT_MAX;
   if (kind == kUnitFrame)
     HIP_TRY(launch_meter_fft(m, s->advanced != 0, s->records.as<double>(), s->channels, 1, s->stream));
   else
@@ -83,12 +54,9 @@ static int session_meter_step(peaq_session* s, StreamUnit kind, uint32_t first, 
 // a fresh meter of the geometry that is set: every snapshot as launch_points_init leaves it, the index at 0
 static int session_meter_restart(peaq_session* s) {
   peaq_session::Meter& mt = s->meter;
-  HIP_TRY(launch_points_init(mt.open.as<PointSnap>(), mt.k_open, s->stream));
-  HIP_TRY(launch_points_init(mt.delivered.as<PointSnap>(), mt.ring, s->stream));
-  mt.n_taken = 0;
-  mt.ended = false;
-  mt.n_ref = mt.n_test = 0;
-  mt.total[0] = mt.total[1] = 0;
+  HIP_TRY(launch_points_init(mt.buf.open.as<PointSnap>(), mt.k_open, s->stream));
+  HIP_TRY(launch_points_init(mt.buf.ring.as<PointSnap>(), mt.ring, s->stream));
+  static_cast<MeterStream&>(mt) = MeterStream();
   mt.closed[0] = mt.closed[1] = false;
   return PEAQ_OK;
 }
@@ -98,7 +66,7 @@ static int session_align_restart(peaq_session* s) {
   peaq_session::Align& al = s->align;
   al.delay = peaq_live_delay{};
   if (al.max_lag) s->framer.hold();
-  if (al.window) HIP_TRY(hipMemsetAsync(al.state.p, 0, sizeof(WatchState), s->stream));
+  if (al.window) HIP_TRY(hipMemsetAsync(al.buf.state.p, 0, sizeof(WatchState), s->stream));
   return PEAQ_OK;
 }
 
@@ -108,26 +76,21 @@ static int session_acquire(peaq_session* s) {
   peaq_session::Align& al = s->align;
   StreamFramer& fr = s->framer;
   const uint64_t have[2] = {fr.pad[0].total, fr.pad[1].total};
-  peaq_live_delay d{};
-  live_align_plan(al.probe, have[0], have[1], 0, &d);
-  const uint32_t n[2] = {d.probe_ref, d.probe_test};
+  const uint32_t n[2] = {static_cast<uint32_t>(std::min<uint64_t>(have[0], al.probe)),
+                         static_cast<uint32_t>(std::min<uint64_t>(have[1], al.probe))};
   peaq_delay rec{};                                  // (an empty pad: the record the aligner documents for it)
   if (n[0] && n[1]) {
     for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(al.probe_sig[p].p, fr.pad[p].at(0, s->channels), (size_t)n[p] * s->channels * sizeof(float),
+      HIP_TRY(hipMemcpyAsync(al.buf.probe[p].p, fr.pad[p].at(0, s->channels), (size_t)n[p] * s->channels * sizeof(float),
                              hipMemcpyHostToDevice, s->stream));
-    if (int rc = peaq_batch_estimate_delay(s->ctx, s->channels, 1, al.probe_sig[0].as<float>(), al.probe_sig[1].as<float>(),
-                                           al.probe, n, n + 1, 0, al.max_lag, al.rec.as<peaq_delay>(), s->stream))
+    if (int rc = peaq_batch_estimate_delay(s->ctx, s->channels, 1, al.buf.probe[0].as<float>(), al.buf.probe[1].as<float>(),
+                                           al.probe, n, n + 1, 0, al.max_lag, al.buf.rec.as<peaq_delay>(), s->stream))
       return rc;
-    HIP_TRY(hipMemcpyAsync(&rec, al.rec.p, sizeof rec, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(&rec, al.buf.rec.p, sizeof rec, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
-  live_align_plan(al.probe, have[0], have[1], rec.lag, &d);
-  static_assert(sizeof d.d == sizeof rec, "peaq_live_delay::d mirrors peaq_delay");
-  std::memcpy(&d.d, &rec, sizeof rec);
-  d.acquired = 1;
-  al.delay = d;
-  fr.release(d.skip_ref, d.skip_test);
+  al.delay = live_delay_acquired(al.probe, have, &rec);
+  fr.release(al.delay.skip_ref, al.delay.skip_test);
   return PEAQ_OK;
 }
 
@@ -206,10 +169,7 @@ static int session_stage(peaq_session* s, const StreamWindow& w) {
 
 // run the FFT frames of window w (valid[] is shorter than whole frames only for the flush frame)
 static int session_run_frames(peaq_session* s, const StreamWindow& w) {
-  {
-    const int rc = session_stage(s, w);
-    if (rc != PEAQ_OK) return rc;
-  }
+  if (int rc = session_stage(s, w)) return rc;
   const ModelSetup m = s->model();
   FrontendArgs fa = m.frontend();
   fa.ref = s->d_sig[0].as<float>();
@@ -224,16 +184,7 @@ static int session_run_frames(peaq_session* s, const StreamWindow& w) {
   fa.records = s->records.as<double>();
   HIP_TRY(launch_frontend(m.fft_bands(), fa, 1, s->stream));
   if (s->align.window && !w.flush) {
-    WatchArgs wa{};
-    wa.ref = fa.ref;
-    wa.test = fa.test;
-    wa.pair_stride = fa.pair_stride;
-    wa.channels = s->channels;
-    wa.n_frames = w.count;
-    wa.window = s->align.window;
-    wa.rows = s->align.rows.as<double>();
-    wa.row_stride = w.count;
-    wa.state = s->align.state.as<WatchState>();
+    const WatchArgs wa = s->align.buf.watch(fa, s->align.window, w.count, w.count);
     HIP_TRY(launch_delay_watch(wa, 1, s->stream));
   }
   BackendArgs ba = m.backend(fa);
@@ -241,16 +192,13 @@ static int session_run_frames(peaq_session* s, const StreamWindow& w) {
   ba.frames_per_launch = w.count;
   ba.n_frames_uniform = w.first + w.count;
   ba.state = s->state.as<PairState>();
-  HIP_TRY(launch_backend(ba, 1, s->stream, s->meter_outputs()));
+  HIP_TRY(launch_backend(ba, 1, s->stream, s->meter.buf.outputs(s->meter)));
   return s->meter.on ? session_meter_step(s, kUnitFrame, w.first, w.count) : PEAQ_OK;
 }
 
 // run the filter-bank blocks of window w (advanced mode)
 static int session_run_blocks(peaq_session* s, const StreamWindow& w) {
-  {
-    const int rc = session_stage(s, w);
-    if (rc != PEAQ_OK) return rc;
-  }
+  if (int rc = session_stage(s, w)) return rc;
   const ModelSetup m = s->model();
   FbFrontArgs ff = m.fb_frontend();
   ff.ref = s->d_sig[0].as<float>();
@@ -274,7 +222,7 @@ static int session_run_blocks(peaq_session* s, const StreamWindow& w) {
   fbk.blocks_per_launch = w.count;
   fbk.n_blocks_uniform = w.first + w.count;
   fbk.state = s->state.as<PairState>();
-  HIP_TRY(launch_fb_backend(fbk, 1, s->stream, s->meter_outputs()));
+  HIP_TRY(launch_fb_backend(fbk, 1, s->stream, s->meter.buf.outputs(s->meter)));
   return s->meter.on ? session_meter_step(s, kUnitBlock, w.first, w.count) : PEAQ_OK;
 }
 
@@ -365,6 +313,14 @@ extern "C" int peaq_session_reset(peaq_session* s) {
   return s->meter.on ? session_meter_restart(s) : PEAQ_OK;
 }
 
+// the meter and the alignment are set on a stream that has not begun (the caller holds the session's lock)
+static int session_not_begun(const peaq_session* s, const std::string& who, const char* what) {
+  const uint64_t pushed = s->framer.pad[0].total + s->framer.pad[1].total;
+  if (!pushed) return PEAQ_OK;
+  return fail(PEAQ_ERR_ARG, who + ": the stream has begun (" + std::to_string(pushed) + " samples pushed); set " + what +
+                                " before the first push or right after peaq_session_reset");
+}
+
 extern "C" size_t peaq_meter_reading_size(void) { return sizeof(peaq_meter_reading); }
 
 extern "C" int peaq_meter_frames(double seconds, uint32_t* frames) {
@@ -398,10 +354,7 @@ extern "C" int peaq_session_set_meter(peaq_session* s, const peaq_meter_config* 
   if (!off)
     if (int rc = check_meter_config("peaq_session_set_meter", *cfg)) return rc;
   std::lock_guard<std::mutex> lock(s->mu);
-  const uint64_t pushed = s->framer.pad[0].total + s->framer.pad[1].total;
-  if (pushed)
-    return fail(PEAQ_ERR_ARG, "peaq_session_set_meter: the stream has begun (" + std::to_string(pushed) +
-                                  " samples pushed); set the meter before the first push or right after peaq_session_reset");
+  if (int rc = session_not_begun(s, "peaq_session_set_meter", "the meter")) return rc;
   peaq_session::Meter& mt = s->meter;
   if (off) {
     mt.on = false;
@@ -411,18 +364,8 @@ extern "C" int peaq_session_set_meter(peaq_session* s, const peaq_meter_config* 
   mt.on = false;                                     // (stays off if the workspace cannot be reserved)
   MeterGeometry g;
   g.set(*cfg);
-  const uint32_t k_open = g.k_open, ring = g.ring;
   HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
-  HIP_TRY(mt.open.reserve((size_t)k_open * sizeof(PointSnap)));
-  HIP_TRY(mt.delivered.reserve((size_t)ring * sizeof(PointSnap)));
-  HIP_TRY(mt.readout.reserve((size_t)ring * sizeof(ResultRecord)));
-  HIP_TRY(mt.frame_trc.reserve((size_t)kSessionMaxFrames * sizeof(FrameTrace)));
-  if (s->advanced) HIP_TRY(mt.block_trc.reserve((size_t)kSessionMaxBlocks * sizeof(BlockTrace)));
-  try {
-    mt.h_readout.resize(ring);
-  } catch (const std::bad_alloc&) {
-    return fail(PEAQ_ERR_NOMEM, "out of host memory");
-  }
+  if (int rc = mt.buf.reserve(g, 1, kSessionMaxFrames, kSessionMaxBlocks, s->advanced != 0)) return rc;
   mt.set(*cfg);
   if (int rc = session_meter_restart(s)) return rc;
   mt.on = true;
@@ -439,7 +382,7 @@ extern "C" int peaq_session_meter_read(peaq_session* s, peaq_meter_reading* out,
   peaq_session::Meter& mt = s->meter;
   if (!mt.on) return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: the meter is off (peaq_session_set_meter)");
   HIP_TRY(hipSetDevice(s->ctx->device));
-  return mt.read(s->framer, mt, mt.delivered.as<PointSnap>(), mt.readout, mt.h_readout, s->channels, s->stream, s->cfg,
+  return mt.read(s->framer, mt, mt.buf.ring.as<PointSnap>(), mt.buf.readout, mt.buf.host, s->channels, s->stream, s->cfg,
                  out, cap, n_read, dropped);
 }
 
@@ -486,10 +429,7 @@ extern "C" int peaq_session_set_align(peaq_session* s, const peaq_live_align_con
   if (cfg)
     if (int rc = check_live_align(who, *cfg, &probe)) return rc;
   std::lock_guard<std::mutex> lock(s->mu);
-  const uint64_t pushed = s->framer.pad[0].total + s->framer.pad[1].total;
-  if (pushed)
-    return fail(PEAQ_ERR_ARG, who + ": the stream has begun (" + std::to_string(pushed) +
-                                  " samples pushed); set the alignment before the first push or right after peaq_session_reset");
+  if (int rc = session_not_begun(s, who, "the alignment")) return rc;
   peaq_session::Align& al = s->align;
   al.max_lag = al.probe = al.window = 0;             // (stays off if the workspace cannot be reserved)
   al.delay = peaq_live_delay{};
@@ -497,14 +437,7 @@ extern "C" int peaq_session_set_align(peaq_session* s, const peaq_live_align_con
   if (off) return PEAQ_OK;
   HIP_TRY(hipSetDevice(s->ctx->device));
   HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
-  if (cfg->max_lag) {
-    for (int p = 0; p < 2; ++p) HIP_TRY(al.probe_sig[p].reserve((size_t)probe * s->channels * sizeof(float)));
-    HIP_TRY(al.rec.reserve(sizeof(peaq_delay)));
-  }
-  if (cfg->watch_frames) {
-    HIP_TRY(al.rows.reserve((size_t)kSessionMaxFrames * kWatchRow * sizeof(double)));
-    HIP_TRY(al.state.reserve(sizeof(WatchState)));
-  }
+  if (int rc = al.buf.reserve(*cfg, probe, s->channels, 1, 1, kSessionMaxFrames)) return rc;
   al.max_lag = cfg->max_lag;
   al.probe = probe;
   al.window = cfg->watch_frames;
@@ -529,7 +462,7 @@ extern "C" int peaq_session_watch_read(peaq_session* s, peaq_delay_watch* out) {
     return fail(PEAQ_ERR_ARG, "peaq_session_watch_read: the watch is off (peaq_session_set_align, watch_frames)");
   HIP_TRY(hipSetDevice(s->ctx->device));
   WatchState st;
-  HIP_TRY(hipMemcpyAsync(&st, s->align.state.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(&st, s->align.buf.state.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   delay_watch_record(st, out);
   return PEAQ_OK;

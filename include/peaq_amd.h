@@ -2088,6 +2088,21 @@ int peaq_debug_stream_plan (int advanced, unsigned max_frames, unsigned max_bloc
                             size_t n_pushes, const int *pad, const uint64_t *n_samples, size_t max_windows,
                             uint64_t *windows, size_t *n_windows);
 
+/* Host only, no device, no samples: what ONE slot of a broker contributes to its ticks -- the per-slot policy of the
+ * tick (csrc/peaq_host.h, take_slot_windows) on a stream of one channel, under the broker's caps of 8 FFT frames and 48
+ * filter-bank blocks a tick.  Event k: pad[k] = 0 or 1 pushes n_samples[k] samples to that pad (counted, not stored),
+ * -1 requests a flush (peaq_broker_flush), -2 is one tick (n_samples[k] is ignored for both).  After the last event a
+ * flush is requested if none is pending, and ticks run until one takes nothing and no flush is pending.  metered: the
+ * slot's meter is on, which holds the blocks back behind the frames and, in the advanced version, adds a closing entry
+ * when the blocks end without a flush block.
+ *   rows[r] = { tick (from 0; every tick counts, also one that takes nothing), kind, first unit, units,
+ *               valid samples on ref, on test }
+ * kind 0 = FFT frames, 1 = filter-bank blocks, 2 = the meter's closing entry (first = the stream's block count, the
+ * rest 0).  *n_rows is the number of rows; the first max_rows of them are written (rows may be NULL if that is 0). */
+#define PEAQ_DEBUG_BROKER_PLAN_FIELDS 6
+int peaq_debug_broker_plan (int advanced, int metered, size_t n_events, const int *pad, const uint64_t *n_samples,
+                            size_t max_rows, uint64_t *rows, size_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif
