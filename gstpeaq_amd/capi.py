@@ -37,6 +37,12 @@ class ResamplePlan(C.Structure):
                 ("lds_bytes", C.c_uint32), ("table_bytes", C.c_uint64), ("max_sum_abs_taps", C.c_double)]
 
 
+class RateSegment(C.Structure):
+    """mirrors peaq_rate_segment (include/peaq_amd.h)"""
+    _fields_ = [("out_first", C.c_uint64), ("in_base", C.c_uint64), ("in_total", C.c_uint64),
+                ("out_count", C.c_uint32), ("in_have", C.c_uint32)]
+
+
 class Delay(C.Structure):
     """mirrors peaq_delay (include/peaq_amd.h)"""
     _fields_ = [("lag", C.c_int32), ("reserved", C.c_int32), ("peak", C.c_double), ("runner_up", C.c_double),
@@ -442,6 +448,18 @@ def load_library():
                                           vp, C.c_size_t, u32p, vp]
         L.peaq_run_pair_rate.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint32, fp, C.c_size_t, fp, C.c_size_t, dp]
         L.peaq_resample_plan_info.argtypes = [C.c_uint32, C.POINTER(ResamplePlan)]
+    if hasattr(L, "peaq_batch_resample_range"):      # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_rate_segment_size.restype = C.c_size_t
+        L.peaq_rate_segment_size.argtypes = []
+        L.peaq_live_rate_ready.argtypes = [C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        L.peaq_live_rate_inputs.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.peaq_batch_resample_range.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.POINTER(RateSegment), vp, C.c_size_t,
+                                                vp, C.c_size_t, vp]
+        L.peaq_session_set_rates.argtypes = [vp, C.c_uint32, C.c_uint32]
+        L.peaq_broker_set_rates.argtypes = [vp, C.c_uint32, C.c_uint32]
+        if L.peaq_rate_segment_size() != C.sizeof(RateSegment):
+            raise PeaqError(f"peaq_rate_segment is {L.peaq_rate_segment_size()} bytes in the library, "
+                            f"{C.sizeof(RateSegment)} in this binding")
     if hasattr(L, "peaq_batch_estimate_delay"):      # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         L.peaq_batch_estimate_delay.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, u32p, u32p, C.c_uint32,
                                                 C.c_uint32, vp, vp]
@@ -764,12 +782,21 @@ class Context:
 class Session:
     """Streaming session = one `peaq` element instance (host buffers in, results out)."""
 
-    def __init__(self, ctx, advanced, channels, playback_level=92.0):
+    def __init__(self, ctx, advanced, channels, playback_level=92.0, rates=(48000, 48000)):
+        """rates: the sampling rates of the (ref, test) pads, see set_rates"""
         self.ctx, self.advanced, self.channels = ctx, bool(advanced), channels
         self.L = ctx.L
         self.h = C.c_void_p()
         _check(self.L.peaq_session_create(ctx.h, int(advanced), int(channels), float(playback_level),
                                           C.byref(self.h)))
+        if tuple(rates) != (48000, 48000):
+            self.set_rates(*rates)
+
+    def set_rates(self, rate_ref, rate_test=None):
+        """peaq_session_set_rates: the pads take samples at these rates and convert them to 48 kHz on the device, as
+        resample does for a whole signal (rate_test None: the same as rate_ref; 48000: that pad as it is).  Before the
+        first push or right after reset() only; reset() keeps the rates."""
+        _check(self.L.peaq_session_set_rates(self.h, int(rate_ref), int(rate_ref if rate_test is None else rate_test)))
 
     def push(self, pad, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -856,10 +883,11 @@ class Session:
 class Broker:
     """Many live sessions (one per hosted `peaq` element), one batched launch per tick."""
 
-    def __init__(self, ctx, channels, max_sessions, playback_level=92.0, advanced=False, devices=None, fir_mode=None):
+    def __init__(self, ctx, channels, max_sessions, playback_level=92.0, advanced=False, devices=None, fir_mode=None,
+                 rates=None):
         """devices = None: one broker on ctx's GPU.  devices = [ordinals]: peaq_broker_create_multi -- one device
         broker (with a context of its own) per entry, sessions dealt out to the least loaded; ctx only lends the
-        loaded library then."""
+        loaded library then.  rates: the sampling rates of the (ref, test) pads of every session, see set_rates."""
         self.ctx, self.channels, self.advanced = ctx, channels, bool(advanced)
         self.L = ctx.L
         self.h = C.c_void_p()
@@ -872,6 +900,13 @@ class Broker:
             mode = -1 if fir_mode is None else FIR_MODES[fir_mode]
             _check(self.L.peaq_broker_create_multi(arr, len(devices), int(bool(advanced)), int(channels),
                                                    float(playback_level), int(max_sessions), None, mode, C.byref(self.h)))
+        if rates is not None:
+            self.set_rates(*rates)
+
+    def set_rates(self, rate_ref, rate_test=None):
+        """peaq_broker_set_rates: one pair of rates for all sessions of the broker (see Session.set_rates), before the
+        first open() and before start()"""
+        _check(self.L.peaq_broker_set_rates(self.h, int(rate_ref), int(rate_ref if rate_test is None else rate_test)))
 
     def devices(self):
         return int(self.L.peaq_broker_devices(self.h))
@@ -1031,6 +1066,52 @@ def resample(ctx, x, rate, n=None, out=None, stream=None):
                                      C.c_void_p(out.data_ptr()), out.shape[1], n_out.ctypes.data_as(u32p),
                                      _stream_ptr(stream)))
     return out, n_out
+
+
+RATE_OPEN = 2**64 - 1   # in_total of a segment whose stream has not ended
+RANGE_TILE = 256         # outputs a workgroup of resample_range_kernel takes (kRangeTile, csrc/peaq_live_rate.hip)
+
+
+def live_rate_ready(rate, n_have, ended=False):
+    """converted samples a stream at `rate` can deliver once n_have raw samples have arrived (peaq_live_rate_ready, host
+    arithmetic): not ended, the outputs whose taps all lie below n_have; ended, resampled_length without its limit"""
+    v = C.c_uint64(0)
+    _check(load_library().peaq_live_rate_ready(int(rate), int(n_have), int(bool(ended)), C.byref(v)))
+    return v.value
+
+
+def live_rate_span(rate, out_first, out_count):
+    """(in_first, in_end): the raw samples the outputs [out_first, out_first + out_count) read (peaq_live_rate_inputs,
+    host arithmetic)"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _check(load_library().peaq_live_rate_inputs(int(rate), int(out_first), int(out_count), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def resample_range(ctx, x, rate, segments, out=None, stream=None):
+    """Converts runs of outputs of streams sampled at `rate` (peaq_batch_resample_range).  x: CUDA float32 tensor
+    [n_segments, in_stride, channels], row i holding the raw samples [in_base, in_base + in_have) of segment i's
+    stream.  segments: one (out_first, out_count, in_base, in_have, in_total) each, in_total None (or RATE_OPEN) while
+    the stream has not ended.  out: optional tensor [n_segments, out_stride, channels]; without it a zero-filled one
+    as long as the longest out_count (at least 1).  Returns out; row i holds the outputs in its first out_count
+    samples."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    n_seg, in_stride, channels = x.shape
+    assert len(segments) == n_seg
+    arr = (RateSegment * max(n_seg, 1))()
+    for i, (out_first, out_count, in_base, in_have, in_total) in enumerate(segments):
+        arr[i] = RateSegment(int(out_first), int(in_base), RATE_OPEN if in_total is None else int(in_total),
+                             int(out_count), int(in_have))
+    if out is None:
+        with _torch_stream(stream):
+            out = torch.zeros((n_seg, max([int(s[1]) for s in segments] + [1]), channels), dtype=torch.float32,
+                              device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == n_seg and out.shape[2] == channels
+    _check(ctx.L.peaq_batch_resample_range(ctx.h, channels, int(rate), n_seg, arr, C.c_void_p(x.data_ptr()), in_stride,
+                                           C.c_void_p(out.data_ptr()), out.shape[1], _stream_ptr(stream)))
+    return out
 
 
 def _to_48k(ctx, ref, test, n_ref, n_test, rate, stream):

@@ -81,19 +81,30 @@ struct BrokerStage {
   float* h[2] = {nullptr, nullptr};         // [launch pair][stage samples][channels]
   DevBuf d[2];
   size_t samples = 0;
-  int alloc(size_t n_sessions, size_t stage_samples, int channels) {
+  int alloc(size_t n_sessions, size_t stage_samples, int channels, bool pad0 = true, bool pad1 = true) {
+    release();
     samples = stage_samples;
     const size_t bytes = n_sessions * stage_samples * channels * sizeof(float);
     for (int p = 0; p < 2; ++p) {
+      if (!(p ? pad1 : pad0) || !bytes) continue;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h[p]), bytes, hipHostMallocDefault));
       HIP_TRY(d[p].reserve(bytes));
     }
     return PEAQ_OK;
   }
-  ~BrokerStage() {
-    for (int p = 0; p < 2; ++p)
+  void release() {
+    for (int p = 0; p < 2; ++p) {
       if (h[p]) (void)hipHostFree(h[p]);
+      h[p] = nullptr;
+    }
   }
+  ~BrokerStage() { release(); }
+};
+
+// live rate conversion: the raw samples behind one kind of unit (or behind the probes) of the rated pads, an entry per
+// launch pair as in the BrokerStage they convert into, and the segments of one tick
+struct BrokerRawStage : BrokerStage {
+  std::vector<peaq_rate_segment> seg[2];
 };
 
 // The per-pair scalars of a tick's launches: rows of max_sessions entries each, pinned on the host and uploaded as one
@@ -283,12 +294,19 @@ struct peaq_broker {
   peaq_delay* a_hrec = nullptr;     // pinned: the records of the last tick's estimates
   std::vector<BrokerAcquire> a_pending;      // the estimates the last tick enqueued
 
+  // live rate conversion (peaq_broker_set_rates; peaq_live_rate.hip): one pair of rates for all slots, because they
+  // size the staging; the raw side of the FFT windows, of the filter-bank windows and of the probes
+  uint32_t rate[2] = {48000, 48000};
+  RateGeometry geo[2] = {{1, 1, 0}, {1, 1, 0}};
+  BrokerRawStage raw_fft, raw_fbs, raw_acq;
+  bool rated(int p) const { return rate[p] != 48000; }
+
   ModelSetup model() const { return ModelSetup{ctx, cfg, advanced, channels, level_db}; }
 };
 
 // a held slot whose probe is there, or whose flush has been asked for: the next tick with room estimates its delay
 static inline bool broker_probe_ready(const peaq_broker* b, const BrokerSlot& sl) {
-  return sl.flush.requested || std::min(sl.framer.pad[0].total, sl.framer.pad[1].total) >= b->align.probe;
+  return sl.flush.requested || std::min(sl.framer.have(0), sl.framer.have(1)) >= b->align.probe;
 }
 
 static inline bool broker_is_multi(const peaq_broker* b) { return b && !b->shards.empty(); }
@@ -303,11 +321,30 @@ static std::optional<int> broker_forward(peaq_broker* b, int sid, const char* wh
 }
 
 // window w of the slot's stream into staging entry `idx`
-static void broker_stage_copy(const peaq_broker* b, const BrokerSlot& sl, const BrokerStage& st, unsigned idx,
+static void broker_stage_copy(peaq_broker* b, const BrokerSlot& sl, const BrokerStage& st, BrokerRawStage& rs, unsigned idx,
                               const StreamWindow& w) {
-  const size_t off = idx * st.samples * b->channels;
+  const size_t off = idx * st.samples * b->channels, roff = idx * rs.samples * b->channels;
   float* const dst[2] = {st.h[0] + off, st.h[1] + off};
-  stage_window(sl.framer, w, dst);
+  float* const raw[2] = {rs.h[0] ? rs.h[0] + roff : nullptr, rs.h[1] ? rs.h[1] + roff : nullptr};
+  peaq_rate_segment* const seg[2] = {rs.seg[0].empty() ? nullptr : &rs.seg[0][idx],      // (of a rated pad only)
+                                     rs.seg[1].empty() ? nullptr : &rs.seg[1][idx]};
+  stage_window(sl.framer, w, dst, raw, seg);
+}
+
+// the samples of `n` launch pairs up: a plain pad's windows as they are staged, a rated pad's raw samples and ONE
+// launch of the range converter over the tick's segments, which writes the windows in place of the copy
+static int broker_upload(peaq_broker* b, const BrokerStage& st, const BrokerRawStage& rs, unsigned n) {
+  for (int p = 0; p < 2; ++p) {
+    if (!b->rated(p)) {
+      HIP_TRY(hipMemcpyAsync(st.d[p].p, st.h[p], n * st.samples * b->channels * sizeof(float), hipMemcpyHostToDevice, b->stream));
+      continue;
+    }
+    HIP_TRY(hipMemcpyAsync(rs.d[p].p, rs.h[p], n * rs.samples * b->channels * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    if (int rc = live_rate_convert(b->ctx, b->channels, b->rate[p], (int)n, rs.seg[p].data(), rs.d[p].as<float>(),
+                                           rs.samples, st.d[p].as<float>(), st.samples, b->stream))
+      return rc;
+  }
+  return PEAQ_OK;
 }
 
 // ---- the phases of a tick, in the order broker_tick_locked runs them -----------------------------------------
@@ -347,7 +384,8 @@ static void broker_release_acquired(peaq_broker* b) {
 // wait.  A flush with nothing on a pad releases the stream at once: no device work.
 static void broker_scan_held(peaq_broker* b, TickPlan& pl, int sid, BrokerSlot& sl) {
   if (sl.acquiring || !broker_probe_ready(b, sl)) return;
-  const uint64_t have[2] = {sl.framer.pad[0].total, sl.framer.pad[1].total};
+  const StreamFramer& fr = sl.framer;
+  const uint64_t have[2] = {fr.have(0), fr.have(1)};   // (a rated pad: converted samples, as the probe and the skips)
   if (!have[0] || !have[1]) {
     sl.delay = live_delay_acquired(b->align.probe, have, nullptr);
     sl.framer.release(sl.delay.skip_ref, sl.delay.skip_test);   // (0, 0)
@@ -357,8 +395,17 @@ static void broker_scan_held(peaq_broker* b, TickPlan& pl, int sid, BrokerSlot& 
   const size_t i = pl.n_acq++;
   for (int p = 0; p < 2; ++p) {
     pl.acq_n[p][i] = static_cast<uint32_t>(std::min<uint64_t>(have[p], b->align.probe));
-    std::memcpy(b->a_hprobe[p] + i * (size_t)b->align.probe * b->channels, sl.framer.pad[p].at(0, b->channels),
-                (size_t)pl.acq_n[p][i] * b->channels * sizeof(float));
+    if (!fr.rated(p)) {
+      std::memcpy(b->a_hprobe[p] + i * (size_t)b->align.probe * b->channels, fr.pad[p].at(0, b->channels),
+                  (size_t)pl.acq_n[p][i] * b->channels * sizeof(float));
+      continue;
+    }
+    uint64_t lo, hi;                                 // the probe's raw samples; the launch converts them
+    fr.raw_span(p, 0, pl.acq_n[p][i], &lo, &hi);
+    std::memcpy(b->raw_acq.h[p] + i * b->raw_acq.samples * b->channels, fr.pad[p].at(lo, b->channels),
+                (size_t)(hi - lo) * b->channels * sizeof(float));
+    b->raw_acq.seg[p][i] = peaq_rate_segment{0, lo, fr.ended ? fr.pad[p].total : UINT64_MAX, pl.acq_n[p][i],
+                                             static_cast<uint32_t>(hi - lo)};
   }
   b->a_pending.push_back(BrokerAcquire{sid, sl.epoch, {have[0], have[1]}});
   sl.acquiring = true;
@@ -434,8 +481,8 @@ static int broker_stage(peaq_broker* b, const TickPlan& pl) {
     const BrokerJob& j = pl.jobs[i];
     BrokerSlot& sl = *b->slots[j.sid];
     std::lock_guard<std::mutex> lock(sl.mu);
-    if (j.fft.count) broker_stage_copy(b, sl, b->fft, j.fft_idx, j.fft);
-    if (j.fb.count) broker_stage_copy(b, sl, b->fbs, j.fb_idx, j.fb);
+    if (j.fft.count) broker_stage_copy(b, sl, b->fft, b->raw_fft, j.fft_idx, j.fft);
+    if (j.fb.count) broker_stage_copy(b, sl, b->fbs, b->raw_fbs, j.fb_idx, j.fb);
     sl.framer.trim();
   });
   HIP_TRY(hipEventRecord(b->t_begin, b->stream));
@@ -450,9 +497,7 @@ static int broker_launch_fft(peaq_broker* b, const TickPlan& pl) {
   if (!pl.active) return PEAQ_OK;
   const BrokerMeta& mt = b->meta;
   const ModelSetup m = b->model();
-  const size_t stride = b->fft.samples * b->channels;
-  for (int p = 0; p < 2; ++p)
-    HIP_TRY(hipMemcpyAsync(b->fft.d[p].p, b->fft.h[p], pl.active * stride * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  if (int rc = broker_upload(b, b->fft, b->raw_fft, pl.active)) return rc;
   FrontendArgs fa = m.frontend();
   fa.ref = b->fft.d[0].as<float>();
   fa.test = b->fft.d[1].as<float>();
@@ -495,10 +540,7 @@ static int broker_launch_fb(peaq_broker* b, const TickPlan& pl) {
   if (pl.fb_active) {
     const BrokerMeta& mt = b->meta;
     const ModelSetup m = b->model();
-    const size_t stride = b->fbs.samples * b->channels;
-    for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(b->fbs.d[p].p, b->fbs.h[p], pl.fb_active * stride * sizeof(float), hipMemcpyHostToDevice,
-                             b->stream));
+    if (int rc = broker_upload(b, b->fbs, b->raw_fbs, pl.fb_active)) return rc;
     HIP_TRY(hipMemcpyAsync(b->d_win.p, b->h_win, win_bytes, hipMemcpyHostToDevice, b->stream));
     FbFrontArgs ff = m.fb_frontend();
     ff.ref = b->fbs.d[0].as<float>();
@@ -533,8 +575,18 @@ static int broker_launch_acquire(peaq_broker* b, const TickPlan& pl) {
   if (!pl.n_acq) return PEAQ_OK;
   const LiveAlignBuffers& a = b->a_buf;
   const size_t row = (size_t)b->align.probe * b->channels;
-  for (int p = 0; p < 2; ++p)
-    HIP_TRY(hipMemcpyAsync(a.probe[p].p, b->a_hprobe[p], pl.n_acq * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  for (int p = 0; p < 2; ++p) {
+    if (!b->rated(p)) {
+      HIP_TRY(hipMemcpyAsync(a.probe[p].p, b->a_hprobe[p], pl.n_acq * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+      continue;
+    }
+    const BrokerRawStage& rs = b->raw_acq;           // the probes' raw samples up, converted into the probe buffer
+    HIP_TRY(hipMemcpyAsync(rs.d[p].p, rs.h[p], pl.n_acq * rs.samples * b->channels * sizeof(float), hipMemcpyHostToDevice,
+                           b->stream));
+    if (int rc = live_rate_convert(b->ctx, b->channels, b->rate[p], (int)pl.n_acq, rs.seg[p].data(),
+                                           rs.d[p].as<float>(), rs.samples, a.probe[p].as<float>(), b->align.probe, b->stream))
+      return rc;
+  }
   if (int rc = peaq_batch_estimate_delay(b->ctx, b->channels, (int)pl.n_acq, a.probe[0].as<float>(), a.probe[1].as<float>(),
                                          b->align.probe, pl.acq_n[0], pl.acq_n[1], 0, b->align.max_lag,
                                          a.rec.as<peaq_delay>(), b->stream))
@@ -848,6 +900,9 @@ extern "C" int peaq_broker_push(peaq_broker* b, int session_id, int pad, const f
   {
     std::lock_guard<std::mutex> lock(sl->mu);
     if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_push: session is not open");
+    if (sl->framer.ended && sl->framer.rated(pad))
+      return fail(PEAQ_ERR_STATE, "peaq_broker_push: the stream of a pad at " + std::to_string(sl->framer.rate[pad]) +
+                                      " Hz ended at its flush; close the session and open it again");
     try {
       sl->framer.append(pad, data, n);
     } catch (const std::bad_alloc&) {
@@ -879,6 +934,7 @@ extern "C" int peaq_broker_flush(peaq_broker* b, int session_id) {
   std::lock_guard<std::mutex> lock(sl->mu);
   if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_flush: session is not open");
   sl->flush.request();
+  sl->framer.ended = true;                           // (rated pads: what is there converts to the end)
   if (sl->t_ready_us < 0.) sl->t_ready_us = now_us();
   return PEAQ_OK;
 }
@@ -978,6 +1034,34 @@ extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cf
   return PEAQ_OK;
 }
 
+// the raw staging of the rated pads: the windows of both kinds and, with an acquisition set, the probes; sized from
+// the rates alone (the caller holds tick_mu; the device is idle)
+static int broker_raw_reserve(peaq_broker* b) {
+  const size_t S = (size_t)b->max_sessions;
+  const bool r0 = b->rated(0), r1 = b->rated(1);
+  auto span = [b](size_t count) {
+    size_t n = 0;
+    for (int p = 0; p < 2; ++p)
+      if (b->rated(p)) n = std::max(n, live_rate_span_max(b->geo[p], count));
+    return n;
+  };
+  struct Want {
+    BrokerRawStage* rs;
+    size_t entries, count;
+  } const want[3] = {{&b->raw_fft, S, kBrokerStageSamples},
+                     {&b->raw_fbs, b->advanced ? S : 0, kBrokerFbStageSamples},
+                     {&b->raw_acq, b->align.max_lag ? kBrokerAcquirePerTick : 0, b->align.probe}};
+  for (const Want& w : want) {
+    if (int rc = w.rs->alloc(w.entries, span(w.count), b->channels, r0, r1)) return rc;
+    try {
+      for (int p = 0; p < 2; ++p) w.rs->seg[p].assign(b->rated(p) ? w.entries : 0, peaq_rate_segment{});
+    } catch (const std::bad_alloc&) {
+      return fail(PEAQ_ERR_NOMEM, "out of host memory");
+    }
+  }
+  return PEAQ_OK;
+}
+
 // One configuration for all sessions of the broker, where peaq_broker_set_meter is accepted.
 extern "C" int peaq_broker_set_align(peaq_broker* b, const peaq_live_align_config* cfg) {
   const std::string who("peaq_broker_set_align");
@@ -1013,6 +1097,44 @@ extern "C" int peaq_broker_set_align(peaq_broker* b, const peaq_live_align_confi
   b->align.max_lag = cfg->max_lag;
   b->align.probe = probe;
   b->align.window = cfg->watch_frames;
+  return broker_raw_reserve(b);
+}
+
+// One pair of rates for all sessions of the broker, because they size the staging: where peaq_broker_set_meter is
+// accepted.
+extern "C" int peaq_broker_set_rates(peaq_broker* b, uint32_t rate_ref, uint32_t rate_test) {
+  const std::string who("peaq_broker_set_rates");
+  if (!b) return fail(PEAQ_ERR_ARG, who + ": broker is NULL");
+  const uint32_t rate[2] = {rate_ref, rate_test};
+  RateGeometry geo[2] = {{1, 1, 0}, {1, 1, 0}};
+  for (int p = 0; p < 2; ++p)
+    if (rate[p] != 48000)
+      if (int rc = resample_geometry(who.c_str(), rate[p], &geo[p])) return rc;
+  if (broker_is_multi(b)) {                            // every shard
+    for (peaq_broker* sh : b->shards)
+      if (int rc = peaq_broker_set_rates(sh, rate_ref, rate_test)) return rc;
+    return PEAQ_OK;
+  }
+  if ((rate_ref != 48000 || rate_test != 48000) && b->max_sessions > 65535)
+    return fail(PEAQ_ERR_ARG, who + ": more than 65535 sessions are more segments than one launch of the converter takes");
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (int rc = broker_not_begun(b, who, "the rates")) return rc;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
+  auto set = [b](const uint32_t* r, const RateGeometry* g) {
+    for (int p = 0; p < 2; ++p) {
+      b->rate[p] = r[p];
+      b->geo[p] = g[p];
+      for (BrokerSlot* sl : b->slots) sl->framer.set_rate(p, r[p], g[p]);
+    }
+  };
+  set(rate, geo);
+  if (int rc = broker_raw_reserve(b)) {                // (stays off if the staging cannot be reserved)
+    const uint32_t r48[2] = {48000, 48000};
+    const RateGeometry g48[2] = {{1, 1, 0}, {1, 1, 0}};
+    set(r48, g48);
+    return rc;
+  }
   return PEAQ_OK;
 }
 

@@ -27,6 +27,8 @@
 //   peaq_debug.hip    stage-level entry points for the parity tests, and the framer on its own (no device)
 //   peaq_debug_wave.hip  the primitives of peaq_wave.h on their own, for their unit tests
 //   peaq_watch.hip    the delay watch of a live stream (kernels; the host side is in the session and the broker)
+//   peaq_live_rate.hip  rate conversion of live streams: the range converter over segments (kernel and host side), the
+//                     host arithmetic from raw to converted counts that the stream framer counts with
 //   peaq_session.hip  streaming sessions (one per `peaq` element): one StreamFramer, one launch per window
 //   peaq_broker.hip   live-pipeline broker (a StreamFramer per session, one launch per tick), one or several devices
 #pragma once
@@ -224,6 +226,27 @@ void gain_release(peaq_ctx* c);
 void frac_release(peaq_ctx* c);
 void steps_release(peaq_ctx* c);
 void wide_release(peaq_ctx* c);
+// The rate converter for the range converter of live streams (peaq_resample.hip -> peaq_live_rate.hip): L, M and K of a
+// rate, with the refusal every entry gives for a rate it does not take (host only); the converted length without the
+// 32-bit limit; and the plain [L][2K] tap table on the device -- for a tiled rate uploaded at the first call -- with
+// the converter's length slots (the caller holds the context's lock).
+struct RateGeometry {
+  uint32_t L, M, K;
+};
+int resample_geometry(const char* who, uint32_t rate, RateGeometry* out);
+uint64_t resampled_length_u64(uint64_t n, uint32_t rate);
+int resample_plain_table(peaq_ctx* c, uint32_t rate, const double** taps, RateGeometry* geo, struct LenStage** lens);
+// Live rate conversion on the host (peaq_live_rate.hip; include/peaq_amd.h, "live rate conversion"), for a geometry
+// that resample_geometry gave: the converted samples n_have raw ones deliver, the raw span of a run of outputs, and
+// the longest raw span any run of `count` outputs has.
+uint64_t live_rate_ready(const RateGeometry& g, uint32_t rate, uint64_t n_have, bool ended);
+void live_rate_span(const RateGeometry& g, uint64_t out_first, uint32_t out_count, uint64_t* in_first, uint64_t* in_end);
+// one launch of the range converter over segments that stage_window made (no checks but the strides; enqueues on `stream`)
+int live_rate_convert(peaq_ctx* c, int channels, uint32_t rate, int n_segments, const peaq_rate_segment* seg,
+                      const float* d_in, size_t in_stride, float* d_out, size_t out_stride, hipStream_t stream);
+inline size_t live_rate_span_max(const RateGeometry& g, size_t count) {
+  return (count * g.M + g.L - 1) / g.L + 2 * (size_t)g.K + 1;
+}
 // the sub-sample stage's shift table on the device and its length slots, for the drift cut (peaq_frac.hip; the caller
 // holds the context's lock)
 int frac_shift_table(peaq_ctx* c, const double** shift, struct LenStage** lens);
@@ -637,18 +660,45 @@ struct StreamFramer {
   // stream as scored, pad p from its sample skip[p] on.  Never held and nothing skipped unless the owner asks.
   bool held = false;
   uint64_t skip[2] = {0, 0};
+  // Live rate conversion (include/peaq_amd.h, "live rate conversion"): the FIFO of a pad whose rate is not 48000 holds
+  // RAW samples, and pad[p].total counts them; everything else here -- have(), left(), scored(), pos, skip, the
+  // windows' pos / valid -- counts CONVERTED samples.  `ended`: the flush has been asked for, so that the converted
+  // length is the stream's own.  The rates outlive reset().
+  uint32_t rate[2] = {48000, 48000};
+  RateGeometry geo[2] = {{1, 1, 0}, {1, 1, 0}};
+  bool ended = false;
 
   void reset(bool advanced_, int channels_) {
-    *this = StreamFramer();
+    StreamFramer fresh;
+    for (int p = 0; p < 2; ++p) {
+      fresh.rate[p] = rate[p];
+      fresh.geo[p] = geo[p];
+    }
+    *this = std::move(fresh);
     advanced = advanced_;
     channels = channels_;
   }
+  void set_rate(int p, uint32_t r, const RateGeometry& g) {
+    rate[p] = r;
+    geo[p] = g;
+  }
+  bool rated(int p) const { return rate[p] != 48000; }
   // n samples (per channel) more on pad p; data == nullptr: counted but not stored (peaq_debug_stream_plan)
   void append(int p, const float* data, size_t n) {
     if (data) pad[p].append(data, n * channels);
     pad[p].total += n;
   }
-  uint64_t left(StreamUnit kind, int p) const { return pad[p].total - pos[kind][p]; }
+  // samples of pad p that can be framed: what was pushed, or what of it converts
+  uint64_t have(int p) const {
+    return rated(p) ? live_rate_ready(geo[p], rate[p], pad[p].total, ended) : pad[p].total;
+  }
+  // the raw samples [*lo, *hi) of a rated pad behind `count` converted ones from `first` on, inside what the pad holds
+  void raw_span(int p, uint64_t first, uint64_t count, uint64_t* lo, uint64_t* hi) const {
+    live_rate_span(geo[p], first, static_cast<uint32_t>(count), lo, hi);
+    *hi = std::min(*hi, pad[p].total);
+    *lo = std::min(*lo, *hi);
+  }
+  uint64_t left(StreamUnit kind, int p) const { return have(p) - pos[kind][p]; }
   void hold() { held = true; }
   void release(uint64_t skip_ref, uint64_t skip_test) {   // (a skip stops at what the pad holds: the caller's plan)
     skip[0] = skip_ref;
@@ -657,7 +707,7 @@ struct StreamFramer {
       for (int p = 0; p < 2; ++p) pos[kind][p] = skip[p];
     held = false;
   }
-  uint64_t scored(int p) const { return pad[p].total - skip[p]; }   // samples of pad p in the stream as scored
+  uint64_t scored(int p) const { return have(p) - skip[p]; }   // samples of pad p in the stream as scored
   // samples present on both pads and not yet framed: of one kind, and the larger of the kinds in use (what the
   // broker's back-pressure counts)
   uint64_t backlog(StreamUnit kind) const { return std::min(left(kind, 0), left(kind, 1)); }
@@ -705,16 +755,30 @@ struct StreamFramer {
   }
   // drops what both consumers are done with (windows taken before are no longer readable: copy first)
   void trim() {
-    for (int p = 0; p < 2; ++p)
-      pad[p].drop_until(advanced ? std::min(pos[kUnitFrame][p], pos[kUnitBlock][p]) : pos[kUnitFrame][p], channels);
+    for (int p = 0; p < 2; ++p) {
+      uint64_t keep = advanced ? std::min(pos[kUnitFrame][p], pos[kUnitBlock][p]) : pos[kUnitFrame][p], end;
+      if (rated(p)) raw_span(p, keep, 1, &keep, &end);   // (the first raw sample the next unit reads)
+      pad[p].drop_until(keep, channels);
+    }
   }
 };
 
-// the samples of window w, from the framer's FIFOs into dst[pad] (pinned staging)
-inline void stage_window(const StreamFramer& fr, const StreamWindow& w, float* const dst[2]) {
-  for (int p = 0; p < 2; ++p)
-    if (w.valid[p])
-      std::memcpy(dst[p], fr.pad[p].at(w.pos[p], fr.channels), (size_t)w.valid[p] * fr.channels * sizeof(float));
+// the samples of window w, from the framer's FIFOs into dst[pad] (pinned staging); a rated pad: the raw samples behind
+// the window into raw[pad], and seg[pad] the segment that converts them into the window
+inline void stage_window(const StreamFramer& fr, const StreamWindow& w, float* const dst[2], float* const raw[2] = nullptr,
+                         peaq_rate_segment* const seg[2] = nullptr) {
+  for (int p = 0; p < 2; ++p) {
+    if (!fr.rated(p)) {
+      if (w.valid[p])
+        std::memcpy(dst[p], fr.pad[p].at(w.pos[p], fr.channels), (size_t)w.valid[p] * fr.channels * sizeof(float));
+      continue;
+    }
+    uint64_t lo, hi;
+    fr.raw_span(p, w.pos[p], w.valid[p], &lo, &hi);
+    if (hi > lo) std::memcpy(raw[p], fr.pad[p].at(lo, fr.channels), (size_t)(hi - lo) * fr.channels * sizeof(float));
+    *seg[p] = peaq_rate_segment{w.pos[p], lo, fr.ended ? fr.pad[p].total : UINT64_MAX, static_cast<uint32_t>(w.valid[p]),
+                                static_cast<uint32_t>(hi - lo)};
+  }
 }
 
 // What a session does after every push and, with `flushing`, at its flush: frames, then (advanced) blocks, in

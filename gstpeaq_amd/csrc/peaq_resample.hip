@@ -214,7 +214,26 @@ struct RsPlan {
   size_t lds_bytes = 0;
   uint32_t zero_taps = 0;       // tiled: W - 2K, taps evaluated beside the filter's own (all zero)
   DevBuf taps, off;
+  DevBuf plain;                 // tiled: the plain [L][2K] table, for the range converter only (peaq_live_rate.hip)
 };
+
+// the filter of `rate` (the CLI's parameters) and its K
+RsFilter rate_filter(uint32_t rate, long* K) {
+  const double ratio = 48000. / rate;
+  RsFilter k;
+  if (ratio >= 1.) {
+    k.fc = 0.94 * 0.5;
+    k.half = 32.15;
+    k.beta = 8.49;
+  } else {
+    k.fc = 0.921 * 0.5 * ratio;
+    k.half = 4. * std::ceil(64. / ratio / 8.);
+    k.beta = 8.41;
+  }
+  k.i0b = bessel_i0(k.beta);
+  *K = (long)std::ceil(k.half) + 1;
+  return k;
+}
 
 }  // namespace
 
@@ -241,21 +260,13 @@ static int check_rate(const char* who, uint32_t rate) {
 
 // The plan of `rate`, host only: filter, tile geometry, and the tables the kernels read (tiled: group tables and
 // window offsets; otherwise the plain [L][2K] table).
-static int build_plan(uint32_t rate, RsPlan* pl, std::vector<double>* h_taps, std::vector<int>* h_off) {
-  const double ratio = 48000. / rate, delay = 0.125;
-  RsFilter k;
-  if (ratio >= 1.) {
-    k.fc = 0.94 * 0.5;
-    k.half = 32.15;
-    k.beta = 8.49;
-  } else {
-    k.fc = 0.921 * 0.5 * ratio;
-    k.half = 4. * std::ceil(64. / ratio / 8.);
-    k.beta = 8.41;
-  }
-  k.i0b = bessel_i0(k.beta);
+// With h_plain, the plain table of a tiled rate goes there as well (otherwise h_taps is the plain table).
+static int build_plan(uint32_t rate, RsPlan* pl, std::vector<double>* h_taps, std::vector<int>* h_off,
+                      std::vector<double>* h_plain = nullptr) {
+  const double delay = 0.125;
+  long K = 0;
+  const RsFilter k = rate_filter(rate, &K);
   const uint32_t g = gcd_u32(48000u, rate), L = 48000u / g, M = rate / g;
-  const long K = (long)std::ceil(k.half) + 1;
   pl->L = L;
   pl->M = M;
   pl->K = (uint32_t)K;
@@ -325,6 +336,7 @@ static int build_plan(uint32_t rate, RsPlan* pl, std::vector<double>* h_taps, st
         for (long j = 0; j < 2 * K; j++) gt[((size_t)q * W + (size_t)(shift + j)) * kRsGroup + i] = table[(size_t)p * 2 * K + j];
       }
     *h_off = off;
+    if (h_plain) *h_plain = std::move(table);
   } else {
     *h_taps = std::move(table);
     h_off->clear();
@@ -354,6 +366,37 @@ static int get_plan(peaq_ctx* c, uint32_t rate, RsPlan** out) {
   }
   *out = pl.get();
   c->rs->plans[rate] = std::move(pl);
+  return PEAQ_OK;
+}
+
+// ---- for the range converter of live streams (peaq_live_rate.hip; declared in peaq_host.h) ----
+int resample_geometry(const char* who, uint32_t rate, RateGeometry* out) {
+  if (int rc = check_rate(who, rate)) return rc;
+  long K = 0;
+  (void)rate_filter(rate, &K);
+  const uint32_t g = gcd_u32(48000u, rate);
+  *out = RateGeometry{48000u / g, rate / g, (uint32_t)K};
+  return PEAQ_OK;
+}
+
+uint64_t resampled_length_u64(uint64_t n, uint32_t rate) {
+  return n ? (uint64_t)(std::floor((double)(n - 1) * (48000. / rate)) + 1.) : 0;   // (resampled_length, no limit)
+}
+
+int resample_plain_table(peaq_ctx* c, uint32_t rate, const double** taps, RateGeometry* geo, LenStage** lens) {
+  RsPlan* pl = nullptr;
+  if (int rc = get_plan(c, rate, &pl)) return rc;
+  if (pl->tiled && !pl->plain.p) {                   // (once per rate and context, synchronously, as the plan's own tables)
+    RsPlan again;
+    std::vector<double> h_taps, h_plain;
+    std::vector<int> h_off;
+    if (int rc = build_plan(rate, &again, &h_taps, &h_off, &h_plain)) return rc;
+    HIP_TRY(pl->plain.reserve(h_plain.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(pl->plain.p, h_plain.data(), h_plain.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  *taps = pl->tiled ? pl->plain.as<double>() : pl->taps.as<double>();
+  *geo = RateGeometry{pl->L, pl->M, pl->K};
+  *lens = &c->rs->lens;
   return PEAQ_OK;
 }
 

@@ -15,8 +15,18 @@ struct peaq_session {
   hipEvent_t staged = nullptr;    // the pinned staging buffers may be rewritten after this
   bool staged_pending = false;
   float* h_stage[2] = {nullptr, nullptr};   // pinned
-  DevBuf d_sig[2], records, state, result;
+  DevBuf d_sig, records, state, result;     // d_sig: the two pads' windows, [pad][stage_samples][channels]
   size_t stage_samples = 0;
+  float* sig(int p) const { return d_sig.as<float>() + (size_t)p * stage_samples * channels; }
+
+  // live rate conversion (peaq_session_set_rates; peaq_live_rate.hip), guarded by mu like the rest: the raw samples
+  // behind a window of a rated pad, [pad][h_raw_samples] pinned and [pad][d_raw_samples] on the device (the device
+  // rows take a probe's raw samples as well)
+  float* h_raw = nullptr;
+  DevBuf d_raw;
+  size_t h_raw_samples = 0, d_raw_samples = 0;
+  float* raw_host(int p) const { return h_raw + (size_t)p * h_raw_samples * channels; }
+  float* raw_dev(int p) const { return d_raw.as<float>() + (size_t)p * d_raw_samples * channels; }
 
   // the meter (peaq_session_set_meter; peaq_meter.hip), guarded by mu like the rest
   struct Meter : MeterGeometry, MeterStream {
@@ -75,14 +85,27 @@ static int session_align_restart(peaq_session* s) {
 static int session_acquire(peaq_session* s) {
   peaq_session::Align& al = s->align;
   StreamFramer& fr = s->framer;
-  const uint64_t have[2] = {fr.pad[0].total, fr.pad[1].total};
+  const uint64_t have[2] = {fr.have(0), fr.have(1)};   // (a rated pad: converted samples, as the probe and the skips)
   const uint32_t n[2] = {static_cast<uint32_t>(std::min<uint64_t>(have[0], al.probe)),
                          static_cast<uint32_t>(std::min<uint64_t>(have[1], al.probe))};
   peaq_delay rec{};                                  // (an empty pad: the record the aligner documents for it)
   if (n[0] && n[1]) {
-    for (int p = 0; p < 2; ++p)
-      HIP_TRY(hipMemcpyAsync(al.buf.probe[p].p, fr.pad[p].at(0, s->channels), (size_t)n[p] * s->channels * sizeof(float),
+    for (int p = 0; p < 2; ++p) {
+      if (!fr.rated(p)) {
+        HIP_TRY(hipMemcpyAsync(al.buf.probe[p].p, fr.pad[p].at(0, s->channels), (size_t)n[p] * s->channels * sizeof(float),
+                               hipMemcpyHostToDevice, s->stream));
+        continue;
+      }
+      // the probe's raw samples up, converted into the probe buffer
+      uint64_t lo, hi;
+      fr.raw_span(p, 0, n[p], &lo, &hi);
+      HIP_TRY(hipMemcpyAsync(s->raw_dev(p), fr.pad[p].at(lo, s->channels), (size_t)(hi - lo) * s->channels * sizeof(float),
                              hipMemcpyHostToDevice, s->stream));
+      const peaq_rate_segment seg{0, lo, fr.ended ? fr.pad[p].total : UINT64_MAX, n[p], static_cast<uint32_t>(hi - lo)};
+      if (int rc = live_rate_convert(s->ctx, s->channels, fr.rate[p], 1, &seg, s->raw_dev(p), s->d_raw_samples,
+                                             al.buf.probe[p].as<float>(), al.probe, s->stream))
+        return rc;
+    }
     if (int rc = peaq_batch_estimate_delay(s->ctx, s->channels, 1, al.buf.probe[0].as<float>(), al.buf.probe[1].as<float>(),
                                            al.probe, n, n + 1, 0, al.max_lag, al.buf.rec.as<peaq_delay>(), s->stream))
       return rc;
@@ -97,10 +120,9 @@ static int session_acquire(peaq_session* s) {
 static int session_alloc(peaq_session* s) {
   s->stage_samples = (size_t)(kSessionMaxFrames - 1) * kHop + kFrame;   // >= kSessionMaxBlocks * 192
   const size_t bytes = s->stage_samples * s->channels * sizeof(float);
-  for (int p = 0; p < 2; ++p) {
+  for (int p = 0; p < 2; ++p)
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_stage[p]), bytes, hipHostMallocDefault));
-    HIP_TRY(s->d_sig[p].reserve(bytes));
-  }
+  HIP_TRY(s->d_sig.reserve(2 * bytes));
   HIP_TRY(s->records.reserve((size_t)kSessionMaxFrames * s->channels * kRecDoubles * sizeof(double)));
   HIP_TRY(s->state.reserve(sizeof(PairState)));
   HIP_TRY(s->result.reserve(sizeof(ResultRecord)));
@@ -146,6 +168,7 @@ extern "C" void peaq_session_destroy(peaq_session* s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (int p = 0; p < 2; ++p)
     if (s->h_stage[p]) (void)hipHostFree(s->h_stage[p]);
+  if (s->h_raw) (void)hipHostFree(s->h_raw);
   if (s->staged) (void)hipEventDestroy(s->staged);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;                         // (the device buffers go with it)
@@ -157,13 +180,51 @@ static int session_stage(peaq_session* s, const StreamWindow& w) {
     HIP_TRY(hipEventSynchronize(s->staged));
     s->staged_pending = false;
   }
-  stage_window(s->framer, w, s->h_stage);
-  for (int p = 0; p < 2; ++p)
-    if (w.valid[p])
-      HIP_TRY(hipMemcpyAsync(s->d_sig[p].p, s->h_stage[p], (size_t)w.valid[p] * s->channels * sizeof(float),
-                             hipMemcpyHostToDevice, s->stream));
+  const StreamFramer& fr = s->framer;
+  peaq_rate_segment seg[2];
+  float* const raw[2] = {s->h_raw ? s->raw_host(0) : nullptr, s->h_raw ? s->raw_host(1) : nullptr};
+  peaq_rate_segment* const segp[2] = {&seg[0], &seg[1]};
+  stage_window(fr, w, s->h_stage, raw, segp);
+  for (int p = 0; p < 2; ++p) {
+    const size_t n = fr.rated(p) ? seg[p].in_have : w.valid[p];
+    if (n)
+      HIP_TRY(hipMemcpyAsync(fr.rated(p) ? s->raw_dev(p) : s->sig(p), fr.rated(p) ? raw[p] : s->h_stage[p],
+                             n * s->channels * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  }
   HIP_TRY(hipEventRecord(s->staged, s->stream));
   s->staged_pending = true;
+  // rated pads: the range converter writes the window in place of the copy -- both pads in one launch where they share
+  // a rate, the rows of d_raw and d_sig being the pads
+  const bool both = fr.rated(0) && fr.rate[0] == fr.rate[1];
+  for (int p = 0; p < 2; ++p) {
+    if (!fr.rated(p) || (both && p)) continue;
+    if (int rc = live_rate_convert(s->ctx, s->channels, fr.rate[p], both ? 2 : 1, seg + p, s->raw_dev(p),
+                                           s->d_raw_samples, s->sig(p), s->stage_samples, s->stream))
+      return rc;
+  }
+  return PEAQ_OK;
+}
+
+// the raw staging of the rated pads, for the largest window and (device side) the probe of an acquisition
+static int session_raw_reserve(peaq_session* s) {
+  const StreamFramer& fr = s->framer;
+  size_t h_need = 0, d_need = 0;
+  for (int p = 0; p < 2; ++p) {
+    if (!fr.rated(p)) continue;
+    h_need = std::max(h_need, live_rate_span_max(fr.geo[p], s->stage_samples));
+    d_need = std::max(d_need, live_rate_span_max(fr.geo[p], std::max<size_t>(s->stage_samples, s->align.probe)));
+  }
+  if (h_need > s->h_raw_samples) {
+    if (s->h_raw) (void)hipHostFree(s->h_raw);
+    s->h_raw = nullptr;
+    s->h_raw_samples = 0;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_raw), 2 * h_need * s->channels * sizeof(float), hipHostMallocDefault));
+    s->h_raw_samples = h_need;
+  }
+  if (d_need > s->d_raw_samples) {
+    HIP_TRY(s->d_raw.reserve(2 * d_need * s->channels * sizeof(float)));
+    s->d_raw_samples = d_need;
+  }
   return PEAQ_OK;
 }
 
@@ -172,8 +233,8 @@ static int session_run_frames(peaq_session* s, const StreamWindow& w) {
   if (int rc = session_stage(s, w)) return rc;
   const ModelSetup m = s->model();
   FrontendArgs fa = m.frontend();
-  fa.ref = s->d_sig[0].as<float>();
-  fa.test = s->d_sig[1].as<float>();
+  fa.ref = s->sig(0);
+  fa.test = s->sig(1);
   fa.pair_stride = s->stage_samples;
   fa.n_uniform_ref = static_cast<uint32_t>(w.valid[0]);
   fa.n_uniform_test = static_cast<uint32_t>(w.valid[1]);
@@ -201,8 +262,8 @@ static int session_run_blocks(peaq_session* s, const StreamWindow& w) {
   if (int rc = session_stage(s, w)) return rc;
   const ModelSetup m = s->model();
   FbFrontArgs ff = m.fb_frontend();
-  ff.ref = s->d_sig[0].as<float>();
-  ff.test = s->d_sig[1].as<float>();
+  ff.ref = s->sig(0);
+  ff.test = s->sig(1);
   ff.pair_stride = s->stage_samples;
   ff.n_uniform_ref = static_cast<uint32_t>(w.valid[0]);
   ff.n_uniform_test = static_cast<uint32_t>(w.valid[1]);
@@ -240,13 +301,16 @@ extern "C" int peaq_session_push(peaq_session* s, int pad, const float* data, si
   if (n == 0) return PEAQ_OK;
   if (!data) return fail(PEAQ_ERR_ARG, "peaq_session_push: data is NULL");
   std::lock_guard<std::mutex> lock(s->mu);          // GST_OBJECT_LOCK in pad_chain (gstpeaq.c:619)
+  if (s->framer.ended && s->framer.rated(pad))
+    return fail(PEAQ_ERR_STATE, "peaq_session_push: the stream of a pad at " + std::to_string(s->framer.rate[pad]) +
+                                    " Hz ended at its flush; peaq_session_reset starts the next one");
   HIP_TRY(hipSetDevice(s->ctx->device));
   try {
     s->framer.append(pad, data, n);
   } catch (const std::bad_alloc&) {
     return fail(PEAQ_ERR_NOMEM, "out of host memory");
   }
-  if (s->framer.held && std::min(s->framer.pad[0].total, s->framer.pad[1].total) >= s->align.probe)
+  if (s->framer.held && std::min(s->framer.have(0), s->framer.have(1)) >= s->align.probe)
     if (int rc = session_acquire(s)) return rc;
   return session_drain(s, false);
 }
@@ -255,6 +319,7 @@ extern "C" int peaq_session_flush(peaq_session* s) {
   if (!s) return fail(PEAQ_ERR_ARG, "peaq_session_flush: session is NULL");
   std::lock_guard<std::mutex> lock(s->mu);
   HIP_TRY(hipSetDevice(s->ctx->device));
+  s->framer.ended = true;                            // (rated pads: what is there converts to the end)
   if (s->framer.held)                                // the probe is what is there
     if (int rc = session_acquire(s)) return rc;
   peaq_session::Meter& mt = s->meter;
@@ -441,7 +506,29 @@ extern "C" int peaq_session_set_align(peaq_session* s, const peaq_live_align_con
   al.max_lag = cfg->max_lag;
   al.probe = probe;
   al.window = cfg->watch_frames;
+  if (int rc = session_raw_reserve(s)) return rc;
   return session_align_restart(s);
+}
+
+// Live rate conversion (include/peaq_amd.h): the pads' rates, on a stream that has not begun.
+extern "C" int peaq_session_set_rates(peaq_session* s, uint32_t rate_ref, uint32_t rate_test) {
+  const std::string who("peaq_session_set_rates");
+  if (!s) return fail(PEAQ_ERR_ARG, who + ": session is NULL");
+  const uint32_t rate[2] = {rate_ref, rate_test};
+  RateGeometry geo[2] = {{1, 1, 0}, {1, 1, 0}};
+  for (int p = 0; p < 2; ++p)
+    if (rate[p] != 48000)
+      if (int rc = resample_geometry(who.c_str(), rate[p], &geo[p])) return rc;
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (int rc = session_not_begun(s, who, "the rates")) return rc;
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
+  for (int p = 0; p < 2; ++p) s->framer.set_rate(p, rate[p], geo[p]);
+  if (int rc = session_raw_reserve(s)) {             // (stays off if the staging cannot be reserved)
+    for (int p = 0; p < 2; ++p) s->framer.set_rate(p, 48000, RateGeometry{1, 1, 0});
+    return rc;
+  }
+  return PEAQ_OK;
 }
 
 extern "C" int peaq_session_align_read(peaq_session* s, peaq_live_delay* out) {

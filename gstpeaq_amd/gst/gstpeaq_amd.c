@@ -31,7 +31,12 @@
 GST_DEBUG_CATEGORY_STATIC (peaq_amd_debug);
 #define GST_CAT_DEFAULT peaq_amd_debug
 
-#define PEAQ_CAPS "audio/x-raw, format = (string) F32LE, layout = (string) interleaved, rate = (int) 48000"
+/* 48 kHz as the reference -- a structure of its own and the first, so that an upstream that can deliver 48 kHz goes on
+ * doing so (audiotestsrc alone would settle on 44.1 kHz) -- and behind it the rates the device converter takes in front
+ * of the model (include/peaq_amd.h, "live rate conversion"); the pads may differ */
+#define PEAQ_CAPS_AT(rates) "audio/x-raw, format = (string) F32LE, layout = (string) interleaved, rate = (int) " rates
+#define PEAQ_CAPS PEAQ_CAPS_AT ("48000") "; " \
+    PEAQ_CAPS_AT ("{ 44100, 32000, 96000, 88200, 192000, 176400, 24000, 22050, 16000, 11025, 8000 }")
 
 typedef struct _GstPeaqAmd
 {
@@ -42,6 +47,10 @@ typedef struct _GstPeaqAmd
   gboolean console_output;
   gdouble playback_level;
   gint channels;
+  gint rate[2];                 /* what each pad's caps said; 0 until they have */
+  GQueue held[2];               /* buffers that arrived before the other pad's caps: the session is made once both rates
+                                 * are known, and takes them then, in order */
+  guint broker_rate[2];         /* the rates the broker of this element took */
   peaq_session *session;        /* NULL until caps are known */
   peaq_broker *broker;          /* set instead of `session` when the process-wide broker serves this element */
   gint broker_sid;
@@ -183,11 +192,38 @@ broker_align_config (peaq_live_align_config * cfg)
   return ok && align_config_of ((guint) v[0], (guint) v[1], watch, cfg) && (cfg->max_lag || cfg->watch_frames);
 }
 
+/* PEAQ_AMD_BROKER_RATES=REF[:TEST] in Hz: the sampling rates of the pads of every broker of the process (one pair per
+ * broker, because they size its staging); unset: 48000 on both.  FALSE if it is set and malformed. */
+static gboolean
+broker_rates (guint rate[2])
+{
+  const gchar *r = g_getenv ("PEAQ_AMD_BROKER_RATES");
+  gchar *end = NULL;
+  guint64 v;
+  rate[0] = rate[1] = 48000;
+  if (!r || !*r)
+    return TRUE;
+  v = g_ascii_strtoull (r, &end, 10);
+  if (end == r || v > G_MAXUINT32)
+    return FALSE;
+  rate[0] = rate[1] = (guint) v;
+  if (*end == ':') {
+    const gchar *t = end + 1;
+    v = g_ascii_strtoull (t, &end, 10);
+    if (end == t || v > G_MAXUINT32)
+      return FALSE;
+    rate[1] = (guint) v;
+  }
+  return !*end;
+}
+
+/* taken[]: the rates the broker accepted (48000 where PEAQ_AMD_BROKER_RATES is unset, malformed or was refused) */
 static peaq_broker *
-shared_broker (gboolean advanced, gint channels)
+shared_broker (gboolean advanced, gint channels, guint taken[2])
 {
   static GMutex lock;
   static peaq_broker *brokers[2][3] = { {NULL, NULL, NULL}, {NULL, NULL, NULL} };
+  static guint rates_taken[2][3][2];
   const gchar *max = g_getenv ("PEAQ_AMD_BROKER");
   const gint adv = advanced ? 1 : 0;
   peaq_broker *b = NULL;
@@ -228,6 +264,7 @@ shared_broker (gboolean advanced, gint channels)
       peaq_ctx *ctx = shared_context ();
       rc = ctx ? peaq_broker_create (ctx, adv, channels, 92., atoi (max), &brokers[adv][channels]) : PEAQ_ERR_DEVICE;
     }
+    rates_taken[adv][channels][0] = rates_taken[adv][channels][1] = 48000;
     if (rc == PEAQ_OK) {
       gdouble mw, mh;
       peaq_meter_config cfg;
@@ -243,6 +280,17 @@ shared_broker (gboolean advanced, gint channels)
         else if (peaq_broker_set_align (brokers[adv][channels], &acfg) != PEAQ_OK)
           GST_WARNING ("PEAQ_AMD_BROKER_ALIGN: no alignment (%s)", peaq_last_error ());
       }
+      if (g_getenv ("PEAQ_AMD_BROKER_RATES")) {
+        guint rates[2];
+        if (!broker_rates (rates))
+          GST_WARNING ("PEAQ_AMD_BROKER_RATES: 48000 Hz on both pads (not REF[:TEST])");
+        else if (peaq_broker_set_rates (brokers[adv][channels], rates[0], rates[1]) != PEAQ_OK)
+          GST_WARNING ("PEAQ_AMD_BROKER_RATES: 48000 Hz on both pads (%s)", peaq_last_error ());
+        else {
+          rates_taken[adv][channels][0] = rates[0];
+          rates_taken[adv][channels][1] = rates[1];
+        }
+      }
       if (peaq_broker_start (brokers[adv][channels], period ? (unsigned) atoi (period) : 0) != PEAQ_OK)
         GST_WARNING ("libpeaq_amd: %s", peaq_last_error ());
     } else {
@@ -251,6 +299,8 @@ shared_broker (gboolean advanced, gint channels)
     }
   }
   b = brokers[adv][channels];
+  taken[0] = rates_taken[adv][channels][0];
+  taken[1] = rates_taken[adv][channels][1];
   g_mutex_unlock (&lock);
   return b;
 }
@@ -281,10 +331,11 @@ renew_session (GstPeaqAmd * self)
   self->st_odg = self->st_di = self->st_totalsnr = NAN;
   self->aligning = self->watching = self->delay_acquired = self->watch_seen = FALSE;
   self->delay = self->delay_offset = 0;
-  if (self->channels <= 0)
+  /* (not before both pads' rates are known: what a pad pushes until then waits in `held`) */
+  if (self->channels <= 0 || !self->rate[0] || !self->rate[1])
     return TRUE;
   if (self->playback_level == 92.) {
-    peaq_broker *b = shared_broker (self->advanced, self->channels);
+    peaq_broker *b = shared_broker (self->advanced, self->channels, self->broker_rate);
     if (b && peaq_broker_open (b, &self->broker_sid) == PEAQ_OK) {
       gdouble mw, mh;
       peaq_live_align_config acfg;
@@ -303,6 +354,13 @@ renew_session (GstPeaqAmd * self)
     g_free (self->pending_error);
     self->pending_error = g_strdup_printf ("libpeaq_amd: %s", peaq_last_error ());
     self->session = NULL;
+    return FALSE;
+  }
+  if ((self->rate[0] != 48000 || self->rate[1] != 48000)
+      && peaq_session_set_rates (self->session, (guint) self->rate[0], (guint) self->rate[1]) != PEAQ_OK) {
+    g_free (self->pending_error);
+    self->pending_error = g_strdup_printf ("libpeaq_amd: %s", peaq_last_error ());
+    drop_session (self);
     return FALSE;
   }
   if (self->meter_window > 0.) {
@@ -647,6 +705,53 @@ pad_index (GstPeaqAmd * self, GstPad * pad)
   return pad == self->pads[0] ? 0 : 1;
 }
 
+/* samples into the session or the broker slot (the caller holds the object lock) */
+static GstFlowReturn
+push_samples (GstPeaqAmd * self, gint idx, const guint8 * data, gsize size)
+{
+  const size_t n = size / (sizeof (float) * self->channels);
+  if (self->broker)
+    return peaq_broker_push (self->broker, self->broker_sid, idx, (const float *) data, n) == PEAQ_OK ? GST_FLOW_OK : GST_FLOW_ERROR;
+  if (!self->session)
+    return GST_FLOW_NOT_NEGOTIATED;
+  return peaq_session_push (self->session, idx, (const float *) data, n) == PEAQ_OK ? GST_FLOW_OK : GST_FLOW_ERROR;
+}
+
+/* what the pads pushed before the session existed, in order (the caller holds the object lock); FALSE: a push failed */
+static gboolean
+push_held (GstPeaqAmd * self)
+{
+  gboolean ok = TRUE;
+  gint idx;
+  for (idx = 0; idx < 2; idx++) {
+    GstBuffer *b;
+    while ((b = g_queue_pop_head (&self->held[idx]))) {
+      GstMapInfo map;
+      if (ok && (self->session || self->broker) && gst_buffer_map (b, &map, GST_MAP_READ)) {
+        ok = push_samples (self, idx, map.data, map.size) == GST_FLOW_OK;
+        gst_buffer_unmap (b, &map);
+      }
+      gst_buffer_unref (b);
+    }
+  }
+  return ok;
+}
+
+/* A stream ends (or the element stops) while one pad never had caps: that pad counts as 48 kHz, and the session is made
+ * for what the other one pushed (the caller holds the object lock). */
+static void
+settle_unknown_rates (GstPeaqAmd * self)
+{
+  if (self->session || self->broker || self->channels <= 0 || !(self->rate[0] || self->rate[1]))
+    return;
+  if (!self->rate[0])
+    self->rate[0] = 48000;
+  if (!self->rate[1])
+    self->rate[1] = 48000;
+  if (renew_session (self) && !push_held (self))
+    GST_ERROR_OBJECT (self, "libpeaq_amd: %s", peaq_last_error ());
+}
+
 static GstFlowReturn
 gst_peaq_amd_chain (GstPad * pad, GstObject * parent, GstBuffer * buffer)
 {
@@ -662,16 +767,11 @@ gst_peaq_amd_chain (GstPad * pad, GstObject * parent, GstBuffer * buffer)
   GST_OBJECT_LOCK (self);               /* the two streaming threads are serialised, gstpeaq.c:619,658 */
   self->eos[idx] = FALSE;
   self->pushed = TRUE;
-  if (self->broker) {
-    if (peaq_broker_push (self->broker, self->broker_sid, idx, (const float *) map.data,
-            map.size / (sizeof (float) * self->channels)) != PEAQ_OK)
-      ret = GST_FLOW_ERROR;
-  } else if (!self->session) {
-    ret = GST_FLOW_NOT_NEGOTIATED;
-  } else if (peaq_session_push (self->session, idx, (const float *) map.data,
-          map.size / (sizeof (float) * self->channels)) != PEAQ_OK) {
-    ret = GST_FLOW_ERROR;
-  }
+  if (!self->session && !self->broker && self->rate[idx] && !self->rate[1 - idx]) {
+    /* this pad has its caps, the other one not yet: the buffer waits for the session */
+    g_queue_push_tail (&self->held[idx], gst_buffer_ref (buffer));
+  } else
+    ret = push_samples (self, idx, map.data, map.size);
   GST_OBJECT_UNLOCK (self);
   if (ret == GST_FLOW_OK && self->metered)
     post_meter_readings (self);         /* what this push completed (a broker: what its ticks have delivered so far) */
@@ -687,23 +787,71 @@ gst_peaq_amd_chain (GstPad * pad, GstObject * parent, GstBuffer * buffer)
 }
 
 static gboolean
-gst_peaq_amd_set_caps (GstPeaqAmd * self, GstCaps * caps)
+gst_peaq_amd_set_caps (GstPeaqAmd * self, gint idx, GstCaps * caps)
 {
-  gint channels = 0;
+  gint channels = 0, rate = 48000;
   gboolean ok = TRUE;
   if (!gst_structure_get_int (gst_caps_get_structure (caps, 0), "channels", &channels) || channels < 1
       || channels > 2) {
     GST_ELEMENT_ERROR (self, CORE, NEGOTIATION, ("peaq handles mono or stereo, got %d channels", channels), (NULL));
     return FALSE;
   }
+  if (!gst_structure_get_int (gst_caps_get_structure (caps, 0), "rate", &rate) || rate <= 0)
+    rate = 48000;
   GST_OBJECT_LOCK (self);
-  if (channels != self->channels || !(self->session || self->broker)) {
+  /* Both pads' rates go to the session, so it is made when the second pad's caps are known; what the first pad pushed
+   * until then was held back and goes in now.  Later caps: a new session where the channels or, in mid-stream, a rate
+   * changed -- as the reference re-allocates on new caps --, else the one that is there, whose stream has not begun. */
+  if (channels != self->channels || !(self->session || self->broker) || (rate != self->rate[idx] && self->pushed)) {
+    const gboolean restart = (self->session || self->broker) || (self->channels > 0 && channels != self->channels);
+    if (restart) {                      /* (a stream of other channels or another rate: nothing held belongs to it) */
+      gint i;
+      for (i = 0; i < 2; i++)
+        g_queue_clear_full (&self->held[i], (GDestroyNotify) gst_buffer_unref);
+    }
     self->channels = channels;
+    self->rate[idx] = rate;
     ok = renew_session (self);
+    if (ok && (self->session || self->broker) && !push_held (self)) {
+      g_free (self->pending_error);
+      self->pending_error = g_strdup_printf ("libpeaq_amd: %s", peaq_last_error ());
+      ok = FALSE;
+    }
+  } else if (rate != self->rate[idx]) {
+    self->rate[idx] = rate;
+    if (self->session && peaq_session_set_rates (self->session, (guint) self->rate[0], (guint) self->rate[1]) != PEAQ_OK) {
+      g_free (self->pending_error);
+      self->pending_error = g_strdup_printf ("libpeaq_amd: %s", peaq_last_error ());
+      ok = FALSE;
+    }
+  }
+  /* a broker's rates are the process's (PEAQ_AMD_BROKER_RATES, as far as the broker took them): a pad with another
+   * rate cannot ride in it */
+  if (ok && self->broker) {
+    gint i;
+    for (i = 0; i < 2 && ok; i++)
+      if (self->broker_rate[i] != (guint) self->rate[i]) {
+        g_free (self->pending_error);
+        self->pending_error =
+            g_strdup_printf ("peaq: the %s pad's caps say %d Hz, the broker of this process takes %u Hz there "
+            "(PEAQ_AMD_BROKER_RATES=REF[:TEST])", i ? "test" : "ref", self->rate[i], self->broker_rate[i]);
+        ok = FALSE;
+      }
   }
   GST_OBJECT_UNLOCK (self);
   post_pending_error (self);
   return ok;
+}
+
+/* a copy of caps without the rates: the pads agree on channels and format, not on the rate */
+static GstCaps *
+caps_without_rate (GstCaps * caps)
+{
+  GstCaps *c = gst_caps_copy (caps);
+  guint i;
+  for (i = 0; i < gst_caps_get_size (c); i++)
+    gst_structure_remove_field (gst_caps_get_structure (c, i), "rate");
+  return c;
 }
 
 static gboolean
@@ -722,6 +870,8 @@ gst_peaq_amd_sink_event (GstPad * pad, GstObject * parent, GstEvent * event)
       GST_OBJECT_LOCK (self);
       self->eos[idx] = TRUE;
       both = self->eos[0] && self->eos[1];
+      if (both)
+        settle_unknown_rates (self);
       GST_OBJECT_UNLOCK (self);
       ret = TRUE;
       if (both && (self->metered || self->aligning || self->watching)) {
@@ -754,7 +904,15 @@ gst_peaq_amd_sink_event (GstPad * pad, GstObject * parent, GstEvent * event)
       gst_event_parse_caps (event, &caps);
       /* both inputs must carry the same number of channels: only accept what the
        * other pad's upstream can also deliver (gstpeaq.c:689-708) */
-      ret = gst_pad_peer_query_accept_caps (self->pads[1 - idx], caps) && gst_peaq_amd_set_caps (self, caps);
+      {
+        /* (the rate aside: a fixed rate of its own is the other pad's business) */
+        GstCaps *other = gst_pad_peer_query_caps (self->pads[1 - idx], NULL), *mine = caps_without_rate (caps);
+        GstCaps *theirs = caps_without_rate (other);
+        ret = gst_caps_can_intersect (mine, theirs) && gst_peaq_amd_set_caps (self, idx, caps);
+        gst_caps_unref (other);
+        gst_caps_unref (mine);
+        gst_caps_unref (theirs);
+      }
       gst_event_unref (event);
       return ret;
     }
@@ -770,11 +928,18 @@ gst_peaq_amd_sink_query (GstPad * pad, GstObject * parent, GstQuery * query)
   if (GST_QUERY_TYPE (query) == GST_QUERY_CAPS) {
     /* offer the template caps restricted to what the OTHER input can produce */
     const gint idx = pad_index (self, pad);
-    GstCaps *filter, *tmpl, *other, *result;
+    GstCaps *filter, *tmpl, *other, *any_rate, *result;
     gst_query_parse_caps (query, &filter);
     tmpl = gst_pad_get_pad_template_caps (pad);
-    other = gst_pad_peer_query_caps (self->pads[1 - idx], filter);
-    result = gst_caps_intersect (tmpl, other);
+    if (filter) {
+      GstCaps *f = caps_without_rate (filter);
+      other = gst_pad_peer_query_caps (self->pads[1 - idx], f);
+      gst_caps_unref (f);
+    } else
+      other = gst_pad_peer_query_caps (self->pads[1 - idx], NULL);
+    any_rate = caps_without_rate (other);           /* (each pad keeps the rate of its own upstream) */
+    result = gst_caps_intersect_full (tmpl, any_rate, GST_CAPS_INTERSECT_FIRST);   /* (48 kHz stays first) */
+    gst_caps_unref (any_rate);
     gst_caps_unref (tmpl);
     gst_caps_unref (other);
     gst_query_set_caps_result (query, result);
@@ -790,6 +955,9 @@ gst_peaq_amd_change_state (GstElement * element, GstStateChange transition)
   GstPeaqAmd *self = GST_PEAQ_AMD (element);
   if (transition == GST_STATE_CHANGE_PAUSED_TO_READY) {
     /* do_flush + calculate_odg, gstpeaq.c:764-778 */
+    GST_OBJECT_LOCK (self);
+    settle_unknown_rates (self);
+    GST_OBJECT_UNLOCK (self);
     if ((self->broker && peaq_broker_flush (self->broker, self->broker_sid) != PEAQ_OK)
         || (self->session && peaq_session_flush (self->session) != PEAQ_OK))
       GST_ERROR_OBJECT (self, "libpeaq_amd: %s", peaq_last_error ());
@@ -803,6 +971,8 @@ gst_peaq_amd_finalize (GObject * obj)
 {
   GstPeaqAmd *self = GST_PEAQ_AMD (obj);
   drop_session (self);
+  g_queue_clear_full (&self->held[0], (GDestroyNotify) gst_buffer_unref);
+  g_queue_clear_full (&self->held[1], (GDestroyNotify) gst_buffer_unref);
   g_free (self->pending_error);
   G_OBJECT_CLASS (gst_peaq_amd_parent_class)->finalize (obj);
 }
@@ -900,6 +1070,10 @@ gst_peaq_amd_init (GstPeaqAmd * self)
   }
   GST_OBJECT_FLAG_SET (self, GST_ELEMENT_FLAG_SINK);
   self->channels = 0;
+  self->rate[0] = self->rate[1] = 0;
+  g_queue_init (&self->held[0]);
+  g_queue_init (&self->held[1]);
+  self->broker_rate[0] = self->broker_rate[1] = 48000;
   self->session = NULL;
   self->broker = NULL;
   self->broker_sid = -1;

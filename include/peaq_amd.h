@@ -995,6 +995,80 @@ int peaq_resample_plan_info (uint32_t rate, peaq_resample_plan *out);
 int peaq_run_pair_rate (peaq_ctx *ctx, int advanced, int channels, double playback_level_db, uint32_t rate,
                         const float *ref, size_t n_ref, const float *test, size_t n_test, peaq_result *out);
 
+/* ---- live rate conversion: the converter above, window by window ----------------------------------------------------
+ * Output sample m of the converter depends on m and on the 2K input samples n_first (m) .. last (m) alone:
+ *   n_first (m) = (m M) div L + (8 p < L ? -1 : 0) - K + 1, p = (m M) mod L;   last (m) = n_first (m) + 2K - 1
+ * (L, M, K, h_p as in "sample-rate conversion" above; both are non-decreasing in m).  So a stream can be converted a
+ * window at a time, from whatever raw samples are there, and gives exactly the samples peaq_batch_resample gives for
+ * the whole stream.
+ *
+ * peaq_live_rate_ready: how many converted samples a stream of which n_have raw samples (per channel) have arrived can
+ *   deliver.  Not ended: the count of outputs m with last (m) < n_have -- a prefix, since last is non-decreasing --, in
+ *   closed form: with A = 8 L (n_have - K) + L, 0 if A <= 0, else (A - 1) div (8 M) + 1.  Ended: the converter's own
+ *   length, peaq_resampled_length (n_have, rate), without the limit of 32 bits.  The first never passes the second
+ *   (m M < L (n_have - K) + L / 8 implies m M <= L (n_have - 1)), and holds back the outputs whose taps reach within K
+ *   samples of the end: 36 at 44.1 kHz, 50 at 32 kHz, 32 at 96 kHz, 144 at 11.025 kHz, 198 at 8 kHz at most, under 5 ms.
+ * peaq_live_rate_inputs: the raw samples [in_first, in_end) the outputs [out_first, out_first + out_count) read,
+ *   in_first = max (0, n_first (out_first)), in_end = last (out_first + out_count - 1) + 1 (the end of the stream does
+ *   not clamp it: the caller knows where that is); out_count == 0: in_end = in_first.
+ *   (Named _inputs, not _span: "spans" are the advanced version's scored stretches further up.)
+ * Both are host arithmetic, need no device, and refuse rate 48000 and every rate peaq_resample_supported does not take
+ * with PEAQ_ERR_ARG and a message that names the rate; positions past 2^62 / 48000 are PEAQ_ERR_ARG as well.
+ *
+ * peaq_batch_resample_range converts n_segments segments in one launch.  Segment i reads row i of d_in -- interleaved
+ * F32, `in_stride` samples per channel between rows, holding the raw samples [in_base, in_base + in_have) of its stream
+ * -- and writes the outputs m = out_first .. out_first + out_count - 1 to row i of d_out (`out_stride` between rows;
+ * what lies behind out_count is left as it is).  Each output is acc = fma (h_p[j], (double) x[n_first + j], acc) from
+ * acc = 0 with j ascending, rounded once to FP32: the chain of both kernels of peaq_batch_resample, so that for finite
+ * input the samples are bit for bit those of peaq_batch_resample over the whole stream at the same indices.  Taps
+ * outside [0, in_total) are absent (in_total: the stream's length once it has ended, UINT64_MAX before).  A tap inside
+ * the stream that the row does not hold is PEAQ_ERR_ARG, found on the host before anything is enqueued; so are outputs
+ * past the ended stream's converted length, out_count > out_stride, in_have > in_stride, an unsupported rate, rate ==
+ * 48000, channels other than 1 or 2, more than 65535 segments and NULL buffers.  Positions are 64-bit throughout (a
+ * 44.1 kHz stream passes 2^32 samples in 27 hours).  Enqueues on `stream` and synchronises nothing: the segments travel
+ * through the pinned slots peaq_batch_resample's lengths travel through, under the same rule.  (The first call for a
+ * rate on a context uploads that rate's plain tap table, synchronously.)
+ * One kernel, resample_range_kernel: a workgroup of 256 threads takes 256 consecutive outputs of one segment, stages
+ * their raw span (all channels) in LDS once, and each lane runs one output's chain, its tap row read from the plain
+ * [L][2K] table.  No atomics, a fixed order. */
+typedef struct peaq_rate_segment {
+  uint64_t out_first;  /* outputs m in [out_first, out_first + out_count) ...              */
+  uint64_t in_base;    /* ... from a row that holds raw samples [in_base, in_base + in_have) */
+  uint64_t in_total;   /* the stream's length once it has ended, UINT64_MAX before          */
+  uint32_t out_count, in_have;
+} peaq_rate_segment;
+size_t peaq_rate_segment_size (void);   /* the struct's size in THIS library, as peaq_meter_reading_size */
+int peaq_live_rate_ready (uint32_t rate, uint64_t n_have, int ended, uint64_t *ready);
+int peaq_live_rate_inputs (uint32_t rate, uint64_t out_first, uint32_t out_count, uint64_t *in_first, uint64_t *in_end);
+int peaq_batch_resample_range (peaq_ctx *ctx, int channels, uint32_t rate, int n_segments,
+                               const peaq_rate_segment *seg /* host */, const float *d_in, size_t in_stride,
+                               float *d_out, size_t out_stride, void *stream);
+/* Sessions.  peaq_session_set_rates gives each pad a rate: 48000 leaves the pad as it is, any other rate the converter
+ * takes makes it a RATED pad, whose pushes are raw samples at that rate.  A rated session IS the plain session fed
+ * each pad's peaq_batch_resample'd stream, whatever the pushes were: bit for bit in the basic version, and in the
+ * advanced version as far as one stream cut into other launches is the same.  The host FIFO of a rated pad holds raw
+ * samples; every count of the stream -- what is ready to be framed, frames, blocks, the meter's frames, {start,
+ * length} and totals, and with live alignment `probe`, `max_lag`, the probe lengths and the skips that
+ * peaq_session_align_read reports -- is in CONVERTED samples, through peaq_live_rate_ready of what has arrived.  Each
+ * launch uploads the raw span of its window (peaq_live_rate_inputs) and one launch of the range converter writes the
+ * window where the copy would have put it -- two segments, the two pads, where they share a rate --; an acquisition
+ * converts the probes the same way in front of peaq_batch_estimate_delay.  Everything behind is untouched.  Windows
+ * overlap by a hop, so a launch converts up to 1024 outputs that the launch before converted, and in the advanced
+ * version frames and blocks each convert their own window.  peaq_session_flush ends the stream: the outputs held back
+ * are delivered with the taps past the end absent, as peaq_batch_resample has them.  After it a push on a rated pad is
+ * PEAQ_ERR_STATE until peaq_session_reset, which keeps the rates.  Accepted where peaq_session_set_meter is, before
+ * the first push or right after peaq_session_reset; otherwise, and for an unsupported rate, PEAQ_ERR_ARG with a
+ * message that names entry and rate.
+ * The broker.  peaq_broker_set_rates sets ONE pair of rates for all sessions of the broker, because they size the
+ * pinned staging: accepted where peaq_broker_set_meter is, for a broker made by peaq_broker_create_multi in every
+ * shard; brokers of more than 65535 sessions are refused.  A tick uploads the raw samples of its windows and runs one
+ * launch of the range converter per path and rated pad over the tick's segments, in front of the front end; the
+ * probes of an acquisition likewise.  With both rates 48000 a tick enqueues exactly what it enqueues without the call.
+ * Every slot is its rated session.  peaq_broker_flush ends the slot's stream; a later push on a rated pad is
+ * PEAQ_ERR_STATE until the slot is closed and opened again. */
+int peaq_session_set_rates (peaq_session *s, uint32_t rate_ref, uint32_t rate_test);
+int peaq_broker_set_rates (peaq_broker *b, uint32_t rate_ref, uint32_t rate_test);
+
 /* ---- time alignment on the device ------------------------------------------------
  * PEAQ compares frame against frame and takes the two signals as sample-aligned (BS.1387; the reference has no
  * aligner).  A codec's output is late by its own delay; these entry points find that delay and cut both signals to
