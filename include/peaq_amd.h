@@ -155,13 +155,29 @@ int peaq_session_flush (peaq_session *s);
 int peaq_session_results (peaq_session *s, peaq_result *out);
 
 /* set_property "playback_level" (gstpeaq.c:508-515 -> fftearmodel.c:305-314,
- * fbearmodel.c:249-254): applies to every frame processed from now on, state is
- * kept -- exactly what the reference's ear models do when the property changes
- * mid-stream. */
+ * fbearmodel.c:249-254): the level factors of both ear models change, no state
+ * does -- exactly what the reference's ear models do when the property changes
+ * mid-stream.  The new level holds for the FFT frames and filter-bank blocks
+ * that are processed by the pushes and the flush AFTER the call, whatever their
+ * samples' age: samples that were pushed earlier and still wait for the other
+ * pad (do_processing, gstpeaq.c:596-611) take it, frames and blocks that an
+ * earlier push processed keep theirs.  What they left behind -- the smeared
+ * excitation, the pattern layer's adapters, the filter bank's high-pass state
+ * and the filtered samples the next blocks' FIR windows reach back into -- stays
+ * as computed at the old level, as in the reference.  Callable at any time, also
+ * before the first push (then the same as creating the session at that level)
+ * and after the flush (no result changes).  A level outside 0 .. 130, NaN or a
+ * NULL session: PEAQ_ERR_ARG, level and stream as before.
+ * (tests/test_gpu_level_steps.py, against the reference driven along the same
+ * schedules of pushes and level changes.) */
 int peaq_session_set_level (peaq_session *s, double playback_level_db);
 
 /* explicit reset (the reference never resets, gstpeaq.c:357-361; the element
- * does not call this) */
+ * does not call this): the stream starts over -- adapters, ear-model states,
+ * pattern layer, accumulators, counters, a meter or an alignment that is set.
+ * The playback level is NOT part of the stream: the level last set with
+ * peaq_session_set_level (or the one of peaq_session_create) stays, so a reset
+ * session equals a session created at that level. */
 int peaq_session_reset (peaq_session *s);
 
 /* ---- meter: sliding-window scores of a live stream ---------------------------------------------------------------------

@@ -199,9 +199,18 @@ spread_bands (const orc_fftmodel *m, const double *pp, double *e2)
 }
 
 void
+orc_fftmodel_set_level (orc_fftmodel *m, double level_db)
+{
+  /* fftearmodel.c:305-314 (set_playback_level): the level factor alone, no table and no state */
+  const double gamma = 0.84971762641205;       /* fftearmodel.c:52 */
+  const int n = ORC_FFT_FRAME;
+  m->level_factor = pow (10, level_db / 10) /
+    (8. / 3. * (gamma / 4 * (n - 1)) * (gamma / 4 * (n - 1)));
+}
+
+void
 orc_fftmodel_init (orc_fftmodel *m, int bands, double level_db)
 {
-  const double gamma = 0.84971762641205;       /* fftearmodel.c:52 */
   const int n = ORC_FFT_FRAME;
   double fc[ORC_MAXBANDS], ones[ORC_MAXBANDS], sp[ORC_MAXBANDS];
   double z_lo = 7. * asinh (80. / 650.), z_hi = 7. * asinh (18000. / 650.);
@@ -215,9 +224,7 @@ orc_fftmodel_init (orc_fftmodel *m, int bands, double level_db)
   /* fftearmodel.c:253-256: squared outer/middle ear weight per bin */
   for (k = 0; k <= n / 2; k++)
     m->ear_weight2[k] = pow (ear_weight ((double) k * FS / n), 2);
-  /* fftearmodel.c:312-313 */
-  m->level_factor = pow (10, level_db / 10) /
-    (8. / 3. * (gamma / 4 * (n - 1)) * (gamma / 4 * (n - 1)));
+  orc_fftmodel_set_level (m, level_db);
 
   /* fftearmodel.c:701-773 */
   m->delta_z = 27. / (bands - 1);
@@ -331,12 +338,19 @@ static const int fb_len[ORC_FB_BANDS] = {      /* BS.1387 Table 8; fbearmodel.c:
 #define FB_CL 0.0802581846102741               /* fbearmodel.c:51 */
 
 void
+orc_fbmodel_set_level (orc_fbmodel *m, double level_db)
+{
+  /* fbearmodel.c:249-254 (set_playback_level): the level factor alone, no filter and no state */
+  m->level_factor = pow (10., level_db / 20.);
+}
+
+void
 orc_fbmodel_init (orc_fbmodel *m, double level_db)
 {
   double fc[ORC_FB_BANDS];
   int band, n;
   memset (m, 0, sizeof *m);
-  m->level_factor = pow (10., level_db / 20.);      /* fbearmodel.c:252-253 */
+  orc_fbmodel_set_level (m, level_db);
   for (n = 0; n < 6; n++)                           /* fbearmodel.c:182-185 */
     m->back_mask[n] = cos (M_PI * (n - 5.) / 12.) * cos (M_PI * (n - 5.) / 12.) * 0.9761 / 6.;
   for (band = 0; band < ORC_FB_BANDS; band++) {
@@ -1465,6 +1479,27 @@ orc_session_new (int advanced, int channels, double level_db)
 }
 
 void
+orc_session_set_level (orc_session *s, double level_db)
+{
+  /* gstpeaq.c:508-515 (set_property, PROP_PLAYBACK_LEVEL): both ear models, whichever version runs; the adapters,
+   * the ear models' states, the pattern layer and the accumulators are not touched, so the frames and blocks that
+   * later pushes or the flush process -- samples that already wait for the other pad included (do_processing,
+   * gstpeaq.c:596-611) -- take the new level */
+  orc_fftmodel_set_level (&s->fftm, level_db);
+  if (s->advanced)
+    orc_fbmodel_set_level (&s->fbm, level_db);
+}
+
+/* Test hook: a basic-version session that is driven push by push writes orc_flat_mov_trace's rows into
+ * out[n_frames][channels][8] as its frames are processed. */
+void
+orc_session_trace_basic (orc_session *s, double *out, unsigned n_frames)
+{
+  s->trace = s->advanced ? NULL : out;
+  s->trace_frames = n_frames;
+}
+
+void
 orc_session_free (orc_session *s)
 {
   if (!s)
@@ -1608,17 +1643,20 @@ flat_bands (int bands, orc_fftmodel *fm, orc_fbmodel *bm)
   return &fm->b;
 }
 
+/* n_steps level changes: level[i] is set on the model before frame at[i] (at[] ascending), the state is kept */
 void
-orc_flat_fftear (int bands, double level_db, const float *x, int n_frames, int hop,
-                 double *power, double *weighted, double *unsmeared, double *excitation,
-                 int *energy, double *loudness)
+orc_flat_fftear_steps (int bands, double level_db, int n_steps, const int *at, const double *level, const float *x,
+                       int n_frames, int hop, double *power, double *weighted, double *unsmeared,
+                       double *excitation, int *energy, double *loudness)
 {
   orc_fftmodel *m = (orc_fftmodel *) malloc (sizeof *m);
   orc_fftstate st;
-  int f;
+  int f, i = 0;
   orc_fftmodel_init (m, bands, level_db);
   orc_fftstate_reset (&st);
   for (f = 0; f < n_frames; f++) {
+    for (; i < n_steps && at[i] <= f; i++)
+      orc_fftmodel_set_level (m, level[i]);
     orc_fftmodel_process (m, &st, x + (size_t) f * hop);
     if (power) memcpy (power + (size_t) f * ORC_FFT_BINS, st.power, sizeof st.power);
     if (weighted) memcpy (weighted + (size_t) f * ORC_FFT_BINS, st.weighted, sizeof st.weighted);
@@ -1631,15 +1669,27 @@ orc_flat_fftear (int bands, double level_db, const float *x, int n_frames, int h
 }
 
 void
-orc_flat_fbear (double level_db, const float *x, int n_blocks,
-                double *unsmeared, double *excitation, double *loudness)
+orc_flat_fftear (int bands, double level_db, const float *x, int n_frames, int hop,
+                 double *power, double *weighted, double *unsmeared, double *excitation,
+                 int *energy, double *loudness)
+{
+  orc_flat_fftear_steps (bands, level_db, 0, NULL, NULL, x, n_frames, hop, power, weighted, unsmeared, excitation,
+                         energy, loudness);
+}
+
+/* the same for the filter bank: level[i] before block at[i] */
+void
+orc_flat_fbear_steps (double level_db, int n_steps, const int *at, const double *level, const float *x, int n_blocks,
+                      double *unsmeared, double *excitation, double *loudness)
 {
   orc_fbmodel m;
   orc_fbstate *st = (orc_fbstate *) malloc (sizeof *st);
-  int f;
+  int f, i = 0;
   orc_fbmodel_init (&m, level_db);
   orc_fbstate_reset (st);
   for (f = 0; f < n_blocks; f++) {
+    for (; i < n_steps && at[i] <= f; i++)
+      orc_fbmodel_set_level (&m, level[i]);
     orc_fbmodel_process (&m, st, x + (size_t) f * ORC_FB_FRAME);
     if (unsmeared) memcpy (unsmeared + (size_t) f * ORC_FB_BANDS, st->unsmeared, sizeof st->unsmeared);
     if (excitation) memcpy (excitation + (size_t) f * ORC_FB_BANDS, st->excitation, sizeof st->excitation);
@@ -1647,6 +1697,13 @@ orc_flat_fbear (double level_db, const float *x, int n_blocks,
   }
   orc_fbmodel_free (&m);
   free (st);
+}
+
+void
+orc_flat_fbear (double level_db, const float *x, int n_blocks,
+                double *unsmeared, double *excitation, double *loudness)
+{
+  orc_flat_fbear_steps (level_db, 0, NULL, NULL, x, n_blocks, unsmeared, excitation, loudness);
 }
 
 void

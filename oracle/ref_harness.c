@@ -14,9 +14,17 @@
  *   ref_harness time ADV CH SEED0 NPAIRS NSAMPLES [REPEATS START_EPOCH]
  *                                              wall-clock of the element on NPAIRS synth pairs, with their MOVs/DI/ODG;
  *                                              REPEATS > 0: one timed region that starts at START_EPOCH (all-core runs)
- *   (environment REF_PLAYBACK_LEVEL=<dB> sets the element's playback_level in pair / synth / launch)
- *   ref_harness fftear BANDS FILE.f32             per-frame ear-model dumps (mono, hop 1024)
- *   ref_harness fbear FILE.f32                    per-block filter-bank dumps (mono, 192)
+ *   (environment REF_PLAYBACK_LEVEL=<dB> sets the element's playback_level in pair / synth / launch / sched)
+ *   ref_harness sched ADV CH REF.f32 TEST.f32 SCHEDULE
+ *                                              the element alone, driven on ONE thread: SCHEDULE is a comma-separated
+ *                                              list of  r:N  (chain the next N samples per channel of REF.f32 into the
+ *                                              ref pad),  t:N  (the same on the test pad) and  l:DB  (set the
+ *                                              playback_level property); then PAUSED->READY flushes.  Which frame sees
+ *                                              which level is the schedule's business alone (in `pair` the two
+ *                                              filesrc threads decide it)
+ *   ref_harness fftear BANDS FILE.f32 [F:DB,...]  per-frame ear-model dumps (mono, hop 1024); playback level DB is
+ *                                              set on the ear model before frame F
+ *   ref_harness fbear FILE.f32 [B:DB,...]         per-block filter-bank dumps (mono, 192); the same before block B
  * Output: one JSON object on stdout.
  */
 #include REF_GSTPEAQ_C
@@ -44,6 +52,26 @@ print_arr (const char *name, const double *v, int n, int last)
   printf ("]%s", last ? "" : ", ");
 }
 
+/* the element's results as one JSON object: MOVs through the reference's own peaq_movaccum_get_value */
+static void
+print_results (GstElement *peaq_el, int advanced)
+{
+  GstPeaq *pq = GST_PEAQ (peaq_el);
+  double movs[COUNT_MOV_BASIC], di, odg, snr;
+  int i, n = advanced ? COUNT_MOV_ADVANCED : COUNT_MOV_BASIC;
+  for (i = 0; i < n; i++)
+    movs[i] = peaq_movaccum_get_value (pq->mov_accum[i]);
+  g_object_get (peaq_el, "di", &di, "odg", &odg, "totalsnr", &snr, NULL);
+  printf ("{\"advanced\": %d, \"channels\": %d, \"frames\": %u, \"fb_frames\": %u, "
+          "\"loudness_reached_frame\": %u, ", advanced, pq->channels, pq->frame_counter,
+          pq->frame_counter_fb, pq->loudness_reached_frame);
+  print_arr ("movs", movs, n, 0);
+  print_arr ("di", &di, 1, 0);
+  print_arr ("odg", &odg, 1, 0);
+  print_arr ("totalsnr", &snr, 1, 1);
+  printf ("}\n");
+}
+
 static int
 run_pipeline (int advanced, const char *desc)
 {
@@ -51,9 +79,6 @@ run_pipeline (int advanced, const char *desc)
   GstElement *pipe, *peaq_el;
   GstBus *bus;
   GstMessage *msg;
-  GstPeaq *pq;
-  double movs[COUNT_MOV_BASIC], di, odg, snr;
-  int i, n;
 
   pipe = gst_parse_launch (desc, &err);
   if (!pipe) {
@@ -76,19 +101,7 @@ run_pipeline (int advanced, const char *desc)
   gst_object_unref (bus);
   gst_element_set_state (pipe, GST_STATE_NULL);     /* PAUSED->READY flushes, gstpeaq.c:764-778 */
 
-  pq = GST_PEAQ (peaq_el);
-  n = advanced ? COUNT_MOV_ADVANCED : COUNT_MOV_BASIC;
-  for (i = 0; i < n; i++)
-    movs[i] = peaq_movaccum_get_value (pq->mov_accum[i]);
-  g_object_get (peaq_el, "di", &di, "odg", &odg, "totalsnr", &snr, NULL);
-  printf ("{\"advanced\": %d, \"channels\": %d, \"frames\": %u, \"fb_frames\": %u, "
-          "\"loudness_reached_frame\": %u, ", advanced, pq->channels, pq->frame_counter,
-          pq->frame_counter_fb, pq->loudness_reached_frame);
-  print_arr ("movs", movs, n, 0);
-  print_arr ("di", &di, 1, 0);
-  print_arr ("odg", &odg, 1, 0);
-  print_arr ("totalsnr", &snr, 1, 1);
-  printf ("}\n");
+  print_results (peaq_el, advanced);
   gst_object_unref (peaq_el);
   gst_object_unref (pipe);
   return 0;
@@ -252,8 +265,25 @@ read_f32 (const char *path, size_t *n)
   return buf;
 }
 
+/* "N:DB,N:DB,...": DB is set on `ear` before unit N; *sched walks along the list */
+static void
+apply_levels (PeaqEarModel *ear, const char **sched, size_t unit)
+{
+  while (*sched && **sched) {
+    char *end;
+    unsigned long at = strtoul (*sched, &end, 10);
+    double level;
+    if (*end != ':') { fprintf (stderr, "bad level list at \"%s\"\n", *sched); exit (2); }
+    if (at > unit)
+      return;
+    level = g_ascii_strtod (end + 1, &end);
+    g_object_set (ear, "playback-level", level, NULL);
+    *sched = *end == ',' ? end + 1 : end;
+  }
+}
+
 static int
-dump_fftear (int bands, const char *path)
+dump_fftear (int bands, const char *path, const char *levels)
 {
   size_t n, pos;
   float *x = read_f32 (path, &n);
@@ -262,6 +292,7 @@ dump_fftear (int bands, const char *path)
   int first = 1;
   printf ("{\"bands\": %d, \"frames\": [", bands);
   for (pos = 0; pos + 2048 <= n; pos += 1024) {
+    apply_levels (ear, &levels, pos / 1024);
     peaq_earmodel_process_block (ear, st, x + pos);
     printf ("%s{", first ? "" : ", ");
     first = 0;
@@ -277,7 +308,7 @@ dump_fftear (int bands, const char *path)
 }
 
 static int
-dump_fbear (const char *path)
+dump_fbear (const char *path, const char *levels)
 {
   size_t n, pos;
   float *x = read_f32 (path, &n);
@@ -286,6 +317,7 @@ dump_fbear (const char *path)
   int first = 1;
   printf ("{\"bands\": 40, \"frames\": [");
   for (pos = 0; pos + 192 <= n; pos += 192) {
+    apply_levels (ear, &levels, pos / 192);
     peaq_earmodel_process_block (ear, st, x + pos);
     printf ("%s{", first ? "" : ", ");
     first = 0;
@@ -294,6 +326,77 @@ dump_fbear (const char *path)
     printf ("\"loudness\": %.17g}", peaq_earmodel_calc_loudness (ear, st));
   }
   printf ("]}\n");
+  return 0;
+}
+
+/* The element alone, no pipeline and no streaming threads: this thread sends the events a source would send, chains the
+ * buffers in the schedule's order and sets the property between them.  pad_chain (gstpeaq.c:613-661) processes, inside
+ * the call, every frame and block both adapters hold; set_property (gstpeaq.c:505-515) changes the ear models' level
+ * factors between two such calls. */
+static int
+run_sched (int advanced, int channels, const char *ref_path, const char *test_path, const char *sched)
+{
+  size_t n[2], pos[2] = { 0, 0 };
+  float *x[2];
+  GstElement *el = gst_element_factory_make ("peaq", "peaq");
+  GstPeaq *pq = GST_PEAQ (el);
+  GstPad *pad[2];
+  GstSegment seg;
+  GstCaps *caps;
+  int p;
+  x[0] = read_f32 (ref_path, &n[0]);
+  x[1] = read_f32 (test_path, &n[1]);
+  g_object_set (el, "advanced", advanced, "console-output", FALSE, NULL);
+  if (getenv ("REF_PLAYBACK_LEVEL"))
+    g_object_set (el, "playback_level", atof (getenv ("REF_PLAYBACK_LEVEL")), NULL);
+  if (gst_element_set_state (el, GST_STATE_PLAYING) == GST_STATE_CHANGE_FAILURE) {
+    fprintf (stderr, "the element does not go to PLAYING\n");
+    return 3;
+  }
+  pad[0] = pq->refpad;
+  pad[1] = pq->testpad;
+  caps = gst_caps_new_simple ("audio/x-raw", "format", G_TYPE_STRING, "F32LE", "layout", G_TYPE_STRING, "interleaved",
+                              "rate", G_TYPE_INT, 48000, "channels", G_TYPE_INT, channels, NULL);
+  if (channels == 2)
+    gst_caps_set_simple (caps, "channel-mask", GST_TYPE_BITMASK, (guint64) 3, NULL);
+  gst_segment_init (&seg, GST_FORMAT_TIME);
+  for (p = 0; p < 2; p++)
+    if (!gst_pad_send_event (pad[p], gst_event_new_stream_start (p ? "test" : "ref"))
+        || !gst_pad_send_event (pad[p], gst_event_new_caps (caps))
+        || !gst_pad_send_event (pad[p], gst_event_new_segment (&seg))) {
+      fprintf (stderr, "pad %d refuses its start events\n", p);
+      return 3;
+    }
+  gst_caps_unref (caps);
+  if (pq->channels != channels) {
+    fprintf (stderr, "the element has %d channels after the caps event\n", pq->channels);
+    return 3;
+  }
+  while (*sched) {
+    char op = sched[0], *end;
+    if (!strchr ("rtl", op) || sched[1] != ':') { fprintf (stderr, "bad schedule at \"%s\"\n", sched); return 2; }
+    if (op == 'l') {
+      g_object_set (el, "playback_level", g_ascii_strtod (sched + 2, &end), NULL);
+    } else {
+      size_t cnt = strtoul (sched + 2, &end, 10) * channels;
+      GstBuffer *buf;
+      p = op == 't';
+      if (pos[p] + cnt > n[p]) { fprintf (stderr, "schedule runs past the end of pad %d\n", p); return 2; }
+      buf = gst_buffer_new_allocate (NULL, cnt * sizeof (float), NULL);
+      gst_buffer_fill (buf, 0, x[p] + pos[p], cnt * sizeof (float));
+      pos[p] += cnt;
+      if (gst_pad_chain (pad[p], buf) != GST_FLOW_OK) { fprintf (stderr, "pad %d refuses a buffer\n", p); return 3; }
+    }
+    if (*end && *end != ',') { fprintf (stderr, "bad schedule at \"%s\"\n", sched); return 2; }
+    sched = *end ? end + 1 : end;
+  }
+  if (pos[0] != n[0] || pos[1] != n[1]) {
+    fprintf (stderr, "schedule leaves %zu / %zu floats unpushed\n", n[0] - pos[0], n[1] - pos[1]);
+    return 2;
+  }
+  gst_element_set_state (el, GST_STATE_NULL);        /* PAUSED->READY flushes, gstpeaq.c:764-778 */
+  print_results (el, advanced);
+  gst_object_unref (el);
   return 0;
 }
 
@@ -332,6 +435,8 @@ main (int argc, char **argv)
   GST_PLUGIN_STATIC_REGISTER (peaq);
   if (argc >= 6 && !strcmp (argv[1], "pair"))
     return run_files (atoi (argv[2]), atoi (argv[3]), argv[4], argv[5]);
+  if (argc >= 7 && !strcmp (argv[1], "sched"))
+    return run_sched (atoi (argv[2]), atoi (argv[3]), argv[4], argv[5], argv[6]);
   if (argc >= 6 && !strcmp (argv[1], "synth")) {
     int adv = atoi (argv[2]), ch = atoi (argv[3]);
     uint32_t seed = (uint32_t) strtoul (argv[4], NULL, 0), ns = (uint32_t) strtoul (argv[5], NULL, 0);
@@ -356,9 +461,9 @@ main (int argc, char **argv)
   if (argc >= 4 && !strcmp (argv[1], "launch"))
     return run_pipeline (atoi (argv[2]), argv[3]);
   if (argc >= 4 && !strcmp (argv[1], "fftear"))
-    return dump_fftear (atoi (argv[2]), argv[3]);
+    return dump_fftear (atoi (argv[2]), argv[3], argc >= 5 ? argv[4] : NULL);
   if (argc >= 3 && !strcmp (argv[1], "fbear"))
-    return dump_fbear (argv[2]);
+    return dump_fbear (argv[2], argc >= 4 ? argv[3] : NULL);
   if (argc >= 3 && !strcmp (argv[1], "tables"))
     return dump_tables (atoi (argv[2]));
   fprintf (stderr, "usage: see the header of oracle/ref_harness.c\n");

@@ -32,6 +32,9 @@ def make_inputs(case):
             ref, test = ref * g, test * g
         if case.get("gain"):                           # drive into full scale ...
             ref, test = ref * np.float32(case["gain"]), test * np.float32(case["gain"])
+        if case.get("peak_to"):                        # ... or exactly to it: the pair's largest |sample| becomes peak_to
+            g = np.float32(case["peak_to"]) / max(np.abs(ref).max(), np.abs(test).max())
+            ref, test = ref * g, test * g
         # severe degradations of the test signal alone: element-wise float32 operations in a fixed association, so
         # that the bits are the same on every machine (no convolve / dot, whose summation order the library chooses)
         for _ in range(case.get("box8_test", 0)):
@@ -198,13 +201,124 @@ def severe_stage_cases():
 
 
 def level_cases():
-    """playback_level other than the default (the level enters both ear models' input scaling)"""
+    """playback_level other than the default (the level enters both ear models' input scaling): the eight stereo cases
+    at 60 .. 130 dB first, then the lower end of the property's range 0 .. 130 (gstpeaq.c:275-281) and the two ends of
+    the first eight in mono.  At 0 dB a loudness gate may never open: NaN results are recorded as the reference gives
+    them."""
     cases = []
     for adv in (0, 1):
         for level, seed in ((60.0, 3), (75.5, 4), (105.0, 5), (130.0, 6)):
             cases.append(dict(name=f"synth_s{seed}_L{level:g}", kind="synth", seed=seed, channels=2, n=96000,
                               level=level, advanced=adv))
+    for adv in (0, 1):
+        for level, seed in ((0.0, 7), (30.0, 8), (45.0, 9)):
+            cases.append(dict(name=f"synth_s{seed}_L{level:g}", kind="synth", seed=seed, channels=2, n=96000,
+                              level=level, advanced=adv))
+        for level, seed in ((60.0, 14), (130.0, 15)):
+            cases.append(dict(name=f"synth_s{seed}_L{level:g}_mono", kind="synth", seed=seed, channels=1, n=96000,
+                              level=level, advanced=adv))
     return cases
+
+
+LEVEL_STEP_N = 96000        # 93 frames, 500 blocks: frame 24, block 125 and the loudness gates are behind the steps
+LEVEL_STEP_AT = 48128       # = 47 * 1024: frames 0 .. 45 and blocks 0 .. 249 lie wholly in front of it
+
+
+def level_schedule(n, chunk, sets, lead=0):
+    """A schedule for tests/cases.py:level_step_cases(): a list of ["r", count], ["t", count] (push that many samples per
+    channel on the ref / test pad) and ["l", level] (set the playback level).  Both pads are pushed alternately, ref
+    first, in buffers of `chunk` samples that are cut at each position of `sets` = [(sample, level), ...]; the level is
+    set once the test pad stands at `sample` and the ref pad `lead` samples further (or at its end)."""
+    out, pos = [], [0, 0]
+    for at, level in list(sets) + [(n, None)]:
+        goal = [min(n, at + lead), at]
+        while pos[0] < goal[0] or pos[1] < goal[1]:
+            for p in (0, 1):
+                step = min(chunk, goal[p] - pos[p])
+                if step > 0:
+                    out.append(["rt"[p], step])
+                    pos[p] += step
+        if level is not None:
+            out.append(["l", float(level)])
+    return out
+
+
+def schedule_string(schedule):
+    """the form oracle/ref_harness.c's `sched` mode reads: r:4096,t:4096,l:112,..."""
+    return ",".join(f"{op}:{v if op != 'l' else repr(float(v))}" for op, v in schedule)
+
+
+def run_schedule(session, ref, test, schedule, after_push=None):
+    """drive a session (the oracle's or the HIP one: push_ref / push_test / set_level) along a schedule; after_push is
+    called behind every push"""
+    pos = {"r": 0, "t": 0}
+    for op, v in schedule:
+        if op == "l":
+            session.set_level(v)
+            continue
+        x = ref if op == "r" else test
+        (session.push_ref if op == "r" else session.push_test)(x[pos[op]:pos[op] + v])
+        pos[op] += v
+        if after_push:
+            after_push()
+    assert pos["r"] == len(ref) and pos["t"] == len(test), pos
+
+
+def level_step_cases():
+    """The playback level changed in mid-stream (gstpeaq.c:508-515): `level` is the level the element starts at,
+    `schedule` what follows (level_schedule).  Recorded by tools/make_golden.py level_steps from the reference element
+    driven on one thread, so that the schedule alone decides which frame and block sees which level.
+
+      up / down       92 -> 112 / 60 dB after sample 48128 of both pads, buffers of 4096: a step of +20 / -32 dB into
+                      running state (smeared excitation, adapters, high-pass state, the filter bank's FIR tail)
+      waiting         the ref pad stands 5000 samples further than the test pad at the change: the four frames and 26
+                      blocks that wait for the test pad take the new level
+      extremes        buffers of 1000 samples on each pad, the level alternating 60 / 130 dB from one round (ref, then
+                      test) to the next: every launch of a session has another level than the one before
+      low             92 -> 0 dB at 48128 and back to 92 dB 10000 samples later
+      flush_only      the level changes behind the last push: the flush frame alone takes it (500 whole blocks: the
+                      filter bank has no flush block)
+      headroom_up / headroom_down
+                      a pair whose largest sample is at full scale (1 to a float32 rounding), 60 -> 130 / 130 -> 60 dB at 48128: the FIR
+                      window behind the step holds a tail filtered at a level 70 dB away
+
+    Seeds: 70 .. 79 in the table's order, except where a frame of the basic version, run along the schedule in the
+    oracle, has its largest noise-to-mask ratio within 0.1 dB of RelDistFrames' 1.5 dB threshold
+    (tests/test_level_steps_host.py).  Those take the first seed from 80 upwards that keeps the margin, one seed per
+    case: step_down_stereo 81 (73 came to 0.048 dB, 80 to 0.010 dB), step_waiting_stereo 83 (74: 0.005 dB,
+    82: 0.029 dB)."""
+    n, at = LEVEL_STEP_N, LEVEL_STEP_AT
+    rounds = -(-n // 1000)
+    rows = [
+        ("up_mono", 70, 1, {}, 92.0, level_schedule(n, 4096, [(at, 112.0)])),
+        ("up_stereo", 71, 2, {}, 92.0, level_schedule(n, 4096, [(at, 112.0)])),
+        ("down_mono", 72, 1, {}, 92.0, level_schedule(n, 4096, [(at, 60.0)])),
+        ("down_stereo", 81, 2, {}, 92.0, level_schedule(n, 4096, [(at, 60.0)])),
+        ("waiting_stereo", 83, 2, {}, 92.0, level_schedule(n, 4096, [(at, 112.0)], lead=5000)),
+        ("extremes_stereo", 75, 2, {}, 60.0,
+         level_schedule(n, 1000, [(1000 * k, 130.0 if k % 2 else 60.0) for k in range(1, rounds)])),
+        ("low_mono", 76, 1, {}, 92.0, level_schedule(n, 4096, [(at, 0.0), (at + 10000, 92.0)])),
+        ("flush_only_stereo", 77, 2, {}, 92.0, level_schedule(n, 4096, [(n, 112.0)])),
+        ("headroom_up_mono", 78, 1, dict(peak_to=1.0), 60.0, level_schedule(n, 4096, [(at, 130.0)])),
+        ("headroom_down_mono", 79, 1, dict(peak_to=1.0), 130.0, level_schedule(n, 4096, [(at, 60.0)])),
+    ]
+    cases = []
+    for adv in (0, 1):
+        for name, seed, channels, keys, level, schedule in rows:
+            cases.append(dict(name=f"step_{name}", kind="synth", seed=seed, channels=channels, n=n, level=level,
+                              schedule=schedule, advanced=adv, **keys))
+    return cases
+
+
+# stage dumps across one step (tests/golden/ref_stages_level_step.npz): the ear models alone, mono, 92 -> 112 dB set
+# before FFT frame 20 / filter-bank block 100, 40 frames / 200 blocks of the signals of stage_inputs()' pair run longer
+LEVEL_STEP_STAGE = dict(level=92.0, to=112.0, frame=20, frames=40, block=100, blocks=200)
+
+
+def level_step_stage_inputs():
+    n = max((LEVEL_STEP_STAGE["frames"] - 1) * 1024 + 2048, LEVEL_STEP_STAGE["blocks"] * 192)
+    ref, test = synth_np.pair(5, 1, n)
+    return {"synth5_ref": ref[:, 0].copy(), "synth5_test": test[:, 0].copy()}
 
 
 def resampled_cases():

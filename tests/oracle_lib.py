@@ -31,6 +31,8 @@ def lib():
         L.orc_session_new.restype = C.c_void_p
         L.orc_session_new.argtypes = [C.c_int, C.c_int, C.c_double]
         L.orc_session_free.argtypes = [C.c_void_p]
+        L.orc_session_set_level.argtypes = [C.c_void_p, C.c_double]
+        L.orc_session_trace_basic.argtypes = [C.c_void_p, _dp, C.c_uint]
         L.orc_session_push_ref.argtypes = [C.c_void_p, _fp, C.c_size_t]
         L.orc_session_push_test.argtypes = [C.c_void_p, _fp, C.c_size_t]
         L.orc_session_flush.argtypes = [C.c_void_p]
@@ -41,6 +43,9 @@ def lib():
         L.orc_session_frames.argtypes = [C.c_void_p]
         L.orc_flat_fftear.argtypes = [C.c_int, C.c_double, _fp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp]
         L.orc_flat_fbear.argtypes = [C.c_double, _fp, C.c_int, _dp, _dp, _dp]
+        L.orc_flat_fftear_steps.argtypes = [C.c_int, C.c_double, C.c_int, _ip, _dp, _fp, C.c_int, C.c_int, _dp, _dp, _dp,
+                                            _dp, _ip, _dp]
+        L.orc_flat_fbear_steps.argtypes = [C.c_double, C.c_int, _ip, _dp, _fp, C.c_int, _dp, _dp, _dp]
         L.orc_flat_leveladapt.argtypes = [C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.orc_flat_modproc.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp]
         L.orc_flat_tables.argtypes = [C.c_int, _dp]
@@ -73,6 +78,16 @@ class Session:
     def push_test(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
         self.L.orc_session_push_test(self.h, _ptr(x, _fp), x.size // self.channels)
+
+    def set_level(self, level):
+        """the playback_level property in mid-stream (gstpeaq.c:508-515): frames and blocks processed from now on"""
+        self.L.orc_session_set_level(self.h, float(level))
+
+    def trace_basic(self, n_frames):
+        """basic version: mov_trace's dict, filled in as the frames are processed (keep it while the session lives)"""
+        self._trace = np.zeros((n_frames, self.channels, 8))
+        self.L.orc_session_trace_basic(self.h, _ptr(self._trace, _dp), n_frames)
+        return dict(zip(MOV_TRACE, np.moveaxis(self._trace, 2, 0)))
 
     def flush(self):
         self.L.orc_session_flush(self.h)
@@ -235,23 +250,34 @@ def backend_records_advanced(fb_recs, fft_recs):
                 trace_frames=dict(zip(MOV_TRACE_ADV_FRAME, np.moveaxis(of, 2, 0))))
 
 
-def fftear(bands, x, n_frames, hop, level=92.0):
+def _steps(steps):
+    """[(unit, level), ...] -> the two arrays of the oracle's *_steps entry points"""
+    at = np.array([int(u) for u, _ in steps], dtype=np.int32)
+    lv = np.array([float(v) for _, v in steps], dtype=np.float64)
+    return len(steps), _ptr(at, _ip), _ptr(lv, _dp), (at, lv)
+
+
+def fftear(bands, x, n_frames, hop, level=92.0, steps=()):
+    """steps: [(frame, level), ...], each level set on the model before that frame (state kept)"""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = dict(power=np.zeros((n_frames, 1025)), weighted=np.zeros((n_frames, 1025)),
                unsmeared=np.zeros((n_frames, bands)), excitation=np.zeros((n_frames, bands)),
                energy=np.zeros(n_frames, dtype=np.int32), loudness=np.zeros(n_frames))
-    lib().orc_flat_fftear(bands, level, _ptr(x, _fp), n_frames, hop, _ptr(out["power"], _dp),
-                          _ptr(out["weighted"], _dp), _ptr(out["unsmeared"], _dp),
-                          _ptr(out["excitation"], _dp), _ptr(out["energy"], _ip), _ptr(out["loudness"], _dp))
+    n, at, lv, _keep = _steps(steps)
+    lib().orc_flat_fftear_steps(bands, level, n, at, lv, _ptr(x, _fp), n_frames, hop, _ptr(out["power"], _dp),
+                                _ptr(out["weighted"], _dp), _ptr(out["unsmeared"], _dp),
+                                _ptr(out["excitation"], _dp), _ptr(out["energy"], _ip), _ptr(out["loudness"], _dp))
     return out
 
 
-def fbear(x, n_blocks, level=92.0):
+def fbear(x, n_blocks, level=92.0, steps=()):
+    """steps: [(block, level), ...] as in fftear"""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = dict(unsmeared=np.zeros((n_blocks, 40)), excitation=np.zeros((n_blocks, 40)),
                loudness=np.zeros(n_blocks))
-    lib().orc_flat_fbear(level, _ptr(x, _fp), n_blocks, _ptr(out["unsmeared"], _dp),
-                         _ptr(out["excitation"], _dp), _ptr(out["loudness"], _dp))
+    n, at, lv, _keep = _steps(steps)
+    lib().orc_flat_fbear_steps(level, n, at, lv, _ptr(x, _fp), n_blocks, _ptr(out["unsmeared"], _dp),
+                               _ptr(out["excitation"], _dp), _ptr(out["loudness"], _dp))
     return out
 
 

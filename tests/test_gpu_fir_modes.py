@@ -55,7 +55,7 @@ def test_filterbank_blocks_fp32_fir(fp32_ctx, case):
 
 
 def test_advanced_goldens_fp32_fir(fp32_ctx, golden_dir):
-    """all advanced end-to-end cases of the real reference (27 + 4 playback levels)"""
+    """all advanced end-to-end cases of the real reference (and the playback levels of ref_e2e_level.json)"""
     import torch
     import gstpeaq_amd
     recs = [r for r in json.loads((golden_dir / "ref_e2e.json").read_text()) if r["case"]["advanced"]]

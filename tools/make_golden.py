@@ -10,6 +10,10 @@ not exist on the GPU box, the committed fixtures travel instead.
   tests/golden/ref_stages.npz         per-frame ear-model outputs (public getters)
   tests/golden/ref_tables.json        band tables (Appendix C of SURVEY.md, in full)
   tests/golden/ref_e2e_level.json     the same for other playback levels      (python tools/make_golden.py levels)
+  tests/golden/ref_e2e_level_steps.json  the level changed in mid-stream: the element alone, driven on one thread along
+                                      each schedule of tests/cases.py:level_step_cases()   (python tools/make_golden.py level_steps)
+  tests/golden/ref_stages_level_step.npz  per-frame / per-block ear-model outputs across one level step
+                                      (python tools/make_golden.py level_steps)
   tests/golden/ref_e2e_settings.json  the same for the reference built with each settings.h switch flipped
                                       (oracle/Makefile ref_variants)          (python tools/make_golden.py settings)
   tests/golden/ref_e2e_resampled.json pairs at 44.1 / 32 / 96 kHz through the chain of the reference's CLI,
@@ -108,6 +112,64 @@ def e2e_levels():
                                 odg=r["odg"][0], totalsnr=r["totalsnr"][0]))
             print(f"{case['name']:28s} adv={case['advanced']} level={case['level']} odg={r['odg'][0]}")
     (GOLD / "ref_e2e_level.json").write_text(json.dumps(results, indent=0))
+
+
+def e2e_level_steps():
+    """tests/golden/ref_e2e_level_steps.json: the playback_level property set between buffers (gstpeaq.c:508-515).  The
+    harness's `sched` mode chains the buffers and sets the property on one thread; a schedule without a level change
+    must give what the two-thread pipeline of `pair` gives, bit for bit (checked here on every case)."""
+    results = []
+    with tempfile.TemporaryDirectory() as td:
+        for case in case_defs.level_step_cases():
+            ref, test = case_defs.make_inputs(case)
+            rp, tp = Path(td) / "r.f32", Path(td) / "t.f32"
+            ref.astype("<f4").tofile(rp)
+            test.astype("<f4").tofile(tp)
+            pushes = [e for e in case["schedule"] if e[0] != "l"]
+            plain = run_harness("sched", case["advanced"], case["channels"], rp, tp, case_defs.schedule_string(pushes),
+                                level=case["level"])
+            piped = run_harness("pair", case["advanced"], case["channels"], rp, tp, level=case["level"])
+            assert plain == piped, case["name"]
+            r = run_harness("sched", case["advanced"], case["channels"], rp, tp,
+                            case_defs.schedule_string(case["schedule"]), level=case["level"])
+            assert r["movs"] != plain["movs"], case["name"]     # the schedule's level changes matter
+            results.append(dict(case=case, frames=r["frames"], fb_frames=r["fb_frames"], movs=r["movs"], di=r["di"][0],
+                                odg=r["odg"][0], totalsnr=r["totalsnr"][0]))
+            print(f"{case['name']:28s} adv={case['advanced']} frames={r['frames']} odg={r['odg'][0]} "
+                  f"(constant {case['level']} dB: {plain['odg'][0]})")
+    (GOLD / "ref_e2e_level_steps.json").write_text(json.dumps(results, indent=0))
+
+
+def stages_level_step():
+    """tests/golden/ref_stages_level_step.npz: the ear models alone across one level step (cases.LEVEL_STEP_STAGE).
+    Band patterns and loudness whole; the 1025-bin spectra of the reference signal whole on the frames within 3 of the
+    step (`*_near`) and at every fourth bin on all frames (`*_far`) -- the fixture stays well under the size limit."""
+    st = case_defs.LEVEL_STEP_STAGE
+    arrays = {}
+    near = slice(st["frame"] - 3, st["frame"] + 4)
+    with tempfile.TemporaryDirectory() as td:
+        for name, x in case_defs.level_step_stage_inputs().items():
+            p = Path(td) / "x.f32"
+            x.astype("<f4").tofile(p)
+            for bands in (109, 55):
+                d = run_harness("fftear", bands, p, f"{st['frame']}:{st['to']!r}", level=None)
+                assert len(d["frames"]) == st["frames"]
+                for key in ("unsmeared", "excitation"):
+                    arrays[f"fft{bands}_{name}_{key}"] = np.array([_fix(f[key]) for f in d["frames"]])
+                arrays[f"fft{bands}_{name}_energy"] = np.array([f["energy"] for f in d["frames"]])
+                arrays[f"fft{bands}_{name}_loudness"] = np.array([f["loudness"] for f in d["frames"]])
+                if bands == 109 and name == "synth5_ref":
+                    for key in ("power", "weighted"):
+                        a = np.array([_fix(f[key]) for f in d["frames"]])
+                        arrays[f"fft_{name}_{key}_near"] = a[near]
+                        arrays[f"fft_{name}_{key}_far"] = a[:, ::4]
+            d = run_harness("fbear", p, f"{st['block']}:{st['to']!r}")
+            assert len(d["frames"]) >= st["blocks"]
+            for key in ("unsmeared", "excitation"):
+                arrays[f"fb_{name}_{key}"] = np.array([_fix(f[key]) for f in d["frames"][:st["blocks"]]])
+            arrays[f"fb_{name}_loudness"] = np.array([f["loudness"] for f in d["frames"][:st["blocks"]]])
+    np.savez_compressed(GOLD / "ref_stages_level_step.npz", **arrays)
+    print("level-step stage arrays:", {k: v.shape for k, v in arrays.items()})
 
 
 # the reference built with ONE settings.h switch flipped (oracle/Makefile ref_variants): name -> the
@@ -301,11 +363,17 @@ def main():
     stages()
     e2e()
     e2e_levels()
+    e2e_level_steps()
+    stages_level_step()
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "levels":      # only the playback-level cases
         subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
         e2e_levels()
+    elif len(sys.argv) > 1 and sys.argv[1] == "level_steps":   # only the mid-stream level changes
+        subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
+        e2e_level_steps()
+        stages_level_step()
     else:
         main()
