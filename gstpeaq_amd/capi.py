@@ -246,6 +246,9 @@ class MeterReading(C.Structure):
 
 
 METER_MAX_OPEN, METER_MAX_DEPTH = 64, 4096
+# the band meter (include/peaq_amd.h, "meter: band rows"): rows per channel and reading -- the first four of
+# BAND_SUMMARY_ROWS --, and the narrower limits of the geometry with bands on
+METER_BAND_ROWS, METER_BANDS_MAX_OPEN, METER_BANDS_MAX_DEPTH = 4, 16, 256
 
 
 class LiveAlignConfig(C.Structure):
@@ -414,6 +417,15 @@ def load_library():
         if L.peaq_meter_reading_size() != C.sizeof(MeterReading):
             raise PeaqError(f"peaq_meter_reading is {L.peaq_meter_reading_size()} bytes in the library, "
                             f"{C.sizeof(MeterReading)} in this binding")
+    if hasattr(L, "peaq_session_set_meter_bands"):     # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
+        L.peaq_meter_band_rows.argtypes = []
+        L.peaq_meter_bands_workspace.argtypes = [C.POINTER(MeterConfig), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.peaq_session_set_meter_bands.argtypes = [vp, C.c_int]
+        L.peaq_session_meter_read_bands.argtypes = [vp, C.POINTER(MeterReading), dp, C.c_int, C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_uint64)]
+        L.peaq_broker_set_meter_bands.argtypes = [vp, C.c_int]
+        L.peaq_broker_meter_read_bands.argtypes = [vp, C.c_int, C.POINTER(MeterReading), dp, C.c_int, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_uint64)]
     if hasattr(L, "peaq_session_set_align"):           # (A/B runs load older variant libraries through PEAQ_AMD_LIB)
         i32p = C.POINTER(C.c_int32)
         L.peaq_live_delay_size.restype = C.c_size_t
@@ -667,6 +679,37 @@ def meter_windows(n_ref, n_test, window, hop=None):
     return [_meter_dict(rows[i]) for i in range(n.value)]
 
 
+def meter_bands_workspace(window, hop=None, depth=64, advanced=False, channels=2):
+    """peaq_meter_bands_workspace: the device bytes the band meter adds to a session of this geometry (a broker slot
+    holds 8 frames of planes in place of 64).  Host arithmetic only; refuses what set_meter(..., bands=True) refuses."""
+    cfg = MeterConfig(int(window), int(window if hop is None else hop), int(depth))
+    n = C.c_size_t(0)
+    _check(load_library().peaq_meter_bands_workspace(C.byref(cfg), int(bool(advanced)), int(channels), C.byref(n)))
+    return n.value
+
+
+def _meter_read(L, read, read_bands, advanced, channels, cap, bands):
+    """the common body of Session.meter_read and Broker.meter_read; read / read_bands: the entry with its handle bound"""
+    rows = (MeterReading * cap)()
+    n, dropped = C.c_int(0), C.c_uint64(0)
+    if not bands:
+        _check(read(rows, int(cap), C.byref(n), C.byref(dropped)))
+        return [_meter_dict(rows[i], advanced) for i in range(n.value)], dropped.value
+    row = L.peaq_band_row(int(advanced))
+    nb = L.peaq_band_count(int(advanced))
+    band_rows = np.zeros((cap, channels, METER_BAND_ROWS, row))
+    _check(read_bands(rows, band_rows.ctypes.data_as(C.POINTER(C.c_double)), int(cap), C.byref(n), C.byref(dropped)))
+    out = []
+    for i in range(n.value):
+        d = _meter_dict(rows[i], advanced)
+        d["bands"] = band_rows[i].copy()
+        for k, name in enumerate(BAND_SUMMARY_ROWS[:METER_BAND_ROWS]):
+            d[name] = d["bands"][:, k, :nb]
+        d["counted"] = d["bands"][:, 0, nb].astype(np.int64)
+        out.append(d)
+    return out, dropped.value
+
+
 def _align_config(max_lag, probe, watch):
     return LiveAlignConfig(int(max_lag or 0), int(probe or 0), int(watch or 0), 0)
 
@@ -824,10 +867,11 @@ class Session:
         """peaq_session_reset: the stream starts over; a meter that is set starts over with it"""
         _check(self.L.peaq_session_reset(self.h))
 
-    def set_meter(self, window, hop=None, depth=64):
+    def set_meter(self, window, hop=None, depth=64, bands=False):
         """peaq_session_set_meter: sliding-window readings of `window` FFT frames every `hop` (default: window), the
         `depth` newest kept (meter_frames converts seconds).  window = 0 or None switches the meter off.  Before the
-        first push or right after reset() only."""
+        first push or right after reset() only.  bands: the band meter as well (peaq_session_set_meter_bands: at most
+        METER_BANDS_MAX_OPEN windows open at once, depth at most METER_BANDS_MAX_DEPTH)."""
         if not window:
             _check(self.L.peaq_session_set_meter(self.h, None))
             self._meter_depth = 0
@@ -835,16 +879,25 @@ class Session:
         cfg = MeterConfig(int(window), int(window if hop is None else hop), int(depth))
         _check(self.L.peaq_session_set_meter(self.h, C.byref(cfg)))
         self._meter_depth = int(depth)
+        if bands:
+            self.set_meter_bands(True)
 
-    def meter_read(self, cap=None):
+    def set_meter_bands(self, on=True):
+        """peaq_session_set_meter_bands: the band rows of every reading on or off; after set_meter, which switches
+        them off"""
+        _check(self.L.peaq_session_set_meter_bands(self.h, int(bool(on))))
+
+    def meter_read(self, cap=None, bands=False):
         """(readings, dropped): the delivered, not yet read readings, oldest first -- each a dict of the result's
         fields plus index, start, length, first_frame, n_frames, first_block, n_blocks -- and how many were lost since
-        the previous read (peaq_session_meter_read).  cap: at most so many (default: the depth that was set)."""
+        the previous read (peaq_session_meter_read).  cap: at most so many (default: the depth that was set).
+        bands (peaq_session_meter_read_bands; the band meter must be on): every dict also has "bands", ndarray
+        [channels, 4, row], its named views nmr_sum, nmr_max, nmr_disturbed, exc_ref_sum [channels, bands] and
+        counted [channels], the window's counted frames."""
         cap = max(1, getattr(self, "_meter_depth", 0)) if cap is None else int(cap)
-        rows = (MeterReading * cap)()
-        n, dropped = C.c_int(0), C.c_uint64(0)
-        _check(self.L.peaq_session_meter_read(self.h, rows, int(cap), C.byref(n), C.byref(dropped)))
-        return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
+        return _meter_read(self.L, lambda *a: self.L.peaq_session_meter_read(self.h, *a),
+                           lambda *a: self.L.peaq_session_meter_read_bands(self.h, *a), self.advanced, self.channels,
+                           cap, bands)
 
     def set_align(self, max_lag, probe=None, watch=None):
         """peaq_session_set_align: hold the stream until both pads have `probe` samples (default 48000 + 2 max_lag),
@@ -941,24 +994,29 @@ class Broker:
         _check(self.L.peaq_broker_results(self.h, int(sid), out.ctypes.data_as(C.POINTER(C.c_double))))
         return _result_dict(out, self.advanced)
 
-    def set_meter(self, window, hop=None, depth=64):
+    def set_meter(self, window, hop=None, depth=64, bands=False):
         """peaq_broker_set_meter: one geometry for all sessions of the broker (see Session.set_meter), before the first
-        open() and before start()"""
+        open() and before start().  bands: the band meter as well (peaq_broker_set_meter_bands)."""
         self._meter_depth = int(depth) if window else 0
         if not window:
             _check(self.L.peaq_broker_set_meter(self.h, None))
             return
         cfg = MeterConfig(int(window), int(window if hop is None else hop), int(depth))
         _check(self.L.peaq_broker_set_meter(self.h, C.byref(cfg)))
+        if bands:
+            self.set_meter_bands(True)
 
-    def meter_read(self, sid, cap=None):
+    def set_meter_bands(self, on=True):
+        """peaq_broker_set_meter_bands: the band rows of every slot's readings on or off; after set_meter"""
+        _check(self.L.peaq_broker_set_meter_bands(self.h, int(bool(on))))
+
+    def meter_read(self, sid, cap=None, bands=False):
         """(readings, dropped) of session sid, as Session.meter_read: what was delivered up to the last tick; no tick
-        is forced (peaq_broker_meter_read)"""
+        is forced (peaq_broker_meter_read, with bands peaq_broker_meter_read_bands)"""
         cap = max(1, getattr(self, "_meter_depth", 0)) if cap is None else int(cap)
-        rows = (MeterReading * cap)()
-        n, dropped = C.c_int(0), C.c_uint64(0)
-        _check(self.L.peaq_broker_meter_read(self.h, int(sid), rows, cap, C.byref(n), C.byref(dropped)))
-        return [_meter_dict(rows[i], self.advanced) for i in range(n.value)], dropped.value
+        return _meter_read(self.L, lambda *a: self.L.peaq_broker_meter_read(self.h, int(sid), *a),
+                           lambda *a: self.L.peaq_broker_meter_read_bands(self.h, int(sid), *a), self.advanced,
+                           self.channels, cap, bands)
 
     def set_align(self, max_lag, probe=None, watch=None):
         """peaq_broker_set_align: one configuration for all sessions of the broker (see Session.set_align), before the

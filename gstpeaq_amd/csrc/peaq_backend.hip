@@ -646,6 +646,17 @@ __global__ __launch_bounds__(128, 3) void backend_live_kernel(BackendArgs a, Tra
   constexpr PatternBandArgs pbd{};
 #include "peaq_backend_fft.inc"
 }
+// the live-band instantiation (the launches of a metered session with the band meter on): the live instantiation, and
+// the planes of `bnd` at the same launch-relative index beside the trace record -- the feed of peaq_meter_bands.hip.
+// (A name of its own that contains neither the live nor the bands kernels' names.)
+template <int NB, bool ADV>
+__global__ __launch_bounds__(128, 3) void backend_liveband_kernel(BackendArgs a, TraceArgs trc, BandArgs bnd) {
+  constexpr bool DBG = false, PTS = false, TRC = true, LIVE = true, BND = true, PBD = false, SUM = false, WARM = false;
+  constexpr SummaryArgs sum{};
+  constexpr PointArgs pts{};
+  constexpr PatternBandArgs pbd{};
+#include "peaq_backend_fft.inc"
+}
 // the bands instantiation: a fourth kernel of its own name with the same body
 template <int NB, bool ADV>
 __global__ __launch_bounds__(128, 3) void backend_bands_kernel(BackendArgs a, BandArgs bnd) {
@@ -690,6 +701,7 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 //
 //   out.spn              x    x    x  needs   x      x           x             x     as spn.blocks
 //   out.live             x    x    x    x    x      x           .             .            .
+//   out.live_bnd       needs out.live, and is held to what out.live is held to
 //
 // The rows-per-band outputs (bnd, pbd, sum) belong to a run's own launches: each stands alone.  The trace and the
 // points are not held against each other, the debug dump or a broker's windows: the trace wins over the points, either
@@ -698,7 +710,9 @@ __global__ __launch_bounds__(128, 3) void backend_summary_kernel(BackendArgs a, 
 // run's own launch leaves -- the basic or the 55-band one, as a.advanced says --, so it needs out.trc and nothing else of
 // the run's own outputs.  out.live (a metered session's launches: the feed of peaq_meter.hip, launch-relative) stands
 // alone among the outputs -- out.spn included -- and is the one that goes with a launch's own frame windows and slots; it
-// needs live.frames.
+// needs live.frames.  out.live_bnd (the band meter) selects the live-band instantiations: the same launch with the planes
+// of live_bnd beside the records; without out.live, without live_bnd.frame_stride or with planes that the version does
+// not have it is refused.
 hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t stream, const RunOutputs& out) {
   if (n_pairs == 0) return hipSuccess;
   const dim3 block(64 * a.channels);
@@ -711,9 +725,16 @@ hipError_t launch_backend(const BackendArgs& a, unsigned n_pairs, hipStream_t st
   if (out.has_spn() && (!trc || alone || pts || a.debug || a.pair_frame0 || a.pair_slot ||
                         (a.advanced != 0) != (out.spn.blocks != nullptr)))   // (block records: the advanced version's)
     return hipErrorInvalidValue;
+  if (out.has_live_bnd() && (!out.has_live() || !out.live_bnd.frame_stride || !out.live_bnd.planes ||
+                             (out.live_bnd.planes & ~(a.advanced ? kBandAdvanced : kBandAll))))
+    return hipErrorInvalidValue;
   if (out.has_live()) {
     if (alone || pts || trc || out.has_spn() || a.debug || !out.live.frames) return hipErrorInvalidValue;
-    if (!a.advanced)
+    if (out.has_live_bnd() && !a.advanced)
+      hipLaunchKernelGGL((backend_liveband_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.live, out.live_bnd);
+    else if (out.has_live_bnd())
+      hipLaunchKernelGGL((backend_liveband_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.live, out.live_bnd);
+    else if (!a.advanced)
       hipLaunchKernelGGL((backend_live_kernel<109, false>), dim3(n_pairs), block, 0, stream, a, out.live);
     else
       hipLaunchKernelGGL((backend_live_kernel<55, true>), dim3(n_pairs), block, 0, stream, a, out.live);

@@ -2,7 +2,8 @@
 // PBD = SUM = false), backend_points_kernel<NB, ADV> (PTS = true), backend_trace_kernel<NB, ADV> (TRC = true),
 // backend_bands_kernel<NB, ADV> (BND = true), backend_pattern_bands_kernel<NB, false> (PBD = true) and
 // backend_summary_kernel<NB, ADV> (SUM = true) in peaq_backend.hip, and by backend_live_kernel<NB, ADV> (TRC = LIVE =
-// true; LIVE is false in all the others): one text, seven kernels of their own names.
+// true) and backend_liveband_kernel<NB, ADV> (TRC = LIVE = BND = true; LIVE is false in all the others): one text, eight
+// kernels of their own names.
   __shared__ BackendShared sh;
   __shared__ double sh_tab[T_COUNT * kBandStride];
   __shared__ __attribute__((aligned(16))) double sh_ltab[2 * kLogTabEntries + 2];
@@ -230,14 +231,16 @@
       const double ac = bt.ear_tc(b);
       // (summary instantiation, basic version: the two filters spelt out as the compiler contracts them in the plain
       // instantiation -- the reference's rounds (1 - a) u and fuses a s, the test's rounds a s and fuses (1 - a) u.  Left
-      // to itself it fuses a s in both here, and the results would not be peaq_batch_run's to the bit.)
-      if (SUM && !ADV)
+      // to itself it fuses a s in both here, and the results would not be peaq_batch_run's to the bit.  The live-band
+      // instantiation spells them out as well: a session's scores must not depend on its band meter.)
+      constexpr bool SPELT = SUM || (BND && LIVE);
+      if (SPELT && !ADV)
         sm[0][s] = __builtin_fma(ac, sm[0][s], (1. - ac) * ur[s]);
       else
         sm[0][s] = ac * sm[0][s] + (1. - ac) * ur[s];
       er[s] = sm[0][s] > ur[s] ? sm[0][s] : ur[s];
       if (!ADV) {
-        if (SUM)
+        if (SPELT)
           sm[1][s] = __builtin_fma(1. - ac, ut[s], ac * sm[1][s]);
         else
           sm[1][s] = ac * sm[1][s] + (1. - ac) * ut[s];
@@ -247,8 +250,10 @@
       }
     }
 
-    // (bands instantiation only) the row cell of this (pair, frame, channel); the smeared excitations go out here
-    const size_t bnd_cell = BND ? ((size_t)pair * bnd.frame_stride + frame) * channels + chan : 0;
+    // (bands instantiations only) the row cell of this (pair, frame, channel) -- LIVE: of the frame's index within the
+    // launch, as the trace record's --; the smeared excitations go out here
+    const size_t bnd_cell =
+        BND ? ((size_t)pair * bnd.frame_stride + (LIVE ? frame - f_begin : frame)) * channels + chan : 0;
     if (BND) {
       band_store<NB>(bnd, kBandExcRef, bnd_cell, lane, er[0], bl.valid(1) ? er[1] : 0.);
       if (!ADV) band_store<NB>(bnd, kBandExcTest, bnd_cell, lane, et[0], bl.valid(1) ? et[1] : 0.);

@@ -528,6 +528,8 @@ static int broker_launch_fft(peaq_broker* b, const TickPlan& pl) {
   mf.s_slot = mt.dev(BrokerMeta::kSlot);
   mf.s_total_frames = mf.s_total_units = mt.dev(BrokerMeta::kTotalFrames);
   HIP_TRY(launch_meter_fft(mf, b->advanced != 0, b->records.as<double>(), b->channels, pl.active, b->stream));
+  if (b->meter.bands)                                // the band rows of the same windows, by the same per-stream rows
+    HIP_TRY(launch_meter_bands(mf, b->m_buf.band_args(), b->advanced != 0, b->channels, pl.active, b->stream));
   return PEAQ_OK;
 }
 
@@ -835,6 +837,8 @@ extern "C" int peaq_broker_open(peaq_broker* b, int* session_id) {
     if (b->meter.on) {                                 // a fresh meter: every snapshot as launch_points_init leaves it
       HIP_TRY(launch_points_init(b->m_buf.open.as<PointSnap>() + (size_t)sid * b->meter.k_open, b->meter.k_open, b->stream));
       HIP_TRY(launch_points_init(b->m_buf.ring.as<PointSnap>() + (size_t)sid * b->meter.ring, b->meter.ring, b->stream));
+      if (b->meter.bands)
+        if (int rc = b->m_buf.restart_bands((size_t)sid, 1, b->stream)) return rc;
     }
     if (b->align.window)                               // a fresh watch: index 0, nothing complete
       HIP_TRY(hipMemsetAsync(b->a_buf.state.as<WatchState>() + sid, 0, sizeof(WatchState), b->stream));
@@ -1023,6 +1027,7 @@ extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cf
   std::lock_guard<std::mutex> tick(b->tick_mu);
   if (int rc = broker_not_begun(b, "peaq_broker_set_meter", "the meter")) return rc;
   b->meter.on = false;
+  b->meter.bands = false;                              // (the band meter goes with the geometry: meter first, then bands)
   if (off) return PEAQ_OK;
   MeterGeometry g;
   g.set(*cfg);
@@ -1031,6 +1036,29 @@ extern "C" int peaq_broker_set_meter(peaq_broker* b, const peaq_meter_config* cf
   if (int rc = b->m_buf.reserve(g, (size_t)b->max_sessions, kBrokerMaxFrames, kBrokerMaxBlocks, b->advanced != 0)) return rc;
   b->meter = g;
   b->meter.on = true;
+  return PEAQ_OK;
+}
+
+// The band rows of every slot's readings, where peaq_broker_set_meter is accepted and after it (which switches them off).
+extern "C" int peaq_broker_set_meter_bands(peaq_broker* b, int on) {
+  const std::string who("peaq_broker_set_meter_bands");
+  if (!b) return fail(PEAQ_ERR_ARG, who + ": broker is NULL");
+  if (broker_is_multi(b)) {                            // every shard
+    for (peaq_broker* sh : b->shards)
+      if (int rc = peaq_broker_set_meter_bands(sh, on)) return rc;
+    return PEAQ_OK;
+  }
+  std::lock_guard<std::mutex> tick(b->tick_mu);
+  if (int rc = broker_not_begun(b, who, "the band meter")) return rc;
+  if (!b->meter.on) return fail(PEAQ_ERR_ARG, who + ": the meter is off; set it first (peaq_broker_set_meter)");
+  b->meter.bands = false;                              // (stays off if the workspace cannot be reserved)
+  if (!on) return PEAQ_OK;
+  if (int rc = check_meter_bands_config(who, peaq_meter_config{b->meter.window, b->meter.hop, b->meter.depth})) return rc;
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));            // (the buffers may be replaced)
+  if (int rc = b->m_buf.reserve_bands(b->meter, (size_t)b->max_sessions, kBrokerMaxFrames, b->advanced != 0, b->channels))
+    return rc;
+  b->meter.bands = true;                               // (a slot's rows start fresh at its open)
   return PEAQ_OK;
 }
 
@@ -1189,27 +1217,44 @@ extern "C" int peaq_broker_watch_read(peaq_broker* b, int session_id, peaq_delay
 }
 
 // What was delivered up to the last tick that has been enqueued (the call waits for it); it does not tick.
-extern "C" int peaq_broker_meter_read(peaq_broker* b, int session_id, peaq_meter_reading* out, int cap, int* n_read,
-                                      uint64_t* dropped) {
-  if (!b || !n_read) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: NULL argument");
+// peaq_broker_meter_read and (with_rows) peaq_broker_meter_read_bands: one cursor per slot
+static int broker_meter_read(peaq_broker* b, const char* who_c, int session_id, peaq_meter_reading* out, bool with_rows,
+                             double* rows, int cap, int* n_read, uint64_t* dropped) {
+  const std::string who(who_c);
+  if (!b || !n_read) return fail(PEAQ_ERR_ARG, who + ": NULL argument");
   *n_read = 0;
   if (dropped) *dropped = 0;
   if (cap < 0 || (cap > 0 && !out))
-    return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
-  if (const auto fwd = broker_forward(b, session_id, "peaq_broker_meter_read", [&](peaq_broker* sh, int id) {
-        return peaq_broker_meter_read(sh, id, out, cap, n_read, dropped);
+    return fail(PEAQ_ERR_ARG, who + ": cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
+  if (with_rows && cap > 0 && !rows) return fail(PEAQ_ERR_ARG, who + ": cap " + std::to_string(cap) + " with rows NULL");
+  if (const auto fwd = broker_forward(b, session_id, who_c, [&](peaq_broker* sh, int id) {
+        return broker_meter_read(sh, who_c, id, out, with_rows, rows, cap, n_read, dropped);
       }))
     return *fwd;
   BrokerSlot* sl = broker_slot(b, session_id);
-  if (!sl) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: bad session id " + std::to_string(session_id));
+  if (!sl) return fail(PEAQ_ERR_ARG, who + ": bad session id " + std::to_string(session_id));
   std::lock_guard<std::mutex> tick(b->tick_mu);
-  if (!b->meter.on) return fail(PEAQ_ERR_ARG, "peaq_broker_meter_read: the meter is off (peaq_broker_set_meter)");
-  if (b->failed.load()) return broker_failed(b, "peaq_broker_meter_read");
+  if (!b->meter.on) return fail(PEAQ_ERR_ARG, who + ": the meter is off (peaq_broker_set_meter)");
+  if (with_rows && !b->meter.bands) return fail(PEAQ_ERR_ARG, who + ": the band meter is off (peaq_broker_set_meter_bands)");
+  if (b->failed.load()) return broker_failed(b, who_c);
   std::lock_guard<std::mutex> lock(sl->mu);
-  if (!sl->open) return fail(PEAQ_ERR_STATE, "peaq_broker_meter_read: session is not open");
+  if (!sl->open) return fail(PEAQ_ERR_STATE, who + ": session is not open");
   HIP_TRY(hipSetDevice(b->ctx->device));
+  const size_t set = with_rows ? MeterBandSizes(b->meter.k_open, b->meter.ring, 0, b->advanced != 0, b->channels).set : 0;
   return sl->meter.read(sl->framer, b->meter, b->m_buf.ring.as<PointSnap>() + (size_t)session_id * b->meter.ring,
-                        b->m_buf.readout, b->m_buf.host, b->channels, b->stream, b->cfg, out, cap, n_read, dropped);
+                        b->m_buf.readout, b->m_buf.host, b->channels, b->stream, b->cfg, out, cap, n_read, dropped,
+                        b->m_buf.band_ring.as<double>() + (size_t)session_id * b->m_buf.band_ring_doubles,
+                        with_rows ? rows : nullptr, set);
+}
+
+extern "C" int peaq_broker_meter_read(peaq_broker* b, int session_id, peaq_meter_reading* out, int cap, int* n_read,
+                                      uint64_t* dropped) {
+  return broker_meter_read(b, "peaq_broker_meter_read", session_id, out, false, nullptr, cap, n_read, dropped);
+}
+
+extern "C" int peaq_broker_meter_read_bands(peaq_broker* b, int session_id, peaq_meter_reading* out, double* rows, int cap,
+                                            int* n_read, uint64_t* dropped) {
+  return broker_meter_read(b, "peaq_broker_meter_read_bands", session_id, out, true, rows, cap, n_read, dropped);
 }
 
 extern "C" int peaq_broker_start(peaq_broker* b, unsigned period_us) {

@@ -819,6 +819,32 @@ inline int check_meter_config(const std::string& who, const peaq_meter_config& c
                                   std::to_string(peaq::kMeterMaxDepth));
   return PEAQ_OK;
 }
+// The band meter (include/peaq_amd.h, "meter: band rows") on a geometry that check_meter_config has passed: every open
+// window keeps its rows twice, hence the narrower limits.
+inline int check_meter_bands_config(const std::string& who, const peaq_meter_config& c) {
+  const uint64_t k_open = ((uint64_t)c.window_frames + c.hop_frames - 1) / c.hop_frames;
+  if (k_open > peaq::kMeterBandsMaxOpen)
+    return fail(PEAQ_ERR_ARG, who + ": window_frames " + std::to_string(c.window_frames) + " over hop_frames " +
+                                  std::to_string(c.hop_frames) + " keeps " + std::to_string(k_open) +
+                                  " windows open at once, more than the band meter's " +
+                                  std::to_string(peaq::kMeterBandsMaxOpen));
+  if (c.depth > peaq::kMeterBandsMaxDepth)
+    return fail(PEAQ_ERR_ARG, who + ": depth " + std::to_string(c.depth) + " is outside the band meter's 1 .. " +
+                                  std::to_string(peaq::kMeterBandsMaxDepth));
+  return PEAQ_OK;
+}
+// doubles of the band meter's three device arrays per stream: the launch's planes, the open windows, the delivered ring
+struct MeterBandSizes {
+  size_t planes, open, ring, set;   // set: one reading's rows [channel][4][row]
+  MeterBandSizes(uint32_t k_open, uint32_t ring_slots, unsigned max_frames, bool advanced, int channels) {
+    const size_t row = (size_t)peaq::band_row(advanced ? 55 : 109);
+    set = (size_t)channels * peaq::kMeterBandRows * row;
+    planes = (size_t)max_frames * channels * 2 * row;
+    open = (size_t)k_open * channels * (size_t)peaq::meter_band_snap(advanced ? 55 : 109);
+    ring = (size_t)ring_slots * set;
+  }
+  size_t bytes() const { return (planes + open + ring) * sizeof(double); }
+};
 // windows that are complete once `units` frames have run: b_k = k H + W <= units
 inline uint64_t meter_complete(uint64_t units, uint32_t W, uint32_t H) { return units >= W ? (units - W) / H + 1 : 0; }
 // readings of a finished stream of T frames: the complete windows and, if the end cuts one short, the oldest such
@@ -972,6 +998,7 @@ inline void delay_watch_record(const peaq::WatchState& st, peaq_delay_watch* out
 // One geometry, and what the host keeps per metered stream (a session, a broker slot): guarded by the owner's lock.
 struct MeterGeometry {
   bool on = false;
+  bool bands = false;               // the band meter (set_meter_bands): only with `on`, off again with every set_meter
   uint32_t window = 0, hop = 0, depth = 0, k_open = 0;
   uint32_t ring = 0;                // depth + 2 slots: at a read the filter-bank path may have finished one window more
                                     // than the FFT path, and during a flush the FFT path two more than the other
@@ -992,6 +1019,31 @@ struct MeterBuffers {
   DevBuf readout;                   // ResultRecord [ring]
   std::vector<peaq::ResultRecord> host;
   size_t frame_stride = 0, block_stride = 0;
+  // the band meter (reserve_bands): one launch's planes [launch index][max_frames][channel][2][row] -- the live-band back
+  // ends' output, meter_bands_kernel's feed --, the open windows' rows and the delivered rows (peaq::MeterBandArgs)
+  DevBuf band_planes, band_open, band_ring;
+  size_t band_open_doubles = 0, band_ring_doubles = 0;   // per stream
+  int reserve_bands(const MeterGeometry& g, size_t streams, unsigned max_frames, bool advanced, int channels) {
+    const MeterBandSizes z(g.k_open, g.ring, max_frames, advanced, channels);
+    HIP_TRY(band_planes.reserve(streams * z.planes * sizeof(double)));
+    HIP_TRY(band_open.reserve(streams * z.open * sizeof(double)));
+    HIP_TRY(band_ring.reserve(streams * z.ring * sizeof(double)));
+    band_open_doubles = z.open;
+    band_ring_doubles = z.ring;
+    return PEAQ_OK;
+  }
+  // fresh rows for streams [first, first + count): no counted frame, status initial (kInit is 0), zeros delivered
+  int restart_bands(size_t first, size_t count, hipStream_t stream) {
+    static_assert(peaq::kInit == 0, "a fresh band snapshot is all zero bytes");
+    HIP_TRY(hipMemsetAsync(band_open.as<double>() + first * band_open_doubles, 0,
+                           count * band_open_doubles * sizeof(double), stream));
+    HIP_TRY(hipMemsetAsync(band_ring.as<double>() + first * band_ring_doubles, 0,
+                           count * band_ring_doubles * sizeof(double), stream));
+    return PEAQ_OK;
+  }
+  peaq::MeterBandArgs band_args() const {
+    return peaq::MeterBandArgs{band_planes.as<double>(), band_open.as<double>(), band_ring.as<double>()};
+  }
   int reserve(const MeterGeometry& g, size_t streams, unsigned max_frames, unsigned max_blocks, bool advanced) {
     HIP_TRY(open.reserve(streams * g.k_open * sizeof(peaq::PointSnap)));
     HIP_TRY(ring.reserve(streams * g.ring * sizeof(peaq::PointSnap)));
@@ -1031,6 +1083,11 @@ struct MeterBuffers {
       out.live.blocks = block_trc.as<peaq::BlockTrace>();
       out.live.block_stride = block_stride;
       out.live.n_uniform = UINT_MAX;
+      if (g.bands) {
+        out.live_bnd.bands = band_planes.as<double>();
+        out.live_bnd.frame_stride = frame_stride;
+        out.live_bnd.planes = peaq::kBandNmr | peaq::kBandExcRef;
+      }
     }
     return out;
   }
@@ -1061,10 +1118,12 @@ struct MeterStream {
     return ended ? std::min(d, meter_complete(total[kUnitFrame] ? total[kUnitFrame] - 1 : 0, g.window, g.hop)) : d;
   }
   // The delivered, not yet read readings of the stream whose ring is `snaps`, oldest first, at most cap: the read-out
-  // of their slots alone (at most two runs of the ring), then the rows' own fields.  Waits for `stream`.
+  // of their slots alone (at most two runs of the ring), then the rows' own fields.  Waits for `stream`.  With
+  // band_rows, the band meter's rows of the same readings from the stream's ring of them, `band_ring`.
   int read(const StreamFramer& fr, const MeterGeometry& g, const peaq::PointSnap* snaps, DevBuf& readout,
            std::vector<peaq::ResultRecord>& host, int channels, hipStream_t stream, const peaq::Settings& cfg,
-           peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped) {
+           peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped, const double* band_ring = nullptr,
+           double* band_rows = nullptr, size_t band_set = 0) {
     const uint64_t have = delivered(fr, g);
     uint64_t from = n_taken;
     if (have > g.depth && from < have - g.depth) from = have - g.depth;
@@ -1079,6 +1138,10 @@ struct MeterStream {
                                            readout.as<peaq::ResultRecord>() + s0, stream, cfg));
       HIP_TRY(hipMemcpyAsync(host.data() + s0, readout.as<peaq::ResultRecord>() + s0, run * sizeof(peaq::ResultRecord),
                              hipMemcpyDeviceToHost, stream));
+      // (band_rows: the rows of the same slots, `band_set` doubles a reading, straight into the caller's array)
+      if (band_rows)
+        HIP_TRY(hipMemcpyAsync(band_rows + done * band_set, band_ring + s0 * band_set, run * band_set * sizeof(double),
+                               hipMemcpyDeviceToHost, stream));
       done += run;
     }
     HIP_TRY(hipStreamSynchronize(stream));

@@ -364,6 +364,26 @@ hipError_t launch_meter_fft(const MeterArgs& m, bool advanced, const double* rec
 // and AvgLinDist of the windows that are open in them
 hipError_t launch_meter_fb(const MeterArgs& m, int channels, unsigned n_streams, hipStream_t stream);
 
+// ---- band rows of the meter's readings (peaq_session_set_meter_bands, peaq_session_meter_read_bands) -----------------
+// Rows 0 .. 3 of the band summary (kSumNmrSum .. kSumExcRef) of every window of the meter, reduced over the window's
+// COUNTED frames: the first .. the last of its frames above the data boundary, what accumulators that start fresh at
+// the window's first frame count.  The feed is what the live-band instantiations of the FFT back end leave
+// (RunOutputs::live_bnd): the planes NMR and EXC_REF of frame u of a launch at [stream][u - first unit], and the frame's
+// flags in its trace record (MeterArgs::frames).  A kernel argument of meter_bands_kernel only (peaq_meter_bands.hip),
+// beside the launch's MeterArgs, whose windows, units and per-stream rows it walks.
+constexpr int kMeterBandRows = 4;
+constexpr uint32_t kMeterBandsMaxOpen = 16, kMeterBandsMaxDepth = 256;
+// doubles of one (open window, channel): the running rows, the saved rows, then the status word and its padding
+constexpr int meter_band_snap(int bands) { return 2 * kMeterBandRows * band_row(bands) + 2; }
+struct MeterBandArgs {
+  const double* planes;         // [stream][MeterArgs::frame_stride][channel][2][band_row]: NMR, EXC_REF, launch-relative
+  double* open;                 // [stream][k_open][channel][meter_band_snap]: the open windows between launches
+  double* ring;                 // [stream][ring_depth][channel][kMeterBandRows][band_row]: the delivered windows' rows
+};
+// after launch_meter_fft of the same units, on the same stream, with the same MeterArgs
+hipError_t launch_meter_bands(const MeterArgs& m, const MeterBandArgs& mb, bool advanced, int channels, unsigned n_streams,
+                              hipStream_t stream);
+
 // ---- delay watch of a live stream (peaq_session_set_align, peaq_session_watch_read; peaq_watch.hip) ----------------
 // Watch window k of a stream covers the whole FFT frames [k W, (k + 1) W).  A frame's row: c[d + 31] for d = -31 .. 31,
 // the sum of r[n] t[n + d] over the frame's own n = 512 .. 1535 (r, t: the mono sums in double), then e_ref and e_test,
@@ -420,7 +440,10 @@ struct RunOutputs {
                                 // version, block) scratch: the replays' feed
   TraceArgs live{};             // a metered session's launches: the trace records, but record u of the launch at [launch
                                 // index][u - first unit of the launch] -- the feed of peaq_meter.hip.  Stands alone.
+  BandArgs live_bnd{};          // with `live` only (the band meter): the planes of a frame at the same launch-relative
+                                // index, frame_stride the most frames of a launch -- the feed of peaq_meter_bands.hip
   bool has_live() const { return live.frames != nullptr || live.blocks != nullptr; }
+  bool has_live_bnd() const { return live_bnd.bands != nullptr; }
   bool has_pts() const { return d_points != nullptr; }
   bool has_trc() const { return trc.frames != nullptr; }
   bool has_bnd() const { return bnd.bands != nullptr; }
@@ -431,7 +454,7 @@ struct RunOutputs {
   bool has_spn() const { return spn.out != nullptr; }
   bool any() const {
     return has_pts() || has_trc() || has_bnd() || has_fbnd() || has_pbd() || has_sum() || has_fsum() || has_spn() ||
-           has_live();
+           has_live() || has_live_bnd();
   }
 };
 // The instantiation of the FFT back end: summary, pattern bands, bands, trace, points, a.debug, plain -- the first

@@ -53,9 +53,10 @@ static int session_meter_step(peaq_session* s, StreamUnit kind, uint32_t first, 
   m.rec_stride = count;
   m.total_frames = mt.ended ? mt.total[kUnitFrame] : UINT_MAX;
   m.total_units = mt.ended ? mt.total[kind] : UINT_MAX;
-  if (kind == kUnitFrame)
+  if (kind == kUnitFrame) {
     HIP_TRY(launch_meter_fft(m, s->advanced != 0, s->records.as<double>(), s->channels, 1, s->stream));
-  else
+    if (mt.bands) HIP_TRY(launch_meter_bands(m, mt.buf.band_args(), s->advanced != 0, s->channels, 1, s->stream));
+  } else
     HIP_TRY(launch_meter_fb(m, s->channels, 1, s->stream));
   if (s->meter.ended && first + count == s->meter.total[kind]) s->meter.closed[kind] = true;
   return PEAQ_OK;
@@ -66,6 +67,8 @@ static int session_meter_restart(peaq_session* s) {
   peaq_session::Meter& mt = s->meter;
   HIP_TRY(launch_points_init(mt.buf.open.as<PointSnap>(), mt.k_open, s->stream));
   HIP_TRY(launch_points_init(mt.buf.ring.as<PointSnap>(), mt.ring, s->stream));
+  if (mt.bands)
+    if (int rc = mt.buf.restart_bands(0, 1, s->stream)) return rc;
   static_cast<MeterStream&>(mt) = MeterStream();
   mt.closed[0] = mt.closed[1] = false;
   return PEAQ_OK;
@@ -421,6 +424,7 @@ extern "C" int peaq_session_set_meter(peaq_session* s, const peaq_meter_config* 
   std::lock_guard<std::mutex> lock(s->mu);
   if (int rc = session_not_begun(s, "peaq_session_set_meter", "the meter")) return rc;
   peaq_session::Meter& mt = s->meter;
+  mt.bands = false;                                  // (the band meter goes with the geometry: meter first, then bands)
   if (off) {
     mt.on = false;
     return PEAQ_OK;
@@ -437,18 +441,65 @@ extern "C" int peaq_session_set_meter(peaq_session* s, const peaq_meter_config* 
   return PEAQ_OK;
 }
 
-extern "C" int peaq_session_meter_read(peaq_session* s, peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped) {
-  if (!s || !n_read) return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: NULL argument");
+// peaq_session_meter_read and (with_rows) peaq_session_meter_read_bands: one cursor
+static int session_meter_read(peaq_session* s, const std::string& who, peaq_meter_reading* out, bool with_rows, double* rows,
+                              int cap, int* n_read, uint64_t* dropped) {
+  if (!s || !n_read) return fail(PEAQ_ERR_ARG, who + ": NULL argument");
   *n_read = 0;
   if (dropped) *dropped = 0;
   if (cap < 0 || (cap > 0 && !out))
-    return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
+    return fail(PEAQ_ERR_ARG, who + ": cap " + std::to_string(cap) + " with out " + (out ? "set" : "NULL"));
+  if (with_rows && cap > 0 && !rows) return fail(PEAQ_ERR_ARG, who + ": cap " + std::to_string(cap) + " with rows NULL");
   std::lock_guard<std::mutex> lock(s->mu);
   peaq_session::Meter& mt = s->meter;
-  if (!mt.on) return fail(PEAQ_ERR_ARG, "peaq_session_meter_read: the meter is off (peaq_session_set_meter)");
+  if (!mt.on) return fail(PEAQ_ERR_ARG, who + ": the meter is off (peaq_session_set_meter)");
+  if (with_rows && !mt.bands) return fail(PEAQ_ERR_ARG, who + ": the band meter is off (peaq_session_set_meter_bands)");
   HIP_TRY(hipSetDevice(s->ctx->device));
+  const size_t set = with_rows ? MeterBandSizes(mt.k_open, mt.ring, 0, s->advanced != 0, s->channels).set : 0;
   return mt.read(s->framer, mt, mt.buf.ring.as<PointSnap>(), mt.buf.readout, mt.buf.host, s->channels, s->stream, s->cfg,
-                 out, cap, n_read, dropped);
+                 out, cap, n_read, dropped, mt.buf.band_ring.as<double>(), with_rows ? rows : nullptr, set);
+}
+
+extern "C" int peaq_session_meter_read(peaq_session* s, peaq_meter_reading* out, int cap, int* n_read, uint64_t* dropped) {
+  return session_meter_read(s, "peaq_session_meter_read", out, false, nullptr, cap, n_read, dropped);
+}
+
+extern "C" int peaq_session_meter_read_bands(peaq_session* s, peaq_meter_reading* out, double* rows, int cap, int* n_read,
+                                             uint64_t* dropped) {
+  return session_meter_read(s, "peaq_session_meter_read_bands", out, true, rows, cap, n_read, dropped);
+}
+
+extern "C" int peaq_meter_band_rows(void) { return kMeterBandRows; }
+
+extern "C" int peaq_meter_bands_workspace(const peaq_meter_config* cfg, int advanced, int channels, size_t* bytes) {
+  const std::string who("peaq_meter_bands_workspace");
+  if (!cfg || !bytes) return fail(PEAQ_ERR_ARG, who + ": NULL argument");
+  *bytes = 0;
+  if (int rc = check_meter_config(who, *cfg)) return rc;
+  if (int rc = check_meter_bands_config(who, *cfg)) return rc;
+  if (int rc = check_channels(who, channels)) return rc;
+  MeterGeometry g;
+  g.set(*cfg);
+  *bytes = MeterBandSizes(g.k_open, g.ring, kSessionMaxFrames, advanced != 0, channels).bytes();
+  return PEAQ_OK;
+}
+
+extern "C" int peaq_session_set_meter_bands(peaq_session* s, int on) {
+  const std::string who("peaq_session_set_meter_bands");
+  if (!s) return fail(PEAQ_ERR_ARG, who + ": session is NULL");
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (int rc = session_not_begun(s, who, "the band meter")) return rc;
+  peaq_session::Meter& mt = s->meter;
+  if (!mt.on) return fail(PEAQ_ERR_ARG, who + ": the meter is off; set it first (peaq_session_set_meter)");
+  mt.bands = false;                                  // (stays off if the workspace cannot be reserved)
+  if (!on) return PEAQ_OK;
+  if (int rc = check_meter_bands_config(who, peaq_meter_config{mt.window, mt.hop, mt.depth})) return rc;
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));          // (the buffers may be replaced)
+  if (int rc = mt.buf.reserve_bands(mt, 1, kSessionMaxFrames, s->advanced != 0, s->channels)) return rc;
+  if (int rc = mt.buf.restart_bands(0, 1, s->stream)) return rc;
+  mt.bands = true;
+  return PEAQ_OK;
 }
 
 extern "C" size_t peaq_live_delay_size(void) { return sizeof(peaq_live_delay); }

@@ -256,6 +256,51 @@ int peaq_meter_readings (uint64_t n_ref, uint64_t n_test, const peaq_meter_confi
 int peaq_session_set_meter (peaq_session *s, const peaq_meter_config *cfg);
 int peaq_session_meter_read (peaq_session *s, peaq_meter_reading *out, int cap, int *n_read, uint64_t *dropped);
 
+/* ---- meter: band rows ---------------------------------------------------------------------------------------------------
+ * The meter says in which window the score was lost; the band rows say in which band.  With the band meter on, every
+ * reading carries rows 0 .. 3 of the band summary ("per-band summary" below), reduced on the device over the window's
+ * frames: per band the sum of the noise-to-mask ratio, its maximum, the count of frames in which it is above 1.5 dB,
+ * and the sum of the reference excitation -- a noise-to-mask spectrum per window, in the basic version (109 bands) and
+ * the advanced version (55 bands).
+ *
+ * Counted frames.  Window k covers frames [a_k, b_k) = [k H, k H + W), cut at T at the flush, as above.  Let A_k be
+ *   those of its frames that have PEAQ_TRACE_ABOVE -- the frame trace's flag: over all channels, the flush frame
+ *   included.  The counted frames of the window are min A_k .. max A_k inclusive, none if A_k is empty: frames below the
+ *   boundary in between count, a leading run before the first frame above it does not, a trailing run is dropped.
+ *   This is what accumulators that start fresh at a_k count, and the rule of peaq_batch_run_band_summary with "the
+ *   pair's frames" read as "the window's frames".
+ * Rows.  peaq_meter_band_rows () = 4 rows per channel, each of row = peaq_band_row (advanced) doubles, with the meaning
+ *   and order of PEAQ_BAND_SUMMARY_NMR_SUM, _NMR_MAX, _NMR_DISTURBED, _EXC_REF_SUM.  Sums are FP64 in frame order.
+ *   Entry nb = peaq_band_count (advanced) of every row is the number of counted frames; a window without a counted
+ *   frame reads 0 everywhere.  The values per frame are those of the running stream, in context, as the meter's scores
+ *   are: those peaq_batch_run_bands gives for the planes PEAQ_BAND_NMR and PEAQ_BAND_EXC_REF in the window's frames.
+ *
+ * peaq_session_set_meter_bands (s, on): accepted where peaq_session_set_meter is, and it needs a meter that is set;
+ * peaq_session_set_meter switches it off again, so the order is always meter, then bands.  Every open window keeps its
+ * rows twice (the running rows, and the rows as they were at the last frame above the boundary), so with bands on the
+ * geometry is limited to K = ceil (W / H) <= 16 and depth <= 256: outside that, PEAQ_ERR_ARG before a device is touched,
+ * the message naming entry and value; PEAQ_ERR_NOMEM where the workspace cannot be reserved.  Off is the default, and
+ * with bands off a metered session's and a broker's launches are exactly what they are without this section.
+ * peaq_session_meter_read_bands: peaq_session_meter_read, with the same single cursor, that also fills
+ *   rows[((i * channels + c) * 4 + k) * row + b]  for reading i, channel c, row k, entry b;
+ * `rows` holds cap * channels * 4 * row doubles (NULL only with cap 0).  peaq_session_meter_read goes on working with
+ * bands on and just does not copy rows.  With bands off: PEAQ_ERR_ARG.  peaq_session_reset restarts the rows with the
+ * meter.
+ * peaq_meter_bands_workspace: host arithmetic only; the device bytes the band meter adds to a session,
+ *   *bytes = 8 channels (K (8 row + 2) + 4 (D + 2) row + 2 * 64 row)
+ * -- per open window and channel the running and the saved rows and a status word, D + 2 delivered sets, and the two
+ * planes of one launch's 64 frames --; a broker slot holds a tick's 8 frames in place of the 64.  It refuses a NULL
+ * pointer, channels other than 1 or 2 and what peaq_session_set_meter_bands refuses for a geometry (PEAQ_ERR_ARG).
+ * The broker: peaq_broker_set_meter_bands for every slot of the broker, every shard of a peaq_broker_create_multi broker
+ * included -- accepted where peaq_broker_set_meter is, after it --, and peaq_broker_meter_read_bands; closing a slot
+ * and opening it again starts fresh rows.  A tick adds one more small kernel behind the FFT back end; no new rows of
+ * metadata, no copy, no wait. */
+int peaq_meter_band_rows (void);
+int peaq_meter_bands_workspace (const peaq_meter_config *cfg, int advanced, int channels, size_t *bytes);
+int peaq_session_set_meter_bands (peaq_session *s, int on);
+int peaq_session_meter_read_bands (peaq_session *s, peaq_meter_reading *out, double *rows, int cap, int *n_read,
+                                   uint64_t *dropped);
+
 /* ---- live alignment: find the chain's delay, align the pads, watch it move ---------------------------------------------
  * A monitored chain -- a codec, a link, a processor between the reference pad and the test pad -- has a delay, and PEAQ
  * takes the two signals as sample-aligned ("time alignment on the device" below, the batch side's cure).  Two things for a
@@ -405,6 +450,9 @@ int  peaq_broker_stats   (peaq_broker *b, peaq_broker_stats_t *out);
 int  peaq_broker_set_meter (peaq_broker *b, const peaq_meter_config *cfg);     /* see "meter" above */
 int  peaq_broker_meter_read (peaq_broker *b, int session_id, peaq_meter_reading *out, int cap, int *n_read,
                              uint64_t *dropped);
+int  peaq_broker_set_meter_bands (peaq_broker *b, int on);                       /* see "meter: band rows" above */
+int  peaq_broker_meter_read_bands (peaq_broker *b, int session_id, peaq_meter_reading *out, double *rows, int cap,
+                                   int *n_read, uint64_t *dropped);
 int  peaq_broker_set_align (peaq_broker *b, const peaq_live_align_config *cfg);   /* see "live alignment" above */
 int  peaq_broker_align_read (peaq_broker *b, int session_id, peaq_live_delay *out);
 int  peaq_broker_watch_read (peaq_broker *b, int session_id, peaq_delay_watch *out);
